@@ -5,8 +5,8 @@ A step = one pass of the whole device path (pileup/classify per window -> run-le
 three launches) over the rank's resident input.  Inputs are resident in HBM when the timed region starts.
 
   --gpus 1 (default)   BASELINE.json configs[1], the configuration the metric is quoted on: ONE
-                       chr21-shaped contig (46 709 983 bp, 30x, 2x150 bp paired reads).  The whole contig
-                       is also run through the CPU oracle (single thread, like the reference) and the BED /
+                       chr21-shaped contig (46 709 983 bp, 30x, 2x150 bp paired reads).  With --full the whole
+                       contig is also run through the CPU oracle (single thread, like the reference) and the BED /
                        summary compared bit for bit; configs[2] (long reads) and configs[4] (site pileup) are
                        measured as secondary lines under "configs".
   --gpus N > 1         BASELINE.json configs[3]: the FIXED whole-genome input -- the 25 hg38 primary contigs
@@ -17,9 +17,14 @@ three launches) over the rank's resident input.  Inputs are resident in HBM when
                        summary records taken straight from HBM (cl_device_summary).
   --workload chr21|wgs overrides the choice (e.g. the whole genome on one GPU; chr21 per rank = weak scaling).
 
-K steps are timed exactly as the contract says (barrier + synchronize on both sides, max over ranks).  One
-such block lasts ~10 ms at the default K, so the block is repeated until --min-time seconds of timed
-blocks have accumulated; ms_per_step is the mean over the blocks (every block's figures are kept).
+K steps are timed exactly as the contract says (barrier + synchronize on both sides, max over ranks), once:
+ms_per_step and value come from exactly --steps timed steps.
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step (--dump-outputs DIR) and
+prints its line.  --full adds everything else, all after the timed steps: more K-step blocks until --min-time
+seconds of them have accumulated (the spread under "timing"), per-kernel times and the roofline, the CPU oracle's
+baseline and bit-exactness check, the byte form, the BAM + FASTA file runs, the secondary configs, the PMC
+traffic passes and the whole genome on one GPU.
 
 Prints ONE JSON line on rank 0.
 """
@@ -27,6 +32,7 @@ import argparse
 import json
 import math
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -104,12 +110,44 @@ def cpu_baseline_all_cores(rec, ref, opt, tid, piece, threads):
 
 
 # ------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------
+MAX_DUMPED_INTERVALS = 1_500_000     # 36 MB of rows + 12 MB of row numbers: the dump stays under 64 MB
+
+
+def dump_outputs(dirpath, arrays):
+    """Every array as DIR/<name>.npy in float64 (the outputs are integers below 2^53: exact)."""
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def interval_outputs(intervals):
+    """The run-length intervals of a step, (n, 3): start, end (exclusive), state.  A longer list than
+    MAX_DUMPED_INTERVALS is sampled: a fixed seeded choice of rows, in list order, with their row numbers."""
+    n = intervals.shape[0]
+    if n <= MAX_DUMPED_INTERVALS:
+        return {"intervals": intervals}
+    rows = np.sort(np.random.default_rng(0).choice(n, size=MAX_DUMPED_INTERVALS, replace=False))
+    return {"intervals": intervals[rows], "interval_rows": rows}
+
+
+def summary_words(res):
+    """cl_contig_summary of a ContigResult as its 14 words: state_counts[6], n_covered_bases, summed_coverage,
+    summed_baseq, summed_mapq, quality_bases, extent, max_raw_depth, n_intervals."""
+    d = res.as_dict()
+    return np.array(d["state_counts"] + [d[k] for k in ("n_covered_bases", "summed_coverage", "summed_baseq", "summed_mapq",
+                                                         "quality_bases", "extent", "max_raw_depth", "n_intervals")], np.float64)
+
+
+# ------------------------------------------------------------------------------------------------
 # timing
 # ------------------------------------------------------------------------------------------------
 def timed_blocks(step, sync, args, world, dist, torch, coll_dev):
-    """W warm-up steps, then blocks of EXACTLY K steps, each bracketed by barrier + synchronize on both
-    sides; blocks repeat until --min-time seconds of them have accumulated (the count is agreed across
-    ranks).  Returns per-block durations (max over ranks), seconds."""
+    """W warm-up steps, then one block of EXACTLY K steps bracketed by barrier + synchronize on both sides
+    (the headline's).  With --full, more such blocks follow until --min-time seconds of them have accumulated
+    (the count is agreed across ranks).  Returns per-block durations (max over ranks), seconds: the headline's
+    block first."""
     for _ in range(args.warmup):
         step()
     sync()
@@ -127,10 +165,12 @@ def timed_blocks(step, sync, args, world, dist, torch, coll_dev):
             dist.barrier()
         return time.perf_counter() - t0
     first = block()
-    t = torch.tensor([first], dtype=torch.float64, device=coll_dev)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    n_more = int(min(args.max_blocks - 1, max(0, math.ceil(args.min_time / max(float(t.item()), 1e-6)) - 1)))
+    n_more = 0
+    if args.full:
+        t = torch.tensor([first], dtype=torch.float64, device=coll_dev)
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        n_more = int(min(args.max_blocks - 1, max(0, math.ceil(args.min_time / max(float(t.item()), 1e-6)) - 1)))
     dts = [first] + [block() for _ in range(n_more)]
     t = torch.tensor(dts, dtype=torch.float64, device=coll_dev)
     if world > 1:
@@ -637,7 +677,7 @@ def cached_wgs_1gpu(total_bases, args, write=None):
 def wgs_point(args, dev_id, torch, dist, coll_dev):
     """configs[3] on this ONE GPU: the fixed whole-genome input of the N > 1 runs, all 25 contigs resident -- the 1-GPU
     point of the strong-scaling curve."""
-    full = run_wgs(args, 0, 1, dev_id, torch, dist, coll_dev)
+    full = run_wgs(argparse.Namespace(**dict(vars(args), dump_outputs=None)), 0, 1, dev_id, torch, dist, coll_dev)
     keep = {k: full[k] for k in ("value", "unit", "ms_per_step", "scaling", "timing", "roofline", "callable_fraction",
                                  "hbm_resident_bytes_per_rank", "upload_h2d_bytes_per_rank")}
     cached_wgs_1gpu(full["config"]["total_bases"], args, write=full)
@@ -678,21 +718,25 @@ def run_chr21(args, rank, world, dev_id, torch, dist, coll_dev):
     first = eng.contig_collect()
     log(f"[bench r{rank}] end-to-end first pass (host admission + PCIe + kernels + BED): {e2e:.2f}s "
         f"= {L / e2e / 1e9:.3f} Gbase/s; intervals {first.summary.n_intervals}")
-    # the same call once more: what every contig but a process's first costs (device and staging buffers exist,
-    # code objects are loaded); its BED goes to a scratch file
-    counter2 = CallableProfiler(os.path.join(tmpd, f"g{rank}_again.bed"))
-    t0 = time.perf_counter()
-    process_single_contig(eng, counter2, ContigProfiler("chr21", L), opt, tid, rec, ref)
-    counter2.close()
-    e2e_next = time.perf_counter() - t0
-    log(f"[bench r{rank}] end-to-end, the same contig again on the warm engine: {e2e_next:.3f}s")
+    if args.full:
+        # the same call once more: what every contig but a process's first costs (device and staging buffers exist,
+        # code objects are loaded); its BED goes to a scratch file
+        counter2 = CallableProfiler(os.path.join(tmpd, f"g{rank}_again.bed"))
+        t0 = time.perf_counter()
+        process_single_contig(eng, counter2, ContigProfiler("chr21", L), opt, tid, rec, ref)
+        counter2.close()
+        e2e_next = time.perf_counter() - t0
+        log(f"[bench r{rank}] end-to-end, the same contig again on the warm engine: {e2e_next:.3f}s")
 
-    # ---- timed region: resident contig, blocks of K steps ----
+    # ---- timed region: resident contig, K steps ----
     dts = timed_blocks(eng.contig_run, eng.sync, args, world, dist, torch, coll_dev)
-    kms, _ = kernel_profile([eng], args.steps)
-    again = eng.contig_collect()
-    assert again.as_dict() == first.as_dict() and np.array_equal(again.intervals, first.intervals), \
-        "resident re-run changed the result"
+    last = eng.contig_collect()                     # what the last timed step computed
+    if args.full:
+        kms, _ = kernel_profile([eng], args.steps)
+        again = eng.contig_collect()
+        assert again.as_dict() == first.as_dict() and np.array_equal(again.intervals, first.intervals) \
+            and last.as_dict() == first.as_dict() and np.array_equal(last.intervals, first.intervals), \
+            "resident re-run changed the result"
 
     # RCCL gather of the per-contig summaries (the path's only exchange), straight from HBM
     from decodingustools_amd.coverage import device_summary_tensor
@@ -707,13 +751,14 @@ def run_chr21(args, rank, world, dev_id, torch, dist, coll_dev):
     total_bases = sum(int(s[11].item()) for s in allsum)           # word 11: extent
     if rank != 0:
         eng.close()
+        shutil.rmtree(tmpd, ignore_errors=True)
         return None
-    dt_mean = sum(dts) / len(dts)
-    ms_step = dt_mean * 1e3 / args.steps
-    alg, layb, rleb, lay = engine_figures(eng, rec, L)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(summary=summary_words(last), **interval_outputs(last.intervals)))
+    ms_step = dts[0] * 1e3 / args.steps
     out = {
         "metric": METRIC,
-        "value": total_bases / (dt_mean / args.steps), "unit": "bases/s", "n_gpus": world, "steps": args.steps,
+        "value": total_bases / (dts[0] / args.steps), "unit": "bases/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u8 (quality bytes thresholded to pass bits on the host, counted bit-sliced on the device)", "data": "synthetic",
         "config": {"workload": "coverage -L chr21 synthetic 30x 150bp paired, device-resident, one contig per GPU",
@@ -722,12 +767,15 @@ def run_chr21(args, rank, world, dev_id, torch, dist, coll_dev):
                    "options": "cli defaults (4,500,10,20,10,1,0.1)"},
         "timing": {"blocks": len(dts), "steps_per_block": args.steps, "timed_region_s": sum(dts),
                    "ms_per_step_min": min(dts) * 1e3 / args.steps, "ms_per_step_max": max(dts) * 1e3 / args.steps},
-        "roofline": roofline(alg, kms["pileup"], ms_step, kms, layout_bytes=layb, rle_bytes=rleb),
-        "layout": lay,
         "end_to_end_first_pass_s": e2e,
-        "end_to_end_next_pass_s": e2e_next,
     }
-    if world == 1 and args.cpu_sample != 0:
+    if args.full:
+        alg, layb, rleb, lay = engine_figures(eng, rec, L)
+        out["timing"]["ms_per_step_mean"] = sum(dts) * 1e3 / (len(dts) * args.steps)
+        out["roofline"] = roofline(alg, kms["pileup"], ms_step, kms, layout_bytes=layb, rle_bytes=rleb)
+        out["layout"] = lay
+        out["end_to_end_next_pass_s"] = e2e_next
+    if args.full and world == 1 and args.cpu_sample != 0:
         Ls = L if args.cpu_sample < 0 else min(args.cpu_sample, L)
         sub, ost, obed, cdt = cpu_baseline(rec, ref, Ls, opt, tid)
         if Ls == L:
@@ -756,7 +804,8 @@ def run_chr21(args, rank, world, dev_id, torch, dist, coll_dev):
         if not exact:
             log("[bench] WARNING: GPU BED/summary differs from the oracle")
     eng.close()
-    if world != 1:
+    if world != 1 or not args.full:
+        shutil.rmtree(tmpd, ignore_errors=True)
         return out
     # the byte form of rounds 1-3 on the same input (DUT_QUAL_FORM=bytes): its >= 50 %-of-HBM figure stays reproducible
     try:
@@ -856,7 +905,6 @@ def run_chr21(args, rank, world, dev_id, torch, dist, coll_dev):
         else:
             skipped.append("traffic")
     if cache_dir:
-        import shutil
         shutil.rmtree(cache_dir, ignore_errors=True)
     for v in out["configs"].values():
         if isinstance(v, dict):
@@ -876,6 +924,7 @@ def run_chr21(args, rank, world, dev_id, torch, dist, coll_dev):
     if skipped:
         out["skipped_for_time_budget"] = skipped
     out["bench_wall_s"] = round(time.perf_counter() - t_start, 1)
+    shutil.rmtree(tmpd, ignore_errors=True)
     return out
 
 
@@ -899,7 +948,9 @@ def run_wgs(args, rank, world, dev_id, torch, dist, coll_dev):
             stream.synchronize()
         dts = timed_blocks(step, sync, args, world, dist, torch, coll_dev)
         table = shard.parse(last["g"])
-        kms, _ = kernel_profile([c.engine for c in shard.mine], args.steps, one_at_a_time=shard.side_stream is not None)
+        kms = {}
+        if args.full:
+            kms, _ = kernel_profile([c.engine for c in shard.mine], args.steps, one_at_a_time=shard.side_stream is not None)
         stream.synchronize()
         for st in shard.side_streams:
             st.synchronize()
@@ -918,23 +969,26 @@ def run_wgs(args, rank, world, dev_id, torch, dist, coll_dev):
         else:
             infos = [info]
     infos = [x.cpu().tolist() for x in infos]
-    # every rank holds the whole table: check it against the rank's own first pass
-    for c in shard.mine:
-        row = table[c.tid]
-        assert [int(x) for x in row[:6]] == c.outcome.state_counts and int(row[13]) == c.outcome.intervals.shape[0], \
-            f"gathered summary of {c.name} differs from the first pass"
+    if args.full:
+        # every rank holds the whole table: check it against the rank's own first pass
+        for c in shard.mine:
+            row = table[c.tid]
+            assert [int(x) for x in row[:6]] == c.outcome.state_counts and int(row[13]) == c.outcome.intervals.shape[0], \
+                f"gathered summary of {c.name} differs from the first pass"
     total_bases = sum(int(table[t][11]) for t, _, _ in shard.contigs)       # word 11: extent (= length, no overhang)
     out = None
     if rank == 0:
-        dt_mean = sum(dts) / len(dts)
-        ms_step = dt_mean * 1e3 / args.steps
+        if args.dump_outputs:
+            # the gathered table every rank receives: the 14 summary words of every contig, in contig order
+            dump_outputs(args.dump_outputs, {"summary_table": [table[t] for t, _, _ in shard.contigs]})
+        ms_step = dts[0] * 1e3 / args.steps
         loads = [x[0] for x in infos]
         alg = sum(x[5] for x in infos)
         pile_ms = sum(x[4] for x in infos)
         callable_b = sum(int(table[t][1]) for t, _, _ in shard.contigs)
         out = {
             "metric": METRIC,
-            "value": total_bases / (dt_mean / args.steps), "unit": "bases/s", "n_gpus": world, "steps": args.steps,
+            "value": total_bases / (dts[0] / args.steps), "unit": "bases/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",
             "config": {"workload": "whole-genome synthetic 30x hg38 (25 primary contigs), contigs LPT-dealt to the GPUs, "
@@ -944,14 +998,12 @@ def run_wgs(args, rank, world, dev_id, torch, dist, coll_dev):
                        "collective_backend": args.backend, "options": "cli defaults (4,500,10,20,10,1,0.1)"},
             "timing": {"blocks": len(dts), "steps_per_block": args.steps, "timed_region_s": sum(dts),
                        "ms_per_step_min": min(dts) * 1e3 / args.steps, "ms_per_step_max": max(dts) * 1e3 / args.steps},
-            "sharding": {"per_rank_bases": [int(x) for x in loads], "per_rank_kernel_ms": [x[1] for x in infos],
+            "sharding": {"per_rank_bases": [int(x) for x in loads],
                          "per_rank_first_pass_s": [x[2] for x in infos],
                          "lpt_imbalance": max(loads) / (sum(loads) / len(loads)),
                          "contigs_of_rank": [[n for (_, n, _), r in zip(shard.contigs, shard.rank_of) if r == k] for k in range(world)],
                          "build_s": [x[6] for x in infos],
                          "host_threads_per_rank": int(os.environ.get("DUT_THREADS", "0")) or None, "gen_threads": args.gen_threads},
-            # the dominant kernel over the whole job: every rank's algorithmic bytes / every rank's pileup kernel time
-            "roofline": roofline(alg, pile_ms, ms_step, kms, world, layout_bytes=sum(x[7] for x in infos)),
             "callable_fraction": callable_b / max(total_bases, 1),
             # self-describing for a reader of `value` across N: this is the FIXED whole-genome input (strong scaling)
             "total_bases": total_bases,
@@ -959,12 +1011,17 @@ def run_wgs(args, rank, world, dev_id, torch, dist, coll_dev):
             "hbm_resident_bytes_per_rank": [int(x[8]) for x in infos],
             "upload_h2d_bytes_per_rank": [int(x[9]) for x in infos],
         }
-        ref1 = cached_wgs_1gpu(total_bases, args)
-        if world > 1 and ref1:
-            out["value_vs_wgs_1gpu"] = out["value"] / ref1["value"]
-            out["wgs_1gpu_reference"] = ref1
-        out["roofline"]["per_rank_frac"] = [x[5] / (x[4] * 1e-3) / 1e9 / PEAK_HBM_GBS if x[4] > 0 else 0.0 for x in infos]
-        out["roofline"]["all_kernel_ms_of"] = "rank 0"
+        if args.full:
+            ref1 = cached_wgs_1gpu(total_bases, args)
+            if world > 1 and ref1:
+                out["value_vs_wgs_1gpu"] = out["value"] / ref1["value"]
+                out["wgs_1gpu_reference"] = ref1
+            out["timing"]["ms_per_step_mean"] = sum(dts) * 1e3 / (len(dts) * args.steps)
+            out["sharding"]["per_rank_kernel_ms"] = [x[1] for x in infos]
+            # the dominant kernel over the whole job: every rank's algorithmic bytes / every rank's pileup kernel time
+            out["roofline"] = roofline(alg, pile_ms, ms_step, kms, world, layout_bytes=sum(x[7] for x in infos))
+            out["roofline"]["per_rank_frac"] = [x[5] / (x[4] * 1e-3) / 1e9 / PEAK_HBM_GBS if x[4] > 0 else 0.0 for x in infos]
+            out["roofline"]["all_kernel_ms_of"] = "rank 0"
     shard.close()
     return out
 
@@ -1053,13 +1110,17 @@ def launch_check(args, rank, world, dist, torch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps: ms_per_step and value are taken over exactly these")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline (see the module docstring)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     ap.add_argument("--workload", choices=["auto", "chr21", "wgs"], default="auto",
                     help="auto: chr21 (configs[1]) on one GPU, the whole genome (configs[3]) on several")
     ap.add_argument("--length", type=int, default=46_709_983, help="chr21 workload: contig length")
     ap.add_argument("--depth", type=float, default=30.0)
-    ap.add_argument("--min-time", type=float, default=0.6, help="seconds of timed K-step blocks to accumulate")
+    ap.add_argument("--min-time", type=float, default=0.6, help="--full: seconds of timed K-step blocks to accumulate")
     ap.add_argument("--max-blocks", type=int, default=400)
     ap.add_argument("--cpu-sample", type=int, default=-1,
                     help="positions of the CPU baseline / bit-exactness sample (-1 = the whole contig, 0 = skip)")
@@ -1082,7 +1143,9 @@ def main():
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started plainly for several GPUs: this process becomes the launcher, before anything touches a GPU
-        sys.exit(launch_ranks(args, sys.argv[1:]))
+        # (the ranks start in the repository: the dump directory goes to them as an absolute path, the last one given wins)
+        dump = ["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else []
+        sys.exit(launch_ranks(args, sys.argv[1:] + dump))
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1117,7 +1180,7 @@ def main():
     # only -- the library itself is loaded further down, after the device is set.
     from decodingustools_amd import build as _native_build
     _native_build.build()
-    if world == 1:                               # the checker of the N = 1 line; no other rank configuration uses it
+    if world == 1 and args.full:                 # the checker of the N = 1 line; no other rank configuration uses it
         import oracle
         oracle.build()
     n_dev = torch.cuda.device_count()

@@ -2,6 +2,7 @@
 shapes), site collection, per-site calls, branch scoring, row ordering and the TSV text
 (SURVEY.md 8f-3).  Host-only: runs without a GPU."""
 import json
+import os
 import random
 
 import numpy as np
@@ -95,7 +96,7 @@ def random_calls(rng, tree_oracle, build, frac=0.7):
     return calls
 
 
-def check_tree(text, provider_name, builds, rng, ref_names=("chrY", "Y")):
+def check_tree(text, provider_name, builds, rng, out_dir, ref_names=("chrY", "Y")):
     provider = H.DECODINGUS if provider_name == "decodingus" else H.FTDNA
     all_nodes, ot = O.load_tree(text, provider_name)
     t = H.HaplogroupTree(text, provider)
@@ -112,7 +113,7 @@ def check_tree(text, provider_name, builds, rng, ref_names=("chrY", "Y")):
             for show in (False, True):
                 want, rows = O.report_text(ot, calls, build, show)
                 n_rows += len(rows)
-                path = "/tmp/_hap_%d.tsv" % rng.randrange(10 ** 9)
+                path = os.path.join(out_dir, "_hap_%d.tsv" % rng.randrange(10 ** 9))
                 t.write_report(path, pc, build, show)
                 assert open(path).read() == want
             got_rows = t.score(pc, build)
@@ -123,25 +124,25 @@ def check_tree(text, provider_name, builds, rng, ref_names=("chrY", "Y")):
 
 
 @pytest.mark.parametrize("seed,n_nodes", [(1, 1), (2, 5), (3, 40), (4, 400), (5, 3000)])
-def test_ftdna_trees_random(seed, n_nodes):
+def test_ftdna_trees_random(seed, n_nodes, tmp_path):
     rng = random.Random(seed)
     pool = [rng.randrange(1, 50_000_000) for _ in range(max(3, n_nodes))]
     text = ftdna_tree(rng, n_nodes, pool, id0=rng.choice([1, 7, 1000]))
     # FTDNA loci only carry GRCh38 coordinates (ftdna.rs:30-38): any other build id finds nothing
-    _, _, n_rows = check_tree(text, "ftdna", ["GRCh38", "rCRS", "GRCh37"], rng)
+    _, _, n_rows = check_tree(text, "ftdna", ["GRCh38", "rCRS", "GRCh37"], rng, str(tmp_path))
     assert n_nodes < 40 or n_rows > 20                       # the comparison is not vacuous
 
 
 @pytest.mark.parametrize("seed,n_nodes", [(11, 1), (12, 6), (13, 60), (14, 900)])
-def test_decodingus_trees_random(seed, n_nodes):
+def test_decodingus_trees_random(seed, n_nodes, tmp_path):
     rng = random.Random(seed)
     pool = [rng.randrange(1, 60_000_000) for _ in range(max(3, n_nodes // 2))]
     text = decodingus_tree(rng, n_nodes, pool)
-    _, _, n_rows = check_tree(text, "decodingus", ["GRCh38", "T2T-CHM13v2.0", "GRCh37", "hs1"], rng)
+    _, _, n_rows = check_tree(text, "decodingus", ["GRCh38", "T2T-CHM13v2.0", "GRCh37", "hs1"], rng, str(tmp_path))
     assert n_nodes < 60 or n_rows > 20
 
 
-def test_known_answer_report():
+def test_known_answer_report(tmp_path):
     """Hand-derived from scoring.rs:8-148 and mod.rs:92-258.
 
     root R (no loci) -> A {a1@100 A>G, a2@110 C>T} -> B {b1@200 G>A, b2@210 T>C, b3@220 A>C} -> C {c1@300 C>G}
@@ -152,15 +153,15 @@ def test_known_answer_report():
     C: derived 0, ancestral 1 -> a > d*3 -> 0.0 -> filtered (and ancestral 1 > 0*10 triggers the early return, score 0 as well).
     X: the call has depth 3 < 4 -> no_call, score 0 -> filtered.
     Order: top = B (cumulative 5); its path to the root is B, A, R -> B then A."""
-    import os
     kat = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "haplogroup_kat.json")))
     tree = kat["tree"]
     calls = [H.SnpCall(p, b, d, f) for p, b, d, f in kat["calls"]]
     t = H.HaplogroupTree(json.dumps(tree))
-    t.write_report("/tmp/_hap_kat.tsv", calls, kat["build_id"], kat["show_snps"])
-    assert open("/tmp/_hap_kat.tsv").read() == kat["expected_tsv"]
+    path = str(tmp_path / "_hap_kat.tsv")
+    t.write_report(path, calls, kat["build_id"], kat["show_snps"])
+    assert open(path).read() == kat["expected_tsv"]
     text, _ = O.report_text(O.load_tree(json.dumps(tree), "ftdna")[1], {c.position: (c.base, c.depth, c.freq) for c in calls}, "GRCh38", True)
-    assert text == open("/tmp/_hap_kat.tsv").read()
+    assert text == open(path).read()
 
 
 def test_call_sites_against_oracle():
@@ -258,12 +259,13 @@ def test_tree_errors():
     assert t.score([H.SnpCall(10, "A", 3, 1.0)], "GRCh38") == []          # below MIN_DEPTH the alleles are never looked at
 
 
-def test_json_reader_escapes_and_unicode():
+def test_json_reader_escapes_and_unicode(tmp_path):
     tree = {"allNodes": {"1": {"haplogroupId": 1, "name": 'R "quoted" \\ é\U0001F9EC\t', "isRoot": True, "root": "R", "kitsCount": 0,
                                "subBranches": 0, "bigYCount": 0, "variants": [{"variant": "vü", "position": 5, "ancestral": "A", "derived": "G"}]}}}
     for ensure_ascii in (True, False):
         text = json.dumps(tree, ensure_ascii=ensure_ascii)
         t = H.HaplogroupTree(text)
         assert t.root_name == tree["allNodes"]["1"]["name"]
-    t.write_report("/tmp/_hap_u.tsv", [H.SnpCall(5, "G", 9, 1.0)], "GRCh38", True)
-    assert open("/tmp/_hap_u.tsv", encoding="utf-8").read().splitlines()[1:] == []     # the root is never a row (mod.rs:78-87)
+    path = str(tmp_path / "_hap_u.tsv")
+    t.write_report(path, [H.SnpCall(5, "G", 9, 1.0)], "GRCh38", True)
+    assert open(path, encoding="utf-8").read().splitlines()[1:] == []     # the root is never a row (mod.rs:78-87)

@@ -3,6 +3,7 @@
 # what configs.wgs_1gpu of the N = 1 line measures) under rocprofv3 -- a kernel trace with statistics, then FETCH_SIZE
 # and WRITE_SIZE, each counter in a pass of its own (never beside a tracing domain other than the kernel trace).
 # WGS_SCALE < 1 shortens the contigs (rehearsal).  The program after `--` is python3 itself (no exec hop).
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 # one stream under the profiler: the contigs' kernels then run one after the other and a kernel's traced duration is its own
 # (bench.py measures them one at a time for the same reason; the timed step itself enqueues on four streams)
@@ -11,7 +12,7 @@ for pass in "trace --kernel-trace --stats" "fetch --pmc FETCH_SIZE" "write --pmc
   set -- $pass; tag=$1; shift
   out=$GRAFT_REPO_ROOT/gpurun_out/prof_wgs_$tag
   rm -rf "$out"; mkdir -p "$out"
-  timeout -k 10 ${WGS_PASS_TIMEOUT:-400} rocprofv3 "$@" --output-format csv -d "$out" -- python3 $GRAFT_REPO_ROOT/bench.py --workload wgs --steps 5 --warmup 2 --min-time 0 --max-blocks 1 --wgs-scale ${WGS_SCALE:-1.0} > "$out/bench.json" 2> "$out/bench.err" || { echo "wgs $tag failed"; tail -3 "$out/bench.err"; continue; }
+  timeout -k 10 ${WGS_PASS_TIMEOUT:-400} rocprofv3 "$@" --output-format csv -d "$out" -- python3 "$ROOT/bench.py" --full --workload wgs --steps 5 --warmup 2 --min-time 0 --max-blocks 1 --wgs-scale ${WGS_SCALE:-1.0} > "$out/bench.json" 2> "$out/bench.err" || { echo "wgs $tag failed"; tail -3 "$out/bench.err"; continue; }
   echo "wgs $tag ok"
 done
 python3 - <<'PY'
