@@ -1,5 +1,5 @@
 """ctypes binding of libcallable_hip.so (include/callable_loci.h, dut_coverage.h, dut_bam.h, dut_report.h,
-dut_haplogroup.h).
+dut_haplogroup.h, dut_fingerprint.h).
 
 There is no fallback: if the shared library is missing or does not load, importing the engine
 raises.  Build it with `python -m decodingustools_amd.build` (or __graft_entry__.build()).
@@ -101,6 +101,16 @@ class dut_haplogroup_result(C.Structure):
                 ("total_snps", C.c_uint32), ("cumulative_snps", C.c_uint32), ("depth", C.c_uint32)]
 
 
+class dut_fp_options(C.Structure):
+    _fields_ = [("ksize", C.c_uint32), ("scaled", C.c_uint64), ("max_frequency", C.c_uint32),
+                ("has_max_frequency", C.c_int32)]
+
+
+class dut_fp_result(C.Structure):
+    _fields_ = [("processed", C.c_uint64), ("n_distinct", C.c_uint64), ("n_entries", C.c_uint64),
+                ("hashes", C.c_void_p), ("counts", C.c_void_p), ("hexdigest", C.c_char * 65)]
+
+
 CL_K_NAMES = ("prep", "bounds", "pileup", "rle")
 CL_K_COUNT = 4
 
@@ -189,6 +199,28 @@ SYMBOLS = [
                                            C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
                                            C.c_uint, C.c_char_p, C.c_size_t]),
     ("dut_bam_sample", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("dut_bam_next_seqs", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.c_void_p)]),
+    # include/dut_fingerprint.h
+    ("dut_fp_create", C.c_int, [C.POINTER(dut_fp_options), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("dut_fp_push_seq4", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("dut_fp_push_bytes", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("dut_fp_finish", C.c_int, [C.c_void_p, C.POINTER(dut_fp_result)]),
+    ("dut_fp_destroy", None, [C.c_void_p]),
+    ("dut_fp_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("dut_fp_last_error", C.c_char_p, [C.c_void_p]),
+    ("dut_fp_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(dut_fp_options), C.c_char_p, C.c_int,
+                               C.c_char_p, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    ("dut_fp_input_kind", C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
+    ("dut_fp_kmer_hashes_host", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("dut_fp_kmer_hashes_host_seq4", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("dut_fp_max_hash", C.c_uint64, [C.c_uint64]),
+    ("dut_fp_sha256", None, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dut_fastq_open", C.c_void_p, [C.c_char_p, C.c_char_p, C.c_size_t]),
+    ("dut_fastq_next", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_void_p)]),
+    ("dut_fastq_close", None, [C.c_void_p]),
     # include/dut_report.h
     ("dut_detect_aligner", C.c_char_p, [C.c_char_p, C.c_size_t]),
     ("dut_reference_build", C.c_char_p, [C.c_char_p, C.c_size_t]),

@@ -360,6 +360,7 @@ struct dut_bam {
     // dut_bam_read_contig_bits: the base-quality test taken at parse (one bit per base) and the reads' sums
     RawBuf<uint64_t> qbits;
     RawBuf<uint32_t> qsum;
+    bool seq_walk = false;                   // `st` is in the middle of dut_bam_next_seqs' whole-file walk
 };
 
 namespace {
@@ -529,6 +530,7 @@ static int dut_bam_read_contig_impl(dut_bam *b, int tid, dut_records *out, const
     const bool want_seq = seq_off && seq4;
     BlockStream &st = b->st;
     st.fp = b->z.fp;
+    if (b->seq_walk) { st.valid = false; b->seq_walk = false; }      // the whole-file walk left the stream elsewhere
     bool nothing = false;
     // position the stream at the first record that can belong to tid
     if (b->has_index) {
@@ -840,6 +842,65 @@ int dut_bam_sample(dut_bam *b, dut_bam_sample_fn fn, void *ud)
     b->pending = false;
     if (!b->z.seek(b->data_start) && rc == CL_OK) { b->err = "rewind failed"; rc = CL_ERR_INVALID; }
     return rc;
+}
+
+static int dut_bam_next_seqs_impl(dut_bam *b, uint64_t max_bases, uint64_t *n_seq, const uint64_t **base_off, const uint8_t **seq4)
+{
+    if (!b || !n_seq || !base_off || !seq4) return CL_ERR_INVALID;
+    *n_seq = 0;
+    b->err.clear();
+    BlockStream &st = b->st;
+    if (!b->seq_walk) { st.fp = b->z.fp; st.reset(b->data_start); b->seq_walk = true; b->last_tid_done = -1; }
+    b->seq_off.clear(); b->seq4.clear();
+    uint64_t n = 0, bases = 0;
+    for (;;) {
+        const size_t avail = st.buf.n - st.cur;
+        uint32_t bs = avail >= 4 ? rd32(st.buf.p + st.cur) : 0;
+        if (avail >= 4 && (bs < 32 || bs > (1u << 29))) { b->err = "bad BAM block_size"; return CL_ERR_INVALID; }
+        if (avail < 4 || avail < 4 + (size_t)bs) {                    // the record goes on in the next blocks
+            if (st.fill()) continue;
+            if (!st.err.empty()) { b->err = st.err; return CL_ERR_INVALID; }
+            if (st.cur < st.buf.n) { b->err = "truncated BAM record"; return CL_ERR_INVALID; }
+            break;                                                    // clean EOF
+        }
+        const uint8_t *r = st.buf.p + st.cur + 4;
+        const uint32_t l_read_name = r[8], n_cigar = rd16(r + 12), l_seq = rd32(r + 16);
+        if (l_read_name == 0 || 32ull + l_read_name + 4ull * n_cigar + (l_seq + 1ull) / 2 + (uint64_t)l_seq > bs) {
+            b->err = "malformed BAM record"; return CL_ERR_INVALID;
+        }
+        if (n > 0 && bases + l_seq > max_bases) break;               // the record opens the next batch
+        if (!b->seq_off.reserve(n + 2) || !b->seq4.reserve((size_t)((bases + l_seq + 1) / 2) + 1)) { b->err = "out of memory"; return CL_ERR_NOMEM; }
+        b->seq_off.p[n] = bases;
+        const uint8_t *pk = r + 32 + l_read_name + 4ull * n_cigar;
+        uint8_t *d = b->seq4.p;
+        uint32_t i = 0;
+        if (bases & 1u) {                                             // odd start: the low nibble of the shared byte
+            if (l_seq) { d[bases >> 1] = (uint8_t)((d[bases >> 1] & 0xF0u) | (pk[0] >> 4)); i = 1; }
+            const uint64_t byte0 = (bases + 1) >> 1;
+            const uint32_t full = (l_seq - i) >> 1;
+            for (uint32_t k = 0; k < full; ++k) d[byte0 + k] = (uint8_t)((pk[k] << 4) | (pk[k + 1] >> 4));
+            i += 2 * full;
+            if (i < l_seq) d[(bases + i) >> 1] = (uint8_t)(pk[i >> 1] << 4);
+        } else {
+            memcpy(d + (bases >> 1), pk, l_seq >> 1);
+            if (l_seq & 1u) d[(bases + l_seq) >> 1] = (uint8_t)(pk[l_seq >> 1] & 0xF0u);
+        }
+        bases += l_seq;
+        n += 1;
+        st.cur += 4 + (size_t)bs;
+    }
+    if (!b->seq_off.reserve(n + 1) || !b->seq4.reserve(1)) { b->err = "out of memory"; return CL_ERR_NOMEM; }
+    b->seq_off.p[n] = bases;
+    b->seq_off.n = n + 1; b->seq4.n = (size_t)((bases + 1) / 2);
+    *n_seq = n; *base_off = b->seq_off.p; *seq4 = b->seq4.p;
+    return CL_OK;
+}
+
+int dut_bam_next_seqs(dut_bam *b, uint64_t max_bases, uint64_t *n_seq, const uint64_t **base_off, const uint8_t **seq4)
+{
+    try { return dut_bam_next_seqs_impl(b, max_bases, n_seq, base_off, seq4); }
+    catch (const std::bad_alloc &) { return CL_ERR_NOMEM; }
+    catch (...) { return CL_ERR_INVALID; }
 }
 
 } // extern "C"

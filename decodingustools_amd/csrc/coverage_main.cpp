@@ -5,6 +5,7 @@
 // per-contig coverage figures <contig>_coverage.svg go beside the BED file.
 #include "../../include/dut_bam.h"
 #include "../../include/dut_haplogroup.h"
+#include "../../include/dut_fingerprint.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +25,79 @@ static void usage()
             "Usage: dut-coverage [coverage] <BAM_FILE> -r <REFERENCE_FILE> [-o callable_regions.bed] [-s summary.html]\n"
             "       [-L <CONTIG>]... [--min-depth 4] [--max-depth 500] [--min-mapping-quality 10]\n"
             "       [--min-base-quality 20] [--min-depth-for-low-mapq 10] [--max-low-mapq 1]\n"
-            "       [--max-low-mapq-fraction 0.1] [--device 0 | --devices 0,1,...]\n");
+            "       [--max-low-mapq-fraction 0.1] [--device 0 | --devices 0,1,...]\n"
+            "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n");
+}
+
+// fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
+// BAM or FASTQ file.  Argument and file-format errors are reported before any device is opened.
+static int fingerprint_main(int argc, char **argv)
+{
+    std::string input, ref, out, region = "full";
+    dut_fp_options opt = {31, 1000, 0, 0};
+    int device = 0;
+    auto usage_fp = []() {
+        fprintf(stderr,
+                "Usage: dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE]\n"
+                "       [-R full|chrY|chrM] [--device 0]\n"
+                "  INPUT: .bam, .fastq, .fq or .gz (FASTQ, plain or gzip; 4-line records).  1 <= ksize <= 64.\n"
+                "  -R only labels the output file (#region=...), as in the reference: every read of the file is used.\n");
+    };
+    auto number = [&](const char *flag, const char *v, unsigned long long &dst) -> bool {
+        char *end = nullptr;
+        errno = 0;
+        if (!*v || *v == '-') { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v, flag); return false; }
+        dst = strtoull(v, &end, 10);
+        if (errno || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v, flag); return false; }
+        return true;
+    };
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i], val;
+        const size_t eq = a.find('=');
+        const bool has_eq = a.rfind("--", 0) == 0 && eq != std::string::npos;
+        if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
+        auto next = [&]() -> const char * {
+            if (has_eq) return val.c_str();
+            if (i + 1 >= argc) { usage_fp(); exit(2); }
+            return argv[++i];
+        };
+        unsigned long long v = 0;
+        if (a == "-r" || a == "--reference") ref = next();
+        else if (a == "-o" || a == "--output") out = next();
+        else if (a == "--ksize") {
+            if (!number("--ksize", next(), v)) return 2;
+            if (v < 1 || v > 64) { fprintf(stderr, "error: invalid value '%llu' for '--ksize': this build supports 1..64\n", v); return 2; }
+            opt.ksize = (uint32_t)v;
+        }
+        else if (a == "--scaled") { if (!number("--scaled", next(), v)) return 2; opt.scaled = v; }
+        else if (a == "--max-frequency") {
+            if (!number("--max-frequency", next(), v) || v > 0xFFFFFFFFull) { if (v > 0xFFFFFFFFull) fprintf(stderr, "error: invalid value for '--max-frequency'\n"); return 2; }
+            opt.max_frequency = (uint32_t)v; opt.has_max_frequency = 1;
+        }
+        else if (a == "-R" || a == "--region") {
+            region = next();
+            if (region != "full" && region != "chrY" && region != "chrM") {
+                fprintf(stderr, "error: invalid value '%s' for '--region <REGION>'\n  [possible values: full, chrY, chrM]\n", region.c_str());
+                return 2;
+            }
+        }
+        else if (a == "--device") device = atoi(next());
+        else if (a == "-h" || a == "--help") { usage_fp(); return 0; }
+        else if (!a.empty() && a[0] != '-' && input.empty()) input = a;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fp(); return 2; }
+    }
+    if (input.empty()) { usage_fp(); return 2; }
+    char err[1024] = {0};
+    if (dut_fp_input_kind(input.c_str(), err, sizeof(err)) < 0) { fprintf(stderr, "Error: %s\n", err); return 1; }
+    if (access(input.c_str(), R_OK) != 0) { fprintf(stderr, "Error: cannot open %s: %s\n", input.c_str(), strerror(errno)); return 1; }
+    char digest[65] = {0};
+    uint64_t processed = 0;
+    const int rc = dut_fp_files(input.c_str(), ref.empty() ? nullptr : ref.c_str(), out.empty() ? nullptr : out.c_str(), &opt,
+                                region.c_str(), device, digest, &processed, err, sizeof(err));
+    if (digest[0]) printf("Processed %llu sequences\n%s\n", (unsigned long long)processed, digest);
+    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
+    fflush(nullptr);
+    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
 }
 
 // find-y-branch / find-mt-branch (src/cli.rs:62-105, src/commands/find_branch.rs).  The reference
@@ -91,6 +164,7 @@ int main(int argc, char **argv)
     stamp("main");
     if (argc > 1 && !strcmp(argv[1], "find-y-branch")) return find_branch_main(argc, argv, DUT_TREE_YDNA);
     if (argc > 1 && !strcmp(argv[1], "find-mt-branch")) return find_branch_main(argc, argv, DUT_TREE_MTDNA);
+    if (argc > 1 && !strcmp(argv[1], "fingerprint")) return fingerprint_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

@@ -52,6 +52,14 @@ typedef int (*dut_bam_sample_fn)(void *ud, uint64_t index, uint16_t flag, uint32
                                  const uint8_t *qname, size_t qname_len, int32_t tlen);
 int dut_bam_sample(dut_bam *b, dut_bam_sample_fn fn, void *ud);
 
+/* Every record of the file from the first one, mapped or not, in file order, without the index (the
+ * `fingerprint` reader, readers/bam.rs:94-133; dut_fingerprint.h), a batch at a time: *n_seq records whose
+ * bases total at most max_bases (at least one record), their sequences as 4-bit codes, two per byte,
+ * continuous over the records (first base in the high nibble of byte 0), record i at bases
+ * [base_off[i], base_off[i+1]).  Reader-owned until the next call on this reader; *n_seq = 0 at the end.
+ * The first call -- and the first after dut_bam_read_contig -- starts at the first record. */
+int dut_bam_next_seqs(dut_bam *b, uint64_t max_bases, uint64_t *n_seq, const uint64_t **base_off, const uint8_t **seq4);
+
 /* FASTA with a faidx index (faidx::Reader::from_path, api/coverage.rs:73): the .fai beside the file is read and
  * validated, or built (and written there when possible) when it is missing.  NULL on failure. */
 dut_fasta *dut_fasta_open(const char *path, char *err, size_t err_len);

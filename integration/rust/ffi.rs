@@ -53,6 +53,29 @@ extern "C" {
                                     summary_json: *const c_char, summary_html: *const c_char, opt: *const ClOptions,
                                     contigs: *const *const c_char, n_contigs: usize, devices: *const c_int, n_devices: usize,
                                     flags: c_uint, err: *mut c_char, err_len: usize) -> c_int;
+    // include/dut_fingerprint.h: the `fingerprint` sketch on the device (1 <= ksize <= 64)
+    pub fn dut_fp_create(opt: *const DutFpOptions, device_id: c_int, stream: *mut c_void, out: *mut *mut DutFpCtx) -> c_int;
+    pub fn dut_fp_push_seq4(ctx: *mut DutFpCtx, seq4: *const u8, base_off: *const u64, n_seq: u64) -> c_int;
+    pub fn dut_fp_push_bytes(ctx: *mut DutFpCtx, bytes: *const u8, base_off: *const u64, n_seq: u64) -> c_int;
+    pub fn dut_fp_finish(ctx: *mut DutFpCtx, out: *mut DutFpResult) -> c_int;
+    pub fn dut_fp_destroy(ctx: *mut DutFpCtx);
+    pub fn dut_fp_last_error(ctx: *const DutFpCtx) -> *const c_char;
+    pub fn dut_fp_files(input: *const c_char, reference: *const c_char, output: *const c_char, opt: *const DutFpOptions,
+                        region: *const c_char, device_id: c_int, digest_out: *mut c_char, processed_out: *mut u64,
+                        err: *mut c_char, err_len: usize) -> c_int;
+}
+
+pub enum DutFpCtx {}
+
+#[repr(C)]
+pub struct DutFpOptions {         // dut_fp_options, include/dut_fingerprint.h
+    pub ksize: u32, pub scaled: u64, pub max_frequency: u32, pub has_max_frequency: i32,
+}
+
+#[repr(C)]
+pub struct DutFpResult {          // dut_fp_result: hashes / counts stay valid until dut_fp_destroy
+    pub processed: u64, pub n_distinct: u64, pub n_entries: u64,
+    pub hashes: *const u64, pub counts: *const u32, pub hexdigest: [c_char; 65],
 }
 
 #[repr(C)] #[derive(Default)]

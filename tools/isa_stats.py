@@ -15,9 +15,12 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def extract(lib, out):
+    """Writes every gfx950 code object of the library (one per HIP translation unit) to out.0, out.1, ...;
+    returns their paths."""
     data = open(lib, "rb").read()
     # the clang offload bundle lives in .hip_fatbin; the gfx950 ELF inside starts with \x7fELF after the host ELF header
     idx = [m.start() for m in re.finditer(b"\x7fELF", data)]
+    paths = []
     for i in idx[1:]:
         # e_machine EM_AMDGPU = 224
         if int.from_bytes(data[i + 18:i + 20], "little") == 224:
@@ -25,9 +28,10 @@ def extract(lib, out):
             shoff = int.from_bytes(data[i + 40:i + 48], "little")
             shentsize = int.from_bytes(data[i + 58:i + 60], "little")
             shnum = int.from_bytes(data[i + 60:i + 62], "little")
-            open(out, "wb").write(data[i:i + shoff + shnum * shentsize])
-            return True
-    return False
+            path = f"{out}.{len(paths)}"
+            open(path, "wb").write(data[i:i + shoff + shnum * shentsize])
+            paths.append(path)
+    return paths
 
 
 def main():
@@ -35,11 +39,12 @@ def main():
         os.path.dirname(os.path.abspath(__file__)), "..", "decodingustools_amd", "lib", "libcallable_hip.so")
     pats = [a for a in sys.argv[1:] if not a.endswith(".so")]
     with tempfile.TemporaryDirectory() as d:
-        co = os.path.join(d, "k.co")
-        if not extract(lib, co):
+        cos = extract(lib, os.path.join(d, "k.co"))
+        if not cos:
             sys.exit("no gfx950 code object found in " + lib)
-        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
-        dis = subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
+        notes = "".join(subprocess.run([LLVM + "/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout for co in cos)
+        dis = "".join(subprocess.run([LLVM + "/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True).stdout
+                      for co in cos)
     # metadata: one YAML list entry per kernel under amdhsa.kernels (keys in alphabetical order, .agpr_count first;
     # the entries of .args are indented deeper)
     kern = {}
