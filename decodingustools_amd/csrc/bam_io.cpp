@@ -1,8 +1,6 @@
-// bam_io.cpp -- implementation of include/dut_bam.h: BGZF/BAM/BAI and FASTA/FAI input and the
-// file-level `coverage` driver.  Host-only code (zlib for the inflate); the per-position work is the
-// device engine's (callable_loci.hip).
+// bam_io.cpp -- implementation of include/dut_bam.h: BGZF/BAM/BAI/CSI and FASTA/FAI input.  Host-only
+// code (zlib for the inflate).  The file-level `coverage` driver that reads through it is coverage_files.cpp.
 #include "../../include/dut_bam.h"
-#include "../../include/dut_report.h"
 #include "host_parallel.h"
 #include "qual_pack.h"
 
@@ -12,13 +10,11 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -119,9 +115,6 @@ struct Bgzf {
 };
 
 struct RefSeq { std::string name; uint32_t len; };
-
-inline double tnow() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-inline bool timing_on() { static const bool on = getenv("DUT_TIMING") && *getenv("DUT_TIMING") == '1'; return on; }
 
 // (Giving back a chr21-sized contig's ~2.7 GB of decode buffers costs ~0.25 s of page-table work at close.
 // Tried and dropped: transparent huge pages for these buffers -- with the usual `defrag = madvise` the
@@ -227,7 +220,7 @@ struct BlockStream {
         std::vector<Blk> blks;
         size_t got = 0, used = 0, out_total = 0;
         for (;;) {
-            const double tr0 = tnow();
+            const double tr0 = dut::now_s();
             if (ahead.joinable()) ahead.join();
             if (ahead_want && ahead_off == next_coff && ahead_want == batch) {
                 std::swap(cbuf.p, cbuf_next.p); std::swap(cbuf.cap, cbuf_next.cap);
@@ -239,7 +232,7 @@ struct BlockStream {
                 if (fseeko(fp, (off_t)next_coff, SEEK_SET) != 0) { err = "seek failed"; return false; }
                 got = fread(cbuf.p, 1, batch, fp);
             }
-            t_read += tnow() - tr0;
+            t_read += dut::now_s() - tr0;
             if (got == 0) { eof = true; return false; }
             blks.clear(); used = 0; out_total = 0;
             while (used + 18 <= got) {
@@ -293,7 +286,7 @@ struct BlockStream {
         // one z_stream per contiguous group of blocks
         const size_t grain = 16;
         const LibDeflate &ld = libdeflate();
-        const double ti0 = tnow();
+        const double ti0 = dut::now_s();
         parallel_for((blks.size() + grain - 1) / grain, 1, [&](size_t g) {
             if (ld.ok) {
                 void *dec = ld.alloc();
@@ -325,7 +318,7 @@ struct BlockStream {
             }
             inflateEnd(&zs);
         });
-        t_inflate += tnow() - ti0;
+        t_inflate += dut::now_s() - ti0;
         if (bad) { err = bad == 3 ? "BGZF CRC mismatch" : "inflate failed"; return false; }
         if (skip) {
             if (skip > buf.n - base) { err = "virtual offset beyond its block"; return false; }
@@ -675,7 +668,7 @@ static int dut_bam_read_contig_impl(dut_bam *b, int tid, dut_records *out, const
         bool done_parallel = false;
         if (st.aligned && size > st.cur) {
             // ---- blocks walked independently: count, place, store (all three in parallel over the blocks) ----
-            const double ts0 = tnow();
+            const double ts0 = dut::now_s();
             units.clear();
             size_t s0 = st.cur;
             for (size_t v : st.bstart) if (v > s0) { units.push_back({s0, v, SIZE_MAX, 0, 0, 0, 0, 0}); s0 = v; }
@@ -717,8 +710,8 @@ static int dut_bam_read_contig_impl(dut_bam *b, int tid, dut_records *out, const
                 }
                 n_bases = n_qual;
                 if (n_cig > 0xFFFFFFF0ull || n_name > 0xFFFFFFF0ull) { b->err = "contig too large for 32-bit offsets"; return CL_ERR_RANGE; }
-                t_scan += tnow() - ts0;
-                const double tp0 = tnow();
+                t_scan += dut::now_s() - ts0;
+                const double tp0 = dut::now_s();
                 if (!make_room()) return CL_ERR_INVALID;
                 parallel_for(n_units, 8, [&](size_t ui) {
                     const Unit &u = units[ui];
@@ -742,13 +735,13 @@ static int dut_bam_read_contig_impl(dut_bam *b, int tid, dut_records *out, const
                 else st.cur = last.e;
                 b->pos.n = b->flag.n = b->mapq.n = n;
                 b->cigar.n = n_cig; b->qual.n = want_bits ? 0 : n_qual; b->qname.n = n_name; b->qsum.n = want_bits ? n : 0;
-                t_parse += tnow() - tp0;
+                t_parse += dut::now_s() - tp0;
                 done_parallel = true;
             }
         }
         if (done_parallel) continue;
         // ---- general walk: pass 1, record boundaries of this window and destination offsets (sequential) ----
-        const double ts0 = tnow();
+        const double ts0 = dut::now_s();
         recs.clear();
         size_t o = st.cur;
         while (o + 4 <= size) {
@@ -772,8 +765,8 @@ static int dut_bam_read_contig_impl(dut_bam *b, int tid, dut_records *out, const
             }
             o += 4 + (size_t)bs;
         }
-        t_scan += tnow() - ts0;
-        const double tp0 = tnow();
+        t_scan += dut::now_s() - ts0;
+        const double tp0 = dut::now_s();
         // ---- pass 2: fill the arrays, records in parallel ----
         if (!make_room()) return CL_ERR_INVALID;
         const RecInfo *ri = recs.data();
@@ -781,13 +774,13 @@ static int dut_bam_read_contig_impl(dut_bam *b, int tid, dut_records *out, const
         b->pos.n = b->flag.n = b->mapq.n = n;
         b->cigar.n = n_cig; b->qual.n = want_bits ? 0 : n_qual; b->qname.n = n_name; b->qsum.n = want_bits ? n : 0;
         st.cur = o;
-        t_parse += tnow() - tp0;
+        t_parse += dut::now_s() - tp0;
     }
     if (!b->cigar_off.reserve(n + 1) || !b->qual_off.reserve(n + 1) || !b->qname_off.reserve(n + 1) || !b->seq_off.reserve(n + 1) ||
         !b->pos.reserve(1) || !b->flag.reserve(1) || !b->mapq.reserve(1) || !b->cigar.reserve(1) || !b->qual.reserve(1) || !b->qname.reserve(1) ||
         !b->seq4.reserve(1)) { b->err = "out of memory"; return CL_ERR_INVALID; }
     b->cigar_off.p[n] = (uint32_t)n_cig; b->qual_off.p[n] = n_qual; b->qname_off.p[n] = (uint32_t)n_name; b->seq_off.p[n] = n_bases;
-    if (timing_on())
+    if (dut::timing_on())
         fprintf(stderr, "[dut-timing]   read %.0f ms, inflate %.0f ms (%s, %d threads), scan %.0f ms, parse %.0f ms\n", st.t_read * 1e3,
                 st.t_inflate * 1e3, libdeflate().ok ? "libdeflate" : "zlib", dut::worker_threads(), t_scan * 1e3, t_parse * 1e3);
     b->last_tid_done = tid;
@@ -904,6 +897,18 @@ int dut_bam_next_seqs(dut_bam *b, uint64_t max_bases, uint64_t *n_seq, const uin
 }
 
 } // extern "C"
+
+namespace dut {
+// For a caller about to leave the process (coverage_files.cpp): the read-ahead ended and the file closed, the reader and
+// its decode buffers left to the exit.
+void bam_release_for_exit(dut_bam *b)
+{
+    if (!b || !b->z.fp) return;
+    b->st.drop_ahead();
+    fclose(b->z.fp);
+    b->z.fp = nullptr;
+}
+} // namespace dut
 
 // ---------------------------------------------------------------------------------------------
 // FASTA + .fai
@@ -1073,334 +1078,3 @@ int dut_fasta_fetch(dut_fasta *f, const char *name, const uint8_t **bases, uint6
 }
 
 } // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// the file-level coverage driver
-// ---------------------------------------------------------------------------------------------
-static double io_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static void io_stage_time(const char *what, double &t0)
-{
-    static const bool on = getenv("DUT_TIMING") && *getenv("DUT_TIMING") == '1';
-    if (!on) return;
-    const double t1 = io_now();
-    fprintf(stderr, "[dut-timing] %-28s %8.1f ms\n", what, (t1 - t0) * 1e3);
-    t0 = t1;
-}
-
-// Contigs dealt to devices by longest-processing-time-first: the heaviest contig next, to the device with the least
-// load so far (weights: the index's mapped-read counts when it records them, the contig lengths otherwise).
-static std::vector<int> lpt_deal(const std::vector<uint64_t> &weight, size_t n_dev)
-{
-    std::vector<size_t> order(weight.size());
-    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weight[a] > weight[b]; });
-    std::vector<uint64_t> load(n_dev, 0);
-    std::vector<int> owner(weight.size(), 0);
-    for (size_t i : order) {
-        size_t best = 0;
-        for (size_t d = 1; d < n_dev; ++d) if (load[d] < load[best]) best = d;
-        owner[i] = (int)best; load[best] += weight[i] + 1;
-    }
-    return owner;
-}
-
-static int dut_coverage_files_impl(const char *bam_path, const char *fasta_path, const char *bed_path,
-                                  const char *summary_json, const char *summary_html, const cl_options *opt,
-                                  const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
-                                  unsigned flags, char *err, size_t err_len)
-{
-    if (!bam_path || !fasta_path || !bed_path || !opt || !devices || n_devices == 0) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
-    const int device_id = devices[0];
-    const bool leave = (flags & DUT_FILES_LEAVE_TO_EXIT) != 0;
-    // the engine's default form wants one bit per base (cl_create reads the same variable): the reader then takes the
-    // base-quality test while it parses the records and no quality byte leaves it
-    const char *qf = getenv("DUT_QUAL_FORM");
-    const char *pr = getenv("DUT_PACKED_READER");                   // =0: bytes from the reader, tested in cl_push_reads (for A/B timing)
-    const bool use_bits = !(qf && strcmp(qf, "bytes") == 0) && !(pr && pr[0] == '0');
-    char e[512] = {0};
-    double tm = io_now();
-    dut_bam_stats *bstats = dut_bam_stats_new(10000);                  // api/coverage.rs:56-59
-    if (dut_bam_stats_collect(bstats, bam_path, e, sizeof(e)) != CL_OK) {
-        set_err(err, err_len, std::string("Failed to collect BAM stats: ") + e);
-        dut_bam_stats_free(bstats);
-        return CL_ERR_INVALID;
-    }
-    dut_bam *bam = dut_bam_open(bam_path, e, sizeof(e));
-    if (!bam) { dut_bam_stats_free(bstats); set_err(err, err_len, std::string("Failed to open BAM file: ") + e); return CL_ERR_INVALID; }   // api/coverage.rs:69-70
-    dut_fasta *fa = dut_fasta_open(fasta_path, e, sizeof(e));
-    if (!fa) { dut_bam_stats_free(bstats); dut_bam_close(bam); set_err(err, err_len, std::string("Failed to open reference: ") + e); return CL_ERR_INVALID; }   // :73-74
-    // initialize_contig_stats / validate_contig_selection, api/coverage.rs:149-204
-    std::vector<int> tids;
-    for (int t = 0; t < dut_bam_n_ref(bam); ++t) {
-        bool take = contigs == nullptr;
-        for (size_t i = 0; !take && i < n_contigs; ++i) take = strcmp(contigs[i], dut_bam_ref_name(bam, t)) == 0;
-        if (take) tids.push_back(t);
-    }
-    int rc = CL_OK;
-    cl_ctx *ctx = nullptr;
-    dut_profiler *prof = nullptr;
-    std::vector<dut_contig_stats> stats;
-    std::vector<std::string> names;
-    std::vector<std::vector<uint64_t>> counts;
-    if (contigs && tids.empty()) {
-        std::string list;
-        for (size_t i = 0; i < n_contigs; ++i) { if (i) list += ", "; list += contigs[i]; }
-        set_err(err, err_len, "None of the specified contigs (" + list + ") were found in the BAM file");
-        rc = CL_ERR_INVALID; goto out;
-    }
-    if (n_devices > 1 && !tids.empty()) {
-        // ---- several devices: one host thread, one reader pair and one engine context per device; the contigs dealt by
-        //      LPT; every contig's runs, counts and statistics come back through host memory and the BED is written here,
-        //      in tid order (api/coverage.rs:229-234 is a serial loop with no cross-contig state but the BED writer's
-        //      pending line, callable_profiler.rs:64-66).  No collective: one process holds every result. ----
-        io_stage_time("(before contigs)", tm);
-        struct Result { int rc = CL_OK; std::string msg; dut_contig_stats st; uint64_t counts[6]; std::vector<cl_interval> iv; bool done = false; };
-        std::vector<Result> res(tids.size());
-        std::mutex mu;
-        std::condition_variable cv;
-        std::atomic<bool> stop{false};
-        std::vector<uint64_t> weight(tids.size());
-        for (size_t i = 0; i < tids.size(); ++i) {
-            const int64_t m = dut_bam_ref_mapped(bam, tids[i]);
-            weight[i] = m >= 0 ? (uint64_t)m : (uint64_t)dut_bam_ref_len(bam, tids[i]);
-        }
-        const std::vector<int> owner = lpt_deal(weight, n_devices);
-        prof = dut_profiler_new(bed_path);
-        if (!prof) { set_err(err, err_len, std::string("Failed to create CallableProfiler: cannot create ") + bed_path); rc = CL_ERR_INVALID; goto out; }
-        {
-            uint32_t largest = 0;
-            for (int t : tids) if (strcmp(dut_bam_ref_name(bam, t), "chrM") != 0) largest = std::max(largest, dut_bam_ref_len(bam, t));
-            dut_profiler_enable_plots(prof, largest);
-        }
-        {
-            std::vector<dut::Thread> workers;
-            for (size_t d = 0; d < n_devices; ++d) {
-                workers.push_back(dut::spawn_or_run([&, d]() {
-                    auto fail_rest = [&](size_t from, int code, const std::string &m) {
-                        std::lock_guard<std::mutex> g(mu);
-                        for (size_t i = from; i < tids.size(); ++i)
-                            if (owner[i] == (int)d && !res[i].done) { res[i].rc = code; res[i].msg = m; res[i].done = true; }
-                        cv.notify_all();
-                    };
-                    char e2[512] = {0};
-                    cl_ctx *dctx = nullptr;
-                    dut_bam *db = nullptr; dut_fasta *df = nullptr;
-                    try {
-                        int drc = cl_create(opt, devices[d], nullptr, &dctx);
-                        if (drc != CL_OK) { fail_rest(0, drc, "no usable HIP device (the engine has no CPU fallback)"); return; }
-                        db = dut_bam_open(bam_path, e2, sizeof(e2));
-                        if (!db) { fail_rest(0, CL_ERR_INVALID, std::string("Failed to open BAM file: ") + e2); cl_destroy(dctx); return; }
-                        df = dut_fasta_open(fasta_path, e2, sizeof(e2));
-                        if (!df) { fail_rest(0, CL_ERR_INVALID, std::string("Failed to open reference: ") + e2); dut_bam_close(db); cl_destroy(dctx); return; }
-                        for (size_t i = 0; i < tids.size(); ++i) {
-                            if (owner[i] != (int)d) continue;
-                            if (stop.load()) { fail_rest(i, CL_ERR_INVALID, "abandoned"); break; }
-                            const int t = tids[i];
-                            dut_records rec;
-                            const uint8_t *bases = nullptr; uint64_t blen = 0;
-                            int frc = CL_OK;
-                            dut::Thread fb;
-                            if (dut_bam_ref_len(db, t) > 0)
-                                fb = dut::spawn_or_run([&]() { frc = dut_fasta_fetch(df, dut_bam_ref_name(db, t), &bases, &blen); });
-                            drc = use_bits ? dut_bam_read_contig_bits(db, t, opt->min_base_quality, &rec) : dut_bam_read_contig(db, t, &rec, nullptr, nullptr);
-                            if (fb.joinable()) fb.join();
-                            if (drc != CL_OK) { fail_rest(i, drc, std::string("Error processing contig: ") + dut_bam_error(db)); break; }
-                            if (frc != CL_OK) { fail_rest(i, frc, std::string("Error processing contig: ") + dut_fasta_error(df)); break; }
-                            Result r;
-                            memset(&r.st, 0, sizeof(r.st));
-                            const cl_interval *iv = nullptr; size_t niv = 0;
-                            drc = dut_process_single_contig_runs(dctx, &r.st, opt, t, dut_bam_ref_len(db, t), bases, blen, &rec, r.counts, &iv, &niv);
-                            if (drc != CL_OK) {
-                                const char *m = cl_last_error(dctx);
-                                fail_rest(i, drc, std::string("Error processing contig: ") + ((m && *m) ? m : (drc == CL_ERR_UNSORTED ? "the input is not sorted" : "failed")));
-                                break;
-                            }
-                            r.iv.assign(iv, iv + niv);
-                            r.done = true;
-                            { std::lock_guard<std::mutex> g(mu); res[i] = std::move(r); }
-                            cv.notify_all();
-                        }
-                    } catch (...) { fail_rest(0, CL_ERR_NOMEM, "out of memory or internal error"); }
-                    if (!leave) {
-                        if (df) dut_fasta_close(df);
-                        if (db) dut_bam_close(db);
-                        if (dctx) cl_destroy(dctx);
-                    }
-                }));
-            }
-            // the BED, in tid order, as each contig's result arrives
-            for (size_t i = 0; i < tids.size(); ++i) {
-                Result r;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return res[i].done; });
-                    r = std::move(res[i]);
-                }
-                if (rc != CL_OK) continue;                       // (after the first error the rest is only waited for)
-                if (r.rc != CL_OK) { rc = r.rc; set_err(err, err_len, r.msg); stop.store(true); continue; }
-                const char *nm = dut_bam_ref_name(bam, tids[i]);
-                double tb = io_now();
-                int frc = dut_profiler_feed_contig(prof, nm, r.iv.data(), r.iv.size(), r.counts);
-                if (frc == CL_OK && dut_profiler_finish_plot(prof, nm, dut_bam_ref_len(bam, tids[i])) < 0) frc = CL_ERR_INVALID;
-                if (frc != CL_OK) { rc = frc; set_err(err, err_len, std::string("cannot write ") + bed_path); stop.store(true); continue; }
-                io_stage_time("BED lines", tb);
-                stats.push_back(r.st); names.push_back(nm); counts.push_back(std::vector<uint64_t>(r.counts, r.counts + 6));
-            }
-            workers.clear();                                     // joins
-        }
-        io_stage_time("contigs over the devices", tm);
-        if (rc != CL_OK) goto out;
-    } else {
-        // the HIP runtime and the engine context come up on their own thread while the first contig is decoded
-        dut::Thread init = dut::spawn_or_run([&]() { rc = cl_create(opt, device_id, nullptr, &ctx); });
-        // Contigs are processed in ascending tid order (api/coverage.rs:229-234).  With an index and more
-        // than one contig, the records and reference bases of contig i+1 are read by a second reader on
-        // its own thread while contig i is admitted, pushed, run and written (DUT_PIPELINE=0: off).
-        struct Slot { dut_bam *bam = nullptr; dut_fasta *fa = nullptr; dut_records rec; const uint8_t *bases = nullptr; uint64_t blen = 0; int rc = CL_OK, frc = CL_OK; };
-        Slot slot[2];
-        slot[0].bam = bam; slot[0].fa = fa;
-        const char *pe = getenv("DUT_PIPELINE");
-        bool pipeline = tids.size() > 1 && dut_bam_has_index(bam) && !(pe && *pe == '0');
-        if (pipeline) {
-            slot[1].bam = dut_bam_open(bam_path, e, sizeof(e));
-            slot[1].fa = slot[1].bam ? dut_fasta_open(fasta_path, e, sizeof(e)) : nullptr;
-            if (!slot[1].bam || !slot[1].fa) {                 // e.g. out of file handles: read in line instead
-                if (slot[1].bam) dut_bam_close(slot[1].bam);
-                slot[1].bam = nullptr; pipeline = false;
-            }
-        }
-        auto fetch = [&](Slot &s, int t) {
-            // the reference bases (one thread: read + strip the line ends) beside the record decode (all threads)
-            s.bases = nullptr; s.blen = 0;
-            // (a zero-length contig fetches nothing: the reference's loops over it run zero times, mod.rs:65-147, so a
-            // FASTA that lacks such an @SQ is not an error)
-            s.frc = CL_OK;
-            dut::Thread fb;
-            if (dut_bam_ref_len(s.bam, t) > 0)
-                fb = dut::spawn_or_run([&]() { s.frc = dut_fasta_fetch(s.fa, dut_bam_ref_name(s.bam, t), &s.bases, &s.blen); });
-            s.rc = use_bits ? dut_bam_read_contig_bits(s.bam, t, opt->min_base_quality, &s.rec) : dut_bam_read_contig(s.bam, t, &s.rec, nullptr, nullptr);
-            if (fb.joinable()) fb.join();
-        };
-        dut::Thread ahead;
-        io_stage_time("(before contigs)", tm);
-        if (!tids.empty()) fetch(slot[0], tids[0]);
-        if (init.joinable()) init.join();
-        if (rc != CL_OK) set_err(err, err_len, "no usable HIP device (the engine has no CPU fallback)");
-        else {
-            prof = dut_profiler_new(bed_path);
-            if (!prof) { set_err(err, err_len, std::string("Failed to create CallableProfiler: cannot create ") + bed_path); rc = CL_ERR_INVALID; }
-            else {
-                uint32_t largest = 0;                       // api/coverage.rs:210-215: the longest selected contig but chrM
-                for (int t : tids) if (strcmp(dut_bam_ref_name(bam, t), "chrM") != 0) largest = std::max(largest, dut_bam_ref_len(bam, t));
-                dut_profiler_enable_plots(prof, largest);
-            }
-        }
-        for (size_t i = 0; rc == CL_OK && i < tids.size(); ++i) {
-            const int t = tids[i];
-            Slot &cur = pipeline ? slot[i & 1] : slot[0];
-            if (i > 0 && !pipeline) fetch(cur, t);
-            io_stage_time(pipeline && i > 0 ? "wait for the read-ahead" : "BAM read + decode, FASTA fetch", tm);
-            if (pipeline && i + 1 < tids.size()) { Slot &nx = slot[(i + 1) & 1]; const int tn = tids[i + 1]; ahead = dut::spawn_or_run([&fetch, &nx, tn]() { fetch(nx, tn); }); }
-            if (cur.rc != CL_OK) { set_err(err, err_len, std::string("Error processing contig: ") + dut_bam_error(cur.bam)); rc = cur.rc; }
-            else if (cur.frc != CL_OK) { set_err(err, err_len, std::string("Error processing contig: ") + dut_fasta_error(cur.fa)); rc = cur.frc; }   // fetch_seq(..)?, mod.rs:79
-            dut_contig_stats st;
-            memset(&st, 0, sizeof(st));
-            if (rc == CL_OK) {
-                rc = dut_process_single_contig(ctx, prof, &st, opt, dut_bam_ref_name(bam, t), t, dut_bam_ref_len(bam, t), cur.bases, cur.blen, &cur.rec);
-                if (rc != CL_OK) {
-                    const char *m = cl_last_error(ctx);
-                    set_err(err, err_len, std::string("Error processing contig: ") + ((m && *m) ? m : (rc == CL_ERR_UNSORTED ? "the input is not sorted" : "failed")));
-                }
-            }
-            if (ahead.joinable()) ahead.join();
-            if (rc != CL_OK) break;
-            uint64_t c6[6];
-            dut_profiler_contig_counts(prof, dut_bam_ref_name(bam, t), c6);
-            stats.push_back(st); names.push_back(dut_bam_ref_name(bam, t)); counts.push_back(std::vector<uint64_t>(c6, c6 + 6));
-        }
-        if (slot[1].bam) { dut_fasta_close(slot[1].fa); dut_bam_close(slot[1].bam); }
-        if (rc != CL_OK) goto out;
-    }
-    if (summary_json || summary_html) {
-        std::vector<const char *> nm;
-        std::vector<uint64_t> c6;
-        for (size_t i = 0; i < stats.size(); ++i) { nm.push_back(names[i].c_str()); c6.insert(c6.end(), counts[i].begin(), counts[i].end()); }
-        // collect_coverage_plots (api/coverage.rs:263-274): the figures that exist relative to the working directory
-        // (they are written beside the BED file); listed in tid order here, in HashMap order there
-        std::vector<std::string> plots;
-        for (size_t i = 0; i < stats.size(); ++i) {
-            const std::string pth = names[i] + "_coverage.svg";
-            if (FILE *pf = fopen(pth.c_str(), "rb")) { fclose(pf); plots.push_back(pth); }
-        }
-        std::vector<const char *> plot_ptrs;
-        for (const std::string &q : plots) plot_ptrs.push_back(q.c_str());
-        dut_export_meta meta;
-        memset(&meta, 0, sizeof(meta));
-        meta.aligner = dut_bam_stats_aligner(bstats);
-        meta.reference_build = dut_bam_stats_reference_build(bstats);
-        meta.sequencing_platform = dut_bam_stats_infer_platform(bstats);
-        meta.read_length = dut_bam_stats_average_read_length(bstats);
-        meta.bed_file = bed_path;
-        meta.summary_html = summary_html ? summary_html : "summary.html";
-        meta.coverage_plots = plot_ptrs.data(); meta.n_coverage_plots = plot_ptrs.size();
-        if (summary_html) {                                   // api/coverage.rs:104
-            rc = dut_write_html_report(stats.data(), nm.data(), c6.data(), stats.size(), &meta, 10000, summary_html);
-            if (rc != CL_OK) { set_err(err, err_len, std::string("cannot create ") + summary_html); goto out; }
-        }
-    if (summary_json) {
-        // CoverageOutput as main.rs:68-69 serialises it
-        char *js = nullptr; size_t jl = 0;
-        rc = dut_coverage_output_json(stats.data(), nm.data(), c6.data(), stats.size(), &meta, &js, &jl);
-        if (rc != CL_OK) { set_err(err, err_len, "cannot build the summary"); goto out; }
-        FILE *jf = fopen(summary_json, "wb");
-        if (!jf) { dut_free(js); set_err(err, err_len, std::string("cannot create ") + summary_json); rc = CL_ERR_INVALID; goto out; }
-        fwrite(js, 1, jl, jf);
-        fclose(jf);
-        dut_free(js);
-    }
-    }
-out:
-    io_stage_time("(since the last decode) + summary", tm);
-    dut_bam_stats_free(bstats);
-    if (prof) dut_profiler_free(prof);
-    if (leave) {
-        // the caller is about to leave the process (DUT_FILES_LEAVE_TO_EXIT: the command line tool): every result is on
-        // disk; the device context, the readers and their decode buffers are left to the exit -- giving them back one by
-        // one costs a few hundred milliseconds of page-table and driver work that the exit does once, in one sweep
-        if (bam && bam->z.fp) { bam->st.drop_ahead(); fclose(bam->z.fp); bam->z.fp = nullptr; }
-        io_stage_time("left to the exit", tm);
-        return rc;
-    }
-    {
-        // giving the device memory back and unmapping the decode buffers take a few hundred ms at chr21 size: side by
-        // side, and both joined -- a library call leaves no thread behind
-        dut::Thread td = dut::spawn_or_run([&]() { if (ctx) cl_destroy(ctx); });
-        dut_fasta_close(fa);
-        if (bam) dut_bam_close(bam);
-        io_stage_time("readers closed", tm);
-        if (td.joinable()) td.join();
-    }
-    io_stage_time("engine destroyed", tm);
-    return rc;
-}
-
-extern "C" int dut_coverage_files(const char *bam_path, const char *fasta_path, const char *bed_path,
-                                  const char *summary_json, const char *summary_html, const cl_options *opt,
-                                  const char *const *contigs, size_t n_contigs, int device_id, char *err, size_t err_len)
-{
-    // no exception leaves the library through the C ABI
-    try { return dut_coverage_files_impl(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, &device_id, 1, 0u, err, err_len); }
-    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
-    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
-}
-
-extern "C" int dut_coverage_files_multi(const char *bam_path, const char *fasta_path, const char *bed_path,
-                                        const char *summary_json, const char *summary_html, const cl_options *opt,
-                                        const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
-                                        unsigned flags, char *err, size_t err_len)
-{
-    try { return dut_coverage_files_impl(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len); }
-    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
-    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
-}
-

@@ -21,9 +21,9 @@
 
 #include "../../include/dut_bam.h"
 #include "../../include/dut_fingerprint.h"
+#include "host_parallel.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -297,9 +297,6 @@ __global__ __launch_bounds__(kBlock) void k_fp_hash(const uint8_t *__restrict__ 
 struct SumU32 {
     __host__ __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }   // u32 wraps as the reference's
 };
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-bool timing_on() { static const bool on = getenv("DUT_TIMING") && *getenv("DUT_TIMING") == '1'; return on; }
 
 } // namespace fp
 
@@ -741,7 +738,7 @@ int fp_files_impl(const char *input, const char *output, const dut_fp_options *o
     uint64_t cap = fp::kDefaultBatchBases;
     if (const char *e = getenv("DUT_FP_BATCH_BASES")) { const unsigned long long v = strtoull(e, nullptr, 10); if (v) cap = std::min<uint64_t>(v, fp::kMaxBatchBases); }
     auto read_batch = [&](Batch &b) {
-        const double t0 = fp::now_s();
+        const double t0 = dut::now_s();
         uint64_t n = 0; const uint64_t *off = nullptr; const uint8_t *d = nullptr;
         b.rc = seq4 ? dut_bam_next_seqs(bam, cap, &n, &off, &d) : dut_fastq_next(fq, cap, &n, &off, &d);
         b.n = 0;
@@ -752,7 +749,7 @@ int fp_files_impl(const char *input, const char *output, const dut_fp_options *o
             b.data.assign(d, d + bytes);
             if (b.data.empty()) b.data.push_back(0);
         }
-        b.decode_ms = (fp::now_s() - t0) * 1e3;
+        b.decode_ms = (dut::now_s() - t0) * 1e3;
     };
     auto close_readers = [&]() { if (bam) dut_bam_close(bam); if (fq) dut_fastq_close(fq); };
     dut_fp_ctx *ctx = nullptr;
@@ -760,17 +757,17 @@ int fp_files_impl(const char *input, const char *output, const dut_fp_options *o
     if (rc != CL_OK) { set(ctx ? dut_fp_last_error(ctx) : "cannot create the fingerprint context on the device"); close_readers(); return rc; }
     Batch cur, next;
     read_batch(cur);
-    const bool timing = fp::timing_on();
+    const bool timing = dut::timing_on();
     uint64_t bi = 0;
     while (rc == CL_OK) {
         if (cur.rc != CL_OK) { rc = cur.rc; set(std::string("reading ") + input + ": " + (bam ? dut_bam_error(bam) : "read failed")); break; }
         if (cur.n == 0) break;
         // decode of the next batch on a second thread while this one is hashed on the device
         std::thread th([&]() { read_batch(next); });
-        const double t0 = fp::now_s();
+        const double t0 = dut::now_s();
         double hash0 = ctx->hash_ms + ctx->reduce_ms + ctx->h2d_ms;
         rc = seq4 ? dut_fp_push_seq4(ctx, cur.data.data(), cur.off.data(), cur.n) : dut_fp_push_bytes(ctx, cur.data.data(), cur.off.data(), cur.n);
-        const double push_ms = (fp::now_s() - t0) * 1e3;
+        const double push_ms = (dut::now_s() - t0) * 1e3;
         th.join();
         if (timing)
             fprintf(stderr, "[dut-timing] fingerprint batch %llu: %llu sequences, host decode %.2f ms, device %.2f ms (push call %.2f ms)\n",

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -704,75 +705,68 @@ static int dut_find_branch_files_impl(const char *bam_path, const char *fasta_pa
 {
     if (!bam_path || !fasta_path || !tree_json_path || !output_path) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
     char e[512] = {0};
-    dut_fasta *fa = dut_fasta_open(fasta_path, e, sizeof(e));                 // mod.rs:28
+    std::unique_ptr<dut_fasta, decltype(&dut_fasta_close)> fa(dut_fasta_open(fasta_path, e, sizeof(e)), dut_fasta_close);   // mod.rs:28
     if (!fa) { set_err(err, err_len, e); return CL_ERR_INVALID; }
-    dut_bam *bam = dut_bam_open(bam_path, e, sizeof(e));                      // mod.rs:46 (IndexedReader)
-    if (!bam) { dut_fasta_close(fa); set_err(err, err_len, e); return CL_ERR_INVALID; }
-    int rc = CL_OK;
-    dut_tree *tree = nullptr;
-    cl_ctx *ctx = nullptr;
-    uint32_t *sites = nullptr; uint8_t *rel = nullptr; size_t n_sites = 0;
-    dut_snp_call *calls = nullptr; size_t n_calls = 0;
-    dut_haplogroup_result *res = nullptr; size_t n_res = 0;
-    char build[64] = {0}, chrom[256] = {0};
+    std::unique_ptr<dut_bam, decltype(&dut_bam_close)> bam(dut_bam_open(bam_path, e, sizeof(e)), dut_bam_close);           // mod.rs:46 (IndexedReader)
+    if (!bam) { set_err(err, err_len, e); return CL_ERR_INVALID; }
+    if (!dut_bam_has_index(bam.get())) { set_err(err, err_len, std::string("no .bai or .csi index beside ") + bam_path); return CL_ERR_INVALID; }
     std::vector<const char *> names;
-    std::vector<uint32_t> hist;
+    for (int t = 0; t < dut_bam_n_ref(bam.get()); ++t) names.push_back(dut_bam_ref_name(bam.get(), t));
+    char build[64] = {0}, chrom[256] = {0};
+    size_t tl = 0;
+    const char *text = dut_bam_header_text(bam.get(), &tl);
+    // the reference tests the header text *with* its @SQ lines (HeaderView::as_bytes)
+    int rc = dut_validate_reference(text, tl, names.data(), names.size(), tree_type, build, sizeof(build), chrom, sizeof(chrom), err, err_len);
+    if (rc != CL_OK) return rc;
     int tid = -1;
-    if (!dut_bam_has_index(bam)) { set_err(err, err_len, std::string("no .bai or .csi index beside ") + bam_path); rc = CL_ERR_INVALID; goto out; }
-    for (int t = 0; t < dut_bam_n_ref(bam); ++t) names.push_back(dut_bam_ref_name(bam, t));
-    {
-        size_t tl = 0;
-        const char *text = dut_bam_header_text(bam, &tl);
-        // the reference tests the header text *with* its @SQ lines (HeaderView::as_bytes)
-        rc = dut_validate_reference(text, tl, names.data(), names.size(), tree_type, build, sizeof(build), chrom, sizeof(chrom), err, err_len);
-        if (rc != CL_OK) goto out;
-    }
     for (size_t i = 0; i < names.size(); ++i) if (strcmp(names[i], chrom) == 0) { tid = (int)i; break; }
-    {
-        // Three independent pieces of work side by side: the tree JSON (one thread: parse + collect the sites),
-        // the HIP runtime + engine context (one thread), and the contig's records with their 4-bit sequences
-        // (this thread and the decode pool).  Errors are reported in the reference's order: tree, then BAM.
-        char terr[512] = {0};
-        int trc = CL_OK, crc = CL_OK;
-        cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};
-        dut::Thread tt = dut::spawn_or_run([&]() {
-            tree = dut_tree_load(tree_json_path, provider, tree_type, terr, sizeof(terr));
-            if (!tree) { trc = CL_ERR_INVALID; return; }
-            trc = dut_tree_collect_sites(tree, build, chrom, &sites, &rel, &n_sites);
-            if (trc != CL_OK) snprintf(terr, sizeof(terr), "collect_snps failed");
-        });
-        dut::Thread ct = dut::spawn_or_run([&]() { crc = cl_create(&opt, device_id, nullptr, &ctx); });
-        dut_records rec; const uint64_t *seq_off = nullptr; const uint8_t *seq4 = nullptr;
-        const int brc = dut_bam_read_contig(bam, tid, &rec, &seq_off, &seq4);
-        const uint8_t *bases = nullptr; uint64_t blen = 0;
-        const int frc = dut_fasta_fetch(fa, chrom, &bases, &blen);       // fetch_seq(..)?, caller.rs:110
-        if (tt.joinable()) tt.join();
-        if (ct.joinable()) ct.join();
-        if (frc != CL_OK) { set_err(err, err_len, dut_fasta_error(fa)); rc = frc; goto out; }
-        if (trc != CL_OK) { set_err(err, err_len, terr); rc = trc; goto out; }
-        if (brc != CL_OK) { set_err(err, err_len, dut_bam_error(bam)); rc = brc; goto out; }
-        if (crc != CL_OK) { set_err(err, err_len, "no usable HIP device (the engine has no CPU fallback)"); rc = crc; goto out; }
-        cl_site_tile tile;
-        tile.n_reads = rec.n; tile.pos = rec.pos; tile.mapq = rec.mapq; tile.cigar_off = rec.cigar_off; tile.cigar = rec.cigar;
-        tile.seq_off = seq_off; tile.seq4 = seq4;
-        hist.assign(std::max<size_t>(n_sites, 1) * 16, 0u);
-        if (n_sites) {
-            rc = cl_site_pileup(ctx, min_quality, dut_bam_ref_len(bam, tid), blen, &tile, sites, n_sites, hist.data());
-            if (rc != CL_OK) { const char *m = cl_last_error(ctx); set_err(err, err_len, (m && *m) ? m : "site pileup failed"); goto out; }
-        }
+    // Three independent pieces of work side by side: the tree JSON (one thread: parse + collect the sites),
+    // the HIP runtime + engine context (one thread), and the contig's records with their 4-bit sequences
+    // (this thread and the decode pool).  Errors are reported in the reference's order: tree, then BAM.
+    std::unique_ptr<dut_tree, decltype(&dut_tree_free)> tree(nullptr, dut_tree_free);
+    std::unique_ptr<cl_ctx, decltype(&cl_destroy)> ctx(nullptr, cl_destroy);
+    std::unique_ptr<uint32_t, decltype(&free)> sites(nullptr, free);
+    std::unique_ptr<uint8_t, decltype(&free)> rel(nullptr, free);
+    size_t n_sites = 0;
+    char terr[512] = {0};
+    int trc = CL_OK, crc = CL_OK;
+    cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};
+    dut::Thread tt = dut::spawn_or_run([&]() {
+        tree.reset(dut_tree_load(tree_json_path, provider, tree_type, terr, sizeof(terr)));
+        if (!tree) { trc = CL_ERR_INVALID; return; }
+        uint32_t *s = nullptr; uint8_t *r = nullptr;
+        trc = dut_tree_collect_sites(tree.get(), build, chrom, &s, &r, &n_sites);
+        sites.reset(s); rel.reset(r);
+        if (trc != CL_OK) snprintf(terr, sizeof(terr), "collect_snps failed");
+    });
+    dut::Thread ct = dut::spawn_or_run([&]() { cl_ctx *c = nullptr; crc = cl_create(&opt, device_id, nullptr, &c); ctx.reset(c); });
+    dut_records rec{}; const uint64_t *seq_off = nullptr; const uint8_t *seq4 = nullptr;
+    const int brc = dut_bam_read_contig(bam.get(), tid, &rec, &seq_off, &seq4);
+    const uint8_t *bases = nullptr; uint64_t blen = 0;
+    const int frc = dut_fasta_fetch(fa.get(), chrom, &bases, &blen);       // fetch_seq(..)?, caller.rs:110
+    if (tt.joinable()) tt.join();
+    if (ct.joinable()) ct.join();
+    if (frc != CL_OK) { set_err(err, err_len, dut_fasta_error(fa.get())); return frc; }
+    if (trc != CL_OK) { set_err(err, err_len, terr); return trc; }
+    if (brc != CL_OK) { set_err(err, err_len, dut_bam_error(bam.get())); return brc; }
+    if (crc != CL_OK) { set_err(err, err_len, "no usable HIP device (the engine has no CPU fallback)"); return crc; }
+    cl_site_tile tile;
+    tile.n_reads = rec.n; tile.pos = rec.pos; tile.mapq = rec.mapq; tile.cigar_off = rec.cigar_off; tile.cigar = rec.cigar;
+    tile.seq_off = seq_off; tile.seq4 = seq4;
+    std::vector<uint32_t> hist(std::max<size_t>(n_sites, 1) * 16, 0u);
+    if (n_sites) {
+        rc = cl_site_pileup(ctx.get(), min_quality, dut_bam_ref_len(bam.get(), tid), blen, &tile, sites.get(), n_sites, hist.data());
+        if (rc != CL_OK) { const char *m = cl_last_error(ctx.get()); set_err(err, err_len, (m && *m) ? m : "site pileup failed"); return rc; }
     }
-    rc = dut_call_sites(sites, rel, hist.data(), n_sites, min_depth, &calls, &n_calls);
-    if (rc != CL_OK) { set_err(err, err_len, "calling failed"); goto out; }
-    rc = dut_tree_score(tree, calls, n_calls, build, &res, &n_res, err, err_len);
-    if (rc != CL_OK) goto out;
-    rc = dut_write_haplogroup_report(output_path, tree, res, n_res, calls, n_calls, build, show_snps, err, err_len);
-out:
-    free(res); free(calls); free(sites); free(rel);
-    if (ctx) cl_destroy(ctx);
-    if (tree) dut_tree_free(tree);
-    dut_bam_close(bam);
-    dut_fasta_close(fa);
-    return rc;
+    dut_snp_call *calls_p = nullptr; size_t n_calls = 0;
+    rc = dut_call_sites(sites.get(), rel.get(), hist.data(), n_sites, min_depth, &calls_p, &n_calls);
+    std::unique_ptr<dut_snp_call, decltype(&free)> calls(calls_p, free);
+    if (rc != CL_OK) { set_err(err, err_len, "calling failed"); return rc; }
+    dut_haplogroup_result *res_p = nullptr; size_t n_res = 0;
+    rc = dut_tree_score(tree.get(), calls.get(), n_calls, build, &res_p, &n_res, err, err_len);
+    std::unique_ptr<dut_haplogroup_result, decltype(&free)> res(res_p, free);
+    if (rc != CL_OK) return rc;
+    return dut_write_haplogroup_report(output_path, tree.get(), res.get(), n_res, calls.get(), n_calls, build, show_snps, err, err_len);
 }
 
 int dut_find_branch_files(const char *bam_path, const char *fasta_path, const char *tree_json_path,

@@ -7,7 +7,6 @@
 
 #include <algorithm>
 #include <array>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -372,17 +371,6 @@ int dut_profiler_feed_contig(dut_profiler *p, const char *contig, const cl_inter
     return CL_OK;
 }
 
-// DUT_TIMING=1: wall-clock of the host stages on stderr (tooling; off by default)
-static double dut_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static bool dut_timing_on() { static const bool on = getenv("DUT_TIMING") && *getenv("DUT_TIMING") == '1'; return on; }
-static void dut_stage_time(const char *what, double &t0)
-{
-    if (!dut_timing_on()) return;
-    const double t1 = dut_now();
-    fprintf(stderr, "[dut-timing] %-28s %8.1f ms\n", what, (t1 - t0) * 1e3);
-    t0 = t1;
-}
-
 // 64-bit hashes of every record's name (not value-initialised: first touched by the threads that fill it)
 static dut::Scratch<uint64_t> hash_all_names(const dut_records *rec)
 {
@@ -404,7 +392,7 @@ static dut::Scratch<uint64_t> hash_all_names(const dut_records *rec)
 // array at random twice per insert.  Classes are counted in parallel and the counts add up.
 static uint32_t count_unique_names(const dut_records *rec, const uint8_t *accepted, uint64_t nacc, const uint64_t *h)
 {
-    double tm = dut_now();
+    double tm = dut::now_s();
     if (!rec->qname_off || !nacc) return 0;
     const int bits = nacc > (1u << 22) ? 12 : (nacc > (1u << 16) ? 8 : 0);
     const size_t kClasses = (size_t)1 << bits;
@@ -449,7 +437,7 @@ static uint32_t count_unique_names(const dut_records *rec, const uint8_t *accept
             ro[k] += 1; bo[k] += nl;
         }
     });
-    dut_stage_time("  names: partition", tm);
+    dut::stage_lap("  names: partition", tm);
     std::vector<uint64_t> per(kClasses, 0);
     dut::parallel_for(kClasses, 16, [&](size_t k) {
         const uint64_t a = rstart[k], b = rstart[k + 1];
@@ -479,7 +467,7 @@ static uint32_t count_unique_names(const dut_records *rec, const uint8_t *accept
     });
     uint64_t total = 0;
     for (uint64_t v : per) total += v;
-    dut_stage_time("  names: sets", tm);
+    dut::stage_lap("  names: sets", tm);
     return (uint32_t)total;
 }
 
@@ -510,12 +498,12 @@ static int dut_admit_reads_impl(const cl_options *opt, int32_t tid, uint32_t con
         ++cnt;
     };
     // reference spans of all reads up front, in parallel (the sequential rule below only compares numbers)
-    double tm = dut_now();
+    double tm = dut::now_s();
     // (not value-initialised: the pages are first touched by the threads that fill them)
     dut::Scratch<uint64_t> rlen_buf(rec->n ? rec->n : 1);
     uint64_t *rlen = rlen_buf.get();
     dut::parallel_for(rec->n, dut::grain_for(rec->n, 65536), [&](size_t i) { rlen[i] = ref_length(rec->cigar + rec->cigar_off[i], rec->cigar_off[i + 1] - rec->cigar_off[i]); });
-    dut_stage_time("  admit: spans", tm);
+    dut::stage_lap("  admit: spans", tm);
     bool any_pushed = false;
     int64_t cur_start = -1;
     uint64_t nacc = 0;
@@ -600,7 +588,7 @@ static int dut_admit_reads_impl(const cl_options *opt, int32_t tid, uint32_t con
         live_push(end);
         if (rl > 0) { accepted[i] = 1; ++nacc; }
     }
-    dut_stage_time("  admit: cap rule", tm);
+    dut::stage_lap("  admit: cap rule", tm);
     if (n_accepted) *n_accepted = nacc;
     if (n_unique_names) {
         const dut::Scratch<uint64_t> h = hash_all_names(rec);
@@ -628,10 +616,10 @@ int dut_process_single_contig(cl_ctx *ctx, dut_profiler *prof, dut_contig_stats 
     uint64_t counts[6]; const cl_interval *iv = nullptr; size_t niv = 0;
     int rc = dut_process_single_contig_runs(ctx, stats, opt, tid, contig_len, ref, ref_len, rec, counts, &iv, &niv);
     if (rc != CL_OK) return rc;
-    double tm = dut_now();
+    double tm = dut::now_s();
     rc = dut_profiler_feed_contig(prof, contig_name, iv, niv, counts);
     if (rc == CL_OK && dut_profiler_finish_plot(prof, contig_name, contig_len) < 0) rc = CL_ERR_INVALID;   // finish_contig, :67-84
-    dut_stage_time("BED lines", tm);
+    dut::stage_lap("BED lines", tm);
     return rc;
 }
 
@@ -640,7 +628,7 @@ static int dut_process_single_contig_runs_impl(cl_ctx *ctx, dut_contig_stats *st
                                    uint64_t state_counts[6], const cl_interval **intervals, size_t *n_intervals)
 {
     if (!ctx || !stats || !opt || !rec || !state_counts || !intervals || !n_intervals) return CL_ERR_INVALID;
-    double tm = dut_now();
+    double tm = dut::now_s();
     int rc = cl_contig_begin(ctx, tid, contig_len, ref, ref_len);
     if (rc != CL_OK) return rc;
     // Every early return below abandons the contig: a quality prefetch in flight still reads `rec->qual` and holds the
@@ -671,7 +659,7 @@ static int dut_process_single_contig_runs_impl(cl_ctx *ctx, dut_contig_stats *st
     dut::Thread hasher = dut::spawn_or_run([&]() { name_hash = hash_all_names(rec); hashed = true; });
     rc = dut_admit_reads(opt, tid, contig_len, rec, acc.data(), nullptr, &n_acc);
     if (rc != CL_OK) return rc;
-    dut_stage_time("admit", tm);
+    dut::stage_lap("admit", tm);
     // the distinct-name count is needed at the very end only: on its own thread beside the push, the kernels and the
     // read-back (joined before this function returns, also on every error path: dut::Thread joins in its destructor)
     bool names_done = false;
@@ -701,7 +689,7 @@ static int dut_process_single_contig_runs_impl(cl_ctx *ctx, dut_contig_stats *st
         });
         for (size_t c = 0; c < nchunk; ++c) { n_in += c_in[c]; in_order = in_order && c_ok[c]; }
     }
-    dut_stage_time("  push: order check", tm);
+    dut::stage_lap("  push: order check", tm);
     if (in_order && a0 < n_keep) {
         // the patched copy lives in a per-thread scratch buffer that is kept from contig to contig (a fresh,
         // zero-filled vector of a contig's 40 MB of CIGAR words cost more than the patching)
@@ -723,7 +711,7 @@ static int dut_process_single_contig_runs_impl(cl_ctx *ctx, dut_contig_stats *st
             });
             cig = patched.p;
         }
-        dut_stage_time("  push: patched CIGARs", tm);
+        dut::stage_lap("  push: patched CIGARs", tm);
         if (rec->pass_bits) {
             // the packed variant: the reader has taken the base-quality test (dut_bam_read_contig_bits)
             cl_read_tile_bits t;
@@ -779,14 +767,14 @@ static int dut_process_single_contig_runs_impl(cl_ctx *ctx, dut_contig_stats *st
             if (rc != CL_OK) return rc;
         }
     }
-    dut_stage_time("compact + push", tm);
+    dut::stage_lap("compact + push", tm);
     cl_contig_summary sum; const cl_interval *iv = nullptr; size_t niv = 0;
     rc = cl_contig_finish(ctx, &sum, &iv, &niv);
     if (rc != CL_OK) return rc;
-    dut_stage_time("upload + kernels + collect", tm);
+    dut::stage_lap("upload + kernels + collect", tm);
     if (names.joinable()) names.join();
     if (!names_done) return CL_ERR_NOMEM;
-    dut_stage_time("wait for the name count", tm);
+    dut::stage_lap("wait for the name count", tm);
     for (int i = 0; i < 6; ++i) state_counts[i] = sum.state_counts[i];
     *intervals = iv; *n_intervals = niv;
     stats->length = contig_len;

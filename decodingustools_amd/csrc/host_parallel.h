@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdlib>
@@ -334,6 +335,18 @@ struct ScratchPool {
     }
 };
 inline ScratchPool &scratch_pool() { static ScratchPool *p = new ScratchPool(); return *p; }   // (never destroyed: threads may outlive main)
+
+// DUT_TIMING=1: wall-clock of the host stages on stderr (tooling; off by default)
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+inline bool timing_on() { static const bool on = getenv("DUT_TIMING") && *getenv("DUT_TIMING") == '1'; return on; }
+// one line for the stage that ends now: the time since t0, which then moves on to now
+inline void stage_lap(const char *what, double &t0)
+{
+    if (!timing_on()) return;
+    const double t1 = now_s();
+    fprintf(stderr, "[dut-timing] %-28s %8.1f ms\n", what, (t1 - t0) * 1e3);
+    t0 = t1;
+}
 
 template <class T> class Scratch {
     T *p_ = nullptr;

@@ -205,7 +205,7 @@ int main(int argc, char **argv)
     for (int pass = 0; pass < 2; ++pass) {
         for (int k = 0; k < n_ref; ++k) {
             const int tid = pass ? n_ref - 1 - k : k;
-            dut_records rec; const uint64_t *so = nullptr; const uint8_t *sq = nullptr;
+            dut_records rec{}; const uint64_t *so = nullptr; const uint8_t *sq = nullptr;
             const int rc = dut_bam_read_contig(b, tid, &rec, pass ? &so : nullptr, pass ? &sq : nullptr);
             if (rc != CL_OK) { printf("tid %d: %s\n", tid, dut_bam_error(b)); continue; }
             unsigned long long h = checksum(rec.pos, rec.n * 4) ^ checksum(rec.qual, rec.qual_off[rec.n]) ^ checksum(rec.cigar, 4ull * rec.cigar_off[rec.n]) ^
@@ -214,7 +214,7 @@ int main(int argc, char **argv)
             {   // the packed variant of the same contig: its bits and sums against the bytes just read
                 const std::vector<uint8_t> q(rec.qual, rec.qual + rec.qual_off[rec.n]);
                 const std::vector<uint64_t> qo(rec.qual_off, rec.qual_off + rec.n + 1);
-                dut_records pr;
+                dut_records pr{};
                 const uint8_t thr = (uint8_t)(pass ? 20 : 0);
                 if (dut_bam_read_contig_bits(b, tid, thr, &pr) == CL_OK && pr.n == qo.size() - 1) {
                     unsigned long long wrong = pr.qual != nullptr;

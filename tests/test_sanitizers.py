@@ -13,7 +13,8 @@ from bamio import write_bam, write_fasta
 from decodingustools_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = [os.path.join(ROOT, "decodingustools_amd", "csrc", f) for f in ("bam_io.cpp", "host_coverage.cpp", "report.cpp", "haplogroup.cpp", "qual_pack.cpp")]
+SRC = [os.path.join(ROOT, "decodingustools_amd", "csrc", f) for f in ("bam_io.cpp", "coverage_files.cpp", "host_coverage.cpp", "report.cpp",
+                                                                           "haplogroup.cpp", "qual_pack.cpp")]
 DRIVER = os.path.join(ROOT, "tests", "native", "sanitize_host.cpp")
 
 
