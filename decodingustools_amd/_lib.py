@@ -114,8 +114,41 @@ class dut_fp_result(C.Structure):
 CL_K_NAMES = ("prep", "bounds", "pileup", "rle")
 CL_K_COUNT = 4
 
+class cl_depth_profile(C.Structure):
+    _fields_ = [("n_bins", C.c_uint32), ("window", C.c_uint32), ("n_windows", C.c_uint64), ("extent", C.c_uint64),
+                ("sum_raw", C.c_uint64), ("sum_qc", C.c_uint64),
+                ("hist_raw", C.POINTER(C.c_uint64)), ("hist_qc", C.POINTER(C.c_uint64)),
+                ("win_raw", C.POINTER(C.c_uint64)), ("win_qc", C.POINTER(C.c_uint64))]
+
+
+DEPTH_THRESHOLDS = (1, 5, 10, 15, 20, 30, 50, 100)
+
+
+class dut_depth_summary(C.Structure):
+    _fields_ = [("positions", C.c_uint64), ("mean", C.c_double), ("q1", C.c_uint32), ("median", C.c_uint32), ("q3", C.c_uint32),
+                ("q1_saturated", C.c_uint8), ("median_saturated", C.c_uint8), ("q3_saturated", C.c_uint8), ("reserved", C.c_uint8),
+                ("frac_at_least", C.c_double * len(DEPTH_THRESHOLDS))]
+
+
+class dut_depth_options(C.Structure):
+    _fields_ = [("n_bins", C.c_uint32), ("window", C.c_uint32), ("dist_path", C.c_char_p), ("windows_path", C.c_char_p),
+                ("summary_path", C.c_char_p)]
+
+
 # every symbol the headers declare: (name, restype, argtypes)
 SYMBOLS = [
+    ("cl_contig_depth_profile", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(cl_depth_profile)]),
+    ("cl_contig_depth_profile_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("dut_depth_stats", C.c_int, [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.POINTER(dut_depth_summary)]),
+    ("dut_depth_acc_new", C.c_void_p, [C.c_uint32, C.c_uint32, C.c_char_p]),
+    ("dut_depth_acc_free", None, [C.c_void_p]),
+    ("dut_depth_acc_add", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(cl_depth_profile)]),
+    ("dut_depth_acc_total", C.c_int, [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint64)),
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("dut_depth_acc_finish", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p]),
+    ("dut_coverage_files_ex", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                        C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
+                                        C.c_uint, C.POINTER(dut_depth_options), C.c_char_p, C.c_size_t]),
     ("cl_abi_version", C.c_int, []),
     ("cl_device_count", C.c_int, []),
     ("cl_create", C.c_int, [C.POINTER(cl_options), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -107,13 +107,16 @@ class FastaReader:
 
 def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callable_regions.bed",
                    summary_json: str = None, options: CallableOptions = None, contigs=None, device_id: int = 0,
-                   output_summary: str = None, devices=None):
+                   output_summary: str = None, devices=None, depth_dist: str = None, depth_windows: str = None,
+                   depth_summary: str = None, depth_cap: int = 1000, window: int = 0):
     """CoverageAnalyzer::analyze on files (CoverageInput of api/coverage.rs:124-132); summary_json
     receives the CoverageOutput JSON of main.rs:68-69; output_summary, when given, the HTML report
     (api/coverage.rs:104; None: not written, the JSON then names "summary.html").  The per-contig coverage
     figures `<contig>_coverage.svg` go beside the BED file (callable_profiler.rs:80-84).
     devices: a list of HIP ordinals (one may repeat) -- the contigs are dealt to them inside the library
-    (dut_coverage_files_multi: one host thread and one engine context per entry, no torch, no collective)."""
+    (dut_coverage_files_multi: one host thread and one engine context per entry, no torch, no collective).
+    depth_dist / depth_windows (with window >= 16) / depth_summary: the depth profile files of dut_coverage_files_ex
+    (formats: include/dut_coverage.h); depth_cap: depths above it share the last histogram bin."""
     lib = _lib.load()
     options = options or CallableOptions()
     oc = options.to_c()
@@ -123,7 +126,14 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
         n = len(contigs)
         arr = (C.c_char_p * max(n, 1))(*[c.encode() for c in contigs])
     err = C.create_string_buffer(1024)
-    if devices is not None:
+    if depth_dist or depth_windows or depth_summary:
+        dlist = [int(d) for d in devices] if devices is not None else [int(device_id)]
+        dv = (C.c_int * len(dlist))(*dlist)
+        enc = lambda p: p.encode() if p else None          # noqa: E731
+        do = _lib.dut_depth_options(int(depth_cap) + 1, int(window), enc(depth_dist), enc(depth_windows), enc(depth_summary))
+        st = lib.dut_coverage_files_ex(bam_file.encode(), reference_file.encode(), output_bed.encode(), enc(summary_json),
+                                       enc(output_summary), C.byref(oc), arr, n, dv, len(dlist), 0, C.byref(do), err, 1024)
+    elif devices is not None:
         dv = (C.c_int * len(devices))(*[int(d) for d in devices])
         st = lib.dut_coverage_files_multi(bam_file.encode(), reference_file.encode(), output_bed.encode(),
                                           summary_json.encode() if summary_json else None, output_summary.encode() if output_summary else None,

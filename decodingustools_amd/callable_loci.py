@@ -237,6 +237,108 @@ class Engine:
         self._check(self._lib.cl_site_pileup_stats(self._h, C.byref(ms), C.byref(b)))
         return ms.value, b.value
 
+    def depth_profile(self, n_bins=1001, window=0):
+        """The depth distribution of the resident contig, reduced on the device (cl_contig_depth_profile): a
+        DepthProfile of numpy uint64 arrays (copies).  window = 0: no window table."""
+        p = _lib.cl_depth_profile()
+        self._check(self._lib.cl_contig_depth_profile(self._h, int(n_bins), int(window), C.byref(p)))
+
+        def arr(ptr, n):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n and ptr else np.zeros(0, np.uint64)
+        nw = int(p.n_windows)
+        ms = C.c_double()
+        self._check(self._lib.cl_contig_depth_profile_ms(self._h, C.byref(ms)))
+        return DepthProfile(n_bins=int(p.n_bins), window=int(p.window), n_windows=nw, extent=int(p.extent),
+                            sum_raw=int(p.sum_raw), sum_qc=int(p.sum_qc), hist_raw=arr(p.hist_raw, int(p.n_bins)),
+                            hist_qc=arr(p.hist_qc, int(p.n_bins)), win_raw=arr(p.win_raw, nw) if window else None,
+                            win_qc=arr(p.win_qc, nw) if window else None, kernel_ms=float(ms.value))
+
+
+@dataclass
+class DepthProfile:
+    """cl_depth_profile (include/callable_loci.h): hist_*[b] = positions with min(depth, n_bins - 1) == b, the exact
+    sums, and per window of `window` positions the sum of the depths (None without a window)."""
+    n_bins: int
+    window: int
+    n_windows: int
+    extent: int
+    sum_raw: int
+    sum_qc: int
+    hist_raw: np.ndarray
+    hist_qc: np.ndarray
+    win_raw: Optional[np.ndarray]
+    win_qc: Optional[np.ndarray]
+    kernel_ms: float = 0.0          # cl_contig_depth_profile_ms: the kernel by device events while profiling is on
+
+    def _c(self):
+        p = _lib.cl_depth_profile()
+        p.n_bins, p.window, p.n_windows, p.extent = self.n_bins, self.window, self.n_windows, self.extent
+        p.sum_raw, p.sum_qc = self.sum_raw, self.sum_qc
+        keep = [np.ascontiguousarray(a, np.uint64) if a is not None else None
+                for a in (self.hist_raw, self.hist_qc, self.win_raw, self.win_qc)]
+        u64p = C.POINTER(C.c_uint64)
+        p.hist_raw, p.hist_qc, p.win_raw, p.win_qc = [k.ctypes.data_as(u64p) if k is not None and k.size else u64p() for k in keep]
+        # (an empty histogram still needs a pointer: n_bins >= 2 always; only the window tables may be empty)
+        return p, keep
+
+
+def depth_stats(hist, total):
+    """dut_depth_stats: positions, mean, quartiles (value, saturated) and the share of positions at or above
+    1, 5, 10, 15, 20, 30, 50, 100 (None where the histogram's last exact bin lies below the threshold)."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    out = _lib.dut_depth_summary()
+    st = _lib.load().dut_depth_stats(h.ctypes.data_as(C.POINTER(C.c_uint64)), h.shape[0], int(total), C.byref(out))
+    if st != 0:
+        raise EngineError(st, "dut_depth_stats: a histogram needs at least two bins")
+    return {"positions": int(out.positions), "mean": float(out.mean),
+            "q1": (int(out.q1), bool(out.q1_saturated)), "median": (int(out.median), bool(out.median_saturated)),
+            "q3": (int(out.q3), bool(out.q3_saturated)),
+            "frac_at_least": {t: (None if out.frac_at_least[k] < 0 else float(out.frac_at_least[k]))
+                              for k, t in enumerate(_lib.DEPTH_THRESHOLDS)}}
+
+
+class DepthAccumulator:
+    """dut_depth_acc: adds contigs' depth profiles (in output order) into a total and writes the distribution,
+    window and summary files (formats: include/dut_coverage.h)."""
+
+    def __init__(self, n_bins, window=0, windows_path=None):
+        self._lib = _lib.load()
+        self.n_bins = n_bins
+        self._h = self._lib.dut_depth_acc_new(n_bins, window, windows_path.encode() if windows_path else None)
+        if not self._h:
+            raise EngineError(-1, "dut_depth_acc_new: bad bin count or window, or the window file cannot be created")
+
+    def add(self, contig, profile: DepthProfile):
+        p, keep = profile._c()
+        st = self._lib.dut_depth_acc_add(self._h, contig.encode(), C.byref(p))
+        del keep
+        if st != 0:
+            raise EngineError(st, "dut_depth_acc_add: the profile does not fit the accumulator")
+
+    def total(self):
+        hr, hq = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        sr, sq = C.c_uint64(), C.c_uint64()
+        self._lib.dut_depth_acc_total(self._h, C.byref(hr), C.byref(hq), C.byref(sr), C.byref(sq))
+        return (np.ctypeslib.as_array(hr, shape=(self.n_bins,)).copy(), np.ctypeslib.as_array(hq, shape=(self.n_bins,)).copy(),
+                int(sr.value), int(sq.value))
+
+    def finish(self, dist_path=None, summary_path=None):
+        st = self._lib.dut_depth_acc_finish(self._h, dist_path.encode() if dist_path else None,
+                                            summary_path.encode() if summary_path else None)
+        if st != 0:
+            raise EngineError(st, "dut_depth_acc_finish: cannot write the depth profile files")
+
+    def close(self):
+        if self._h:
+            self._lib.dut_depth_acc_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class HostStage(Engine):
     """A context WITHOUT a device (cl_debug_host_create), for the CPU test suite: contig_begin / push_reads stage a

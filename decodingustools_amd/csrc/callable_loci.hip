@@ -4,6 +4,7 @@
 // itself is in kernels.hip.h.  No CPU fallback exists: without a HIP device cl_create fails.
 #include "../../include/callable_loci.h"
 #include "kernels.hip.h"
+#include "depth_profile.hip.h"
 #include "host_parallel.h"
 #include "qual_pack.h"
 #include "pass_rows.h"
@@ -384,6 +385,11 @@ struct cl_ctx {
     DevBuf<DevSummary> d_summary;
     DevBuf<Interval> d_iv;
     DevBuf<uint32_t> d_dbg;          // 3 * n_win * T
+    // cl_contig_depth_profile: {sum_raw, sum_qc}, hist_raw, hist_qc, win_raw, win_qc -- on the device and as copied back
+    DevBuf<unsigned long long> d_prof;
+    std::vector<unsigned long long> h_prof;
+    hipEvent_t prof_ev[2] = {nullptr, nullptr};
+    double prof_ms = 0.0;            // the last profile's kernel by those events (while profiling is on)
 
     uint32_t n_reads = 0;
     uint64_t n_cigar = 0, n_qual = 0;
@@ -1446,8 +1452,9 @@ void cl_destroy(cl_ctx *c)
     c->d_wide_idx.release();
     c->d_runs.release(); c->d_first_state.release(); c->d_last_state.release(); c->d_win_wide.release();
     c->d_winpart.release(); c->d_lut.release(); c->d_summary.release();
-    c->d_iv.release(); c->d_dbg.release(); c->d_fin.release(); c->d_errflag.release(); c->d_runtab.release(); c->site.release();
+    c->d_iv.release(); c->d_dbg.release(); c->d_prof.release(); c->d_fin.release(); c->d_errflag.release(); c->d_runtab.release(); c->site.release();
     for (int i = 0; i < 2; ++i) if (c->site_ev[i]) (void)hipEventDestroy(c->site_ev[i]);
+    for (int i = 0; i < 2; ++i) if (c->prof_ev[i]) (void)hipEventDestroy(c->prof_ev[i]);
     if (c->ev_made)
         for (int s = 0; s < cl_ctx::kEvSets; ++s)
             for (int i = 0; i <= CL_K_COUNT; ++i) (void)hipEventDestroy(c->ev[s][i]);
@@ -2573,6 +2580,74 @@ cl_status cl_debug_depths(cl_ctx *c, uint32_t *raw, uint32_t *qc, uint32_t *low,
     catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
 }
 
+
+// The depth distribution of the resident contig (include/callable_loci.h): one extra launch of k_depth_profile over the
+// residents of the last run, a few KB back.  Nothing of a run is touched: summary, intervals and window partials stay.
+static cl_status cl_contig_depth_profile_impl(cl_ctx *c, uint32_t n_bins, uint32_t window, cl_depth_profile *out)
+{
+    if (!c) return CL_ERR_INVALID;
+    if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: null result");
+    memset(out, 0, sizeof(*out));
+    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
+    if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
+    if (n_bins < CL_DEPTH_MIN_BINS || n_bins > CL_DEPTH_MAX_BINS) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: n_bins outside [2, 4096]");
+    if (window != 0 && window < CL_DEPTH_MIN_WINDOW) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: a window of 1 to 15 positions (0 = no window table, else at least 16)");
+    if (!c->uploaded || !c->ran || c->form != 3) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile needs a contig that has been run");
+    if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t n_windows = window ? ((uint64_t)c->extent + window - 1) / window : 0;
+    const size_t n_words = 2 + 2 * (size_t)n_bins + 2 * (size_t)n_windows;
+    HIP_TRY(c, c->d_prof.reserve(n_words));
+    c->h_prof.assign(n_words, 0ull);
+    HIP_TRY(c, hipMemsetAsync(c->d_prof.p, 0, n_words * sizeof(unsigned long long), c->stream));
+    if (c->profiling && !c->prof_ev[0]) for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventCreate(&c->prof_ev[i]));
+    if (c->n_win) {
+        DepthArgs a;
+        a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
+        a.extent = c->extent; a.n_win = c->n_win; a.n_bins = n_bins; a.window = window;
+        a.sums = c->d_prof.p; a.hist = c->d_prof.p + 2; a.wins = c->d_prof.p + 2 + 2 * (size_t)n_bins; a.n_windows = n_windows;
+        const size_t lds = 2u * (size_t)n_bins * sizeof(uint32_t);
+        // workgroups that stay: a histogram is flushed once per workgroup
+        const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
+        if (c->profiling) HIP_TRY(c, hipEventRecord(c->prof_ev[0], c->stream));
+        if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_profile<8>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
+        else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_profile<16>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
+        else hipLaunchKernelGGL((k_depth_profile<32>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+        if (c->profiling) HIP_TRY(c, hipEventRecord(c->prof_ev[1], c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_prof.data(), c->d_prof.p, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->prof_ms = 0.0;
+    if (c->profiling && c->n_win) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->prof_ev[0], c->prof_ev[1]));
+        c->prof_ms = ms;
+    }
+    // (no window of the engine: every position of [0, extent) -- there is none -- is in bin 0)
+    const uint64_t *h = reinterpret_cast<const uint64_t *>(c->h_prof.data());
+    out->n_bins = n_bins; out->window = window; out->n_windows = n_windows; out->extent = c->extent;
+    out->sum_raw = h[0]; out->sum_qc = h[1];
+    out->hist_raw = h + 2; out->hist_qc = h + 2 + n_bins;
+    out->win_raw = window ? h + 2 + 2 * (size_t)n_bins : nullptr;
+    out->win_qc = window ? h + 2 + 2 * (size_t)n_bins + n_windows : nullptr;
+    return CL_OK;
+}
+
+cl_status cl_contig_depth_profile_ms(cl_ctx *c, double *kernel_ms)
+{
+    if (!c || !kernel_ms) return CL_ERR_INVALID;
+    *kernel_ms = c->prof_ms;
+    return CL_OK;
+}
+
+cl_status cl_contig_depth_profile(cl_ctx *c, uint32_t n_bins, uint32_t window, cl_depth_profile *out)
+{
+    // no exception leaves the library through the C ABI
+    try { return cl_contig_depth_profile_impl(c, n_bins, window, out); }
+    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
+    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+}
 
 // the site list as the kernel wants it: sorted by 0-based position (vcf_pos - 1, caller.rs:94) with the original
 // indices, vcf_pos 0 left out (it can never match), and the first sorted site at or after every 256th position

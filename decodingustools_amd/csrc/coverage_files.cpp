@@ -4,6 +4,7 @@
 // per-contig work host_coverage.cpp's and the device engine's.
 #include "../../include/dut_bam.h"
 #include "../../include/dut_report.h"
+#include "coverage_hook.h"
 #include "host_parallel.h"
 
 #include <algorithm>
@@ -67,7 +68,7 @@ struct Result { dut_contig_stats st{}; uint64_t counts[6] = {0}; const cl_interv
 
 int coverage_files(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
                    const char *summary_html, const cl_options *opt, const char *const *contigs, size_t n_contigs,
-                   const int *devices, size_t n_devices, unsigned flags, char *err, size_t err_len)
+                   const int *devices, size_t n_devices, unsigned flags, char *err, size_t err_len, const dut::ContigHook *hook)
 {
     if (!bam_path || !fasta_path || !bed_path || !opt || !devices || n_devices == 0) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
     const bool leave = (flags & DUT_FILES_LEAVE_TO_EXIT) != 0;
@@ -124,6 +125,7 @@ int coverage_files(const char *bam_path, const char *fasta_path, const char *bed
         uint64_t c6[6];
         dut_profiler_contig_counts(prof.get(), nm, c6);
         stats.push_back(r.st); names.push_back(nm); counts.insert(counts.end(), c6, c6 + 6);
+        if (hook && hook->deliver) return hook->deliver(hook->user, i, nm);   // (what `resident` took of it: in tid order too)
         return CL_OK;
     };
     // a contig's records beside its reference bases (one thread: read + strip the line ends); a zero-length contig
@@ -172,6 +174,8 @@ int coverage_files(const char *bam_path, const char *fasta_path, const char *bed
             if (cur.frc != CL_OK) return {cur.frc, std::string("Error processing contig: ") + dut_fasta_error(cur.f)};   // fetch_seq(..)?, mod.rs:79
             Result r;
             int rc = dut_process_single_contig_runs(ctx[d].get(), &r.st, opt, t, dut_bam_ref_len(b.get(), t), cur.bases, cur.blen, &cur.rec, r.counts, &r.iv, &r.n_iv);
+            // (the contig is still resident: what else a caller wants of it is taken here, on the device's thread)
+            if (rc == CL_OK && hook && hook->resident) rc = hook->resident(hook->user, ctx[d].get(), i);
             if (rc == CL_OK) rc = put(i, r);
             if (rc != CL_OK) {
                 const char *m = cl_last_error(ctx[d].get());
@@ -240,7 +244,8 @@ int coverage_files(const char *bam_path, const char *fasta_path, const char *bed
 
     int rc = s.rc;
     if (rc != CL_OK) set_err(err, err_len, s.msg);
-    else if (summary_json || summary_html) {
+    else if (hook && hook->finish && (rc = hook->finish(hook->user)) != CL_OK) set_err(err, err_len, "cannot write the depth profile files");
+    if (rc == CL_OK && (summary_json || summary_html)) {
         // collect_coverage_plots (api/coverage.rs:263-274): the figures that exist relative to the working directory
         // (they are written beside the BED file); listed in tid order here, in HashMap order there
         std::vector<std::string> plots;
@@ -299,6 +304,16 @@ int coverage_files(const char *bam_path, const char *fasta_path, const char *bed
 
 } // namespace
 
+int dut::coverage_files_hooked(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
+                               const char *summary_html, const cl_options *opt, const char *const *contigs, size_t n_contigs,
+                               const int *devices, size_t n_devices, unsigned flags, char *err, size_t err_len, const ContigHook *hook)
+{
+    // no exception leaves the library through the C ABI
+    try { return coverage_files(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len, hook); }
+    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
+    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+}
+
 extern "C" int dut_coverage_files(const char *bam_path, const char *fasta_path, const char *bed_path,
                                   const char *summary_json, const char *summary_html, const cl_options *opt,
                                   const char *const *contigs, size_t n_contigs, int device_id, char *err, size_t err_len)
@@ -311,8 +326,5 @@ extern "C" int dut_coverage_files_multi(const char *bam_path, const char *fasta_
                                         const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
                                         unsigned flags, char *err, size_t err_len)
 {
-    // no exception leaves the library through the C ABI
-    try { return coverage_files(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len); }
-    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
-    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+    return dut::coverage_files_hooked(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len, nullptr);
 }

@@ -1,0 +1,25 @@
+// coverage_hook.h -- the seam between the file-level coverage driver (coverage_files.cpp) and what a caller wants of a
+// contig beyond its runs, while it is resident on the device (depth_files.cpp: the depth profile).  The driver itself
+// calls nothing of the engine that its existing entry points did not call; they pass no hook.
+#pragma once
+#include "../../include/dut_bam.h"
+
+namespace dut {
+
+struct ContigHook {
+    // on the device's host thread, right after selected contig i (index in tid order) has been run and collected on ctx
+    // and before the next contig replaces it.  A negative cl_status ends the analysis (message: cl_last_error(ctx)).
+    int (*resident)(void *user, cl_ctx *ctx, size_t i);
+    // on the calling thread, in tid order, after contig i's BED lines are written (one device or several)
+    int (*deliver)(void *user, size_t i, const char *contig_name);
+    // once, after the last contig of a run without error, before the summaries are written and the outputs are closed
+    int (*finish)(void *user);
+    void *user;
+};
+
+// dut_coverage_files_multi with a hook (null: exactly that call)
+int coverage_files_hooked(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
+                          const char *summary_html, const cl_options *opt, const char *const *contigs, size_t n_contigs,
+                          const int *devices, size_t n_devices, unsigned flags, char *err, size_t err_len, const ContigHook *hook);
+
+} // namespace dut

@@ -26,6 +26,9 @@ static void usage()
             "       [-L <CONTIG>]... [--min-depth 4] [--max-depth 500] [--min-mapping-quality 10]\n"
             "       [--min-base-quality 20] [--min-depth-for-low-mapq 10] [--max-low-mapq 1]\n"
             "       [--max-low-mapq-fraction 0.1] [--device 0 | --devices 0,1,...]\n"
+            "       [--depth-dist FILE] [--depth-windows FILE --window S] [--depth-summary FILE] [--depth-cap 1000]\n"
+            "         depth profile per contig and in total: histogram of raw / quality-filtered depth (depths above the cap in\n"
+            "         one last bin, cap 1..4095), mean depth per window of S >= 16 positions, quartiles and share at >= Nx\n"
             "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n");
 }
 
@@ -169,6 +172,17 @@ int main(int argc, char **argv)
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;
     std::vector<int> devices;
+    std::string depth_dist, depth_windows, depth_summary;
+    unsigned long long depth_cap = 1000, depth_window = 0;
+    bool has_window = false;
+    // a whole non-negative number, or exit 2 with a message (before any device is opened)
+    auto number = [](const char *flag, const char *v) -> unsigned long long {
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long x = (*v && *v != '-') ? strtoull(v, &end, 10) : 0ull;
+        if (!*v || *v == '-' || errno || *end) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v, flag); exit(2); }
+        return x;
+    };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         std::string val;
@@ -192,6 +206,11 @@ int main(int argc, char **argv)
         else if (a == "--min-depth-for-low-mapq") opt.min_depth_for_low_mapq = (uint32_t)strtoul(next(), nullptr, 10);
         else if (a == "--max-low-mapq") opt.max_low_mapq = (uint8_t)strtoul(next(), nullptr, 10);
         else if (a == "--max-low-mapq-fraction") opt.max_low_mapq_fraction = strtod(next(), nullptr);
+        else if (a == "--depth-dist") depth_dist = next();
+        else if (a == "--depth-windows") depth_windows = next();
+        else if (a == "--depth-summary") depth_summary = next();
+        else if (a == "--depth-cap") depth_cap = number("--depth-cap", next());
+        else if (a == "--window") { depth_window = number("--window", next()); has_window = true; }
         else if (a == "--device") devices.assign(1, atoi(next()));
         else if (a == "--devices") {
             // the contigs are dealt to these devices (HIP ordinals, comma separated; an ordinal may repeat)
@@ -209,6 +228,13 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage(); return 2; }
     }
     if (bam.empty() || ref.empty()) { usage(); return 2; }
+    // the depth profile's arguments, checked before a device is opened
+    if (depth_cap < 1 || depth_cap > CL_DEPTH_MAX_BINS - 1) { fprintf(stderr, "error: invalid value '%llu' for '--depth-cap': 1..%u\n", depth_cap, CL_DEPTH_MAX_BINS - 1); return 2; }
+    if (has_window && (depth_window < CL_DEPTH_MIN_WINDOW || depth_window > 0xFFFFFFFFull)) { fprintf(stderr, "error: invalid value '%llu' for '--window': at least %u positions\n", depth_window, CL_DEPTH_MIN_WINDOW); return 2; }
+    if (!depth_windows.empty() && !has_window) { fprintf(stderr, "error: '--depth-windows' needs '--window <S>' (S >= %u)\n", CL_DEPTH_MIN_WINDOW); return 2; }
+    if (has_window && depth_windows.empty()) { fprintf(stderr, "error: '--window' needs '--depth-windows <FILE>'\n"); return 2; }
+    dut_depth_options depth = {(uint32_t)depth_cap + 1u, (uint32_t)depth_window, depth_dist.empty() ? nullptr : depth_dist.c_str(),
+                               depth_windows.empty() ? nullptr : depth_windows.c_str(), depth_summary.empty() ? nullptr : depth_summary.c_str()};
     if (devices.empty()) devices.push_back(0);
     // The analysis runs in a child process and this one returns as soon as the child reports that every output file is
     // written and closed: what is left then -- the kernel taking a few gigabytes of decode buffers, the pinned staging
@@ -251,9 +277,9 @@ int main(int argc, char **argv)
     // the exit (DUT_CLI_TEARDOWN=1: given back piece by piece first, as a library caller's process would)
     const char *td = getenv("DUT_CLI_TEARDOWN");
     const unsigned flags = (td && *td == '1') ? 0u : DUT_FILES_LEAVE_TO_EXIT;
-    const int rc = dut_coverage_files_multi(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
-                                            contigs.empty() ? nullptr : contigs.data(), contigs.size(), devices.data(), devices.size(),
-                                            flags, err, sizeof(err));
+    const int rc = dut_coverage_files_ex(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
+                                         contigs.empty() ? nullptr : contigs.data(), contigs.size(), devices.data(), devices.size(),
+                                         flags, &depth, err, sizeof(err));
     if (rc != CL_OK) { fprintf(stderr, "Error: Analysis error: %s\n", err); leave(1); }
     // every output file is written and closed: leave without the HIP runtime's exit handlers
     stamp("exit");

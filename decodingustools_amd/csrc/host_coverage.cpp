@@ -878,4 +878,156 @@ void dut_genome_summary_build(const dut_contig_stats *stats, const uint64_t *cal
     out->contigs_analyzed = n;
 }
 
+
+// ---- depth profile: statistics, accumulator and writers (include/dut_coverage.h) ----
+const uint32_t dut_depth_thresholds[DUT_DEPTH_N_THRESHOLDS] = {1, 5, 10, 15, 20, 30, 50, 100};
+
+int dut_depth_stats(const uint64_t *hist, uint32_t n_bins, uint64_t sum, dut_depth_summary *out)
+{
+    if (!hist || !out || n_bins < 2) return CL_ERR_INVALID;
+    memset(out, 0, sizeof(*out));
+    uint64_t n = 0;
+    for (uint32_t b = 0; b < n_bins; ++b) n += hist[b];
+    out->positions = n;
+    out->mean = n ? (double)sum / (double)n : 0.0;
+    // smallest d whose cumulative count reaches ceil(k / 4 x positions)
+    uint32_t *const q[3] = {&out->q1, &out->median, &out->q3};
+    uint8_t *const qs[3] = {&out->q1_saturated, &out->median_saturated, &out->q3_saturated};
+    for (int k = 1; k <= 3; ++k) {
+        const unsigned __int128 t = ((unsigned __int128)n * (unsigned)k + 3u) / 4u;
+        unsigned __int128 cum = 0;
+        uint32_t d = 0;
+        for (; d < n_bins; ++d) { cum += hist[d]; if (cum >= t) break; }
+        if (d >= n_bins) d = n_bins - 1;
+        *q[k - 1] = n ? d : 0u;
+        *qs[k - 1] = (n && d == n_bins - 1) ? 1 : 0;
+    }
+    for (int k = 0; k < DUT_DEPTH_N_THRESHOLDS; ++k) {
+        const uint32_t t = dut_depth_thresholds[k];
+        if (t > n_bins - 1) { out->frac_at_least[k] = -1.0; continue; }
+        uint64_t at = 0;
+        for (uint32_t b = t; b < n_bins; ++b) at += hist[b];
+        out->frac_at_least[k] = n ? (double)at / (double)n : 0.0;
+    }
+    return CL_OK;
+}
+
+struct dut_depth_acc {
+    uint32_t n_bins = 0, window = 0;
+    FILE *wf = nullptr;
+    struct Entry { std::string name; std::vector<uint64_t> raw, qc; uint64_t sum_raw = 0, sum_qc = 0; };
+    std::vector<Entry> contigs;
+    Entry total;
+};
+
+dut_depth_acc *dut_depth_acc_new(uint32_t n_bins, uint32_t window, const char *windows_path)
+{
+    if (n_bins < CL_DEPTH_MIN_BINS || n_bins > CL_DEPTH_MAX_BINS || (window != 0 && window < CL_DEPTH_MIN_WINDOW)) return nullptr;
+    try {
+        std::unique_ptr<dut_depth_acc> a(new dut_depth_acc);
+        a->n_bins = n_bins; a->window = window;
+        a->total.name = "total"; a->total.raw.assign(n_bins, 0); a->total.qc.assign(n_bins, 0);
+        if (windows_path) {
+            if (window == 0) return nullptr;
+            a->wf = fopen(windows_path, "wb");
+            if (!a->wf) return nullptr;
+            fputs("#contig\tstart\tend\tmean_raw\tmean_qc\n", a->wf);
+        }
+        return a.release();
+    } catch (...) { return nullptr; }
+}
+
+void dut_depth_acc_free(dut_depth_acc *a)
+{
+    if (!a) return;
+    if (a->wf) fclose(a->wf);
+    delete a;
+}
+
+int dut_depth_acc_add(dut_depth_acc *a, const char *contig, const cl_depth_profile *p)
+{
+    if (!a || !contig || !p || p->n_bins != a->n_bins || p->window != a->window || !p->hist_raw || !p->hist_qc) return CL_ERR_INVALID;
+    try {
+        dut_depth_acc::Entry e;
+        e.name = contig;
+        e.raw.assign(p->hist_raw, p->hist_raw + p->n_bins); e.qc.assign(p->hist_qc, p->hist_qc + p->n_bins);
+        e.sum_raw = p->sum_raw; e.sum_qc = p->sum_qc;
+        for (uint32_t b = 0; b < a->n_bins; ++b) { a->total.raw[b] += e.raw[b]; a->total.qc[b] += e.qc[b]; }
+        a->total.sum_raw += e.sum_raw; a->total.sum_qc += e.sum_qc;
+        a->contigs.push_back(std::move(e));
+    } catch (...) { return CL_ERR_NOMEM; }
+    if (a->wf && p->n_windows) {
+        if (!p->win_raw || !p->win_qc) return CL_ERR_INVALID;
+        for (uint64_t i = 0; i < p->n_windows; ++i) {
+            const uint64_t start = i * p->window, end = std::min<uint64_t>(start + p->window, p->extent);
+            const double len = (double)(end - start);
+            fprintf(a->wf, "%s\t%llu\t%llu\t%.2f\t%.2f\n", contig, (unsigned long long)start, (unsigned long long)end,
+                    (double)p->win_raw[i] / len, (double)p->win_qc[i] / len);
+        }
+        if (ferror(a->wf)) return CL_ERR_INVALID;
+    }
+    return CL_OK;
+}
+
+int dut_depth_acc_total(const dut_depth_acc *a, const uint64_t **hist_raw, const uint64_t **hist_qc, uint64_t *sum_raw, uint64_t *sum_qc)
+{
+    if (!a) return CL_ERR_INVALID;
+    if (hist_raw) *hist_raw = a->total.raw.data();
+    if (hist_qc) *hist_qc = a->total.qc.data();
+    if (sum_raw) *sum_raw = a->total.sum_raw;
+    if (sum_qc) *sum_qc = a->total.sum_qc;
+    return CL_OK;
+}
+
+int dut_depth_acc_finish(dut_depth_acc *a, const char *dist_path, const char *summary_path)
+{
+    if (!a) return CL_ERR_INVALID;
+    int rc = CL_OK;
+    if (a->wf) { if (fclose(a->wf) != 0) rc = CL_ERR_INVALID; a->wf = nullptr; }
+    auto each = [&](auto &&fn) { for (const dut_depth_acc::Entry &e : a->contigs) fn(e); fn(a->total); };
+    if (dist_path) {
+        FILE *f = fopen(dist_path, "wb");
+        if (!f) return CL_ERR_INVALID;
+        fputs("#contig\tkind\tdepth\tpositions\tfraction_at_or_above\n", f);
+        each([&](const dut_depth_acc::Entry &e) {
+            for (int kind = 0; kind < 2; ++kind) {
+                const std::vector<uint64_t> &h = kind ? e.qc : e.raw;
+                uint64_t n = 0, below = 0;
+                for (uint64_t v : h) n += v;
+                for (uint32_t b = 0; b < a->n_bins; ++b) {
+                    if (h[b])
+                        fprintf(f, "%s\t%s\t%u%s\t%llu\t%.6f\n", e.name.c_str(), kind ? "qc" : "raw", b, b + 1 == a->n_bins ? "+" : "",
+                                (unsigned long long)h[b], (double)(n - below) / (double)n);
+                    below += h[b];
+                }
+            }
+        });
+        if (ferror(f)) rc = CL_ERR_INVALID;
+        if (fclose(f) != 0) rc = CL_ERR_INVALID;
+    }
+    if (summary_path) {
+        FILE *f = fopen(summary_path, "wb");
+        if (!f) return CL_ERR_INVALID;
+        fputs("#contig\tkind\tpositions\tsum\tmean\tq1\tmedian\tq3", f);
+        for (int k = 0; k < DUT_DEPTH_N_THRESHOLDS; ++k) fprintf(f, "\tfrac_ge_%u", dut_depth_thresholds[k]);
+        fputc('\n', f);
+        each([&](const dut_depth_acc::Entry &e) {
+            for (int kind = 0; kind < 2; ++kind) {
+                dut_depth_summary s;
+                dut_depth_stats(kind ? e.qc.data() : e.raw.data(), a->n_bins, kind ? e.sum_qc : e.sum_raw, &s);
+                fprintf(f, "%s\t%s\t%llu\t%llu\t%.4f\t%u%s\t%u%s\t%u%s", e.name.c_str(), kind ? "qc" : "raw", (unsigned long long)s.positions,
+                        (unsigned long long)(kind ? e.sum_qc : e.sum_raw), s.mean, s.q1, s.q1_saturated ? "+" : "", s.median,
+                        s.median_saturated ? "+" : "", s.q3, s.q3_saturated ? "+" : "");
+                for (int k = 0; k < DUT_DEPTH_N_THRESHOLDS; ++k) {
+                    if (s.frac_at_least[k] < 0.0) fputs("\tNA", f); else fprintf(f, "\t%.6f", s.frac_at_least[k]);
+                }
+                fputc('\n', f);
+            }
+        });
+        if (ferror(f)) rc = CL_ERR_INVALID;
+        if (fclose(f) != 0) rc = CL_ERR_INVALID;
+    }
+    return rc;
+}
+
 } // extern "C"

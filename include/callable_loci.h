@@ -183,6 +183,37 @@ cl_status cl_sync(cl_ctx *ctx);
  * collective without a host round trip */
 cl_status cl_device_summary(cl_ctx *ctx, void **dev_ptr, size_t *bytes);
 
+/* ---- depth distribution of the resident contig ------------------------------------------ */
+/* What a coverage tool reports beside the intervals: the histogram of the per-position depths, their exact sums and
+ * the sum per fixed window.  With raw[p] and qc[p], 0 <= p < extent, the raw_depth and qc_depth of mod.rs:17-42 (what
+ * cl_debug_depths dumps; deletions and reference skips count in raw only):
+ *   hist_raw[b], hist_qc[b]   positions with min(depth, n_bins - 1) == b: the last bin saturates
+ *   sum_raw, sum_qc           the sums of all depths, exact whatever n_bins is
+ *   win_raw[i], win_qc[i]     window > 0: the sums over [i * window, min((i + 1) * window, extent)),
+ *                             n_windows = ceil(extent / window); window == 0: no table (NULL, n_windows 0)
+ * so that sum hist == extent, extent - hist_raw[0] == n_covered_bases, sum_raw == summed_coverage, sum_qc ==
+ * quality_bases and sum win == sum.  Every figure is a plain count: profiles of contigs, devices or ranks add up.
+ * Reduced on the device by one extra kernel over the resident contig -- no per-position array exists anywhere --, taken
+ * only when asked: cl_contig_run enqueues what it always did.  Any number of calls per resident contig, after
+ * cl_contig_run (or cl_contig_finish); the call waits for the stream.  The arrays are context-owned host memory, valid
+ * until the next cl_contig_depth_profile, cl_contig_begin or cl_destroy.
+ * CL_ERR_INVALID: n_bins outside [CL_DEPTH_MIN_BINS, CL_DEPTH_MAX_BINS]; a window of 1 to CL_DEPTH_MIN_WINDOW - 1
+ * positions (per-base output is not this call); no contig has been run; a context of the byte forms
+ * (DUT_QUAL_FORM=bytes: pass-bit form only, like cl_push_reads_bits).  CL_ERR_DEVICE: a host-only debug context. */
+#define CL_DEPTH_MIN_BINS 2u
+#define CL_DEPTH_MAX_BINS 4096u
+#define CL_DEPTH_MIN_WINDOW 16u
+typedef struct cl_depth_profile {
+    uint32_t n_bins, window;
+    uint64_t n_windows, extent, sum_raw, sum_qc;
+    const uint64_t *hist_raw, *hist_qc;   /* n_bins each             */
+    const uint64_t *win_raw, *win_qc;     /* n_windows each, or NULL */
+} cl_depth_profile;
+cl_status cl_contig_depth_profile(cl_ctx *ctx, uint32_t n_bins, uint32_t window, cl_depth_profile *out);
+/* Measurement: the kernel of the last cl_contig_depth_profile by device events, milliseconds; 0 unless cl_set_profiling
+ * was on for that call. */
+cl_status cl_contig_depth_profile_ms(cl_ctx *ctx, double *kernel_ms);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 enum { CL_K_PREP = 0, CL_K_BOUNDS = 1, CL_K_PILEUP = 2, CL_K_RLE = 3, CL_K_COUNT = 4 };
 /* When on, every cl_contig_run brackets each kernel group with hipEvents on the stream. */

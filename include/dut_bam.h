@@ -105,6 +105,26 @@ int dut_coverage_files_multi(const char *bam_path, const char *fasta_path, const
                              const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
                              unsigned flags, char *err, size_t err_len);
 
+/* dut_coverage_files_multi that also writes the depth profile of every selected contig (cl_contig_depth_profile,
+ * callable_loci.h; the statistics and the three file formats: dut_coverage.h, dut_depth_acc): the profile is taken on the
+ * device while the contig is resident -- one more kernel per contig --, travels to the calling thread with the contig's
+ * runs and is written in tid order, so one device and several give the same bytes; the files are complete when the call
+ * returns.  BED, figures and summaries are those of dut_coverage_files_multi.  depth == NULL or no path given: exactly
+ * that call.  Pass-bit form only (DUT_QUAL_FORM=bytes: CL_ERR_INVALID).
+ *   n_bins        histogram bins, 2 .. 4096: depths 0 .. n_bins - 2 exactly, the last bin "n_bins - 1 or more"
+ *   window        positions per window of windows_path, >= 16 (ignored without windows_path)
+ * A bad n_bins or window is refused (CL_ERR_INVALID, message) before any file or device is touched; a depth file that
+ * cannot be written is named in the message.
+ *   dist_path, windows_path, summary_path    any may be NULL */
+typedef struct dut_depth_options {
+    uint32_t n_bins, window;
+    const char *dist_path, *windows_path, *summary_path;
+} dut_depth_options;
+int dut_coverage_files_ex(const char *bam_path, const char *fasta_path, const char *bed_path,
+                          const char *summary_json, const char *summary_html, const cl_options *opt,
+                          const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
+                          unsigned flags, const dut_depth_options *depth, char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

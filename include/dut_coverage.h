@@ -136,6 +136,48 @@ int  dut_compare_contig_names(const char *a, const char *b);
 void dut_genome_summary_build(const dut_contig_stats *stats, const uint64_t *callable, size_t n_contigs,
                               dut_genome_summary *out);
 
+/* ---- depth profile: statistics and text files of cl_contig_depth_profile's histograms ---------------------
+ * (host code only; histograms of contigs, devices or ranks add up bin by bin) */
+#define DUT_DEPTH_N_THRESHOLDS 8
+/* the depths of frac_at_least[]: 1, 5, 10, 15, 20, 30, 50, 100 */
+extern const uint32_t dut_depth_thresholds[DUT_DEPTH_N_THRESHOLDS];
+typedef struct dut_depth_summary {
+    uint64_t positions;            /* sum of the histogram                                                        */
+    double   mean;                 /* sum / positions in f64; 0 without positions                                 */
+    uint32_t q1, median, q3;       /* smallest depth d whose cumulative count reaches ceil(q * positions)         */
+    uint8_t  q1_saturated, median_saturated, q3_saturated;   /* it is the last bin: "that depth or more"          */
+    uint8_t  reserved;
+    /* share of the positions with depth >= dut_depth_thresholds[k]; -1.0 = not available: the threshold lies
+     * beyond the last exact bin (> n_bins - 1), the histogram cannot tell; 0 without positions */
+    double   frac_at_least[DUT_DEPTH_N_THRESHOLDS];
+} dut_depth_summary;
+/* hist: n_bins >= 2 counts, the last bin saturating; sum: the exact sum of the depths.  CL_OK or CL_ERR_INVALID. */
+int dut_depth_stats(const uint64_t *hist, uint32_t n_bins, uint64_t sum, dut_depth_summary *out);
+
+/* The accumulator behind `--depth-dist`, `--depth-windows` and `--depth-summary`: contigs are added in the order their
+ * lines shall have (the BED's), their histograms and sums also go into a `total`.
+ *   windows file (written as the contigs are added; windows_path NULL: none), header
+ *       #contig\tstart\tend\tmean_raw\tmean_qc
+ *     one line per window [start, end) of every contig, the means sum / (end - start) in f64 as %.2f
+ *   distribution file, header
+ *       #contig\tkind\tdepth\tpositions\tfraction_at_or_above
+ *     per contig, then for `total`: kind `raw`, then `qc`, one line per non-empty bin in ascending depth; the last bin's
+ *     depth is written `<n_bins-1>+`; the fraction (positions at that depth or above / positions) as %.6f
+ *   summary file, header
+ *       #contig\tkind\tpositions\tsum\tmean\tq1\tmedian\tq3\tfrac_ge_1\tfrac_ge_5\tfrac_ge_10\tfrac_ge_15\tfrac_ge_20\tfrac_ge_30\tfrac_ge_50\tfrac_ge_100
+ *     per contig, then for `total`: a `raw` and a `qc` line of dut_depth_stats: positions and sum as integers, the
+ *     mean as %.4f, a quartile as an integer with `+` behind it when saturated, a fraction as %.6f or `NA`
+ * dut_depth_acc_new: NULL when n_bins is outside [2, 4096], window is 1..15, or the windows file cannot be created. */
+typedef struct dut_depth_acc dut_depth_acc;
+dut_depth_acc *dut_depth_acc_new(uint32_t n_bins, uint32_t window, const char *windows_path);
+void dut_depth_acc_free(dut_depth_acc *a);
+/* p: n_bins and window as the accumulator's.  Copies what it keeps. */
+int dut_depth_acc_add(dut_depth_acc *a, const char *contig, const cl_depth_profile *p);
+/* the total so far: context-owned, n_bins entries each */
+int dut_depth_acc_total(const dut_depth_acc *a, const uint64_t **hist_raw, const uint64_t **hist_qc, uint64_t *sum_raw, uint64_t *sum_qc);
+/* closes the windows file and writes the other two (either path may be NULL) */
+int dut_depth_acc_finish(dut_depth_acc *a, const char *dist_path, const char *summary_path);
+
 /* Debug names of CalledState (types.rs:36-43) */
 const char *dut_state_name(uint32_t state);
 

@@ -53,6 +53,22 @@ extern "C" {
                                     summary_json: *const c_char, summary_html: *const c_char, opt: *const ClOptions,
                                     contigs: *const *const c_char, n_contigs: usize, devices: *const c_int, n_devices: usize,
                                     flags: c_uint, err: *mut c_char, err_len: usize) -> c_int;
+    // the depth distribution of the resident contig (after cl_contig_finish / cl_contig_run), reduced on the device
+    pub fn cl_contig_depth_profile(ctx: *mut ClCtx, n_bins: u32, window: u32, out: *mut ClDepthProfile) -> c_int;
+    pub fn cl_contig_depth_profile_ms(ctx: *mut ClCtx, kernel_ms: *mut f64) -> c_int;   // measurement: its kernel by events
+    // include/dut_coverage.h: statistics of a histogram, the accumulator and its writers (host only)
+    pub fn dut_depth_stats(hist: *const u64, n_bins: u32, sum: u64, out: *mut DutDepthSummary) -> c_int;
+    pub fn dut_depth_acc_new(n_bins: u32, window: u32, windows_path: *const c_char) -> *mut DutDepthAcc;
+    pub fn dut_depth_acc_add(acc: *mut DutDepthAcc, contig: *const c_char, p: *const ClDepthProfile) -> c_int;
+    pub fn dut_depth_acc_total(acc: *const DutDepthAcc, hist_raw: *mut *const u64, hist_qc: *mut *const u64,
+                               sum_raw: *mut u64, sum_qc: *mut u64) -> c_int;
+    pub fn dut_depth_acc_finish(acc: *mut DutDepthAcc, dist_path: *const c_char, summary_path: *const c_char) -> c_int;
+    pub fn dut_depth_acc_free(acc: *mut DutDepthAcc);
+    // include/dut_bam.h: dut_coverage_files_multi + the depth profile files (depth NULL: exactly that call)
+    pub fn dut_coverage_files_ex(bam: *const c_char, fasta: *const c_char, bed: *const c_char,
+                                 summary_json: *const c_char, summary_html: *const c_char, opt: *const ClOptions,
+                                 contigs: *const *const c_char, n_contigs: usize, devices: *const c_int, n_devices: usize,
+                                 flags: c_uint, depth: *const DutDepthOptions, err: *mut c_char, err_len: usize) -> c_int;
     // include/dut_fingerprint.h: the `fingerprint` sketch on the device (1 <= ksize <= 64)
     pub fn dut_fp_create(opt: *const DutFpOptions, device_id: c_int, stream: *mut c_void, out: *mut *mut DutFpCtx) -> c_int;
     pub fn dut_fp_push_seq4(ctx: *mut DutFpCtx, seq4: *const u8, base_off: *const u64, n_seq: u64) -> c_int;
@@ -66,6 +82,29 @@ extern "C" {
 }
 
 pub enum DutFpCtx {}
+pub enum DutDepthAcc {}
+
+#[repr(C)]
+pub struct ClDepthProfile {       // cl_depth_profile: the arrays are context-owned, valid until the next profile / contig
+    pub n_bins: u32, pub window: u32,
+    pub n_windows: u64, pub extent: u64, pub sum_raw: u64, pub sum_qc: u64,
+    pub hist_raw: *const u64, pub hist_qc: *const u64,     // n_bins each; the last bin saturates
+    pub win_raw: *const u64, pub win_qc: *const u64,       // n_windows each, or null (window == 0)
+}
+
+#[repr(C)]
+pub struct DutDepthSummary {      // dut_depth_summary; frac_at_least: depth >= 1, 5, 10, 15, 20, 30, 50, 100; -1.0 = not available
+    pub positions: u64, pub mean: f64,
+    pub q1: u32, pub median: u32, pub q3: u32,
+    pub q1_saturated: u8, pub median_saturated: u8, pub q3_saturated: u8, pub reserved: u8,
+    pub frac_at_least: [f64; 8],
+}
+
+#[repr(C)]
+pub struct DutDepthOptions {      // dut_depth_options: n_bins 2..=4096, window >= 16 with windows_path; paths may be null
+    pub n_bins: u32, pub window: u32,
+    pub dist_path: *const c_char, pub windows_path: *const c_char, pub summary_path: *const c_char,
+}
 
 #[repr(C)]
 pub struct DutFpOptions {         // dut_fp_options, include/dut_fingerprint.h
