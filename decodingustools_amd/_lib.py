@@ -1,5 +1,5 @@
 """ctypes binding of libcallable_hip.so (include/callable_loci.h, dut_coverage.h, dut_bam.h, dut_report.h,
-dut_haplogroup.h, dut_fingerprint.h).
+dut_haplogroup.h, dut_fingerprint.h, dut_variants.h).
 
 There is no fallback: if the shared library is missing or does not load, importing the engine
 raises.  Build it with `python -m decodingustools_amd.build` (or __graft_entry__.build()).
@@ -135,8 +135,45 @@ class dut_depth_options(C.Structure):
                 ("summary_path", C.c_char_p)]
 
 
+class cl_scan_candidate(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8), ("pad", C.c_uint8 * 2),
+                ("a", C.c_uint32), ("c", C.c_uint32), ("g", C.c_uint32), ("t", C.c_uint32), ("depth", C.c_uint32)]
+
+
+class cl_scan_result(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_low_depth", C.c_uint64), ("n_mixed", C.c_uint64),
+                ("n_uncomparable", C.c_uint64), ("n_match", C.c_uint64), ("n_variant", C.c_uint64),
+                ("candidates", C.POINTER(cl_scan_candidate))]
+
+
+class dut_variant_note(C.Structure):
+    _fields_ = [("known", C.c_int), ("names", C.c_char_p), ("alleles", C.c_char_p)]
+
+
+class dut_tree_locus(C.Structure):
+    _fields_ = [("position", C.c_uint32), ("name", C.c_char_p), ("ancestral", C.c_char_p), ("derived", C.c_char_p)]
+
+
+CL_SCAN_MAX_DENSE = 1 << 20
+
 # every symbol the headers declare: (name, restype, argtypes)
 SYMBOLS = [
+    ("cl_site_scan", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                               C.POINTER(cl_scan_result)]),
+    ("cl_site_scan_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("cl_site_scan_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    # include/dut_variants.h
+    ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
+    ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
+    ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(C.POINTER(dut_variant_note))]),
+    ("dut_variants_free_notes", None, [C.POINTER(dut_variant_note), C.c_size_t]),
+    ("dut_variants_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_scan_result), C.c_uint32, C.c_uint8,
+                                     C.POINTER(dut_variant_note), C.c_char_p, C.c_size_t]),
+    ("dut_find_variants_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p,
+                                          C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint8, C.c_int, C.c_char_p, C.c_size_t]),
+    ("dut_tree_collect_loci", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(dut_tree_locus)),
+                                        C.POINTER(C.c_size_t)]),
     ("cl_contig_depth_profile", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(cl_depth_profile)]),
     ("cl_contig_depth_profile_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     ("dut_depth_stats", C.c_int, [C.POINTER(C.c_uint64), C.c_uint32, C.c_uint64, C.POINTER(dut_depth_summary)]),

@@ -15,10 +15,11 @@ LIB = os.path.join(LIBDIR, "libcallable_hip.so")
 SOURCES = [os.path.join(CSRC, "callable_loci.hip"), os.path.join(CSRC, "qual_pack.cpp"), os.path.join(CSRC, "host_coverage.cpp"),
            os.path.join(CSRC, "bam_io.cpp"), os.path.join(CSRC, "coverage_files.cpp"), os.path.join(CSRC, "report.cpp"),
            os.path.join(CSRC, "haplogroup.cpp"), os.path.join(CSRC, "fingerprint.hip"), os.path.join(CSRC, "fastq_io.cpp"),
-           os.path.join(CSRC, "depth_files.cpp")]
+           os.path.join(CSRC, "depth_files.cpp"), os.path.join(CSRC, "variants.cpp")]
 CLI = os.path.join(LIBDIR, "dut-coverage")
 CLI_SRC = os.path.join(CSRC, "coverage_main.cpp")
-HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "depth_profile.hip.h"), os.path.join(CSRC, "coverage_hook.h"),
+HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "depth_profile.hip.h"), os.path.join(CSRC, "site_scan.hip.h"),
+           os.path.join(CSRC, "coverage_hook.h"),
            os.path.join(CSRC, "host_parallel.h"),
            os.path.join(CSRC, "qual_pack.h"), os.path.join(CSRC, "pass_rows.h"),
            os.path.join(HERE, "..", "include", "callable_loci.h"),
@@ -26,7 +27,8 @@ HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "depth_profil
            os.path.join(HERE, "..", "include", "dut_bam.h"),
            os.path.join(HERE, "..", "include", "dut_report.h"),
            os.path.join(HERE, "..", "include", "dut_haplogroup.h"),
-           os.path.join(HERE, "..", "include", "dut_fingerprint.h"), CLI_SRC]
+           os.path.join(HERE, "..", "include", "dut_fingerprint.h"),
+           os.path.join(HERE, "..", "include", "dut_variants.h"), CLI_SRC]
 
 
 def _stale():

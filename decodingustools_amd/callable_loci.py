@@ -237,6 +237,34 @@ class Engine:
         self._check(self._lib.cl_site_pileup_stats(self._h, C.byref(ms), C.byref(b)))
         return ms.value, b.value
 
+    def site_scan(self, min_quality, min_depth, ref, start=0, end=None):
+        """cl_site_scan over [start, end) of the resident tile (end=None: the length of `ref`, which must be the ref_len
+        given to site_upload): a ScanResult with the five class counts and the candidates as a structured array."""
+        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
+        if end is None:
+            end = ref.shape[0]
+        r = _lib.cl_scan_result()
+        self._check(self._lib.cl_site_scan(self._h, int(min_quality), int(min_depth), _ptr(ref), ref.shape[0], int(start), int(end),
+                                           C.byref(r)))
+        n = int(r.n_variant)
+        cand = np.zeros(n, SCAN_CANDIDATE)
+        if n:
+            C.memmove(cand.ctypes.data, r.candidates, n * SCAN_CANDIDATE.itemsize)
+        return ScanResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), mixed=int(r.n_mixed),
+                          uncomparable=int(r.n_uncomparable), match=int(r.n_match), variant=n, candidates=cand)
+
+    def site_scan_counts(self, min_quality, start, end):
+        """cl_site_scan_counts: (end - start, 5) uint32 -- A, C, G, T, depth -- for at most CL_SCAN_MAX_DENSE positions."""
+        counts = np.zeros((max(int(end) - int(start), 0), 5), np.uint32)
+        self._check(self._lib.cl_site_scan_counts(self._h, int(min_quality), int(start), int(end), _ptr(counts)))
+        return counts
+
+    def site_scan_stats(self):
+        """(kernel milliseconds, algorithmic bytes) of the last site_scan / site_scan_counts."""
+        ms = C.c_double(); b = C.c_uint64()
+        self._check(self._lib.cl_site_scan_stats(self._h, C.byref(ms), C.byref(b)))
+        return ms.value, b.value
+
     def depth_profile(self, n_bins=1001, window=0):
         """The depth distribution of the resident contig, reduced on the device (cl_contig_depth_profile): a
         DepthProfile of numpy uint64 arrays (copies).  window = 0: no window table."""
@@ -252,6 +280,25 @@ class Engine:
                             sum_raw=int(p.sum_raw), sum_qc=int(p.sum_qc), hist_raw=arr(p.hist_raw, int(p.n_bins)),
                             hist_qc=arr(p.hist_qc, int(p.n_bins)), win_raw=arr(p.win_raw, nw) if window else None,
                             win_qc=arr(p.win_qc, nw) if window else None, kernel_ms=float(ms.value))
+
+
+# cl_scan_candidate as a numpy record: pos is 1-based, ref and alt are ASCII codes
+SCAN_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("alt", np.uint8), ("pad", np.uint8, (2,)), ("a", np.uint32),
+                           ("c", np.uint32), ("g", np.uint32), ("t", np.uint32), ("depth", np.uint32)])
+
+
+@dataclass
+class ScanResult:
+    """cl_scan_result (include/callable_loci.h): the five classes add up to end - start; candidates = the positions of
+    class variant, ascending."""
+    start: int
+    end: int
+    low_depth: int
+    mixed: int
+    uncomparable: int
+    match: int
+    variant: int
+    candidates: np.ndarray
 
 
 @dataclass

@@ -5,6 +5,7 @@
 #include "../../include/callable_loci.h"
 #include "kernels.hip.h"
 #include "depth_profile.hip.h"
+#include "site_scan.hip.h"
 #include "host_parallel.h"
 #include "qual_pack.h"
 #include "pass_rows.h"
@@ -283,7 +284,19 @@ struct SiteResident {
     uint32_t contig_len = 0;
     bool resident = false;
     bool filtered = false;           // the resident tile holds only the reads that overlap a site of the list it was uploaded for (cl_site_pileup)
-    void release() { rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release(); resident = false; }
+    // cl_site_scan: the per-read ends and per-window read ranges of the resident tile (built by the first scan), the
+    // reference bytes of the range, class counts + candidate count, candidates, dense counters
+    DevBuf<uint32_t> sc_end, sc_wfirst, sc_wlast, sc_dense;
+    DevBuf<uint8_t> sc_ref;
+    DevBuf<unsigned long long> sc_cls;
+    DevBuf<ScanCand> sc_cand;
+    bool scan_indexed = false;
+    void release()
+    {
+        rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
+        sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
+        resident = false; scan_indexed = false;
+    }
 };
 
 struct cl_ctx {
@@ -411,6 +424,11 @@ struct cl_ctx {
     double site_ms = 0.0;
     uint64_t site_bytes = 0;
     SiteResident site;
+    // the last cl_site_scan / cl_site_scan_counts: its kernel by events, its algorithmic bytes, its candidates
+    hipEvent_t scan_ev[2] = {nullptr, nullptr};
+    double scan_ms = 0.0;
+    uint64_t scan_bytes = 0;
+    std::vector<cl_scan_candidate> scan_cand;
 };
 
 static void join_prealloc(cl_ctx *c) { if (c->prealloc.joinable()) c->prealloc.join(); }   // (cl_contig_reserve's helper thread)
@@ -1454,6 +1472,7 @@ void cl_destroy(cl_ctx *c)
     c->d_winpart.release(); c->d_lut.release(); c->d_summary.release();
     c->d_iv.release(); c->d_dbg.release(); c->d_prof.release(); c->d_fin.release(); c->d_errflag.release(); c->d_runtab.release(); c->site.release();
     for (int i = 0; i < 2; ++i) if (c->site_ev[i]) (void)hipEventDestroy(c->site_ev[i]);
+    for (int i = 0; i < 2; ++i) if (c->scan_ev[i]) (void)hipEventDestroy(c->scan_ev[i]);
     for (int i = 0; i < 2; ++i) if (c->prof_ev[i]) (void)hipEventDestroy(c->prof_ev[i]);
     if (c->ev_made)
         for (int s = 0; s < cl_ctx::kEvSets; ++s)
@@ -2759,7 +2778,7 @@ static cl_status cl_site_upload_impl(cl_ctx *c, uint32_t contig_len, uint64_t re
     HIP_TRY(c, hipSetDevice(c->device));
     drop_prefetch(c);                                        // the ring is needed below
     SiteResident &S = c->site;
-    S.resident = false; S.filtered = false;
+    S.resident = false; S.filtered = false; S.scan_indexed = false;
     const uint64_t n_all = t->n_reads;
     if (n_all > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "too many reads");
     if (n_all && (!t->pos || !t->mapq || !t->cigar_off || !t->seq_off)) return fail(c, CL_ERR_INVALID, "null tile array");
@@ -2910,6 +2929,196 @@ static cl_status cl_site_run_impl(cl_ctx *c, uint8_t min_quality, const uint32_t
         c->site_bytes = (S.nbase + 1) / 2 + S.n * sizeof(SiteRec) + S.ncig * 4 + (uint64_t)pos0.size() * 8 + (uint64_t)n_sites * 64;
     }
     tmr.lap("site run: kernel + histogram back");
+    return CL_OK;
+}
+
+// ---- config 5, dense form: base counts and calls at every position of a range of the resident tile (site_scan.hip.h) ----
+static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_candidate) == 28, "the device writes cl_scan_candidate");
+
+// the argument checks every scan shares, in front of any device work
+static cl_status site_scan_check(cl_ctx *c, const char *who, uint32_t start, uint32_t end)
+{
+    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
+    const SiteResident &S = c->site;
+    if (!S.resident) return fail(c, CL_ERR_INVALID, std::string(who) + " without cl_site_upload");
+    if (S.filtered) return fail(c, CL_ERR_INVALID, std::string(who) + ": the resident tile was uploaded by cl_site_pileup for its own site list; cl_site_upload gives a tile that serves a scan");
+    if (start > end) return fail(c, CL_ERR_INVALID, std::string(who) + ": start > end");
+    if (end > S.contig_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": the range ends beyond the contig");
+    return CL_OK;
+}
+
+// the per-read ends and per-window read ranges of the resident tile: one kernel, the first time a scan asks
+static cl_status site_scan_index(cl_ctx *c)
+{
+    SiteResident &S = c->site;
+    if (S.scan_indexed) return CL_OK;
+    const size_t n_win = ((size_t)S.contig_len + kScanWin - 1) / kScanWin;
+    HIP_TRY(c, S.sc_end.reserve(S.n + 1)); HIP_TRY(c, S.sc_wfirst.reserve(n_win + 1)); HIP_TRY(c, S.sc_wlast.reserve(n_win + 1));
+    HIP_TRY(c, hipMemsetAsync(S.sc_wfirst.p, 0xFF, (n_win + 1) * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(S.sc_wlast.p, 0, (n_win + 1) * 4, c->stream));
+    if (S.n) {
+        ScanIndexArgs A;
+        A.rec = S.rec.p; A.cigar = S.cig.p; A.n = (uint32_t)S.n; A.contig_len = S.contig_len;
+        A.end = S.sc_end.p; A.wfirst = S.sc_wfirst.p; A.wlast = S.sc_wlast.p;
+        hipLaunchKernelGGL(k_site_scan_index, dim3((uint32_t)((S.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
+        HIP_TRY(c, hipGetLastError());
+    }
+    S.scan_indexed = true;
+    return CL_OK;
+}
+
+static void site_scan_fill(cl_ctx *c, ScanArgs &A, uint8_t min_quality, uint32_t min_depth, uint32_t start, uint32_t end)
+{
+    SiteResident &S = c->site;
+    A.rec = S.rec.p; A.seq_base = S.base.p; A.cigar = S.cig.p; A.seq4 = S.seq.p;
+    A.end = S.sc_end.p; A.wfirst = S.sc_wfirst.p; A.wlast = S.sc_wlast.p;
+    A.min_quality = min_quality; A.contig_len = S.contig_len; A.min_depth = min_depth; A.ref_len = S.ref_len;
+    A.start = start; A.end_pos = end; A.win0 = start / kScanWin;
+    A.refb = nullptr; A.cls = nullptr; A.n_cand = nullptr; A.cand = nullptr; A.cand_cap = 0; A.dense = nullptr;
+}
+
+// settles the positions the six counter planes cannot classify (site_scan.hip.h) with cl_site_run's 16-code histogram:
+// one code with 7/10 of the depth is a call of a code that is not A/C/G/T -> uncomparable; otherwise mixed
+static cl_status site_scan_settle(cl_ctx *c, uint8_t min_quality, const std::vector<uint32_t> &pos1, uint64_t &n_unc, uint64_t &n_mixed)
+{
+    if (pos1.empty()) return CL_OK;
+    std::vector<uint32_t> hist(pos1.size() * 16);
+    const double ms = c->site_ms; const uint64_t by = c->site_bytes;          // (cl_site_pileup_stats keeps speaking of the caller's own runs)
+    const cl_status s = cl_site_run_impl(c, min_quality, pos1.data(), pos1.size(), hist.data(), nullptr);
+    c->site_ms = ms; c->site_bytes = by;
+    if (s != CL_OK) return s;
+    for (size_t i = 0; i < pos1.size(); ++i) {
+        uint64_t depth = 0, m = 0;
+        for (int k = 0; k < 16; ++k) { depth += hist[i * 16 + k]; m = std::max<uint64_t>(m, hist[i * 16 + k]); }
+        if (10 * m >= 7 * depth) ++n_unc; else ++n_mixed;
+    }
+    return CL_OK;
+}
+
+static cl_status cl_site_scan_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const uint8_t *ref_bases, uint64_t ref_len,
+                                   uint32_t start, uint32_t end, cl_scan_result *out)
+{
+    if (!c) return CL_ERR_INVALID;
+    if (!out) return fail(c, CL_ERR_INVALID, "cl_site_scan: null result");
+    cl_status s = site_scan_check(c, "cl_site_scan", start, end);
+    if (s != CL_OK) return s;
+    SiteResident &S = c->site;
+    if (min_depth == 0) return fail(c, CL_ERR_INVALID, "cl_site_scan: min_depth must be at least 1");
+    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan: ref_len differs from the one given to cl_site_upload");
+    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan: null reference");
+    memset(out, 0, sizeof(*out));
+    out->start = start; out->end = end;
+    c->scan_cand.clear();
+    out->candidates = c->scan_cand.data();
+    c->scan_ms = 0.0; c->scan_bytes = 0;
+    if (start == end) return CL_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    StageTimer tmr;
+    if ((s = site_scan_index(c)) != CL_OK) return s;
+    // the reference bytes of the range (those that exist: positions at and beyond ref_len read as "other")
+    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len), n_ref = ref_hi > start ? ref_hi - start : 0;
+    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
+    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
+    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
+    const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
+    // candidates are few where the sample follows the reference: a buffer of a position in 64 (at least 64 K entries);
+    // when more are wanted the kernel says how many, the buffer grows and the scan runs again -- nothing is cut short
+    uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
+    unsigned long long h_cls[8];
+    double ms_all = 0.0;
+    for (;;) {
+        HIP_TRY(c, S.sc_cand.reserve(cap));
+        HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
+        ScanArgs A;
+        site_scan_fill(c, A, min_quality, min_depth, start, end);
+        A.refb = S.sc_ref.p; A.cls = S.sc_cls.p; A.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
+        A.cand = S.sc_cand.p; A.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+        HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
+        hipLaunchKernelGGL(k_site_scan<false>, dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
+        HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float t = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
+        ms_all += t;
+        const uint64_t want = (uint32_t)h_cls[SCAN_CLASSES];
+        if (want <= cap) break;
+        cap = want;
+    }
+    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
+    c->scan_cand.resize(n_cand);
+    if (n_cand) HIP_TRY(c, hipMemcpy(c->scan_cand.data(), S.sc_cand.p, n_cand * sizeof(cl_scan_candidate), hipMemcpyDeviceToHost));
+    c->scan_ms = ms_all;
+    c->scan_bytes = (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + n_ref + n_cand * sizeof(cl_scan_candidate);
+    tmr.lap("site scan: reference in, kernel, candidates back");
+    // the compaction runs wave by wave: ascending position is restored here; ambiguous positions leave the list
+    std::sort(c->scan_cand.begin(), c->scan_cand.end(), [](const cl_scan_candidate &a, const cl_scan_candidate &b) { return a.pos < b.pos; });
+    out->n_low_depth = h_cls[SCAN_LOW_DEPTH]; out->n_mixed = h_cls[SCAN_MIXED]; out->n_uncomparable = h_cls[SCAN_UNCOMPARABLE];
+    out->n_match = h_cls[SCAN_MATCH]; out->n_variant = h_cls[SCAN_VARIANT];
+    if (h_cls[SCAN_AMBIGUOUS]) {
+        std::vector<uint32_t> amb;
+        size_t k = 0;
+        for (const cl_scan_candidate &cd : c->scan_cand) { if (cd.alt == 0) amb.push_back(cd.pos); else c->scan_cand[k++] = cd; }
+        c->scan_cand.resize(k);
+        if ((s = site_scan_settle(c, min_quality, amb, out->n_uncomparable, out->n_mixed)) != CL_OK) return s;
+        tmr.lap("site scan: ambiguous positions settled by the site pileup");
+    }
+    out->candidates = c->scan_cand.data();
+    return CL_OK;
+}
+
+static cl_status cl_site_scan_counts_impl(cl_ctx *c, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts)
+{
+    if (!c) return CL_ERR_INVALID;
+    cl_status s = site_scan_check(c, "cl_site_scan_counts", start, end);
+    if (s != CL_OK) return s;
+    if (end - start > CL_SCAN_MAX_DENSE) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts: more than CL_SCAN_MAX_DENSE positions");
+    c->scan_ms = 0.0; c->scan_bytes = 0;
+    if (start == end) return CL_OK;
+    if (!counts) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts: null array");
+    SiteResident &S = c->site;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((s = site_scan_index(c)) != CL_OK) return s;
+    const size_t n5 = (size_t)(end - start) * 5;
+    HIP_TRY(c, S.sc_dense.reserve(n5));
+    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
+    ScanArgs A;
+    site_scan_fill(c, A, min_quality, 1, start, end);
+    A.dense = S.sc_dense.p;
+    HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
+    hipLaunchKernelGGL(k_site_scan<true>, dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counts, S.sc_dense.p, n5 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float t = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
+    c->scan_ms = t;
+    c->scan_bytes = (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + n5 * 4;
+    return CL_OK;
+}
+
+cl_status cl_site_scan(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const uint8_t *ref_bases, uint64_t ref_len,
+                       uint32_t start, uint32_t end, cl_scan_result *out)
+{
+    try { return cl_site_scan_impl(c, min_quality, min_depth, ref_bases, ref_len, start, end, out); }
+    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
+    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+}
+
+cl_status cl_site_scan_counts(cl_ctx *c, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts)
+{
+    try { return cl_site_scan_counts_impl(c, min_quality, start, end, counts); }
+    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
+    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+}
+
+cl_status cl_site_scan_stats(cl_ctx *c, double *kernel_ms, uint64_t *bytes)
+{
+    if (!c) return CL_ERR_INVALID;
+    if (kernel_ms) *kernel_ms = c->scan_ms;
+    if (bytes) *bytes = c->scan_bytes;
     return CL_OK;
 }
 

@@ -1,4 +1,5 @@
-// dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI;
+// dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
+// project's own `fingerprint` front end and `find-variants`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -6,6 +7,7 @@
 #include "../../include/dut_bam.h"
 #include "../../include/dut_haplogroup.h"
 #include "../../include/dut_fingerprint.h"
+#include "../../include/dut_variants.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -29,7 +31,9 @@ static void usage()
             "       [--depth-dist FILE] [--depth-windows FILE --window S] [--depth-summary FILE] [--depth-cap 1000]\n"
             "         depth profile per contig and in total: histogram of raw / quality-filtered depth (depths above the cap in\n"
             "         one last bin, cap 1..4095), mean depth per window of S >= 16 positions, quartiles and share at >= Nx\n"
-            "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n");
+            "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n"
+            "       dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
+            "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -151,6 +155,92 @@ static int find_branch_main(int argc, char **argv, int tree_type)
     _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
 }
 
+// find-variants: every position of a contig (or of --region, 0-based half open) where the sample's called base differs
+// from the reference, by the counting and the call of find-y-branch (defaults as there, src/cli.rs:62-105); with --tree,
+// which of them the haplogroup tree knows.  Argument errors leave with 2 before a device is opened.
+static int find_variants_main(int argc, char **argv)
+{
+    std::string bam, ref, out, tree, contig, region;
+    unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
+    int provider = DUT_PROVIDER_FTDNA, tree_type = DUT_TREE_YDNA, device = 0;
+    bool has_provider = false, has_tree_type = false, has_region = false;
+    auto usage_fv = []() {
+        fprintf(stderr, "Usage: dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
+                        "       [--min-depth 10] [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
+                        "  --region: 0-based, half open, within the contig.  SNVs only; every fetched record counts (no flag or\n"
+                        "  base-quality filter), as in find-y-branch.\n");
+    };
+    auto number = [](const char *flag, const std::string &v, unsigned long long &dst) -> bool {
+        char *e = nullptr;
+        errno = 0;
+        if (v.empty() || v[0] < '0' || v[0] > '9') { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), flag); return false; }
+        dst = strtoull(v.c_str(), &e, 10);
+        if (errno || *e) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), flag); return false; }
+        return true;
+    };
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i], val;
+        const size_t eq = a.find('=');
+        const bool has_eq = a.rfind("--", 0) == 0 && eq != std::string::npos;
+        if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
+        auto next = [&]() -> const char * {
+            if (has_eq) return val.c_str();
+            if (i + 1 >= argc) { usage_fv(); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-r" || a == "--reference") ref = next();
+        else if (a == "-o" || a == "--output") out = next();
+        else if (a == "-L" || a == "--contig") contig = next();
+        else if (a == "--tree") tree = next();
+        else if (a == "--region") {
+            region = next();
+            const size_t dash = region.find('-');
+            if (dash == std::string::npos || !number("--region", region.substr(0, dash), start) || !number("--region", region.substr(dash + 1), end)) {
+                if (dash == std::string::npos) fprintf(stderr, "error: invalid value '%s' for '--region': START-END\n", region.c_str());
+                return 2;
+            }
+            if (start >= end || end > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%s' for '--region': the range is empty or beyond 2^32\n", region.c_str()); return 2; }
+            has_region = true;
+        }
+        else if (a == "--min-depth") {
+            if (!number("--min-depth", next(), min_depth)) return 2;
+            if (min_depth < 1 || min_depth > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%llu' for '--min-depth': at least 1\n", min_depth); return 2; }
+        }
+        else if (a == "--min-quality") {
+            if (!number("--min-quality", next(), min_quality)) return 2;
+            if (min_quality > 255) { fprintf(stderr, "error: invalid value '%llu' for '--min-quality': 0..255\n", min_quality); return 2; }
+        }
+        else if (a == "--provider") {
+            const std::string p = next();
+            if (p == "ftdna") provider = DUT_PROVIDER_FTDNA;
+            else if (p == "decodingus") provider = DUT_PROVIDER_DECODINGUS;
+            else { fprintf(stderr, "error: invalid value '%s' for '--provider'\n", p.c_str()); return 2; }
+            has_provider = true;
+        }
+        else if (a == "--tree-type") {
+            const std::string p = next();
+            if (p == "y") tree_type = DUT_TREE_YDNA;
+            else if (p == "mt") tree_type = DUT_TREE_MTDNA;
+            else { fprintf(stderr, "error: invalid value '%s' for '--tree-type'\n", p.c_str()); return 2; }
+            has_tree_type = true;
+        }
+        else if (a == "--device") device = atoi(next());
+        else if (a == "-h" || a == "--help") { usage_fv(); return 0; }
+        else if (!a.empty() && a[0] != '-' && bam.empty()) bam = a;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fv(); return 2; }
+    }
+    if (bam.empty() || ref.empty() || out.empty()) { usage_fv(); return 2; }
+    if (contig.empty()) { fprintf(stderr, "error: find-variants needs '-L <CONTIG>'\n"); usage_fv(); return 2; }
+    if ((has_provider || has_tree_type) && tree.empty()) { fprintf(stderr, "error: '--provider' and '--tree-type' need '--tree <FILE>'\n"); return 2; }
+    char err[1024] = {0};
+    const int rc = dut_find_variants_files(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end,
+                                           tree.empty() ? nullptr : tree.c_str(), provider, tree_type, out.c_str(), (uint32_t)min_depth,
+                                           (uint8_t)min_quality, device, err, sizeof(err));
+    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
+    fflush(nullptr);
+    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -168,6 +258,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "find-y-branch")) return find_branch_main(argc, argv, DUT_TREE_YDNA);
     if (argc > 1 && !strcmp(argv[1], "find-mt-branch")) return find_branch_main(argc, argv, DUT_TREE_MTDNA);
     if (argc > 1 && !strcmp(argv[1], "fingerprint")) return fingerprint_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "find-variants")) return find_variants_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

@@ -545,6 +545,35 @@ int dut_tree_collect_sites(const dut_tree *t, const char *build_id, const char *
     return CL_OK;
 }
 
+int dut_tree_collect_loci(const dut_tree *t, const char *build_id, const char *ref_name, dut_tree_locus **loci, size_t *n_loci)
+{
+    if (!t || !build_id || !ref_name || !loci || !n_loci) return CL_ERR_INVALID;
+    const std::string build(build_id), chrom(ref_name);
+    std::vector<dut_tree_locus> v;
+    std::vector<const Haplogroup *> stack{&t->root};
+    while (!stack.empty()) {
+        const Haplogroup *h = stack.back(); stack.pop_back();
+        for (const Locus &l : *h->loci)
+            if (const Coord *c = l.get(build))
+                if (l.is_snp && c->chromosome == chrom) v.push_back(dut_tree_locus{c->position, l.name.c_str(), c->ancestral.c_str(), c->derived.c_str()});
+        for (const Haplogroup &c : h->children) stack.push_back(&c);
+    }
+    auto key = [](const dut_tree_locus &a, const dut_tree_locus &b) {
+        if (a.position != b.position) return a.position < b.position;
+        int d = strcmp(a.name, b.name);
+        if (d == 0) d = strcmp(a.ancestral, b.ancestral);
+        if (d == 0) d = strcmp(a.derived, b.derived);
+        return d < 0;
+    };
+    std::sort(v.begin(), v.end(), key);
+    v.erase(std::unique(v.begin(), v.end(), [&](const dut_tree_locus &a, const dut_tree_locus &b) { return !key(a, b) && !key(b, a); }), v.end());
+    dut_tree_locus *o = (dut_tree_locus *)malloc(std::max<size_t>(v.size(), 1) * sizeof(dut_tree_locus));
+    if (!o) return CL_ERR_NOMEM;
+    if (!v.empty()) memcpy(o, v.data(), v.size() * sizeof(dut_tree_locus));
+    *loci = o; *n_loci = v.size();
+    return CL_OK;
+}
+
 int dut_call_sites(const uint32_t *sites, const uint8_t *relevant, const uint32_t *hist, size_t n_sites,
                    uint32_t min_depth, dut_snp_call **calls, size_t *n_calls)
 {

@@ -1,0 +1,101 @@
+"""`find-variants`: where a sample differs from the reference at all, and which of those differences the haplogroup
+tree does not know (include/dut_variants.h).  The counting and the call run on the device (Engine.site_scan); this module
+holds the host side: the per-position classification in plain code, the annotation against a tree, the TSV."""
+import ctypes as C
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+from . import _lib
+from .callable_loci import SCAN_CANDIDATE, EngineError, ScanResult
+from .haplogroup import FTDNA, YDNA, HaplogroupTree
+
+LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
+CLASS_NAMES = ("low_depth", "mixed", "uncomparable", "match", "variant", "undetermined")
+
+
+def _classify(fn, counts, width, ref_byte, min_depth) -> Tuple[int, str]:
+    arr = np.ascontiguousarray(counts, np.uint32)
+    if arr.shape != (width,):
+        raise ValueError(f"expected {width} counters")
+    if isinstance(ref_byte, (str, bytes)):
+        ref_byte = ord(ref_byte)
+    called = C.create_string_buffer(2)
+    st = fn(arr.ctypes.data, int(ref_byte), int(min_depth), called)
+    if st < 0:
+        raise EngineError(st, "invalid counters")
+    return st, called.value.decode()
+
+
+def scan_classify(hist16, ref_byte, min_depth) -> Tuple[int, str]:
+    """(class, called base or '') of one position from its 16-code histogram, by the f64 rule of caller.rs:132-149."""
+    return _classify(_lib.load().dut_scan_classify, hist16, 16, ref_byte, min_depth)
+
+
+def scan_classify_counts(counts5, ref_byte, min_depth) -> Tuple[int, str]:
+    """The same from (a, c, g, t, depth) of Engine.site_scan_counts; UNDETERMINED when the other codes hold 0.7 together."""
+    return _classify(_lib.load().dut_scan_classify_counts, counts5, 5, ref_byte, min_depth)
+
+
+def _candidates(candidates) -> np.ndarray:
+    cand = np.ascontiguousarray(candidates, SCAN_CANDIDATE)
+    return cand.reshape(-1)
+
+
+def annotate_variants(tree: HaplogroupTree, build_id: str, chromosome: str, candidates) -> List[Tuple[bool, str, str]]:
+    """Per candidate (known, names, alleles): dut_variants_annotate; names and alleles are '' for a novel one."""
+    lib = _lib.load()
+    cand = _candidates(candidates)
+    notes = C.POINTER(_lib.dut_variant_note)()
+    st = lib.dut_variants_annotate(tree._h, build_id.encode(), chromosome.encode(), cand.ctypes.data, cand.shape[0], C.byref(notes))
+    if st != 0:
+        raise EngineError(st, "annotation failed")
+    try:
+        return [(bool(notes[i].known), (notes[i].names or b"").decode(), (notes[i].alleles or b"").decode())
+                for i in range(cand.shape[0])]
+    finally:
+        lib.dut_variants_free_notes(notes, cand.shape[0])
+
+
+def write_variants(path: str, contig: str, result: ScanResult, min_depth: int, min_quality: int,
+                   tree: Optional[HaplogroupTree] = None, build_id: Optional[str] = None):
+    """The TSV of find-variants for a ScanResult; with a tree (and its build id) the candidates are annotated."""
+    lib = _lib.load()
+    cand = _candidates(result.candidates)
+    if cand.shape[0] != result.variant:
+        raise ValueError("variant count and candidates disagree")
+    r = _lib.cl_scan_result()
+    r.start, r.end = result.start, result.end
+    r.n_low_depth, r.n_mixed, r.n_uncomparable, r.n_match, r.n_variant = (result.low_depth, result.mixed, result.uncomparable,
+                                                                          result.match, result.variant)
+    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_scan_candidate))
+    notes = C.POINTER(_lib.dut_variant_note)()
+    err = C.create_string_buffer(512)
+    if tree is not None:
+        if not build_id:
+            raise ValueError("a tree needs its build id")
+        st = lib.dut_variants_annotate(tree._h, build_id.encode(), contig.encode(), cand.ctypes.data, cand.shape[0], C.byref(notes))
+        if st != 0:
+            raise EngineError(st, "annotation failed")
+    try:
+        st = lib.dut_variants_write(path.encode(), contig.encode(), C.byref(r), int(min_depth), int(min_quality),
+                                    notes if tree is not None else None, err, 512)
+        if st != 0:
+            raise EngineError(st, err.value.decode())
+    finally:
+        if tree is not None:
+            lib.dut_variants_free_notes(notes, cand.shape[0])
+
+
+def find_variants(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
+                  tree_json: Optional[str] = None, provider: int = FTDNA, tree_type: int = YDNA, min_depth: int = 10,
+                  min_quality: int = 20, device_id: int = 0):
+    """dut_find_variants_files: BAM (+ index) and FASTA in, the TSV out; region = (start, end), 0-based half open."""
+    lib = _lib.load()
+    err = C.create_string_buffer(1024)
+    start, end = region if region is not None else (0, 0)
+    st = lib.dut_find_variants_files(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
+                                     int(start), int(end), tree_json.encode() if tree_json else None, provider, tree_type,
+                                     output_file.encode(), int(min_depth), int(min_quality), device_id, err, 1024)
+    if st != 0:
+        raise EngineError(st, err.value.decode())

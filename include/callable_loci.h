@@ -316,6 +316,45 @@ cl_status cl_site_run(cl_ctx *ctx, uint8_t min_quality, const uint32_t *sites, s
  * counters written). */
 cl_status cl_site_pileup_stats(cl_ctx *ctx, double *kernel_ms, uint64_t *bytes);
 
+/* ---- the dense form: base counts and SNV calls at every position of a range of the resident tile ------------- */
+/* Relative to the tile cl_site_upload left resident (a tile cl_site_pileup filtered for its own list does not serve:
+ * CL_ERR_INVALID, as for cl_site_run), for every position p of [start, end), 0-based half open, end <= contig_len:
+ *   hist[p][c]   what cl_site_run(ctx, min_quality, {p + 1}, 1, ...) returns for the 1-based site p + 1
+ *   a c g t      hist[p][1], [2], [4], [8];  depth = the sum of all 16 codes (bases.len(), caller.rs:133)
+ *   refbase      ref_bases[p] upper-cased if that is one of ACGT, else "other" (N, IUPAC codes, p >= ref_len)
+ *   called       depth >= min_depth and largest hist[p][c] / depth >= 0.7 (caller.rs:132-149; the device takes the
+ *                test as 10 * m >= 7 * depth in 64 bits, which is the same for every depth below 2^32)
+ * and p falls in exactly one class: low_depth (depth < min_depth); mixed (deep enough, not called); uncomparable (called,
+ * but the called code is not A/C/G/T or refbase is "other"); match (called, equal to refbase); variant (called, A/C/G/T
+ * on both sides, different).  The five counts add up to end - start.  The positions of class variant come back as
+ * candidates, all of them, ascending; the counting and the call happen on the device (k_site_scan), what crosses the
+ * link is the reference bytes of the range going in and the candidates coming out.  The call at a position equals what
+ * dut_call_sites makes of cl_site_run's histogram there.  Reads need not be coordinate sorted: counts are exact for any
+ * order (a sorted tile is faster: a window's reads are then a short run of the tile).
+ * ref_len must be the one given to cl_site_upload.  CL_ERR_INVALID (with a message): no resident tile, a filtered
+ * tile, start > end, end > contig_len, min_depth == 0, another ref_len, a null argument; an empty range answers zeros.
+ * CL_ERR_DEVICE: a host-only debug context.  out->candidates is context-owned, valid until the next cl_site_scan,
+ * cl_site_upload or cl_destroy.  Any number of scans per resident tile, interleaved with cl_site_run. */
+typedef struct cl_scan_candidate {
+    uint32_t pos;                 /* 1-based */
+    uint8_t  ref, alt, pad[2];    /* 'A' 'C' 'G' 'T' */
+    uint32_t a, c, g, t, depth;
+} cl_scan_candidate;
+typedef struct cl_scan_result {
+    uint32_t start, end;
+    uint64_t n_low_depth, n_mixed, n_uncomparable, n_match, n_variant;   /* sum == end - start */
+    const cl_scan_candidate *candidates;                                 /* n_variant, ascending position */
+} cl_scan_result;
+cl_status cl_site_scan(cl_ctx *ctx, uint8_t min_quality, uint32_t min_depth, const uint8_t *ref_bases,
+                       uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result *out);
+/* The counters themselves for a short range (at most CL_SCAN_MAX_DENSE positions): counts[(p - start) * 5 + 0..4] =
+ * a, c, g, t, depth, into the caller's array.  Same tile, same refusals. */
+#define CL_SCAN_MAX_DENSE (1u << 20)
+cl_status cl_site_scan_counts(cl_ctx *ctx, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts);
+/* Measurement: the kernel of the last scan by device events (milliseconds) and its algorithmic bytes (4-bit bases,
+ * records and CIGAR words read, reference bytes read, candidates or counters written). */
+cl_status cl_site_scan_stats(cl_ctx *ctx, double *kernel_ms, uint64_t *bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,15 @@ const char *dut_tree_root_name(const dut_tree *t);
 int dut_tree_collect_sites(const dut_tree *t, const char *build_id, const char *ref_name,
                            uint32_t **sites, uint8_t **relevant, size_t *n_sites);
 
+/* The loci behind those sites, for a caller that wants to name them: every SNP locus with coordinates for build_id
+ * whose chromosome there is ref_name, sorted by position, then by name (bytes); a locus that several nodes repeat with
+ * the same alleles comes once.  The strings belong to the tree; the array is malloc'd (dut_free). */
+typedef struct dut_tree_locus {
+    uint32_t    position;       /* 1-based */
+    const char *name, *ancestral, *derived;
+} dut_tree_locus;
+int dut_tree_collect_loci(const dut_tree *t, const char *build_id, const char *ref_name, dut_tree_locus **loci, size_t *n_loci);
+
 /* snp_calls entry: HashMap<u32, (char, u32, f64)> (caller.rs:143-147) */
 typedef struct dut_snp_call {
     uint32_t position;      /* 1-based */

@@ -1,0 +1,66 @@
+/*
+ * dut_variants.h -- the plumbing around the dense site scan (cl_site_scan) of `find-variants`: where does the sample
+ * differ from the reference at all, and which of those differences does the haplogroup tree not know.
+ *
+ * The reference has no such subcommand.  The counting and the call are the ones of find-y-branch / find-mt-branch
+ * (haplogroup::caller::process_region, src/haplogroup/caller.rs:62-152), taken at every position of a contig or a
+ * region instead of at the tree's sites, so the two never disagree about a tree site.  SNVs only: no insertions or
+ * deletions, no base-quality or flag filter (the site tile carries neither), no consensus FASTA.
+ */
+#ifndef DUT_VARIANTS_H
+#define DUT_VARIANTS_H
+
+#include "dut_haplogroup.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The classes of cl_site_scan (include/callable_loci.h). */
+enum { DUT_SCAN_LOW_DEPTH = 0, DUT_SCAN_MIXED = 1, DUT_SCAN_UNCOMPARABLE = 2, DUT_SCAN_MATCH = 3, DUT_SCAN_VARIANT = 4,
+       DUT_SCAN_UNDETERMINED = 5 };
+
+/* One position in plain C++, no device, with the f64 rule of caller.rs:132-149 as dut_call_sites takes it:
+ * depth = sum of the 16 codes, called <=> depth >= min_depth && (largest as f64 / depth as f64) >= 0.7.
+ * ref_byte: the FASTA byte, case preserved (anything but ACGTacgt is "other"; pass 'N' beyond the reference).
+ * *called (may be NULL): the called base ("=ACMGRSVTWYHKDBN") or 0 when there is no call. */
+int dut_scan_classify(const uint32_t hist16[16], uint8_t ref_byte, uint32_t min_depth, char *called);
+/* The same from the five counters of cl_site_scan_counts (a, c, g, t, depth).  The codes that are not A/C/G/T are only
+ * known by their sum: when that sum reaches 0.7 of the depth the position is uncomparable if one code holds it and
+ * mixed if several share it, which five counters cannot tell -- DUT_SCAN_UNDETERMINED. */
+int dut_scan_classify_counts(const uint32_t counts5[5], uint8_t ref_byte, uint32_t min_depth, char *called);
+
+/* What the tree knows about a candidate.  known = 1 when the tree has a SNP locus with coordinates for build_id on
+ * `chromosome` at the position (the "relevant" of dut_tree_collect_sites); then names = the loci's names, ascending,
+ * comma separated, and alleles = per locus, in that order, whether alt is its derived allele, its ancestral allele or
+ * neither: "derived" / "ancestral" / "other".  known = 0 (novel): both NULL. */
+typedef struct dut_variant_note {
+    int   known;
+    char *names;
+    char *alleles;
+} dut_variant_note;
+int dut_variants_annotate(const dut_tree *t, const char *build_id, const char *chromosome,
+                          const cl_scan_candidate *candidates, size_t n, dut_variant_note **notes);
+void dut_variants_free_notes(dut_variant_note *notes, size_t n);
+
+/* The TSV: comment lines ##contig= ##range=start-end (0-based half open) ##min_depth= ##min_quality= ##positions=
+ * ##low_depth= ##mixed= ##uncomparable= ##match= ##variant=, the header
+ *   #contig pos ref alt depth A C G T freq status names alleles
+ * and one line per candidate: pos 1-based, freq = alt count / depth in f64 as %.4f, status novel | known.
+ * notes == NULL (no tree was given): status, names and alleles are all "."; a novel candidate has names and alleles ".". */
+int dut_variants_write(const char *path, const char *contig, const cl_scan_result *res, uint32_t min_depth,
+                       uint8_t min_quality, const dut_variant_note *notes, char *err, size_t err_len);
+
+/* `find-variants` on files, one GPU: open the BAM (its index is required) and the FASTA, read the contig's records,
+ * cl_site_upload, cl_site_scan over the region (has_region == 0: the whole contig), annotate against the tree
+ * (tree_json_path may be NULL: no annotation), write the TSV.  Errors with a message: an unknown contig, a region
+ * that is empty or ends beyond the contig, min_depth == 0, with a tree a BAM header that does not name its genome. */
+int dut_find_variants_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
+                            uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
+                            const char *output_path, uint32_t min_depth, uint8_t min_quality, int device_id,
+                            char *err, size_t err_len);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* DUT_VARIANTS_H */

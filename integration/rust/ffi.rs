@@ -69,6 +69,24 @@ extern "C" {
                                  summary_json: *const c_char, summary_html: *const c_char, opt: *const ClOptions,
                                  contigs: *const *const c_char, n_contigs: usize, devices: *const c_int, n_devices: usize,
                                  flags: c_uint, depth: *const DutDepthOptions, err: *mut c_char, err_len: usize) -> c_int;
+    // the dense form of the site pileup: base counts and SNV calls at every position of a range of the tile
+    // cl_site_upload left resident (README "Variant scan"); candidates are context-owned until the next scan / upload
+    pub fn cl_site_scan(ctx: *mut ClCtx, min_quality: u8, min_depth: u32, ref_bases: *const u8, ref_len: u64,
+                        start: u32, end: u32, out: *mut ClScanResult) -> c_int;
+    pub fn cl_site_scan_counts(ctx: *mut ClCtx, min_quality: u8, start: u32, end: u32, counts: *mut u32) -> c_int; // (end - start) * 5, at most 1 << 20 positions
+    pub fn cl_site_scan_stats(ctx: *mut ClCtx, kernel_ms: *mut f64, bytes: *mut u64) -> c_int;
+    // include/dut_variants.h: classification on the host (f64 rule), annotation against a tree, the TSV, `find-variants` on files
+    pub fn dut_scan_classify(hist16: *const u32, ref_byte: u8, min_depth: u32, called: *mut c_char) -> c_int;
+    pub fn dut_scan_classify_counts(counts5: *const u32, ref_byte: u8, min_depth: u32, called: *mut c_char) -> c_int;
+    pub fn dut_variants_annotate(tree: *const DutTree, build_id: *const c_char, chromosome: *const c_char,
+                                 candidates: *const ClScanCandidate, n: usize, notes: *mut *mut DutVariantNote) -> c_int;
+    pub fn dut_variants_free_notes(notes: *mut DutVariantNote, n: usize);
+    pub fn dut_variants_write(path: *const c_char, contig: *const c_char, res: *const ClScanResult, min_depth: u32,
+                              min_quality: u8, notes: *const DutVariantNote, err: *mut c_char, err_len: usize) -> c_int;
+    pub fn dut_find_variants_files(bam: *const c_char, fasta: *const c_char, contig: *const c_char, has_region: c_int,
+                                   start: u32, end: u32, tree_json: *const c_char, provider: c_int, tree_type: c_int,
+                                   output: *const c_char, min_depth: u32, min_quality: u8, device_id: c_int,
+                                   err: *mut c_char, err_len: usize) -> c_int;
     // include/dut_fingerprint.h: the `fingerprint` sketch on the device (1 <= ksize <= 64)
     pub fn dut_fp_create(opt: *const DutFpOptions, device_id: c_int, stream: *mut c_void, out: *mut *mut DutFpCtx) -> c_int;
     pub fn dut_fp_push_seq4(ctx: *mut DutFpCtx, seq4: *const u8, base_off: *const u64, n_seq: u64) -> c_int;
@@ -82,6 +100,26 @@ extern "C" {
 }
 
 pub enum DutFpCtx {}
+pub enum DutTree {}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ClScanCandidate {      // cl_scan_candidate: pos 1-based, ref / alt ASCII 'A' 'C' 'G' 'T'
+    pub pos: u32, pub ref_base: u8, pub alt: u8, pub pad: [u8; 2],
+    pub a: u32, pub c: u32, pub g: u32, pub t: u32, pub depth: u32,
+}
+
+#[repr(C)]
+pub struct ClScanResult {         // cl_scan_result: the five classes add up to end - start
+    pub start: u32, pub end: u32,
+    pub n_low_depth: u64, pub n_mixed: u64, pub n_uncomparable: u64, pub n_match: u64, pub n_variant: u64,
+    pub candidates: *const ClScanCandidate,                 // n_variant, ascending position
+}
+
+#[repr(C)]
+pub struct DutVariantNote {       // dut_variant_note: names / alleles null when known == 0
+    pub known: c_int, pub names: *mut c_char, pub alleles: *mut c_char,
+}
 pub enum DutDepthAcc {}
 
 #[repr(C)]
