@@ -146,6 +146,32 @@ class cl_scan_result(C.Structure):
                 ("candidates", C.POINTER(cl_scan_candidate))]
 
 
+class cl_site_quals(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("flag", C.c_void_p), ("qual_off", C.c_void_p), ("qual", C.c_void_p),
+                ("seq_off", C.c_void_p)]
+
+
+class cl_scan_filter(C.Structure):
+    _fields_ = [("exclude_flags", C.c_uint16), ("use_base_quality", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class cl_scan_candidate_ex(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8), ("pad", C.c_uint8 * 2),
+                ("a", C.c_uint32), ("c", C.c_uint32), ("g", C.c_uint32), ("t", C.c_uint32), ("depth", C.c_uint32),
+                ("alt_fwd", C.c_uint32), ("alt_rev", C.c_uint32), ("ref_fwd", C.c_uint32), ("ref_rev", C.c_uint32)]
+
+
+class cl_scan_result_ex(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_low_depth", C.c_uint64), ("n_mixed", C.c_uint64),
+                ("n_uncomparable", C.c_uint64), ("n_match", C.c_uint64), ("n_variant", C.c_uint64),
+                ("candidates", C.POINTER(cl_scan_candidate_ex))]
+
+
+class dut_variants_options(C.Structure):
+    _fields_ = [("filtered", C.c_int), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
+                ("exclude_flags", C.c_uint16), ("min_alt_per_strand", C.c_uint32)]
+
+
 class dut_variant_note(C.Structure):
     _fields_ = [("known", C.c_int), ("names", C.c_char_p), ("alleles", C.c_char_p)]
 
@@ -162,7 +188,19 @@ SYMBOLS = [
                                C.POINTER(cl_scan_result)]),
     ("cl_site_scan_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_uint32, C.c_void_p]),
     ("cl_site_scan_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("cl_site_attach_quals", C.c_int, [C.c_void_p, C.POINTER(cl_site_quals), C.c_uint8]),
+    ("cl_site_scan_ex", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.POINTER(cl_scan_filter), C.c_void_p, C.c_uint64, C.c_uint32,
+                                  C.c_uint32, C.POINTER(cl_scan_result_ex)]),
+    ("cl_site_scan_counts_ex", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
+    ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.POINTER(dut_variant_note))]),
+    ("dut_variants_write_ex", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_scan_result_ex), C.c_uint32, C.c_uint8,
+                                        C.POINTER(dut_variants_options), C.POINTER(dut_variant_note), C.c_char_p, C.c_size_t]),
+    ("dut_find_variants_files_ex", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p,
+                                             C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint8, C.POINTER(dut_variants_options),
+                                             C.c_int, C.c_char_p, C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

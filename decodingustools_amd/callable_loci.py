@@ -74,6 +74,25 @@ def _records_c(rec: ContigRecords):
     return r
 
 
+def _site_quals(rec: ContigRecords):
+    q = _lib.cl_site_quals()
+    q.n_reads = rec.n
+    q.flag = _ptr(rec.flag); q.qual_off = _ptr(rec.qual_off); q.qual = _ptr(rec.qual); q.seq_off = _ptr(rec.seq_off)
+    return q
+
+
+def site_pass_bits(rec: ContigRecords, min_base_quality) -> np.ndarray:
+    """cl_debug_site_pass_bits (host only): the attachment's pass bits as uint64 words, bit i of word w <-> base 64 w + i
+    in the numbering of rec.seq_off."""
+    n_words = (int(rec.seq_off[-1]) + 63) // 64
+    out = np.zeros(n_words, np.uint64)
+    q = _site_quals(rec)
+    st = _lib.load().cl_debug_site_pass_bits(C.byref(q), int(min_base_quality), _ptr(out), n_words)
+    if st != 0:
+        raise EngineError(st, "invalid attachment")
+    return out
+
+
 class Engine:
     """One device context (cl_ctx): one per GPU, driven by one host thread."""
 
@@ -259,8 +278,38 @@ class Engine:
         self._check(self._lib.cl_site_scan_counts(self._h, int(min_quality), int(start), int(end), _ptr(counts)))
         return counts
 
+    def site_attach_quals(self, rec: ContigRecords, min_base_quality):
+        """cl_site_attach_quals: the flags and, per base, (qual >= min_base_quality) of `rec` -- the records the resident
+        tile was uploaded from -- for site_scan_ex / site_scan_counts_ex.  Replaces an earlier attachment."""
+        q = _site_quals(rec)
+        self._check(self._lib.cl_site_attach_quals(self._h, C.byref(q), int(min_base_quality)))
+
+    def site_scan_ex(self, min_quality, min_depth, ref, exclude_flags=0, use_base_quality=False, start=0, end=None):
+        """cl_site_scan_ex: site_scan under a flag mask and (use_base_quality) the attachment's pass bits; the candidates
+        (SCAN_CANDIDATE_EX) also carry alt_fwd, alt_rev, ref_fwd, ref_rev."""
+        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
+        if end is None:
+            end = ref.shape[0]
+        f = _lib.cl_scan_filter(int(exclude_flags), 1 if use_base_quality else 0, 0)
+        r = _lib.cl_scan_result_ex()
+        self._check(self._lib.cl_site_scan_ex(self._h, int(min_quality), int(min_depth), C.byref(f), _ptr(ref), ref.shape[0],
+                                              int(start), int(end), C.byref(r)))
+        n = int(r.n_variant)
+        cand = np.zeros(n, SCAN_CANDIDATE_EX)
+        if n:
+            C.memmove(cand.ctypes.data, r.candidates, n * SCAN_CANDIDATE_EX.itemsize)
+        return ScanResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), mixed=int(r.n_mixed),
+                          uncomparable=int(r.n_uncomparable), match=int(r.n_match), variant=n, candidates=cand)
+
+    def site_scan_counts_ex(self, min_quality, start, end, exclude_flags=0, use_base_quality=False):
+        """cl_site_scan_counts_ex: (end - start, 9) uint32 -- A+ A- C+ C- G+ G- T+ T- depth (+ forward, - reverse)."""
+        counts = np.zeros((max(int(end) - int(start), 0), 9), np.uint32)
+        f = _lib.cl_scan_filter(int(exclude_flags), 1 if use_base_quality else 0, 0)
+        self._check(self._lib.cl_site_scan_counts_ex(self._h, int(min_quality), C.byref(f), int(start), int(end), _ptr(counts)))
+        return counts
+
     def site_scan_stats(self):
-        """(kernel milliseconds, algorithmic bytes) of the last site_scan / site_scan_counts."""
+        """(kernel milliseconds, algorithmic bytes) of the last site_scan / site_scan_counts, filtered or not."""
         ms = C.c_double(); b = C.c_uint64()
         self._check(self._lib.cl_site_scan_stats(self._h, C.byref(ms), C.byref(b)))
         return ms.value, b.value
@@ -285,6 +334,9 @@ class Engine:
 # cl_scan_candidate as a numpy record: pos is 1-based, ref and alt are ASCII codes
 SCAN_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("alt", np.uint8), ("pad", np.uint8, (2,)), ("a", np.uint32),
                            ("c", np.uint32), ("g", np.uint32), ("t", np.uint32), ("depth", np.uint32)])
+# cl_scan_candidate_ex: a c g t depth over both strands, the alternative and reference base by strand
+SCAN_CANDIDATE_EX = np.dtype(SCAN_CANDIDATE.descr + [("alt_fwd", np.uint32), ("alt_rev", np.uint32), ("ref_fwd", np.uint32),
+                                                     ("ref_rev", np.uint32)])
 
 
 @dataclass

@@ -6,6 +6,8 @@
 #include "kernels.hip.h"
 #include "depth_profile.hip.h"
 #include "site_scan.hip.h"
+#include "site_scan_ex.hip.h"
+#include "site_pass_bits.h"
 #include "host_parallel.h"
 #include "qual_pack.h"
 #include "pass_rows.h"
@@ -291,8 +293,16 @@ struct SiteResident {
     DevBuf<unsigned long long> sc_cls;
     DevBuf<ScanCand> sc_cand;
     bool scan_indexed = false;
+    // cl_site_attach_quals: one pass bit per base of seq, one flag per read; the filtered scan's candidates, ambiguous
+    // positions and their 16-code histograms, dense counters
+    DevBuf<unsigned long long> q_pass;
+    DevBuf<uint16_t> q_flag;
+    DevBuf<ScanCandEx> sx_cand;
+    DevBuf<uint32_t> sx_amb, sx_hist, sx_dense;
+    bool attached = false;
     void release()
     {
+        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sx_dense.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -429,6 +439,7 @@ struct cl_ctx {
     double scan_ms = 0.0;
     uint64_t scan_bytes = 0;
     std::vector<cl_scan_candidate> scan_cand;
+    std::vector<cl_scan_candidate_ex> scan_cand_ex;
 };
 
 static void join_prealloc(cl_ctx *c) { if (c->prealloc.joinable()) c->prealloc.join(); }   // (cl_contig_reserve's helper thread)
@@ -2778,7 +2789,7 @@ static cl_status cl_site_upload_impl(cl_ctx *c, uint32_t contig_len, uint64_t re
     HIP_TRY(c, hipSetDevice(c->device));
     drop_prefetch(c);                                        // the ring is needed below
     SiteResident &S = c->site;
-    S.resident = false; S.filtered = false; S.scan_indexed = false;
+    S.resident = false; S.filtered = false; S.scan_indexed = false; S.attached = false;
     const uint64_t n_all = t->n_reads;
     if (n_all > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "too many reads");
     if (n_all && (!t->pos || !t->mapq || !t->cigar_off || !t->seq_off)) return fail(c, CL_ERR_INVALID, "null tile array");
@@ -3112,6 +3123,222 @@ cl_status cl_site_scan_counts(cl_ctx *c, uint8_t min_quality, uint32_t start, ui
     try { return cl_site_scan_counts_impl(c, min_quality, start, end, counts); }
     catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
     catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+}
+
+// ---- the filtered, strand-aware form (site_scan_ex.hip.h): the attachment, the scan, the dense counters ----
+static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
+
+static cl_status site_quals_check(const cl_site_quals *q, std::string &why)
+{
+    if (!q) { why = "null attachment"; return CL_ERR_INVALID; }
+    if (!q->qual_off || !q->seq_off || (q->n_reads && !q->flag)) { why = "null attachment array"; return CL_ERR_INVALID; }
+    std::atomic<int> bad{0};
+    dut::parallel_for(q->n_reads, 262144, [&](size_t i) { if (q->qual_off[i + 1] < q->qual_off[i] || q->seq_off[i + 1] < q->seq_off[i]) bad = 1; });
+    if (bad) { why = "offset arrays must be non-decreasing"; return CL_ERR_INVALID; }
+    if (q->qual_off[q->n_reads] > q->qual_off[0] && !q->qual) { why = "null quality array"; return CL_ERR_INVALID; }
+    return CL_OK;
+}
+
+static cl_status cl_site_attach_quals_impl(cl_ctx *c, const cl_site_quals *q, uint8_t min_base_quality)
+{
+    if (!c) return CL_ERR_INVALID;
+    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
+    SiteResident &S = c->site;
+    if (!S.resident) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals without cl_site_upload");
+    if (S.filtered) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: the resident tile was uploaded by cl_site_pileup for its own site list; cl_site_upload gives a tile that serves a scan");
+    std::string why;
+    if (site_quals_check(q, why) != CL_OK) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: " + why);
+    if (q->n_reads != S.n) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: n_reads differs from the resident tile's");
+    if (q->seq_off[q->n_reads] != S.nbase) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: seq_off is not the one of the resident tile");
+    HIP_TRY(c, hipSetDevice(c->device));
+    drop_prefetch(c);                                        // the ring is needed below
+    S.attached = false;
+    StageTimer tmr;
+    const uint64_t n = S.n, n_words = (S.nbase + 63) / 64;
+    HIP_TRY(c, S.q_pass.reserve(n_words + 2)); HIP_TRY(c, S.q_flag.reserve(n + 1));
+    if (n_words) {
+        const cl_site_quals Q = *q;
+        cl_status rs = ring_start(c, reinterpret_cast<uint8_t *>(S.q_pass.p), n_words * 8, [Q, min_base_quality](uint64_t off, uint64_t len, uint8_t *out) {
+            // (a buffer is a whole number of words)
+            dut::site_pass_words(Q.n_reads, Q.seq_off, Q.qual_off, Q.qual, min_base_quality, off / 8, (off + len) / 8, reinterpret_cast<uint64_t *>(out));
+        }, PinRing::kPinBytes, PinRing::kCopyThreads);
+        if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
+        if (rs != CL_OK) return rs;
+    }
+    cl_status rs = CL_OK;
+    if (n && (rs = ring_copy(c, S.q_flag.p, q->flag, n * 2)) != CL_OK) return rs;
+    tmr.lap("site attach: pass bits + flags");
+    S.attached = true;
+    return CL_OK;
+}
+
+static cl_status site_scan_ex_check(cl_ctx *c, const char *who, const cl_scan_filter *f, uint32_t start, uint32_t end)
+{
+    cl_status s = site_scan_check(c, who, start, end);
+    if (s != CL_OK) return s;
+    if (!f) return fail(c, CL_ERR_INVALID, std::string(who) + ": null filter");
+    if (!c->site.attached) return fail(c, CL_ERR_INVALID, std::string(who) + " without cl_site_attach_quals on the resident tile");
+    return CL_OK;
+}
+
+static void site_scan_ex_fill(cl_ctx *c, ScanExArgs &A, const cl_scan_filter *f, uint8_t min_quality, uint32_t min_depth, uint32_t start, uint32_t end)
+{
+    SiteResident &S = c->site;
+    site_scan_fill(c, A.s, min_quality, min_depth, start, end);
+    A.flag = S.q_flag.p; A.pass = S.q_pass.p; A.exclude_flags = f->exclude_flags; A.use_bq = f->use_base_quality ? 1u : 0u;
+    A.cand = nullptr; A.dense = nullptr;
+}
+
+// the tile bytes a filtered scan reads: those of cl_site_scan, the pass bits and the flags
+static uint64_t site_scan_ex_tile_bytes(const SiteResident &S)
+{
+    return (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + (S.nbase + 7) / 8 + S.n * 2;
+}
+
+static cl_status cl_site_scan_ex_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const cl_scan_filter *filter, const uint8_t *ref_bases,
+                                      uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out)
+{
+    if (!c) return CL_ERR_INVALID;
+    if (!out) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: null result");
+    cl_status s = site_scan_ex_check(c, "cl_site_scan_ex", filter, start, end);
+    if (s != CL_OK) return s;
+    SiteResident &S = c->site;
+    if (min_depth == 0) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: min_depth must be at least 1");
+    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: ref_len differs from the one given to cl_site_upload");
+    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: null reference");
+    memset(out, 0, sizeof(*out));
+    out->start = start; out->end = end;
+    c->scan_cand_ex.clear();
+    out->candidates = c->scan_cand_ex.data();
+    c->scan_ms = 0.0; c->scan_bytes = 0;
+    if (start == end) return CL_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    StageTimer tmr;
+    if ((s = site_scan_index(c)) != CL_OK) return s;
+    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len), n_ref = ref_hi > start ? ref_hi - start : 0;
+    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
+    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
+    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
+    const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
+    // the candidate buffer grows and the scan runs again when more are wanted, as in cl_site_scan
+    uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
+    unsigned long long h_cls[8];
+    double ms_all = 0.0;
+    ScanExArgs A;
+    for (;;) {
+        HIP_TRY(c, S.sx_cand.reserve(cap));
+        HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
+        site_scan_ex_fill(c, A, filter, min_quality, min_depth, start, end);
+        A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
+        A.cand = S.sx_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+        HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
+        hipLaunchKernelGGL(k_site_scan_ex<false>, dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
+        HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float t = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
+        ms_all += t;
+        const uint64_t want = (uint32_t)h_cls[SCAN_CLASSES];
+        if (want <= cap) break;
+        cap = want;
+    }
+    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
+    c->scan_cand_ex.resize(n_cand);
+    if (n_cand) HIP_TRY(c, hipMemcpy(c->scan_cand_ex.data(), S.sx_cand.p, n_cand * sizeof(cl_scan_candidate_ex), hipMemcpyDeviceToHost));
+    c->scan_ms = ms_all;
+    c->scan_bytes = site_scan_ex_tile_bytes(S) + n_ref + n_cand * sizeof(cl_scan_candidate_ex);
+    tmr.lap("filtered site scan: reference in, kernel, candidates back");
+    std::sort(c->scan_cand_ex.begin(), c->scan_cand_ex.end(), [](const cl_scan_candidate_ex &a, const cl_scan_candidate_ex &b) { return a.pos < b.pos; });
+    out->n_low_depth = h_cls[SCAN_LOW_DEPTH]; out->n_mixed = h_cls[SCAN_MIXED]; out->n_uncomparable = h_cls[SCAN_UNCOMPARABLE];
+    out->n_match = h_cls[SCAN_MATCH]; out->n_variant = h_cls[SCAN_VARIANT];
+    if (h_cls[SCAN_AMBIGUOUS]) {
+        // the positions ten planes cannot classify: their 16-code histograms under the same filter (k_site_scan_settle)
+        std::vector<uint32_t> amb;
+        size_t k = 0;
+        for (const cl_scan_candidate_ex &cd : c->scan_cand_ex) { if (cd.alt == 0) amb.push_back(cd.pos); else c->scan_cand_ex[k++] = cd; }
+        c->scan_cand_ex.resize(k);
+        std::vector<uint32_t> hist(amb.size() * 16);
+        HIP_TRY(c, S.sx_amb.reserve(amb.size())); HIP_TRY(c, S.sx_hist.reserve(hist.size()));
+        HIP_TRY(c, hipMemcpyAsync(S.sx_amb.p, amb.data(), amb.size() * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_site_scan_settle, dim3((uint32_t)amb.size()), dim3(kBlock), 0, c->stream, A, S.sx_amb.p, S.sx_hist.p);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(hist.data(), S.sx_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < amb.size(); ++i) {
+            uint64_t depth = 0, m = 0;
+            for (int q = 0; q < 16; ++q) { depth += hist[i * 16 + q]; m = std::max<uint64_t>(m, hist[i * 16 + q]); }
+            if (10 * m >= 7 * depth) ++out->n_uncomparable; else ++out->n_mixed;
+        }
+        tmr.lap("filtered site scan: ambiguous positions settled");
+    }
+    out->candidates = c->scan_cand_ex.data();
+    return CL_OK;
+}
+
+static cl_status cl_site_scan_counts_ex_impl(cl_ctx *c, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)
+{
+    if (!c) return CL_ERR_INVALID;
+    cl_status s = site_scan_ex_check(c, "cl_site_scan_counts_ex", filter, start, end);
+    if (s != CL_OK) return s;
+    if (end - start > CL_SCAN_MAX_DENSE) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts_ex: more than CL_SCAN_MAX_DENSE positions");
+    c->scan_ms = 0.0; c->scan_bytes = 0;
+    if (start == end) return CL_OK;
+    if (!counts) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts_ex: null array");
+    SiteResident &S = c->site;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((s = site_scan_index(c)) != CL_OK) return s;
+    const size_t n9 = (size_t)(end - start) * 9;
+    HIP_TRY(c, S.sx_dense.reserve(n9));
+    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
+    ScanExArgs A;
+    site_scan_ex_fill(c, A, filter, min_quality, 1, start, end);
+    A.dense = S.sx_dense.p;
+    HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
+    hipLaunchKernelGGL(k_site_scan_ex<true>, dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counts, S.sx_dense.p, n9 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float t = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
+    c->scan_ms = t;
+    c->scan_bytes = site_scan_ex_tile_bytes(S) + n9 * 4;
+    return CL_OK;
+}
+
+cl_status cl_site_attach_quals(cl_ctx *c, const cl_site_quals *quals, uint8_t min_base_quality)
+{
+    try { return cl_site_attach_quals_impl(c, quals, min_base_quality); }
+    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
+    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+}
+
+cl_status cl_site_scan_ex(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const cl_scan_filter *filter, const uint8_t *ref_bases,
+                          uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out)
+{
+    try { return cl_site_scan_ex_impl(c, min_quality, min_depth, filter, ref_bases, ref_len, start, end, out); }
+    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
+    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+}
+
+cl_status cl_site_scan_counts_ex(cl_ctx *c, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)
+{
+    try { return cl_site_scan_counts_ex_impl(c, min_quality, filter, start, end, counts); }
+    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
+    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+}
+
+cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words)
+{
+    try {
+        std::string why;
+        if (site_quals_check(quals, why) != CL_OK || (n_words && !words_out)) return CL_ERR_INVALID;
+        dut::site_pass_words(quals->n_reads, quals->seq_off, quals->qual_off, quals->qual, min_base_quality, 0, n_words, words_out);
+        return CL_OK;
+    }
+    catch (...) { return CL_ERR_NOMEM; }
 }
 
 cl_status cl_site_scan_stats(cl_ctx *c, double *kernel_ms, uint64_t *bytes)

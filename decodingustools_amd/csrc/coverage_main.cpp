@@ -9,6 +9,7 @@
 #include "../../include/dut_fingerprint.h"
 #include "../../include/dut_variants.h"
 
+#include <cctype>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -164,11 +165,15 @@ static int find_variants_main(int argc, char **argv)
     unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
     int provider = DUT_PROVIDER_FTDNA, tree_type = DUT_TREE_YDNA, device = 0;
     bool has_provider = false, has_tree_type = false, has_region = false;
+    dut_variants_options vopt = {0, 0, 0, 0, 0};
     auto usage_fv = []() {
         fprintf(stderr, "Usage: dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
                         "       [--min-depth 10] [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
-                        "  --region: 0-based, half open, within the contig.  SNVs only; every fetched record counts (no flag or\n"
-                        "  base-quality filter), as in find-y-branch.\n");
+                        "       [--min-base-quality Q] [--exclude-flags MASK] [--min-alt-per-strand K]\n"
+                        "  --region: 0-based, half open, within the contig.  SNVs only.  Without the last three flags every fetched\n"
+                        "  record counts (no flag or base-quality filter), as in find-y-branch.  With any of them: bases below Q\n"
+                        "  (0..255) and reads with a flag bit of MASK (decimal or 0x hex, 0..65535) do not count, the TSV gains\n"
+                        "  alt_fwd alt_rev ref_fwd ref_rev filter, and filter is 'strand' when min(alt_fwd, alt_rev) < K.\n");
     };
     auto number = [](const char *flag, const std::string &v, unsigned long long &dst) -> bool {
         char *e = nullptr;
@@ -210,6 +215,29 @@ static int find_variants_main(int argc, char **argv)
             if (!number("--min-quality", next(), min_quality)) return 2;
             if (min_quality > 255) { fprintf(stderr, "error: invalid value '%llu' for '--min-quality': 0..255\n", min_quality); return 2; }
         }
+        else if (a == "--min-base-quality") {
+            const std::string v = next();
+            unsigned long long q = 0;
+            if (!number("--min-base-quality", v, q)) return 2;
+            if (q > 255) { fprintf(stderr, "error: invalid value '%s' for '--min-base-quality': 0..255\n", v.c_str()); return 2; }
+            vopt.filtered = 1; vopt.has_min_base_quality = 1; vopt.min_base_quality = (uint8_t)q;
+        }
+        else if (a == "--exclude-flags") {
+            const std::string v = next();
+            const bool hex = v.size() > 2 && v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+            char *e = nullptr;
+            errno = 0;
+            const unsigned long long m = (hex ? isxdigit((unsigned char)v[2]) : (!v.empty() && isdigit((unsigned char)v[0]))) ? strtoull(v.c_str(), &e, hex ? 16 : 10) : 0;
+            if (!e || errno || *e || m > 65535) { fprintf(stderr, "error: invalid value '%s' for '--exclude-flags': 0..65535, decimal or 0x hex\n", v.c_str()); return 2; }
+            vopt.filtered = 1; vopt.exclude_flags = (uint16_t)m;
+        }
+        else if (a == "--min-alt-per-strand") {
+            const std::string v = next();
+            unsigned long long k = 0;
+            if (!number("--min-alt-per-strand", v, k)) return 2;
+            if (k > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%s' for '--min-alt-per-strand'\n", v.c_str()); return 2; }
+            vopt.filtered = 1; vopt.min_alt_per_strand = (uint32_t)k;
+        }
         else if (a == "--provider") {
             const std::string p = next();
             if (p == "ftdna") provider = DUT_PROVIDER_FTDNA;
@@ -233,9 +261,9 @@ static int find_variants_main(int argc, char **argv)
     if (contig.empty()) { fprintf(stderr, "error: find-variants needs '-L <CONTIG>'\n"); usage_fv(); return 2; }
     if ((has_provider || has_tree_type) && tree.empty()) { fprintf(stderr, "error: '--provider' and '--tree-type' need '--tree <FILE>'\n"); return 2; }
     char err[1024] = {0};
-    const int rc = dut_find_variants_files(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end,
-                                           tree.empty() ? nullptr : tree.c_str(), provider, tree_type, out.c_str(), (uint32_t)min_depth,
-                                           (uint8_t)min_quality, device, err, sizeof(err));
+    const int rc = dut_find_variants_files_ex(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end,
+                                              tree.empty() ? nullptr : tree.c_str(), provider, tree_type, out.c_str(), (uint32_t)min_depth,
+                                              (uint8_t)min_quality, &vopt, device, err, sizeof(err));
     if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
     fflush(nullptr);
     _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)

@@ -1,6 +1,6 @@
 // variants.cpp -- implementation of include/dut_variants.h: the per-position classification in plain C++ (the f64 rule
 // the device's integer test is held against), the annotation of candidates against a haplogroup tree, the TSV of
-// `find-variants`.  Host-only except dut_find_variants_files, which runs the device engine's cl_site_scan.
+// `find-variants`.  Host-only except dut_find_variants_files(_ex), which runs the device engine's cl_site_scan(_ex).
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -11,6 +11,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "host_parallel.h"
 
@@ -42,6 +43,81 @@ char *dup(const std::string &s)
     char *p = (char *)malloc(s.size() + 1);
     if (p) memcpy(p, s.c_str(), s.size() + 1);
     return p;
+}
+
+template <class Cand>
+int annotate(const dut_tree *t, const char *build_id, const char *chromosome, const Cand *candidates, size_t n, dut_variant_note **notes)
+{
+    if (!t || !build_id || !chromosome || (n && !candidates) || !notes) return CL_ERR_INVALID;
+    dut_tree_locus *lp = nullptr; size_t nl = 0;
+    const int rc = dut_tree_collect_loci(t, build_id, chromosome, &lp, &nl);
+    if (rc != CL_OK) return rc;
+    std::unique_ptr<dut_tree_locus, decltype(&free)> loci(lp, free);
+    dut_variant_note *o = (dut_variant_note *)calloc(std::max<size_t>(n, 1), sizeof(dut_variant_note));
+    if (!o) return CL_ERR_NOMEM;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t pos = candidates[i].pos;
+        const dut_tree_locus *b = std::lower_bound(lp, lp + nl, pos, [](const dut_tree_locus &l, uint32_t p) { return l.position < p; });
+        if (b == lp + nl || b->position != pos) continue;                     // novel
+        std::string names, alleles;
+        for (; b != lp + nl && b->position == pos; ++b) {
+            if (!names.empty()) { names += ","; alleles += ","; }
+            names += b->name;
+            const char alt = (char)candidates[i].alt;
+            alleles += (b->derived[0] && b->derived[0] == alt) ? "derived" : (b->ancestral[0] && b->ancestral[0] == alt) ? "ancestral" : "other";
+        }
+        o[i].known = 1; o[i].names = dup(names); o[i].alleles = dup(alleles);
+        if (!o[i].names || !o[i].alleles) { dut_variants_free_notes(o, n); return CL_ERR_NOMEM; }
+    }
+    *notes = o;
+    return CL_OK;
+}
+
+// opt: the extended TSV of dut_variants_write_ex (Res = cl_scan_result_ex); nullptr: the one of dut_variants_write
+template <class Res>
+int write_tsv(const char *path, const char *contig, const Res *res, uint32_t min_depth, uint8_t min_quality,
+              const dut_variants_options *opt, const dut_variant_note *notes, char *err, size_t err_len)
+{
+    if (!path || !contig || !res || (res->n_variant && !res->candidates)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    std::string s;
+    char b[512];
+    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n", contig, res->start, res->end,
+             min_depth, (unsigned)min_quality);
+    s += b;
+    if (opt) {
+        if (opt->has_min_base_quality) snprintf(b, sizeof(b), "##min_base_quality=%u\n##exclude_flags=0x%04x\n", (unsigned)opt->min_base_quality, (unsigned)opt->exclude_flags);
+        else snprintf(b, sizeof(b), "##min_base_quality=.\n##exclude_flags=0x%04x\n", (unsigned)opt->exclude_flags);
+        s += b;
+    }
+    snprintf(b, sizeof(b), "##positions=%u\n", res->end - res->start);
+    s += b;
+    snprintf(b, sizeof(b), "##low_depth=%llu\n##mixed=%llu\n##uncomparable=%llu\n##match=%llu\n##variant=%llu\n",
+             (unsigned long long)res->n_low_depth, (unsigned long long)res->n_mixed, (unsigned long long)res->n_uncomparable,
+             (unsigned long long)res->n_match, (unsigned long long)res->n_variant);
+    s += b;
+    s += "#contig\tpos\tref\talt\tdepth\tA\tC\tG\tT\tfreq\tstatus\tnames\talleles";
+    s += opt ? "\talt_fwd\talt_rev\tref_fwd\tref_rev\tfilter\n" : "\n";
+    for (uint64_t i = 0; i < res->n_variant; ++i) {
+        const auto &c = res->candidates[i];
+        const uint32_t ac = c.alt == 'A' ? c.a : c.alt == 'C' ? c.c : c.alt == 'G' ? c.g : c.t;
+        const double freq = c.depth ? (double)ac / (double)c.depth : 0.0;
+        snprintf(b, sizeof(b), "\t%u\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%.4f\t", c.pos, (char)c.ref, (char)c.alt, c.depth, c.a, c.c, c.g, c.t, freq);
+        s += contig; s += b;
+        if (!notes) s += ".\t.\t.";
+        else if (!notes[i].known) s += "novel\t.\t.";
+        else { s += "known\t"; s += notes[i].names ? notes[i].names : "."; s += "\t"; s += notes[i].alleles ? notes[i].alleles : "."; }
+        if constexpr (std::is_same<Res, cl_scan_result_ex>::value) {
+            const bool strand = std::min(c.alt_fwd, c.alt_rev) < opt->min_alt_per_strand;
+            snprintf(b, sizeof(b), "\t%u\t%u\t%u\t%u\t%s", c.alt_fwd, c.alt_rev, c.ref_fwd, c.ref_rev, strand ? "strand" : "PASS");
+            s += b;
+        }
+        s += "\n";
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) { set_err(err, err_len, std::string("cannot create ") + path); return CL_ERR_INVALID; }
+    const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
+    if (fclose(f) != 0 || !ok) { set_err(err, err_len, std::string("cannot write ") + path); return CL_ERR_INVALID; }
+    return CL_OK;
 }
 
 } // namespace
@@ -82,29 +158,13 @@ int dut_scan_classify_counts(const uint32_t counts5[5], uint8_t ref_byte, uint32
 int dut_variants_annotate(const dut_tree *t, const char *build_id, const char *chromosome,
                           const cl_scan_candidate *candidates, size_t n, dut_variant_note **notes)
 {
-    if (!t || !build_id || !chromosome || (n && !candidates) || !notes) return CL_ERR_INVALID;
-    dut_tree_locus *lp = nullptr; size_t nl = 0;
-    const int rc = dut_tree_collect_loci(t, build_id, chromosome, &lp, &nl);
-    if (rc != CL_OK) return rc;
-    std::unique_ptr<dut_tree_locus, decltype(&free)> loci(lp, free);
-    dut_variant_note *o = (dut_variant_note *)calloc(std::max<size_t>(n, 1), sizeof(dut_variant_note));
-    if (!o) return CL_ERR_NOMEM;
-    for (size_t i = 0; i < n; ++i) {
-        const uint32_t pos = candidates[i].pos;
-        const dut_tree_locus *b = std::lower_bound(lp, lp + nl, pos, [](const dut_tree_locus &l, uint32_t p) { return l.position < p; });
-        if (b == lp + nl || b->position != pos) continue;                     // novel
-        std::string names, alleles;
-        for (; b != lp + nl && b->position == pos; ++b) {
-            if (!names.empty()) { names += ","; alleles += ","; }
-            names += b->name;
-            const char alt = (char)candidates[i].alt;
-            alleles += (b->derived[0] && b->derived[0] == alt) ? "derived" : (b->ancestral[0] && b->ancestral[0] == alt) ? "ancestral" : "other";
-        }
-        o[i].known = 1; o[i].names = dup(names); o[i].alleles = dup(alleles);
-        if (!o[i].names || !o[i].alleles) { dut_variants_free_notes(o, n); return CL_ERR_NOMEM; }
-    }
-    *notes = o;
-    return CL_OK;
+    return annotate(t, build_id, chromosome, candidates, n, notes);
+}
+
+int dut_variants_annotate_ex(const dut_tree *t, const char *build_id, const char *chromosome,
+                             const cl_scan_candidate_ex *candidates, size_t n, dut_variant_note **notes)
+{
+    return annotate(t, build_id, chromosome, candidates, n, notes);
 }
 
 void dut_variants_free_notes(dut_variant_note *notes, size_t n)
@@ -117,39 +177,21 @@ void dut_variants_free_notes(dut_variant_note *notes, size_t n)
 int dut_variants_write(const char *path, const char *contig, const cl_scan_result *res, uint32_t min_depth,
                        uint8_t min_quality, const dut_variant_note *notes, char *err, size_t err_len)
 {
-    if (!path || !contig || !res || (res->n_variant && !res->candidates)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
-    std::string s;
-    char b[512];
-    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n##positions=%u\n", contig, res->start, res->end,
-             min_depth, (unsigned)min_quality, res->end - res->start);
-    s += b;
-    snprintf(b, sizeof(b), "##low_depth=%llu\n##mixed=%llu\n##uncomparable=%llu\n##match=%llu\n##variant=%llu\n",
-             (unsigned long long)res->n_low_depth, (unsigned long long)res->n_mixed, (unsigned long long)res->n_uncomparable,
-             (unsigned long long)res->n_match, (unsigned long long)res->n_variant);
-    s += b;
-    s += "#contig\tpos\tref\talt\tdepth\tA\tC\tG\tT\tfreq\tstatus\tnames\talleles\n";
-    for (uint64_t i = 0; i < res->n_variant; ++i) {
-        const cl_scan_candidate &c = res->candidates[i];
-        const uint32_t ac = c.alt == 'A' ? c.a : c.alt == 'C' ? c.c : c.alt == 'G' ? c.g : c.t;
-        const double freq = c.depth ? (double)ac / (double)c.depth : 0.0;
-        snprintf(b, sizeof(b), "\t%u\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%.4f\t", c.pos, (char)c.ref, (char)c.alt, c.depth, c.a, c.c, c.g, c.t, freq);
-        s += contig; s += b;
-        if (!notes) s += ".\t.\t.";
-        else if (!notes[i].known) s += "novel\t.\t.";
-        else { s += "known\t"; s += notes[i].names ? notes[i].names : "."; s += "\t"; s += notes[i].alleles ? notes[i].alleles : "."; }
-        s += "\n";
-    }
-    FILE *f = fopen(path, "wb");
-    if (!f) { set_err(err, err_len, std::string("cannot create ") + path); return CL_ERR_INVALID; }
-    const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
-    if (fclose(f) != 0 || !ok) { set_err(err, err_len, std::string("cannot write ") + path); return CL_ERR_INVALID; }
-    return CL_OK;
+    return write_tsv(path, contig, res, min_depth, min_quality, nullptr, notes, err, err_len);
+}
+
+int dut_variants_write_ex(const char *path, const char *contig, const cl_scan_result_ex *res, uint32_t min_depth,
+                          uint8_t min_quality, const dut_variants_options *opt, const dut_variant_note *notes,
+                          char *err, size_t err_len)
+{
+    if (!opt) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    return write_tsv(path, contig, res, min_depth, min_quality, opt, notes, err, err_len);
 }
 
 static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
                                         uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
-                                        const char *output_path, uint32_t min_depth, uint8_t min_quality, int device_id,
-                                        char *err, size_t err_len)
+                                        const char *output_path, uint32_t min_depth, uint8_t min_quality,
+                                        const dut_variants_options *vopt, int device_id, char *err, size_t err_len)
 {
     if (!bam_path || !fasta_path || !contig || !output_path) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
     if (min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
@@ -199,6 +241,24 @@ static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_
     auto engine_err = [&](const char *what) { const char *m = cl_last_error(ctx.get()); set_err(err, err_len, (m && *m) ? m : what); };
     int rc = cl_site_upload(ctx.get(), contig_len, blen, &tile);
     if (rc != CL_OK) { engine_err("site upload failed"); return rc; }
+    if (vopt && vopt->filtered) {
+        cl_site_quals q;
+        q.n_reads = rec.n; q.flag = rec.flag; q.qual_off = rec.qual_off; q.qual = rec.qual; q.seq_off = seq_off;
+        rc = cl_site_attach_quals(ctx.get(), &q, vopt->has_min_base_quality ? vopt->min_base_quality : 0);
+        if (rc != CL_OK) { engine_err("site attachment failed"); return rc; }
+        const cl_scan_filter flt = {vopt->exclude_flags, (uint8_t)(vopt->has_min_base_quality ? 1 : 0), 0};
+        cl_scan_result_ex res;
+        rc = cl_site_scan_ex(ctx.get(), min_quality, min_depth, &flt, bases, blen, start, end, &res);
+        if (rc != CL_OK) { engine_err("site scan failed"); return rc; }
+        dut_variant_note *notes = nullptr;
+        if (tree) {
+            rc = dut_variants_annotate_ex(tree.get(), build.c_str(), contig, res.candidates, (size_t)res.n_variant, &notes);
+            if (rc != CL_OK) { set_err(err, err_len, "annotation failed"); return rc; }
+        }
+        rc = dut_variants_write_ex(output_path, contig, &res, min_depth, min_quality, vopt, notes, err, err_len);
+        dut_variants_free_notes(notes, (size_t)res.n_variant);
+        return rc;
+    }
     cl_scan_result res;
     rc = cl_site_scan(ctx.get(), min_quality, min_depth, bases, blen, start, end, &res);
     if (rc != CL_OK) { engine_err("site scan failed"); return rc; }
@@ -212,16 +272,25 @@ static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_
     return rc;
 }
 
+int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
+                               uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
+                               const char *output_path, uint32_t min_depth, uint8_t min_quality,
+                               const dut_variants_options *opt, int device_id, char *err, size_t err_len)
+{
+    // no exception leaves the library through the C ABI
+    try { return dut_find_variants_files_impl(bam_path, fasta_path, contig, has_region, start, end, tree_json_path, provider, tree_type,
+                                               output_path, min_depth, min_quality, opt, device_id, err, err_len); }
+    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
+    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+}
+
 int dut_find_variants_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
                             uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
                             const char *output_path, uint32_t min_depth, uint8_t min_quality, int device_id,
                             char *err, size_t err_len)
 {
-    // no exception leaves the library through the C ABI
-    try { return dut_find_variants_files_impl(bam_path, fasta_path, contig, has_region, start, end, tree_json_path, provider, tree_type,
-                                               output_path, min_depth, min_quality, device_id, err, err_len); }
-    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
-    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+    return dut_find_variants_files_ex(bam_path, fasta_path, contig, has_region, start, end, tree_json_path, provider, tree_type,
+                                      output_path, min_depth, min_quality, nullptr, device_id, err, err_len);
 }
 
 } // extern "C"

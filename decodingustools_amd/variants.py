@@ -7,7 +7,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .callable_loci import SCAN_CANDIDATE, EngineError, ScanResult
+from .callable_loci import SCAN_CANDIDATE, SCAN_CANDIDATE_EX, EngineError, ScanResult
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
@@ -87,15 +87,70 @@ def write_variants(path: str, contig: str, result: ScanResult, min_depth: int, m
             lib.dut_variants_free_notes(notes, cand.shape[0])
 
 
+def _options(min_base_quality, exclude_flags, min_alt_per_strand) -> "_lib.dut_variants_options":
+    if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
+        raise ValueError("min_base_quality: 0..255")
+    if not 0 <= int(exclude_flags) <= 0xFFFF:
+        raise ValueError("exclude_flags: 0..65535")
+    if not 0 <= int(min_alt_per_strand) <= 0xFFFFFFFF:
+        raise ValueError("min_alt_per_strand: 0..2^32-1")
+    o = _lib.dut_variants_options()
+    o.filtered = 1
+    o.has_min_base_quality = 0 if min_base_quality is None else 1
+    o.min_base_quality = 0 if min_base_quality is None else int(min_base_quality)
+    o.exclude_flags = int(exclude_flags)
+    o.min_alt_per_strand = int(min_alt_per_strand)
+    return o
+
+
+def write_variants_ex(path: str, contig: str, result: ScanResult, min_depth: int, min_quality: int, min_base_quality=None,
+                      exclude_flags: int = 0, min_alt_per_strand: int = 0, tree: Optional[HaplogroupTree] = None,
+                      build_id: Optional[str] = None):
+    """The extended TSV (dut_variants_write_ex) for the ScanResult of Engine.site_scan_ex: per-strand counts and the
+    strand filter; min_base_quality=None prints '.'.  No device is needed."""
+    lib = _lib.load()
+    cand = np.ascontiguousarray(result.candidates, SCAN_CANDIDATE_EX).reshape(-1)
+    if cand.shape[0] != result.variant:
+        raise ValueError("variant count and candidates disagree")
+    opt = _options(min_base_quality, exclude_flags, min_alt_per_strand)
+    r = _lib.cl_scan_result_ex()
+    r.start, r.end = result.start, result.end
+    r.n_low_depth, r.n_mixed, r.n_uncomparable, r.n_match, r.n_variant = (result.low_depth, result.mixed, result.uncomparable,
+                                                                          result.match, result.variant)
+    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_scan_candidate_ex))
+    notes = C.POINTER(_lib.dut_variant_note)()
+    err = C.create_string_buffer(512)
+    if tree is not None:
+        if not build_id:
+            raise ValueError("a tree needs its build id")
+        st = lib.dut_variants_annotate_ex(tree._h, build_id.encode(), contig.encode(), cand.ctypes.data, cand.shape[0], C.byref(notes))
+        if st != 0:
+            raise EngineError(st, "annotation failed")
+    try:
+        st = lib.dut_variants_write_ex(path.encode(), contig.encode(), C.byref(r), int(min_depth), int(min_quality), C.byref(opt),
+                                       notes if tree is not None else None, err, 512)
+        if st != 0:
+            raise EngineError(st, err.value.decode())
+    finally:
+        if tree is not None:
+            lib.dut_variants_free_notes(notes, cand.shape[0])
+
+
 def find_variants(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
                   tree_json: Optional[str] = None, provider: int = FTDNA, tree_type: int = YDNA, min_depth: int = 10,
-                  min_quality: int = 20, device_id: int = 0):
-    """dut_find_variants_files: BAM (+ index) and FASTA in, the TSV out; region = (start, end), 0-based half open."""
+                  min_quality: int = 20, device_id: int = 0, min_base_quality: Optional[int] = None, exclude_flags: int = 0,
+                  min_alt_per_strand: int = 0):
+    """dut_find_variants_files(_ex): BAM (+ index) and FASTA in, the TSV out; region = (start, end), 0-based half open.
+    With min_base_quality, exclude_flags or min_alt_per_strand the scan is the filtered, strand-aware one and the TSV the
+    extended one; with none of them nothing changes."""
     lib = _lib.load()
     err = C.create_string_buffer(1024)
     start, end = region if region is not None else (0, 0)
-    st = lib.dut_find_variants_files(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
-                                     int(start), int(end), tree_json.encode() if tree_json else None, provider, tree_type,
-                                     output_file.encode(), int(min_depth), int(min_quality), device_id, err, 1024)
+    opt = None
+    if min_base_quality is not None or exclude_flags or min_alt_per_strand:
+        opt = C.byref(_options(min_base_quality, exclude_flags, min_alt_per_strand))
+    st = lib.dut_find_variants_files_ex(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
+                                        int(start), int(end), tree_json.encode() if tree_json else None, provider, tree_type,
+                                        output_file.encode(), int(min_depth), int(min_quality), opt, device_id, err, 1024)
     if st != 0:
         raise EngineError(st, err.value.decode())

@@ -351,9 +351,66 @@ cl_status cl_site_scan(cl_ctx *ctx, uint8_t min_quality, uint32_t min_depth, con
  * a, c, g, t, depth, into the caller's array.  Same tile, same refusals. */
 #define CL_SCAN_MAX_DENSE (1u << 20)
 cl_status cl_site_scan_counts(cl_ctx *ctx, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts);
-/* Measurement: the kernel of the last scan by device events (milliseconds) and its algorithmic bytes (4-bit bases,
- * records and CIGAR words read, reference bytes read, candidates or counters written). */
+/* Measurement: the kernel of the last scan of either form by device events (milliseconds) and its algorithmic bytes
+ * (4-bit bases, records and CIGAR words read, reference bytes read, candidates or counters written; for the filtered form
+ * also the pass bits and the flags). */
 cl_status cl_site_scan_stats(cl_ctx *ctx, double *kernel_ms, uint64_t *bytes);
+
+/* ---- the filtered, strand-aware form of the dense scan ------------------------------------------------------------ */
+/* The attachment of the resident tile: per read its BAM flag, per base one pass bit, qual >= min_base_quality, taken on
+ * the host by this call.  Base i of read r has the quality value qual[qual_off[r] + i] when
+ * i < qual_off[r + 1] - qual_off[r], otherwise none; a base without a value passes, and so does 0xFF (absent qualities).
+ * One bit per base (in the numbering of seq_off, to which the host realigns per read) and two bytes per read go to HBM
+ * through the staging ring, never the quality bytes.  seq_off must be the array that was given to cl_site_upload (the
+ * engine keeps no copy of the tile's host arrays; its length and total are checked).  A new attachment replaces the
+ * earlier one; the next cl_site_upload or cl_site_pileup drops it.  CL_ERR_INVALID (with a message): no resident tile,
+ * a tile cl_site_pileup filtered, another n_reads or another number of bases than the tile's, a null array, offsets
+ * that decrease.  CL_ERR_DEVICE: a host-only debug context. */
+typedef struct cl_site_quals {
+    uint64_t        n_reads;
+    const uint16_t *flag;
+    const uint64_t *qual_off;   /* n_reads + 1 */
+    const uint8_t  *qual;       /* may be NULL when qual_off[n_reads] == 0 */
+    const uint64_t *seq_off;    /* n_reads + 1: cl_site_tile.seq_off of the resident tile */
+} cl_site_quals;
+cl_status cl_site_attach_quals(cl_ctx *ctx, const cl_site_quals *quals, uint8_t min_base_quality);
+
+/* cl_site_scan / cl_site_scan_counts under a filter, by strand.  Relative to the definitions above:
+ *   a read counts only if it counts there and (flag & exclude_flags) == 0;
+ *   a base of it counts only if it counts there and (!use_base_quality or its pass bit is set);
+ *   the read is reverse iff flag & 0x10, else forward;
+ *   depth = all counted bases of all 16 codes, both strands; classes, the call (10 m >= 7 depth over the 16 codes summed
+ *   over the strands) and the candidate order are those of cl_site_scan applied to the filtered counts.
+ * With exclude_flags == 0 and use_base_quality == 0 the result equals cl_site_scan's (strands summed).  Positions the
+ * device's counter planes cannot classify are settled with a 16-code count under the same filter.  Same refusals as
+ * cl_site_scan, plus: nothing attached, a null filter.  Interleaves freely with cl_site_run, cl_site_scan and other
+ * filters on one resident tile.  out->candidates is context-owned, valid until the next cl_site_scan_ex, cl_site_upload
+ * or cl_destroy. */
+typedef struct cl_scan_filter {
+    uint16_t exclude_flags;       /* e.g. 0x704: unmapped, secondary, QC fail, duplicate (samtools --ff default) */
+    uint8_t  use_base_quality;    /* 0 / 1 */
+    uint8_t  pad;
+} cl_scan_filter;
+typedef struct cl_scan_candidate_ex {
+    uint32_t pos;                 /* 1-based */
+    uint8_t  ref, alt, pad[2];
+    uint32_t a, c, g, t, depth;   /* both strands */
+    uint32_t alt_fwd, alt_rev, ref_fwd, ref_rev;
+} cl_scan_candidate_ex;
+typedef struct cl_scan_result_ex {
+    uint32_t start, end;
+    uint64_t n_low_depth, n_mixed, n_uncomparable, n_match, n_variant;
+    const cl_scan_candidate_ex *candidates;
+} cl_scan_result_ex;
+cl_status cl_site_scan_ex(cl_ctx *ctx, uint8_t min_quality, uint32_t min_depth, const cl_scan_filter *filter,
+                          const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out);
+/* counts[(p - start) * 9 + 0..8] = a_fwd a_rev c_fwd c_rev g_fwd g_rev t_fwd t_rev depth; at most CL_SCAN_MAX_DENSE
+ * positions. */
+cl_status cl_site_scan_counts_ex(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start,
+                                 uint32_t end, uint32_t *counts);
+/* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
+ * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
+cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,8 @@
  * The reference has no such subcommand.  The counting and the call are the ones of find-y-branch / find-mt-branch
  * (haplogroup::caller::process_region, src/haplogroup/caller.rs:62-152), taken at every position of a contig or a
  * region instead of at the tree's sites, so the two never disagree about a tree site.  SNVs only: no insertions or
- * deletions, no base-quality or flag filter (the site tile carries neither), no consensus FASTA.
+ * deletions, no consensus FASTA.  With dut_variants_options the scan takes a flag mask and a base-quality threshold
+ * (cl_site_scan_ex) and the TSV carries per-strand allele counts and a strand filter.
  */
 #ifndef DUT_VARIANTS_H
 #define DUT_VARIANTS_H
@@ -59,6 +60,38 @@ int dut_find_variants_files(const char *bam_path, const char *fasta_path, const 
                             uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
                             const char *output_path, uint32_t min_depth, uint8_t min_quality, int device_id,
                             char *err, size_t err_len);
+
+/* ---- the filtered, strand-aware form ------------------------------------------------------------------------ */
+/* filtered == 0: the unfiltered scan and the TSV above, the other fields are ignored.  Otherwise the scan is
+ * cl_site_scan_ex with exclude_flags and, when has_min_base_quality, the pass bits of min_base_quality; a candidate whose
+ * alternative base has fewer than min_alt_per_strand observations on either strand is marked, not dropped. */
+typedef struct dut_variants_options {
+    int      filtered;
+    int      has_min_base_quality;
+    uint8_t  min_base_quality;
+    uint16_t exclude_flags;
+    uint32_t min_alt_per_strand;
+} dut_variants_options;
+
+/* dut_variants_annotate for the candidates of cl_site_scan_ex. */
+int dut_variants_annotate_ex(const dut_tree *t, const char *build_id, const char *chromosome,
+                             const cl_scan_candidate_ex *candidates, size_t n, dut_variant_note **notes);
+
+/* The extended TSV (no device needed): the comment lines of dut_variants_write with ##min_base_quality= ("." when
+ * !has_min_base_quality) and ##exclude_flags=0x%04x after ##min_quality=, the header
+ *   #contig pos ref alt depth A C G T freq status names alleles alt_fwd alt_rev ref_fwd ref_rev filter
+ * and per candidate filter = "strand" when min(alt_fwd, alt_rev) < min_alt_per_strand, else "PASS".  ##variant= is the
+ * scan's count: marked candidates stay in the file. */
+int dut_variants_write_ex(const char *path, const char *contig, const cl_scan_result_ex *res, uint32_t min_depth,
+                          uint8_t min_quality, const dut_variants_options *opt, const dut_variant_note *notes,
+                          char *err, size_t err_len);
+
+/* dut_find_variants_files with options (NULL or filtered == 0: exactly that call).  With a filter: cl_site_upload,
+ * cl_site_attach_quals with the records' flags and qualities, cl_site_scan_ex, dut_variants_write_ex. */
+int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
+                               uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
+                               const char *output_path, uint32_t min_depth, uint8_t min_quality,
+                               const dut_variants_options *opt, int device_id, char *err, size_t err_len);
 
 #ifdef __cplusplus
 }
