@@ -307,7 +307,11 @@ cl_status cl_site_pileup(cl_ctx *ctx, uint8_t min_quality, uint32_t contig_len,
 /* The same in two steps: the tile goes to HBM once (through the pinned staging ring) and stays resident -- until the
  * next cl_site_upload or cl_destroy -- and any number of site lists are run over it (find-y-branch --show-snps asks the
  * same reads about several lists; caller.rs:8-59 fetches the region again each time).  cl_site_pileup = both, for one
- * list (and sends less: above). */
+ * list (and sends less: above).
+ * Every entry of the list gets its row, hist[i * 16 .. i * 16 + 15] for sites[i]: a row depends on the tile, on
+ * min_quality and on the site's own value, never on the rest of the list -- not on its order, not on what else is in it,
+ * not on whether the same site is entered again (each of its entries gets the same row).  A site of 0 and a site beyond
+ * the contig or ref_len get a row of zeros.  The same holds for cl_site_pileup. */
 cl_status cl_site_upload(cl_ctx *ctx, uint32_t contig_len, uint64_t ref_len, const cl_site_tile *tile);
 cl_status cl_site_run(cl_ctx *ctx, uint8_t min_quality, const uint32_t *sites, size_t n_sites, uint32_t *hist);
 

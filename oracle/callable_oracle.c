@@ -740,6 +740,26 @@ void orc_genome_summary_build(const orc_contig_stats *stats, const uint64_t *cal
 /* ------------------------------------------------------------------------------------------ */
 /* config 5: haplogroup::caller::process_region (src/haplogroup/caller.rs:62-152)             */
 /* ------------------------------------------------------------------------------------------ */
+typedef struct { uint32_t vcf_pos; size_t index; } site_key;
+
+static int site_key_cmp(const void *a, const void *b)
+{
+    const site_key *x = (const site_key *)a, *y = (const site_key *)b;
+    if (x->vcf_pos != y->vcf_pos) return x->vcf_pos < y->vcf_pos ? -1 : 1;
+    return x->index < y->index ? -1 : x->index > y->index ? 1 : 0;
+}
+
+/* the first entry of the sorted list with vcf_pos >= v (n: none) */
+static size_t site_lower_bound(const site_key *key, size_t n, uint64_t v)
+{
+    size_t lo = 0, hi = n;
+    while (lo < hi) {
+        size_t mid = lo + (hi - lo) / 2;
+        if ((uint64_t)key[mid].vcf_pos < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 int orc_site_pileup(uint32_t min_depth, uint8_t min_quality, uint32_t contig_len,
                     const uint8_t *ref, uint64_t ref_len,
                     const orc_reads *R, const uint64_t *seq_off, const uint8_t *seq4,
@@ -748,17 +768,18 @@ int orc_site_pileup(uint32_t min_depth, uint8_t min_quality, uint32_t contig_len
                     uint8_t *out_called, double *out_freq, uint32_t *base_hist)
 {
     static const char CODE[] = "=ACMGRSVTWYHKDBN";      /* rust-htslib seq().as_bytes() */
-    /* positions: HashMap<u32, ...> keyed by 1-based vcf_pos -> dense lookup position->site */
-    uint64_t maxp = 0;
-    for (size_t i = 0; i < n_sites; ++i) if (sites[i] > maxp) maxp = sites[i];
-    int64_t *lut = (int64_t *)malloc((size_t)(maxp + 2) * sizeof(int64_t));
-    for (uint64_t i = 0; i <= maxp + 1; ++i) lut[i] = -1;
-    for (size_t i = 0; i < n_sites; ++i) lut[sites[i]] = (int64_t)i;
-    uint32_t *hist = (uint32_t *)calloc(n_sites * 16, sizeof(uint32_t));
+    /* positions: HashMap<u32, ...> keyed by 1-based vcf_pos -> the list sorted by (vcf_pos, index), searched by
+     * bisection (memory by the number of sites, whatever their values).  Of the entries that name one vcf_pos the
+     * last one is counted, as an insert into the map would leave it; the others get a copy of its row below: every
+     * entry of the list has its row, which does not depend on the rest of the list (callable_loci.h, cl_site_run). */
+    site_key *key = (site_key *)malloc((n_sites ? n_sites : 1) * sizeof(site_key));
+    for (size_t i = 0; i < n_sites; ++i) { key[i].vcf_pos = sites[i]; key[i].index = i; }
+    qsort(key, n_sites, sizeof(site_key), site_key_cmp);
+    uint32_t *hist = (uint32_t *)calloc(n_sites ? n_sites * 16 : 1, sizeof(uint32_t));
 
     /* fetch("chr:1-len") (:33-36): records overlapping [0,len) on this contig, NO flag filter */
     for (int64_t r = 0; r < R->n; ++r) {
-        if ((int64_t)R->pos[r] >= (int64_t)contig_len) continue;
+        if (R->pos[r] < 0 || (int64_t)R->pos[r] >= (int64_t)contig_len) continue;
         if (R->mapq[r] < min_quality) continue;                               /* :80 */
         uint64_t slen = seq_off[r + 1] - seq_off[r];
         uint64_t ref_pos = (uint64_t)R->pos[r];
@@ -769,19 +790,22 @@ int orc_site_pileup(uint32_t min_depth, uint8_t min_quality, uint32_t contig_len
             int op = (int)(cig[k] & 15);
             uint64_t len = cig[k] >> 4;
             if (op_is_match(op)) {                                            /* :91-119 */
-                for (uint64_t i = 0; i < len; ++i) {
-                    uint64_t vcf_pos = ref_pos + 1;
-                    if (vcf_pos <= maxp && lut[vcf_pos] >= 0) {
-                        if (read_pos + i < slen) {                            /* :105 */
-                            uint64_t bi = seq_off[r] + read_pos + i;
-                            uint8_t byte = seq4[bi >> 1];
-                            int code = (bi & 1) ? (byte & 15) : (byte >> 4);
-                            /* fetch_seq(ref_pos, ref_pos) must be non-empty (:110-113) */
-                            if (ref && ref_pos < ref_len) hist[lut[vcf_pos] * 16 + code] += 1;
-                        }
+                /* the bases of the operation stand at vcf_pos ref_pos + 1 ... ref_pos + len: of the loop over them
+                 * (:92-118) only the steps whose vcf_pos is a key of the map do anything, and those are one run of
+                 * the sorted list */
+                for (size_t j = site_lower_bound(key, n_sites, ref_pos + 1);
+                     j < n_sites && (uint64_t)key[j].vcf_pos <= ref_pos + len; ++j) {
+                    if (j + 1 < n_sites && key[j + 1].vcf_pos == key[j].vcf_pos) continue;   /* the last of its entries */
+                    uint64_t i = (uint64_t)key[j].vcf_pos - (ref_pos + 1);
+                    if (read_pos + i < slen) {                                /* :105 */
+                        uint64_t bi = seq_off[r] + read_pos + i;
+                        uint8_t byte = seq4[bi >> 1];
+                        int code = (bi & 1) ? (byte & 15) : (byte >> 4);
+                        /* fetch_seq(ref_pos, ref_pos) must be non-empty (:110-113) */
+                        if (ref && ref_pos + i < ref_len) hist[key[j].index * 16 + code] += 1;
                     }
-                    ref_pos += 1;
                 }
+                ref_pos += len;
                 read_pos += len;
             } else if (op == OP_D || op == OP_N) {
                 ref_pos += len;                                               /* :120-122 */
@@ -790,6 +814,9 @@ int orc_site_pileup(uint32_t min_depth, uint8_t min_quality, uint32_t contig_len
             }
         }
     }
+    for (size_t j = n_sites; j-- > 1; )                                       /* the other entries of a vcf_pos */
+        if (key[j - 1].vcf_pos == key[j].vcf_pos)
+            memcpy(hist + key[j - 1].index * 16, hist + key[j].index * 16, 16 * sizeof(uint32_t));
     for (size_t i = 0; i < n_sites; ++i) {                                    /* :132-149 */
         uint32_t total = 0, best = 0; int bc = 0;
         /* to_ascii_uppercase of "=ACMGRSVTWYHKDBN" is the identity, so codes <-> chars 1:1 */
@@ -806,6 +833,6 @@ int orc_site_pileup(uint32_t min_depth, uint8_t min_quality, uint32_t contig_len
         out_called[i] = (total >= min_depth && total > 0 && freq >= 0.7) ? 1 : 0;
         if (base_hist) memcpy(base_hist + i * 16, hist + i * 16, 16 * sizeof(uint32_t));
     }
-    free(hist); free(lut);
+    free(hist); free(key);
     return 0;
 }
