@@ -256,21 +256,30 @@ class Engine:
         self._check(self._lib.cl_site_pileup_stats(self._h, C.byref(ms), C.byref(b)))
         return ms.value, b.value
 
-    def site_scan(self, min_quality, min_depth, ref, start=0, end=None):
-        """cl_site_scan over [start, end) of the resident tile (end=None: the length of `ref`, which must be the ref_len
-        given to site_upload): a ScanResult with the five class counts and the candidates as a structured array."""
+    def _site_scan(self, min_quality, min_depth, ref, start, end, filt):
+        """cl_site_scan (filt is None) or cl_site_scan_ex (filt: a cl_scan_filter) and the result as a ScanResult."""
         ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
         if end is None:
             end = ref.shape[0]
-        r = _lib.cl_scan_result()
-        self._check(self._lib.cl_site_scan(self._h, int(min_quality), int(min_depth), _ptr(ref), ref.shape[0], int(start), int(end),
-                                           C.byref(r)))
+        if filt is None:
+            r, dtype = _lib.cl_scan_result(), SCAN_CANDIDATE
+            st = self._lib.cl_site_scan(self._h, int(min_quality), int(min_depth), _ptr(ref), ref.shape[0], int(start), int(end), C.byref(r))
+        else:
+            r, dtype = _lib.cl_scan_result_ex(), SCAN_CANDIDATE_EX
+            st = self._lib.cl_site_scan_ex(self._h, int(min_quality), int(min_depth), C.byref(filt), _ptr(ref), ref.shape[0], int(start),
+                                           int(end), C.byref(r))
+        self._check(st)
         n = int(r.n_variant)
-        cand = np.zeros(n, SCAN_CANDIDATE)
+        cand = np.zeros(n, dtype)
         if n:
-            C.memmove(cand.ctypes.data, r.candidates, n * SCAN_CANDIDATE.itemsize)
+            C.memmove(cand.ctypes.data, r.candidates, n * dtype.itemsize)
         return ScanResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), mixed=int(r.n_mixed),
                           uncomparable=int(r.n_uncomparable), match=int(r.n_match), variant=n, candidates=cand)
+
+    def site_scan(self, min_quality, min_depth, ref, start=0, end=None):
+        """cl_site_scan over [start, end) of the resident tile (end=None: the length of `ref`, which must be the ref_len
+        given to site_upload): a ScanResult with the five class counts and the candidates as a structured array."""
+        return self._site_scan(min_quality, min_depth, ref, start, end, None)
 
     def site_scan_counts(self, min_quality, start, end):
         """cl_site_scan_counts: (end - start, 5) uint32 -- A, C, G, T, depth -- for at most CL_SCAN_MAX_DENSE positions."""
@@ -287,19 +296,8 @@ class Engine:
     def site_scan_ex(self, min_quality, min_depth, ref, exclude_flags=0, use_base_quality=False, start=0, end=None):
         """cl_site_scan_ex: site_scan under a flag mask and (use_base_quality) the attachment's pass bits; the candidates
         (SCAN_CANDIDATE_EX) also carry alt_fwd, alt_rev, ref_fwd, ref_rev."""
-        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
-        if end is None:
-            end = ref.shape[0]
-        f = _lib.cl_scan_filter(int(exclude_flags), 1 if use_base_quality else 0, 0)
-        r = _lib.cl_scan_result_ex()
-        self._check(self._lib.cl_site_scan_ex(self._h, int(min_quality), int(min_depth), C.byref(f), _ptr(ref), ref.shape[0],
-                                              int(start), int(end), C.byref(r)))
-        n = int(r.n_variant)
-        cand = np.zeros(n, SCAN_CANDIDATE_EX)
-        if n:
-            C.memmove(cand.ctypes.data, r.candidates, n * SCAN_CANDIDATE_EX.itemsize)
-        return ScanResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), mixed=int(r.n_mixed),
-                          uncomparable=int(r.n_uncomparable), match=int(r.n_match), variant=n, candidates=cand)
+        return self._site_scan(min_quality, min_depth, ref, start, end,
+                               _lib.cl_scan_filter(int(exclude_flags), 1 if use_base_quality else 0, 0))
 
     def site_scan_counts_ex(self, min_quality, start, end, exclude_flags=0, use_base_quality=False):
         """cl_site_scan_counts_ex: (end - start, 9) uint32 -- A+ A- C+ C- G+ G- T+ T- depth (+ forward, - reverse)."""

@@ -6,7 +6,6 @@
 #include "kernels.hip.h"
 #include "depth_profile.hip.h"
 #include "site_scan.hip.h"
-#include "site_scan_ex.hip.h"
 #include "site_pass_bits.h"
 #include "host_parallel.h"
 #include "qual_pack.h"
@@ -287,22 +286,22 @@ struct SiteResident {
     bool resident = false;
     bool filtered = false;           // the resident tile holds only the reads that overlap a site of the list it was uploaded for (cl_site_pileup)
     // cl_site_scan: the per-read ends and per-window read ranges of the resident tile (built by the first scan), the
-    // reference bytes of the range, class counts + candidate count, candidates, dense counters
+    // reference bytes of the range, class counts + candidate count, candidates, dense counters (of either form)
     DevBuf<uint32_t> sc_end, sc_wfirst, sc_wlast, sc_dense;
     DevBuf<uint8_t> sc_ref;
     DevBuf<unsigned long long> sc_cls;
     DevBuf<ScanCand> sc_cand;
     bool scan_indexed = false;
     // cl_site_attach_quals: one pass bit per base of seq, one flag per read; the filtered scan's candidates, ambiguous
-    // positions and their 16-code histograms, dense counters
+    // positions and their 16-code histograms
     DevBuf<unsigned long long> q_pass;
     DevBuf<uint16_t> q_flag;
     DevBuf<ScanCandEx> sx_cand;
-    DevBuf<uint32_t> sx_amb, sx_hist, sx_dense;
+    DevBuf<uint32_t> sx_amb, sx_hist;
     bool attached = false;
     void release()
     {
-        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sx_dense.release();
+        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -2943,8 +2942,10 @@ static cl_status cl_site_run_impl(cl_ctx *c, uint8_t min_quality, const uint32_t
     return CL_OK;
 }
 
-// ---- config 5, dense form: base counts and calls at every position of a range of the resident tile (site_scan.hip.h) ----
+// ---- config 5, dense form: base counts and calls at every position of a range of the resident tile (site_scan.hip.h),
+// ---- unfiltered (cl_site_scan) and filtered, strand-aware (cl_site_scan_ex, behind cl_site_attach_quals) ----
 static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_candidate) == 28, "the device writes cl_scan_candidate");
+static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
 
 // the argument checks every scan shares, in front of any device work
 static cl_status site_scan_check(cl_ctx *c, const char *who, uint32_t start, uint32_t end)
@@ -2978,49 +2979,119 @@ static cl_status site_scan_index(cl_ctx *c)
     return CL_OK;
 }
 
-static void site_scan_fill(cl_ctx *c, ScanArgs &A, uint8_t min_quality, uint32_t min_depth, uint32_t start, uint32_t end)
-{
-    SiteResident &S = c->site;
-    A.rec = S.rec.p; A.seq_base = S.base.p; A.cigar = S.cig.p; A.seq4 = S.seq.p;
-    A.end = S.sc_end.p; A.wfirst = S.sc_wfirst.p; A.wlast = S.sc_wlast.p;
-    A.min_quality = min_quality; A.contig_len = S.contig_len; A.min_depth = min_depth; A.ref_len = S.ref_len;
-    A.start = start; A.end_pos = end; A.win0 = start / kScanWin;
-    A.refb = nullptr; A.cls = nullptr; A.n_cand = nullptr; A.cand = nullptr; A.cand_cap = 0; A.dense = nullptr;
-}
+extern "C++" {                                                 // (templates: one host path for the two forms)
 
-// settles the positions the six counter planes cannot classify (site_scan.hip.h) with cl_site_run's 16-code histogram:
-// one code with 7/10 of the depth is a call of a code that is not A/C/G/T -> uncomparable; otherwise mixed
-static cl_status site_scan_settle(cl_ctx *c, uint8_t min_quality, const std::vector<uint32_t> &pos1, uint64_t &n_unc, uint64_t &n_mixed)
+// what the host path of the two forms differs in: the C types, the names in messages, where the candidates live (those
+// of cl_site_scan stay valid until the next cl_site_scan, those of cl_site_scan_ex until the next cl_site_scan_ex),
+// the filter argument (none, or the caller's cl_scan_filter) and the tile bytes a scan reads
+template <bool FILTERED> struct ScanHost;
+template <> struct ScanHost<false> {
+    using Result = cl_scan_result;
+    using Cand = cl_scan_candidate;
+    using Filter = ScanNoFilter;
+    static constexpr const char *kScan = "cl_site_scan", *kCounts = "cl_site_scan_counts";
+    static constexpr const char *kLap = "site scan: reference in, kernel, candidates back";
+    static constexpr const char *kLapSettle = "site scan: ambiguous positions settled by the site pileup";
+    static std::vector<Cand> &host_cand(cl_ctx *c) { return c->scan_cand; }
+    static DevBuf<ScanCand> &dev_cand(SiteResident &S) { return S.sc_cand; }
+    static uint64_t tile_bytes(const SiteResident &S) { return (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4; }
+};
+template <> struct ScanHost<true> {
+    using Result = cl_scan_result_ex;
+    using Cand = cl_scan_candidate_ex;
+    using Filter = const cl_scan_filter *;
+    static constexpr const char *kScan = "cl_site_scan_ex", *kCounts = "cl_site_scan_counts_ex";
+    static constexpr const char *kLap = "filtered site scan: reference in, kernel, candidates back";
+    static constexpr const char *kLapSettle = "filtered site scan: ambiguous positions settled";
+    static std::vector<Cand> &host_cand(cl_ctx *c) { return c->scan_cand_ex; }
+    static DevBuf<ScanCandEx> &dev_cand(SiteResident &S) { return S.sx_cand; }
+    // those of cl_site_scan, the pass bits and the flags
+    static uint64_t tile_bytes(const SiteResident &S) { return ScanHost<false>::tile_bytes(S) + (S.nbase + 7) / 8 + S.n * 2; }
+};
+
+// site_scan_check and, for the filtered form, its filter and the attachment
+template <bool FILTERED>
+static cl_status site_scan_check_form(cl_ctx *c, const char *who, typename ScanHost<FILTERED>::Filter f, uint32_t start, uint32_t end)
 {
-    if (pos1.empty()) return CL_OK;
-    std::vector<uint32_t> hist(pos1.size() * 16);
-    const double ms = c->site_ms; const uint64_t by = c->site_bytes;          // (cl_site_pileup_stats keeps speaking of the caller's own runs)
-    const cl_status s = cl_site_run_impl(c, min_quality, pos1.data(), pos1.size(), hist.data(), nullptr);
-    c->site_ms = ms; c->site_bytes = by;
+    cl_status s = site_scan_check(c, who, start, end);
     if (s != CL_OK) return s;
-    for (size_t i = 0; i < pos1.size(); ++i) {
-        uint64_t depth = 0, m = 0;
-        for (int k = 0; k < 16; ++k) { depth += hist[i * 16 + k]; m = std::max<uint64_t>(m, hist[i * 16 + k]); }
-        if (10 * m >= 7 * depth) ++n_unc; else ++n_mixed;
+    if constexpr (FILTERED) {
+        if (!f) return fail(c, CL_ERR_INVALID, std::string(who) + ": null filter");
+        if (!c->site.attached) return fail(c, CL_ERR_INVALID, std::string(who) + " without cl_site_attach_quals on the resident tile");
     }
     return CL_OK;
 }
 
-static cl_status cl_site_scan_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const uint8_t *ref_bases, uint64_t ref_len,
-                                   uint32_t start, uint32_t end, cl_scan_result *out)
+template <bool FILTERED>
+static void site_scan_fill(cl_ctx *c, ScanFormArgs<FILTERED> &A, typename ScanHost<FILTERED>::Filter f, uint8_t min_quality, uint32_t min_depth,
+                           uint32_t start, uint32_t end)
 {
+    SiteResident &S = c->site;
+    A.s.rec = S.rec.p; A.s.seq_base = S.base.p; A.s.cigar = S.cig.p; A.s.seq4 = S.seq.p;
+    A.s.end = S.sc_end.p; A.s.wfirst = S.sc_wfirst.p; A.s.wlast = S.sc_wlast.p;
+    A.s.min_quality = min_quality; A.s.contig_len = S.contig_len; A.s.min_depth = min_depth; A.s.ref_len = S.ref_len;
+    A.s.start = start; A.s.end_pos = end; A.s.win0 = start / kScanWin;
+    A.s.refb = nullptr; A.s.cls = nullptr; A.s.n_cand = nullptr; A.s.cand_cap = 0; A.s.dense = nullptr;
+    A.cand = nullptr;
+    if constexpr (FILTERED) {
+        A.f.flag = S.q_flag.p; A.f.pass = S.q_pass.p; A.f.exclude_flags = f->exclude_flags; A.f.use_bq = f->use_base_quality ? 1u : 0u;
+    }
+}
+
+// The 16-code histograms of the positions the counter planes cannot classify (site_scan.hip.h).  Unfiltered: those of
+// cl_site_run.  Filtered: k_site_scan_settle under the filter of A (cl_site_run's histogram is unfiltered).
+template <bool FILTERED>
+static cl_status site_scan_hist16(cl_ctx *c, const ScanFormArgs<FILTERED> &A, const std::vector<uint32_t> &pos1, std::vector<uint32_t> &hist)
+{
+    hist.resize(pos1.size() * 16);
+    if constexpr (FILTERED) {
+        SiteResident &S = c->site;
+        HIP_TRY(c, S.sx_amb.reserve(pos1.size())); HIP_TRY(c, S.sx_hist.reserve(hist.size()));
+        HIP_TRY(c, hipMemcpyAsync(S.sx_amb.p, pos1.data(), pos1.size() * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_site_scan_settle, dim3((uint32_t)pos1.size()), dim3(kBlock), 0, c->stream, A, S.sx_amb.p, S.sx_hist.p);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(hist.data(), S.sx_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return CL_OK;
+    } else {
+        const double ms = c->site_ms; const uint64_t by = c->site_bytes;      // (cl_site_pileup_stats keeps speaking of the caller's own runs)
+        const cl_status s = cl_site_run_impl(c, (uint8_t)A.s.min_quality, pos1.data(), pos1.size(), hist.data(), nullptr);
+        c->site_ms = ms; c->site_bytes = by;
+        return s;
+    }
+}
+
+// settles ambiguous positions from their 16-code histograms: one code with 7/10 of the depth is a call of a code that
+// is not A/C/G/T -> uncomparable; otherwise mixed
+static void site_scan_settle(const std::vector<uint32_t> &hist, uint64_t &n_unc, uint64_t &n_mixed)
+{
+    for (size_t i = 0; i < hist.size(); i += 16) {
+        uint64_t depth = 0, m = 0;
+        for (int k = 0; k < 16; ++k) { depth += hist[i + k]; m = std::max<uint64_t>(m, hist[i + k]); }
+        if (10 * m >= 7 * depth) ++n_unc; else ++n_mixed;
+    }
+}
+
+template <bool FILTERED>
+static cl_status site_scan_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, typename ScanHost<FILTERED>::Filter filter, const uint8_t *ref_bases,
+                                uint64_t ref_len, uint32_t start, uint32_t end, typename ScanHost<FILTERED>::Result *out)
+{
+    using H = ScanHost<FILTERED>;
+    using Cand = typename H::Cand;
     if (!c) return CL_ERR_INVALID;
-    if (!out) return fail(c, CL_ERR_INVALID, "cl_site_scan: null result");
-    cl_status s = site_scan_check(c, "cl_site_scan", start, end);
+    if (!out) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": null result");
+    cl_status s = site_scan_check_form<FILTERED>(c, H::kScan, filter, start, end);
     if (s != CL_OK) return s;
     SiteResident &S = c->site;
-    if (min_depth == 0) return fail(c, CL_ERR_INVALID, "cl_site_scan: min_depth must be at least 1");
-    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan: ref_len differs from the one given to cl_site_upload");
-    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan: null reference");
+    if (min_depth == 0) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": min_depth must be at least 1");
+    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": ref_len differs from the one given to cl_site_upload");
+    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": null reference");
+    std::vector<Cand> &cand = H::host_cand(c);
+    auto &d_cand = H::dev_cand(S);
     memset(out, 0, sizeof(*out));
     out->start = start; out->end = end;
-    c->scan_cand.clear();
-    out->candidates = c->scan_cand.data();
+    cand.clear();
+    out->candidates = cand.data();
     c->scan_ms = 0.0; c->scan_bytes = 0;
     if (start == end) return CL_OK;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3037,15 +3108,15 @@ static cl_status cl_site_scan_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_
     uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
     unsigned long long h_cls[8];
     double ms_all = 0.0;
+    ScanFormArgs<FILTERED> A;
     for (;;) {
-        HIP_TRY(c, S.sc_cand.reserve(cap));
+        HIP_TRY(c, d_cand.reserve(cap));
         HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
-        ScanArgs A;
-        site_scan_fill(c, A, min_quality, min_depth, start, end);
-        A.refb = S.sc_ref.p; A.cls = S.sc_cls.p; A.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
-        A.cand = S.sc_cand.p; A.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+        site_scan_fill<FILTERED>(c, A, filter, min_quality, min_depth, start, end);
+        A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
+        A.cand = d_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
         HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
-        hipLaunchKernelGGL(k_site_scan<false>, dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+        hipLaunchKernelGGL((k_site_scan<FILTERED, false>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
         HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
@@ -3058,76 +3129,80 @@ static cl_status cl_site_scan_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_
         cap = want;
     }
     const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
-    c->scan_cand.resize(n_cand);
-    if (n_cand) HIP_TRY(c, hipMemcpy(c->scan_cand.data(), S.sc_cand.p, n_cand * sizeof(cl_scan_candidate), hipMemcpyDeviceToHost));
+    cand.resize(n_cand);
+    if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), d_cand.p, n_cand * sizeof(Cand), hipMemcpyDeviceToHost));
     c->scan_ms = ms_all;
-    c->scan_bytes = (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + n_ref + n_cand * sizeof(cl_scan_candidate);
-    tmr.lap("site scan: reference in, kernel, candidates back");
+    c->scan_bytes = H::tile_bytes(S) + n_ref + n_cand * sizeof(Cand);
+    tmr.lap(H::kLap);
     // the compaction runs wave by wave: ascending position is restored here; ambiguous positions leave the list
-    std::sort(c->scan_cand.begin(), c->scan_cand.end(), [](const cl_scan_candidate &a, const cl_scan_candidate &b) { return a.pos < b.pos; });
+    std::sort(cand.begin(), cand.end(), [](const Cand &a, const Cand &b) { return a.pos < b.pos; });
     out->n_low_depth = h_cls[SCAN_LOW_DEPTH]; out->n_mixed = h_cls[SCAN_MIXED]; out->n_uncomparable = h_cls[SCAN_UNCOMPARABLE];
     out->n_match = h_cls[SCAN_MATCH]; out->n_variant = h_cls[SCAN_VARIANT];
     if (h_cls[SCAN_AMBIGUOUS]) {
-        std::vector<uint32_t> amb;
+        std::vector<uint32_t> amb, hist;
         size_t k = 0;
-        for (const cl_scan_candidate &cd : c->scan_cand) { if (cd.alt == 0) amb.push_back(cd.pos); else c->scan_cand[k++] = cd; }
-        c->scan_cand.resize(k);
-        if ((s = site_scan_settle(c, min_quality, amb, out->n_uncomparable, out->n_mixed)) != CL_OK) return s;
-        tmr.lap("site scan: ambiguous positions settled by the site pileup");
+        for (const Cand &cd : cand) { if (cd.alt == 0) amb.push_back(cd.pos); else cand[k++] = cd; }
+        cand.resize(k);
+        if ((s = site_scan_hist16<FILTERED>(c, A, amb, hist)) != CL_OK) return s;
+        site_scan_settle(hist, out->n_uncomparable, out->n_mixed);
+        tmr.lap(H::kLapSettle);
     }
-    out->candidates = c->scan_cand.data();
+    out->candidates = cand.data();
     return CL_OK;
 }
 
-static cl_status cl_site_scan_counts_impl(cl_ctx *c, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts)
+template <bool FILTERED>
+static cl_status site_scan_counts_impl(cl_ctx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, uint32_t start, uint32_t end,
+                                       uint32_t *counts)
 {
+    using H = ScanHost<FILTERED>;
     if (!c) return CL_ERR_INVALID;
-    cl_status s = site_scan_check(c, "cl_site_scan_counts", start, end);
+    cl_status s = site_scan_check_form<FILTERED>(c, H::kCounts, filter, start, end);
     if (s != CL_OK) return s;
-    if (end - start > CL_SCAN_MAX_DENSE) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts: more than CL_SCAN_MAX_DENSE positions");
+    if (end - start > CL_SCAN_MAX_DENSE) return fail(c, CL_ERR_INVALID, std::string(H::kCounts) + ": more than CL_SCAN_MAX_DENSE positions");
     c->scan_ms = 0.0; c->scan_bytes = 0;
     if (start == end) return CL_OK;
-    if (!counts) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts: null array");
+    if (!counts) return fail(c, CL_ERR_INVALID, std::string(H::kCounts) + ": null array");
     SiteResident &S = c->site;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((s = site_scan_index(c)) != CL_OK) return s;
-    const size_t n5 = (size_t)(end - start) * 5;
-    HIP_TRY(c, S.sc_dense.reserve(n5));
+    const size_t n_dense = (size_t)(end - start) * ScanForm<FILTERED>::kDense;
+    HIP_TRY(c, S.sc_dense.reserve(n_dense));
     if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
-    ScanArgs A;
-    site_scan_fill(c, A, min_quality, 1, start, end);
-    A.dense = S.sc_dense.p;
+    ScanFormArgs<FILTERED> A;
+    site_scan_fill<FILTERED>(c, A, filter, min_quality, 1, start, end);
+    A.s.dense = S.sc_dense.p;
     HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
-    hipLaunchKernelGGL(k_site_scan<true>, dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
+    hipLaunchKernelGGL((k_site_scan<FILTERED, true>), dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
-    HIP_TRY(c, hipMemcpyAsync(counts, S.sc_dense.p, n5 * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(counts, S.sc_dense.p, n_dense * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     float t = 0.f;
     HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
     c->scan_ms = t;
-    c->scan_bytes = (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + n5 * 4;
+    c->scan_bytes = H::tile_bytes(S) + n_dense * 4;
     return CL_OK;
 }
+
+} // extern "C++"
 
 cl_status cl_site_scan(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const uint8_t *ref_bases, uint64_t ref_len,
                        uint32_t start, uint32_t end, cl_scan_result *out)
 {
-    try { return cl_site_scan_impl(c, min_quality, min_depth, ref_bases, ref_len, start, end, out); }
+    try { return site_scan_impl<false>(c, min_quality, min_depth, ScanNoFilter{}, ref_bases, ref_len, start, end, out); }
     catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
     catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
 }
 
 cl_status cl_site_scan_counts(cl_ctx *c, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts)
 {
-    try { return cl_site_scan_counts_impl(c, min_quality, start, end, counts); }
+    try { return site_scan_counts_impl<false>(c, min_quality, ScanNoFilter{}, start, end, counts); }
     catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
     catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
 }
 
-// ---- the filtered, strand-aware form (site_scan_ex.hip.h): the attachment, the scan, the dense counters ----
-static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
-
+// ---- the attachment of the filtered form ----
 static cl_status site_quals_check(const cl_site_quals *q, std::string &why)
 {
     if (!q) { why = "null attachment"; return CL_ERR_INVALID; }
@@ -3172,142 +3247,6 @@ static cl_status cl_site_attach_quals_impl(cl_ctx *c, const cl_site_quals *q, ui
     return CL_OK;
 }
 
-static cl_status site_scan_ex_check(cl_ctx *c, const char *who, const cl_scan_filter *f, uint32_t start, uint32_t end)
-{
-    cl_status s = site_scan_check(c, who, start, end);
-    if (s != CL_OK) return s;
-    if (!f) return fail(c, CL_ERR_INVALID, std::string(who) + ": null filter");
-    if (!c->site.attached) return fail(c, CL_ERR_INVALID, std::string(who) + " without cl_site_attach_quals on the resident tile");
-    return CL_OK;
-}
-
-static void site_scan_ex_fill(cl_ctx *c, ScanExArgs &A, const cl_scan_filter *f, uint8_t min_quality, uint32_t min_depth, uint32_t start, uint32_t end)
-{
-    SiteResident &S = c->site;
-    site_scan_fill(c, A.s, min_quality, min_depth, start, end);
-    A.flag = S.q_flag.p; A.pass = S.q_pass.p; A.exclude_flags = f->exclude_flags; A.use_bq = f->use_base_quality ? 1u : 0u;
-    A.cand = nullptr; A.dense = nullptr;
-}
-
-// the tile bytes a filtered scan reads: those of cl_site_scan, the pass bits and the flags
-static uint64_t site_scan_ex_tile_bytes(const SiteResident &S)
-{
-    return (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + (S.nbase + 7) / 8 + S.n * 2;
-}
-
-static cl_status cl_site_scan_ex_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const cl_scan_filter *filter, const uint8_t *ref_bases,
-                                      uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out)
-{
-    if (!c) return CL_ERR_INVALID;
-    if (!out) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: null result");
-    cl_status s = site_scan_ex_check(c, "cl_site_scan_ex", filter, start, end);
-    if (s != CL_OK) return s;
-    SiteResident &S = c->site;
-    if (min_depth == 0) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: min_depth must be at least 1");
-    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: ref_len differs from the one given to cl_site_upload");
-    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, "cl_site_scan_ex: null reference");
-    memset(out, 0, sizeof(*out));
-    out->start = start; out->end = end;
-    c->scan_cand_ex.clear();
-    out->candidates = c->scan_cand_ex.data();
-    c->scan_ms = 0.0; c->scan_bytes = 0;
-    if (start == end) return CL_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    StageTimer tmr;
-    if ((s = site_scan_index(c)) != CL_OK) return s;
-    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len), n_ref = ref_hi > start ? ref_hi - start : 0;
-    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
-    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
-    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
-    const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
-    // the candidate buffer grows and the scan runs again when more are wanted, as in cl_site_scan
-    uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
-    unsigned long long h_cls[8];
-    double ms_all = 0.0;
-    ScanExArgs A;
-    for (;;) {
-        HIP_TRY(c, S.sx_cand.reserve(cap));
-        HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
-        site_scan_ex_fill(c, A, filter, min_quality, min_depth, start, end);
-        A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
-        A.cand = S.sx_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-        HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
-        hipLaunchKernelGGL(k_site_scan_ex<false>, dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
-        HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float t = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
-        ms_all += t;
-        const uint64_t want = (uint32_t)h_cls[SCAN_CLASSES];
-        if (want <= cap) break;
-        cap = want;
-    }
-    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
-    c->scan_cand_ex.resize(n_cand);
-    if (n_cand) HIP_TRY(c, hipMemcpy(c->scan_cand_ex.data(), S.sx_cand.p, n_cand * sizeof(cl_scan_candidate_ex), hipMemcpyDeviceToHost));
-    c->scan_ms = ms_all;
-    c->scan_bytes = site_scan_ex_tile_bytes(S) + n_ref + n_cand * sizeof(cl_scan_candidate_ex);
-    tmr.lap("filtered site scan: reference in, kernel, candidates back");
-    std::sort(c->scan_cand_ex.begin(), c->scan_cand_ex.end(), [](const cl_scan_candidate_ex &a, const cl_scan_candidate_ex &b) { return a.pos < b.pos; });
-    out->n_low_depth = h_cls[SCAN_LOW_DEPTH]; out->n_mixed = h_cls[SCAN_MIXED]; out->n_uncomparable = h_cls[SCAN_UNCOMPARABLE];
-    out->n_match = h_cls[SCAN_MATCH]; out->n_variant = h_cls[SCAN_VARIANT];
-    if (h_cls[SCAN_AMBIGUOUS]) {
-        // the positions ten planes cannot classify: their 16-code histograms under the same filter (k_site_scan_settle)
-        std::vector<uint32_t> amb;
-        size_t k = 0;
-        for (const cl_scan_candidate_ex &cd : c->scan_cand_ex) { if (cd.alt == 0) amb.push_back(cd.pos); else c->scan_cand_ex[k++] = cd; }
-        c->scan_cand_ex.resize(k);
-        std::vector<uint32_t> hist(amb.size() * 16);
-        HIP_TRY(c, S.sx_amb.reserve(amb.size())); HIP_TRY(c, S.sx_hist.reserve(hist.size()));
-        HIP_TRY(c, hipMemcpyAsync(S.sx_amb.p, amb.data(), amb.size() * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_site_scan_settle, dim3((uint32_t)amb.size()), dim3(kBlock), 0, c->stream, A, S.sx_amb.p, S.sx_hist.p);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(hist.data(), S.sx_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (size_t i = 0; i < amb.size(); ++i) {
-            uint64_t depth = 0, m = 0;
-            for (int q = 0; q < 16; ++q) { depth += hist[i * 16 + q]; m = std::max<uint64_t>(m, hist[i * 16 + q]); }
-            if (10 * m >= 7 * depth) ++out->n_uncomparable; else ++out->n_mixed;
-        }
-        tmr.lap("filtered site scan: ambiguous positions settled");
-    }
-    out->candidates = c->scan_cand_ex.data();
-    return CL_OK;
-}
-
-static cl_status cl_site_scan_counts_ex_impl(cl_ctx *c, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)
-{
-    if (!c) return CL_ERR_INVALID;
-    cl_status s = site_scan_ex_check(c, "cl_site_scan_counts_ex", filter, start, end);
-    if (s != CL_OK) return s;
-    if (end - start > CL_SCAN_MAX_DENSE) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts_ex: more than CL_SCAN_MAX_DENSE positions");
-    c->scan_ms = 0.0; c->scan_bytes = 0;
-    if (start == end) return CL_OK;
-    if (!counts) return fail(c, CL_ERR_INVALID, "cl_site_scan_counts_ex: null array");
-    SiteResident &S = c->site;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((s = site_scan_index(c)) != CL_OK) return s;
-    const size_t n9 = (size_t)(end - start) * 9;
-    HIP_TRY(c, S.sx_dense.reserve(n9));
-    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
-    ScanExArgs A;
-    site_scan_ex_fill(c, A, filter, min_quality, 1, start, end);
-    A.dense = S.sx_dense.p;
-    HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
-    hipLaunchKernelGGL(k_site_scan_ex<true>, dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
-    HIP_TRY(c, hipMemcpyAsync(counts, S.sx_dense.p, n9 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float t = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
-    c->scan_ms = t;
-    c->scan_bytes = site_scan_ex_tile_bytes(S) + n9 * 4;
-    return CL_OK;
-}
-
 cl_status cl_site_attach_quals(cl_ctx *c, const cl_site_quals *quals, uint8_t min_base_quality)
 {
     try { return cl_site_attach_quals_impl(c, quals, min_base_quality); }
@@ -3318,14 +3257,14 @@ cl_status cl_site_attach_quals(cl_ctx *c, const cl_site_quals *quals, uint8_t mi
 cl_status cl_site_scan_ex(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const cl_scan_filter *filter, const uint8_t *ref_bases,
                           uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out)
 {
-    try { return cl_site_scan_ex_impl(c, min_quality, min_depth, filter, ref_bases, ref_len, start, end, out); }
+    try { return site_scan_impl<true>(c, min_quality, min_depth, filter, ref_bases, ref_len, start, end, out); }
     catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
     catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
 }
 
 cl_status cl_site_scan_counts_ex(cl_ctx *c, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)
 {
-    try { return cl_site_scan_counts_ex_impl(c, min_quality, filter, start, end, counts); }
+    try { return site_scan_counts_impl<true>(c, min_quality, filter, start, end, counts); }
     catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
     catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
 }

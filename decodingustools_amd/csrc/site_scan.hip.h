@@ -5,35 +5,53 @@
 // lies in its span, 64 sites per workgroup in LDS.  With a site at every base none of that helps, and the histogram
 // (64 bytes per position) has to cross HBM and the link.  Here a workgroup owns a window of kScanWin reference positions:
 // it counts the bases of every read over the window in LDS, applies the calling rule of caller.rs:132-149 there and
-// writes back only the positions that differ from the reference (or, in the dense mode, five counters per position).
+// writes back only the positions that differ from the reference (or, in the dense mode, the counters per position).
 //
 // Per position the semantics are those of k_site_pileup, condition by condition (hist[p][c] of cl_site_run for the
 // 1-based site p + 1): read start < contig_len, mapq >= min_quality, bases of M/=/X operations, query index < l_seq,
-// p < ref_len; no flag or base-quality filter.
+// p < ref_len.  The unfiltered form has no flag or base-quality filter.
 //
-// Two kernels:
+// Three kernels:
 //   k_site_scan_index   once per resident tile: the reference end of every read and, per window, the index range
 //                       [first, last) of the reads that overlap it (atomicMin / atomicMax of the read's index over
 //                       the windows of its span).  The range holds every overlapping read whatever the order of the
 //                       tile, so an unsorted tile gives exact counts too -- its ranges are merely wider.
-//   k_site_scan<DENSE>  one workgroup per window: reads of the window's range are dealt to the threads, a thread walks
-//                       its read's CIGAR over the window and adds into six LDS counter planes (A, C, G, T, N, any other
-//                       code; one ds_add without return per base, consecutive positions in consecutive banks); then
-//                       every thread classifies positions and the candidates are compacted with one ballot and one
-//                       atomic per wave.
+//   k_site_scan<FILTERED, DENSE>
+//                       one workgroup per window: reads of the window's range are dealt to the threads, a thread walks
+//                       its read's CIGAR over the window and adds into LDS counter planes (one ds_add without return
+//                       per base, consecutive positions in consecutive banks); then every thread classifies positions
+//                       and the candidates are compacted with one ballot and one atomic per wave.
+//   k_site_scan_settle  filtered form only: the 16-code histogram of the few positions the planes cannot classify.
 //
-// Six planes and not sixteen: depth = their sum, and the call needs the largest single code.  That is one of the five
-// named planes unless the codes of the sixth plane (=, IUPAC ambiguity codes) together reach 7/10 of the depth; such a
-// position cannot be classified from six counters (one code with 7/10 is "uncomparable", several that share it are
-// "mixed").  It is reported as ambiguous and the host settles it with the 16-code histogram of cl_site_run.
+// The unfiltered form (ScanForm<false>) counts in six planes: A, C, G, T, N, any other code.  Six planes and not
+// sixteen: depth = their sum, and the call needs the largest single code.  That is one of the five named planes unless
+// the codes of the sixth plane (=, IUPAC ambiguity codes) together reach 7/10 of the depth; such a position cannot be
+// classified from six counters (one code with 7/10 is "uncomparable", several that share it are "mixed").  It is
+// reported as ambiguous and the host settles it with the 16-code histogram of cl_site_run.
+//
+// The filtered, strand-aware form (ScanForm<true>) is for a resident tile that carries an attachment
+// (cl_site_attach_quals): per read its BAM flag, per base one pass bit (qual >= min_base_quality, taken on the host;
+// bit i of word w <-> base 64 w + i in the numbering of seq4).  It runs over the same index and the same window of
+// kScanWin positions per workgroup.  Relative to the unfiltered form:
+//   per read   one 2-byte load of the flag and one early exit on (flag & exclude_flags); flag & 0x10 picks the strand;
+//   per base   one bit of a 64-bit word of pass bits that is loaded once per CIGAR operation and once more whenever
+//              the base index crosses a multiple of 64 -- never the quality bytes;
+//   counters   ten LDS planes instead of six: A C G T by strand (forward, reverse), N, any other code.  Exactly 40 KB of
+//              LDS per workgroup: 4 workgroups (16 waves) per CU of 160 KiB where the unfiltered kernel has 6.
+// The call sums the strands and is the same rule (scan_classify); a candidate also carries the per-strand counts of its
+// alternative and reference bases.  A position whose "other" plane holds 7/10 of the depth is reported as ambiguous
+// exactly as in the unfiltered form, and settled with k_site_scan_settle under the same filter (cl_site_run's histogram
+// is unfiltered and cannot serve).  The unfiltered instantiations hold no flag load, no pass-bit load and no test of
+// use_base_quality: the filter is an empty type there and every use of it sits behind if constexpr.
 #pragma once
+
+#include <type_traits>
 
 #include "kernels.hip.h"
 
 namespace clk {
 
-constexpr uint32_t kScanWin = 1024;          // positions per workgroup: 6 planes x 1024 x 4 B = 24 KB of LDS, 6 workgroups per CU
-constexpr uint32_t kScanPlanes = 6;          // A C G T N other
+constexpr uint32_t kScanWin = 1024;          // positions per workgroup: 6 planes x 1024 x 4 B = 24 KB of LDS, 6 workgroups per CU (10 planes: 40 KB, 4)
 enum { SCAN_LOW_DEPTH = 0, SCAN_MIXED = 1, SCAN_UNCOMPARABLE = 2, SCAN_MATCH = 3, SCAN_VARIANT = 4, SCAN_AMBIGUOUS = 5, SCAN_CLASSES = 6 };
 
 // one compacted position: a variant (alt = 'A' 'C' 'G' 'T') or an ambiguous one (alt = 0, settled by the host)
@@ -41,6 +59,37 @@ struct ScanCand {
     uint32_t pos;                            // 1-based
     uint8_t  ref, alt, pad[2];
     uint32_t a, c, g, t, depth;
+};
+
+struct ScanCandEx {
+    uint32_t pos;                            // 1-based
+    uint8_t  ref, alt, pad[2];
+    uint32_t a, c, g, t, depth;              // both strands
+    uint32_t alt_fwd, alt_rev, ref_fwd, ref_rev;
+};
+
+struct ScanNoFilter {};
+
+struct ScanFilter {
+    const uint16_t *flag;                    // per read
+    const unsigned long long *pass;          // one bit per base of seq4
+    uint32_t exclude_flags, use_bq;
+};
+
+// everything the two forms differ in
+template <bool FILTERED>
+struct ScanForm {
+    static constexpr uint32_t kStrands = FILTERED ? 2u : 1u;
+    static constexpr uint32_t kPlanes = 4u * kStrands + 2u;    // A C G T N other, or A+ A- C+ C- G+ G- T+ T- N other  (+ forward, - reverse: flag & 0x10)
+    static constexpr uint32_t kDense = 4u * kStrands + 1u;     // dense counters per position: A C G T depth, or A+ A- C+ C- G+ G- T+ T- depth
+    using Cand = std::conditional_t<FILTERED, ScanCandEx, ScanCand>;
+    using Filter = std::conditional_t<FILTERED, ScanFilter, ScanNoFilter>;
+    // the plane of a 4-bit base code on strand rev (always 0 in the unfiltered form)
+    static __device__ __forceinline__ uint32_t plane(uint32_t code, uint32_t rev)
+    {
+        return code == 1u ? rev : code == 2u ? kStrands + rev : code == 4u ? 2u * kStrands + rev : code == 8u ? 3u * kStrands + rev
+             : code == 15u ? 4u * kStrands : 4u * kStrands + 1u;
+    }
 };
 
 struct ScanIndexArgs {
@@ -64,9 +113,15 @@ struct ScanArgs {
     const uint8_t *refb;                     // reference bytes of [start, min(end_pos, ref_len)), refb[0] <-> start
     unsigned long long *cls;                 // SCAN_CLASSES counts
     uint32_t *n_cand;                        // candidates wanted (also beyond cand_cap)
-    ScanCand *cand;
     uint32_t cand_cap;
-    uint32_t *dense;                         // DENSE: (end_pos - start) * 5: A C G T depth
+    uint32_t *dense;                         // DENSE: (end_pos - start) * ScanForm::kDense
+};
+
+template <bool FILTERED>
+struct ScanFormArgs {
+    ScanArgs s;
+    typename ScanForm<FILTERED>::Filter f;
+    typename ScanForm<FILTERED>::Cand *cand;
 };
 
 // number of CIGAR operations and bases of a read, with SiteRec's escape to the next record's offsets
@@ -107,114 +162,123 @@ __global__ __launch_bounds__(kBlock) void k_site_scan_index(ScanIndexArgs a)
     a.end[r] = e;
 }
 
-__device__ __forceinline__ uint32_t scan_plane(uint32_t code)
+// window w of the contig: [ws, ws + kScanWin); [lo, we) is the part that is asked for, [lo, hi) the part that can hold a
+// count (p < ref_len, caller.rs:110-113).  lo <= we: the host launches overlapping windows only
+struct ScanWindow { uint32_t ws, lo, we, hi; };
+
+__device__ __forceinline__ ScanWindow scan_window(const ScanArgs &a, uint32_t w)
 {
-    return code == 1u ? 0u : code == 2u ? 1u : code == 4u ? 2u : code == 8u ? 3u : code == 15u ? 4u : 5u;
+    const unsigned long long ws64 = (unsigned long long)w * kScanWin;
+    ScanWindow v;
+    v.ws = (uint32_t)ws64;
+    v.lo = v.ws > a.start ? v.ws : a.start;
+    v.we = (ws64 + kScanWin < (unsigned long long)a.end_pos) ? v.ws + kScanWin : a.end_pos;
+    v.hi = (unsigned long long)v.we < a.ref_len ? v.we : (uint32_t)a.ref_len;
+    return v;
 }
 
-template <bool DENSE>
-__global__ __launch_bounds__(kBlock) void k_site_scan(ScanArgs a)
+// read start < contig_len (end = 0 otherwise), the mapping-quality gate (caller.rs:80), overlap with [lo, hi)
+__device__ __forceinline__ bool scan_read_counts(const ScanArgs &a, const uint4 &rr, uint32_t e, uint32_t lo, uint32_t hi)
 {
-    __shared__ uint32_t s_cnt[kScanPlanes * kScanWin];
-    __shared__ unsigned long long s_cls[SCAN_CLASSES];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t w = a.win0 + blockIdx.x;
-    const unsigned long long ws64 = (unsigned long long)w * kScanWin;
-    // the part of the window that is asked for and that can hold a count (p < ref_len, caller.rs:110-113)
-    const uint32_t ws = (uint32_t)ws64;
-    const uint32_t lo = ws > a.start ? ws : a.start;
-    const uint32_t we = (ws64 + kScanWin < (unsigned long long)a.end_pos) ? ws + kScanWin : a.end_pos;   // lo <= we: the host launches overlapping windows only
-    const uint32_t hi = (unsigned long long)we < a.ref_len ? we : (uint32_t)a.ref_len;
-    for (uint32_t i = tid; i < kScanPlanes * kScanWin; i += kBlock) s_cnt[i] = 0;
+    return (rr.w & 255u) >= a.min_quality && e > lo && (uint32_t)rr.x < hi;
+}
+
+// The walk of read r over the bases of its M/=/X operations at the positions of [lo, hi).  Per operation:
+// run = begin_run(bi, any) with the base bi of its first position in [lo, hi), in the numbering of seq4, and whether it
+// has one at all; then per_base(p, bi, run) for every position p.  What a form keeps from base to base (the word of pass
+// bits) is that run value: it does not outlive the operation, and so holds no register across the CIGAR loop.
+template <class BeginRun, class PerBase>
+__device__ __forceinline__ void scan_walk_read(const ScanArgs &a, uint32_t r, const uint4 &rr, uint32_t lo, uint32_t hi, BeginRun &&begin_run,
+                                               PerBase &&per_base)
+{
+    uint32_t k1; unsigned long long slen;
+    scan_read_extent(a.rec, r, rr, k1, slen);
+    const unsigned long long base = a.seq_base[r / kBlock];
+    const unsigned long long s0 = base + (uint32_t)(rr.z - (uint32_t)base);
+    unsigned long long x = (uint32_t)rr.x, y = 0;
+    for (uint32_t kk = rr.y; kk < k1 && x < hi; ++kk) {
+        const uint32_t c = a.cigar[kk];
+        const uint32_t op = c & 15u, l = c >> 4;
+        if (op_match(op)) {
+            // [x, x + l) cut to [lo, hi) and to the bases the read has (query index < l_seq, caller.rs:105)
+            unsigned long long p0 = x > lo ? x : lo, p1 = x + l < hi ? x + l : hi;
+            if (y < slen) { if (p1 - x > slen - y && p1 > x) p1 = x + (slen - y); } else p1 = p0;
+            unsigned long long bi = s0 + y + (p0 - x);
+            auto run = begin_run(bi, p0 < p1);
+            for (unsigned long long p = p0; p < p1; ++p, ++bi) per_base((uint32_t)p, bi, run);
+            x += l; y += l;
+        } else if (op_del(op)) {
+            x += l;
+        } else if (op_ins(op)) {
+            y += l;
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t scan_base_code(const uint8_t *seq4, unsigned long long bi)
+{
+    const uint32_t byte = seq4[bi >> 1];
+    return (bi & 1ull) ? (byte & 15u) : (byte >> 4);
+}
+
+// the word of pass bits of a run's first base bi (all ones without a base-quality filter) ...
+__device__ __forceinline__ unsigned long long scan_pass_word(const ScanFilter &f, unsigned long long bi, bool any)
+{
+    return (f.use_bq && any) ? f.pass[bi >> 6] : ~0ull;
+}
+
+// ... and the pass bit of base bi of that run: pw is loaded again when bi crosses a multiple of 64
+__device__ __forceinline__ bool scan_base_passes(const ScanFilter &f, unsigned long long bi, unsigned long long &pw)
+{
+    if (!f.use_bq) return true;
+    if ((bi & 63ull) == 0ull) pw = f.pass[bi >> 6];
+    return (pw >> (bi & 63ull)) & 1ull;
+}
+
+// The calling rule.  Returns the class; rb becomes the upper-cased reference byte (anything but ACGT is "other"),
+// alt the most frequent of A C G T N (the first in that order among equals) and ai its index in that order.
+__device__ __forceinline__ int scan_classify(uint32_t A, uint32_t Cc, uint32_t G, uint32_t T, uint32_t N, uint32_t O, uint32_t &rb, uint32_t min_depth,
+                                             uint32_t &alt, uint32_t &ai, unsigned long long &depth)
+{
+    depth = (unsigned long long)A + Cc + G + T + N + O;                     // below 2^32: one count per read
+    uint32_t m = A; alt = 'A'; ai = 0;
+    if (Cc > m) { m = Cc; alt = 'C'; ai = 1; }
+    if (G > m) { m = G; alt = 'G'; ai = 2; }
+    if (T > m) { m = T; alt = 'T'; ai = 3; }
+    if (N > m) { m = N; alt = 'N'; ai = 4; }
+    rb &= ~32u;
+    const bool ref_ok = rb == 'A' || rb == 'C' || rb == 'G' || rb == 'T';
+    // called <=> m / depth >= 0.7 in f64 <=> 10 m >= 7 depth (a ratio off 7/10 is off by more than an f64 divide rounds)
+    if (depth < min_depth) return SCAN_LOW_DEPTH;
+    if (10ull * m >= 7ull * depth) return (alt == 'N' || !ref_ok) ? SCAN_UNCOMPARABLE : (alt == rb ? SCAN_MATCH : SCAN_VARIANT);
+    if (10ull * O >= 7ull * depth) return SCAN_AMBIGUOUS;
+    return SCAN_MIXED;
+}
+
+// the candidates of a wave go out behind one another: one ballot, one atomic of lane 0 (every lane of the wave calls)
+template <class Cand>
+__device__ __forceinline__ void scan_compact(bool emit, const Cand &cd, uint32_t lane, uint32_t *n_cand, Cand *cand, uint32_t cand_cap)
+{
+    const unsigned long long bal = __ballot(emit);
+    if (!bal) return;
+    uint32_t base_i = 0;
+    if (lane == 0) base_i = atomicAdd(n_cand, (uint32_t)__popcll(bal));
+    base_i = __shfl(base_i, 0);
+    if (emit) {
+        const uint32_t i = base_i + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (i < cand_cap) cand[i] = cd;
+    }
+}
+
+// The class counts of the threads: by wave, then by workgroup in s_cls, then one atomic per class.  s_cls is the first
+// words of the counter planes (the filtered kernel has exactly 40 KB: four workgroups fit a CU's 160 KiB, a byte more
+// and only three do), so it is cleared only once every thread has read its counters.
+__device__ __forceinline__ void scan_reduce_classes(const uint32_t (&mine)[SCAN_CLASSES], unsigned long long *s_cls, unsigned long long *cls,
+                                                    uint32_t tid, uint32_t lane)
+{
+    __syncthreads();
     if (tid < (uint32_t)SCAN_CLASSES) s_cls[tid] = 0;
     __syncthreads();
-    const uint32_t r_first = a.wfirst[w], r_last = a.wlast[w];
-    if (r_first < r_last && lo < hi) {
-        for (uint32_t r = r_first + tid; r < r_last; r += kBlock) {
-            const uint4 rr = *reinterpret_cast<const uint4 *>(a.rec + r);
-            const uint32_t e = a.end[r];
-            // read start < contig_len (end = 0 otherwise), the mapping-quality gate (caller.rs:80), overlap with [lo, hi)
-            if ((rr.w & 255u) < a.min_quality || e <= lo || (uint32_t)rr.x >= hi) continue;
-            uint32_t k1; unsigned long long slen;
-            scan_read_extent(a.rec, r, rr, k1, slen);
-            const unsigned long long base = a.seq_base[r / kBlock];
-            const unsigned long long s0 = base + (uint32_t)(rr.z - (uint32_t)base);
-            unsigned long long x = (uint32_t)rr.x, y = 0;
-            for (uint32_t kk = rr.y; kk < k1 && x < hi; ++kk) {
-                const uint32_t c = a.cigar[kk];
-                const uint32_t op = c & 15u, l = c >> 4;
-                if (op_match(op)) {
-                    // [x, x + l) cut to [lo, hi) and to the bases the read has (query index < l_seq, caller.rs:105)
-                    unsigned long long p0 = x > lo ? x : lo, p1 = x + l < hi ? x + l : hi;
-                    if (y < slen) { if (p1 - x > slen - y && p1 > x) p1 = x + (slen - y); } else p1 = p0;
-                    for (unsigned long long p = p0; p < p1; ++p) {
-                        const unsigned long long bi = s0 + y + (p - x);
-                        const uint32_t byte = a.seq4[bi >> 1];
-                        const uint32_t code = (bi & 1ull) ? (byte & 15u) : (byte >> 4);
-                        atomicAdd(&s_cnt[scan_plane(code) * kScanWin + ((uint32_t)p - ws)], 1u);
-                    }
-                    x += l; y += l;
-                } else if (op_del(op)) {
-                    x += l;
-                } else if (op_ins(op)) {
-                    y += l;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (DENSE) {
-        // five counters per position of the range, in the order of the output array: consecutive threads, consecutive words
-        const uint32_t n5 = (we - lo) * 5u;
-        uint32_t *out = a.dense + (unsigned long long)(lo - a.start) * 5ull;
-        for (uint32_t i = tid; i < n5; i += kBlock) {
-            const uint32_t q = i / 5u, cc = i - q * 5u, o = lo - ws + q;
-            uint32_t v = s_cnt[(cc < 4u ? cc : 4u) * kScanWin + o];
-            if (cc == 4u) v += s_cnt[o] + s_cnt[kScanWin + o] + s_cnt[2u * kScanWin + o] + s_cnt[3u * kScanWin + o] + s_cnt[5u * kScanWin + o];
-            out[i] = v;
-        }
-        return;
-    }
-    uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
-    const uint32_t lane = tid & 63u;
-    for (uint32_t o0 = 0; o0 < kScanWin; o0 += kBlock) {                       // (uniform trip count: the ballot below needs whole waves)
-        const uint32_t o = o0 + tid, p = ws + o;
-        const bool in = p >= lo && p < we;
-        int cls = -1;
-        ScanCand cd;
-        if (in) {
-            const uint32_t A = s_cnt[o], Cc = s_cnt[kScanWin + o], G = s_cnt[2u * kScanWin + o], T = s_cnt[3u * kScanWin + o];
-            const uint32_t N = s_cnt[4u * kScanWin + o], O = s_cnt[5u * kScanWin + o];
-            const unsigned long long depth = (unsigned long long)A + Cc + G + T + N + O;      // below 2^32: one count per read
-            uint32_t m = A; uint32_t alt = 'A';
-            if (Cc > m) { m = Cc; alt = 'C'; }
-            if (G > m) { m = G; alt = 'G'; }
-            if (T > m) { m = T; alt = 'T'; }
-            if (N > m) { m = N; alt = 'N'; }
-            uint32_t rb = p < hi ? a.refb[p - a.start] : (uint32_t)'N';
-            rb &= ~32u;                                                          // upper case; anything but ACGT is "other"
-            const bool ref_ok = rb == 'A' || rb == 'C' || rb == 'G' || rb == 'T';
-            // called <=> m / depth >= 0.7 in f64 <=> 10 m >= 7 depth (a ratio off 7/10 is off by more than an f64 divide rounds)
-            if (depth < a.min_depth) cls = SCAN_LOW_DEPTH;
-            else if (10ull * m >= 7ull * depth) cls = (alt == 'N' || !ref_ok) ? SCAN_UNCOMPARABLE : (alt == rb ? SCAN_MATCH : SCAN_VARIANT);
-            else if (10ull * O >= 7ull * depth) cls = SCAN_AMBIGUOUS;
-            else cls = SCAN_MIXED;
-            mine[cls] += 1u;
-            cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.alt = cls == SCAN_VARIANT ? (uint8_t)alt : (uint8_t)0; cd.pad[0] = cd.pad[1] = 0;
-            cd.a = A; cd.c = Cc; cd.g = G; cd.t = T; cd.depth = (uint32_t)depth;
-        }
-        const bool emit = cls == SCAN_VARIANT || cls == SCAN_AMBIGUOUS;
-        const unsigned long long bal = __ballot(emit);
-        if (bal) {
-            uint32_t base_i = 0;
-            if (lane == 0) base_i = atomicAdd(a.n_cand, (uint32_t)__popcll(bal));
-            base_i = __shfl(base_i, 0);
-            if (emit) {
-                const uint32_t i = base_i + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-                if (i < a.cand_cap) a.cand[i] = cd;
-            }
-        }
-    }
 #pragma unroll
     for (int k = 0; k < SCAN_CLASSES; ++k) {
         uint32_t v = mine[k];
@@ -222,7 +286,117 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanArgs a)
         if (lane == 0 && v) atomicAdd(&s_cls[k], (unsigned long long)v);
     }
     __syncthreads();
-    if (tid < (uint32_t)SCAN_CLASSES && s_cls[tid]) atomicAdd(&a.cls[tid], s_cls[tid]);
+    if (tid < (uint32_t)SCAN_CLASSES && s_cls[tid]) atomicAdd(&cls[tid], s_cls[tid]);
+}
+
+template <bool FILTERED, bool DENSE>
+__global__ __launch_bounds__(kBlock) void k_site_scan(ScanFormArgs<FILTERED> ax)
+{
+    using Form = ScanForm<FILTERED>;
+    constexpr uint32_t S = Form::kStrands;
+    __shared__ alignas(8) uint32_t s_cnt[Form::kPlanes * kScanWin];
+    const ScanArgs &a = ax.s;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t w = a.win0 + blockIdx.x;
+    const ScanWindow win = scan_window(a, w);
+    const uint32_t ws = win.ws, lo = win.lo, we = win.we, hi = win.hi;
+    for (uint32_t i = tid; i < Form::kPlanes * kScanWin; i += kBlock) s_cnt[i] = 0;
+    __syncthreads();
+    const uint32_t r_first = a.wfirst[w], r_last = a.wlast[w];
+    if (r_first < r_last && lo < hi) {
+        for (uint32_t r = r_first + tid; r < r_last; r += kBlock) {
+            const uint4 rr = *reinterpret_cast<const uint4 *>(a.rec + r);
+            if (!scan_read_counts(a, rr, a.end[r], lo, hi)) continue;
+            uint32_t rev = 0;
+            if constexpr (FILTERED) {
+                const uint32_t fl = ax.f.flag[r];
+                if (fl & ax.f.exclude_flags) continue;
+                rev = (fl >> 4) & 1u;
+            }
+            scan_walk_read(a, r, rr, lo, hi,
+                [&](unsigned long long bi, bool any) {
+                    if constexpr (FILTERED) return scan_pass_word(ax.f, bi, any); else return ScanNoFilter{};
+                },
+                [&](uint32_t p, unsigned long long bi, auto &pw) {
+                    if constexpr (FILTERED) { if (!scan_base_passes(ax.f, bi, pw)) return; }
+                    atomicAdd(&s_cnt[Form::plane(scan_base_code(a.seq4, bi), rev) * kScanWin + (p - ws)], 1u);
+                });
+        }
+    }
+    __syncthreads();
+    if (DENSE) {
+        // kDense counters per position of the range, in the order of the output array: consecutive threads, consecutive words
+        const uint32_t nd = (we - lo) * Form::kDense;
+        uint32_t *out = a.dense + (unsigned long long)(lo - a.start) * Form::kDense;
+        for (uint32_t i = tid; i < nd; i += kBlock) {
+            const uint32_t q = i / Form::kDense, cc = i - q * Form::kDense, o = lo - ws + q;
+            uint32_t v;
+            if (cc < Form::kDense - 1u) v = s_cnt[cc * kScanWin + o];
+            else { v = 0; for (uint32_t k = 0; k < Form::kPlanes; ++k) v += s_cnt[k * kScanWin + o]; }
+            out[i] = v;
+        }
+        return;
+    }
+    uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
+    const uint32_t lane = tid & 63u;
+    for (uint32_t o0 = 0; o0 < kScanWin; o0 += kBlock) {                       // (uniform trip count: the ballot needs whole waves)
+        const uint32_t o = o0 + tid, p = ws + o;
+        int cls = -1;
+        typename Form::Cand cd;
+        if (p >= lo && p < we) {
+            uint32_t f[4], v[4];                                                // A C G T, forward and reverse
+#pragma unroll
+            for (uint32_t b = 0; b < 4u; ++b) { f[b] = s_cnt[(S * b) * kScanWin + o]; v[b] = FILTERED ? s_cnt[(S * b + 1u) * kScanWin + o] : 0u; }
+            const uint32_t A = f[0] + v[0], Cc = f[1] + v[1], G = f[2] + v[2], T = f[3] + v[3];
+            uint32_t rb = p < hi ? a.refb[p - a.start] : (uint32_t)'N', alt, ai;
+            unsigned long long depth;
+            cls = scan_classify(A, Cc, G, T, s_cnt[(4u * S) * kScanWin + o], s_cnt[(4u * S + 1u) * kScanWin + o], rb, a.min_depth, alt, ai, depth);
+            mine[cls] += 1u;
+            cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.alt = cls == SCAN_VARIANT ? (uint8_t)alt : (uint8_t)0; cd.pad[0] = cd.pad[1] = 0;
+            cd.a = A; cd.c = Cc; cd.g = G; cd.t = T; cd.depth = (uint32_t)depth;
+            if constexpr (FILTERED) {
+                cd.alt_fwd = cd.alt_rev = cd.ref_fwd = cd.ref_rev = 0;
+                if (cls == SCAN_VARIANT) {
+                    const uint32_t ri = rb == 'A' ? 0u : rb == 'C' ? 1u : rb == 'G' ? 2u : 3u;    // (a variant's reference base is of ACGT)
+#pragma unroll
+                    for (uint32_t b = 0; b < 4u; ++b) {                           // (selects, not indexed registers)
+                        if (b == ai) { cd.alt_fwd = f[b]; cd.alt_rev = v[b]; }
+                        if (b == ri) { cd.ref_fwd = f[b]; cd.ref_rev = v[b]; }
+                    }
+                }
+            }
+        }
+        scan_compact(cls == SCAN_VARIANT || cls == SCAN_AMBIGUOUS, cd, lane, a.n_cand, ax.cand, a.cand_cap);
+    }
+    scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);
+}
+
+// The 16-code histogram of single positions under the filter of ax: one workgroup per position of pos1 (1-based, inside
+// the contig), over the reads of the position's window range.  For the few positions the ten planes cannot classify.
+__global__ __launch_bounds__(kBlock) void k_site_scan_settle(ScanFormArgs<true> ax, const uint32_t *pos1, uint32_t *hist16)
+{
+    __shared__ uint32_t s_h[16];
+    const ScanArgs &a = ax.s;
+    const uint32_t tid = threadIdx.x;
+    if (tid < 16u) s_h[tid] = 0;
+    __syncthreads();
+    const uint32_t p = pos1[blockIdx.x] - 1u;
+    const uint32_t w = p / kScanWin;
+    const uint32_t r_first = a.wfirst[w], r_last = a.wlast[w];
+    if (r_first < r_last && (unsigned long long)p < a.ref_len) {
+        for (uint32_t r = r_first + tid; r < r_last; r += kBlock) {
+            const uint4 rr = *reinterpret_cast<const uint4 *>(a.rec + r);
+            if (!scan_read_counts(a, rr, a.end[r], p, p + 1u)) continue;       // (p < contig_len <= 2^32 - 1)
+            if ((uint32_t)ax.f.flag[r] & ax.f.exclude_flags) continue;
+            scan_walk_read(a, r, rr, p, p + 1u,
+                [&](unsigned long long bi, bool any) { return scan_pass_word(ax.f, bi, any); },
+                [&](uint32_t, unsigned long long bi, unsigned long long &pw) {
+                    if (scan_base_passes(ax.f, bi, pw)) atomicAdd(&s_h[scan_base_code(a.seq4, bi)], 1u);
+                });
+        }
+    }
+    __syncthreads();
+    if (tid < 16u) hist16[(size_t)blockIdx.x * 16u + tid] = s_h[tid];
 }
 
 } // namespace clk

@@ -241,6 +241,18 @@ static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_
     auto engine_err = [&](const char *what) { const char *m = cl_last_error(ctx.get()); set_err(err, err_len, (m && *m) ? m : what); };
     int rc = cl_site_upload(ctx.get(), contig_len, blen, &tile);
     if (rc != CL_OK) { engine_err("site upload failed"); return rc; }
+    // scan result -> annotation -> TSV, for either result type (wopt: the filter columns of the header, or none)
+    auto finish = [&](int scan_rc, const auto &res, const dut_variants_options *wopt) {
+        if (scan_rc != CL_OK) { engine_err("site scan failed"); return scan_rc; }
+        dut_variant_note *notes = nullptr;
+        if (tree) {
+            const int arc = annotate(tree.get(), build.c_str(), contig, res.candidates, (size_t)res.n_variant, &notes);
+            if (arc != CL_OK) { set_err(err, err_len, "annotation failed"); return arc; }
+        }
+        const int wrc = write_tsv(output_path, contig, &res, min_depth, min_quality, wopt, notes, err, err_len);
+        dut_variants_free_notes(notes, (size_t)res.n_variant);
+        return wrc;
+    };
     if (vopt && vopt->filtered) {
         cl_site_quals q;
         q.n_reads = rec.n; q.flag = rec.flag; q.qual_off = rec.qual_off; q.qual = rec.qual; q.seq_off = seq_off;
@@ -248,28 +260,10 @@ static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_
         if (rc != CL_OK) { engine_err("site attachment failed"); return rc; }
         const cl_scan_filter flt = {vopt->exclude_flags, (uint8_t)(vopt->has_min_base_quality ? 1 : 0), 0};
         cl_scan_result_ex res;
-        rc = cl_site_scan_ex(ctx.get(), min_quality, min_depth, &flt, bases, blen, start, end, &res);
-        if (rc != CL_OK) { engine_err("site scan failed"); return rc; }
-        dut_variant_note *notes = nullptr;
-        if (tree) {
-            rc = dut_variants_annotate_ex(tree.get(), build.c_str(), contig, res.candidates, (size_t)res.n_variant, &notes);
-            if (rc != CL_OK) { set_err(err, err_len, "annotation failed"); return rc; }
-        }
-        rc = dut_variants_write_ex(output_path, contig, &res, min_depth, min_quality, vopt, notes, err, err_len);
-        dut_variants_free_notes(notes, (size_t)res.n_variant);
-        return rc;
+        return finish(cl_site_scan_ex(ctx.get(), min_quality, min_depth, &flt, bases, blen, start, end, &res), res, vopt);
     }
     cl_scan_result res;
-    rc = cl_site_scan(ctx.get(), min_quality, min_depth, bases, blen, start, end, &res);
-    if (rc != CL_OK) { engine_err("site scan failed"); return rc; }
-    dut_variant_note *notes = nullptr;
-    if (tree) {
-        rc = dut_variants_annotate(tree.get(), build.c_str(), contig, res.candidates, (size_t)res.n_variant, &notes);
-        if (rc != CL_OK) { set_err(err, err_len, "annotation failed"); return rc; }
-    }
-    rc = dut_variants_write(output_path, contig, &res, min_depth, min_quality, notes, err, err_len);
-    dut_variants_free_notes(notes, (size_t)res.n_variant);
-    return rc;
+    return finish(cl_site_scan(ctx.get(), min_quality, min_depth, bases, blen, start, end, &res), res, nullptr);
 }
 
 int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, const char *contig, int has_region,

@@ -8,7 +8,8 @@ own flags plus a seeded 0x10 on half of the reads, and its config-2 quality mix)
   2. The attachment (cl_site_attach_quals: host pass-bit pack + upload of bits and flags), call to return.
   3. With --parent-lib: the unfiltered cl_site_scan of another build of the library (the parent commit's) on the same
      tile in the same process, alternating with this build's.  That library is loaded beside this one and only the
-     calls both have are bound (cl_create, cl_site_upload, cl_site_scan, cl_site_scan_stats, cl_destroy).
+     calls both have are bound (cl_create, cl_site_upload, cl_site_scan, cl_site_scan_stats, cl_destroy) -- and, when it
+     exports them, cl_site_attach_quals and cl_site_scan_ex: its filtered scan is then timed in the same loop too.
 
     python tools/filtered_scan_bench.py [--length 57227415] [--reps 5] [--parent-lib FILE] [--bench-note FILE] [--out FILE]
 """
@@ -26,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from decodingustools_amd import CallableOptions, Engine, _lib, synth  # noqa: E402
+from decodingustools_amd.callable_loci import _site_quals  # noqa: E402
 
 
 def spread(v):
@@ -33,7 +35,8 @@ def spread(v):
 
 
 class OtherLib:
-    """The unfiltered scan of another build of the library, through the calls every build has."""
+    """The scans of another build of the library: the unfiltered one through the calls every build has, the filtered
+    one when that build exports it."""
 
     def __init__(self, path, rec, L):
         self.lib = lib = C.CDLL(path)
@@ -52,11 +55,27 @@ class OtherLib:
         for f in ("pos", "mapq", "cigar_off", "cigar", "seq_off", "seq4"):
             setattr(t, f, getattr(rec, f).ctypes.data)
         assert lib.cl_site_upload(self.h, L, L, C.byref(t)) == 0
+        self.filtered = hasattr(lib, "cl_site_attach_quals") and hasattr(lib, "cl_site_scan_ex")
+        if self.filtered:
+            lib.cl_site_attach_quals.argtypes = [C.c_void_p, C.POINTER(_lib.cl_site_quals), C.c_uint8]
+            lib.cl_site_scan_ex.argtypes = [C.c_void_p, C.c_uint8, C.c_uint32, C.POINTER(_lib.cl_scan_filter), C.c_void_p, C.c_uint64,
+                                            C.c_uint32, C.c_uint32, C.POINTER(_lib.cl_scan_result_ex)]
 
-    def scan(self, mq, md, ref):
-        r = _lib.cl_scan_result()
-        t0 = time.perf_counter()
-        assert self.lib.cl_site_scan(self.h, mq, md, ref.ctypes.data, ref.shape[0], 0, ref.shape[0], C.byref(r)) == 0
+    def attach(self, rec, min_base_quality):
+        q = _site_quals(rec)
+        assert self.lib.cl_site_attach_quals(self.h, C.byref(q), min_base_quality) == 0
+
+    def scan(self, mq, md, ref, exclude_flags=None):
+        """(call ms, kernel ms, variants) of cl_site_scan, or of cl_site_scan_ex (exclude_flags given; base quality on)."""
+        if exclude_flags is None:
+            r = _lib.cl_scan_result()
+            t0 = time.perf_counter()
+            assert self.lib.cl_site_scan(self.h, mq, md, ref.ctypes.data, ref.shape[0], 0, ref.shape[0], C.byref(r)) == 0
+        else:
+            r = _lib.cl_scan_result_ex()
+            f = _lib.cl_scan_filter(exclude_flags, 1, 0)
+            t0 = time.perf_counter()
+            assert self.lib.cl_site_scan_ex(self.h, mq, md, C.byref(f), ref.ctypes.data, ref.shape[0], 0, ref.shape[0], C.byref(r)) == 0
         call = (time.perf_counter() - t0) * 1e3
         ms = C.c_double(); b = C.c_uint64()
         self.lib.cl_site_scan_stats(self.h, C.byref(ms), C.byref(b))
@@ -76,7 +95,7 @@ def main():
     ap.add_argument("--exclude-flags", type=lambda s: int(s, 0), default=0x704)
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--bench-note", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_filtered_scan.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r09_scan_unified.json"))
     a = ap.parse_args()
     L = a.length
     seed = synth.seed_for(5, 23)
@@ -102,16 +121,23 @@ def main():
             t0 = time.perf_counter()
             eng.site_attach_quals(rec, a.min_base_quality)
             attach.append((time.perf_counter() - t0) * 1e3)
-        eng.site_scan_ex(mq, md, scan_ref, ex, True)
+        first_f = eng.site_scan_ex(mq, md, scan_ref, ex, True)
         other = OtherLib(a.parent_lib, rec, L) if a.parent_lib else None
         if other:
             assert other.scan(mq, md, scan_ref)[2] == first.variant
-        f_call, f_kern, u_call, u_kern, p_call, p_kern = [], [], [], [], [], []
+            if other.filtered:
+                other.attach(rec, a.min_base_quality)
+                assert other.scan(mq, md, scan_ref, ex)[2] == first_f.variant
+        f_call, f_kern, u_call, u_kern, p_call, p_kern, pf_call, pf_kern = [], [], [], [], [], [], [], []
         for _ in range(a.reps):
             if other:
                 c, k, nv = other.scan(mq, md, scan_ref)
                 p_call.append(c); p_kern.append(k)
                 assert nv == first.variant
+                if other.filtered:
+                    c, k, nv = other.scan(mq, md, scan_ref, ex)
+                    pf_call.append(c); pf_kern.append(k)
+                    assert nv == first_f.variant
             t0 = time.perf_counter()
             u = eng.site_scan(mq, md, scan_ref)
             u_call.append((time.perf_counter() - t0) * 1e3)
@@ -135,6 +161,12 @@ def main():
             out["kernel_ratio_filtered_over_parent"] = out["filtered_scan"]["kernel_ms"]["median"] / out["parent_unfiltered_scan"]["kernel_ms"]["median"]
             pk, uk = out["parent_unfiltered_scan"]["kernel_ms"], out["unfiltered_scan"]["kernel_ms"]
             out["unfiltered_ranges_overlap_parent"] = bool(uk["min"] <= pk["max"] and pk["min"] <= uk["max"])
+            if other.filtered:
+                out["parent_filtered_scan"] = {"call_ms": spread(pf_call), "kernel_ms": spread(pf_kern)}
+            # the gate of a change that must cost nothing: this build's median within the parent's own observed range
+            out["median_within_parent_max"] = {
+                f"{form}_{q}": bool(out[f"{form}_scan"][q]["median"] <= out[f"parent_{form}_scan"][q]["max"])
+                for form in ("unfiltered", "filtered") if f"parent_{form}_scan" in out for q in ("kernel_ms", "call_ms")}
             other.close()
     if a.bench_note:
         out.update(json.load(open(a.bench_note)))
