@@ -1,67 +1,17 @@
 // callable_loci.hip -- implementation of include/callable_loci.h for MI355X (gfx950).
 //
-// Host side of the engine: device buffers, uploads, kernel launches, event timing.  The work
-// itself is in kernels.hip.h.  No CPU fallback exists: without a HIP device cl_create fails.
+// Host side of the coverage engine: staging, uploads, kernel launches, event timing.  The work itself is in
+// kernels.hip.h; engine_base.hip.h holds the memory and transfer plumbing, site_engine.hip.h the site engine (both are
+// parts of this translation unit).  No CPU fallback exists: without a HIP device cl_create fails.
 #include "../../include/callable_loci.h"
 #include "kernels.hip.h"
 #include "depth_profile.hip.h"
-#include "site_scan.hip.h"
-#include "site_pass_bits.h"
-#include "host_parallel.h"
+#include "engine_base.hip.h"
+#include "site_engine.hip.h"
 #include "qual_pack.h"
 #include "pass_rows.h"
 
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <new>
-#include <string>
-#include <thread>
-#include <vector>
-
 using namespace clk;
-
-namespace {
-
-// rocTX ranges around the host-visible phases (rocprofv3 --marker-trace shows them); bound at run time so
-// that the library does not depend on the profiler's marker library being installed -- and only when that library
-// is in the process already (a profiler brought it) or DUT_ROCTX=1 asks for it: loading it cold took 35 ms of a
-// process's first contig
-struct Roctx {
-    int (*push)(const char *) = nullptr;
-    int (*pop)() = nullptr;
-    Roctx()
-    {
-        const char *want = getenv("DUT_ROCTX");
-        const int mode = RTLD_NOW | RTLD_LOCAL | ((want && *want == '1') ? 0 : RTLD_NOLOAD);
-        for (const char *lib : {"librocprofiler-sdk-roctx.so", "libroctx64.so"}) {
-            void *h = dlopen(lib, mode);
-            if (!h) continue;
-            push = (int (*)(const char *))dlsym(h, "roctxRangePushA");
-            pop = (int (*)())dlsym(h, "roctxRangePop");
-            if (push && pop) return;
-            push = nullptr; pop = nullptr;
-        }
-    }
-};
-struct Range {
-    static const Roctx &rt() { static const Roctx r; return r; }
-    explicit Range(const char *name) { if (rt().push) rt().push(name); }
-    ~Range() { if (rt().pop) rt().pop(); }
-};
-
 
 // window size (reference positions per workgroup).  2048 -> about 19 KB of LDS per workgroup of the short-read
 // variant, eight workgroups (32 waves) per CU.
@@ -69,198 +19,6 @@ struct Range {
 #define CL_WINDOW 2048
 #endif
 constexpr uint32_t kT = CL_WINDOW;
-
-// Host staging array of a trivially copyable type that grows without value-initialising what it adds (a contig's
-// per-read arrays are hundreds of megabytes: zero-filling them before they are overwritten showed) and appends in
-// parallel chunks.  Throws std::bad_alloc like a vector.
-template <typename T> struct RawVec {
-    T *p = nullptr;
-    size_t n = 0, cap = 0;
-    RawVec() = default;
-    RawVec(const RawVec &) = delete;
-    RawVec &operator=(const RawVec &) = delete;
-    RawVec(RawVec &&o) noexcept : p(o.p), n(o.n), cap(o.cap) { o.p = nullptr; o.n = o.cap = 0; }
-    ~RawVec() { free(p); }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    T *data() { return p; }
-    const T *data() const { return p; }
-    T &operator[](size_t i) { return p[i]; }
-    const T &operator[](size_t i) const { return p[i]; }
-    const T &back() const { return p[n - 1]; }
-    void clear() { n = 0; }
-    void release() { free(p); p = nullptr; n = cap = 0; }
-    void swap(RawVec &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); }
-    void reserve(size_t want)
-    {
-        if (want <= cap) return;
-        size_t nc = std::max(want, cap + cap / 2 + 16);
-        T *q = static_cast<T *>(realloc(p, nc * sizeof(T)));
-        if (!q) throw std::bad_alloc();
-        p = q; cap = nc;
-    }
-    void resize(size_t m) { reserve(m); n = m; }                 // new elements are NOT initialised
-    void push_back(const T &v) { reserve(n + 1); p[n++] = v; }
-    void append(const T *src, size_t m)                          // parallel copy
-    {
-        reserve(n + m);
-        T *dst = p + n;
-        const size_t grain = (4u << 20) / sizeof(T);
-        dut::parallel_for((m + grain - 1) / grain, 1, [&](size_t k) {
-            const size_t a = k * grain, b = std::min(m, a + grain);
-            memcpy(dst + a, src + a, (b - a) * sizeof(T));
-        });
-        n += m;
-    }
-};
-
-// DUT_TIMING=1: wall-clock of the engine's host stages on stderr (tooling; off by default)
-struct StageTimer {
-    bool on;
-    double t0;
-    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-    StageTimer() : on(getenv("DUT_TIMING") && *getenv("DUT_TIMING") == '1'), t0(on ? now() : 0.0) {}
-    void lap(const char *what)
-    {
-        if (!on) return;
-        const double t1 = now();
-        fprintf(stderr, "[dut-timing]     engine: %-24s %8.1f ms\n", what, (t1 - t0) * 1e3);
-        t0 = t1;
-    }
-};
-
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;     // elements
-    hipError_t reserve(size_t n)
-    {
-        if (n <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
-        return hipSuccess;
-    }
-    // like reserve, but the first `used` elements survive a reallocation
-    hipError_t grow_keep(size_t n, size_t used, hipStream_t stream)
-    {
-        if (n <= cap) return hipSuccess;
-        if (!p || used == 0) return reserve(n);
-        T *q = nullptr;
-        size_t want = n + n / 4 + 64;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&q), want * sizeof(T));
-        if (e != hipSuccess) return e;
-        e = hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { (void)hipFree(q); return e; }
-        (void)hipFree(p);
-        p = q; cap = want;
-        return hipSuccess;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-} // namespace
-
-// Pinned staging ring for host-to-device copies, one per device and process (its contexts share it; a transfer holds
-// it from start to finish): kCopyThreads host threads, each with its own stream and two pinned buffers; a thread fills
-// one buffer (memcpy from the caller's pageable memory, or records built in place) while the DMA of its other buffer
-// runs, so the link sees pinned memory only and the fills of all threads overlap all transfers.
-struct PinRing {
-    static constexpr int kCopyThreads = 16;                 // buffer pairs: plain copies use threads() of them, the walkers
-                                                            // that produce a stream into the buffers (rows, run table) all
-    static constexpr size_t kPinBytes = 4u << 20;
-    static int threads()                                    // DUT_COPY_THREADS (1..16), default 8
-    {
-        static const int n = [] {
-            const char *e = getenv("DUT_COPY_THREADS");
-            const int v = e ? atoi(e) : 8;
-            return v < 1 ? 1 : (v > kCopyThreads ? kCopyThreads : v);
-        }();
-        return n;
-    }
-    int device = 0;
-    hipStream_t copy_stream[kCopyThreads] = {};
-    uint8_t *pin[kCopyThreads][2] = {};
-    hipEvent_t pin_ev[kCopyThreads][2] = {};
-    // who is using the ring: a transfer holds it from ring_start to ring_finish -- across C-ABI calls for a quality
-    // prefetch, and possibly released on another thread than the one that took it, so an ownership flag under a
-    // condition variable rather than a mutex (unlocking a std::mutex from another thread is undefined)
-    std::mutex own_mu;
-    std::condition_variable own_cv;
-    const void *owner = nullptr;
-    void acquire(const void *who)
-    {
-        std::unique_lock<std::mutex> lk(own_mu);
-        // a context of this device with an unclaimed prefetch pins the ring until its next push / upload / begin /
-        // abort / destroy; a thread that drives two contexts must not interleave them there
-        int waited = 0;
-        while (owner && !own_cv.wait_for(lk, std::chrono::seconds(10), [this] { return owner == nullptr; }))
-            if (++waited == 1)
-                fprintf(stderr, "[callable_loci] waiting for the device's pinned staging ring: another context holds it "
-                                "(an unclaimed cl_contig_prefetch_qual keeps it until that context's next push, upload, begin, abort or destroy)\n");
-        owner = who;
-    }
-    void release(const void *who)
-    {
-        { std::lock_guard<std::mutex> g(own_mu); if (owner == who) owner = nullptr; }
-        own_cv.notify_one();
-    }
-    // The ring's own threads: started once (at cl_create), asleep between transfers.  (A thread created per transfer had to
-    // wait for the process's address-space lock whenever another thread was giving a few hundred megabytes back to the
-    // system -- 26 ms in front of a 3 ms transfer, measured: profiles/r04_first_pass_stages.txt.)
-    dut::Crew crew;
-    bool ok = false;
-    int slots = 0;                                          // thread slots that have their stream, buffers and events
-    // slots [slots, n) are made (by the ring's owner, or at construction); false when the runtime refuses
-    bool ensure_slots(int n)
-    {
-        if (n > kCopyThreads) n = kCopyThreads;
-        if (hipSetDevice(device) != hipSuccess) return false;
-        for (int t = slots; t < n; ++t) {
-            if (hipStreamCreateWithFlags(&copy_stream[t], hipStreamNonBlocking) != hipSuccess) return false;
-            for (int b = 0; b < 2; ++b) {
-                if (hipHostMalloc(reinterpret_cast<void **>(&pin[t][b]), kPinBytes, hipHostMallocDefault) != hipSuccess) return false;
-                // blocking waits: a copier that spins on its buffer's event burns a core the host stages beside it
-                // need (DUT_PIN_SPIN=1: the runtime's default busy wait, for comparison)
-                const char *spin = getenv("DUT_PIN_SPIN");
-                const unsigned flags = hipEventDisableTiming | ((spin && *spin == '1') ? 0u : (unsigned)hipEventBlockingSync);
-                if (hipEventCreateWithFlags(&pin_ev[t][b], flags) != hipSuccess) return false;
-            }
-            slots = t + 1;
-        }
-        return true;
-    }
-    explicit PinRing(int dev) : device(dev) { ok = ensure_slots(kCopyThreads); if (ok) crew.ensure(kCopyThreads); }
-    ~PinRing()
-    {
-        (void)hipSetDevice(device);
-        for (int t = 0; t < kCopyThreads; ++t) {
-            for (int b = 0; b < 2; ++b) {
-                if (pin_ev[t][b]) (void)hipEventDestroy(pin_ev[t][b]);
-                if (pin[t][b]) (void)hipHostFree(pin[t][b]);
-            }
-            if (copy_stream[t]) (void)hipStreamDestroy(copy_stream[t]);
-        }
-    }
-    PinRing(const PinRing &) = delete;
-    PinRing &operator=(const PinRing &) = delete;
-};
-
-static std::shared_ptr<PinRing> acquire_ring(int device)
-{
-    static std::mutex mu;
-    static std::map<int, std::weak_ptr<PinRing>> rings;
-    std::lock_guard<std::mutex> g(mu);
-    std::shared_ptr<PinRing> r = rings[device].lock();
-    if (!r) {
-        r = std::make_shared<PinRing>(device);
-        if (!r->ok) return nullptr;
-        rings[device] = r;
-    }
-    return r;
-}
 
 // The host staging arrays of a contig (hundreds of megabytes) are only needed between cl_contig_begin and
 // cl_contig_upload.  A context hands them to this process-wide pool when its contig is uploaded and takes a set back
@@ -278,60 +36,16 @@ constexpr size_t kStagingSets = 2;
 static std::mutex g_staging_mu;
 static std::vector<std::unique_ptr<StagingSet>> g_staging;
 
-// config 5: the resident tile of the site pileup (cl_site_upload) and the buffers of a run
-struct SiteResident {
-    DevBuf<SiteRec> rec; DevBuf<uint8_t> seq; DevBuf<uint32_t> cig, p0, ix, hist, bk; DevBuf<unsigned long long> base;
-    uint64_t n = 0, ncig = 0, nbase = 0, ref_len = 0;
-    uint32_t contig_len = 0;
-    bool resident = false;
-    bool filtered = false;           // the resident tile holds only the reads that overlap a site of the list it was uploaded for (cl_site_pileup)
-    // cl_site_scan: the per-read ends and per-window read ranges of the resident tile (built by the first scan), the
-    // reference bytes of the range, class counts + candidate count, candidates, dense counters (of either form)
-    DevBuf<uint32_t> sc_end, sc_wfirst, sc_wlast, sc_dense;
-    DevBuf<uint8_t> sc_ref;
-    DevBuf<unsigned long long> sc_cls;
-    DevBuf<ScanCand> sc_cand;
-    bool scan_indexed = false;
-    // cl_site_attach_quals: one pass bit per base of seq, one flag per read; the filtered scan's candidates, ambiguous
-    // positions and their 16-code histograms
-    DevBuf<unsigned long long> q_pass;
-    DevBuf<uint16_t> q_flag;
-    DevBuf<ScanCandEx> sx_cand;
-    DevBuf<uint32_t> sx_amb, sx_hist;
-    bool attached = false;
-    void release()
-    {
-        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release();
-        rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
-        sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
-        resident = false; scan_indexed = false;
-    }
-};
-
-struct cl_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's state in its one member `site`)
     uint64_t host_max_end = 0;         // largest pos + reference span over the pushed reads (32-bit clamped spans), for the extent
-    std::shared_ptr<PinRing> ring;                    // the device's pinned staging ring (shared by its contexts)
-    bool crew_busy = false;                           // a transfer in flight on the ring's threads (waited for by ring_finish)
     dut::Thread prealloc;                             // cl_contig_reserve: the device buffers of the contig being pushed, allocated beside the push
-    hipError_t copy_err[PinRing::kCopyThreads] = {};
-    bool ring_held = false;                           // this context holds the ring's lock (ring_start .. ring_finish)
-    double ring_t0 = 0;                               // DUT_TIMING: when the transfer in flight was started
-    // cl_contig_prefetch_qual: quality bytes on their way to d_qual + kQualPad + pf_off before their tile is pushed
-    const uint8_t *pf_src = nullptr;
-    uint64_t pf_n = 0, pf_off = 0;
-    bool pf_active = false;
     cl_options opt{};
     Opts dopt{};
-    std::string err;
 
     // host staging of the current contig
     bool in_contig = false, uploaded = false, ran = false;
     bool deep = false;               // this contig needs the 32-bit counter variant of k_pileup
     bool bits = true;                // the pass-bit form (default); DUT_QUAL_FORM=bytes at cl_create: the byte forms
-    bool host_only = false;          // cl_debug_host_create: staging and the row builder only, for the CPU test suite
     int form = 0;                    // the form of k_pileup the resident contig gets (pick_form, at upload)
     uint32_t tune_ablate = 0;        // CL_TUNING builds: CL_ABLATE, read once at cl_create
     bool has_long = false;           // some read has more than kLongOps CIGAR ops (its checkpoints are in h_ck_x / h_ck_y)
@@ -410,8 +124,7 @@ struct cl_ctx {
     // cl_contig_depth_profile: {sum_raw, sum_qc}, hist_raw, hist_qc, win_raw, win_qc -- on the device and as copied back
     DevBuf<unsigned long long> d_prof;
     std::vector<unsigned long long> h_prof;
-    hipEvent_t prof_ev[2] = {nullptr, nullptr};
-    double prof_ms = 0.0;            // the last profile's kernel by those events (while profiling is on)
+    KernelTimer t_prof;              // the last profile's kernel (recorded while profiling is on)
 
     uint32_t n_reads = 0;
     uint64_t n_cigar = 0, n_qual = 0;
@@ -428,19 +141,9 @@ struct cl_ctx {
     int ev_pending = 0;
     double ms[CL_K_COUNT] = {};
     uint64_t n_runs = 0;
-    // the last cl_site_pileup: duration of its kernel (HIP events on the stream) and its algorithmic bytes
-    hipEvent_t site_ev[2] = {nullptr, nullptr};
-    double site_ms = 0.0;
-    uint64_t site_bytes = 0;
-    SiteResident site;
-    // the last cl_site_scan / cl_site_scan_counts: its kernel by events, its algorithmic bytes, its candidates
-    hipEvent_t scan_ev[2] = {nullptr, nullptr};
-    double scan_ms = 0.0;
-    uint64_t scan_bytes = 0;
-    std::vector<cl_scan_candidate> scan_cand;
-    std::vector<cl_scan_candidate_ex> scan_cand_ex;
 };
 
+static SiteCtx *site_ctx(cl_ctx *c) { return c; }
 static void join_prealloc(cl_ctx *c) { if (c->prealloc.joinable()) c->prealloc.join(); }   // (cl_contig_reserve's helper thread)
 
 static void swap_staging(cl_ctx *c, StagingSet &o)
@@ -478,20 +181,6 @@ static void give_staging(cl_ctx *c)
 
 namespace {
 
-cl_status fail(cl_ctx *c, cl_status s, const std::string &m)
-{
-    if (c) c->err = m;
-    return s;
-}
-
-#define HIP_TRY(ctx, call)                                                                   \
-    do {                                                                                     \
-        hipError_t e__ = (call);                                                             \
-        if (e__ != hipSuccess)                                                               \
-            return fail(ctx, e__ == hipErrorOutOfMemory ? CL_ERR_NOMEM : CL_ERR_DEVICE,      \
-                        std::string(#call) + ": " + hipGetErrorString(e__));                 \
-    } while (0)
-
 // constants of the byte-parallel threshold test (kernels.hip.h swar_ge7)
 void make_ge_consts(uint8_t T, uint32_t &ge_add, uint32_t &ge_or, uint32_t &ge_and)
 {
@@ -517,90 +206,6 @@ void build_lut(double frac, std::vector<uint32_t> &lut)
         while (low <= raw && !(((double)low / (double)raw) > frac)) ++low;
         if (low <= raw) lut[raw] = low;
     }
-}
-
-cl_status ensure_pins(cl_ctx *c)
-{
-    if (c->ring) return CL_OK;
-    c->ring = acquire_ring(c->device);
-    if (!c->ring) return fail(c, CL_ERR_DEVICE, "cannot create the pinned staging ring (hipHostMalloc)");
-    return CL_OK;
-}
-
-// n bytes to `dst` through the ring: fill(off, len, out) writes the bytes [off, off + len) of the transfer into the
-// pinned buffer `out`.  Chunks are dealt round-robin to the copier threads.  Returns at once; ring_finish joins.
-template <class Fill>
-cl_status ring_start(cl_ctx *c, uint8_t *dst, uint64_t n, Fill fill, uint64_t chunk_bytes = PinRing::kPinBytes, int want_threads = 0)
-{
-    cl_status s = ensure_pins(c);
-    if (s != CL_OK) return s;
-    PinRing *R = c->ring.get();
-    c->ring_t0 = StageTimer::now();
-    R->acquire(c);                                        // another context of this device may be using the ring
-    c->ring_held = true;
-    const uint64_t CH = chunk_bytes, nch = (n + CH - 1) / CH;
-    // (plain copies saturate the link with DUT_COPY_THREADS buffers in flight; a fill that gathers small pieces is bound by
-    // the fill and asks for all of the ring's pairs)
-    const int T = want_threads > 0 ? std::min(want_threads, std::max(1, R->slots)) : PinRing::threads();
-    const int nt = (int)std::min<uint64_t>((uint64_t)T, nch);
-    for (int t = 0; t < PinRing::kCopyThreads; ++t) c->copy_err[t] = hipSuccess;
-    c->crew_busy = true;
-    R->crew.start(nt, [c, R, dst, n, fill, nch, CH, T](int t) {
-            const bool timing = StageTimer().on;
-            double t_fill = 0, t_issue = 0, t_wait = 0, t0 = timing ? StageTimer::now() : 0.0, ta;
-            hipError_t e = hipSetDevice(c->device);
-            int k = 0;
-            for (uint64_t ch = (uint64_t)t; ch < nch && e == hipSuccess; ch += (uint64_t)T, ++k) {
-                const int b = k & 1;
-                const uint64_t off = ch * CH, len = std::min<uint64_t>(CH, n - off);
-                if (timing) ta = StageTimer::now();
-                if (k >= 2) e = hipEventSynchronize(R->pin_ev[t][b]);           // the buffer's previous transfer is done
-                if (e != hipSuccess) break;
-                if (timing) { const double tb = StageTimer::now(); t_wait += tb - ta; ta = tb; }
-                fill(off, len, R->pin[t][b]);
-                if (timing) { const double tb = StageTimer::now(); t_fill += tb - ta; ta = tb; }
-                e = hipMemcpyAsync(dst + off, R->pin[t][b], len, hipMemcpyHostToDevice, R->copy_stream[t]);
-                if (e == hipSuccess) e = hipEventRecord(R->pin_ev[t][b], R->copy_stream[t]);
-                if (timing) t_issue += StageTimer::now() - ta;
-            }
-            // the thread's last transfers (one per buffer it used), waited for on their events
-            if (timing) ta = StageTimer::now();
-            hipError_t e2 = hipSuccess;
-            for (int b = 0; b < 2 && b < k; ++b) { const hipError_t w = hipEventSynchronize(R->pin_ev[t][b]); if (e2 == hipSuccess) e2 = w; }
-            c->copy_err[t] = e != hipSuccess ? e : e2;
-            if (timing) {
-                const double t1 = StageTimer::now();
-                fprintf(stderr, "[dut-timing]       ring thread %d: %d buffers, started %.1f ms after the call, fill %.1f, issue %.1f, wait %.1f + %.1f ms\n", t, k,
-                        (t0 - c->ring_t0) * 1e3, t_fill * 1e3, t_issue * 1e3, t_wait * 1e3, (t1 - ta) * 1e3);
-            }
-    });
-    return CL_OK;
-}
-
-cl_status ring_finish(cl_ctx *c)
-{
-    if (c->crew_busy) { c->ring->crew.wait(); c->crew_busy = false; }   // the ring's threads are done with this transfer
-    if (c->ring_held) { c->ring_held = false; c->ring->release(c); }
-    for (int t = 0; t < PinRing::kCopyThreads; ++t) HIP_TRY(c, c->copy_err[t]);
-    return CL_OK;
-}
-
-// plain bytes through the ring, start to finish
-cl_status ring_copy(cl_ctx *c, void *dst, const void *src, uint64_t n)
-{
-    if (n == 0) return CL_OK;
-    const uint8_t *s8 = static_cast<const uint8_t *>(src);
-    cl_status s = ring_start(c, static_cast<uint8_t *>(dst), n, [s8](uint64_t off, uint64_t len, uint8_t *out) { memcpy(out, s8 + off, len); });
-    if (s != CL_OK) return s;
-    return ring_finish(c);
-}
-
-// a prefetch that was started and never claimed by a tile: wait for it, its bytes are simply overwritten later
-void drop_prefetch(cl_ctx *c)
-{
-    if (!c->pf_active) return;
-    (void)ring_finish(c);
-    c->pf_active = false; c->pf_src = nullptr; c->pf_n = 0;
 }
 
 cl_status ensure_events(cl_ctx *c)
@@ -843,7 +448,6 @@ void finish_windows(const cl_ctx *c, const std::vector<uint32_t> &wro_v, std::ve
     flags |= fl.load();
 }
 
-
 // The run table of the run-table form (kernels.hip.h, LONG = 2): per window of kT positions the M/=/X pieces of the reads
 // that cover it -- what the reference's column walk visits as (alignment, qpos) with !is_del (mod.rs:30-37), grouped by
 // window instead of by column.  One more walk over the staged CIGARs, at upload: a thread takes a range of windows
@@ -954,7 +558,7 @@ cl_status stream_run_table(cl_ctx *c, std::vector<WinMeta> &win)
         std::atomic<uint64_t> dev_next{0};
         std::atomic<size_t> next_task{0};
         PinRing *R = c->ring.get();
-        R->acquire(c);
+        R->acquire(static_cast<EngineBase *>(c));                // (the identity ring_finish releases it under)
         c->ring_held = true;
         if (!R->ensure_slots(nt)) { (void)ring_finish(c); return fail(c, CL_ERR_DEVICE, "cannot extend the pinned staging ring (hipHostMalloc)"); }
         for (int t = 0; t < PinRing::kCopyThreads; ++t) c->copy_err[t] = hipSuccess;
@@ -1003,7 +607,7 @@ cl_status stream_run_table(cl_ctx *c, std::vector<WinMeta> &win)
                     }
                     act.push_back(cu);
                 };
-                try {
+                walker_guarded(err, [&] {
                     size_t task;
                     while ((task = next_task.fetch_add(1)) < ntasks) {
                         const size_t w0 = task * per, w1 = std::min<size_t>(n_win, w0 + per);
@@ -1047,7 +651,7 @@ cl_status stream_run_table(cl_ctx *c, std::vector<WinMeta> &win)
                         }
                     }
                     flush();
-                } catch (...) { if (err == hipSuccess) err = hipErrorOutOfMemory; }
+                });
                 for (int b = 0; b < 2 && b < kb; ++b) { const hipError_t e = hipEventSynchronize(R->pin_ev[t][b]); if (err == hipSuccess) err = e; }
                 c->copy_err[t] = err;
         });
@@ -1119,7 +723,7 @@ cl_status stream_rows(cl_ctx *c, std::vector<WinMeta> &win)
         std::atomic<size_t> next_task{0};
         std::atomic<uint32_t> max_groups{0};
         PinRing *R = c->ring.get();
-        R->acquire(c);
+        R->acquire(static_cast<EngineBase *>(c));                // (the identity ring_finish releases it under)
         c->ring_held = true;
         if (!R->ensure_slots(nt)) { (void)ring_finish(c); return fail(c, CL_ERR_DEVICE, "cannot extend the pinned staging ring (hipHostMalloc)"); }
         for (int t = 0; t < PinRing::kCopyThreads; ++t) c->copy_err[t] = hipSuccess;
@@ -1148,7 +752,7 @@ cl_status stream_rows(cl_ctx *c, std::vector<WinMeta> &win)
                     for (uint32_t w : in_buf) win[w].rlo += (uint32_t)off;
                     in_buf.clear(); used = 0;
                 };
-                try {
+                walker_guarded(err, [&] {
                     size_t task;
                     while ((task = next_task.fetch_add(1)) < ntasks) {
                         const size_t w0 = task * per, w1 = std::min<size_t>(n_win, w0 + per);
@@ -1195,7 +799,7 @@ cl_status stream_rows(cl_ctx *c, std::vector<WinMeta> &win)
                         }
                     }
                     flush();
-                } catch (...) { if (err == hipSuccess) err = hipErrorOutOfMemory; }
+                });
                 for (int b = 0; b < 2 && b < kb; ++b) { const hipError_t e = hipEventSynchronize(R->pin_ev[t][b]); if (err == hipSuccess) err = e; }
                 uint32_t seen = max_groups.load();
                 while (seen < my_max && !max_groups.compare_exchange_weak(seen, my_max)) {}
@@ -1343,9 +947,7 @@ template <bool DEBUG> void launch_pileup(cl_ctx *c, const PileupArgs &a)
 {
     const uint32_t grid = a.n_win8 * 8u;
     if (grid == 0) return;
-    // (the ORF template parameter once selected a shorter threshold test for min_base_quality <= 128; one form
-    // serves every threshold now and only ORF = true is instantiated)
-#define CL_LAUNCH(DEEP_, LONG_) hipLaunchKernelGGL((k_pileup<(int)kT, DEBUG, true, DEEP_, LONG_>), dim3(grid), dim3(kBlock), 0, c->stream, a)
+#define CL_LAUNCH(DEEP_, LONG_) hipLaunchKernelGGL((k_pileup<(int)kT, DEBUG, DEEP_, LONG_>), dim3(grid), dim3(kBlock), 0, c->stream, a)
 #define CL_LAUNCH_L(DEEP_) do { if (c->form == 2) CL_LAUNCH(DEEP_, 2); else CL_LAUNCH(DEEP_, 0); } while (0)
 #define CL_LAUNCH_R(DEEP_, NP_) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, CL_ROWS_BLOCK>), dim3(grid), dim3(CL_ROWS_BLOCK), 0, c->stream, a)
 #define CL_LAUNCH_RN(DEEP_) do { if (c->max_groups <= 63u) CL_LAUNCH_R(DEEP_, 8); else if (c->max_groups <= 16383u) CL_LAUNCH_R(DEEP_, 16); else CL_LAUNCH_R(DEEP_, 32); } while (0)
@@ -1481,9 +1083,7 @@ void cl_destroy(cl_ctx *c)
     c->d_runs.release(); c->d_first_state.release(); c->d_last_state.release(); c->d_win_wide.release();
     c->d_winpart.release(); c->d_lut.release(); c->d_summary.release();
     c->d_iv.release(); c->d_dbg.release(); c->d_prof.release(); c->d_fin.release(); c->d_errflag.release(); c->d_runtab.release(); c->site.release();
-    for (int i = 0; i < 2; ++i) if (c->site_ev[i]) (void)hipEventDestroy(c->site_ev[i]);
-    for (int i = 0; i < 2; ++i) if (c->scan_ev[i]) (void)hipEventDestroy(c->scan_ev[i]);
-    for (int i = 0; i < 2; ++i) if (c->prof_ev[i]) (void)hipEventDestroy(c->prof_ev[i]);
+    c->t_prof.destroy();
     if (c->ev_made)
         for (int s = 0; s < cl_ctx::kEvSets; ++s)
             for (int i = 0; i <= CL_K_COUNT; ++i) (void)hipEventDestroy(c->ev[s][i]);
@@ -1497,39 +1097,31 @@ void cl_destroy(cl_ctx *c)
 
 const char *cl_last_error(const cl_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-static cl_status cl_contig_begin_impl(cl_ctx *c, int32_t tid, uint32_t contig_len, const uint8_t *ref_bases,
-                          uint64_t ref_len)
-{
-    if (!c) return CL_ERR_INVALID;
-    if (contig_len > 0xFFF00000u) return fail(c, CL_ERR_RANGE, "contig length beyond the engine's 32-bit range");
-    if (ref_len && !ref_bases) return fail(c, CL_ERR_INVALID, "ref_bases is null");
-    if (!c->host_only) { drop_prefetch(c); join_prealloc(c); }
-    take_staging(c);
-    c->tid = tid; c->contig_len = contig_len;
-    const uint64_t nref = std::min<uint64_t>(ref_len, contig_len);
-    c->h_ref.clear(); c->h_ref.append(ref_bases, nref);
-    c->h_pos.clear(); c->h_mapq.clear(); c->h_cigar.clear(); c->h_qual.clear();
-    c->h_cigar_off.clear(); c->h_cigar_off.push_back(0u); c->h_qual_off.clear(); c->h_qual_off.push_back(0ull);
-    c->h_iv.clear();
-    c->q_dev = 0;
-    c->h_wide_idx.clear(); c->h_wide_pos.clear(); c->span_n = 0; c->span_w = 0; c->n_wide = 0; c->host_max_end = 0;
-    c->h_end.clear(); c->h_ck_x.clear(); c->h_ck_y.clear(); c->n_long = 0; c->host_err = 0; c->bounds_err = 0;
-    c->h_rec_cnt.clear(); c->rec_counted = true;
-    c->h_qbits.clear(); c->h_rb_off.clear(); c->h_sc_off.clear(); c->h_sc.clear(); c->host_sum_q = 0; c->host_n_ops = 0;
-    c->host_sum_cov = 0; c->host_sum_mapq = 0;
-    c->in_contig = true; c->uploaded = false; c->ran = false; c->has_long = false;
-    return CL_OK;
-}
-
 cl_status cl_contig_begin(cl_ctx *c, int32_t tid, uint32_t contig_len, const uint8_t *ref_bases,
                           uint64_t ref_len)
 {
-    // no exception leaves the library through the C ABI
-    try { return cl_contig_begin_impl(c, tid, contig_len, ref_bases, ref_len); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+    return guarded(c, [&]() -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (contig_len > 0xFFF00000u) return fail(c, CL_ERR_RANGE, "contig length beyond the engine's 32-bit range");
+        if (ref_len && !ref_bases) return fail(c, CL_ERR_INVALID, "ref_bases is null");
+        if (!c->host_only) { drop_prefetch(c); join_prealloc(c); }
+        take_staging(c);
+        c->tid = tid; c->contig_len = contig_len;
+        const uint64_t nref = std::min<uint64_t>(ref_len, contig_len);
+        c->h_ref.clear(); c->h_ref.append(ref_bases, nref);
+        c->h_pos.clear(); c->h_mapq.clear(); c->h_cigar.clear(); c->h_qual.clear();
+        c->h_cigar_off.clear(); c->h_cigar_off.push_back(0u); c->h_qual_off.clear(); c->h_qual_off.push_back(0ull);
+        c->h_iv.clear();
+        c->q_dev = 0;
+        c->h_wide_idx.clear(); c->h_wide_pos.clear(); c->span_n = 0; c->span_w = 0; c->n_wide = 0; c->host_max_end = 0;
+        c->h_end.clear(); c->h_ck_x.clear(); c->h_ck_y.clear(); c->n_long = 0; c->host_err = 0; c->bounds_err = 0;
+        c->h_rec_cnt.clear(); c->rec_counted = true;
+        c->h_qbits.clear(); c->h_rb_off.clear(); c->h_sc_off.clear(); c->h_sc.clear(); c->host_sum_q = 0; c->host_n_ops = 0;
+        c->host_sum_cov = 0; c->host_sum_mapq = 0;
+        c->in_contig = true; c->uploaded = false; c->ran = false; c->has_long = false;
+        return CL_OK;
+    });
 }
-
 
 namespace {
 // quality bytes staged on the host so far go to the device, behind the ones already there
@@ -1552,7 +1144,7 @@ cl_status cl_contig_prefetch_qual(cl_ctx *c, const uint8_t *qual, uint64_t n_byt
     if (!c || !c->in_contig || c->uploaded) return fail(c, CL_ERR_INVALID, "cl_contig_prefetch_qual outside cl_contig_begin .. upload");
     if (c->bits) return CL_OK;                                  // pass-bit form: no quality byte goes to the device
     if (!qual || n_bytes < kDirectQual) return CL_OK;            // small tiles are staged on the host anyway
-    try {
+    return guarded(c, [&] {
         drop_prefetch(c);
         cl_status fs = flush_staged_qual(c);
         if (fs != CL_OK) return fs;
@@ -1564,9 +1156,7 @@ cl_status cl_contig_prefetch_qual(cl_ctx *c, const uint8_t *qual, uint64_t n_byt
         if (rs != CL_OK) { (void)ring_finish(c); return rs; }
         c->pf_src = qual; c->pf_n = n_bytes; c->pf_off = c->q_dev; c->pf_active = true;
         return CL_OK;
-    }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+    });
 }
 
 // Pass-bit form: what cl_contig_upload will need on the device is known from the contig's length and the caller's hint --
@@ -1619,6 +1209,33 @@ cl_status cl_contig_reserve(cl_ctx *c, uint64_t n_reads, uint64_t n_cigar_ops, u
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, c->d_qual.grow_keep(n_qual_bytes + 2 * kQualPad, c->q_dev ? kQualPad + c->q_dev : 0, c->stream));
     return CL_OK;
+}
+
+// What cl_push_reads and cl_push_reads_bits check of a tile before they look at a read, over the arrays both tile structs
+// have; `who` names the caller in the one message that does.  An empty tile is h.n == 0 with CL_OK.
+struct TileHead { uint64_t n = 0, q0 = 0, ncig = 0, nq = 0; uint32_t cig0 = 0; };
+static cl_status tile_header(cl_ctx *c, const char *who, uint64_t n, const int32_t *pos, const uint8_t *mapq, const uint32_t *cigar_off,
+                             const uint32_t *cigar, const uint64_t *qual_off, TileHead &h)
+{
+    if (!c->in_contig || c->uploaded) return fail(c, CL_ERR_INVALID, std::string(who) + " outside cl_contig_begin .. upload");
+    if (n == 0) return CL_OK;
+    if (!pos || !mapq || !cigar_off || !qual_off) return fail(c, CL_ERR_INVALID, "null tile array");
+    if (c->h_pos.size() + n >= (1ull << 29)) return fail(c, CL_ERR_RANGE, "more than 2^29 reads in one contig");
+    h.cig0 = cigar_off[0]; h.q0 = qual_off[0];
+    if (cigar_off[n] < h.cig0 || qual_off[n] < h.q0) return fail(c, CL_ERR_INVALID, "offset arrays must be non-decreasing");
+    h.ncig = (uint64_t)cigar_off[n] - h.cig0; h.nq = qual_off[n] - h.q0;
+    if (h.ncig && !cigar) return fail(c, CL_ERR_INVALID, "null cigar array");
+    h.n = n;
+    return CL_OK;
+}
+
+// the first offence a tile's walk over its reads met (a chunk's `bad`, 1 .. 3), as the status and message of the refusal
+struct Offence { cl_status st; const char *msg; };
+static Offence walk_offence(int bad)
+{
+    if (bad == 1) return {CL_ERR_INVALID, "read position outside [0, contig_len): the region fetch (mod.rs:53) never yields it"};
+    if (bad == 2) return {CL_ERR_UNSORTED, "reads are not coordinate sorted"};
+    return {CL_ERR_INVALID, "offset arrays must be non-decreasing"};
 }
 
 // cl_push_reads of the pass-bit form: nothing goes to the device here.  One walk over the tile, in chunks on all host
@@ -1738,11 +1355,8 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
     const unsigned long long closing_rb = c->h_qbits.size();
     const uint32_t closing_sc = (uint32_t)c->h_sc.size();
     auto refuse = [&](cl_status st, const char *m) { rb_off[0] = closing_rb; sc_off[0] = closing_sc; return fail(c, st, m); };
-    for (const Chunk &o : ch) {                                // the first offence in tile order decides the message
-        if (o.bad == 1) return refuse(CL_ERR_INVALID, "read position outside [0, contig_len): the region fetch (mod.rs:53) never yields it");
-        if (o.bad == 2) return refuse(CL_ERR_UNSORTED, "reads are not coordinate sorted");
-        if (o.bad == 3) return refuse(CL_ERR_INVALID, "offset arrays must be non-decreasing");
-    }
+    for (const Chunk &o : ch)                                  // the first offence in tile order decides the message
+        if (o.bad) { const Offence f = walk_offence(o.bad); return refuse(f.st, f.msg); }
     // ---- where every chunk's strings go: behind the contig's ----
     std::vector<uint64_t> rb_base(nchunk + 1), sc_base(nchunk + 1);
     rb_base[0] = c->h_qbits.size(); sc_base[0] = c->h_sc.size();
@@ -1856,17 +1470,11 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
 static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
 {
     if (!c || !t) return CL_ERR_INVALID;
-    if (!c->in_contig || c->uploaded) return fail(c, CL_ERR_INVALID, "cl_push_reads outside cl_contig_begin .. upload");
-    const uint64_t n = t->n_reads;
-    if (n == 0) return CL_OK;
-    if (!t->pos || !t->mapq || !t->cigar_off || !t->qual_off) return fail(c, CL_ERR_INVALID, "null tile array");
-    if (c->h_pos.size() + n >= (1ull << 29)) return fail(c, CL_ERR_RANGE, "more than 2^29 reads in one contig");
-    const uint32_t cig0 = t->cigar_off[0];
-    const uint64_t q0 = t->qual_off[0];
-    if (t->cigar_off[n] < cig0 || t->qual_off[n] < q0) return fail(c, CL_ERR_INVALID, "offset arrays must be non-decreasing");
-    const uint64_t ncig = (uint64_t)t->cigar_off[n] - cig0;
-    const uint64_t nq = t->qual_off[n] - q0;
-    if (ncig && !t->cigar) return fail(c, CL_ERR_INVALID, "null cigar array");
+    TileHead h;
+    const cl_status hs = tile_header(c, "cl_push_reads", t->n_reads, t->pos, t->mapq, t->cigar_off, t->cigar, t->qual_off, h);
+    if (hs != CL_OK || h.n == 0) return hs;
+    const uint64_t n = h.n, q0 = h.q0, ncig = h.ncig, nq = h.nq;
+    const uint32_t cig0 = h.cig0;
     if (nq && !t->qual) return fail(c, CL_ERR_INVALID, "null qual array");
     if (c->h_cigar.size() + ncig > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "more than 2^32 CIGAR operations in one contig");
     if (c->q_dev + c->h_qual.size() + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality bytes in one contig");
@@ -1995,11 +1603,8 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
         }
     });
     tmr.lap("push: validate + spans");
-    for (const Chunk &o : ch) {                                // the first offence in tile order decides the message
-        if (o.bad == 1) return fail(c, CL_ERR_INVALID, "read position outside [0, contig_len): the region fetch (mod.rs:53) never yields it");
-        if (o.bad == 2) return fail(c, CL_ERR_UNSORTED, "reads are not coordinate sorted");
-        if (o.bad == 3) return fail(c, CL_ERR_INVALID, "offset arrays must be non-decreasing");
-    }
+    for (const Chunk &o : ch)                                  // the first offence in tile order decides the message
+        if (o.bad) { const Offence f = walk_offence(o.bad); return fail(c, f.st, f.msg); }
 
     // ---- staging of the small arrays (offsets rebased onto the contig's); undone if anything below fails, so that
     //      a refused tile leaves the context as it was ----
@@ -2057,42 +1662,29 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
 
 cl_status cl_push_reads(cl_ctx *c, const cl_read_tile *t)
 {
-    // no exception leaves the library through the C ABI
-    try { return cl_push_reads_impl(c, t); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-static cl_status cl_push_reads_bits_impl(cl_ctx *c, const cl_read_tile_bits *b)
-{
-    if (!c || !b) return CL_ERR_INVALID;
-    if (!c->in_contig || c->uploaded) return fail(c, CL_ERR_INVALID, "cl_push_reads_bits outside cl_contig_begin .. upload");
-    if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_push_reads_bits: this context runs the byte forms (DUT_QUAL_FORM=bytes), which need the quality bytes: use cl_push_reads");
-    const uint64_t n = b->n_reads;
-    if (n == 0) return CL_OK;
-    if (!b->pos || !b->mapq || !b->cigar_off || !b->qual_off) return fail(c, CL_ERR_INVALID, "null tile array");
-    if (c->h_pos.size() + n >= (1ull << 29)) return fail(c, CL_ERR_RANGE, "more than 2^29 reads in one contig");
-    const uint32_t cig0 = b->cigar_off[0];
-    const uint64_t q0 = b->qual_off[0];
-    if (b->cigar_off[n] < cig0 || b->qual_off[n] < q0) return fail(c, CL_ERR_INVALID, "offset arrays must be non-decreasing");
-    const uint64_t ncig = (uint64_t)b->cigar_off[n] - cig0, nq = b->qual_off[n] - q0;
-    if (ncig && !b->cigar) return fail(c, CL_ERR_INVALID, "null cigar array");
-    if (nq && (!b->pass_bits || !b->pass_sum)) return fail(c, CL_ERR_INVALID, "null pass_bits / pass_sum array");
-    if (c->q_dev + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality values in one contig");
-    cl_read_tile t;
-    t.n_reads = n; t.pos = b->pos; t.mapq = b->mapq; t.cigar_off = b->cigar_off; t.cigar = b->cigar; t.qual_off = b->qual_off; t.qual = nullptr;
-    static const uint64_t kNoBits[2] = {0, 0};
-    static const uint32_t kNoSum[1] = {0};
-    return push_reads_bits(c, &t, cig0, q0, ncig, nq, b->pass_bits ? b->pass_bits : kNoBits, b->pass_sum ? b->pass_sum : kNoSum);
+    return guarded(c, [&] { return cl_push_reads_impl(c, t); });
 }
 
 cl_status cl_push_reads_bits(cl_ctx *c, const cl_read_tile_bits *b)
 {
-    try { return cl_push_reads_bits_impl(c, b); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+    return guarded(c, [&]() -> cl_status {
+        if (!c || !b) return CL_ERR_INVALID;
+        // (inside a contig the wrong form is the first refusal; outside one, tile_header's)
+        if (c->in_contig && !c->uploaded && !c->bits) return fail(c, CL_ERR_INVALID, "cl_push_reads_bits: this context runs the byte forms (DUT_QUAL_FORM=bytes), which need the quality bytes: use cl_push_reads");
+        TileHead h;
+        const cl_status hs = tile_header(c, "cl_push_reads_bits", b->n_reads, b->pos, b->mapq, b->cigar_off, b->cigar, b->qual_off, h);
+        if (hs != CL_OK || h.n == 0) return hs;
+        const uint64_t n = h.n, q0 = h.q0, ncig = h.ncig, nq = h.nq;
+        const uint32_t cig0 = h.cig0;
+        if (nq && (!b->pass_bits || !b->pass_sum)) return fail(c, CL_ERR_INVALID, "null pass_bits / pass_sum array");
+        if (c->q_dev + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality values in one contig");
+        cl_read_tile t;
+        t.n_reads = n; t.pos = b->pos; t.mapq = b->mapq; t.cigar_off = b->cigar_off; t.cigar = b->cigar; t.qual_off = b->qual_off; t.qual = nullptr;
+        static const uint64_t kNoBits[2] = {0, 0};
+        static const uint32_t kNoSum[1] = {0};
+        return push_reads_bits(c, &t, cig0, q0, ncig, nq, b->pass_bits ? b->pass_bits : kNoBits, b->pass_sum ? b->pass_sum : kNoSum);
+    });
 }
-
 
 static cl_status cl_contig_upload_impl(cl_ctx *c)
 {
@@ -2256,12 +1848,8 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
 
 cl_status cl_contig_upload(cl_ctx *c)
 {
-    // no exception leaves the library through the C ABI
-    try { return cl_contig_upload_impl(c); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+    return guarded(c, [&] { return cl_contig_upload_impl(c); });
 }
-
 
 cl_status cl_debug_read_records(int32_t pos, const uint32_t *cigar, uint32_t n_ops, uint8_t mapq, uint8_t min_mapping_quality,
                                 uint64_t qual_off, uint64_t qual_len, uint32_t *out, uint32_t cap,
@@ -2318,61 +1906,55 @@ cl_status cl_debug_host_create(const cl_options *opt, cl_ctx **out)
     return CL_OK;
 }
 
-static cl_status cl_debug_pass_rows_impl(cl_ctx *c, uint32_t *n_groups, uint32_t n_win_cap, uint32_t *rows, uint64_t cap_words,
-                                         uint64_t *n_words, uint32_t *n_windows, uint64_t *summed_baseq)
-{
-    if (!c || !c->in_contig || !c->bits) return fail(c, CL_ERR_INVALID, "cl_debug_pass_rows: no staged contig in the pass-bit form");
-    const uint32_t extent = (uint32_t)std::max<uint64_t>(c->contig_len, c->host_max_end);
-    const uint32_t n_win = (uint32_t)(((uint64_t)extent + kT - 1) / kT);
-    c->n_win = n_win;
-    if (n_windows) *n_windows = n_win;
-    if (summed_baseq) *summed_baseq = c->host_sum_q;
-    std::vector<WinMeta> win;
-    uint32_t flags = 0;
-    host_window_bounds(c, win, flags);
-    const dut::RowReads H = row_reads(c);
-    std::vector<dut::RowCur> act, save;
-    dut::RowScratch sc;
-    std::vector<uint32_t> buf;
-    uint64_t used = 0;
-    for (uint32_t w = 0; w < n_win; ++w) {
-        const uint32_t W = w * kT;
-        const WinMeta &m = win[w];
-        // (every third window entered afresh, as the first window of a thread's range is -- through the checkpoints of the
-        // long reads --, the others carried over from the window before, as inside a range)
-        act.clear();
-        if (w % 3u == 0u) {
-            for (uint32_t i = 0; i < m.wn; ++i) dut::rows_enter(act, H, c->h_wide_idx[m.wlo + i], W);
-            for (uint32_t r = m.lo; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
-        } else {
-            act = save;
-            for (uint32_t r = win[w - 1].hi; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
-        }
-        size_t cap = 16, cnt;
-        std::vector<dut::RowCur> start = act;
-        for (;;) {
-            buf.assign(cap * dut::kRowGroupWords, 0xDEADBEEFu);         // groups must be zeroed by the builder itself
-            act = start;
-            cnt = dut::rows_window<kT>(act, H, W, buf.data(), cap, sc);
-            if (cnt != SIZE_MAX) break;
-            cap *= 4;
-        }
-        save = act;
-        if (w < n_win_cap && n_groups) n_groups[w] = (uint32_t)cnt;
-        const uint64_t nw = (uint64_t)cnt * dut::kRowGroupWords;
-        if (rows && used + nw <= cap_words) memcpy(rows + used, buf.data(), nw * sizeof(uint32_t));
-        used += nw;
-    }
-    if (n_words) *n_words = used;
-    return CL_OK;
-}
-
 cl_status cl_debug_pass_rows(cl_ctx *c, uint32_t *n_groups, uint32_t n_win_cap, uint32_t *rows, uint64_t cap_words,
                              uint64_t *n_words, uint32_t *n_windows, uint64_t *summed_baseq)
 {
-    try { return cl_debug_pass_rows_impl(c, n_groups, n_win_cap, rows, cap_words, n_words, n_windows, summed_baseq); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+    return guarded(c, [&]() -> cl_status {
+        if (!c || !c->in_contig || !c->bits) return fail(c, CL_ERR_INVALID, "cl_debug_pass_rows: no staged contig in the pass-bit form");
+        const uint32_t extent = (uint32_t)std::max<uint64_t>(c->contig_len, c->host_max_end);
+        const uint32_t n_win = (uint32_t)(((uint64_t)extent + kT - 1) / kT);
+        c->n_win = n_win;
+        if (n_windows) *n_windows = n_win;
+        if (summed_baseq) *summed_baseq = c->host_sum_q;
+        std::vector<WinMeta> win;
+        uint32_t flags = 0;
+        host_window_bounds(c, win, flags);
+        const dut::RowReads H = row_reads(c);
+        std::vector<dut::RowCur> act, save;
+        dut::RowScratch sc;
+        std::vector<uint32_t> buf;
+        uint64_t used = 0;
+        for (uint32_t w = 0; w < n_win; ++w) {
+            const uint32_t W = w * kT;
+            const WinMeta &m = win[w];
+            // (every third window entered afresh, as the first window of a thread's range is -- through the checkpoints of the
+            // long reads --, the others carried over from the window before, as inside a range)
+            act.clear();
+            if (w % 3u == 0u) {
+                for (uint32_t i = 0; i < m.wn; ++i) dut::rows_enter(act, H, c->h_wide_idx[m.wlo + i], W);
+                for (uint32_t r = m.lo; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
+            } else {
+                act = save;
+                for (uint32_t r = win[w - 1].hi; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
+            }
+            size_t cap = 16, cnt;
+            std::vector<dut::RowCur> start = act;
+            for (;;) {
+                buf.assign(cap * dut::kRowGroupWords, 0xDEADBEEFu);         // groups must be zeroed by the builder itself
+                act = start;
+                cnt = dut::rows_window<kT>(act, H, W, buf.data(), cap, sc);
+                if (cnt != SIZE_MAX) break;
+                cap *= 4;
+            }
+            save = act;
+            if (w < n_win_cap && n_groups) n_groups[w] = (uint32_t)cnt;
+            const uint64_t nw = (uint64_t)cnt * dut::kRowGroupWords;
+            if (rows && used + nw <= cap_words) memcpy(rows + used, buf.data(), nw * sizeof(uint32_t));
+            used += nw;
+        }
+        if (n_words) *n_words = used;
+        return CL_OK;
+    });
 }
 
 cl_status cl_contig_run(cl_ctx *c)
@@ -2402,73 +1984,66 @@ static cl_status check_summary(cl_ctx *c)
     return CL_OK;
 }
 
-static cl_status cl_contig_collect_impl(cl_ctx *c, cl_contig_summary *out, const cl_interval **intervals, size_t *n_intervals)
-{
-    Range rg("cl_contig_collect");
-    if (!c || !c->ran) return fail(c, CL_ERR_INVALID, "cl_contig_collect before cl_contig_run");
-    HIP_TRY(c, hipSetDevice(c->device));
-    StageTimer tmr;
-    // every `continue` below re-runs the contig for one distinct reason (32-bit counters: once; 16-bit fields in the
-    // marked windows: the marks are sticky, at most twice; a larger extent: once per overhang level), so a handful of
-    // rounds always suffices -- if they do not, the device state and h_sum disagree and nothing may be returned
-    bool converged = false;
-    for (int attempt = 0; attempt < 8 && !converged; ++attempt) {
-        HIP_TRY(c, hipMemcpyAsync(&c->h_sum, c->d_summary.p, sizeof(DevSummary), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        cl_status s = harvest_events(c);
-        if (s != CL_OK) return s;
-        s = check_summary(c);
-        if (s != CL_OK) return s;
-        // a window touched by more reads than the 16-bit counters hold: redo with 32-bit counters
-        if ((c->h_sum.err & kNeedDeep) && !c->deep) {
-            c->deep = true;
-            s = enqueue(c, false, nullptr, nullptr, nullptr);
-            if (s != CL_OK) return s;
-            continue;
-        }
-        // a position deeper than 255 in a window that used the 8-bit counter sets beyond their safe
-        // candidate count: the kernel marked those windows, run again (they now use 16-bit fields)
-        if ((c->h_sum.err & kNeedWide8) && !c->deep) {             // the marks are sticky: at most one more run raises it
-            s = enqueue(c, false, nullptr, nullptr, nullptr);
-            if (s != CL_OK) return s;
-            continue;
-        }
-        // (a read that overhangs the contig end makes the reference walk, and classify as REF_N, positions up to its
-        // end, mod.rs:100-101: the extent was sized for that at upload from the ends computed at cl_push_reads)
-        if (c->h_sum.n_intervals > c->d_iv.cap) {
-            HIP_TRY(c, c->d_iv.reserve(c->h_sum.n_intervals));
-            launch_tail(c);
-            HIP_TRY(c, hipGetLastError());
-        }
-        converged = true;
-    }
-    if (!converged) return fail(c, CL_ERR_DEVICE, "cl_contig_collect: the re-run loop (counter width / extent) did not converge");
-    tmr.lap("collect: kernels + summary");
-    const size_t niv = c->h_sum.n_intervals;
-    static_assert(sizeof(cl_interval) == sizeof(Interval), "interval layout");
-    try { c->h_iv.resize(niv); } catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "interval buffer"); }
-    if (niv) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_iv.data(), c->d_iv.p, niv * sizeof(Interval), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    tmr.lap("collect: intervals D2H");
-    if (out) {
-        static_assert(offsetof(DevSummary, max_end) == sizeof(cl_contig_summary), "summary layout");
-        memcpy(out, &c->h_sum, sizeof(cl_contig_summary));
-    }
-    if (intervals) *intervals = c->h_iv.data();
-    if (n_intervals) *n_intervals = niv;
-    return CL_OK;
-}
-
 cl_status cl_contig_collect(cl_ctx *c, cl_contig_summary *out, const cl_interval **intervals, size_t *n_intervals)
 {
-    // no exception leaves the library through the C ABI
-    try { return cl_contig_collect_impl(c, out, intervals, n_intervals); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+    return guarded(c, [&]() -> cl_status {
+        Range rg("cl_contig_collect");
+        if (!c || !c->ran) return fail(c, CL_ERR_INVALID, "cl_contig_collect before cl_contig_run");
+        HIP_TRY(c, hipSetDevice(c->device));
+        StageTimer tmr;
+        // every `continue` below re-runs the contig for one distinct reason (32-bit counters: once; 16-bit fields in the
+        // marked windows: the marks are sticky, at most twice; a larger extent: once per overhang level), so a handful of
+        // rounds always suffices -- if they do not, the device state and h_sum disagree and nothing may be returned
+        bool converged = false;
+        for (int attempt = 0; attempt < 8 && !converged; ++attempt) {
+            HIP_TRY(c, hipMemcpyAsync(&c->h_sum, c->d_summary.p, sizeof(DevSummary), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            cl_status s = harvest_events(c);
+            if (s != CL_OK) return s;
+            s = check_summary(c);
+            if (s != CL_OK) return s;
+            // a window touched by more reads than the 16-bit counters hold: redo with 32-bit counters
+            if ((c->h_sum.err & kNeedDeep) && !c->deep) {
+                c->deep = true;
+                s = enqueue(c, false, nullptr, nullptr, nullptr);
+                if (s != CL_OK) return s;
+                continue;
+            }
+            // a position deeper than 255 in a window that used the 8-bit counter sets beyond their safe
+            // candidate count: the kernel marked those windows, run again (they now use 16-bit fields)
+            if ((c->h_sum.err & kNeedWide8) && !c->deep) {             // the marks are sticky: at most one more run raises it
+                s = enqueue(c, false, nullptr, nullptr, nullptr);
+                if (s != CL_OK) return s;
+                continue;
+            }
+            // (a read that overhangs the contig end makes the reference walk, and classify as REF_N, positions up to its
+            // end, mod.rs:100-101: the extent was sized for that at upload from the ends computed at cl_push_reads)
+            if (c->h_sum.n_intervals > c->d_iv.cap) {
+                HIP_TRY(c, c->d_iv.reserve(c->h_sum.n_intervals));
+                launch_tail(c);
+                HIP_TRY(c, hipGetLastError());
+            }
+            converged = true;
+        }
+        if (!converged) return fail(c, CL_ERR_DEVICE, "cl_contig_collect: the re-run loop (counter width / extent) did not converge");
+        tmr.lap("collect: kernels + summary");
+        const size_t niv = c->h_sum.n_intervals;
+        static_assert(sizeof(cl_interval) == sizeof(Interval), "interval layout");
+        try { c->h_iv.resize(niv); } catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "interval buffer"); }
+        if (niv) {
+            HIP_TRY(c, hipMemcpyAsync(c->h_iv.data(), c->d_iv.p, niv * sizeof(Interval), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        tmr.lap("collect: intervals D2H");
+        if (out) {
+            static_assert(offsetof(DevSummary, max_end) == sizeof(cl_contig_summary), "summary layout");
+            memcpy(out, &c->h_sum, sizeof(cl_contig_summary));
+        }
+        if (intervals) *intervals = c->h_iv.data();
+        if (n_intervals) *n_intervals = niv;
+        return CL_OK;
+    });
 }
-
 
 cl_status cl_contig_finish(cl_ctx *c, cl_contig_summary *out, const cl_interval **intervals, size_t *n_intervals)
 {
@@ -2583,758 +2158,81 @@ cl_status cl_contig_layout(cl_ctx *c, cl_layout_info *out)
     return CL_OK;
 }
 
-static cl_status cl_debug_depths_impl(cl_ctx *c, uint32_t *raw, uint32_t *qc, uint32_t *low, uint8_t *state, uint64_t cap)
-{
-    if (!c || !c->ran) return fail(c, CL_ERR_INVALID, "cl_debug_depths needs a collected contig");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (cap < c->extent) return fail(c, CL_ERR_INVALID, "cap < extent");
-    const size_t padded = (size_t)c->n_win * kT;
-    HIP_TRY(c, c->d_dbg.reserve(3 * padded + 1));
-    cl_status s = enqueue(c, true, c->d_dbg.p, c->d_dbg.p + padded, c->d_dbg.p + 2 * padded);
-    if (s != CL_OK) return s;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t nb = (size_t)c->extent * sizeof(uint32_t);
-    if (raw && nb) HIP_TRY(c, hipMemcpy(raw, c->d_dbg.p, nb, hipMemcpyDeviceToHost));
-    if (qc && nb) HIP_TRY(c, hipMemcpy(qc, c->d_dbg.p + padded, nb, hipMemcpyDeviceToHost));
-    if (low && nb) HIP_TRY(c, hipMemcpy(low, c->d_dbg.p + 2 * padded, nb, hipMemcpyDeviceToHost));
-    if (state && c->extent) HIP_TRY(c, hipMemcpy(state, c->d_state.p, c->extent, hipMemcpyDeviceToHost));
-    return CL_OK;
-}
-
 cl_status cl_debug_depths(cl_ctx *c, uint32_t *raw, uint32_t *qc, uint32_t *low, uint8_t *state, uint64_t cap)
 {
-    // no exception leaves the library through the C ABI
-    try { return cl_debug_depths_impl(c, raw, qc, low, state, cap); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
+    return guarded(c, [&]() -> cl_status {
+        if (!c || !c->ran) return fail(c, CL_ERR_INVALID, "cl_debug_depths needs a collected contig");
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (cap < c->extent) return fail(c, CL_ERR_INVALID, "cap < extent");
+        const size_t padded = (size_t)c->n_win * kT;
+        HIP_TRY(c, c->d_dbg.reserve(3 * padded + 1));
+        cl_status s = enqueue(c, true, c->d_dbg.p, c->d_dbg.p + padded, c->d_dbg.p + 2 * padded);
+        if (s != CL_OK) return s;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const size_t nb = (size_t)c->extent * sizeof(uint32_t);
+        if (raw && nb) HIP_TRY(c, hipMemcpy(raw, c->d_dbg.p, nb, hipMemcpyDeviceToHost));
+        if (qc && nb) HIP_TRY(c, hipMemcpy(qc, c->d_dbg.p + padded, nb, hipMemcpyDeviceToHost));
+        if (low && nb) HIP_TRY(c, hipMemcpy(low, c->d_dbg.p + 2 * padded, nb, hipMemcpyDeviceToHost));
+        if (state && c->extent) HIP_TRY(c, hipMemcpy(state, c->d_state.p, c->extent, hipMemcpyDeviceToHost));
+        return CL_OK;
+    });
 }
-
 
 // The depth distribution of the resident contig (include/callable_loci.h): one extra launch of k_depth_profile over the
 // residents of the last run, a few KB back.  Nothing of a run is touched: summary, intervals and window partials stay.
-static cl_status cl_contig_depth_profile_impl(cl_ctx *c, uint32_t n_bins, uint32_t window, cl_depth_profile *out)
-{
-    if (!c) return CL_ERR_INVALID;
-    if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: null result");
-    memset(out, 0, sizeof(*out));
-    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-    if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
-    if (n_bins < CL_DEPTH_MIN_BINS || n_bins > CL_DEPTH_MAX_BINS) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: n_bins outside [2, 4096]");
-    if (window != 0 && window < CL_DEPTH_MIN_WINDOW) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: a window of 1 to 15 positions (0 = no window table, else at least 16)");
-    if (!c->uploaded || !c->ran || c->form != 3) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile needs a contig that has been run");
-    if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t n_windows = window ? ((uint64_t)c->extent + window - 1) / window : 0;
-    const size_t n_words = 2 + 2 * (size_t)n_bins + 2 * (size_t)n_windows;
-    HIP_TRY(c, c->d_prof.reserve(n_words));
-    c->h_prof.assign(n_words, 0ull);
-    HIP_TRY(c, hipMemsetAsync(c->d_prof.p, 0, n_words * sizeof(unsigned long long), c->stream));
-    if (c->profiling && !c->prof_ev[0]) for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventCreate(&c->prof_ev[i]));
-    if (c->n_win) {
-        DepthArgs a;
-        a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
-        a.extent = c->extent; a.n_win = c->n_win; a.n_bins = n_bins; a.window = window;
-        a.sums = c->d_prof.p; a.hist = c->d_prof.p + 2; a.wins = c->d_prof.p + 2 + 2 * (size_t)n_bins; a.n_windows = n_windows;
-        const size_t lds = 2u * (size_t)n_bins * sizeof(uint32_t);
-        // workgroups that stay: a histogram is flushed once per workgroup
-        const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
-        if (c->profiling) HIP_TRY(c, hipEventRecord(c->prof_ev[0], c->stream));
-        if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_profile<8>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
-        else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_profile<16>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
-        else hipLaunchKernelGGL((k_depth_profile<32>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
-        HIP_TRY(c, hipGetLastError());
-        if (c->profiling) HIP_TRY(c, hipEventRecord(c->prof_ev[1], c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->h_prof.data(), c->d_prof.p, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->prof_ms = 0.0;
-    if (c->profiling && c->n_win) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->prof_ev[0], c->prof_ev[1]));
-        c->prof_ms = ms;
-    }
-    // (no window of the engine: every position of [0, extent) -- there is none -- is in bin 0)
-    const uint64_t *h = reinterpret_cast<const uint64_t *>(c->h_prof.data());
-    out->n_bins = n_bins; out->window = window; out->n_windows = n_windows; out->extent = c->extent;
-    out->sum_raw = h[0]; out->sum_qc = h[1];
-    out->hist_raw = h + 2; out->hist_qc = h + 2 + n_bins;
-    out->win_raw = window ? h + 2 + 2 * (size_t)n_bins : nullptr;
-    out->win_qc = window ? h + 2 + 2 * (size_t)n_bins + n_windows : nullptr;
-    return CL_OK;
-}
-
 cl_status cl_contig_depth_profile_ms(cl_ctx *c, double *kernel_ms)
 {
     if (!c || !kernel_ms) return CL_ERR_INVALID;
-    *kernel_ms = c->prof_ms;
+    *kernel_ms = c->t_prof.ms;
     return CL_OK;
 }
 
 cl_status cl_contig_depth_profile(cl_ctx *c, uint32_t n_bins, uint32_t window, cl_depth_profile *out)
 {
-    // no exception leaves the library through the C ABI
-    try { return cl_contig_depth_profile_impl(c, n_bins, window, out); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-// the site list as the kernel wants it: sorted by 0-based position (vcf_pos - 1, caller.rs:94) with the original
-// indices, vcf_pos 0 left out (it can never match), and the first sorted site at or after every 256th position
-struct SitePrep { std::vector<uint32_t> pos0, idx, bucket; uint32_t n_buckets = 0; };
-static void site_prepare(const uint32_t *sites, size_t n_sites, SitePrep &P)
-{
-    // (position, original index) sorted by position, ties by index: a stable radix sort on the 32-bit positions, three
-    // passes of 11 bits (std::sort took 10 of the 11 ms of a run on a resident tile with 200 000 sites)
-    std::vector<unsigned long long> key(n_sites), tmp(n_sites);
-    for (size_t i = 0; i < n_sites; ++i) key[i] = ((unsigned long long)sites[i] << 32) | (unsigned long long)i;
-    for (int pass = 0; pass < 3; ++pass) {
-        const int sh = 32 + 11 * pass;
-        size_t cnt[2049] = {0};
-        for (size_t i = 0; i < n_sites; ++i) cnt[((key[i] >> sh) & 2047u) + 1] += 1;
-        for (int b = 0; b < 2048; ++b) cnt[b + 1] += cnt[b];
-        for (size_t i = 0; i < n_sites; ++i) tmp[cnt[(key[i] >> sh) & 2047u]++] = key[i];
-        key.swap(tmp);
-    }
-    P.pos0.reserve(n_sites); P.idx.reserve(n_sites);
-    for (size_t i = 0; i < n_sites; ++i) {
-        const uint32_t s = (uint32_t)(key[i] >> 32);
-        if (s == 0) continue;
-        P.pos0.push_back(s - 1); P.idx.push_back((uint32_t)key[i]);
-    }
-    if (P.pos0.empty()) return;
-    P.n_buckets = (uint32_t)(((uint64_t)P.pos0.back() >> 8) + 2);
-    P.bucket.resize(P.n_buckets);
-    size_t j = 0;
-    for (uint32_t bk = 0; bk < P.n_buckets; ++bk) {
-        while (j < P.pos0.size() && P.pos0[j] < ((uint64_t)bk << 8)) ++j;
-        P.bucket[bk] = (uint32_t)j;
-    }
-}
-
-
-// cl_site_pileup knows the site list when the tile is uploaded: only the reads that can add to the histogram travel --
-// those the kernel itself would walk (k_site_pileup: position inside the contig, mapq >= min_quality, a site inside
-// [pos, pos + reference span)); at one site per ~300 bases that is two short reads in five, and the bases are what the
-// call spends its time sending (1.1 GB at the link's rate for BASELINE configs[4]).  The kept reads' records, CIGAR words
-// and base BYTES are gathered straight into the pinned buffers; a read keeps its nibble parity (its bytes are copied
-// whole), so read lengths can no longer be taken from offset differences: tiles with a read of 65 535 bases or 255
-// operations and more (the records' escape values) are sent whole instead.
-struct SiteGather {
-    dut::Scratch<uint32_t> kidx;               // kept read k = read kidx[k] of the tile
-    dut::Scratch<unsigned long long> B;        // K + 1: first byte of kept read k in the gathered base array
-    dut::Scratch<uint32_t> coff;               // K + 1: first CIGAR word of kept read k in the gathered CIGAR array
-    uint64_t K = 0;
-    bool on = false;
-};
-static void site_filter(const cl_site_tile *t, const SitePrep &P, uint8_t min_quality, uint32_t contig_len, SiteGather &G)
-{
-    const uint64_t n = t->n_reads;
-    G.on = false;
-    if (n == 0 || P.pos0.empty()) return;
-    const size_t grain = 1u << 16, nchunk = (n + grain - 1) / grain;
-    dut::Scratch<uint8_t> keep(n);
-    std::vector<uint64_t> c_k(nchunk + 1, 0), c_b(nchunk + 1, 0), c_c(nchunk + 1, 0);
-    std::atomic<bool> escape{false};
-    const uint32_t *pos0 = P.pos0.data(); const uint32_t *bucket = P.bucket.data();
-    const uint32_t n_sites = (uint32_t)P.pos0.size(), n_buckets = P.n_buckets;
-    uint8_t *kp = keep.get();
-    dut::parallel_for(nchunk, 1, [&](size_t ch) {
-        const size_t a = ch * grain, b = std::min<size_t>(n, a + grain);
-        uint64_t k = 0, nb = 0, nc = 0;
-        for (size_t i = a; i < b; ++i) {
-            kp[i] = 0;
-            const uint32_t c0 = t->cigar_off[i], c1 = t->cigar_off[i + 1];
-            const uint64_t s0 = t->seq_off[i], s1 = t->seq_off[i + 1];
-            if (c1 < c0 || s1 < s0) { escape.store(true); continue; }          // (refused by the upload's own check)
-            if (c1 - c0 >= 255u || s1 - s0 >= 0xFFFFull) escape.store(true);
-            if ((uint32_t)t->pos[i] >= contig_len || t->mapq[i] < min_quality) continue;
-            unsigned long long reflen = 0;
-            for (uint32_t q = c0; q < c1; ++q) { const uint32_t cw = t->cigar[q]; reflen += ((0x18Du >> (cw & 15u)) & 1u) ? (cw >> 4) : 0u; }
-            const unsigned long long x = (uint32_t)t->pos[i];
-            const unsigned long long bx = x >> 8;
-            uint32_t lo = bx < n_buckets ? bucket[bx] : n_sites;
-            while (lo < n_sites && pos0[lo] < x) ++lo;
-            if (lo < n_sites && pos0[lo] < x + reflen) { kp[i] = 1; ++k; nb += ((s1 + 1) >> 1) - (s0 >> 1); nc += c1 - c0; }
+    return guarded(c, [&]() -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: null result");
+        memset(out, 0, sizeof(*out));
+        if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
+        if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
+        if (n_bins < CL_DEPTH_MIN_BINS || n_bins > CL_DEPTH_MAX_BINS) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: n_bins outside [2, 4096]");
+        if (window != 0 && window < CL_DEPTH_MIN_WINDOW) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: a window of 1 to 15 positions (0 = no window table, else at least 16)");
+        if (!c->uploaded || !c->ran || c->form != 3) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile needs a contig that has been run");
+        if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
+        HIP_TRY(c, hipSetDevice(c->device));
+        const uint64_t n_windows = window ? ((uint64_t)c->extent + window - 1) / window : 0;
+        const size_t n_words = 2 + 2 * (size_t)n_bins + 2 * (size_t)n_windows;
+        HIP_TRY(c, c->d_prof.reserve(n_words));
+        c->h_prof.assign(n_words, 0ull);
+        HIP_TRY(c, hipMemsetAsync(c->d_prof.p, 0, n_words * sizeof(unsigned long long), c->stream));
+        if (c->n_win) {
+            DepthArgs a;
+            a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
+            a.extent = c->extent; a.n_win = c->n_win; a.n_bins = n_bins; a.window = window;
+            a.sums = c->d_prof.p; a.hist = c->d_prof.p + 2; a.wins = c->d_prof.p + 2 + 2 * (size_t)n_bins; a.n_windows = n_windows;
+            const size_t lds = 2u * (size_t)n_bins * sizeof(uint32_t);
+            // workgroups that stay: a histogram is flushed once per workgroup
+            const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
+            if (c->profiling) HIP_TRY(c, c->t_prof.start(c->stream));
+            if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_profile<8>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
+            else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_profile<16>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
+            else hipLaunchKernelGGL((k_depth_profile<32>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
+            HIP_TRY(c, hipGetLastError());
+            if (c->profiling) HIP_TRY(c, c->t_prof.stop(c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->h_prof.data(), c->d_prof.p, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         }
-        c_k[ch + 1] = k; c_b[ch + 1] = nb; c_c[ch + 1] = nc;
-    });
-    if (escape.load()) return;
-    for (size_t ch = 0; ch < nchunk; ++ch) { c_k[ch + 1] += c_k[ch]; c_b[ch + 1] += c_b[ch]; c_c[ch + 1] += c_c[ch]; }
-    const uint64_t K = c_k[nchunk];
-    if (c_c[nchunk] > 0xFFFFFFF0ull) return;
-    G.kidx = dut::Scratch<uint32_t>(K + 1); G.B = dut::Scratch<unsigned long long>(K + 1); G.coff = dut::Scratch<uint32_t>(K + 1);
-    uint32_t *kidx = G.kidx.get(); unsigned long long *B = G.B.get(); uint32_t *coff = G.coff.get();
-    dut::parallel_for(nchunk, 1, [&](size_t ch) {
-        const size_t a = ch * grain, b = std::min<size_t>(n, a + grain);
-        uint64_t k = c_k[ch], nb = c_b[ch], nc = c_c[ch];
-        for (size_t i = a; i < b; ++i) {
-            if (!kp[i]) continue;
-            kidx[k] = (uint32_t)i; B[k] = nb; coff[k] = (uint32_t)nc;
-            nb += ((t->seq_off[i + 1] + 1) >> 1) - (t->seq_off[i] >> 1); nc += t->cigar_off[i + 1] - t->cigar_off[i];
-            ++k;
-        }
-    });
-    kidx[K] = 0; B[K] = c_b[nchunk]; coff[K] = (uint32_t)c_c[nchunk];
-    G.K = K; G.on = true;
-}
-
-// ---- config 5: the tile goes to HBM once (cl_site_upload: packed records built straight into the pinned buffers, the
-//      4-bit bases and the CIGAR words through the staging ring) and stays resident; any number of site lists can then be
-//      run over it (cl_site_run).  cl_site_pileup is the two in one call. ----
-static cl_status cl_site_upload_impl(cl_ctx *c, uint32_t contig_len, uint64_t ref_len, const cl_site_tile *t, const SiteGather *G = nullptr)
-{
-    if (!c || !t) return CL_ERR_INVALID;
-    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-    HIP_TRY(c, hipSetDevice(c->device));
-    drop_prefetch(c);                                        // the ring is needed below
-    SiteResident &S = c->site;
-    S.resident = false; S.filtered = false; S.scan_indexed = false; S.attached = false;
-    const uint64_t n_all = t->n_reads;
-    if (n_all > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "too many reads");
-    if (n_all && (!t->pos || !t->mapq || !t->cigar_off || !t->seq_off)) return fail(c, CL_ERR_INVALID, "null tile array");
-    StageTimer tmr;
-    // what travels: the whole tile, or (cl_site_pileup, site_filter above) the reads that overlap a site of its list
-    const bool g = G && G->on;
-    if (!g) {                                                // (site_filter has looked at every offset pair already)
-        std::atomic<int> bad{0};
-        dut::parallel_for(n_all, 262144, [&](size_t i) { if (t->cigar_off[i + 1] < t->cigar_off[i] || t->seq_off[i + 1] < t->seq_off[i]) bad = 1; });
-        if (bad) return fail(c, CL_ERR_INVALID, "offset arrays must be non-decreasing");
-    }
-    const uint64_t n = g ? G->K : n_all;
-    const uint32_t *kidx = g ? G->kidx.get() : nullptr;
-    const unsigned long long *GB = g ? G->B.get() : nullptr;
-    const uint32_t *gco = g ? G->coff.get() : nullptr;
-    const uint64_t ncig = g ? gco[n] : (n_all ? t->cigar_off[n_all] : 0);
-    const uint64_t nbytes = g ? GB[n] : ((n_all ? t->seq_off[n_all] : 0) + 1) / 2;
-    const uint64_t nbase = g ? 2 * GB[n] : (n_all ? t->seq_off[n_all] : 0);
-    const uint64_t *hs_all = t->seq_off;
-    // base offset of (kept) read k in the array that travels; k = n: its end
-    auto seq_at = [=](uint64_t k) -> uint64_t { return !g ? hs_all[k] : (k < n ? 2 * GB[k] + (hs_all[kidx[k]] & 1ull) : nbase); };
-    const uint64_t n_blocks = (n + kBlock - 1) / kBlock;
-    // a workgroup's reads must lie within 2^32 bases of its first one (256 reads: always, short of 16 M-base reads)
-    for (uint64_t b = 0; b < n_blocks; ++b)
-        if (seq_at(std::min<uint64_t>(n, (b + 1) * kBlock)) - seq_at(b * kBlock) > 0xFFFF0000ull)
-            return fail(c, CL_ERR_RANGE, "reads too long for the site pileup");
-    HIP_TRY(c, S.rec.reserve(n + 1)); HIP_TRY(c, S.base.reserve(n_blocks + 1));
-    HIP_TRY(c, S.cig.reserve(ncig + 8)); HIP_TRY(c, S.seq.reserve(nbytes + 16));
-    tmr.lap("site upload: checks + device buffers");
-    cl_status rs = CL_OK;
-    // the bases: the bulk of the tile (0.5 byte per aligned base)
-    if (nbytes && !g && (rs = ring_copy(c, S.seq.p, t->seq4, nbytes)) != CL_OK) return rs;
-    if (nbytes && g) {
-        const uint8_t *seq4 = t->seq4;
-        rs = ring_start(c, S.seq.p, nbytes, [seq4, hs_all, kidx, GB, n](uint64_t off, uint64_t len, uint8_t *out) {
-            // the kept reads whose bytes fall into [off, off + len): whole bytes of the tile's array, read by read
-            uint64_t k = (uint64_t)(std::upper_bound(GB, GB + n + 1, (unsigned long long)off) - GB) - 1;
-            uint64_t at = off;
-            const uint64_t end = off + len;
-            while (at < end && k < n) {
-                const uint64_t src0 = hs_all[kidx[k]] >> 1, take = std::min<uint64_t>(GB[k + 1], end) - at;
-                memcpy(out + (at - off), seq4 + src0 + (at - GB[k]), take);
-                at += take;
-                if (at == GB[k + 1]) ++k;
-            }
-        }, PinRing::kPinBytes, PinRing::kCopyThreads);
-        if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
-        if (rs != CL_OK) return rs;
-    }
-    tmr.lap("site upload: bases");
-    // one packed record per read (+ the sentinel with the totals), built in the pinned buffers
-    {
-        const int32_t *hp = t->pos; const uint8_t *hm = t->mapq; const uint32_t *hc = t->cigar_off;
-        const uint64_t ncig_all = ncig;
-        rs = ring_start(c, reinterpret_cast<uint8_t *>(S.rec.p), (n + 1) * sizeof(SiteRec), [=](uint64_t off, uint64_t len, uint8_t *out) {
-            SiteRec *o = reinterpret_cast<SiteRec *>(out);
-            const size_t i0 = off / sizeof(SiteRec), i1 = (off + len) / sizeof(SiteRec);
-            for (size_t k = i0; k < i1; ++k) {
-                SiteRec r;
-                if (k < n) {
-                    const size_t i = g ? kidx[k] : k;
-                    const uint32_t nc = hc[i + 1] - hc[i];
-                    const uint64_t sl = hs_all[i + 1] - hs_all[i];
-                    r.pos = hp[i]; r.cigar_off = g ? gco[k] : hc[i]; r.seq_lo = (uint32_t)seq_at(k);
-                    r.meta = (uint32_t)hm[i] | (std::min<uint32_t>(nc, 255u) << 8) | ((uint32_t)std::min<uint64_t>(sl, 0xFFFFull) << 16);
-                } else { r.pos = 0; r.cigar_off = (uint32_t)ncig_all; r.seq_lo = (uint32_t)nbase; r.meta = 0; }
-                o[k - i0] = r;
-            }
-        }, PinRing::kPinBytes, g ? PinRing::kCopyThreads : 0);
-        // ... beside it, the 64-bit base offset of every workgroup's first read
-        std::vector<unsigned long long> h_base(n_blocks + 1);
-        for (uint64_t b = 0; b < n_blocks; ++b) h_base[b] = seq_at(b * kBlock);
-        h_base[n_blocks] = nbase;
-        if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
-        if (rs != CL_OK) return rs;
-        HIP_TRY(c, hipMemcpyAsync(S.base.p, h_base.data(), (n_blocks + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    if (ncig && !g && (rs = ring_copy(c, S.cig.p, t->cigar, ncig * 4)) != CL_OK) return rs;
-    if (ncig && g) {
-        const uint32_t *cig = t->cigar; const uint32_t *hc = t->cigar_off;
-        rs = ring_start(c, reinterpret_cast<uint8_t *>(S.cig.p), ncig * 4, [cig, hc, kidx, gco, n](uint64_t off, uint64_t len, uint8_t *out) {
-            const uint64_t w0 = off / 4, w1 = (off + len) / 4;                  // (a buffer is a whole number of words)
-            uint64_t k = (uint64_t)(std::upper_bound(gco, gco + n + 1, (uint32_t)w0) - gco) - 1;
-            uint64_t at = w0;
-            uint32_t *o = reinterpret_cast<uint32_t *>(out);
-            while (at < w1 && k < n) {
-                const uint64_t take = std::min<uint64_t>(gco[k + 1], w1) - at;
-                const uint32_t *src = cig + hc[kidx[k]] + (at - gco[k]);
-                uint32_t *dstw = o + (at - w0);
-                for (uint64_t q = 0; q < take; ++q) dstw[q] = src[q];          // (a read has a word or three)
-                at += take;
-                if (at == gco[k + 1]) ++k;
-            }
-        }, PinRing::kPinBytes, PinRing::kCopyThreads);
-        if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
-        if (rs != CL_OK) return rs;
-    }
-    tmr.lap("site upload: records + cigar");
-    S.n = n; S.ncig = ncig; S.nbase = nbase; S.contig_len = contig_len; S.ref_len = ref_len;
-    S.resident = true; S.filtered = g;
-    return CL_OK;
-}
-
-static cl_status cl_site_run_impl(cl_ctx *c, uint8_t min_quality, const uint32_t *sites, size_t n_sites, uint32_t *hist, const SitePrep *ready)
-{
-    if (!c || (!sites && n_sites) || (!hist && n_sites)) return CL_ERR_INVALID;
-    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-    SiteResident &S = c->site;
-    if (!S.resident) return fail(c, CL_ERR_INVALID, "cl_site_run without cl_site_upload");
-    // (a tile that cl_site_pileup filtered for its own list serves that call only: ready != nullptr is that call)
-    if (S.filtered && !ready) return fail(c, CL_ERR_INVALID, "cl_site_run: the resident tile was uploaded by cl_site_pileup for its own site list; cl_site_upload gives a tile that serves any list");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (n_sites == 0) return CL_OK;
-    if (n_sites > 0x0FFFFFFFu) return fail(c, CL_ERR_RANGE, "too many sites");
-    StageTimer tmr;
-    SitePrep mine;
-    if (!ready) { site_prepare(sites, n_sites, mine); ready = &mine; }
-    const std::vector<uint32_t> &pos0 = ready->pos0, &idx = ready->idx, &bucket = ready->bucket;
-    const uint32_t n_buckets = ready->n_buckets;
-    memset(hist, 0, n_sites * 16 * sizeof(uint32_t));
-    if (S.n == 0 || pos0.empty()) return CL_OK;
-    tmr.lap("site run: sort + buckets");
-    HIP_TRY(c, S.p0.reserve(pos0.size())); HIP_TRY(c, S.ix.reserve(pos0.size())); HIP_TRY(c, S.hist.reserve(n_sites * 16));
-    HIP_TRY(c, S.bk.reserve(n_buckets));
-    HIP_TRY(c, hipMemsetAsync(S.hist.p, 0, n_sites * 16 * 4, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(S.p0.p, pos0.data(), pos0.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(S.ix.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(S.bk.p, bucket.data(), (size_t)n_buckets * 4, hipMemcpyHostToDevice, c->stream));
-    SiteArgs A;
-    A.rec = S.rec.p; A.seq_base = S.base.p; A.cigar = S.cig.p; A.seq4 = S.seq.p; A.n = (uint32_t)S.n;
-    A.min_quality = min_quality; A.contig_len = S.contig_len; A.ref_len = S.ref_len;
-    A.sorted_pos0 = S.p0.p; A.sorted_idx = S.ix.p; A.bucket = S.bk.p; A.n_buckets = n_buckets; A.n_sites = (uint32_t)pos0.size();
-    A.hist = S.hist.p;
-    if (!c->site_ev[0]) { HIP_TRY(c, hipEventCreate(&c->site_ev[0])); HIP_TRY(c, hipEventCreate(&c->site_ev[1])); }
-    HIP_TRY(c, hipEventRecord(c->site_ev[0], c->stream));
-    hipLaunchKernelGGL(k_site_pileup, dim3((uint32_t)((S.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->site_ev[1], c->stream));
-    HIP_TRY(c, hipMemcpyAsync(hist, S.hist.p, n_sites * 16 * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    {
-        float t = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&t, c->site_ev[0], c->site_ev[1]));
-        c->site_ms = t;
-        // 4-bit bases + per-read pos/mapq/offsets + CIGAR words read, the sites' positions /
-        // indices read and their 16 counters written
-        c->site_bytes = (S.nbase + 1) / 2 + S.n * sizeof(SiteRec) + S.ncig * 4 + (uint64_t)pos0.size() * 8 + (uint64_t)n_sites * 64;
-    }
-    tmr.lap("site run: kernel + histogram back");
-    return CL_OK;
-}
-
-// ---- config 5, dense form: base counts and calls at every position of a range of the resident tile (site_scan.hip.h),
-// ---- unfiltered (cl_site_scan) and filtered, strand-aware (cl_site_scan_ex, behind cl_site_attach_quals) ----
-static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_candidate) == 28, "the device writes cl_scan_candidate");
-static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
-
-// the argument checks every scan shares, in front of any device work
-static cl_status site_scan_check(cl_ctx *c, const char *who, uint32_t start, uint32_t end)
-{
-    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-    const SiteResident &S = c->site;
-    if (!S.resident) return fail(c, CL_ERR_INVALID, std::string(who) + " without cl_site_upload");
-    if (S.filtered) return fail(c, CL_ERR_INVALID, std::string(who) + ": the resident tile was uploaded by cl_site_pileup for its own site list; cl_site_upload gives a tile that serves a scan");
-    if (start > end) return fail(c, CL_ERR_INVALID, std::string(who) + ": start > end");
-    if (end > S.contig_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": the range ends beyond the contig");
-    return CL_OK;
-}
-
-// the per-read ends and per-window read ranges of the resident tile: one kernel, the first time a scan asks
-static cl_status site_scan_index(cl_ctx *c)
-{
-    SiteResident &S = c->site;
-    if (S.scan_indexed) return CL_OK;
-    const size_t n_win = ((size_t)S.contig_len + kScanWin - 1) / kScanWin;
-    HIP_TRY(c, S.sc_end.reserve(S.n + 1)); HIP_TRY(c, S.sc_wfirst.reserve(n_win + 1)); HIP_TRY(c, S.sc_wlast.reserve(n_win + 1));
-    HIP_TRY(c, hipMemsetAsync(S.sc_wfirst.p, 0xFF, (n_win + 1) * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(S.sc_wlast.p, 0, (n_win + 1) * 4, c->stream));
-    if (S.n) {
-        ScanIndexArgs A;
-        A.rec = S.rec.p; A.cigar = S.cig.p; A.n = (uint32_t)S.n; A.contig_len = S.contig_len;
-        A.end = S.sc_end.p; A.wfirst = S.sc_wfirst.p; A.wlast = S.sc_wlast.p;
-        hipLaunchKernelGGL(k_site_scan_index, dim3((uint32_t)((S.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream, A);
-        HIP_TRY(c, hipGetLastError());
-    }
-    S.scan_indexed = true;
-    return CL_OK;
-}
-
-extern "C++" {                                                 // (templates: one host path for the two forms)
-
-// what the host path of the two forms differs in: the C types, the names in messages, where the candidates live (those
-// of cl_site_scan stay valid until the next cl_site_scan, those of cl_site_scan_ex until the next cl_site_scan_ex),
-// the filter argument (none, or the caller's cl_scan_filter) and the tile bytes a scan reads
-template <bool FILTERED> struct ScanHost;
-template <> struct ScanHost<false> {
-    using Result = cl_scan_result;
-    using Cand = cl_scan_candidate;
-    using Filter = ScanNoFilter;
-    static constexpr const char *kScan = "cl_site_scan", *kCounts = "cl_site_scan_counts";
-    static constexpr const char *kLap = "site scan: reference in, kernel, candidates back";
-    static constexpr const char *kLapSettle = "site scan: ambiguous positions settled by the site pileup";
-    static std::vector<Cand> &host_cand(cl_ctx *c) { return c->scan_cand; }
-    static DevBuf<ScanCand> &dev_cand(SiteResident &S) { return S.sc_cand; }
-    static uint64_t tile_bytes(const SiteResident &S) { return (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4; }
-};
-template <> struct ScanHost<true> {
-    using Result = cl_scan_result_ex;
-    using Cand = cl_scan_candidate_ex;
-    using Filter = const cl_scan_filter *;
-    static constexpr const char *kScan = "cl_site_scan_ex", *kCounts = "cl_site_scan_counts_ex";
-    static constexpr const char *kLap = "filtered site scan: reference in, kernel, candidates back";
-    static constexpr const char *kLapSettle = "filtered site scan: ambiguous positions settled";
-    static std::vector<Cand> &host_cand(cl_ctx *c) { return c->scan_cand_ex; }
-    static DevBuf<ScanCandEx> &dev_cand(SiteResident &S) { return S.sx_cand; }
-    // those of cl_site_scan, the pass bits and the flags
-    static uint64_t tile_bytes(const SiteResident &S) { return ScanHost<false>::tile_bytes(S) + (S.nbase + 7) / 8 + S.n * 2; }
-};
-
-// site_scan_check and, for the filtered form, its filter and the attachment
-template <bool FILTERED>
-static cl_status site_scan_check_form(cl_ctx *c, const char *who, typename ScanHost<FILTERED>::Filter f, uint32_t start, uint32_t end)
-{
-    cl_status s = site_scan_check(c, who, start, end);
-    if (s != CL_OK) return s;
-    if constexpr (FILTERED) {
-        if (!f) return fail(c, CL_ERR_INVALID, std::string(who) + ": null filter");
-        if (!c->site.attached) return fail(c, CL_ERR_INVALID, std::string(who) + " without cl_site_attach_quals on the resident tile");
-    }
-    return CL_OK;
-}
-
-template <bool FILTERED>
-static void site_scan_fill(cl_ctx *c, ScanFormArgs<FILTERED> &A, typename ScanHost<FILTERED>::Filter f, uint8_t min_quality, uint32_t min_depth,
-                           uint32_t start, uint32_t end)
-{
-    SiteResident &S = c->site;
-    A.s.rec = S.rec.p; A.s.seq_base = S.base.p; A.s.cigar = S.cig.p; A.s.seq4 = S.seq.p;
-    A.s.end = S.sc_end.p; A.s.wfirst = S.sc_wfirst.p; A.s.wlast = S.sc_wlast.p;
-    A.s.min_quality = min_quality; A.s.contig_len = S.contig_len; A.s.min_depth = min_depth; A.s.ref_len = S.ref_len;
-    A.s.start = start; A.s.end_pos = end; A.s.win0 = start / kScanWin;
-    A.s.refb = nullptr; A.s.cls = nullptr; A.s.n_cand = nullptr; A.s.cand_cap = 0; A.s.dense = nullptr;
-    A.cand = nullptr;
-    if constexpr (FILTERED) {
-        A.f.flag = S.q_flag.p; A.f.pass = S.q_pass.p; A.f.exclude_flags = f->exclude_flags; A.f.use_bq = f->use_base_quality ? 1u : 0u;
-    }
-}
-
-// The 16-code histograms of the positions the counter planes cannot classify (site_scan.hip.h).  Unfiltered: those of
-// cl_site_run.  Filtered: k_site_scan_settle under the filter of A (cl_site_run's histogram is unfiltered).
-template <bool FILTERED>
-static cl_status site_scan_hist16(cl_ctx *c, const ScanFormArgs<FILTERED> &A, const std::vector<uint32_t> &pos1, std::vector<uint32_t> &hist)
-{
-    hist.resize(pos1.size() * 16);
-    if constexpr (FILTERED) {
-        SiteResident &S = c->site;
-        HIP_TRY(c, S.sx_amb.reserve(pos1.size())); HIP_TRY(c, S.sx_hist.reserve(hist.size()));
-        HIP_TRY(c, hipMemcpyAsync(S.sx_amb.p, pos1.data(), pos1.size() * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_site_scan_settle, dim3((uint32_t)pos1.size()), dim3(kBlock), 0, c->stream, A, S.sx_amb.p, S.sx_hist.p);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(hist.data(), S.sx_hist.p, hist.size() * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->t_prof.ms = 0.0;
+        if (c->profiling && c->n_win) HIP_TRY(c, c->t_prof.read());
+        // (no window of the engine: every position of [0, extent) -- there is none -- is in bin 0)
+        const uint64_t *h = reinterpret_cast<const uint64_t *>(c->h_prof.data());
+        out->n_bins = n_bins; out->window = window; out->n_windows = n_windows; out->extent = c->extent;
+        out->sum_raw = h[0]; out->sum_qc = h[1];
+        out->hist_raw = h + 2; out->hist_qc = h + 2 + n_bins;
+        out->win_raw = window ? h + 2 + 2 * (size_t)n_bins : nullptr;
+        out->win_qc = window ? h + 2 + 2 * (size_t)n_bins + n_windows : nullptr;
         return CL_OK;
-    } else {
-        const double ms = c->site_ms; const uint64_t by = c->site_bytes;      // (cl_site_pileup_stats keeps speaking of the caller's own runs)
-        const cl_status s = cl_site_run_impl(c, (uint8_t)A.s.min_quality, pos1.data(), pos1.size(), hist.data(), nullptr);
-        c->site_ms = ms; c->site_bytes = by;
-        return s;
-    }
+    });
 }
-
-// settles ambiguous positions from their 16-code histograms: one code with 7/10 of the depth is a call of a code that
-// is not A/C/G/T -> uncomparable; otherwise mixed
-static void site_scan_settle(const std::vector<uint32_t> &hist, uint64_t &n_unc, uint64_t &n_mixed)
-{
-    for (size_t i = 0; i < hist.size(); i += 16) {
-        uint64_t depth = 0, m = 0;
-        for (int k = 0; k < 16; ++k) { depth += hist[i + k]; m = std::max<uint64_t>(m, hist[i + k]); }
-        if (10 * m >= 7 * depth) ++n_unc; else ++n_mixed;
-    }
-}
-
-template <bool FILTERED>
-static cl_status site_scan_impl(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, typename ScanHost<FILTERED>::Filter filter, const uint8_t *ref_bases,
-                                uint64_t ref_len, uint32_t start, uint32_t end, typename ScanHost<FILTERED>::Result *out)
-{
-    using H = ScanHost<FILTERED>;
-    using Cand = typename H::Cand;
-    if (!c) return CL_ERR_INVALID;
-    if (!out) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": null result");
-    cl_status s = site_scan_check_form<FILTERED>(c, H::kScan, filter, start, end);
-    if (s != CL_OK) return s;
-    SiteResident &S = c->site;
-    if (min_depth == 0) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": min_depth must be at least 1");
-    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": ref_len differs from the one given to cl_site_upload");
-    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": null reference");
-    std::vector<Cand> &cand = H::host_cand(c);
-    auto &d_cand = H::dev_cand(S);
-    memset(out, 0, sizeof(*out));
-    out->start = start; out->end = end;
-    cand.clear();
-    out->candidates = cand.data();
-    c->scan_ms = 0.0; c->scan_bytes = 0;
-    if (start == end) return CL_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    StageTimer tmr;
-    if ((s = site_scan_index(c)) != CL_OK) return s;
-    // the reference bytes of the range (those that exist: positions at and beyond ref_len read as "other")
-    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len), n_ref = ref_hi > start ? ref_hi - start : 0;
-    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
-    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
-    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
-    const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
-    // candidates are few where the sample follows the reference: a buffer of a position in 64 (at least 64 K entries);
-    // when more are wanted the kernel says how many, the buffer grows and the scan runs again -- nothing is cut short
-    uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
-    unsigned long long h_cls[8];
-    double ms_all = 0.0;
-    ScanFormArgs<FILTERED> A;
-    for (;;) {
-        HIP_TRY(c, d_cand.reserve(cap));
-        HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
-        site_scan_fill<FILTERED>(c, A, filter, min_quality, min_depth, start, end);
-        A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
-        A.cand = d_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-        HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
-        hipLaunchKernelGGL((k_site_scan<FILTERED, false>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
-        HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        float t = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
-        ms_all += t;
-        const uint64_t want = (uint32_t)h_cls[SCAN_CLASSES];
-        if (want <= cap) break;
-        cap = want;
-    }
-    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
-    cand.resize(n_cand);
-    if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), d_cand.p, n_cand * sizeof(Cand), hipMemcpyDeviceToHost));
-    c->scan_ms = ms_all;
-    c->scan_bytes = H::tile_bytes(S) + n_ref + n_cand * sizeof(Cand);
-    tmr.lap(H::kLap);
-    // the compaction runs wave by wave: ascending position is restored here; ambiguous positions leave the list
-    std::sort(cand.begin(), cand.end(), [](const Cand &a, const Cand &b) { return a.pos < b.pos; });
-    out->n_low_depth = h_cls[SCAN_LOW_DEPTH]; out->n_mixed = h_cls[SCAN_MIXED]; out->n_uncomparable = h_cls[SCAN_UNCOMPARABLE];
-    out->n_match = h_cls[SCAN_MATCH]; out->n_variant = h_cls[SCAN_VARIANT];
-    if (h_cls[SCAN_AMBIGUOUS]) {
-        std::vector<uint32_t> amb, hist;
-        size_t k = 0;
-        for (const Cand &cd : cand) { if (cd.alt == 0) amb.push_back(cd.pos); else cand[k++] = cd; }
-        cand.resize(k);
-        if ((s = site_scan_hist16<FILTERED>(c, A, amb, hist)) != CL_OK) return s;
-        site_scan_settle(hist, out->n_uncomparable, out->n_mixed);
-        tmr.lap(H::kLapSettle);
-    }
-    out->candidates = cand.data();
-    return CL_OK;
-}
-
-template <bool FILTERED>
-static cl_status site_scan_counts_impl(cl_ctx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, uint32_t start, uint32_t end,
-                                       uint32_t *counts)
-{
-    using H = ScanHost<FILTERED>;
-    if (!c) return CL_ERR_INVALID;
-    cl_status s = site_scan_check_form<FILTERED>(c, H::kCounts, filter, start, end);
-    if (s != CL_OK) return s;
-    if (end - start > CL_SCAN_MAX_DENSE) return fail(c, CL_ERR_INVALID, std::string(H::kCounts) + ": more than CL_SCAN_MAX_DENSE positions");
-    c->scan_ms = 0.0; c->scan_bytes = 0;
-    if (start == end) return CL_OK;
-    if (!counts) return fail(c, CL_ERR_INVALID, std::string(H::kCounts) + ": null array");
-    SiteResident &S = c->site;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((s = site_scan_index(c)) != CL_OK) return s;
-    const size_t n_dense = (size_t)(end - start) * ScanForm<FILTERED>::kDense;
-    HIP_TRY(c, S.sc_dense.reserve(n_dense));
-    if (!c->scan_ev[0]) { HIP_TRY(c, hipEventCreate(&c->scan_ev[0])); HIP_TRY(c, hipEventCreate(&c->scan_ev[1])); }
-    ScanFormArgs<FILTERED> A;
-    site_scan_fill<FILTERED>(c, A, filter, min_quality, 1, start, end);
-    A.s.dense = S.sc_dense.p;
-    HIP_TRY(c, hipEventRecord(c->scan_ev[0], c->stream));
-    hipLaunchKernelGGL((k_site_scan<FILTERED, true>), dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->scan_ev[1], c->stream));
-    HIP_TRY(c, hipMemcpyAsync(counts, S.sc_dense.p, n_dense * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float t = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&t, c->scan_ev[0], c->scan_ev[1]));
-    c->scan_ms = t;
-    c->scan_bytes = H::tile_bytes(S) + n_dense * 4;
-    return CL_OK;
-}
-
-} // extern "C++"
-
-cl_status cl_site_scan(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const uint8_t *ref_bases, uint64_t ref_len,
-                       uint32_t start, uint32_t end, cl_scan_result *out)
-{
-    try { return site_scan_impl<false>(c, min_quality, min_depth, ScanNoFilter{}, ref_bases, ref_len, start, end, out); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-cl_status cl_site_scan_counts(cl_ctx *c, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts)
-{
-    try { return site_scan_counts_impl<false>(c, min_quality, ScanNoFilter{}, start, end, counts); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-// ---- the attachment of the filtered form ----
-static cl_status site_quals_check(const cl_site_quals *q, std::string &why)
-{
-    if (!q) { why = "null attachment"; return CL_ERR_INVALID; }
-    if (!q->qual_off || !q->seq_off || (q->n_reads && !q->flag)) { why = "null attachment array"; return CL_ERR_INVALID; }
-    std::atomic<int> bad{0};
-    dut::parallel_for(q->n_reads, 262144, [&](size_t i) { if (q->qual_off[i + 1] < q->qual_off[i] || q->seq_off[i + 1] < q->seq_off[i]) bad = 1; });
-    if (bad) { why = "offset arrays must be non-decreasing"; return CL_ERR_INVALID; }
-    if (q->qual_off[q->n_reads] > q->qual_off[0] && !q->qual) { why = "null quality array"; return CL_ERR_INVALID; }
-    return CL_OK;
-}
-
-static cl_status cl_site_attach_quals_impl(cl_ctx *c, const cl_site_quals *q, uint8_t min_base_quality)
-{
-    if (!c) return CL_ERR_INVALID;
-    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-    SiteResident &S = c->site;
-    if (!S.resident) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals without cl_site_upload");
-    if (S.filtered) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: the resident tile was uploaded by cl_site_pileup for its own site list; cl_site_upload gives a tile that serves a scan");
-    std::string why;
-    if (site_quals_check(q, why) != CL_OK) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: " + why);
-    if (q->n_reads != S.n) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: n_reads differs from the resident tile's");
-    if (q->seq_off[q->n_reads] != S.nbase) return fail(c, CL_ERR_INVALID, "cl_site_attach_quals: seq_off is not the one of the resident tile");
-    HIP_TRY(c, hipSetDevice(c->device));
-    drop_prefetch(c);                                        // the ring is needed below
-    S.attached = false;
-    StageTimer tmr;
-    const uint64_t n = S.n, n_words = (S.nbase + 63) / 64;
-    HIP_TRY(c, S.q_pass.reserve(n_words + 2)); HIP_TRY(c, S.q_flag.reserve(n + 1));
-    if (n_words) {
-        const cl_site_quals Q = *q;
-        cl_status rs = ring_start(c, reinterpret_cast<uint8_t *>(S.q_pass.p), n_words * 8, [Q, min_base_quality](uint64_t off, uint64_t len, uint8_t *out) {
-            // (a buffer is a whole number of words)
-            dut::site_pass_words(Q.n_reads, Q.seq_off, Q.qual_off, Q.qual, min_base_quality, off / 8, (off + len) / 8, reinterpret_cast<uint64_t *>(out));
-        }, PinRing::kPinBytes, PinRing::kCopyThreads);
-        if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
-        if (rs != CL_OK) return rs;
-    }
-    cl_status rs = CL_OK;
-    if (n && (rs = ring_copy(c, S.q_flag.p, q->flag, n * 2)) != CL_OK) return rs;
-    tmr.lap("site attach: pass bits + flags");
-    S.attached = true;
-    return CL_OK;
-}
-
-cl_status cl_site_attach_quals(cl_ctx *c, const cl_site_quals *quals, uint8_t min_base_quality)
-{
-    try { return cl_site_attach_quals_impl(c, quals, min_base_quality); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-cl_status cl_site_scan_ex(cl_ctx *c, uint8_t min_quality, uint32_t min_depth, const cl_scan_filter *filter, const uint8_t *ref_bases,
-                          uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out)
-{
-    try { return site_scan_impl<true>(c, min_quality, min_depth, filter, ref_bases, ref_len, start, end, out); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-cl_status cl_site_scan_counts_ex(cl_ctx *c, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)
-{
-    try { return site_scan_counts_impl<true>(c, min_quality, filter, start, end, counts); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words)
-{
-    try {
-        std::string why;
-        if (site_quals_check(quals, why) != CL_OK || (n_words && !words_out)) return CL_ERR_INVALID;
-        dut::site_pass_words(quals->n_reads, quals->seq_off, quals->qual_off, quals->qual, min_base_quality, 0, n_words, words_out);
-        return CL_OK;
-    }
-    catch (...) { return CL_ERR_NOMEM; }
-}
-
-cl_status cl_site_scan_stats(cl_ctx *c, double *kernel_ms, uint64_t *bytes)
-{
-    if (!c) return CL_ERR_INVALID;
-    if (kernel_ms) *kernel_ms = c->scan_ms;
-    if (bytes) *bytes = c->scan_bytes;
-    return CL_OK;
-}
-
-cl_status cl_site_pileup_stats(cl_ctx *c, double *kernel_ms, uint64_t *bytes)
-{
-    if (!c) return CL_ERR_INVALID;
-    if (kernel_ms) *kernel_ms = c->site_ms;
-    if (bytes) *bytes = c->site_bytes;
-    return CL_OK;
-}
-
-cl_status cl_site_upload(cl_ctx *c, uint32_t contig_len, uint64_t ref_len, const cl_site_tile *t)
-{
-    // no exception leaves the library through the C ABI
-    try { return cl_site_upload_impl(c, contig_len, ref_len, t); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-cl_status cl_site_run(cl_ctx *c, uint8_t min_quality, const uint32_t *sites, size_t n_sites, uint32_t *hist)
-{
-    try { return cl_site_run_impl(c, min_quality, sites, n_sites, hist, nullptr); }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
-cl_status cl_site_pileup(cl_ctx *c, uint8_t min_quality, uint32_t contig_len, uint64_t ref_len,
-                         const cl_site_tile *t, const uint32_t *sites, size_t n_sites, uint32_t *hist)
-{
-    if (!c || !t || (!sites && n_sites) || (!hist && n_sites)) return CL_ERR_INVALID;
-    if (n_sites == 0) return CL_OK;
-    try {
-        if (n_sites > 0x0FFFFFFFu) return fail(c, CL_ERR_RANGE, "too many sites");
-        // the sorted site list first (a millisecond): it says which reads need to travel at all
-        SitePrep prep;
-        site_prepare(sites, n_sites, prep);
-        SiteGather G;
-        static const bool no_filter = [] { const char *e = getenv("DUT_SITE_FILTER"); return e && *e == '0'; }();   // =0: the whole tile travels (A/B, tests)
-        if (!no_filter && t->n_reads && t->pos && t->mapq && t->cigar_off && t->seq_off) {
-            StageTimer tf;
-            site_filter(t, prep, min_quality, contig_len, G);
-            tf.lap("site pileup: reads that overlap a site");
-        }
-        cl_status s = cl_site_upload_impl(c, contig_len, ref_len, t, &G);
-        if (s != CL_OK) return s;
-        return cl_site_run_impl(c, min_quality, sites, n_sites, hist, &prep);
-    }
-    catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "out of memory"); }
-    catch (...) { return fail(c, CL_ERR_INVALID, "internal error"); }
-}
-
 
 } // extern "C"

@@ -277,7 +277,6 @@ struct PileupArgs {
 // (otherwise host_window_bounds raises kNeedDeep and the contig runs with DEEP = true: one
 // 32-bit counter per position).
 // ---------------------------------------------------------------------------------------------
-template <bool ORF>
 __device__ __forceinline__ uint32_t pass_bytes(uint32_t xw, uint32_t vm, const Opts &o)
 {
     // 0x01 in every byte of xw that is a valid position (vm) and passes the threshold (mod.rs:33).  v_lerp_u8 is a
@@ -290,12 +289,11 @@ __device__ __forceinline__ uint32_t pass_bytes(uint32_t xw, uint32_t vm, const O
 // 8-bit counters, two sets (reads alternate between the sets, a window handled this way is
 // touched by <= 510 reads, so no byte exceeds 255): positions 8e..8e+7 are one 8-byte entry
 // e = 2u + h of set `set`, stored at 2u + (h ^ ((u>>3)&1)); one ds_add_u64 covers 8 positions.
-template <bool ORF>
 __device__ __forceinline__ uint32_t apply_unit8(const Q16 &v, const uint4 vm, uint32_t u, uint32_t set_off,
                                                 unsigned long long *__restrict__ s_qc, const Opts &o)
 {
-    const uint32_t i0 = pass_bytes<ORF>(v.w[0], vm.x, o), i1 = pass_bytes<ORF>(v.w[1], vm.y, o);
-    const uint32_t i2 = pass_bytes<ORF>(v.w[2], vm.z, o), i3 = pass_bytes<ORF>(v.w[3], vm.w, o);
+    const uint32_t i0 = pass_bytes(v.w[0], vm.x, o), i1 = pass_bytes(v.w[1], vm.y, o);
+    const uint32_t i2 = pass_bytes(v.w[2], vm.z, o), i3 = pass_bytes(v.w[3], vm.w, o);
     uint32_t sq = __builtin_amdgcn_udot4(v.w[0], i0, 0u, false);      // += quality of every passing byte
     sq = __builtin_amdgcn_udot4(v.w[1], i1, sq, false);
     sq = __builtin_amdgcn_udot4(v.w[2], i2, sq, false);
@@ -308,7 +306,6 @@ __device__ __forceinline__ uint32_t apply_unit8(const Q16 &v, const uint4 vm, ui
 
 // 16-bit counters: positions 4e..4e+3 are one 8-byte entry e = 4u + jj, stored at
 // 4u + (jj ^ ((u>>2)&3)) so that lanes holding the same jj spread over all banks.
-template <bool ORF>
 __device__ __forceinline__ uint32_t apply_unit16(const Q16 &v, const uint4 vm, uint32_t u,
                                                  unsigned long long *__restrict__ s_qc, const Opts &o)
 {
@@ -318,7 +315,7 @@ __device__ __forceinline__ uint32_t apply_unit16(const Q16 &v, const uint4 vm, u
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
         const uint32_t xw = v.w[jj];
-        const uint32_t inc = pass_bytes<ORF>(xw, vmw[jj], o);
+        const uint32_t inc = pass_bytes(xw, vmw[jj], o);
         const uint32_t lo = __builtin_amdgcn_perm(0u, inc, 0x0c010c00u);   // bytes 0,1 -> 16-bit fields
         const uint32_t hi = __builtin_amdgcn_perm(0u, inc, 0x0c030c02u);   // bytes 2,3
         atomicAdd(&s_qc[e0 ^ (uint32_t)jj], ((unsigned long long)hi << 32) | lo);
@@ -327,7 +324,6 @@ __device__ __forceinline__ uint32_t apply_unit16(const Q16 &v, const uint4 vm, u
     return sq;
 }
 
-template <bool ORF>
 __device__ __forceinline__ uint32_t apply_unit32(const Q16 &v, const uint4 vm, uint32_t u,
                                                  uint32_t *__restrict__ s_qc, const Opts &o)
 {
@@ -336,7 +332,7 @@ __device__ __forceinline__ uint32_t apply_unit32(const Q16 &v, const uint4 vm, u
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
         const uint32_t xw = v.w[jj];
-        const uint32_t inc = pass_bytes<ORF>(xw, vmw[jj], o);
+        const uint32_t inc = pass_bytes(xw, vmw[jj], o);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if ((inc >> (8 * i)) & 1u) atomicAdd(&s_qc[(u << 4) + 4 * jj + i], 1u);
@@ -374,7 +370,7 @@ __device__ __forceinline__ SegView seg_view(uint2 d, uint32_t ql)
 #define CL_ABL(bit) false
 #endif
 
-template <int T, bool DEBUG, bool ORF, bool DEEP, int LONG>
+template <int T, bool DEBUG, bool DEEP, int LONG>
 __global__ __launch_bounds__(kBlock, DEEP ? 4 : CL_MINWAVES) void k_pileup(PileupArgs a)
 {
     constexpr int PER = T / kBlock;                 // positions per thread in the final phase
@@ -516,9 +512,9 @@ __global__ __launch_bounds__(kBlock, DEEP ? 4 : CL_MINWAVES) void k_pileup(Pileu
                     // a slot past the segment's end adds zeros: to the word of its own unit number, not (with the lanes
                     // beside it) to the word of the segment's last unit
                     const uint32_t un = u + 4u * j, ua = un < (uint32_t)(T / 16) ? un : (uint32_t)(T / 16) - 1u;
-                    if (MODE == 2) sq32 += apply_unit32<ORF>(v[j], vm, uu[j], s_qcw, a.o);
-                    else if (MODE == 0) sq32 += apply_unit8<ORF>(v[j], vm, ua, sv.set * (uint32_t)(T / 8), reinterpret_cast<unsigned long long *>(s_qcw), a.o);
-                    else sq32 += apply_unit16<ORF>(v[j], vm, uu[j], reinterpret_cast<unsigned long long *>(s_qcw), a.o);
+                    if (MODE == 2) sq32 += apply_unit32(v[j], vm, uu[j], s_qcw, a.o);
+                    else if (MODE == 0) sq32 += apply_unit8(v[j], vm, ua, sv.set * (uint32_t)(T / 8), reinterpret_cast<unsigned long long *>(s_qcw), a.o);
+                    else sq32 += apply_unit16(v[j], vm, uu[j], reinterpret_cast<unsigned long long *>(s_qcw), a.o);
                 }
             }
         }
@@ -617,9 +613,9 @@ __global__ __launch_bounds__(kBlock, DEEP ? 4 : CL_MINWAVES) void k_pileup(Pileu
                                 const uint32_t ve = (trel - ps) < 16u ? (trel - ps) : 16u;
                                 const uint4 ms = s_mstart[vs], me = s_mend[ve];
                                 const uint4 vm = make_uint4(ms.x & me.x, ms.y & me.y, ms.z & me.z, ms.w & me.w);
-                                if (DEEP) sq32 += apply_unit32<ORF>(v[j][h], vm, u, s_qcw, a.o);
-                                else if (mode8) sq32 += apply_unit8<ORF>(v[j][h], vm, u, set_off, reinterpret_cast<unsigned long long *>(s_qcw), a.o);
-                                else sq32 += apply_unit16<ORF>(v[j][h], vm, u, reinterpret_cast<unsigned long long *>(s_qcw), a.o);
+                                if (DEEP) sq32 += apply_unit32(v[j][h], vm, u, s_qcw, a.o);
+                                else if (mode8) sq32 += apply_unit8(v[j][h], vm, u, set_off, reinterpret_cast<unsigned long long *>(s_qcw), a.o);
+                                else sq32 += apply_unit16(v[j][h], vm, u, reinterpret_cast<unsigned long long *>(s_qcw), a.o);
                             }
                         }
                     }
@@ -1541,124 +1537,5 @@ __global__ __launch_bounds__(kBlock) void k_rle_write(const uint16_t *__restrict
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// config 5: site-list pileup (src/haplogroup/caller.rs:62-152): for every M/=/X base of a read with
-// mapq >= min_quality whose 1-based position is a listed site, hist[site][4-bit base code] += 1.
-//
-// sorted_pos0 / sorted_idx: the sites sorted by 0-based position and their original indices; bucket[b]: index of
-// the first sorted site with position >= 256*b.  One packed record per read (built on the host per call, like
-// ReadRec): pos, CIGAR offset, low half of the base offset (the full offset = the block's 64-bit base + the 32-bit
-// difference), mapq | n_cigar << 8 | n_bases << 16 with 255 / 0xFFFF meaning "the next record's offsets".
-//
-// A workgroup takes 256 consecutive reads.  A thread walks its read's first four CIGAR words (one 16-byte load) for
-// the reference span and leaves at once when no site lies inside it (three reads in five at one site per ~300
-// bases: no per-operation walk, no base is touched); hits go to a histogram of the workgroup's own sites in LDS
-// (the reads are sorted, so they share a handful of sites) which is added to the global one once at the end --
-// hits outside that range (unsorted input, a very long read) add to the global histogram directly.
-// ---------------------------------------------------------------------------------------------
-struct __attribute__((aligned(16))) SiteRec {
-    int32_t  pos;
-    uint32_t cigar_off;
-    uint32_t seq_lo;
-    uint32_t meta;
-};
-constexpr int kSiteLds = 64;            // sites a workgroup privatises
-
-struct SiteArgs {
-    const SiteRec *rec;                 // n + 1
-    const unsigned long long *seq_base; // per workgroup of kBlock reads: base offset (in bases) of its first read
-    const uint32_t *cigar;              // padded by 8 words
-    const uint8_t  *seq4;
-    uint32_t n;
-    uint32_t min_quality, contig_len;
-    unsigned long long ref_len;
-    const uint32_t *sorted_pos0, *sorted_idx, *bucket;
-    uint32_t n_buckets, n_sites;
-    uint32_t *hist;
-};
-
-__global__ __launch_bounds__(kBlock) void k_site_pileup(SiteArgs a)
-{
-    __shared__ uint32_t s_hist[kSiteLds * 16];
-    __shared__ uint32_t s_first;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t r0 = blockIdx.x * kBlock;
-    for (uint32_t i = tid; i < (uint32_t)kSiteLds * 16u; i += kBlock) s_hist[i] = 0;
-    auto first_site_at = [&](unsigned long long x) {             // first sorted site with position >= x
-        const unsigned long long bx = x >> 8;
-        uint32_t lo = bx < a.n_buckets ? a.bucket[bx] : a.n_sites;
-        while (lo < a.n_sites && a.sorted_pos0[lo] < x) ++lo;
-        return lo;
-    };
-    if (tid == 0) {
-        const int32_t p0 = a.rec[r0].pos;
-        s_first = first_site_at(p0 < 0 ? 0ull : (unsigned long long)p0);
-    }
-    __syncthreads();
-    const uint32_t first = s_first;
-    const uint32_t r = r0 + tid;
-    if (r < a.n) {
-        const uint4 rr = *reinterpret_cast<const uint4 *>(a.rec + r);
-        const uint32_t mq = rr.w & 255u;
-        // fetch("chr:1-len"), caller.rs:33-36; the mapping-quality gate, caller.rs:80
-        if ((uint32_t)rr.x < a.contig_len && mq >= a.min_quality) {
-            uint32_t k = rr.y, k1 = k + ((rr.w >> 8) & 255u);
-            unsigned long long slen = rr.w >> 16;
-            if (((rr.w >> 8) & 255u) == 255u || slen == 0xFFFFull) {
-                const uint4 nx = *reinterpret_cast<const uint4 *>(a.rec + r + 1);
-                k1 = nx.y; slen = (uint32_t)(nx.z - rr.z);
-            }
-            const unsigned long long base = a.seq_base[blockIdx.x];
-            const unsigned long long s0 = base + (uint32_t)(rr.z - (uint32_t)base);
-            Q16 c4;
-            __builtin_memcpy(&c4, a.cigar + k, 16);
-            const uint32_t n = k1 - k;
-            unsigned long long x = (uint32_t)rr.x, reflen = 0;
-#pragma unroll
-            for (uint32_t d = 0; d < 4u; ++d) {
-                const uint32_t c = d < n ? c4.w[d] : 5u;
-                reflen += ((0x18Du >> (c & 15u)) & 1u) ? (c >> 4) : 0u;
-            }
-            for (uint32_t kk = k + 4u; kk < k1; ++kk) {
-                const uint32_t c = a.cigar[kk];
-                reflen += ((0x18Du >> (c & 15u)) & 1u) ? (c >> 4) : 0u;
-            }
-            uint32_t lo = first_site_at(x);
-            if (lo < a.n_sites && a.sorted_pos0[lo] < x + reflen) {      // some site inside the read's span: walk it
-                unsigned long long y = 0;
-                for (uint32_t kk = k; kk < k1; ++kk) {
-                    const uint32_t d = kk - k;
-                    const uint32_t c = d == 0 ? c4.w[0] : d == 1 ? c4.w[1] : d == 2 ? c4.w[2] : d == 3 ? c4.w[3] : a.cigar[kk];
-                    const uint32_t op = c & 15u, l = c >> 4;
-                    if (op_match(op)) {
-                        while (lo < a.n_sites && a.sorted_pos0[lo] < x) ++lo;
-                        for (; lo < a.n_sites && a.sorted_pos0[lo] < x + l; ++lo) {
-                            const unsigned long long p = a.sorted_pos0[lo];
-                            const unsigned long long qi = y + (p - x);
-                            if (qi < slen && p < a.ref_len) {           // caller.rs:105,110-113
-                                const unsigned long long bi = s0 + qi;
-                                const uint32_t byte = a.seq4[bi >> 1];
-                                const uint32_t code = (bi & 1ull) ? (byte & 15u) : (byte >> 4);
-                                const uint32_t slot = lo - first;       // below `first`: wraps, goes to the global one
-                                if (slot < (uint32_t)kSiteLds) atomicAdd(&s_hist[slot * 16u + code], 1u);
-                                else atomicAdd(&a.hist[(unsigned long long)a.sorted_idx[lo] * 16ull + code], 1u);
-                            }
-                        }
-                        x += l; y += l;
-                    } else if (op_del(op)) {
-                        x += l;
-                    } else if (op_ins(op)) {
-                        y += l;
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < (uint32_t)kSiteLds * 16u; i += kBlock) {
-        const uint32_t v = s_hist[i], si = first + (i >> 4);
-        if (v && si < a.n_sites) atomicAdd(&a.hist[(unsigned long long)a.sorted_idx[si] * 16ull + (i & 15u)], v);
-    }
-}
-
 } // namespace clk
+

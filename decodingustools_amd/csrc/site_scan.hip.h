@@ -1,7 +1,7 @@
 // site_scan.hip.h -- the dense form of the site pileup (config 5): base counts and SNV calls at EVERY position of a
 // range of the resident site tile (cl_site_upload), instead of at the sites of a list.
 //
-// k_site_pileup (kernels.hip.h) is built for a sparse list: one thread per read, a read leaves at once when no site
+// k_site_pileup (site_engine.hip.h) is built for a sparse list: one thread per read, a read leaves at once when no site
 // lies in its span, 64 sites per workgroup in LDS.  With a site at every base none of that helps, and the histogram
 // (64 bytes per position) has to cross HBM and the link.  Here a workgroup owns a window of kScanWin reference positions:
 // it counts the bases of every read over the window in LDS, applies the calling rule of caller.rs:132-149 there and

@@ -341,3 +341,55 @@ def test_one_tile_past_2_32_bases_through_all_three_kernels():
             assert np.array_equal(want, oracle.site_pileup(1, mq, L, ref, tile2, sites)["hist"]), ("the two references differ", mq)
             same(eng.site_pileup(mq, L, L, tile2, sites), want, sites, ("site_pileup, gathered", mq))
             assert travelled(eng, sites) < tile_bytes(tile2) - (0 if mq == 0 else I.MARK // 4)
+
+
+# ---- the statistics of the caller's own site pileup survive a scan that runs one ------------------------------------------
+class SettledByThePileup:
+    """A small tile for site_pileup and the same reads with an ambiguity code (R) planted in every plain read over three
+    positions, which the unfiltered scan can only settle through the site pileup's 16-code histogram; what the references
+    say of both.  The conditions on the input are asserted here, from the references alone."""
+
+    def __init__(self):
+        L = self.L = 4000
+        ref = self.ref = synth.make_reference(L, 71)
+        rec = self.rec = synth.short_read_contig(L, 15, 72, with_seq=True, ref=ref)
+        assert 200 <= rec.n <= 600 and S.no_escape(rec) and not (rec.seq_off & np.uint64(1)).any()
+        self.sites = np.array([0, 7, 300, 301, 1024, 1999, 2000, 2500, 3100, 3500, 3990, L + 5], np.uint32)
+        keep = S.kept(L, rec, 0, self.sites)
+        assert 0 < int(keep.sum()) < rec.n
+        # (whole bytes per read: what the one-call form gathers is the tile of the kept reads)
+        self.bytes = tile_bytes(S.permuted(rec, np.flatnonzero(keep))) + 8 * int(np.count_nonzero(self.sites)) + 64 * self.sites.shape[0]
+        self.want = S.hist_at_sites(L, L, rec, 0, self.sites)
+        assert np.array_equal(self.want, oracle.site_pileup(1, 0, L, ref, rec, self.sites)["hist"]) and self.want.any()
+        # the planted tile
+        planted = self.planted = np.array([700, 1800, 2900])
+        codes = scan_ref.unpack_seq4(rec.seq4, int(rec.seq_off[-1])).copy()
+        plain = (np.diff(rec.cigar_off.astype(np.int64)) == 1) & ((rec.cigar[rec.cigar_off[:-1]] & 15) == 0)
+        for p in planted:
+            r = np.flatnonzero(plain & (rec.pos <= p) & (p < rec.pos.astype(np.int64) + 150))
+            codes[rec.seq_off[r].astype(np.int64) + (p - rec.pos[r])] = 5
+        amb = self.amb = S.permuted(rec, np.arange(rec.n))
+        amb.seq4 = S.pack_seq4(codes)
+        h = oracle.site_pileup(1, 0, L, ref, amb, (planted + 1).astype(np.uint32))["hist"].astype(np.int64)
+        depth = h.sum(1)
+        assert (depth >= 5).all() and (10 * h[:, 5] >= 7 * depth).all(), h.tolist()    # R holds 7/10: neither A, C, G, T nor N
+        self.exp = scan_ref.reduce(np.stack([S.hist_all(L, L, amb, 0), np.zeros((L, 16), np.uint32)]), ref, L, 1, 0, L)
+        clean = scan_ref.reduce(np.stack([S.hist_all(L, L, rec, 0), np.zeros((L, 16), np.uint32)]), ref, L, 1, 0, L)
+        assert self.exp["uncomparable"] == clean["uncomparable"] + planted.shape[0]
+
+
+def test_a_scan_settled_by_the_site_pileup_leaves_the_callers_pileup_stats():
+    """cl_site_scan settles the positions its counter planes cannot classify with a run of the site pileup of its own
+    (site_scan_hist16).  site_pileup_stats keeps speaking of the caller's last site_pileup all the same -- its kernel time
+    and its algorithmic bytes, both exactly -- and site_scan_stats of the scan."""
+    I = SettledByThePileup()
+    with Engine(CallableOptions(), 0) as eng:
+        same(eng.site_pileup(0, I.L, I.L, I.rec, I.sites), I.want, I.sites, "site_pileup")
+        ms0, bytes0 = eng.site_pileup_stats()
+        assert ms0 > 0 and bytes0 == I.bytes, (ms0, bytes0, I.bytes)
+        eng.site_upload(I.L, I.L, I.amb)
+        res = eng.site_scan(0, 1, I.ref)
+        same_scan(res, I.exp, "site_scan over the planted tile")
+        assert res.uncomparable + res.mixed > 0 and res.uncomparable >= I.planted.shape[0]     # the settling path was taken
+        assert eng.site_pileup_stats() == (ms0, bytes0)
+        assert eng.site_scan_stats()[0] > 0
