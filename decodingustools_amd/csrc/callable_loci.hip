@@ -28,10 +28,43 @@ constexpr uint32_t kT = CL_WINDOW;
 struct StagingSet {
     RawVec<uint8_t> ref, mapq;
     RawVec<int32_t> pos;
-    RawVec<uint32_t> cigar_off, cigar, end, ck_x, ck_y, rec_cnt, rec_of;
-    RawVec<unsigned long long> qual_off, rb_off;
-    RawVec<uint64_t> qbits;
+    RawVec<uint32_t> cigar_off, cigar;
+    RawVec<unsigned long long> qual_off;
+    // the index over the CIGARs, built by the one host walk that validates a tile (cl_push_reads): every read's end,
+    // and for reads with more than kLongOps operations the (reference, query) position before every 64th operation
+    // of the contig's CIGAR array
+    RawVec<uint32_t> end, ck_x, ck_y;
+    // per read, from the same walk: how many records the record forms get for it (gen_read_recs); their prefix sums
+    // are taken at upload: read i's records are rec[rec_of[i] .. rec_of[i + 1])
+    RawVec<uint32_t> rec_cnt, rec_of;
+    // pass-bit form (the default): bit g = quality byte g of the contig passes min_base_quality (mod.rs:33), taken in
+    // cl_push_reads' walk
+    RawVec<uint64_t> qbits;               // the reads' bit strings (reference order; pass_rows.h), word-aligned per read
+    RawVec<unsigned long long> rb_off;    // n + 1 word offsets into qbits (| dut::kRowSparse)
 };
+// Everything a context stages of its contig between cl_contig_begin and cl_contig_upload: the pooled arrays and the few
+// that are too small to pool.  A new array is added to clear() -- and to swap_pooled() if it is pooled --, nowhere else.
+namespace {
+struct Staging : StagingSet {
+    std::vector<uint8_t> qual;            // quality bytes of small tiles, not yet on the device (byte forms)
+    // reads whose reference span exceeds kWideSpan (ascending read index = ascending position)
+    std::vector<uint32_t> wide_idx;
+    std::vector<int32_t> wide_pos;
+    std::vector<uint32_t> wide_rec_of;    // prefix sums of the wide reads' record counts (n_wide + 1 entries; built at upload)
+    RawVec<uint32_t> sc_off, sc;          // pass-bit form: the CIGARs of the sparse reads (n + 1 offsets)
+    void swap_pooled(StagingSet &o)
+    {
+        ref.swap(o.ref); mapq.swap(o.mapq); pos.swap(o.pos); cigar_off.swap(o.cigar_off); cigar.swap(o.cigar); qual_off.swap(o.qual_off);
+        end.swap(o.end); ck_x.swap(o.ck_x); ck_y.swap(o.ck_y); rec_cnt.swap(o.rec_cnt); rec_of.swap(o.rec_of); qbits.swap(o.qbits); rb_off.swap(o.rb_off);
+    }
+    void clear()                          // (sizes only, the memory stays; but qual gives its memory back: only contigs of small tiles fill it)
+    {
+        ref.clear(); mapq.clear(); pos.clear(); cigar_off.clear(); cigar.clear(); qual_off.clear();
+        end.clear(); ck_x.clear(); ck_y.clear(); rec_cnt.clear(); rec_of.clear(); qbits.clear(); rb_off.clear();
+        std::vector<uint8_t>().swap(qual); wide_idx.clear(); wide_pos.clear(); wide_rec_of.clear(); sc_off.clear(); sc.clear();
+    }
+};
+} // namespace
 constexpr size_t kStagingSets = 2;
 static std::mutex g_staging_mu;
 static std::vector<std::unique_ptr<StagingSet>> g_staging;
@@ -48,37 +81,14 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     bool bits = true;                // the pass-bit form (default); DUT_QUAL_FORM=bytes at cl_create: the byte forms
     int form = 0;                    // the form of k_pileup the resident contig gets (pick_form, at upload)
     uint32_t tune_ablate = 0;        // CL_TUNING builds: CL_ABLATE, read once at cl_create
-    bool has_long = false;           // some read has more than kLongOps CIGAR ops (its checkpoints are in h_ck_x / h_ck_y)
+    bool has_long = false;           // some read has more than kLongOps CIGAR ops (its checkpoints are in hs.ck_x / hs.ck_y)
     int32_t tid = 0;
     uint32_t contig_len = 0;
-    RawVec<uint8_t> h_ref;
-    RawVec<int32_t> h_pos;
-    RawVec<uint8_t> h_mapq;
-    RawVec<uint32_t> h_cigar_off;
-    RawVec<uint32_t> h_cigar;
-    RawVec<unsigned long long> h_qual_off;
-    std::vector<uint8_t> h_qual;     // quality bytes of small tiles, not yet on the device
-    uint64_t q_dev = 0;              // quality bytes of this contig that already are (d_qual + kQualPad ..)
-    // reads whose reference span exceeds kWideSpan (ascending read index = ascending position)
-    std::vector<uint32_t> h_wide_idx;
-    // short-read form: read i's records are rec[h_rec_of[i] .. h_rec_of[i + 1]) (built at upload, gen_read_recs)
-    RawVec<uint32_t> h_rec_of;            // (pooled with the other staging arrays: 4 bytes per read, written at every upload)
-    std::vector<uint32_t> h_wide_rec_of;   // prefix sums of the wide reads' record counts (n_wide + 1 entries)
+    Staging hs;                      // the staged arrays themselves
+    uint64_t q_dev = 0;              // quality bytes of this contig that already are on the device (d_qual + kQualPad ..)
     uint32_t n_rec = 0;
-    std::vector<int32_t> h_wide_pos;
-    // the index over the CIGARs, built by the one host walk that validates a tile (cl_push_reads): every read's end,
-    // and for reads with more than kLongOps operations the (reference, query) position before every 64th operation
-    // of the contig's CIGAR array
-    RawVec<uint32_t> h_end, h_ck_x, h_ck_y;
-    // per read, from the same walk: how many records the record forms get for it (gen_read_recs); their prefix sums
-    // are taken at upload
-    RawVec<uint32_t> h_rec_cnt;
-    // pass-bit form (the default): bit g = quality byte g of the contig passes min_base_quality (mod.rs:33), taken in
-    // cl_push_reads' walk; and, from the same walk, the sum of the passing qualities over the M/=/X bases of the reads
+    // from cl_push_reads' walk in the pass-bit form: the sum of the passing qualities over the M/=/X bases of the reads
     // with mapq >= min_mapping_quality (contig_profiler.rs:65-70: summed_baseq is per-read separable)
-    RawVec<uint64_t> h_qbits;        // the reads' bit strings (reference order; pass_rows.h), word-aligned per read
-    RawVec<unsigned long long> h_rb_off;   // n + 1 word offsets into h_qbits (| dut::kRowSparse)
-    RawVec<uint32_t> h_sc_off, h_sc; // the CIGARs of the sparse reads (n + 1 offsets)
     uint64_t host_sum_q = 0;         // of the contig being pushed
     // ... and the reads' other separable sums (contig_profiler.rs:74, 79-82): reference spans of the reads
     // the pileup holds (-> summed_coverage) and mapq x span over those with mapq >= min_mapping_quality (-> summed_mapq)
@@ -146,32 +156,25 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
 static SiteCtx *site_ctx(cl_ctx *c) { return c; }
 static void join_prealloc(cl_ctx *c) { if (c->prealloc.joinable()) c->prealloc.join(); }   // (cl_contig_reserve's helper thread)
 
-static void swap_staging(cl_ctx *c, StagingSet &o)
-{
-    c->h_ref.swap(o.ref); c->h_mapq.swap(o.mapq); c->h_pos.swap(o.pos); c->h_cigar_off.swap(o.cigar_off);
-    c->h_cigar.swap(o.cigar); c->h_end.swap(o.end); c->h_ck_x.swap(o.ck_x); c->h_ck_y.swap(o.ck_y); c->h_qual_off.swap(o.qual_off);
-    c->h_qbits.swap(o.qbits); c->h_rec_cnt.swap(o.rec_cnt); c->h_rb_off.swap(o.rb_off); c->h_rec_of.swap(o.rec_of);
-}
 // a context without staging memory of its own takes a pooled set (cl_contig_begin) ...
 static void take_staging(cl_ctx *c)
 {
-    if (c->h_pos.cap || c->h_cigar.cap || c->h_qual_off.cap || c->h_qbits.cap) return;
+    if (c->hs.pos.cap || c->hs.cigar.cap || c->hs.qual_off.cap || c->hs.qbits.cap) return;
     std::unique_ptr<StagingSet> s;
     {
         std::lock_guard<std::mutex> g(g_staging_mu);
         if (g_staging.empty()) return;
         s = std::move(g_staging.back()); g_staging.pop_back();
     }
-    swap_staging(c, *s);                                   // what the context had (nothing) is freed with s
+    c->hs.swap_pooled(*s);                                 // what the context had (nothing) is freed with s
 }
-// ... and gives its set back once the contig is on the device (cl_contig_upload); a full pool keeps the larger sets
+// ... and gives its set back, empty, once the contig is on the device (cl_contig_upload); a full pool keeps the larger sets
 static void give_staging(cl_ctx *c)
 {
+    c->hs.clear();
     std::unique_ptr<StagingSet> s(new (std::nothrow) StagingSet());
     if (!s) return;
-    swap_staging(c, *s);
-    s->ref.clear(); s->mapq.clear(); s->pos.clear(); s->cigar_off.clear(); s->cigar.clear(); s->end.clear();
-    s->ck_x.clear(); s->ck_y.clear(); s->qual_off.clear(); s->qbits.clear(); s->rec_cnt.clear(); s->rb_off.clear(); s->rec_of.clear();
+    c->hs.swap_pooled(*s);
     std::lock_guard<std::mutex> g(g_staging_mu);
     if (g_staging.size() < kStagingSets) { g_staging.push_back(std::move(s)); return; }
     size_t small = 0;
@@ -353,25 +356,46 @@ uint64_t rec_chunk_bytes()
     return n;
 }
 
-// h_rec_of: the prefix sums of the reads' record counts (counted by cl_push_reads' walk)
+// The fill of ring_start for an array of n_rec records (heads, ReadRec) plus a zeroed padding record, built in place by
+// record number: read i of n owns the records [ro[i], ro[i + 1]).  A pinned buffer covers a range [j0, j1) of record
+// numbers; the read that holds j0 is found by binary search, and emit(i, put) is called for every read with a record in
+// the range: put(k, rec) stores the read's k-th record if the buffer holds it.
+template <class Rec, class Emit>
+auto rec_range_fill(const uint32_t *ro, size_t n, uint32_t n_rec, Emit emit)
+{
+    return [ro, n, n_rec, emit](uint64_t off, uint64_t len, uint8_t *out) {
+        Rec *o = reinterpret_cast<Rec *>(out);
+        const uint64_t j0 = off / sizeof(Rec), j1 = (off + len) / sizeof(Rec);
+        if (j1 > n_rec) memset(static_cast<void *>(o + (std::max<uint64_t>(n_rec, j0) - j0)), 0, (j1 - std::max<uint64_t>(n_rec, j0)) * sizeof(Rec));   // the padding record
+        if (j0 >= n_rec) return;
+        // the read that holds record j0: the last one whose range starts at or before it
+        size_t i = (size_t)(std::upper_bound(ro, ro + n + 1, (uint32_t)j0) - ro) - 1;
+        for (; i < n && ro[i] < j1; ++i) {
+            const uint64_t jb = ro[i];
+            emit(i, [&](uint32_t k, const Rec &r) { const uint64_t j = jb + k; if (j >= j0 && j < j1) o[j - j0] = r; });
+        }
+    };
+}
+
+// hs.rec_of: the prefix sums of the reads' record counts (counted by cl_push_reads' walk)
 cl_status build_rec_index(cl_ctx *c)
 {
-    const size_t n = c->h_pos.size();
-    RawVec<uint32_t> &ro = c->h_rec_of;
+    const size_t n = c->hs.pos.size();
+    RawVec<uint32_t> &ro = c->hs.rec_of;
     ro.resize(n + 1);
     ro[0] = 0u;
     if (!c->rec_counted) {
         // some tile looked like long reads and skipped the count, yet the contig as a whole gets the short-read form
-        const int32_t *hp = c->h_pos.data(); const uint8_t *hm = c->h_mapq.data(); const uint32_t *he = c->h_end.data();
-        const uint32_t *hc = c->h_cigar_off.data(), *hcig = c->h_cigar.data(); const unsigned long long *hq = c->h_qual_off.data();
+        const int32_t *hp = c->hs.pos.data(); const uint8_t *hm = c->hs.mapq.data(); const uint32_t *he = c->hs.end.data();
+        const uint32_t *hc = c->hs.cigar_off.data(), *hcig = c->hs.cigar.data(); const unsigned long long *hq = c->hs.qual_off.data();
         const uint32_t min_mapq = c->opt.min_mapping_quality;
-        uint32_t *cw = c->h_rec_cnt.data();
+        uint32_t *cw = c->hs.rec_cnt.data();
         dut::parallel_for(n, dut::grain_for(n, 65536), [&](size_t i) {
             cw[i] = gen_read_recs(hp[i], he[i], hm[i], min_mapq, hcig + hc[i], hc[i + 1] - hc[i], 0ull, hq[i + 1] - hq[i], [](uint32_t, const ReadRec &) {});
         });
         c->rec_counted = true;
     }
-    const uint32_t *cnt = c->h_rec_cnt.data();
+    const uint32_t *cnt = c->hs.rec_cnt.data();
     const size_t grain = dut::grain_for(n, 262144), nchunk = n ? (n + grain - 1) / grain : 0;
     std::vector<uint64_t> tot(nchunk + 1, 0);
     dut::parallel_for(nchunk, 1, [&](size_t k) {
@@ -396,8 +420,8 @@ cl_status build_rec_index(cl_ctx *c)
 // device function in front of every pileup launch; the parity tests hold the results of this one against the oracle).
 void host_window_bounds(const cl_ctx *c, std::vector<WinMeta> &win, uint32_t &flags)
 {
-    const uint32_t n = (uint32_t)c->h_pos.size(), n_wide = (uint32_t)c->h_wide_pos.size();
-    const int32_t *pos = c->h_pos.data(), *wpos = c->h_wide_pos.data();
+    const uint32_t n = (uint32_t)c->hs.pos.size(), n_wide = (uint32_t)c->hs.wide_pos.size();
+    const int32_t *pos = c->hs.pos.data(), *wpos = c->hs.wide_pos.data();
     auto lb = [](const int32_t *p, uint32_t cnt, long long key) {
         return (uint32_t)(std::lower_bound(p, p + cnt, key, [](int32_t v, long long k) { return (long long)v < k; }) - p);
     };
@@ -416,8 +440,8 @@ void host_window_bounds(const cl_ctx *c, std::vector<WinMeta> &win, uint32_t &fl
         m.q0 = 0; m.rlo = 0; m.rn = 0;
         if (!c->bits) {
             // the byte forms of k_pileup address the quality bytes of a window with 32-bit offsets
-            const uint32_t first = m.wn ? c->h_wide_idx[m.wlo] : m.lo;      // lo <= n: the offsets array has n + 1 entries
-            const unsigned long long qf = c->h_qual_off[first], qh = c->h_qual_off[m.hi];
+            const uint32_t first = m.wn ? c->hs.wide_idx[m.wlo] : m.lo;      // lo <= n: the offsets array has n + 1 entries
+            const unsigned long long qf = c->hs.qual_off[first], qh = c->hs.qual_off[m.hi];
             m.q0 = qf;
             if (m.hi > first && qh - qf > 0xFFFF0000ull) fl.fetch_or(kErrRange);
         }
@@ -437,7 +461,7 @@ void finish_windows(const cl_ctx *c, const std::vector<uint32_t> &wro_v, std::ve
     dut::parallel_for(c->n_win, 4096, [&](size_t w) {
         WinMeta &m = win[w];
         if (c->form != 2) {
-            const uint32_t *ro = c->h_rec_of.data();
+            const uint32_t *ro = c->hs.rec_of.data();
             m.lo = ro[m.lo]; m.hi = ro[m.hi];
             const uint32_t w1 = wro[m.wlo + m.wn];
             m.wlo = wro[m.wlo]; m.wn = w1 - m.wlo;
@@ -456,9 +480,7 @@ void finish_windows(const cl_ctx *c, const std::vector<uint32_t> &wro_v, std::ve
 // (the 64-operation checkpoints of cl_push_reads' walk).  Reads below min_mapping_quality never enter (mod.rs:25).
 // A piece = {x, y}: x + 16 u = the byte offset of unit u's qualities from the window's quality base;
 // y = start | end - 1 << 11 | (read & 1) << 29 | valid << 31; it covers the unit of its start and at most the next one.
-// The pieces are written straight into the pinned buffers of the staging ring and leave for HBM as a buffer fills: the
-// table exists nowhere in host memory.  Buffers are placed in the device array in the order they fill (a window only
-// needs its own pieces contiguous: its record holds their absolute index).
+// The pieces go to HBM through stream_windows<RunTableForm>, below.
 struct RunCur { uint32_t k, k1, x, y, qlen, flags; unsigned long long q0; };
 
 // One window: the cursors of `act` emit their pieces inside [W, W + kT) to out[0, cap) and move on; finished reads
@@ -525,145 +547,51 @@ size_t run_chunk_entries()
     return n;
 }
 
-cl_status stream_run_table(cl_ctx *c, std::vector<WinMeta> &win)
+// host views of the staged contig for the run table's sweep (what dut::RowReads is for the rows')
+struct RunReads {
+    const int32_t *pos;
+    const uint8_t *mapq;
+    const uint32_t *end, *coff, *cig, *ckx, *cky;
+    const unsigned long long *qoff;
+    uint32_t min_mapq;
+    uint32_t inject_read;                         // DUT_FAULT_INJECT=runtab: the read whose quality offset is moved out of range
+};
+
+RunReads run_reads(const cl_ctx *c)
 {
-    const uint32_t n_win = c->n_win;
-    const int32_t *pos = c->h_pos.data();
-    const uint8_t *mapq = c->h_mapq.data();
-    const uint32_t *end = c->h_end.data(), *coff = c->h_cigar_off.data(), *cig = c->h_cigar.data();
-    const uint32_t *ckx = c->h_ck_x.data(), *cky = c->h_ck_y.data(), *wide_idx = c->h_wide_idx.data();
-    const unsigned long long *qoff = c->h_qual_off.data();
-    const uint32_t min_mapq = c->opt.min_mapping_quality;
-    c->n_runtab = 0;
-    if (n_win == 0) return CL_OK;
-    cl_status s = ensure_pins(c);
-    if (s != CL_OK) return s;
-    // (as many walkers as the staging ring has buffer pairs -- DUT_COPY_THREADS, 8 by default --: pinning 16 MB more per
-    // further walker costs more than the walker saves: 73 ms with 16 walkers against 23 ms with 8 at chr21 30x)
-    const int nt = std::max(1, std::min<int>(std::max(1, c->ring->slots), dut::worker_threads()));
-    // tasks: several per thread so that uneven depth evens out, not so short that the range-start walks show
-    const size_t per = std::max<size_t>(16, (size_t)n_win / (8 * (size_t)nt) + 1);
-    const size_t ntasks = ((size_t)n_win + per - 1) / per;
-    const size_t capE = run_chunk_entries();
-    const unsigned long long qend = c->n_qual + 2ull * kQualPad;
-    std::atomic<bool> oor{false};
-    const bool inject = fault_injected("runtab");                // test hook: one read's quality offset is moved out of range
-    // the device array: an estimate first (a piece per ~12 aligned bases); a contig that needs more tells how much
-    uint64_t want = c->n_qual / 12 + (uint64_t)n_win * 8 + 65536;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, c->d_runtab.reserve(want));
-        uint2 *const d_tab = c->d_runtab.p;
-        const uint64_t dev_cap = c->d_runtab.cap;
-        std::atomic<uint64_t> dev_next{0};
-        std::atomic<size_t> next_task{0};
-        PinRing *R = c->ring.get();
-        R->acquire(static_cast<EngineBase *>(c));                // (the identity ring_finish releases it under)
-        c->ring_held = true;
-        if (!R->ensure_slots(nt)) { (void)ring_finish(c); return fail(c, CL_ERR_DEVICE, "cannot extend the pinned staging ring (hipHostMalloc)"); }
-        for (int t = 0; t < PinRing::kCopyThreads; ++t) c->copy_err[t] = hipSuccess;
-        c->crew_busy = true;
-        R->crew.start(nt, [&](int t) {
-                hipError_t err = hipSetDevice(c->device);
-                int kb = 0;                                                  // buffers this thread has sent
-                auto cur_buf = [&]() { return reinterpret_cast<uint2 *>(R->pin[t][kb & 1]); };
-                auto send = [&](uint2 *dst, size_t cnt) {                    // the current buffer leaves; on to the other one
-                    if (err != hipSuccess) return;
-                    err = hipMemcpyAsync(dst, cur_buf(), cnt * sizeof(uint2), hipMemcpyHostToDevice, R->copy_stream[t]);
-                    if (err == hipSuccess) err = hipEventRecord(R->pin_ev[t][kb & 1], R->copy_stream[t]);
-                    ++kb;
-                    if (kb >= 2 && err == hipSuccess) err = hipEventSynchronize(R->pin_ev[t][kb & 1]);   // its previous transfer is done
-                };
-                std::vector<RunCur> act, save;
-                std::vector<uint32_t> in_buf;                                // windows whose pieces lie in the current buffer
-                RawVec<uint2> big;
-                size_t used = 0;
-                auto flush = [&]() {
-                    if (!used) return;
-                    const uint64_t off = dev_next.fetch_add(used);
-                    if (off + used <= dev_cap) send(d_tab + off, used);      // else: the array is too small, only the total counts now
-                    for (uint32_t w : in_buf) win[w].rlo += (uint32_t)off;
-                    in_buf.clear(); used = 0;
-                };
-                auto enter = [&](uint32_t r, uint32_t W) {                   // a read that covers positions at or after W
-                    if (mapq[r] < min_mapq) return;
-                    RunCur cu;
-                    cu.k = coff[r]; cu.k1 = coff[r + 1]; cu.x = (uint32_t)pos[r]; cu.y = 0;
-                    if (cu.k >= cu.k1 || end[r] <= W) return;
-                    const unsigned long long ql = qoff[r + 1] - qoff[r];
-                    cu.qlen = ql > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ql;
-                    cu.q0 = qoff[r]; cu.flags = ((r & 1u) << 29) | 0x80000000u;
-                    if (inject && r == c->n_reads / 2u) cu.q0 += 0x7FFFFFF0ull;
-                    if (cu.k1 - cu.k > kLongOps && cu.x < W) {               // the last checkpoint at or before W
-                        const uint32_t jlo = (cu.k + 63u) >> 6, jhi = (cu.k1 - 1u) >> 6;
-                        if (jlo <= jhi && ckx[jlo] <= W) {
-                            uint32_t lo_j = jlo, hi_j = jhi;
-                            while (lo_j < hi_j) {
-                                const uint32_t mid = lo_j + ((hi_j - lo_j + 1u) >> 1);
-                                if (ckx[mid] <= W) lo_j = mid; else hi_j = mid - 1u;
-                            }
-                            cu.k = lo_j << 6; cu.x = ckx[lo_j]; cu.y = cky[lo_j];
-                        }
-                    }
-                    act.push_back(cu);
-                };
-                walker_guarded(err, [&] {
-                    size_t task;
-                    while ((task = next_task.fetch_add(1)) < ntasks) {
-                        const size_t w0 = task * per, w1 = std::min<size_t>(n_win, w0 + per);
-                        act.clear();
-                        for (size_t w = w0; w < w1; ++w) {
-                            const uint32_t W = (uint32_t)(w * kT);
-                            WinMeta &m = win[w];
-                            if (w == w0) {
-                                // what covers the range's first window: the wide reads in front of read lo, then [lo, hi)
-                                for (uint32_t i = 0; i < m.wn; ++i) enter(wide_idx[m.wlo + i], W);
-                                for (uint32_t r = m.lo; r < m.hi; ++r) enter(r, W);
-                            } else {
-                                for (uint32_t r = win[w - 1].hi; r < m.hi; ++r) enter(r, W);   // the reads that start in this window
-                            }
-                            save = act;
-                            size_t cnt = sweep_window(act, cig, W, m.q0, cur_buf() + used, capE - used, qend, &oor);
-                            if (cnt == SIZE_MAX) {                           // the buffer is full: it leaves, the window starts over
-                                flush();
-                                act = save;
-                                cnt = sweep_window(act, cig, W, m.q0, cur_buf(), capE, qend, &oor);
-                            }
-                            if (cnt == SIZE_MAX) {
-                                // a window that no buffer holds (thousandfold depth): through a block of its own
-                                size_t bc = capE * 4;
-                                for (;;) {
-                                    big.clear(); big.resize(bc);
-                                    act = save;
-                                    cnt = sweep_window(act, cig, W, m.q0, big.data(), bc, qend, &oor);
-                                    if (cnt != SIZE_MAX) break;
-                                    bc *= 4;
-                                }
-                                const uint64_t off = dev_next.fetch_add(cnt);
-                                if (off + cnt <= dev_cap && err == hipSuccess)
-                                    err = hipMemcpy(d_tab + off, big.data(), cnt * sizeof(uint2), hipMemcpyHostToDevice);
-                                m.rlo = (uint32_t)off; m.rn = (uint32_t)std::min<size_t>(cnt, 0xFFFFFFFFu);
-                                continue;
-                            }
-                            m.rlo = (uint32_t)used; m.rn = (uint32_t)cnt;
-                            if (cnt) in_buf.push_back((uint32_t)w);
-                            used += cnt;
-                        }
-                    }
-                    flush();
-                });
-                for (int b = 0; b < 2 && b < kb; ++b) { const hipError_t e = hipEventSynchronize(R->pin_ev[t][b]); if (err == hipSuccess) err = e; }
-                c->copy_err[t] = err;
-        });
-        s = ring_finish(c);
-        if (s != CL_OK) return s;
-        const uint64_t total = dev_next.load();
-        if (oor.load()) return fail(c, CL_ERR_RANGE, "a match piece of the run table addresses quality bytes outside the resident array");
-        if (total >= 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "more than 2^32 match pieces in one contig");
-        if (total <= dev_cap) { c->n_runtab = total; return CL_OK; }
-        want = total;                                            // exact now: once more
+    RunReads H;
+    H.pos = c->hs.pos.data(); H.mapq = c->hs.mapq.data(); H.end = c->hs.end.data();
+    H.coff = c->hs.cigar_off.data(); H.cig = c->hs.cigar.data(); H.ckx = c->hs.ck_x.data(); H.cky = c->hs.ck_y.data();
+    H.qoff = c->hs.qual_off.data();
+    H.min_mapq = c->opt.min_mapping_quality;
+    H.inject_read = fault_injected("runtab") ? c->n_reads / 2u : 0xFFFFFFFFu;
+    return H;
+}
+
+// a read that covers positions at or after W enters the sweep (reads below min_mapq never do, mod.rs:25): at its first
+// operation, or -- a read of more than kLongOps operations that starts before W -- at its last checkpoint at or before W
+inline void run_enter(std::vector<RunCur> &act, const RunReads &H, uint32_t r, uint32_t W)
+{
+    if (H.mapq[r] < H.min_mapq) return;
+    RunCur cu;
+    cu.k = H.coff[r]; cu.k1 = H.coff[r + 1]; cu.x = (uint32_t)H.pos[r]; cu.y = 0;
+    if (cu.k >= cu.k1 || H.end[r] <= W) return;
+    const unsigned long long ql = H.qoff[r + 1] - H.qoff[r];
+    cu.qlen = ql > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)ql;
+    cu.q0 = H.qoff[r]; cu.flags = ((r & 1u) << 29) | 0x80000000u;
+    if (r == H.inject_read) cu.q0 += 0x7FFFFFF0ull;
+    if (cu.k1 - cu.k > kLongOps && cu.x < W) {
+        const uint32_t jlo = (cu.k + 63u) >> 6, jhi = (cu.k1 - 1u) >> 6;
+        if (jlo <= jhi && H.ckx[jlo] <= W) {
+            uint32_t lo_j = jlo, hi_j = jhi;
+            while (lo_j < hi_j) {
+                const uint32_t mid = lo_j + ((hi_j - lo_j + 1u) >> 1);
+                if (H.ckx[mid] <= W) lo_j = mid; else hi_j = mid - 1u;
+            }
+            cu.k = lo_j << 6; cu.x = H.ckx[lo_j]; cu.y = H.cky[lo_j];
+        }
     }
-    return fail(c, CL_ERR_DEVICE, "run table: the second sizing pass did not fit");
+    act.push_back(cu);
 }
 
 // groups of rows per pinned buffer (DUT_ROW_CHUNK: a test hook that makes the buffer-full and oversized-window paths
@@ -682,46 +610,98 @@ size_t row_chunk_groups()
 dut::RowReads row_reads(const cl_ctx *c)
 {
     dut::RowReads H;
-    H.pos = c->h_pos.data(); H.end = c->h_end.data(); H.mapq = c->h_mapq.data();
-    H.off = c->h_rb_off.data(); H.bits = c->h_qbits.data();
-    H.sc_off = c->h_sc_off.data(); H.sc = c->h_sc.data();
+    H.pos = c->hs.pos.data(); H.end = c->hs.end.data(); H.mapq = c->hs.mapq.data();
+    H.off = c->hs.rb_off.data(); H.bits = c->hs.qbits.data();
+    H.sc_off = c->hs.sc_off.data(); H.sc = c->hs.sc.data();
     H.min_mapq = c->opt.min_mapping_quality;
     return H;
 }
 
-// The pass-bit rows of the resident contig (pass_rows.h), laid out at upload from the reads' reference-order bit strings
-// (no CIGAR is looked at but those of the few gapped reads) and streamed to HBM the way the run table is: a thread takes
-// a range of windows and sweeps it with a list of read cursors;
-// the groups of a window are written straight into the pinned buffers of the staging ring, a buffer leaves when the
-// next window no longer fits, buffers are placed in the device array in the order they fill (a window only needs its
-// own groups contiguous: its record holds their index).  win[w].rlo / rn = first group / number of groups.
-cl_status stream_rows(cl_ctx *c, std::vector<WinMeta> &win)
+// the first size of the row array: rows ~ 1.7 x the mean depth, a quarter of that in groups, one group of rounding per
+// window (cl_contig_reserve allocates by it ahead of the upload)
+uint64_t row_groups_estimate(uint64_t n_qual, uint64_t n_win) { return (n_qual / kT) * 17 / 40 + n_win + 1024; }
+
+// What differs between the two tables that stream_windows builds: the unit a window is made of (Word x kUnitWords), how
+// many units a pinned buffer holds, the device array (in units), the cursor of a read and how it enters and is swept,
+// what is checked and kept at the end, and the messages.
+struct RunTableForm {                     // byte form, long reads: a unit = a match piece (sweep_window)
+    using Word = uint2;
+    using Cur = RunCur;
+    struct Scratch {};
+    static constexpr size_t kUnitWords = 1;
+    static constexpr const char *kTooMany = "more than 2^32 match pieces in one contig";
+    static constexpr const char *kNoFit = "run table: the second sizing pass did not fit";
+    cl_ctx *c;
+    const RunReads H;
+    const unsigned long long qend;
+    std::atomic<bool> oor{false};
+    explicit RunTableForm(cl_ctx *c_) : c(c_), H(run_reads(c_)), qend(c_->n_qual + 2ull * kQualPad) {}
+    static size_t chunk_units() { return run_chunk_entries(); }
+    uint64_t estimate() const { return c->n_qual / 12 + (uint64_t)c->n_win * 8 + 65536; }   // a piece per ~12 aligned bases
+    hipError_t reserve(uint64_t units) { return c->d_runtab.reserve(units); }
+    Word *table() const { return c->d_runtab.p; }
+    uint64_t capacity() const { return c->d_runtab.cap; }
+    void enter(std::vector<Cur> &act, uint32_t r, uint32_t W) const { run_enter(act, H, r, W); }
+    size_t window(std::vector<Cur> &act, uint32_t W, const WinMeta &m, Word *out, size_t cap, Scratch &) { return sweep_window(act, H.cig, W, m.q0, out, cap, qend, &oor); }
+    cl_status check() { return oor.load() ? fail(c, CL_ERR_RANGE, "a match piece of the run table addresses quality bytes outside the resident array") : CL_OK; }
+    void done(uint64_t total, uint32_t) { c->n_runtab = total; }
+};
+
+struct RowsForm {                         // pass-bit form: a unit = a group of 4 rows (pass_rows.h)
+    using Word = uint32_t;
+    using Cur = dut::RowCur;
+    using Scratch = dut::RowScratch;
+    static constexpr size_t kUnitWords = dut::kRowGroupWords;
+    static constexpr const char *kTooMany = "more than 2^32 groups of pass-bit rows in one contig";
+    static constexpr const char *kNoFit = "pass-bit rows: the second sizing pass did not fit";
+    cl_ctx *c;
+    const dut::RowReads H;
+    explicit RowsForm(cl_ctx *c_) : c(c_), H(row_reads(c_)) {}
+    static size_t chunk_units() { return row_chunk_groups(); }
+    uint64_t estimate() const { return row_groups_estimate(c->n_qual, c->n_win); }
+    hipError_t reserve(uint64_t units) { return c->d_rows.reserve(units * (kUnitWords / 4)); }
+    Word *table() const { return reinterpret_cast<Word *>(c->d_rows.p); }
+    uint64_t capacity() const { return c->d_rows.cap / (kUnitWords / 4); }
+    void enter(std::vector<Cur> &act, uint32_t r, uint32_t W) const { dut::rows_enter(act, H, r, W); }
+    size_t window(std::vector<Cur> &act, uint32_t W, const WinMeta &, Word *out, size_t cap, Scratch &sc) { return dut::rows_window<kT>(act, H, W, out, cap, sc); }
+    cl_status check() { return CL_OK; }
+    void done(uint64_t total, uint32_t most) { c->n_row_groups = total; c->max_groups = most; }   // most: picks the counter planes
+};
+
+// A per-window table of the resident contig, built at upload and streamed to HBM: a thread takes a range of windows
+// and sweeps it with a list of read cursors (Form::enter, Form::window); the units of a window are written straight
+// into the pinned buffers of the staging ring, a buffer leaves when the next window no longer fits, buffers are placed
+// in the device array in the order they fill (a window only needs its own units contiguous: its record holds their
+// index), so the table exists nowhere in host memory.  win[w].rlo / rn = first unit / number of units; a window that no
+// read's cursor reaches gets rlo = rn = 0.
+template <class Form>
+cl_status stream_windows(cl_ctx *c, std::vector<WinMeta> &win)
 {
+    using Word = typename Form::Word;
+    constexpr size_t UW = Form::kUnitWords;
     const uint32_t n_win = c->n_win;
-    const dut::RowReads H = row_reads(c);
-    const uint32_t *wide_idx = c->h_wide_idx.data();
-    c->n_row_groups = 0; c->max_groups = 0;
     if (n_win == 0) return CL_OK;
     cl_status s = ensure_pins(c);
     if (s != CL_OK) return s;
+    Form F(c);
+    const uint32_t *wide_idx = c->hs.wide_idx.data();
     // (as many walkers as the staging ring has buffer pairs -- DUT_COPY_THREADS, 8 by default --: pinning 16 MB more per
     // further walker costs more than the walker saves: 73 ms with 16 walkers against 23 ms with 8 at chr21 30x)
     const int nt = std::max(1, std::min<int>(std::max(1, c->ring->slots), dut::worker_threads()));
+    // tasks: several per thread so that uneven depth evens out, not so short that the range-start walks show
     const size_t per = std::max<size_t>(16, (size_t)n_win / (8 * (size_t)nt) + 1);
     const size_t ntasks = ((size_t)n_win + per - 1) / per;
-    const size_t capG = row_chunk_groups();
-    constexpr size_t GW = dut::kRowGroupWords;
-    // the device array: an estimate first (rows ~ 1.7 x the mean depth, a quarter of that in groups, one group of
-    // rounding per window); a contig that needs more tells how much
-    uint64_t want = (c->n_qual / kT) * 17 / 40 + (uint64_t)n_win + 1024;
+    const size_t capU = Form::chunk_units();
+    // the device array: an estimate first; a contig that needs more tells how much
+    uint64_t want = F.estimate();
     for (int attempt = 0; attempt < 2; ++attempt) {
         HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, c->d_rows.reserve(want * (GW / 4)));
-        uint32_t *const d_tab = reinterpret_cast<uint32_t *>(c->d_rows.p);
-        const uint64_t dev_cap = c->d_rows.cap / (GW / 4);              // groups
+        HIP_TRY(c, F.reserve(want));
+        Word *const d_tab = F.table();
+        const uint64_t dev_cap = F.capacity();
         std::atomic<uint64_t> dev_next{0};
         std::atomic<size_t> next_task{0};
-        std::atomic<uint32_t> max_groups{0};
+        std::atomic<uint32_t> most{0};                           // units of the largest window
         PinRing *R = c->ring.get();
         R->acquire(static_cast<EngineBase *>(c));                // (the identity ring_finish releases it under)
         c->ring_held = true;
@@ -731,24 +711,24 @@ cl_status stream_rows(cl_ctx *c, std::vector<WinMeta> &win)
         R->crew.start(nt, [&](int t) {
                 hipError_t err = hipSetDevice(c->device);
                 int kb = 0;                                                  // buffers this thread has sent
-                auto cur_buf = [&]() { return reinterpret_cast<uint32_t *>(R->pin[t][kb & 1]); };
-                auto send = [&](uint32_t *dst, size_t groups) {              // the current buffer leaves; on to the other one
+                auto cur_buf = [&]() { return reinterpret_cast<Word *>(R->pin[t][kb & 1]); };
+                auto send = [&](Word *dst, size_t units) {                   // the current buffer leaves; on to the other one
                     if (err != hipSuccess) return;
-                    err = hipMemcpyAsync(dst, cur_buf(), groups * GW * sizeof(uint32_t), hipMemcpyHostToDevice, R->copy_stream[t]);
+                    err = hipMemcpyAsync(dst, cur_buf(), units * UW * sizeof(Word), hipMemcpyHostToDevice, R->copy_stream[t]);
                     if (err == hipSuccess) err = hipEventRecord(R->pin_ev[t][kb & 1], R->copy_stream[t]);
                     ++kb;
                     if (kb >= 2 && err == hipSuccess) err = hipEventSynchronize(R->pin_ev[t][kb & 1]);   // its previous transfer is done
                 };
-                std::vector<dut::RowCur> act, save;
-                std::vector<uint32_t> in_buf;                                // windows whose groups lie in the current buffer
-                dut::RowScratch sc;
-                RawVec<uint32_t> big;
+                std::vector<typename Form::Cur> act, save;
+                std::vector<uint32_t> in_buf;                                // windows whose units lie in the current buffer
+                typename Form::Scratch scr;
+                RawVec<Word> big;
                 size_t used = 0;
-                uint32_t my_max = 0;
+                uint32_t my_most = 0;
                 auto flush = [&]() {
                     if (!used) return;
                     const uint64_t off = dev_next.fetch_add(used);
-                    if (off + used <= dev_cap) send(d_tab + off * GW, used);  // else: the array is too small, only the total counts now
+                    if (off + used <= dev_cap) send(d_tab + off * UW, used);  // else: the array is too small, only the total counts now
                     for (uint32_t w : in_buf) win[w].rlo += (uint32_t)off;
                     in_buf.clear(); used = 0;
                 };
@@ -762,38 +742,38 @@ cl_status stream_rows(cl_ctx *c, std::vector<WinMeta> &win)
                             WinMeta &m = win[w];
                             if (w == w0) {
                                 // what covers the range's first window: the wide reads in front of read lo, then [lo, hi)
-                                for (uint32_t i = 0; i < m.wn; ++i) dut::rows_enter(act, H, wide_idx[m.wlo + i], W);
-                                for (uint32_t r = m.lo; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
+                                for (uint32_t i = 0; i < m.wn; ++i) F.enter(act, wide_idx[m.wlo + i], W);
+                                for (uint32_t r = m.lo; r < m.hi; ++r) F.enter(act, r, W);
                             } else {
-                                for (uint32_t r = win[w - 1].hi; r < m.hi; ++r) dut::rows_enter(act, H, r, W);   // the reads that start in this window
+                                for (uint32_t r = win[w - 1].hi; r < m.hi; ++r) F.enter(act, r, W);   // the reads that start in this window
                             }
                             if (act.empty()) { m.rlo = 0; m.rn = 0; continue; }
                             save = act;
-                            size_t cnt = dut::rows_window<kT>(act, H, W, cur_buf() + used * GW, capG - used, sc);
+                            size_t cnt = F.window(act, W, m, cur_buf() + used * UW, capU - used, scr);
                             if (cnt == SIZE_MAX) {                           // the buffer is full: it leaves, the window starts over
                                 flush();
                                 act = save;
-                                cnt = dut::rows_window<kT>(act, H, W, cur_buf(), capG, sc);
+                                cnt = F.window(act, W, m, cur_buf(), capU, scr);
                             }
                             if (cnt == SIZE_MAX) {
-                                // a window that no buffer holds (depth in the ten thousands): through a block of its own
-                                size_t bc = capG * 4;
+                                // a window that no buffer holds (depth in the thousands): through a block of its own
+                                size_t bc = capU * 4;
                                 for (;;) {
-                                    big.clear(); big.resize(bc * GW);
+                                    big.clear(); big.resize(bc * UW);
                                     act = save;
-                                    cnt = dut::rows_window<kT>(act, H, W, big.data(), bc, sc);
+                                    cnt = F.window(act, W, m, big.data(), bc, scr);
                                     if (cnt != SIZE_MAX) break;
                                     bc *= 4;
                                 }
                                 const uint64_t off = dev_next.fetch_add(cnt);
                                 if (off + cnt <= dev_cap && err == hipSuccess)
-                                    err = hipMemcpy(d_tab + off * GW, big.data(), cnt * GW * sizeof(uint32_t), hipMemcpyHostToDevice);
+                                    err = hipMemcpy(d_tab + off * UW, big.data(), cnt * UW * sizeof(Word), hipMemcpyHostToDevice);
                                 m.rlo = (uint32_t)off; m.rn = (uint32_t)std::min<size_t>(cnt, 0xFFFFFFFFu);
-                                my_max = std::max(my_max, m.rn);
+                                my_most = std::max(my_most, m.rn);
                                 continue;
                             }
                             m.rlo = (uint32_t)used; m.rn = (uint32_t)cnt;
-                            my_max = std::max(my_max, m.rn);
+                            my_most = std::max(my_most, m.rn);
                             if (cnt) in_buf.push_back((uint32_t)w);
                             used += cnt;
                         }
@@ -801,18 +781,30 @@ cl_status stream_rows(cl_ctx *c, std::vector<WinMeta> &win)
                     flush();
                 });
                 for (int b = 0; b < 2 && b < kb; ++b) { const hipError_t e = hipEventSynchronize(R->pin_ev[t][b]); if (err == hipSuccess) err = e; }
-                uint32_t seen = max_groups.load();
-                while (seen < my_max && !max_groups.compare_exchange_weak(seen, my_max)) {}
+                uint32_t seen = most.load();
+                while (seen < my_most && !most.compare_exchange_weak(seen, my_most)) {}
                 c->copy_err[t] = err;
         });
         s = ring_finish(c);
         if (s != CL_OK) return s;
         const uint64_t total = dev_next.load();
-        if (total >= 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "more than 2^32 groups of pass-bit rows in one contig");
-        if (total <= dev_cap) { c->n_row_groups = total; c->max_groups = max_groups.load(); return CL_OK; }
+        if ((s = F.check()) != CL_OK) return s;
+        if (total >= 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, Form::kTooMany);
+        if (total <= dev_cap) { F.done(total, most.load()); return CL_OK; }
         want = total;                                            // exact now: once more
     }
-    return fail(c, CL_ERR_DEVICE, "pass-bit rows: the second sizing pass did not fit");
+    return fail(c, CL_ERR_DEVICE, Form::kNoFit);
+}
+
+// The device buffers whose size follows from the number of windows, each with its element count: f(buffer, elements).
+// The reference is d_refn (a bit per position) in the pass-bit form, d_ref (the bytes) in the byte forms.
+template <class F> void each_extent_buffer(cl_ctx *c, size_t n_win, bool pass_bits, F &&f)
+{
+    const size_t padded = n_win * kT;
+    f(c->d_win, n_win + 1); f(c->d_win_off, n_win + 1); f(c->d_winpart, n_win + 1);
+    f(c->d_fin, n_win / kFinBlock + 2); f(c->d_runs, padded + 16);
+    f(c->d_first_state, n_win + 1); f(c->d_last_state, n_win + 1); f(c->d_win_wide, n_win + 1);
+    if (pass_bits) f(c->d_refn, padded / 32 + 4); else f(c->d_ref, padded + 16);
 }
 
 // allocate and lay out everything that depends on the extent (called by cl_contig_upload, the staged arrays still there)
@@ -821,22 +813,16 @@ cl_status size_for_extent(cl_ctx *c, uint32_t extent)
     c->extent = extent;
     c->n_win = (uint32_t)(((uint64_t)extent + kT - 1) / kT);
     const size_t padded = (size_t)c->n_win * kT;
-    HIP_TRY(c, c->d_win.reserve(c->n_win + 1));
-    HIP_TRY(c, c->d_win_off.reserve(c->n_win + 1));
-    HIP_TRY(c, c->d_winpart.reserve(c->n_win + 1));
-    HIP_TRY(c, c->d_fin.reserve(c->n_win / kFinBlock + 2));
-    HIP_TRY(c, c->d_runs.reserve(padded + 16));
-    HIP_TRY(c, c->d_first_state.reserve(c->n_win + 1));
-    HIP_TRY(c, c->d_last_state.reserve(c->n_win + 1));
-    HIP_TRY(c, c->d_win_wide.reserve(c->n_win + 1));
+    hipError_t alloc = hipSuccess;
+    each_extent_buffer(c, c->n_win, c->form == 3, [&](auto &buf, size_t n) { if (alloc == hipSuccess) alloc = buf.reserve(n); });
+    HIP_TRY(c, alloc);
     HIP_TRY(c, hipMemsetAsync(c->d_win_wide.p, 0, c->n_win + 1, c->stream));
     // reference bytes: [0,ref_len) from the caller, 'N' beyond (mod.rs:79-80).  The pass-bit form needs one bit of a
     // base -- is it 'N' / 'n' (mod.rs:100-101) --, taken here, where the bytes pass through the host's hands anyway:
     // 1/8 of the transfer, 1/8 of what every run reads
-    if (c->form == 3) HIP_TRY(c, c->d_refn.reserve(padded / 32 + 4)); else HIP_TRY(c, c->d_ref.reserve(padded + 16));
     {
-        const uint8_t *ref = c->h_ref.data();
-        const uint64_t nref = std::min<uint64_t>(c->h_ref.size(), padded);
+        const uint8_t *ref = c->hs.ref.data();
+        const uint64_t nref = std::min<uint64_t>(c->hs.ref.size(), padded);
         cl_status rs;
         if (c->form == 3)
             rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_refn.p), padded / 8, [ref, nref](uint64_t off, uint64_t len, uint8_t *out) {
@@ -859,21 +845,21 @@ cl_status size_for_extent(cl_ctx *c, uint32_t extent)
         if (c->form == 3) {
             // the windows' pass-bit rows: one more walk over the staged CIGARs, streamed to HBM through the ring
             StageTimer tr;
-            rs = stream_rows(c, win);
+            rs = stream_windows<RowsForm>(c, win);
             if (rs != CL_OK) return rs;
             tr.lap("upload: pass-bit rows (walk + H2D)");
         }
         if (c->form == 2 && !(flags & kErrRange)) {
             // the windows' match pieces: one more walk over the staged CIGARs, streamed to HBM through the ring
             StageTimer tr;
-            rs = stream_run_table(c, win);
+            rs = stream_windows<RunTableForm>(c, win);
             if (rs != CL_OK) return rs;
             tr.lap("upload: run table (walk + H2D)");
         }
         // DUT_VALIDATE=1 (tooling: tools/fuzz_parity.py sets it): what the kernels will index is checked on the host before
         // anything is launched -- candidate ranges against the resident arrays, and every entry of the run table (read
         // back from the device) against the quality array -- so that a bad index is an error message, not a GPU fault
-        finish_windows(c, c->h_wide_rec_of, win, flags);
+        finish_windows(c, c->hs.wide_rec_of, win, flags);
         // what k_pileup_rows streams per window must lie inside the resident rows: checked in the product build, once per
         // contig (an index past the array is an error return, not a device fault)
         if (c->form == 3) {
@@ -885,9 +871,9 @@ cl_status size_for_extent(cl_ctx *c, uint32_t extent)
         }
         static const bool validate = [] { const char *e = getenv("DUT_VALIDATE"); return e && *e == '1'; }();
         if (validate && !(flags & kErrRange)) {
-            const uint64_t n_cand = c->form != 2 ? c->n_rec : c->h_pos.size();
-            uint64_t n_wide_list = c->h_wide_idx.size();
-            if (c->form != 2) n_wide_list = c->h_wide_rec_of.empty() ? 0 : c->h_wide_rec_of.back();
+            const uint64_t n_cand = c->form != 2 ? c->n_rec : c->hs.pos.size();
+            uint64_t n_wide_list = c->hs.wide_idx.size();
+            if (c->form != 2) n_wide_list = c->hs.wide_rec_of.empty() ? 0 : c->hs.wide_rec_of.back();
             std::vector<uint2> tab;
             if (c->form == 2 && c->n_runtab) {
                 tab.resize(c->n_runtab);
@@ -1108,15 +1094,14 @@ cl_status cl_contig_begin(cl_ctx *c, int32_t tid, uint32_t contig_len, const uin
         take_staging(c);
         c->tid = tid; c->contig_len = contig_len;
         const uint64_t nref = std::min<uint64_t>(ref_len, contig_len);
-        c->h_ref.clear(); c->h_ref.append(ref_bases, nref);
-        c->h_pos.clear(); c->h_mapq.clear(); c->h_cigar.clear(); c->h_qual.clear();
-        c->h_cigar_off.clear(); c->h_cigar_off.push_back(0u); c->h_qual_off.clear(); c->h_qual_off.push_back(0ull);
+        c->hs.clear();
+        c->hs.ref.append(ref_bases, nref); c->hs.cigar_off.push_back(0u); c->hs.qual_off.push_back(0ull);
         c->h_iv.clear();
         c->q_dev = 0;
-        c->h_wide_idx.clear(); c->h_wide_pos.clear(); c->span_n = 0; c->span_w = 0; c->n_wide = 0; c->host_max_end = 0;
-        c->h_end.clear(); c->h_ck_x.clear(); c->h_ck_y.clear(); c->n_long = 0; c->host_err = 0; c->bounds_err = 0;
-        c->h_rec_cnt.clear(); c->rec_counted = true;
-        c->h_qbits.clear(); c->h_rb_off.clear(); c->h_sc_off.clear(); c->h_sc.clear(); c->host_sum_q = 0; c->host_n_ops = 0;
+        c->span_n = 0; c->span_w = 0; c->n_wide = 0; c->host_max_end = 0;
+        c->n_long = 0; c->host_err = 0; c->bounds_err = 0;
+        c->rec_counted = true;
+        c->host_sum_q = 0; c->host_n_ops = 0;
         c->host_sum_cov = 0; c->host_sum_mapq = 0;
         c->in_contig = true; c->uploaded = false; c->ran = false; c->has_long = false;
         return CL_OK;
@@ -1127,13 +1112,13 @@ namespace {
 // quality bytes staged on the host so far go to the device, behind the ones already there
 cl_status flush_staged_qual(cl_ctx *c)
 {
-    if (c->h_qual.empty()) return CL_OK;
+    if (c->hs.qual.empty()) return CL_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, c->d_qual.grow_keep(c->q_dev + c->h_qual.size() + 2 * kQualPad, kQualPad + c->q_dev, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_qual.p + kQualPad + c->q_dev, c->h_qual.data(), c->h_qual.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, c->d_qual.grow_keep(c->q_dev + c->hs.qual.size() + 2 * kQualPad, kQualPad + c->q_dev, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_qual.p + kQualPad + c->q_dev, c->hs.qual.data(), c->hs.qual.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->q_dev += c->h_qual.size();
-    c->h_qual.clear();
+    c->q_dev += c->hs.qual.size();
+    c->hs.qual.clear();
     return CL_OK;
 }
 constexpr uint64_t kDirectQual = 4u << 20;   // tiles with at least this many quality bytes skip the host staging copy
@@ -1167,25 +1152,19 @@ static void start_prealloc(cl_ctx *c, uint64_t n_reads, uint64_t n_qual)
 {
     join_prealloc(c);
     const uint32_t contig_len = c->contig_len;
-    {   // nothing to do for a context whose buffers hold this contig already (the usual case from its second contig on):
-        // no thread is made for that
-        const size_t n_win = ((size_t)contig_len + kT - 1) / kT + 1, padded = n_win * kT;
-        const size_t rows_want = n_qual ? ((n_qual / kT) * 17 / 40 + n_win + 1024) * (dut::kRowGroupWords / 4) : 0;
-        const bool enough = c->d_win.cap >= n_win + 1 && c->d_win_off.cap >= n_win + 1 && c->d_winpart.cap >= n_win + 1 &&
-                            c->d_fin.cap >= n_win / kFinBlock + 2 && c->d_runs.cap >= padded + 16 && c->d_first_state.cap >= n_win + 1 &&
-                            c->d_last_state.cap >= n_win + 1 && c->d_win_wide.cap >= n_win + 1 && c->d_refn.cap >= padded / 32 + 4 &&
-                            c->d_heads.cap >= (n_reads ? (size_t)n_reads + 1 : 0) && c->d_rows.cap >= rows_want && c->d_iv.cap != 0;
-        if (enough) return;
-    }
-    c->prealloc = dut::spawn_or_run([c, n_reads, n_qual, contig_len]() {
+    // (one window more than the contig's length gives: the extent may turn out larger than the length)
+    const size_t n_win = ((size_t)contig_len + kT - 1) / kT + 1;
+    const size_t n_heads = n_reads ? (size_t)n_reads + 1 : 0;
+    const size_t n_rows = n_qual ? row_groups_estimate(n_qual, n_win) * (dut::kRowGroupWords / 4) : 0;
+    // nothing to do for a context whose buffers hold this contig already (the usual case from its second contig on):
+    // no thread is made for that
+    bool enough = c->d_heads.cap >= n_heads && c->d_rows.cap >= n_rows && c->d_iv.cap != 0;
+    each_extent_buffer(c, n_win, true, [&](auto &buf, size_t n) { enough = enough && buf.cap >= n; });
+    if (enough) return;
+    c->prealloc = dut::spawn_or_run([c, n_win, n_heads, n_rows]() {
         if (hipSetDevice(c->device) != hipSuccess) return;
-        const size_t n_win = ((size_t)contig_len + kT - 1) / kT + 1, padded = n_win * kT;
-        (void)c->d_win.reserve(n_win + 1); (void)c->d_win_off.reserve(n_win + 1); (void)c->d_winpart.reserve(n_win + 1);
-        (void)c->d_fin.reserve(n_win / kFinBlock + 2); (void)c->d_runs.reserve(padded + 16);
-        (void)c->d_first_state.reserve(n_win + 1); (void)c->d_last_state.reserve(n_win + 1); (void)c->d_win_wide.reserve(n_win + 1);
-        (void)c->d_refn.reserve(padded / 32 + 4);
-        if (n_reads) (void)c->d_heads.reserve((size_t)n_reads + 1);
-        if (n_qual) (void)c->d_rows.reserve(((n_qual / kT) * 17 / 40 + n_win + 1024) * (dut::kRowGroupWords / 4));   // stream_rows' own estimate
+        each_extent_buffer(c, n_win, true, [](auto &buf, size_t n) { (void)buf.reserve(n); });
+        (void)c->d_heads.reserve(n_heads); (void)c->d_rows.reserve(n_rows);
         if (c->d_iv.cap == 0) (void)c->d_iv.reserve(1u << 20);
     });
 }
@@ -1195,15 +1174,15 @@ cl_status cl_contig_reserve(cl_ctx *c, uint64_t n_reads, uint64_t n_cigar_ops, u
     if (!c || !c->in_contig || c->uploaded) return fail(c, CL_ERR_INVALID, "cl_contig_reserve outside cl_contig_begin .. upload");
     drop_prefetch(c);                                        // the quality buffer may move below
     try {
-        c->h_pos.reserve(n_reads); c->h_mapq.reserve(n_reads);
-        c->h_cigar_off.reserve(n_reads + 1); c->h_qual_off.reserve(n_reads + 1);
-        c->h_cigar.reserve(n_cigar_ops);
-        if (c->bits) c->h_qbits.reserve(((n_qual_bytes + 63) >> 6) + 2);
+        c->hs.pos.reserve(n_reads); c->hs.mapq.reserve(n_reads);
+        c->hs.cigar_off.reserve(n_reads + 1); c->hs.qual_off.reserve(n_reads + 1);
+        c->hs.cigar.reserve(n_cigar_ops);
+        if (c->bits) c->hs.qbits.reserve(((n_qual_bytes + 63) >> 6) + 2);
     } catch (const std::bad_alloc &) {
         return fail(c, CL_ERR_NOMEM, "host staging allocation failed");
     }
     if (c->bits) {
-        if (!c->host_only && c->h_pos.empty()) start_prealloc(c, n_reads, n_qual_bytes);
+        if (!c->host_only && c->hs.pos.empty()) start_prealloc(c, n_reads, n_qual_bytes);
         return CL_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1220,7 +1199,7 @@ static cl_status tile_header(cl_ctx *c, const char *who, uint64_t n, const int32
     if (!c->in_contig || c->uploaded) return fail(c, CL_ERR_INVALID, std::string(who) + " outside cl_contig_begin .. upload");
     if (n == 0) return CL_OK;
     if (!pos || !mapq || !cigar_off || !qual_off) return fail(c, CL_ERR_INVALID, "null tile array");
-    if (c->h_pos.size() + n >= (1ull << 29)) return fail(c, CL_ERR_RANGE, "more than 2^29 reads in one contig");
+    if (c->hs.pos.size() + n >= (1ull << 29)) return fail(c, CL_ERR_RANGE, "more than 2^29 reads in one contig");
     h.cig0 = cigar_off[0]; h.q0 = qual_off[0];
     if (cigar_off[n] < h.cig0 || qual_off[n] < h.q0) return fail(c, CL_ERR_INVALID, "offset arrays must be non-decreasing");
     h.ncig = (uint64_t)cigar_off[n] - h.cig0; h.nq = qual_off[n] - h.q0;
@@ -1236,6 +1215,40 @@ static Offence walk_offence(int bad)
     if (bad == 1) return {CL_ERR_INVALID, "read position outside [0, contig_len): the region fetch (mod.rs:53) never yields it"};
     if (bad == 2) return {CL_ERR_UNSORTED, "reads are not coordinate sorted"};
     return {CL_ERR_INVALID, "offset arrays must be non-decreasing"};
+}
+
+// What both walks over a tile's reads (push_reads_bits, cl_push_reads_impl) keep per chunk of reads; it reaches the
+// context only when the whole tile is accepted (walk_fold), so that a refused tile leaves the context as it was.
+struct WalkChunk { int bad = 0; uint32_t err = 0, span_n = 0, span_w = 0; uint64_t max_end = 0; std::vector<uint32_t> wide; };
+// read i before its CIGAR is looked at: position and order (offences 1, 2: the walk goes on), offsets (3: false, no walk)
+static inline bool walk_read_checks(WalkChunk &o, const cl_read_tile *t, size_t i, int32_t &last, uint32_t contig_len, const TileHead &h)
+{
+    const int32_t p = t->pos[i];
+    if (p < 0 || (uint32_t)p >= contig_len) { if (!o.bad) o.bad = 1; }
+    else if (p < last) { if (!o.bad) o.bad = 2; }
+    last = p;
+    const bool ok = t->cigar_off[i + 1] >= t->cigar_off[i] && t->qual_off[i + 1] >= t->qual_off[i] &&
+                    t->cigar_off[i] >= h.cig0 && t->cigar_off[i + 1] <= h.cig0 + h.ncig && t->qual_off[i] >= h.q0 && t->qual_off[i + 1] <= h.q0 + h.nq;
+    if (!ok && !o.bad) o.bad = 3;
+    return ok;
+}
+// ... and once its CIGAR has given the reference length l: the end (beyond the engine's 32-bit coordinate range: flagged,
+// the read then spans nothing), the longest ordinary span (it bounds every window's candidate range), the wide list
+static inline void walk_close_span(WalkChunk &o, size_t i, int32_t p, unsigned long long l, uint32_t &end)
+{
+    const uint32_t sp = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
+    if (l <= 0xFFFF0000ull - (uint64_t)p) { end = (uint32_t)((uint64_t)p + l); o.max_end = std::max<uint64_t>(o.max_end, (uint64_t)p + l); }
+    else o.err |= kErrRange;
+    if (sp > kWideSpan) { o.wide.push_back((uint32_t)i); o.span_w = std::max(o.span_w, sp); }
+    else o.span_n = std::max(o.span_n, sp);
+}
+// a chunk of an accepted tile into the context (rbase: the contig's reads before this tile)
+static inline void walk_fold(cl_ctx *c, const WalkChunk &o, uint64_t rbase, const int32_t *pos)
+{
+    c->host_err |= o.err;
+    c->span_n = std::max(c->span_n, o.span_n); c->span_w = std::max(c->span_w, o.span_w);
+    c->host_max_end = std::max(c->host_max_end, o.max_end);
+    for (uint32_t i : o.wide) { c->hs.wide_idx.push_back((uint32_t)(rbase + i)); c->hs.wide_pos.push_back(pos[i]); }
 }
 
 // cl_push_reads of the pass-bit form: nothing goes to the device here.  One walk over the tile, in chunks on all host
@@ -1264,32 +1277,27 @@ static inline void copy_bits_to_words(uint64_t *dst, const uint64_t *src, unsign
 
 // (pbits / psum: the packed variant, cl_push_reads_bits -- the caller has taken the base-quality test: bit
 // t->qual_off[i] + k of pbits <-> quality value k of read i, psum[i] the read's share of summed_baseq; t->qual is unused)
-static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0, uint64_t q0, uint64_t ncig, uint64_t nq,
-                                 const uint64_t *pbits = nullptr, const uint32_t *psum = nullptr)
+static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, const TileHead &h, const uint64_t *pbits = nullptr, const uint32_t *psum = nullptr)
 {
-    const uint64_t n = t->n_reads;
-    const uint64_t rbase = c->h_pos.size();
+    const uint64_t n = h.n, q0 = h.q0, nq = h.nq;
+    const uint64_t rbase = c->hs.pos.size();
     StageTimer tmr;
     const size_t grain = dut::grain_for(n, 65536);
     const size_t nchunk = (n + grain - 1) / grain;
-    struct Chunk {
-        int bad = 0; uint32_t err = 0, span_n = 0, span_w = 0; uint64_t max_end = 0, sum_q = 0, n_ops = 0, n_words = 0, n_sc = 0;
-        uint64_t sum_cov = 0, sum_mapq = 0;
-        std::vector<uint32_t> wide;
-    };
+    struct Chunk : WalkChunk { uint64_t sum_q = 0, n_ops = 0, n_words = 0, n_sc = 0, sum_cov = 0, sum_mapq = 0; };
     std::vector<Chunk> ch(nchunk);
-    const int32_t last0 = c->h_pos.empty() ? 0 : c->h_pos.back();
+    const int32_t last0 = c->hs.pos.empty() ? 0 : c->hs.pos.back();
     try {
-        c->h_rec_cnt.reserve(rbase + n); c->h_end.reserve(rbase + n);
-        c->h_rb_off.reserve(rbase + n + 1); c->h_sc_off.reserve(rbase + n + 1);
+        c->hs.rec_cnt.reserve(rbase + n); c->hs.end.reserve(rbase + n);
+        c->hs.rb_off.reserve(rbase + n + 1); c->hs.sc_off.reserve(rbase + n + 1);
     } catch (const std::bad_alloc &) {
         return fail(c, CL_ERR_NOMEM, "host staging allocation failed");
     }
     // (entries [rbase, rbase + n) of the staging arrays are written below; their sizes follow when the tile is accepted,
     // so a refused tile leaves nothing but unused capacity behind)
-    uint32_t *const h_end = c->h_end.data() + rbase, *const h_rec_cnt = c->h_rec_cnt.data() + rbase;
-    unsigned long long *const rb_off = c->h_rb_off.data() + rbase;      // first the reads' word counts (| kRowSparse), then their offsets
-    uint32_t *const sc_off = c->h_sc_off.data() + rbase;
+    uint32_t *const h_end = c->hs.end.data() + rbase, *const h_rec_cnt = c->hs.rec_cnt.data() + rbase;
+    unsigned long long *const rb_off = c->hs.rb_off.data() + rbase;      // first the reads' word counts (| kRowSparse), then their offsets
+    uint32_t *const sc_off = c->hs.sc_off.data() + rbase;
     const uint32_t min_mapq = c->opt.min_mapping_quality;
     const uint8_t min_bq = c->opt.min_base_quality;
     const uint64_t head_span = c->head_span;
@@ -1297,18 +1305,13 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
     const uint8_t *const qsrc = t->qual ? t->qual + q0 : nullptr;
     // ---- first: what needs the CIGAR operations only -- validation, ends, how many words of bits every read will leave ----
     dut::parallel_for(nchunk, 1, [&](size_t k) {
-        Chunk &o = ch[k];
+        Chunk o;                                                // (on the walker's stack: neighbouring chunks of ch share cache lines)
         const size_t a = k * grain, b = std::min<size_t>(n, a + grain);
         int32_t last = a ? t->pos[a - 1] : last0;
         for (size_t i = a; i < b; ++i) {
             const int32_t p = t->pos[i];
-            if (p < 0 || (uint32_t)p >= c->contig_len) { if (!o.bad) o.bad = 1; }
-            else if (p < last) { if (!o.bad) o.bad = 2; }
-            last = p;
             h_end[i] = (uint32_t)p; h_rec_cnt[i] = 0u; rb_off[i] = 0ull; sc_off[i] = 0u;
-            if (t->cigar_off[i + 1] < t->cigar_off[i] || t->qual_off[i + 1] < t->qual_off[i]) { if (!o.bad) o.bad = 3; continue; }
-            if (t->cigar_off[i] < cig0 || t->cigar_off[i + 1] > cig0 + ncig) { if (!o.bad) o.bad = 3; continue; }
-            if (t->qual_off[i] < q0 || t->qual_off[i + 1] > q0 + nq) { if (!o.bad) o.bad = 3; continue; }
+            if (!walk_read_checks(o, t, i, last, c->contig_len, h)) continue;
             const uint32_t q0i = t->cigar_off[i], nops = t->cigar_off[i + 1] - q0i;
             const uint32_t *cig = t->cigar + q0i;
             o.n_ops += nops;
@@ -1323,12 +1326,7 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
             if (zero_len) o.err |= kErrCigar;
             // a read that reaches a column with a single non-match op is undefined in htslib
             if (l > 0 && nops == 1u && !(((0x181u >> (cig[0] & 15u)) & 1u) != 0u)) o.err |= kErrCigar;
-            const uint32_t sp = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
-            // an end beyond the engine's 32-bit coordinate range: flagged; the read then spans nothing
-            if (l <= 0xFFFF0000ull - (uint64_t)p) { h_end[i] = (uint32_t)((uint64_t)p + l); o.max_end = std::max<uint64_t>(o.max_end, (uint64_t)p + l); }
-            else o.err |= kErrRange;
-            if (sp > kWideSpan) { o.wide.push_back((uint32_t)i); o.span_w = std::max(o.span_w, sp); }
-            else o.span_n = std::max(o.span_n, sp);
+            walk_close_span(o, i, p, l, h_end[i]);
             const bool in_pileup = h_end[i] != (uint32_t)p;
             const uint64_t span = h_end[i] - (uint32_t)p;
             // the heads k_pileup_rows reads: one, unless the span is beyond what a head holds
@@ -1348,37 +1346,38 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
             rb_off[i] = nw;
             o.n_words += nw & ~dut::kRowSparse;
         }
+        ch[k] = std::move(o);
     });
     tmr.lap("push: validate + spans");
     // (entry rbase of the two offset arrays closes the tiles before this one; the walk above used it for this tile's
     // first read: put back whenever the tile is refused)
-    const unsigned long long closing_rb = c->h_qbits.size();
-    const uint32_t closing_sc = (uint32_t)c->h_sc.size();
+    const unsigned long long closing_rb = c->hs.qbits.size();
+    const uint32_t closing_sc = (uint32_t)c->hs.sc.size();
     auto refuse = [&](cl_status st, const char *m) { rb_off[0] = closing_rb; sc_off[0] = closing_sc; return fail(c, st, m); };
     for (const Chunk &o : ch)                                  // the first offence in tile order decides the message
         if (o.bad) { const Offence f = walk_offence(o.bad); return refuse(f.st, f.msg); }
     // ---- where every chunk's strings go: behind the contig's ----
     std::vector<uint64_t> rb_base(nchunk + 1), sc_base(nchunk + 1);
-    rb_base[0] = c->h_qbits.size(); sc_base[0] = c->h_sc.size();
+    rb_base[0] = c->hs.qbits.size(); sc_base[0] = c->hs.sc.size();
     for (size_t k = 0; k < nchunk; ++k) { rb_base[k + 1] = rb_base[k] + ch[k].n_words; sc_base[k + 1] = sc_base[k] + ch[k].n_sc; }
     if (sc_base[nchunk] > 0xFFFFFFF0ull) return refuse(CL_ERR_RANGE, "more than 2^32 CIGAR operations of gapped reads in one contig");
     size_t n_wide_new = 0;
     for (const Chunk &o : ch) n_wide_new += o.wide.size();
     try {
-        c->h_qbits.reserve(rb_base[nchunk] + 2); c->h_sc.reserve(sc_base[nchunk] + 1);
-        c->h_pos.reserve(rbase + n); c->h_mapq.reserve(rbase + n);
-        c->h_wide_idx.reserve(c->h_wide_idx.size() + n_wide_new); c->h_wide_pos.reserve(c->h_wide_pos.size() + n_wide_new);
+        c->hs.qbits.reserve(rb_base[nchunk] + 2); c->hs.sc.reserve(sc_base[nchunk] + 1);
+        c->hs.pos.reserve(rbase + n); c->hs.mapq.reserve(rbase + n);
+        c->hs.wide_idx.reserve(c->hs.wide_idx.size() + n_wide_new); c->hs.wide_pos.reserve(c->hs.wide_pos.size() + n_wide_new);
     } catch (const std::bad_alloc &) {
         return refuse(CL_ERR_NOMEM, "host staging allocation failed");
     }
-    uint64_t *const bits = c->h_qbits.data();
-    uint32_t *const scw = c->h_sc.data();
+    uint64_t *const bits = c->hs.qbits.data();
+    uint32_t *const scw = c->hs.sc.data();
     // ---- then: what needs the quality bytes -- the base-quality test (one bit per base), the reads' shares of
     //      summed_baseq, and the bits of every read that is not a plain match mapped through its CIGAR into reference
     //      order -- written straight to their place (the chunks' ranges are disjoint) ----
     std::atomic<bool> oom{false};
     dut::parallel_for(nchunk, 1, [&](size_t k) {
-        Chunk &o = ch[k];
+        uint64_t sum_q = 0;
         const size_t a = k * grain, b = std::min<size_t>(n, a + grain);
         uint64_t wat = rb_base[k], sat = sc_base[k];
         RawVec<uint64_t> qw;                                    // a read's query-order bits
@@ -1399,7 +1398,7 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
             if (pbits) {
                 // the packed variant: the bits are there, in query order from bit qual_off[i]
                 const bool sparse = (cnt & dut::kRowSparse) != 0ull;
-                o.sum_q += psum[i];
+                sum_q += psum[i];
                 if (nops == 1u) copy_bits_to_words(bits + wat, pbits, t->qual_off[i], std::min<uint64_t>(span, ql));
                 else if (sparse) {
                     copy_bits_to_words(bits + wat, pbits, t->qual_off[i], ql);
@@ -1413,7 +1412,7 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
                     dut::ref_bits_from_query(qw.data(), ql, cig, nops, bits + wat, um.data(), &n_um, &qlen);
                 }
             } else if (nops == 1u) {
-                o.sum_q += dut::qual_pass_read(q, std::min<uint64_t>(span, ql), min_bq, bits + wat, plevel);
+                sum_q += dut::qual_pass_read(q, std::min<uint64_t>(span, ql), min_bq, bits + wat, plevel);
             } else {
                 const uint64_t nqw = (ql + 63) >> 6;
                 const bool sparse = (cnt & dut::kRowSparse) != 0ull;
@@ -1439,29 +1438,27 @@ static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, uint32_t cig0
                     // ... mapped through the CIGAR into reference order, here where the operations are in the cache
                     dut::ref_bits_from_query(qw.data(), ql, cig, nops, bits + wat, um.data(), &n_um, &qlen);
                 }
-                o.sum_q += all - dut::unmatched_pass_sum(q, ql, um.data(), n_um, qlen, min_bq);   // ... minus those of inserted / clipped bases
+                sum_q += all - dut::unmatched_pass_sum(q, ql, um.data(), n_um, qlen, min_bq);   // ... minus those of inserted / clipped bases
             }
             wat += nw; sat += nsc;
         }
         } catch (const std::bad_alloc &) { oom.store(true); }
+        ch[k].sum_q = sum_q;
     });
     tmr.lap("push: pass bits in reference order");
     if (oom.load()) return refuse(CL_ERR_NOMEM, "host staging allocation failed");
     // ---- the tile is accepted (nothing below can fail: the capacity is there) ----
     for (const Chunk &o : ch) {
-        c->host_err |= o.err; c->host_sum_q += o.sum_q; c->host_n_ops += o.n_ops;
-        c->host_sum_cov += o.sum_cov; c->host_sum_mapq += o.sum_mapq;
-        c->span_n = std::max(c->span_n, o.span_n); c->span_w = std::max(c->span_w, o.span_w);
-        c->host_max_end = std::max(c->host_max_end, o.max_end);
-        for (uint32_t i : o.wide) { c->h_wide_idx.push_back((uint32_t)(rbase + i)); c->h_wide_pos.push_back(t->pos[i]); }
+        walk_fold(c, o, rbase, t->pos);
+        c->host_sum_q += o.sum_q; c->host_n_ops += o.n_ops; c->host_sum_cov += o.sum_cov; c->host_sum_mapq += o.sum_mapq;
     }
-    c->h_qbits.resize(rb_base[nchunk]); c->h_sc.resize(sc_base[nchunk]);
-    c->h_qbits.data()[rb_base[nchunk]] = 0ull;                 // the word deposit_bits may read behind the last string
-    c->h_end.resize(rbase + n); c->h_rec_cnt.resize(rbase + n);
-    c->h_rb_off.resize(rbase + n + 1); c->h_sc_off.resize(rbase + n + 1);
+    c->hs.qbits.resize(rb_base[nchunk]); c->hs.sc.resize(sc_base[nchunk]);
+    c->hs.qbits.data()[rb_base[nchunk]] = 0ull;                 // the word deposit_bits may read behind the last string
+    c->hs.end.resize(rbase + n); c->hs.rec_cnt.resize(rbase + n);
+    c->hs.rb_off.resize(rbase + n + 1); c->hs.sc_off.resize(rbase + n + 1);
     rb_off[n] = rb_base[nchunk]; sc_off[n] = (uint32_t)sc_base[nchunk];
-    c->h_pos.append(t->pos, n);
-    c->h_mapq.append(t->mapq, n);
+    c->hs.pos.append(t->pos, n);
+    c->hs.mapq.append(t->mapq, n);
     tmr.lap("push: stage small arrays");
     c->q_dev += nq;                                          // (the contig's quality bytes so far: none on the device)
     return CL_OK;
@@ -1476,11 +1473,11 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
     const uint64_t n = h.n, q0 = h.q0, ncig = h.ncig, nq = h.nq;
     const uint32_t cig0 = h.cig0;
     if (nq && !t->qual) return fail(c, CL_ERR_INVALID, "null qual array");
-    if (c->h_cigar.size() + ncig > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "more than 2^32 CIGAR operations in one contig");
-    if (c->q_dev + c->h_qual.size() + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality bytes in one contig");
-    if (c->bits) return push_reads_bits(c, t, cig0, q0, ncig, nq);      // the pass-bit form: no quality byte goes to the device
-    const uint32_t cbase = (uint32_t)c->h_cigar.size();
-    const uint64_t rbase = c->h_pos.size();
+    if (c->hs.cigar.size() + ncig > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "more than 2^32 CIGAR operations in one contig");
+    if (c->q_dev + c->hs.qual.size() + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality bytes in one contig");
+    if (c->bits) return push_reads_bits(c, t, h);      // the pass-bit form: no quality byte goes to the device
+    const uint32_t cbase = (uint32_t)c->hs.cigar.size();
+    const uint64_t rbase = c->hs.pos.size();
 
     // ---- a large tile: its quality bytes go from the caller's buffer to the device through the pinned staging
     //      ring, and they start now (unless cl_contig_prefetch_qual already sent exactly these bytes): the copier
@@ -1491,7 +1488,7 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
     const bool direct = nq >= kDirectQual;
     if (direct) {
         const uint8_t *src = t->qual + q0;
-        const bool prefetched = c->pf_active && c->pf_src == src && c->pf_n == nq && c->h_qual.empty() && c->pf_off == c->q_dev;
+        const bool prefetched = c->pf_active && c->pf_src == src && c->pf_n == nq && c->hs.qual.empty() && c->pf_off == c->q_dev;
         if (prefetched) {
             c->pf_active = false; c->pf_src = nullptr; c->pf_n = 0;
             ring.active = true;                               // the transfer in flight is this tile's
@@ -1510,7 +1507,7 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
     } else if (c->pf_active) {
         drop_prefetch(c);
     }
-    const unsigned long long qbase = c->q_dev + c->h_qual.size();
+    const unsigned long long qbase = c->q_dev + c->hs.qual.size();
     StageTimer tmr;
 
     // ---- the one walk over every CIGAR of the tile: validation that protects the kernels' indexing; the end of every
@@ -1524,36 +1521,31 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
     // that every thread has some)
     const size_t grain = dut::grain_for(n, 65536);
     const size_t nchunk = (n + grain - 1) / grain;
-    struct Chunk { int bad = 0; uint32_t n_long = 0, err = 0; uint32_t span_n = 0, span_w = 0; uint64_t max_end = 0; std::vector<uint32_t> wide; };
+    struct Chunk : WalkChunk { uint32_t n_long = 0; };
     std::vector<Chunk> ch(nchunk);
-    const int32_t last0 = c->h_pos.empty() ? 0 : c->h_pos.back();
+    const int32_t last0 = c->hs.pos.empty() ? 0 : c->hs.pos.back();
     try {
-        c->h_rec_cnt.reserve(rbase + n);
-        c->h_end.reserve(rbase + n);                           // entries [rbase, rbase + n) are written below; the
-        c->h_ck_x.reserve(((cbase + ncig) >> 6) + 2);          // sizes follow when the tile is accepted (a refused
-        c->h_ck_y.reserve(((cbase + ncig) >> 6) + 2);          // tile leaves only unused capacity behind)
+        c->hs.rec_cnt.reserve(rbase + n);
+        c->hs.end.reserve(rbase + n);                           // entries [rbase, rbase + n) are written below; the
+        c->hs.ck_x.reserve(((cbase + ncig) >> 6) + 2);          // sizes follow when the tile is accepted (a refused
+        c->hs.ck_y.reserve(((cbase + ncig) >> 6) + 2);          // tile leaves only unused capacity behind)
     } catch (const std::bad_alloc &) {
         return fail(c, CL_ERR_NOMEM, "host staging allocation failed");
     }
-    uint32_t *const h_end = c->h_end.data() + rbase, *const h_ck_x = c->h_ck_x.data(), *const h_ck_y = c->h_ck_y.data();
-    uint32_t *const h_rec_cnt = c->h_rec_cnt.data() + rbase;
+    uint32_t *const h_end = c->hs.end.data() + rbase, *const h_ck_x = c->hs.ck_x.data(), *const h_ck_y = c->hs.ck_y.data();
+    uint32_t *const h_rec_cnt = c->hs.rec_cnt.data() + rbase;
     const uint32_t min_mapq = c->opt.min_mapping_quality;
     // (a tile of long-read shape -- 8 or more operations per read -- will not get the short-read form: its reads'
     // records are not counted here, that would be a second pass over every operation)
     const bool count_recs = ncig < 8ull * n;
     dut::parallel_for(nchunk, 1, [&](size_t k) {
-        Chunk &o = ch[k];
+        Chunk o;                                                // (on the walker's stack: neighbouring chunks of ch share cache lines)
         const size_t a = k * grain, b = std::min<size_t>(n, a + grain);
         int32_t last = a ? t->pos[a - 1] : last0;
         for (size_t i = a; i < b; ++i) {
             const int32_t p = t->pos[i];
-            if (p < 0 || (uint32_t)p >= c->contig_len) { if (!o.bad) o.bad = 1; }
-            else if (p < last) { if (!o.bad) o.bad = 2; }
-            last = p;
             h_end[i] = (uint32_t)p; h_rec_cnt[i] = 0u;
-            if (t->cigar_off[i + 1] < t->cigar_off[i] || t->qual_off[i + 1] < t->qual_off[i]) { if (!o.bad) o.bad = 3; continue; }
-            if (t->cigar_off[i] < cig0 || t->cigar_off[i + 1] > cig0 + ncig) { if (!o.bad) o.bad = 3; continue; }
-            if (t->qual_off[i] < q0 || t->qual_off[i + 1] > q0 + nq) { if (!o.bad) o.bad = 3; continue; }
+            if (!walk_read_checks(o, t, i, last, c->contig_len, h)) continue;
             const uint32_t q0i = t->cigar_off[i], q1i = t->cigar_off[i + 1], nops = q1i - q0i;
             unsigned long long l = 0;
             if (nops <= kLongOps) {
@@ -1583,12 +1575,7 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
                     if (radv && len == 0u) o.err |= kErrCigar;
                 }
             }
-            const uint32_t sp = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
-            // an end beyond the engine's 32-bit coordinate range: flagged; the read then spans nothing
-            if (l <= 0xFFFF0000ull - (uint64_t)p) { h_end[i] = (uint32_t)((uint64_t)p + l); o.max_end = std::max<uint64_t>(o.max_end, (uint64_t)p + l); }
-            else o.err |= kErrRange;
-            if (sp > kWideSpan) { o.wide.push_back((uint32_t)i); o.span_w = std::max(o.span_w, sp); }
-            else o.span_n = std::max(o.span_n, sp);
+            walk_close_span(o, i, p, l, h_end[i]);
             // the records the short-read form would get for this read (counted here, where its CIGAR is hot)
             if (count_recs) {
                 const unsigned long long ql = t->qual_off[i + 1] - t->qual_off[i];
@@ -1601,6 +1588,7 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
                 h_rec_cnt[i] = cnt;
             }
         }
+        ch[k] = std::move(o);
     });
     tmr.lap("push: validate + spans");
     for (const Chunk &o : ch)                                  // the first offence in tile order decides the message
@@ -1613,34 +1601,32 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
         ~Undo()
         {
             if (!armed) return;
-            c->h_pos.resize(n_pos); c->h_mapq.resize(n_pos); c->h_cigar.resize(n_cig); c->h_qual.resize(n_qual);
-            c->h_cigar_off.resize(n_pos + 1); c->h_qual_off.resize(n_pos + 1);
-            c->h_wide_idx.resize(n_wide); c->h_wide_pos.resize(n_wide); c->n_long = n_long; c->host_err = host_err;
-            c->h_end.resize(n_pos); c->h_ck_x.resize((n_cig >> 6) + 2); c->h_ck_y.resize((n_cig >> 6) + 2);
-            c->h_rec_cnt.resize(n_pos);
+            c->hs.pos.resize(n_pos); c->hs.mapq.resize(n_pos); c->hs.cigar.resize(n_cig); c->hs.qual.resize(n_qual);
+            c->hs.cigar_off.resize(n_pos + 1); c->hs.qual_off.resize(n_pos + 1);
+            c->hs.wide_idx.resize(n_wide); c->hs.wide_pos.resize(n_wide); c->n_long = n_long; c->host_err = host_err;
+            c->hs.end.resize(n_pos); c->hs.ck_x.resize((n_cig >> 6) + 2); c->hs.ck_y.resize((n_cig >> 6) + 2);
+            c->hs.rec_cnt.resize(n_pos);
             c->has_long = has_long; c->span_n = span_n; c->span_w = span_w; c->host_max_end = max_end;
         }
-    } undo{c, c->h_pos.size(), c->h_cigar.size(), c->h_qual.size(), c->h_wide_idx.size(), c->n_long, c->host_err, c->has_long, c->span_n, c->span_w, c->host_max_end};
+    } undo{c, c->hs.pos.size(), c->hs.cigar.size(), c->hs.qual.size(), c->hs.wide_idx.size(), c->n_long, c->host_err, c->has_long, c->span_n, c->span_w, c->host_max_end};
     try {
         for (const Chunk &o : ch) {
+            walk_fold(c, o, rbase, t->pos);
             if (o.n_long) c->has_long = true;
-            c->n_long += o.n_long; c->host_err |= o.err;
-            c->span_n = std::max(c->span_n, o.span_n); c->span_w = std::max(c->span_w, o.span_w);
-            c->host_max_end = std::max(c->host_max_end, o.max_end);
-            for (uint32_t i : o.wide) { c->h_wide_idx.push_back((uint32_t)(rbase + i)); c->h_wide_pos.push_back(t->pos[i]); }
+            c->n_long += o.n_long;
         }
-        c->h_end.resize(rbase + n); c->h_ck_x.resize(((cbase + ncig) >> 6) + 2); c->h_ck_y.resize(((cbase + ncig) >> 6) + 2);
-        c->h_rec_cnt.resize(rbase + n);
+        c->hs.end.resize(rbase + n); c->hs.ck_x.resize(((cbase + ncig) >> 6) + 2); c->hs.ck_y.resize(((cbase + ncig) >> 6) + 2);
+        c->hs.rec_cnt.resize(rbase + n);
         if (!count_recs) c->rec_counted = false;
-        c->h_pos.append(t->pos, n);
-        c->h_mapq.append(t->mapq, n);
-        c->h_cigar.append(t->cigar + cig0, ncig);
-        if (!direct) c->h_qual.insert(c->h_qual.end(), t->qual + q0, t->qual + q0 + nq);
-        const size_t o0 = c->h_cigar_off.size();               // == rbase + 1: entry r+1 closes read r
-        c->h_cigar_off.resize(o0 + n);
-        c->h_qual_off.resize(o0 + n);
-        uint32_t *co = c->h_cigar_off.data() + o0 - 1;
-        unsigned long long *qo = c->h_qual_off.data() + o0 - 1;
+        c->hs.pos.append(t->pos, n);
+        c->hs.mapq.append(t->mapq, n);
+        c->hs.cigar.append(t->cigar + cig0, ncig);
+        if (!direct) c->hs.qual.insert(c->hs.qual.end(), t->qual + q0, t->qual + q0 + nq);
+        const size_t o0 = c->hs.cigar_off.size();               // == rbase + 1: entry r+1 closes read r
+        c->hs.cigar_off.resize(o0 + n);
+        c->hs.qual_off.resize(o0 + n);
+        uint32_t *co = c->hs.cigar_off.data() + o0 - 1;
+        unsigned long long *qo = c->hs.qual_off.data() + o0 - 1;
         dut::parallel_for(n, 262144, [&](size_t i) {
             co[i + 1] = cbase + (t->cigar_off[i + 1] - cig0);
             qo[i + 1] = qbase + (t->qual_off[i + 1] - q0);
@@ -1674,15 +1660,14 @@ cl_status cl_push_reads_bits(cl_ctx *c, const cl_read_tile_bits *b)
         TileHead h;
         const cl_status hs = tile_header(c, "cl_push_reads_bits", b->n_reads, b->pos, b->mapq, b->cigar_off, b->cigar, b->qual_off, h);
         if (hs != CL_OK || h.n == 0) return hs;
-        const uint64_t n = h.n, q0 = h.q0, ncig = h.ncig, nq = h.nq;
-        const uint32_t cig0 = h.cig0;
+        const uint64_t n = h.n, nq = h.nq;
         if (nq && (!b->pass_bits || !b->pass_sum)) return fail(c, CL_ERR_INVALID, "null pass_bits / pass_sum array");
         if (c->q_dev + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality values in one contig");
         cl_read_tile t;
         t.n_reads = n; t.pos = b->pos; t.mapq = b->mapq; t.cigar_off = b->cigar_off; t.cigar = b->cigar; t.qual_off = b->qual_off; t.qual = nullptr;
         static const uint64_t kNoBits[2] = {0, 0};
         static const uint32_t kNoSum[1] = {0};
-        return push_reads_bits(c, &t, cig0, q0, ncig, nq, b->pass_bits ? b->pass_bits : kNoBits, b->pass_sum ? b->pass_sum : kNoSum);
+        return push_reads_bits(c, &t, h, b->pass_bits ? b->pass_bits : kNoBits, b->pass_sum ? b->pass_sum : kNoSum);
     });
 }
 
@@ -1694,15 +1679,15 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     HIP_TRY(c, hipSetDevice(c->device));
     drop_prefetch(c);
     join_prealloc(c);
-    c->n_reads = (uint32_t)c->h_pos.size();
-    c->n_cigar = c->bits ? c->host_n_ops : c->h_cigar.size();
+    c->n_reads = (uint32_t)c->hs.pos.size();
+    c->n_cigar = c->bits ? c->host_n_ops : c->hs.cigar.size();
     if (!c->bits) {
         cl_status fs = flush_staged_qual(c);
         if (fs != CL_OK) return fs;
     }
     c->n_qual = c->q_dev;
     c->dev_sum_q = c->host_sum_q; c->dev_sum_cov = c->bits ? c->host_sum_cov : 0; c->dev_sum_mapq = c->bits ? c->host_sum_mapq : 0;
-    c->n_wide = (uint32_t)c->h_wide_idx.size();
+    c->n_wide = (uint32_t)c->hs.wide_idx.size();
     const size_t n = c->n_reads;
     c->form = pick_form(c);
     const int form = c->form;
@@ -1724,11 +1709,11 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     if (form == 2) {
         HIP_TRY(c, c->d_pos.reserve(n + 1));
         HIP_TRY(c, c->d_mapq.reserve(n + 1));
-        if ((rs = ring_copy(c, c->d_pos.p, c->h_pos.data(), n * sizeof(int32_t))) != CL_OK) return rs;
-        if ((rs = ring_copy(c, c->d_mapq.p, c->h_mapq.data(), n)) != CL_OK) return rs;
-        if ((rs = ring_copy(c, c->d_end.p, c->h_end.data(), n * sizeof(uint32_t))) != CL_OK) return rs;
+        if ((rs = ring_copy(c, c->d_pos.p, c->hs.pos.data(), n * sizeof(int32_t))) != CL_OK) return rs;
+        if ((rs = ring_copy(c, c->d_mapq.p, c->hs.mapq.data(), n)) != CL_OK) return rs;
+        if ((rs = ring_copy(c, c->d_end.p, c->hs.end.data(), n * sizeof(uint32_t))) != CL_OK) return rs;
     }
-    c->h_rec_of.clear(); c->h_wide_rec_of.clear(); c->n_rec = 0;
+    c->hs.rec_of.clear(); c->hs.wide_rec_of.clear(); c->n_rec = 0;
     if (form == 3) {
         // the heads (kernels.hip.h): 8 bytes per read the pileup holds -- [pos, pos + span) and whether its mapq counts
         // as low (mod.rs:22-28) --, built straight into the pinned buffers; a span beyond kHeadSpanMax is cut into
@@ -1737,29 +1722,16 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
         tmr.lap("upload: record index");
         const uint32_t n_rec = c->n_rec;
         HIP_TRY(c, c->d_heads.reserve((size_t)n_rec + 1));
-        const int32_t *hp = c->h_pos.data(); const uint8_t *hm = c->h_mapq.data(); const uint32_t *he = c->h_end.data();
-        const uint32_t *ro = c->h_rec_of.data();
+        const int32_t *hp = c->hs.pos.data(); const uint8_t *hm = c->hs.mapq.data(); const uint32_t *he = c->hs.end.data();
+        const uint32_t *ro = c->hs.rec_of.data();
         const uint32_t max_low = c->opt.max_low_mapq, hs = c->head_span;
         rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_heads.p), ((uint64_t)n_rec + 1) * sizeof(uint2),
-                        [hp, hm, he, ro, n, n_rec, max_low, hs](uint64_t off, uint64_t len, uint8_t *out) {
-            uint2 *o = reinterpret_cast<uint2 *>(out);
-            const uint64_t j0 = off / sizeof(uint2), j1 = (off + len) / sizeof(uint2);
-            if (j1 > n_rec) memset(static_cast<void *>(o + (std::max<uint64_t>(n_rec, j0) - j0)), 0, (j1 - std::max<uint64_t>(n_rec, j0)) * sizeof(uint2));   // the padding head
-            if (j0 >= n_rec) return;
-            // the read that holds head j0: the last one whose range starts at or before it
-            size_t i = (size_t)(std::upper_bound(ro, ro + n + 1, (uint32_t)j0) - ro) - 1;
-            for (; i < n && ro[i] < j1; ++i) {
-                const uint64_t jb = ro[i], je = ro[i + 1];
-                const uint32_t low = (uint32_t)hm[i] <= max_low ? 0x80000000u : 0u;
-                uint64_t x = (uint32_t)hp[i];
-                const uint64_t e = he[i];
-                for (uint64_t j = jb; j < je; ++j, x += hs) {
-                    if (j < j0 || j >= j1) continue;
-                    const uint64_t sp = std::min<uint64_t>(hs, e - x);
-                    o[j - j0] = make_uint2((uint32_t)x, (uint32_t)sp | low);
-                }
-            }
-        }, rec_chunk_bytes());
+                        rec_range_fill<uint2>(ro, n, n_rec, [hp, hm, he, ro, max_low, hs](size_t i, auto &&put) {
+            const uint32_t low = (uint32_t)hm[i] <= max_low ? 0x80000000u : 0u, cnt = ro[i + 1] - ro[i];
+            uint64_t x = (uint32_t)hp[i];
+            const uint64_t e = he[i];
+            for (uint32_t k = 0; k < cnt; ++k, x += hs) put(k, make_uint2((uint32_t)x, (uint32_t)std::min<uint64_t>(hs, e - x) | low));
+        }), rec_chunk_bytes());
         if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
         if (rs != CL_OK) return rs;
         tmr.lap("upload: heads built + sent");
@@ -1773,9 +1745,9 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
         tmr.lap("upload: record index");
         const uint32_t n_rec = c->n_rec;
         HIP_TRY(c, c->d_rec.reserve((size_t)n_rec + 1));
-        const int32_t *hp = c->h_pos.data(); const uint8_t *hm = c->h_mapq.data(); const uint32_t *he = c->h_end.data();
-        const uint32_t *hc = c->h_cigar_off.data(), *hcig = c->h_cigar.data(); const unsigned long long *hq = c->h_qual_off.data();
-        const uint32_t *ro = c->h_rec_of.data();
+        const int32_t *hp = c->hs.pos.data(); const uint8_t *hm = c->hs.mapq.data(); const uint32_t *he = c->hs.end.data();
+        const uint32_t *hc = c->hs.cigar_off.data(), *hcig = c->hs.cigar.data(); const unsigned long long *hq = c->hs.qual_off.data();
+        const uint32_t *ro = c->hs.rec_of.data();
         const uint32_t min_mapq = c->opt.min_mapping_quality;
         // byte form: k_pileup loads 16-byte units around a record's run [qoff, qoff + len): within 15 bytes of its ends,
         // which the padding of the quality array covers as long as the run itself lies inside [0, n_qual] -- checked for
@@ -1785,21 +1757,11 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
         const unsigned long long nq_all = c->n_qual;
         const size_t inject_read = fault_injected("rec") ? n / 2 : (size_t)-1;
         rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_rec.p), ((uint64_t)n_rec + 1) * sizeof(ReadRec),
-                        [hp, hm, he, hc, hcig, hq, ro, n, n_rec, min_mapq, roor, nq_all, inject_read](uint64_t off, uint64_t len, uint8_t *out) {
-            ReadRec *o = reinterpret_cast<ReadRec *>(out);
-            const uint64_t j0 = off / sizeof(ReadRec), j1 = (off + len) / sizeof(ReadRec);
-            if (j1 > n_rec) memset(static_cast<void *>(o + (std::max<uint64_t>(n_rec, j0) - j0)), 0, (j1 - std::max<uint64_t>(n_rec, j0)) * sizeof(ReadRec));   // the padding record
-            if (j0 >= n_rec) return;
-            // the read that holds record j0: the last one whose range starts at or before it
-            size_t i = (size_t)(std::upper_bound(ro, ro + n + 1, (uint32_t)j0) - ro) - 1;
-            for (; i < n && ro[i] < j1; ++i) {
-                const uint64_t jb = ro[i];
-                const unsigned long long q0i = hq[i] + (i == inject_read ? 0x7FFFFFF0ull : 0ull);
-                if (q0i + (hq[i + 1] - hq[i]) > nq_all) roor->store(true, std::memory_order_relaxed);   // (runs lie inside the read's bytes)
-                gen_read_recs(hp[i], he[i], hm[i], min_mapq, hcig + hc[i], hc[i + 1] - hc[i], q0i, hq[i + 1] - hq[i],
-                              [&](uint32_t k, const ReadRec &r) { const uint64_t j = jb + k; if (j >= j0 && j < j1) o[j - j0] = r; });
-            }
-        }, rec_chunk_bytes());
+                        rec_range_fill<ReadRec>(ro, n, n_rec, [hp, hm, he, hc, hcig, hq, min_mapq, roor, nq_all, inject_read](size_t i, auto &&put) {
+            const unsigned long long q0i = hq[i] + (i == inject_read ? 0x7FFFFFF0ull : 0ull);
+            if (q0i + (hq[i + 1] - hq[i]) > nq_all) roor->store(true, std::memory_order_relaxed);   // (runs lie inside the read's bytes)
+            gen_read_recs(hp[i], he[i], hm[i], min_mapq, hcig + hc[i], hc[i + 1] - hc[i], q0i, hq[i + 1] - hq[i], put);
+        }), rec_chunk_bytes());
         if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
         if (rs != CL_OK) return rs;
         if (rec_oor.load()) return fail(c, CL_ERR_RANGE, "a read record addresses quality bytes outside the resident array");
@@ -1807,17 +1769,17 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     }
     std::vector<uint32_t> wide_rec;                      // record forms: the wide reads' records, read by read
     if (c->n_wide && form != 2) {
-        c->h_wide_rec_of.assign(c->n_wide + 1, 0u);
+        c->hs.wide_rec_of.assign(c->n_wide + 1, 0u);
         for (uint32_t j = 0; j < c->n_wide; ++j) {
-            const uint32_t i = c->h_wide_idx[j];
-            for (uint32_t r = c->h_rec_of[i]; r < c->h_rec_of[i + 1]; ++r) wide_rec.push_back(r);
-            c->h_wide_rec_of[j + 1] = (uint32_t)wide_rec.size();
+            const uint32_t i = c->hs.wide_idx[j];
+            for (uint32_t r = c->hs.rec_of[i]; r < c->hs.rec_of[i + 1]; ++r) wide_rec.push_back(r);
+            c->hs.wide_rec_of[j + 1] = (uint32_t)wide_rec.size();
         }
         HIP_TRY(c, c->d_wide_idx.reserve(wide_rec.size() + 1));
         if (!wide_rec.empty())
             HIP_TRY(c, hipMemcpyAsync(c->d_wide_idx.p, wide_rec.data(), wide_rec.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     } else if (c->n_wide) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_wide_idx.p, c->h_wide_idx.data(), c->n_wide * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_wide_idx.p, c->hs.wide_idx.data(), c->n_wide * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     }
     if (!c->bits && c->d_qual.p) {
         HIP_TRY(c, hipMemsetAsync(c->d_qual.p, 0, kQualPad, c->stream));
@@ -1835,12 +1797,7 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     // The staged copy is no longer needed; its memory goes to the process's staging pool for the next contig, this
     // context's or another's (giving back and re-faulting a few hundred megabytes per contig was a fifth of a contig's
     // host time).
-    c->h_pos.clear(); c->h_mapq.clear(); c->h_cigar.clear(); c->h_cigar_off.clear(); c->h_qual_off.clear(); c->h_ref.clear();
-    c->h_end.clear(); c->h_ck_x.clear(); c->h_ck_y.clear(); c->h_qbits.clear(); c->h_rb_off.clear(); c->h_sc_off.clear(); c->h_sc.clear();
-    c->h_rec_of.clear(); c->h_wide_rec_of.clear();       // (capacity kept for the context's next contig)
-    c->h_rec_cnt.clear();
     give_staging(c);
-    std::vector<uint8_t>().swap(c->h_qual);
     tmr.lap("upload: done");
     c->uploaded = true; c->ran = false;
     return CL_OK;
@@ -1931,7 +1888,7 @@ cl_status cl_debug_pass_rows(cl_ctx *c, uint32_t *n_groups, uint32_t n_win_cap, 
             // long reads --, the others carried over from the window before, as inside a range)
             act.clear();
             if (w % 3u == 0u) {
-                for (uint32_t i = 0; i < m.wn; ++i) dut::rows_enter(act, H, c->h_wide_idx[m.wlo + i], W);
+                for (uint32_t i = 0; i < m.wn; ++i) dut::rows_enter(act, H, c->hs.wide_idx[m.wlo + i], W);
                 for (uint32_t r = m.lo; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
             } else {
                 act = save;
@@ -2068,9 +2025,7 @@ cl_status cl_contig_abort(cl_ctx *c)
         join_prealloc(c);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
     }
-    c->h_pos.clear(); c->h_mapq.clear(); c->h_cigar.clear(); c->h_cigar_off.clear(); c->h_qual_off.clear(); c->h_ref.clear();
-    c->h_end.clear(); c->h_ck_x.clear(); c->h_ck_y.clear(); c->h_qual.clear(); c->h_qbits.clear(); c->h_rec_cnt.clear();
-    c->h_rb_off.clear(); c->h_sc_off.clear(); c->h_sc.clear();
+    c->hs.clear();
     c->q_dev = 0; c->host_sum_q = 0; c->host_n_ops = 0; c->host_sum_cov = 0; c->host_sum_mapq = 0;
     c->in_contig = false; c->uploaded = false; c->ran = false;
     return CL_OK;

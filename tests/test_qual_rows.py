@@ -287,3 +287,70 @@ def test_rows_of_gapped_reads_and_every_cigar_shape():
     for o in (None, dict(min_mapping_quality=0, min_base_quality=0), dict(min_base_quality=36)):
         check(rec, L, o, seed=3)
         check(rec, L, o, tiles=[(0, rec.n)])
+
+
+def _staging_contigs():
+    """contig A: 6 000 positions (three windows by its length; the wide read overhangs its end, so the extent is larger)
+    with one read wider than kWideSpan (16 384), one gapped read whose span exceeds 4 * qlen + 1024 (kept in query order:
+    the sparse path), one read of more than kLongOps (64) operations, and ordinary reads; contig B: another length, other
+    reads of the same kinds; and a tile that is refused: a wide and a sparse read, out of order."""
+    rng = np.random.default_rng(2024)
+
+    def quals(cig):
+        from decodingustools_amd.records import cigar_from_string, cigar_query_length
+        return [int(x) for x in rng.choice([5, 19, 20, 35, 255], size=cigar_query_length(cigar_from_string(cig)))]
+
+    def contig(L, n_plain, wide_at, sparse_at, long_at):
+        reads = [(wide_at, "4000M12500D100M", 60), (sparse_at, "30M5000N30M", 60), (long_at, "7M1I" * 40, 60)]
+        for _ in range(n_plain):
+            reads.append((int(rng.integers(0, L - 100)), str(rng.choice(["100M", "50M2D50M", "5S90M5S", "60M3I37M"])),
+                          int(rng.choice([9, 60, 60, 60]))))
+        reads.sort(key=lambda r: r[0])
+        return ContigRecords.from_reads([(p, cig, mq, quals(cig)) for p, cig, mq in reads])
+    rec_a, rec_b = contig(6000, 40, 700, 2500, 1900), contig(9000, 30, 3000, 100, 5000)
+    refused = ContigRecords.from_reads([(p, cig, 60, quals(cig)) for p, cig in ((5000, "100M"), (5100, "4000M12500D100M"),
+                                                                                 (5200, "30M5000N30M"), (4000, "100M"))])
+    return rec_a, rec_b, refused
+
+
+def test_a_context_that_abandoned_a_contig_stages_the_next_one_as_a_fresh_context_does():
+    """The staged arrays of a contig are one object with one clear(): whatever an aborted contig, or a contig left
+    unfinished behind a refused tile, put into them -- wide lists, sparse CIGARs, checkpoints, bit strings -- is gone
+    at the next cl_contig_begin, and a refused tile leaves the contig it was pushed to as it was.  The rows, group
+    counts and summed_baseq of contig A on such a context equal, word for word, those of a fresh context."""
+    opt = CallableOptions()
+    LA, LB = 6000, 9000
+    rec_a, rec_b, refused = _staging_contigs()
+    h = rec_a.n // 2
+
+    def push(st, r, a, b):
+        st.push_reads(r.pos[a:b], r.mapq[a:b], r.cigar_off[a:b + 1], r.cigar, r.qual_off[a:b + 1], r.qual)
+
+    def stage_a(st, refuse_between=False):
+        st.contig_begin(0, LA, None)
+        push(st, rec_a, 0, h)
+        if refuse_between:
+            with pytest.raises(EngineError) as e:
+                push(st, refused, 0, refused.n)
+            assert e.value.status == -3                             # CL_ERR_UNSORTED
+        push(st, rec_a, h, rec_a.n)
+        return st.pass_rows()
+
+    def same(got, want):
+        return np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]) and got[2] == want[2]
+    with HostStage(opt) as st:
+        want = stage_a(st)
+    assert want[0].shape[0] == (700 + 16600 + T - 1) // T            # the extent follows the wide read's end
+    # (what the rows must say, by the checker: the same contig through check())
+    check(rec_a, LA, None, tiles=[(0, h), (h, rec_a.n)])
+    with HostStage(opt) as st:                                       # contig B half way, aborted
+        st.contig_begin(1, LB, None)
+        push(st, rec_b, 0, rec_b.n // 2)
+        st.contig_abort()
+        assert same(stage_a(st), want)
+    with HostStage(opt) as st:                                       # contig B half way, then a refused tile, never aborted
+        st.contig_begin(1, LB, None)
+        push(st, rec_b, 0, rec_b.n // 2)
+        with pytest.raises(EngineError):
+            push(st, refused, 0, refused.n)
+        assert same(stage_a(st, refuse_between=True), want)
