@@ -128,6 +128,7 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     DevBuf<uint2> d_runtab;            // run-table form: the windows' match pieces (host_build_runs)
     uint64_t n_runtab = 0;
     DevBuf<uint32_t> d_lut;
+    DevBuf<uint32_t> d_lut8;         // build_lut8's 64 words, what k_pileup_rows' fast path looks up
     DevBuf<DevSummary> d_summary;
     DevBuf<Interval> d_iv;
     DevBuf<uint32_t> d_dbg;          // 3 * n_win * T
@@ -208,6 +209,18 @@ void build_lut(double frac, std::vector<uint32_t> &lut)
         uint32_t low = g < 0.0 ? 0u : (uint32_t)g;
         while (low <= raw && !(((double)low / (double)raw) > frac)) ++low;
         if (low <= raw) lut[raw] = low;
+    }
+}
+
+// The thresholds of depths 0..255 as bytes, four per word, for k_pileup_rows' fast path (which sees depths below 255 only):
+// 255 = never -- depth 0, a depth below min_depth_for_low_mapq (callable_profiler.rs:100), and a threshold no byte-sized
+// count reaches (a count is at most the depth: below 255 here).
+void build_lut8(const std::vector<uint32_t> &lut, uint32_t min_depth_for_low_mapq, uint32_t (&lut8)[64])
+{
+    for (uint32_t i = 0; i < 256; ++i) {
+        const uint32_t v = (i == 0 || i < min_depth_for_low_mapq || lut[i] > 254u) ? 255u : lut[i];
+        if (i % 4 == 0) lut8[i / 4] = 0;
+        lut8[i / 4] |= v << (8 * (i % 4));
     }
 }
 
@@ -935,10 +948,18 @@ template <bool DEBUG> void launch_pileup(cl_ctx *c, const PileupArgs &a)
     if (grid == 0) return;
 #define CL_LAUNCH(DEEP_, LONG_) hipLaunchKernelGGL((k_pileup<(int)kT, DEBUG, DEEP_, LONG_>), dim3(grid), dim3(kBlock), 0, c->stream, a)
 #define CL_LAUNCH_L(DEEP_) do { if (c->form == 2) CL_LAUNCH(DEEP_, 2); else CL_LAUNCH(DEEP_, 0); } while (0)
-#define CL_LAUNCH_R(DEEP_, NP_) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, CL_ROWS_BLOCK>), dim3(grid), dim3(CL_ROWS_BLOCK), 0, c->stream, a)
+#define CL_LAUNCH_R(DEEP_, NP_) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, CL_ROWS_BLOCK>), dim3(grid), dim3(CL_ROWS_BLOCK), 0, c->stream, ra)
 #define CL_LAUNCH_RN(DEEP_) do { if (c->max_groups <= 63u) CL_LAUNCH_R(DEEP_, 8); else if (c->max_groups <= 16383u) CL_LAUNCH_R(DEEP_, 16); else CL_LAUNCH_R(DEEP_, 32); } while (0)
     // the 32-bit counter variant is used only when the window bounds asked for it (kNeedDeep)
     if (c->form == 3) {
+        RowsArgs ra{};
+        ra.rows = a.rows; ra.heads = a.heads; ra.wide_idx = a.wide_idx; ra.win = a.win; ra.refn = a.refn;
+        ra.lut8 = c->d_lut8.p;
+        ra.runs = a.runs; ra.first_state = a.first_state; ra.last_state = a.last_state; ra.winpart = a.winpart;
+        ra.extent = a.extent; ra.n_win = a.n_win; ra.n_win8 = a.n_win8;
+        ra.min_depth = a.o.min_depth; ra.max_depth = a.o.max_depth;
+        ra.min_depth_for_low_mapq = a.o.min_depth_for_low_mapq; ra.lut = a.lut; ra.max_low_mapq_fraction = a.o.max_low_mapq_fraction;
+        ra.state = a.state; ra.dbg_raw = a.dbg_raw; ra.dbg_qc = a.dbg_qc; ra.dbg_low = a.dbg_low;
         // pass-bit form: the counter planes by the deepest window's rows (4 per group): 8 planes count to 255
         if (!c->deep) CL_LAUNCH_RN(false); else CL_LAUNCH_RN(true);
     } else if (!c->deep) CL_LAUNCH_L(false); else CL_LAUNCH_L(true);
@@ -1044,9 +1065,12 @@ cl_status cl_create(const cl_options *opt, int device_id, void *stream, cl_ctx *
 #endif
     std::vector<uint32_t> lut;
     build_lut(opt->max_low_mapq_fraction, lut);
-    bool ok = c->d_lut.reserve(kLutSize) == hipSuccess &&
+    uint32_t lut8[64];
+    build_lut8(lut, opt->min_depth_for_low_mapq, lut8);
+    bool ok = c->d_lut.reserve(kLutSize) == hipSuccess && c->d_lut8.reserve(64) == hipSuccess &&
               c->d_summary.reserve(1) == hipSuccess && c->d_errflag.reserve(2) == hipSuccess &&
-              hipMemcpy(c->d_lut.p, lut.data(), kLutSize * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess;
+              hipMemcpy(c->d_lut.p, lut.data(), kLutSize * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(c->d_lut8.p, lut8, sizeof(lut8), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok || ensure_pins(c) != CL_OK) { cl_destroy(c); return CL_ERR_DEVICE; }
     *out = c;
     return CL_OK;
@@ -1067,7 +1091,7 @@ void cl_destroy(cl_ctx *c)
     c->d_win.release(); c->d_win_off.release(); c->d_state.release();
     c->d_wide_idx.release();
     c->d_runs.release(); c->d_first_state.release(); c->d_last_state.release(); c->d_win_wide.release();
-    c->d_winpart.release(); c->d_lut.release(); c->d_summary.release();
+    c->d_winpart.release(); c->d_lut.release(); c->d_lut8.release(); c->d_summary.release();
     c->d_iv.release(); c->d_dbg.release(); c->d_prof.release(); c->d_fin.release(); c->d_errflag.release(); c->d_runtab.release(); c->site.release();
     c->t_prof.destroy();
     if (c->ev_made)
@@ -2101,7 +2125,7 @@ cl_status cl_contig_layout(cl_ctx *c, cl_layout_info *out)
     b += c->d_rows.cap * sizeof(uint4) + c->d_win_off.cap * 4 + c->d_wide_idx.cap * 4 + c->d_win.cap * sizeof(WinMeta);
     b += c->d_state.cap + c->d_runs.cap * 2 + c->d_first_state.cap + c->d_last_state.cap + c->d_win_wide.cap;
     b += c->d_winpart.cap * sizeof(WinPartial) + c->d_fin.cap * sizeof(FinPartial) + c->d_errflag.cap * 4 + c->d_runtab.cap * 8;
-    b += c->d_lut.cap * 4 + c->d_summary.cap * sizeof(DevSummary) + c->d_iv.cap * sizeof(Interval) + c->d_dbg.cap * 4;
+    b += c->d_lut.cap * 4 + c->d_lut8.cap * 4 + c->d_summary.cap * sizeof(DevSummary) + c->d_iv.cap * sizeof(Interval) + c->d_dbg.cap * 4;
     out->device_bytes = b;
     // what cl_contig_upload sent over the link for this contig (every transfer goes through the pinned staging ring)
     const uint64_t padded = (uint64_t)c->n_win * kT + 16;

@@ -22,6 +22,7 @@
 // Integer / byte work throughout: HBM-bound, no MFMA.  Wave = 64 lanes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -1009,8 +1010,42 @@ __device__ __forceinline__ uint32_t bs_less_than(const uint32_t (&c)[NP], unsign
 #ifndef CL_ROWS_BLOCK
 #define CL_ROWS_BLOCK 128
 #endif
+// What k_pileup_rows takes: its own argument record, not PileupArgs -- the scalar registers of a wave are one of the
+// three things that limit the production instantiation's residency (see the LDS comment in the kernel), every argument
+// that is read takes one or two of them, and this kernel reads a third of what the byte forms do.
+struct RowsArgs {
+    const uint4    *rows;         // per window, groups of 4 rows x 64 blocks (host, at upload)
+    const uint2    *heads;        // {pos, span | low << 31} per read with a reference span
+    const uint32_t *wide_idx;     // read indices of the wide reads, ascending
+    const WinMeta  *win;
+    const uint32_t *refn;         // bit p = the reference base at p is 'N' / 'n' (or beyond the reference)
+    const uint32_t *lut8;         // the low-MAPQ thresholds of depths 0..255 as bytes (255 = never): 64 words, built once per
+                                  // engine from its options (callable_loci.hip: build_lut8)
+    uint16_t       *runs;
+    uint8_t        *first_state, *last_state;
+    WinPartial     *winpart;
+    uint32_t        extent, n_win, n_win8;
+    uint32_t        min_depth, max_depth;
+    // the general path (a thread that sees a depth of 255 or more, or DEEP)
+    uint32_t        min_depth_for_low_mapq;
+    const uint32_t *lut;          // kLutSize entries: smallest low count that is "too many"
+    double          max_low_mapq_fraction;
+    // DEBUG instantiations only (test dumps; nullptr otherwise)
+    uint8_t        *state;
+    uint32_t       *dbg_raw, *dbg_qc, *dbg_low;
+};
+// (its one caller starts from `RowsArgs ra{}`: a member added here and not filled there is zero, not garbage)
+
+// the waves per SIMD the register allocation is to leave room for: what LDS admits -- 8 for the production form (16
+// workgroups of 2 waves per CU), 7 for 16 planes without DEEP (12 KB: 13 workgroups), 3 or 4 for the large forms; the
+// DEBUG forms (test dumps: s_dbg adds 2 to 8 KB of LDS) keep the bounds they always had
+constexpr int rows_min_waves(bool DEBUG, bool DEEP, int NP, int BS)
+{
+    if (DEBUG) return (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS == 128 ? 6 : 8);
+    return (DEEP || NP > 16) ? (BS == 128 ? 3 : 4) : (NP > 8 ? (BS == 128 ? 7 : 4) : 8);
+}
 template <int T, bool DEBUG, bool DEEP, int NP, int BS>
-__global__ __launch_bounds__(BS, (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS == 128 ? 6 : 8)) void k_pileup_rows(PileupArgs a)
+__global__ __launch_bounds__(BS, rows_min_waves(DEBUG, DEEP, NP, BS)) void k_pileup_rows(RowsArgs a)
 {
     constexpr int kBlock = BS;                             // (shadows the namespace's 256 inside this kernel)
     constexpr int PER = T / kBlock;
@@ -1020,8 +1055,11 @@ __global__ __launch_bounds__(BS, (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS ==
     constexpr int G = BS == 128 ? 6 : 4;                   // groups a wave has in flight: 12 / 16 per window before a second trip
     __shared__ __attribute__((aligned(16))) uint32_t s_raw[kDiffWords];
     __shared__ __attribute__((aligned(16))) uint32_t s_low[kDiffWords];
-    // LDS: the two difference arrays and ONE pool that is used twice -- 10 240 bytes in all, so that a CU holds 16
-    // workgroups (the kernel's time follows the number of workgroups a CU runs: profiles/r04_occupancy.txt):
+    // LDS: the two difference arrays and ONE pool that is used twice -- 10 240 bytes in all, which admits 16 workgroups
+    // per CU (the kernel's time follows the number of workgroups a CU runs: profiles/r04_occupancy.txt).  LDS is one of
+    // three limits and with 2 waves per workgroup all three must allow 8 waves per SIMD: at most 64 vector registers,
+    // and at most 80 scalar registers (.sgpr_count; 81..96 leave 7 waves = 14 workgroups, 97.. leave 6 = 12, which is
+    // where this kernel stood while the compiler's own figure said 8: profiles/r11_rows_residency.json):
     //   first   the counter planes of waves 1.. (wave 0 adds them to its own after the barrier; it is their only reader)
     //   then    s_lt / s_gt and the low-MAPQ thresholds s_lut: a lane of wave 0 writes its words after it has read its
     //           planes (they lie in the slots of that lane's own planes 0, 1 and kLutPlane of wave 1); s_last, s_wtot, s_wmax:
@@ -1037,7 +1075,7 @@ __global__ __launch_bounds__(BS, (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS ==
     uint8_t *const s_last = reinterpret_cast<uint8_t *>(s_pool + 128);         // kBlock bytes
     unsigned long long (*s_wtot)[12] = reinterpret_cast<unsigned long long (*)[12]>(s_pool + 128 + kBlock / 4);
     uint32_t *const s_wmax = s_pool + 128 + kBlock / 4 + kWaves * 24;
-    // the low-MAPQ thresholds of depths below 255 as bytes: 255 = never (a count is at most the depth)
+    // the low-MAPQ thresholds of depths below 255 as bytes: 255 = never (a count is at most the depth): a copy of a.lut8
     uint8_t *const s_lut = reinterpret_cast<uint8_t *>(s_pool + kLutPlane * 64);
     __shared__ uint32_t s_dbg[DEBUG ? NP : 1][64];         // DEBUG: the window's planes, for the dump of qc_depth
 #ifdef CL_ROWS_LDS_PAD
@@ -1084,6 +1122,9 @@ __global__ __launch_bounds__(BS, (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS ==
     };
     uint2 hh[U];
     load_heads(0u, hh);
+    // ... and wave 0's word of the byte thresholds, which it puts into LDS once it is done with the planes there
+    uint32_t wlut = 0u;
+    if (wv == 0) wlut = a.lut8[lane];
     // (bit p of refn: the reference base at p is 'N' / 'n' or lies beyond the reference, mod.rs:79-80, :100-101)
     const uint32_t refn = PER == 16 ? (uint32_t)reinterpret_cast<const uint16_t *>(a.refn)[(size_t)w * (T / 16) + tid]
                                     : (uint32_t)reinterpret_cast<const uint8_t *>(a.refn)[(size_t)w * (T / 8) + tid];
@@ -1174,26 +1215,15 @@ __global__ __launch_bounds__(BS, (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS ==
             // quality_bases (contig_profiler.rs:71): the sum of the block's 32 counts = sum over the planes of 2^p x set bits
 #pragma unroll
             for (int p = 0; p < NP; ++p) nbits += (unsigned long long)__popc(c[p]) << p;
-            s_lt[lane] = bs_less_than<NP>(c, (unsigned long long)a.o.min_depth);
+            s_lt[lane] = bs_less_than<NP>(c, (unsigned long long)a.min_depth);
             // qc > max_depth  <=>  !(qc < max_depth + 1); the rule is off for max_depth == 0
-            s_gt[lane] = a.o.max_depth > 0u ? ~bs_less_than<NP>(c, (unsigned long long)a.o.max_depth + 1ull) : 0u;
+            s_gt[lane] = a.max_depth > 0u ? ~bs_less_than<NP>(c, (unsigned long long)a.max_depth + 1ull) : 0u;
             if (DEBUG) {
 #pragma unroll
                 for (int p = 0; p < NP; ++p) s_dbg[p][lane] = c[p];
             }
-            // the thresholds of depths 4 lane .. 4 lane + 3, four bytes in the lane's own word
-            {
-                const uint4 lv = reinterpret_cast<const uint4 *>(a.lut)[lane];
-                const uint32_t l4[4] = {lv.x, lv.y, lv.z, lv.w};
-                uint32_t wlut = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t i = 4u * lane + (uint32_t)k;
-                    const uint32_t v = (i >= a.o.min_depth_for_low_mapq && i > 0) ? l4[k] : 0xFFFFFFFFu;
-                    wlut |= (v > 254u ? 255u : v) << (8 * k);
-                }
-                s_pool[kLutPlane * 64 + lane] = wlut;
-            }
+            // the thresholds of depths 4 lane .. 4 lane + 3, four bytes in the lane's own word (requested at the top)
+            s_pool[kLutPlane * 64 + lane] = wlut;
         }
         uint32_t vr[PER], vl[PER];
         uint32_t sr = 0, sl = 0;
@@ -1245,17 +1275,27 @@ __global__ __launch_bounds__(BS, (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS ==
             }
             covb = ~ncov & FULL; lowb = ~nlow & FULL;
         } else {
+            // The same two sign bits as above, so that no test's outcome waits in a pair of scalar registers for the
+            // others: a threshold is clamped to 2^31 - 1 = never (a count is below 2^29), and so is that of a depth
+            // below min_depth_for_low_mapq; lut[0] is "never" already (build_lut fills with 0xFFFFFFFF and starts at depth
+            // 1).  A depth beyond the table takes the f64 divide (its load of the table's last entry is not used).
+            const uint32_t mdl = a.min_depth_for_low_mapq < 0x7FFFFFFFu ? a.min_depth_for_low_mapq : 0x7FFFFFFFu;
+            uint32_t ncov = 0, nlow = 0;
 #pragma unroll
             for (int i = PER - 1; i >= 0; --i) {
                 const uint32_t raw = vr[i], low = vl[i];
-                bool is_low = false;
-                if (raw >= a.o.min_depth_for_low_mapq && raw > 0) {
-                    if (raw < kLutSize) is_low = low >= a.lut[raw];
-                    else is_low = ((double)low / (double)raw) > a.o.max_low_mapq_fraction;   // IEEE f64 divide
+                uint32_t thr = a.lut[raw < kLutSize ? raw : kLutSize - 1u];
+                thr = thr < 0x7FFFFFFFu ? thr : 0x7FFFFFFFu;
+                thr |= (uint32_t)((int32_t)(raw - mdl) >> 31) >> 1;
+                uint32_t d = low - thr;
+                if (raw >= kLutSize) {
+                    const bool is_low = raw >= a.min_depth_for_low_mapq && ((double)low / (double)raw) > a.max_low_mapq_fraction;   // IEEE f64 divide
+                    d = is_low ? 0u : 0x80000000u;
                 }
-                covb = covb + covb + (raw > 0 ? 1u : 0u);
-                lowb = lowb + lowb + (is_low ? 1u : 0u);
+                ncov = __builtin_amdgcn_alignbit(ncov, raw - 1u, 31);
+                nlow = __builtin_amdgcn_alignbit(nlow, d, 31);
             }
+            covb = ~ncov & FULL; lowb = ~nlow & FULL;
         }
         // priorities of callable_profiler.rs:104-116, resolved into disjoint masks:
         // REF_N > NO_COVERAGE > POOR_MAPPING_QUALITY > LOW_COVERAGE > EXCESSIVE_COVERAGE > CALLABLE
@@ -1360,18 +1400,22 @@ __global__ __launch_bounds__(BS, (DEEP || NP > 8) ? (BS == 128 ? 3 : 4) : (BS ==
             if (tid == kBlock - 1) a.last_state[w] = (uint8_t)last_st;
         }
     }
-    if (tid == 0) {
-        WinPartial wp;
-        unsigned long long tot[12];
-        for (int q = 0; q < 12; ++q) { tot[q] = 0; for (int i = 0; i < kWaves; ++i) tot[q] += s_wtot[i][q]; }
-        for (int q = 0; q < 6; ++q) wp.cnt[q] = tot[q];
-        wp.n_cov = tot[6]; wp.sum_qc = tot[7]; wp.sum_q = tot[8];
-        wp.sum_reflen = tot[10]; wp.sum_mapq_reflen = tot[11];
-        wp.n_inner = (uint32_t)tot[9];
-        uint32_t m = 0;
-        for (int i = 0; i < kWaves; ++i) m = s_wmax[i] > m ? s_wmax[i] : m;
-        wp.max_raw = m;
-        a.winpart[w] = wp;
+    // the window's partial: twelve 8-byte words, one per lane -- word k < 9 is the waves' total k (cnt[6], n_cov, sum_qc,
+    // sum_q), words 9 and 10 are totals 10 and 11 (sum_reflen, sum_mapq_reflen), word 11 is {n_inner = total 9, max_raw}
+    static_assert(sizeof(WinPartial) == 96 && offsetof(WinPartial, sum_reflen) == 72 && offsetof(WinPartial, n_inner) == 88 &&
+                  offsetof(WinPartial, max_raw) == 92, "WinPartial as twelve 8-byte words");
+    if (tid < 12u) {
+        const uint32_t q = tid < 9u ? tid : (tid == 11u ? 9u : tid + 1u);
+        unsigned long long v = 0;
+#pragma unroll
+        for (int i = 0; i < kWaves; ++i) v += s_wtot[i][q];
+        if (tid == 11u) {
+            uint32_t m = 0;
+#pragma unroll
+            for (int i = 0; i < kWaves; ++i) m = s_wmax[i] > m ? s_wmax[i] : m;
+            v = (unsigned long long)(uint32_t)v | ((unsigned long long)m << 32);
+        }
+        reinterpret_cast<unsigned long long *>(a.winpart + w)[tid] = v;
     }
 }
 
