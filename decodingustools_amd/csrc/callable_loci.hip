@@ -1,10 +1,14 @@
 // callable_loci.hip -- implementation of include/callable_loci.h for MI355X (gfx950).
 //
-// Host side of the coverage engine: staging, uploads, kernel launches, event timing.  The work itself is in
-// kernels.hip.h; engine_base.hip.h holds the memory and transfer plumbing, site_engine.hip.h the site engine (both are
-// parts of this translation unit).  No CPU fallback exists: without a HIP device cl_create fails.
+// Host side of the coverage engine: staging, uploads, kernel launches, event timing.  The work itself is in three headers:
+// pileup_rows.hip.h (k_pileup_rows, the pass-bit form: the product), pileup_bytes.hip.h (k_pileup, the byte forms of
+// DUT_QUAL_FORM=bytes) and kernels.hip.h (what both share: constants, the records between kernels and host, the wave
+// primitives, k_fin_windows and k_rle_write).  engine_base.hip.h holds the memory and transfer plumbing, site_engine.hip.h
+// the site engine (all parts of this translation unit).  No CPU fallback exists: without a HIP device cl_create fails.
 #include "../../include/callable_loci.h"
 #include "kernels.hip.h"
+#include "pileup_bytes.hip.h"
+#include "pileup_rows.hip.h"
 #include "depth_profile.hip.h"
 #include "engine_base.hip.h"
 #include "site_engine.hip.h"
@@ -80,7 +84,6 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     bool deep = false;               // this contig needs the 32-bit counter variant of k_pileup
     bool bits = true;                // the pass-bit form (default); DUT_QUAL_FORM=bytes at cl_create: the byte forms
     int form = 0;                    // the form of k_pileup the resident contig gets (pick_form, at upload)
-    uint32_t tune_ablate = 0;        // CL_TUNING builds: CL_ABLATE, read once at cl_create
     bool has_long = false;           // some read has more than kLongOps CIGAR ops (its checkpoints are in hs.ck_x / hs.ck_y)
     int32_t tid = 0;
     uint32_t contig_len = 0;
@@ -185,7 +188,7 @@ static void give_staging(cl_ctx *c)
 
 namespace {
 
-// constants of the byte-parallel threshold test (kernels.hip.h swar_ge7)
+// constants of the byte-parallel threshold test (pileup_bytes.hip.h: swar_ge7)
 void make_ge_consts(uint8_t T, uint32_t &ge_add, uint32_t &ge_or, uint32_t &ge_and)
 {
     uint32_t add;
@@ -253,7 +256,7 @@ cl_status harvest_events(cl_ctx *c)
 }
 
 // which form of k_pileup a resident contig gets: by its shape, decided once at upload and kept in the context
-// (kernels.hip.h: LONG = 0 records (short reads), 2 the run table (long reads))
+// (3 k_pileup_rows; the byte forms, pileup_bytes.hip.h: LONG = 0 records (short reads), 2 the run table (long reads))
 int pick_form(const cl_ctx *c)
 {
     if (c->bits) return 3;           // the pass-bit form: head records + rows, whatever the reads' shape
@@ -263,20 +266,10 @@ int pick_form(const cl_ctx *c)
     // match runs, HiFi-like: 0.157 against 0.292 ms at 20 Mb with 800-base runs, 0.185 against 0.382 with 150-base runs
     // (profiles/r03_hifi_forms.txt) --, so every long-read shape gets it.
     if (c->n_reads && c->n_cigar >= 8ull * c->n_reads) form = 2;
-#ifdef CL_TUNING
-    if (const char *fl = getenv("CL_FORCE_LONG")) { const int f = atoi(fl); if (f == 0 || f == 2) form = f; }
-#endif
     return form;
 }
 
-Reads device_reads(const cl_ctx *c)
-{
-    Reads R;
-    R.pos = c->d_pos.p; R.mapq = c->d_mapq.p; R.qual = c->d_qual.p + kQualPad; R.n = c->n_reads;
-    return R;
-}
-
-// The records of one read for the short-read form of k_pileup (kernels.hip.h: ReadRec), in order: put(k, rec) for
+// The records of one read for the short-read form of k_pileup (pileup_bytes.hip.h: ReadRec), in order: put(k, rec) for
 // k = 0 .. count - 1; returns the count.  What the reference's column walk sees of the read (mod.rs:22-37): it is in
 // every column of [pos, end) -- the head record --, and the bases of its M/=/X operations that have a quality byte are
 // tested against min_base_quality -- the head's own run and the piece records.  Reads below min_mapping_quality are
@@ -485,7 +478,7 @@ void finish_windows(const cl_ctx *c, const std::vector<uint32_t> &wro_v, std::ve
     flags |= fl.load();
 }
 
-// The run table of the run-table form (kernels.hip.h, LONG = 2): per window of kT positions the M/=/X pieces of the reads
+// The run table of the run-table form (pileup_bytes.hip.h, LONG = 2): per window of kT positions the M/=/X pieces of the reads
 // that cover it -- what the reference's column walk visits as (alignment, qpos) with !is_del (mod.rs:30-37), grouped by
 // window instead of by column.  One more walk over the staged CIGARs, at upload: a thread takes a range of windows
 // and sweeps it with a list of read cursors (operation index, reference and query position), so every operation is
@@ -942,30 +935,50 @@ void launch_tail(cl_ctx *c)
                        c->d_errflag.p, c->d_summary.p, c->n_win, c->extent, c->d_iv.p, cap, sq, sc, sm);
 }
 
-template <bool DEBUG> void launch_pileup(cl_ctx *c, const PileupArgs &a)
+// What a launch of either pileup kernel is given: one aggregate initialisation in the record's member order, so that a
+// member added to the record and not filled here fails the build instead of reaching the device as a null pointer.
+#pragma clang diagnostic push
+#pragma clang diagnostic error "-Wmissing-field-initializers"
+BytesArgs bytes_args(const cl_ctx *c, uint32_t *dbg_raw, uint32_t *dbg_qc, uint32_t *dbg_low)
+{
+    return BytesArgs{
+        Reads{c->d_pos.p, c->d_mapq.p, c->d_qual.p + kQualPad, c->n_reads}, c->dopt,
+        c->d_rec.p, c->d_end.p, c->d_win.p, c->d_wide_idx.p, c->d_ref.p, c->d_lut.p, c->d_runtab.p,
+        c->d_state.p, c->d_runs.p, c->d_first_state.p, c->d_last_state.p, c->d_winpart.p,
+        c->extent, c->n_win, (c->n_win + 7) / 8, dbg_raw, dbg_qc, dbg_low,
+        (c->n_reads && c->n_qual <= 128ull * c->n_reads) ? 2u : 3u,   // upl: by the mean read length
+        c->d_win_wide.p, c->d_errflag.p};
+}
+RowsArgs rows_args(const cl_ctx *c, uint32_t *dbg_raw, uint32_t *dbg_qc, uint32_t *dbg_low)
+{
+    return RowsArgs{
+        c->d_rows.p, c->d_heads.p, c->d_wide_idx.p, c->d_win.p, c->d_refn.p, c->d_lut8.p,
+        c->d_runs.p, c->d_first_state.p, c->d_last_state.p, c->d_winpart.p,
+        c->extent, c->n_win, (c->n_win + 7) / 8, c->opt.min_depth, c->opt.max_depth,
+        c->opt.min_depth_for_low_mapq, c->d_lut.p, c->opt.max_low_mapq_fraction,
+        c->d_state.p, dbg_raw, dbg_qc, dbg_low};
+}
+#pragma clang diagnostic pop
+
+// (the 32-bit counter variant, DEEP, of either kernel is used only when the window bounds asked for it: kNeedDeep)
+template <bool DEBUG> void launch_bytes(cl_ctx *c, const BytesArgs &a)
 {
     const uint32_t grid = a.n_win8 * 8u;
     if (grid == 0) return;
 #define CL_LAUNCH(DEEP_, LONG_) hipLaunchKernelGGL((k_pileup<(int)kT, DEBUG, DEEP_, LONG_>), dim3(grid), dim3(kBlock), 0, c->stream, a)
-#define CL_LAUNCH_L(DEEP_) do { if (c->form == 2) CL_LAUNCH(DEEP_, 2); else CL_LAUNCH(DEEP_, 0); } while (0)
-#define CL_LAUNCH_R(DEEP_, NP_) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, CL_ROWS_BLOCK>), dim3(grid), dim3(CL_ROWS_BLOCK), 0, c->stream, ra)
-#define CL_LAUNCH_RN(DEEP_) do { if (c->max_groups <= 63u) CL_LAUNCH_R(DEEP_, 8); else if (c->max_groups <= 16383u) CL_LAUNCH_R(DEEP_, 16); else CL_LAUNCH_R(DEEP_, 32); } while (0)
-    // the 32-bit counter variant is used only when the window bounds asked for it (kNeedDeep)
-    if (c->form == 3) {
-        RowsArgs ra{};
-        ra.rows = a.rows; ra.heads = a.heads; ra.wide_idx = a.wide_idx; ra.win = a.win; ra.refn = a.refn;
-        ra.lut8 = c->d_lut8.p;
-        ra.runs = a.runs; ra.first_state = a.first_state; ra.last_state = a.last_state; ra.winpart = a.winpart;
-        ra.extent = a.extent; ra.n_win = a.n_win; ra.n_win8 = a.n_win8;
-        ra.min_depth = a.o.min_depth; ra.max_depth = a.o.max_depth;
-        ra.min_depth_for_low_mapq = a.o.min_depth_for_low_mapq; ra.lut = a.lut; ra.max_low_mapq_fraction = a.o.max_low_mapq_fraction;
-        ra.state = a.state; ra.dbg_raw = a.dbg_raw; ra.dbg_qc = a.dbg_qc; ra.dbg_low = a.dbg_low;
-        // pass-bit form: the counter planes by the deepest window's rows (4 per group): 8 planes count to 255
-        if (!c->deep) CL_LAUNCH_RN(false); else CL_LAUNCH_RN(true);
-    } else if (!c->deep) CL_LAUNCH_L(false); else CL_LAUNCH_L(true);
-#undef CL_LAUNCH_RN
-#undef CL_LAUNCH_R
-#undef CL_LAUNCH_L
+    if (c->form == 2) { if (c->deep) CL_LAUNCH(true, 2); else CL_LAUNCH(false, 2); }
+    else { if (c->deep) CL_LAUNCH(true, 0); else CL_LAUNCH(false, 0); }
+#undef CL_LAUNCH
+}
+template <bool DEBUG> void launch_rows(cl_ctx *c, const RowsArgs &a)
+{
+    const uint32_t grid = a.n_win8 * 8u;
+    if (grid == 0) return;
+#define CL_LAUNCH(DEEP_, NP_) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_>), dim3(grid), dim3(kRowsBlock), 0, c->stream, a)
+    // the counter planes by the deepest window's rows (4 per group): 8 planes count to 255
+    if (c->max_groups <= 63u) { if (c->deep) CL_LAUNCH(true, 8); else CL_LAUNCH(false, 8); }
+    else if (c->max_groups <= 16383u) { if (c->deep) CL_LAUNCH(true, 16); else CL_LAUNCH(false, 16); }
+    else { if (c->deep) CL_LAUNCH(true, 32); else CL_LAUNCH(false, 32); }
 #undef CL_LAUNCH
 }
 
@@ -979,26 +992,18 @@ cl_status enqueue(cl_ctx *c, bool debug, uint32_t *dbg_raw, uint32_t *dbg_qc, ui
         if (s != CL_OK) return s;
     }
     hipEvent_t *ev = c->ev[c->ev_pending < cl_ctx::kEvSets ? c->ev_pending : 0];
-    const Reads R = device_reads(c);
-
     // d_errflag is zero here: cleared at upload, and by the summary workgroup at the end of every run
     // (a run has no per-read kernel: the read ends and CIGAR checkpoints the long-read forms need are an index the host
     // built at upload; CL_K_PREP stays in the timing table as an empty slot)
     if (prof) HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-    PileupArgs a;
-    a.R = R; a.o = c->dopt;
-    a.rec = c->d_rec.p; a.heads = c->d_heads.p; a.end = c->d_end.p; a.win = c->d_win.p;
-    a.wide_idx = c->d_wide_idx.p;
-    a.ref = c->d_ref.p; a.refn = c->d_refn.p; a.lut = c->d_lut.p; a.state = c->d_state.p; a.winpart = c->d_winpart.p;
-    a.runs = c->d_runs.p; a.first_state = c->d_first_state.p; a.last_state = c->d_last_state.p;
-    if (debug) { HIP_TRY(c, c->d_state.reserve((size_t)c->n_win * kT + 16)); a.state = c->d_state.p; }
-    a.extent = c->extent; a.n_win = c->n_win; a.n_win8 = (c->n_win + 7) / 8;
-    a.dbg_raw = dbg_raw; a.dbg_qc = dbg_qc; a.dbg_low = dbg_low;
-    a.win_wide = c->d_win_wide.p; a.err_flag = c->d_errflag.p;
-    a.upl = (c->n_reads && c->n_qual <= 128ull * c->n_reads) ? 2u : 3u;   // by the mean read length
-    a.ablate = c->tune_ablate;        // 0 outside tuning builds
-    a.runtab = c->d_runtab.p; a.rows = c->d_rows.p;
-    if (debug) launch_pileup<true>(c, a); else launch_pileup<false>(c, a);
+    if (debug) HIP_TRY(c, c->d_state.reserve((size_t)c->n_win * kT + 16));
+    if (c->form == 3) {
+        const RowsArgs a = rows_args(c, dbg_raw, dbg_qc, dbg_low);
+        if (debug) launch_rows<true>(c, a); else launch_rows<false>(c, a);
+    } else {
+        const BytesArgs a = bytes_args(c, dbg_raw, dbg_qc, dbg_low);
+        if (debug) launch_bytes<true>(c, a); else launch_bytes<false>(c, a);
+    }
     if (prof) HIP_TRY(c, hipEventRecord(ev[3], c->stream));
     launch_tail(c);
     if (prof) {
@@ -1057,12 +1062,6 @@ cl_status cl_create(const cl_options *opt, int device_id, void *stream, cl_ctx *
     make_ge_consts((uint8_t)(opt->min_depth > 255 ? 255 : opt->min_depth), o.md_add, o.md_or, o.md_and);
     o.xd_on = (opt->max_depth >= 1 && opt->max_depth <= 254) ? 1u : 0u;
     make_ge_consts((uint8_t)(o.xd_on ? opt->max_depth + 1 : 255), o.xd_add, o.xd_or, o.xd_and);
-#ifdef CL_TUNING
-    if (const char *ab = getenv("CL_ABLATE")) {   // timing experiments: skips phases of k_pileup (results are then wrong)
-        c->tune_ablate = (uint32_t)strtoul(ab, nullptr, 0);
-        if (c->tune_ablate) fprintf(stderr, "[callable_loci] CL_ABLATE=%u: kernel phases are skipped, RESULTS ARE WRONG (tuning build)\n", c->tune_ablate);
-    }
-#endif
     std::vector<uint32_t> lut;
     build_lut(opt->max_low_mapq_fraction, lut);
     uint32_t lut8[64];
@@ -1739,7 +1738,7 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     }
     c->hs.rec_of.clear(); c->hs.wide_rec_of.clear(); c->n_rec = 0;
     if (form == 3) {
-        // the heads (kernels.hip.h): 8 bytes per read the pileup holds -- [pos, pos + span) and whether its mapq counts
+        // the heads (pileup_rows.hip.h): 8 bytes per read the pileup holds -- [pos, pos + span) and whether its mapq counts
         // as low (mod.rs:22-28) --, built straight into the pinned buffers; a span beyond kHeadSpanMax is cut into
         // several heads (h_rec_cnt, counted by cl_push_reads' walk)
         if ((rs = build_rec_index(c)) != CL_OK) return rs;
@@ -1760,7 +1759,7 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
         if (rs != CL_OK) return rs;
         tmr.lap("upload: heads built + sent");
     } else if (form != 2) {
-        // the records (kernels.hip.h: ReadRec): the host's walk over the CIGARs, so that the device decodes none --
+        // the records (pileup_bytes.hip.h: ReadRec): the host's walk over the CIGARs, so that the device decodes none --
         // north_star's "CIGAR-expanded ref spans" on the host side of the boundary.  Counted first (the reads' record
         // ranges are what the windows' candidate ranges index), then built straight into the pinned buffers: a buffer
         // covers a range of record numbers, the reads it belongs to are found by binary search.  Pass-bit form: a head

@@ -1,5 +1,5 @@
 // depth_profile.hip.h -- k_depth_profile: the depth distribution of the resident contig, reduced on the device
-// (cl_contig_depth_profile, include/callable_loci.h).  Included by callable_loci.hip behind kernels.hip.h.
+// (cl_contig_depth_profile, include/callable_loci.h).  Included by callable_loci.hip behind pileup_rows.hip.h (bs_add4, bs_maj, the heads).
 //
 // A kernel of its own beside k_pileup_rows, not a further template flag of it: it reads the same residents (the
 // windows' pass-bit rows, heads and window records) and rebuilds raw_depth and qc_depth per position the same way

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Kernel-level timing of the resident chr21-shaped contig (depth / read-length sweeps: KB_LEN, KB_DEPTH, KB_READLEN;
 DUT_QUAL_FORM=bytes for the byte forms; a library variant through DUT_CALLABLE_LIB).  Tools only; not part of the
-product or of bench.py.  (The CL_ABLATE hooks of the byte forms are read once at cl_create and exist only in the tuning
-build: tools/rt_ablate.sh.)"""
+product or of bench.py."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
