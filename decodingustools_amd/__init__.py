@@ -5,13 +5,14 @@ the host-side mirror of the reference's callable_loci module API.
 """
 from .records import ContigRecords  # noqa: F401
 from .callable_loci import (CallableOptions, CalledState, CallableProfiler, ContigProfiler,  # noqa: F401
-                            ContigResult, DepthAccumulator, DepthProfile, Engine, EngineError, ScanResult, admit_reads,
-                            compare_contig_names, depth_stats, genome_summary, process_single_contig)
+                            ContigResult, DepthAccumulator, DepthProfile, DepthRuns, Engine, EngineError, ScanResult,
+                            admit_reads, compare_contig_names, depth_stats, genome_summary, process_single_contig,
+                            quantize_parse, write_depth_bed)
 from .fingerprint import Fingerprint, FingerprintError, FingerprintResult, fingerprint_file  # noqa: F401
 from .variants import annotate_variants, find_variants, scan_classify, scan_classify_counts, write_variants  # noqa: F401
 
 __all__ = ["ContigRecords", "CallableOptions", "CalledState", "CallableProfiler", "ContigProfiler",
-           "ContigResult", "DepthAccumulator", "DepthProfile", "Engine", "EngineError", "admit_reads",
+           "ContigResult", "DepthAccumulator", "DepthProfile", "DepthRuns", "Engine", "EngineError", "admit_reads",
            "compare_contig_names", "depth_stats", "genome_summary", "process_single_contig", "Fingerprint", "FingerprintError", "FingerprintResult",
            "fingerprint_file", "ScanResult", "annotate_variants", "find_variants", "scan_classify", "scan_classify_counts",
-           "write_variants"]
+           "write_variants", "quantize_parse", "write_depth_bed"]

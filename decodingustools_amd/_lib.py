@@ -135,6 +135,19 @@ class dut_depth_options(C.Structure):
                 ("summary_path", C.c_char_p)]
 
 
+CL_RUNS_MAX_EDGES = 64
+CL_DEPTH_KINDS = {"raw": 0, "qc": 1}
+
+
+class cl_depth_runs(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("n_edges", C.c_uint32), ("extent", C.c_uint64), ("n_runs", C.c_uint64),
+                ("start", C.POINTER(C.c_uint32)), ("value", C.POINTER(C.c_uint32))]
+
+
+class dut_depth_bed_options(C.Structure):
+    _fields_ = [("path", C.c_char_p), ("kind", C.c_uint32), ("edges", C.POINTER(C.c_uint32)), ("n_edges", C.c_uint32)]
+
+
 class cl_scan_candidate(C.Structure):
     _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8), ("pad", C.c_uint8 * 2),
                 ("a", C.c_uint32), ("c", C.c_uint32), ("g", C.c_uint32), ("t", C.c_uint32), ("depth", C.c_uint32)]
@@ -224,6 +237,14 @@ SYMBOLS = [
     ("dut_coverage_files_ex", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
                                         C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
                                         C.c_uint, C.POINTER(dut_depth_options), C.c_char_p, C.c_size_t]),
+    ("cl_contig_depth_runs", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(cl_depth_runs)]),
+    ("cl_contig_depth_runs_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    ("dut_quantize_parse", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    ("dut_depth_bed_write", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(cl_depth_runs), C.POINTER(C.c_uint32)]),
+    ("dut_coverage_files_ex2", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                         C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
+                                         C.c_uint, C.POINTER(dut_depth_options), C.POINTER(dut_depth_bed_options), C.c_char_p,
+                                         C.c_size_t]),
     ("cl_abi_version", C.c_int, []),
     ("cl_device_count", C.c_int, []),
     ("cl_create", C.c_int, [C.POINTER(cl_options), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

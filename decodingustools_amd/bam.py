@@ -108,7 +108,8 @@ class FastaReader:
 def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callable_regions.bed",
                    summary_json: str = None, options: CallableOptions = None, contigs=None, device_id: int = 0,
                    output_summary: str = None, devices=None, depth_dist: str = None, depth_windows: str = None,
-                   depth_summary: str = None, depth_cap: int = 1000, window: int = 0):
+                   depth_summary: str = None, depth_cap: int = 1000, window: int = 0, depth_bed: str = None,
+                   depth_bed_kind: str = "raw", quantize: str = None):
     """CoverageAnalyzer::analyze on files (CoverageInput of api/coverage.rs:124-132); summary_json
     receives the CoverageOutput JSON of main.rs:68-69; output_summary, when given, the HTML report
     (api/coverage.rs:104; None: not written, the JSON then names "summary.html").  The per-contig coverage
@@ -116,7 +117,9 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
     devices: a list of HIP ordinals (one may repeat) -- the contigs are dealt to them inside the library
     (dut_coverage_files_multi: one host thread and one engine context per entry, no torch, no collective).
     depth_dist / depth_windows (with window >= 16) / depth_summary: the depth profile files of dut_coverage_files_ex
-    (formats: include/dut_coverage.h); depth_cap: depths above it share the last histogram bin."""
+    (formats: include/dut_coverage.h); depth_cap: depths above it share the last histogram bin.
+    depth_bed: the per-base depth of every contig as a BED of runs of equal depth (dut_coverage_files_ex2);
+    depth_bed_kind "raw" or "qc"; quantize: band edges such as "1:4:100" (None or "": exact depth)."""
     lib = _lib.load()
     options = options or CallableOptions()
     oc = options.to_c()
@@ -126,7 +129,22 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
         n = len(contigs)
         arr = (C.c_char_p * max(n, 1))(*[c.encode() for c in contigs])
     err = C.create_string_buffer(1024)
-    if depth_dist or depth_windows or depth_summary:
+    if depth_bed is None and (quantize is not None or depth_bed_kind != "raw"):
+        raise EngineError(-1, "quantize and depth_bed_kind need depth_bed")
+    if depth_bed:
+        from .callable_loci import quantize_parse
+        if depth_bed_kind not in _lib.CL_DEPTH_KINDS:
+            raise EngineError(-1, f"depth_bed_kind {depth_bed_kind!r}: raw or qc")
+        edges = quantize_parse(quantize)
+        ea = (C.c_uint32 * max(len(edges), 1))(*edges)
+        bo = _lib.dut_depth_bed_options(depth_bed.encode(), _lib.CL_DEPTH_KINDS[depth_bed_kind], ea, len(edges))
+        dlist = [int(d) for d in devices] if devices is not None else [int(device_id)]
+        dv = (C.c_int * len(dlist))(*dlist)
+        enc = lambda p: p.encode() if p else None          # noqa: E731
+        do = _lib.dut_depth_options(int(depth_cap) + 1, int(window), enc(depth_dist), enc(depth_windows), enc(depth_summary))
+        st = lib.dut_coverage_files_ex2(bam_file.encode(), reference_file.encode(), output_bed.encode(), enc(summary_json),
+                                        enc(output_summary), C.byref(oc), arr, n, dv, len(dlist), 0, C.byref(do), C.byref(bo), err, 1024)
+    elif depth_dist or depth_windows or depth_summary:
         dlist = [int(d) for d in devices] if devices is not None else [int(device_id)]
         dv = (C.c_int * len(dlist))(*dlist)
         enc = lambda p: p.encode() if p else None          # noqa: E731

@@ -328,6 +328,24 @@ class Engine:
                             hist_qc=arr(p.hist_qc, int(p.n_bins)), win_raw=arr(p.win_raw, nw) if window else None,
                             win_qc=arr(p.win_qc, nw) if window else None, kernel_ms=float(ms.value))
 
+    def depth_runs(self, kind="raw", edges=None):
+        """The per-position depth of the resident contig as runs of equal value, built on the device
+        (cl_contig_depth_runs): a DepthRuns of numpy uint32 arrays (copies).  kind: "raw" or "qc" (or the ABI's 0 / 1);
+        edges: None or empty for the depth itself, else ascending band edges -- the value is the number of edges <= depth."""
+        k = _lib.CL_DEPTH_KINDS.get(kind, kind)
+        e = np.ascontiguousarray(edges if edges is not None else [], np.uint32)
+        r = _lib.cl_depth_runs()
+        self._check(self._lib.cl_contig_depth_runs(self._h, int(k), e.ctypes.data_as(C.POINTER(C.c_uint32)) if e.size else None,
+                                                   int(e.size), C.byref(r)))
+        n = int(r.n_runs)
+
+        def arr(ptr):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        ms = C.c_double()
+        self._check(self._lib.cl_contig_depth_runs_ms(self._h, C.byref(ms)))
+        return DepthRuns(kind=int(r.kind), edges=e.copy(), extent=int(r.extent), n_runs=n, start=arr(r.start), value=arr(r.value),
+                         kernel_ms=float(ms.value))
+
 
 # cl_scan_candidate as a numpy record: pos is 1-based, ref and alt are ASCII codes
 SCAN_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("alt", np.uint8), ("pad", np.uint8, (2,)), ("a", np.uint32),
@@ -377,6 +395,55 @@ class DepthProfile:
         p.hist_raw, p.hist_qc, p.win_raw, p.win_qc = [k.ctypes.data_as(u64p) if k is not None and k.size else u64p() for k in keep]
         # (an empty histogram still needs a pointer: n_bins >= 2 always; only the window tables may be empty)
         return p, keep
+
+
+@dataclass
+class DepthRuns:
+    """cl_depth_runs (include/callable_loci.h): run i = [start[i], start[i + 1]) -- the last one ends at extent -- of
+    value[i]; the value is the depth, or with edges the number of edges <= depth."""
+    kind: int
+    edges: np.ndarray
+    extent: int
+    n_runs: int
+    start: np.ndarray
+    value: np.ndarray
+    kernel_ms: float = 0.0          # cl_contig_depth_runs_ms: both launches and the scan, while profiling is on
+
+    def ends(self):
+        return np.append(self.start[1:], np.uint32(self.extent)).astype(np.uint64) if self.n_runs else np.zeros(0, np.uint64)
+
+
+def quantize_parse(spec):
+    """dut_quantize_parse: the band edges of a `--quantize` argument ("1:4:100", "0:1:4:100:") as a list; None or empty
+    text: [] (exact depth).  Raises EngineError with the reason for a malformed one."""
+    edges = (C.c_uint32 * _lib.CL_RUNS_MAX_EDGES)()
+    n = C.c_uint32()
+    err = C.create_string_buffer(256)
+    st = _lib.load().dut_quantize_parse(spec.encode() if spec is not None else None, edges, C.byref(n), err, 256)
+    if st != 0:
+        raise EngineError(st, err.value.decode())
+    return [int(edges[i]) for i in range(n.value)]
+
+
+def write_depth_bed(path, contig, runs: DepthRuns, append=False):
+    """dut_depth_bed_write: the runs of one contig as lines of a depth BED (contig, start, end, depth or LO:HI band)."""
+    lib = _lib.load()
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    u32p = C.POINTER(C.c_uint32)
+    keep = [np.ascontiguousarray(a, np.uint32) for a in (runs.start, runs.value, runs.edges)]
+    r = _lib.cl_depth_runs(int(runs.kind), int(keep[2].size), int(runs.extent), int(runs.n_runs),
+                           keep[0].ctypes.data_as(u32p), keep[1].ctypes.data_as(u32p))
+    f = libc.fopen(path.encode(), b"ab" if append else b"wb")
+    if not f:
+        raise OSError("cannot open " + path)
+    st = lib.dut_depth_bed_write(f, contig.encode(), C.byref(r), keep[2].ctypes.data_as(u32p) if keep[2].size else None)
+    if libc.fclose(f) != 0 and st == 0:
+        st = -1
+    if st != 0:
+        raise EngineError(st, "dut_depth_bed_write: cannot write " + path)
 
 
 def depth_stats(hist, total):

@@ -10,6 +10,7 @@
 #include "pileup_bytes.hip.h"
 #include "pileup_rows.hip.h"
 #include "depth_profile.hip.h"
+#include "depth_runs.hip.h"
 #include "engine_base.hip.h"
 #include "site_engine.hip.h"
 #include "qual_pack.h"
@@ -139,6 +140,14 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     DevBuf<unsigned long long> d_prof;
     std::vector<unsigned long long> h_prof;
     KernelTimer t_prof;              // the last profile's kernel (recorded while profiling is on)
+    // cl_contig_depth_runs: per window {cnt, first, last} and the error word behind them; the windows' 64-bit offsets and
+    // the total behind them; the runs, start[n] then value[n], on the device and as copied back (pinned)
+    DevBuf<uint32_t> d_dr_win;
+    DevBuf<unsigned long long> d_dr_off;
+    DevBuf<uint32_t> d_dr_out;
+    PinBuf<uint32_t> h_dr_out;
+    KernelTimer t_dr_count, t_dr_write;   // count launch + scan, write launch (recorded while profiling is on)
+    double dr_ms = 0.0;
 
     uint32_t n_reads = 0;
     uint64_t n_cigar = 0, n_qual = 0;
@@ -1093,6 +1102,8 @@ void cl_destroy(cl_ctx *c)
     c->d_winpart.release(); c->d_lut.release(); c->d_lut8.release(); c->d_summary.release();
     c->d_iv.release(); c->d_dbg.release(); c->d_prof.release(); c->d_fin.release(); c->d_errflag.release(); c->d_runtab.release(); c->site.release();
     c->t_prof.destroy();
+    c->d_dr_win.release(); c->d_dr_off.release(); c->d_dr_out.release(); c->h_dr_out.release();
+    c->t_dr_count.destroy(); c->t_dr_write.destroy();
     if (c->ev_made)
         for (int s = 0; s < cl_ctx::kEvSets; ++s)
             for (int i = 0; i <= CL_K_COUNT; ++i) (void)hipEventDestroy(c->ev[s][i]);
@@ -2125,6 +2136,7 @@ cl_status cl_contig_layout(cl_ctx *c, cl_layout_info *out)
     b += c->d_state.cap + c->d_runs.cap * 2 + c->d_first_state.cap + c->d_last_state.cap + c->d_win_wide.cap;
     b += c->d_winpart.cap * sizeof(WinPartial) + c->d_fin.cap * sizeof(FinPartial) + c->d_errflag.cap * 4 + c->d_runtab.cap * 8;
     b += c->d_lut.cap * 4 + c->d_lut8.cap * 4 + c->d_summary.cap * sizeof(DevSummary) + c->d_iv.cap * sizeof(Interval) + c->d_dbg.cap * 4;
+    b += c->d_dr_win.cap * 4 + c->d_dr_off.cap * 8 + c->d_dr_out.cap * 4;
     out->device_bytes = b;
     // what cl_contig_upload sent over the link for this contig (every transfer goes through the pinned staging ring)
     const uint64_t padded = (uint64_t)c->n_win * kT + 16;
@@ -2209,6 +2221,94 @@ cl_status cl_contig_depth_profile(cl_ctx *c, uint32_t n_bins, uint32_t window, c
         out->hist_raw = h + 2; out->hist_qc = h + 2 + n_bins;
         out->win_raw = window ? h + 2 + 2 * (size_t)n_bins : nullptr;
         out->win_qc = window ? h + 2 + 2 * (size_t)n_bins + n_windows : nullptr;
+        return CL_OK;
+    });
+}
+
+// The per-position depth of the resident contig as runs (include/callable_loci.h): k_depth_runs counts the run starts
+// per window, k_depth_runs_scan turns the counts into offsets, k_depth_runs again stores the runs at them
+// (depth_runs.hip.h).  The output buffers are sized from the scan's total, between the two passes.  Nothing of a run is
+// touched: summary, intervals and window partials stay.
+cl_status cl_contig_depth_runs_ms(cl_ctx *c, double *kernel_ms)
+{
+    if (!c || !kernel_ms) return CL_ERR_INVALID;
+    *kernel_ms = c->dr_ms;
+    return CL_OK;
+}
+
+cl_status cl_contig_depth_runs(cl_ctx *c, uint32_t kind, const uint32_t *edges, uint32_t n_edges, cl_depth_runs *out)
+{
+    return guarded(c, [&]() -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: null result");
+        memset(out, 0, sizeof(*out));
+        if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
+        if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
+        if (kind != CL_DEPTH_RAW && kind != CL_DEPTH_QC) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: unknown depth kind (CL_DEPTH_RAW or CL_DEPTH_QC)");
+        if (n_edges > CL_RUNS_MAX_EDGES) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: more than 64 edges");
+        if (n_edges && !edges) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: null edges");
+        if (n_edges && edges[0] == 0u) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: the first edge is 0 (the first band starts at depth 0 by itself)");
+        for (uint32_t i = 1; i < n_edges; ++i)
+            if (edges[i] <= edges[i - 1]) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: the edges are not strictly ascending");
+        if (!c->uploaded || !c->ran || c->form != 3) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs needs a contig that has been run");
+        if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
+        HIP_TRY(c, hipSetDevice(c->device));
+        c->dr_ms = 0.0;
+        unsigned long long total = 0ull;
+        uint32_t err = 0u;
+        if (c->n_win && c->extent) {
+            const size_t nw = c->n_win;
+            HIP_TRY(c, c->d_dr_win.reserve(3 * nw + 1));
+            HIP_TRY(c, c->d_dr_off.reserve(nw + 1));
+            RunsArgs a;
+            memset(&a, 0, sizeof(a));
+            a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
+            a.extent = c->extent; a.n_win = c->n_win; a.n_edges = n_edges;
+            for (uint32_t i = 0; i < n_edges; ++i) a.edges[i] = edges[i];
+            a.cnt = c->d_dr_win.p; a.first = c->d_dr_win.p + nw; a.last = c->d_dr_win.p + 2 * nw; a.err = c->d_dr_win.p + 3 * nw;
+            a.off = c->d_dr_off.p;
+            const uint32_t grid = std::min<uint32_t>(c->n_win, 65536u);
+            auto launch = [&]() {
+                if (kind == CL_DEPTH_RAW) hipLaunchKernelGGL((k_depth_runs<8, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_runs<8, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_runs<16, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else hipLaunchKernelGGL((k_depth_runs<32, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+            };
+            // ---- count, scan: how many runs there are ----
+            HIP_TRY(c, hipMemsetAsync(a.err, 0, sizeof(uint32_t), c->stream));
+            if (c->profiling) HIP_TRY(c, c->t_dr_count.start(c->stream));
+            a.write = 0u;
+            launch();
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(k_depth_runs_scan, dim3(1), dim3(kRunsScanBlock), 0, c->stream, a.cnt, a.first, a.last, c->n_win, c->d_dr_off.p, c->d_dr_off.p + nw);
+            HIP_TRY(c, hipGetLastError());
+            if (c->profiling) HIP_TRY(c, c->t_dr_count.stop(c->stream));
+            HIP_TRY(c, hipMemcpyAsync(&total, c->d_dr_off.p + nw, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (total == 0ull || total > (unsigned long long)c->extent) return fail(c, CL_ERR_INTERNAL, "cl_contig_depth_runs: the count pass gave an impossible number of runs");
+            // ---- write: into buffers of exactly that many slots ----
+            HIP_TRY(c, c->d_dr_out.reserve(2 * (size_t)total));
+            HIP_TRY(c, c->h_dr_out.reserve(2 * (size_t)total));
+            a.write = 1u; a.start = c->d_dr_out.p; a.value = c->d_dr_out.p + total; a.cap = total;
+            if (c->profiling) HIP_TRY(c, c->t_dr_write.start(c->stream));
+            launch();
+            HIP_TRY(c, hipGetLastError());
+            if (c->profiling) HIP_TRY(c, c->t_dr_write.stop(c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->h_dr_out.p, c->d_dr_out.p, 2 * (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(&err, a.err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (c->profiling) {
+                HIP_TRY(c, c->t_dr_count.read());
+                HIP_TRY(c, c->t_dr_write.read());
+                c->dr_ms = c->t_dr_count.ms + c->t_dr_write.ms;
+            }
+            if (err) return fail(c, CL_ERR_INTERNAL, "cl_contig_depth_runs: the write pass met a slot outside the counted runs");
+        } else {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        out->kind = kind; out->n_edges = n_edges; out->extent = c->extent; out->n_runs = total;
+        out->start = total ? c->h_dr_out.p : nullptr;
+        out->value = total ? c->h_dr_out.p + total : nullptr;
         return CL_OK;
     });
 }

@@ -32,6 +32,10 @@ static void usage()
             "       [--depth-dist FILE] [--depth-windows FILE --window S] [--depth-summary FILE] [--depth-cap 1000]\n"
             "         depth profile per contig and in total: histogram of raw / quality-filtered depth (depths above the cap in\n"
             "         one last bin, cap 1..4095), mean depth per window of S >= 16 positions, quartiles and share at >= Nx\n"
+            "       [--depth-bed FILE [--depth-bed-kind raw|qc] [--quantize SPEC]]\n"
+            "         per-base depth as a BED of runs of equal depth (contig, start, end, depth; no header); kind raw (default)\n"
+            "         or qc (quality-filtered); SPEC such as 1:4:100 merges runs within the bands 0, 1-3, 4-99, 100+ (at most\n"
+            "         64 edges; a leading 0: and a trailing : are accepted)\n"
             "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n"
             "       dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n");
@@ -294,6 +298,8 @@ int main(int argc, char **argv)
     std::string depth_dist, depth_windows, depth_summary;
     unsigned long long depth_cap = 1000, depth_window = 0;
     bool has_window = false;
+    std::string depth_bed, depth_bed_kind, quantize;
+    bool has_kind = false, has_quantize = false;
     // a whole non-negative number, or exit 2 with a message (before any device is opened)
     auto number = [](const char *flag, const char *v) -> unsigned long long {
         char *end = nullptr;
@@ -330,6 +336,9 @@ int main(int argc, char **argv)
         else if (a == "--depth-summary") depth_summary = next();
         else if (a == "--depth-cap") depth_cap = number("--depth-cap", next());
         else if (a == "--window") { depth_window = number("--window", next()); has_window = true; }
+        else if (a == "--depth-bed") depth_bed = next();
+        else if (a == "--depth-bed-kind") { depth_bed_kind = next(); has_kind = true; }
+        else if (a == "--quantize") { quantize = next(); has_quantize = true; }
         else if (a == "--device") devices.assign(1, atoi(next()));
         else if (a == "--devices") {
             // the contigs are dealt to these devices (HIP ordinals, comma separated; an ordinal may repeat)
@@ -354,6 +363,23 @@ int main(int argc, char **argv)
     if (has_window && depth_windows.empty()) { fprintf(stderr, "error: '--window' needs '--depth-windows <FILE>'\n"); return 2; }
     dut_depth_options depth = {(uint32_t)depth_cap + 1u, (uint32_t)depth_window, depth_dist.empty() ? nullptr : depth_dist.c_str(),
                                depth_windows.empty() ? nullptr : depth_windows.c_str(), depth_summary.empty() ? nullptr : depth_summary.c_str()};
+    // ... and the depth BED's
+    if (has_kind && depth_bed.empty()) { fprintf(stderr, "error: '--depth-bed-kind' needs '--depth-bed <FILE>'\n"); return 2; }
+    if (has_quantize && depth_bed.empty()) { fprintf(stderr, "error: '--quantize' needs '--depth-bed <FILE>'\n"); return 2; }
+    if (has_kind && depth_bed_kind != "raw" && depth_bed_kind != "qc") {
+        fprintf(stderr, "error: invalid value '%s' for '--depth-bed-kind'\n  [possible values: raw, qc]\n", depth_bed_kind.c_str());
+        return 2;
+    }
+    uint32_t edges[CL_RUNS_MAX_EDGES] = {0}, n_edges = 0;
+    if (has_quantize) {
+        char why[256] = {0};
+        if (dut_quantize_parse(quantize.c_str(), edges, &n_edges, why, sizeof(why)) != CL_OK) {
+            fprintf(stderr, "error: invalid value '%s' for '--quantize': %s\n", quantize.c_str(), why);
+            return 2;
+        }
+    }
+    const dut_depth_bed_options depth_bed_opt = {depth_bed.empty() ? nullptr : depth_bed.c_str(),
+                                                 depth_bed_kind == "qc" ? (uint32_t)CL_DEPTH_QC : (uint32_t)CL_DEPTH_RAW, edges, n_edges};
     if (devices.empty()) devices.push_back(0);
     // The analysis runs in a child process and this one returns as soon as the child reports that every output file is
     // written and closed: what is left then -- the kernel taking a few gigabytes of decode buffers, the pinned staging
@@ -396,9 +422,9 @@ int main(int argc, char **argv)
     // the exit (DUT_CLI_TEARDOWN=1: given back piece by piece first, as a library caller's process would)
     const char *td = getenv("DUT_CLI_TEARDOWN");
     const unsigned flags = (td && *td == '1') ? 0u : DUT_FILES_LEAVE_TO_EXIT;
-    const int rc = dut_coverage_files_ex(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
-                                         contigs.empty() ? nullptr : contigs.data(), contigs.size(), devices.data(), devices.size(),
-                                         flags, &depth, err, sizeof(err));
+    const int rc = dut_coverage_files_ex2(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
+                                          contigs.empty() ? nullptr : contigs.data(), contigs.size(), devices.data(), devices.size(),
+                                          flags, &depth, &depth_bed_opt, err, sizeof(err));
     if (rc != CL_OK) { fprintf(stderr, "Error: Analysis error: %s\n", err); leave(1); }
     // every output file is written and closed: leave without the HIP runtime's exit handlers
     stamp("exit");

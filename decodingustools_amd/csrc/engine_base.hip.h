@@ -146,6 +146,24 @@ template <typename T> struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// Pinned host memory that only grows (what was in it is not kept): the target of a device-to-host copy too large to go
+// through pageable memory at the link's rate (cl_contig_depth_runs).
+template <typename T> struct PinBuf {
+    T *p = nullptr;
+    size_t cap = 0;     // elements
+    hipError_t reserve(size_t n)
+    {
+        if (n <= cap) return hipSuccess;
+        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+        size_t want = n + n / 8 + 64;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), want * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = want;
+        return hipSuccess;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
 } // namespace
 
 // Pinned staging ring for host-to-device copies, one per device and process (its contexts share it; a transfer holds

@@ -1030,4 +1030,71 @@ int dut_depth_acc_finish(dut_depth_acc *a, const char *dist_path, const char *su
     return rc;
 }
 
+// ---- per-base depth: the --quantize argument and the depth BED's text (include/dut_coverage.h) ----
+int dut_quantize_parse(const char *spec, uint32_t *edges, uint32_t *n_edges, char *err, size_t err_len)
+{
+    auto bad = [&](const std::string &m) { if (err && err_len) snprintf(err, err_len, "%s", m.c_str()); return (int)CL_ERR_INVALID; };
+    if (!edges || !n_edges) return bad("null argument");
+    *n_edges = 0;
+    if (!spec || !*spec) return CL_OK;                             // exact depth
+    const std::string text(spec);
+    const std::string what = "quantize '" + text + "': ";
+    // the tokens between the colons; mosdepth's trailing ':' ("100 and more") and leading "0:" say what holds anyway
+    std::vector<std::string> tok;
+    for (size_t b = 0; b <= text.size();) {
+        const size_t e = std::min(text.find(':', b), text.size());
+        tok.push_back(text.substr(b, e - b));
+        b = e + 1;
+    }
+    if (tok.size() > 1 && tok.back().empty()) tok.pop_back();
+    uint32_t n = 0;
+    uint64_t prev = 0;
+    for (size_t i = 0; i < tok.size(); ++i) {
+        const std::string &t = tok[i];
+        if (t.empty()) return bad(what + "an empty edge");
+        uint64_t v = 0;
+        for (char ch : t) {
+            if (ch < '0' || ch > '9') return bad(what + "'" + t + "' is not a whole number");
+            v = v * 10 + (uint64_t)(ch - '0');
+            if (v > 0xFFFFFFFFull) return bad(what + "'" + t + "' is beyond 2^32 - 1");
+        }
+        if (i == 0 && v == 0) continue;                            // "0:1:4": the first band starts at 0 by itself
+        if (v <= prev) return bad(what + "the edges must ascend strictly ('" + t + "')");
+        if (n == CL_RUNS_MAX_EDGES) return bad(what + "more than 64 edges");
+        edges[n++] = (uint32_t)v;
+        prev = v;
+    }
+    if (n == 0) return bad(what + "no edge above 0");
+    *n_edges = n;
+    return CL_OK;
+}
+
+int dut_depth_bed_write(FILE *f, const char *contig, const cl_depth_runs *r, const uint32_t *edges)
+{
+    if (!f || !contig || !r || (r->n_runs && (!r->start || !r->value)) || (r->n_edges && !edges) || r->n_edges > CL_RUNS_MAX_EDGES) return CL_ERR_INVALID;
+    try {
+        // the label of every band once: 0:e_0, e_0:e_1, ..., e_k-1:inf
+        std::vector<std::string> band;
+        for (uint32_t v = 0; r->n_edges && v <= r->n_edges; ++v) {
+            std::string b;
+            dut_profiler::put_u64(b, v ? edges[v - 1] : 0u);
+            b.push_back(':');
+            if (v < r->n_edges) dut_profiler::put_u64(b, edges[v]); else b += "inf";
+            band.push_back(std::move(b));
+        }
+        std::string o;
+        for (uint64_t i = 0; i < r->n_runs; ++i) {
+            if (r->n_edges && r->value[i] > r->n_edges) return CL_ERR_INVALID;
+            o += contig; o.push_back('\t');
+            dut_profiler::put_u64(o, r->start[i]); o.push_back('\t');
+            dut_profiler::put_u64(o, i + 1 < r->n_runs ? (uint64_t)r->start[i + 1] : r->extent); o.push_back('\t');
+            if (r->n_edges) o += band[r->value[i]]; else dut_profiler::put_u64(o, r->value[i]);
+            o.push_back('\n');
+            if (o.size() >= (1u << 20)) { if (fwrite(o.data(), 1, o.size(), f) != o.size()) return CL_ERR_INVALID; o.clear(); }
+        }
+        if (!o.empty() && fwrite(o.data(), 1, o.size(), f) != o.size()) return CL_ERR_INVALID;
+    } catch (...) { return CL_ERR_NOMEM; }
+    return ferror(f) ? CL_ERR_INVALID : CL_OK;
+}
+
 } // extern "C"

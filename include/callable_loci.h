@@ -38,7 +38,8 @@ typedef enum cl_status {
     CL_ERR_UNSORTED = -3,     /* reads not coordinate sorted (htslib: "unsorted input")     */
     CL_ERR_CIGAR = -4,        /* malformed CIGAR (the cases htslib asserts on)              */
     CL_ERR_NOMEM = -5,
-    CL_ERR_RANGE = -6         /* coordinate beyond what the engine addresses (2^32-1)       */
+    CL_ERR_RANGE = -6,        /* coordinate beyond what the engine addresses (2^32-1)       */
+    CL_ERR_INTERNAL = -7      /* a device-side consistency check failed (nothing was written out of range) */
 } cl_status;
 
 /* CallableOptions, src/callable_loci/options.rs:2-9 (CLI defaults src/cli.rs:34-60:
@@ -213,6 +214,37 @@ cl_status cl_contig_depth_profile(cl_ctx *ctx, uint32_t n_bins, uint32_t window,
 /* Measurement: the kernel of the last cl_contig_depth_profile by device events, milliseconds; 0 unless cl_set_profiling
  * was on for that call. */
 cl_status cl_contig_depth_profile_ms(cl_ctx *ctx, double *kernel_ms);
+
+/* ---- per-base depth of the resident contig, run-length encoded ---------------------------- */
+/* What a coverage tool writes as its per-base and quantized depth BED: one run per stretch of equal value.  For the depth
+ * kind of the call (CL_DEPTH_RAW: raw_depth, CL_DEPTH_QC: qc_depth of mod.rs:17-42, as above) every position p of
+ * [0, extent) has a value:
+ *   n_edges == 0                   the depth itself
+ *   edges e_0 < e_1 < ... < e_k-1  the number of edges <= depth, 0 .. k: the band [e_v-1, e_v) the depth falls in
+ *                                  (band 0 starts at depth 0, band k has no upper end)
+ * and a run starts at p == 0 and wherever value(p) != value(p - 1).  The runs are maximal, ascending and cover
+ * [0, extent): start[0] == 0, value[i] != value[i + 1], run i = [start[i], i + 1 < n_runs ? start[i + 1] : extent);
+ * extent == 0 gives no run.  Built on the device from the resident rows and heads in two passes over the windows (count,
+ * then write at the scanned offsets: the order does not depend on timing, two calls give the same arrays); only the runs
+ * cross the link, no per-position array exists anywhere.  Taken only when asked: cl_contig_run enqueues what it always
+ * did.  Any number of calls per resident contig, with any kinds and edge sets, after cl_contig_run (or cl_contig_finish),
+ * interleaved with cl_contig_depth_profile and cl_contig_run; the call waits for the stream.  The arrays are
+ * context-owned host memory, valid until the next cl_contig_depth_runs, cl_contig_begin or cl_destroy.
+ * CL_ERR_INVALID (with a message): an unknown kind; n_edges > CL_RUNS_MAX_EDGES; edges == NULL with n_edges > 0; edges
+ * that are not strictly ascending, or a first edge of 0; no contig has been run; a context of the byte forms
+ * (DUT_QUAL_FORM=bytes).  CL_ERR_DEVICE: a host-only debug context.  CL_ERR_INTERNAL: the write pass met a slot beyond
+ * what the count pass counted (it stores nothing out of range). */
+#define CL_RUNS_MAX_EDGES 64u
+enum { CL_DEPTH_RAW = 0, CL_DEPTH_QC = 1 };
+typedef struct cl_depth_runs {
+    uint32_t kind, n_edges;
+    uint64_t extent, n_runs;
+    const uint32_t *start, *value;   /* n_runs each; run i = [start[i], i + 1 < n_runs ? start[i+1] : extent) */
+} cl_depth_runs;
+cl_status cl_contig_depth_runs(cl_ctx *ctx, uint32_t kind, const uint32_t *edges, uint32_t n_edges, cl_depth_runs *out);
+/* Measurement: both launches and the scan of the last cl_contig_depth_runs by device events, milliseconds; 0 unless
+ * cl_set_profiling was on for that call. */
+cl_status cl_contig_depth_runs_ms(cl_ctx *ctx, double *kernel_ms);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 enum { CL_K_PREP = 0, CL_K_BOUNDS = 1, CL_K_PILEUP = 2, CL_K_RLE = 3, CL_K_COUNT = 4 };

@@ -125,6 +125,30 @@ int dut_coverage_files_ex(const char *bam_path, const char *fasta_path, const ch
                           const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
                           unsigned flags, const dut_depth_options *depth, char *err, size_t err_len);
 
+/* dut_coverage_files_ex that also writes the depth BED of every selected contig: its per-base depth as runs of equal
+ * value (cl_contig_depth_runs, callable_loci.h; the text: dut_depth_bed_write, dut_coverage.h), contig after contig in tid
+ * order into one file, no header.  The runs are taken on the device while the contig is resident -- two more launches
+ * and a scan per contig --, copied on the device's thread, and written by the calling thread behind the contig's BED
+ * lines, so one device and several give the same bytes.  Both option sets work in one run.  bed == NULL or no path:
+ * exactly dut_coverage_files_ex.  Pass-bit form only (DUT_QUAL_FORM=bytes: CL_ERR_INVALID).
+ *   path      the depth BED
+ *   kind      CL_DEPTH_RAW or CL_DEPTH_QC
+ *   edges     n_edges band edges (dut_quantize_parse), strictly ascending, the first above 0, at most CL_RUNS_MAX_EDGES;
+ *             n_edges == 0: exact depth
+ * Bad options are refused (CL_ERR_INVALID, message) before any file or device is touched; a depth BED that cannot be
+ * created or written is named in the message. */
+typedef struct dut_depth_bed_options {
+    const char *path;
+    uint32_t kind;
+    const uint32_t *edges;
+    uint32_t n_edges;
+} dut_depth_bed_options;
+int dut_coverage_files_ex2(const char *bam_path, const char *fasta_path, const char *bed_path,
+                           const char *summary_json, const char *summary_html, const cl_options *opt,
+                           const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
+                           unsigned flags, const dut_depth_options *depth, const dut_depth_bed_options *bed,
+                           char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

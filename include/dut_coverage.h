@@ -23,6 +23,8 @@
 
 #include "callable_loci.h"
 
+#include <stdio.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -177,6 +179,19 @@ int dut_depth_acc_add(dut_depth_acc *a, const char *contig, const cl_depth_profi
 int dut_depth_acc_total(const dut_depth_acc *a, const uint64_t **hist_raw, const uint64_t **hist_qc, uint64_t *sum_raw, uint64_t *sum_qc);
 /* closes the windows file and writes the other two (either path may be NULL) */
 int dut_depth_acc_finish(dut_depth_acc *a, const char *dist_path, const char *summary_path);
+
+/* ---- per-base depth: the text of cl_contig_depth_runs' runs (host code only) -------------------------------
+ * dut_quantize_parse: the band edges of `--quantize SPEC`, colon separated whole numbers that ascend strictly, at most
+ * CL_RUNS_MAX_EDGES of them: "1:4:100" = the bands 0, 1-3, 4-99 and 100 or more.  As mosdepth writes them, a leading
+ * "0:" and a trailing ":" are accepted and say nothing more: "0:1:4:100:" is "1:4:100".  NULL or empty text: no edge,
+ * *n_edges = 0 (exact depth).  edges: room for CL_RUNS_MAX_EDGES values.  CL_OK, or CL_ERR_INVALID with the reason in
+ * err (an empty or non-numeric edge, a value beyond 2^32 - 1, edges that do not ascend, no edge above 0, more than 64).
+ * dut_depth_bed_write: one contig's runs as tab-separated lines, no header, as mosdepth's per-base.bed and quantized.bed:
+ *     contig\tstart\tend\tDEPTH          r->n_edges == 0
+ *     contig\tstart\tend\tLO:HI          the value's band: 0:e_0 for value 0, e_v-1:e_v, and e_k-1:inf for the last
+ * with end = the next run's start, r->extent for the last run.  edges: the r->n_edges edges the runs were taken with. */
+int dut_quantize_parse(const char *spec, uint32_t *edges, uint32_t *n_edges, char *err, size_t err_len);
+int dut_depth_bed_write(FILE *f, const char *contig, const cl_depth_runs *r, const uint32_t *edges);
 
 /* Debug names of CalledState (types.rs:36-43) */
 const char *dut_state_name(uint32_t state);

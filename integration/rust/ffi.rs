@@ -69,6 +69,15 @@ extern "C" {
                                  summary_json: *const c_char, summary_html: *const c_char, opt: *const ClOptions,
                                  contigs: *const *const c_char, n_contigs: usize, devices: *const c_int, n_devices: usize,
                                  flags: c_uint, depth: *const DutDepthOptions, err: *mut c_char, err_len: usize) -> c_int;
+    // per-base depth as runs of equal value (README "Per-base depth"); kind 0 raw, 1 qc; edges null with n_edges 0: exact depth
+    pub fn cl_contig_depth_runs(ctx: *mut ClCtx, kind: u32, edges: *const u32, n_edges: u32, out: *mut ClDepthRuns) -> c_int;
+    pub fn cl_contig_depth_runs_ms(ctx: *mut ClCtx, kernel_ms: *mut f64) -> c_int;
+    pub fn dut_quantize_parse(spec: *const c_char, edges: *mut u32, n_edges: *mut u32, err: *mut c_char, err_len: usize) -> c_int; // edges: room for 64
+    pub fn dut_coverage_files_ex2(bam: *const c_char, fasta: *const c_char, bed: *const c_char,
+                                  summary_json: *const c_char, summary_html: *const c_char, opt: *const ClOptions,
+                                  contigs: *const *const c_char, n_contigs: usize, devices: *const c_int, n_devices: usize,
+                                  flags: c_uint, depth: *const DutDepthOptions, depth_bed: *const DutDepthBedOptions,
+                                  err: *mut c_char, err_len: usize) -> c_int;
     // the dense form of the site pileup: base counts and SNV calls at every position of a range of the tile
     // cl_site_upload left resident (README "Variant scan"); candidates are context-owned until the next scan / upload
     pub fn cl_site_scan(ctx: *mut ClCtx, min_quality: u8, min_depth: u32, ref_bases: *const u8, ref_len: u64,
@@ -142,6 +151,18 @@ pub struct DutDepthSummary {      // dut_depth_summary; frac_at_least: depth >= 
 pub struct DutDepthOptions {      // dut_depth_options: n_bins 2..=4096, window >= 16 with windows_path; paths may be null
     pub n_bins: u32, pub window: u32,
     pub dist_path: *const c_char, pub windows_path: *const c_char, pub summary_path: *const c_char,
+}
+
+#[repr(C)]
+pub struct ClDepthRuns {          // cl_depth_runs: run i = [start[i], start[i + 1]), the last one ends at extent; context-owned arrays
+    pub kind: u32, pub n_edges: u32,
+    pub extent: u64, pub n_runs: u64,
+    pub start: *const u32, pub value: *const u32,          // n_runs each
+}
+
+#[repr(C)]
+pub struct DutDepthBedOptions {   // dut_depth_bed_options: kind 0 raw / 1 qc; at most 64 strictly ascending edges, the first above 0
+    pub path: *const c_char, pub kind: u32, pub edges: *const u32, pub n_edges: u32,
 }
 
 #[repr(C)]
