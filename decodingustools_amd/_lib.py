@@ -180,6 +180,27 @@ class cl_scan_result_ex(C.Structure):
                 ("candidates", C.POINTER(cl_scan_candidate_ex))]
 
 
+class cl_minor_params(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_minor_count", C.c_uint32), ("min_minor_per_10k", C.c_uint32)]
+
+
+class cl_minor_candidate(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("major", C.c_uint8), ("minor", C.c_uint8), ("pad", C.c_uint8),
+                ("a", C.c_uint32), ("c", C.c_uint32), ("g", C.c_uint32), ("t", C.c_uint32), ("depth", C.c_uint32),
+                ("major_fwd", C.c_uint32), ("major_rev", C.c_uint32), ("minor_fwd", C.c_uint32), ("minor_rev", C.c_uint32)]
+
+
+class cl_minor_result(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_low_depth", C.c_uint64), ("n_single", C.c_uint64),
+                ("n_minor", C.c_uint64), ("candidates", C.POINTER(cl_minor_candidate))]
+
+
+class dut_minor_options(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_quality", C.c_uint8), ("has_min_base_quality", C.c_int),
+                ("min_base_quality", C.c_uint8), ("exclude_flags", C.c_uint16), ("min_minor_per_10k", C.c_uint32),
+                ("min_minor_count", C.c_uint32), ("min_minor_per_strand", C.c_uint32)]
+
+
 class dut_variants_options(C.Structure):
     _fields_ = [("filtered", C.c_int), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
                 ("exclude_flags", C.c_uint16), ("min_alt_per_strand", C.c_uint32)]
@@ -205,6 +226,8 @@ SYMBOLS = [
     ("cl_site_scan_ex", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.POINTER(cl_scan_filter), C.c_void_p, C.c_uint64, C.c_uint32,
                                   C.c_uint32, C.POINTER(cl_scan_result_ex)]),
     ("cl_site_scan_counts_ex", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("cl_site_scan_minor", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_minor_params), C.c_void_p, C.c_uint64,
+                                     C.c_uint32, C.c_uint32, C.POINTER(cl_minor_result)]),
     ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
     ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
@@ -214,6 +237,12 @@ SYMBOLS = [
     ("dut_find_variants_files_ex", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p,
                                              C.c_int, C.c_int, C.c_char_p, C.c_uint32, C.c_uint8, C.POINTER(dut_variants_options),
                                              C.c_int, C.c_char_p, C.c_size_t]),
+    ("dut_minor_fraction_parse", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    ("dut_minor_classify_counts", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(cl_minor_params),
+                                            C.c_char_p, C.c_char_p]),
+    ("dut_minor_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_minor_result), C.POINTER(dut_minor_options), C.c_char_p, C.c_size_t]),
+    ("dut_find_minor_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_minor_options),
+                                       C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

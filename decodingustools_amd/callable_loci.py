@@ -306,6 +306,25 @@ class Engine:
         self._check(self._lib.cl_site_scan_counts_ex(self._h, int(min_quality), C.byref(f), int(start), int(end), _ptr(counts)))
         return counts
 
+    def site_scan_minor(self, min_quality, min_depth, min_minor_count, min_minor_per_10k, ref, start=0, end=None, filter=None):
+        """cl_site_scan_minor over [start, end) of the resident tile: positions where a second base of A C G T stands beside
+        the most frequent one.  filter: None for the unfiltered form, else (exclude_flags, use_base_quality) of the
+        attachment.  A MinorResult: the three class counts, the candidates (MINOR_CANDIDATE) and the kernel's milliseconds."""
+        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
+        if end is None:
+            end = ref.shape[0]
+        flt = None if filter is None else C.byref(_lib.cl_scan_filter(int(filter[0]), 1 if filter[1] else 0, 0))
+        prm = _lib.cl_minor_params(int(min_depth), int(min_minor_count), int(min_minor_per_10k))
+        r = _lib.cl_minor_result()
+        self._check(self._lib.cl_site_scan_minor(self._h, int(min_quality), flt, C.byref(prm), _ptr(ref), ref.shape[0], int(start), int(end),
+                                                 C.byref(r)))
+        n = int(r.n_minor)
+        cand = np.zeros(n, MINOR_CANDIDATE)
+        if n:
+            C.memmove(cand.ctypes.data, r.candidates, n * MINOR_CANDIDATE.itemsize)
+        return MinorResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), single=int(r.n_single), minor=n,
+                           candidates=cand, kernel_ms=self.site_scan_stats()[0])
+
     def site_scan_stats(self):
         """(kernel milliseconds, algorithmic bytes) of the last site_scan / site_scan_counts, filtered or not."""
         ms = C.c_double(); b = C.c_uint64()
@@ -353,6 +372,25 @@ SCAN_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("alt", np.uin
 # cl_scan_candidate_ex: a c g t depth over both strands, the alternative and reference base by strand
 SCAN_CANDIDATE_EX = np.dtype(SCAN_CANDIDATE.descr + [("alt_fwd", np.uint32), ("alt_rev", np.uint32), ("ref_fwd", np.uint32),
                                                      ("ref_rev", np.uint32)])
+
+
+# cl_minor_candidate: major and minor are ASCII codes; the strand counts are 0 in the unfiltered form
+MINOR_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("major", np.uint8), ("minor", np.uint8), ("pad", np.uint8),
+                            ("a", np.uint32), ("c", np.uint32), ("g", np.uint32), ("t", np.uint32), ("depth", np.uint32),
+                            ("major_fwd", np.uint32), ("major_rev", np.uint32), ("minor_fwd", np.uint32), ("minor_rev", np.uint32)])
+
+
+@dataclass
+class MinorResult:
+    """cl_minor_result (include/callable_loci.h): the three classes add up to end - start; candidates = the positions of
+    class minor, ascending."""
+    start: int
+    end: int
+    low_depth: int
+    single: int
+    minor: int
+    candidates: np.ndarray
+    kernel_ms: float = 0.0
 
 
 @dataclass

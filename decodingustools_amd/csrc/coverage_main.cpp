@@ -1,5 +1,5 @@
 // dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
-// project's own `fingerprint` front end and `find-variants`);
+// project's own `fingerprint` front end, `find-variants` and `find-minor-alleles`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -38,7 +38,10 @@ static void usage()
             "         64 edges; a leading 0: and a trailing : are accepted)\n"
             "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n"
             "       dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
-            "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n");
+            "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
+            "       dut-coverage find-minor-alleles <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
+            "       [--min-quality 20] [--min-minor-fraction 0.05] [--min-minor-count 3] [--min-base-quality Q] [--exclude-flags MASK]\n"
+            "       [--min-minor-per-strand K] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -160,12 +163,79 @@ static int find_branch_main(int argc, char **argv, int tree_type)
     _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
 }
 
+// The values the scan subcommands share; each prints its message and returns false on a malformed one.
+static bool cli_number(const char *flag, const std::string &v, unsigned long long &dst)
+{
+    char *e = nullptr;
+    errno = 0;
+    if (v.empty() || v[0] < '0' || v[0] > '9') { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), flag); return false; }
+    dst = strtoull(v.c_str(), &e, 10);
+    if (errno || *e) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), flag); return false; }
+    return true;
+}
+
+// --region START-END: 0-based, half open, not empty, below 2^32
+static bool cli_region(const std::string &region, unsigned long long &start, unsigned long long &end)
+{
+    const size_t dash = region.find('-');
+    if (dash == std::string::npos || !cli_number("--region", region.substr(0, dash), start) || !cli_number("--region", region.substr(dash + 1), end)) {
+        if (dash == std::string::npos) fprintf(stderr, "error: invalid value '%s' for '--region': START-END\n", region.c_str());
+        return false;
+    }
+    if (start >= end || end > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%s' for '--region': the range is empty or beyond 2^32\n", region.c_str()); return false; }
+    return true;
+}
+
+static bool cli_min_depth(const std::string &v, unsigned long long &min_depth)
+{
+    if (!cli_number("--min-depth", v, min_depth)) return false;
+    if (min_depth < 1 || min_depth > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%llu' for '--min-depth': at least 1\n", min_depth); return false; }
+    return true;
+}
+
+static bool cli_min_quality(const std::string &v, unsigned long long &min_quality)
+{
+    if (!cli_number("--min-quality", v, min_quality)) return false;
+    if (min_quality > 255) { fprintf(stderr, "error: invalid value '%llu' for '--min-quality': 0..255\n", min_quality); return false; }
+    return true;
+}
+
+static bool cli_base_quality(const std::string &v, uint8_t &dst)
+{
+    unsigned long long q = 0;
+    if (!cli_number("--min-base-quality", v, q)) return false;
+    if (q > 255) { fprintf(stderr, "error: invalid value '%s' for '--min-base-quality': 0..255\n", v.c_str()); return false; }
+    dst = (uint8_t)q;
+    return true;
+}
+
+// --exclude-flags MASK: 0..65535, decimal or 0x hex
+static bool cli_flag_mask(const std::string &v, uint16_t &dst)
+{
+    const bool hex = v.size() > 2 && v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
+    char *e = nullptr;
+    errno = 0;
+    const unsigned long long m = (hex ? isxdigit((unsigned char)v[2]) : (!v.empty() && isdigit((unsigned char)v[0]))) ? strtoull(v.c_str(), &e, hex ? 16 : 10) : 0;
+    if (!e || errno || *e || m > 65535) { fprintf(stderr, "error: invalid value '%s' for '--exclude-flags': 0..65535, decimal or 0x hex\n", v.c_str()); return false; }
+    dst = (uint16_t)m;
+    return true;
+}
+
+static bool cli_count32(const char *flag, const std::string &v, uint32_t &dst)
+{
+    unsigned long long k = 0;
+    if (!cli_number(flag, v, k)) return false;
+    if (k > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), flag); return false; }
+    dst = (uint32_t)k;
+    return true;
+}
+
 // find-variants: every position of a contig (or of --region, 0-based half open) where the sample's called base differs
 // from the reference, by the counting and the call of find-y-branch (defaults as there, src/cli.rs:62-105); with --tree,
 // which of them the haplogroup tree knows.  Argument errors leave with 2 before a device is opened.
 static int find_variants_main(int argc, char **argv)
 {
-    std::string bam, ref, out, tree, contig, region;
+    std::string bam, ref, out, tree, contig;
     unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
     int provider = DUT_PROVIDER_FTDNA, tree_type = DUT_TREE_YDNA, device = 0;
     bool has_provider = false, has_tree_type = false, has_region = false;
@@ -178,14 +248,6 @@ static int find_variants_main(int argc, char **argv)
                         "  record counts (no flag or base-quality filter), as in find-y-branch.  With any of them: bases below Q\n"
                         "  (0..255) and reads with a flag bit of MASK (decimal or 0x hex, 0..65535) do not count, the TSV gains\n"
                         "  alt_fwd alt_rev ref_fwd ref_rev filter, and filter is 'strand' when min(alt_fwd, alt_rev) < K.\n");
-    };
-    auto number = [](const char *flag, const std::string &v, unsigned long long &dst) -> bool {
-        char *e = nullptr;
-        errno = 0;
-        if (v.empty() || v[0] < '0' || v[0] > '9') { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), flag); return false; }
-        dst = strtoull(v.c_str(), &e, 10);
-        if (errno || *e) { fprintf(stderr, "error: invalid value '%s' for '%s'\n", v.c_str(), flag); return false; }
-        return true;
     };
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i], val;
@@ -201,47 +263,12 @@ static int find_variants_main(int argc, char **argv)
         else if (a == "-o" || a == "--output") out = next();
         else if (a == "-L" || a == "--contig") contig = next();
         else if (a == "--tree") tree = next();
-        else if (a == "--region") {
-            region = next();
-            const size_t dash = region.find('-');
-            if (dash == std::string::npos || !number("--region", region.substr(0, dash), start) || !number("--region", region.substr(dash + 1), end)) {
-                if (dash == std::string::npos) fprintf(stderr, "error: invalid value '%s' for '--region': START-END\n", region.c_str());
-                return 2;
-            }
-            if (start >= end || end > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%s' for '--region': the range is empty or beyond 2^32\n", region.c_str()); return 2; }
-            has_region = true;
-        }
-        else if (a == "--min-depth") {
-            if (!number("--min-depth", next(), min_depth)) return 2;
-            if (min_depth < 1 || min_depth > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%llu' for '--min-depth': at least 1\n", min_depth); return 2; }
-        }
-        else if (a == "--min-quality") {
-            if (!number("--min-quality", next(), min_quality)) return 2;
-            if (min_quality > 255) { fprintf(stderr, "error: invalid value '%llu' for '--min-quality': 0..255\n", min_quality); return 2; }
-        }
-        else if (a == "--min-base-quality") {
-            const std::string v = next();
-            unsigned long long q = 0;
-            if (!number("--min-base-quality", v, q)) return 2;
-            if (q > 255) { fprintf(stderr, "error: invalid value '%s' for '--min-base-quality': 0..255\n", v.c_str()); return 2; }
-            vopt.filtered = 1; vopt.has_min_base_quality = 1; vopt.min_base_quality = (uint8_t)q;
-        }
-        else if (a == "--exclude-flags") {
-            const std::string v = next();
-            const bool hex = v.size() > 2 && v[0] == '0' && (v[1] == 'x' || v[1] == 'X');
-            char *e = nullptr;
-            errno = 0;
-            const unsigned long long m = (hex ? isxdigit((unsigned char)v[2]) : (!v.empty() && isdigit((unsigned char)v[0]))) ? strtoull(v.c_str(), &e, hex ? 16 : 10) : 0;
-            if (!e || errno || *e || m > 65535) { fprintf(stderr, "error: invalid value '%s' for '--exclude-flags': 0..65535, decimal or 0x hex\n", v.c_str()); return 2; }
-            vopt.filtered = 1; vopt.exclude_flags = (uint16_t)m;
-        }
-        else if (a == "--min-alt-per-strand") {
-            const std::string v = next();
-            unsigned long long k = 0;
-            if (!number("--min-alt-per-strand", v, k)) return 2;
-            if (k > 0xFFFFFFFFull) { fprintf(stderr, "error: invalid value '%s' for '--min-alt-per-strand'\n", v.c_str()); return 2; }
-            vopt.filtered = 1; vopt.min_alt_per_strand = (uint32_t)k;
-        }
+        else if (a == "--region") { if (!cli_region(next(), start, end)) return 2; has_region = true; }
+        else if (a == "--min-depth") { if (!cli_min_depth(next(), min_depth)) return 2; }
+        else if (a == "--min-quality") { if (!cli_min_quality(next(), min_quality)) return 2; }
+        else if (a == "--min-base-quality") { if (!cli_base_quality(next(), vopt.min_base_quality)) return 2; vopt.filtered = 1; vopt.has_min_base_quality = 1; }
+        else if (a == "--exclude-flags") { if (!cli_flag_mask(next(), vopt.exclude_flags)) return 2; vopt.filtered = 1; }
+        else if (a == "--min-alt-per-strand") { if (!cli_count32("--min-alt-per-strand", next(), vopt.min_alt_per_strand)) return 2; vopt.filtered = 1; }
         else if (a == "--provider") {
             const std::string p = next();
             if (p == "ftdna") provider = DUT_PROVIDER_FTDNA;
@@ -273,6 +300,73 @@ static int find_variants_main(int argc, char **argv)
     _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
 }
 
+// find-minor-alleles: every position of a contig (or of --region) where a second base of A C G T stands beside the most
+// frequent one -- at least --min-minor-count observations and --min-minor-fraction of the depth (cl_site_scan_minor).
+// Counting as in find-variants with its filter flags.  Argument errors leave with 2 before a device is opened.
+static int find_minor_main(int argc, char **argv)
+{
+    std::string bam, ref, out, contig;
+    unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
+    int device = 0;
+    bool has_region = false;
+    dut_minor_options mopt = {10, 20, 0, 0, 0, 500, 3, 0};
+    auto usage_fm = []() {
+        fprintf(stderr, "Usage: dut-coverage find-minor-alleles <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
+                        "       [--min-depth 10] [--min-quality 20] [--min-minor-fraction 0.05] [--min-minor-count 3]\n"
+                        "       [--min-base-quality Q] [--exclude-flags MASK] [--min-minor-per-strand K] [--device 0]\n"
+                        "  A position is listed when it is at least --min-depth deep and the second most frequent of A C G T has at\n"
+                        "  least --min-minor-count observations and --min-minor-fraction of the depth (a decimal in (0, 0.5], at most\n"
+                        "  four decimals).  --region: 0-based, half open.  Q, MASK as in find-variants; filter is 'strand' when\n"
+                        "  min(minor_fwd, minor_rev) < K.  SNVs only, one device.\n");
+    };
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i], val;
+        const size_t eq = a.find('=');
+        const bool has_eq = a.rfind("--", 0) == 0 && eq != std::string::npos;
+        if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
+        auto next = [&]() -> const char * {
+            if (has_eq) return val.c_str();
+            if (i + 1 >= argc) { usage_fm(); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-r" || a == "--reference") ref = next();
+        else if (a == "-o" || a == "--output") out = next();
+        else if (a == "-L" || a == "--contig") contig = next();
+        else if (a == "--region") { if (!cli_region(next(), start, end)) return 2; has_region = true; }
+        else if (a == "--min-depth") { if (!cli_min_depth(next(), min_depth)) return 2; }
+        else if (a == "--min-quality") { if (!cli_min_quality(next(), min_quality)) return 2; }
+        else if (a == "--min-minor-fraction") {
+            const std::string v = next();
+            char why[128] = {0};
+            if (dut_minor_fraction_parse(v.c_str(), &mopt.min_minor_per_10k, why, sizeof(why)) != CL_OK) {
+                fprintf(stderr, "error: invalid value '%s' for '--min-minor-fraction': %s\n", v.c_str(), why);
+                return 2;
+            }
+        }
+        else if (a == "--min-minor-count") {
+            const std::string v = next();
+            if (!cli_count32("--min-minor-count", v, mopt.min_minor_count)) return 2;
+            if (mopt.min_minor_count == 0) { fprintf(stderr, "error: invalid value '%s' for '--min-minor-count': at least 1\n", v.c_str()); return 2; }
+        }
+        else if (a == "--min-base-quality") { if (!cli_base_quality(next(), mopt.min_base_quality)) return 2; mopt.has_min_base_quality = 1; }
+        else if (a == "--exclude-flags") { if (!cli_flag_mask(next(), mopt.exclude_flags)) return 2; }
+        else if (a == "--min-minor-per-strand") { if (!cli_count32("--min-minor-per-strand", next(), mopt.min_minor_per_strand)) return 2; }
+        else if (a == "--device") device = atoi(next());
+        else if (a == "-h" || a == "--help") { usage_fm(); return 0; }
+        else if (!a.empty() && a[0] != '-' && bam.empty()) bam = a;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fm(); return 2; }
+    }
+    if (bam.empty() || ref.empty() || out.empty()) { usage_fm(); return 2; }
+    if (contig.empty()) { fprintf(stderr, "error: find-minor-alleles needs '-L <CONTIG>'\n"); usage_fm(); return 2; }
+    mopt.min_depth = (uint32_t)min_depth; mopt.min_quality = (uint8_t)min_quality;
+    char err[1024] = {0};
+    const int rc = dut_find_minor_files(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end, &mopt,
+                                        out.c_str(), device, err, sizeof(err));
+    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
+    fflush(nullptr);
+    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -291,6 +385,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "find-mt-branch")) return find_branch_main(argc, argv, DUT_TREE_MTDNA);
     if (argc > 1 && !strcmp(argv[1], "fingerprint")) return fingerprint_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-variants")) return find_variants_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "find-minor-alleles")) return find_minor_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

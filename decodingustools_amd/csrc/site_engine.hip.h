@@ -157,15 +157,17 @@ struct SiteResident {
     DevBuf<ScanCandEx> sx_cand;
     DevBuf<uint32_t> sx_amb, sx_hist;
     bool attached = false;
+    DevBuf<ScanMinorCand> sm_cand;   // cl_site_scan_minor's candidates, of either form
     // the last cl_site_pileup / cl_site_run and the last cl_site_scan* of either form: the kernels' duration and their
-    // algorithmic bytes; the candidates of the last cl_site_scan and the last cl_site_scan_ex
+    // algorithmic bytes; the candidates of the last cl_site_scan, the last cl_site_scan_ex and the last cl_site_scan_minor
     KernelTimer t_pileup, t_scan;
     std::vector<cl_scan_candidate> scan_cand;
     std::vector<cl_scan_candidate_ex> scan_cand_ex;
+    std::vector<cl_minor_candidate> minor_cand;
     void release()
     {
         t_pileup.destroy(); t_scan.destroy();
-        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release();
+        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -438,6 +440,7 @@ static cl_status cl_site_run_impl(SiteCtx *c, uint8_t min_quality, const uint32_
 // ---- unfiltered (cl_site_scan) and filtered, strand-aware (cl_site_scan_ex, behind cl_site_attach_quals) ----
 static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_candidate) == 28, "the device writes cl_scan_candidate");
 static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
+static_assert(sizeof(ScanMinorCand) == sizeof(cl_minor_candidate) && sizeof(cl_minor_candidate) == 44, "the device writes cl_minor_candidate");
 
 // the argument checks every scan shares, in front of any device work
 static cl_status site_scan_check(SiteCtx *c, const char *who, uint32_t start, uint32_t end)
@@ -512,8 +515,8 @@ static cl_status site_scan_check_form(SiteCtx *c, const char *who, typename Scan
     return CL_OK;
 }
 
-template <bool FILTERED>
-static void site_scan_fill(SiteCtx *c, ScanFormArgs<FILTERED> &A, typename ScanHost<FILTERED>::Filter f, uint8_t min_quality, uint32_t min_depth,
+template <bool FILTERED, class Args>
+static void site_scan_fill(SiteCtx *c, Args &A, typename ScanHost<FILTERED>::Filter f, uint8_t min_quality, uint32_t min_depth,
                            uint32_t start, uint32_t end)
 {
     SiteResident &S = c->site;
@@ -563,6 +566,47 @@ static void site_scan_settle(const std::vector<uint32_t> &hist, uint64_t &n_unc,
     }
 }
 
+// A scan that compacts candidates, of any mode: the index, the reference bytes of the range, then fill() -- the caller's
+// site_scan_fill of A and what else its mode needs, once the index and every buffer stand -- and launch(n_blocks) -- its
+// kernel over A -- until the candidates fit.  A.s.refb, A.s.cls, A.s.n_cand, A.cand and A.s.cand_cap are set here, behind
+// fill().  The class counts and the candidate count come back in h_cls, the number of reference bytes sent in n_ref; the
+// candidates stay in d_cand.
+template <class Args, class DevCand, class Fill, class Launch>
+static cl_status site_scan_compacting(SiteCtx *c, Args &A, DevBuf<DevCand> &d_cand, const uint8_t *ref_bases, uint64_t ref_len, uint32_t start,
+                                      uint32_t end, unsigned long long (&h_cls)[8], uint64_t &n_ref, Fill &&fill, Launch &&launch)
+{
+    SiteResident &S = c->site;
+    cl_status s = site_scan_index(c);
+    if (s != CL_OK) return s;
+    // the reference bytes of the range (those that exist: positions at and beyond ref_len read as "other")
+    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len);
+    n_ref = ref_hi > start ? ref_hi - start : 0;
+    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
+    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
+    const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
+    // candidates are few where the sample follows the reference: a buffer of a position in 64 (at least 64 K entries);
+    // when more are wanted the kernel says how many, the buffer grows and the scan runs again -- nothing is cut short
+    uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
+    for (;;) {
+        HIP_TRY(c, d_cand.reserve(cap));
+        HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
+        fill();
+        A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
+        A.cand = d_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
+        HIP_TRY(c, S.t_scan.start(c->stream));
+        launch(n_blocks);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, S.t_scan.stop(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, S.t_scan.read(true));                         // (a scan that ran again: the launches' sum)
+        const uint64_t want = (uint32_t)h_cls[SCAN_CLASSES];
+        if (want <= cap) break;
+        cap = want;
+    }
+    return CL_OK;
+}
+
 template <bool FILTERED>
 static cl_status site_scan_impl(SiteCtx *c, uint8_t min_quality, uint32_t min_depth, typename ScanHost<FILTERED>::Filter filter, const uint8_t *ref_bases,
                                 uint64_t ref_len, uint32_t start, uint32_t end, typename ScanHost<FILTERED>::Result *out)
@@ -587,34 +631,14 @@ static cl_status site_scan_impl(SiteCtx *c, uint8_t min_quality, uint32_t min_de
     if (start == end) return CL_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     StageTimer tmr;
-    if ((s = site_scan_index(c)) != CL_OK) return s;
-    // the reference bytes of the range (those that exist: positions at and beyond ref_len read as "other")
-    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len), n_ref = ref_hi > start ? ref_hi - start : 0;
-    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
-    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
-    const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
-    // candidates are few where the sample follows the reference: a buffer of a position in 64 (at least 64 K entries);
-    // when more are wanted the kernel says how many, the buffer grows and the scan runs again -- nothing is cut short
-    uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
     unsigned long long h_cls[8];
+    uint64_t n_ref = 0;
     ScanFormArgs<FILTERED> A;
-    for (;;) {
-        HIP_TRY(c, d_cand.reserve(cap));
-        HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
-        site_scan_fill<FILTERED>(c, A, filter, min_quality, min_depth, start, end);
-        A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
-        A.cand = d_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-        HIP_TRY(c, S.t_scan.start(c->stream));
-        hipLaunchKernelGGL((k_site_scan<FILTERED, false>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, S.t_scan.stop(c->stream));
-        HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, S.t_scan.read(true));                         // (a scan that ran again: the launches' sum)
-        const uint64_t want = (uint32_t)h_cls[SCAN_CLASSES];
-        if (want <= cap) break;
-        cap = want;
-    }
+    s = site_scan_compacting(c, A, d_cand, ref_bases, ref_len, start, end, h_cls, n_ref,
+                             [&] { site_scan_fill<FILTERED>(c, A, filter, min_quality, min_depth, start, end); }, [&](uint32_t n_blocks) {
+        hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_CALLS>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+    });
+    if (s != CL_OK) return s;
     const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
     cand.resize(n_cand);
     if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), d_cand.p, n_cand * sizeof(Cand), hipMemcpyDeviceToHost));
@@ -633,6 +657,54 @@ static cl_status site_scan_impl(SiteCtx *c, uint8_t min_quality, uint32_t min_de
         site_scan_settle(hist, out->n_uncomparable, out->n_mixed);
         tmr.lap(H::kLapSettle);
     }
+    out->candidates = cand.data();
+    return CL_OK;
+}
+
+// ---- the minor mode: a second allele beside the most frequent one (site_scan.hip.h), over either form ----
+template <bool FILTERED>
+static cl_status site_scan_minor_impl(SiteCtx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, const cl_minor_params *prm,
+                                      const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, cl_minor_result *out)
+{
+    using H = ScanHost<FILTERED>;
+    static const char *const who = "cl_site_scan_minor";
+    if (!out) return fail(c, CL_ERR_INVALID, std::string(who) + ": null result");
+    cl_status s = site_scan_check_form<FILTERED>(c, who, filter, start, end);
+    if (s != CL_OK) return s;
+    SiteResident &S = c->site;
+    if (!prm) return fail(c, CL_ERR_INVALID, std::string(who) + ": null params");
+    if (prm->min_depth == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_depth must be at least 1");
+    if (prm->min_minor_count == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_minor_count must be at least 1");
+    if (prm->min_minor_per_10k < 1 || prm->min_minor_per_10k > 5000) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_minor_per_10k must lie in 1..5000");
+    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": ref_len differs from the one given to cl_site_upload");
+    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": null reference");
+    std::vector<cl_minor_candidate> &cand = S.minor_cand;
+    memset(out, 0, sizeof(*out));
+    out->start = start; out->end = end;
+    cand.clear();
+    out->candidates = cand.data();
+    S.t_scan.ms = 0.0; S.t_scan.bytes = 0;
+    if (start == end) return CL_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    StageTimer tmr;
+    unsigned long long h_cls[8];
+    uint64_t n_ref = 0;
+    ScanMinorArgs<FILTERED> A;
+    s = site_scan_compacting(c, A, S.sm_cand, ref_bases, ref_len, start, end, h_cls, n_ref, [&] {
+        site_scan_fill<FILTERED>(c, A, filter, min_quality, prm->min_depth, start, end);
+        A.min_minor_count = prm->min_minor_count; A.min_minor_per_10k = prm->min_minor_per_10k;
+    }, [&](uint32_t n_blocks) {
+        hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_MINOR>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+    });
+    if (s != CL_OK) return s;
+    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
+    cand.resize(n_cand);
+    if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), S.sm_cand.p, n_cand * sizeof(cl_minor_candidate), hipMemcpyDeviceToHost));
+    S.t_scan.bytes = H::tile_bytes(S) + n_ref + n_cand * sizeof(cl_minor_candidate);
+    tmr.lap("minor-allele scan: reference in, kernel, candidates back");
+    // the compaction runs wave by wave: ascending position is restored here
+    std::sort(cand.begin(), cand.end(), [](const cl_minor_candidate &a, const cl_minor_candidate &b) { return a.pos < b.pos; });
+    out->n_low_depth = h_cls[MINOR_LOW_DEPTH]; out->n_single = h_cls[MINOR_SINGLE]; out->n_minor = h_cls[MINOR_MINOR];
     out->candidates = cand.data();
     return CL_OK;
 }
@@ -658,7 +730,7 @@ static cl_status site_scan_counts_impl(SiteCtx *c, uint8_t min_quality, typename
     site_scan_fill<FILTERED>(c, A, filter, min_quality, 1, start, end);
     A.s.dense = S.sc_dense.p;
     HIP_TRY(c, S.t_scan.start(c->stream));
-    hipLaunchKernelGGL((k_site_scan<FILTERED, true>), dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
+    hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_DENSE>), dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, S.t_scan.stop(c->stream));
     HIP_TRY(c, hipMemcpyAsync(counts, S.sc_dense.p, n_dense * 4, hipMemcpyDeviceToHost, c->stream));
@@ -739,6 +811,16 @@ cl_status cl_site_scan_ex(cl_ctx *h, uint8_t min_quality, uint32_t min_depth, co
                           uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out)
 {
     return site_entry(h, [&](SiteCtx *c) { return site_scan_impl<true>(c, min_quality, min_depth, filter, ref_bases, ref_len, start, end, out); });
+}
+
+cl_status cl_site_scan_minor(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, const cl_minor_params *params, const uint8_t *ref_bases,
+                             uint64_t ref_len, uint32_t start, uint32_t end, cl_minor_result *out)
+{
+    return site_entry(h, [&](SiteCtx *c) -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (filter) return site_scan_minor_impl<true>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
+        return site_scan_minor_impl<false>(c, min_quality, ScanNoFilter{}, params, ref_bases, ref_len, start, end, out);
+    });
 }
 
 cl_status cl_site_scan_counts_ex(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)

@@ -16,11 +16,13 @@
 //                       [first, last) of the reads that overlap it (atomicMin / atomicMax of the read's index over
 //                       the windows of its span).  The range holds every overlapping read whatever the order of the
 //                       tile, so an unsorted tile gives exact counts too -- its ranges are merely wider.
-//   k_site_scan<FILTERED, DENSE>
+//   k_site_scan<FILTERED, MODE>
 //                       one workgroup per window: reads of the window's range are dealt to the threads, a thread walks
 //                       its read's CIGAR over the window and adds into LDS counter planes (one ds_add without return
 //                       per base, consecutive positions in consecutive banks); then every thread classifies positions
-//                       and the candidates are compacted with one ballot and one atomic per wave.
+//                       and the candidates are compacted with one ballot and one atomic per wave.  What happens to
+//                       the finished planes is the MODE: the calling rule and its candidates (SCAN_CALLS), the counters
+//                       themselves (SCAN_DENSE), or the second-allele rule and its candidates (SCAN_MINOR).
 //   k_site_scan_settle  filtered form only: the 16-code histogram of the few positions the planes cannot classify.
 //
 // The unfiltered form (ScanForm<false>) counts in six planes: A, C, G, T, N, any other code.  Six planes and not
@@ -43,6 +45,12 @@
 // exactly as in the unfiltered form, and settled with k_site_scan_settle under the same filter (cl_site_run's histogram
 // is unfiltered and cannot serve).  The unfiltered instantiations hold no flag load, no pass-bit load and no test of
 // use_base_quality: the filter is an empty type there and every use of it sits behind if constexpr.
+//
+// The minor mode (cl_site_scan_minor) asks another question of the same planes: does a second base of A C G T stand
+// beside the most frequent one?  major = the largest of A C G T, minor = the largest of the other three (the first in
+// that order among equals, both times); a position is low_depth (depth < min_depth, the depth of scan_classify: N and
+// the other codes included), minor (c2 >= min_minor_count and 10000 c2 >= min_minor_per_10k depth, in 64 bits) or
+// single.  Nothing is ambiguous: N and the other codes take part only through the depth.
 #pragma once
 
 #include <type_traits>
@@ -67,6 +75,17 @@ struct ScanCandEx {
     uint32_t a, c, g, t, depth;              // both strands
     uint32_t alt_fwd, alt_rev, ref_fwd, ref_rev;
 };
+
+// one compacted position of the minor mode; the strand counts are 0 in the unfiltered form
+struct ScanMinorCand {
+    uint32_t pos;                            // 1-based
+    uint8_t  ref, major, minor, pad;
+    uint32_t a, c, g, t, depth;              // both strands
+    uint32_t major_fwd, major_rev, minor_fwd, minor_rev;
+};
+enum { MINOR_LOW_DEPTH = 0, MINOR_SINGLE = 1, MINOR_MINOR = 2 };             // its classes, in the first slots of cls
+
+enum ScanMode { SCAN_CALLS = 0, SCAN_DENSE = 1, SCAN_MINOR = 2 };
 
 struct ScanNoFilter {};
 
@@ -114,7 +133,7 @@ struct ScanArgs {
     unsigned long long *cls;                 // SCAN_CLASSES counts
     uint32_t *n_cand;                        // candidates wanted (also beyond cand_cap)
     uint32_t cand_cap;
-    uint32_t *dense;                         // DENSE: (end_pos - start) * ScanForm::kDense
+    uint32_t *dense;                         // SCAN_DENSE: (end_pos - start) * ScanForm::kDense
 };
 
 template <bool FILTERED>
@@ -123,6 +142,18 @@ struct ScanFormArgs {
     typename ScanForm<FILTERED>::Filter f;
     typename ScanForm<FILTERED>::Cand *cand;
 };
+
+// the minor mode's record: its own candidate type and thresholds (the other modes' record stays as it is)
+template <bool FILTERED>
+struct ScanMinorArgs {
+    ScanArgs s;
+    typename ScanForm<FILTERED>::Filter f;
+    ScanMinorCand *cand;
+    uint32_t min_minor_count, min_minor_per_10k;
+};
+
+template <bool FILTERED, ScanMode MODE>
+using ScanModeArgs = std::conditional_t<MODE == SCAN_MINOR, ScanMinorArgs<FILTERED>, ScanFormArgs<FILTERED>>;
 
 // number of CIGAR operations and bases of a read, with SiteRec's escape to the next record's offsets
 __device__ __forceinline__ void scan_read_extent(const SiteRec *rec, uint32_t r, const uint4 &rr, uint32_t &k1, unsigned long long &slen)
@@ -289,8 +320,25 @@ __device__ __forceinline__ void scan_reduce_classes(const uint32_t (&mine)[SCAN_
     if (tid < (uint32_t)SCAN_CLASSES && s_cls[tid]) atomicAdd(&cls[tid], s_cls[tid]);
 }
 
-template <bool FILTERED, bool DENSE>
-__global__ __launch_bounds__(kBlock) void k_site_scan(ScanFormArgs<FILTERED> ax)
+// The second-allele rule.  cnt: A C G T.  major / minor become the indices of the largest and of the largest of the
+// other three (the first in that order among equals), c2 the latter's count.
+__device__ __forceinline__ int scan_classify_minor(const uint32_t (&cnt)[4], unsigned long long depth, uint32_t min_depth, uint32_t min_minor_count,
+                                                   uint32_t min_minor_per_10k, uint32_t &major, uint32_t &minor, uint32_t &c2)
+{
+    uint32_t c1 = cnt[0];
+    major = 0;
+#pragma unroll
+    for (uint32_t b = 1; b < 4u; ++b) if (cnt[b] > c1) { c1 = cnt[b]; major = b; }
+    minor = major == 0u ? 1u : 0u;
+    c2 = major == 0u ? cnt[1] : cnt[0];
+#pragma unroll
+    for (uint32_t b = 1; b < 4u; ++b) if (b != major && cnt[b] > c2) { c2 = cnt[b]; minor = b; }
+    if (depth < min_depth) return MINOR_LOW_DEPTH;
+    return (c2 >= min_minor_count && 10000ull * c2 >= (unsigned long long)min_minor_per_10k * depth) ? MINOR_MINOR : MINOR_SINGLE;
+}
+
+template <bool FILTERED, ScanMode MODE>
+__global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MODE> ax)
 {
     using Form = ScanForm<FILTERED>;
     constexpr uint32_t S = Form::kStrands;
@@ -324,7 +372,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanFormArgs<FILTERED> ax)
         }
     }
     __syncthreads();
-    if (DENSE) {
+    if constexpr (MODE == SCAN_DENSE) {
         // kDense counters per position of the range, in the order of the output array: consecutive threads, consecutive words
         const uint32_t nd = (we - lo) * Form::kDense;
         uint32_t *out = a.dense + (unsigned long long)(lo - a.start) * Form::kDense;
@@ -335,40 +383,74 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanFormArgs<FILTERED> ax)
             else { v = 0; for (uint32_t k = 0; k < Form::kPlanes; ++k) v += s_cnt[k * kScanWin + o]; }
             out[i] = v;
         }
-        return;
-    }
-    uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
-    const uint32_t lane = tid & 63u;
-    for (uint32_t o0 = 0; o0 < kScanWin; o0 += kBlock) {                       // (uniform trip count: the ballot needs whole waves)
-        const uint32_t o = o0 + tid, p = ws + o;
-        int cls = -1;
-        typename Form::Cand cd;
-        if (p >= lo && p < we) {
-            uint32_t f[4], v[4];                                                // A C G T, forward and reverse
+    } else if constexpr (MODE == SCAN_MINOR) {
+        uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
+        const uint32_t lane = tid & 63u;
+        for (uint32_t o0 = 0; o0 < kScanWin; o0 += kBlock) {                   // (uniform trip count: the ballot needs whole waves)
+            const uint32_t o = o0 + tid, p = ws + o;
+            int cls = -1;
+            ScanMinorCand cd;
+            if (p >= lo && p < we) {
+                uint32_t f[4], v[4], cnt[4];                                    // A C G T: forward, reverse, both
+                unsigned long long depth = (unsigned long long)s_cnt[(4u * S) * kScanWin + o] + s_cnt[(4u * S + 1u) * kScanWin + o];
 #pragma unroll
-            for (uint32_t b = 0; b < 4u; ++b) { f[b] = s_cnt[(S * b) * kScanWin + o]; v[b] = FILTERED ? s_cnt[(S * b + 1u) * kScanWin + o] : 0u; }
-            const uint32_t A = f[0] + v[0], Cc = f[1] + v[1], G = f[2] + v[2], T = f[3] + v[3];
-            uint32_t rb = p < hi ? a.refb[p - a.start] : (uint32_t)'N', alt, ai;
-            unsigned long long depth;
-            cls = scan_classify(A, Cc, G, T, s_cnt[(4u * S) * kScanWin + o], s_cnt[(4u * S + 1u) * kScanWin + o], rb, a.min_depth, alt, ai, depth);
-            mine[cls] += 1u;
-            cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.alt = cls == SCAN_VARIANT ? (uint8_t)alt : (uint8_t)0; cd.pad[0] = cd.pad[1] = 0;
-            cd.a = A; cd.c = Cc; cd.g = G; cd.t = T; cd.depth = (uint32_t)depth;
-            if constexpr (FILTERED) {
-                cd.alt_fwd = cd.alt_rev = cd.ref_fwd = cd.ref_rev = 0;
-                if (cls == SCAN_VARIANT) {
-                    const uint32_t ri = rb == 'A' ? 0u : rb == 'C' ? 1u : rb == 'G' ? 2u : 3u;    // (a variant's reference base is of ACGT)
+                for (uint32_t b = 0; b < 4u; ++b) {
+                    f[b] = s_cnt[(S * b) * kScanWin + o]; v[b] = FILTERED ? s_cnt[(S * b + 1u) * kScanWin + o] : 0u;
+                    cnt[b] = f[b] + v[b]; depth += cnt[b];
+                }
+                uint32_t major, minor, c2;
+                cls = scan_classify_minor(cnt, depth, a.min_depth, ax.min_minor_count, ax.min_minor_per_10k, major, minor, c2);
+                mine[cls] += 1u;
+                const uint32_t rb = (p < hi ? a.refb[p - a.start] : (uint32_t)'N') & ~32u;
+                cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.pad = 0;
+                cd.major = (uint8_t)(0x54474341u >> (8u * major)); cd.minor = (uint8_t)(0x54474341u >> (8u * minor));   // "ACGT"
+                cd.a = cnt[0]; cd.c = cnt[1]; cd.g = cnt[2]; cd.t = cnt[3]; cd.depth = (uint32_t)depth;
+                cd.major_fwd = cd.major_rev = cd.minor_fwd = cd.minor_rev = 0;
+                if constexpr (FILTERED) {
 #pragma unroll
                     for (uint32_t b = 0; b < 4u; ++b) {                           // (selects, not indexed registers)
-                        if (b == ai) { cd.alt_fwd = f[b]; cd.alt_rev = v[b]; }
-                        if (b == ri) { cd.ref_fwd = f[b]; cd.ref_rev = v[b]; }
+                        if (b == major) { cd.major_fwd = f[b]; cd.major_rev = v[b]; }
+                        if (b == minor) { cd.minor_fwd = f[b]; cd.minor_rev = v[b]; }
                     }
                 }
             }
+            scan_compact(cls == MINOR_MINOR, cd, lane, a.n_cand, ax.cand, a.cand_cap);
         }
-        scan_compact(cls == SCAN_VARIANT || cls == SCAN_AMBIGUOUS, cd, lane, a.n_cand, ax.cand, a.cand_cap);
+        scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);
+    } else {
+        uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
+        const uint32_t lane = tid & 63u;
+        for (uint32_t o0 = 0; o0 < kScanWin; o0 += kBlock) {                       // (uniform trip count: the ballot needs whole waves)
+            const uint32_t o = o0 + tid, p = ws + o;
+            int cls = -1;
+            typename Form::Cand cd;
+            if (p >= lo && p < we) {
+                uint32_t f[4], v[4];                                                // A C G T, forward and reverse
+#pragma unroll
+                for (uint32_t b = 0; b < 4u; ++b) { f[b] = s_cnt[(S * b) * kScanWin + o]; v[b] = FILTERED ? s_cnt[(S * b + 1u) * kScanWin + o] : 0u; }
+                const uint32_t A = f[0] + v[0], Cc = f[1] + v[1], G = f[2] + v[2], T = f[3] + v[3];
+                uint32_t rb = p < hi ? a.refb[p - a.start] : (uint32_t)'N', alt, ai;
+                unsigned long long depth;
+                cls = scan_classify(A, Cc, G, T, s_cnt[(4u * S) * kScanWin + o], s_cnt[(4u * S + 1u) * kScanWin + o], rb, a.min_depth, alt, ai, depth);
+                mine[cls] += 1u;
+                cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.alt = cls == SCAN_VARIANT ? (uint8_t)alt : (uint8_t)0; cd.pad[0] = cd.pad[1] = 0;
+                cd.a = A; cd.c = Cc; cd.g = G; cd.t = T; cd.depth = (uint32_t)depth;
+                if constexpr (FILTERED) {
+                    cd.alt_fwd = cd.alt_rev = cd.ref_fwd = cd.ref_rev = 0;
+                    if (cls == SCAN_VARIANT) {
+                        const uint32_t ri = rb == 'A' ? 0u : rb == 'C' ? 1u : rb == 'G' ? 2u : 3u;    // (a variant's reference base is of ACGT)
+#pragma unroll
+                        for (uint32_t b = 0; b < 4u; ++b) {                           // (selects, not indexed registers)
+                            if (b == ai) { cd.alt_fwd = f[b]; cd.alt_rev = v[b]; }
+                            if (b == ri) { cd.ref_fwd = f[b]; cd.ref_rev = v[b]; }
+                        }
+                    }
+                }
+            }
+            scan_compact(cls == SCAN_VARIANT || cls == SCAN_AMBIGUOUS, cd, lane, a.n_cand, ax.cand, a.cand_cap);
+        }
+        scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);
     }
-    scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);
 }
 
 // The 16-code histogram of single positions under the filter of ax: one workgroup per position of pos1 (1-based, inside

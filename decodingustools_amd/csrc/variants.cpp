@@ -1,6 +1,8 @@
 // variants.cpp -- implementation of include/dut_variants.h: the per-position classification in plain C++ (the f64 rule
 // the device's integer test is held against), the annotation of candidates against a haplogroup tree, the TSV of
-// `find-variants`.  Host-only except dut_find_variants_files(_ex), which runs the device engine's cl_site_scan(_ex).
+// `find-variants`; the second-allele rule of `find-minor-alleles` in plain C++, its fraction parser and its TSV.  Host-only
+// except dut_find_variants_files(_ex) and dut_find_minor_files, which run the device engine's cl_site_scan(_ex) and
+// cl_site_scan_minor.
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -73,6 +75,15 @@ int annotate(const dut_tree *t, const char *build_id, const char *chromosome, co
     return CL_OK;
 }
 
+int write_file(const char *path, const std::string &s, char *err, size_t err_len)
+{
+    FILE *f = fopen(path, "wb");
+    if (!f) { set_err(err, err_len, std::string("cannot create ") + path); return CL_ERR_INVALID; }
+    const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
+    if (fclose(f) != 0 || !ok) { set_err(err, err_len, std::string("cannot write ") + path); return CL_ERR_INVALID; }
+    return CL_OK;
+}
+
 // opt: the extended TSV of dut_variants_write_ex (Res = cl_scan_result_ex); nullptr: the one of dut_variants_write
 template <class Res>
 int write_tsv(const char *path, const char *contig, const Res *res, uint32_t min_depth, uint8_t min_quality,
@@ -113,11 +124,74 @@ int write_tsv(const char *path, const char *contig, const Res *res, uint32_t min
         }
         s += "\n";
     }
-    FILE *f = fopen(path, "wb");
-    if (!f) { set_err(err, err_len, std::string("cannot create ") + path); return CL_ERR_INVALID; }
-    const bool ok = fwrite(s.data(), 1, s.size(), f) == s.size();
-    if (fclose(f) != 0 || !ok) { set_err(err, err_len, std::string("cannot write ") + path); return CL_ERR_INVALID; }
+    return write_file(path, s, err, err_len);
+}
+
+// What the file-level scans share: the opened files, the contig's records and reference bases, the context with the tile
+// resident.  scan_files_open: everything that needs no device and no record; scan_files_upload: the HIP runtime + context
+// beside `side` (the caller's own slow start, such as a tree's JSON) and the contig's records, then cl_site_upload.
+struct ScanFiles {
+    std::unique_ptr<dut_fasta, decltype(&dut_fasta_close)> fa{nullptr, dut_fasta_close};
+    std::unique_ptr<dut_bam, decltype(&dut_bam_close)> bam{nullptr, dut_bam_close};
+    std::unique_ptr<cl_ctx, decltype(&cl_destroy)> ctx{nullptr, cl_destroy};
+    int tid = -1;
+    uint32_t contig_len = 0;
+    dut_records rec{};
+    const uint64_t *seq_off = nullptr; const uint8_t *seq4 = nullptr;
+    const uint8_t *bases = nullptr; uint64_t blen = 0;
+    void engine_err(char *err, size_t err_len, const char *what) const { const char *m = cl_last_error(ctx.get()); set_err(err, err_len, (m && *m) ? m : what); }
+};
+
+int scan_files_open(ScanFiles &F, const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t &start,
+                           uint32_t &end, char *err, size_t err_len)
+{
+    if (has_region && start >= end) { set_err(err, err_len, "the region is empty"); return CL_ERR_INVALID; }
+    char e[512] = {0};
+    F.fa.reset(dut_fasta_open(fasta_path, e, sizeof(e)));
+    if (!F.fa) { set_err(err, err_len, e); return CL_ERR_INVALID; }
+    F.bam.reset(dut_bam_open(bam_path, e, sizeof(e)));
+    if (!F.bam) { set_err(err, err_len, e); return CL_ERR_INVALID; }
+    if (!dut_bam_has_index(F.bam.get())) { set_err(err, err_len, std::string("no .bai or .csi index beside ") + bam_path); return CL_ERR_INVALID; }
+    for (int t = 0; t < dut_bam_n_ref(F.bam.get()); ++t) if (strcmp(dut_bam_ref_name(F.bam.get(), t), contig) == 0) { F.tid = t; break; }
+    if (F.tid < 0) { set_err(err, err_len, std::string("contig ") + contig + " is not in the BAM header"); return CL_ERR_INVALID; }
+    F.contig_len = dut_bam_ref_len(F.bam.get(), F.tid);
+    if (!has_region) { start = 0; end = F.contig_len; }
+    if (end > F.contig_len) { set_err(err, err_len, "the region ends beyond contig " + std::string(contig) + " (" + std::to_string(F.contig_len) + " bases)"); return CL_ERR_INVALID; }
     return CL_OK;
+}
+
+// side(): runs beside the context's creation; side_ok(): its verdict (it sets the message itself), asked after the FASTA's
+template <class Side, class SideOk>
+int scan_files_upload(ScanFiles &F, const char *contig, int device_id, Side &&side, SideOk &&side_ok, char *err, size_t err_len)
+{
+    int crc = CL_OK;
+    cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};
+    dut::Thread tt = dut::spawn_or_run([&]() { side(); });
+    dut::Thread ct = dut::spawn_or_run([&]() { cl_ctx *c = nullptr; crc = cl_create(&opt, device_id, nullptr, &c); F.ctx.reset(c); });
+    const int brc = dut_bam_read_contig(F.bam.get(), F.tid, &F.rec, &F.seq_off, &F.seq4);
+    const int frc = dut_fasta_fetch(F.fa.get(), contig, &F.bases, &F.blen);
+    if (tt.joinable()) tt.join();
+    if (ct.joinable()) ct.join();
+    if (frc != CL_OK) { set_err(err, err_len, dut_fasta_error(F.fa.get())); return frc; }
+    if (!side_ok()) return CL_ERR_INVALID;
+    if (brc != CL_OK) { set_err(err, err_len, dut_bam_error(F.bam.get())); return brc; }
+    if (crc != CL_OK) { set_err(err, err_len, "no usable HIP device (the engine has no CPU fallback)"); return crc; }
+    cl_site_tile tile;
+    tile.n_reads = F.rec.n; tile.pos = F.rec.pos; tile.mapq = F.rec.mapq; tile.cigar_off = F.rec.cigar_off; tile.cigar = F.rec.cigar;
+    tile.seq_off = F.seq_off; tile.seq4 = F.seq4;
+    const int rc = cl_site_upload(F.ctx.get(), F.contig_len, F.blen, &tile);
+    if (rc != CL_OK) F.engine_err(err, err_len, "site upload failed");
+    return rc;
+}
+
+// the records' flags and, per base, qual >= min_base_quality (none: every base passes) onto the resident tile
+int scan_files_attach(ScanFiles &F, int has_min_base_quality, uint8_t min_base_quality, char *err, size_t err_len)
+{
+    cl_site_quals q;
+    q.n_reads = F.rec.n; q.flag = F.rec.flag; q.qual_off = F.rec.qual_off; q.qual = F.rec.qual; q.seq_off = F.seq_off;
+    const int rc = cl_site_attach_quals(F.ctx.get(), &q, has_min_base_quality ? min_base_quality : 0);
+    if (rc != CL_OK) F.engine_err(err, err_len, "site attachment failed");
+    return rc;
 }
 
 } // namespace
@@ -153,6 +227,72 @@ int dut_scan_classify_counts(const uint32_t counts5[5], uint8_t ref_byte, uint32
     }
     if ((double)(total - named) / (double)total >= 0.7) return DUT_SCAN_UNDETERMINED;
     return DUT_SCAN_MIXED;
+}
+
+int dut_minor_fraction_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len)
+{
+    if (per_10k) *per_10k = 0;
+    if (!text || !per_10k) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    // digits [ '.' digits ] or '.' digits, at most four decimals; the value in parts per 10 000, exactly
+    const char *p = text;
+    uint64_t whole = 0; int n_whole = 0, n_frac = 0; uint32_t frac = 0;
+    for (; *p >= '0' && *p <= '9'; ++p, ++n_whole) whole = std::min<uint64_t>(whole * 10 + (uint64_t)(*p - '0'), 1000000);
+    if (*p == '.') for (++p; *p >= '0' && *p <= '9'; ++p, ++n_frac) if (n_frac < 4) frac = frac * 10 + (uint32_t)(*p - '0');
+    if (*p || n_whole + n_frac == 0) { set_err(err, err_len, "not a decimal fraction"); return CL_ERR_INVALID; }
+    if (n_frac > 4) { set_err(err, err_len, "at most four decimals"); return CL_ERR_INVALID; }
+    for (int k = n_frac; k < 4; ++k) frac *= 10;
+    const uint64_t v = whole * 10000 + frac;
+    if (v < 1 || v > 5000) { set_err(err, err_len, "the fraction must lie in (0, 0.5]"); return CL_ERR_INVALID; }
+    *per_10k = (uint32_t)v;
+    return CL_OK;
+}
+
+int dut_minor_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint64_t depth, const cl_minor_params *params, char *major, char *minor)
+{
+    if (major) *major = 0;
+    if (minor) *minor = 0;
+    if (!params || params->min_depth == 0 || params->min_minor_count == 0 || params->min_minor_per_10k < 1 || params->min_minor_per_10k > 5000) return CL_ERR_INVALID;
+    if ((uint64_t)a + c + g + t > depth || depth > 0xFFFFFFFFull) return CL_ERR_INVALID;
+    const uint32_t cnt[4] = {a, c, g, t};
+    int mi = 0;
+    for (int b = 1; b < 4; ++b) if (cnt[b] > cnt[mi]) mi = b;                  // the first among equals
+    int ni = mi == 0 ? 1 : 0;
+    for (int b = 1; b < 4; ++b) if (b != mi && cnt[b] > cnt[ni]) ni = b;
+    if (major) *major = "ACGT"[mi];
+    if (minor) *minor = "ACGT"[ni];
+    if (depth < params->min_depth) return DUT_MINOR_LOW_DEPTH;
+    const uint64_t c2 = cnt[ni];
+    return (c2 >= params->min_minor_count && 10000ull * c2 >= (uint64_t)params->min_minor_per_10k * depth) ? DUT_MINOR_MINOR : DUT_MINOR_SINGLE;
+}
+
+int dut_minor_write(const char *path, const char *contig, const cl_minor_result *res, const dut_minor_options *opt, char *err, size_t err_len)
+{
+    if (!path || !contig || !res || !opt || (res->n_minor && !res->candidates)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    std::string s;
+    char b[512];
+    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n", contig, res->start, res->end, opt->min_depth,
+             (unsigned)opt->min_quality);
+    s += b;
+    if (opt->has_min_base_quality) snprintf(b, sizeof(b), "##min_base_quality=%u\n", (unsigned)opt->min_base_quality);
+    else snprintf(b, sizeof(b), "##min_base_quality=.\n");
+    s += b;
+    snprintf(b, sizeof(b), "##exclude_flags=0x%04x\n##min_minor_fraction=%.4f\n##min_minor_count=%u\n##positions=%u\n", (unsigned)opt->exclude_flags,
+             (double)opt->min_minor_per_10k / 10000.0, opt->min_minor_count, res->end - res->start);
+    s += b;
+    snprintf(b, sizeof(b), "##low_depth=%llu\n##single=%llu\n##minor=%llu\n", (unsigned long long)res->n_low_depth,
+             (unsigned long long)res->n_single, (unsigned long long)res->n_minor);
+    s += b;
+    s += "#contig\tpos\tref\tmajor\tminor\tdepth\tA\tC\tG\tT\tminor_freq\tmajor_fwd\tmajor_rev\tminor_fwd\tminor_rev\tfilter\n";
+    for (uint64_t i = 0; i < res->n_minor; ++i) {
+        const cl_minor_candidate &c = res->candidates[i];
+        const uint32_t c2 = c.minor == 'A' ? c.a : c.minor == 'C' ? c.c : c.minor == 'G' ? c.g : c.t;
+        const double freq = c.depth ? (double)c2 / (double)c.depth : 0.0;
+        const bool strand = std::min(c.minor_fwd, c.minor_rev) < opt->min_minor_per_strand;
+        snprintf(b, sizeof(b), "\t%u\t%c\t%c\t%c\t%u\t%u\t%u\t%u\t%u\t%.4f\t%u\t%u\t%u\t%u\t%s\n", c.pos, (char)c.ref, (char)c.major, (char)c.minor, c.depth,
+                 c.a, c.c, c.g, c.t, freq, c.major_fwd, c.major_rev, c.minor_fwd, c.minor_rev, strand ? "strand" : "PASS");
+        s += contig; s += b;
+    }
+    return write_file(path, s, err, err_len);
 }
 
 int dut_variants_annotate(const dut_tree *t, const char *build_id, const char *chromosome,
@@ -195,55 +335,28 @@ static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_
 {
     if (!bam_path || !fasta_path || !contig || !output_path) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
     if (min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
-    if (has_region && start >= end) { set_err(err, err_len, "the region is empty"); return CL_ERR_INVALID; }
-    char e[512] = {0};
-    std::unique_ptr<dut_fasta, decltype(&dut_fasta_close)> fa(dut_fasta_open(fasta_path, e, sizeof(e)), dut_fasta_close);
-    if (!fa) { set_err(err, err_len, e); return CL_ERR_INVALID; }
-    std::unique_ptr<dut_bam, decltype(&dut_bam_close)> bam(dut_bam_open(bam_path, e, sizeof(e)), dut_bam_close);
-    if (!bam) { set_err(err, err_len, e); return CL_ERR_INVALID; }
-    if (!dut_bam_has_index(bam.get())) { set_err(err, err_len, std::string("no .bai or .csi index beside ") + bam_path); return CL_ERR_INVALID; }
-    int tid = -1;
-    for (int t = 0; t < dut_bam_n_ref(bam.get()); ++t) if (strcmp(dut_bam_ref_name(bam.get(), t), contig) == 0) { tid = t; break; }
-    if (tid < 0) { set_err(err, err_len, std::string("contig ") + contig + " is not in the BAM header"); return CL_ERR_INVALID; }
-    const uint32_t contig_len = dut_bam_ref_len(bam.get(), tid);
-    if (!has_region) { start = 0; end = contig_len; }
-    if (end > contig_len) { set_err(err, err_len, "the region ends beyond contig " + std::string(contig) + " (" + std::to_string(contig_len) + " bases)"); return CL_ERR_INVALID; }
+    ScanFiles F;
+    int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
+    if (rc != CL_OK) return rc;
     // the build id the tree's coordinates are looked up by (mod.rs:51-54): the genome the header names, rCRS for mt
     std::string build;
     if (tree_json_path) {
         size_t tl = 0;
-        const char *text = dut_bam_header_text(bam.get(), &tl);
+        const char *text = dut_bam_header_text(F.bam.get(), &tl);
         build = dut_reference_build(text, tl);
         if (build == "Unknown") { set_err(err, err_len, "Could not determine reference genome from BAM header"); return CL_ERR_INVALID; }
         if (tree_type == DUT_TREE_MTDNA) build = "rCRS";
     }
     // side by side, as dut_find_branch_files does: the tree JSON, the HIP runtime + context, the contig's records
     std::unique_ptr<dut_tree, decltype(&dut_tree_free)> tree(nullptr, dut_tree_free);
-    std::unique_ptr<cl_ctx, decltype(&cl_destroy)> ctx(nullptr, cl_destroy);
     char terr[512] = {0};
-    int crc = CL_OK;
-    cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};
-    dut::Thread tt = dut::spawn_or_run([&]() { if (tree_json_path) tree.reset(dut_tree_load(tree_json_path, provider, tree_type, terr, sizeof(terr))); });
-    dut::Thread ct = dut::spawn_or_run([&]() { cl_ctx *c = nullptr; crc = cl_create(&opt, device_id, nullptr, &c); ctx.reset(c); });
-    dut_records rec{}; const uint64_t *seq_off = nullptr; const uint8_t *seq4 = nullptr;
-    const int brc = dut_bam_read_contig(bam.get(), tid, &rec, &seq_off, &seq4);
-    const uint8_t *bases = nullptr; uint64_t blen = 0;
-    const int frc = dut_fasta_fetch(fa.get(), contig, &bases, &blen);
-    if (tt.joinable()) tt.join();
-    if (ct.joinable()) ct.join();
-    if (frc != CL_OK) { set_err(err, err_len, dut_fasta_error(fa.get())); return frc; }
-    if (tree_json_path && !tree) { set_err(err, err_len, terr); return CL_ERR_INVALID; }
-    if (brc != CL_OK) { set_err(err, err_len, dut_bam_error(bam.get())); return brc; }
-    if (crc != CL_OK) { set_err(err, err_len, "no usable HIP device (the engine has no CPU fallback)"); return crc; }
-    cl_site_tile tile;
-    tile.n_reads = rec.n; tile.pos = rec.pos; tile.mapq = rec.mapq; tile.cigar_off = rec.cigar_off; tile.cigar = rec.cigar;
-    tile.seq_off = seq_off; tile.seq4 = seq4;
-    auto engine_err = [&](const char *what) { const char *m = cl_last_error(ctx.get()); set_err(err, err_len, (m && *m) ? m : what); };
-    int rc = cl_site_upload(ctx.get(), contig_len, blen, &tile);
-    if (rc != CL_OK) { engine_err("site upload failed"); return rc; }
+    rc = scan_files_upload(F, contig, device_id,
+                           [&]() { if (tree_json_path) tree.reset(dut_tree_load(tree_json_path, provider, tree_type, terr, sizeof(terr))); },
+                           [&]() { if (tree_json_path && !tree) { set_err(err, err_len, terr); return false; } return true; }, err, err_len);
+    if (rc != CL_OK) return rc;
     // scan result -> annotation -> TSV, for either result type (wopt: the filter columns of the header, or none)
     auto finish = [&](int scan_rc, const auto &res, const dut_variants_options *wopt) {
-        if (scan_rc != CL_OK) { engine_err("site scan failed"); return scan_rc; }
+        if (scan_rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return scan_rc; }
         dut_variant_note *notes = nullptr;
         if (tree) {
             const int arc = annotate(tree.get(), build.c_str(), contig, res.candidates, (size_t)res.n_variant, &notes);
@@ -254,16 +367,42 @@ static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_
         return wrc;
     };
     if (vopt && vopt->filtered) {
-        cl_site_quals q;
-        q.n_reads = rec.n; q.flag = rec.flag; q.qual_off = rec.qual_off; q.qual = rec.qual; q.seq_off = seq_off;
-        rc = cl_site_attach_quals(ctx.get(), &q, vopt->has_min_base_quality ? vopt->min_base_quality : 0);
-        if (rc != CL_OK) { engine_err("site attachment failed"); return rc; }
+        if ((rc = scan_files_attach(F, vopt->has_min_base_quality, vopt->min_base_quality, err, err_len)) != CL_OK) return rc;
         const cl_scan_filter flt = {vopt->exclude_flags, (uint8_t)(vopt->has_min_base_quality ? 1 : 0), 0};
         cl_scan_result_ex res;
-        return finish(cl_site_scan_ex(ctx.get(), min_quality, min_depth, &flt, bases, blen, start, end, &res), res, vopt);
+        return finish(cl_site_scan_ex(F.ctx.get(), min_quality, min_depth, &flt, F.bases, F.blen, start, end, &res), res, vopt);
     }
     cl_scan_result res;
-    return finish(cl_site_scan(ctx.get(), min_quality, min_depth, bases, blen, start, end, &res), res, nullptr);
+    return finish(cl_site_scan(F.ctx.get(), min_quality, min_depth, F.bases, F.blen, start, end, &res), res, nullptr);
+}
+
+static int minor_options_check(const dut_minor_options *o, char *err, size_t err_len)
+{
+    if (!o) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    if (o->min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
+    if (o->min_minor_count == 0) { set_err(err, err_len, "min_minor_count must be at least 1"); return CL_ERR_INVALID; }
+    if (o->min_minor_per_10k < 1 || o->min_minor_per_10k > 5000) { set_err(err, err_len, "min_minor_per_10k must lie in 1..5000"); return CL_ERR_INVALID; }
+    return CL_OK;
+}
+
+static int dut_find_minor_files_impl(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
+                                     uint32_t end, const dut_minor_options *o, const char *output_path, int device_id, char *err, size_t err_len)
+{
+    if (!bam_path || !fasta_path || !contig || !output_path) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    int rc = minor_options_check(o, err, err_len);
+    if (rc != CL_OK) return rc;
+    ScanFiles F;
+    if ((rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len)) != CL_OK) return rc;
+    if ((rc = scan_files_upload(F, contig, device_id, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
+    // always the filtered form: its strand planes give the per-strand counts; with no mask and no threshold it counts
+    // what the unfiltered form does
+    if ((rc = scan_files_attach(F, o->has_min_base_quality, o->min_base_quality, err, err_len)) != CL_OK) return rc;
+    const cl_scan_filter flt = {o->exclude_flags, (uint8_t)(o->has_min_base_quality ? 1 : 0), 0};
+    const cl_minor_params prm = {o->min_depth, o->min_minor_count, o->min_minor_per_10k};
+    cl_minor_result res;
+    rc = cl_site_scan_minor(F.ctx.get(), o->min_quality, &flt, &prm, F.bases, F.blen, start, end, &res);
+    if (rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return rc; }
+    return dut_minor_write(output_path, contig, &res, o, err, err_len);
 }
 
 int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
@@ -274,6 +413,14 @@ int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, con
     // no exception leaves the library through the C ABI
     try { return dut_find_variants_files_impl(bam_path, fasta_path, contig, has_region, start, end, tree_json_path, provider, tree_type,
                                                output_path, min_depth, min_quality, opt, device_id, err, err_len); }
+    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
+    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+}
+
+int dut_find_minor_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
+                         const dut_minor_options *opt, const char *output_path, int device_id, char *err, size_t err_len)
+{
+    try { return dut_find_minor_files_impl(bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id, err, err_len); }
     catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
     catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
 }

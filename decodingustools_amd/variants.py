@@ -7,10 +7,12 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .callable_loci import SCAN_CANDIDATE, SCAN_CANDIDATE_EX, EngineError, ScanResult
+from .callable_loci import MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, EngineError, MinorResult, ScanResult
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
+MINOR_LOW_DEPTH, MINOR_SINGLE, MINOR_MINOR = range(3)
+MINOR_CLASS_NAMES = ("low_depth", "single", "minor")
 CLASS_NAMES = ("low_depth", "mixed", "uncomparable", "match", "variant", "undetermined")
 
 
@@ -152,5 +154,78 @@ def find_variants(bam_file: str, reference_file: str, contig: str, output_file: 
     st = lib.dut_find_variants_files_ex(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
                                         int(start), int(end), tree_json.encode() if tree_json else None, provider, tree_type,
                                         output_file.encode(), int(min_depth), int(min_quality), opt, device_id, err, 1024)
+    if st != 0:
+        raise EngineError(st, err.value.decode())
+
+
+def minor_fraction_parse(text: str) -> int:
+    """dut_minor_fraction_parse: decimal text in (0, 0.5] with at most four decimals to parts per 10 000, exactly."""
+    v = C.c_uint32()
+    err = C.create_string_buffer(256)
+    st = _lib.load().dut_minor_fraction_parse(text.encode(), C.byref(v), err, 256)
+    if st != 0:
+        raise ValueError(f"invalid fraction '{text}': {err.value.decode()}")
+    return int(v.value)
+
+
+def minor_classify_counts(a, c, g, t, depth, min_depth, min_minor_count, min_minor_per_10k) -> Tuple[int, str, str]:
+    """(class, major, minor) of one position by the rule of cl_site_scan_minor in plain code (dut_minor_classify_counts)."""
+    prm = _lib.cl_minor_params(int(min_depth), int(min_minor_count), int(min_minor_per_10k))
+    major, minor = C.create_string_buffer(2), C.create_string_buffer(2)
+    st = _lib.load().dut_minor_classify_counts(int(a), int(c), int(g), int(t), int(depth), C.byref(prm), major, minor)
+    if st < 0:
+        raise EngineError(st, "invalid counters or parameters")
+    return st, major.value.decode(), minor.value.decode()
+
+
+def _minor_options(min_depth, min_quality, min_minor_count, min_minor_per_10k, min_base_quality, exclude_flags,
+                   min_minor_per_strand) -> "_lib.dut_minor_options":
+    if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
+        raise ValueError("min_base_quality: 0..255")
+    if not 0 <= int(exclude_flags) <= 0xFFFF:
+        raise ValueError("exclude_flags: 0..65535")
+    if not 0 <= int(min_quality) <= 255:
+        raise ValueError("min_quality: 0..255")
+    for name, v in (("min_depth", min_depth), ("min_minor_count", min_minor_count), ("min_minor_per_10k", min_minor_per_10k),
+                    ("min_minor_per_strand", min_minor_per_strand)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name}: 0..2^32-1")
+    o = _lib.dut_minor_options()
+    o.min_depth, o.min_quality = int(min_depth), int(min_quality)
+    o.has_min_base_quality = 0 if min_base_quality is None else 1
+    o.min_base_quality = 0 if min_base_quality is None else int(min_base_quality)
+    o.exclude_flags = int(exclude_flags)
+    o.min_minor_per_10k, o.min_minor_count, o.min_minor_per_strand = int(min_minor_per_10k), int(min_minor_count), int(min_minor_per_strand)
+    return o
+
+
+def write_minor(path: str, contig: str, result: MinorResult, min_depth: int, min_quality: int, min_minor_count: int,
+                min_minor_per_10k: int, min_base_quality=None, exclude_flags: int = 0, min_minor_per_strand: int = 0):
+    """The TSV of find-minor-alleles (dut_minor_write) for the MinorResult of Engine.site_scan_minor.  No device is needed."""
+    cand = np.ascontiguousarray(result.candidates, MINOR_CANDIDATE).reshape(-1)
+    if cand.shape[0] != result.minor:
+        raise ValueError("minor count and candidates disagree")
+    opt = _minor_options(min_depth, min_quality, min_minor_count, min_minor_per_10k, min_base_quality, exclude_flags, min_minor_per_strand)
+    r = _lib.cl_minor_result()
+    r.start, r.end = result.start, result.end
+    r.n_low_depth, r.n_single, r.n_minor = result.low_depth, result.single, result.minor
+    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_minor_candidate))
+    err = C.create_string_buffer(512)
+    st = _lib.load().dut_minor_write(path.encode(), contig.encode(), C.byref(r), C.byref(opt), err, 512)
+    if st != 0:
+        raise EngineError(st, err.value.decode())
+
+
+def find_minor_alleles(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
+                       min_depth: int = 10, min_quality: int = 20, min_minor_fraction="0.05", min_minor_count: int = 3,
+                       min_base_quality: Optional[int] = None, exclude_flags: int = 0, min_minor_per_strand: int = 0, device_id: int = 0):
+    """dut_find_minor_files: BAM (+ index) and FASTA in, the TSV of second alleles out; region = (start, end), 0-based half
+    open.  min_minor_fraction: decimal text (or a number whose text is one) in (0, 0.5], at most four decimals."""
+    per_10k = minor_fraction_parse(str(min_minor_fraction))
+    opt = _minor_options(min_depth, min_quality, min_minor_count, per_10k, min_base_quality, exclude_flags, min_minor_per_strand)
+    err = C.create_string_buffer(1024)
+    start, end = region if region is not None else (0, 0)
+    st = _lib.load().dut_find_minor_files(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
+                                          int(start), int(end), C.byref(opt), output_file.encode(), device_id, err, 1024)
     if st != 0:
         raise EngineError(st, err.value.decode())

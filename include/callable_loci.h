@@ -444,6 +444,39 @@ cl_status cl_site_scan_ex(cl_ctx *ctx, uint8_t min_quality, uint32_t min_depth, 
  * positions. */
 cl_status cl_site_scan_counts_ex(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start,
                                  uint32_t end, uint32_t *counts);
+/* ---- the minor mode of the dense scan: a second allele beside the most frequent one ------------------------------ */
+/* Over the counters of cl_site_scan (filter == NULL) or cl_site_scan_ex (a filter; needs cl_site_attach_quals), for
+ * every position p of [start, end):
+ *   A C G T      the four counters, strands summed;  depth = the depth of the scan there (N and every other code included)
+ *   major, c1    the largest of A C G T, the first in that order among equals, and its count
+ *   minor, c2    the largest of the other three, the first in that order among equals, and its count
+ *   low_depth    depth < min_depth
+ *   minor        not low, c2 >= min_minor_count and 10000 * c2 >= min_minor_per_10k * depth (taken in 64 bits)
+ *   single       everything else
+ * The three counts add up to end - start.  The positions of class minor come back as candidates, all of them, ascending.
+ * major_fwd .. minor_rev are the strand counts of the two bases under a filter and 0 without one.  ref is the upper-cased
+ * reference byte ('N' at and beyond ref_len); it takes no part in the rule.
+ * Refusals: those of cl_site_scan / cl_site_scan_ex, and CL_ERR_INVALID (with a message) for null params,
+ * min_depth == 0, min_minor_count == 0, min_minor_per_10k outside [1, 5000].  out->candidates is context-owned, valid
+ * until the next cl_site_scan_minor, cl_site_upload or cl_destroy; the candidates of cl_site_scan and cl_site_scan_ex
+ * live elsewhere and stay valid across this call.  Interleaves freely with cl_site_run and every other scan;
+ * cl_site_scan_stats speaks of this scan after it. */
+typedef struct cl_minor_params { uint32_t min_depth, min_minor_count, min_minor_per_10k; } cl_minor_params;
+typedef struct cl_minor_candidate {
+    uint32_t pos;                         /* 1-based */
+    uint8_t  ref, major, minor, pad;      /* major, minor: 'A' 'C' 'G' 'T' */
+    uint32_t a, c, g, t, depth;           /* both strands */
+    uint32_t major_fwd, major_rev, minor_fwd, minor_rev;
+} cl_minor_candidate;
+typedef struct cl_minor_result {
+    uint32_t start, end;
+    uint64_t n_low_depth, n_single, n_minor;      /* sum == end - start */
+    const cl_minor_candidate *candidates;         /* n_minor, ascending position */
+} cl_minor_result;
+cl_status cl_site_scan_minor(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: unfiltered form */,
+                             const cl_minor_params *params, const uint8_t *ref_bases, uint64_t ref_len,
+                             uint32_t start, uint32_t end, cl_minor_result *out);
+
 /* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
  * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
 cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);

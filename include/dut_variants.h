@@ -93,6 +93,48 @@ int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, con
                                const char *output_path, uint32_t min_depth, uint8_t min_quality,
                                const dut_variants_options *opt, int device_id, char *err, size_t err_len);
 
+/* ---- find-minor-alleles: a second allele beside the most frequent one (cl_site_scan_minor) ------------------------- */
+/* The classes of cl_site_scan_minor. */
+enum { DUT_MINOR_LOW_DEPTH = 0, DUT_MINOR_SINGLE = 1, DUT_MINOR_MINOR = 2 };
+
+/* Decimal text to parts per 10 000, exactly: digits, optionally '.' and at most four decimals ("0.05" -> 500, "0.5" ->
+ * 5000, ".0125" -> 125).  The value must lie in (0, 0.5]; no sign, no exponent, nothing after the number. */
+int dut_minor_fraction_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len);
+
+/* The rule of cl_site_scan_minor for one position in plain C++, with the same integer comparison: the class, and in
+ * *major / *minor (may be NULL) the two bases.  depth is the depth of the scan there (a + c + g + t and every other
+ * code).  CL_ERR_INVALID: null or refused params (as cl_site_scan_minor refuses them), a + c + g + t > depth,
+ * depth >= 2^32. */
+int dut_minor_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint64_t depth, const cl_minor_params *params,
+                              char *major, char *minor);
+
+/* What a find-minor-alleles run is asked: the scan's parameters and filter, and the strand mark of the TSV. */
+typedef struct dut_minor_options {
+    uint32_t min_depth;
+    uint8_t  min_quality;
+    int      has_min_base_quality;
+    uint8_t  min_base_quality;
+    uint16_t exclude_flags;
+    uint32_t min_minor_per_10k;       /* 1..5000 */
+    uint32_t min_minor_count;         /* >= 1 */
+    uint32_t min_minor_per_strand;    /* K: filter = "strand" when min(minor_fwd, minor_rev) < K; 0: always PASS */
+} dut_minor_options;
+
+/* The TSV (no device needed): comment lines ##contig= ##range=start-end ##min_depth= ##min_quality= ##min_base_quality=
+ * ("." when !has_min_base_quality) ##exclude_flags=0x%04x ##min_minor_fraction=%.4f ##min_minor_count= ##positions=
+ * ##low_depth= ##single= ##minor=, the header
+ *   #contig pos ref major minor depth A C G T minor_freq major_fwd major_rev minor_fwd minor_rev filter
+ * and one line per candidate: minor_freq = c2 / depth as %.4f.  ##minor= is the scan's count: marked lines stay. */
+int dut_minor_write(const char *path, const char *contig, const cl_minor_result *res, const dut_minor_options *opt,
+                    char *err, size_t err_len);
+
+/* `find-minor-alleles` on files, one GPU: reads as dut_find_variants_files_ex does, always attaches the records' flags
+ * and pass bits and runs the filtered form of cl_site_scan_minor (with no mask and no threshold it counts what the
+ * unfiltered form does), writes the TSV.  Errors with a message: those of dut_find_variants_files, refused options. */
+int dut_find_minor_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
+                         uint32_t end, const dut_minor_options *opt, const char *output_path, int device_id,
+                         char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif
