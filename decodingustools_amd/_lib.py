@@ -201,6 +201,31 @@ class dut_minor_options(C.Structure):
                 ("min_minor_count", C.c_uint32), ("min_minor_per_strand", C.c_uint32)]
 
 
+class cl_del_params(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_del_count", C.c_uint32), ("min_del_per_10k", C.c_uint32)]
+
+
+class cl_del_candidate(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("pad", C.c_uint8 * 3), ("del", C.c_uint32), ("depth", C.c_uint32),
+                ("del_fwd", C.c_uint32), ("del_rev", C.c_uint32), ("depth_fwd", C.c_uint32), ("depth_rev", C.c_uint32)]
+
+
+class cl_del_result(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_low_depth", C.c_uint64), ("n_kept", C.c_uint64),
+                ("n_deleted", C.c_uint64), ("candidates", C.POINTER(cl_del_candidate))]
+
+
+class dut_del_event(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("length", C.c_uint32), ("q", C.c_uint32), ("del", C.c_uint32),
+                ("del_fwd", C.c_uint32), ("del_rev", C.c_uint32), ("max_del", C.c_uint32), ("span", C.c_uint64)]
+
+
+class dut_del_options(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_quality", C.c_uint8), ("has_min_base_quality", C.c_int),
+                ("min_base_quality", C.c_uint8), ("exclude_flags", C.c_uint16), ("min_del_per_10k", C.c_uint32),
+                ("min_del_count", C.c_uint32), ("min_del_per_strand", C.c_uint32)]
+
+
 class dut_variants_options(C.Structure):
     _fields_ = [("filtered", C.c_int), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
                 ("exclude_flags", C.c_uint16), ("min_alt_per_strand", C.c_uint32)]
@@ -228,6 +253,8 @@ SYMBOLS = [
     ("cl_site_scan_counts_ex", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_uint32, C.c_uint32, C.c_void_p]),
     ("cl_site_scan_minor", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_minor_params), C.c_void_p, C.c_uint64,
                                      C.c_uint32, C.c_uint32, C.POINTER(cl_minor_result)]),
+    ("cl_site_scan_dels", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_del_params), C.c_void_p, C.c_uint64,
+                                    C.c_uint32, C.c_uint32, C.POINTER(cl_del_result)]),
     ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
     ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
@@ -243,6 +270,13 @@ SYMBOLS = [
     ("dut_minor_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_minor_result), C.POINTER(dut_minor_options), C.c_char_p, C.c_size_t]),
     ("dut_find_minor_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_minor_options),
                                        C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
+    ("dut_del_fraction_parse", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    ("dut_del_classify_counts", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(cl_del_params)]),
+    ("dut_del_events", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(dut_del_event)), C.POINTER(C.c_size_t)]),
+    ("dut_del_events_free", None, [C.POINTER(dut_del_event)]),
+    ("dut_del_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_del_result), C.POINTER(dut_del_options), C.c_char_p, C.c_size_t]),
+    ("dut_find_deletions_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_del_options),
+                                           C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

@@ -325,6 +325,25 @@ class Engine:
         return MinorResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), single=int(r.n_single), minor=n,
                            candidates=cand, kernel_ms=self.site_scan_stats()[0])
 
+    def site_scan_dels(self, min_quality, min_depth, min_del_count, min_del_per_10k, ref, start=0, end=None, filter=None):
+        """cl_site_scan_dels over [start, end) of the resident tile: positions that the reads delete (a D operation over
+        them), beside the scan's depth.  filter: None for the unfiltered form, else (exclude_flags, use_base_quality) of the
+        attachment.  A DelResult: the three class counts, the candidates (DEL_CANDIDATE) and the kernel's milliseconds."""
+        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
+        if end is None:
+            end = ref.shape[0]
+        flt = None if filter is None else C.byref(_lib.cl_scan_filter(int(filter[0]), 1 if filter[1] else 0, 0))
+        prm = _lib.cl_del_params(int(min_depth), int(min_del_count), int(min_del_per_10k))
+        r = _lib.cl_del_result()
+        self._check(self._lib.cl_site_scan_dels(self._h, int(min_quality), flt, C.byref(prm), _ptr(ref), ref.shape[0], int(start), int(end),
+                                                C.byref(r)))
+        n = int(r.n_deleted)
+        cand = np.zeros(n, DEL_CANDIDATE)
+        if n:
+            C.memmove(cand.ctypes.data, r.candidates, n * DEL_CANDIDATE.itemsize)
+        return DelResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), kept=int(r.n_kept), deleted=n,
+                         candidates=cand, kernel_ms=self.site_scan_stats()[0])
+
     def site_scan_stats(self):
         """(kernel milliseconds, algorithmic bytes) of the last site_scan / site_scan_counts, filtered or not."""
         ms = C.c_double(); b = C.c_uint64()
@@ -378,6 +397,24 @@ SCAN_CANDIDATE_EX = np.dtype(SCAN_CANDIDATE.descr + [("alt_fwd", np.uint32), ("a
 MINOR_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("major", np.uint8), ("minor", np.uint8), ("pad", np.uint8),
                             ("a", np.uint32), ("c", np.uint32), ("g", np.uint32), ("t", np.uint32), ("depth", np.uint32),
                             ("major_fwd", np.uint32), ("major_rev", np.uint32), ("minor_fwd", np.uint32), ("minor_rev", np.uint32)])
+
+
+# cl_del_candidate: the strand counts are 0 in the unfiltered form
+DEL_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("pad", np.uint8, (3,)), ("del", np.uint32), ("depth", np.uint32),
+                          ("del_fwd", np.uint32), ("del_rev", np.uint32), ("depth_fwd", np.uint32), ("depth_rev", np.uint32)])
+
+
+@dataclass
+class DelResult:
+    """cl_del_result (include/callable_loci.h): the three classes add up to end - start; candidates = the positions of
+    class deleted, ascending."""
+    start: int
+    end: int
+    low_depth: int
+    kept: int
+    deleted: int
+    candidates: np.ndarray
+    kernel_ms: float = 0.0
 
 
 @dataclass

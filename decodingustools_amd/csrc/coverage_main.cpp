@@ -1,5 +1,5 @@
 // dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
-// project's own `fingerprint` front end, `find-variants` and `find-minor-alleles`);
+// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles` and `find-deletions`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -41,7 +41,10 @@ static void usage()
             "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
             "       dut-coverage find-minor-alleles <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--min-minor-fraction 0.05] [--min-minor-count 3] [--min-base-quality Q] [--exclude-flags MASK]\n"
-            "       [--min-minor-per-strand K] [--device 0]\n");
+            "       [--min-minor-per-strand K] [--device 0]\n"
+            "       dut-coverage find-deletions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
+            "       [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3] [--min-base-quality Q] [--exclude-flags MASK]\n"
+            "       [--min-del-per-strand K] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -367,6 +370,73 @@ static int find_minor_main(int argc, char **argv)
     _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
 }
 
+// find-deletions: every position of a contig (or of --region) that the reads delete -- at least --min-del-count reads with a
+// D operation over it and --min-del-fraction of depth + deletions (cl_site_scan_dels) -- merged into events of consecutive
+// positions.  Counting as in find-variants with its filter flags.  Argument errors leave with 2 before a device is opened.
+static int find_deletions_main(int argc, char **argv)
+{
+    std::string bam, ref, out, contig;
+    unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
+    int device = 0;
+    bool has_region = false;
+    dut_del_options dopt = {10, 20, 0, 0, 0, 7000, 3, 0};
+    auto usage_fd = []() {
+        fprintf(stderr, "Usage: dut-coverage find-deletions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
+                        "       [--min-depth 10] [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3]\n"
+                        "       [--min-base-quality Q] [--exclude-flags MASK] [--min-del-per-strand K] [--device 0]\n"
+                        "  A position is listed when bases plus deletions there are at least --min-depth and the reads with a D\n"
+                        "  operation over it are at least --min-del-count and --min-del-fraction of that sum (a decimal in (0, 1], at\n"
+                        "  most four decimals).  One line per run of consecutive positions.  --region: 0-based, half open.  Q, MASK as\n"
+                        "  in find-variants; filter is 'strand' when min(del_fwd, del_rev) < K.  Deletions only, one device.\n");
+    };
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i], val;
+        const size_t eq = a.find('=');
+        const bool has_eq = a.rfind("--", 0) == 0 && eq != std::string::npos;
+        if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
+        auto next = [&]() -> const char * {
+            if (has_eq) return val.c_str();
+            if (i + 1 >= argc) { usage_fd(); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-r" || a == "--reference") ref = next();
+        else if (a == "-o" || a == "--output") out = next();
+        else if (a == "-L" || a == "--contig") contig = next();
+        else if (a == "--region") { if (!cli_region(next(), start, end)) return 2; has_region = true; }
+        else if (a == "--min-depth") { if (!cli_min_depth(next(), min_depth)) return 2; }
+        else if (a == "--min-quality") { if (!cli_min_quality(next(), min_quality)) return 2; }
+        else if (a == "--min-del-fraction") {
+            const std::string v = next();
+            char why[128] = {0};
+            if (dut_del_fraction_parse(v.c_str(), &dopt.min_del_per_10k, why, sizeof(why)) != CL_OK) {
+                fprintf(stderr, "error: invalid value '%s' for '--min-del-fraction': %s\n", v.c_str(), why);
+                return 2;
+            }
+        }
+        else if (a == "--min-del-count") {
+            const std::string v = next();
+            if (!cli_count32("--min-del-count", v, dopt.min_del_count)) return 2;
+            if (dopt.min_del_count == 0) { fprintf(stderr, "error: invalid value '%s' for '--min-del-count': at least 1\n", v.c_str()); return 2; }
+        }
+        else if (a == "--min-base-quality") { if (!cli_base_quality(next(), dopt.min_base_quality)) return 2; dopt.has_min_base_quality = 1; }
+        else if (a == "--exclude-flags") { if (!cli_flag_mask(next(), dopt.exclude_flags)) return 2; }
+        else if (a == "--min-del-per-strand") { if (!cli_count32("--min-del-per-strand", next(), dopt.min_del_per_strand)) return 2; }
+        else if (a == "--device") device = atoi(next());
+        else if (a == "-h" || a == "--help") { usage_fd(); return 0; }
+        else if (!a.empty() && a[0] != '-' && bam.empty()) bam = a;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fd(); return 2; }
+    }
+    if (bam.empty() || ref.empty() || out.empty()) { usage_fd(); return 2; }
+    if (contig.empty()) { fprintf(stderr, "error: find-deletions needs '-L <CONTIG>'\n"); usage_fd(); return 2; }
+    dopt.min_depth = (uint32_t)min_depth; dopt.min_quality = (uint8_t)min_quality;
+    char err[1024] = {0};
+    const int rc = dut_find_deletions_files(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end, &dopt,
+                                            out.c_str(), device, err, sizeof(err));
+    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
+    fflush(nullptr);
+    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -386,6 +456,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "fingerprint")) return fingerprint_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-variants")) return find_variants_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-minor-alleles")) return find_minor_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "find-deletions")) return find_deletions_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

@@ -158,16 +158,18 @@ struct SiteResident {
     DevBuf<uint32_t> sx_amb, sx_hist;
     bool attached = false;
     DevBuf<ScanMinorCand> sm_cand;   // cl_site_scan_minor's candidates, of either form
+    DevBuf<ScanDelCand> sd_cand;     // cl_site_scan_dels' candidates, of either form
     // the last cl_site_pileup / cl_site_run and the last cl_site_scan* of either form: the kernels' duration and their
-    // algorithmic bytes; the candidates of the last cl_site_scan, the last cl_site_scan_ex and the last cl_site_scan_minor
+    // algorithmic bytes; the candidates of the last cl_site_scan, cl_site_scan_ex, cl_site_scan_minor and cl_site_scan_dels
     KernelTimer t_pileup, t_scan;
     std::vector<cl_scan_candidate> scan_cand;
     std::vector<cl_scan_candidate_ex> scan_cand_ex;
     std::vector<cl_minor_candidate> minor_cand;
+    std::vector<cl_del_candidate> del_cand;
     void release()
     {
         t_pileup.destroy(); t_scan.destroy();
-        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release();
+        q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release(); sd_cand.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -441,6 +443,7 @@ static cl_status cl_site_run_impl(SiteCtx *c, uint8_t min_quality, const uint32_
 static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_candidate) == 28, "the device writes cl_scan_candidate");
 static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
 static_assert(sizeof(ScanMinorCand) == sizeof(cl_minor_candidate) && sizeof(cl_minor_candidate) == 44, "the device writes cl_minor_candidate");
+static_assert(sizeof(ScanDelCand) == sizeof(cl_del_candidate) && sizeof(cl_del_candidate) == 32, "the device writes cl_del_candidate");
 
 // the argument checks every scan shares, in front of any device work
 static cl_status site_scan_check(SiteCtx *c, const char *who, uint32_t start, uint32_t end)
@@ -709,6 +712,54 @@ static cl_status site_scan_minor_impl(SiteCtx *c, uint8_t min_quality, typename 
     return CL_OK;
 }
 
+// ---- the deletion mode: reads whose D operation covers a position, beside the scan's depth (site_scan.hip.h) ----
+template <bool FILTERED>
+static cl_status site_scan_dels_impl(SiteCtx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, const cl_del_params *prm,
+                                     const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, cl_del_result *out)
+{
+    static const char *const who = "cl_site_scan_dels";
+    if (!out) return fail(c, CL_ERR_INVALID, std::string(who) + ": null result");
+    cl_status s = site_scan_check_form<FILTERED>(c, who, filter, start, end);
+    if (s != CL_OK) return s;
+    SiteResident &S = c->site;
+    if (!prm) return fail(c, CL_ERR_INVALID, std::string(who) + ": null params");
+    if (prm->min_depth == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_depth must be at least 1");
+    if (prm->min_del_count == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_del_count must be at least 1");
+    if (prm->min_del_per_10k < 1 || prm->min_del_per_10k > 10000) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_del_per_10k must lie in 1..10000");
+    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": ref_len differs from the one given to cl_site_upload");
+    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": null reference");
+    std::vector<cl_del_candidate> &cand = S.del_cand;
+    memset(out, 0, sizeof(*out));
+    out->start = start; out->end = end;
+    cand.clear();
+    out->candidates = cand.data();
+    S.t_scan.ms = 0.0; S.t_scan.bytes = 0;
+    if (start == end) return CL_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    StageTimer tmr;
+    unsigned long long h_cls[8];
+    uint64_t n_ref = 0;
+    ScanDelArgs<FILTERED> A;
+    s = site_scan_compacting(c, A, S.sd_cand, ref_bases, ref_len, start, end, h_cls, n_ref, [&] {
+        site_scan_fill<FILTERED>(c, A, filter, min_quality, prm->min_depth, start, end);
+        A.min_del_count = prm->min_del_count; A.min_del_per_10k = prm->min_del_per_10k;
+    }, [&](uint32_t n_blocks) {
+        hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_DELS>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+    });
+    if (s != CL_OK) return s;
+    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
+    cand.resize(n_cand);
+    if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), S.sd_cand.p, n_cand * sizeof(cl_del_candidate), hipMemcpyDeviceToHost));
+    // the tile without its bases: records, ends, CIGAR words; under a filter the flags and the pass bits
+    S.t_scan.bytes = S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + (FILTERED ? (S.nbase + 7) / 8 + S.n * 2 : 0) + n_ref + n_cand * sizeof(cl_del_candidate);
+    tmr.lap("deletion scan: reference in, kernel, candidates back");
+    // the compaction runs wave by wave: ascending position is restored here
+    std::sort(cand.begin(), cand.end(), [](const cl_del_candidate &a, const cl_del_candidate &b) { return a.pos < b.pos; });
+    out->n_low_depth = h_cls[DEL_LOW_DEPTH]; out->n_kept = h_cls[DEL_KEPT]; out->n_deleted = h_cls[DEL_DELETED];
+    out->candidates = cand.data();
+    return CL_OK;
+}
+
 template <bool FILTERED>
 static cl_status site_scan_counts_impl(SiteCtx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, uint32_t start, uint32_t end,
                                        uint32_t *counts)
@@ -820,6 +871,16 @@ cl_status cl_site_scan_minor(cl_ctx *h, uint8_t min_quality, const cl_scan_filte
         if (!c) return CL_ERR_INVALID;
         if (filter) return site_scan_minor_impl<true>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
         return site_scan_minor_impl<false>(c, min_quality, ScanNoFilter{}, params, ref_bases, ref_len, start, end, out);
+    });
+}
+
+cl_status cl_site_scan_dels(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, const cl_del_params *params, const uint8_t *ref_bases,
+                            uint64_t ref_len, uint32_t start, uint32_t end, cl_del_result *out)
+{
+    return site_entry(h, [&](SiteCtx *c) -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (filter) return site_scan_dels_impl<true>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
+        return site_scan_dels_impl<false>(c, min_quality, ScanNoFilter{}, params, ref_bases, ref_len, start, end, out);
     });
 }
 

@@ -51,6 +51,16 @@
 // that order among equals, both times); a position is low_depth (depth < min_depth, the depth of scan_classify: N and
 // the other codes included), minor (c2 >= min_minor_count and 10000 c2 >= min_minor_per_10k depth, in 64 bits) or
 // single.  Nothing is ambiguous: N and the other codes take part only through the depth.
+//
+// The deletion mode (cl_site_scan_dels) counts what the other modes step over: per position the reads whose D operation
+// (CIGAR op 2; not N) covers it, beside the scan's depth.  It needs no base code and loads no seq4.  Its planes are
+// depth and del (by strand under a filter) and they are built from range ends: a run of counted positions is one +1 at
+// its first position and one -1 behind its last (uint32 wrap-around; a -1 that would fall on index kScanWin is dropped),
+// and one workgroup-wide inclusive scan per plane turns the ends into counts.  A D operation is one run with one pass
+// bit, that of its carrier: the read's last query base before it (query index y - 1, 1 <= y <= l_seq; a leading D, a D
+// behind the read's last base and every D of a read without bases do not count).  Without a filter an M run is one run
+// too; under a filter the depth is added per base, by the pass bits.  span = depth + del; a position is low_depth
+// (span < min_depth), deleted (del >= min_del_count and 10000 del >= min_del_per_10k span, in 64 bits) or kept.
 #pragma once
 
 #include <type_traits>
@@ -85,7 +95,19 @@ struct ScanMinorCand {
 };
 enum { MINOR_LOW_DEPTH = 0, MINOR_SINGLE = 1, MINOR_MINOR = 2 };             // its classes, in the first slots of cls
 
-enum ScanMode { SCAN_CALLS = 0, SCAN_DENSE = 1, SCAN_MINOR = 2 };
+// one compacted position of the deletion mode; the strand counts are 0 in the unfiltered form
+struct ScanDelCand {
+    uint32_t pos;                            // 1-based
+    uint8_t  ref, pad[3];
+    uint32_t del, depth;                     // both strands
+    uint32_t del_fwd, del_rev, depth_fwd, depth_rev;
+};
+enum { DEL_LOW_DEPTH = 0, DEL_KEPT = 1, DEL_DELETED = 2 };                   // its classes, in the first slots of cls
+
+enum ScanMode { SCAN_CALLS = 0, SCAN_DENSE = 1, SCAN_MINOR = 2, SCAN_DELS = 3 };
+
+struct ScanNoHook {};                        // a hook of scan_walk_read that a mode does not use
+template <class T> inline constexpr bool scan_hooked = !std::is_same_v<std::remove_cv_t<std::remove_reference_t<T>>, ScanNoHook>;
 
 struct ScanNoFilter {};
 
@@ -152,8 +174,22 @@ struct ScanMinorArgs {
     uint32_t min_minor_count, min_minor_per_10k;
 };
 
+// the deletion mode's record
+template <bool FILTERED>
+struct ScanDelArgs {
+    ScanArgs s;                              // (s.seq4 is never read)
+    typename ScanForm<FILTERED>::Filter f;
+    ScanDelCand *cand;
+    uint32_t min_del_count, min_del_per_10k;
+};
+
 template <bool FILTERED, ScanMode MODE>
-using ScanModeArgs = std::conditional_t<MODE == SCAN_MINOR, ScanMinorArgs<FILTERED>, ScanFormArgs<FILTERED>>;
+using ScanModeArgs = std::conditional_t<MODE == SCAN_MINOR, ScanMinorArgs<FILTERED>,
+                                        std::conditional_t<MODE == SCAN_DELS, ScanDelArgs<FILTERED>, ScanFormArgs<FILTERED>>>;
+
+// LDS planes of a mode: depth and del by strand in the deletion mode (8 KB, 16 KB), the form's base planes otherwise
+template <bool FILTERED, ScanMode MODE>
+inline constexpr uint32_t kScanPlanes = MODE == SCAN_DELS ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
 
 // number of CIGAR operations and bases of a read, with SiteRec's escape to the next record's offsets
 __device__ __forceinline__ void scan_read_extent(const SiteRec *rec, uint32_t r, const uint4 &rr, uint32_t &k1, unsigned long long &slen)
@@ -218,9 +254,13 @@ __device__ __forceinline__ bool scan_read_counts(const ScanArgs &a, const uint4 
 // run = begin_run(bi, any) with the base bi of its first position in [lo, hi), in the numbering of seq4, and whether it
 // has one at all; then per_base(p, bi, run) for every position p.  What a form keeps from base to base (the word of pass
 // bits) is that run value: it does not outlive the operation, and so holds no register across the CIGAR loop.
-template <class BeginRun, class PerBase>
+// Two more hooks, for the deletion mode (ScanNoHook: not compiled in): on_run(p0, p1) once per M/=/X operation with a
+// position in [lo, hi), [p0, p1) being the positions per_base would see; on_del(p0, p1, ci) once per D operation (op 2,
+// not N) whose carrier exists, [p0, p1) being its positions in [lo, hi) and ci the carrier's base in the numbering of
+// seq4.  per_base itself may be ScanNoHook.
+template <class BeginRun, class PerBase, class OnRun = ScanNoHook, class OnDel = ScanNoHook>
 __device__ __forceinline__ void scan_walk_read(const ScanArgs &a, uint32_t r, const uint4 &rr, uint32_t lo, uint32_t hi, BeginRun &&begin_run,
-                                               PerBase &&per_base)
+                                               PerBase &&per_base, OnRun &&on_run = OnRun{}, OnDel &&on_del = OnDel{})
 {
     uint32_t k1; unsigned long long slen;
     scan_read_extent(a.rec, r, rr, k1, slen);
@@ -234,11 +274,20 @@ __device__ __forceinline__ void scan_walk_read(const ScanArgs &a, uint32_t r, co
             // [x, x + l) cut to [lo, hi) and to the bases the read has (query index < l_seq, caller.rs:105)
             unsigned long long p0 = x > lo ? x : lo, p1 = x + l < hi ? x + l : hi;
             if (y < slen) { if (p1 - x > slen - y && p1 > x) p1 = x + (slen - y); } else p1 = p0;
-            unsigned long long bi = s0 + y + (p0 - x);
-            auto run = begin_run(bi, p0 < p1);
-            for (unsigned long long p = p0; p < p1; ++p, ++bi) per_base((uint32_t)p, bi, run);
+            if constexpr (scan_hooked<OnRun>) { if (p0 < p1) on_run((uint32_t)p0, (uint32_t)p1); }
+            if constexpr (scan_hooked<PerBase>) {
+                unsigned long long bi = s0 + y + (p0 - x);
+                auto run = begin_run(bi, p0 < p1);
+                for (unsigned long long p = p0; p < p1; ++p, ++bi) per_base((uint32_t)p, bi, run);
+            }
             x += l; y += l;
         } else if (op_del(op)) {
+            if constexpr (scan_hooked<OnDel>) {
+                if (op == 2u && y >= 1ull && y <= slen) {                      // the carrier: query index y - 1
+                    const unsigned long long p0 = x > lo ? x : lo, p1 = x + l < hi ? x + l : hi;
+                    if (p0 < p1) on_del((uint32_t)p0, (uint32_t)p1, s0 + y - 1ull);
+                }
+            }
             x += l;
         } else if (op_ins(op)) {
             y += l;
@@ -342,13 +391,14 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
 {
     using Form = ScanForm<FILTERED>;
     constexpr uint32_t S = Form::kStrands;
-    __shared__ alignas(8) uint32_t s_cnt[Form::kPlanes * kScanWin];
+    constexpr uint32_t kPlanes = kScanPlanes<FILTERED, MODE>;
+    __shared__ alignas(MODE == SCAN_DELS ? 16 : 8) uint32_t s_cnt[kPlanes * kScanWin];   // (the deletion mode reads it four words at a time)
     const ScanArgs &a = ax.s;
     const uint32_t tid = threadIdx.x;
     const uint32_t w = a.win0 + blockIdx.x;
     const ScanWindow win = scan_window(a, w);
     const uint32_t ws = win.ws, lo = win.lo, we = win.we, hi = win.hi;
-    for (uint32_t i = tid; i < Form::kPlanes * kScanWin; i += kBlock) s_cnt[i] = 0;
+    for (uint32_t i = tid; i < kPlanes * kScanWin; i += kBlock) s_cnt[i] = 0;
     __syncthreads();
     const uint32_t r_first = a.wfirst[w], r_last = a.wlast[w];
     if (r_first < r_last && lo < hi) {
@@ -361,14 +411,38 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
                 if (fl & ax.f.exclude_flags) continue;
                 rev = (fl >> 4) & 1u;
             }
-            scan_walk_read(a, r, rr, lo, hi,
-                [&](unsigned long long bi, bool any) {
-                    if constexpr (FILTERED) return scan_pass_word(ax.f, bi, any); else return ScanNoFilter{};
-                },
-                [&](uint32_t p, unsigned long long bi, auto &pw) {
-                    if constexpr (FILTERED) { if (!scan_base_passes(ax.f, bi, pw)) return; }
-                    atomicAdd(&s_cnt[Form::plane(scan_base_code(a.seq4, bi), rev) * kScanWin + (p - ws)], 1u);
-                });
+            if constexpr (MODE == SCAN_DELS) {
+                // planes: depth by strand, then del by strand.  A run's ends: +1 at its first position, -1 behind its last
+                auto run_ends = [&](uint32_t plane, uint32_t p0, uint32_t p1) {
+                    atomicAdd(&s_cnt[plane * kScanWin + (p0 - ws)], 1u);
+                    if (p1 - ws < kScanWin) atomicAdd(&s_cnt[plane * kScanWin + (p1 - ws)], 0xFFFFFFFFu);
+                };
+                if constexpr (FILTERED) {
+                    scan_walk_read(a, r, rr, lo, hi,
+                        [&](unsigned long long bi, bool any) { return scan_pass_word(ax.f, bi, any); },
+                        [&](uint32_t p, unsigned long long bi, unsigned long long &pw) {
+                            if (scan_base_passes(ax.f, bi, pw)) atomicAdd(&s_cnt[rev * kScanWin + (p - ws)], 1u);
+                        },
+                        ScanNoHook{},
+                        [&](uint32_t p0, uint32_t p1, unsigned long long ci) {
+                            if (ax.f.use_bq && !((ax.f.pass[ci >> 6] >> (ci & 63ull)) & 1ull)) return;
+                            run_ends(S + rev, p0, p1);
+                        });
+                } else {
+                    scan_walk_read(a, r, rr, lo, hi, ScanNoHook{}, ScanNoHook{},
+                        [&](uint32_t p0, uint32_t p1) { run_ends(0u, p0, p1); },
+                        [&](uint32_t p0, uint32_t p1, unsigned long long) { run_ends(1u, p0, p1); });
+                }
+            } else {
+                scan_walk_read(a, r, rr, lo, hi,
+                    [&](unsigned long long bi, bool any) {
+                        if constexpr (FILTERED) return scan_pass_word(ax.f, bi, any); else return ScanNoFilter{};
+                    },
+                    [&](uint32_t p, unsigned long long bi, auto &pw) {
+                        if constexpr (FILTERED) { if (!scan_base_passes(ax.f, bi, pw)) return; }
+                        atomicAdd(&s_cnt[Form::plane(scan_base_code(a.seq4, bi), rev) * kScanWin + (p - ws)], 1u);
+                    });
+            }
         }
     }
     __syncthreads();
@@ -380,9 +454,59 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
             const uint32_t q = i / Form::kDense, cc = i - q * Form::kDense, o = lo - ws + q;
             uint32_t v;
             if (cc < Form::kDense - 1u) v = s_cnt[cc * kScanWin + o];
-            else { v = 0; for (uint32_t k = 0; k < Form::kPlanes; ++k) v += s_cnt[k * kScanWin + o]; }
+            else { v = 0; for (uint32_t k = 0; k < kPlanes; ++k) v += s_cnt[k * kScanWin + o]; }
             out[i] = v;
         }
+    } else if constexpr (MODE == SCAN_DELS) {
+        // Four consecutive positions per thread, all planes into registers.  The planes of range ends (both unfiltered,
+        // the del planes under a filter: always the last two) become counts by an inclusive scan over the window: within
+        // the thread, over the wave by DPP, over the workgroup through the waves' totals.
+        static_assert(kScanWin == 4u * (uint32_t)kBlock, "four positions per thread");
+        __shared__ uint32_t s_wtot[2][kBlock / 64];
+        const uint32_t lane = tid & 63u, wv = tid >> 6;
+        uint32_t q[kPlanes][4];
+#pragma unroll
+        for (uint32_t k = 0; k < kPlanes; ++k) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(&s_cnt[k * kScanWin + 4u * tid]);
+            q[k][0] = v.x; q[k][1] = v.y; q[k][2] = v.z; q[k][3] = v.w;
+        }
+        uint32_t before[2];                                                    // the sum of the wave's earlier threads
+#pragma unroll
+        for (uint32_t k = kPlanes - 2u; k < kPlanes; ++k) {
+            q[k][1] += q[k][0]; q[k][2] += q[k][1]; q[k][3] += q[k][2];
+            const uint32_t inc = dpp_incl_scan_u32(q[k][3]);
+            if (lane == 63u) s_wtot[k - (kPlanes - 2u)][wv] = inc;
+            before[k - (kPlanes - 2u)] = inc - q[k][3];
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t k = kPlanes - 2u; k < kPlanes; ++k) {
+            uint32_t add = before[k - (kPlanes - 2u)];
+#pragma unroll
+            for (uint32_t j = 0; j < (uint32_t)kBlock / 64u; ++j) add += j < wv ? s_wtot[k - (kPlanes - 2u)][j] : 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) q[k][j] += add;
+        }
+        uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {                                     // (uniform trip count: the ballot needs whole waves)
+            const uint32_t o = 4u * tid + j, p = ws + o;
+            int cls = -1;
+            ScanDelCand cd;
+            if (p >= lo && p < we) {
+                const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, del_f = q[S][j], del_r = FILTERED ? q[2u * S - 1u][j] : 0u;
+                const unsigned long long depth = (unsigned long long)depth_f + depth_r, del = (unsigned long long)del_f + del_r, span = depth + del;
+                cls = span < a.min_depth ? DEL_LOW_DEPTH
+                    : (del >= ax.min_del_count && 10000ull * del >= (unsigned long long)ax.min_del_per_10k * span) ? DEL_DELETED : DEL_KEPT;
+                mine[cls] += 1u;
+                const uint32_t rb = (p < hi ? a.refb[p - a.start] : (uint32_t)'N') & ~32u;
+                cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.pad[0] = cd.pad[1] = cd.pad[2] = 0;
+                cd.del = (uint32_t)del; cd.depth = (uint32_t)depth;
+                cd.del_fwd = FILTERED ? del_f : 0u; cd.del_rev = del_r; cd.depth_fwd = FILTERED ? depth_f : 0u; cd.depth_rev = depth_r;
+            }
+            scan_compact(cls == DEL_DELETED, cd, lane, a.n_cand, ax.cand, a.cand_cap);
+        }
+        scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);
     } else if constexpr (MODE == SCAN_MINOR) {
         uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
         const uint32_t lane = tid & 63u;

@@ -2,7 +2,8 @@
 // the device's integer test is held against), the annotation of candidates against a haplogroup tree, the TSV of
 // `find-variants`; the second-allele rule of `find-minor-alleles` in plain C++, its fraction parser and its TSV.  Host-only
 // except dut_find_variants_files(_ex) and dut_find_minor_files, which run the device engine's cl_site_scan(_ex) and
-// cl_site_scan_minor.
+// cl_site_scan_minor.  The same for `find-deletions`: the deletion rule, the merge of candidate positions into events,
+// the TSV, and dut_find_deletions_files over cl_site_scan_dels.
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -229,7 +230,8 @@ int dut_scan_classify_counts(const uint32_t counts5[5], uint8_t ref_byte, uint32
     return DUT_SCAN_MIXED;
 }
 
-int dut_minor_fraction_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len)
+// decimal text to parts per 10 000, exactly; the value in [1, max_per_10k], `range` naming that interval in the message
+static int fraction_parse(const char *text, uint32_t *per_10k, uint32_t max_per_10k, const char *range, char *err, size_t err_len)
 {
     if (per_10k) *per_10k = 0;
     if (!text || !per_10k) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
@@ -242,9 +244,113 @@ int dut_minor_fraction_parse(const char *text, uint32_t *per_10k, char *err, siz
     if (n_frac > 4) { set_err(err, err_len, "at most four decimals"); return CL_ERR_INVALID; }
     for (int k = n_frac; k < 4; ++k) frac *= 10;
     const uint64_t v = whole * 10000 + frac;
-    if (v < 1 || v > 5000) { set_err(err, err_len, "the fraction must lie in (0, 0.5]"); return CL_ERR_INVALID; }
+    if (v < 1 || v > max_per_10k) { set_err(err, err_len, std::string("the fraction must lie in ") + range); return CL_ERR_INVALID; }
     *per_10k = (uint32_t)v;
     return CL_OK;
+}
+
+int dut_minor_fraction_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len)
+{
+    return fraction_parse(text, per_10k, 5000, "(0, 0.5]", err, err_len);
+}
+
+int dut_del_fraction_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len)
+{
+    return fraction_parse(text, per_10k, 10000, "(0, 1]", err, err_len);
+}
+
+static bool del_params_ok(const cl_del_params *p)
+{
+    return p && p->min_depth != 0 && p->min_del_count != 0 && p->min_del_per_10k >= 1 && p->min_del_per_10k <= 10000;
+}
+
+int dut_del_classify_counts(uint32_t del, uint32_t depth, const cl_del_params *params)
+{
+    if (!del_params_ok(params)) return CL_ERR_INVALID;
+    const uint64_t span = (uint64_t)del + depth;
+    if (span < params->min_depth) return DUT_DEL_LOW_DEPTH;
+    return (del >= params->min_del_count && 10000ull * del >= (uint64_t)params->min_del_per_10k * span) ? DUT_DEL_DELETED : DUT_DEL_KEPT;
+}
+
+// maximal runs of consecutive positions; per run the position of the smallest del (the first among equals)
+static int del_events(const cl_del_candidate *cand, size_t n, std::vector<dut_del_event> &ev)
+{
+    for (size_t i = 0; i < n; ++i) {
+        const cl_del_candidate &c = cand[i];
+        if (i && c.pos <= cand[i - 1].pos) return CL_ERR_INVALID;
+        if (i == 0 || c.pos != cand[i - 1].pos + 1) {
+            dut_del_event e{};
+            e.start = e.end = e.q = c.pos; e.length = 1;
+            e.del = e.max_del = c.del; e.del_fwd = c.del_fwd; e.del_rev = c.del_rev; e.span = (uint64_t)c.del + c.depth;
+            ev.push_back(e);
+            continue;
+        }
+        dut_del_event &e = ev.back();
+        e.end = c.pos; e.length += 1;
+        if (c.del < e.del) { e.q = c.pos; e.del = c.del; e.del_fwd = c.del_fwd; e.del_rev = c.del_rev; e.span = (uint64_t)c.del + c.depth; }
+        e.max_del = std::max(e.max_del, c.del);
+    }
+    return CL_OK;
+}
+
+int dut_del_events(const cl_del_candidate *candidates, size_t n, dut_del_event **events, size_t *n_events)
+{
+    if (events) *events = nullptr;
+    if (n_events) *n_events = 0;
+    if (!events || !n_events || (n && !candidates)) return CL_ERR_INVALID;
+    try {
+        std::vector<dut_del_event> ev;
+        if (del_events(candidates, n, ev) != CL_OK) return CL_ERR_INVALID;
+        if (ev.empty()) return CL_OK;
+        dut_del_event *out = static_cast<dut_del_event *>(malloc(ev.size() * sizeof(dut_del_event)));
+        if (!out) return CL_ERR_NOMEM;
+        memcpy(out, ev.data(), ev.size() * sizeof(dut_del_event));
+        *events = out; *n_events = ev.size();
+        return CL_OK;
+    }
+    catch (...) { return CL_ERR_NOMEM; }
+}
+
+void dut_del_events_free(dut_del_event *events) { free(events); }
+
+static int del_write(const char *path, const char *contig, const cl_del_result *res, const dut_del_options *opt, char *err, size_t err_len)
+{
+    if (!path || !contig || !res || !opt || (res->n_deleted && !res->candidates)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    std::vector<dut_del_event> ev;
+    if (del_events(res->candidates, (size_t)res->n_deleted, ev) != CL_OK) { set_err(err, err_len, "candidate positions must ascend"); return CL_ERR_INVALID; }
+    std::string s;
+    char b[512];
+    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n", contig, res->start, res->end, opt->min_depth,
+             (unsigned)opt->min_quality);
+    s += b;
+    if (opt->has_min_base_quality) snprintf(b, sizeof(b), "##min_base_quality=%u\n", (unsigned)opt->min_base_quality);
+    else snprintf(b, sizeof(b), "##min_base_quality=.\n");
+    s += b;
+    snprintf(b, sizeof(b), "##exclude_flags=0x%04x\n##min_del_fraction=%.4f\n##min_del_count=%u\n##positions=%u\n", (unsigned)opt->exclude_flags,
+             (double)opt->min_del_per_10k / 10000.0, opt->min_del_count, res->end - res->start);
+    s += b;
+    snprintf(b, sizeof(b), "##low_depth=%llu\n##kept=%llu\n##deleted=%llu\n##events=%llu\n", (unsigned long long)res->n_low_depth,
+             (unsigned long long)res->n_kept, (unsigned long long)res->n_deleted, (unsigned long long)ev.size());
+    s += b;
+    s += "#contig\tstart\tend\tlength\tref\tdel\tspan\tfreq\tmax_del\tdel_fwd\tdel_rev\tfilter\n";
+    size_t at = 0;                                                           // the event's first candidate
+    for (const dut_del_event &e : ev) {
+        std::string ref = ".";
+        if (e.length <= 64) { ref.clear(); for (uint32_t k = 0; k < e.length; ++k) ref += (char)res->candidates[at + k].ref; }
+        at += e.length;
+        const double freq = e.span ? (double)e.del / (double)e.span : 0.0;
+        const bool strand = std::min(e.del_fwd, e.del_rev) < opt->min_del_per_strand;
+        snprintf(b, sizeof(b), "\t%u\t%u\t%u\t%s\t%u\t%llu\t%.4f\t%u\t%u\t%u\t%s\n", e.start, e.end, e.length, ref.c_str(), e.del,
+                 (unsigned long long)e.span, freq, e.max_del, e.del_fwd, e.del_rev, strand ? "strand" : "PASS");
+        s += contig; s += b;
+    }
+    return write_file(path, s, err, err_len);
+}
+
+int dut_del_write(const char *path, const char *contig, const cl_del_result *res, const dut_del_options *opt, char *err, size_t err_len)
+{
+    try { return del_write(path, contig, res, opt, err, err_len); }
+    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
 }
 
 int dut_minor_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint64_t depth, const cl_minor_params *params, char *major, char *minor)
@@ -413,6 +519,36 @@ int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, con
     // no exception leaves the library through the C ABI
     try { return dut_find_variants_files_impl(bam_path, fasta_path, contig, has_region, start, end, tree_json_path, provider, tree_type,
                                                output_path, min_depth, min_quality, opt, device_id, err, err_len); }
+    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
+    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+}
+
+static int dut_find_deletions_files_impl(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
+                                         uint32_t end, const dut_del_options *o, const char *output_path, int device_id, char *err, size_t err_len)
+{
+    if (!bam_path || !fasta_path || !contig || !output_path || !o) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    if (o->min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
+    if (o->min_del_count == 0) { set_err(err, err_len, "min_del_count must be at least 1"); return CL_ERR_INVALID; }
+    if (o->min_del_per_10k < 1 || o->min_del_per_10k > 10000) { set_err(err, err_len, "min_del_per_10k must lie in 1..10000"); return CL_ERR_INVALID; }
+    ScanFiles F;
+    int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
+    if (rc != CL_OK) return rc;
+    if ((rc = scan_files_upload(F, contig, device_id, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
+    // always the filtered form: its strand planes give the per-strand counts; with no mask and no threshold it counts
+    // what the unfiltered form does
+    if ((rc = scan_files_attach(F, o->has_min_base_quality, o->min_base_quality, err, err_len)) != CL_OK) return rc;
+    const cl_scan_filter flt = {o->exclude_flags, (uint8_t)(o->has_min_base_quality ? 1 : 0), 0};
+    const cl_del_params prm = {o->min_depth, o->min_del_count, o->min_del_per_10k};
+    cl_del_result res;
+    rc = cl_site_scan_dels(F.ctx.get(), o->min_quality, &flt, &prm, F.bases, F.blen, start, end, &res);
+    if (rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return rc; }
+    return dut_del_write(output_path, contig, &res, o, err, err_len);
+}
+
+int dut_find_deletions_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
+                             const dut_del_options *opt, const char *output_path, int device_id, char *err, size_t err_len)
+{
+    try { return dut_find_deletions_files_impl(bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id, err, err_len); }
     catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
     catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
 }

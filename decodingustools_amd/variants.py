@@ -7,12 +7,14 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .callable_loci import MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, EngineError, MinorResult, ScanResult
+from .callable_loci import DEL_CANDIDATE, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, DelResult, EngineError, MinorResult, ScanResult
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
 MINOR_LOW_DEPTH, MINOR_SINGLE, MINOR_MINOR = range(3)
 MINOR_CLASS_NAMES = ("low_depth", "single", "minor")
+DEL_LOW_DEPTH, DEL_KEPT, DEL_DELETED = range(3)
+DEL_CLASS_NAMES = ("low_depth", "kept", "deleted")
 CLASS_NAMES = ("low_depth", "mixed", "uncomparable", "match", "variant", "undetermined")
 
 
@@ -227,5 +229,95 @@ def find_minor_alleles(bam_file: str, reference_file: str, contig: str, output_f
     start, end = region if region is not None else (0, 0)
     st = _lib.load().dut_find_minor_files(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
                                           int(start), int(end), C.byref(opt), output_file.encode(), device_id, err, 1024)
+    if st != 0:
+        raise EngineError(st, err.value.decode())
+
+
+def del_fraction_parse(text: str) -> int:
+    """dut_del_fraction_parse: decimal text in (0, 1] with at most four decimals to parts per 10 000, exactly."""
+    v = C.c_uint32()
+    err = C.create_string_buffer(256)
+    st = _lib.load().dut_del_fraction_parse(text.encode(), C.byref(v), err, 256)
+    if st != 0:
+        raise ValueError(f"invalid fraction '{text}': {err.value.decode()}")
+    return int(v.value)
+
+
+def del_classify_counts(n_del, depth, min_depth, min_del_count, min_del_per_10k) -> int:
+    """The class of one position by the rule of cl_site_scan_dels in plain code (dut_del_classify_counts)."""
+    prm = _lib.cl_del_params(int(min_depth), int(min_del_count), int(min_del_per_10k))
+    st = _lib.load().dut_del_classify_counts(int(n_del), int(depth), C.byref(prm))
+    if st < 0:
+        raise EngineError(st, "invalid parameters")
+    return st
+
+
+def del_events(candidates) -> List[dict]:
+    """dut_del_events: the candidates (DEL_CANDIDATE, ascending position) merged into events, one per maximal run of
+    consecutive positions: start, end (1-based, inclusive), length, and of the position q where del is smallest (the first
+    among equals) del, span, del_fwd, del_rev; max_del over the run."""
+    cand = np.ascontiguousarray(candidates, DEL_CANDIDATE).reshape(-1)
+    ev = C.POINTER(_lib.dut_del_event)()
+    n = C.c_size_t()
+    lib = _lib.load()
+    st = lib.dut_del_events(cand.ctypes.data if cand.shape[0] else None, cand.shape[0], C.byref(ev), C.byref(n))
+    if st != 0:
+        raise EngineError(st, "candidate positions must ascend")
+    try:
+        return [dict(start=int(e.start), end=int(e.end), length=int(e.length), q=int(e.q), span=int(e.span), max_del=int(e.max_del),
+                     del_fwd=int(e.del_fwd), del_rev=int(e.del_rev), **{"del": int(getattr(e, "del"))}) for e in ev[:n.value]]
+    finally:
+        lib.dut_del_events_free(ev)
+
+
+def _del_options(min_depth, min_quality, min_del_count, min_del_per_10k, min_base_quality, exclude_flags,
+                 min_del_per_strand) -> "_lib.dut_del_options":
+    if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
+        raise ValueError("min_base_quality: 0..255")
+    if not 0 <= int(exclude_flags) <= 0xFFFF:
+        raise ValueError("exclude_flags: 0..65535")
+    if not 0 <= int(min_quality) <= 255:
+        raise ValueError("min_quality: 0..255")
+    for name, v in (("min_depth", min_depth), ("min_del_count", min_del_count), ("min_del_per_10k", min_del_per_10k),
+                    ("min_del_per_strand", min_del_per_strand)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name}: 0..2^32-1")
+    o = _lib.dut_del_options()
+    o.min_depth, o.min_quality = int(min_depth), int(min_quality)
+    o.has_min_base_quality = 0 if min_base_quality is None else 1
+    o.min_base_quality = 0 if min_base_quality is None else int(min_base_quality)
+    o.exclude_flags = int(exclude_flags)
+    o.min_del_per_10k, o.min_del_count, o.min_del_per_strand = int(min_del_per_10k), int(min_del_count), int(min_del_per_strand)
+    return o
+
+
+def write_deletions(path: str, contig: str, result: DelResult, min_depth: int, min_quality: int, min_del_count: int,
+                    min_del_per_10k: int, min_base_quality=None, exclude_flags: int = 0, min_del_per_strand: int = 0):
+    """The TSV of find-deletions (dut_del_write) for the DelResult of Engine.site_scan_dels.  No device is needed."""
+    cand = np.ascontiguousarray(result.candidates, DEL_CANDIDATE).reshape(-1)
+    if cand.shape[0] != result.deleted:
+        raise ValueError("deleted count and candidates disagree")
+    opt = _del_options(min_depth, min_quality, min_del_count, min_del_per_10k, min_base_quality, exclude_flags, min_del_per_strand)
+    r = _lib.cl_del_result()
+    r.start, r.end = result.start, result.end
+    r.n_low_depth, r.n_kept, r.n_deleted = result.low_depth, result.kept, result.deleted
+    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_del_candidate))
+    err = C.create_string_buffer(512)
+    st = _lib.load().dut_del_write(path.encode(), contig.encode(), C.byref(r), C.byref(opt), err, 512)
+    if st != 0:
+        raise EngineError(st, err.value.decode())
+
+
+def find_deletions(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
+                   min_depth: int = 10, min_quality: int = 20, min_del_fraction="0.7", min_del_count: int = 3,
+                   min_base_quality: Optional[int] = None, exclude_flags: int = 0, min_del_per_strand: int = 0, device_id: int = 0):
+    """dut_find_deletions_files: BAM (+ index) and FASTA in, the TSV of deletion events out; region = (start, end), 0-based
+    half open.  min_del_fraction: decimal text (or a number whose text is one) in (0, 1], at most four decimals."""
+    per_10k = del_fraction_parse(str(min_del_fraction))
+    opt = _del_options(min_depth, min_quality, min_del_count, per_10k, min_base_quality, exclude_flags, min_del_per_strand)
+    err = C.create_string_buffer(1024)
+    start, end = region if region is not None else (0, 0)
+    st = _lib.load().dut_find_deletions_files(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
+                                              int(start), int(end), C.byref(opt), output_file.encode(), device_id, err, 1024)
     if st != 0:
         raise EngineError(st, err.value.decode())

@@ -477,6 +477,46 @@ cl_status cl_site_scan_minor(cl_ctx *ctx, uint8_t min_quality, const cl_scan_fil
                              const cl_minor_params *params, const uint8_t *ref_bases, uint64_t ref_len,
                              uint32_t start, uint32_t end, cl_minor_result *out);
 
+/* ---- the deletion mode of the dense scan: per-position deletion counts and calls --------------------------------- */
+/* The read gates are those of cl_site_scan (filter == NULL) or cl_site_scan_ex (a filter, exclude_flags included; needs
+ * cl_site_attach_quals).  For every position p of [start, end):
+ *   depth        the scan's depth: every base of an M/=/X operation, all 16 codes; under use_base_quality only bases whose
+ *                pass bit is set.  Exactly the depth of cl_site_scan_counts / cl_site_scan_counts_ex at p.
+ *   del          the reads passing the same gates that have a D operation (CIGAR op 2; N, op 3, is no deletion) covering
+ *                p, with p < min(contig_len, ref_len), and whose carrier base exists.  The carrier is the read's last
+ *                query base before the operation: query index y - 1, y = the query bases the operations before it consume
+ *                (M I S = X), 1 <= y <= l_seq.  A leading D (y == 0), a D behind the point where the read has run out of
+ *                bases (y > l_seq) and every D of a read with l_seq == 0 do not count.  Under use_base_quality the
+ *                deletion counts only if the carrier's pass bit is set (a carrier without a quality value passes).
+ *   span         depth + del, strands summed
+ *   low_depth    span < min_depth
+ *   deleted      not low, del >= min_del_count and 10000 * del >= min_del_per_10k * span (taken in 64 bits)
+ *   kept         everything else
+ * The three counts add up to end - start.  The positions of class deleted come back as candidates, all of them,
+ * ascending.  del_fwd .. depth_rev are the strand counts under a filter and 0 without one.  ref is the upper-cased
+ * reference byte ('N' at and beyond ref_len); it takes no part in the rule.  min_del_per_10k = 7000 is the calling
+ * rule's 0.7 applied to the deletion.
+ * Refusals: those of cl_site_scan / cl_site_scan_ex, and CL_ERR_INVALID (with a message) for null params,
+ * min_depth == 0, min_del_count == 0, min_del_per_10k outside [1, 10000].  out->candidates is context-owned, valid until
+ * the next cl_site_scan_dels, cl_site_upload or cl_destroy; the candidates of the other scans live elsewhere and stay
+ * valid across this call.  Interleaves freely with cl_site_run and every other scan; cl_site_scan_stats speaks of this
+ * scan after it. */
+typedef struct cl_del_params { uint32_t min_depth, min_del_count, min_del_per_10k; } cl_del_params;
+typedef struct cl_del_candidate {
+    uint32_t pos;                         /* 1-based */
+    uint8_t  ref, pad[3];
+    uint32_t del, depth;                  /* both strands */
+    uint32_t del_fwd, del_rev, depth_fwd, depth_rev;
+} cl_del_candidate;
+typedef struct cl_del_result {
+    uint32_t start, end;
+    uint64_t n_low_depth, n_kept, n_deleted;      /* sum == end - start */
+    const cl_del_candidate *candidates;           /* n_deleted, ascending position */
+} cl_del_result;
+cl_status cl_site_scan_dels(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: unfiltered form */,
+                            const cl_del_params *params, const uint8_t *ref_bases, uint64_t ref_len,
+                            uint32_t start, uint32_t end, cl_del_result *out);
+
 /* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
  * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
 cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);

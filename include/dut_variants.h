@@ -4,8 +4,8 @@
  *
  * The reference has no such subcommand.  The counting and the call are the ones of find-y-branch / find-mt-branch
  * (haplogroup::caller::process_region, src/haplogroup/caller.rs:62-152), taken at every position of a contig or a
- * region instead of at the tree's sites, so the two never disagree about a tree site.  SNVs only: no insertions or
- * deletions, no consensus FASTA.  With dut_variants_options the scan takes a flag mask and a base-quality threshold
+ * region instead of at the tree's sites, so the two never disagree about a tree site.  find-variants itself calls SNVs
+ * only; deletions are counted and called per position by find-deletions (below); no insertions, no consensus FASTA.  With dut_variants_options the scan takes a flag mask and a base-quality threshold
  * (cl_site_scan_ex) and the TSV carries per-strand allele counts and a strand filter.
  */
 #ifndef DUT_VARIANTS_H
@@ -134,6 +134,63 @@ int dut_minor_write(const char *path, const char *contig, const cl_minor_result 
 int dut_find_minor_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
                          uint32_t end, const dut_minor_options *opt, const char *output_path, int device_id,
                          char *err, size_t err_len);
+
+/* ---- find-deletions: per-position deletion counts and calls (cl_site_scan_dels) ------------------------------------ */
+/* The classes of cl_site_scan_dels. */
+enum { DUT_DEL_LOW_DEPTH = 0, DUT_DEL_KEPT = 1, DUT_DEL_DELETED = 2 };
+
+/* Decimal text to parts per 10 000, exactly, as dut_minor_fraction_parse takes it ("0.7" -> 7000, "1" -> 10000,
+ * ".0001" -> 1).  The value must lie in (0, 1]. */
+int dut_del_fraction_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len);
+
+/* The rule of cl_site_scan_dels for one position in plain C++, with the same integer comparison: span = del + depth;
+ * low_depth when span < min_depth; deleted when del >= min_del_count and 10000 * del >= min_del_per_10k * span (in 64
+ * bits); kept otherwise.  CL_ERR_INVALID: null or refused params (as cl_site_scan_dels refuses them). */
+int dut_del_classify_counts(uint32_t del, uint32_t depth, const cl_del_params *params);
+
+/* One deletion event: a maximal run of consecutive candidate positions (runs end at the range's borders, where the
+ * candidates do).  start .. end are 1-based, inclusive; length = end - start + 1.  q is the position of the run where
+ * del is smallest, the first among equals: del, span = del + depth, del_fwd, del_rev are those of q.  max_del is the
+ * largest del of the run. */
+typedef struct dut_del_event {
+    uint32_t start, end, length;
+    uint32_t q;
+    uint32_t del, del_fwd, del_rev, max_del;
+    uint64_t span;
+} dut_del_event;
+
+/* Merges candidates (ascending position, as cl_site_scan_dels returns them) into events.  *events: malloc'ed, release
+ * with dut_del_events_free (NULL when there is none).  CL_ERR_INVALID: null argument, positions not ascending. */
+int dut_del_events(const cl_del_candidate *candidates, size_t n, dut_del_event **events, size_t *n_events);
+void dut_del_events_free(dut_del_event *events);
+
+/* What a find-deletions run is asked: the scan's parameters and filter, and the strand mark of the TSV. */
+typedef struct dut_del_options {
+    uint32_t min_depth;
+    uint8_t  min_quality;
+    int      has_min_base_quality;
+    uint8_t  min_base_quality;
+    uint16_t exclude_flags;
+    uint32_t min_del_per_10k;         /* 1..10000 */
+    uint32_t min_del_count;           /* >= 1 */
+    uint32_t min_del_per_strand;      /* K: filter = "strand" when min(del_fwd, del_rev) < K; 0: always PASS */
+} dut_del_options;
+
+/* The TSV (no device needed): comment lines ##contig= ##range=start-end ##min_depth= ##min_quality= ##min_base_quality=
+ * ("." when !has_min_base_quality) ##exclude_flags=0x%04x ##min_del_fraction=%.4f ##min_del_count= ##positions=
+ * ##low_depth= ##kept= ##deleted= ##events=, the header
+ *   #contig start end length ref del span freq max_del del_fwd del_rev filter
+ * and one line per event of dut_del_events: ref = the deleted reference bases (the candidates' ref bytes) when
+ * length <= 64, else "."; freq = del / span as %.4f.  ##deleted= is the scan's position count: marked lines stay. */
+int dut_del_write(const char *path, const char *contig, const cl_del_result *res, const dut_del_options *opt,
+                  char *err, size_t err_len);
+
+/* `find-deletions` on files, one GPU: reads as dut_find_minor_files does, always attaches the records' flags and pass
+ * bits and runs the filtered form of cl_site_scan_dels (with no mask and no threshold it counts what the unfiltered form
+ * does), writes the TSV.  Errors with a message: those of dut_find_variants_files, refused options. */
+int dut_find_deletions_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
+                             uint32_t end, const dut_del_options *opt, const char *output_path, int device_id,
+                             char *err, size_t err_len);
 
 #ifdef __cplusplus
 }
