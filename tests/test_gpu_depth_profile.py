@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import depth_contigs
 import depth_ref
 from bamio import write_bam, write_fasta
 from helpers import contig_inputs, load_kats, make_options, oracle_run
@@ -42,11 +43,13 @@ def same_profile(got, exp, what):
         assert got.win_raw is None and got.win_qc is None
 
 
-def check(contigs, opt_dict, tmp_path, n_bins=N_BINS, windows=None):
+def check(contigs, opt_dict, tmp_path, n_bins=N_BINS, windows=None, o_res=None):
     """every contig through the product path on one engine; while it is resident: the profile for every (n_bins, S)
-    against the oracle's depths and the engine's own dump, the invariants against the summary, and the run repeated."""
+    against the oracle's depths and the engine's own dump, the invariants against the summary, and the run repeated.
+    o_res: what oracle_run gave for these contigs and options, where a case has it already."""
     opt = _opts(opt_dict)
-    o_res, _ = oracle_run(contigs, make_options(opt_dict), str(tmp_path / "o.bed"), dump=True)
+    if o_res is None:
+        o_res, _ = oracle_run(contigs, make_options(opt_dict), str(tmp_path / "o.bed"), dump=True)
     with Engine(opt, 0) as eng:
         counter = CallableProfiler(str(tmp_path / "g.bed"))
         for name, tid, length, ref, rec in contigs:
@@ -109,6 +112,29 @@ def test_short_reads_2mb_30x(tmp_path):
     L = 2_000_000
     rec = synth.short_read_contig(L, 30, synth.seed_for(2, 20))
     check([("chr21", 20, L, synth.make_reference(L, synth.seed_for(2, 20)), rec)], dict(), tmp_path)
+
+
+def test_two_windows_per_workgroup(tmp_path):
+    """3078 windows on a grid of 2048: workgroups 0..1029 of k_depth_profile take windows w and w + 2048, with both in
+    their LDS histograms and register sums, and with another first window slot (kW) per trip"""
+    contig, o_res, extent, depths = depth_contigs.scan_steps()
+    T, B2 = depth_contigs.T, depth_contigs.SCAN_B[1]
+    assert extent == depth_contigs.SCAN_L and -(-extent // T) == 2048 + 1030
+    # from the reference alone: most of these workgroups see depth of both kinds in both of their windows, and other
+    # depths in the second than in the first
+    for kind in ("raw", "qc"):
+        first = depths[kind][:1030 * T].reshape(1030, T)
+        second = depth_ref.pad(depths[kind][B2:], 1030 * T).reshape(1030, T)
+        assert int((first.any(axis=1) & second.any(axis=1)).sum()) > 900, kind
+        assert int((first.sum(axis=1) != second.sum(axis=1)).sum()) > 900, kind
+    check([contig], {}, tmp_path, n_bins=(17, 1001), windows=(0, 16, 2049, 100_000), o_res=o_res)
+
+
+def test_windows_that_only_the_wide_list_covers(tmp_path):
+    contig, o_res, extent, depths = depth_contigs.wide_list()
+    assert extent == depth_contigs.WIDE_L
+    depth_contigs.assert_wide_only_windows(contig[4], depths)
+    check([contig], depth_contigs.WIDE_OPTIONS, tmp_path, o_res=o_res)
 
 
 def test_long_reads_indel_rich(tmp_path):

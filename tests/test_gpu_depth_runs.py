@@ -3,12 +3,15 @@ per-position raw_depth / qc_depth, and to the engine's own cl_debug_depths.  Eve
 import json
 import os
 import subprocess
+import time
 
 import numpy as np
 import pytest
 
+import depth_contigs
 import depth_ref
 import runs_ref
+import sparse_ref
 from bamio import write_bam, write_fasta
 from helpers import contig_inputs, load_kats, make_options, oracle_run
 from decodingustools_amd import (CallableOptions, CallableProfiler, ContigProfiler, Engine, EngineError, build as _b,
@@ -37,12 +40,14 @@ def same_runs(got, depth, edges, what):
     assert np.array_equal(got.value, v), (what, "value")
 
 
-def check(contigs, opt_dict, tmp_path, edge_sets=EDGE_SETS, expect=None):
+def check(contigs, opt_dict, tmp_path, edge_sets=EDGE_SETS, expect=None, o_res=None):
     """every contig through the product path on one engine; while it is resident: the runs of both kinds for every edge
     set against the oracle's depths and the engine's own dump, the invariants, the ties to the depth profile, a repeated
-    call, and the run repeated.  expect(name, kind, edges, runs): what a case wants to see beyond that."""
+    call, and the run repeated.  expect(name, kind, edges, runs): what a case wants to see beyond that.  o_res: what
+    oracle_run gave for these contigs and options, where a case has it already."""
     opt = _opts(opt_dict)
-    o_res, _ = oracle_run(contigs, make_options(opt_dict), str(tmp_path / "o.bed"), dump=True)
+    if o_res is None:
+        o_res, _ = oracle_run(contigs, make_options(opt_dict), str(tmp_path / "o.bed"), dump=True)
     with Engine(opt, 0) as eng:
         counter = CallableProfiler(str(tmp_path / "g.bed"))
         for name, tid, length, ref, rec in contigs:
@@ -179,6 +184,148 @@ def test_short_reads_2mb_30x(tmp_path):
     L = 2_000_000
     rec = synth.short_read_contig(L, 30, synth.seed_for(2, 20))
     check([("chr21", 20, L, synth.make_reference(L, synth.seed_for(2, 20)), rec)], dict(), tmp_path)
+
+
+SCAN_EDGE_SETS = (None, [1, 4, 100], E64)
+
+
+def _runs_around(start, value, B):
+    """the (start, value) of the runs that start inside the zone cleared around B -- behind its first position, where the
+    background's last run may end --, and the value at B"""
+    lo, hi = np.searchsorted(start, [B - depth_contigs.SCAN_CLEAR + 1, B + depth_contigs.SCAN_CLEAR])
+    at = int(value[np.searchsorted(start, B, side="right") - 1])
+    return [(int(s), int(v)) for s, v in zip(start[lo:hi], value[lo:hi])], at
+
+
+def _scan_boundaries_as_planted(start, value, edges, what):
+    B1, B2, B3 = depth_contigs.SCAN_B
+    # B_1, one read across: no start at it, the provisional start of window 1024 is dropped across the step
+    assert _runs_around(start, value, B1) == ([(B1 - 500, 1), (B1 + 500, 0)], 1), what
+    # B_2, nothing: depth 0 goes on
+    assert _runs_around(start, value, B2) == ([], 0), what
+    # B_3, 1 and 2 below it, 1 from it: a start of its own unless 1 and 2 share a band
+    if edges == [1, 4, 100]:
+        assert _runs_around(start, value, B3) == ([(B3 - 500, 1), (B3 + 500, 0)], 1), what
+    else:
+        assert _runs_around(start, value, B3) == ([(B3 - 500, 1), (B3 - 200, 2), (B3, 1), (B3 + 500, 0)], 1), what
+
+
+def test_scan_of_four_steps_with_runs_across_its_step_boundaries(tmp_path):
+    """3078 windows: k_depth_runs_scan takes four steps of 1024 windows.  Around the first positions of windows 1024, 2048
+    and 3072 the background is cleared and the three ways of a run to meet a step boundary are planted."""
+    contig, o_res, extent, depths = depth_contigs.scan_steps()
+    assert extent == depth_contigs.SCAN_L and -(-extent // depth_contigs.T) == 3078
+    # from the reference alone: every step's offset carry is non-zero and every later step has runs to place, and the
+    # boundaries are what the planted reads say
+    for kind in ("raw", "qc"):
+        for edges in SCAN_EDGE_SETS:
+            s, v = runs_ref.runs(depths[kind], edges)
+            n_from = [int((s >= B).sum()) for B in (0,) + depth_contigs.SCAN_B]
+            assert n_from[0] > n_from[1] > n_from[2] > n_from[3] > 10, (kind, edges, n_from)
+            _scan_boundaries_as_planted(s, v, edges, (kind, edges, "reference"))
+    seen = []
+
+    def expect(name, kind, edges, got):
+        seen.append(kind)
+        _scan_boundaries_as_planted(got.start, got.value, edges, (kind, edges))
+    check([contig], {}, tmp_path, edge_sets=SCAN_EDGE_SETS, expect=expect, o_res=o_res)
+    assert seen.count("raw") == seen.count("qc") == len(SCAN_EDGE_SETS)
+
+
+def test_contig_beyond_the_grid_of_65536_workgroups():
+    """65540 windows: workgroups 0..3 of k_depth_runs take a second window in both passes, the scan takes 65 steps, every
+    workgroup of k_depth_profile takes 32 or 33 windows.  134,223,877 positions are too many for the oracle and for
+    per-position arrays: a few thousand reads of one M each, against tests/sparse_ref.py.
+    Residents and kernels follow the 65540 window records, not the positions: on an MI355X the whole test takes 0.08 s
+    (begin to finish 0.02 s, the eight depth_runs and the six depth_profile calls under 0.01 s each lot); it prints the
+    stage times (-s)."""
+    T, B, L = depth_contigs.T, depth_contigs.BIG_B, depth_contigs.BIG_L
+    rec, raw, qc = depth_contigs.beyond_the_runs_grid()
+    reads = {"raw": raw, "qc": qc}
+    assert -(-L // T) == depth_contigs.RUNS_GRID + 4 and B % (1024 * T) == 0
+    # from the reference alone: a workgroup's two windows hold depth of both kinds, and not the same; the boundaries
+    per_window = sparse_ref.profile(raw, qc, L, 2, T)
+    for w in (1, 2, 3, depth_contigs.RUNS_GRID, depth_contigs.RUNS_GRID + 1, depth_contigs.RUNS_GRID + 2, depth_contigs.RUNS_GRID + 3):
+        assert per_window["win_raw"][w] > per_window["win_qc"][w], w
+    for kind in ("raw", "qc"):
+        win = per_window["win_" + kind]
+        for k in range(4):
+            assert win[k] > 0 and win[depth_contigs.RUNS_GRID + k] > 0 and win[k] != win[depth_contigs.RUNS_GRID + k], (kind, k)
+        for edges in (None, [1, 2]):
+            s, v = sparse_ref.runs(*reads[kind], L, edges)
+            at = dict(zip(s.tolist(), v.tolist()))
+            assert B not in at and B - 50 in at and at[B - 50] == 2            # 2 on both sides of B: no start
+            assert at[B + T - 100] == 2 and at[B + T] == 1                     # 2 below B + 2048, 1 from it: a start
+            assert int((s >= B).sum()) > 10
+    t = [time.perf_counter()]
+    opt = _opts({})
+    with Engine(opt, 0) as eng:
+        eng.contig_begin(7, L, None)
+        eng.push_reads(rec.pos, rec.mapq, rec.cigar_off, rec.cigar, rec.qual_off, rec.qual)
+        before = eng.contig_finish()
+        t.append(time.perf_counter())
+        summary = before.summary
+        assert int(summary.extent) == L
+        for kind in ("raw", "qc"):
+            for edges in (None, [1, 2]):
+                got = eng.depth_runs(kind, edges)
+                s, v = sparse_ref.runs(*reads[kind], L, edges)
+                assert got.extent == L and got.n_runs == len(s), (kind, edges, got.n_runs, len(s))
+                assert np.array_equal(got.start, s), (kind, edges, "start")
+                assert np.array_equal(got.value, v), (kind, edges, "value")
+                again = eng.depth_runs(kind, edges)
+                assert np.array_equal(again.start, got.start) and np.array_equal(again.value, got.value), (kind, edges)
+        t.append(time.perf_counter())
+        for nb, S in ((1001, 0), (17, 500), (4096, 100_000)):
+            got = eng.depth_profile(nb, S)
+            exp = sparse_ref.profile(raw, qc, L, nb, S)
+            what = (nb, S)
+            assert (got.n_bins, got.window, got.n_windows, got.extent) == (nb, S, exp["n_windows"], L), what
+            assert (got.sum_raw, got.sum_qc) == (exp["sum_raw"], exp["sum_qc"]), what
+            assert got.sum_raw != got.sum_qc
+            assert np.array_equal(got.hist_raw, exp["hist_raw"]) and np.array_equal(got.hist_qc, exp["hist_qc"]), what
+            if S:
+                assert np.array_equal(got.win_raw, exp["win_raw"]) and np.array_equal(got.win_qc, exp["win_qc"]), what
+            else:
+                assert got.win_raw is None and got.win_qc is None
+            assert got.sum_raw == summary.summed_coverage and got.sum_qc == summary.quality_bases, what
+            assert L - int(got.hist_raw[0]) == summary.n_covered_bases, what
+            assert int(got.hist_raw.sum()) == int(got.hist_qc.sum()) == L, what
+            again = eng.depth_profile(nb, S)
+            assert np.array_equal(again.hist_raw, got.hist_raw) and np.array_equal(again.hist_qc, got.hist_qc), what
+            assert (again.sum_raw, again.sum_qc) == (got.sum_raw, got.sum_qc), what
+            if S:
+                assert np.array_equal(again.win_raw, got.win_raw) and np.array_equal(again.win_qc, got.win_qc), what
+        t.append(time.perf_counter())
+        eng.contig_run()
+        after = eng.contig_collect()
+        assert after.as_dict() == before.as_dict()
+        assert np.array_equal(np.asarray(after.intervals), np.asarray(before.intervals))
+        t.append(time.perf_counter())
+    print("134,223,877 positions: begin to finish %.2f s, 8 depth_runs %.2f s, 6 depth_profile %.2f s, run again %.2f s"
+          % tuple(b - a for a, b in zip(t, t[1:])))
+
+
+def test_candidates_beyond_32767_in_a_window(tmp_path):
+    """k_depth_runs has its own copy of the window-depth rebuild: the difference words must hold these counts too"""
+    L = 5000
+    rng = np.random.default_rng(5)
+    reads = [(int(p), "30M", 60, 30, 0, f"r{i}") for i, p in enumerate(np.sort(rng.integers(100, 1900, 40_000)))]
+    check([("chrP", 0, L, synth.make_reference(L, 9), ContigRecords.from_reads(reads))], dict(max_depth=1_000_000), tmp_path)
+
+
+@pytest.mark.parametrize("head_span", ["37", "1000"])
+def test_spans_cut_into_several_heads(head_span, tmp_path, monkeypatch):
+    monkeypatch.setenv("DUT_HEAD_SPAN", head_span)
+    rec = synth.long_read_contig(60_000, 8, 17)
+    check([("chrL", 2, 60_000, synth.make_reference(60_000, 3), rec)], None, tmp_path)
+
+
+def test_windows_that_only_the_wide_list_covers(tmp_path):
+    contig, o_res, extent, depths = depth_contigs.wide_list()
+    assert extent == depth_contigs.WIDE_L
+    depth_contigs.assert_wide_only_windows(contig[4], depths)
+    check([contig], depth_contigs.WIDE_OPTIONS, tmp_path, o_res=o_res)
 
 
 def test_long_reads_indel_rich(tmp_path):
