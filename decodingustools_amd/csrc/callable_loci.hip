@@ -99,6 +99,8 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     uint64_t host_sum_cov = 0, host_sum_mapq = 0;
     uint64_t dev_sum_cov = 0, dev_sum_mapq = 0;   // of the resident contig
     uint32_t head_span = kHeadSpanMax;   // most positions one head of k_pileup_rows spans (DUT_HEAD_SPAN: a test hook)
+    bool heads8_only = false;            // DUT_HEADS8=1 (a test hook): every contig gets 8-byte heads
+    bool heads4 = false;                 // the resident contig's heads are the 4-byte form (pileup_rows.hip.h: HEAD4)
     uint64_t host_n_ops = 0;         // CIGAR operations pushed for it (pass-bit form: none is staged; for cl_contig_layout)
     uint64_t dev_sum_q = 0;          // of the resident contig (handed to the summary workgroup of every run)
     bool rec_counted = true;           // false: a tile of long-read shape skipped the count (cl_contig_upload makes up for it if the contig gets the short-read form after all)
@@ -115,7 +117,8 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     DevBuf<uint8_t> d_ref;
     DevBuf<uint32_t> d_end;
     DevBuf<ReadRec> d_rec;           // the records of the short-read form of k_pileup
-    DevBuf<uint2> d_heads;           // pass-bit form: the heads k_pileup_rows reads, {pos, span | low << 31}
+    DevBuf<uint2> d_heads;           // pass-bit form: the heads k_pileup_rows reads, {pos, span | low << 31} -- or, with
+                                     // heads4, 4-byte heads, two to an element
     DevBuf<uint32_t> d_refn;         // pass-bit form: bit p = the reference base at p is 'N' / 'n' or lies beyond the reference
     DevBuf<uint4> d_rows;            // pass-bit form: the windows' rows, groups of 4 rows x 64 blocks (1 KB each)
     uint64_t n_row_groups = 0;
@@ -983,7 +986,9 @@ template <bool DEBUG> void launch_rows(cl_ctx *c, const RowsArgs &a)
 {
     const uint32_t grid = a.n_win8 * 8u;
     if (grid == 0) return;
-#define CL_LAUNCH(DEEP_, NP_) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_>), dim3(grid), dim3(kRowsBlock), 0, c->stream, a)
+#define CL_LAUNCH(DEEP_, NP_) do { \
+        if (c->heads4) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, true>), dim3(grid), dim3(kRowsBlock), 0, c->stream, a); \
+        else hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, false>), dim3(grid), dim3(kRowsBlock), 0, c->stream, a); } while (0)
     // the counter planes by the deepest window's rows (4 per group): 8 planes count to 255
     if (c->max_groups <= 63u) { if (c->deep) CL_LAUNCH(true, 8); else CL_LAUNCH(false, 8); }
     else if (c->max_groups <= 16383u) { if (c->deep) CL_LAUNCH(true, 16); else CL_LAUNCH(false, 16); }
@@ -1053,6 +1058,7 @@ cl_status cl_create(const cl_options *opt, int device_id, void *stream, cl_ctx *
     { const char *qf = getenv("DUT_QUAL_FORM"); c->bits = !(qf && strcmp(qf, "bytes") == 0); }
     // DUT_HEAD_SPAN (a test hook): spans beyond this many positions are cut into several heads -- 2^31 - 1 in earnest, which
     // only a contig of more than 2 Gb can hold; the tests put the seams into ordinary reads
+    { const char *h8 = getenv("DUT_HEADS8"); c->heads8_only = h8 && *h8 == '1'; }   // (a test hook: both head forms on one input)
     { const char *hs = getenv("DUT_HEAD_SPAN"); if (hs) { const unsigned long long v = strtoull(hs, nullptr, 0); if (v >= 1 && v <= kHeadSpanMax) c->head_span = (uint32_t)v; } }
     if (hipSetDevice(device_id) != hipSuccess) { delete c; return CL_ERR_DEVICE; }
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
@@ -1188,7 +1194,9 @@ static void start_prealloc(cl_ctx *c, uint64_t n_reads, uint64_t n_qual)
     const uint32_t contig_len = c->contig_len;
     // (one window more than the contig's length gives: the extent may turn out larger than the length)
     const size_t n_win = ((size_t)contig_len + kT - 1) / kT + 1;
-    const size_t n_heads = n_reads ? (size_t)n_reads + 1 : 0;
+    // (heads: 4 bytes each where the reads are short -- a contig of long reads has spans beyond kWideSpan and keeps 8)
+    const bool guess4 = !c->heads8_only && n_qual / std::max<uint64_t>(n_reads, 1) < kWideSpan / 8;
+    const size_t n_heads = n_reads ? (guess4 ? ((size_t)n_reads + 2) / 2 : (size_t)n_reads + 1) : 0;
     const size_t n_rows = n_qual ? row_groups_estimate(n_qual, n_win) * (dut::kRowGroupWords / 4) : 0;
     // nothing to do for a context whose buffers hold this contig already (the usual case from its second contig on):
     // no thread is made for that
@@ -1751,21 +1759,33 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     if (form == 3) {
         // the heads (pileup_rows.hip.h): 8 bytes per read the pileup holds -- [pos, pos + span) and whether its mapq counts
         // as low (mod.rs:22-28) --, built straight into the pinned buffers; a span beyond kHeadSpanMax is cut into
-        // several heads (h_rec_cnt, counted by cl_push_reads' walk)
+        // several heads (h_rec_cnt, counted by cl_push_reads' walk).  4 bytes per head where every head fits them: no
+        // wide read (every span <= kWideSpan: 15 bits hold it) and no span cut (span_n is the longest of those spans), so
+        // that a read has at most one head and every window reads it as an ordinary candidate.
         if ((rs = build_rec_index(c)) != CL_OK) return rs;
         tmr.lap("upload: record index");
         const uint32_t n_rec = c->n_rec;
-        HIP_TRY(c, c->d_heads.reserve((size_t)n_rec + 1));
+        c->heads4 = !c->heads8_only && c->n_wide == 0 && c->span_n <= c->head_span && c->span_n <= kWideSpan;
+        const size_t head_bytes = c->heads4 ? sizeof(uint32_t) : sizeof(uint2);
+        HIP_TRY(c, c->d_heads.reserve((((size_t)n_rec + 1) * head_bytes + sizeof(uint2) - 1) / sizeof(uint2)));
         const int32_t *hp = c->hs.pos.data(); const uint8_t *hm = c->hs.mapq.data(); const uint32_t *he = c->hs.end.data();
         const uint32_t *ro = c->hs.rec_of.data();
         const uint32_t max_low = c->opt.max_low_mapq, hs = c->head_span;
-        rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_heads.p), ((uint64_t)n_rec + 1) * sizeof(uint2),
-                        rec_range_fill<uint2>(ro, n, n_rec, [hp, hm, he, ro, max_low, hs](size_t i, auto &&put) {
-            const uint32_t low = (uint32_t)hm[i] <= max_low ? 0x80000000u : 0u, cnt = ro[i + 1] - ro[i];
-            uint64_t x = (uint32_t)hp[i];
-            const uint64_t e = he[i];
-            for (uint32_t k = 0; k < cnt; ++k, x += hs) put(k, make_uint2((uint32_t)x, (uint32_t)std::min<uint64_t>(hs, e - x) | low));
-        }), rec_chunk_bytes());
+        if (c->heads4) {
+            rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_heads.p), ((uint64_t)n_rec + 1) * sizeof(uint32_t),
+                            rec_range_fill<uint32_t>(ro, n, n_rec, [hp, hm, he, ro, max_low](size_t i, auto &&put) {
+                const uint32_t low = (uint32_t)hm[i] <= max_low ? 0x80000000u : 0u, x = (uint32_t)hp[i];
+                if (ro[i + 1] != ro[i]) put(0u, (x & 0xFFFFu) | ((he[i] - x) << 16) | low);
+            }), rec_chunk_bytes());
+        } else {
+            rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_heads.p), ((uint64_t)n_rec + 1) * sizeof(uint2),
+                            rec_range_fill<uint2>(ro, n, n_rec, [hp, hm, he, ro, max_low, hs](size_t i, auto &&put) {
+                const uint32_t low = (uint32_t)hm[i] <= max_low ? 0x80000000u : 0u, cnt = ro[i + 1] - ro[i];
+                uint64_t x = (uint32_t)hp[i];
+                const uint64_t e = he[i];
+                for (uint32_t k = 0; k < cnt; ++k, x += hs) put(k, make_uint2((uint32_t)x, (uint32_t)std::min<uint64_t>(hs, e - x) | low));
+            }), rec_chunk_bytes());
+        }
         if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
         if (rs != CL_OK) return rs;
         tmr.lap("upload: heads built + sent");
@@ -2107,11 +2127,11 @@ cl_status cl_contig_bytes(cl_ctx *c, uint64_t *input_bytes, uint64_t *output_byt
     // addresses, nothing it does not (no CIGAR word: none is resident in any form), and what it must write: the intervals
     // (12 bytes each; the per-position counters and states never reach HBM).
     //   every form   reference bytes (extent; pass bits: one bit per position) + one 32-byte window record per window
-    //   pass bits    the rows (1 KB per group of 4 rows) + an 8-byte head per read with a span + the wide list
+    //   pass bits    the rows (1 KB per group of 4 rows) + a head per read with a span, 8 bytes or 4 + the wide list
     //   bytes, 0     the quality bytes + the 16-byte records (heads and pieces) + the wide list
     //   bytes, 2     the quality bytes + 8 bytes per piece of the run table + pos 4, end 4, mapq 1 per read + the wide list
     uint64_t in = (c->form == 3 ? ((uint64_t)c->extent + 7) / 8 : (uint64_t)c->extent) + (uint64_t)c->n_win * sizeof(WinMeta);
-    if (c->form == 3) in += c->n_row_groups * (uint64_t)(dut::kRowGroupWords * sizeof(uint32_t)) + (uint64_t)c->n_rec * sizeof(uint2) + (uint64_t)c->n_wide * 4;
+    if (c->form == 3) in += c->n_row_groups * (uint64_t)(dut::kRowGroupWords * sizeof(uint32_t)) + (uint64_t)c->n_rec * (c->heads4 ? sizeof(uint32_t) : sizeof(uint2)) + (uint64_t)c->n_wide * 4;
     else if (c->form == 0) in += c->n_qual + (uint64_t)c->n_rec * sizeof(ReadRec) + (uint64_t)c->n_wide * 4;
     else in += c->n_qual + c->n_runtab * 8 + (uint64_t)c->n_reads * 9 + (uint64_t)c->n_wide * 4;
     if (input_bytes) *input_bytes = in;
@@ -2141,7 +2161,7 @@ cl_status cl_contig_layout(cl_ctx *c, cl_layout_info *out)
     // what cl_contig_upload sent over the link for this contig (every transfer goes through the pinned staging ring)
     const uint64_t padded = (uint64_t)c->n_win * kT + 16;
     uint64_t h = (c->form == 3 ? ((uint64_t)c->n_win * kT) / 8 : padded) + (uint64_t)c->n_win * sizeof(WinMeta) + (uint64_t)c->n_wide * 4;
-    if (c->form == 3) h += c->n_row_groups * (uint64_t)(dut::kRowGroupWords * sizeof(uint32_t)) + ((uint64_t)c->n_rec + 1) * sizeof(uint2);
+    if (c->form == 3) h += c->n_row_groups * (uint64_t)(dut::kRowGroupWords * sizeof(uint32_t)) + ((uint64_t)c->n_rec + 1) * (c->heads4 ? sizeof(uint32_t) : sizeof(uint2));
     else if (c->form == 0) h += c->n_qual + ((uint64_t)c->n_rec + 1) * sizeof(ReadRec);
     else h += c->n_qual + c->n_runtab * 8 + (uint64_t)c->n_reads * 9;
     out->upload_h2d_bytes = h;
@@ -2204,9 +2224,13 @@ cl_status cl_contig_depth_profile(cl_ctx *c, uint32_t n_bins, uint32_t window, c
             // workgroups that stay: a histogram is flushed once per workgroup
             const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
             if (c->profiling) HIP_TRY(c, c->t_prof.start(c->stream));
-            if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_profile<8>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
-            else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_profile<16>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
-            else hipLaunchKernelGGL((k_depth_profile<32>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
+#define CL_LAUNCH(NP_) do { \
+            if (c->heads4) hipLaunchKernelGGL((k_depth_profile<NP_, true>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a); \
+            else hipLaunchKernelGGL((k_depth_profile<NP_, false>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a); } while (0)
+            if (c->max_groups <= 63u) CL_LAUNCH(8);
+            else if (c->max_groups <= 16383u) CL_LAUNCH(16);
+            else CL_LAUNCH(32);
+#undef CL_LAUNCH
             HIP_TRY(c, hipGetLastError());
             if (c->profiling) HIP_TRY(c, c->t_prof.stop(c->stream));
             HIP_TRY(c, hipMemcpyAsync(c->h_prof.data(), c->d_prof.p, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -2269,10 +2293,12 @@ cl_status cl_contig_depth_runs(cl_ctx *c, uint32_t kind, const uint32_t *edges, 
             a.off = c->d_dr_off.p;
             const uint32_t grid = std::min<uint32_t>(c->n_win, 65536u);
             auto launch = [&]() {
-                if (kind == CL_DEPTH_RAW) hipLaunchKernelGGL((k_depth_runs<8, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_runs<8, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_runs<16, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else hipLaunchKernelGGL((k_depth_runs<32, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                // (only the raw depths come from the heads: the qc depths are the rows' column sums)
+                if (kind == CL_DEPTH_RAW && c->heads4) hipLaunchKernelGGL((k_depth_runs<8, false, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else if (kind == CL_DEPTH_RAW) hipLaunchKernelGGL((k_depth_runs<8, false, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_runs<8, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_runs<16, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else hipLaunchKernelGGL((k_depth_runs<32, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
             };
             // ---- count, scan: how many runs there are ----
             HIP_TRY(c, hipMemsetAsync(a.err, 0, sizeof(uint32_t), c->stream));

@@ -27,7 +27,7 @@ constexpr int kDepthWinSlots = 2048 / 16 + 2;
 
 struct DepthArgs {
     const WinMeta  *win;
-    const uint2    *heads;
+    const void     *heads;            // 8 bytes each, or 4 with HEAD4 (pileup_rows.hip.h)
     const uint32_t *wide_idx;
     const uint4    *rows;
     uint32_t extent, n_win;
@@ -38,7 +38,7 @@ struct DepthArgs {
     unsigned long long *sums;          // [2]: raw, qc
 };
 
-template <int NP>
+template <int NP, bool HEAD4>
 __global__ __launch_bounds__(kDepthBlock) void k_depth_profile(DepthArgs a)
 {
     constexpr int T = 2048, BS = kDepthBlock, PER = T / BS;
@@ -81,13 +81,10 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_profile(DepthArgs a)
         for (uint32_t v = tid; v < n_cand; v += BS) {
             uint32_t r = lo + (v - wn);
             if (v < wn) r = a.wide_idx[wlo + v];
-            const uint2 h = a.heads[r];
-            const uint32_t x = h.x, span = h.y & kHeadSpanMax;
-            const uint32_t e = x + span;
-            if (span && e > W && x < W + (uint32_t)T) {
-                const uint32_t cb = x > W ? x - W : 0u, ce = e - W;
-                atomicAdd(&s_diff[cb], 1u);
-                if (ce < (uint32_t)T) atomicAdd(&s_diff[ce], 0xFFFFFFFFu);
+            const HeadCand hc = head_cand<T>(head_at<HEAD4>(a.heads, r), W);
+            if (hc.hit) {
+                atomicAdd(&s_diff[hc.cb], 1u);
+                if (hc.ce < (uint32_t)T) atomicAdd(&s_diff[hc.ce], 0xFFFFFFFFu);
             }
         }
         if (wv != 0) {

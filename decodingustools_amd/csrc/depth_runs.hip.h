@@ -29,7 +29,7 @@ constexpr int kRunsScanBlock = 1024;
 
 struct RunsArgs {
     const WinMeta  *win;
-    const uint2    *heads;
+    const void     *heads;            // 8 bytes each, or 4 with HEAD4 (pileup_rows.hip.h)
     const uint32_t *wide_idx;
     const uint4    *rows;
     uint32_t extent, n_win;
@@ -42,7 +42,7 @@ struct RunsArgs {
     uint32_t edges[kRunsMaxEdges];
 };
 
-template <int NP, bool QC>
+template <int NP, bool QC, bool HEAD4>
 __global__ __launch_bounds__(kDepthBlock) void k_depth_runs(RunsArgs a)
 {
     constexpr int T = 2048, BS = kDepthBlock, PER = T / BS;
@@ -85,13 +85,10 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_runs(RunsArgs a)
             for (uint32_t v = tid; v < n_cand; v += BS) {
                 uint32_t r = lo + (v - wn);
                 if (v < wn) r = a.wide_idx[wlo + v];
-                const uint2 h = a.heads[r];
-                const uint32_t x = h.x, span = h.y & kHeadSpanMax;
-                const uint32_t e = x + span;
-                if (span && e > W && x < W + (uint32_t)T) {
-                    const uint32_t cb = x > W ? x - W : 0u, ce = e - W;
-                    atomicAdd(&s_diff[cb], 1u);
-                    if (ce < (uint32_t)T) atomicAdd(&s_diff[ce], 0xFFFFFFFFu);
+                const HeadCand hc = head_cand<T>(head_at<HEAD4>(a.heads, r), W);
+                if (hc.hit) {
+                    atomicAdd(&s_diff[hc.cb], 1u);
+                    if (hc.ce < (uint32_t)T) atomicAdd(&s_diff[hc.ce], 0xFFFFFFFFu);
                 }
             }
             __syncthreads();

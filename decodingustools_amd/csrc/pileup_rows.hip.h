@@ -6,13 +6,40 @@
 
 namespace clk {
 
-// k_pileup_rows reads HEADS, 8 bytes each: {pos, span | low << 31} -- the read as the pileup holds
+// k_pileup_rows reads HEADS, in their general form 8 bytes each: {pos, span | low << 31} -- the read as the pileup holds
 // it, [pos, pos + span) (span = bam_cigar2rlen: D and N included; mod.rs:22-28), and whether its mapq is at or below
 // max_low_mapq (mod.rs:26-28).  Nothing else of a read is needed there: its M/=/X bases are in the rows, and its shares of
 // summed_coverage and summed_mapq (contig_profiler.rs:74, 79-82: per-read separable) are added up by
 // cl_push_reads' walk on the host.  A span of more than kHeadSpanMax positions is cut into several heads (the +-1
 // scatter of [a, b) and [b, c) is that of [a, c)); a read without a reference span has none.
 constexpr uint32_t kHeadSpanMax = 0x7FFFFFFFu;
+//
+// HEAD4, the 4-byte form of the same: pos & 0xFFFF | span << 16 | low << 31 -- for a contig in which every span fits 15
+// bits and none was cut (callable_loci.hip: no wide read, that is no span beyond kWideSpan = 16 384, and no head span
+// below a read's).  A window W reads only its ordinary candidates, W - 16 384 < pos < W + T, so 16 bits of the position
+// say where it lies: pos - W = (int16)(pos16 - W16), in (-16 384, 2 048).  The same head serves every window that reads
+// it.  One wide read anywhere keeps the whole contig on 8-byte heads.
+template <bool HEAD4> struct HeadOf { typedef uint2 type; };
+template <> struct HeadOf<true> { typedef uint32_t type; };
+template <bool HEAD4> __device__ __forceinline__ typename HeadOf<HEAD4>::type head_at(const void *heads, uint32_t r)
+{
+    return reinterpret_cast<const typename HeadOf<HEAD4>::type *>(heads)[r];
+}
+// What the kernels that scatter a window's candidates need of a head (k_pileup_rows, k_depth_profile, k_depth_runs): the
+// span clipped to the window [W, W + T) as [cb, ce) -- ce may be T or beyond: nothing ends inside the window then --,
+// whether the read's mapq counts as low, and whether the head touches the window at all (a zeroed head, a head of a cut
+// span that lies elsewhere, a read that ends in front of the window: hit = false and nothing else is to be used).
+struct HeadCand { uint32_t cb, ce, low; bool hit; };
+template <int T> __device__ __forceinline__ HeadCand head_cand(const uint2 h, uint32_t W)
+{
+    const uint32_t x = h.x, span = h.y & kHeadSpanMax, e = x + span;
+    return HeadCand{x > W ? x - W : 0u, e - W, h.y >> 31, span && e > W && x < W + (uint32_t)T};
+}
+template <int T> __device__ __forceinline__ HeadCand head_cand(const uint32_t h, uint32_t W)
+{
+    const int32_t span = (int32_t)((h >> 16) & 0x7FFFu), dx = (int32_t)(int16_t)(uint16_t)(h - W), e = dx + span;
+    return HeadCand{(uint32_t)(dx > 0 ? dx : 0), (uint32_t)e, h >> 31, span && e > 0 && dx < T};
+}
 
 // ---------------------------------------------------------------------------------------------
 // k_pileup_rows: the pass-bit form of the pileup (the default; DUT_QUAL_FORM=bytes selects the byte forms, k_pileup).
@@ -29,7 +56,7 @@ constexpr uint32_t kHeadSpanMax = 0x7FFFFFFFu;
 // quality_bases is the number of set bits (contig_profiler.rs:71: taken from the planes, sum of 2^p x popcount);
 // summed_baseq comes with the bits from the host's walk (contig_profiler.rs:70, per-read separable: SURVEY 8a-7).
 //
-// The window's candidates are heads (8 bytes, one per read with a reference span; above): the +-1 scatter of raw_depth
+// The window's candidates are heads (8 or 4 bytes, one per read with a reference span; above): the +-1 scatter of raw_depth
 // and low_mapq_count (mod.rs:22-28) into difference arrays in LDS, nothing else -- the reads' other separable sums
 // (summed_coverage, summed_mapq) come from the host's walk too.
 //
@@ -77,7 +104,7 @@ __device__ __forceinline__ uint32_t bs_less_than(const uint32_t (&c)[NP], unsign
 // kernel) and every argument that is read takes one or two of them.
 struct RowsArgs {
     const uint4    *rows;         // per window, groups of 4 rows x 64 blocks (host, at upload)
-    const uint2    *heads;        // {pos, span | low << 31} per read with a reference span
+    const void     *heads;        // per read with a reference span: 8 bytes, or 4 in an instantiation with HEAD4 (above)
     const uint32_t *wide_idx;     // read indices of the wide reads, ascending
     const WinMeta  *win;
     const uint32_t *refn;         // bit p = the reference base at p is 'N' / 'n' (or beyond the reference)
@@ -108,7 +135,7 @@ constexpr int rows_min_waves(bool DEBUG, bool DEEP, int NP)
     if (DEBUG) return (DEEP || NP > 8) ? 3 : 6;
     return (DEEP || NP > 16) ? 3 : (NP > 8 ? 7 : 8);
 }
-template <int T, bool DEBUG, bool DEEP, int NP>
+template <int T, bool DEBUG, bool DEEP, int NP, bool HEAD4>
 __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k_pileup_rows(RowsArgs a)
 {
     constexpr int kBlock = kRowsBlock;                     // (shadows the namespace's 256 inside this kernel)
@@ -171,20 +198,21 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
             rv[j] = rows[(size_t)(g < ng ? g : ng - 1u) * 64u + lane];
         }
     }
-    // ... and the window's first candidates: heads ({pos, span | low << 31}, above), U per lane and trip
+    // ... and the window's first candidates: heads (above), U per lane and trip
     constexpr int U = 4;
-    auto load_heads = [&](uint32_t base, uint2 (&hh)[U]) {
+    typedef typename HeadOf<HEAD4>::type Head;
+    auto load_heads = [&](uint32_t base, Head (&hh)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t v = base + (uint32_t)u * kBlock + tid;
             uint32_t r = lo + (v - wn);
             if (v < wn) r = a.wide_idx[wlo + v];
             __builtin_assume(r < (1u << 29));
-            hh[u] = make_uint2(0u, 0u);
-            if (v < n_cand) hh[u] = a.heads[r];
+            hh[u] = Head();
+            if (v < n_cand) hh[u] = head_at<HEAD4>(a.heads, r);
         }
     };
-    uint2 hh[U];
+    Head hh[U];
     load_heads(0u, hh);
     // ... and wave 0's word of the byte thresholds, which it puts into LDS once it is done with the planes there
     uint32_t wlut = 0u;
@@ -228,11 +256,10 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
     for (uint32_t base = 0;;) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const uint32_t x = hh[u].x, span = hh[u].y & kHeadSpanMax;
-            const uint32_t e = x + span;
-            // (a head of a cut span may lie past the window; span = 0: no candidate in this slot)
-            if (span && e > W && x < W + (uint32_t)T) {
-                const uint32_t cb = x > W ? x - W : 0u, ce = e - W;
+            const HeadCand hc = head_cand<T>(hh[u], W);
+            // (a head of a cut span may lie past the window; a zeroed head: no candidate in this slot)
+            if (hc.hit) {
+                const uint32_t cb = hc.cb, ce = hc.ce;
                 uint32_t ib, vb, ie, ve2;
                 if (DEEP) { ib = cb; vb = 1u; ie = ce; ve2 = 0xFFFFFFFFu; }
                 else {
@@ -241,7 +268,7 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
                 }
                 atomicAdd(&s_raw[ib], vb);
                 if (ce < (uint32_t)T) atomicAdd(&s_raw[ie], ve2);
-                if (hh[u].y >> 31) {
+                if (hc.low) {
                     atomicAdd(&s_low[ib], vb);
                     if (ce < (uint32_t)T) atomicAdd(&s_low[ie], ve2);
                 }
