@@ -81,6 +81,11 @@ def _site_quals(rec: ContigRecords):
     return q
 
 
+def _filter_ref(filter):
+    """filter=(exclude_flags, use_base_quality) of a scan mode as the cl_scan_filter argument; None: the unfiltered form."""
+    return None if filter is None else C.byref(_lib.cl_scan_filter(int(filter[0]), 1 if filter[1] else 0, 0))
+
+
 def site_pass_bits(rec: ContigRecords, min_base_quality) -> np.ndarray:
     """cl_debug_site_pass_bits (host only): the attachment's pass bits as uint64 words, bit i of word w <-> base 64 w + i
     in the numbering of rec.seq_off."""
@@ -256,30 +261,29 @@ class Engine:
         self._check(self._lib.cl_site_pileup_stats(self._h, C.byref(ms), C.byref(b)))
         return ms.value, b.value
 
-    def _site_scan(self, min_quality, min_depth, ref, start, end, filt):
-        """cl_site_scan (filt is None) or cl_site_scan_ex (filt: a cl_scan_filter) and the result as a ScanResult."""
+    def _site_scan_mode(self, fn, head, ref, start, end, result_type, dtype, n_field):
+        """A compacting scan of the resident tile: fn(ctx, *head, ref, ref_len, start, end, out) -- head: what the entry point
+        takes in front of the reference.  (the C result, its n_field candidates as a structured array of dtype, a copy)."""
         ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
         if end is None:
             end = ref.shape[0]
-        if filt is None:
-            r, dtype = _lib.cl_scan_result(), SCAN_CANDIDATE
-            st = self._lib.cl_site_scan(self._h, int(min_quality), int(min_depth), _ptr(ref), ref.shape[0], int(start), int(end), C.byref(r))
-        else:
-            r, dtype = _lib.cl_scan_result_ex(), SCAN_CANDIDATE_EX
-            st = self._lib.cl_site_scan_ex(self._h, int(min_quality), int(min_depth), C.byref(filt), _ptr(ref), ref.shape[0], int(start),
-                                           int(end), C.byref(r))
-        self._check(st)
-        n = int(r.n_variant)
+        r = result_type()
+        self._check(fn(self._h, *head, _ptr(ref), ref.shape[0], int(start), int(end), C.byref(r)))
+        n = int(getattr(r, n_field))
         cand = np.zeros(n, dtype)
         if n:
             C.memmove(cand.ctypes.data, r.candidates, n * dtype.itemsize)
+        return r, cand
+
+    def _site_scan(self, fn, head, ref, start, end, result_type, dtype):
+        r, cand = self._site_scan_mode(fn, head, ref, start, end, result_type, dtype, "n_variant")
         return ScanResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), mixed=int(r.n_mixed),
-                          uncomparable=int(r.n_uncomparable), match=int(r.n_match), variant=n, candidates=cand)
+                          uncomparable=int(r.n_uncomparable), match=int(r.n_match), variant=cand.shape[0], candidates=cand)
 
     def site_scan(self, min_quality, min_depth, ref, start=0, end=None):
         """cl_site_scan over [start, end) of the resident tile (end=None: the length of `ref`, which must be the ref_len
         given to site_upload): a ScanResult with the five class counts and the candidates as a structured array."""
-        return self._site_scan(min_quality, min_depth, ref, start, end, None)
+        return self._site_scan(self._lib.cl_site_scan, (int(min_quality), int(min_depth)), ref, start, end, _lib.cl_scan_result, SCAN_CANDIDATE)
 
     def site_scan_counts(self, min_quality, start, end):
         """cl_site_scan_counts: (end - start, 5) uint32 -- A, C, G, T, depth -- for at most CL_SCAN_MAX_DENSE positions."""
@@ -296,8 +300,9 @@ class Engine:
     def site_scan_ex(self, min_quality, min_depth, ref, exclude_flags=0, use_base_quality=False, start=0, end=None):
         """cl_site_scan_ex: site_scan under a flag mask and (use_base_quality) the attachment's pass bits; the candidates
         (SCAN_CANDIDATE_EX) also carry alt_fwd, alt_rev, ref_fwd, ref_rev."""
-        return self._site_scan(min_quality, min_depth, ref, start, end,
-                               _lib.cl_scan_filter(int(exclude_flags), 1 if use_base_quality else 0, 0))
+        filt = _lib.cl_scan_filter(int(exclude_flags), 1 if use_base_quality else 0, 0)
+        return self._site_scan(self._lib.cl_site_scan_ex, (int(min_quality), int(min_depth), C.byref(filt)), ref, start, end, _lib.cl_scan_result_ex,
+                               SCAN_CANDIDATE_EX)
 
     def site_scan_counts_ex(self, min_quality, start, end, exclude_flags=0, use_base_quality=False):
         """cl_site_scan_counts_ex: (end - start, 9) uint32 -- A+ A- C+ C- G+ G- T+ T- depth (+ forward, - reverse)."""
@@ -310,38 +315,20 @@ class Engine:
         """cl_site_scan_minor over [start, end) of the resident tile: positions where a second base of A C G T stands beside
         the most frequent one.  filter: None for the unfiltered form, else (exclude_flags, use_base_quality) of the
         attachment.  A MinorResult: the three class counts, the candidates (MINOR_CANDIDATE) and the kernel's milliseconds."""
-        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
-        if end is None:
-            end = ref.shape[0]
-        flt = None if filter is None else C.byref(_lib.cl_scan_filter(int(filter[0]), 1 if filter[1] else 0, 0))
         prm = _lib.cl_minor_params(int(min_depth), int(min_minor_count), int(min_minor_per_10k))
-        r = _lib.cl_minor_result()
-        self._check(self._lib.cl_site_scan_minor(self._h, int(min_quality), flt, C.byref(prm), _ptr(ref), ref.shape[0], int(start), int(end),
-                                                 C.byref(r)))
-        n = int(r.n_minor)
-        cand = np.zeros(n, MINOR_CANDIDATE)
-        if n:
-            C.memmove(cand.ctypes.data, r.candidates, n * MINOR_CANDIDATE.itemsize)
-        return MinorResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), single=int(r.n_single), minor=n,
+        r, cand = self._site_scan_mode(self._lib.cl_site_scan_minor, (int(min_quality), _filter_ref(filter), C.byref(prm)), ref, start, end,
+                                       _lib.cl_minor_result, MINOR_CANDIDATE, "n_minor")
+        return MinorResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), single=int(r.n_single), minor=cand.shape[0],
                            candidates=cand, kernel_ms=self.site_scan_stats()[0])
 
     def site_scan_dels(self, min_quality, min_depth, min_del_count, min_del_per_10k, ref, start=0, end=None, filter=None):
         """cl_site_scan_dels over [start, end) of the resident tile: positions that the reads delete (a D operation over
         them), beside the scan's depth.  filter: None for the unfiltered form, else (exclude_flags, use_base_quality) of the
         attachment.  A DelResult: the three class counts, the candidates (DEL_CANDIDATE) and the kernel's milliseconds."""
-        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
-        if end is None:
-            end = ref.shape[0]
-        flt = None if filter is None else C.byref(_lib.cl_scan_filter(int(filter[0]), 1 if filter[1] else 0, 0))
         prm = _lib.cl_del_params(int(min_depth), int(min_del_count), int(min_del_per_10k))
-        r = _lib.cl_del_result()
-        self._check(self._lib.cl_site_scan_dels(self._h, int(min_quality), flt, C.byref(prm), _ptr(ref), ref.shape[0], int(start), int(end),
-                                                C.byref(r)))
-        n = int(r.n_deleted)
-        cand = np.zeros(n, DEL_CANDIDATE)
-        if n:
-            C.memmove(cand.ctypes.data, r.candidates, n * DEL_CANDIDATE.itemsize)
-        return DelResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), kept=int(r.n_kept), deleted=n,
+        r, cand = self._site_scan_mode(self._lib.cl_site_scan_dels, (int(min_quality), _filter_ref(filter), C.byref(prm)), ref, start, end,
+                                       _lib.cl_del_result, DEL_CANDIDATE, "n_deleted")
+        return DelResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), kept=int(r.n_kept), deleted=cand.shape[0],
                          candidates=cand, kernel_ms=self.site_scan_stats()[0])
 
     def site_scan_stats(self):

@@ -233,25 +233,31 @@ static bool cli_count32(const char *flag, const std::string &v, uint32_t &dst)
     return true;
 }
 
-// find-variants: every position of a contig (or of --region, 0-based half open) where the sample's called base differs
-// from the reference, by the counting and the call of find-y-branch (defaults as there, src/cli.rs:62-105); with --tree,
-// which of them the haplogroup tree knows.  Argument errors leave with 2 before a device is opened.
-static int find_variants_main(int argc, char **argv)
-{
-    std::string bam, ref, out, tree, contig;
+// What the scan subcommands (find-variants, find-minor-alleles, find-deletions) share on the command line: the BAM, -r, -o,
+// -L, --region (0-based, half open), --min-depth, --min-quality, the two filter flags, --device, -h.
+struct ScanCli {
+    const char *name;
+    void (*usage)();
+    std::string bam, ref, out, contig;
     unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
-    int provider = DUT_PROVIDER_FTDNA, tree_type = DUT_TREE_YDNA, device = 0;
-    bool has_provider = false, has_tree_type = false, has_region = false;
-    dut_variants_options vopt = {0, 0, 0, 0, 0};
-    auto usage_fv = []() {
-        fprintf(stderr, "Usage: dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
-                        "       [--min-depth 10] [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
-                        "       [--min-base-quality Q] [--exclude-flags MASK] [--min-alt-per-strand K]\n"
-                        "  --region: 0-based, half open, within the contig.  SNVs only.  Without the last three flags every fetched\n"
-                        "  record counts (no flag or base-quality filter), as in find-y-branch.  With any of them: bases below Q\n"
-                        "  (0..255) and reads with a flag bit of MASK (decimal or 0x hex, 0..65535) do not count, the TSV gains\n"
-                        "  alt_fwd alt_rev ref_fwd ref_rev filter, and filter is 'strand' when min(alt_fwd, alt_rev) < K.\n");
-    };
+    int device = 0;
+    bool has_region = false, filter_flag = false;            // (a filter flag was given, whatever its value)
+    uint8_t min_base_quality = 0;
+    int has_min_base_quality = 0;
+    uint16_t exclude_flags = 0;
+    // the two filter fields into a command's options (dut_variants_options, dut_minor_options, dut_del_options)
+    template <class Options> void filter_into(Options &o) const
+    {
+        o.has_min_base_quality = has_min_base_quality; o.min_base_quality = min_base_quality; o.exclude_flags = exclude_flags;
+    }
+};
+
+// The argument loop of a scan subcommand.  own(a, next) takes the command's own flags: 1 taken, 0 not one of them, -1 a
+// malformed value (its message printed).  Returns -1 to go on, else the exit status: argument errors leave with 2 before a
+// device is opened.
+template <class Own>
+static int scan_cli_parse(int argc, char **argv, ScanCli &c, Own &&own)
+{
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i], val;
         const size_t eq = a.find('=');
@@ -259,182 +265,167 @@ static int find_variants_main(int argc, char **argv)
         if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
         auto next = [&]() -> const char * {
             if (has_eq) return val.c_str();
-            if (i + 1 >= argc) { usage_fv(); exit(2); }
+            if (i + 1 >= argc) { c.usage(); exit(2); }
             return argv[++i];
         };
-        if (a == "-r" || a == "--reference") ref = next();
-        else if (a == "-o" || a == "--output") out = next();
-        else if (a == "-L" || a == "--contig") contig = next();
-        else if (a == "--tree") tree = next();
-        else if (a == "--region") { if (!cli_region(next(), start, end)) return 2; has_region = true; }
-        else if (a == "--min-depth") { if (!cli_min_depth(next(), min_depth)) return 2; }
-        else if (a == "--min-quality") { if (!cli_min_quality(next(), min_quality)) return 2; }
-        else if (a == "--min-base-quality") { if (!cli_base_quality(next(), vopt.min_base_quality)) return 2; vopt.filtered = 1; vopt.has_min_base_quality = 1; }
-        else if (a == "--exclude-flags") { if (!cli_flag_mask(next(), vopt.exclude_flags)) return 2; vopt.filtered = 1; }
-        else if (a == "--min-alt-per-strand") { if (!cli_count32("--min-alt-per-strand", next(), vopt.min_alt_per_strand)) return 2; vopt.filtered = 1; }
+        int mine = 0;
+        if (a == "-r" || a == "--reference") c.ref = next();
+        else if (a == "-o" || a == "--output") c.out = next();
+        else if (a == "-L" || a == "--contig") c.contig = next();
+        else if (a == "--region") { if (!cli_region(next(), c.start, c.end)) return 2; c.has_region = true; }
+        else if (a == "--min-depth") { if (!cli_min_depth(next(), c.min_depth)) return 2; }
+        else if (a == "--min-quality") { if (!cli_min_quality(next(), c.min_quality)) return 2; }
+        else if (a == "--min-base-quality") { if (!cli_base_quality(next(), c.min_base_quality)) return 2; c.has_min_base_quality = 1; c.filter_flag = true; }
+        else if (a == "--exclude-flags") { if (!cli_flag_mask(next(), c.exclude_flags)) return 2; c.filter_flag = true; }
+        else if (a == "--device") c.device = atoi(next());
+        else if (a == "-h" || a == "--help") { c.usage(); return 0; }
+        else if ((mine = own(a, next)) != 0) { if (mine < 0) return 2; }
+        else if (!a.empty() && a[0] != '-' && c.bam.empty()) c.bam = a;
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); c.usage(); return 2; }
+    }
+    if (c.bam.empty() || c.ref.empty() || c.out.empty()) { c.usage(); return 2; }
+    if (c.contig.empty()) { fprintf(stderr, "error: %s needs '-L <CONTIG>'\n", c.name); c.usage(); return 2; }
+    return -1;
+}
+
+// the three flags of a rule of a count and a fraction, --min-STEM-fraction, --min-STEM-count and --min-STEM-per-strand, for own()
+template <class Next>
+static int cli_rule_flags(const std::string &a, Next &&next, const std::string &stem, int (*parse)(const char *, uint32_t *, char *, size_t),
+                          uint32_t &per_10k, uint32_t &count, uint32_t &per_strand)
+{
+    const std::string fraction = "--min-" + stem + "-fraction", cnt = "--min-" + stem + "-count", strand = "--min-" + stem + "-per-strand";
+    if (a == fraction) {
+        const std::string v = next();
+        char why[128] = {0};
+        if (parse(v.c_str(), &per_10k, why, sizeof(why)) == CL_OK) return 1;
+        fprintf(stderr, "error: invalid value '%s' for '%s': %s\n", v.c_str(), fraction.c_str(), why);
+        return -1;
+    }
+    if (a == cnt) {
+        const std::string v = next();
+        if (!cli_count32(cnt.c_str(), v, count)) return -1;
+        if (count == 0) { fprintf(stderr, "error: invalid value '%s' for '%s': at least 1\n", v.c_str(), cnt.c_str()); return -1; }
+        return 1;
+    }
+    if (a == strand) return cli_count32(strand.c_str(), next(), per_strand) ? 1 : -1;
+    return 0;
+}
+
+// the end of a scan subcommand: outputs are closed; skip the HIP runtime's exit handlers (see main)
+static int scan_cli_leave(int rc, const char *err)
+{
+    if (rc != CL_OK) fprintf(stderr, "Error: %s\n", err);
+    fflush(nullptr);
+    _exit(rc != CL_OK ? 1 : 0);
+}
+
+static void usage_fv()
+{
+    fprintf(stderr, "Usage: dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
+                    "       [--min-depth 10] [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
+                    "       [--min-base-quality Q] [--exclude-flags MASK] [--min-alt-per-strand K]\n"
+                    "  --region: 0-based, half open, within the contig.  SNVs only.  Without the last three flags every fetched\n"
+                    "  record counts (no flag or base-quality filter), as in find-y-branch.  With any of them: bases below Q\n"
+                    "  (0..255) and reads with a flag bit of MASK (decimal or 0x hex, 0..65535) do not count, the TSV gains\n"
+                    "  alt_fwd alt_rev ref_fwd ref_rev filter, and filter is 'strand' when min(alt_fwd, alt_rev) < K.\n");
+}
+
+// find-variants: every position of a contig (or of --region, 0-based half open) where the sample's called base differs
+// from the reference, by the counting and the call of find-y-branch (defaults as there, src/cli.rs:62-105); with --tree,
+// which of them the haplogroup tree knows.
+static int find_variants_main(int argc, char **argv)
+{
+    ScanCli c = {"find-variants", usage_fv};
+    std::string tree;
+    int provider = DUT_PROVIDER_FTDNA, tree_type = DUT_TREE_YDNA;
+    bool has_provider = false, has_tree_type = false;
+    dut_variants_options vopt = {0, 0, 0, 0, 0};
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        if (a == "--tree") tree = next();
+        else if (a == "--min-alt-per-strand") { if (!cli_count32("--min-alt-per-strand", next(), vopt.min_alt_per_strand)) return -1; vopt.filtered = 1; }
         else if (a == "--provider") {
             const std::string p = next();
             if (p == "ftdna") provider = DUT_PROVIDER_FTDNA;
             else if (p == "decodingus") provider = DUT_PROVIDER_DECODINGUS;
-            else { fprintf(stderr, "error: invalid value '%s' for '--provider'\n", p.c_str()); return 2; }
+            else { fprintf(stderr, "error: invalid value '%s' for '--provider'\n", p.c_str()); return -1; }
             has_provider = true;
         }
         else if (a == "--tree-type") {
             const std::string p = next();
             if (p == "y") tree_type = DUT_TREE_YDNA;
             else if (p == "mt") tree_type = DUT_TREE_MTDNA;
-            else { fprintf(stderr, "error: invalid value '%s' for '--tree-type'\n", p.c_str()); return 2; }
+            else { fprintf(stderr, "error: invalid value '%s' for '--tree-type'\n", p.c_str()); return -1; }
             has_tree_type = true;
         }
-        else if (a == "--device") device = atoi(next());
-        else if (a == "-h" || a == "--help") { usage_fv(); return 0; }
-        else if (!a.empty() && a[0] != '-' && bam.empty()) bam = a;
-        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fv(); return 2; }
-    }
-    if (bam.empty() || ref.empty() || out.empty()) { usage_fv(); return 2; }
-    if (contig.empty()) { fprintf(stderr, "error: find-variants needs '-L <CONTIG>'\n"); usage_fv(); return 2; }
+        else return 0;
+        return 1;
+    });
+    if (st >= 0) return st;
     if ((has_provider || has_tree_type) && tree.empty()) { fprintf(stderr, "error: '--provider' and '--tree-type' need '--tree <FILE>'\n"); return 2; }
+    c.filter_into(vopt);
+    if (c.filter_flag) vopt.filtered = 1;
     char err[1024] = {0};
-    const int rc = dut_find_variants_files_ex(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end,
-                                              tree.empty() ? nullptr : tree.c_str(), provider, tree_type, out.c_str(), (uint32_t)min_depth,
-                                              (uint8_t)min_quality, &vopt, device, err, sizeof(err));
-    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
-    fflush(nullptr);
-    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
+    return scan_cli_leave(dut_find_variants_files_ex(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), c.has_region ? 1 : 0, (uint32_t)c.start, (uint32_t)c.end,
+                                                     tree.empty() ? nullptr : tree.c_str(), provider, tree_type, c.out.c_str(), (uint32_t)c.min_depth,
+                                                     (uint8_t)c.min_quality, &vopt, c.device, err, sizeof(err)), err);
+}
+
+static void usage_fm()
+{
+    fprintf(stderr, "Usage: dut-coverage find-minor-alleles <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
+                    "       [--min-depth 10] [--min-quality 20] [--min-minor-fraction 0.05] [--min-minor-count 3]\n"
+                    "       [--min-base-quality Q] [--exclude-flags MASK] [--min-minor-per-strand K] [--device 0]\n"
+                    "  A position is listed when it is at least --min-depth deep and the second most frequent of A C G T has at\n"
+                    "  least --min-minor-count observations and --min-minor-fraction of the depth (a decimal in (0, 0.5], at most\n"
+                    "  four decimals).  --region: 0-based, half open.  Q, MASK as in find-variants; filter is 'strand' when\n"
+                    "  min(minor_fwd, minor_rev) < K.  SNVs only, one device.\n");
 }
 
 // find-minor-alleles: every position of a contig (or of --region) where a second base of A C G T stands beside the most
 // frequent one -- at least --min-minor-count observations and --min-minor-fraction of the depth (cl_site_scan_minor).
-// Counting as in find-variants with its filter flags.  Argument errors leave with 2 before a device is opened.
+// Counting as in find-variants with its filter flags.
 static int find_minor_main(int argc, char **argv)
 {
-    std::string bam, ref, out, contig;
-    unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
-    int device = 0;
-    bool has_region = false;
+    ScanCli c = {"find-minor-alleles", usage_fm};
     dut_minor_options mopt = {10, 20, 0, 0, 0, 500, 3, 0};
-    auto usage_fm = []() {
-        fprintf(stderr, "Usage: dut-coverage find-minor-alleles <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
-                        "       [--min-depth 10] [--min-quality 20] [--min-minor-fraction 0.05] [--min-minor-count 3]\n"
-                        "       [--min-base-quality Q] [--exclude-flags MASK] [--min-minor-per-strand K] [--device 0]\n"
-                        "  A position is listed when it is at least --min-depth deep and the second most frequent of A C G T has at\n"
-                        "  least --min-minor-count observations and --min-minor-fraction of the depth (a decimal in (0, 0.5], at most\n"
-                        "  four decimals).  --region: 0-based, half open.  Q, MASK as in find-variants; filter is 'strand' when\n"
-                        "  min(minor_fwd, minor_rev) < K.  SNVs only, one device.\n");
-    };
-    for (int i = 2; i < argc; ++i) {
-        std::string a = argv[i], val;
-        const size_t eq = a.find('=');
-        const bool has_eq = a.rfind("--", 0) == 0 && eq != std::string::npos;
-        if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
-        auto next = [&]() -> const char * {
-            if (has_eq) return val.c_str();
-            if (i + 1 >= argc) { usage_fm(); exit(2); }
-            return argv[++i];
-        };
-        if (a == "-r" || a == "--reference") ref = next();
-        else if (a == "-o" || a == "--output") out = next();
-        else if (a == "-L" || a == "--contig") contig = next();
-        else if (a == "--region") { if (!cli_region(next(), start, end)) return 2; has_region = true; }
-        else if (a == "--min-depth") { if (!cli_min_depth(next(), min_depth)) return 2; }
-        else if (a == "--min-quality") { if (!cli_min_quality(next(), min_quality)) return 2; }
-        else if (a == "--min-minor-fraction") {
-            const std::string v = next();
-            char why[128] = {0};
-            if (dut_minor_fraction_parse(v.c_str(), &mopt.min_minor_per_10k, why, sizeof(why)) != CL_OK) {
-                fprintf(stderr, "error: invalid value '%s' for '--min-minor-fraction': %s\n", v.c_str(), why);
-                return 2;
-            }
-        }
-        else if (a == "--min-minor-count") {
-            const std::string v = next();
-            if (!cli_count32("--min-minor-count", v, mopt.min_minor_count)) return 2;
-            if (mopt.min_minor_count == 0) { fprintf(stderr, "error: invalid value '%s' for '--min-minor-count': at least 1\n", v.c_str()); return 2; }
-        }
-        else if (a == "--min-base-quality") { if (!cli_base_quality(next(), mopt.min_base_quality)) return 2; mopt.has_min_base_quality = 1; }
-        else if (a == "--exclude-flags") { if (!cli_flag_mask(next(), mopt.exclude_flags)) return 2; }
-        else if (a == "--min-minor-per-strand") { if (!cli_count32("--min-minor-per-strand", next(), mopt.min_minor_per_strand)) return 2; }
-        else if (a == "--device") device = atoi(next());
-        else if (a == "-h" || a == "--help") { usage_fm(); return 0; }
-        else if (!a.empty() && a[0] != '-' && bam.empty()) bam = a;
-        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fm(); return 2; }
-    }
-    if (bam.empty() || ref.empty() || out.empty()) { usage_fm(); return 2; }
-    if (contig.empty()) { fprintf(stderr, "error: find-minor-alleles needs '-L <CONTIG>'\n"); usage_fm(); return 2; }
-    mopt.min_depth = (uint32_t)min_depth; mopt.min_quality = (uint8_t)min_quality;
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        return cli_rule_flags(a, next, "minor", dut_minor_fraction_parse, mopt.min_minor_per_10k, mopt.min_minor_count, mopt.min_minor_per_strand);
+    });
+    if (st >= 0) return st;
+    c.filter_into(mopt);
+    mopt.min_depth = (uint32_t)c.min_depth; mopt.min_quality = (uint8_t)c.min_quality;
     char err[1024] = {0};
-    const int rc = dut_find_minor_files(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end, &mopt,
-                                        out.c_str(), device, err, sizeof(err));
-    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
-    fflush(nullptr);
-    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
+    return scan_cli_leave(dut_find_minor_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), c.has_region ? 1 : 0, (uint32_t)c.start, (uint32_t)c.end, &mopt,
+                                               c.out.c_str(), c.device, err, sizeof(err)), err);
+}
+
+static void usage_fd()
+{
+    fprintf(stderr, "Usage: dut-coverage find-deletions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
+                    "       [--min-depth 10] [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3]\n"
+                    "       [--min-base-quality Q] [--exclude-flags MASK] [--min-del-per-strand K] [--device 0]\n"
+                    "  A position is listed when bases plus deletions there are at least --min-depth and the reads with a D\n"
+                    "  operation over it are at least --min-del-count and --min-del-fraction of that sum (a decimal in (0, 1], at\n"
+                    "  most four decimals).  One line per run of consecutive positions.  --region: 0-based, half open.  Q, MASK as\n"
+                    "  in find-variants; filter is 'strand' when min(del_fwd, del_rev) < K.  Deletions only, one device.\n");
 }
 
 // find-deletions: every position of a contig (or of --region) that the reads delete -- at least --min-del-count reads with a
 // D operation over it and --min-del-fraction of depth + deletions (cl_site_scan_dels) -- merged into events of consecutive
-// positions.  Counting as in find-variants with its filter flags.  Argument errors leave with 2 before a device is opened.
+// positions.  Counting as in find-variants with its filter flags.
 static int find_deletions_main(int argc, char **argv)
 {
-    std::string bam, ref, out, contig;
-    unsigned long long min_depth = 10, min_quality = 20, start = 0, end = 0;
-    int device = 0;
-    bool has_region = false;
+    ScanCli c = {"find-deletions", usage_fd};
     dut_del_options dopt = {10, 20, 0, 0, 0, 7000, 3, 0};
-    auto usage_fd = []() {
-        fprintf(stderr, "Usage: dut-coverage find-deletions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
-                        "       [--min-depth 10] [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3]\n"
-                        "       [--min-base-quality Q] [--exclude-flags MASK] [--min-del-per-strand K] [--device 0]\n"
-                        "  A position is listed when bases plus deletions there are at least --min-depth and the reads with a D\n"
-                        "  operation over it are at least --min-del-count and --min-del-fraction of that sum (a decimal in (0, 1], at\n"
-                        "  most four decimals).  One line per run of consecutive positions.  --region: 0-based, half open.  Q, MASK as\n"
-                        "  in find-variants; filter is 'strand' when min(del_fwd, del_rev) < K.  Deletions only, one device.\n");
-    };
-    for (int i = 2; i < argc; ++i) {
-        std::string a = argv[i], val;
-        const size_t eq = a.find('=');
-        const bool has_eq = a.rfind("--", 0) == 0 && eq != std::string::npos;
-        if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
-        auto next = [&]() -> const char * {
-            if (has_eq) return val.c_str();
-            if (i + 1 >= argc) { usage_fd(); exit(2); }
-            return argv[++i];
-        };
-        if (a == "-r" || a == "--reference") ref = next();
-        else if (a == "-o" || a == "--output") out = next();
-        else if (a == "-L" || a == "--contig") contig = next();
-        else if (a == "--region") { if (!cli_region(next(), start, end)) return 2; has_region = true; }
-        else if (a == "--min-depth") { if (!cli_min_depth(next(), min_depth)) return 2; }
-        else if (a == "--min-quality") { if (!cli_min_quality(next(), min_quality)) return 2; }
-        else if (a == "--min-del-fraction") {
-            const std::string v = next();
-            char why[128] = {0};
-            if (dut_del_fraction_parse(v.c_str(), &dopt.min_del_per_10k, why, sizeof(why)) != CL_OK) {
-                fprintf(stderr, "error: invalid value '%s' for '--min-del-fraction': %s\n", v.c_str(), why);
-                return 2;
-            }
-        }
-        else if (a == "--min-del-count") {
-            const std::string v = next();
-            if (!cli_count32("--min-del-count", v, dopt.min_del_count)) return 2;
-            if (dopt.min_del_count == 0) { fprintf(stderr, "error: invalid value '%s' for '--min-del-count': at least 1\n", v.c_str()); return 2; }
-        }
-        else if (a == "--min-base-quality") { if (!cli_base_quality(next(), dopt.min_base_quality)) return 2; dopt.has_min_base_quality = 1; }
-        else if (a == "--exclude-flags") { if (!cli_flag_mask(next(), dopt.exclude_flags)) return 2; }
-        else if (a == "--min-del-per-strand") { if (!cli_count32("--min-del-per-strand", next(), dopt.min_del_per_strand)) return 2; }
-        else if (a == "--device") device = atoi(next());
-        else if (a == "-h" || a == "--help") { usage_fd(); return 0; }
-        else if (!a.empty() && a[0] != '-' && bam.empty()) bam = a;
-        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fd(); return 2; }
-    }
-    if (bam.empty() || ref.empty() || out.empty()) { usage_fd(); return 2; }
-    if (contig.empty()) { fprintf(stderr, "error: find-deletions needs '-L <CONTIG>'\n"); usage_fd(); return 2; }
-    dopt.min_depth = (uint32_t)min_depth; dopt.min_quality = (uint8_t)min_quality;
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        return cli_rule_flags(a, next, "del", dut_del_fraction_parse, dopt.min_del_per_10k, dopt.min_del_count, dopt.min_del_per_strand);
+    });
+    if (st >= 0) return st;
+    c.filter_into(dopt);
+    dopt.min_depth = (uint32_t)c.min_depth; dopt.min_quality = (uint8_t)c.min_quality;
     char err[1024] = {0};
-    const int rc = dut_find_deletions_files(bam.c_str(), ref.c_str(), contig.c_str(), has_region ? 1 : 0, (uint32_t)start, (uint32_t)end, &dopt,
-                                            out.c_str(), device, err, sizeof(err));
-    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
-    fflush(nullptr);
-    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
+    return scan_cli_leave(dut_find_deletions_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), c.has_region ? 1 : 0, (uint32_t)c.start, (uint32_t)c.end, &dopt,
+                                                   c.out.c_str(), c.device, err, sizeof(err)), err);
 }
 
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so

@@ -477,30 +477,21 @@ static cl_status site_scan_index(SiteCtx *c)
     return CL_OK;
 }
 
-// what the host path of the two forms differs in: the C types, the names in messages, where the candidates live (those
-// of cl_site_scan stay valid until the next cl_site_scan, those of cl_site_scan_ex until the next cl_site_scan_ex),
-// the filter argument (none, or the caller's cl_scan_filter) and the tile bytes a scan reads
+// what the host path of the two forms differs in: the filter argument (none, or the caller's cl_scan_filter), the tile
+// bytes a scan reads, and the names and laps of the entry points that exist once per form
 template <bool FILTERED> struct ScanHost;
 template <> struct ScanHost<false> {
-    using Result = cl_scan_result;
-    using Cand = cl_scan_candidate;
     using Filter = ScanNoFilter;
     static constexpr const char *kScan = "cl_site_scan", *kCounts = "cl_site_scan_counts";
     static constexpr const char *kLap = "site scan: reference in, kernel, candidates back";
     static constexpr const char *kLapSettle = "site scan: ambiguous positions settled by the site pileup";
-    static std::vector<Cand> &host_cand(SiteResident &S) { return S.scan_cand; }
-    static DevBuf<ScanCand> &dev_cand(SiteResident &S) { return S.sc_cand; }
     static uint64_t tile_bytes(const SiteResident &S) { return (S.nbase + 1) / 2 + S.n * (sizeof(SiteRec) + 4) + S.ncig * 4; }
 };
 template <> struct ScanHost<true> {
-    using Result = cl_scan_result_ex;
-    using Cand = cl_scan_candidate_ex;
     using Filter = const cl_scan_filter *;
     static constexpr const char *kScan = "cl_site_scan_ex", *kCounts = "cl_site_scan_counts_ex";
     static constexpr const char *kLap = "filtered site scan: reference in, kernel, candidates back";
     static constexpr const char *kLapSettle = "filtered site scan: ambiguous positions settled";
-    static std::vector<Cand> &host_cand(SiteResident &S) { return S.scan_cand_ex; }
-    static DevBuf<ScanCandEx> &dev_cand(SiteResident &S) { return S.sx_cand; }
     // those of cl_site_scan, the pass bits and the flags
     static uint64_t tile_bytes(const SiteResident &S) { return ScanHost<false>::tile_bytes(S) + (S.nbase + 7) / 8 + S.n * 2; }
 };
@@ -537,7 +528,7 @@ static void site_scan_fill(SiteCtx *c, Args &A, typename ScanHost<FILTERED>::Fil
 // The 16-code histograms of the positions the counter planes cannot classify (site_scan.hip.h).  Unfiltered: those of
 // cl_site_run.  Filtered: k_site_scan_settle under the filter of A (cl_site_run's histogram is unfiltered).
 template <bool FILTERED>
-static cl_status site_scan_hist16(SiteCtx *c, const ScanFormArgs<FILTERED> &A, const std::vector<uint32_t> &pos1, std::vector<uint32_t> &hist)
+static cl_status site_scan_hist16(SiteCtx *c, const ScanModeArgs<FILTERED, SCAN_CALLS> &A, const std::vector<uint32_t> &pos1, std::vector<uint32_t> &hist)
 {
     hist.resize(pos1.size() * 16);
     if constexpr (FILTERED) {
@@ -569,35 +560,140 @@ static void site_scan_settle(const std::vector<uint32_t> &hist, uint64_t &n_unc,
     }
 }
 
-// A scan that compacts candidates, of any mode: the index, the reference bytes of the range, then fill() -- the caller's
-// site_scan_fill of A and what else its mode needs, once the index and every buffer stand -- and launch(n_blocks) -- its
-// kernel over A -- until the candidates fit.  A.s.refb, A.s.cls, A.s.n_cand, A.cand and A.s.cand_cap are set here, behind
-// fill().  The class counts and the candidate count come back in h_cls, the number of reference bytes sent in n_ref; the
-// candidates stay in d_cand.
-template <class Args, class DevCand, class Fill, class Launch>
-static cl_status site_scan_compacting(SiteCtx *c, Args &A, DevBuf<DevCand> &d_cand, const uint8_t *ref_bases, uint64_t ref_len, uint32_t start,
-                                      uint32_t end, unsigned long long (&h_cls)[8], uint64_t &n_ref, Fill &&fill, Launch &&launch)
+// What the host path of a compacting mode differs in, beside the kernel's own ScanModeTraits: the C types of its
+// result, candidates and parameters; the name in its messages and its lap; where the candidates live -- one host vector
+// and one device buffer per result type: those of a scan stay valid until the next call of the same scan; fault(), the
+// first of its parameters it refuses, in the order null, min_depth, count, per-10k range; min_depth() and fill(), what it
+// sets in the kernel's record behind site_scan_fill; classes(), its class counts out of h_cls; the tile bytes it reads;
+// post(), what is left to do behind the sorted candidates (nothing, unless the mode says so).
+struct ScanModeHostBase {
+    static constexpr const char *kNoDepth = "min_depth must be at least 1";
+    template <class... T> static cl_status post(T &&...) { return CL_OK; }
+};
+template <bool FILTERED, ScanMode MODE> struct ScanModeHost;
+
+template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_CALLS> : ScanModeHostBase {
+    using H = ScanHost<FILTERED>;
+    using Result = std::conditional_t<FILTERED, cl_scan_result_ex, cl_scan_result>;
+    using Cand = std::conditional_t<FILTERED, cl_scan_candidate_ex, cl_scan_candidate>;
+    using Params = uint32_t;                                     // min_depth itself
+    static constexpr const char *kWho = H::kScan, *kLap = H::kLap;
+    static auto &host_cand(SiteResident &S) { if constexpr (FILTERED) return S.scan_cand_ex; else return S.scan_cand; }
+    static auto &dev_cand(SiteResident &S) { if constexpr (FILTERED) return S.sx_cand; else return S.sc_cand; }
+    static const char *fault(Params min_depth) { return min_depth == 0 ? kNoDepth : nullptr; }
+    static uint32_t min_depth(Params min_depth) { return min_depth; }
+    static void fill(ScanModeArgs<FILTERED, SCAN_CALLS> &, Params) {}
+    static void classes(Result &out, const unsigned long long (&h)[8])
+    {
+        out.n_low_depth = h[SCAN_LOW_DEPTH]; out.n_mixed = h[SCAN_MIXED]; out.n_uncomparable = h[SCAN_UNCOMPARABLE];
+        out.n_match = h[SCAN_MATCH]; out.n_variant = h[SCAN_VARIANT];
+    }
+    static uint64_t tile_bytes(const SiteResident &S) { return H::tile_bytes(S); }
+    // ambiguous positions leave the list and are settled from their 16-code histograms
+    static cl_status post(SiteCtx *c, const ScanModeArgs<FILTERED, SCAN_CALLS> &A, std::vector<Cand> &cand, const unsigned long long (&h)[8],
+                          Result &out, StageTimer &tmr)
+    {
+        if (!h[SCAN_AMBIGUOUS]) return CL_OK;
+        std::vector<uint32_t> amb, hist;
+        size_t k = 0;
+        for (const Cand &cd : cand) { if (cd.alt == 0) amb.push_back(cd.pos); else cand[k++] = cd; }
+        cand.resize(k);
+        const cl_status s = site_scan_hist16<FILTERED>(c, A, amb, hist);
+        if (s != CL_OK) return s;
+        site_scan_settle(hist, out.n_uncomparable, out.n_mixed);
+        tmr.lap(H::kLapSettle);
+        return CL_OK;
+    }
+};
+
+// the minor mode: a second allele beside the most frequent one (site_scan.hip.h), over either form
+template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_MINOR> : ScanModeHostBase {
+    using Result = cl_minor_result;
+    using Cand = cl_minor_candidate;
+    using Params = const cl_minor_params *;
+    static constexpr const char *kWho = "cl_site_scan_minor", *kLap = "minor-allele scan: reference in, kernel, candidates back";
+    static std::vector<Cand> &host_cand(SiteResident &S) { return S.minor_cand; }
+    static DevBuf<ScanMinorCand> &dev_cand(SiteResident &S) { return S.sm_cand; }
+    static const char *fault(Params p)
+    {
+        return !p ? "null params" : p->min_depth == 0 ? kNoDepth : p->min_minor_count == 0 ? "min_minor_count must be at least 1"
+             : (p->min_minor_per_10k < 1 || p->min_minor_per_10k > 5000) ? "min_minor_per_10k must lie in 1..5000" : nullptr;
+    }
+    static uint32_t min_depth(Params p) { return p->min_depth; }
+    static void fill(ScanModeArgs<FILTERED, SCAN_MINOR> &A, Params p) { A.t.min_count = p->min_minor_count; A.t.min_per_10k = p->min_minor_per_10k; }
+    static void classes(Result &out, const unsigned long long (&h)[8]) { out.n_low_depth = h[MINOR_LOW_DEPTH]; out.n_single = h[MINOR_SINGLE]; out.n_minor = h[MINOR_MINOR]; }
+    static uint64_t tile_bytes(const SiteResident &S) { return ScanHost<FILTERED>::tile_bytes(S); }
+};
+
+// the deletion mode: reads whose D operation covers a position, beside the scan's depth (site_scan.hip.h)
+template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_DELS> : ScanModeHostBase {
+    using Result = cl_del_result;
+    using Cand = cl_del_candidate;
+    using Params = const cl_del_params *;
+    static constexpr const char *kWho = "cl_site_scan_dels", *kLap = "deletion scan: reference in, kernel, candidates back";
+    static std::vector<Cand> &host_cand(SiteResident &S) { return S.del_cand; }
+    static DevBuf<ScanDelCand> &dev_cand(SiteResident &S) { return S.sd_cand; }
+    static const char *fault(Params p)
+    {
+        return !p ? "null params" : p->min_depth == 0 ? kNoDepth : p->min_del_count == 0 ? "min_del_count must be at least 1"
+             : (p->min_del_per_10k < 1 || p->min_del_per_10k > 10000) ? "min_del_per_10k must lie in 1..10000" : nullptr;
+    }
+    static uint32_t min_depth(Params p) { return p->min_depth; }
+    static void fill(ScanModeArgs<FILTERED, SCAN_DELS> &A, Params p) { A.t.min_count = p->min_del_count; A.t.min_per_10k = p->min_del_per_10k; }
+    static void classes(Result &out, const unsigned long long (&h)[8]) { out.n_low_depth = h[DEL_LOW_DEPTH]; out.n_kept = h[DEL_KEPT]; out.n_deleted = h[DEL_DELETED]; }
+    // the tile without its bases: records, ends, CIGAR words; under a filter the flags and the pass bits
+    static uint64_t tile_bytes(const SiteResident &S) { return S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + (FILTERED ? (S.nbase + 7) / 8 + S.n * 2 : 0); }
+};
+
+// A scan that compacts candidates, of any mode and form: the checks, the index, the reference bytes of the range, the
+// kernel until the candidates fit, the candidates back and in ascending position, the mode's post step.
+template <bool FILTERED, ScanMode MODE>
+static cl_status site_scan_run(SiteCtx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, typename ScanModeHost<FILTERED, MODE>::Params prm,
+                               const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, typename ScanModeHost<FILTERED, MODE>::Result *out)
 {
-    SiteResident &S = c->site;
-    cl_status s = site_scan_index(c);
+    using M = ScanModeHost<FILTERED, MODE>;
+    using Cand = typename M::Cand;
+    if (!c) return CL_ERR_INVALID;
+    const std::string who = M::kWho;
+    if (!out) return fail(c, CL_ERR_INVALID, who + ": null result");
+    cl_status s = site_scan_check_form<FILTERED>(c, M::kWho, filter, start, end);
     if (s != CL_OK) return s;
+    SiteResident &S = c->site;
+    if (const char *fault = M::fault(prm)) return fail(c, CL_ERR_INVALID, who + ": " + fault);
+    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, who + ": ref_len differs from the one given to cl_site_upload");
+    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, who + ": null reference");
+    std::vector<Cand> &cand = M::host_cand(S);
+    auto &d_cand = M::dev_cand(S);
+    memset(out, 0, sizeof(*out));
+    out->start = start; out->end = end;
+    cand.clear();
+    out->candidates = cand.data();
+    S.t_scan.ms = 0.0; S.t_scan.bytes = 0;
+    if (start == end) return CL_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    StageTimer tmr;
+    if ((s = site_scan_index(c)) != CL_OK) return s;
     // the reference bytes of the range (those that exist: positions at and beyond ref_len read as "other")
     const uint64_t ref_hi = std::min<uint64_t>(end, ref_len);
-    n_ref = ref_hi > start ? ref_hi - start : 0;
+    const uint64_t n_ref = ref_hi > start ? ref_hi - start : 0;
     HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
     if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
     const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
     // candidates are few where the sample follows the reference: a buffer of a position in 64 (at least 64 K entries);
     // when more are wanted the kernel says how many, the buffer grows and the scan runs again -- nothing is cut short
     uint64_t cap = std::max<uint64_t>(65536, (uint64_t)(end - start) / 64);
+    unsigned long long h_cls[8];                                 // the class counts, then the candidates wanted
+    ScanModeArgs<FILTERED, MODE> A;
     for (;;) {
         HIP_TRY(c, d_cand.reserve(cap));
         HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
-        fill();
+        // (the record is filled once the index and every buffer stand)
+        site_scan_fill<FILTERED>(c, A, filter, min_quality, M::min_depth(prm), start, end);
+        M::fill(A, prm);
         A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
         A.cand = d_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
         HIP_TRY(c, S.t_scan.start(c->stream));
-        launch(n_blocks);
+        hipLaunchKernelGGL((k_site_scan<FILTERED, MODE>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, S.t_scan.stop(c->stream));
         HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
@@ -607,157 +703,25 @@ static cl_status site_scan_compacting(SiteCtx *c, Args &A, DevBuf<DevCand> &d_ca
         if (want <= cap) break;
         cap = want;
     }
-    return CL_OK;
-}
-
-template <bool FILTERED>
-static cl_status site_scan_impl(SiteCtx *c, uint8_t min_quality, uint32_t min_depth, typename ScanHost<FILTERED>::Filter filter, const uint8_t *ref_bases,
-                                uint64_t ref_len, uint32_t start, uint32_t end, typename ScanHost<FILTERED>::Result *out)
-{
-    using H = ScanHost<FILTERED>;
-    using Cand = typename H::Cand;
-    if (!c) return CL_ERR_INVALID;
-    if (!out) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": null result");
-    cl_status s = site_scan_check_form<FILTERED>(c, H::kScan, filter, start, end);
-    if (s != CL_OK) return s;
-    SiteResident &S = c->site;
-    if (min_depth == 0) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": min_depth must be at least 1");
-    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": ref_len differs from the one given to cl_site_upload");
-    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, std::string(H::kScan) + ": null reference");
-    std::vector<Cand> &cand = H::host_cand(S);
-    auto &d_cand = H::dev_cand(S);
-    memset(out, 0, sizeof(*out));
-    out->start = start; out->end = end;
-    cand.clear();
-    out->candidates = cand.data();
-    c->site.t_scan.ms = 0.0; c->site.t_scan.bytes = 0;
-    if (start == end) return CL_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    StageTimer tmr;
-    unsigned long long h_cls[8];
-    uint64_t n_ref = 0;
-    ScanFormArgs<FILTERED> A;
-    s = site_scan_compacting(c, A, d_cand, ref_bases, ref_len, start, end, h_cls, n_ref,
-                             [&] { site_scan_fill<FILTERED>(c, A, filter, min_quality, min_depth, start, end); }, [&](uint32_t n_blocks) {
-        hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_CALLS>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-    });
-    if (s != CL_OK) return s;
     const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
     cand.resize(n_cand);
     if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), d_cand.p, n_cand * sizeof(Cand), hipMemcpyDeviceToHost));
-    S.t_scan.bytes = H::tile_bytes(S) + n_ref + n_cand * sizeof(Cand);
-    tmr.lap(H::kLap);
-    // the compaction runs wave by wave: ascending position is restored here; ambiguous positions leave the list
+    S.t_scan.bytes = M::tile_bytes(S) + n_ref + n_cand * sizeof(Cand);
+    tmr.lap(M::kLap);
+    // the compaction runs wave by wave: ascending position is restored here
     std::sort(cand.begin(), cand.end(), [](const Cand &a, const Cand &b) { return a.pos < b.pos; });
-    out->n_low_depth = h_cls[SCAN_LOW_DEPTH]; out->n_mixed = h_cls[SCAN_MIXED]; out->n_uncomparable = h_cls[SCAN_UNCOMPARABLE];
-    out->n_match = h_cls[SCAN_MATCH]; out->n_variant = h_cls[SCAN_VARIANT];
-    if (h_cls[SCAN_AMBIGUOUS]) {
-        std::vector<uint32_t> amb, hist;
-        size_t k = 0;
-        for (const Cand &cd : cand) { if (cd.alt == 0) amb.push_back(cd.pos); else cand[k++] = cd; }
-        cand.resize(k);
-        if ((s = site_scan_hist16<FILTERED>(c, A, amb, hist)) != CL_OK) return s;
-        site_scan_settle(hist, out->n_uncomparable, out->n_mixed);
-        tmr.lap(H::kLapSettle);
-    }
+    M::classes(*out, h_cls);
+    if ((s = M::post(c, A, cand, h_cls, *out, tmr)) != CL_OK) return s;
     out->candidates = cand.data();
     return CL_OK;
 }
 
-// ---- the minor mode: a second allele beside the most frequent one (site_scan.hip.h), over either form ----
-template <bool FILTERED>
-static cl_status site_scan_minor_impl(SiteCtx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, const cl_minor_params *prm,
-                                      const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, cl_minor_result *out)
+// a mode whose filter may be null: that is its unfiltered form
+template <ScanMode MODE, class... Rest>
+static cl_status site_scan_either(SiteCtx *c, uint8_t min_quality, const cl_scan_filter *filter, Rest... rest)
 {
-    using H = ScanHost<FILTERED>;
-    static const char *const who = "cl_site_scan_minor";
-    if (!out) return fail(c, CL_ERR_INVALID, std::string(who) + ": null result");
-    cl_status s = site_scan_check_form<FILTERED>(c, who, filter, start, end);
-    if (s != CL_OK) return s;
-    SiteResident &S = c->site;
-    if (!prm) return fail(c, CL_ERR_INVALID, std::string(who) + ": null params");
-    if (prm->min_depth == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_depth must be at least 1");
-    if (prm->min_minor_count == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_minor_count must be at least 1");
-    if (prm->min_minor_per_10k < 1 || prm->min_minor_per_10k > 5000) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_minor_per_10k must lie in 1..5000");
-    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": ref_len differs from the one given to cl_site_upload");
-    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": null reference");
-    std::vector<cl_minor_candidate> &cand = S.minor_cand;
-    memset(out, 0, sizeof(*out));
-    out->start = start; out->end = end;
-    cand.clear();
-    out->candidates = cand.data();
-    S.t_scan.ms = 0.0; S.t_scan.bytes = 0;
-    if (start == end) return CL_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    StageTimer tmr;
-    unsigned long long h_cls[8];
-    uint64_t n_ref = 0;
-    ScanMinorArgs<FILTERED> A;
-    s = site_scan_compacting(c, A, S.sm_cand, ref_bases, ref_len, start, end, h_cls, n_ref, [&] {
-        site_scan_fill<FILTERED>(c, A, filter, min_quality, prm->min_depth, start, end);
-        A.min_minor_count = prm->min_minor_count; A.min_minor_per_10k = prm->min_minor_per_10k;
-    }, [&](uint32_t n_blocks) {
-        hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_MINOR>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-    });
-    if (s != CL_OK) return s;
-    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
-    cand.resize(n_cand);
-    if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), S.sm_cand.p, n_cand * sizeof(cl_minor_candidate), hipMemcpyDeviceToHost));
-    S.t_scan.bytes = H::tile_bytes(S) + n_ref + n_cand * sizeof(cl_minor_candidate);
-    tmr.lap("minor-allele scan: reference in, kernel, candidates back");
-    // the compaction runs wave by wave: ascending position is restored here
-    std::sort(cand.begin(), cand.end(), [](const cl_minor_candidate &a, const cl_minor_candidate &b) { return a.pos < b.pos; });
-    out->n_low_depth = h_cls[MINOR_LOW_DEPTH]; out->n_single = h_cls[MINOR_SINGLE]; out->n_minor = h_cls[MINOR_MINOR];
-    out->candidates = cand.data();
-    return CL_OK;
-}
-
-// ---- the deletion mode: reads whose D operation covers a position, beside the scan's depth (site_scan.hip.h) ----
-template <bool FILTERED>
-static cl_status site_scan_dels_impl(SiteCtx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, const cl_del_params *prm,
-                                     const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, cl_del_result *out)
-{
-    static const char *const who = "cl_site_scan_dels";
-    if (!out) return fail(c, CL_ERR_INVALID, std::string(who) + ": null result");
-    cl_status s = site_scan_check_form<FILTERED>(c, who, filter, start, end);
-    if (s != CL_OK) return s;
-    SiteResident &S = c->site;
-    if (!prm) return fail(c, CL_ERR_INVALID, std::string(who) + ": null params");
-    if (prm->min_depth == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_depth must be at least 1");
-    if (prm->min_del_count == 0) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_del_count must be at least 1");
-    if (prm->min_del_per_10k < 1 || prm->min_del_per_10k > 10000) return fail(c, CL_ERR_INVALID, std::string(who) + ": min_del_per_10k must lie in 1..10000");
-    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": ref_len differs from the one given to cl_site_upload");
-    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, std::string(who) + ": null reference");
-    std::vector<cl_del_candidate> &cand = S.del_cand;
-    memset(out, 0, sizeof(*out));
-    out->start = start; out->end = end;
-    cand.clear();
-    out->candidates = cand.data();
-    S.t_scan.ms = 0.0; S.t_scan.bytes = 0;
-    if (start == end) return CL_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    StageTimer tmr;
-    unsigned long long h_cls[8];
-    uint64_t n_ref = 0;
-    ScanDelArgs<FILTERED> A;
-    s = site_scan_compacting(c, A, S.sd_cand, ref_bases, ref_len, start, end, h_cls, n_ref, [&] {
-        site_scan_fill<FILTERED>(c, A, filter, min_quality, prm->min_depth, start, end);
-        A.min_del_count = prm->min_del_count; A.min_del_per_10k = prm->min_del_per_10k;
-    }, [&](uint32_t n_blocks) {
-        hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_DELS>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-    });
-    if (s != CL_OK) return s;
-    const uint64_t n_cand = (uint32_t)h_cls[SCAN_CLASSES];
-    cand.resize(n_cand);
-    if (n_cand) HIP_TRY(c, hipMemcpy(cand.data(), S.sd_cand.p, n_cand * sizeof(cl_del_candidate), hipMemcpyDeviceToHost));
-    // the tile without its bases: records, ends, CIGAR words; under a filter the flags and the pass bits
-    S.t_scan.bytes = S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + (FILTERED ? (S.nbase + 7) / 8 + S.n * 2 : 0) + n_ref + n_cand * sizeof(cl_del_candidate);
-    tmr.lap("deletion scan: reference in, kernel, candidates back");
-    // the compaction runs wave by wave: ascending position is restored here
-    std::sort(cand.begin(), cand.end(), [](const cl_del_candidate &a, const cl_del_candidate &b) { return a.pos < b.pos; });
-    out->n_low_depth = h_cls[DEL_LOW_DEPTH]; out->n_kept = h_cls[DEL_KEPT]; out->n_deleted = h_cls[DEL_DELETED];
-    out->candidates = cand.data();
-    return CL_OK;
+    if (filter) return site_scan_run<true, MODE>(c, min_quality, filter, rest...);
+    return site_scan_run<false, MODE>(c, min_quality, ScanNoFilter{}, rest...);
 }
 
 template <bool FILTERED>
@@ -777,7 +741,7 @@ static cl_status site_scan_counts_impl(SiteCtx *c, uint8_t min_quality, typename
     if ((s = site_scan_index(c)) != CL_OK) return s;
     const size_t n_dense = (size_t)(end - start) * ScanForm<FILTERED>::kDense;
     HIP_TRY(c, S.sc_dense.reserve(n_dense));
-    ScanFormArgs<FILTERED> A;
+    ScanModeArgs<FILTERED, SCAN_DENSE> A;
     site_scan_fill<FILTERED>(c, A, filter, min_quality, 1, start, end);
     A.s.dense = S.sc_dense.p;
     HIP_TRY(c, S.t_scan.start(c->stream));
@@ -815,7 +779,7 @@ extern "C" {
 cl_status cl_site_scan(cl_ctx *h, uint8_t min_quality, uint32_t min_depth, const uint8_t *ref_bases, uint64_t ref_len,
                        uint32_t start, uint32_t end, cl_scan_result *out)
 {
-    return site_entry(h, [&](SiteCtx *c) { return site_scan_impl<false>(c, min_quality, min_depth, ScanNoFilter{}, ref_bases, ref_len, start, end, out); });
+    return site_entry(h, [&](SiteCtx *c) { return site_scan_run<false, SCAN_CALLS>(c, min_quality, ScanNoFilter{}, min_depth, ref_bases, ref_len, start, end, out); });
 }
 
 cl_status cl_site_scan_counts(cl_ctx *h, uint8_t min_quality, uint32_t start, uint32_t end, uint32_t *counts)
@@ -861,27 +825,19 @@ cl_status cl_site_attach_quals(cl_ctx *h, const cl_site_quals *q, uint8_t min_ba
 cl_status cl_site_scan_ex(cl_ctx *h, uint8_t min_quality, uint32_t min_depth, const cl_scan_filter *filter, const uint8_t *ref_bases,
                           uint64_t ref_len, uint32_t start, uint32_t end, cl_scan_result_ex *out)
 {
-    return site_entry(h, [&](SiteCtx *c) { return site_scan_impl<true>(c, min_quality, min_depth, filter, ref_bases, ref_len, start, end, out); });
+    return site_entry(h, [&](SiteCtx *c) { return site_scan_run<true, SCAN_CALLS>(c, min_quality, filter, min_depth, ref_bases, ref_len, start, end, out); });
 }
 
 cl_status cl_site_scan_minor(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, const cl_minor_params *params, const uint8_t *ref_bases,
                              uint64_t ref_len, uint32_t start, uint32_t end, cl_minor_result *out)
 {
-    return site_entry(h, [&](SiteCtx *c) -> cl_status {
-        if (!c) return CL_ERR_INVALID;
-        if (filter) return site_scan_minor_impl<true>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
-        return site_scan_minor_impl<false>(c, min_quality, ScanNoFilter{}, params, ref_bases, ref_len, start, end, out);
-    });
+    return site_entry(h, [&](SiteCtx *c) { return site_scan_either<SCAN_MINOR>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out); });
 }
 
 cl_status cl_site_scan_dels(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, const cl_del_params *params, const uint8_t *ref_bases,
                             uint64_t ref_len, uint32_t start, uint32_t end, cl_del_result *out)
 {
-    return site_entry(h, [&](SiteCtx *c) -> cl_status {
-        if (!c) return CL_ERR_INVALID;
-        if (filter) return site_scan_dels_impl<true>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
-        return site_scan_dels_impl<false>(c, min_quality, ScanNoFilter{}, params, ref_bases, ref_len, start, end, out);
-    });
+    return site_entry(h, [&](SiteCtx *c) { return site_scan_either<SCAN_DELS>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out); });
 }
 
 cl_status cl_site_scan_counts_ex(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)

@@ -19,10 +19,10 @@
 //   k_site_scan<FILTERED, MODE>
 //                       one workgroup per window: reads of the window's range are dealt to the threads, a thread walks
 //                       its read's CIGAR over the window and adds into LDS counter planes (one ds_add without return
-//                       per base, consecutive positions in consecutive banks); then every thread classifies positions
-//                       and the candidates are compacted with one ballot and one atomic per wave.  What happens to
-//                       the finished planes is the MODE: the calling rule and its candidates (SCAN_CALLS), the counters
-//                       themselves (SCAN_DENSE), or the second-allele rule and its candidates (SCAN_MINOR).
+//                       per base, consecutive positions in consecutive banks).  What happens to the finished planes is
+//                       the MODE: the counters themselves go out (SCAN_DENSE), or every thread judges positions and the
+//                       candidates are compacted with one ballot and one atomic per wave -- by the calling rule
+//                       (SCAN_CALLS), the second-allele rule (SCAN_MINOR) or the deletion rule (SCAN_DELS).
 //   k_site_scan_settle  filtered form only: the 16-code histogram of the few positions the planes cannot classify.
 //
 // The unfiltered form (ScanForm<false>) counts in six planes: A, C, G, T, N, any other code.  Six planes and not
@@ -145,7 +145,7 @@ struct ScanArgs {
     const SiteRec *rec;
     const unsigned long long *seq_base;      // per kBlock reads: base offset of the first one
     const uint32_t *cigar;
-    const uint8_t  *seq4;
+    const uint8_t  *seq4;                    // (never read by the deletion mode)
     const uint32_t *end, *wfirst, *wlast;
     uint32_t min_quality, contig_len, min_depth;
     unsigned long long ref_len;
@@ -158,38 +158,33 @@ struct ScanArgs {
     uint32_t *dense;                         // SCAN_DENSE: (end_pos - start) * ScanForm::kDense
 };
 
-template <bool FILTERED>
-struct ScanFormArgs {
+// What a mode is to k_site_scan: the candidate it compacts, the thresholds of its rule beside min_depth (none, or a count and
+// parts per 10 000) and, for scan_judge_positions, the class it emits.  Primary: SCAN_CALLS, whose record SCAN_DENSE keeps.
+struct ScanNoThresholds {};
+struct ScanThresholds { uint32_t min_count, min_per_10k; };
+template <bool FILTERED, ScanMode MODE> struct ScanModeTraits {
+    using Cand = typename ScanForm<FILTERED>::Cand;
+    using Thresholds = ScanNoThresholds;
+};
+template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_MINOR> {
+    using Cand = ScanMinorCand;
+    using Thresholds = ScanThresholds;
+    static __device__ __forceinline__ bool emits(int cls) { return cls == MINOR_MINOR; }
+};
+template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_DELS> {
+    using Cand = ScanDelCand;
+    using Thresholds = ScanThresholds;
+    static __device__ __forceinline__ bool emits(int cls) { return cls == DEL_DELETED; }
+};
+template <bool FILTERED, ScanMode MODE> struct ScanModeArgs {                // the kernel's record
     ScanArgs s;
     typename ScanForm<FILTERED>::Filter f;
-    typename ScanForm<FILTERED>::Cand *cand;
+    typename ScanModeTraits<FILTERED, MODE>::Cand *cand;
+    [[no_unique_address]] typename ScanModeTraits<FILTERED, MODE>::Thresholds t;
 };
-
-// the minor mode's record: its own candidate type and thresholds (the other modes' record stays as it is)
-template <bool FILTERED>
-struct ScanMinorArgs {
-    ScanArgs s;
-    typename ScanForm<FILTERED>::Filter f;
-    ScanMinorCand *cand;
-    uint32_t min_minor_count, min_minor_per_10k;
-};
-
-// the deletion mode's record
-template <bool FILTERED>
-struct ScanDelArgs {
-    ScanArgs s;                              // (s.seq4 is never read)
-    typename ScanForm<FILTERED>::Filter f;
-    ScanDelCand *cand;
-    uint32_t min_del_count, min_del_per_10k;
-};
-
-template <bool FILTERED, ScanMode MODE>
-using ScanModeArgs = std::conditional_t<MODE == SCAN_MINOR, ScanMinorArgs<FILTERED>,
-                                        std::conditional_t<MODE == SCAN_DELS, ScanDelArgs<FILTERED>, ScanFormArgs<FILTERED>>>;
 
 // LDS planes of a mode: depth and del by strand in the deletion mode (8 KB, 16 KB), the form's base planes otherwise
-template <bool FILTERED, ScanMode MODE>
-inline constexpr uint32_t kScanPlanes = MODE == SCAN_DELS ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
+template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanPlanes = MODE == SCAN_DELS ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
 
 // number of CIGAR operations and bases of a read, with SiteRec's escape to the next record's offsets
 __device__ __forceinline__ void scan_read_extent(const SiteRec *rec, uint32_t r, const uint4 &rr, uint32_t &k1, unsigned long long &slen)
@@ -386,6 +381,29 @@ __device__ __forceinline__ int scan_classify_minor(const uint32_t (&cnt)[4], uns
     return (c2 >= min_minor_count && 10000ull * c2 >= (unsigned long long)min_minor_per_10k * depth) ? MINOR_MINOR : MINOR_SINGLE;
 }
 
+// The tail of the two rule modes (the calling rule keeps its own, in the kernel).  A thread has kScanWin / kBlock
+// positions: offset(j) is the window offset o of its j-th, judge(j, o, ref, cd) returns the class of position ws + o and
+// fills cd but for its pos, ref() being the reference byte as sent ('N' at and beyond hi).  The emitted class is compacted.
+template <bool FILTERED, ScanMode MODE, class Offset, class Judge>
+__device__ __forceinline__ void scan_judge_positions(const ScanModeArgs<FILTERED, MODE> &ax, const ScanWindow &win, uint32_t *s_cnt, Offset &&offset, Judge &&judge)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (uint32_t j = 0; j < kScanWin / (uint32_t)kBlock; ++j) {                   // (uniform trip count: the ballot needs whole waves)
+        const uint32_t o = offset(j), p = win.ws + o;
+        int cls = -1;
+        typename ScanModeTraits<FILTERED, MODE>::Cand cd;
+        if (p >= win.lo && p < win.we) {
+            cls = judge(j, o, [&]() -> uint32_t { return p < win.hi ? ax.s.refb[p - ax.s.start] : (uint32_t)'N'; }, cd);
+            mine[cls] += 1u;
+            cd.pos = p + 1u;
+        }
+        scan_compact(ScanModeTraits<FILTERED, MODE>::emits(cls), cd, lane, ax.s.n_cand, ax.cand, ax.s.cand_cap);
+    }
+    scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), ax.s.cls, tid, lane);     // (s_cnt: every judge has read it)
+}
+
 template <bool FILTERED, ScanMode MODE>
 __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MODE> ax)
 {
@@ -487,69 +505,51 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
 #pragma unroll
             for (uint32_t j = 0; j < 4u; ++j) q[k][j] += add;
         }
-        uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (uint32_t j = 0; j < 4u; ++j) {                                     // (uniform trip count: the ballot needs whole waves)
-            const uint32_t o = 4u * tid + j, p = ws + o;
-            int cls = -1;
-            ScanDelCand cd;
-            if (p >= lo && p < we) {
-                const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, del_f = q[S][j], del_r = FILTERED ? q[2u * S - 1u][j] : 0u;
-                const unsigned long long depth = (unsigned long long)depth_f + depth_r, del = (unsigned long long)del_f + del_r, span = depth + del;
-                cls = span < a.min_depth ? DEL_LOW_DEPTH
-                    : (del >= ax.min_del_count && 10000ull * del >= (unsigned long long)ax.min_del_per_10k * span) ? DEL_DELETED : DEL_KEPT;
-                mine[cls] += 1u;
-                const uint32_t rb = (p < hi ? a.refb[p - a.start] : (uint32_t)'N') & ~32u;
-                cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.pad[0] = cd.pad[1] = cd.pad[2] = 0;
-                cd.del = (uint32_t)del; cd.depth = (uint32_t)depth;
-                cd.del_fwd = FILTERED ? del_f : 0u; cd.del_rev = del_r; cd.depth_fwd = FILTERED ? depth_f : 0u; cd.depth_rev = depth_r;
-            }
-            scan_compact(cls == DEL_DELETED, cd, lane, a.n_cand, ax.cand, a.cand_cap);
-        }
-        scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);
+        scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return 4u * tid + j; }, [&](uint32_t j, uint32_t, auto &&ref, ScanDelCand &cd) {
+            // (j is a constant of the unrolled loop: q stays in registers)
+            const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, del_f = q[S][j], del_r = FILTERED ? q[2u * S - 1u][j] : 0u;
+            const unsigned long long depth = (unsigned long long)depth_f + depth_r, del = (unsigned long long)del_f + del_r, span = depth + del;
+            const int cls = span < a.min_depth ? DEL_LOW_DEPTH
+                          : (del >= ax.t.min_count && 10000ull * del >= (unsigned long long)ax.t.min_per_10k * span) ? DEL_DELETED : DEL_KEPT;
+            cd.ref = (uint8_t)(ref() & ~32u); cd.pad[0] = cd.pad[1] = cd.pad[2] = 0;
+            cd.del = (uint32_t)del; cd.depth = (uint32_t)depth;
+            cd.del_fwd = FILTERED ? del_f : 0u; cd.del_rev = del_r; cd.depth_fwd = FILTERED ? depth_f : 0u; cd.depth_rev = depth_r;
+            return cls;
+        });
     } else if constexpr (MODE == SCAN_MINOR) {
+        scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return j * (uint32_t)kBlock + tid; }, [&](uint32_t, uint32_t o, auto &&ref, ScanMinorCand &cd) {
+            uint32_t f[4], v[4], cnt[4];                                    // A C G T: forward, reverse, both
+            unsigned long long depth = (unsigned long long)s_cnt[(4u * S) * kScanWin + o] + s_cnt[(4u * S + 1u) * kScanWin + o];
+#pragma unroll
+            for (uint32_t b = 0; b < 4u; ++b) {
+                f[b] = s_cnt[(S * b) * kScanWin + o]; v[b] = FILTERED ? s_cnt[(S * b + 1u) * kScanWin + o] : 0u;
+                cnt[b] = f[b] + v[b]; depth += cnt[b];
+            }
+            uint32_t major, minor, c2;
+            const int cls = scan_classify_minor(cnt, depth, a.min_depth, ax.t.min_count, ax.t.min_per_10k, major, minor, c2);
+            cd.ref = (uint8_t)(ref() & ~32u); cd.pad = 0;
+            cd.major = (uint8_t)(0x54474341u >> (8u * major)); cd.minor = (uint8_t)(0x54474341u >> (8u * minor));   // "ACGT"
+            cd.a = cnt[0]; cd.c = cnt[1]; cd.g = cnt[2]; cd.t = cnt[3]; cd.depth = (uint32_t)depth;
+            cd.major_fwd = cd.major_rev = cd.minor_fwd = cd.minor_rev = 0;
+            if constexpr (FILTERED) {
+#pragma unroll
+                for (uint32_t b = 0; b < 4u; ++b) {                           // (selects, not indexed registers)
+                    if (b == major) { cd.major_fwd = f[b]; cd.major_rev = v[b]; }
+                    if (b == minor) { cd.minor_fwd = f[b]; cd.minor_rev = v[b]; }
+                }
+            }
+            return cls;
+        });
+    } else {
+        // (a tail of its own: through scan_judge_positions the filtered form was 2 % slower, profiles/r14_scan_modes_folded.txt)
         uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
         const uint32_t lane = tid & 63u;
         for (uint32_t o0 = 0; o0 < kScanWin; o0 += kBlock) {                   // (uniform trip count: the ballot needs whole waves)
             const uint32_t o = o0 + tid, p = ws + o;
             int cls = -1;
-            ScanMinorCand cd;
-            if (p >= lo && p < we) {
-                uint32_t f[4], v[4], cnt[4];                                    // A C G T: forward, reverse, both
-                unsigned long long depth = (unsigned long long)s_cnt[(4u * S) * kScanWin + o] + s_cnt[(4u * S + 1u) * kScanWin + o];
-#pragma unroll
-                for (uint32_t b = 0; b < 4u; ++b) {
-                    f[b] = s_cnt[(S * b) * kScanWin + o]; v[b] = FILTERED ? s_cnt[(S * b + 1u) * kScanWin + o] : 0u;
-                    cnt[b] = f[b] + v[b]; depth += cnt[b];
-                }
-                uint32_t major, minor, c2;
-                cls = scan_classify_minor(cnt, depth, a.min_depth, ax.min_minor_count, ax.min_minor_per_10k, major, minor, c2);
-                mine[cls] += 1u;
-                const uint32_t rb = (p < hi ? a.refb[p - a.start] : (uint32_t)'N') & ~32u;
-                cd.pos = p + 1u; cd.ref = (uint8_t)rb; cd.pad = 0;
-                cd.major = (uint8_t)(0x54474341u >> (8u * major)); cd.minor = (uint8_t)(0x54474341u >> (8u * minor));   // "ACGT"
-                cd.a = cnt[0]; cd.c = cnt[1]; cd.g = cnt[2]; cd.t = cnt[3]; cd.depth = (uint32_t)depth;
-                cd.major_fwd = cd.major_rev = cd.minor_fwd = cd.minor_rev = 0;
-                if constexpr (FILTERED) {
-#pragma unroll
-                    for (uint32_t b = 0; b < 4u; ++b) {                           // (selects, not indexed registers)
-                        if (b == major) { cd.major_fwd = f[b]; cd.major_rev = v[b]; }
-                        if (b == minor) { cd.minor_fwd = f[b]; cd.minor_rev = v[b]; }
-                    }
-                }
-            }
-            scan_compact(cls == MINOR_MINOR, cd, lane, a.n_cand, ax.cand, a.cand_cap);
-        }
-        scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);
-    } else {
-        uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
-        const uint32_t lane = tid & 63u;
-        for (uint32_t o0 = 0; o0 < kScanWin; o0 += kBlock) {                       // (uniform trip count: the ballot needs whole waves)
-            const uint32_t o = o0 + tid, p = ws + o;
-            int cls = -1;
             typename Form::Cand cd;
             if (p >= lo && p < we) {
-                uint32_t f[4], v[4];                                                // A C G T, forward and reverse
+                uint32_t f[4], v[4];                                            // A C G T, forward and reverse
 #pragma unroll
                 for (uint32_t b = 0; b < 4u; ++b) { f[b] = s_cnt[(S * b) * kScanWin + o]; v[b] = FILTERED ? s_cnt[(S * b + 1u) * kScanWin + o] : 0u; }
                 const uint32_t A = f[0] + v[0], Cc = f[1] + v[1], G = f[2] + v[2], T = f[3] + v[3];
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
                     if (cls == SCAN_VARIANT) {
                         const uint32_t ri = rb == 'A' ? 0u : rb == 'C' ? 1u : rb == 'G' ? 2u : 3u;    // (a variant's reference base is of ACGT)
 #pragma unroll
-                        for (uint32_t b = 0; b < 4u; ++b) {                           // (selects, not indexed registers)
+                        for (uint32_t b = 0; b < 4u; ++b) {                       // (selects, not indexed registers)
                             if (b == ai) { cd.alt_fwd = f[b]; cd.alt_rev = v[b]; }
                             if (b == ri) { cd.ref_fwd = f[b]; cd.ref_rev = v[b]; }
                         }
@@ -579,7 +579,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
 
 // The 16-code histogram of single positions under the filter of ax: one workgroup per position of pos1 (1-based, inside
 // the contig), over the reads of the position's window range.  For the few positions the ten planes cannot classify.
-__global__ __launch_bounds__(kBlock) void k_site_scan_settle(ScanFormArgs<true> ax, const uint32_t *pos1, uint32_t *hist16)
+__global__ __launch_bounds__(kBlock) void k_site_scan_settle(ScanModeArgs<true, SCAN_CALLS> ax, const uint32_t *pos1, uint32_t *hist16)
 {
     __shared__ uint32_t s_h[16];
     const ScanArgs &a = ax.s;

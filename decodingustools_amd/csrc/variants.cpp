@@ -85,6 +85,52 @@ int write_file(const char *path, const std::string &s, char *err, size_t err_len
     return CL_OK;
 }
 
+// A rule of a count and parts per 10 000 (the second allele, the deletion): its names in messages and TSV lines and the
+// largest per-10k value
+struct Rule { const char *count, *per_10k, *fraction; uint32_t max_per_10k; };
+const Rule MINOR_RULE = {"min_minor_count", "min_minor_per_10k", "min_minor_fraction", 5000};
+const Rule DEL_RULE = {"min_del_count", "min_del_per_10k", "min_del_fraction", 10000};
+
+// what a file-level scan is asked with: the flag and base-quality filter, and a rule's own values -- dut_minor_options and
+// dut_del_options member by member
+struct FilterOptions { int has_min_base_quality; uint8_t min_base_quality; uint16_t exclude_flags; };
+struct ScanOptions { uint32_t min_depth; uint8_t min_quality; FilterOptions flt; uint32_t per_10k, count, per_strand; };
+ScanOptions scan_options(const dut_minor_options &o)
+{
+    return {o.min_depth, o.min_quality, {o.has_min_base_quality, o.min_base_quality, o.exclude_flags}, o.min_minor_per_10k, o.min_minor_count, o.min_minor_per_strand};
+}
+ScanOptions scan_options(const dut_del_options &o)
+{
+    return {o.min_depth, o.min_quality, {o.has_min_base_quality, o.min_base_quality, o.exclude_flags}, o.min_del_per_10k, o.min_del_count, o.min_del_per_strand};
+}
+
+// the range checks of a rule, written once
+bool rule_ok(const Rule &r, uint32_t min_depth, uint32_t count, uint32_t per_10k, char *err = nullptr, size_t err_len = 0)
+{
+    char b[96] = {0};
+    if (min_depth == 0) snprintf(b, sizeof(b), "min_depth must be at least 1");
+    else if (count == 0) snprintf(b, sizeof(b), "%s must be at least 1", r.count);
+    else if (per_10k < 1 || per_10k > r.max_per_10k) snprintf(b, sizeof(b), "%s must lie in 1..%u", r.per_10k, r.max_per_10k);
+    else return true;
+    set_err(err, err_len, b);
+    return false;
+}
+
+// the comment lines every scan's TSV opens with, down to ##positions; the two filter lines and the two lines of a rule
+// where the mode prints them
+void tsv_preamble(std::string &s, const char *contig, uint32_t start, uint32_t end, const ScanOptions &o, bool filter_lines, const Rule *rule)
+{
+    char b[512], q[8] = ".";
+    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n", contig, start, end, o.min_depth, (unsigned)o.min_quality);
+    s += b;
+    if (o.flt.has_min_base_quality) snprintf(q, sizeof(q), "%u", (unsigned)o.flt.min_base_quality);
+    snprintf(b, sizeof(b), "##min_base_quality=%s\n##exclude_flags=0x%04x\n", q, (unsigned)o.flt.exclude_flags);
+    if (filter_lines) s += b;
+    if (rule) { snprintf(b, sizeof(b), "##%s=%.4f\n##%s=%u\n", rule->fraction, (double)o.per_10k / 10000.0, rule->count, o.count); s += b; }
+    snprintf(b, sizeof(b), "##positions=%u\n", end - start);
+    s += b;
+}
+
 // opt: the extended TSV of dut_variants_write_ex (Res = cl_scan_result_ex); nullptr: the one of dut_variants_write
 template <class Res>
 int write_tsv(const char *path, const char *contig, const Res *res, uint32_t min_depth, uint8_t min_quality,
@@ -93,16 +139,9 @@ int write_tsv(const char *path, const char *contig, const Res *res, uint32_t min
     if (!path || !contig || !res || (res->n_variant && !res->candidates)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
     std::string s;
     char b[512];
-    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n", contig, res->start, res->end,
-             min_depth, (unsigned)min_quality);
-    s += b;
-    if (opt) {
-        if (opt->has_min_base_quality) snprintf(b, sizeof(b), "##min_base_quality=%u\n##exclude_flags=0x%04x\n", (unsigned)opt->min_base_quality, (unsigned)opt->exclude_flags);
-        else snprintf(b, sizeof(b), "##min_base_quality=.\n##exclude_flags=0x%04x\n", (unsigned)opt->exclude_flags);
-        s += b;
-    }
-    snprintf(b, sizeof(b), "##positions=%u\n", res->end - res->start);
-    s += b;
+    ScanOptions o = {min_depth, min_quality, {}, 0, 0, 0};
+    if (opt) o.flt = {opt->has_min_base_quality, opt->min_base_quality, opt->exclude_flags};
+    tsv_preamble(s, contig, res->start, res->end, o, opt != nullptr, nullptr);
     snprintf(b, sizeof(b), "##low_depth=%llu\n##mixed=%llu\n##uncomparable=%llu\n##match=%llu\n##variant=%llu\n",
              (unsigned long long)res->n_low_depth, (unsigned long long)res->n_mixed, (unsigned long long)res->n_uncomparable,
              (unsigned long long)res->n_match, (unsigned long long)res->n_variant);
@@ -185,14 +224,52 @@ int scan_files_upload(ScanFiles &F, const char *contig, int device_id, Side &&si
     return rc;
 }
 
-// the records' flags and, per base, qual >= min_base_quality (none: every base passes) onto the resident tile
-int scan_files_attach(ScanFiles &F, int has_min_base_quality, uint8_t min_base_quality, char *err, size_t err_len)
+// The tile of the opened files resident for a scan: scan_files_upload, then, for a filtered scan (flt), the attachment --
+// the records' flags and, per base, qual >= min_base_quality (none: every base passes) -- and the engine's filter in f
+template <class Side, class SideOk>
+int scan_files_resident(ScanFiles &F, const char *contig, int device_id, const FilterOptions *flt, cl_scan_filter &f, Side &&side, SideOk &&side_ok,
+                        char *err, size_t err_len)
 {
+    int rc = scan_files_upload(F, contig, device_id, side, side_ok, err, err_len);
+    if (rc != CL_OK || !flt) return rc;
     cl_site_quals q;
     q.n_reads = F.rec.n; q.flag = F.rec.flag; q.qual_off = F.rec.qual_off; q.qual = F.rec.qual; q.seq_off = F.seq_off;
-    const int rc = cl_site_attach_quals(F.ctx.get(), &q, has_min_base_quality ? min_base_quality : 0);
+    rc = cl_site_attach_quals(F.ctx.get(), &q, flt->has_min_base_quality ? flt->min_base_quality : 0);
     if (rc != CL_OK) F.engine_err(err, err_len, "site attachment failed");
+    f = {flt->exclude_flags, (uint8_t)(flt->has_min_base_quality ? 1 : 0), 0};
     return rc;
+}
+
+// The file-level scan of a rule: its options checked, then always the filtered form -- its strand planes give the
+// per-strand counts; with no mask and no threshold it counts what the unfiltered form does -- by the engine's scan of the
+// rule, and its TSV by write
+template <class Options, class Params, class Result>
+int rule_files_run(const Rule &rule, const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
+                   const Options *o, const char *output_path, int device_id,
+                   cl_status (*scan)(cl_ctx *, uint8_t, const cl_scan_filter *, const Params *, const uint8_t *, uint64_t, uint32_t, uint32_t, Result *),
+                   int (*write)(const char *, const char *, const Result *, const Options *, char *, size_t), char *err, size_t err_len)
+{
+    if (!bam_path || !fasta_path || !contig || !output_path || !o) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    const ScanOptions r = scan_options(*o);
+    if (!rule_ok(rule, r.min_depth, r.count, r.per_10k, err, err_len)) return CL_ERR_INVALID;
+    ScanFiles F;
+    cl_scan_filter f;
+    int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
+    if (rc != CL_OK) return rc;
+    if ((rc = scan_files_resident(F, contig, device_id, &r.flt, f, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
+    const Params prm = {r.min_depth, r.count, r.per_10k};
+    Result res;
+    rc = scan(F.ctx.get(), r.min_quality, &f, &prm, F.bases, F.blen, start, end, &res);
+    if (rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return rc; }
+    return write(output_path, contig, &res, o, err, err_len);
+}
+
+// no exception leaves the library through the C ABI
+template <class F> int no_throw(char *err, size_t err_len, F &&f)
+{
+    try { return f(); }
+    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
+    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
 }
 
 } // namespace
@@ -259,14 +336,9 @@ int dut_del_fraction_parse(const char *text, uint32_t *per_10k, char *err, size_
     return fraction_parse(text, per_10k, 10000, "(0, 1]", err, err_len);
 }
 
-static bool del_params_ok(const cl_del_params *p)
-{
-    return p && p->min_depth != 0 && p->min_del_count != 0 && p->min_del_per_10k >= 1 && p->min_del_per_10k <= 10000;
-}
-
 int dut_del_classify_counts(uint32_t del, uint32_t depth, const cl_del_params *params)
 {
-    if (!del_params_ok(params)) return CL_ERR_INVALID;
+    if (!params || !rule_ok(DEL_RULE, params->min_depth, params->min_del_count, params->min_del_per_10k)) return CL_ERR_INVALID;
     const uint64_t span = (uint64_t)del + depth;
     if (span < params->min_depth) return DUT_DEL_LOW_DEPTH;
     return (del >= params->min_del_count && 10000ull * del >= (uint64_t)params->min_del_per_10k * span) ? DUT_DEL_DELETED : DUT_DEL_KEPT;
@@ -320,15 +392,7 @@ static int del_write(const char *path, const char *contig, const cl_del_result *
     if (del_events(res->candidates, (size_t)res->n_deleted, ev) != CL_OK) { set_err(err, err_len, "candidate positions must ascend"); return CL_ERR_INVALID; }
     std::string s;
     char b[512];
-    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n", contig, res->start, res->end, opt->min_depth,
-             (unsigned)opt->min_quality);
-    s += b;
-    if (opt->has_min_base_quality) snprintf(b, sizeof(b), "##min_base_quality=%u\n", (unsigned)opt->min_base_quality);
-    else snprintf(b, sizeof(b), "##min_base_quality=.\n");
-    s += b;
-    snprintf(b, sizeof(b), "##exclude_flags=0x%04x\n##min_del_fraction=%.4f\n##min_del_count=%u\n##positions=%u\n", (unsigned)opt->exclude_flags,
-             (double)opt->min_del_per_10k / 10000.0, opt->min_del_count, res->end - res->start);
-    s += b;
+    tsv_preamble(s, contig, res->start, res->end, scan_options(*opt), true, &DEL_RULE);
     snprintf(b, sizeof(b), "##low_depth=%llu\n##kept=%llu\n##deleted=%llu\n##events=%llu\n", (unsigned long long)res->n_low_depth,
              (unsigned long long)res->n_kept, (unsigned long long)res->n_deleted, (unsigned long long)ev.size());
     s += b;
@@ -357,7 +421,7 @@ int dut_minor_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, ui
 {
     if (major) *major = 0;
     if (minor) *minor = 0;
-    if (!params || params->min_depth == 0 || params->min_minor_count == 0 || params->min_minor_per_10k < 1 || params->min_minor_per_10k > 5000) return CL_ERR_INVALID;
+    if (!params || !rule_ok(MINOR_RULE, params->min_depth, params->min_minor_count, params->min_minor_per_10k)) return CL_ERR_INVALID;
     if ((uint64_t)a + c + g + t > depth || depth > 0xFFFFFFFFull) return CL_ERR_INVALID;
     const uint32_t cnt[4] = {a, c, g, t};
     int mi = 0;
@@ -376,15 +440,7 @@ int dut_minor_write(const char *path, const char *contig, const cl_minor_result 
     if (!path || !contig || !res || !opt || (res->n_minor && !res->candidates)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
     std::string s;
     char b[512];
-    snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##min_depth=%u\n##min_quality=%u\n", contig, res->start, res->end, opt->min_depth,
-             (unsigned)opt->min_quality);
-    s += b;
-    if (opt->has_min_base_quality) snprintf(b, sizeof(b), "##min_base_quality=%u\n", (unsigned)opt->min_base_quality);
-    else snprintf(b, sizeof(b), "##min_base_quality=.\n");
-    s += b;
-    snprintf(b, sizeof(b), "##exclude_flags=0x%04x\n##min_minor_fraction=%.4f\n##min_minor_count=%u\n##positions=%u\n", (unsigned)opt->exclude_flags,
-             (double)opt->min_minor_per_10k / 10000.0, opt->min_minor_count, res->end - res->start);
-    s += b;
+    tsv_preamble(s, contig, res->start, res->end, scan_options(*opt), true, &MINOR_RULE);
     snprintf(b, sizeof(b), "##low_depth=%llu\n##single=%llu\n##minor=%llu\n", (unsigned long long)res->n_low_depth,
              (unsigned long long)res->n_single, (unsigned long long)res->n_minor);
     s += b;
@@ -434,131 +490,70 @@ int dut_variants_write_ex(const char *path, const char *contig, const cl_scan_re
     return write_tsv(path, contig, res, min_depth, min_quality, opt, notes, err, err_len);
 }
 
-static int dut_find_variants_files_impl(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
-                                        uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
-                                        const char *output_path, uint32_t min_depth, uint8_t min_quality,
-                                        const dut_variants_options *vopt, int device_id, char *err, size_t err_len)
-{
-    if (!bam_path || !fasta_path || !contig || !output_path) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
-    if (min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
-    ScanFiles F;
-    int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
-    if (rc != CL_OK) return rc;
-    // the build id the tree's coordinates are looked up by (mod.rs:51-54): the genome the header names, rCRS for mt
-    std::string build;
-    if (tree_json_path) {
-        size_t tl = 0;
-        const char *text = dut_bam_header_text(F.bam.get(), &tl);
-        build = dut_reference_build(text, tl);
-        if (build == "Unknown") { set_err(err, err_len, "Could not determine reference genome from BAM header"); return CL_ERR_INVALID; }
-        if (tree_type == DUT_TREE_MTDNA) build = "rCRS";
-    }
-    // side by side, as dut_find_branch_files does: the tree JSON, the HIP runtime + context, the contig's records
-    std::unique_ptr<dut_tree, decltype(&dut_tree_free)> tree(nullptr, dut_tree_free);
-    char terr[512] = {0};
-    rc = scan_files_upload(F, contig, device_id,
-                           [&]() { if (tree_json_path) tree.reset(dut_tree_load(tree_json_path, provider, tree_type, terr, sizeof(terr))); },
-                           [&]() { if (tree_json_path && !tree) { set_err(err, err_len, terr); return false; } return true; }, err, err_len);
-    if (rc != CL_OK) return rc;
-    // scan result -> annotation -> TSV, for either result type (wopt: the filter columns of the header, or none)
-    auto finish = [&](int scan_rc, const auto &res, const dut_variants_options *wopt) {
-        if (scan_rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return scan_rc; }
-        dut_variant_note *notes = nullptr;
-        if (tree) {
-            const int arc = annotate(tree.get(), build.c_str(), contig, res.candidates, (size_t)res.n_variant, &notes);
-            if (arc != CL_OK) { set_err(err, err_len, "annotation failed"); return arc; }
-        }
-        const int wrc = write_tsv(output_path, contig, &res, min_depth, min_quality, wopt, notes, err, err_len);
-        dut_variants_free_notes(notes, (size_t)res.n_variant);
-        return wrc;
-    };
-    if (vopt && vopt->filtered) {
-        if ((rc = scan_files_attach(F, vopt->has_min_base_quality, vopt->min_base_quality, err, err_len)) != CL_OK) return rc;
-        const cl_scan_filter flt = {vopt->exclude_flags, (uint8_t)(vopt->has_min_base_quality ? 1 : 0), 0};
-        cl_scan_result_ex res;
-        return finish(cl_site_scan_ex(F.ctx.get(), min_quality, min_depth, &flt, F.bases, F.blen, start, end, &res), res, vopt);
-    }
-    cl_scan_result res;
-    return finish(cl_site_scan(F.ctx.get(), min_quality, min_depth, F.bases, F.blen, start, end, &res), res, nullptr);
-}
-
-static int minor_options_check(const dut_minor_options *o, char *err, size_t err_len)
-{
-    if (!o) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
-    if (o->min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
-    if (o->min_minor_count == 0) { set_err(err, err_len, "min_minor_count must be at least 1"); return CL_ERR_INVALID; }
-    if (o->min_minor_per_10k < 1 || o->min_minor_per_10k > 5000) { set_err(err, err_len, "min_minor_per_10k must lie in 1..5000"); return CL_ERR_INVALID; }
-    return CL_OK;
-}
-
-static int dut_find_minor_files_impl(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
-                                     uint32_t end, const dut_minor_options *o, const char *output_path, int device_id, char *err, size_t err_len)
-{
-    if (!bam_path || !fasta_path || !contig || !output_path) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
-    int rc = minor_options_check(o, err, err_len);
-    if (rc != CL_OK) return rc;
-    ScanFiles F;
-    if ((rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len)) != CL_OK) return rc;
-    if ((rc = scan_files_upload(F, contig, device_id, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
-    // always the filtered form: its strand planes give the per-strand counts; with no mask and no threshold it counts
-    // what the unfiltered form does
-    if ((rc = scan_files_attach(F, o->has_min_base_quality, o->min_base_quality, err, err_len)) != CL_OK) return rc;
-    const cl_scan_filter flt = {o->exclude_flags, (uint8_t)(o->has_min_base_quality ? 1 : 0), 0};
-    const cl_minor_params prm = {o->min_depth, o->min_minor_count, o->min_minor_per_10k};
-    cl_minor_result res;
-    rc = cl_site_scan_minor(F.ctx.get(), o->min_quality, &flt, &prm, F.bases, F.blen, start, end, &res);
-    if (rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return rc; }
-    return dut_minor_write(output_path, contig, &res, o, err, err_len);
-}
-
 int dut_find_variants_files_ex(const char *bam_path, const char *fasta_path, const char *contig, int has_region,
                                uint32_t start, uint32_t end, const char *tree_json_path, int provider, int tree_type,
                                const char *output_path, uint32_t min_depth, uint8_t min_quality,
-                               const dut_variants_options *opt, int device_id, char *err, size_t err_len)
+                               const dut_variants_options *vopt, int device_id, char *err, size_t err_len)
 {
-    // no exception leaves the library through the C ABI
-    try { return dut_find_variants_files_impl(bam_path, fasta_path, contig, has_region, start, end, tree_json_path, provider, tree_type,
-                                               output_path, min_depth, min_quality, opt, device_id, err, err_len); }
-    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
-    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
-}
-
-static int dut_find_deletions_files_impl(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
-                                         uint32_t end, const dut_del_options *o, const char *output_path, int device_id, char *err, size_t err_len)
-{
-    if (!bam_path || !fasta_path || !contig || !output_path || !o) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
-    if (o->min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
-    if (o->min_del_count == 0) { set_err(err, err_len, "min_del_count must be at least 1"); return CL_ERR_INVALID; }
-    if (o->min_del_per_10k < 1 || o->min_del_per_10k > 10000) { set_err(err, err_len, "min_del_per_10k must lie in 1..10000"); return CL_ERR_INVALID; }
-    ScanFiles F;
-    int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
-    if (rc != CL_OK) return rc;
-    if ((rc = scan_files_upload(F, contig, device_id, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
-    // always the filtered form: its strand planes give the per-strand counts; with no mask and no threshold it counts
-    // what the unfiltered form does
-    if ((rc = scan_files_attach(F, o->has_min_base_quality, o->min_base_quality, err, err_len)) != CL_OK) return rc;
-    const cl_scan_filter flt = {o->exclude_flags, (uint8_t)(o->has_min_base_quality ? 1 : 0), 0};
-    const cl_del_params prm = {o->min_depth, o->min_del_count, o->min_del_per_10k};
-    cl_del_result res;
-    rc = cl_site_scan_dels(F.ctx.get(), o->min_quality, &flt, &prm, F.bases, F.blen, start, end, &res);
-    if (rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return rc; }
-    return dut_del_write(output_path, contig, &res, o, err, err_len);
+    return no_throw(err, err_len, [&]() -> int {
+        if (!bam_path || !fasta_path || !contig || !output_path) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (min_depth == 0) { set_err(err, err_len, "min_depth must be at least 1"); return CL_ERR_INVALID; }
+        ScanFiles F;
+        int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
+        if (rc != CL_OK) return rc;
+        // the build id the tree's coordinates are looked up by (mod.rs:51-54): the genome the header names, rCRS for mt
+        std::string build;
+        if (tree_json_path) {
+            size_t tl = 0;
+            const char *text = dut_bam_header_text(F.bam.get(), &tl);
+            build = dut_reference_build(text, tl);
+            if (build == "Unknown") { set_err(err, err_len, "Could not determine reference genome from BAM header"); return CL_ERR_INVALID; }
+            if (tree_type == DUT_TREE_MTDNA) build = "rCRS";
+        }
+        // side by side, as dut_find_branch_files does: the tree JSON, the HIP runtime + context, the contig's records
+        std::unique_ptr<dut_tree, decltype(&dut_tree_free)> tree(nullptr, dut_tree_free);
+        char terr[512] = {0};
+        const bool filtered = vopt && vopt->filtered;
+        FilterOptions flt{};
+        if (filtered) flt = {vopt->has_min_base_quality, vopt->min_base_quality, vopt->exclude_flags};
+        cl_scan_filter f;
+        rc = scan_files_resident(F, contig, device_id, filtered ? &flt : nullptr, f,
+                                 [&]() { if (tree_json_path) tree.reset(dut_tree_load(tree_json_path, provider, tree_type, terr, sizeof(terr))); },
+                                 [&]() { if (tree_json_path && !tree) { set_err(err, err_len, terr); return false; } return true; }, err, err_len);
+        if (rc != CL_OK) return rc;
+        // scan result -> annotation -> TSV, for either result type (wopt: the filter columns of the header, or none)
+        auto finish = [&](int scan_rc, const auto &res, const dut_variants_options *wopt) {
+            if (scan_rc != CL_OK) { F.engine_err(err, err_len, "site scan failed"); return scan_rc; }
+            dut_variant_note *notes = nullptr;
+            if (tree) {
+                const int arc = annotate(tree.get(), build.c_str(), contig, res.candidates, (size_t)res.n_variant, &notes);
+                if (arc != CL_OK) { set_err(err, err_len, "annotation failed"); return arc; }
+            }
+            const int wrc = write_tsv(output_path, contig, &res, min_depth, min_quality, wopt, notes, err, err_len);
+            dut_variants_free_notes(notes, (size_t)res.n_variant);
+            return wrc;
+        };
+        if (filtered) {
+            cl_scan_result_ex res;
+            return finish(cl_site_scan_ex(F.ctx.get(), min_quality, min_depth, &f, F.bases, F.blen, start, end, &res), res, vopt);
+        }
+        cl_scan_result res;
+        return finish(cl_site_scan(F.ctx.get(), min_quality, min_depth, F.bases, F.blen, start, end, &res), res, nullptr);
+    });
 }
 
 int dut_find_deletions_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
                              const dut_del_options *opt, const char *output_path, int device_id, char *err, size_t err_len)
 {
-    try { return dut_find_deletions_files_impl(bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id, err, err_len); }
-    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
-    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+    return no_throw(err, err_len, [&] { return rule_files_run(DEL_RULE, bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id,
+                                                              cl_site_scan_dels, dut_del_write, err, err_len); });
 }
 
 int dut_find_minor_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
                          const dut_minor_options *opt, const char *output_path, int device_id, char *err, size_t err_len)
 {
-    try { return dut_find_minor_files_impl(bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id, err, err_len); }
-    catch (const std::bad_alloc &) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
-    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_INVALID; }
+    return no_throw(err, err_len, [&] { return rule_files_run(MINOR_RULE, bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id,
+                                                              cl_site_scan_minor, dut_minor_write, err, err_len); });
 }
 
 int dut_find_variants_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region,

@@ -61,48 +61,80 @@ def annotate_variants(tree: HaplogroupTree, build_id: str, chromosome: str, cand
         lib.dut_variants_free_notes(notes, cand.shape[0])
 
 
-def write_variants(path: str, contig: str, result: ScanResult, min_depth: int, min_quality: int,
-                   tree: Optional[HaplogroupTree] = None, build_id: Optional[str] = None):
-    """The TSV of find-variants for a ScanResult; with a tree (and its build id) the candidates are annotated."""
-    lib = _lib.load()
-    cand = _candidates(result.candidates)
-    if cand.shape[0] != result.variant:
-        raise ValueError("variant count and candidates disagree")
-    r = _lib.cl_scan_result()
+def _call(fn, *args, size=512):
+    """fn(*args, err, size) of the library; an EngineError with its message unless it answers 0."""
+    err = C.create_string_buffer(size)
+    st = fn(*args, err, size)
+    if st != 0:
+        raise EngineError(st, err.value.decode())
+
+
+def _c_result(ctype, cand_ctype, dtype, result, what, **counts):
+    """(the C result struct of `result` with its n_* counts, the candidates as a contiguous array that it points to)."""
+    cand = np.ascontiguousarray(result.candidates, dtype).reshape(-1)
+    if cand.shape[0] != getattr(result, what):
+        raise ValueError(f"{what} count and candidates disagree")
+    r = ctype()
     r.start, r.end = result.start, result.end
-    r.n_low_depth, r.n_mixed, r.n_uncomparable, r.n_match, r.n_variant = (result.low_depth, result.mixed, result.uncomparable,
-                                                                          result.match, result.variant)
-    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_scan_candidate))
+    for name, v in counts.items():
+        setattr(r, name, v)
+    r.candidates = C.cast(cand.ctypes.data, C.POINTER(cand_ctype))
+    return r, cand
+
+
+def _find_files(fn, bam_file, reference_file, contig, region, *rest):
+    """A dut_find_*_files: the paths, the region as (has_region, start, end), then `rest`."""
+    start, end = region if region is not None else (0, 0)
+    _call(fn, bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0, int(start), int(end), *rest, size=1024)
+
+
+def _scan_result(ctype, cand_ctype, dtype, result):
+    return _c_result(ctype, cand_ctype, dtype, result, "variant", n_low_depth=result.low_depth, n_mixed=result.mixed,
+                     n_uncomparable=result.uncomparable, n_match=result.match, n_variant=result.variant)
+
+
+def _write_variants(writer, annotate, r, cand, path, contig, args, tree, build_id):
+    """The TSV of the C result r over cand by `writer`, annotated by `annotate` when there is a tree."""
+    lib = _lib.load()
     notes = C.POINTER(_lib.dut_variant_note)()
-    err = C.create_string_buffer(512)
     if tree is not None:
         if not build_id:
             raise ValueError("a tree needs its build id")
-        st = lib.dut_variants_annotate(tree._h, build_id.encode(), contig.encode(), cand.ctypes.data, cand.shape[0], C.byref(notes))
+        st = annotate(tree._h, build_id.encode(), contig.encode(), cand.ctypes.data, cand.shape[0], C.byref(notes))
         if st != 0:
             raise EngineError(st, "annotation failed")
     try:
-        st = lib.dut_variants_write(path.encode(), contig.encode(), C.byref(r), int(min_depth), int(min_quality),
-                                    notes if tree is not None else None, err, 512)
-        if st != 0:
-            raise EngineError(st, err.value.decode())
+        _call(writer, path.encode(), contig.encode(), C.byref(r), *args, notes if tree is not None else None)
     finally:
         if tree is not None:
             lib.dut_variants_free_notes(notes, cand.shape[0])
 
 
-def _options(min_base_quality, exclude_flags, min_alt_per_strand) -> "_lib.dut_variants_options":
+def write_variants(path: str, contig: str, result: ScanResult, min_depth: int, min_quality: int,
+                   tree: Optional[HaplogroupTree] = None, build_id: Optional[str] = None):
+    """The TSV of find-variants for a ScanResult; with a tree (and its build id) the candidates are annotated."""
+    lib = _lib.load()
+    r, cand = _scan_result(_lib.cl_scan_result, _lib.cl_scan_candidate, SCAN_CANDIDATE, result)
+    _write_variants(lib.dut_variants_write, lib.dut_variants_annotate, r, cand, path, contig, (int(min_depth), int(min_quality)), tree, build_id)
+
+
+def _filter_options(o, min_base_quality, exclude_flags):
+    """The filter fields every options struct has, checked and set."""
     if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
         raise ValueError("min_base_quality: 0..255")
     if not 0 <= int(exclude_flags) <= 0xFFFF:
         raise ValueError("exclude_flags: 0..65535")
-    if not 0 <= int(min_alt_per_strand) <= 0xFFFFFFFF:
-        raise ValueError("min_alt_per_strand: 0..2^32-1")
-    o = _lib.dut_variants_options()
-    o.filtered = 1
     o.has_min_base_quality = 0 if min_base_quality is None else 1
     o.min_base_quality = 0 if min_base_quality is None else int(min_base_quality)
     o.exclude_flags = int(exclude_flags)
+    return o
+
+
+def _options(min_base_quality, exclude_flags, min_alt_per_strand) -> "_lib.dut_variants_options":
+    o = _filter_options(_lib.dut_variants_options(), min_base_quality, exclude_flags)
+    if not 0 <= int(min_alt_per_strand) <= 0xFFFFFFFF:
+        raise ValueError("min_alt_per_strand: 0..2^32-1")
+    o.filtered = 1
     o.min_alt_per_strand = int(min_alt_per_strand)
     return o
 
@@ -113,31 +145,10 @@ def write_variants_ex(path: str, contig: str, result: ScanResult, min_depth: int
     """The extended TSV (dut_variants_write_ex) for the ScanResult of Engine.site_scan_ex: per-strand counts and the
     strand filter; min_base_quality=None prints '.'.  No device is needed."""
     lib = _lib.load()
-    cand = np.ascontiguousarray(result.candidates, SCAN_CANDIDATE_EX).reshape(-1)
-    if cand.shape[0] != result.variant:
-        raise ValueError("variant count and candidates disagree")
+    r, cand = _scan_result(_lib.cl_scan_result_ex, _lib.cl_scan_candidate_ex, SCAN_CANDIDATE_EX, result)
     opt = _options(min_base_quality, exclude_flags, min_alt_per_strand)
-    r = _lib.cl_scan_result_ex()
-    r.start, r.end = result.start, result.end
-    r.n_low_depth, r.n_mixed, r.n_uncomparable, r.n_match, r.n_variant = (result.low_depth, result.mixed, result.uncomparable,
-                                                                          result.match, result.variant)
-    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_scan_candidate_ex))
-    notes = C.POINTER(_lib.dut_variant_note)()
-    err = C.create_string_buffer(512)
-    if tree is not None:
-        if not build_id:
-            raise ValueError("a tree needs its build id")
-        st = lib.dut_variants_annotate_ex(tree._h, build_id.encode(), contig.encode(), cand.ctypes.data, cand.shape[0], C.byref(notes))
-        if st != 0:
-            raise EngineError(st, "annotation failed")
-    try:
-        st = lib.dut_variants_write_ex(path.encode(), contig.encode(), C.byref(r), int(min_depth), int(min_quality), C.byref(opt),
-                                       notes if tree is not None else None, err, 512)
-        if st != 0:
-            raise EngineError(st, err.value.decode())
-    finally:
-        if tree is not None:
-            lib.dut_variants_free_notes(notes, cand.shape[0])
+    _write_variants(lib.dut_variants_write_ex, lib.dut_variants_annotate_ex, r, cand, path, contig, (int(min_depth), int(min_quality), C.byref(opt)),
+                    tree, build_id)
 
 
 def find_variants(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
@@ -147,27 +158,25 @@ def find_variants(bam_file: str, reference_file: str, contig: str, output_file: 
     """dut_find_variants_files(_ex): BAM (+ index) and FASTA in, the TSV out; region = (start, end), 0-based half open.
     With min_base_quality, exclude_flags or min_alt_per_strand the scan is the filtered, strand-aware one and the TSV the
     extended one; with none of them nothing changes."""
-    lib = _lib.load()
-    err = C.create_string_buffer(1024)
-    start, end = region if region is not None else (0, 0)
     opt = None
     if min_base_quality is not None or exclude_flags or min_alt_per_strand:
         opt = C.byref(_options(min_base_quality, exclude_flags, min_alt_per_strand))
-    st = lib.dut_find_variants_files_ex(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
-                                        int(start), int(end), tree_json.encode() if tree_json else None, provider, tree_type,
-                                        output_file.encode(), int(min_depth), int(min_quality), opt, device_id, err, 1024)
+    _find_files(_lib.load().dut_find_variants_files_ex, bam_file, reference_file, contig, region, tree_json.encode() if tree_json else None, provider,
+                tree_type, output_file.encode(), int(min_depth), int(min_quality), opt, device_id)
+
+
+def _fraction_parse(fn, text: str) -> int:
+    v = C.c_uint32()
+    err = C.create_string_buffer(256)
+    st = fn(text.encode(), C.byref(v), err, 256)
     if st != 0:
-        raise EngineError(st, err.value.decode())
+        raise ValueError(f"invalid fraction '{text}': {err.value.decode()}")
+    return int(v.value)
 
 
 def minor_fraction_parse(text: str) -> int:
     """dut_minor_fraction_parse: decimal text in (0, 0.5] with at most four decimals to parts per 10 000, exactly."""
-    v = C.c_uint32()
-    err = C.create_string_buffer(256)
-    st = _lib.load().dut_minor_fraction_parse(text.encode(), C.byref(v), err, 256)
-    if st != 0:
-        raise ValueError(f"invalid fraction '{text}': {err.value.decode()}")
-    return int(v.value)
+    return _fraction_parse(_lib.load().dut_minor_fraction_parse, text)
 
 
 def minor_classify_counts(a, c, g, t, depth, min_depth, min_minor_count, min_minor_per_10k) -> Tuple[int, str, str]:
@@ -180,42 +189,28 @@ def minor_classify_counts(a, c, g, t, depth, min_depth, min_minor_count, min_min
     return st, major.value.decode(), minor.value.decode()
 
 
-def _minor_options(min_depth, min_quality, min_minor_count, min_minor_per_10k, min_base_quality, exclude_flags,
-                   min_minor_per_strand) -> "_lib.dut_minor_options":
-    if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
-        raise ValueError("min_base_quality: 0..255")
-    if not 0 <= int(exclude_flags) <= 0xFFFF:
-        raise ValueError("exclude_flags: 0..65535")
+def _rule_options(stem, min_depth, min_quality, count, per_10k, min_base_quality, exclude_flags, per_strand):
+    """dut_minor_options (stem "minor") or dut_del_options ("del"): the same members under the rule's names."""
+    o = _filter_options(getattr(_lib, f"dut_{stem}_options")(), min_base_quality, exclude_flags)
     if not 0 <= int(min_quality) <= 255:
         raise ValueError("min_quality: 0..255")
-    for name, v in (("min_depth", min_depth), ("min_minor_count", min_minor_count), ("min_minor_per_10k", min_minor_per_10k),
-                    ("min_minor_per_strand", min_minor_per_strand)):
+    own = {f"min_{stem}_count": count, f"min_{stem}_per_10k": per_10k, f"min_{stem}_per_strand": per_strand}
+    for name, v in (("min_depth", min_depth), *own.items()):
         if not 0 <= int(v) <= 0xFFFFFFFF:
             raise ValueError(f"{name}: 0..2^32-1")
-    o = _lib.dut_minor_options()
     o.min_depth, o.min_quality = int(min_depth), int(min_quality)
-    o.has_min_base_quality = 0 if min_base_quality is None else 1
-    o.min_base_quality = 0 if min_base_quality is None else int(min_base_quality)
-    o.exclude_flags = int(exclude_flags)
-    o.min_minor_per_10k, o.min_minor_count, o.min_minor_per_strand = int(min_minor_per_10k), int(min_minor_count), int(min_minor_per_strand)
+    for name, v in own.items():
+        setattr(o, name, int(v))
     return o
 
 
 def write_minor(path: str, contig: str, result: MinorResult, min_depth: int, min_quality: int, min_minor_count: int,
                 min_minor_per_10k: int, min_base_quality=None, exclude_flags: int = 0, min_minor_per_strand: int = 0):
     """The TSV of find-minor-alleles (dut_minor_write) for the MinorResult of Engine.site_scan_minor.  No device is needed."""
-    cand = np.ascontiguousarray(result.candidates, MINOR_CANDIDATE).reshape(-1)
-    if cand.shape[0] != result.minor:
-        raise ValueError("minor count and candidates disagree")
-    opt = _minor_options(min_depth, min_quality, min_minor_count, min_minor_per_10k, min_base_quality, exclude_flags, min_minor_per_strand)
-    r = _lib.cl_minor_result()
-    r.start, r.end = result.start, result.end
-    r.n_low_depth, r.n_single, r.n_minor = result.low_depth, result.single, result.minor
-    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_minor_candidate))
-    err = C.create_string_buffer(512)
-    st = _lib.load().dut_minor_write(path.encode(), contig.encode(), C.byref(r), C.byref(opt), err, 512)
-    if st != 0:
-        raise EngineError(st, err.value.decode())
+    r, _cand = _c_result(_lib.cl_minor_result, _lib.cl_minor_candidate, MINOR_CANDIDATE, result, "minor", n_low_depth=result.low_depth,
+                         n_single=result.single, n_minor=result.minor)
+    opt = _rule_options("minor", min_depth, min_quality, min_minor_count, min_minor_per_10k, min_base_quality, exclude_flags, min_minor_per_strand)
+    _call(_lib.load().dut_minor_write, path.encode(), contig.encode(), C.byref(r), C.byref(opt))
 
 
 def find_minor_alleles(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
@@ -224,23 +219,13 @@ def find_minor_alleles(bam_file: str, reference_file: str, contig: str, output_f
     """dut_find_minor_files: BAM (+ index) and FASTA in, the TSV of second alleles out; region = (start, end), 0-based half
     open.  min_minor_fraction: decimal text (or a number whose text is one) in (0, 0.5], at most four decimals."""
     per_10k = minor_fraction_parse(str(min_minor_fraction))
-    opt = _minor_options(min_depth, min_quality, min_minor_count, per_10k, min_base_quality, exclude_flags, min_minor_per_strand)
-    err = C.create_string_buffer(1024)
-    start, end = region if region is not None else (0, 0)
-    st = _lib.load().dut_find_minor_files(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
-                                          int(start), int(end), C.byref(opt), output_file.encode(), device_id, err, 1024)
-    if st != 0:
-        raise EngineError(st, err.value.decode())
+    opt = _rule_options("minor", min_depth, min_quality, min_minor_count, per_10k, min_base_quality, exclude_flags, min_minor_per_strand)
+    _find_files(_lib.load().dut_find_minor_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(), device_id)
 
 
 def del_fraction_parse(text: str) -> int:
     """dut_del_fraction_parse: decimal text in (0, 1] with at most four decimals to parts per 10 000, exactly."""
-    v = C.c_uint32()
-    err = C.create_string_buffer(256)
-    st = _lib.load().dut_del_fraction_parse(text.encode(), C.byref(v), err, 256)
-    if st != 0:
-        raise ValueError(f"invalid fraction '{text}': {err.value.decode()}")
-    return int(v.value)
+    return _fraction_parse(_lib.load().dut_del_fraction_parse, text)
 
 
 def del_classify_counts(n_del, depth, min_depth, min_del_count, min_del_per_10k) -> int:
@@ -270,42 +255,13 @@ def del_events(candidates) -> List[dict]:
         lib.dut_del_events_free(ev)
 
 
-def _del_options(min_depth, min_quality, min_del_count, min_del_per_10k, min_base_quality, exclude_flags,
-                 min_del_per_strand) -> "_lib.dut_del_options":
-    if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
-        raise ValueError("min_base_quality: 0..255")
-    if not 0 <= int(exclude_flags) <= 0xFFFF:
-        raise ValueError("exclude_flags: 0..65535")
-    if not 0 <= int(min_quality) <= 255:
-        raise ValueError("min_quality: 0..255")
-    for name, v in (("min_depth", min_depth), ("min_del_count", min_del_count), ("min_del_per_10k", min_del_per_10k),
-                    ("min_del_per_strand", min_del_per_strand)):
-        if not 0 <= int(v) <= 0xFFFFFFFF:
-            raise ValueError(f"{name}: 0..2^32-1")
-    o = _lib.dut_del_options()
-    o.min_depth, o.min_quality = int(min_depth), int(min_quality)
-    o.has_min_base_quality = 0 if min_base_quality is None else 1
-    o.min_base_quality = 0 if min_base_quality is None else int(min_base_quality)
-    o.exclude_flags = int(exclude_flags)
-    o.min_del_per_10k, o.min_del_count, o.min_del_per_strand = int(min_del_per_10k), int(min_del_count), int(min_del_per_strand)
-    return o
-
-
 def write_deletions(path: str, contig: str, result: DelResult, min_depth: int, min_quality: int, min_del_count: int,
                     min_del_per_10k: int, min_base_quality=None, exclude_flags: int = 0, min_del_per_strand: int = 0):
     """The TSV of find-deletions (dut_del_write) for the DelResult of Engine.site_scan_dels.  No device is needed."""
-    cand = np.ascontiguousarray(result.candidates, DEL_CANDIDATE).reshape(-1)
-    if cand.shape[0] != result.deleted:
-        raise ValueError("deleted count and candidates disagree")
-    opt = _del_options(min_depth, min_quality, min_del_count, min_del_per_10k, min_base_quality, exclude_flags, min_del_per_strand)
-    r = _lib.cl_del_result()
-    r.start, r.end = result.start, result.end
-    r.n_low_depth, r.n_kept, r.n_deleted = result.low_depth, result.kept, result.deleted
-    r.candidates = C.cast(cand.ctypes.data, C.POINTER(_lib.cl_del_candidate))
-    err = C.create_string_buffer(512)
-    st = _lib.load().dut_del_write(path.encode(), contig.encode(), C.byref(r), C.byref(opt), err, 512)
-    if st != 0:
-        raise EngineError(st, err.value.decode())
+    r, _cand = _c_result(_lib.cl_del_result, _lib.cl_del_candidate, DEL_CANDIDATE, result, "deleted", n_low_depth=result.low_depth,
+                         n_kept=result.kept, n_deleted=result.deleted)
+    opt = _rule_options("del", min_depth, min_quality, min_del_count, min_del_per_10k, min_base_quality, exclude_flags, min_del_per_strand)
+    _call(_lib.load().dut_del_write, path.encode(), contig.encode(), C.byref(r), C.byref(opt))
 
 
 def find_deletions(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
@@ -314,10 +270,5 @@ def find_deletions(bam_file: str, reference_file: str, contig: str, output_file:
     """dut_find_deletions_files: BAM (+ index) and FASTA in, the TSV of deletion events out; region = (start, end), 0-based
     half open.  min_del_fraction: decimal text (or a number whose text is one) in (0, 1], at most four decimals."""
     per_10k = del_fraction_parse(str(min_del_fraction))
-    opt = _del_options(min_depth, min_quality, min_del_count, per_10k, min_base_quality, exclude_flags, min_del_per_strand)
-    err = C.create_string_buffer(1024)
-    start, end = region if region is not None else (0, 0)
-    st = _lib.load().dut_find_deletions_files(bam_file.encode(), reference_file.encode(), contig.encode(), 1 if region is not None else 0,
-                                              int(start), int(end), C.byref(opt), output_file.encode(), device_id, err, 1024)
-    if st != 0:
-        raise EngineError(st, err.value.decode())
+    opt = _rule_options("del", min_depth, min_quality, min_del_count, per_10k, min_base_quality, exclude_flags, min_del_per_strand)
+    _find_files(_lib.load().dut_find_deletions_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(), device_id)

@@ -413,7 +413,11 @@ def test_del_scan_invariants_and_interleaving():
         same_dels(plain, D.reduce(*D.walk(L, L, rec, 20), ref, L, 10, 3, 7000, 0, L, stranded=False), "plain")
         ms, nbytes = eng.site_scan_stats()
         assert ms > 0 and nbytes > 20 * rec.n + 32 * every_plain.deleted
-        # the other calls after: the same results
+        # the other calls after: the same results, and the deletion scan's own candidate array stays as it is across them
+        r4, dprm = _lib.cl_del_result(), _lib.cl_del_params(10, 3, 7000)
+        assert lib.cl_site_scan_dels(h, 20, C.byref(f704), C.byref(dprm), refp, L, 0, L, C.byref(r4)) == 0
+        keep_del = C.string_at(r4.candidates, int(r4.n_deleted) * 32)
+        assert int(r4.n_deleted) == on.deleted and keep_del == on.candidates.tobytes()
         assert np.array_equal(eng.site_run(20, sites), run0)
         scan1, ex1 = eng.site_scan(20, 10, ref), eng.site_scan_ex(20, 10, ref, 0x704, True)
         for x, y in ((scan0, scan1), (ex0, ex1)):
@@ -421,6 +425,7 @@ def test_del_scan_invariants_and_interleaving():
             assert np.array_equal(x.candidates, y.candidates)
         minor1 = eng.site_scan_minor(20, 10, 3, 500, ref, filter=(0x704, True))
         assert (minor0.low_depth, minor0.single, minor0.minor) == (minor1.low_depth, minor1.single, minor1.minor) and np.array_equal(minor0.candidates, minor1.candidates)
+        assert keep_del == C.string_at(r4.candidates, int(r4.n_deleted) * 32)
         assert np.array_equal(eng.site_scan_counts_ex(20, 0, L, 0x704, True), c9) and np.array_equal(eng.site_scan_counts(20, 0, L), c5)
         again = eng.site_scan_dels(20, 10, 3, 7000, ref, filter=(0x704, True))
         assert np.array_equal(again.candidates, on.candidates)
