@@ -215,6 +215,36 @@ class cl_del_result(C.Structure):
                 ("n_deleted", C.c_uint64), ("candidates", C.POINTER(cl_del_candidate))]
 
 
+class cl_ins_params(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_ins_count", C.c_uint32), ("min_ins_per_10k", C.c_uint32)]
+
+
+class cl_ins_candidate(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("pad", C.c_uint8 * 3), ("ins", C.c_uint32), ("depth", C.c_uint32),
+                ("ins_fwd", C.c_uint32), ("ins_rev", C.c_uint32), ("depth_fwd", C.c_uint32), ("depth_rev", C.c_uint32)]
+
+
+class cl_ins_obs(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("len", C.c_uint32), ("key", C.c_uint64 * 2), ("strand", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class cl_ins_result(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_low_depth", C.c_uint64), ("n_kept", C.c_uint64),
+                ("n_inserted", C.c_uint64), ("candidates", C.POINTER(cl_ins_candidate)), ("n_obs", C.c_uint64),
+                ("obs", C.POINTER(cl_ins_obs))]
+
+
+class dut_ins_allele(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("len", C.c_uint32), ("key", C.c_uint64 * 2), ("count", C.c_uint32), ("fwd", C.c_uint32),
+                ("rev", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class dut_ins_options(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_quality", C.c_uint8), ("has_min_base_quality", C.c_int),
+                ("min_base_quality", C.c_uint8), ("exclude_flags", C.c_uint16), ("min_ins_per_10k", C.c_uint32),
+                ("min_ins_count", C.c_uint32), ("min_ins_per_strand", C.c_uint32)]
+
+
 class dut_del_event(C.Structure):
     _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("length", C.c_uint32), ("q", C.c_uint32), ("del", C.c_uint32),
                 ("del_fwd", C.c_uint32), ("del_rev", C.c_uint32), ("max_del", C.c_uint32), ("span", C.c_uint64)]
@@ -255,6 +285,9 @@ SYMBOLS = [
                                      C.c_uint32, C.c_uint32, C.POINTER(cl_minor_result)]),
     ("cl_site_scan_dels", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_del_params), C.c_void_p, C.c_uint64,
                                     C.c_uint32, C.c_uint32, C.POINTER(cl_del_result)]),
+    ("cl_site_scan_ins", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_ins_params), C.c_void_p, C.c_uint64,
+                                   C.c_uint32, C.c_uint32, C.POINTER(cl_ins_result)]),
+    ("cl_site_scan_ins_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
     ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
@@ -277,6 +310,12 @@ SYMBOLS = [
     ("dut_del_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_del_result), C.POINTER(dut_del_options), C.c_char_p, C.c_size_t]),
     ("dut_find_deletions_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_del_options),
                                            C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
+    ("dut_ins_classify_counts", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(cl_ins_params)]),
+    ("dut_ins_alleles", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(dut_ins_allele)), C.POINTER(C.c_size_t)]),
+    ("dut_ins_alleles_free", None, [C.POINTER(dut_ins_allele)]),
+    ("dut_ins_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_ins_result), C.POINTER(dut_ins_options), C.c_char_p, C.c_size_t]),
+    ("dut_find_insertions_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_ins_options),
+                                            C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

@@ -331,6 +331,27 @@ class Engine:
         return DelResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), kept=int(r.n_kept), deleted=cand.shape[0],
                          candidates=cand, kernel_ms=self.site_scan_stats()[0])
 
+    def site_scan_ins(self, min_quality, min_depth, min_ins_count, min_ins_per_10k, ref, start=0, end=None, filter=None):
+        """cl_site_scan_ins over [start, end) of the resident tile: positions behind whose base the reads insert something
+        (an I operation anchored there), beside the scan's depth, and what they insert.  filter: None for the unfiltered
+        form, else (exclude_flags, use_base_quality) of the attachment.  An InsResult: the three class counts, the
+        candidates (INS_CANDIDATE), one observation per counting insertion at a candidate (INS_OBS, by pos, len, key,
+        strand) and the milliseconds of both launches."""
+        prm = _lib.cl_ins_params(int(min_depth), int(min_ins_count), int(min_ins_per_10k))
+        r, cand = self._site_scan_mode(self._lib.cl_site_scan_ins, (int(min_quality), _filter_ref(filter), C.byref(prm)), ref, start, end,
+                                       _lib.cl_ins_result, INS_CANDIDATE, "n_inserted")
+        obs = np.zeros(int(r.n_obs), INS_OBS)
+        if obs.shape[0]:
+            C.memmove(obs.ctypes.data, r.obs, obs.shape[0] * INS_OBS.itemsize)
+        return InsResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), kept=int(r.n_kept), inserted=cand.shape[0],
+                         candidates=cand, observations=obs, kernel_ms=self.site_scan_stats()[0])
+
+    def site_scan_ins_stats(self):
+        """(window scan milliseconds, allele launch milliseconds) of the last site_scan_ins."""
+        a = C.c_double(); b = C.c_double()
+        self._check(self._lib.cl_site_scan_ins_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def site_scan_stats(self):
         """(kernel milliseconds, algorithmic bytes) of the last site_scan / site_scan_counts, filtered or not."""
         ms = C.c_double(); b = C.c_uint64()
@@ -389,6 +410,28 @@ MINOR_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("major", np.
 # cl_del_candidate: the strand counts are 0 in the unfiltered form
 DEL_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("pad", np.uint8, (3,)), ("del", np.uint32), ("depth", np.uint32),
                           ("del_fwd", np.uint32), ("del_rev", np.uint32), ("depth_fwd", np.uint32), ("depth_rev", np.uint32)])
+
+
+# cl_ins_candidate: pos is the anchor; the strand counts are 0 in the unfiltered form
+INS_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("pad", np.uint8, (3,)), ("ins", np.uint32), ("depth", np.uint32),
+                          ("ins_fwd", np.uint32), ("ins_rev", np.uint32), ("depth_fwd", np.uint32), ("depth_rev", np.uint32)])
+
+# cl_ins_obs: key = the first 32 inserted 4-bit codes, base j in key[j // 16] at bits 60 - 4 * (j % 16)
+INS_OBS = np.dtype([("pos", np.uint32), ("len", np.uint32), ("key", np.uint64, (2,)), ("strand", np.uint32), ("pad", np.uint32)])
+
+
+@dataclass
+class InsResult:
+    """cl_ins_result (include/callable_loci.h): the three classes add up to end - start; candidates = the positions of
+    class inserted, ascending; observations = every counting insertion at a candidate."""
+    start: int
+    end: int
+    low_depth: int
+    kept: int
+    inserted: int
+    candidates: np.ndarray
+    observations: np.ndarray
+    kernel_ms: float = 0.0
 
 
 @dataclass

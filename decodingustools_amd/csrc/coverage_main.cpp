@@ -1,5 +1,5 @@
 // dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
-// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles` and `find-deletions`);
+// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions` and `find-insertions`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -44,7 +44,10 @@ static void usage()
             "       [--min-minor-per-strand K] [--device 0]\n"
             "       dut-coverage find-deletions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3] [--min-base-quality Q] [--exclude-flags MASK]\n"
-            "       [--min-del-per-strand K] [--device 0]\n");
+            "       [--min-del-per-strand K] [--device 0]\n"
+            "       dut-coverage find-insertions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
+            "       [--min-quality 20] [--min-ins-fraction 0.7] [--min-ins-count 3] [--min-base-quality Q] [--exclude-flags MASK]\n"
+            "       [--min-ins-per-strand K] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -233,7 +236,7 @@ static bool cli_count32(const char *flag, const std::string &v, uint32_t &dst)
     return true;
 }
 
-// What the scan subcommands (find-variants, find-minor-alleles, find-deletions) share on the command line: the BAM, -r, -o,
+// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions) share on the command line: the BAM, -r, -o,
 // -L, --region (0-based, half open), --min-depth, --min-quality, the two filter flags, --device, -h.
 struct ScanCli {
     const char *name;
@@ -245,7 +248,7 @@ struct ScanCli {
     uint8_t min_base_quality = 0;
     int has_min_base_quality = 0;
     uint16_t exclude_flags = 0;
-    // the two filter fields into a command's options (dut_variants_options, dut_minor_options, dut_del_options)
+    // the two filter fields into a command's options (dut_variants_options, dut_minor_options, dut_del_options, dut_ins_options)
     template <class Options> void filter_into(Options &o) const
     {
         o.has_min_base_quality = has_min_base_quality; o.min_base_quality = min_base_quality; o.exclude_flags = exclude_flags;
@@ -428,6 +431,36 @@ static int find_deletions_main(int argc, char **argv)
                                                    c.out.c_str(), c.device, err, sizeof(err)), err);
 }
 
+static void usage_fi()
+{
+    fprintf(stderr, "Usage: dut-coverage find-insertions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END]\n"
+                    "       [--min-depth 10] [--min-quality 20] [--min-ins-fraction 0.7] [--min-ins-count 3]\n"
+                    "       [--min-base-quality Q] [--exclude-flags MASK] [--min-ins-per-strand K] [--device 0]\n"
+                    "  A position is listed when it is at least --min-depth deep and the reads with an I operation directly behind\n"
+                    "  their base there are at least --min-ins-count and --min-ins-fraction of the depth (a decimal in (0, 1], at\n"
+                    "  most four decimals).  pos is the base before the insertion; the most frequent inserted sequence is shown\n"
+                    "  (its first 32 bases).  --region: 0-based, half open.  Q, MASK as in find-variants; filter is 'strand' when\n"
+                    "  min(ins_fwd, ins_rev) < K.  Insertions only, no left-alignment, one device.\n");
+}
+
+// find-insertions: every position of a contig (or of --region) behind whose base the reads insert something -- at least
+// --min-ins-count reads with an I operation anchored there and --min-ins-fraction of the depth (cl_site_scan_ins) -- with the
+// inserted alleles.  Counting as in find-variants with its filter flags.
+static int find_insertions_main(int argc, char **argv)
+{
+    ScanCli c = {"find-insertions", usage_fi};
+    dut_ins_options iopt = {10, 20, 0, 0, 0, 7000, 3, 0};
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        return cli_rule_flags(a, next, "ins", dut_del_fraction_parse, iopt.min_ins_per_10k, iopt.min_ins_count, iopt.min_ins_per_strand);
+    });
+    if (st >= 0) return st;
+    c.filter_into(iopt);
+    iopt.min_depth = (uint32_t)c.min_depth; iopt.min_quality = (uint8_t)c.min_quality;
+    char err[1024] = {0};
+    return scan_cli_leave(dut_find_insertions_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), c.has_region ? 1 : 0, (uint32_t)c.start, (uint32_t)c.end, &iopt,
+                                                    c.out.c_str(), c.device, err, sizeof(err)), err);
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -448,6 +481,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "find-variants")) return find_variants_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-minor-alleles")) return find_minor_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-deletions")) return find_deletions_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "find-insertions")) return find_insertions_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

@@ -159,6 +159,12 @@ struct SiteResident {
     bool attached = false;
     DevBuf<ScanMinorCand> sm_cand;   // cl_site_scan_minor's candidates, of either form
     DevBuf<ScanDelCand> sd_cand;     // cl_site_scan_dels' candidates, of either form
+    // cl_site_scan_ins: its candidates, of either form; the called positions as its allele launch takes them, the
+    // observations and the insertions found per position
+    DevBuf<ScanInsCand> si_cand;
+    DevBuf<ScanInsSite> si_site;
+    DevBuf<ScanInsObs> si_obs;
+    DevBuf<uint32_t> si_found;
     // the last cl_site_pileup / cl_site_run and the last cl_site_scan* of either form: the kernels' duration and their
     // algorithmic bytes; the candidates of the last cl_site_scan, cl_site_scan_ex, cl_site_scan_minor and cl_site_scan_dels
     KernelTimer t_pileup, t_scan;
@@ -166,10 +172,14 @@ struct SiteResident {
     std::vector<cl_scan_candidate_ex> scan_cand_ex;
     std::vector<cl_minor_candidate> minor_cand;
     std::vector<cl_del_candidate> del_cand;
+    std::vector<cl_ins_candidate> ins_cand;
+    std::vector<cl_ins_obs> ins_obs;
+    double ins_scan_ms = 0.0, ins_alleles_ms = 0.0;      // the last cl_site_scan_ins: its two launches
     void release()
     {
         t_pileup.destroy(); t_scan.destroy();
         q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release(); sd_cand.release();
+        si_cand.release(); si_site.release(); si_obs.release(); si_found.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -444,6 +454,10 @@ static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_ca
 static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
 static_assert(sizeof(ScanMinorCand) == sizeof(cl_minor_candidate) && sizeof(cl_minor_candidate) == 44, "the device writes cl_minor_candidate");
 static_assert(sizeof(ScanDelCand) == sizeof(cl_del_candidate) && sizeof(cl_del_candidate) == 32, "the device writes cl_del_candidate");
+static_assert(sizeof(ScanInsCand) == sizeof(cl_ins_candidate) && sizeof(cl_ins_candidate) == 32, "the device writes cl_ins_candidate");
+static_assert(sizeof(ScanInsObs) == sizeof(cl_ins_obs) && sizeof(cl_ins_obs) == 32 && offsetof(ScanInsObs, strand) == offsetof(cl_ins_obs, strand),
+              "the device writes cl_ins_obs");
+static_assert(sizeof(ScanInsSite) == 16, "one called position of the allele launch");
 
 // the argument checks every scan shares, in front of any device work
 static cl_status site_scan_check(SiteCtx *c, const char *who, uint32_t start, uint32_t end)
@@ -645,6 +659,76 @@ template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_DELS> : ScanModeHost
     static uint64_t tile_bytes(const SiteResident &S) { return S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + (FILTERED ? (S.nbase + 7) / 8 + S.n * 2 : 0); }
 };
 
+// the insertion mode: reads with a counting I operation anchored at a position, beside the scan's depth; behind the
+// candidates a second launch over them alone fetches what was inserted (site_scan.hip.h)
+template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_INS> : ScanModeHostBase {
+    using Result = cl_ins_result;
+    using Cand = cl_ins_candidate;
+    using Params = const cl_ins_params *;
+    static constexpr const char *kWho = "cl_site_scan_ins", *kLap = "insertion scan: reference in, kernel, candidates back";
+    static std::vector<Cand> &host_cand(SiteResident &S) { return S.ins_cand; }
+    static DevBuf<ScanInsCand> &dev_cand(SiteResident &S) { return S.si_cand; }
+    static const char *fault(Params p)
+    {
+        return !p ? "null params" : p->min_depth == 0 ? kNoDepth : p->min_ins_count == 0 ? "min_ins_count must be at least 1"
+             : (p->min_ins_per_10k < 1 || p->min_ins_per_10k > 10000) ? "min_ins_per_10k must lie in 1..10000" : nullptr;
+    }
+    static uint32_t min_depth(Params p) { return p->min_depth; }
+    static void fill(ScanModeArgs<FILTERED, SCAN_INS> &A, Params p) { A.t.min_count = p->min_ins_count; A.t.min_per_10k = p->min_ins_per_10k; }
+    static void classes(Result &out, const unsigned long long (&h)[8]) { out.n_low_depth = h[INS_LOW_DEPTH]; out.n_kept = h[INS_KEPT]; out.n_inserted = h[INS_INSERTED]; }
+    // the window scan reads what the deletion mode does
+    static uint64_t tile_bytes(const SiteResident &S) { return ScanModeHost<FILTERED, SCAN_DELS>::tile_bytes(S); }
+    // The observations: the candidates' positions with the exclusive prefix sum of their ins go to the device, one
+    // workgroup per candidate stores its insertions into its own slots of a buffer of exactly sum(ins) entries and says
+    // how many it found.  t_scan and its bytes become those of both launches.
+    static cl_status post(SiteCtx *c, const ScanModeArgs<FILTERED, SCAN_INS> &A, std::vector<Cand> &cand, const unsigned long long (&)[8],
+                          Result &out, StageTimer &tmr)
+    {
+        SiteResident &S = c->site;
+        std::vector<cl_ins_obs> &obs = S.ins_obs;
+        obs.clear();
+        S.ins_scan_ms = S.t_scan.ms; S.ins_alleles_ms = 0.0;
+        out.n_obs = 0; out.obs = obs.data();
+        if (cand.empty()) return CL_OK;
+        std::vector<ScanInsSite> site(cand.size());
+        uint64_t n_obs = 0;
+        for (size_t i = 0; i < cand.size(); ++i) { site[i] = {cand[i].pos, cand[i].ins, n_obs}; n_obs += cand[i].ins; }
+        std::vector<uint32_t> found(cand.size());
+        HIP_TRY(c, S.si_site.reserve(site.size())); HIP_TRY(c, S.si_found.reserve(site.size())); HIP_TRY(c, S.si_obs.reserve(n_obs));
+        HIP_TRY(c, hipMemcpyAsync(S.si_site.p, site.data(), site.size() * sizeof(ScanInsSite), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, S.t_scan.start(c->stream));
+        for (size_t at = 0; at < site.size(); at += (size_t)1 << 30) {          // (a grid holds fewer than 2^31 workgroups)
+            const uint32_t n = (uint32_t)std::min<size_t>(site.size() - at, (size_t)1 << 30);
+            hipLaunchKernelGGL((k_site_scan_ins_alleles<FILTERED>), dim3(n), dim3(kBlock), 0, c->stream, A, S.si_site.p + at, S.si_obs.p, S.si_found.p + at);
+            HIP_TRY(c, hipGetLastError());
+        }
+        HIP_TRY(c, S.t_scan.stop(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(found.data(), S.si_found.p, found.size() * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, S.t_scan.read(true));
+        S.ins_alleles_ms = S.t_scan.ms - S.ins_scan_ms;
+        for (size_t i = 0; i < cand.size(); ++i)
+            if (found[i] != cand[i].ins)
+                return fail(c, CL_ERR_INTERNAL, "cl_site_scan_ins: the allele launch found " + std::to_string(found[i]) + " insertions at position " +
+                                                    std::to_string(cand[i].pos) + " where the scan counted " + std::to_string(cand[i].ins));
+        obs.resize(n_obs);
+        if (n_obs) HIP_TRY(c, hipMemcpy(obs.data(), S.si_obs.p, n_obs * sizeof(cl_ins_obs), hipMemcpyDeviceToHost));
+        // (of the tile the allele launch reads a window's records per candidate and the inserted bases: not counted)
+        S.t_scan.bytes += site.size() * (sizeof(ScanInsSite) + 4) + n_obs * sizeof(cl_ins_obs);
+        tmr.lap("insertion scan: observations of the called positions back");
+        // the slots of a position fill in the order its reads arrive: the order of the result is restored here
+        std::sort(obs.begin(), obs.end(), [](const cl_ins_obs &a, const cl_ins_obs &b) {
+            if (a.pos != b.pos) return a.pos < b.pos;
+            if (a.len != b.len) return a.len < b.len;
+            if (a.key[0] != b.key[0]) return a.key[0] < b.key[0];
+            if (a.key[1] != b.key[1]) return a.key[1] < b.key[1];
+            return a.strand < b.strand;
+        });
+        out.n_obs = n_obs; out.obs = obs.data();
+        return CL_OK;
+    }
+};
+
 // A scan that compacts candidates, of any mode and form: the checks, the index, the reference bytes of the range, the
 // kernel until the candidates fit, the candidates back and in ascending position, the mode's post step.
 template <bool FILTERED, ScanMode MODE>
@@ -838,6 +922,23 @@ cl_status cl_site_scan_dels(cl_ctx *h, uint8_t min_quality, const cl_scan_filter
                             uint64_t ref_len, uint32_t start, uint32_t end, cl_del_result *out)
 {
     return site_entry(h, [&](SiteCtx *c) { return site_scan_either<SCAN_DELS>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out); });
+}
+
+cl_status cl_site_scan_ins(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, const cl_ins_params *params, const uint8_t *ref_bases,
+                           uint64_t ref_len, uint32_t start, uint32_t end, cl_ins_result *out)
+{
+    return site_entry(h, [&](SiteCtx *c) {
+        if (c) c->site.ins_scan_ms = c->site.ins_alleles_ms = 0.0;
+        return site_scan_either<SCAN_INS>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
+    });
+}
+
+cl_status cl_site_scan_ins_stats(cl_ctx *h, double *scan_ms, double *alleles_ms)
+{
+    if (!h) return CL_ERR_INVALID;
+    if (scan_ms) *scan_ms = site_ctx(h)->site.ins_scan_ms;
+    if (alleles_ms) *alleles_ms = site_ctx(h)->site.ins_alleles_ms;
+    return CL_OK;
 }
 
 cl_status cl_site_scan_counts_ex(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, uint32_t start, uint32_t end, uint32_t *counts)

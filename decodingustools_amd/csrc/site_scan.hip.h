@@ -22,8 +22,11 @@
 //                       per base, consecutive positions in consecutive banks).  What happens to the finished planes is
 //                       the MODE: the counters themselves go out (SCAN_DENSE), or every thread judges positions and the
 //                       candidates are compacted with one ballot and one atomic per wave -- by the calling rule
-//                       (SCAN_CALLS), the second-allele rule (SCAN_MINOR) or the deletion rule (SCAN_DELS).
+//                       (SCAN_CALLS), the second-allele rule (SCAN_MINOR), the deletion rule (SCAN_DELS) or the insertion
+//                       rule (SCAN_INS).
 //   k_site_scan_settle  filtered form only: the 16-code histogram of the few positions the planes cannot classify.
+//   k_site_scan_ins_alleles<FILTERED>
+//                       behind SCAN_INS: what was inserted at the called positions, one workgroup per position.
 //
 // The unfiltered form (ScanForm<false>) counts in six planes: A, C, G, T, N, any other code.  Six planes and not
 // sixteen: depth = their sum, and the call needs the largest single code.  That is one of the five named planes unless
@@ -61,6 +64,16 @@
 // behind the read's last base and every D of a read without bases do not count).  Without a filter an M run is one run
 // too; under a filter the depth is added per base, by the pass bits.  span = depth + del; a position is low_depth
 // (span < min_depth), deleted (del >= min_del_count and 10000 del >= min_del_per_10k span, in 64 bits) or kept.
+//
+// The insertion mode (cl_site_scan_ins) counts the third thing the walk steps over: I operations (CIGAR op 1), at their
+// anchor -- the position of the last base of the M/=/X operation directly in front (VCF's placement).  An insertion
+// counts when that operation is a match of at least one base, the anchor base and every inserted base exist in the read
+// (query index < l_seq), the anchor lies below min(contig_len, ref_len) and, under a base-quality filter, the anchor's pass
+// bit is set.  Planes: depth and ins (by strand under a filter), the deletion mode's layout; depth is built as there, ins
+// is one plain add at the anchor, so only the unfiltered depth plane is scanned.  It loads no seq4 either: a position is
+// low_depth (depth < min_depth), inserted (ins >= min_ins_count and 10000 ins >= min_ins_per_10k depth, in 64 bits) or
+// kept, and only for the inserted ones does k_site_scan_ins_alleles fetch the inserted bases: per counting insertion one
+// observation {pos, len, key, strand}, key being the first 32 inserted 4-bit codes, most significant nibble first.
 #pragma once
 
 #include <type_traits>
@@ -104,7 +117,25 @@ struct ScanDelCand {
 };
 enum { DEL_LOW_DEPTH = 0, DEL_KEPT = 1, DEL_DELETED = 2 };                   // its classes, in the first slots of cls
 
-enum ScanMode { SCAN_CALLS = 0, SCAN_DENSE = 1, SCAN_MINOR = 2, SCAN_DELS = 3 };
+// one compacted position of the insertion mode (pos: the anchor); the strand counts are 0 in the unfiltered form
+struct ScanInsCand {
+    uint32_t pos;                            // 1-based
+    uint8_t  ref, pad[3];
+    uint32_t ins, depth;                     // both strands
+    uint32_t ins_fwd, ins_rev, depth_fwd, depth_rev;
+};
+enum { INS_LOW_DEPTH = 0, INS_KEPT = 1, INS_INSERTED = 2 };                  // its classes, in the first slots of cls
+
+// k_site_scan_ins_alleles: a called position as the host sends it (the candidates in ascending position; off = the
+// exclusive prefix sum of their ins) and one counting insertion there as the device answers
+struct ScanInsSite { uint32_t pos, ins; unsigned long long off; };          // pos 1-based
+struct ScanInsObs {
+    uint32_t pos, len;                       // 1-based anchor; inserted bases
+    unsigned long long key[2];               // the first min(len, 32) codes: base j in key[j / 16], bits 60 - 4 (j % 16)
+    uint32_t strand, pad;                    // 1 reverse (always 0 in the unfiltered form)
+};
+
+enum ScanMode { SCAN_CALLS = 0, SCAN_DENSE = 1, SCAN_MINOR = 2, SCAN_DELS = 3, SCAN_INS = 4 };
 
 struct ScanNoHook {};                        // a hook of scan_walk_read that a mode does not use
 template <class T> inline constexpr bool scan_hooked = !std::is_same_v<std::remove_cv_t<std::remove_reference_t<T>>, ScanNoHook>;
@@ -145,7 +176,7 @@ struct ScanArgs {
     const SiteRec *rec;
     const unsigned long long *seq_base;      // per kBlock reads: base offset of the first one
     const uint32_t *cigar;
-    const uint8_t  *seq4;                    // (never read by the deletion mode)
+    const uint8_t  *seq4;                    // (never read by the deletion and insertion modes)
     const uint32_t *end, *wfirst, *wlast;
     uint32_t min_quality, contig_len, min_depth;
     unsigned long long ref_len;
@@ -176,6 +207,11 @@ template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_DELS> {
     using Thresholds = ScanThresholds;
     static __device__ __forceinline__ bool emits(int cls) { return cls == DEL_DELETED; }
 };
+template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_INS> {
+    using Cand = ScanInsCand;
+    using Thresholds = ScanThresholds;
+    static __device__ __forceinline__ bool emits(int cls) { return cls == INS_INSERTED; }
+};
 template <bool FILTERED, ScanMode MODE> struct ScanModeArgs {                // the kernel's record
     ScanArgs s;
     typename ScanForm<FILTERED>::Filter f;
@@ -183,8 +219,14 @@ template <bool FILTERED, ScanMode MODE> struct ScanModeArgs {                // 
     [[no_unique_address]] typename ScanModeTraits<FILTERED, MODE>::Thresholds t;
 };
 
-// LDS planes of a mode: depth and del by strand in the deletion mode (8 KB, 16 KB), the form's base planes otherwise
-template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanPlanes = MODE == SCAN_DELS ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
+// LDS planes of a mode: depth and del (ins) by strand in the deletion (insertion) mode (8 KB, 16 KB), the form's base
+// planes otherwise
+template <ScanMode MODE> inline constexpr bool kScanTwoCounts = MODE == SCAN_DELS || MODE == SCAN_INS;
+template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanPlanes = kScanTwoCounts<MODE> ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
+// ... of which the last kScanEnds hold range ends that one workgroup-wide scan each turns into counts: both unfiltered
+// planes and the del planes under a filter in the deletion mode; the unfiltered depth plane, the first, in the insertion mode
+template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds = MODE == SCAN_DELS ? 2u : (MODE == SCAN_INS && !FILTERED) ? 1u : 0u;
+template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds0 = MODE == SCAN_DELS ? kScanPlanes<FILTERED, MODE> - 2u : 0u;
 
 // number of CIGAR operations and bases of a read, with SiteRec's escape to the next record's offsets
 __device__ __forceinline__ void scan_read_extent(const SiteRec *rec, uint32_t r, const uint4 &rr, uint32_t &k1, unsigned long long &slen)
@@ -253,9 +295,13 @@ __device__ __forceinline__ bool scan_read_counts(const ScanArgs &a, const uint4 
 // position in [lo, hi), [p0, p1) being the positions per_base would see; on_del(p0, p1, ci) once per D operation (op 2,
 // not N) whose carrier exists, [p0, p1) being its positions in [lo, hi) and ci the carrier's base in the numbering of
 // seq4.  per_base itself may be ScanNoHook.
-template <class BeginRun, class PerBase, class OnRun = ScanNoHook, class OnDel = ScanNoHook>
+// One more, for the insertion mode: on_ins(p, anchor_bi, first_bi, len) once per I operation (op 1) that stands directly
+// behind an M/=/X operation of at least one base whose last position p lies in [lo, hi), when that base and all len
+// inserted bases exist (query index < l_seq); anchor_bi and first_bi are the anchor's and the first inserted base in the
+// numbering of seq4.  It fires from the match branch, by the next CIGAR word: an M that ends exactly at hi ends the loop.
+template <class BeginRun, class PerBase, class OnRun = ScanNoHook, class OnDel = ScanNoHook, class OnIns = ScanNoHook>
 __device__ __forceinline__ void scan_walk_read(const ScanArgs &a, uint32_t r, const uint4 &rr, uint32_t lo, uint32_t hi, BeginRun &&begin_run,
-                                               PerBase &&per_base, OnRun &&on_run = OnRun{}, OnDel &&on_del = OnDel{})
+                                               PerBase &&per_base, OnRun &&on_run = OnRun{}, OnDel &&on_del = OnDel{}, OnIns &&on_ins = OnIns{})
 {
     uint32_t k1; unsigned long long slen;
     scan_read_extent(a.rec, r, rr, k1, slen);
@@ -274,6 +320,14 @@ __device__ __forceinline__ void scan_walk_read(const ScanArgs &a, uint32_t r, co
                 unsigned long long bi = s0 + y + (p0 - x);
                 auto run = begin_run(bi, p0 < p1);
                 for (unsigned long long p = p0; p < p1; ++p, ++bi) per_base((uint32_t)p, bi, run);
+            }
+            if constexpr (scan_hooked<OnIns>) {
+                const unsigned long long pa = x + l - 1ull;                    // the anchor: this operation's last position
+                if (l && pa >= lo && pa < hi && kk + 1u < k1) {
+                    const uint32_t cn = a.cigar[kk + 1u];
+                    // the anchor base (query index y + l - 1) and the cn >> 4 bases behind it exist
+                    if ((cn & 15u) == 1u && y + l + (cn >> 4) <= slen) on_ins((uint32_t)pa, s0 + y + l - 1ull, s0 + y + l, cn >> 4);
+                }
             }
             x += l; y += l;
         } else if (op_del(op)) {
@@ -410,7 +464,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
     using Form = ScanForm<FILTERED>;
     constexpr uint32_t S = Form::kStrands;
     constexpr uint32_t kPlanes = kScanPlanes<FILTERED, MODE>;
-    __shared__ alignas(MODE == SCAN_DELS ? 16 : 8) uint32_t s_cnt[kPlanes * kScanWin];   // (the deletion mode reads it four words at a time)
+    __shared__ alignas(kScanTwoCounts<MODE> ? 16 : 8) uint32_t s_cnt[kPlanes * kScanWin];   // (the deletion and insertion modes read it four words at a time)
     const ScanArgs &a = ax.s;
     const uint32_t tid = threadIdx.x;
     const uint32_t w = a.win0 + blockIdx.x;
@@ -429,13 +483,28 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
                 if (fl & ax.f.exclude_flags) continue;
                 rev = (fl >> 4) & 1u;
             }
-            if constexpr (MODE == SCAN_DELS) {
-                // planes: depth by strand, then del by strand.  A run's ends: +1 at its first position, -1 behind its last
+            if constexpr (kScanTwoCounts<MODE>) {
+                // planes: depth by strand, then del (ins) by strand.  A run's ends: +1 at its first position, -1 behind its last
                 auto run_ends = [&](uint32_t plane, uint32_t p0, uint32_t p1) {
                     atomicAdd(&s_cnt[plane * kScanWin + (p0 - ws)], 1u);
                     if (p1 - ws < kScanWin) atomicAdd(&s_cnt[plane * kScanWin + (p1 - ws)], 0xFFFFFFFFu);
                 };
-                if constexpr (FILTERED) {
+                if constexpr (MODE == SCAN_INS && FILTERED) {
+                    scan_walk_read(a, r, rr, lo, hi,
+                        [&](unsigned long long bi, bool any) { return scan_pass_word(ax.f, bi, any); },
+                        [&](uint32_t p, unsigned long long bi, unsigned long long &pw) {
+                            if (scan_base_passes(ax.f, bi, pw)) atomicAdd(&s_cnt[rev * kScanWin + (p - ws)], 1u);
+                        },
+                        ScanNoHook{}, ScanNoHook{},
+                        [&](uint32_t p, unsigned long long ai, unsigned long long, uint32_t) {
+                            if (ax.f.use_bq && !((ax.f.pass[ai >> 6] >> (ai & 63ull)) & 1ull)) return;
+                            atomicAdd(&s_cnt[(S + rev) * kScanWin + (p - ws)], 1u);
+                        });
+                } else if constexpr (MODE == SCAN_INS) {
+                    scan_walk_read(a, r, rr, lo, hi, ScanNoHook{}, ScanNoHook{},
+                        [&](uint32_t p0, uint32_t p1) { run_ends(0u, p0, p1); }, ScanNoHook{},
+                        [&](uint32_t p, unsigned long long, unsigned long long, uint32_t) { atomicAdd(&s_cnt[kScanWin + (p - ws)], 1u); });
+                } else if constexpr (FILTERED) {
                     scan_walk_read(a, r, rr, lo, hi,
                         [&](unsigned long long bi, bool any) { return scan_pass_word(ax.f, bi, any); },
                         [&](uint32_t p, unsigned long long bi, unsigned long long &pw) {
@@ -475,11 +544,13 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
             else { v = 0; for (uint32_t k = 0; k < kPlanes; ++k) v += s_cnt[k * kScanWin + o]; }
             out[i] = v;
         }
-    } else if constexpr (MODE == SCAN_DELS) {
-        // Four consecutive positions per thread, all planes into registers.  The planes of range ends (both unfiltered,
-        // the del planes under a filter: always the last two) become counts by an inclusive scan over the window: within
-        // the thread, over the wave by DPP, over the workgroup through the waves' totals.
+    } else if constexpr (kScanTwoCounts<MODE>) {
+        // Four consecutive positions per thread, all planes into registers.  The planes of range ends (deletion mode: both
+        // unfiltered, the del planes under a filter: always the last two; insertion mode: the unfiltered depth plane)
+        // become counts by an inclusive scan over the window: within the thread, over the wave by DPP, over the workgroup
+        // through the waves' totals.
         static_assert(kScanWin == 4u * (uint32_t)kBlock, "four positions per thread");
+        constexpr uint32_t kE0 = kScanEnds0<FILTERED, MODE>, kE1 = kE0 + kScanEnds<FILTERED, MODE>;
         __shared__ uint32_t s_wtot[2][kBlock / 64];
         const uint32_t lane = tid & 63u, wv = tid >> 6;
         uint32_t q[kPlanes][4];
@@ -490,22 +561,32 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
         }
         uint32_t before[2];                                                    // the sum of the wave's earlier threads
 #pragma unroll
-        for (uint32_t k = kPlanes - 2u; k < kPlanes; ++k) {
+        for (uint32_t k = kE0; k < kE1; ++k) {
             q[k][1] += q[k][0]; q[k][2] += q[k][1]; q[k][3] += q[k][2];
             const uint32_t inc = dpp_incl_scan_u32(q[k][3]);
-            if (lane == 63u) s_wtot[k - (kPlanes - 2u)][wv] = inc;
-            before[k - (kPlanes - 2u)] = inc - q[k][3];
+            if (lane == 63u) s_wtot[k - kE0][wv] = inc;
+            before[k - kE0] = inc - q[k][3];
         }
-        __syncthreads();
+        if constexpr (kE1 > kE0) __syncthreads();
 #pragma unroll
-        for (uint32_t k = kPlanes - 2u; k < kPlanes; ++k) {
-            uint32_t add = before[k - (kPlanes - 2u)];
+        for (uint32_t k = kE0; k < kE1; ++k) {
+            uint32_t add = before[k - kE0];
 #pragma unroll
-            for (uint32_t j = 0; j < (uint32_t)kBlock / 64u; ++j) add += j < wv ? s_wtot[k - (kPlanes - 2u)][j] : 0u;
+            for (uint32_t j = 0; j < (uint32_t)kBlock / 64u; ++j) add += j < wv ? s_wtot[k - kE0][j] : 0u;
 #pragma unroll
             for (uint32_t j = 0; j < 4u; ++j) q[k][j] += add;
         }
-        scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return 4u * tid + j; }, [&](uint32_t j, uint32_t, auto &&ref, ScanDelCand &cd) {
+        if constexpr (MODE == SCAN_INS) scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return 4u * tid + j; }, [&](uint32_t j, uint32_t, auto &&ref, ScanInsCand &cd) {
+            const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, ins_f = q[S][j], ins_r = FILTERED ? q[2u * S - 1u][j] : 0u;
+            const unsigned long long depth = (unsigned long long)depth_f + depth_r, ins = (unsigned long long)ins_f + ins_r;
+            const int cls = depth < a.min_depth ? INS_LOW_DEPTH
+                          : (ins >= ax.t.min_count && 10000ull * ins >= (unsigned long long)ax.t.min_per_10k * depth) ? INS_INSERTED : INS_KEPT;
+            cd.ref = (uint8_t)(ref() & ~32u); cd.pad[0] = cd.pad[1] = cd.pad[2] = 0;
+            cd.ins = (uint32_t)ins; cd.depth = (uint32_t)depth;
+            cd.ins_fwd = FILTERED ? ins_f : 0u; cd.ins_rev = ins_r; cd.depth_fwd = FILTERED ? depth_f : 0u; cd.depth_rev = depth_r;
+            return cls;
+        });
+        else scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return 4u * tid + j; }, [&](uint32_t j, uint32_t, auto &&ref, ScanDelCand &cd) {
             // (j is a constant of the unrolled loop: q stays in registers)
             const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, del_f = q[S][j], del_r = FILTERED ? q[2u * S - 1u][j] : 0u;
             const unsigned long long depth = (unsigned long long)depth_f + depth_r, del = (unsigned long long)del_f + del_r, span = depth + del;
@@ -603,6 +684,52 @@ __global__ __launch_bounds__(kBlock) void k_site_scan_settle(ScanModeArgs<true, 
     }
     __syncthreads();
     if (tid < 16u) hist16[(size_t)blockIdx.x * 16u + tid] = s_h[tid];
+}
+
+// What was inserted at the called positions of the insertion mode: one workgroup per site (ascending, off = the exclusive
+// prefix sum of their ins), over the reads of the site's window range, under the gates and the filter of ax.  Every
+// counting insertion anchored there takes a slot k of the workgroup's counter and, if k < ins, stores its observation at
+// obs[off + k]: the buffer is exact and nothing is stored beyond a site's own slots.  found[c] = the slots taken.
+template <bool FILTERED>
+__global__ __launch_bounds__(kBlock) void k_site_scan_ins_alleles(ScanModeArgs<FILTERED, SCAN_INS> ax, const ScanInsSite *site, ScanInsObs *obs, uint32_t *found)
+{
+    __shared__ uint32_t s_n;
+    const ScanArgs &a = ax.s;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    const ScanInsSite st = site[blockIdx.x];
+    const uint32_t p = st.pos - 1u;
+    const uint32_t w = p / kScanWin;
+    const uint32_t r_first = a.wfirst[w], r_last = a.wlast[w];
+    if (r_first < r_last && (unsigned long long)p < a.ref_len) {
+        for (uint32_t r = r_first + tid; r < r_last; r += kBlock) {
+            const uint4 rr = *reinterpret_cast<const uint4 *>(a.rec + r);
+            if (!scan_read_counts(a, rr, a.end[r], p, p + 1u)) continue;       // (p < contig_len <= 2^32 - 1)
+            uint32_t rev = 0;
+            if constexpr (FILTERED) {
+                const uint32_t fl = ax.f.flag[r];
+                if (fl & ax.f.exclude_flags) continue;
+                rev = (fl >> 4) & 1u;
+            }
+            scan_walk_read(a, r, rr, p, p + 1u, ScanNoHook{}, ScanNoHook{}, ScanNoHook{}, ScanNoHook{},
+                [&](uint32_t, unsigned long long ai, unsigned long long bi, uint32_t len) {
+                    if constexpr (FILTERED) { if (ax.f.use_bq && !((ax.f.pass[ai >> 6] >> (ai & 63ull)) & 1ull)) return; }
+                    const uint32_t k = atomicAdd(&s_n, 1u);
+                    if (k >= st.ins) return;
+                    ScanInsObs o;
+                    o.pos = st.pos; o.len = len; o.key[0] = o.key[1] = 0; o.strand = rev; o.pad = 0;
+                    const uint32_t n = len < 32u ? len : 32u;
+                    for (uint32_t j = 0; j < n; ++j) {
+                        const unsigned long long code = scan_base_code(a.seq4, bi + j);
+                        if (j < 16u) o.key[0] |= code << (60u - 4u * j); else o.key[1] |= code << (60u - 4u * (j - 16u));
+                    }
+                    obs[st.off + k] = o;
+                });
+        }
+    }
+    __syncthreads();
+    if (tid == 0) found[blockIdx.x] = s_n;
 }
 
 } // namespace clk

@@ -3,7 +3,8 @@
 // `find-variants`; the second-allele rule of `find-minor-alleles` in plain C++, its fraction parser and its TSV.  Host-only
 // except dut_find_variants_files(_ex) and dut_find_minor_files, which run the device engine's cl_site_scan(_ex) and
 // cl_site_scan_minor.  The same for `find-deletions`: the deletion rule, the merge of candidate positions into events,
-// the TSV, and dut_find_deletions_files over cl_site_scan_dels.
+// the TSV, and dut_find_deletions_files over cl_site_scan_dels.  And for `find-insertions`: the insertion rule, the
+// grouping of observations into alleles, the TSV, and dut_find_insertions_files over cl_site_scan_ins.
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -85,14 +86,15 @@ int write_file(const char *path, const std::string &s, char *err, size_t err_len
     return CL_OK;
 }
 
-// A rule of a count and parts per 10 000 (the second allele, the deletion): its names in messages and TSV lines and the
+// A rule of a count and parts per 10 000 (the second allele, the deletion, the insertion): its names in messages and TSV lines and the
 // largest per-10k value
 struct Rule { const char *count, *per_10k, *fraction; uint32_t max_per_10k; };
 const Rule MINOR_RULE = {"min_minor_count", "min_minor_per_10k", "min_minor_fraction", 5000};
 const Rule DEL_RULE = {"min_del_count", "min_del_per_10k", "min_del_fraction", 10000};
+const Rule INS_RULE = {"min_ins_count", "min_ins_per_10k", "min_ins_fraction", 10000};
 
-// what a file-level scan is asked with: the flag and base-quality filter, and a rule's own values -- dut_minor_options and
-// dut_del_options member by member
+// what a file-level scan is asked with: the flag and base-quality filter, and a rule's own values -- dut_minor_options,
+// dut_del_options and dut_ins_options member by member
 struct FilterOptions { int has_min_base_quality; uint8_t min_base_quality; uint16_t exclude_flags; };
 struct ScanOptions { uint32_t min_depth; uint8_t min_quality; FilterOptions flt; uint32_t per_10k, count, per_strand; };
 ScanOptions scan_options(const dut_minor_options &o)
@@ -102,6 +104,10 @@ ScanOptions scan_options(const dut_minor_options &o)
 ScanOptions scan_options(const dut_del_options &o)
 {
     return {o.min_depth, o.min_quality, {o.has_min_base_quality, o.min_base_quality, o.exclude_flags}, o.min_del_per_10k, o.min_del_count, o.min_del_per_strand};
+}
+ScanOptions scan_options(const dut_ins_options &o)
+{
+    return {o.min_depth, o.min_quality, {o.has_min_base_quality, o.min_base_quality, o.exclude_flags}, o.min_ins_per_10k, o.min_ins_count, o.min_ins_per_strand};
 }
 
 // the range checks of a rule, written once
@@ -417,6 +423,104 @@ int dut_del_write(const char *path, const char *contig, const cl_del_result *res
     catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
 }
 
+int dut_ins_classify_counts(uint32_t ins, uint32_t depth, const cl_ins_params *params)
+{
+    if (!params || !rule_ok(INS_RULE, params->min_depth, params->min_ins_count, params->min_ins_per_10k)) return CL_ERR_INVALID;
+    if (depth < params->min_depth) return DUT_INS_LOW_DEPTH;
+    return (ins >= params->min_ins_count && 10000ull * ins >= (uint64_t)params->min_ins_per_10k * depth) ? DUT_INS_INSERTED : DUT_INS_KEPT;
+}
+
+// observations of equal (pos, len, key) counted; per position the top allele in front, the others by (len, key)
+static void ins_alleles(const cl_ins_obs *obs, size_t n, std::vector<dut_ins_allele> &al)
+{
+    std::vector<const cl_ins_obs *> o(n);
+    for (size_t i = 0; i < n; ++i) o[i] = obs + i;
+    auto same = [](const cl_ins_obs &a, const cl_ins_obs &b) { return a.pos == b.pos && a.len == b.len && a.key[0] == b.key[0] && a.key[1] == b.key[1]; };
+    std::sort(o.begin(), o.end(), [](const cl_ins_obs *a, const cl_ins_obs *b) {
+        if (a->pos != b->pos) return a->pos < b->pos;
+        if (a->len != b->len) return a->len < b->len;
+        if (a->key[0] != b->key[0]) return a->key[0] < b->key[0];
+        return a->key[1] < b->key[1];
+    });
+    size_t first = 0;                                                        // the first allele of the position at hand
+    for (size_t i = 0; i < n; ++i) {
+        if (i == 0 || !same(*o[i], *o[i - 1])) {
+            if (i && o[i]->pos != o[i - 1]->pos) first = al.size();
+            dut_ins_allele a{};
+            a.pos = o[i]->pos; a.len = o[i]->len; a.key[0] = o[i]->key[0]; a.key[1] = o[i]->key[1];
+            al.push_back(a);
+        }
+        dut_ins_allele &a = al.back();
+        a.count += 1; (o[i]->strand ? a.rev : a.fwd) += 1;
+        // the position's last observation: its largest allele (the first in (len, key) order among equals) moves to the front
+        if (i + 1 == n || o[i + 1]->pos != o[i]->pos) {
+            size_t top = first;
+            for (size_t k = first + 1; k < al.size(); ++k) if (al[k].count > al[top].count) top = k;
+            std::rotate(al.begin() + first, al.begin() + top, al.begin() + top + 1);
+        }
+    }
+}
+
+int dut_ins_alleles(const cl_ins_obs *obs, size_t n_obs, dut_ins_allele **alleles, size_t *n_alleles)
+{
+    if (alleles) *alleles = nullptr;
+    if (n_alleles) *n_alleles = 0;
+    if (!alleles || !n_alleles || (n_obs && !obs)) return CL_ERR_INVALID;
+    try {
+        std::vector<dut_ins_allele> al;
+        ins_alleles(obs, n_obs, al);
+        if (al.empty()) return CL_OK;
+        dut_ins_allele *out = static_cast<dut_ins_allele *>(malloc(al.size() * sizeof(dut_ins_allele)));
+        if (!out) return CL_ERR_NOMEM;
+        memcpy(out, al.data(), al.size() * sizeof(dut_ins_allele));
+        *alleles = out; *n_alleles = al.size();
+        return CL_OK;
+    }
+    catch (...) { return CL_ERR_NOMEM; }
+}
+
+void dut_ins_alleles_free(dut_ins_allele *alleles) { free(alleles); }
+
+static int ins_write(const char *path, const char *contig, const cl_ins_result *res, const dut_ins_options *opt, char *err, size_t err_len)
+{
+    if (!path || !contig || !res || !opt || (res->n_inserted && !res->candidates) || (res->n_obs && !res->obs)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    std::vector<dut_ins_allele> al;
+    ins_alleles(res->obs, (size_t)res->n_obs, al);
+    std::string s;
+    char b[512];
+    tsv_preamble(s, contig, res->start, res->end, scan_options(*opt), true, &INS_RULE);
+    snprintf(b, sizeof(b), "##low_depth=%llu\n##kept=%llu\n##inserted=%llu\n", (unsigned long long)res->n_low_depth,
+             (unsigned long long)res->n_kept, (unsigned long long)res->n_inserted);
+    s += b;
+    s += "#contig\tpos\tref\tins\tdepth\tfreq\talleles\tlength\tseq\tallele_count\tallele_fwd\tallele_rev\tins_fwd\tins_rev\tfilter\n";
+    size_t at = 0;                                                           // the candidate's first allele
+    for (uint64_t i = 0; i < res->n_inserted; ++i) {
+        const cl_ins_candidate &c = res->candidates[i];
+        if (i && c.pos <= res->candidates[i - 1].pos) { set_err(err, err_len, "candidate positions must ascend"); return CL_ERR_INVALID; }
+        size_t n_al = 0; uint64_t n_obs = 0;
+        while (at + n_al < al.size() && al[at + n_al].pos == c.pos) { n_obs += al[at + n_al].count; ++n_al; }
+        if (n_obs != c.ins || n_al == 0) { set_err(err, err_len, "a candidate's observations must be as many as its ins"); return CL_ERR_INVALID; }
+        const dut_ins_allele &top = al[at];
+        at += n_al;
+        std::string seq;
+        for (uint32_t j = 0; j < std::min<uint32_t>(top.len, 32u); ++j) seq += CODE[(top.key[j / 16] >> (60 - 4 * (j % 16))) & 15u];
+        if (top.len > 32) seq += "...";
+        const double freq = c.depth ? (double)c.ins / (double)c.depth : 0.0;
+        const bool strand = std::min(c.ins_fwd, c.ins_rev) < opt->min_ins_per_strand;
+        snprintf(b, sizeof(b), "\t%u\t%c\t%u\t%u\t%.4f\t%llu\t%u\t%s\t%u\t%u\t%u\t%u\t%u\t%s\n", c.pos, (char)c.ref, c.ins, c.depth, freq,
+                 (unsigned long long)n_al, top.len, seq.c_str(), top.count, top.fwd, top.rev, c.ins_fwd, c.ins_rev, strand ? "strand" : "PASS");
+        s += contig; s += b;
+    }
+    if (at != al.size()) { set_err(err, err_len, "observations at a position that is no candidate"); return CL_ERR_INVALID; }
+    return write_file(path, s, err, err_len);
+}
+
+int dut_ins_write(const char *path, const char *contig, const cl_ins_result *res, const dut_ins_options *opt, char *err, size_t err_len)
+{
+    try { return ins_write(path, contig, res, opt, err, err_len); }
+    catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
+}
+
 int dut_minor_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint64_t depth, const cl_minor_params *params, char *major, char *minor)
 {
     if (major) *major = 0;
@@ -547,6 +651,13 @@ int dut_find_deletions_files(const char *bam_path, const char *fasta_path, const
 {
     return no_throw(err, err_len, [&] { return rule_files_run(DEL_RULE, bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id,
                                                               cl_site_scan_dels, dut_del_write, err, err_len); });
+}
+
+int dut_find_insertions_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
+                              const dut_ins_options *opt, const char *output_path, int device_id, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&] { return rule_files_run(INS_RULE, bam_path, fasta_path, contig, has_region, start, end, opt, output_path, device_id,
+                                                              cl_site_scan_ins, dut_ins_write, err, err_len); });
 }
 
 int dut_find_minor_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,

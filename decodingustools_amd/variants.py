@@ -7,7 +7,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .callable_loci import DEL_CANDIDATE, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, DelResult, EngineError, MinorResult, ScanResult
+from .callable_loci import (DEL_CANDIDATE, INS_CANDIDATE, INS_OBS, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, DelResult, EngineError,
+                            InsResult, MinorResult, ScanResult)
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
@@ -15,6 +16,9 @@ MINOR_LOW_DEPTH, MINOR_SINGLE, MINOR_MINOR = range(3)
 MINOR_CLASS_NAMES = ("low_depth", "single", "minor")
 DEL_LOW_DEPTH, DEL_KEPT, DEL_DELETED = range(3)
 DEL_CLASS_NAMES = ("low_depth", "kept", "deleted")
+INS_LOW_DEPTH, INS_KEPT, INS_INSERTED = range(3)
+INS_CLASS_NAMES = ("low_depth", "kept", "inserted")
+INS_CODES = "=ACMGRSVTWYHKDBN"
 CLASS_NAMES = ("low_depth", "mixed", "uncomparable", "match", "variant", "undetermined")
 
 
@@ -190,7 +194,8 @@ def minor_classify_counts(a, c, g, t, depth, min_depth, min_minor_count, min_min
 
 
 def _rule_options(stem, min_depth, min_quality, count, per_10k, min_base_quality, exclude_flags, per_strand):
-    """dut_minor_options (stem "minor") or dut_del_options ("del"): the same members under the rule's names."""
+    """dut_minor_options (stem "minor"), dut_del_options ("del") or dut_ins_options ("ins"): the same members under the
+    rule's names."""
     o = _filter_options(getattr(_lib, f"dut_{stem}_options")(), min_base_quality, exclude_flags)
     if not 0 <= int(min_quality) <= 255:
         raise ValueError("min_quality: 0..255")
@@ -272,3 +277,58 @@ def find_deletions(bam_file: str, reference_file: str, contig: str, output_file:
     per_10k = del_fraction_parse(str(min_del_fraction))
     opt = _rule_options("del", min_depth, min_quality, min_del_count, per_10k, min_base_quality, exclude_flags, min_del_per_strand)
     _find_files(_lib.load().dut_find_deletions_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(), device_id)
+
+
+def ins_classify_counts(n_ins, depth, min_depth, min_ins_count, min_ins_per_10k) -> int:
+    """The class of one position by the rule of cl_site_scan_ins in plain code (dut_ins_classify_counts)."""
+    prm = _lib.cl_ins_params(int(min_depth), int(min_ins_count), int(min_ins_per_10k))
+    st = _lib.load().dut_ins_classify_counts(int(n_ins), int(depth), C.byref(prm))
+    if st < 0:
+        raise EngineError(st, "invalid parameters")
+    return st
+
+
+def ins_key_text(length, key) -> str:
+    """The inserted bases a key holds: the first min(length, 32), decoded with =ACMGRSVTWYHKDBN."""
+    return "".join(INS_CODES[(int(key[j // 16]) >> (60 - 4 * (j % 16))) & 15] for j in range(min(int(length), 32)))
+
+
+def ins_alleles(observations) -> List[dict]:
+    """dut_ins_alleles: the observations (INS_OBS, any order) grouped into alleles of equal (len, key): ascending position,
+    within a position the top allele first (most observations, then the smaller len, then the smaller key), the others by
+    (len, key).  Per allele pos, len, key (two ints), seq (the first 32 bases), count, fwd, rev.  Insertions longer than 32
+    bases that agree in length and in their first 32 bases are one allele."""
+    obs = np.ascontiguousarray(observations, INS_OBS).reshape(-1)
+    al = C.POINTER(_lib.dut_ins_allele)()
+    n = C.c_size_t()
+    lib = _lib.load()
+    st = lib.dut_ins_alleles(obs.ctypes.data if obs.shape[0] else None, obs.shape[0], C.byref(al), C.byref(n))
+    if st != 0:
+        raise EngineError(st, "dut_ins_alleles failed")
+    try:
+        return [dict(pos=int(a.pos), len=int(a.len), key=(int(a.key[0]), int(a.key[1])), seq=ins_key_text(a.len, a.key), count=int(a.count),
+                     fwd=int(a.fwd), rev=int(a.rev)) for a in al[:n.value]]
+    finally:
+        lib.dut_ins_alleles_free(al)
+
+
+def write_insertions(path: str, contig: str, result: InsResult, min_depth: int, min_quality: int, min_ins_count: int,
+                     min_ins_per_10k: int, min_base_quality=None, exclude_flags: int = 0, min_ins_per_strand: int = 0):
+    """The TSV of find-insertions (dut_ins_write) for the InsResult of Engine.site_scan_ins.  No device is needed."""
+    r, _cand = _c_result(_lib.cl_ins_result, _lib.cl_ins_candidate, INS_CANDIDATE, result, "inserted", n_low_depth=result.low_depth,
+                         n_kept=result.kept, n_inserted=result.inserted)
+    obs = np.ascontiguousarray(result.observations, INS_OBS).reshape(-1)
+    r.n_obs = obs.shape[0]
+    r.obs = C.cast(obs.ctypes.data, C.POINTER(_lib.cl_ins_obs))
+    opt = _rule_options("ins", min_depth, min_quality, min_ins_count, min_ins_per_10k, min_base_quality, exclude_flags, min_ins_per_strand)
+    _call(_lib.load().dut_ins_write, path.encode(), contig.encode(), C.byref(r), C.byref(opt))
+
+
+def find_insertions(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None,
+                    min_depth: int = 10, min_quality: int = 20, min_ins_fraction="0.7", min_ins_count: int = 3,
+                    min_base_quality: Optional[int] = None, exclude_flags: int = 0, min_ins_per_strand: int = 0, device_id: int = 0):
+    """dut_find_insertions_files: BAM (+ index) and FASTA in, the TSV of insertions out; region = (start, end), 0-based half
+    open.  min_ins_fraction: decimal text (or a number whose text is one) in (0, 1], at most four decimals."""
+    per_10k = del_fraction_parse(str(min_ins_fraction))
+    opt = _rule_options("ins", min_depth, min_quality, min_ins_count, per_10k, min_base_quality, exclude_flags, min_ins_per_strand)
+    _find_files(_lib.load().dut_find_insertions_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(), device_id)

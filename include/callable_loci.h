@@ -517,6 +517,57 @@ cl_status cl_site_scan_dels(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filt
                             const cl_del_params *params, const uint8_t *ref_bases, uint64_t ref_len,
                             uint32_t start, uint32_t end, cl_del_result *out);
 
+/* ---- the insertion mode of the dense scan: per-position insertion counts, calls and the inserted sequences ---------- */
+/* The read gates are those of cl_site_scan (filter == NULL) or cl_site_scan_ex (a filter; needs cl_site_attach_quals).
+ * For every position p of [start, end):
+ *   depth        the scan's depth, exactly that of cl_site_scan_counts / cl_site_scan_counts_ex at p.
+ *   ins          the reads passing the same gates with a counting I operation (CIGAR op 1) anchored at p.  The anchor of
+ *                an I operation is the reference position of the last base of the operation directly before it, which
+ *                must be M, = or X with at least one base (VCF's placement: the base before the insertion).  A first
+ *                operation and an I directly behind S H P D N or another I do not count.  The anchor base and every
+ *                inserted base must exist in the read (query index < l_seq), p < min(contig_len, ref_len), and under
+ *                use_base_quality the anchor's pass bit must be set (an anchor without a quality value passes; the
+ *                inserted bases' qualities take no part).  At most one per read and position, so ins <= depth by strand.
+ *   low_depth    depth < min_depth
+ *   inserted     not low, ins >= min_ins_count and 10000 * ins >= min_ins_per_10k * depth (taken in 64 bits)
+ *   kept         everything else
+ * The three counts add up to end - start; the reference base takes no part.  The positions of class inserted come back
+ * as candidates, all of them, ascending; ins_fwd .. depth_rev are the strand counts under a filter and 0 without one.
+ * For every candidate, each counting insertion there comes back as one observation (a second launch over the candidates
+ * only): key holds the 4-bit codes of the first min(len, 32) inserted bases as they stand in seq4, base j in key[j / 16]
+ * at bits 60 - 4 * (j % 16), unused nibbles 0, so (key[0], key[1]) compares in sequence order.  Insertions longer than 32
+ * bases that agree in length and in their first 32 bases cannot be told apart.  strand is 1 for a reverse read (flag &
+ * 0x10) and 0 without a filter.  Observations are sorted by (pos, len, key, strand); n_obs == the sum of the candidates' ins.
+ * Refusals: those of cl_site_scan_dels under the same checks, with min_ins_count / min_ins_per_10k (1..10000) in the
+ * messages.  CL_ERR_INTERNAL (with a message): the second launch found another number of insertions at a candidate than
+ * the first; nothing was stored out of range.  candidates and obs are context-owned, in storage of their own, valid
+ * until the next cl_site_scan_ins, cl_site_upload or cl_destroy; any order of the other scans and this call on one tile
+ * is allowed.  cl_site_scan_stats speaks of both launches after it; cl_site_scan_ins_stats tells them apart. */
+typedef struct cl_ins_params { uint32_t min_depth, min_ins_count, min_ins_per_10k; } cl_ins_params;
+typedef struct cl_ins_candidate {
+    uint32_t pos;                         /* 1-based anchor */
+    uint8_t  ref, pad[3];
+    uint32_t ins, depth;                  /* both strands */
+    uint32_t ins_fwd, ins_rev, depth_fwd, depth_rev;
+} cl_ins_candidate;
+typedef struct cl_ins_obs {
+    uint32_t pos, len;                    /* 1-based anchor; inserted bases */
+    uint64_t key[2];
+    uint32_t strand, pad;
+} cl_ins_obs;
+typedef struct cl_ins_result {
+    uint32_t start, end;
+    uint64_t n_low_depth, n_kept, n_inserted;     /* sum == end - start */
+    const cl_ins_candidate *candidates;           /* n_inserted, ascending position */
+    uint64_t n_obs;
+    const cl_ins_obs *obs;                        /* n_obs, by (pos, len, key, strand) */
+} cl_ins_result;
+cl_status cl_site_scan_ins(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: unfiltered form */,
+                           const cl_ins_params *params, const uint8_t *ref_bases, uint64_t ref_len,
+                           uint32_t start, uint32_t end, cl_ins_result *out);
+/* The kernel milliseconds of the last cl_site_scan_ins: its window scan and its allele launch (0 without candidates). */
+cl_status cl_site_scan_ins_stats(cl_ctx *ctx, double *scan_ms, double *alleles_ms);
+
 /* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
  * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
 cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);

@@ -5,7 +5,7 @@
  * The reference has no such subcommand.  The counting and the call are the ones of find-y-branch / find-mt-branch
  * (haplogroup::caller::process_region, src/haplogroup/caller.rs:62-152), taken at every position of a contig or a
  * region instead of at the tree's sites, so the two never disagree about a tree site.  find-variants itself calls SNVs
- * only; deletions are counted and called per position by find-deletions (below); no insertions, no consensus FASTA.  With dut_variants_options the scan takes a flag mask and a base-quality threshold
+ * only; deletions are counted and called per position by find-deletions and insertions by find-insertions (both below); no consensus FASTA.  With dut_variants_options the scan takes a flag mask and a base-quality threshold
  * (cl_site_scan_ex) and the TSV carries per-strand allele counts and a strand filter.
  */
 #ifndef DUT_VARIANTS_H
@@ -191,6 +191,61 @@ int dut_del_write(const char *path, const char *contig, const cl_del_result *res
 int dut_find_deletions_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
                              uint32_t end, const dut_del_options *opt, const char *output_path, int device_id,
                              char *err, size_t err_len);
+
+/* ---- find-insertions: per-position insertion counts, calls and alleles (cl_site_scan_ins) ------------------------- */
+/* The classes of cl_site_scan_ins. */
+enum { DUT_INS_LOW_DEPTH = 0, DUT_INS_KEPT = 1, DUT_INS_INSERTED = 2 };
+
+/* The rule of cl_site_scan_ins for one position in plain C++, with the same integer comparison: low_depth when depth <
+ * min_depth; inserted when ins >= min_ins_count and 10000 * ins >= min_ins_per_10k * depth (in 64 bits); kept otherwise.
+ * CL_ERR_INVALID: null or refused params (as cl_site_scan_ins refuses them).  The fraction of the command line is parsed
+ * by dut_del_fraction_parse: the same interval (0, 1]. */
+int dut_ins_classify_counts(uint32_t ins, uint32_t depth, const cl_ins_params *params);
+
+/* One allele of a position: the observations of cl_site_scan_ins there with equal (len, key).  Insertions longer than 32
+ * bases that agree in length and in their first 32 bases are one allele: the key holds no more.  fwd + rev == count. */
+typedef struct dut_ins_allele {
+    uint32_t pos, len;                /* 1-based anchor; inserted bases */
+    uint64_t key[2];                  /* as in cl_ins_obs */
+    uint32_t count, fwd, rev, pad;
+} dut_ins_allele;
+
+/* Groups observations (in any order) into alleles: ascending position; within a position the top allele first -- the
+ * most observations, then the smaller len, then the smaller key -- and the others behind it by (len, key).  *alleles:
+ * malloc'ed, release with dut_ins_alleles_free (NULL when there is none).  CL_ERR_INVALID: null argument. */
+int dut_ins_alleles(const cl_ins_obs *obs, size_t n_obs, dut_ins_allele **alleles, size_t *n_alleles);
+void dut_ins_alleles_free(dut_ins_allele *alleles);
+
+/* What a find-insertions run is asked: the scan's parameters and filter, and the strand mark of the TSV. */
+typedef struct dut_ins_options {
+    uint32_t min_depth;
+    uint8_t  min_quality;
+    int      has_min_base_quality;
+    uint8_t  min_base_quality;
+    uint16_t exclude_flags;
+    uint32_t min_ins_per_10k;         /* 1..10000 */
+    uint32_t min_ins_count;           /* >= 1 */
+    uint32_t min_ins_per_strand;      /* K: filter = "strand" when min(ins_fwd, ins_rev) < K; 0: always PASS */
+} dut_ins_options;
+
+/* The TSV (no device needed): comment lines ##contig= ##range=start-end ##min_depth= ##min_quality= ##min_base_quality=
+ * ("." when !has_min_base_quality) ##exclude_flags=0x%04x ##min_ins_fraction=%.4f ##min_ins_count= ##positions=
+ * ##low_depth= ##kept= ##inserted=, the header
+ *   #contig pos ref ins depth freq alleles length seq allele_count allele_fwd allele_rev ins_fwd ins_rev filter
+ * and one line per candidate: pos = the 1-based anchor, the base before the insertion; freq = ins / depth as %.4f;
+ * alleles = the number of alleles there; length, seq, allele_count, allele_fwd, allele_rev describe the top allele, seq
+ * decoded with "=ACMGRSVTWYHKDBN" and, for length > 32, its first 32 bases followed by "...".  ##inserted= is the scan's
+ * count: marked lines stay.  CL_ERR_INVALID: null argument, candidates that do not ascend, a candidate whose
+ * observations are not ins many. */
+int dut_ins_write(const char *path, const char *contig, const cl_ins_result *res, const dut_ins_options *opt,
+                  char *err, size_t err_len);
+
+/* `find-insertions` on files, one GPU: reads as dut_find_deletions_files does, always attaches the records' flags and
+ * pass bits and runs the filtered form of cl_site_scan_ins, writes the TSV.  Errors with a message: those of
+ * dut_find_variants_files, refused options. */
+int dut_find_insertions_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
+                              uint32_t end, const dut_ins_options *opt, const char *output_path, int device_id,
+                              char *err, size_t err_len);
 
 #ifdef __cplusplus
 }
