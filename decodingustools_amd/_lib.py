@@ -376,6 +376,8 @@ SYMBOLS = [
     ("cl_debug_host_create", C.c_int, [C.POINTER(cl_options), C.POINTER(C.c_void_p)]),
     ("cl_debug_pass_rows", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    ("cl_debug_pass_rows_segments", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("cl_debug_depths", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("cl_debug_read_records", C.c_int, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint64, C.c_uint64,
                                         C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

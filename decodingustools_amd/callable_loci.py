@@ -611,7 +611,8 @@ class DepthAccumulator:
 
 class HostStage(Engine):
     """A context WITHOUT a device (cl_debug_host_create), for the CPU test suite: contig_begin / push_reads stage a
-    contig exactly as a device context does, `pass_rows` runs the upload's row builder over it.  Everything that needs a
+    contig exactly as a device context does, `pass_rows_segments` runs the upload's row builder over it and `pass_rows`
+    the one-stack-per-window builder it is held against.  Everything that needs a
     device raises: there is no CPU pileup."""
 
     def __init__(self, options: CallableOptions):
@@ -635,6 +636,19 @@ class HostStage(Engine):
         self._check(self._lib.cl_debug_pass_rows(self._h, _ptr(ng), nwin.value, _ptr(rows), nwords.value, C.byref(nwords),
                                                  C.byref(nwin), C.byref(sq)))
         return ng[:nwin.value], rows[:nwords.value], int(sq.value)
+
+    def pass_rows_segments(self):
+        """The rows as the device holds them, a stack per segment of 256 positions: (heights (n_windows, 8) in units, the
+        height word of every window's record -- 0: the equal-heights form --, units as uint32 array of 32-word units, window
+        after window and segment after segment)."""
+        nwords = C.c_uint64(); nwin = C.c_uint32()
+        self._check(self._lib.cl_debug_pass_rows_segments(self._h, None, None, 0, None, 0, C.byref(nwords), C.byref(nwin)))
+        h = np.zeros((max(nwin.value, 1), 8), np.uint32)
+        words = np.zeros(max(nwin.value, 1), np.uint64)
+        units = np.zeros(max(nwords.value, 1), np.uint32)
+        self._check(self._lib.cl_debug_pass_rows_segments(self._h, _ptr(h), _ptr(words), nwin.value, _ptr(units), nwords.value,
+                                                          C.byref(nwords), C.byref(nwin)))
+        return h[:nwin.value], words[:nwin.value], units[:nwords.value]
 
 
 @dataclass

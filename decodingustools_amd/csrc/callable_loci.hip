@@ -100,6 +100,7 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     uint64_t dev_sum_cov = 0, dev_sum_mapq = 0;   // of the resident contig
     uint32_t head_span = kHeadSpanMax;   // most positions one head of k_pileup_rows spans (DUT_HEAD_SPAN: a test hook)
     bool heads8_only = false;            // DUT_HEADS8=1 (a test hook): every contig gets 8-byte heads
+    bool rows_uniform = false;           // DUT_ROWS_UNIFORM=1 (a test hook): every segment of a window as high as its highest
     bool heads4 = false;                 // the resident contig's heads are the 4-byte form (pileup_rows.hip.h: HEAD4)
     uint64_t host_n_ops = 0;         // CIGAR operations pushed for it (pass-bit form: none is staged; for cl_contig_layout)
     uint64_t dev_sum_q = 0;          // of the resident contig (handed to the summary workgroup of every run)
@@ -120,9 +121,9 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     DevBuf<uint2> d_heads;           // pass-bit form: the heads k_pileup_rows reads, {pos, span | low << 31} -- or, with
                                      // heads4, 4-byte heads, two to an element
     DevBuf<uint32_t> d_refn;         // pass-bit form: bit p = the reference base at p is 'N' / 'n' or lies beyond the reference
-    DevBuf<uint4> d_rows;            // pass-bit form: the windows' rows, groups of 4 rows x 64 blocks (1 KB each)
-    uint64_t n_row_groups = 0;
-    uint32_t max_groups = 0;         // most groups of any window: picks the number of counter planes of k_pileup_rows
+    DevBuf<uint4> d_rows;            // pass-bit form: the windows' rows, units of 4 rows x 8 blocks (128 bytes each: pass_rows.h)
+    uint64_t n_row_groups = 0;       // ... how many units
+    uint32_t max_groups = 0;         // most units of any segment of any window: picks the number of counter planes of k_pileup_rows
     DevBuf<uint32_t> d_win_off, d_wide_idx;
     DevBuf<WinMeta> d_win;
     DevBuf<uint8_t> d_state;         // per-position states: allocated and written for debug dumps only
@@ -612,18 +613,23 @@ inline void run_enter(std::vector<RunCur> &act, const RunReads &H, uint32_t r, u
     act.push_back(cu);
 }
 
-// groups of rows per pinned buffer (DUT_ROW_CHUNK: a test hook that makes the buffer-full and oversized-window paths
-// reachable with small inputs; read once)
-size_t row_chunk_groups()
+// units of rows per pinned buffer (DUT_ROW_CHUNK, in kilobytes = 8 units: a test hook that makes the buffer-full and
+// oversized-window paths reachable with small inputs; read once)
+size_t row_chunk_units()
 {
     static const size_t n = [] {
+        constexpr size_t kPerKB = 1024 / (dut::kRowUnitWords * sizeof(uint32_t));
         const char *e = getenv("DUT_ROW_CHUNK");
-        const size_t full = PinRing::kPinBytes / (dut::kRowGroupWords * sizeof(uint32_t));
+        const size_t full = PinRing::kPinBytes / 1024;
         const size_t v = e ? (size_t)strtoull(e, nullptr, 0) : full;
-        return v < 1 ? 1 : (v > full ? full : v);
+        return (v < 1 ? 1 : (v > full ? full : v)) * kPerKB;
     }();
     return n;
 }
+
+// DUT_ROWS_UNIFORM=1, read when a context is made (a test and A/B hook: the equal-heights form of every window, that is
+// the bytes of one stack per window through the segments' code)
+bool rows_uniform_env() { const char *e = getenv("DUT_ROWS_UNIFORM"); return e && *e == '1'; }
 
 dut::RowReads row_reads(const cl_ctx *c)
 {
@@ -635,13 +641,15 @@ dut::RowReads row_reads(const cl_ctx *c)
     return H;
 }
 
-// the first size of the row array: rows ~ 1.7 x the mean depth, a quarter of that in groups, one group of rounding per
-// window (cl_contig_reserve allocates by it ahead of the upload)
-uint64_t row_groups_estimate(uint64_t n_qual, uint64_t n_win) { return (n_qual / kT) * 17 / 40 + n_win + 1024; }
+// the first size of the row array, in units: per window of mean depth d eight stacks of ~1.45 d rows (a window's ONE
+// stack stood at ~1.7 d, and a stack per segment stores 0.85 to 0.96 of that), a quarter of that in units, one unit of
+// rounding per segment (cl_contig_reserve allocates by it ahead of the upload)
+uint64_t row_units_estimate(uint64_t n_qual, uint64_t n_win) { return (n_qual / kT) * 31 / 10 + n_win * dut::kRowSegments + 8192; }
 
 // What differs between the two tables that stream_windows builds: the unit a window is made of (Word x kUnitWords), how
 // many units a pinned buffer holds, the device array (in units), the cursor of a read and how it enters and is swept,
-// what is checked and kept at the end, and the messages.
+// what a window's record says of its units (Form::record: rn, and whatever else the form keeps there), what is checked
+// and kept at the end, and the messages.
 struct RunTableForm {                     // byte form, long reads: a unit = a match piece (sweep_window)
     using Word = uint2;
     using Cur = RunCur;
@@ -661,27 +669,30 @@ struct RunTableForm {                     // byte form, long reads: a unit = a m
     uint64_t capacity() const { return c->d_runtab.cap; }
     void enter(std::vector<Cur> &act, uint32_t r, uint32_t W) const { run_enter(act, H, r, W); }
     size_t window(std::vector<Cur> &act, uint32_t W, const WinMeta &m, Word *out, size_t cap, Scratch &) { return sweep_window(act, H.cig, W, m.q0, out, cap, qend, &oor); }
+    static void record(WinMeta &m, size_t cnt, const Scratch &) { m.rn = (uint32_t)std::min<size_t>(cnt, 0xFFFFFFFFu); }
     cl_status check() { return oor.load() ? fail(c, CL_ERR_RANGE, "a match piece of the run table addresses quality bytes outside the resident array") : CL_OK; }
     void done(uint64_t total, uint32_t) { c->n_runtab = total; }
 };
 
-struct RowsForm {                         // pass-bit form: a unit = a group of 4 rows (pass_rows.h)
+struct RowsForm {                         // pass-bit form: a unit = 4 rows of one segment of a window (pass_rows.h)
     using Word = uint32_t;
     using Cur = dut::RowCur;
-    using Scratch = dut::RowScratch;
-    static constexpr size_t kUnitWords = dut::kRowGroupWords;
-    static constexpr const char *kTooMany = "more than 2^32 groups of pass-bit rows in one contig";
+    using Scratch = dut::SegScratch;
+    static constexpr size_t kUnitWords = dut::kRowUnitWords;
+    static constexpr const char *kTooMany = "more than 2^32 units of pass-bit rows in one contig";
     static constexpr const char *kNoFit = "pass-bit rows: the second sizing pass did not fit";
     cl_ctx *c;
     const dut::RowReads H;
     explicit RowsForm(cl_ctx *c_) : c(c_), H(row_reads(c_)) {}
-    static size_t chunk_units() { return row_chunk_groups(); }
-    uint64_t estimate() const { return row_groups_estimate(c->n_qual, c->n_win); }
+    static size_t chunk_units() { return row_chunk_units(); }
+    uint64_t estimate() const { return row_units_estimate(c->n_qual, c->n_win); }
     hipError_t reserve(uint64_t units) { return c->d_rows.reserve(units * (kUnitWords / 4)); }
     Word *table() const { return reinterpret_cast<Word *>(c->d_rows.p); }
     uint64_t capacity() const { return c->d_rows.cap / (kUnitWords / 4); }
     void enter(std::vector<Cur> &act, uint32_t r, uint32_t W) const { dut::rows_enter(act, H, r, W); }
-    size_t window(std::vector<Cur> &act, uint32_t W, const WinMeta &, Word *out, size_t cap, Scratch &sc) { return dut::rows_window<kT>(act, H, W, out, cap, sc); }
+    size_t window(std::vector<Cur> &act, uint32_t W, const WinMeta &, Word *out, size_t cap, Scratch &sc) { return dut::rows_window_segments<kT>(act, H, W, out, cap, sc, c->rows_uniform); }
+    // the record of a window of `cnt` units: rn = its highest segment, the eight heights as the bytes of q0 (kernels.hip.h)
+    static void record(WinMeta &m, size_t, const Scratch &sc) { m.rn = sc.most; m.q0 = sc.word; }
     cl_status check() { return CL_OK; }
     void done(uint64_t total, uint32_t most) { c->n_row_groups = total; c->max_groups = most; }   // most: picks the counter planes
 };
@@ -690,8 +701,8 @@ struct RowsForm {                         // pass-bit form: a unit = a group of 
 // and sweeps it with a list of read cursors (Form::enter, Form::window); the units of a window are written straight
 // into the pinned buffers of the staging ring, a buffer leaves when the next window no longer fits, buffers are placed
 // in the device array in the order they fill (a window only needs its own units contiguous: its record holds their
-// index), so the table exists nowhere in host memory.  win[w].rlo / rn = first unit / number of units; a window that no
-// read's cursor reaches gets rlo = rn = 0.
+// index), so the table exists nowhere in host memory.  win[w].rlo = first unit, rn by Form::record (the number of units, or
+// the pass-bit form's highest segment); a window that no read's cursor reaches gets rlo = rn = 0.
 template <class Form>
 cl_status stream_windows(cl_ctx *c, std::vector<WinMeta> &win)
 {
@@ -719,7 +730,7 @@ cl_status stream_windows(cl_ctx *c, std::vector<WinMeta> &win)
         const uint64_t dev_cap = F.capacity();
         std::atomic<uint64_t> dev_next{0};
         std::atomic<size_t> next_task{0};
-        std::atomic<uint32_t> most{0};                           // units of the largest window
+        std::atomic<uint32_t> most{0};                           // the largest rn of any window
         PinRing *R = c->ring.get();
         R->acquire(static_cast<EngineBase *>(c));                // (the identity ring_finish releases it under)
         c->ring_held = true;
@@ -786,11 +797,11 @@ cl_status stream_windows(cl_ctx *c, std::vector<WinMeta> &win)
                                 const uint64_t off = dev_next.fetch_add(cnt);
                                 if (off + cnt <= dev_cap && err == hipSuccess)
                                     err = hipMemcpy(d_tab + off * UW, big.data(), cnt * UW * sizeof(Word), hipMemcpyHostToDevice);
-                                m.rlo = (uint32_t)off; m.rn = (uint32_t)std::min<size_t>(cnt, 0xFFFFFFFFu);
+                                m.rlo = (uint32_t)off; Form::record(m, cnt, scr);
                                 my_most = std::max(my_most, m.rn);
                                 continue;
                             }
-                            m.rlo = (uint32_t)used; m.rn = (uint32_t)cnt;
+                            m.rlo = (uint32_t)used; Form::record(m, cnt, scr);
                             my_most = std::max(my_most, m.rn);
                             if (cnt) in_buf.push_back((uint32_t)w);
                             used += cnt;
@@ -884,8 +895,12 @@ cl_status size_for_extent(cl_ctx *c, uint32_t extent)
             std::atomic<bool> bad{false};
             const uint64_t ngr = c->n_row_groups;
             if (fault_injected("rows") && c->n_win) win[c->n_win / 2].rlo += 0x7FFFFFF0u;
-            dut::parallel_for(c->n_win, 8192, [&](size_t w) { if ((uint64_t)win[w].rlo + win[w].rn > ngr) bad.store(true); });
-            if (bad.load()) return fail(c, CL_ERR_RANGE, "a window's pass-bit rows lie outside the resident row array");
+            dut::parallel_for(c->n_win, 8192, [&](size_t w) {
+                const uint64_t units = dut::rows_window_units(win[w].rn, win[w].q0);
+                // (the kernels address a window's units with 32-bit byte offsets, below 2^31: pileup_rows.hip.h, row_lane)
+                if ((uint64_t)win[w].rlo + units > ngr || units >= (1ull << 24)) bad.store(true);
+            });
+            if (bad.load()) return fail(c, CL_ERR_RANGE, "a window's pass-bit rows lie outside the resident row array, or take 2 GB or more");
         }
         static const bool validate = [] { const char *e = getenv("DUT_VALIDATE"); return e && *e == '1'; }();
         if (validate && !(flags & kErrRange)) {
@@ -1028,6 +1043,42 @@ cl_status enqueue(cl_ctx *c, bool debug, uint32_t *dbg_raw, uint32_t *dbg_qc, ui
     return CL_OK;
 }
 
+// The staged contig's windows one after the other, each with the cursors the upload's walkers would hold there:
+// build(w, W, act) runs a row builder over the window and leaves in `act` what goes on into the next one.
+template <class Build>
+cl_status debug_rows_walk(cl_ctx *c, const char *who, uint32_t *n_windows, Build &&build)
+{
+    return guarded(c, [&]() -> cl_status {
+        if (!c || !c->in_contig || !c->bits) return fail(c, CL_ERR_INVALID, (std::string(who) + ": no staged contig in the pass-bit form").c_str());
+        const uint32_t extent = (uint32_t)std::max<uint64_t>(c->contig_len, c->host_max_end);
+        const uint32_t n_win = (uint32_t)(((uint64_t)extent + kT - 1) / kT);
+        c->n_win = n_win;
+        if (n_windows) *n_windows = n_win;
+        std::vector<WinMeta> win;
+        uint32_t flags = 0;
+        host_window_bounds(c, win, flags);
+        const dut::RowReads H = row_reads(c);
+        std::vector<dut::RowCur> act, save;
+        for (uint32_t w = 0; w < n_win; ++w) {
+            const uint32_t W = w * kT;
+            const WinMeta &m = win[w];
+            // (every third window entered afresh, as the first window of a thread's range is -- through the checkpoints of the
+            // long reads --, the others carried over from the window before, as inside a range)
+            act.clear();
+            if (w % 3u == 0u) {
+                for (uint32_t i = 0; i < m.wn; ++i) dut::rows_enter(act, H, c->hs.wide_idx[m.wlo + i], W);
+                for (uint32_t r = m.lo; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
+            } else {
+                act = save;
+                for (uint32_t r = win[w - 1].hi; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
+            }
+            build(w, W, H, act);
+            save = act;
+        }
+        return CL_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -1059,6 +1110,7 @@ cl_status cl_create(const cl_options *opt, int device_id, void *stream, cl_ctx *
     // DUT_HEAD_SPAN (a test hook): spans beyond this many positions are cut into several heads -- 2^31 - 1 in earnest, which
     // only a contig of more than 2 Gb can hold; the tests put the seams into ordinary reads
     { const char *h8 = getenv("DUT_HEADS8"); c->heads8_only = h8 && *h8 == '1'; }   // (a test hook: both head forms on one input)
+    c->rows_uniform = rows_uniform_env();
     { const char *hs = getenv("DUT_HEAD_SPAN"); if (hs) { const unsigned long long v = strtoull(hs, nullptr, 0); if (v >= 1 && v <= kHeadSpanMax) c->head_span = (uint32_t)v; } }
     if (hipSetDevice(device_id) != hipSuccess) { delete c; return CL_ERR_DEVICE; }
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
@@ -1197,7 +1249,7 @@ static void start_prealloc(cl_ctx *c, uint64_t n_reads, uint64_t n_qual)
     // (heads: 4 bytes each where the reads are short -- a contig of long reads has spans beyond kWideSpan and keeps 8)
     const bool guess4 = !c->heads8_only && n_qual / std::max<uint64_t>(n_reads, 1) < kWideSpan / 8;
     const size_t n_heads = n_reads ? (guess4 ? ((size_t)n_reads + 2) / 2 : (size_t)n_reads + 1) : 0;
-    const size_t n_rows = n_qual ? row_groups_estimate(n_qual, n_win) * (dut::kRowGroupWords / 4) : 0;
+    const size_t n_rows = n_qual ? row_units_estimate(n_qual, n_win) * (dut::kRowUnitWords / 4) : 0;
     // nothing to do for a context whose buffers hold this contig already (the usual case from its second contig on):
     // no thread is made for that
     bool enough = c->d_heads.cap >= n_heads && c->d_rows.cap >= n_rows && c->d_iv.cap != 0;
@@ -1913,6 +1965,7 @@ cl_status cl_debug_host_create(const cl_options *opt, cl_ctx **out)
     cl_ctx *c = new (std::nothrow) cl_ctx();
     if (!c) return CL_ERR_NOMEM;
     c->device = -1; c->opt = *opt; c->host_only = true; c->bits = true;
+    c->rows_uniform = rows_uniform_env();
     *out = c;
     return CL_OK;
 }
@@ -1920,52 +1973,55 @@ cl_status cl_debug_host_create(const cl_options *opt, cl_ctx **out)
 cl_status cl_debug_pass_rows(cl_ctx *c, uint32_t *n_groups, uint32_t n_win_cap, uint32_t *rows, uint64_t cap_words,
                              uint64_t *n_words, uint32_t *n_windows, uint64_t *summed_baseq)
 {
-    return guarded(c, [&]() -> cl_status {
-        if (!c || !c->in_contig || !c->bits) return fail(c, CL_ERR_INVALID, "cl_debug_pass_rows: no staged contig in the pass-bit form");
-        const uint32_t extent = (uint32_t)std::max<uint64_t>(c->contig_len, c->host_max_end);
-        const uint32_t n_win = (uint32_t)(((uint64_t)extent + kT - 1) / kT);
-        c->n_win = n_win;
-        if (n_windows) *n_windows = n_win;
-        if (summed_baseq) *summed_baseq = c->host_sum_q;
-        std::vector<WinMeta> win;
-        uint32_t flags = 0;
-        host_window_bounds(c, win, flags);
-        const dut::RowReads H = row_reads(c);
-        std::vector<dut::RowCur> act, save;
-        dut::RowScratch sc;
-        std::vector<uint32_t> buf;
-        uint64_t used = 0;
-        for (uint32_t w = 0; w < n_win; ++w) {
-            const uint32_t W = w * kT;
-            const WinMeta &m = win[w];
-            // (every third window entered afresh, as the first window of a thread's range is -- through the checkpoints of the
-            // long reads --, the others carried over from the window before, as inside a range)
-            act.clear();
-            if (w % 3u == 0u) {
-                for (uint32_t i = 0; i < m.wn; ++i) dut::rows_enter(act, H, c->hs.wide_idx[m.wlo + i], W);
-                for (uint32_t r = m.lo; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
-            } else {
-                act = save;
-                for (uint32_t r = win[w - 1].hi; r < m.hi; ++r) dut::rows_enter(act, H, r, W);
-            }
-            size_t cap = 16, cnt;
-            std::vector<dut::RowCur> start = act;
-            for (;;) {
-                buf.assign(cap * dut::kRowGroupWords, 0xDEADBEEFu);         // groups must be zeroed by the builder itself
-                act = start;
-                cnt = dut::rows_window<kT>(act, H, W, buf.data(), cap, sc);
-                if (cnt != SIZE_MAX) break;
-                cap *= 4;
-            }
-            save = act;
-            if (w < n_win_cap && n_groups) n_groups[w] = (uint32_t)cnt;
-            const uint64_t nw = (uint64_t)cnt * dut::kRowGroupWords;
-            if (rows && used + nw <= cap_words) memcpy(rows + used, buf.data(), nw * sizeof(uint32_t));
-            used += nw;
+    dut::RowScratch sc;
+    std::vector<uint32_t> buf;
+    uint64_t used = 0;
+    const cl_status s = debug_rows_walk(c, "cl_debug_pass_rows", n_windows, [&](uint32_t w, uint32_t W, const dut::RowReads &H, std::vector<dut::RowCur> &act) {
+        size_t cap = 16, cnt;
+        const std::vector<dut::RowCur> start = act;
+        for (;;) {
+            buf.assign(cap * dut::kRowGroupWords, 0xDEADBEEFu);         // groups must be zeroed by the builder itself
+            act = start;
+            cnt = dut::rows_window<kT>(act, H, W, buf.data(), cap, sc);
+            if (cnt != SIZE_MAX) break;
+            cap *= 4;
         }
-        if (n_words) *n_words = used;
-        return CL_OK;
+        if (w < n_win_cap && n_groups) n_groups[w] = (uint32_t)cnt;
+        const uint64_t nw = (uint64_t)cnt * dut::kRowGroupWords;
+        if (rows && used + nw <= cap_words) memcpy(rows + used, buf.data(), nw * sizeof(uint32_t));
+        used += nw;
     });
+    if (s != CL_OK) return s;
+    if (summed_baseq) *summed_baseq = c->host_sum_q;
+    if (n_words) *n_words = used;
+    return CL_OK;
+}
+
+cl_status cl_debug_pass_rows_segments(cl_ctx *c, uint32_t *heights, uint64_t *height_words, uint32_t n_win_cap, uint32_t *units,
+                                      uint64_t cap_words, uint64_t *n_words, uint32_t *n_windows)
+{
+    dut::SegScratch sc;
+    std::vector<uint32_t> buf;
+    uint64_t used = 0;
+    const cl_status s = debug_rows_walk(c, "cl_debug_pass_rows_segments", n_windows, [&](uint32_t w, uint32_t W, const dut::RowReads &H, std::vector<dut::RowCur> &act) {
+        size_t cap = 16, cnt;
+        const std::vector<dut::RowCur> start = act;
+        for (;;) {
+            buf.assign(cap * dut::kRowUnitWords, 0xDEADBEEFu);          // units must be written whole by the builder itself
+            act = start;
+            cnt = dut::rows_window_segments<kT>(act, H, W, buf.data(), cap, sc, c->rows_uniform);
+            if (cnt != SIZE_MAX) break;
+            cap *= 4;
+        }
+        if (w < n_win_cap && heights) memcpy(heights + (size_t)w * dut::kRowSegments, sc.h, sizeof(sc.h));
+        if (w < n_win_cap && height_words) height_words[w] = sc.word;
+        const uint64_t nw = (uint64_t)cnt * dut::kRowUnitWords;
+        if (units && used + nw <= cap_words) memcpy(units + used, buf.data(), nw * sizeof(uint32_t));
+        used += nw;
+    });
+    if (s != CL_OK) return s;
+    if (n_words) *n_words = used;
+    return CL_OK;
 }
 
 cl_status cl_contig_run(cl_ctx *c)
@@ -2131,7 +2187,7 @@ cl_status cl_contig_bytes(cl_ctx *c, uint64_t *input_bytes, uint64_t *output_byt
     //   bytes, 0     the quality bytes + the 16-byte records (heads and pieces) + the wide list
     //   bytes, 2     the quality bytes + 8 bytes per piece of the run table + pos 4, end 4, mapq 1 per read + the wide list
     uint64_t in = (c->form == 3 ? ((uint64_t)c->extent + 7) / 8 : (uint64_t)c->extent) + (uint64_t)c->n_win * sizeof(WinMeta);
-    if (c->form == 3) in += c->n_row_groups * (uint64_t)(dut::kRowGroupWords * sizeof(uint32_t)) + (uint64_t)c->n_rec * (c->heads4 ? sizeof(uint32_t) : sizeof(uint2)) + (uint64_t)c->n_wide * 4;
+    if (c->form == 3) in += c->n_row_groups * (uint64_t)(dut::kRowUnitWords * sizeof(uint32_t)) + (uint64_t)c->n_rec * (c->heads4 ? sizeof(uint32_t) : sizeof(uint2)) + (uint64_t)c->n_wide * 4;
     else if (c->form == 0) in += c->n_qual + (uint64_t)c->n_rec * sizeof(ReadRec) + (uint64_t)c->n_wide * 4;
     else in += c->n_qual + c->n_runtab * 8 + (uint64_t)c->n_reads * 9 + (uint64_t)c->n_wide * 4;
     if (input_bytes) *input_bytes = in;
@@ -2161,7 +2217,7 @@ cl_status cl_contig_layout(cl_ctx *c, cl_layout_info *out)
     // what cl_contig_upload sent over the link for this contig (every transfer goes through the pinned staging ring)
     const uint64_t padded = (uint64_t)c->n_win * kT + 16;
     uint64_t h = (c->form == 3 ? ((uint64_t)c->n_win * kT) / 8 : padded) + (uint64_t)c->n_win * sizeof(WinMeta) + (uint64_t)c->n_wide * 4;
-    if (c->form == 3) h += c->n_row_groups * (uint64_t)(dut::kRowGroupWords * sizeof(uint32_t)) + ((uint64_t)c->n_rec + 1) * (c->heads4 ? sizeof(uint32_t) : sizeof(uint2));
+    if (c->form == 3) h += c->n_row_groups * (uint64_t)(dut::kRowUnitWords * sizeof(uint32_t)) + ((uint64_t)c->n_rec + 1) * (c->heads4 ? sizeof(uint32_t) : sizeof(uint2));
     else if (c->form == 0) h += c->n_qual + ((uint64_t)c->n_rec + 1) * sizeof(ReadRec);
     else h += c->n_qual + c->n_runtab * 8 + (uint64_t)c->n_reads * 9;
     out->upload_h2d_bytes = h;

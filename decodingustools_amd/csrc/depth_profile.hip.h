@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_profile(DepthArgs a)
         const uint32_t lo = wm.lo, wlo = wm.wlo, wn = wm.wn;
         const uint32_t n_cand = wn + (wm.hi - lo);
         const uint32_t ng = wm.rn;
-        const uint4 *rows = a.rows + (size_t)wm.rlo * 64u;
+        const RowLane rl = row_lane(a.rows, wm, lane, wv);
 
         // ---- clear (the previous window's readers are behind the barrier at the end of the loop) ----
         {
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_profile(DepthArgs a)
         uint32_t c[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) c[p] = 0u;
-        for (uint32_t g = wv; g < ng; g += 2u) bs_add4<NP>(c, rows[(size_t)g * 64u + lane]);
+        for (int k = 0; wv + (uint32_t)k < ng; k += 2) bs_add4<NP>(c, row_unit(rl, k));
         // ---- the window's candidates: +-1 at the clipped span ends (as k_pileup_rows) ----
         for (uint32_t v = tid; v < n_cand; v += BS) {
             uint32_t r = lo + (v - wn);

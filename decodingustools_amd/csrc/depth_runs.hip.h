@@ -108,11 +108,11 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_runs(RunsArgs a)
         } else {
             // ---- qc_depth: the window's rows into the two waves' counter planes, summed by wave 0 (as k_depth_profile) ----
             const uint32_t ng = wm.rn;
-            const uint4 *rows = a.rows + (size_t)wm.rlo * 64u;
+            const RowLane rl = row_lane(a.rows, wm, lane, wv);
             uint32_t c[NP];
 #pragma unroll
             for (int p = 0; p < NP; ++p) c[p] = 0u;
-            for (uint32_t g = wv; g < ng; g += 2u) bs_add4<NP>(c, rows[(size_t)g * 64u + lane]);
+            for (int k = 0; wv + (uint32_t)k < ng; k += 2) bs_add4<NP>(c, row_unit(rl, k));
             if (wv != 0) {
 #pragma unroll
                 for (int p = 0; p < NP; ++p) s_pl[p][lane] = c[p];

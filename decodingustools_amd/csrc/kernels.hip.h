@@ -149,9 +149,10 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 struct __attribute__((aligned(32))) WinMeta {
     uint32_t lo, hi;                   // ordinary candidates: reads [lo, hi)
     uint32_t wlo, wn;                  // wide candidates: wide_idx[wlo .. wlo+wn)
-    unsigned long long q0;             // byte forms: qual_off of the window's first candidate read
+    unsigned long long q0;             // byte forms: qual_off of the window's first candidate read; pass-bit form: the
+                                       // heights of its eight segments, a byte each (0: all rn; pileup_rows.hip.h: row_lane)
     uint32_t rlo, rn;                  // run-table form: the window's entries are runtab[rlo .. rlo + rn);
-                                       // pass-bit form: its groups of 4 rows are rows[64 rlo .. 64 (rlo + rn))
+                                       // pass-bit form: its units start at rows[8 rlo], rn = those of its highest segment
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -41,6 +41,48 @@ template <int T> __device__ __forceinline__ HeadCand head_cand(const uint32_t h,
     return HeadCand{(uint32_t)(dx > 0 ? dx : 0), (uint32_t)e, h >> 31, span && e > 0 && dx < T};
 }
 
+// What the kernels that read a window's rows need of its record (k_pileup_rows, k_depth_profile, k_depth_runs).  The
+// rows lie in UNITS of 128 bytes (pass_rows.h): 4 rows of one SEGMENT of 256 positions, the 8 blocks of lanes 8 s ..
+// 8 s + 7, 16 bytes per lane.  Segment s has a stack of h_s units of its own; a window's units are contiguous, segment
+// after segment, from unit wm.rlo.  The eight heights are the bytes of wm.q0 (segment 0 lowest); q0 == 0 is the
+// equal-heights form, every segment wm.rn units (a window with a segment beyond 255 units, and DUT_ROWS_UNIFORM=1).
+// wm.rn is the largest height: the wave's loop bound.
+//
+// The units are read through a buffer descriptor of the WINDOW's own bytes, so that no lane can read outside them
+// whatever its offset, and a lane whose segment has no unit k asks for an offset beyond the descriptor: the load
+// returns zeros without touching memory.  That is straight code -- no branch around a load, every add waits for its
+// own load only -- and a segment lower than the window's highest simply adds zeros for the units beyond it.  A lane
+// gets the byte offset of its 16 bytes of unit g0 of its segment (g0: the first unit its wave takes) and how many
+// units the segment has from there on (n <= 0 for none).  Relative to g0, so that the k of an unrolled loop is a constant.
+// (The upload refuses a window whose units take 2^31 bytes or more, so offsets fit 32 bits: callable_loci.hip, size_for_extent.)
+typedef unsigned int RowWords __attribute__((ext_vector_type(4)));
+constexpr uint32_t kRowNoUnit = 0x80000000u;               // an offset no window's descriptor reaches (and + 16 k neither)
+struct RowLane { __amdgpu_buffer_rsrc_t rs; uint32_t off; int32_t n; };
+__device__ __forceinline__ RowLane row_lane(const uint4 *rows, const WinMeta &wm, uint32_t lane, uint32_t g0)
+{
+    const uint32_t s = lane >> 3;
+    uint32_t n = wm.rn, first = s * wm.rn, units = 8u * wm.rn;
+    if (wm.q0) {
+        n = (uint32_t)(wm.q0 >> (8u * s)) & 0xFFu;
+        // the heights below s: the bytes of q0 under byte s, summed four at a time (v_sad_u8 against 0)
+        const unsigned long long below = wm.q0 & ((1ull << (8u * s)) - 1ull);
+        first = __builtin_amdgcn_sad_u8((uint32_t)below, 0u, __builtin_amdgcn_sad_u8((uint32_t)(below >> 32), 0u, 0u));
+        // ... and all eight, in scalar registers: pairs of bytes in 16-bit fields, then the fields
+        const uint32_t lo = (uint32_t)wm.q0, hi = (uint32_t)(wm.q0 >> 32);
+        const uint32_t f = (lo & 0x00FF00FFu) + ((lo >> 8) & 0x00FF00FFu) + (hi & 0x00FF00FFu) + ((hi >> 8) & 0x00FF00FFu);
+        units = (f + (f >> 16)) & 0xFFFFu;
+    }
+    return RowLane{__builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(rows + (size_t)wm.rlo * 8u), 0, (int)(units * 128u), 0x00020000),
+                   (first + g0) * 128u + (lane & 7u) * 16u, (int32_t)(n - g0)};
+}
+// the lane's 16 bytes of unit g0 + k of its segment, zeros where the segment has none; g0 on by `by` units
+__device__ __forceinline__ uint4 row_unit(const RowLane &rl, int k)
+{
+    const RowWords v = __builtin_amdgcn_raw_buffer_load_b128(rl.rs, (k < rl.n ? rl.off : kRowNoUnit) + (uint32_t)k * 128u, 0, 0);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void row_advance(RowLane &rl, int by) { rl.off += (uint32_t)by * 128u; rl.n -= by; }
+
 // ---------------------------------------------------------------------------------------------
 // k_pileup_rows: the pass-bit form of the pileup (the default; DUT_QUAL_FORM=bytes selects the byte forms, k_pileup).
 //
@@ -48,8 +90,9 @@ template <int T> __device__ __forceinline__ HeadCand head_cand(const uint32_t h,
 // (cl_push_reads: one bit per base, qual_pack.cpp), and the bits reach the device as ROWS (pass_rows.h): per window a
 // stack of T-bit rows, bit p of a row <-> reference position W + p, every read of the window (mapq >= min) alone in its
 // stretch of a row.  qc_depth[p] (mod.rs:30-37) is then the column sum of the window's rows -- taken BIT-SLICED: a lane
-// owns a block of 32 positions, a wave streams whole groups of 4 rows (one 16-byte load per lane, 1 KB per wave
-// instruction, no address arithmetic, no masks, no shifts), and adds them into NP counter planes (plane k = bit k of
+// owns a block of 32 positions, a wave streams groups of 4 rows (one 16-byte load per lane: a unit of 128 bytes per
+// segment of 8 lanes, as many as the segment's own stack is high -- row_lane above --, no masks, no shifts), and adds
+// them into NP counter planes (plane k = bit k of
 // the 32 counts) with carry-save adders: three-input boolean operations (v_bitop3), about 4.5 instructions per row
 // for 32 positions.  No LDS atomics, no CIGAR, no offsets.  The other waves' planes are added by wave 0 and compared --
 // still bit-sliced -- with min_depth and max_depth (callable_profiler.rs:108-113): two 32-bit masks per block.
@@ -103,7 +146,7 @@ __device__ __forceinline__ uint32_t bs_less_than(const uint32_t (&c)[NP], unsign
 // of a wave are one of the three things that limit the production instantiation's residency (see the LDS comment in the
 // kernel) and every argument that is read takes one or two of them.
 struct RowsArgs {
-    const uint4    *rows;         // per window, groups of 4 rows x 64 blocks (host, at upload)
+    const uint4    *rows;         // per window and segment, units of 4 rows x 8 blocks (host, at upload)
     const void     *heads;        // per read with a reference span: 8 bytes, or 4 in an instantiation with HEAD4 (above)
     const uint32_t *wide_idx;     // read indices of the wide reads, ascending
     const WinMeta  *win;
@@ -185,19 +228,14 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
     const WinMeta wm = a.win[w];
     const uint32_t lo = wm.lo, hi = wm.hi, wlo = wm.wlo, wn = wm.wn;
     const uint32_t n_cand = wn + (hi - lo);
-    const uint32_t ng = wm.rn;                             // groups of 4 rows
-    const uint4 *rows = a.rows + (size_t)wm.rlo * 64u;
+    const uint32_t ng = wm.rn;                             // groups of 4 rows: the highest of the window's segments
+    RowLane rl = row_lane(a.rows, wm, lane, wv);
 
     // requested first, needed last: the window's rows (this wave's first G groups), the reference bytes
-    // (every load unconditional: a group past the end is clamped onto the last one and zeroed)
+    // (a lane gets the units its segment has, and zeros for the rest: row_lane)
     uint4 rv[G];
-    if (ng) {
 #pragma unroll
-        for (int j = 0; j < G; ++j) {
-            const uint32_t g = wv + (uint32_t)kWaves * j;
-            rv[j] = rows[(size_t)(g < ng ? g : ng - 1u) * 64u + lane];
-        }
-    }
+    for (int j = 0; j < G; ++j) rv[j] = row_unit(rl, kWaves * j);
     // ... and the window's first candidates: heads (above), U per lane and trip
     constexpr int U = 4;
     typedef typename HeadOf<HEAD4>::type Head;
@@ -231,8 +269,8 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
 
     // ---- the window's rows: this wave's groups wv, wv + 2, ... into its counter planes.  The wave number is taken
     //      from a scalar register so that the tests on group numbers are scalar branches: a group slot past the window's
-    //      last group costs nothing (the kernel is bound by vector issue), and the loads of a next trip are only issued
-    //      when there is one (more than 12 groups: depth beyond 48) ----
+    //      highest segment costs nothing (the kernel is bound by vector issue), and the loads of a next trip are only
+    //      issued when there is one (some segment with more than 12 groups: depth beyond 48) ----
     uint32_t c[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) c[p] = 0u;
@@ -243,11 +281,9 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
                 if (g0 + (uint32_t)kWaves * j < ng) bs_add4<NP>(c, rv[j]);
             }
             if (g0 + (uint32_t)kWaves * G < ng) {          // a deeper window: the next trip's groups (requested only now)
+                row_advance(rl, kWaves * G);
 #pragma unroll
-                for (int j = 0; j < G; ++j) {
-                    const uint32_t g = g0 + (uint32_t)kWaves * (G + j);
-                    rv[j] = rows[(size_t)(g < ng ? g : ng - 1u) * 64u + lane];
-                }
+                for (int j = 0; j < G; ++j) rv[j] = row_unit(rl, kWaves * j);
             }
         }
     }

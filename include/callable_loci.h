@@ -269,8 +269,8 @@ typedef struct cl_layout_info {
     uint64_t n_reads, n_records, n_windows;
     uint64_t n_qual;              /* quality bytes of the contig (on the device only in the byte forms)          */
     uint64_t n_cigar;             /* CIGAR operations of the contig (never on the device)                        */
-    uint64_t row_groups;          /* pass-bit form: 1 KB groups of 4 rows                                        */
-    uint64_t max_groups;          /* ... most groups of any window                                               */
+    uint64_t row_groups;          /* pass-bit form: UNITS of 128 bytes, 4 rows of one 256-position segment       */
+    uint64_t max_groups;          /* ... most groups of 4 rows in any segment of any window                      */
     uint64_t run_table_entries;   /* byte form 2                                                                 */
     uint64_t device_bytes;        /* capacity of every device buffer of the context                              */
     uint64_t upload_h2d_bytes;    /* what cl_contig_upload (byte forms: and cl_push_reads) sent over the link    */
@@ -308,12 +308,23 @@ cl_status cl_debug_ref_n_bits(const uint8_t *ref, uint64_t n_bases, uint64_t n_w
  * contig on the host exactly as a device context does, and cl_debug_pass_rows runs the upload's row builder over it.
  * Every call that needs a device fails with CL_ERR_DEVICE: there is no CPU pileup. */
 cl_status cl_debug_host_create(const cl_options *opt, cl_ctx **out);
-/* The pass-bit rows of the staged contig as cl_contig_upload would build them (pass_rows.h): n_groups[w] groups of 4 rows
+/* The pass-bit rows of the staged contig with ONE row stack per window (pass_rows.h: rows_window, the layout the
+ * upload's is held against): n_groups[w] groups of 4 rows
  * per window of 2048 positions (n_win_cap entries at most; *n_windows = how many there are), the groups themselves window
  * after window in rows[0, cap_words) (256 words each: word (block << 2) | (row & 3) of group row >> 2; *n_words = how
  * many words there are, also when that exceeds cap_words), and the contig's share of summed_baseq from the push walk. */
 cl_status cl_debug_pass_rows(cl_ctx *ctx, uint32_t *n_groups, uint32_t n_win_cap, uint32_t *rows, uint64_t cap_words,
                              uint64_t *n_words, uint32_t *n_windows, uint64_t *summed_baseq);
+
+/* The pass-bit rows of the staged contig as cl_contig_upload builds them (pass_rows.h: rows_window_segments): a row stack
+ * per SEGMENT of 256 positions, 8 segments per window.  heights[8 w + s] = units of segment s of window w (a unit = 4
+ * rows x 8 blocks of 32 positions = 32 words: word ((block & 7) << 2) | (row & 3)), height_words[w] = the eight heights
+ * as the window's record carries them, one byte each, segment 0 lowest -- or 0, the equal-heights form: a segment beyond
+ * 255 units, or DUT_ROWS_UNIFORM=1 when the context was made -- (n_win_cap windows at most; *n_windows = how many there
+ * are), and the units themselves, window after window and segment after segment, in units[0, cap_words) (*n_words = how
+ * many words there are, also when that exceeds cap_words). */
+cl_status cl_debug_pass_rows_segments(cl_ctx *ctx, uint32_t *heights, uint64_t *height_words, uint32_t n_win_cap, uint32_t *units,
+                                      uint64_t cap_words, uint64_t *n_words, uint32_t *n_windows);
 
 /* ---- config 5: site-list pileup (haplogroup::caller::process_region,
  *      src/haplogroup/caller.rs:62-152) ---------------------------------------------------- */
