@@ -25,6 +25,7 @@ HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "pileup_bytes
            os.path.join(CSRC, "coverage_hook.h"),
            os.path.join(CSRC, "host_parallel.h"),
            os.path.join(CSRC, "qual_pack.h"), os.path.join(CSRC, "pass_rows.h"),
+           os.path.join(CSRC, "engine_limits.h"), os.path.join(CSRC, "host_stage.h"), os.path.join(CSRC, "tile_walk.h"),
            os.path.join(HERE, "..", "include", "callable_loci.h"),
            os.path.join(HERE, "..", "include", "dut_coverage.h"),
            os.path.join(HERE, "..", "include", "dut_bam.h"),

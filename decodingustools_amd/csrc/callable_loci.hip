@@ -4,7 +4,10 @@
 // pileup_rows.hip.h (k_pileup_rows, the pass-bit form: the product), pileup_bytes.hip.h (k_pileup, the byte forms of
 // DUT_QUAL_FORM=bytes) and kernels.hip.h (what both share: constants, the records between kernels and host, the wave
 // primitives, k_fin_windows and k_rle_write).  engine_base.hip.h holds the memory and transfer plumbing, site_engine.hip.h
-// the site engine (all parts of this translation unit).  No CPU fallback exists: without a HIP device cl_create fails.
+// the site engine (all parts of this translation unit).  What needs no device of the way a tile of reads enters -- the
+// staged contig, the record of a push, the checks, the first pass over a tile and the whole walk of the pass-bit form -- is
+// tile_walk.h, plain C++ that the sanitizer driver runs; here are the entries, the byte forms' device side (prefetch,
+// pinned ring, d_qual) and their share of the first pass.  No CPU fallback exists: without a HIP device cl_create fails.
 #include "../../include/callable_loci.h"
 #include "kernels.hip.h"
 #include "pileup_bytes.hip.h"
@@ -15,6 +18,7 @@
 #include "site_engine.hip.h"
 #include "qual_pack.h"
 #include "pass_rows.h"
+#include "tile_walk.h"
 
 using namespace clk;
 
@@ -25,57 +29,7 @@ using namespace clk;
 #endif
 constexpr uint32_t kT = CL_WINDOW;
 
-// The host staging arrays of a contig (hundreds of megabytes) are only needed between cl_contig_begin and
-// cl_contig_upload.  A context hands them to this process-wide pool when its contig is uploaded and takes a set back
-// at its next cl_contig_begin -- so does a fresh context: memory that has been touched before is written at several
-// times the rate of newly mapped pages (staging a chr21-sized contig: 5 ms against 31 ms), and callers that keep one
-// context per resident contig would otherwise fault a new set in for every contig.  At most kStagingSets sets are kept.
-struct StagingSet {
-    RawVec<uint8_t> ref, mapq;
-    RawVec<int32_t> pos;
-    RawVec<uint32_t> cigar_off, cigar;
-    RawVec<unsigned long long> qual_off;
-    // the index over the CIGARs, built by the one host walk that validates a tile (cl_push_reads): every read's end,
-    // and for reads with more than kLongOps operations the (reference, query) position before every 64th operation
-    // of the contig's CIGAR array
-    RawVec<uint32_t> end, ck_x, ck_y;
-    // per read, from the same walk: how many records the record forms get for it (gen_read_recs); their prefix sums
-    // are taken at upload: read i's records are rec[rec_of[i] .. rec_of[i + 1])
-    RawVec<uint32_t> rec_cnt, rec_of;
-    // pass-bit form (the default): bit g = quality byte g of the contig passes min_base_quality (mod.rs:33), taken in
-    // cl_push_reads' walk
-    RawVec<uint64_t> qbits;               // the reads' bit strings (reference order; pass_rows.h), word-aligned per read
-    RawVec<unsigned long long> rb_off;    // n + 1 word offsets into qbits (| dut::kRowSparse)
-};
-// Everything a context stages of its contig between cl_contig_begin and cl_contig_upload: the pooled arrays and the few
-// that are too small to pool.  A new array is added to clear() -- and to swap_pooled() if it is pooled --, nowhere else.
-namespace {
-struct Staging : StagingSet {
-    std::vector<uint8_t> qual;            // quality bytes of small tiles, not yet on the device (byte forms)
-    // reads whose reference span exceeds kWideSpan (ascending read index = ascending position)
-    std::vector<uint32_t> wide_idx;
-    std::vector<int32_t> wide_pos;
-    std::vector<uint32_t> wide_rec_of;    // prefix sums of the wide reads' record counts (n_wide + 1 entries; built at upload)
-    RawVec<uint32_t> sc_off, sc;          // pass-bit form: the CIGARs of the sparse reads (n + 1 offsets)
-    void swap_pooled(StagingSet &o)
-    {
-        ref.swap(o.ref); mapq.swap(o.mapq); pos.swap(o.pos); cigar_off.swap(o.cigar_off); cigar.swap(o.cigar); qual_off.swap(o.qual_off);
-        end.swap(o.end); ck_x.swap(o.ck_x); ck_y.swap(o.ck_y); rec_cnt.swap(o.rec_cnt); rec_of.swap(o.rec_of); qbits.swap(o.qbits); rb_off.swap(o.rb_off);
-    }
-    void clear()                          // (sizes only, the memory stays; but qual gives its memory back: only contigs of small tiles fill it)
-    {
-        ref.clear(); mapq.clear(); pos.clear(); cigar_off.clear(); cigar.clear(); qual_off.clear();
-        end.clear(); ck_x.clear(); ck_y.clear(); rec_cnt.clear(); rec_of.clear(); qbits.clear(); rb_off.clear();
-        std::vector<uint8_t>().swap(qual); wide_idx.clear(); wide_pos.clear(); wide_rec_of.clear(); sc_off.clear(); sc.clear();
-    }
-};
-} // namespace
-constexpr size_t kStagingSets = 2;
-static std::mutex g_staging_mu;
-static std::vector<std::unique_ptr<StagingSet>> g_staging;
-
 struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's state in its one member `site`)
-    uint64_t host_max_end = 0;         // largest pos + reference span over the pushed reads (32-bit clamped spans), for the extent
     dut::Thread prealloc;                             // cl_contig_reserve: the device buffers of the contig being pushed, allocated beside the push
     cl_options opt{};
     Opts dopt{};
@@ -85,30 +39,18 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     bool deep = false;               // this contig needs the 32-bit counter variant of k_pileup
     bool bits = true;                // the pass-bit form (default); DUT_QUAL_FORM=bytes at cl_create: the byte forms
     int form = 0;                    // the form of k_pileup the resident contig gets (pick_form, at upload)
-    bool has_long = false;           // some read has more than kLongOps CIGAR ops (its checkpoints are in hs.ck_x / hs.ck_y)
     int32_t tid = 0;
     uint32_t contig_len = 0;
-    Staging hs;                      // the staged arrays themselves
-    uint64_t q_dev = 0;              // quality bytes of this contig that already are on the device (d_qual + kQualPad ..)
+    Staging hs;                      // the staged arrays themselves (tile_walk.h)
+    PushRecord acc;                  // what the pushes of the contig being pushed have accumulated beside them (tile_walk.h)
     uint32_t n_rec = 0;
-    // from cl_push_reads' walk in the pass-bit form: the sum of the passing qualities over the M/=/X bases of the reads
-    // with mapq >= min_mapping_quality (contig_profiler.rs:65-70: summed_baseq is per-read separable)
-    uint64_t host_sum_q = 0;         // of the contig being pushed
-    // ... and the reads' other separable sums (contig_profiler.rs:74, 79-82): reference spans of the reads
-    // the pileup holds (-> summed_coverage) and mapq x span over those with mapq >= min_mapping_quality (-> summed_mapq)
-    uint64_t host_sum_cov = 0, host_sum_mapq = 0;
-    uint64_t dev_sum_cov = 0, dev_sum_mapq = 0;   // of the resident contig
+    uint64_t dev_sum_cov = 0, dev_sum_mapq = 0;   // of the resident contig: the reads' separable sums (acc.host_sum_cov, acc.host_sum_mapq at upload)
     uint32_t head_span = kHeadSpanMax;   // most positions one head of k_pileup_rows spans (DUT_HEAD_SPAN: a test hook)
     bool heads8_only = false;            // DUT_HEADS8=1 (a test hook): every contig gets 8-byte heads
     bool rows_uniform = false;           // DUT_ROWS_UNIFORM=1 (a test hook): every segment of a window as high as its highest
     bool heads4 = false;                 // the resident contig's heads are the 4-byte form (pileup_rows.hip.h: HEAD4)
-    uint64_t host_n_ops = 0;         // CIGAR operations pushed for it (pass-bit form: none is staged; for cl_contig_layout)
-    uint64_t dev_sum_q = 0;          // of the resident contig (handed to the summary workgroup of every run)
-    bool rec_counted = true;           // false: a tile of long-read shape skipped the count (cl_contig_upload makes up for it if the contig gets the short-read form after all)
-    uint32_t n_long = 0;                 // reads with more than kLongOps operations
-    uint32_t host_err = 0;               // kErrCigar / kErrRange found by that walk (reported by cl_contig_collect)
+    uint64_t dev_sum_q = 0;          // of the resident contig: acc.host_sum_q at upload (handed to the summary workgroup of every run)
     uint32_t bounds_err = 0;             // kErrRange raised by the window bounds (reported by cl_contig_collect)
-    uint32_t span_n = 0, span_w = 0; // longest span among the ordinary / the wide reads
     uint32_t n_wide = 0;
 
     // device residents
@@ -172,32 +114,6 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
 
 static SiteCtx *site_ctx(cl_ctx *c) { return c; }
 static void join_prealloc(cl_ctx *c) { if (c->prealloc.joinable()) c->prealloc.join(); }   // (cl_contig_reserve's helper thread)
-
-// a context without staging memory of its own takes a pooled set (cl_contig_begin) ...
-static void take_staging(cl_ctx *c)
-{
-    if (c->hs.pos.cap || c->hs.cigar.cap || c->hs.qual_off.cap || c->hs.qbits.cap) return;
-    std::unique_ptr<StagingSet> s;
-    {
-        std::lock_guard<std::mutex> g(g_staging_mu);
-        if (g_staging.empty()) return;
-        s = std::move(g_staging.back()); g_staging.pop_back();
-    }
-    c->hs.swap_pooled(*s);                                 // what the context had (nothing) is freed with s
-}
-// ... and gives its set back, empty, once the contig is on the device (cl_contig_upload); a full pool keeps the larger sets
-static void give_staging(cl_ctx *c)
-{
-    c->hs.clear();
-    std::unique_ptr<StagingSet> s(new (std::nothrow) StagingSet());
-    if (!s) return;
-    c->hs.swap_pooled(*s);
-    std::lock_guard<std::mutex> g(g_staging_mu);
-    if (g_staging.size() < kStagingSets) { g_staging.push_back(std::move(s)); return; }
-    size_t small = 0;
-    for (size_t i = 1; i < g_staging.size(); ++i) if (g_staging[i]->cigar_off.cap < g_staging[small]->cigar_off.cap) small = i;
-    if (g_staging[small]->cigar_off.cap < s->cigar_off.cap) g_staging[small].swap(s);      // s (the smaller one) is freed
-}
 
 namespace {
 
@@ -403,7 +319,7 @@ cl_status build_rec_index(cl_ctx *c)
     RawVec<uint32_t> &ro = c->hs.rec_of;
     ro.resize(n + 1);
     ro[0] = 0u;
-    if (!c->rec_counted) {
+    if (!c->acc.rec_counted) {
         // some tile looked like long reads and skipped the count, yet the contig as a whole gets the short-read form
         const int32_t *hp = c->hs.pos.data(); const uint8_t *hm = c->hs.mapq.data(); const uint32_t *he = c->hs.end.data();
         const uint32_t *hc = c->hs.cigar_off.data(), *hcig = c->hs.cigar.data(); const unsigned long long *hq = c->hs.qual_off.data();
@@ -412,7 +328,7 @@ cl_status build_rec_index(cl_ctx *c)
         dut::parallel_for(n, dut::grain_for(n, 65536), [&](size_t i) {
             cw[i] = gen_read_recs(hp[i], he[i], hm[i], min_mapq, hcig + hc[i], hc[i + 1] - hc[i], 0ull, hq[i + 1] - hq[i], [](uint32_t, const ReadRec &) {});
         });
-        c->rec_counted = true;
+        c->acc.rec_counted = true;
     }
     const uint32_t *cnt = c->hs.rec_cnt.data();
     const size_t grain = dut::grain_for(n, 262144), nchunk = n ? (n + grain - 1) / grain : 0;
@@ -449,12 +365,12 @@ void host_window_bounds(const cl_ctx *c, std::vector<WinMeta> &win, uint32_t &fl
     dut::parallel_for(c->n_win, 512, [&](size_t w) {
         const long long W = (long long)w * kT;
         WinMeta m;
-        m.lo = lb(pos, n, W - (long long)c->span_n + 1);
+        m.lo = lb(pos, n, W - (long long)c->acc.span_n + 1);
         m.hi = lb(pos, n, W + (long long)kT);
         m.wlo = 0; m.wn = 0;
         if (n_wide) {
-            m.wlo = lb(wpos, n_wide, W - (long long)c->span_w + 1);
-            m.wn = lb(wpos, n_wide, W - (long long)c->span_n + 1) - m.wlo;
+            m.wlo = lb(wpos, n_wide, W - (long long)c->acc.span_w + 1);
+            m.wn = lb(wpos, n_wide, W - (long long)c->acc.span_n + 1) - m.wlo;
         }
         m.q0 = 0; m.rlo = 0; m.rn = 0;
         if (!c->bits) {
@@ -1050,7 +966,7 @@ cl_status debug_rows_walk(cl_ctx *c, const char *who, uint32_t *n_windows, Build
 {
     return guarded(c, [&]() -> cl_status {
         if (!c || !c->in_contig || !c->bits) return fail(c, CL_ERR_INVALID, (std::string(who) + ": no staged contig in the pass-bit form").c_str());
-        const uint32_t extent = (uint32_t)std::max<uint64_t>(c->contig_len, c->host_max_end);
+        const uint32_t extent = (uint32_t)std::max<uint64_t>(c->contig_len, c->acc.host_max_end);
         const uint32_t n_win = (uint32_t)(((uint64_t)extent + kT - 1) / kT);
         c->n_win = n_win;
         if (n_windows) *n_windows = n_win;
@@ -1175,6 +1091,9 @@ void cl_destroy(cl_ctx *c)
 
 const char *cl_last_error(const cl_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
+// the staged contig and the record of its pushes as they are without a tile (cl_contig_begin, cl_contig_abort)
+static void drop_staged(cl_ctx *c) { c->hs.clear(); c->acc = PushRecord(); }
+
 cl_status cl_contig_begin(cl_ctx *c, int32_t tid, uint32_t contig_len, const uint8_t *ref_bases,
                           uint64_t ref_len)
 {
@@ -1183,19 +1102,14 @@ cl_status cl_contig_begin(cl_ctx *c, int32_t tid, uint32_t contig_len, const uin
         if (contig_len > 0xFFF00000u) return fail(c, CL_ERR_RANGE, "contig length beyond the engine's 32-bit range");
         if (ref_len && !ref_bases) return fail(c, CL_ERR_INVALID, "ref_bases is null");
         if (!c->host_only) { drop_prefetch(c); join_prealloc(c); }
-        take_staging(c);
+        take_staging(c->hs);
         c->tid = tid; c->contig_len = contig_len;
         const uint64_t nref = std::min<uint64_t>(ref_len, contig_len);
-        c->hs.clear();
+        drop_staged(c);
         c->hs.ref.append(ref_bases, nref); c->hs.cigar_off.push_back(0u); c->hs.qual_off.push_back(0ull);
         c->h_iv.clear();
-        c->q_dev = 0;
-        c->span_n = 0; c->span_w = 0; c->n_wide = 0; c->host_max_end = 0;
-        c->n_long = 0; c->host_err = 0; c->bounds_err = 0;
-        c->rec_counted = true;
-        c->host_sum_q = 0; c->host_n_ops = 0;
-        c->host_sum_cov = 0; c->host_sum_mapq = 0;
-        c->in_contig = true; c->uploaded = false; c->ran = false; c->has_long = false;
+        c->n_wide = 0; c->bounds_err = 0;
+        c->in_contig = true; c->uploaded = false; c->ran = false;
         return CL_OK;
     });
 }
@@ -1206,10 +1120,10 @@ cl_status flush_staged_qual(cl_ctx *c)
 {
     if (c->hs.qual.empty()) return CL_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, c->d_qual.grow_keep(c->q_dev + c->hs.qual.size() + 2 * kQualPad, kQualPad + c->q_dev, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_qual.p + kQualPad + c->q_dev, c->hs.qual.data(), c->hs.qual.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, c->d_qual.grow_keep(c->acc.q_dev + c->hs.qual.size() + 2 * kQualPad, kQualPad + c->acc.q_dev, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_qual.p + kQualPad + c->acc.q_dev, c->hs.qual.data(), c->hs.qual.size(), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->q_dev += c->hs.qual.size();
+    c->acc.q_dev += c->hs.qual.size();
     c->hs.qual.clear();
     return CL_OK;
 }
@@ -1226,12 +1140,12 @@ cl_status cl_contig_prefetch_qual(cl_ctx *c, const uint8_t *qual, uint64_t n_byt
         cl_status fs = flush_staged_qual(c);
         if (fs != CL_OK) return fs;
         HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, c->d_qual.grow_keep(c->q_dev + n_bytes + 2 * kQualPad, c->q_dev ? kQualPad + c->q_dev : 0, c->stream));
+        HIP_TRY(c, c->d_qual.grow_keep(c->acc.q_dev + n_bytes + 2 * kQualPad, c->acc.q_dev ? kQualPad + c->acc.q_dev : 0, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        cl_status rs = ring_start(c, c->d_qual.p + kQualPad + c->q_dev, n_bytes,
+        cl_status rs = ring_start(c, c->d_qual.p + kQualPad + c->acc.q_dev, n_bytes,
                                   [qual](uint64_t off, uint64_t len, uint8_t *out) { memcpy(out, qual + off, len); });
         if (rs != CL_OK) { (void)ring_finish(c); return rs; }
-        c->pf_src = qual; c->pf_n = n_bytes; c->pf_off = c->q_dev; c->pf_active = true;
+        c->pf_src = qual; c->pf_n = n_bytes; c->pf_off = c->acc.q_dev; c->pf_active = true;
         return CL_OK;
     });
 }
@@ -1280,298 +1194,87 @@ cl_status cl_contig_reserve(cl_ctx *c, uint64_t n_reads, uint64_t n_cigar_ops, u
         return CL_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, c->d_qual.grow_keep(n_qual_bytes + 2 * kQualPad, c->q_dev ? kQualPad + c->q_dev : 0, c->stream));
+    HIP_TRY(c, c->d_qual.grow_keep(n_qual_bytes + 2 * kQualPad, c->acc.q_dev ? kQualPad + c->acc.q_dev : 0, c->stream));
     return CL_OK;
 }
 
-// What cl_push_reads and cl_push_reads_bits check of a tile before they look at a read, over the arrays both tile structs
-// have; `who` names the caller in the one message that does.  An empty tile is h.n == 0 with CL_OK.
-struct TileHead { uint64_t n = 0, q0 = 0, ncig = 0, nq = 0; uint32_t cig0 = 0; };
+// a refusal of tile_walk.h as the status of the call, its message in the context
+static cl_status push_status(cl_ctx *c, const Offence &f) { return f.st == CL_OK ? CL_OK : fail(c, f.st, f.msg); }
+
+// what both entries check of a tile before they look at a read; `who` names the caller in the one message that does
 static cl_status tile_header(cl_ctx *c, const char *who, uint64_t n, const int32_t *pos, const uint8_t *mapq, const uint32_t *cigar_off,
                              const uint32_t *cigar, const uint64_t *qual_off, TileHead &h)
 {
     if (!c->in_contig || c->uploaded) return fail(c, CL_ERR_INVALID, std::string(who) + " outside cl_contig_begin .. upload");
-    if (n == 0) return CL_OK;
-    if (!pos || !mapq || !cigar_off || !qual_off) return fail(c, CL_ERR_INVALID, "null tile array");
-    if (c->hs.pos.size() + n >= (1ull << 29)) return fail(c, CL_ERR_RANGE, "more than 2^29 reads in one contig");
-    h.cig0 = cigar_off[0]; h.q0 = qual_off[0];
-    if (cigar_off[n] < h.cig0 || qual_off[n] < h.q0) return fail(c, CL_ERR_INVALID, "offset arrays must be non-decreasing");
-    h.ncig = (uint64_t)cigar_off[n] - h.cig0; h.nq = qual_off[n] - h.q0;
-    if (h.ncig && !cigar) return fail(c, CL_ERR_INVALID, "null cigar array");
-    h.n = n;
-    return CL_OK;
+    return push_status(c, tile_header(c->hs.pos.size(), n, pos, mapq, cigar_off, cigar, qual_off, h));
 }
+static WalkOpts walk_opts(const cl_ctx *c) { return {c->contig_len, c->opt.min_mapping_quality, c->opt.min_base_quality, c->head_span}; }
 
-// the first offence a tile's walk over its reads met (a chunk's `bad`, 1 .. 3), as the status and message of the refusal
-struct Offence { cl_status st; const char *msg; };
-static Offence walk_offence(int bad)
-{
-    if (bad == 1) return {CL_ERR_INVALID, "read position outside [0, contig_len): the region fetch (mod.rs:53) never yields it"};
-    if (bad == 2) return {CL_ERR_UNSORTED, "reads are not coordinate sorted"};
-    return {CL_ERR_INVALID, "offset arrays must be non-decreasing"};
-}
-
-// What both walks over a tile's reads (push_reads_bits, cl_push_reads_impl) keep per chunk of reads; it reaches the
-// context only when the whole tile is accepted (walk_fold), so that a refused tile leaves the context as it was.
-struct WalkChunk { int bad = 0; uint32_t err = 0, span_n = 0, span_w = 0; uint64_t max_end = 0; std::vector<uint32_t> wide; };
-// read i before its CIGAR is looked at: position and order (offences 1, 2: the walk goes on), offsets (3: false, no walk)
-static inline bool walk_read_checks(WalkChunk &o, const cl_read_tile *t, size_t i, int32_t &last, uint32_t contig_len, const TileHead &h)
-{
-    const int32_t p = t->pos[i];
-    if (p < 0 || (uint32_t)p >= contig_len) { if (!o.bad) o.bad = 1; }
-    else if (p < last) { if (!o.bad) o.bad = 2; }
-    last = p;
-    const bool ok = t->cigar_off[i + 1] >= t->cigar_off[i] && t->qual_off[i + 1] >= t->qual_off[i] &&
-                    t->cigar_off[i] >= h.cig0 && t->cigar_off[i + 1] <= h.cig0 + h.ncig && t->qual_off[i] >= h.q0 && t->qual_off[i + 1] <= h.q0 + h.nq;
-    if (!ok && !o.bad) o.bad = 3;
-    return ok;
-}
-// ... and once its CIGAR has given the reference length l: the end (beyond the engine's 32-bit coordinate range: flagged,
-// the read then spans nothing), the longest ordinary span (it bounds every window's candidate range), the wide list
-static inline void walk_close_span(WalkChunk &o, size_t i, int32_t p, unsigned long long l, uint32_t &end)
-{
-    const uint32_t sp = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
-    if (l <= 0xFFFF0000ull - (uint64_t)p) { end = (uint32_t)((uint64_t)p + l); o.max_end = std::max<uint64_t>(o.max_end, (uint64_t)p + l); }
-    else o.err |= kErrRange;
-    if (sp > kWideSpan) { o.wide.push_back((uint32_t)i); o.span_w = std::max(o.span_w, sp); }
-    else o.span_n = std::max(o.span_n, sp);
-}
-// a chunk of an accepted tile into the context (rbase: the contig's reads before this tile)
-static inline void walk_fold(cl_ctx *c, const WalkChunk &o, uint64_t rbase, const int32_t *pos)
-{
-    c->host_err |= o.err;
-    c->span_n = std::max(c->span_n, o.span_n); c->span_w = std::max(c->span_w, o.span_w);
-    c->host_max_end = std::max(c->host_max_end, o.max_end);
-    for (uint32_t i : o.wide) { c->hs.wide_idx.push_back((uint32_t)(rbase + i)); c->hs.wide_pos.push_back(pos[i]); }
-}
-
-// cl_push_reads of the pass-bit form: nothing goes to the device here.  One walk over the tile, in chunks on all host
-// threads, does everything that needs the reads' CIGAR operations and quality bytes while both are in the cache:
-// validation (what protects the later walks' indexing; the CIGAR shapes htslib's resolve_cigar2 asserts on), every
-// read's end (pos + bam_cigar2rlen, the pileup node span), the base-quality test of mod.rs:33 -- one
-// bit per base, qual_pack.cpp --, the read's share of summed_baseq (contig_profiler.rs:65-70) and, for every read with
-// mapq >= min_mapping_quality that is not a plain match, its pass bits mapped through the CIGAR into REFERENCE order
-// (pass_rows.h): what cl_contig_upload then lays out as rows is a string of bits per read, and no CIGAR is staged at all
-// (but those of reads whose span dwarfs their query: long N gaps).  A refused tile leaves the context as it was.
-// n bits of `src` from bit offset sb into dst[0, ceil(n / 64)): whole words, zeros above bit n
-static inline void copy_bits_to_words(uint64_t *dst, const uint64_t *src, unsigned long long sb, unsigned long long n)
-{
-    const unsigned long long w0 = sb >> 6;
-    const uint32_t s = (uint32_t)(sb & 63ull);
-    const unsigned long long nw = (n + 63) >> 6;
-    for (unsigned long long w = 0; w < nw; ++w) {
-        const unsigned long long left = n - (w << 6);                    // bits still wanted from here on (>= 1)
-        const uint32_t want = left >= 64ull ? 64u : (uint32_t)left;
-        uint64_t v = src[w0 + w] >> s;
-        if (s + want > 64u) v |= src[w0 + w + 1] << (64u - s);
-        if (want < 64u) v &= (1ull << want) - 1ull;
-        dst[w] = v;
-    }
-}
-
-// (pbits / psum: the packed variant, cl_push_reads_bits -- the caller has taken the base-quality test: bit
-// t->qual_off[i] + k of pbits <-> quality value k of read i, psum[i] the read's share of summed_baseq; t->qual is unused)
-static cl_status push_reads_bits(cl_ctx *c, const cl_read_tile *t, const TileHead &h, const uint64_t *pbits = nullptr, const uint32_t *psum = nullptr)
-{
-    const uint64_t n = h.n, q0 = h.q0, nq = h.nq;
-    const uint64_t rbase = c->hs.pos.size();
-    StageTimer tmr;
-    const size_t grain = dut::grain_for(n, 65536);
-    const size_t nchunk = (n + grain - 1) / grain;
-    struct Chunk : WalkChunk { uint64_t sum_q = 0, n_ops = 0, n_words = 0, n_sc = 0, sum_cov = 0, sum_mapq = 0; };
-    std::vector<Chunk> ch(nchunk);
-    const int32_t last0 = c->hs.pos.empty() ? 0 : c->hs.pos.back();
-    try {
-        c->hs.rec_cnt.reserve(rbase + n); c->hs.end.reserve(rbase + n);
-        c->hs.rb_off.reserve(rbase + n + 1); c->hs.sc_off.reserve(rbase + n + 1);
-    } catch (const std::bad_alloc &) {
-        return fail(c, CL_ERR_NOMEM, "host staging allocation failed");
-    }
-    // (entries [rbase, rbase + n) of the staging arrays are written below; their sizes follow when the tile is accepted,
-    // so a refused tile leaves nothing but unused capacity behind)
-    uint32_t *const h_end = c->hs.end.data() + rbase, *const h_rec_cnt = c->hs.rec_cnt.data() + rbase;
-    unsigned long long *const rb_off = c->hs.rb_off.data() + rbase;      // first the reads' word counts (| kRowSparse), then their offsets
-    uint32_t *const sc_off = c->hs.sc_off.data() + rbase;
-    const uint32_t min_mapq = c->opt.min_mapping_quality;
-    const uint8_t min_bq = c->opt.min_base_quality;
-    const uint64_t head_span = c->head_span;
-    const int plevel = dut::qual_pack_level();
-    const uint8_t *const qsrc = t->qual ? t->qual + q0 : nullptr;
-    // ---- first: what needs the CIGAR operations only -- validation, ends, how many words of bits every read will leave ----
-    dut::parallel_for(nchunk, 1, [&](size_t k) {
-        Chunk o;                                                // (on the walker's stack: neighbouring chunks of ch share cache lines)
-        const size_t a = k * grain, b = std::min<size_t>(n, a + grain);
-        int32_t last = a ? t->pos[a - 1] : last0;
-        for (size_t i = a; i < b; ++i) {
-            const int32_t p = t->pos[i];
-            h_end[i] = (uint32_t)p; h_rec_cnt[i] = 0u; rb_off[i] = 0ull; sc_off[i] = 0u;
-            if (!walk_read_checks(o, t, i, last, c->contig_len, h)) continue;
-            const uint32_t q0i = t->cigar_off[i], nops = t->cigar_off[i + 1] - q0i;
-            const uint32_t *cig = t->cigar + q0i;
-            o.n_ops += nops;
-            unsigned long long l = 0;
-            uint32_t zero_len = 0;
-            for (uint32_t q = 0; q < nops; ++q) {
-                const uint32_t cw = cig[q], len = cw >> 4;
-                const uint32_t radv = (0x18Du >> (cw & 15u)) & 1u;              // M D N = X consume the reference
-                l += len & (0u - radv);
-                zero_len |= radv & (len == 0u ? 1u : 0u);                      // zero-length reference-consuming op
+// What the byte forms do with a read in the first pass over a tile (walk_tile; the pass-bit form's share is BitsForm): for
+// reads with more than kLongOps operations the (reference, query) position before every operation whose index in the
+// contig's CIGAR array is a multiple of 64, where k_pileup starts its walk of such a read instead of at its first
+// operation; and the records the short-read form would get for the read, counted here where its CIGAR is hot.
+namespace {
+struct BytesChunk : WalkChunk {
+    uint32_t n_long = 0;
+    void fold(PushRecord &a) const { a.n_long += n_long; if (n_long) a.has_long = true; }
+};
+struct BytesForm {
+    const cl_read_tile *t;
+    uint32_t *rec_cnt, *ck_x, *ck_y;                               // (rec_cnt: this tile's entries; ck_x, ck_y: the contig's)
+    uint32_t shift;                                                // tile op index -> contig op index (mod 2^32)
+    uint32_t min_mapq;
+    // (a tile of long-read shape -- 8 or more operations per read -- will not get the short-read form: its reads'
+    // records are not counted here, that would be a second pass over every operation)
+    bool count_recs;
+    void blank(size_t i) const { rec_cnt[i] = 0u; }
+    bool ref_length(BytesChunk &o, size_t i, int32_t p, const uint32_t *cig, uint32_t nops, unsigned long long &l) const
+    {
+        if (nops <= kLongOps) return false;
+        o.n_long += 1;
+        uint32_t yq = 0;                                               // query advance (M I S = X), modulo 2^32
+        const uint32_t k0 = t->cigar_off[i] + shift;
+        for (uint32_t q = 0; q < nops; ++q) {
+            const uint32_t kc = k0 + q;
+            if ((kc & 63u) == 0u) {
+                const unsigned long long cx = (unsigned long long)(uint32_t)p + l;
+                ck_x[kc >> 6] = cx > 0xFFFF0000ull ? 0xFFFF0000u : (uint32_t)cx;
+                ck_y[kc >> 6] = yq;
             }
-            if (zero_len) o.err |= kErrCigar;
-            // a read that reaches a column with a single non-match op is undefined in htslib
-            if (l > 0 && nops == 1u && !(((0x181u >> (cig[0] & 15u)) & 1u) != 0u)) o.err |= kErrCigar;
-            walk_close_span(o, i, p, l, h_end[i]);
-            const bool in_pileup = h_end[i] != (uint32_t)p;
-            const uint64_t span = h_end[i] - (uint32_t)p;
-            // the heads k_pileup_rows reads: one, unless the span is beyond what a head holds
-            h_rec_cnt[i] = in_pileup ? (uint32_t)((span + head_span - 1) / head_span) : 0u;
-            // the read's shares of summed_coverage and summed_mapq (contig_profiler.rs:79-82, :74 -- over its columns,
-            // D and N included: SURVEY 8a-7)
-            o.sum_cov += span;
-            if (t->mapq[i] >= min_mapq) o.sum_mapq += (uint64_t)t->mapq[i] * span;
-            const unsigned long long ql = t->qual_off[i + 1] - t->qual_off[i];
-            if (!in_pileup || !ql || t->mapq[i] < min_mapq) continue;          // in no row (mod.rs:25, :33)
-            uint64_t nw;
-            if (nops == 1u) nw = (std::min<uint64_t>(span, ql) + 63) >> 6;     // a plain match: its thresholded string as it is
-            else if (span > 4 * ql + 1024) {                                   // a span that dwarfs the query: query order + the CIGAR
-                nw = ((ql + 63) >> 6) | dut::kRowSparse;
-                sc_off[i] = nops; o.n_sc += nops;
-            } else nw = (span + 63) >> 6;                                      // mapped into reference order below
-            rb_off[i] = nw;
-            o.n_words += nw & ~dut::kRowSparse;
+            const uint32_t cw = cig[q], len = cw >> 4, op = cw & 15u;
+            const bool radv = ((0x18Du >> op) & 1u) != 0u, qadv = ((0x193u >> op) & 1u) != 0u;
+            l += radv ? len : 0u;
+            yq += qadv ? len : 0u;
+            if (radv && len == 0u) o.err |= kErrCigar;
         }
-        ch[k] = std::move(o);
-    });
-    tmr.lap("push: validate + spans");
-    // (entry rbase of the two offset arrays closes the tiles before this one; the walk above used it for this tile's
-    // first read: put back whenever the tile is refused)
-    const unsigned long long closing_rb = c->hs.qbits.size();
-    const uint32_t closing_sc = (uint32_t)c->hs.sc.size();
-    auto refuse = [&](cl_status st, const char *m) { rb_off[0] = closing_rb; sc_off[0] = closing_sc; return fail(c, st, m); };
-    for (const Chunk &o : ch)                                  // the first offence in tile order decides the message
-        if (o.bad) { const Offence f = walk_offence(o.bad); return refuse(f.st, f.msg); }
-    // ---- where every chunk's strings go: behind the contig's ----
-    std::vector<uint64_t> rb_base(nchunk + 1), sc_base(nchunk + 1);
-    rb_base[0] = c->hs.qbits.size(); sc_base[0] = c->hs.sc.size();
-    for (size_t k = 0; k < nchunk; ++k) { rb_base[k + 1] = rb_base[k] + ch[k].n_words; sc_base[k + 1] = sc_base[k] + ch[k].n_sc; }
-    if (sc_base[nchunk] > 0xFFFFFFF0ull) return refuse(CL_ERR_RANGE, "more than 2^32 CIGAR operations of gapped reads in one contig");
-    size_t n_wide_new = 0;
-    for (const Chunk &o : ch) n_wide_new += o.wide.size();
-    try {
-        c->hs.qbits.reserve(rb_base[nchunk] + 2); c->hs.sc.reserve(sc_base[nchunk] + 1);
-        c->hs.pos.reserve(rbase + n); c->hs.mapq.reserve(rbase + n);
-        c->hs.wide_idx.reserve(c->hs.wide_idx.size() + n_wide_new); c->hs.wide_pos.reserve(c->hs.wide_pos.size() + n_wide_new);
-    } catch (const std::bad_alloc &) {
-        return refuse(CL_ERR_NOMEM, "host staging allocation failed");
+        return true;
     }
-    uint64_t *const bits = c->hs.qbits.data();
-    uint32_t *const scw = c->hs.sc.data();
-    // ---- then: what needs the quality bytes -- the base-quality test (one bit per base), the reads' shares of
-    //      summed_baseq, and the bits of every read that is not a plain match mapped through its CIGAR into reference
-    //      order -- written straight to their place (the chunks' ranges are disjoint) ----
-    std::atomic<bool> oom{false};
-    dut::parallel_for(nchunk, 1, [&](size_t k) {
-        uint64_t sum_q = 0;
-        const size_t a = k * grain, b = std::min<size_t>(n, a + grain);
-        uint64_t wat = rb_base[k], sat = sc_base[k];
-        RawVec<uint64_t> qw;                                    // a read's query-order bits
-        RawVec<dut::QueryStretch> um;                           // where its inserted / clipped bases lie
-        try {
-        for (size_t i = a; i < b; ++i) {
-            const unsigned long long cnt = rb_off[i];
-            const uint64_t nw = cnt & ~dut::kRowSparse;
-            rb_off[i] = wat | (cnt & dut::kRowSparse);
-            const uint32_t nsc = sc_off[i];
-            sc_off[i] = (uint32_t)sat;
-            if (!nw) continue;
-            const uint32_t q0i = t->cigar_off[i], nops = t->cigar_off[i + 1] - q0i;
-            const uint32_t *cig = t->cigar + q0i;
-            const unsigned long long ql = t->qual_off[i + 1] - t->qual_off[i];
-            const uint8_t *q = qsrc ? qsrc + (t->qual_off[i] - q0) : nullptr;
-            const uint64_t span = h_end[i] - (uint32_t)t->pos[i];
-            if (pbits) {
-                // the packed variant: the bits are there, in query order from bit qual_off[i]
-                const bool sparse = (cnt & dut::kRowSparse) != 0ull;
-                sum_q += psum[i];
-                if (nops == 1u) copy_bits_to_words(bits + wat, pbits, t->qual_off[i], std::min<uint64_t>(span, ql));
-                else if (sparse) {
-                    copy_bits_to_words(bits + wat, pbits, t->qual_off[i], ql);
-                    memcpy(scw + sat, cig, (size_t)nops * sizeof(uint32_t));
-                } else {
-                    const uint64_t nqw = (ql + 63) >> 6;
-                    qw.resize(nqw + 2); qw[nqw] = 0ull; qw[nqw + 1] = 0ull;
-                    copy_bits_to_words(qw.data(), pbits, t->qual_off[i], ql);
-                    um.resize(nops + 1);
-                    size_t n_um = 0; unsigned long long qlen = 0;
-                    dut::ref_bits_from_query(qw.data(), ql, cig, nops, bits + wat, um.data(), &n_um, &qlen);
-                }
-            } else if (nops == 1u) {
-                sum_q += dut::qual_pass_read(q, std::min<uint64_t>(span, ql), min_bq, bits + wat, plevel);
-            } else {
-                const uint64_t nqw = (ql + 63) >> 6;
-                const bool sparse = (cnt & dut::kRowSparse) != 0ull;
-                uint64_t *dstq;
-                if (sparse) dstq = bits + wat;
-                else { qw.resize(nqw + 2); dstq = qw.data(); dstq[nqw] = 0ull; dstq[nqw + 1] = 0ull; }   // (two readable words behind the bits: the mapping looks one word ahead of a clamped position)
-                const uint64_t all = dut::qual_pass_read(q, ql, min_bq, dstq, plevel);      // every byte of the string that passes ...
-                um.resize(nops + 1);
-                size_t n_um = 0; unsigned long long qlen = 0;
-                if (sparse) {
-                    // (a gapped read keeps its query-order bits and its CIGAR; the mapping below runs into a scratch word
-                    // count of zero: only the list of its inserted / clipped bases is wanted)
-                    memcpy(scw + sat, cig, (size_t)nops * sizeof(uint32_t));
-                    unsigned long long y = 0;
-                    for (uint32_t j = 0; j < nops; ++j) {
-                        const uint32_t cw = cig[j], op = cw & 15u, l = cw >> 4;
-                        if (!((0x193u >> op) & 1u)) continue;
-                        if (!((0x181u >> op) & 1u)) { um[n_um].y = y; um[n_um].l = l; ++n_um; }
-                        y += l;
-                    }
-                    qlen = y;
-                } else {
-                    // ... mapped through the CIGAR into reference order, here where the operations are in the cache
-                    dut::ref_bits_from_query(qw.data(), ql, cig, nops, bits + wat, um.data(), &n_um, &qlen);
-                }
-                sum_q += all - dut::unmatched_pass_sum(q, ql, um.data(), n_um, qlen, min_bq);   // ... minus those of inserted / clipped bases
-            }
-            wat += nw; sat += nsc;
-        }
-        } catch (const std::bad_alloc &) { oom.store(true); }
-        ch[k].sum_q = sum_q;
-    });
-    tmr.lap("push: pass bits in reference order");
-    if (oom.load()) return refuse(CL_ERR_NOMEM, "host staging allocation failed");
-    // ---- the tile is accepted (nothing below can fail: the capacity is there) ----
-    for (const Chunk &o : ch) {
-        walk_fold(c, o, rbase, t->pos);
-        c->host_sum_q += o.sum_q; c->host_n_ops += o.n_ops; c->host_sum_cov += o.sum_cov; c->host_sum_mapq += o.sum_mapq;
+    void read(BytesChunk &, size_t i, int32_t p, const uint32_t *cig, uint32_t nops, uint32_t end) const
+    {
+        if (!count_recs) return;
+        const unsigned long long ql = t->qual_off[i + 1] - t->qual_off[i];
+        // one M/=/X operation as long as the qualities (96 reads in 100 of aligner output): one record, no walk
+        if (nops == 1u && end != (uint32_t)p && ql < 0x10000ull && ((0x181u >> (cig[0] & 15u)) & 1u) && (cig[0] >> 4) == ql) rec_cnt[i] = 1u;
+        else rec_cnt[i] = gen_read_recs(p, end, t->mapq[i], min_mapq, cig, nops, 0ull, ql, [](uint32_t, const ReadRec &) {});
     }
-    c->hs.qbits.resize(rb_base[nchunk]); c->hs.sc.resize(sc_base[nchunk]);
-    c->hs.qbits.data()[rb_base[nchunk]] = 0ull;                 // the word deposit_bits may read behind the last string
-    c->hs.end.resize(rbase + n); c->hs.rec_cnt.resize(rbase + n);
-    c->hs.rb_off.resize(rbase + n + 1); c->hs.sc_off.resize(rbase + n + 1);
-    rb_off[n] = rb_base[nchunk]; sc_off[n] = (uint32_t)sc_base[nchunk];
-    c->hs.pos.append(t->pos, n);
-    c->hs.mapq.append(t->mapq, n);
-    tmr.lap("push: stage small arrays");
-    c->q_dev += nq;                                          // (the contig's quality bytes so far: none on the device)
-    return CL_OK;
-}
+};
+} // namespace
 
 static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
 {
     if (!c || !t) return CL_ERR_INVALID;
     TileHead h;
-    const cl_status hs = tile_header(c, "cl_push_reads", t->n_reads, t->pos, t->mapq, t->cigar_off, t->cigar, t->qual_off, h);
-    if (hs != CL_OK || h.n == 0) return hs;
+    const cl_status hst = tile_header(c, "cl_push_reads", t->n_reads, t->pos, t->mapq, t->cigar_off, t->cigar, t->qual_off, h);
+    if (hst != CL_OK || h.n == 0) return hst;
     const uint64_t n = h.n, q0 = h.q0, ncig = h.ncig, nq = h.nq;
     const uint32_t cig0 = h.cig0;
+    Staging &hs = c->hs;
     if (nq && !t->qual) return fail(c, CL_ERR_INVALID, "null qual array");
-    if (c->hs.cigar.size() + ncig > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "more than 2^32 CIGAR operations in one contig");
-    if (c->q_dev + c->hs.qual.size() + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality bytes in one contig");
-    if (c->bits) return push_reads_bits(c, t, h);      // the pass-bit form: no quality byte goes to the device
-    const uint32_t cbase = (uint32_t)c->hs.cigar.size();
-    const uint64_t rbase = c->hs.pos.size();
+    if (hs.cigar.size() + ncig > 0xFFFFFFF0ull) return fail(c, CL_ERR_RANGE, "more than 2^32 CIGAR operations in one contig");
+    if (c->acc.q_dev + hs.qual.size() + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality bytes in one contig");
+    if (c->bits) return push_status(c, push_reads_bits(hs, c->acc, walk_opts(c), t, h));   // the pass-bit form: no quality byte goes to the device
+    const uint32_t cbase = (uint32_t)hs.cigar.size();
+    const uint64_t rbase = hs.pos.size();
 
     // ---- a large tile: its quality bytes go from the caller's buffer to the device through the pinned staging
     //      ring, and they start now (unless cl_contig_prefetch_qual already sent exactly these bytes): the copier
@@ -1582,7 +1285,7 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
     const bool direct = nq >= kDirectQual;
     if (direct) {
         const uint8_t *src = t->qual + q0;
-        const bool prefetched = c->pf_active && c->pf_src == src && c->pf_n == nq && c->hs.qual.empty() && c->pf_off == c->q_dev;
+        const bool prefetched = c->pf_active && c->pf_src == src && c->pf_n == nq && hs.qual.empty() && c->pf_off == c->acc.q_dev;
         if (prefetched) {
             c->pf_active = false; c->pf_src = nullptr; c->pf_n = 0;
             ring.active = true;                               // the transfer in flight is this tile's
@@ -1591,9 +1294,9 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
             cl_status fs = flush_staged_qual(c);
             if (fs != CL_OK) return fs;
             HIP_TRY(c, hipSetDevice(c->device));
-            HIP_TRY(c, c->d_qual.grow_keep(c->q_dev + nq + 2 * kQualPad, c->q_dev ? kQualPad + c->q_dev : 0, c->stream));
+            HIP_TRY(c, c->d_qual.grow_keep(c->acc.q_dev + nq + 2 * kQualPad, c->acc.q_dev ? kQualPad + c->acc.q_dev : 0, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));          // the (re)allocation above is done
-            cl_status rs = ring_start(c, c->d_qual.p + kQualPad + c->q_dev, nq,
+            cl_status rs = ring_start(c, c->d_qual.p + kQualPad + c->acc.q_dev, nq,
                                       [src](uint64_t off, uint64_t len, uint8_t *out) { memcpy(out, src + off, len); });
             if (rs != CL_OK) return rs;
             ring.active = true;
@@ -1601,142 +1304,60 @@ static cl_status cl_push_reads_impl(cl_ctx *c, const cl_read_tile *t)
     } else if (c->pf_active) {
         drop_prefetch(c);
     }
-    const unsigned long long qbase = c->q_dev + c->hs.qual.size();
+    const unsigned long long qbase = c->acc.q_dev + hs.qual.size();
     StageTimer tmr;
 
-    // ---- the one walk over every CIGAR of the tile: validation that protects the kernels' indexing; the end of every
-    //      read (pos + bam_cigar2rlen, the pileup node span) -- the longest ordinary span bounds every
-    //      window's candidate range, reads wider than kWideSpan get their own list; the CIGAR shapes htslib's
-    //      resolve_cigar2 asserts on or indexes out of bounds for; and, for reads with more than kLongOps operations,
-    //      the (reference, query) position before every operation whose index in the contig's CIGAR array is a multiple
-    //      of 64, where k_pileup starts its walk of such a read instead of at its first operation.  In chunks, on all
-    //      host threads. ----
-    // (chunks of at most 65 536 reads; long reads -- few records, thousands of operations each -- get smaller ones so
-    // that every thread has some)
-    const size_t grain = dut::grain_for(n, 65536);
-    const size_t nchunk = (n + grain - 1) / grain;
-    struct Chunk : WalkChunk { uint32_t n_long = 0; };
-    std::vector<Chunk> ch(nchunk);
-    const int32_t last0 = c->hs.pos.empty() ? 0 : c->hs.pos.back();
+    // ---- the one walk over every CIGAR of the tile (walk_tile, BytesForm).  Its entries [rbase, rbase + n) of the
+    //      staging arrays, and the tile's checkpoints, are written beyond the arrays' sizes, as everything below is; the
+    //      sizes follow when the tile is accepted, so a refused tile leaves nothing but unused capacity behind ----
+    const size_t n_ck = ((cbase + ncig) >> 6) + 2;
     try {
-        c->hs.rec_cnt.reserve(rbase + n);
-        c->hs.end.reserve(rbase + n);                           // entries [rbase, rbase + n) are written below; the
-        c->hs.ck_x.reserve(((cbase + ncig) >> 6) + 2);          // sizes follow when the tile is accepted (a refused
-        c->hs.ck_y.reserve(((cbase + ncig) >> 6) + 2);          // tile leaves only unused capacity behind)
+        hs.rec_cnt.reserve(rbase + n); hs.end.reserve(rbase + n);
+        hs.ck_x.reserve(n_ck); hs.ck_y.reserve(n_ck);
     } catch (const std::bad_alloc &) {
-        return fail(c, CL_ERR_NOMEM, "host staging allocation failed");
+        return push_status(c, kNoMemory);
     }
-    uint32_t *const h_end = c->hs.end.data() + rbase, *const h_ck_x = c->hs.ck_x.data(), *const h_ck_y = c->hs.ck_y.data();
-    uint32_t *const h_rec_cnt = c->hs.rec_cnt.data() + rbase;
-    const uint32_t min_mapq = c->opt.min_mapping_quality;
-    // (a tile of long-read shape -- 8 or more operations per read -- will not get the short-read form: its reads'
-    // records are not counted here, that would be a second pass over every operation)
     const bool count_recs = ncig < 8ull * n;
-    dut::parallel_for(nchunk, 1, [&](size_t k) {
-        Chunk o;                                                // (on the walker's stack: neighbouring chunks of ch share cache lines)
-        const size_t a = k * grain, b = std::min<size_t>(n, a + grain);
-        int32_t last = a ? t->pos[a - 1] : last0;
-        for (size_t i = a; i < b; ++i) {
-            const int32_t p = t->pos[i];
-            h_end[i] = (uint32_t)p; h_rec_cnt[i] = 0u;
-            if (!walk_read_checks(o, t, i, last, c->contig_len, h)) continue;
-            const uint32_t q0i = t->cigar_off[i], q1i = t->cigar_off[i + 1], nops = q1i - q0i;
-            unsigned long long l = 0;
-            if (nops <= kLongOps) {
-                for (uint32_t q = q0i; q < q1i; ++q) {
-                    const uint32_t cw = t->cigar[q], len = cw >> 4;
-                    const bool radv = ((0x18Du >> (cw & 15u)) & 1u) != 0u;      // M D N = X consume the reference
-                    l += radv ? len : 0u;
-                    if (radv && len == 0u) o.err |= kErrCigar;                 // zero-length reference-consuming op
-                }
-                // a read that reaches a column with a single non-match op is undefined in htslib
-                if (l > 0 && nops == 1u && !(((0x181u >> (t->cigar[q0i] & 15u)) & 1u) != 0u)) o.err |= kErrCigar;
-            } else {
-                o.n_long += 1;
-                uint32_t yq = 0;                                               // query advance (M I S = X), modulo 2^32
-                const uint32_t shift = cbase - cig0;                           // tile op index -> contig op index (mod 2^32)
-                for (uint32_t q = q0i; q < q1i; ++q) {
-                    const uint32_t kc = q + shift;
-                    if ((kc & 63u) == 0u) {
-                        const unsigned long long cx = (unsigned long long)(uint32_t)p + l;
-                        h_ck_x[kc >> 6] = cx > 0xFFFF0000ull ? 0xFFFF0000u : (uint32_t)cx;
-                        h_ck_y[kc >> 6] = yq;
-                    }
-                    const uint32_t cw = t->cigar[q], len = cw >> 4, op = cw & 15u;
-                    const bool radv = ((0x18Du >> op) & 1u) != 0u, qadv = ((0x193u >> op) & 1u) != 0u;
-                    l += radv ? len : 0u;
-                    yq += qadv ? len : 0u;
-                    if (radv && len == 0u) o.err |= kErrCigar;
-                }
-            }
-            walk_close_span(o, i, p, l, h_end[i]);
-            // the records the short-read form would get for this read (counted here, where its CIGAR is hot)
-            if (count_recs) {
-                const unsigned long long ql = t->qual_off[i + 1] - t->qual_off[i];
-                const uint32_t mq = t->mapq[i];
-                uint32_t cnt;
-                // one M/=/X operation as long as the qualities (96 reads in 100 of aligner output): one record, no walk
-                if (nops == 1u && h_end[i] != (uint32_t)p && ql < 0x10000ull && ((0x181u >> (t->cigar[q0i] & 15u)) & 1u) && (t->cigar[q0i] >> 4) == ql)
-                    cnt = 1u;
-                else cnt = gen_read_recs(p, h_end[i], mq, min_mapq, t->cigar + q0i, nops, 0ull, ql, [](uint32_t, const ReadRec &) {});
-                h_rec_cnt[i] = cnt;
-            }
-        }
-        ch[k] = std::move(o);
-    });
+    const std::vector<BytesChunk> ch = walk_tile<BytesChunk>(t, h, hs.pos.empty() ? 0 : hs.pos.back(), c->contig_len, hs.end.data() + rbase,
+        BytesForm{t, hs.rec_cnt.data() + rbase, hs.ck_x.data(), hs.ck_y.data(), cbase - cig0, c->opt.min_mapping_quality, count_recs});
     tmr.lap("push: validate + spans");
-    for (const Chunk &o : ch)                                  // the first offence in tile order decides the message
-        if (o.bad) { const Offence f = walk_offence(o.bad); return fail(c, f.st, f.msg); }
+    if (const Offence f = first_offence(ch); f.st != CL_OK) return push_status(c, f);
 
-    // ---- staging of the small arrays (offsets rebased onto the contig's); undone if anything below fails, so that
-    //      a refused tile leaves the context as it was ----
-    struct Undo {
-        cl_ctx *c; size_t n_pos, n_cig, n_qual, n_wide; uint32_t n_long, host_err; bool has_long; uint32_t span_n, span_w; uint64_t max_end; bool armed = true;
-        ~Undo()
-        {
-            if (!armed) return;
-            c->hs.pos.resize(n_pos); c->hs.mapq.resize(n_pos); c->hs.cigar.resize(n_cig); c->hs.qual.resize(n_qual);
-            c->hs.cigar_off.resize(n_pos + 1); c->hs.qual_off.resize(n_pos + 1);
-            c->hs.wide_idx.resize(n_wide); c->hs.wide_pos.resize(n_wide); c->n_long = n_long; c->host_err = host_err;
-            c->hs.end.resize(n_pos); c->hs.ck_x.resize((n_cig >> 6) + 2); c->hs.ck_y.resize((n_cig >> 6) + 2);
-            c->hs.rec_cnt.resize(n_pos);
-            c->has_long = has_long; c->span_n = span_n; c->span_w = span_w; c->host_max_end = max_end;
-        }
-    } undo{c, c->hs.pos.size(), c->hs.cigar.size(), c->hs.qual.size(), c->hs.wide_idx.size(), c->n_long, c->host_err, c->has_long, c->span_n, c->span_w, c->host_max_end};
+    // ---- staging of the small arrays (offsets rebased onto the contig's): everything the tile can need is reserved,
+    //      then written in parallel while the ring moves the qualities ----
+    const size_t n_wide_new = wide_reads(ch);
     try {
-        for (const Chunk &o : ch) {
-            walk_fold(c, o, rbase, t->pos);
-            if (o.n_long) c->has_long = true;
-            c->n_long += o.n_long;
-        }
-        c->hs.end.resize(rbase + n); c->hs.ck_x.resize(((cbase + ncig) >> 6) + 2); c->hs.ck_y.resize(((cbase + ncig) >> 6) + 2);
-        c->hs.rec_cnt.resize(rbase + n);
-        if (!count_recs) c->rec_counted = false;
-        c->hs.pos.append(t->pos, n);
-        c->hs.mapq.append(t->mapq, n);
-        c->hs.cigar.append(t->cigar + cig0, ncig);
-        if (!direct) c->hs.qual.insert(c->hs.qual.end(), t->qual + q0, t->qual + q0 + nq);
-        const size_t o0 = c->hs.cigar_off.size();               // == rbase + 1: entry r+1 closes read r
-        c->hs.cigar_off.resize(o0 + n);
-        c->hs.qual_off.resize(o0 + n);
-        uint32_t *co = c->hs.cigar_off.data() + o0 - 1;
-        unsigned long long *qo = c->hs.qual_off.data() + o0 - 1;
-        dut::parallel_for(n, 262144, [&](size_t i) {
-            co[i + 1] = cbase + (t->cigar_off[i + 1] - cig0);
-            qo[i + 1] = qbase + (t->qual_off[i + 1] - q0);
-        });
+        hs.pos.reserve(rbase + n); hs.mapq.reserve(rbase + n); hs.cigar.reserve(cbase + ncig);
+        hs.cigar_off.reserve(rbase + n + 1); hs.qual_off.reserve(rbase + n + 1);   // (entry r + 1 closes read r)
+        hs.wide_idx.reserve(hs.wide_idx.size() + n_wide_new); hs.wide_pos.reserve(hs.wide_pos.size() + n_wide_new);
+        if (!direct) hs.qual.reserve(hs.qual.size() + nq);
     } catch (const std::bad_alloc &) {
-        return fail(c, CL_ERR_NOMEM, "host staging allocation failed");
+        return push_status(c, kNoMemory);
     }
+    copy_parallel(hs.pos.data() + rbase, t->pos, n);
+    copy_parallel(hs.mapq.data() + rbase, t->mapq, n);
+    copy_parallel(hs.cigar.data() + cbase, t->cigar + cig0, ncig);
+    uint32_t *co = hs.cigar_off.data() + rbase;
+    unsigned long long *qo = hs.qual_off.data() + rbase;
+    dut::parallel_for(n, 262144, [&](size_t i) {
+        co[i + 1] = cbase + (t->cigar_off[i + 1] - cig0);
+        qo[i + 1] = qbase + (t->qual_off[i + 1] - q0);
+    });
     tmr.lap("push: stage small arrays");
     if (ring.active) {
         ring.active = false;
-        cl_status rs = ring_finish(c);                         // a failed copy: the staged arrays are rolled back
+        cl_status rs = ring_finish(c);                         // a failed copy: nothing was committed
         if (rs != CL_OK) return rs;
     }
     tmr.lap("push: wait for the qualities");
-    if (direct) c->q_dev += nq;
-    undo.armed = false;
+    // ---- the tile is accepted (nothing below can fail: the capacity is there) ----
+    walk_fold(hs, c->acc, ch, rbase, t->pos);
+    if (!count_recs) c->acc.rec_counted = false;
+    hs.end.resize(rbase + n); hs.rec_cnt.resize(rbase + n); hs.ck_x.resize(n_ck); hs.ck_y.resize(n_ck);
+    hs.pos.resize(rbase + n); hs.mapq.resize(rbase + n); hs.cigar.resize(cbase + ncig);
+    hs.cigar_off.resize(rbase + n + 1); hs.qual_off.resize(rbase + n + 1);
+    if (direct) c->acc.q_dev += nq;
+    else hs.qual.insert(hs.qual.end(), t->qual + q0, t->qual + q0 + nq);
     return CL_OK;
 }
 
@@ -1756,12 +1377,12 @@ cl_status cl_push_reads_bits(cl_ctx *c, const cl_read_tile_bits *b)
         if (hs != CL_OK || h.n == 0) return hs;
         const uint64_t n = h.n, nq = h.nq;
         if (nq && (!b->pass_bits || !b->pass_sum)) return fail(c, CL_ERR_INVALID, "null pass_bits / pass_sum array");
-        if (c->q_dev + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality values in one contig");
+        if (c->acc.q_dev + nq >= (1ull << 38)) return fail(c, CL_ERR_RANGE, "more than 2^38 quality values in one contig");
         cl_read_tile t;
         t.n_reads = n; t.pos = b->pos; t.mapq = b->mapq; t.cigar_off = b->cigar_off; t.cigar = b->cigar; t.qual_off = b->qual_off; t.qual = nullptr;
         static const uint64_t kNoBits[2] = {0, 0};
         static const uint32_t kNoSum[1] = {0};
-        return push_reads_bits(c, &t, h, b->pass_bits ? b->pass_bits : kNoBits, b->pass_sum ? b->pass_sum : kNoSum);
+        return push_status(c, push_reads_bits(c->hs, c->acc, walk_opts(c), &t, h, b->pass_bits ? b->pass_bits : kNoBits, b->pass_sum ? b->pass_sum : kNoSum));
     });
 }
 
@@ -1774,13 +1395,13 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     drop_prefetch(c);
     join_prealloc(c);
     c->n_reads = (uint32_t)c->hs.pos.size();
-    c->n_cigar = c->bits ? c->host_n_ops : c->hs.cigar.size();
+    c->n_cigar = c->bits ? c->acc.host_n_ops : c->hs.cigar.size();
     if (!c->bits) {
         cl_status fs = flush_staged_qual(c);
         if (fs != CL_OK) return fs;
     }
-    c->n_qual = c->q_dev;
-    c->dev_sum_q = c->host_sum_q; c->dev_sum_cov = c->bits ? c->host_sum_cov : 0; c->dev_sum_mapq = c->bits ? c->host_sum_mapq : 0;
+    c->n_qual = c->acc.q_dev;
+    c->dev_sum_q = c->acc.host_sum_q; c->dev_sum_cov = c->bits ? c->acc.host_sum_cov : 0; c->dev_sum_mapq = c->bits ? c->acc.host_sum_mapq : 0;
     c->n_wide = (uint32_t)c->hs.wide_idx.size();
     const size_t n = c->n_reads;
     c->form = pick_form(c);
@@ -1817,7 +1438,7 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
         if ((rs = build_rec_index(c)) != CL_OK) return rs;
         tmr.lap("upload: record index");
         const uint32_t n_rec = c->n_rec;
-        c->heads4 = !c->heads8_only && c->n_wide == 0 && c->span_n <= c->head_span && c->span_n <= kWideSpan;
+        c->heads4 = !c->heads8_only && c->n_wide == 0 && c->acc.span_n <= c->head_span && c->acc.span_n <= kWideSpan;
         const size_t head_bytes = c->heads4 ? sizeof(uint32_t) : sizeof(uint2);
         HIP_TRY(c, c->d_heads.reserve((((size_t)n_rec + 1) * head_bytes + sizeof(uint2) - 1) / sizeof(uint2)));
         const int32_t *hp = c->hs.pos.data(); const uint8_t *hm = c->hs.mapq.data(); const uint32_t *he = c->hs.end.data();
@@ -1896,14 +1517,14 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     // a read overhanging the contig end makes the reference walk (and classify as REF_N, mod.rs:100-101) positions
     // up to its end: the extent is known from the spans computed at cl_push_reads
     tmr.lap("upload: small + sync");
-    cl_status s = size_for_extent(c, (uint32_t)std::max<uint64_t>(c->contig_len, c->host_max_end));
+    cl_status s = size_for_extent(c, (uint32_t)std::max<uint64_t>(c->contig_len, c->acc.host_max_end));
     if (s != CL_OK) return s;
     tmr.lap("upload: extent, ref, bounds");
     if (c->d_iv.cap == 0) HIP_TRY(c, c->d_iv.reserve(1u << 20));
     // The staged copy is no longer needed; its memory goes to the process's staging pool for the next contig, this
     // context's or another's (giving back and re-faulting a few hundred megabytes per contig was a fifth of a contig's
     // host time).
-    give_staging(c);
+    give_staging(c->hs);
     tmr.lap("upload: done");
     c->uploaded = true; c->ran = false;
     return CL_OK;
@@ -1992,7 +1613,7 @@ cl_status cl_debug_pass_rows(cl_ctx *c, uint32_t *n_groups, uint32_t n_win_cap, 
         used += nw;
     });
     if (s != CL_OK) return s;
-    if (summed_baseq) *summed_baseq = c->host_sum_q;
+    if (summed_baseq) *summed_baseq = c->acc.host_sum_q;
     if (n_words) *n_words = used;
     return CL_OK;
 }
@@ -2044,8 +1665,8 @@ cl_status cl_sync(cl_ctx *c)
 
 static cl_status check_summary(cl_ctx *c)
 {
-    if ((c->h_sum.err | c->bounds_err | c->host_err) & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
-    if ((c->h_sum.err | c->host_err) & kErrCigar)
+    if ((c->h_sum.err | c->bounds_err | c->acc.host_err) & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
+    if ((c->h_sum.err | c->acc.host_err) & kErrCigar)
         return fail(c, CL_ERR_CIGAR, "malformed CIGAR: zero-length reference-consuming operation, or a single non-match "
                                      "operation on a read that spans reference positions (undefined in htslib's pileup)");
     return CL_OK;
@@ -2135,8 +1756,7 @@ cl_status cl_contig_abort(cl_ctx *c)
         join_prealloc(c);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
     }
-    c->hs.clear();
-    c->q_dev = 0; c->host_sum_q = 0; c->host_n_ops = 0; c->host_sum_cov = 0; c->host_sum_mapq = 0;
+    drop_staged(c);
     c->in_contig = false; c->uploaded = false; c->ran = false;
     return CL_OK;
 }

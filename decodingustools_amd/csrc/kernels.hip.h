@@ -27,17 +27,14 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "engine_limits.h"
+
 namespace clk {
 
 constexpr int kBlock = 256;          // threads per workgroup (4 waves) of k_pileup and k_rle_write
-constexpr uint32_t kLongOps = 64;    // reads with more CIGAR ops get a checkpoint (reference, query position) before
-                                     // every 64th op (op numbering of the contig's CIGAR array): host side only
 constexpr int kQualPad = 32;         // bytes of padding in front of / behind the quality array
-constexpr uint32_t kWideSpan = 16384; // reads spanning more reference than this are "wide": looked up per window
-                                      // in their own list instead of widening every window's candidate range
 constexpr uint32_t kLutSize = 65536; // low-MAPQ threshold table entries (raw depth 0..65535)
-
-enum : uint32_t { kErrCigar = 1u, kErrRange = 2u, kNeedDeep = 4u, kNeedWide8 = 8u };
+// (kLongOps, kWideSpan, kHeadSpanMax and the kErr* / kNeed* bits: engine_limits.h, shared with the host's tile walk)
 
 // per-window output of a pileup kernel (k_pileup_rows or k_pileup)
 struct WinPartial {

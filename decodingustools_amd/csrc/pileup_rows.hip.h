@@ -10,9 +10,8 @@ namespace clk {
 // it, [pos, pos + span) (span = bam_cigar2rlen: D and N included; mod.rs:22-28), and whether its mapq is at or below
 // max_low_mapq (mod.rs:26-28).  Nothing else of a read is needed there: its M/=/X bases are in the rows, and its shares of
 // summed_coverage and summed_mapq (contig_profiler.rs:74, 79-82: per-read separable) are added up by
-// cl_push_reads' walk on the host.  A span of more than kHeadSpanMax positions is cut into several heads (the +-1
-// scatter of [a, b) and [b, c) is that of [a, c)); a read without a reference span has none.
-constexpr uint32_t kHeadSpanMax = 0x7FFFFFFFu;
+// cl_push_reads' walk on the host.  A span of more than kHeadSpanMax positions (engine_limits.h: 2^31 - 1) is cut into
+// several heads (the +-1 scatter of [a, b) and [b, c) is that of [a, c)); a read without a reference span has none.
 //
 // HEAD4, the 4-byte form of the same: pos & 0xFFFF | span << 16 | low << 31 -- for a contig in which every span fits 15
 // bits and none was cut (callable_loci.hip: no wide read, that is no span beyond kWideSpan = 16 384, and no head span

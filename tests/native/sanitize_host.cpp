@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE: drives the host-only parts of the library (BAM / FASTA reader, admission, BamStats,
 // JSON writer, tree parsing / scoring / report) under AddressSanitizer + UBSan or ThreadSanitizer on the CPU.
-// The device engine is not part of this binary: the few cl_* symbols the host sources reference are
-// defined below as failing stubs for the link only (nothing here reaches them).
+// The device engine is not part of this binary: the cl_* symbols the host sources reference are defined below as a
+// stand-in for the link and for the several-"device" orchestration.  The walk that takes a tile of reads into the engine
+// needs no device (tile_walk.h) and is the library's own here.
 #include "../../include/dut_coverage.h"
 #include "../../include/dut_bam.h"
 #include "../../include/dut_haplogroup.h"
@@ -9,6 +10,7 @@
 #include "../../decodingustools_amd/csrc/host_parallel.h"
 #include "../../decodingustools_amd/csrc/pass_rows.h"
 #include "../../decodingustools_amd/csrc/qual_pack.h"
+#include "../../decodingustools_amd/csrc/tile_walk.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -66,29 +68,102 @@ static unsigned long long checksum(const void *p, size_t n)
     return h;
 }
 
-// The host half of the pass-bit form (qual_pack.cpp, pass_rows.h) on random reads with buffers of exactly the documented
-// sizes, so that the sanitizers see every byte it touches: quality bytes -> pass bits (every level) -> reference order
-// through the CIGAR -> rows of one window range; the column sums must be what a per-base walk counts.
+// One round's reads as a caller hands them over, in arrays of exactly the sizes the interface names (the sanitizers see
+// every byte the walk touches beyond them), with what a per-base walk makes of every read.
+namespace {
+struct Reads {
+    std::vector<int32_t> pos; std::vector<uint8_t> mapq; std::vector<uint32_t> cigar_off{0u}, cigar;
+    std::vector<uint64_t> qual_off{0ull}; std::vector<uint8_t> qual;
+    std::vector<uint64_t> pass_bits; std::vector<uint32_t> pass_sum;      // the packed variant of the same (qual_pack)
+    std::vector<uint32_t> end;                                            // pos + span, or pos beyond the 32-bit range
+    std::vector<uint64_t> sum;                                            // the read's share of summed_baseq
+    uint32_t err = 0;                                                     // kErrCigar / kErrRange, as the walk has to find them
+    size_t n() const { return pos.size(); }
+    void add(uint32_t p, uint8_t mq, const std::vector<uint32_t> &cig, const std::vector<uint8_t> &q, uint8_t thr, uint32_t min_mapq, std::vector<uint32_t> &want)
+    {
+        unsigned long long span = 0, x = p, y = 0;
+        uint64_t sm = 0;
+        for (uint32_t cw : cig) { const uint32_t op = cw & 15u, l = cw >> 4; if ((0x18Du >> op) & 1u) { span += l; if (!l) err |= clk::kErrCigar; } }
+        if (span && cig.size() == 1 && !((0x181u >> (cig[0] & 15u)) & 1u)) err |= clk::kErrCigar;
+        const bool in_range = span <= 0xFFFF0000ull - p;
+        if (!in_range) err |= clk::kErrRange;
+        const bool in_rows = in_range && span && mq >= min_mapq && !q.empty();
+        for (uint32_t cw : cig) {                                         // what the column walk counts
+            const uint32_t op = cw & 15u, l = cw >> 4;
+            if (in_rows && ((0x181u >> op) & 1u))
+                for (uint32_t k = 0; k < l && y + k < q.size(); ++k)
+                    if (q[(size_t)(y + k)] >= thr) { sm += q[(size_t)(y + k)]; if (x + k < want.size()) want[(size_t)(x + k)] += 1; }
+            if ((0x18Du >> op) & 1u) x += l;
+            if ((0x193u >> op) & 1u) y += l;
+        }
+        pos.push_back((int32_t)p); mapq.push_back(mq); end.push_back(in_range ? p + (uint32_t)span : p); sum.push_back(sm);
+        cigar.insert(cigar.end(), cig.begin(), cig.end()); cigar_off.push_back((uint32_t)cigar.size());
+        qual.insert(qual.end(), q.begin(), q.end()); qual_off.push_back(qual.size());
+    }
+    // reads [a, b) as a tile: the offset arrays start at read a, the CIGAR and quality arrays are the contig's
+    Offence push(Staging &hs, PushRecord &acc, const WalkOpts &wo, size_t a, size_t b, bool packed) const
+    {
+        cl_read_tile t;
+        t.n_reads = b - a; t.pos = pos.data() + a; t.mapq = mapq.data() + a; t.cigar_off = cigar_off.data() + a; t.cigar = cigar.data();
+        t.qual_off = qual_off.data() + a; t.qual = packed ? nullptr : qual.data();
+        TileHead h;
+        const Offence f = tile_header(hs.pos.size(), t.n_reads, t.pos, t.mapq, t.cigar_off, t.cigar, t.qual_off, h);
+        if (f.st != CL_OK || h.n == 0) return f;
+        return packed ? push_reads_bits(hs, acc, wo, &t, h, pass_bits.data(), pass_sum.data() + a) : push_reads_bits(hs, acc, wo, &t, h);
+    }
+};
+
+// every staged array's size and the checksum of its [0, size) bytes, and every field of the push record
+std::vector<unsigned long long> snapshot(const Staging &hs, const PushRecord &a)
+{
+    std::vector<unsigned long long> v;
+    auto arr = [&](const auto &x) { v.push_back(x.size()); v.push_back(checksum(x.data(), x.size() * sizeof(*x.data()))); };
+    arr(hs.ref); arr(hs.mapq); arr(hs.pos); arr(hs.cigar_off); arr(hs.cigar); arr(hs.qual_off); arr(hs.end); arr(hs.ck_x); arr(hs.ck_y);
+    arr(hs.rec_cnt); arr(hs.rec_of); arr(hs.qbits); arr(hs.rb_off); arr(hs.qual); arr(hs.wide_idx); arr(hs.wide_pos); arr(hs.wide_rec_of);
+    arr(hs.sc_off); arr(hs.sc);
+    for (unsigned long long f : {(unsigned long long)a.host_max_end, (unsigned long long)a.host_sum_q, (unsigned long long)a.host_sum_cov,
+                                 (unsigned long long)a.host_sum_mapq, (unsigned long long)a.host_n_ops, (unsigned long long)a.host_err,
+                                 (unsigned long long)a.span_n, (unsigned long long)a.span_w, (unsigned long long)a.n_long,
+                                 (unsigned long long)a.has_long, (unsigned long long)a.rec_counted, (unsigned long long)a.q_dev})
+        v.push_back(f);
+    return v;
+}
+} // namespace
+
+// The host half of the pass-bit form on random reads, through the walk the library runs (tile_walk.h: push_reads_bits into
+// a staged contig, in several tiles, as bytes and packed) and the row builder (pass_rows.h): the column sums of four
+// windows must be what a per-base walk counts, the accumulated sums what the reads add up to, and a refused tile --
+// one in every round, between accepted ones -- must leave the staged contig and the push record as they were.
+constexpr int kRounds = 60, kRefusals = kRounds;
 static int pass_bit_selftest()
 {
     uint64_t state = 0x9E3779B97F4A7C15ull;
     auto rnd = [&](uint64_t m) { state ^= state << 13; state ^= state >> 7; state ^= state << 17; return state % m; };
-    constexpr uint32_t T = 2048;
-    int bad = 0;
-    for (int round = 0; round < 60; ++round) {
+    constexpr uint32_t T = 2048, kContigLen = 50'000'000u, kMinMapq = 10;
+    int bad = 0, tw_bad = 0, refusals = 0;
+    for (int round = 0; round < kRounds; ++round) {
+        auto miss = [&](const char *what) { ++tw_bad; fprintf(stderr, "tile walk selftest, round %d: %s\n", round, what); };
         const uint8_t thr = (uint8_t)(round % 3 == 0 ? 0 : (round % 3 == 1 ? 20 : 200));
-        const uint32_t n = 40 + (uint32_t)rnd(200);
-        std::vector<int32_t> pos; std::vector<uint32_t> end; std::vector<uint8_t> mapq;
-        std::vector<unsigned long long> off(1, 0ull); std::vector<uint32_t> sc_off(1, 0u), sc;
-        std::vector<uint64_t> bits;
+        const bool packed = round % 2 == 1, single = round % 6 >= 4;      // (single: one read per tile)
+        const int special = round % 15;                                    // 11 a wide read, 12 a span beyond 32 bits, 13 a zero-length D, 14 a lone non-match
+        WalkOpts wo;
+        wo.contig_len = kContigLen; wo.min_mapq = kMinMapq; wo.min_bq = thr;
+        if (round % 10 == 7) wo.head_span = 37;                            // (a DUT_HEAD_SPAN of the Python tests: spans cut into several heads)
+        const uint32_t n = 300 + (uint32_t)rnd(150);
+        Reads R;
         std::vector<uint32_t> want(4 * T, 0);                  // qc_depth of positions [0, 4 T)
         uint32_t p = 0;
         for (uint32_t i = 0; i < n; ++i) {
-            p += (uint32_t)rnd(120);
+            p += (uint32_t)rnd(36);
             std::vector<uint32_t> cig;
             const int kind = (int)rnd(5);
-            unsigned long long qlen = 0, span = 0;
-            if (kind == 0) { const uint32_t l = 1 + (uint32_t)rnd(300); cig.push_back(l << 4); }
+            unsigned long long qlen = 0;
+            bool no_qual = false;
+            if (i == n / 2 && special == 11) cig.push_back(20000u << 4);
+            else if (i == n / 2 && special == 12) { cig.push_back(10u << 4); for (int j = 0; j < 17; ++j) cig.push_back((0xFFFFFFFu << 4) | 3u); cig.push_back(10u << 4); }
+            else if (i == n / 2 && special == 13) { cig.push_back(30u << 4); cig.push_back((0u << 4) | 2u); cig.push_back(25u << 4); }
+            else if (i == n / 2 && special == 14) { cig.push_back((50u << 4) | 2u); no_qual = true; }   // (without a quality string: in no row)
+            else if (kind == 0) { const uint32_t l = 1 + (uint32_t)rnd(300); cig.push_back(l << 4); }
             else {
                 if (rnd(3) == 0) cig.push_back(((uint32_t)(1 + rnd(9)) << 4) | 4u);        // S
                 const int nops = 1 + (int)rnd(kind == 4 ? 150 : 12);
@@ -101,70 +176,88 @@ static int pass_bit_selftest()
                 }
                 cig.push_back(((uint32_t)(1 + rnd(30)) << 4) | 0u);
             }
-            for (uint32_t cw : cig) { const uint32_t op = cw & 15u, l = cw >> 4; if ((0x193u >> op) & 1u) qlen += l; if ((0x18Du >> op) & 1u) span += l; }
+            for (uint32_t cw : cig) { const uint32_t op = cw & 15u, l = cw >> 4; if ((0x193u >> op) & 1u) qlen += l; }
             unsigned long long ql = rnd(7) == 0 ? qlen / 2 : qlen;                             // sometimes a truncated quality string
-            if (rnd(23) == 0) ql = 0;
+            if (rnd(23) == 0 || no_qual) ql = 0;
             std::vector<uint8_t> q((size_t)ql);
             for (auto &b : q) b = (uint8_t)(rnd(4) == 0 ? rnd(256) : 30 + rnd(12));
-            const uint8_t mq = (uint8_t)(rnd(6) == 0 ? 3 : 60);
-            pos.push_back((int32_t)p); end.push_back(p + (uint32_t)span); mapq.push_back(mq);
-            // what the column walk counts
-            if (mq >= 10 && ql) {
-                unsigned long long x = p, y = 0;
-                for (uint32_t cw : cig) {
-                    const uint32_t op = cw & 15u, l = cw >> 4;
-                    if ((0x181u >> op) & 1u) for (uint32_t k = 0; k < l; ++k) if (y + k < ql && q[(size_t)(y + k)] >= thr && x + k < want.size()) want[(size_t)(x + k)] += 1;
-                    if ((0x18Du >> op) & 1u) x += l;
-                    if ((0x193u >> op) & 1u) y += l;
-                }
-            }
-            // what cl_push_reads leaves (push_reads_bits, second phase), with exact-size buffers
-            unsigned long long o0 = bits.size();
-            if (mq >= 10 && ql && span) {
-                if (cig.size() == 1) {
-                    const uint64_t nb = std::min<uint64_t>(span, ql);
-                    std::vector<uint64_t> w((size_t)((nb + 63) >> 6));
-                    const int level = round % 3;
-                    const uint64_t sm = dut::qual_pass_read(q.data(), nb, thr, w.data(), level);
-                    uint64_t naive = 0; for (uint64_t k = 0; k < nb; ++k) naive += q[(size_t)k] >= thr ? q[(size_t)k] : 0u;
-                    if (sm != naive) ++bad;
-                    bits.insert(bits.end(), w.begin(), w.end());
-                } else {
-                    const uint64_t nqw = (ql + 63) >> 6;
-                    const bool sparse = span > 4 * ql + 1024;
-                    std::vector<uint64_t> qw((size_t)nqw + 2, 0ull);
-                    const uint64_t all = dut::qual_pass_read(q.data(), ql, thr, qw.data(), 2);
-                    std::vector<dut::QueryStretch> um(cig.size() + 1);
-                    size_t n_um = 0; unsigned long long qcl = 0;
-                    if (sparse) {
-                        bits.insert(bits.end(), qw.begin(), qw.begin() + (size_t)nqw);
-                        sc.insert(sc.end(), cig.begin(), cig.end());
-                        o0 |= dut::kRowSparse;
-                    } else {
-                        std::vector<uint64_t> rw((size_t)((span + 63) >> 6));
-                        dut::ref_bits_from_query(qw.data(), ql, cig.data(), (uint32_t)cig.size(), rw.data(), um.data(), &n_um, &qcl);
-                        bits.insert(bits.end(), rw.begin(), rw.end());
-                        const uint64_t un = dut::unmatched_pass_sum(q.data(), ql, um.data(), n_um, qcl, thr);
-                        uint64_t naive = 0; unsigned long long y = 0;
-                        for (uint32_t cw : cig) { const uint32_t op = cw & 15u, l = cw >> 4; if ((0x181u >> op) & 1u) for (uint32_t k = 0; k < l; ++k) if (y + k < ql && q[(size_t)(y + k)] >= thr) naive += q[(size_t)(y + k)]; if ((0x193u >> op) & 1u) y += l; }
-                        if (all - un != naive) ++bad;
-                    }
-                }
-            }
-            off.back() = o0; off.push_back(bits.size());
-            sc_off.push_back((uint32_t)sc.size());
+            R.add(p, (uint8_t)(rnd(6) == 0 ? 3 : 60), cig, q, thr, kMinMapq, want);
         }
-        bits.push_back(0ull);                                   // the one word deposit_bits may read behind the last string
-        if (sc.empty()) sc.push_back(0u);
+        {   // the packed variant as a caller builds it: the bits of the whole quality array (every level of qual_pack), the reads' sums
+            R.pass_bits.assign((R.qual.size() + 63) / 64 + (R.qual.empty() ? 1 : 0), 0ull);
+            const uint64_t all = dut::qual_pass_read(R.qual.data(), R.qual.size(), thr, R.pass_bits.data(), round % 3);
+            uint64_t naive = 0;
+            for (uint8_t b : R.qual) naive += b >= thr ? b : 0u;
+            if (all != naive) miss("qual_pass_read's sum");
+            for (size_t i = 0; i < n; ++i) R.pass_sum.push_back((uint32_t)R.sum[i]);
+        }
+        // ---- the contig, staged as cl_contig_begin .. cl_push_reads do ----
+        Staging hs;
+        PushRecord acc;
+        take_staging(hs);
+        hs.clear(); hs.cigar_off.push_back(0u); hs.qual_off.push_back(0ull);
+        // the tiles: cut inside a 64-bit word of the bit array and inside a chunk of 64 reads; the one behind the first cut
+        // is first offered with an offence (three chunks or more: the offence lies in the first, a middle or the last)
+        auto cut_at = [&](size_t c) { while (c % 64 == 0 || R.qual_off[c] % 64 == 0 || (n - c) % 64 < 2) ++c; return c; };
+        const size_t c1 = cut_at(70 + (size_t)rnd(40)), c2 = cut_at(c1 + 130 + (size_t)rnd(30));
+        auto refused_tile = [&]() {
+            const size_t m = n - c1, nchunk = (m + 63) / 64;
+            const int what = round % 4, where = (round / 4) % 3;          // unsorted, outside the contig, offsets that decrease, offsets that leave the tile
+            size_t j = where == 0 ? (what == 0 ? 0 : 3) : (where == 1 ? 64 * (nchunk / 2) + 7 : 64 * (nchunk - 1));
+            Reads B = R;
+            Offence expect{CL_ERR_INVALID, "offset arrays must be non-decreasing"};
+            if (what == 0) { B.pos[c1 + j] = B.pos[c1 + j - 1] - 1; expect = {CL_ERR_UNSORTED, "reads are not coordinate sorted"}; }
+            else if (what == 1) {
+                B.pos[c1 + j] = round % 8 < 4 ? (int32_t)kContigLen : -1;
+                expect = {CL_ERR_INVALID, "read position outside [0, contig_len): the region fetch (mod.rs:53) never yields it"};
+            }
+            else if (what == 2) { if (round % 8 < 4) B.cigar_off[c1 + j + 1] = B.cigar_off[c1 + j] - 1; else B.qual_off[c1 + j + 1] = B.qual_off[c1 + j] - 1; }
+            else { if (round % 8 < 4) B.qual_off[c1 + j + 1] = B.qual_off[n] + 5; else B.cigar_off[c1 + j + 1] = B.cigar_off[n] + 3; }
+            const std::vector<unsigned long long> before = snapshot(hs, acc);
+            const Offence f = B.push(hs, acc, wo, c1, n, packed);
+            if (f.st != expect.st || !f.msg || strcmp(f.msg, expect.msg) != 0) miss("a refusal's status or message");
+            if (snapshot(hs, acc) != before) miss("a refused tile changed the staged contig or the push record");
+            ++refusals;
+        };
+        auto accept = [&](size_t a, size_t b) {
+            const uint64_t sum0 = acc.host_sum_q;
+            if (R.push(hs, acc, wo, a, b, packed).st != CL_OK) miss("a good tile was refused");
+            uint64_t add = 0;
+            for (size_t i = a; i < b; ++i) add += R.sum[i];
+            if (acc.host_sum_q - sum0 != add) miss("the tile's share of summed_baseq");   // (single: that one read's naive sum)
+        };
+        if (single) { for (size_t i = 0; i < n; ++i) { if (i == c1) refused_tile(); accept(i, i + 1); } }
+        else { accept(0, c1); refused_tile(); accept(c1, c2); accept(c2, n); }
+        // ---- what the walk left, against the per-base walk ----
+        uint64_t sum_cov = 0, sum_mapq = 0, max_end = 0;
+        uint32_t span_n = 0, span_w = 0;
+        std::vector<uint32_t> wide;
+        if (hs.pos.size() != n || hs.end.size() != n || hs.rec_cnt.size() != n || hs.rb_off.size() != n + 1 || hs.sc_off.size() != n + 1) miss("the staged sizes");
+        else for (size_t i = 0; i < n; ++i) {
+            const uint64_t span = R.end[i] - (uint32_t)R.pos[i];
+            unsigned long long l = 0;
+            for (uint32_t k = R.cigar_off[i]; k < R.cigar_off[i + 1]; ++k) if ((0x18Du >> (R.cigar[k] & 15u)) & 1u) l += R.cigar[k] >> 4;
+            if (hs.pos[i] != R.pos[i] || hs.mapq[i] != R.mapq[i] || hs.end[i] != R.end[i]) miss("a staged read");
+            if (hs.rec_cnt[i] != (span + wo.head_span - 1) / wo.head_span) miss("a read's head count");
+            sum_cov += span; if (R.mapq[i] >= kMinMapq) sum_mapq += R.mapq[i] * span;
+            if (l <= 0xFFFF0000ull - (uint64_t)R.pos[i]) max_end = std::max<uint64_t>(max_end, (uint64_t)R.pos[i] + l);
+            const uint32_t sp = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
+            if (sp > clk::kWideSpan) { wide.push_back((uint32_t)i); span_w = std::max(span_w, sp); } else span_n = std::max(span_n, sp);
+        }
+        if (acc.host_sum_cov != sum_cov || acc.host_sum_mapq != sum_mapq || acc.host_n_ops != R.cigar.size() || acc.q_dev != R.qual.size() ||
+            acc.host_max_end != max_end || acc.span_n != span_n || acc.span_w != span_w || acc.host_err != R.err || hs.wide_idx != wide)
+            miss("the push record");
+        if ((special == 11 && std::find(wide.begin(), wide.end(), n / 2) == wide.end()) || (special == 12 && !(R.err & clk::kErrRange)) || (special >= 13 && !(R.err & clk::kErrCigar)))
+            miss("the round's special read is not what it should be");
         dut::RowReads H;
-        H.pos = pos.data(); H.end = end.data(); H.mapq = mapq.data(); H.off = off.data(); H.bits = bits.data();
-        H.sc_off = sc_off.data(); H.sc = sc.data(); H.min_mapq = 10;
+        H.pos = hs.pos.data(); H.end = hs.end.data(); H.mapq = hs.mapq.data(); H.off = hs.rb_off.data(); H.bits = hs.qbits.data();
+        H.sc_off = hs.sc_off.data(); H.sc = hs.sc.data(); H.min_mapq = kMinMapq;
         std::vector<dut::RowCur> act;
         dut::RowScratch scr;
         uint32_t next = 0;
         for (uint32_t w = 0; w < 4; ++w) {
             const uint32_t W = w * T;
-            while (next < n && (uint32_t)pos[next] < W + T) { dut::rows_enter(act, H, next, W); ++next; }
+            while (next < n && (uint32_t)hs.pos[next] < W + T) { dut::rows_enter(act, H, next, W); ++next; }
             size_t cap = 2, ng;
             std::vector<dut::RowCur> start = act;
             std::vector<uint32_t> buf;
@@ -175,7 +268,9 @@ static int pass_bit_selftest()
                 if (cnt != want[W + x]) ++bad;
             }
         }
+        give_staging(hs);
     }
+    if (refusals != kRefusals) { ++tw_bad; fprintf(stderr, "tile walk selftest: %d refusal(s) instead of %d\n", refusals, kRefusals); }
     // the reference's "is N" bits, with buffers of exactly the sizes the interface names
     for (int round = 0; round < 40; ++round) {
         const size_t nb = (size_t)rnd(700), nw = (size_t)rnd(14);
@@ -189,7 +284,8 @@ static int pass_bit_selftest()
         }
     }
     printf("pass-bit selftest: %d mismatch(es)\n", bad);
-    return bad;
+    printf("tile walk selftest: %d mismatch(es), %d refusal(s)\n", tw_bad, kRefusals);
+    return bad + tw_bad;
 }
 
 int main(int argc, char **argv)

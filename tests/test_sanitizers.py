@@ -4,6 +4,7 @@ parsing / scoring / report) under AddressSanitizer + UBSan and under ThreadSanit
 import json
 import os
 import random
+import re
 import subprocess
 
 import numpy as np
@@ -71,6 +72,9 @@ def test_host_code_under_sanitizers(tmp_path, tag, flags, envvar):
     # the several-"device" call over the stand-in engine (one thread, reader pair and context per device): same BED text
     good = next(iter(outs[bams[0]]))
     assert "pass-bit selftest: 0 mismatch(es)" in good                 # the host half of the pass-bit form under the sanitizers
+    # ... through the library's own walk over a tile (tile_walk.h), refused tiles between the accepted ones
+    walk = re.search(r"tile walk selftest: 0 mismatch\(es\), (\d+) refusal\(s\)", good)
+    assert walk and int(walk.group(1)) > 0, good[:300]
     assert good.count("bytes same") == 3 and "DIFFERENT" not in good and "a device that does not exist: rc -2" in good, good[-800:]
     # the same records whatever the block layout / index
     body = lambda s: [ln.split(" admit")[0] for ln in s.splitlines() if ln.startswith("tid")]
