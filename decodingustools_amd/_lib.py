@@ -256,6 +256,31 @@ class dut_del_options(C.Structure):
                 ("min_del_count", C.c_uint32), ("min_del_per_strand", C.c_uint32)]
 
 
+class cl_cons_params(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_del_count", C.c_uint32), ("min_del_per_10k", C.c_uint32)]
+
+
+class cl_cons_result(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_low_depth", C.c_uint64), ("n_deleted", C.c_uint64), ("n_no_call", C.c_uint64),
+                ("n_ref", C.c_uint64), ("n_alt", C.c_uint64), ("cons", C.POINTER(C.c_uint8))]
+
+
+class dut_cons_change(C.Structure):
+    _fields_ = [("pos", C.c_uint32), ("end", C.c_uint32), ("kind", C.c_uint32), ("note", C.c_uint32), ("count", C.c_uint32), ("depth", C.c_uint32),
+                ("ref", C.c_char * 68), ("cons", C.c_char * 36)]
+
+
+class dut_cons_assembly(C.Structure):
+    _fields_ = [("seq", C.c_void_p), ("seq_len", C.c_uint64), ("changes", C.POINTER(dut_cons_change)), ("n_changes", C.c_size_t),
+                ("n_deletions", C.c_uint64), ("n_insertions", C.c_uint64), ("n_insertions_skipped", C.c_uint64)]
+
+
+class dut_cons_options(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_quality", C.c_uint8), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
+                ("exclude_flags", C.c_uint16), ("min_del_per_10k", C.c_uint32), ("min_del_count", C.c_uint32), ("min_ins_per_10k", C.c_uint32),
+                ("min_ins_count", C.c_uint32), ("fill_ref", C.c_int), ("line_width", C.c_uint32)]
+
+
 class dut_variants_options(C.Structure):
     _fields_ = [("filtered", C.c_int), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
                 ("exclude_flags", C.c_uint16), ("min_alt_per_strand", C.c_uint32)]
@@ -288,6 +313,8 @@ SYMBOLS = [
     ("cl_site_scan_ins", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_ins_params), C.c_void_p, C.c_uint64,
                                    C.c_uint32, C.c_uint32, C.POINTER(cl_ins_result)]),
     ("cl_site_scan_ins_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("cl_site_scan_consensus", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_cons_params), C.c_void_p, C.c_uint64,
+                                         C.c_uint32, C.c_uint32, C.POINTER(cl_cons_result)]),
     ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
     ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
@@ -316,6 +343,17 @@ SYMBOLS = [
     ("dut_ins_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_ins_result), C.POINTER(dut_ins_options), C.c_char_p, C.c_size_t]),
     ("dut_find_insertions_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_ins_options),
                                             C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
+    ("dut_cons_classify_counts", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(cl_cons_params),
+                                           C.c_uint8, C.c_char_p]),
+    ("dut_cons_assemble", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(cl_ins_result), C.c_void_p, C.c_size_t,
+                                    C.POINTER(cl_ins_params), C.c_int, C.POINTER(dut_cons_assembly)]),
+    ("dut_cons_assembly_free", None, [C.POINTER(dut_cons_assembly)]),
+    ("dut_cons_write_fasta", C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint64, C.c_uint32, C.c_char_p,
+                                       C.c_size_t]),
+    ("dut_cons_write_changes", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_cons_result), C.POINTER(dut_cons_assembly), C.POINTER(dut_cons_options),
+                                         C.c_char_p, C.c_size_t]),
+    ("dut_find_consensus_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_cons_options),
+                                           C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

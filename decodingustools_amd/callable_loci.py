@@ -346,6 +346,25 @@ class Engine:
         return InsResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), kept=int(r.n_kept), inserted=cand.shape[0],
                          candidates=cand, observations=obs, kernel_ms=self.site_scan_stats()[0])
 
+    def site_scan_consensus(self, min_quality, min_depth, min_del_count, min_del_per_10k, ref, start=0, end=None, filter=None):
+        """cl_site_scan_consensus over [start, end) of the resident tile: one byte per position -- the called base, '-' where
+        the deletion rule holds, 'N' for a mixed column, 'n' for a shallow one.  filter: None for the unfiltered form, else
+        (exclude_flags, use_base_quality) of the attachment.  There is no limit on end - start.  A ConsResult: the five class
+        counts, the bytes as a uint8 array (a copy) and the kernel's milliseconds."""
+        prm = _lib.cl_cons_params(int(min_depth), int(min_del_count), int(min_del_per_10k))
+        ref = np.ascontiguousarray(ref, np.uint8) if ref is not None else np.zeros(0, np.uint8)
+        if end is None:
+            end = ref.shape[0]
+        r = _lib.cl_cons_result()
+        self._check(self._lib.cl_site_scan_consensus(self._h, int(min_quality), _filter_ref(filter), C.byref(prm), _ptr(ref), ref.shape[0], int(start),
+                                                     int(end), C.byref(r)))
+        n = int(r.end) - int(r.start)
+        cons = np.zeros(n, np.uint8)
+        if n:
+            C.memmove(cons.ctypes.data, r.cons, n)
+        return ConsResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), deleted=int(r.n_deleted), no_call=int(r.n_no_call),
+                          ref=int(r.n_ref), alt=int(r.n_alt), cons=cons, kernel_ms=self.site_scan_stats()[0])
+
     def site_scan_ins_stats(self):
         """(window scan milliseconds, allele launch milliseconds) of the last site_scan_ins."""
         a = C.c_double(); b = C.c_double()
@@ -418,6 +437,21 @@ INS_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("pad", np.uint
 
 # cl_ins_obs: key = the first 32 inserted 4-bit codes, base j in key[j // 16] at bits 60 - 4 * (j % 16)
 INS_OBS = np.dtype([("pos", np.uint32), ("len", np.uint32), ("key", np.uint64, (2,)), ("strand", np.uint32), ("pad", np.uint32)])
+
+
+@dataclass
+class ConsResult:
+    """cl_cons_result (include/callable_loci.h): the five classes add up to end - start; cons[p - start] = the byte of
+    position p, one of n - A C G T N."""
+    start: int
+    end: int
+    low_depth: int
+    deleted: int
+    no_call: int
+    ref: int
+    alt: int
+    cons: np.ndarray
+    kernel_ms: float = 0.0
 
 
 @dataclass

@@ -1,5 +1,5 @@
 // dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
-// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions` and `find-insertions`);
+// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions`, `find-insertions` and `consensus`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -47,7 +47,10 @@ static void usage()
             "       [--min-del-per-strand K] [--device 0]\n"
             "       dut-coverage find-insertions <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--min-ins-fraction 0.7] [--min-ins-count 3] [--min-base-quality Q] [--exclude-flags MASK]\n"
-            "       [--min-ins-per-strand K] [--device 0]\n");
+            "       [--min-ins-per-strand K] [--device 0]\n"
+            "       dut-coverage consensus <BAM_FILE> -r <REFERENCE_FILE> -o <FASTA> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
+            "       [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3] [--min-ins-fraction 0.7] [--min-ins-count 3]\n"
+            "       [--min-base-quality Q] [--exclude-flags MASK] [--fill N|ref] [--line-width 60] [--changes FILE] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -236,7 +239,7 @@ static bool cli_count32(const char *flag, const std::string &v, uint32_t &dst)
     return true;
 }
 
-// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions) share on the command line: the BAM, -r, -o,
+// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions, consensus) share on the command line: the BAM, -r, -o,
 // -L, --region (0-based, half open), --min-depth, --min-quality, the two filter flags, --device, -h.
 struct ScanCli {
     const char *name;
@@ -461,6 +464,63 @@ static int find_insertions_main(int argc, char **argv)
                                                     c.out.c_str(), c.device, err, sizeof(err)), err);
 }
 
+static void usage_cs()
+{
+    fprintf(stderr, "Usage: dut-coverage consensus <BAM_FILE> -r <REFERENCE_FILE> -o <FASTA> -L <CONTIG> [--region START-END]\n"
+                    "       [--min-depth 10] [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3]\n"
+                    "       [--min-ins-fraction 0.7] [--min-ins-count 3] [--min-base-quality Q] [--exclude-flags MASK]\n"
+                    "       [--fill N|ref] [--line-width 60] [--changes FILE] [--device 0]\n"
+                    "  The sample's sequence over the contig or --region (0-based, half open): per position the called base (0.7 of\n"
+                    "  the depth, as find-variants calls it), nothing where find-deletions would call a deletion, N where the column\n"
+                    "  is mixed or too shallow (--fill ref: the lower-cased reference base where it is too shallow); behind a\n"
+                    "  position where find-insertions calls an insertion, its most frequent allele of at most 32 bases.  --changes:\n"
+                    "  a tab separated list of every difference from the reference.  No left-alignment, one device.\n");
+}
+
+// consensus: the called sequence of a contig or a region as FASTA (cl_site_scan_consensus for the bytes, cl_site_scan_ins for
+// what is spliced in), and the list of its differences from the reference.  Counting as in find-variants with its filter flags.
+static int consensus_main(int argc, char **argv)
+{
+    ScanCli c = {"consensus", usage_cs};
+    dut_cons_options o = {10, 20, 0, 0, 0, 7000, 3, 7000, 3, 0, 60};
+    std::string changes;
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        auto fraction = [&](uint32_t &dst) {
+            const std::string v = next();
+            char why[128] = {0};
+            if (dut_del_fraction_parse(v.c_str(), &dst, why, sizeof(why)) == CL_OK) return 1;
+            fprintf(stderr, "error: invalid value '%s' for '%s': %s\n", v.c_str(), a.c_str(), why);
+            return -1;
+        };
+        auto count = [&](uint32_t &dst) {
+            const std::string v = next();
+            if (!cli_count32(a.c_str(), v, dst)) return -1;
+            if (dst == 0) { fprintf(stderr, "error: invalid value '%s' for '%s': at least 1\n", v.c_str(), a.c_str()); return -1; }
+            return 1;
+        };
+        if (a == "--min-del-fraction") return fraction(o.min_del_per_10k);
+        if (a == "--min-ins-fraction") return fraction(o.min_ins_per_10k);
+        if (a == "--min-del-count") return count(o.min_del_count);
+        if (a == "--min-ins-count") return count(o.min_ins_count);
+        if (a == "--line-width") return count(o.line_width);
+        if (a == "--changes") { changes = next(); return 1; }
+        if (a == "--fill") {
+            const std::string v = next();
+            if (v == "N") o.fill_ref = 0;
+            else if (v == "ref") o.fill_ref = 1;
+            else { fprintf(stderr, "error: invalid value '%s' for '--fill'\n  [possible values: N, ref]\n", v.c_str()); return -1; }
+            return 1;
+        }
+        return 0;
+    });
+    if (st >= 0) return st;
+    c.filter_into(o);
+    o.min_depth = (uint32_t)c.min_depth; o.min_quality = (uint8_t)c.min_quality;
+    char err[1024] = {0};
+    return scan_cli_leave(dut_find_consensus_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), c.has_region ? 1 : 0, (uint32_t)c.start, (uint32_t)c.end, &o,
+                                                   c.out.c_str(), changes.empty() ? nullptr : changes.c_str(), c.device, err, sizeof(err)), err);
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -482,6 +542,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "find-minor-alleles")) return find_minor_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-deletions")) return find_deletions_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-insertions")) return find_insertions_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "consensus")) return consensus_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

@@ -165,6 +165,9 @@ struct SiteResident {
     DevBuf<ScanInsSite> si_site;
     DevBuf<ScanInsObs> si_obs;
     DevBuf<uint32_t> si_found;
+    // cl_site_scan_consensus: the packed bytes of the launched windows, four positions per word, and the range's bytes
+    DevBuf<uint32_t> sk_cons;
+    std::vector<uint8_t> cons_bytes;
     // the last cl_site_pileup / cl_site_run and the last cl_site_scan* of either form: the kernels' duration and their
     // algorithmic bytes; the candidates of the last cl_site_scan, cl_site_scan_ex, cl_site_scan_minor and cl_site_scan_dels
     KernelTimer t_pileup, t_scan;
@@ -179,7 +182,7 @@ struct SiteResident {
     {
         t_pileup.destroy(); t_scan.destroy();
         q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release(); sd_cand.release();
-        si_cand.release(); si_site.release(); si_obs.release(); si_found.release();
+        si_cand.release(); si_site.release(); si_obs.release(); si_found.release(); sk_cons.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -458,6 +461,7 @@ static_assert(sizeof(ScanInsCand) == sizeof(cl_ins_candidate) && sizeof(cl_ins_c
 static_assert(sizeof(ScanInsObs) == sizeof(cl_ins_obs) && sizeof(cl_ins_obs) == 32 && offsetof(ScanInsObs, strand) == offsetof(cl_ins_obs, strand),
               "the device writes cl_ins_obs");
 static_assert(sizeof(ScanInsSite) == 16, "one called position of the allele launch");
+static_assert(CONS_LOW_DEPTH == 0 && CONS_DELETED == 1 && CONS_NO_CALL == 2 && CONS_REF == 3 && CONS_ALT == 4, "the classes of cl_cons_result, in its order");
 
 // the argument checks every scan shares, in front of any device work
 static cl_status site_scan_check(SiteCtx *c, const char *who, uint32_t start, uint32_t end)
@@ -729,6 +733,33 @@ template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_INS> : ScanModeHostB
     }
 };
 
+// What every scan with a reference checks behind its own null result, in this order: site_scan_check_form, the mode's
+// parameters (fault: the first one it refuses, or null), the reference's length and pointer
+template <bool FILTERED>
+static cl_status site_scan_enter(SiteCtx *c, const char *who_c, typename ScanHost<FILTERED>::Filter filter, const char *fault, const uint8_t *ref_bases,
+                                 uint64_t ref_len, uint32_t start, uint32_t end)
+{
+    const std::string who = who_c;
+    const cl_status s = site_scan_check_form<FILTERED>(c, who_c, filter, start, end);
+    if (s != CL_OK) return s;
+    if (fault) return fail(c, CL_ERR_INVALID, who + ": " + fault);
+    if (ref_len != c->site.ref_len) return fail(c, CL_ERR_INVALID, who + ": ref_len differs from the one given to cl_site_upload");
+    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, who + ": null reference");
+    return CL_OK;
+}
+
+// the reference bytes of the range to the device (those that exist: positions at and beyond ref_len read as "other") and
+// the class counters' buffer; n_ref: the bytes sent
+static cl_status site_scan_reference(SiteCtx *c, const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, uint64_t &n_ref)
+{
+    SiteResident &S = c->site;
+    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len);
+    n_ref = ref_hi > start ? ref_hi - start : 0;
+    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
+    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
+    return CL_OK;
+}
+
 // A scan that compacts candidates, of any mode and form: the checks, the index, the reference bytes of the range, the
 // kernel until the candidates fit, the candidates back and in ascending position, the mode's post step.
 template <bool FILTERED, ScanMode MODE>
@@ -740,12 +771,9 @@ static cl_status site_scan_run(SiteCtx *c, uint8_t min_quality, typename ScanHos
     if (!c) return CL_ERR_INVALID;
     const std::string who = M::kWho;
     if (!out) return fail(c, CL_ERR_INVALID, who + ": null result");
-    cl_status s = site_scan_check_form<FILTERED>(c, M::kWho, filter, start, end);
+    cl_status s = site_scan_enter<FILTERED>(c, M::kWho, filter, M::fault(prm), ref_bases, ref_len, start, end);
     if (s != CL_OK) return s;
     SiteResident &S = c->site;
-    if (const char *fault = M::fault(prm)) return fail(c, CL_ERR_INVALID, who + ": " + fault);
-    if (ref_len != S.ref_len) return fail(c, CL_ERR_INVALID, who + ": ref_len differs from the one given to cl_site_upload");
-    if (!ref_bases && ref_len) return fail(c, CL_ERR_INVALID, who + ": null reference");
     std::vector<Cand> &cand = M::host_cand(S);
     auto &d_cand = M::dev_cand(S);
     memset(out, 0, sizeof(*out));
@@ -757,11 +785,8 @@ static cl_status site_scan_run(SiteCtx *c, uint8_t min_quality, typename ScanHos
     HIP_TRY(c, hipSetDevice(c->device));
     StageTimer tmr;
     if ((s = site_scan_index(c)) != CL_OK) return s;
-    // the reference bytes of the range (those that exist: positions at and beyond ref_len read as "other")
-    const uint64_t ref_hi = std::min<uint64_t>(end, ref_len);
-    const uint64_t n_ref = ref_hi > start ? ref_hi - start : 0;
-    HIP_TRY(c, S.sc_ref.reserve(n_ref + 16)); HIP_TRY(c, S.sc_cls.reserve(8));
-    if (n_ref) HIP_TRY(c, hipMemcpyAsync(S.sc_ref.p, ref_bases + start, n_ref, hipMemcpyHostToDevice, c->stream));
+    uint64_t n_ref = 0;
+    if ((s = site_scan_reference(c, ref_bases, ref_len, start, end, n_ref)) != CL_OK) return s;
     const uint32_t n_blocks = (end - 1) / kScanWin - start / kScanWin + 1;
     // candidates are few where the sample follows the reference: a buffer of a position in 64 (at least 64 K entries);
     // when more are wanted the kernel says how many, the buffer grows and the scan runs again -- nothing is cut short
@@ -806,6 +831,58 @@ static cl_status site_scan_either(SiteCtx *c, uint8_t min_quality, const cl_scan
 {
     if (filter) return site_scan_run<true, MODE>(c, min_quality, filter, rest...);
     return site_scan_run<false, MODE>(c, min_quality, ScanNoFilter{}, rest...);
+}
+
+// The consensus scan, of either form: one launch, one byte per position, five class counts.  It compacts nothing, so
+// there is no candidate buffer and nothing to grow: the checks, the index, the reference and the record's fill are those
+// of site_scan_run; the device buffer holds whole windows from the first one's start and the range is copied out of it.
+template <bool FILTERED>
+static cl_status site_scan_consensus_run(SiteCtx *c, uint8_t min_quality, typename ScanHost<FILTERED>::Filter filter, const cl_cons_params *prm,
+                                         const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end, cl_cons_result *out)
+{
+    static constexpr const char *kWho = "cl_site_scan_consensus";
+    if (!c) return CL_ERR_INVALID;
+    if (!out) return fail(c, CL_ERR_INVALID, std::string(kWho) + ": null result");
+    // (the deletion rule's parameters, refused as cl_site_scan_dels refuses them)
+    const cl_del_params dp = prm ? cl_del_params{prm->min_depth, prm->min_del_count, prm->min_del_per_10k} : cl_del_params{};
+    cl_status s = site_scan_enter<FILTERED>(c, kWho, filter, ScanModeHost<FILTERED, SCAN_DELS>::fault(prm ? &dp : nullptr), ref_bases, ref_len, start, end);
+    if (s != CL_OK) return s;
+    SiteResident &S = c->site;
+    memset(out, 0, sizeof(*out));
+    out->start = start; out->end = end;
+    S.cons_bytes.resize((size_t)(end - start));                 // (a second call over as many positions fills nothing in)
+    out->cons = S.cons_bytes.data();
+    S.t_scan.ms = 0.0; S.t_scan.bytes = 0;
+    if (start == end) return CL_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    StageTimer tmr;
+    if ((s = site_scan_index(c)) != CL_OK) return s;
+    uint64_t n_ref = 0;
+    if ((s = site_scan_reference(c, ref_bases, ref_len, start, end, n_ref)) != CL_OK) return s;
+    const uint32_t win0 = start / kScanWin, n_blocks = (end - 1) / kScanWin - win0 + 1;
+    HIP_TRY(c, S.sk_cons.reserve((size_t)n_blocks * kBlock));
+    HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
+    ScanModeArgs<FILTERED, SCAN_CONS> A;
+    site_scan_fill<FILTERED>(c, A, filter, min_quality, prm->min_depth, start, end);
+    A.t.min_count = prm->min_del_count; A.t.min_per_10k = prm->min_del_per_10k;
+    A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.cand = S.sk_cons.p;
+    HIP_TRY(c, S.t_scan.start(c->stream));
+    hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_CONS>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, S.t_scan.stop(c->stream));
+    unsigned long long h_cls[8];
+    HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
+    // the range's bytes: the buffer's byte 0 is position win0 * kScanWin
+    HIP_TRY(c, hipMemcpyAsync(S.cons_bytes.data(), reinterpret_cast<const uint8_t *>(S.sk_cons.p) + (start - win0 * kScanWin), (size_t)(end - start),
+                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, S.t_scan.read());
+    S.t_scan.bytes = ScanHost<FILTERED>::tile_bytes(S) + n_ref + (uint64_t)(end - start);
+    tmr.lap("consensus scan: reference in, kernel, bytes back");
+    out->n_low_depth = h_cls[CONS_LOW_DEPTH]; out->n_deleted = h_cls[CONS_DELETED]; out->n_no_call = h_cls[CONS_NO_CALL];
+    out->n_ref = h_cls[CONS_REF]; out->n_alt = h_cls[CONS_ALT];
+    out->cons = S.cons_bytes.data();
+    return CL_OK;
 }
 
 template <bool FILTERED>
@@ -930,6 +1007,15 @@ cl_status cl_site_scan_ins(cl_ctx *h, uint8_t min_quality, const cl_scan_filter 
     return site_entry(h, [&](SiteCtx *c) {
         if (c) c->site.ins_scan_ms = c->site.ins_alleles_ms = 0.0;
         return site_scan_either<SCAN_INS>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
+    });
+}
+
+cl_status cl_site_scan_consensus(cl_ctx *h, uint8_t min_quality, const cl_scan_filter *filter, const cl_cons_params *params, const uint8_t *ref_bases,
+                                 uint64_t ref_len, uint32_t start, uint32_t end, cl_cons_result *out)
+{
+    return site_entry(h, [&](SiteCtx *c) {
+        if (filter) return site_scan_consensus_run<true>(c, min_quality, filter, params, ref_bases, ref_len, start, end, out);
+        return site_scan_consensus_run<false>(c, min_quality, ScanNoFilter{}, params, ref_bases, ref_len, start, end, out);
     });
 }
 

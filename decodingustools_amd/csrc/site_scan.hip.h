@@ -23,7 +23,8 @@
 //                       the MODE: the counters themselves go out (SCAN_DENSE), or every thread judges positions and the
 //                       candidates are compacted with one ballot and one atomic per wave -- by the calling rule
 //                       (SCAN_CALLS), the second-allele rule (SCAN_MINOR), the deletion rule (SCAN_DELS) or the insertion
-//                       rule (SCAN_INS).
+//                       rule (SCAN_INS) -- or every position gets one byte of the called sequence and nothing is
+//                       compacted (SCAN_CONS).
 //   k_site_scan_settle  filtered form only: the 16-code histogram of the few positions the planes cannot classify.
 //   k_site_scan_ins_alleles<FILTERED>
 //                       behind SCAN_INS: what was inserted at the called positions, one workgroup per position.
@@ -74,6 +75,15 @@
 // low_depth (depth < min_depth), inserted (ins >= min_ins_count and 10000 ins >= min_ins_per_10k depth, in 64 bits) or
 // kept, and only for the inserted ones does k_site_scan_ins_alleles fetch the inserted bases: per counting insertion one
 // observation {pos, len, key, strand}, key being the first 32 inserted 4-bit codes, most significant nibble first.
+//
+// The consensus mode (cl_site_scan_consensus) composes the calling rule and the deletion rule into one byte per position:
+// planes A C G T rest del in both forms (strands are not kept: 24 KB, six workgroups per CU under a filter too), bases
+// added as in the calling modes, del built from range ends and scanned as in the deletion mode.  span = depth + del; a
+// position is low_depth (span < min_depth: n), deleted (the deletion rule over span: -), low_depth again (depth <
+// min_depth: n), ref or alt (10 m >= 7 depth for the largest m of A C G T, the first among equals: the base) or no_call
+// (N).  If the rest plane held 7/10 of the depth m would hold less than 3/10: nothing is ambiguous, nothing is settled.
+// It compacts nothing: every thread packs its four positions' bytes into one word of a buffer indexed from the first
+// window's start, and the class counts go through scan_reduce_classes.
 #pragma once
 
 #include <type_traits>
@@ -135,7 +145,10 @@ struct ScanInsObs {
     uint32_t strand, pad;                    // 1 reverse (always 0 in the unfiltered form)
 };
 
-enum ScanMode { SCAN_CALLS = 0, SCAN_DENSE = 1, SCAN_MINOR = 2, SCAN_DELS = 3, SCAN_INS = 4 };
+enum { CONS_LOW_DEPTH = 0, CONS_DELETED = 1, CONS_NO_CALL = 2, CONS_REF = 3, CONS_ALT = 4 };   // the consensus mode's classes, in the first slots of cls
+constexpr uint32_t kConsPad = 0;             // the byte of a position of a launched window outside the range
+
+enum ScanMode { SCAN_CALLS = 0, SCAN_DENSE = 1, SCAN_MINOR = 2, SCAN_DELS = 3, SCAN_INS = 4, SCAN_CONS = 5 };
 
 struct ScanNoHook {};                        // a hook of scan_walk_read that a mode does not use
 template <class T> inline constexpr bool scan_hooked = !std::is_same_v<std::remove_cv_t<std::remove_reference_t<T>>, ScanNoHook>;
@@ -212,6 +225,11 @@ template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_INS> {
     using Thresholds = ScanThresholds;
     static __device__ __forceinline__ bool emits(int cls) { return cls == INS_INSERTED; }
 };
+// the consensus mode compacts nothing: its "candidates" are the packed bytes, one word per four positions
+template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_CONS> {
+    using Cand = uint32_t;
+    using Thresholds = ScanThresholds;                                       // the deletion rule's
+};
 template <bool FILTERED, ScanMode MODE> struct ScanModeArgs {                // the kernel's record
     ScanArgs s;
     typename ScanForm<FILTERED>::Filter f;
@@ -219,14 +237,17 @@ template <bool FILTERED, ScanMode MODE> struct ScanModeArgs {                // 
     [[no_unique_address]] typename ScanModeTraits<FILTERED, MODE>::Thresholds t;
 };
 
-// LDS planes of a mode: depth and del (ins) by strand in the deletion (insertion) mode (8 KB, 16 KB), the form's base
-// planes otherwise
+// LDS planes of a mode: depth and del (ins) by strand in the deletion (insertion) mode (8 KB, 16 KB); A C G T rest del in
+// the consensus mode, which keeps no strands (24 KB in both forms); the form's base planes otherwise
 template <ScanMode MODE> inline constexpr bool kScanTwoCounts = MODE == SCAN_DELS || MODE == SCAN_INS;
-template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanPlanes = kScanTwoCounts<MODE> ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
+constexpr uint32_t kConsPlanes = 6u, kConsRest = 4u, kConsDel = 5u;
+template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanPlanes = MODE == SCAN_CONS ? kConsPlanes
+                                                                              : kScanTwoCounts<MODE> ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
 // ... of which the last kScanEnds hold range ends that one workgroup-wide scan each turns into counts: both unfiltered
-// planes and the del planes under a filter in the deletion mode; the unfiltered depth plane, the first, in the insertion mode
-template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds = MODE == SCAN_DELS ? 2u : (MODE == SCAN_INS && !FILTERED) ? 1u : 0u;
-template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds0 = MODE == SCAN_DELS ? kScanPlanes<FILTERED, MODE> - 2u : 0u;
+// planes and the del planes under a filter in the deletion mode; the unfiltered depth plane, the first, in the insertion
+// mode; the del plane, the last, in the consensus mode
+template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds = MODE == SCAN_DELS ? 2u : ((MODE == SCAN_INS && !FILTERED) || MODE == SCAN_CONS) ? 1u : 0u;
+template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds0 = MODE == SCAN_DELS ? kScanPlanes<FILTERED, MODE> - 2u : MODE == SCAN_CONS ? kConsDel : 0u;
 
 // number of CIGAR operations and bases of a read, with SiteRec's escape to the next record's offsets
 __device__ __forceinline__ void scan_read_extent(const SiteRec *rec, uint32_t r, const uint4 &rr, uint32_t &k1, unsigned long long &slen)
@@ -435,6 +456,25 @@ __device__ __forceinline__ int scan_classify_minor(const uint32_t (&cnt)[4], uns
     return (c2 >= min_minor_count && 10000ull * c2 >= (unsigned long long)min_minor_per_10k * depth) ? MINOR_MINOR : MINOR_SINGLE;
 }
 
+// The consensus rule: the deletion rule over span = depth + del first, then the calling rule over A C G T alone (rest: N
+// and every other code, which take part only through the depth).  Returns the class; byte becomes n, -, the called base or N.
+__device__ __forceinline__ int scan_classify_cons(uint32_t A, uint32_t Cc, uint32_t G, uint32_t T, uint32_t rest, uint32_t del, uint32_t rb, uint32_t min_depth,
+                                                  uint32_t min_del_count, uint32_t min_del_per_10k, uint32_t &byte)
+{
+    const unsigned long long depth = (unsigned long long)A + Cc + G + T + rest, span = depth + del;
+    uint32_t m = A, called = 'A';
+    if (Cc > m) { m = Cc; called = 'C'; }
+    if (G > m) { m = G; called = 'G'; }
+    if (T > m) { m = T; called = 'T'; }
+    byte = 'n';
+    if (span < min_depth) return CONS_LOW_DEPTH;
+    if (del >= min_del_count && 10000ull * del >= (unsigned long long)min_del_per_10k * span) { byte = '-'; return CONS_DELETED; }
+    if (depth < min_depth) return CONS_LOW_DEPTH;
+    if (10ull * m >= 7ull * depth) { byte = called; return called == (rb & ~32u) ? CONS_REF : CONS_ALT; }
+    byte = 'N';
+    return CONS_NO_CALL;
+}
+
 // The tail of the two rule modes (the calling rule keeps its own, in the kernel).  A thread has kScanWin / kBlock
 // positions: offset(j) is the window offset o of its j-th, judge(j, o, ref, cd) returns the class of position ws + o and
 // fills cd but for its pos, ref() being the reference byte as sent ('N' at and beyond hi).  The emitted class is compacted.
@@ -464,7 +504,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
     using Form = ScanForm<FILTERED>;
     constexpr uint32_t S = Form::kStrands;
     constexpr uint32_t kPlanes = kScanPlanes<FILTERED, MODE>;
-    __shared__ alignas(kScanTwoCounts<MODE> ? 16 : 8) uint32_t s_cnt[kPlanes * kScanWin];   // (the deletion and insertion modes read it four words at a time)
+    __shared__ alignas(kScanTwoCounts<MODE> || MODE == SCAN_CONS ? 16 : 8) uint32_t s_cnt[kPlanes * kScanWin];   // (the deletion, insertion and consensus modes read it four words at a time)
     const ScanArgs &a = ax.s;
     const uint32_t tid = threadIdx.x;
     const uint32_t w = a.win0 + blockIdx.x;
@@ -483,7 +523,25 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
                 if (fl & ax.f.exclude_flags) continue;
                 rev = (fl >> 4) & 1u;
             }
-            if constexpr (kScanTwoCounts<MODE>) {
+            if constexpr (MODE == SCAN_CONS) {
+                // planes: A C G T rest, one add per base; del from range ends, as in the deletion mode, under its carrier gate
+                scan_walk_read(a, r, rr, lo, hi,
+                    [&](unsigned long long bi, bool any) {
+                        if constexpr (FILTERED) return scan_pass_word(ax.f, bi, any); else return ScanNoFilter{};
+                    },
+                    [&](uint32_t p, unsigned long long bi, auto &pw) {
+                        if constexpr (FILTERED) { if (!scan_base_passes(ax.f, bi, pw)) return; }
+                        const uint32_t code = scan_base_code(a.seq4, bi);
+                        const uint32_t plane = code == 1u ? 0u : code == 2u ? 1u : code == 4u ? 2u : code == 8u ? 3u : kConsRest;
+                        atomicAdd(&s_cnt[plane * kScanWin + (p - ws)], 1u);
+                    },
+                    ScanNoHook{},
+                    [&](uint32_t p0, uint32_t p1, unsigned long long ci) {
+                        if constexpr (FILTERED) { if (ax.f.use_bq && !((ax.f.pass[ci >> 6] >> (ci & 63ull)) & 1ull)) return; }
+                        atomicAdd(&s_cnt[kConsDel * kScanWin + (p0 - ws)], 1u);
+                        if (p1 - ws < kScanWin) atomicAdd(&s_cnt[kConsDel * kScanWin + (p1 - ws)], 0xFFFFFFFFu);
+                    });
+            } else if constexpr (kScanTwoCounts<MODE>) {
                 // planes: depth by strand, then del (ins) by strand.  A run's ends: +1 at its first position, -1 behind its last
                 auto run_ends = [&](uint32_t plane, uint32_t p0, uint32_t p1) {
                     atomicAdd(&s_cnt[plane * kScanWin + (p0 - ws)], 1u);
@@ -544,6 +602,43 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
             else { v = 0; for (uint32_t k = 0; k < kPlanes; ++k) v += s_cnt[k * kScanWin + o]; }
             out[i] = v;
         }
+    } else if constexpr (MODE == SCAN_CONS) {
+        // The deletion mode's tail: four consecutive positions per thread, all planes into registers, the del plane's range
+        // ends turned into counts by an inclusive scan (thread, wave by DPP, wave totals through LDS).  Then the rule per
+        // position and one aligned word of four bytes per thread: the buffer is indexed from the first window's start, so
+        // word blockIdx.x * kBlock + tid holds positions ws + 4 tid .. + 3 whatever the range's start is.
+        static_assert(kScanWin == 4u * (uint32_t)kBlock, "four positions per thread");
+        __shared__ uint32_t s_wtot[kBlock / 64];
+        const uint32_t lane = tid & 63u, wv = tid >> 6;
+        uint32_t q[kPlanes][4];
+#pragma unroll
+        for (uint32_t k = 0; k < kPlanes; ++k) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(&s_cnt[k * kScanWin + 4u * tid]);
+            q[k][0] = v.x; q[k][1] = v.y; q[k][2] = v.z; q[k][3] = v.w;
+        }
+        q[kConsDel][1] += q[kConsDel][0]; q[kConsDel][2] += q[kConsDel][1]; q[kConsDel][3] += q[kConsDel][2];
+        const uint32_t inc = dpp_incl_scan_u32(q[kConsDel][3]);
+        if (lane == 63u) s_wtot[wv] = inc;
+        __syncthreads();
+        uint32_t add = inc - q[kConsDel][3];
+#pragma unroll
+        for (uint32_t j = 0; j < (uint32_t)kBlock / 64u; ++j) add += j < wv ? s_wtot[j] : 0u;
+        uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
+        uint32_t word = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) {
+            const uint32_t p = ws + 4u * tid + j;
+            uint32_t byte = kConsPad;
+            if (p >= lo && p < we) {
+                const uint32_t rb = p < hi ? a.refb[p - a.start] : (uint32_t)'N';
+                const int cls = scan_classify_cons(q[0][j], q[1][j], q[2][j], q[3][j], q[kConsRest][j], q[kConsDel][j] + add, rb, a.min_depth,
+                                                   ax.t.min_count, ax.t.min_per_10k, byte);
+                mine[cls] += 1u;
+            }
+            word |= byte << (8u * j);
+        }
+        ax.cand[(size_t)blockIdx.x * kBlock + tid] = word;
+        scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);     // (s_cnt: every thread has read it)
     } else if constexpr (kScanTwoCounts<MODE>) {
         // Four consecutive positions per thread, all planes into registers.  The planes of range ends (deletion mode: both
         // unfiltered, the del planes under a filter: always the last two; insertion mode: the unfiltered depth plane)

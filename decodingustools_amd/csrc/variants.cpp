@@ -4,7 +4,9 @@
 // except dut_find_variants_files(_ex) and dut_find_minor_files, which run the device engine's cl_site_scan(_ex) and
 // cl_site_scan_minor.  The same for `find-deletions`: the deletion rule, the merge of candidate positions into events,
 // the TSV, and dut_find_deletions_files over cl_site_scan_dels.  And for `find-insertions`: the insertion rule, the
-// grouping of observations into alleles, the TSV, and dut_find_insertions_files over cl_site_scan_ins.
+// grouping of observations into alleles, the TSV, and dut_find_insertions_files over cl_site_scan_ins.  And for `consensus`:
+// the composed rule, the assembly of the bytes of cl_site_scan_consensus and the insertions into a sequence and a change
+// list, the FASTA and the change list's file, and dut_find_consensus_files over both scans on one resident tile.
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -270,6 +272,81 @@ int rule_files_run(const Rule &rule, const char *bam_path, const char *fasta_pat
     return write(output_path, contig, &res, o, err, err_len);
 }
 
+// ---- consensus ----
+const char *const CONS_KIND[] = {"snv", "del", "ins", "ins_skipped"};
+const char *const CONS_NOTE[] = {".", "anchor_deleted", "too_long", "no_allele"};
+
+void cons_text(char *dst, size_t cap, const std::string &s) { snprintf(dst, cap, "%s", s.c_str()); }
+
+int cons_assemble(const uint8_t *cons, uint32_t start, uint32_t end, const uint8_t *ref, uint64_t n_ref, const cl_ins_result *ins,
+                  const dut_ins_allele *alleles, size_t n_alleles, const cl_ins_params *ip, int fill_ref, std::string &seq,
+                  std::vector<dut_cons_change> &ch, uint64_t (&n)[3])
+{
+    const uint64_t len = (uint64_t)end - start;
+    auto ref_at = [&](uint64_t i) -> char { return i < n_ref ? (char)ref[i] : 'N'; };       // as sent, case preserved
+    auto ref_upper = [&](uint64_t i) -> char { return (char)(ref_at(i) & ~32); };
+    const uint64_t n_ins = ins ? ins->n_inserted : 0;
+    uint64_t ic = 0; size_t ia = 0;                                          // the next candidate and its first allele
+    seq.reserve(len + 64);
+    for (uint64_t i = 0; i < len; ++i) {
+        const uint8_t b = cons[i];
+        const uint32_t pos = start + (uint32_t)i + 1u;
+        if (b == '-') {
+            if (i == 0 || cons[i - 1] != '-') {
+                uint64_t j = i;
+                while (j + 1 < len && cons[j + 1] == '-') ++j;
+                dut_cons_change c{};
+                c.pos = pos; c.end = start + (uint32_t)j + 1u; c.kind = DUT_CONS_DEL;
+                std::string r = ".";
+                if (j - i + 1 <= 64) { r.clear(); for (uint64_t k = i; k <= j; ++k) r += ref_upper(k); }
+                cons_text(c.ref, sizeof(c.ref), r); cons_text(c.cons, sizeof(c.cons), "-");
+                ch.push_back(c); n[0] += 1;
+            }
+        } else if (b == 'N') seq += 'N';
+        else if (b == 'n') { const char r = ref_base((uint8_t)ref_at(i)); seq += (fill_ref && r) ? (char)(r | 32) : 'N'; }
+        else if (b == 'A' || b == 'C' || b == 'G' || b == 'T') {
+            seq += (char)b;
+            if (ref_base((uint8_t)ref_at(i)) != (char)b) {
+                dut_cons_change c{};
+                c.pos = c.end = pos; c.kind = DUT_CONS_SNV;
+                cons_text(c.ref, sizeof(c.ref), std::string(1, ref_upper(i))); cons_text(c.cons, sizeof(c.cons), std::string(1, (char)b));
+                ch.push_back(c);
+            }
+        } else return CL_ERR_INVALID;
+        // a called insertion behind this position
+        if (ic < n_ins && ins->candidates[ic].pos < pos) return CL_ERR_INVALID;      // not ascending, or below the range
+        if (ic < n_ins && ins->candidates[ic].pos == pos) {
+            const cl_ins_candidate &cd = ins->candidates[ic++];
+            while (ia < n_alleles && alleles[ia].pos < pos) ++ia;
+            if (ia >= n_alleles || alleles[ia].pos != pos) return CL_ERR_INVALID;    // a candidate has observations
+            const dut_ins_allele &top = alleles[ia];
+            std::string text;
+            for (uint32_t j = 0; j < std::min<uint32_t>(top.len, 32u); ++j) {
+                const char k = CODE[(top.key[j / 16] >> (60 - 4 * (j % 16))) & 15u];
+                text += (k == 'A' || k == 'C' || k == 'G' || k == 'T') ? k : 'N';
+            }
+            dut_cons_change c{};
+            c.pos = c.end = pos; c.count = top.count; c.depth = cd.depth;
+            c.note = b == '-' ? DUT_CONS_NOTE_ANCHOR_DELETED : top.len > 32 ? DUT_CONS_NOTE_TOO_LONG
+                   : !(top.count >= ip->min_ins_count && 10000ull * top.count >= (uint64_t)ip->min_ins_per_10k * cd.depth) ? DUT_CONS_NOTE_NO_ALLELE
+                   : DUT_CONS_NOTE_NONE;
+            c.kind = c.note ? DUT_CONS_INS_SKIPPED : DUT_CONS_INS;
+            cons_text(c.ref, sizeof(c.ref), std::string(1, ref_upper(i))); cons_text(c.cons, sizeof(c.cons), text);
+            if (!c.note) seq += text;
+            ch.push_back(c); n[c.note ? 2 : 1] += 1;
+        }
+    }
+    return ic == n_ins ? CL_OK : CL_ERR_INVALID;                             // a candidate beyond the range
+}
+
+bool cons_options_ok(const dut_cons_options &o, char *err, size_t err_len)
+{
+    if (!rule_ok(DEL_RULE, o.min_depth, o.min_del_count, o.min_del_per_10k, err, err_len)) return false;
+    if (!rule_ok(INS_RULE, o.min_depth, o.min_ins_count, o.min_ins_per_10k, err, err_len)) return false;
+    if (o.line_width == 0) { set_err(err, err_len, "line_width must be at least 1"); return false; }
+    return true;
+}
+
 // no exception leaves the library through the C ABI
 template <class F> int no_throw(char *err, size_t err_len, F &&f)
 {
@@ -519,6 +596,144 @@ int dut_ins_write(const char *path, const char *contig, const cl_ins_result *res
 {
     try { return ins_write(path, contig, res, opt, err, err_len); }
     catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
+}
+
+int dut_cons_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint64_t depth, uint32_t del, const cl_cons_params *params,
+                             uint8_t ref_byte, char *byte)
+{
+    if (byte) *byte = 0;
+    if (!params || !rule_ok(DEL_RULE, params->min_depth, params->min_del_count, params->min_del_per_10k)) return CL_ERR_INVALID;
+    if ((uint64_t)a + c + g + t > depth || depth > 0xFFFFFFFFull) return CL_ERR_INVALID;
+    const uint32_t cnt[4] = {a, c, g, t};
+    int mi = 0;
+    for (int b = 1; b < 4; ++b) if (cnt[b] > cnt[mi]) mi = b;                  // the first among equals
+    const uint64_t span = depth + del, m = cnt[mi];
+    auto leave = [&](int cls, char b) { if (byte) *byte = b; return cls; };
+    if (span < params->min_depth) return leave(DUT_CONS_LOW_DEPTH, 'n');
+    if (del >= params->min_del_count && 10000ull * del >= (uint64_t)params->min_del_per_10k * span) return leave(DUT_CONS_DELETED, '-');
+    if (depth < params->min_depth) return leave(DUT_CONS_LOW_DEPTH, 'n');
+    if (10ull * m >= 7ull * depth) return leave("ACGT"[mi] == ref_base(ref_byte) ? DUT_CONS_REF : DUT_CONS_ALT, "ACGT"[mi]);
+    return leave(DUT_CONS_NO_CALL, 'N');
+}
+
+int dut_cons_assemble(const uint8_t *cons, uint32_t start, uint32_t end, const uint8_t *ref, uint64_t n_ref, const cl_ins_result *ins,
+                      const dut_ins_allele *alleles, size_t n_alleles, const cl_ins_params *ins_params, int fill_ref, dut_cons_assembly *out)
+{
+    if (out) memset(out, 0, sizeof(*out));
+    if (!out || start > end || (end > start && !cons) || (n_ref && !ref)) return CL_ERR_INVALID;
+    if (ins && ins->n_inserted && (!ins->candidates || !alleles || !ins_params ||
+                                   !rule_ok(INS_RULE, ins_params->min_depth, ins_params->min_ins_count, ins_params->min_ins_per_10k))) return CL_ERR_INVALID;
+    try {
+        std::string seq;
+        std::vector<dut_cons_change> ch;
+        uint64_t n[3] = {0, 0, 0};
+        const int rc = cons_assemble(cons, start, end, ref, n_ref, ins, alleles, n_alleles, ins_params, fill_ref, seq, ch, n);
+        if (rc != CL_OK) return rc;
+        out->seq = static_cast<char *>(malloc(seq.size() + 1));
+        out->changes = static_cast<dut_cons_change *>(malloc(std::max<size_t>(ch.size(), 1) * sizeof(dut_cons_change)));
+        if (!out->seq || !out->changes) { dut_cons_assembly_free(out); return CL_ERR_NOMEM; }
+        memcpy(out->seq, seq.c_str(), seq.size() + 1);
+        if (!ch.empty()) memcpy(out->changes, ch.data(), ch.size() * sizeof(dut_cons_change));
+        out->seq_len = seq.size(); out->n_changes = ch.size();
+        out->n_deletions = n[0]; out->n_insertions = n[1]; out->n_insertions_skipped = n[2];
+        return CL_OK;
+    }
+    catch (...) { dut_cons_assembly_free(out); return CL_ERR_NOMEM; }
+}
+
+void dut_cons_assembly_free(dut_cons_assembly *a)
+{
+    if (!a) return;
+    free(a->seq); free(a->changes);
+    memset(a, 0, sizeof(*a));
+}
+
+int dut_cons_write_fasta(const char *path, const char *contig, int whole_contig, uint32_t start, uint32_t end, const char *seq, uint64_t seq_len,
+                         uint32_t line_width, char *err, size_t err_len)
+{
+    if (!path || !contig || (seq_len && !seq)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    if (line_width == 0) { set_err(err, err_len, "line_width must be at least 1"); return CL_ERR_INVALID; }
+    return no_throw(err, err_len, [&]() -> int {
+        std::string s = std::string(">") + contig;
+        if (!whole_contig) s += ":" + std::to_string((uint64_t)start + 1) + "-" + std::to_string(end);
+        s += "\n";
+        s.reserve(s.size() + seq_len + seq_len / line_width + 2);
+        for (uint64_t at = 0; at < seq_len; at += line_width) { s.append(seq + at, (size_t)std::min<uint64_t>(line_width, seq_len - at)); s += "\n"; }
+        return write_file(path, s, err, err_len);
+    });
+}
+
+int dut_cons_write_changes(const char *path, const char *contig, const cl_cons_result *res, const dut_cons_assembly *a, const dut_cons_options *opt,
+                           char *err, size_t err_len)
+{
+    if (!path || !contig || !res || !a || !opt || (a->n_changes && !a->changes)) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+    return no_throw(err, err_len, [&]() -> int {
+        std::string s;
+        char b[512];
+        const ScanOptions o = {opt->min_depth, opt->min_quality, {opt->has_min_base_quality, opt->min_base_quality, opt->exclude_flags}, opt->min_del_per_10k,
+                               opt->min_del_count, 0};
+        tsv_preamble(s, contig, res->start, res->end, o, true, &DEL_RULE);
+        // (tsv_preamble ends with ##positions: the insertion rule and the fill mode go in front of it)
+        const size_t at = s.rfind("##positions=");
+        snprintf(b, sizeof(b), "##%s=%.4f\n##%s=%u\n##fill=%s\n", INS_RULE.fraction, (double)opt->min_ins_per_10k / 10000.0, INS_RULE.count, opt->min_ins_count,
+                 opt->fill_ref ? "ref" : "N");
+        s.insert(at, b);
+        snprintf(b, sizeof(b), "##low_depth=%llu\n##deleted=%llu\n##no_call=%llu\n##ref=%llu\n##alt=%llu\n##length=%llu\n##deletions=%llu\n##insertions=%llu\n"
+                               "##insertions_skipped=%llu\n",
+                 (unsigned long long)res->n_low_depth, (unsigned long long)res->n_deleted, (unsigned long long)res->n_no_call, (unsigned long long)res->n_ref,
+                 (unsigned long long)res->n_alt, (unsigned long long)a->seq_len, (unsigned long long)a->n_deletions, (unsigned long long)a->n_insertions,
+                 (unsigned long long)a->n_insertions_skipped);
+        s += b;
+        s += "#contig\tpos\tend\tkind\tref\tcons\tcount\tdepth\tnote\n";
+        for (size_t i = 0; i < a->n_changes; ++i) {
+            const dut_cons_change &c = a->changes[i];
+            if (c.kind > DUT_CONS_INS_SKIPPED || c.note > DUT_CONS_NOTE_NO_ALLELE) { set_err(err, err_len, "unknown kind of change"); return CL_ERR_INVALID; }
+            const bool is_ins = c.kind == DUT_CONS_INS || c.kind == DUT_CONS_INS_SKIPPED;
+            snprintf(b, sizeof(b), "\t%u\t%u\t%s\t%.67s\t%.35s\t", c.pos, c.end, CONS_KIND[c.kind], c.ref, c.cons);
+            s += contig; s += b;
+            if (is_ins) { snprintf(b, sizeof(b), "%u\t%u\t", c.count, c.depth); s += b; } else s += ".\t.\t";
+            s += CONS_NOTE[c.note]; s += "\n";
+        }
+        return write_file(path, s, err, err_len);
+    });
+}
+
+int dut_find_consensus_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
+                             const dut_cons_options *opt, const char *output_path, const char *changes_path, int device_id, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&]() -> int {
+        if (!bam_path || !fasta_path || !contig || !output_path || !opt) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (!cons_options_ok(*opt, err, err_len)) return CL_ERR_INVALID;
+        ScanFiles F;
+        cl_scan_filter f;
+        int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
+        if (rc != CL_OK) return rc;
+        const FilterOptions flt = {opt->has_min_base_quality, opt->min_base_quality, opt->exclude_flags};
+        if ((rc = scan_files_resident(F, contig, device_id, &flt, f, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
+        // both scans on the one resident tile: their results live in storage of their own
+        const cl_cons_params cp = {opt->min_depth, opt->min_del_count, opt->min_del_per_10k};
+        const cl_ins_params ip = {opt->min_depth, opt->min_ins_count, opt->min_ins_per_10k};
+        cl_cons_result cres;
+        cl_ins_result ires;
+        if ((rc = cl_site_scan_consensus(F.ctx.get(), opt->min_quality, &f, &cp, F.bases, F.blen, start, end, &cres)) != CL_OK ||
+            (rc = cl_site_scan_ins(F.ctx.get(), opt->min_quality, &f, &ip, F.bases, F.blen, start, end, &ires)) != CL_OK) {
+            F.engine_err(err, err_len, "site scan failed");
+            return rc;
+        }
+        dut_ins_allele *al = nullptr; size_t n_al = 0;
+        if (ires.n_obs && (rc = dut_ins_alleles(ires.obs, (size_t)ires.n_obs, &al, &n_al)) != CL_OK) { set_err(err, err_len, "grouping the insertions failed"); return rc; }
+        std::unique_ptr<dut_ins_allele, decltype(&dut_ins_alleles_free)> al_own(al, dut_ins_alleles_free);
+        const uint64_t n_ref = std::min<uint64_t>(end, F.blen) > start ? std::min<uint64_t>(end, F.blen) - start : 0;
+        dut_cons_assembly A;
+        if ((rc = dut_cons_assemble(cres.cons, start, end, F.bases + std::min<uint64_t>(start, F.blen), n_ref, &ires, al, n_al, &ip, opt->fill_ref, &A)) != CL_OK) {
+            set_err(err, err_len, "assembling the consensus failed");
+            return rc;
+        }
+        rc = dut_cons_write_fasta(output_path, contig, start == 0 && end == F.contig_len, start, end, A.seq, A.seq_len, opt->line_width, err, err_len);
+        if (rc == CL_OK && changes_path) rc = dut_cons_write_changes(changes_path, contig, &cres, &A, opt, err, err_len);
+        dut_cons_assembly_free(&A);
+        return rc;
+    });
 }
 
 int dut_minor_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint64_t depth, const cl_minor_params *params, char *major, char *minor)

@@ -7,8 +7,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from .callable_loci import (DEL_CANDIDATE, INS_CANDIDATE, INS_OBS, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, DelResult, EngineError,
-                            InsResult, MinorResult, ScanResult)
+from .callable_loci import (DEL_CANDIDATE, INS_CANDIDATE, INS_OBS, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, ConsResult, DelResult,
+                            EngineError, InsResult, MinorResult, ScanResult)
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
@@ -19,6 +19,10 @@ DEL_CLASS_NAMES = ("low_depth", "kept", "deleted")
 INS_LOW_DEPTH, INS_KEPT, INS_INSERTED = range(3)
 INS_CLASS_NAMES = ("low_depth", "kept", "inserted")
 INS_CODES = "=ACMGRSVTWYHKDBN"
+CONS_LOW_DEPTH, CONS_DELETED, CONS_NO_CALL, CONS_REF, CONS_ALT = range(5)
+CONS_CLASS_NAMES = ("low_depth", "deleted", "no_call", "ref", "alt")
+CONS_KINDS = ("snv", "del", "ins", "ins_skipped")
+CONS_NOTES = ("", "anchor_deleted", "too_long", "no_allele")
 CLASS_NAMES = ("low_depth", "mixed", "uncomparable", "match", "variant", "undetermined")
 
 
@@ -332,3 +336,115 @@ def find_insertions(bam_file: str, reference_file: str, contig: str, output_file
     per_10k = del_fraction_parse(str(min_ins_fraction))
     opt = _rule_options("ins", min_depth, min_quality, min_ins_count, per_10k, min_base_quality, exclude_flags, min_ins_per_strand)
     _find_files(_lib.load().dut_find_insertions_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(), device_id)
+
+
+def cons_classify_counts(a, c, g, t, depth, n_del, min_depth, min_del_count, min_del_per_10k, ref_byte) -> Tuple[int, str]:
+    """(class, byte) of one position by the rule of cl_site_scan_consensus in plain code (dut_cons_classify_counts)."""
+    prm = _lib.cl_cons_params(int(min_depth), int(min_del_count), int(min_del_per_10k))
+    if isinstance(ref_byte, (str, bytes)):
+        ref_byte = ord(ref_byte)
+    byte = C.create_string_buffer(2)
+    st = _lib.load().dut_cons_classify_counts(int(a), int(c), int(g), int(t), int(depth), int(n_del), C.byref(prm), int(ref_byte), byte)
+    if st < 0:
+        raise EngineError(st, "invalid counters or parameters")
+    return st, byte.value.decode()
+
+
+class ConsAssembly:
+    """dut_cons_assembly: seq (str), changes (dicts of pos, end, kind, ref, cons, count, depth, note) and the numbers of
+    deletion runs, spliced and skipped insertions.  Holds the C structure for the writers until it is collected."""
+
+    def __init__(self, c):
+        self._c = c
+        self.seq = C.string_at(c.seq, int(c.seq_len)).decode() if c.seq_len else ""
+        self.changes = [dict(pos=int(x.pos), end=int(x.end), kind=CONS_KINDS[x.kind], ref=x.ref.decode(), cons=x.cons.decode(), count=int(x.count),
+                             depth=int(x.depth), note=CONS_NOTES[x.note]) for x in c.changes[:c.n_changes]]
+        self.deletions, self.insertions, self.insertions_skipped = int(c.n_deletions), int(c.n_insertions), int(c.n_insertions_skipped)
+
+    def __del__(self):
+        c, self._c = self._c, None
+        if c is not None:
+            _lib.load().dut_cons_assembly_free(C.byref(c))
+
+
+def cons_assemble(cons, ref, start: int = 0, ins: Optional[InsResult] = None, min_depth: int = 10, min_ins_count: int = 3,
+                  min_ins_per_10k: int = 7000, fill: str = "N") -> ConsAssembly:
+    """dut_cons_assemble: the sequence and the change list of [start, start + len(cons)) from the bytes of
+    Engine.site_scan_consensus.  ref: the whole reference the scans were given (its bytes from `start` on are used); ins: the
+    InsResult of Engine.site_scan_ins over the same range and gates, with the parameters it was asked with; fill: "N" or
+    "ref".  No device is needed."""
+    if fill not in ("N", "ref"):
+        raise ValueError("fill: N or ref")
+    lib = _lib.load()
+    cons = np.ascontiguousarray(cons, np.uint8).reshape(-1)
+    ref = np.ascontiguousarray(ref, np.uint8).reshape(-1)
+    start, end = int(start), int(start) + cons.shape[0]
+    part = np.ascontiguousarray(ref[start:end])
+    r = al = None
+    n_al = C.c_size_t()
+    prm = _lib.cl_ins_params(int(min_depth), int(min_ins_count), int(min_ins_per_10k))
+    alp = C.POINTER(_lib.dut_ins_allele)()
+    if ins is not None:
+        r, _cand = _c_result(_lib.cl_ins_result, _lib.cl_ins_candidate, INS_CANDIDATE, ins, "inserted", n_low_depth=ins.low_depth, n_kept=ins.kept,
+                             n_inserted=ins.inserted)
+        obs = np.ascontiguousarray(ins.observations, INS_OBS).reshape(-1)
+        st = lib.dut_ins_alleles(obs.ctypes.data if obs.shape[0] else None, obs.shape[0], C.byref(alp), C.byref(n_al))
+        if st != 0:
+            raise EngineError(st, "dut_ins_alleles failed")
+    out = _lib.dut_cons_assembly()
+    try:
+        st = lib.dut_cons_assemble(cons.ctypes.data if cons.shape[0] else None, start, end, part.ctypes.data if part.shape[0] else None, part.shape[0],
+                                   C.byref(r) if r is not None else None, C.cast(alp, C.c_void_p), n_al.value, C.byref(prm), 1 if fill == "ref" else 0,
+                                   C.byref(out))
+    finally:
+        lib.dut_ins_alleles_free(alp)
+    if st != 0:
+        raise EngineError(st, "dut_cons_assemble refused its arguments")
+    return ConsAssembly(out)
+
+
+def _cons_options(min_depth, min_quality, min_del_count, min_del_per_10k, min_ins_count, min_ins_per_10k, min_base_quality, exclude_flags, fill, line_width):
+    if fill not in ("N", "ref"):
+        raise ValueError("fill: N or ref")
+    o = _filter_options(_lib.dut_cons_options(), min_base_quality, exclude_flags)
+    if not 0 <= int(min_quality) <= 255:
+        raise ValueError("min_quality: 0..255")
+    for name, v in (("min_depth", min_depth), ("min_del_count", min_del_count), ("min_del_per_10k", min_del_per_10k), ("min_ins_count", min_ins_count),
+                    ("min_ins_per_10k", min_ins_per_10k), ("line_width", line_width)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name}: 0..2^32-1")
+        setattr(o, name, int(v))
+    o.min_quality = int(min_quality)
+    o.fill_ref = 1 if fill == "ref" else 0
+    return o
+
+
+def write_consensus(path: str, contig: str, assembly: ConsAssembly, start: int, end: int, whole_contig: bool = False, line_width: int = 60):
+    """The FASTA of `consensus` (dut_cons_write_fasta): ">contig" for the whole contig, else ">contig:START-END" (1-based,
+    inclusive).  No device is needed."""
+    seq = assembly.seq.encode()
+    _call(_lib.load().dut_cons_write_fasta, path.encode(), contig.encode(), 1 if whole_contig else 0, int(start), int(end), seq, len(seq), int(line_width))
+
+
+def write_consensus_changes(path: str, contig: str, result: ConsResult, assembly: ConsAssembly, min_depth: int = 10, min_quality: int = 20,
+                            min_del_count: int = 3, min_del_per_10k: int = 7000, min_ins_count: int = 3, min_ins_per_10k: int = 7000,
+                            min_base_quality=None, exclude_flags: int = 0, fill: str = "N"):
+    """The change list of `consensus` (dut_cons_write_changes) for a ConsResult and its assembly.  No device is needed."""
+    r = _lib.cl_cons_result()
+    r.start, r.end = result.start, result.end
+    r.n_low_depth, r.n_deleted, r.n_no_call, r.n_ref, r.n_alt = result.low_depth, result.deleted, result.no_call, result.ref, result.alt
+    opt = _cons_options(min_depth, min_quality, min_del_count, min_del_per_10k, min_ins_count, min_ins_per_10k, min_base_quality, exclude_flags, fill, 60)
+    _call(_lib.load().dut_cons_write_changes, path.encode(), contig.encode(), C.byref(r), C.byref(assembly._c), C.byref(opt))
+
+
+def consensus(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None, min_depth: int = 10,
+              min_quality: int = 20, min_del_fraction="0.7", min_del_count: int = 3, min_ins_fraction="0.7", min_ins_count: int = 3,
+              min_base_quality: Optional[int] = None, exclude_flags: int = 0, fill: str = "N", line_width: int = 60,
+              changes_file: Optional[str] = None, device_id: int = 0):
+    """dut_find_consensus_files: BAM (+ index) and FASTA in, the sample's sequence over the contig or the region as FASTA
+    out, and with changes_file the list of its differences from the reference; region = (start, end), 0-based half open.
+    The fractions: decimal text (or a number whose text is one) in (0, 1], at most four decimals."""
+    opt = _cons_options(min_depth, min_quality, min_del_count, del_fraction_parse(str(min_del_fraction)), min_ins_count,
+                        del_fraction_parse(str(min_ins_fraction)), min_base_quality, exclude_flags, fill, line_width)
+    _find_files(_lib.load().dut_find_consensus_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(),
+                changes_file.encode() if changes_file else None, device_id)

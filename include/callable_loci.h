@@ -579,6 +579,35 @@ cl_status cl_site_scan_ins(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filte
 /* The kernel milliseconds of the last cl_site_scan_ins: its window scan and its allele launch (0 without candidates). */
 cl_status cl_site_scan_ins_stats(cl_ctx *ctx, double *scan_ms, double *alleles_ms);
 
+/* ---- the consensus mode of the dense scan: one byte per position, the called sequence with its deletions ------------ */
+/* The read gates are those of cl_site_scan (filter == NULL) or cl_site_scan_ex (a filter; needs cl_site_attach_quals); the
+ * carrier's pass bit gates a deletion exactly as in cl_site_scan_dels.  For every position p of [start, end): a, c, g, t
+ * and depth are those of cl_site_scan_counts(_ex) at p (strands summed, depth over all 16 codes), del is the count of
+ * cl_site_scan_dels there, span = depth + del, m the largest of a, c, g, t (the first in that order among equals).  The
+ * first class whose condition holds:
+ *   low_depth    span < min_depth                                                                     byte n
+ *   deleted      del >= min_del_count and 10000 * del >= min_del_per_10k * span (in 64 bits)          byte -
+ *   low_depth    depth < min_depth (enough reads span it, too few carry a base)                       byte n
+ *   ref / alt    10 * m >= 7 * depth (in 64 bits): ref when the called base equals the upper-cased
+ *                reference byte, else alt (also for a reference byte that is not A/C/G/T)             byte A C G T
+ *   no_call      everything else: mixed columns, columns where N or an IUPAC code holds the majority  byte N
+ * The five counts add up to end - start.  Positions at and beyond ref_len hold no counts and come out low_depth.  A
+ * position is deleted exactly when cl_site_scan_dels lists it under the same gates and parameters.
+ * cons holds end - start bytes, cons[p - start] for position p: context-owned, in storage of its own, valid until the next
+ * cl_site_scan_consensus, cl_site_upload or cl_destroy.  There is no CL_SCAN_MAX_DENSE limit: any end <= contig_len is
+ * accepted; start == end returns an empty result without a launch.
+ * Refusals: those of cl_site_scan_dels, with its messages for the parameters.  Any order of this call and the other
+ * scans on one tile is allowed; cl_site_scan_stats speaks of this scan after it. */
+typedef struct cl_cons_params { uint32_t min_depth, min_del_count, min_del_per_10k; } cl_cons_params;
+typedef struct cl_cons_result {
+    uint32_t start, end;
+    uint64_t n_low_depth, n_deleted, n_no_call, n_ref, n_alt;     /* sum == end - start */
+    const uint8_t *cons;                                          /* end - start bytes of "n-ACGTN" */
+} cl_cons_result;
+cl_status cl_site_scan_consensus(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: unfiltered form */,
+                                 const cl_cons_params *params, const uint8_t *ref_bases, uint64_t ref_len,
+                                 uint32_t start, uint32_t end, cl_cons_result *out);
+
 /* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
  * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
 cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);

@@ -5,7 +5,8 @@
  * The reference has no such subcommand.  The counting and the call are the ones of find-y-branch / find-mt-branch
  * (haplogroup::caller::process_region, src/haplogroup/caller.rs:62-152), taken at every position of a contig or a
  * region instead of at the tree's sites, so the two never disagree about a tree site.  find-variants itself calls SNVs
- * only; deletions are counted and called per position by find-deletions and insertions by find-insertions (both below); no consensus FASTA.  With dut_variants_options the scan takes a flag mask and a base-quality threshold
+ * only; deletions are counted and called per position by find-deletions and insertions by find-insertions (both below);
+ * the sample's sequence itself is written by `consensus` (at the end of this header).  With dut_variants_options the scan takes a flag mask and a base-quality threshold
  * (cl_site_scan_ex) and the TSV carries per-strand allele counts and a strand filter.
  */
 #ifndef DUT_VARIANTS_H
@@ -246,6 +247,98 @@ int dut_ins_write(const char *path, const char *contig, const cl_ins_result *res
 int dut_find_insertions_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
                               uint32_t end, const dut_ins_options *opt, const char *output_path, int device_id,
                               char *err, size_t err_len);
+
+/* ---- consensus: the sample's sequence, one byte per position (cl_site_scan_consensus), with its insertions ---------- */
+/* The classes of cl_site_scan_consensus. */
+enum { DUT_CONS_LOW_DEPTH = 0, DUT_CONS_DELETED = 1, DUT_CONS_NO_CALL = 2, DUT_CONS_REF = 3, DUT_CONS_ALT = 4 };
+
+/* The rule of cl_site_scan_consensus for one position in plain C++, with the same integer comparisons; depth is the scan's
+ * depth there (a + c + g + t and every other code), del the deletion count, ref_byte the FASTA byte, case preserved (pass
+ * 'N' beyond the reference).  Returns the class and, in *byte (may be NULL), n - A C G T or N.  CL_ERR_INVALID: null or
+ * refused params (as cl_site_scan_consensus refuses them), a + c + g + t > depth, depth >= 2^32. */
+int dut_cons_classify_counts(uint32_t a, uint32_t c, uint32_t g, uint32_t t, uint64_t depth, uint32_t del, const cl_cons_params *params,
+                             uint8_t ref_byte, char *byte);
+
+/* One entry of the change list.  pos .. end are 1-based, inclusive.
+ *   DUT_CONS_SNV           an alt position: ref = the upper-cased reference byte, cons = the called base
+ *   DUT_CONS_DEL           a maximal run of '-' (runs end at the range's borders): ref = the deleted reference bases when
+ *                          the run has at most 64 positions, else "."; cons = "-"
+ *   DUT_CONS_INS           an insertion spliced behind its anchor pos: ref = the anchor's reference byte, cons = the
+ *                          inserted bases (codes outside A/C/G/T written N), count = the allele's observations, depth =
+ *                          the anchor's depth
+ *   DUT_CONS_INS_SKIPPED   a called insertion that was not spliced, note saying why: the anchor's byte is '-'
+ *                          (anchor_deleted), the top allele is longer than 32 bases (too_long), or the top allele itself
+ *                          does not meet the insertion rule (no_allele); cons = the allele's first 32 bases */
+enum { DUT_CONS_SNV = 0, DUT_CONS_DEL = 1, DUT_CONS_INS = 2, DUT_CONS_INS_SKIPPED = 3 };
+enum { DUT_CONS_NOTE_NONE = 0, DUT_CONS_NOTE_ANCHOR_DELETED = 1, DUT_CONS_NOTE_TOO_LONG = 2, DUT_CONS_NOTE_NO_ALLELE = 3 };
+typedef struct dut_cons_change {
+    uint32_t pos, end;
+    uint32_t kind, note;
+    uint32_t count, depth;            /* insertions only, else 0 */
+    char     ref[68], cons[36];       /* NUL terminated */
+} dut_cons_change;
+
+/* What dut_cons_assemble returns: the sequence (NUL terminated, seq_len bytes before it), the change list in ascending
+ * position (at one position: the deletion or SNV, then the insertion), and how many deletion runs, spliced and skipped
+ * insertions it holds.  Release with dut_cons_assembly_free. */
+typedef struct dut_cons_assembly {
+    char            *seq;
+    uint64_t         seq_len;
+    dut_cons_change *changes;
+    size_t           n_changes;
+    uint64_t         n_deletions, n_insertions, n_insertions_skipped;
+} dut_cons_assembly;
+
+/* The sequence of [start, end) from the bytes of cl_site_scan_consensus (cons[p - start]), no device needed.  ref: the
+ * reference bytes of the range, ref[0] <-> start, n_ref of them (fewer than end - start when the reference ends inside the
+ * range: the rest reads as N).  ins / alleles: the result of cl_site_scan_ins over the same range and gates and the
+ * alleles of its observations by dut_ins_alleles (ins == NULL: no insertion is spliced); ins_params: the parameters of
+ * that call.  The bytes in order: '-' emits nothing, 'N' emits N, 'n' emits N -- or, with fill_ref, the lower-cased
+ * reference base when that is one of a c g t -- and a base emits itself.  Behind a position that ins lists, the top allele
+ * there is spliced when the position's byte is not '-', the allele has at most 32 bases and allele_count >= min_ins_count
+ * and 10000 * allele_count >= min_ins_per_10k * depth; otherwise the insertion is listed as skipped.  CL_ERR_INVALID: a
+ * null argument, a byte outside "n-ACGTN", candidates that do not ascend or lie outside the range, a candidate without
+ * an allele, refused ins_params. */
+int dut_cons_assemble(const uint8_t *cons, uint32_t start, uint32_t end, const uint8_t *ref, uint64_t n_ref, const cl_ins_result *ins,
+                      const dut_ins_allele *alleles, size_t n_alleles, const cl_ins_params *ins_params, int fill_ref,
+                      dut_cons_assembly *out);
+void dut_cons_assembly_free(dut_cons_assembly *a);
+
+/* What a consensus run is asked. */
+typedef struct dut_cons_options {
+    uint32_t min_depth;
+    uint8_t  min_quality;
+    int      has_min_base_quality;
+    uint8_t  min_base_quality;
+    uint16_t exclude_flags;
+    uint32_t min_del_per_10k, min_del_count;      /* 1..10000, >= 1 */
+    uint32_t min_ins_per_10k, min_ins_count;      /* 1..10000, >= 1 */
+    int      fill_ref;                            /* 0: low-depth positions are N; 1: the lower-cased reference base */
+    uint32_t line_width;                          /* >= 1 */
+} dut_cons_options;
+
+/* The FASTA (no device needed): the header ">contig" when whole_contig, else ">contig:START-END" (1-based, inclusive:
+ * start + 1 .. end), then the sequence in lines of line_width bytes.  An empty sequence writes the header alone. */
+int dut_cons_write_fasta(const char *path, const char *contig, int whole_contig, uint32_t start, uint32_t end, const char *seq,
+                         uint64_t seq_len, uint32_t line_width, char *err, size_t err_len);
+
+/* The change list, tab separated (no device needed): comment lines ##contig= ##range=start-end (0-based half open)
+ * ##min_depth= ##min_quality= ##min_base_quality= ("." when !has_min_base_quality) ##exclude_flags=0x%04x
+ * ##min_del_fraction=%.4f ##min_del_count= ##min_ins_fraction=%.4f ##min_ins_count= ##fill=N|ref ##positions= ##low_depth=
+ * ##deleted= ##no_call= ##ref= ##alt= ##length= (of the sequence) ##deletions= ##insertions= ##insertions_skipped=, the header
+ *   #contig pos end kind ref cons count depth note
+ * and one line per change: kind snv | del | ins | ins_skipped; count and depth "." unless an insertion; note "." or the
+ * reason an insertion was skipped. */
+int dut_cons_write_changes(const char *path, const char *contig, const cl_cons_result *res, const dut_cons_assembly *asm_,
+                           const dut_cons_options *opt, char *err, size_t err_len);
+
+/* `consensus` on files, one GPU: reads as dut_find_deletions_files does, always attaches the records' flags and pass bits
+ * and runs the filtered forms of cl_site_scan_consensus and cl_site_scan_ins on one resident tile, assembles, writes the
+ * FASTA to output_path and, when changes_path is not NULL, the change list.  Errors with a message: those of
+ * dut_find_variants_files, refused options. */
+int dut_find_consensus_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
+                             uint32_t end, const dut_cons_options *opt, const char *output_path, const char *changes_path,
+                             int device_id, char *err, size_t err_len);
 
 #ifdef __cplusplus
 }
