@@ -281,6 +281,32 @@ class dut_cons_options(C.Structure):
                 ("min_ins_count", C.c_uint32), ("fill_ref", C.c_int), ("line_width", C.c_uint32)]
 
 
+class cl_str_locus(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32)]
+
+
+class cl_str_result(C.Structure):
+    _fields_ = [("n_loci", C.c_size_t), ("hist", C.POINTER(C.c_uint32)), ("partial", C.POINTER(C.c_uint32)), ("strands", C.c_uint32)]
+
+
+class dut_str_params(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_allele_per_10k", C.c_uint32)]
+
+
+class dut_str_allele_call(C.Structure):
+    _fields_ = [("status", C.c_int), ("delta", C.c_int32), ("delta2", C.c_int32), ("count", C.c_uint32), ("fwd", C.c_uint32), ("rev", C.c_uint32),
+                ("count2", C.c_uint32), ("n", C.c_uint64), ("other", C.c_uint64)]
+
+
+class dut_str_locus(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("period", C.c_uint32), ("name", C.c_char * 64)]
+
+
+class dut_str_options(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_quality", C.c_uint8), ("exclude_flags", C.c_uint16), ("flank", C.c_uint32),
+                ("min_allele_per_10k", C.c_uint32)]
+
+
 class dut_variants_options(C.Structure):
     _fields_ = [("filtered", C.c_int), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
                 ("exclude_flags", C.c_uint16), ("min_alt_per_strand", C.c_uint32)]
@@ -295,6 +321,8 @@ class dut_tree_locus(C.Structure):
 
 
 CL_SCAN_MAX_DENSE = 1 << 20
+CL_STR_BINS, CL_STR_MAX_FLANK, CL_STR_MAX_LOCI, CL_STR_MAX_SPAN = 128, 64, 65536, 1024
+DUT_STR_UNITS_LEN = 24
 
 # every symbol the headers declare: (name, restype, argtypes)
 SYMBOLS = [
@@ -315,6 +343,7 @@ SYMBOLS = [
     ("cl_site_scan_ins_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("cl_site_scan_consensus", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_cons_params), C.c_void_p, C.c_uint64,
                                          C.c_uint32, C.c_uint32, C.POINTER(cl_cons_result)]),
+    ("cl_site_str_lengths", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(cl_str_result)]),
     ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
     ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
@@ -354,6 +383,17 @@ SYMBOLS = [
                                          C.c_char_p, C.c_size_t]),
     ("dut_find_consensus_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_cons_options),
                                            C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
+    ("dut_str_measure", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint8, C.c_uint16, C.c_uint32,
+                                  C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("dut_str_call", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(dut_str_params), C.POINTER(dut_str_allele_call)]),
+    ("dut_str_units", C.c_int, [C.c_uint32, C.c_int32, C.c_uint32, C.c_char_p]),
+    ("dut_str_loci_parse", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(dut_str_locus)), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                     C.c_char_p, C.c_size_t]),
+    ("dut_str_loci_free", None, [C.POINTER(dut_str_locus)]),
+    ("dut_str_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(dut_str_locus), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32,
+                                C.POINTER(dut_str_options), C.c_char_p, C.c_size_t]),
+    ("dut_find_strs_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(dut_str_options), C.c_char_p, C.c_int, C.c_char_p,
+                                      C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

@@ -21,7 +21,7 @@ CLI_SRC = os.path.join(CSRC, "coverage_main.cpp")
 HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "pileup_bytes.hip.h"), os.path.join(CSRC, "pileup_rows.hip.h"),
            os.path.join(CSRC, "depth_profile.hip.h"), os.path.join(CSRC, "depth_runs.hip.h"), os.path.join(CSRC, "site_scan.hip.h"),
            os.path.join(CSRC, "engine_base.hip.h"), os.path.join(CSRC, "site_engine.hip.h"),
-           os.path.join(CSRC, "site_pass_bits.h"),
+           os.path.join(CSRC, "site_pass_bits.h"), os.path.join(CSRC, "site_str.hip.h"), os.path.join(CSRC, "str_walk.h"),
            os.path.join(CSRC, "coverage_hook.h"),
            os.path.join(CSRC, "host_parallel.h"),
            os.path.join(CSRC, "qual_pack.h"), os.path.join(CSRC, "pass_rows.h"),

@@ -365,6 +365,24 @@ class Engine:
         return ConsResult(start=int(r.start), end=int(r.end), low_depth=int(r.n_low_depth), deleted=int(r.n_deleted), no_call=int(r.n_no_call),
                           ref=int(r.n_ref), alt=int(r.n_alt), cons=cons, kernel_ms=self.site_scan_stats()[0])
 
+    def site_str_lengths(self, loci, flank, min_quality, filter=None):
+        """cl_site_str_lengths over the resident tile: per locus [start, end) of `loci` (an (n, 2) array, 0-based half open,
+        in any order) the histogram of delta = bases between the two flanks of `flank` matched bases - (end - start) over the
+        reads that span it, and the reads that take part without spanning it.  filter: None for one strand, else
+        (exclude_flags, False) of the attachment -- base qualities take no part.  A StrResult: hist of shape
+        (n, strands, 128), partial (n), copies, and the kernel's milliseconds."""
+        loci = np.ascontiguousarray(loci, np.uint32).reshape(-1, 2)
+        r = _lib.cl_str_result()
+        self._check(self._lib.cl_site_str_lengths(self._h, int(min_quality), _filter_ref(filter), int(flank), _ptr(loci) if loci.shape[0] else None,
+                                                  loci.shape[0], C.byref(r)))
+        n, strands = int(r.n_loci), int(r.strands)
+        hist = np.zeros((n, strands, _lib.CL_STR_BINS), np.uint32)
+        partial = np.zeros(n, np.uint32)
+        if n:
+            C.memmove(hist.ctypes.data, r.hist, hist.nbytes)
+            C.memmove(partial.ctypes.data, r.partial, partial.nbytes)
+        return StrResult(hist=hist, partial=partial, kernel_ms=self.site_scan_stats()[0])
+
     def site_scan_ins_stats(self):
         """(window scan milliseconds, allele launch milliseconds) of the last site_scan_ins."""
         a = C.c_double(); b = C.c_double()
@@ -437,6 +455,16 @@ INS_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("pad", np.uint
 
 # cl_ins_obs: key = the first 32 inserted 4-bit codes, base j in key[j // 16] at bits 60 - 4 * (j % 16)
 INS_OBS = np.dtype([("pos", np.uint32), ("len", np.uint32), ("key", np.uint64, (2,)), ("strand", np.uint32), ("pad", np.uint32)])
+
+
+@dataclass
+class StrResult:
+    """cl_str_result (include/callable_loci.h): hist[i, strand, delta + 63] = the reads that span locus i with that delta
+    (bin 127: every delta outside [-63, 63]; strand 0 forward, 1 reverse under a filter), partial[i] = the reads that take
+    part without spanning it."""
+    hist: np.ndarray
+    partial: np.ndarray
+    kernel_ms: float = 0.0
 
 
 @dataclass

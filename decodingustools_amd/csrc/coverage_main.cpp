@@ -1,5 +1,5 @@
 // dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
-// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions`, `find-insertions` and `consensus`);
+// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions`, `find-insertions`, `consensus` and `find-strs`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -50,7 +50,9 @@ static void usage()
             "       [--min-ins-per-strand K] [--device 0]\n"
             "       dut-coverage consensus <BAM_FILE> -r <REFERENCE_FILE> -o <FASTA> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3] [--min-ins-fraction 0.7] [--min-ins-count 3]\n"
-            "       [--min-base-quality Q] [--exclude-flags MASK] [--fill N|ref] [--line-width 60] [--changes FILE] [--device 0]\n");
+            "       [--min-base-quality Q] [--exclude-flags MASK] [--fill N|ref] [--line-width 60] [--changes FILE] [--device 0]\n"
+            "       dut-coverage find-strs <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> --loci FILE [--flank 5] [--min-depth 10]\n"
+            "       [--min-quality 20] [--min-allele-fraction 0.7] [--exclude-flags MASK] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -239,7 +241,7 @@ static bool cli_count32(const char *flag, const std::string &v, uint32_t &dst)
     return true;
 }
 
-// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions, consensus) share on the command line: the BAM, -r, -o,
+// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions, consensus, find-strs) share on the command line: the BAM, -r, -o,
 // -L, --region (0-based, half open), --min-depth, --min-quality, the two filter flags, --device, -h.
 struct ScanCli {
     const char *name;
@@ -521,6 +523,49 @@ static int consensus_main(int argc, char **argv)
                                                    c.out.c_str(), changes.empty() ? nullptr : changes.c_str(), c.device, err, sizeof(err)), err);
 }
 
+static void usage_fs()
+{
+    fprintf(stderr, "Usage: dut-coverage find-strs <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> --loci FILE [--flank 5]\n"
+                    "       [--min-depth 10] [--min-quality 20] [--min-allele-fraction 0.7] [--exclude-flags MASK] [--device 0]\n"
+                    "  The allele length of every short tandem repeat of FILE on the contig (tab separated: contig start end period\n"
+                    "  name, 0-based half open, at most 1024 positions long): the bases each read holds between the two flanks of\n"
+                    "  --flank matched bases (1..64), counted over the reads that span the locus, wherever their aligner put the\n"
+                    "  gaps.  A locus is called when at least --min-depth reads span it and one length holds --min-allele-fraction\n"
+                    "  of them (a decimal in (0, 1], at most four decimals).  MASK as in find-variants.  Lengths only, one device.\n");
+}
+
+// find-strs: per locus of a user-supplied catalogue the histogram of spanning reads' lengths (cl_site_str_lengths) and the
+// allele it supports, in repeat units.  Argument errors leave with 2 before a device is opened.
+static int find_strs_main(int argc, char **argv)
+{
+    ScanCli c = {"find-strs", usage_fs};
+    dut_str_options o = {10, 20, 0, 5, 7000};
+    std::string loci;
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        if (a == "--loci") { loci = next(); return 1; }
+        if (a == "--flank") {
+            const std::string v = next();
+            if (!cli_count32("--flank", v, o.flank)) return -1;
+            if (o.flank < 1 || o.flank > CL_STR_MAX_FLANK) { fprintf(stderr, "error: invalid value '%s' for '--flank': 1..%u\n", v.c_str(), (unsigned)CL_STR_MAX_FLANK); return -1; }
+            return 1;
+        }
+        if (a == "--min-allele-fraction") {
+            const std::string v = next();
+            char why[128] = {0};
+            if (dut_del_fraction_parse(v.c_str(), &o.min_allele_per_10k, why, sizeof(why)) == CL_OK) return 1;
+            fprintf(stderr, "error: invalid value '%s' for '--min-allele-fraction': %s\n", v.c_str(), why);
+            return -1;
+        }
+        return 0;
+    });
+    if (st >= 0) return st;
+    if (loci.empty()) { fprintf(stderr, "error: find-strs needs '--loci <FILE>'\n"); usage_fs(); return 2; }
+    if (c.has_region || c.has_min_base_quality) { fprintf(stderr, "error: find-strs takes neither '--region' nor '--min-base-quality'\n"); usage_fs(); return 2; }
+    o.min_depth = (uint32_t)c.min_depth; o.min_quality = (uint8_t)c.min_quality; o.exclude_flags = c.exclude_flags;
+    char err[1024] = {0};
+    return scan_cli_leave(dut_find_strs_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), loci.c_str(), &o, c.out.c_str(), c.device, err, sizeof(err)), err);
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -543,6 +588,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "find-deletions")) return find_deletions_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-insertions")) return find_insertions_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "consensus")) return consensus_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "find-strs")) return find_strs_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

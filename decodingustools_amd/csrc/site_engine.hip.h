@@ -1,7 +1,8 @@
 // site_engine.hip.h -- the site engine (config 5; a textual part of callable_loci.hip's translation unit): the sparse
 // site pileup k_site_pileup with its host side (cl_site_upload / cl_site_run / cl_site_pileup), the host side of the
-// dense scans of site_scan.hip.h (cl_site_scan*, cl_site_attach_quals) and their entry points.  Of a context it uses
-// what EngineBase holds and its own SiteResident.
+// dense scans of site_scan.hip.h (cl_site_scan*, cl_site_attach_quals) and their entry points, and the repeat lengths
+// of site_str.hip.h (cl_site_str_lengths), which it includes.  Of a context it uses what EngineBase holds and its own
+// SiteResident.
 #pragma once
 
 #include "kernels.hip.h"
@@ -168,6 +169,10 @@ struct SiteResident {
     // cl_site_scan_consensus: the packed bytes of the launched windows, four positions per word, and the range's bytes
     DevBuf<uint32_t> sk_cons;
     std::vector<uint8_t> cons_bytes;
+    // cl_site_str_lengths (site_str.hip.h): the loci as sent, their histograms and partial counts, on the device and back
+    DevBuf<cl_str_locus> st_loci;
+    DevBuf<uint32_t> st_hist, st_partial;
+    std::vector<uint32_t> str_hist, str_partial;
     // the last cl_site_pileup / cl_site_run and the last cl_site_scan* of either form: the kernels' duration and their
     // algorithmic bytes; the candidates of the last cl_site_scan, cl_site_scan_ex, cl_site_scan_minor and cl_site_scan_dels
     KernelTimer t_pileup, t_scan;
@@ -183,6 +188,7 @@ struct SiteResident {
         t_pileup.destroy(); t_scan.destroy();
         q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release(); sd_cand.release();
         si_cand.release(); si_site.release(); si_obs.release(); si_found.release(); sk_cons.release();
+        st_loci.release(); st_hist.release(); st_partial.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -934,6 +940,8 @@ template <class F> static cl_status site_entry(cl_ctx *h, F &&f)
     SiteCtx *c = site_ctx(h);
     return guarded(c, [&] { return f(c); });
 }
+
+#include "site_str.hip.h"
 
 extern "C" {
 

@@ -6,7 +6,9 @@
 // the TSV, and dut_find_deletions_files over cl_site_scan_dels.  And for `find-insertions`: the insertion rule, the
 // grouping of observations into alleles, the TSV, and dut_find_insertions_files over cl_site_scan_ins.  And for `consensus`:
 // the composed rule, the assembly of the bytes of cl_site_scan_consensus and the insertions into a sequence and a change
-// list, the FASTA and the change list's file, and dut_find_consensus_files over both scans on one resident tile.
+// list, the FASTA and the change list's file, and dut_find_consensus_files over both scans on one resident tile.  And for
+// `find-strs`: the host route of cl_site_str_lengths over str_walk.h (dut_str_measure), the rule that turns a length
+// histogram into an allele, the unit notation, the loci file's parser, the TSV, and dut_find_strs_files.
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -20,6 +22,7 @@
 #include <type_traits>
 #include <vector>
 #include "host_parallel.h"
+#include "str_walk.h"
 
 namespace {
 
@@ -889,6 +892,263 @@ int dut_find_variants_files(const char *bam_path, const char *fasta_path, const 
 {
     return dut_find_variants_files_ex(bam_path, fasta_path, contig, has_region, start, end, tree_json_path, provider, tree_type,
                                       output_path, min_depth, min_quality, nullptr, device_id, err, err_len);
+}
+
+// ---- find-strs ----
+static bool str_options_ok(const dut_str_options &o, char *err, size_t err_len)
+{
+    char b[96] = {0};
+    if (o.min_depth == 0) snprintf(b, sizeof(b), "min_depth must be at least 1");
+    else if (o.flank < 1 || o.flank > CL_STR_MAX_FLANK) snprintf(b, sizeof(b), "flank must lie in 1..%u", (unsigned)CL_STR_MAX_FLANK);
+    else if (o.min_allele_per_10k < 1 || o.min_allele_per_10k > 10000) snprintf(b, sizeof(b), "min_allele_per_10k must lie in 1..10000");
+    else return true;
+    set_err(err, err_len, b);
+    return false;
+}
+
+static const char *str_locus_fault(uint32_t start, uint32_t end, uint32_t contig_len)
+{
+    return start >= end ? "start >= end" : end > contig_len ? "it ends beyond the contig" : end - start > CL_STR_MAX_SPAN ? "it is longer than 1024 positions" : nullptr;
+}
+
+int dut_str_measure(const int32_t *pos, const uint16_t *flag, const uint8_t *mapq, const uint32_t *cigar_off, const uint32_t *cigar,
+                    uint64_t n_reads, uint32_t contig_len, uint8_t min_quality, uint16_t exclude_flags, uint32_t flank,
+                    const cl_str_locus *loci, size_t n_loci, uint32_t *hist, uint32_t *partial, uint32_t strands)
+{
+    return no_throw(nullptr, 0, [&]() -> int {
+        if (strands < 1 || strands > 2 || flank < 1 || flank > CL_STR_MAX_FLANK) return CL_ERR_INVALID;
+        if (n_reads && (!pos || !mapq || !cigar_off || (strands == 2 && !flag))) return CL_ERR_INVALID;
+        if (n_loci && (!loci || !hist || !partial)) return CL_ERR_INVALID;
+        if (n_reads > 0xFFFFFFF0ull) return CL_ERR_INVALID;
+        for (size_t i = 0; i < n_loci; ++i) if (str_locus_fault(loci[i].start, loci[i].end, contig_len)) return CL_ERR_INVALID;
+        for (uint64_t r = 0; r < n_reads; ++r) if (cigar_off[r + 1] < cigar_off[r]) return CL_ERR_INVALID;
+        if (n_reads && cigar_off[n_reads] > cigar_off[0] && !cigar) return CL_ERR_INVALID;
+        // the reads of a locus: per read its reference end (0: it never takes part), per window of kWin positions the range
+        // of the reads that overlap it -- wider for an unsorted tile, exact all the same
+        constexpr uint32_t kWin = CL_STR_MAX_SPAN;
+        const size_t n_win = ((size_t)contig_len + kWin - 1) / kWin;
+        std::vector<uint32_t> rend(n_reads, 0), wfirst(n_win + 1, 0xFFFFFFFFu), wlast(n_win + 1, 0);
+        for (uint64_t r = 0; r < n_reads; ++r) {
+            const uint32_t x = (uint32_t)pos[r];
+            if (x >= contig_len) continue;
+            uint64_t span = 0;
+            for (uint32_t k = cigar_off[r]; k < cigar_off[r + 1]; ++k) { const uint32_t c = cigar[k]; span += ((0x18Du >> (c & 15u)) & 1u) ? (c >> 4) : 0u; }
+            if (!span) continue;
+            const uint64_t xe = (uint64_t)x + span;
+            rend[r] = xe > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)xe;
+            const uint32_t last_p = std::min(rend[r], contig_len) - 1u;
+            for (uint32_t w = x / kWin; w <= last_p / kWin; ++w) { wfirst[w] = std::min(wfirst[w], (uint32_t)r); wlast[w] = std::max(wlast[w], (uint32_t)r + 1u); }
+        }
+        dut::parallel_for(n_loci, 16, [&](size_t i) {
+            const uint32_t s = loci[i].start, e = loci[i].end;
+            uint32_t *h = hist + i * strands * CL_STR_BINS;
+            memset(h, 0, (size_t)strands * CL_STR_BINS * 4);
+            uint32_t part = 0;
+            const uint32_t w0 = s / kWin, w1 = (e - 1u) / kWin;
+            const uint32_t r0 = std::min(wfirst[w0], wfirst[w1]), r1 = std::max(wlast[w0], wlast[w1]);
+            for (uint32_t r = r0; r < r1; ++r) {
+                if (mapq[r] < min_quality || rend[r] <= s || (uint32_t)pos[r] >= e) continue;
+                uint32_t rev = 0;
+                if (strands == 2) { if (flag[r] & exclude_flags) continue; rev = (flag[r] >> 4) & 1u; }
+                const dut::StrMeasure m = dut::str_measure_read((uint32_t)pos[r], cigar + cigar_off[r], cigar_off[r + 1] - cigar_off[r], s, e, flank);
+                if (m.spanning) h[rev * CL_STR_BINS + dut::str_bin(m.delta)] += 1u; else part += 1u;
+            }
+            partial[i] = part;
+        });
+        return CL_OK;
+    });
+}
+
+int dut_str_call(const uint32_t *hist_fwd, const uint32_t *hist_rev, const dut_str_params *params, dut_str_allele_call *call)
+{
+    if (!hist_fwd || !params || !call) return CL_ERR_INVALID;
+    if (params->min_depth == 0 || params->min_allele_per_10k < 1 || params->min_allele_per_10k > 10000) return CL_ERR_INVALID;
+    auto at = [&](int b) -> uint64_t { return (uint64_t)hist_fwd[b] + (hist_rev ? hist_rev[b] : 0u); };
+    uint64_t n = 0;
+    for (int b = 0; b < CL_STR_BINS; ++b) n += at(b);
+    int top = 0, second = -1;
+    for (int b = 1; b < CL_STR_BINS - 1; ++b) if (at(b) > at(top)) top = b;                // the first among equals: the smallest delta
+    for (int b = 0; b < CL_STR_BINS - 1; ++b) if (b != top && (second < 0 || at(b) > at(second))) second = b;
+    memset(call, 0, sizeof(*call));
+    call->n = n; call->other = at(CL_STR_BINS - 1);
+    call->delta = top - 63; call->count = (uint32_t)at(top); call->fwd = hist_fwd[top]; call->rev = hist_rev ? hist_rev[top] : 0u;
+    call->delta2 = second - 63; call->count2 = (uint32_t)at(second);
+    call->status = n < params->min_depth ? DUT_STR_LOW_DEPTH
+                 : 10000ull * at(top) >= (uint64_t)params->min_allele_per_10k * n ? DUT_STR_CALLED : DUT_STR_MIXED;
+    return CL_OK;
+}
+
+int dut_str_units(uint32_t span, int32_t delta, uint32_t period, char *buf)
+{
+    if (buf) buf[0] = 0;
+    const int64_t len = (int64_t)span + delta;
+    if (!buf || period < 1 || period > 255 || len < 0) return CL_ERR_INVALID;
+    if (len % period) snprintf(buf, DUT_STR_UNITS_LEN, "%lld.%lld", (long long)(len / period), (long long)(len % period));
+    else snprintf(buf, DUT_STR_UNITS_LEN, "%lld", (long long)(len / period));
+    return CL_OK;
+}
+
+// a decimal number below 2^32 and nothing else
+static bool str_number(const std::string &t, uint32_t &v)
+{
+    if (t.empty() || t.size() > 10) return false;
+    uint64_t x = 0;
+    for (char ch : t) { if (ch < '0' || ch > '9') return false; x = x * 10 + (uint64_t)(ch - '0'); }
+    if (x > 0xFFFFFFFFull) return false;
+    v = (uint32_t)x;
+    return true;
+}
+
+int dut_str_loci_parse(const char *path, const char *contig, dut_str_locus **loci, size_t *n_loci, size_t *n_skipped, char *err, size_t err_len)
+{
+    if (loci) *loci = nullptr;
+    if (n_loci) *n_loci = 0;
+    if (n_skipped) *n_skipped = 0;
+    return no_throw(err, err_len, [&]() -> int {
+        if (!path || !contig || !loci || !n_loci || !n_skipped) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        FILE *f = fopen(path, "rb");
+        if (!f) { set_err(err, err_len, std::string("cannot read the loci file ") + path); return CL_ERR_INVALID; }
+        std::string text;
+        char buf[65536];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got);
+        const bool bad = ferror(f) != 0;
+        fclose(f);
+        if (bad) { set_err(err, err_len, std::string("cannot read the loci file ") + path); return CL_ERR_INVALID; }
+        std::vector<dut_str_locus> out;
+        size_t skipped = 0, line_no = 0;
+        for (size_t at = 0; at < text.size();) {
+            size_t nl = text.find('\n', at);
+            if (nl == std::string::npos) nl = text.size();
+            std::string line = text.substr(at, nl - at);
+            at = nl + 1;
+            ++line_no;
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty() || line[0] == '#') continue;
+            std::vector<std::string> col;
+            for (size_t a = 0; col.size() < 5;) {
+                const size_t t = line.find('\t', a);
+                col.push_back(line.substr(a, t == std::string::npos ? std::string::npos : t - a));
+                if (t == std::string::npos) break;
+                a = t + 1;
+            }
+            auto malformed = [&](const char *why) {
+                set_err(err, err_len, std::string(path) + ": line " + std::to_string(line_no) + ": " + why);
+                return CL_ERR_INVALID;
+            };
+            if (col.size() < 5) return malformed("fewer than five tab-separated columns (contig start end period name)");
+            dut_str_locus l;
+            memset(&l, 0, sizeof(l));
+            if (col[0].empty()) return malformed("an empty contig");
+            if (!str_number(col[1], l.start)) return malformed("start is not a decimal number below 2^32");
+            if (!str_number(col[2], l.end)) return malformed("end is not a decimal number below 2^32");
+            if (!str_number(col[3], l.period)) return malformed("period is not a decimal number");
+            if (l.start >= l.end) return malformed("start >= end");
+            if (l.period < 1 || l.period > 255) return malformed("period must lie in 1..255");
+            if (col[4].empty() || col[4].size() >= sizeof(l.name)) return malformed("the name must have 1..63 bytes");
+            if (col[0] != contig) { ++skipped; continue; }
+            memcpy(l.name, col[4].data(), col[4].size());
+            out.push_back(l);
+        }
+        if (!out.empty()) {
+            dut_str_locus *p = (dut_str_locus *)malloc(out.size() * sizeof(dut_str_locus));
+            if (!p) { set_err(err, err_len, "out of memory"); return CL_ERR_NOMEM; }
+            memcpy(p, out.data(), out.size() * sizeof(dut_str_locus));
+            *loci = p;
+        }
+        *n_loci = out.size(); *n_skipped = skipped;
+        return CL_OK;
+    });
+}
+
+void dut_str_loci_free(dut_str_locus *loci) { free(loci); }
+
+int dut_str_write(const char *path, const char *contig, const dut_str_locus *loci, size_t n_loci, size_t n_skipped, const uint32_t *hist,
+                  const uint32_t *partial, uint32_t strands, const dut_str_options *opt, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&]() -> int {
+        if (!path || !contig || !opt || (n_loci && (!loci || !hist || !partial))) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (strands < 1 || strands > 2) { set_err(err, err_len, "strands must be 1 or 2"); return CL_ERR_INVALID; }
+        if (!str_options_ok(*opt, err, err_len)) return CL_ERR_INVALID;
+        const dut_str_params prm = {opt->min_depth, opt->min_allele_per_10k};
+        const char *const STATUS[] = {"low_depth", "mixed", "called"};
+        uint64_t n_class[3] = {0, 0, 0};
+        std::string body;
+        char b[768];
+        for (size_t i = 0; i < n_loci; ++i) {
+            const dut_str_locus &l = loci[i];
+            const uint32_t *hf = hist + i * strands * CL_STR_BINS, *hr = strands == 2 ? hf + CL_STR_BINS : nullptr;
+            dut_str_allele_call c;
+            if (dut_str_call(hf, hr, &prm, &c) != CL_OK) { set_err(err, err_len, "calling a locus failed"); return CL_ERR_INVALID; }
+            n_class[c.status] += 1;
+            const uint32_t span = l.end - l.start;
+            // (a bin without a read may stand for a length below zero: it is never printed)
+            const bool has1 = c.status != DUT_STR_LOW_DEPTH && c.count > 0, has2 = c.count2 > 0;
+            char ru[DUT_STR_UNITS_LEN], a1[DUT_STR_UNITS_LEN], a2[DUT_STR_UNITS_LEN], d1[16], d2[16];
+            if (l.start >= l.end || dut_str_units(span, 0, l.period, ru) != CL_OK || (has1 && dut_str_units(span, c.delta, l.period, a1) != CL_OK) ||
+                (has2 && dut_str_units(span, c.delta2, l.period, a2) != CL_OK)) {
+                set_err(err, err_len, "locus " + std::to_string(i) + ": start >= end, a period outside 1..255 or reads in a bin below the locus's own length");
+                return CL_ERR_INVALID;
+            }
+            snprintf(d1, sizeof(d1), c.delta ? "%+d" : "%d", c.delta);
+            snprintf(d2, sizeof(d2), c.delta2 ? "%+d" : "%d", c.delta2);
+            snprintf(b, sizeof(b), "%s\t%u\t%u\t%s\t%u\t%s\t%llu\t%u\t%llu\t%s", contig, l.start, l.end, l.name, l.period, ru, (unsigned long long)c.n,
+                     partial[i], (unsigned long long)c.other, STATUS[c.status]);
+            body += b;
+            if (!has1) body += "\t.\t.\t.\t.\t.\t.";
+            else { snprintf(b, sizeof(b), "\t%s\t%s\t%u\t%.4f\t%u\t%u", a1, d1, c.count, (double)c.count / (double)c.n, c.fwd, c.rev); body += b; }
+            if (!has2) body += "\t.\t.\t.\n";
+            else { snprintf(b, sizeof(b), "\t%s\t%s\t%u\n", a2, d2, c.count2); body += b; }
+        }
+        std::string s;
+        snprintf(b, sizeof(b), "##contig=%s\n##loci=%llu\n##loci_skipped=%llu\n##flank=%u\n##min_depth=%u\n##min_quality=%u\n##exclude_flags=0x%04x\n"
+                               "##min_allele_fraction=%.4f\n##low_depth=%llu\n##mixed=%llu\n##called=%llu\n",
+                 contig, (unsigned long long)n_loci, (unsigned long long)n_skipped, opt->flank, opt->min_depth, (unsigned)opt->min_quality,
+                 (unsigned)opt->exclude_flags, (double)opt->min_allele_per_10k / 10000.0, (unsigned long long)n_class[0], (unsigned long long)n_class[1],
+                 (unsigned long long)n_class[2]);
+        s += b;
+        s += "#contig\tstart\tend\tname\tperiod\tref_units\tspanning\tpartial\tother\tstatus\tallele\tdelta\tcount\tfreq\tfwd\trev\tallele2\tdelta2\tcount2\n";
+        s += body;
+        return write_file(path, s, err, err_len);
+    });
+}
+
+int dut_find_strs_files(const char *bam_path, const char *fasta_path, const char *contig, const char *loci_path, const dut_str_options *opt,
+                        const char *output_path, int device_id, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&]() -> int {
+        if (!bam_path || !fasta_path || !contig || !loci_path || !output_path || !opt) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (!str_options_ok(*opt, err, err_len)) return CL_ERR_INVALID;
+        dut_str_locus *lp = nullptr; size_t n = 0, skipped = 0;
+        int rc = dut_str_loci_parse(loci_path, contig, &lp, &n, &skipped, err, err_len);
+        if (rc != CL_OK) return rc;
+        std::unique_ptr<dut_str_locus, decltype(&dut_str_loci_free)> own(lp, dut_str_loci_free);
+        ScanFiles F;
+        uint32_t start = 0, end = 0;
+        if ((rc = scan_files_open(F, bam_path, fasta_path, contig, 0, start, end, err, err_len)) != CL_OK) return rc;
+        for (size_t i = 0; i < n; ++i)
+            if (const char *why = str_locus_fault(lp[i].start, lp[i].end, F.contig_len)) {
+                set_err(err, err_len, std::string("locus ") + lp[i].name + " [" + std::to_string(lp[i].start) + ", " + std::to_string(lp[i].end) + ") of " +
+                                          contig + " (" + std::to_string(F.contig_len) + " bases): " + why);
+                return CL_ERR_INVALID;
+            }
+        const FilterOptions flt = {0, 0, opt->exclude_flags};
+        cl_scan_filter f;
+        if ((rc = scan_files_resident(F, contig, device_id, &flt, f, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
+        std::vector<uint32_t> hist(n * 2 * CL_STR_BINS), partial(n);
+        std::vector<cl_str_locus> chunk;
+        for (size_t at = 0; at < n; at += CL_STR_MAX_LOCI) {
+            const size_t m = std::min<size_t>(n - at, CL_STR_MAX_LOCI);
+            chunk.resize(m);
+            for (size_t i = 0; i < m; ++i) chunk[i] = {lp[at + i].start, lp[at + i].end};
+            cl_str_result res;
+            rc = cl_site_str_lengths(F.ctx.get(), opt->min_quality, &f, opt->flank, chunk.data(), m, &res);
+            if (rc != CL_OK) { F.engine_err(err, err_len, "measuring the loci failed"); return rc; }
+            memcpy(hist.data() + at * 2 * CL_STR_BINS, res.hist, m * 2 * CL_STR_BINS * 4);
+            memcpy(partial.data() + at, res.partial, m * 4);
+        }
+        return dut_str_write(output_path, contig, lp, n, skipped, hist.data(), partial.data(), 2, opt, err, err_len);
+    });
 }
 
 } // extern "C"

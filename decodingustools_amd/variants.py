@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from .callable_loci import (DEL_CANDIDATE, INS_CANDIDATE, INS_OBS, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, ConsResult, DelResult,
-                            EngineError, InsResult, MinorResult, ScanResult)
+                            EngineError, InsResult, MinorResult, ScanResult, StrResult, _ptr)
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
@@ -24,6 +24,8 @@ CONS_CLASS_NAMES = ("low_depth", "deleted", "no_call", "ref", "alt")
 CONS_KINDS = ("snv", "del", "ins", "ins_skipped")
 CONS_NOTES = ("", "anchor_deleted", "too_long", "no_allele")
 CLASS_NAMES = ("low_depth", "mixed", "uncomparable", "match", "variant", "undetermined")
+STR_LOW_DEPTH, STR_MIXED, STR_CALLED = range(3)
+STR_STATUS_NAMES = ("low_depth", "mixed", "called")
 
 
 def _classify(fn, counts, width, ref_byte, min_depth) -> Tuple[int, str]:
@@ -448,3 +450,97 @@ def consensus(bam_file: str, reference_file: str, contig: str, output_file: str,
                         del_fraction_parse(str(min_ins_fraction)), min_base_quality, exclude_flags, fill, line_width)
     _find_files(_lib.load().dut_find_consensus_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(),
                 changes_file.encode() if changes_file else None, device_id)
+
+
+def str_measure(rec, contig_len: int, loci, flank: int, min_quality: int, exclude_flags: Optional[int] = None) -> StrResult:
+    """dut_str_measure: what Engine.site_str_lengths returns, from the records on the host (no device needed).
+    exclude_flags=None: one strand, no flag takes part; a mask (0 included): two strands, forward first."""
+    loci = np.ascontiguousarray(loci, np.uint32).reshape(-1, 2)
+    strands = 1 if exclude_flags is None else 2
+    hist = np.zeros((loci.shape[0], strands, _lib.CL_STR_BINS), np.uint32)
+    partial = np.zeros(loci.shape[0], np.uint32)
+    pos, mapq = np.ascontiguousarray(rec.pos, np.int32), np.ascontiguousarray(rec.mapq, np.uint8)
+    flag = np.ascontiguousarray(rec.flag, np.uint16)
+    cigar_off, cigar = np.ascontiguousarray(rec.cigar_off, np.uint32), np.ascontiguousarray(rec.cigar, np.uint32)
+    st = _lib.load().dut_str_measure(_ptr(pos), _ptr(flag), _ptr(mapq), _ptr(cigar_off), _ptr(cigar), int(rec.n), int(contig_len), int(min_quality),
+                                     int(exclude_flags or 0), int(flank), _ptr(loci) if loci.shape[0] else None, loci.shape[0],
+                                     _ptr(hist) if loci.shape[0] else None, _ptr(partial) if loci.shape[0] else None, strands)
+    if st != 0:
+        raise EngineError(st, "dut_str_measure refused its arguments")
+    return StrResult(hist=hist, partial=partial)
+
+
+def str_call(hist_fwd, hist_rev=None, min_depth: int = 10, min_allele_per_10k: int = 7000) -> dict:
+    """dut_str_call: the allele of one locus from its histogram(s) of 128 bins -- status (STR_LOW_DEPTH, STR_MIXED,
+    STR_CALLED), n, other, the top allele's delta, count, fwd, rev and the second's delta2, count2."""
+    hf = np.ascontiguousarray(hist_fwd, np.uint32).reshape(-1)
+    hr = None if hist_rev is None else np.ascontiguousarray(hist_rev, np.uint32).reshape(-1)
+    if hf.shape[0] != _lib.CL_STR_BINS or (hr is not None and hr.shape[0] != _lib.CL_STR_BINS):
+        raise ValueError("a histogram has 128 bins")
+    prm = _lib.dut_str_params(int(min_depth), int(min_allele_per_10k))
+    c = _lib.dut_str_allele_call()
+    st = _lib.load().dut_str_call(_ptr(hf), _ptr(hr), C.byref(prm), C.byref(c))
+    if st != 0:
+        raise EngineError(st, "invalid parameters")
+    return dict(status=int(c.status), n=int(c.n), other=int(c.other), delta=int(c.delta), count=int(c.count), fwd=int(c.fwd), rev=int(c.rev),
+                delta2=int(c.delta2), count2=int(c.count2))
+
+
+def str_units(span: int, delta: int, period: int) -> str:
+    """dut_str_units: span + delta bases in units of `period`, "9.3" for nine units and three bases."""
+    buf = C.create_string_buffer(_lib.DUT_STR_UNITS_LEN)
+    if not (0 <= int(span) <= 0xFFFFFFFF and -2 ** 31 <= int(delta) < 2 ** 31 and 0 <= int(period) <= 0xFFFFFFFF):
+        raise ValueError("span, delta or period out of range")
+    st = _lib.load().dut_str_units(int(span), int(delta), int(period), buf)
+    if st != 0:
+        raise EngineError(st, "period outside 1..255 or a length below zero")
+    return buf.value.decode()
+
+
+def str_loci_parse(path: str, contig: str) -> Tuple[List[dict], int]:
+    """dut_str_loci_parse: (the loci of `contig` in file order as dicts of start, end, period, name; the lines of other
+    contigs).  An EngineError names a malformed line by its number."""
+    lib = _lib.load()
+    lp = C.POINTER(_lib.dut_str_locus)()
+    n, skipped = C.c_size_t(), C.c_size_t()
+    _call(lib.dut_str_loci_parse, path.encode(), contig.encode(), C.byref(lp), C.byref(n), C.byref(skipped))
+    try:
+        return [dict(start=int(l.start), end=int(l.end), period=int(l.period), name=l.name.decode()) for l in lp[:n.value]], int(skipped.value)
+    finally:
+        lib.dut_str_loci_free(lp)
+
+
+def _str_options(min_depth, min_quality, exclude_flags, flank, min_allele_fraction):
+    if not 0 <= int(min_quality) <= 255:
+        raise ValueError("min_quality: 0..255")
+    if not 0 <= int(exclude_flags) <= 0xFFFF:
+        raise ValueError("exclude_flags: 0..65535")
+    for name, v in (("min_depth", min_depth), ("flank", flank)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name}: 0..2^32-1")
+    return _lib.dut_str_options(int(min_depth), int(min_quality), int(exclude_flags), int(flank), del_fraction_parse(str(min_allele_fraction)))
+
+
+def write_strs(path: str, contig: str, loci, result: StrResult, loci_skipped: int = 0, flank: int = 5, min_depth: int = 10, min_quality: int = 20,
+               min_allele_fraction="0.7", exclude_flags: int = 0):
+    """The TSV of find-strs (dut_str_write) for loci (dicts of start, end, period, name, as str_loci_parse returns them) and
+    the StrResult of Engine.site_str_lengths or str_measure over them.  No device is needed."""
+    arr = (_lib.dut_str_locus * max(len(loci), 1))()
+    for i, l in enumerate(loci):
+        arr[i].start, arr[i].end, arr[i].period, arr[i].name = int(l["start"]), int(l["end"]), int(l["period"]), l["name"].encode()
+    hist = np.ascontiguousarray(result.hist, np.uint32)
+    partial = np.ascontiguousarray(result.partial, np.uint32)
+    if hist.ndim != 3 or hist.shape[0] != len(loci) or hist.shape[2] != _lib.CL_STR_BINS or partial.shape != (len(loci),):
+        raise ValueError("the result does not belong to these loci")
+    opt = _str_options(min_depth, min_quality, exclude_flags, flank, min_allele_fraction)
+    _call(_lib.load().dut_str_write, path.encode(), contig.encode(), arr, len(loci), int(loci_skipped), _ptr(hist) if len(loci) else None,
+          _ptr(partial) if len(loci) else None, int(hist.shape[1]), C.byref(opt))
+
+
+def find_strs(bam_file: str, reference_file: str, contig: str, loci_file: str, output_file: str, flank: int = 5, min_depth: int = 10,
+              min_quality: int = 20, min_allele_fraction="0.7", exclude_flags: int = 0, device_id: int = 0):
+    """dut_find_strs_files: BAM (+ index), FASTA and a loci file (contig start end period name, tab separated, 0-based half
+    open) in, the TSV of repeat alleles out.  min_allele_fraction: decimal text in (0, 1], at most four decimals."""
+    opt = _str_options(min_depth, min_quality, exclude_flags, flank, min_allele_fraction)
+    _call(_lib.load().dut_find_strs_files, bam_file.encode(), reference_file.encode(), contig.encode(), loci_file.encode(), C.byref(opt),
+          output_file.encode(), device_id, size=1024)

@@ -608,6 +608,47 @@ cl_status cl_site_scan_consensus(cl_ctx *ctx, uint8_t min_quality, const cl_scan
                                  const cl_cons_params *params, const uint8_t *ref_bases, uint64_t ref_len,
                                  uint32_t start, uint32_t end, cl_cons_result *out);
 
+/* ---- short tandem repeats: the length of the sample's sequence over whole intervals of the resident tile -------------- */
+/* The unit is a locus [start, end) on the tile's contig, 0-based half open, with a flank F, not a position: how many bases
+ * a read holds between the two flanks does not depend on where its aligner placed the gaps inside the repeat.
+ * A read takes part iff it passes the gates of cl_site_scan (read start < contig_len, mapq >= min_quality; under a filter
+ * (flag & exclude_flags) == 0, reverse iff flag & 0x10), has a reference span and overlaps the locus (pos < end and
+ * pos + span > start).  Its CIGAR is walked with x, the reference position reached, from pos:
+ *   M = X of length l    qlen += |[x, x+l) cut with [s, e)|; m_left += |... cut with [s-F, s)|; m_right += |... cut with
+ *                        [e, e+F)|; x += l
+ *   I of length l at x   s <= x <= e: qlen += l (both borders belong to the locus); s-F < x < s: i_left += l;
+ *                        e < x < e+F: i_right += l; elsewhere nothing
+ *   D                    x += l, nothing else (the deleted positions are simply not in qlen)
+ *   N                    x += l; skipped = true if it overlaps [s, e)
+ *   S H P                take no part
+ * Stored bases take no part: neither seq4 nor pass bits are read, and a read with fewer stored bases than its CIGAR
+ * consumes counts by its CIGAR.  The read is spanning iff m_left == F, m_right == F, i_left == 0, i_right == 0 and not
+ * skipped -- both flanks matched base by base with no gap inside them (so pos <= s - F and pos + span >= e + F; a locus
+ * with s < F has no spanning read) -- and partial otherwise.  A spanning read adds one to bin delta + 63 of its strand for
+ * delta = qlen - (e - s) in [-63, 63], and to bin 127 ("other") for every other delta.
+ * hist[(i * strands + strand) * CL_STR_BINS + bin] and partial[i] for loci[i], in the caller's order; loci may overlap,
+ * repeat and come in any order.  strands is 1 without a filter and 2 with one, forward first.  The arrays are context-owned,
+ * in storage of their own, valid until the next cl_site_str_lengths, cl_site_upload or cl_destroy; any order of this call,
+ * cl_site_run and the scans on one tile is allowed, and the call builds the read index itself when it is the first on a
+ * fresh tile.  n_loci == 0 returns an empty result without a launch.  cl_site_scan_stats speaks of this launch after it.
+ * CL_ERR_INVALID (with a message, the context stays usable): no resident tile, a tile cl_site_pileup filtered, a filter
+ * with nothing attached, filter->use_base_quality != 0 (base qualities take no part), flank outside
+ * [1, CL_STR_MAX_FLANK], n_loci > CL_STR_MAX_LOCI, a locus with start >= end, end > contig_len or
+ * end - start > CL_STR_MAX_SPAN, null loci with n_loci > 0, null out.  CL_ERR_DEVICE: a host-only debug context. */
+#define CL_STR_BINS      128
+#define CL_STR_MAX_FLANK 64
+#define CL_STR_MAX_LOCI  65536
+#define CL_STR_MAX_SPAN  1024
+typedef struct cl_str_locus  { uint32_t start, end; } cl_str_locus;
+typedef struct cl_str_result {
+    size_t          n_loci;
+    const uint32_t *hist;       /* n_loci * strands * CL_STR_BINS */
+    const uint32_t *partial;    /* n_loci */
+    uint32_t        strands;
+} cl_str_result;
+cl_status cl_site_str_lengths(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: one strand */,
+                              uint32_t flank, const cl_str_locus *loci, size_t n_loci, cl_str_result *out);
+
 /* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
  * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
 cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);

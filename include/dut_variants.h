@@ -340,6 +340,89 @@ int dut_find_consensus_files(const char *bam_path, const char *fasta_path, const
                              uint32_t end, const dut_cons_options *opt, const char *output_path, const char *changes_path,
                              int device_id, char *err, size_t err_len);
 
+/* ---- find-strs: allele lengths of short tandem repeats (cl_site_str_lengths) ------------------------------------------ */
+/* cl_site_str_lengths from host arrays, no device needed: the same hist and partial (the rule is written once, in
+ * csrc/str_walk.h, and both routes compile it) for the reads pos / flag / mapq / cigar_off (n_reads + 1) / cigar of a contig
+ * of contig_len positions.  strands == 1: one histogram per locus, flag and exclude_flags take no part (flag may be NULL);
+ * strands == 2: reads with (flag & exclude_flags) != 0 are left out, forward first, reverse iff flag & 0x10.
+ * hist: n_loci * strands * CL_STR_BINS, partial: n_loci, the caller's arrays, in the caller's order of loci.  The loci are
+ * spread over DUT_THREADS threads.  CL_ERR_INVALID: a null array, strands outside 1..2, flank outside
+ * [1, CL_STR_MAX_FLANK], a locus with start >= end, end > contig_len or end - start > CL_STR_MAX_SPAN, offsets that
+ * decrease.  What a caller without a device gets, and the yardstick of tools/str_scan_bench.py. */
+int dut_str_measure(const int32_t *pos, const uint16_t *flag, const uint8_t *mapq, const uint32_t *cigar_off, const uint32_t *cigar,
+                    uint64_t n_reads, uint32_t contig_len, uint8_t min_quality, uint16_t exclude_flags, uint32_t flank,
+                    const cl_str_locus *loci, size_t n_loci, uint32_t *hist, uint32_t *partial, uint32_t strands);
+
+/* The allele of one locus from its histogram(s) of CL_STR_BINS bins (hist_rev may be NULL: one strand).
+ *   n           the sum of all 128 bins, strands summed (the spanning reads); other = bin 127
+ *   low_depth   n < min_depth
+ *   top         the fullest of bins 0..126, among equals the smallest delta; bin 127 ("other") never wins
+ *   called      not low and 10000 * count >= min_allele_per_10k * n (taken in 64 bits);  mixed: everything else
+ *   second      the fullest of the remaining bins 0..126 under the same tie rule; count2 may be 0
+ * delta = bin - 63.  fwd / rev: the top allele by strand (fwd == count, rev == 0 without hist_rev).  top and second are
+ * filled in for every status.  CL_ERR_INVALID: a null argument, min_depth == 0, min_allele_per_10k outside [1, 10000]. */
+enum { DUT_STR_LOW_DEPTH = 0, DUT_STR_MIXED = 1, DUT_STR_CALLED = 2 };
+typedef struct dut_str_params { uint32_t min_depth, min_allele_per_10k; } dut_str_params;
+typedef struct dut_str_allele_call {
+    int      status;
+    int32_t  delta, delta2;
+    uint32_t count, fwd, rev, count2;
+    uint64_t n, other;
+} dut_str_allele_call;
+int dut_str_call(const uint32_t *hist_fwd, const uint32_t *hist_rev /* may be NULL */, const dut_str_params *params,
+                 dut_str_allele_call *call);
+
+/* The usual repeat-unit notation of a length: len = span + delta bases of a repeat with units of `period` bases is
+ * len / period, then '.' and len % period when that is not 0 ("9.3": nine units and three bases).  buf: at least
+ * DUT_STR_UNITS_LEN bytes.  CL_ERR_INVALID: null buf, period outside 1..255, span + delta < 0. */
+#define DUT_STR_UNITS_LEN 24
+int dut_str_units(uint32_t span, int32_t delta, uint32_t period, char *buf);
+
+/* One line of a loci file. */
+typedef struct dut_str_locus {
+    uint32_t start, end;              /* 0-based, half open */
+    uint32_t period;                  /* 1..255 */
+    char     name[64];                /* NUL terminated */
+} dut_str_locus;
+
+/* The loci file: tab separated `contig start end period name`, 0-based half open; lines that start with '#' and empty
+ * lines are skipped, columns behind the fifth are ignored, lines of other contigs are skipped and counted in *n_skipped.
+ * *loci: the lines of `contig` in file order, malloc'ed, release with dut_str_loci_free (NULL when there is none).
+ * CL_ERR_INVALID with a message: an unreadable file; a malformed line, named by its number -- fewer than five columns, a
+ * start, end or period that is not a decimal number below 2^32, start >= end, a period outside 1..255, an empty name or
+ * one of more than 63 bytes.  Whether a locus fits the contig is not the parser's question. */
+int dut_str_loci_parse(const char *path, const char *contig, dut_str_locus **loci, size_t *n_loci, size_t *n_skipped,
+                       char *err, size_t err_len);
+void dut_str_loci_free(dut_str_locus *loci);
+
+/* What a find-strs run is asked. */
+typedef struct dut_str_options {
+    uint32_t min_depth;               /* >= 1 */
+    uint8_t  min_quality;
+    uint16_t exclude_flags;
+    uint32_t flank;                   /* 1..CL_STR_MAX_FLANK */
+    uint32_t min_allele_per_10k;      /* 1..10000 */
+} dut_str_options;
+
+/* The TSV (no device needed) of n_loci loci with hist (n_loci * strands * CL_STR_BINS) and partial (n_loci) as
+ * cl_site_str_lengths or dut_str_measure return them: comment lines ##contig= ##loci= ##loci_skipped= ##flank= ##min_depth=
+ * ##min_quality= ##exclude_flags=0x%04x ##min_allele_fraction=%.4f ##low_depth= ##mixed= ##called=, the header
+ *   #contig start end name period ref_units spanning partial other status allele delta count freq fwd rev allele2 delta2 count2
+ * and one line per locus in the given order: ref_units = dut_str_units of the reference's own length; spanning = n of
+ * dut_str_call; status low_depth | mixed | called; allele, allele2 = dut_str_units texts; delta with its sign (+2, -4, 0);
+ * freq = count / spanning as %.4f; the top allele's columns (allele delta count freq fwd rev) are "." for low_depth (and
+ * when no read fell into bins 0..126 at all), the second allele's when its count is 0.  CL_ERR_INVALID: a null argument, strands outside 1..2, refused options. */
+int dut_str_write(const char *path, const char *contig, const dut_str_locus *loci, size_t n_loci, size_t n_skipped,
+                  const uint32_t *hist, const uint32_t *partial, uint32_t strands, const dut_str_options *opt,
+                  char *err, size_t err_len);
+
+/* `find-strs` on files, one GPU: parses the loci file (before any device is opened), reads as dut_find_insertions_files
+ * does, always attaches the records' flags and runs the filtered form of cl_site_str_lengths, in chunks of at most
+ * CL_STR_MAX_LOCI loci, writes the TSV.  Errors with a message: those of dut_find_variants_files, refused options, an
+ * unreadable or malformed loci file, a locus that ends beyond the contig or is longer than CL_STR_MAX_SPAN. */
+int dut_find_strs_files(const char *bam_path, const char *fasta_path, const char *contig, const char *loci_path,
+                        const dut_str_options *opt, const char *output_path, int device_id, char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

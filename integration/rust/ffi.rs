@@ -96,6 +96,19 @@ extern "C" {
                                    start: u32, end: u32, tree_json: *const c_char, provider: c_int, tree_type: c_int,
                                    output: *const c_char, min_depth: u32, min_quality: u8, device_id: c_int,
                                    err: *mut c_char, err_len: usize) -> c_int;
+    // short tandem repeats (README "Short tandem repeats"): per locus [start, end) the histogram of the spanning reads' deltas
+    // and the partial reads, over the tile cl_site_upload left resident; filter null: one strand.  Context-owned arrays,
+    // valid until the next cl_site_str_lengths / upload.  flank 1..64, at most 65536 loci of at most 1024 positions
+    pub fn cl_site_str_lengths(ctx: *mut ClCtx, min_quality: u8, filter: *const ClScanFilter, flank: u32, loci: *const ClStrLocus,
+                               n_loci: usize, out: *mut ClStrResult) -> c_int;
+    // include/dut_variants.h: the same from host arrays, the call of one locus, the unit notation, `find-strs` on files
+    pub fn dut_str_measure(pos: *const i32, flag: *const u16, mapq: *const u8, cigar_off: *const u32, cigar: *const u32, n_reads: u64,
+                           contig_len: u32, min_quality: u8, exclude_flags: u16, flank: u32, loci: *const ClStrLocus, n_loci: usize,
+                           hist: *mut u32, partial: *mut u32, strands: u32) -> c_int;
+    pub fn dut_str_call(hist_fwd: *const u32, hist_rev: *const u32, params: *const DutStrParams, call: *mut DutStrAlleleCall) -> c_int;
+    pub fn dut_str_units(span: u32, delta: i32, period: u32, buf: *mut c_char) -> c_int;                   // buf: 24 bytes
+    pub fn dut_find_strs_files(bam: *const c_char, fasta: *const c_char, contig: *const c_char, loci_path: *const c_char,
+                               opt: *const DutStrOptions, output: *const c_char, device_id: c_int, err: *mut c_char, err_len: usize) -> c_int;
     // include/dut_fingerprint.h: the `fingerprint` sketch on the device (1 <= ksize <= 64)
     pub fn dut_fp_create(opt: *const DutFpOptions, device_id: c_int, stream: *mut c_void, out: *mut *mut DutFpCtx) -> c_int;
     pub fn dut_fp_push_seq4(ctx: *mut DutFpCtx, seq4: *const u8, base_off: *const u64, n_seq: u64) -> c_int;
@@ -123,6 +136,36 @@ pub struct ClScanResult {         // cl_scan_result: the five classes add up to 
     pub start: u32, pub end: u32,
     pub n_low_depth: u64, pub n_mixed: u64, pub n_uncomparable: u64, pub n_match: u64, pub n_variant: u64,
     pub candidates: *const ClScanCandidate,                 // n_variant, ascending position
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ClScanFilter {         // cl_scan_filter: use_base_quality must be 0 for cl_site_str_lengths
+    pub exclude_flags: u16, pub use_base_quality: u8, pub pad: u8,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct ClStrLocus { pub start: u32, pub end: u32 }      // cl_str_locus: 0-based, half open
+
+#[repr(C)]
+pub struct ClStrResult {          // cl_str_result: hist[(i * strands + strand) * 128 + delta + 63], bin 127 = every other delta
+    pub n_loci: usize, pub hist: *const u32, pub partial: *const u32, pub strands: u32,
+}
+
+#[repr(C)]
+pub struct DutStrParams { pub min_depth: u32, pub min_allele_per_10k: u32 }
+
+#[repr(C)]
+pub struct DutStrAlleleCall {     // dut_str_allele_call: status 0 low_depth, 1 mixed, 2 called
+    pub status: c_int, pub delta: i32, pub delta2: i32,
+    pub count: u32, pub fwd: u32, pub rev: u32, pub count2: u32,
+    pub n: u64, pub other: u64,
+}
+
+#[repr(C)]
+pub struct DutStrOptions {        // dut_str_options
+    pub min_depth: u32, pub min_quality: u8, pub exclude_flags: u16, pub flank: u32, pub min_allele_per_10k: u32,
 }
 
 #[repr(C)]
