@@ -159,10 +159,10 @@ struct SiteResident {
     DevBuf<uint32_t> sx_amb, sx_hist;
     bool attached = false;
     DevBuf<ScanMinorCand> sm_cand;   // cl_site_scan_minor's candidates, of either form
-    DevBuf<ScanDelCand> sd_cand;     // cl_site_scan_dels' candidates, of either form
+    DevBuf<ScanCountCand> sd_cand;   // cl_site_scan_dels' candidates, of either form
     // cl_site_scan_ins: its candidates, of either form; the called positions as its allele launch takes them, the
     // observations and the insertions found per position
-    DevBuf<ScanInsCand> si_cand;
+    DevBuf<ScanCountCand> si_cand;
     DevBuf<ScanInsSite> si_site;
     DevBuf<ScanInsObs> si_obs;
     DevBuf<uint32_t> si_found;
@@ -459,13 +459,28 @@ static cl_status cl_site_run_impl(SiteCtx *c, uint8_t min_quality, const uint32_
 
 // ---- config 5, dense form: base counts and calls at every position of a range of the resident tile (site_scan.hip.h),
 // ---- unfiltered (cl_site_scan) and filtered, strand-aware (cl_site_scan_ex, behind cl_site_attach_quals) ----
-static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_candidate) == 28, "the device writes cl_scan_candidate");
-static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44, "the device writes cl_scan_candidate_ex");
-static_assert(sizeof(ScanMinorCand) == sizeof(cl_minor_candidate) && sizeof(cl_minor_candidate) == 44, "the device writes cl_minor_candidate");
-static_assert(sizeof(ScanDelCand) == sizeof(cl_del_candidate) && sizeof(cl_del_candidate) == 32, "the device writes cl_del_candidate");
-static_assert(sizeof(ScanInsCand) == sizeof(cl_ins_candidate) && sizeof(cl_ins_candidate) == 32, "the device writes cl_ins_candidate");
-static_assert(sizeof(ScanInsObs) == sizeof(cl_ins_obs) && sizeof(cl_ins_obs) == 32 && offsetof(ScanInsObs, strand) == offsetof(cl_ins_obs, strand),
+// The device writes the public records field by field and the host copies them out as bytes: the same size, and every
+// field of the device's struct D at the offset and of the width of its field of the public struct H.
+#define SCAN_AT(D, H, df, hf) (offsetof(D, df) == offsetof(H, hf) && sizeof(D::df) == sizeof(H::hf))
+#define SCAN_AT4(D, H, a, b, c, d) (SCAN_AT(D, H, a, a) && SCAN_AT(D, H, b, b) && SCAN_AT(D, H, c, c) && SCAN_AT(D, H, d, d))
+#define SCAN_COUNT_AS(H, x) (sizeof(ScanCountCand) == sizeof(H) && sizeof(H) == 32 && SCAN_AT4(ScanCountCand, H, pos, ref, pad, depth) && SCAN_AT(ScanCountCand, H, n, x) && \
+                             SCAN_AT(ScanCountCand, H, n_fwd, x##_fwd) && SCAN_AT(ScanCountCand, H, n_rev, x##_rev) && SCAN_AT(ScanCountCand, H, depth_fwd, depth_fwd) && \
+                             SCAN_AT(ScanCountCand, H, depth_rev, depth_rev))
+static_assert(sizeof(ScanCand) == sizeof(cl_scan_candidate) && sizeof(cl_scan_candidate) == 28 && SCAN_AT4(ScanCand, cl_scan_candidate, pos, ref, alt, pad) &&
+              SCAN_AT4(ScanCand, cl_scan_candidate, a, c, g, t) && SCAN_AT(ScanCand, cl_scan_candidate, depth, depth), "the device writes cl_scan_candidate");
+static_assert(sizeof(ScanCandEx) == sizeof(cl_scan_candidate_ex) && sizeof(cl_scan_candidate_ex) == 44 && SCAN_AT4(ScanCandEx, cl_scan_candidate_ex, pos, ref, alt, pad) &&
+              SCAN_AT4(ScanCandEx, cl_scan_candidate_ex, a, c, g, t) && SCAN_AT(ScanCandEx, cl_scan_candidate_ex, depth, depth) &&
+              SCAN_AT4(ScanCandEx, cl_scan_candidate_ex, alt_fwd, alt_rev, ref_fwd, ref_rev), "the device writes cl_scan_candidate_ex");
+static_assert(sizeof(ScanMinorCand) == sizeof(cl_minor_candidate) && sizeof(cl_minor_candidate) == 44 && SCAN_AT4(ScanMinorCand, cl_minor_candidate, pos, ref, major, minor) &&
+              SCAN_AT4(ScanMinorCand, cl_minor_candidate, a, c, g, t) && SCAN_AT(ScanMinorCand, cl_minor_candidate, pad, pad) && SCAN_AT(ScanMinorCand, cl_minor_candidate, depth, depth) &&
+              SCAN_AT4(ScanMinorCand, cl_minor_candidate, major_fwd, major_rev, minor_fwd, minor_rev), "the device writes cl_minor_candidate");
+static_assert(SCAN_COUNT_AS(cl_del_candidate, del), "the device writes cl_del_candidate");
+static_assert(SCAN_COUNT_AS(cl_ins_candidate, ins), "the device writes cl_ins_candidate");
+static_assert(sizeof(ScanInsObs) == sizeof(cl_ins_obs) && sizeof(cl_ins_obs) == 32 && SCAN_AT4(ScanInsObs, cl_ins_obs, pos, len, key, strand) && SCAN_AT(ScanInsObs, cl_ins_obs, pad, pad),
               "the device writes cl_ins_obs");
+#undef SCAN_COUNT_AS
+#undef SCAN_AT4
+#undef SCAN_AT
 static_assert(sizeof(ScanInsSite) == 16, "one called position of the allele launch");
 static_assert(CONS_LOW_DEPTH == 0 && CONS_DELETED == 1 && CONS_NO_CALL == 2 && CONS_REF == 3 && CONS_ALT == 4, "the classes of cl_cons_result, in its order");
 
@@ -649,45 +664,56 @@ template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_MINOR> : ScanModeHos
     static uint64_t tile_bytes(const SiteResident &S) { return ScanHost<FILTERED>::tile_bytes(S); }
 };
 
-// the deletion mode: reads whose D operation covers a position, beside the scan's depth (site_scan.hip.h)
-template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_DELS> : ScanModeHostBase {
-    using Result = cl_del_result;
-    using Cand = cl_del_candidate;
-    using Params = const cl_del_params *;
+// The deletion and the insertion mode -- reads whose D operation covers a position, reads with a counting I operation
+// anchored at it, each beside the scan's depth under one count rule (site_scan.hip.h) -- have one host definition.  What
+// they differ in: their C types, the names of the rule's fields in them, where their candidates live, their messages.
+template <ScanMode MODE> struct ScanCountNames;
+template <> struct ScanCountNames<SCAN_DELS> {
+    using Result = cl_del_result; using Cand = cl_del_candidate; using Rule = cl_del_params;
+    static constexpr auto kMinCount = &Rule::min_del_count, kMinPer10k = &Rule::min_del_per_10k;
+    static constexpr auto kCalled = &Result::n_deleted;
+    static constexpr auto kHostCand = &SiteResident::del_cand;
+    static constexpr auto kDevCand = &SiteResident::sd_cand;
     static constexpr const char *kWho = "cl_site_scan_dels", *kLap = "deletion scan: reference in, kernel, candidates back";
-    static std::vector<Cand> &host_cand(SiteResident &S) { return S.del_cand; }
-    static DevBuf<ScanDelCand> &dev_cand(SiteResident &S) { return S.sd_cand; }
-    static const char *fault(Params p)
-    {
-        return !p ? "null params" : p->min_depth == 0 ? kNoDepth : p->min_del_count == 0 ? "min_del_count must be at least 1"
-             : (p->min_del_per_10k < 1 || p->min_del_per_10k > 10000) ? "min_del_per_10k must lie in 1..10000" : nullptr;
-    }
+    static constexpr const char *kNoCount = "min_del_count must be at least 1", *kPer10kRange = "min_del_per_10k must lie in 1..10000";
+};
+template <> struct ScanCountNames<SCAN_INS> {
+    using Result = cl_ins_result; using Cand = cl_ins_candidate; using Rule = cl_ins_params;
+    static constexpr auto kMinCount = &Rule::min_ins_count, kMinPer10k = &Rule::min_ins_per_10k;
+    static constexpr auto kCalled = &Result::n_inserted;
+    static constexpr auto kHostCand = &SiteResident::ins_cand;
+    static constexpr auto kDevCand = &SiteResident::si_cand;
+    static constexpr const char *kWho = "cl_site_scan_ins", *kLap = "insertion scan: reference in, kernel, candidates back";
+    static constexpr const char *kNoCount = "min_ins_count must be at least 1", *kPer10kRange = "min_ins_per_10k must lie in 1..10000";
+};
+
+// the first parameter of a count rule that is refused, under the names N: p is any of the records that hold one
+// (cl_del_params, cl_ins_params; cl_cons_params, whose rule is the deletion mode's)
+template <class N, class P>
+static const char *scan_count_fault(const P *p, uint32_t P::*min_count, uint32_t P::*min_per_10k)
+{
+    return !p ? "null params" : p->min_depth == 0 ? ScanModeHostBase::kNoDepth : p->*min_count == 0 ? N::kNoCount
+         : (p->*min_per_10k < 1 || p->*min_per_10k > 10000) ? N::kPer10kRange : nullptr;
+}
+
+template <bool FILTERED, ScanMode MODE> struct ScanCountHost : ScanModeHostBase, ScanCountNames<MODE> {
+    using N = ScanCountNames<MODE>;
+    using Params = const typename N::Rule *;
+    static auto &host_cand(SiteResident &S) { return S.*N::kHostCand; }
+    static auto &dev_cand(SiteResident &S) { return S.*N::kDevCand; }
+    static const char *fault(Params p) { return scan_count_fault<N>(p, N::kMinCount, N::kMinPer10k); }
     static uint32_t min_depth(Params p) { return p->min_depth; }
-    static void fill(ScanModeArgs<FILTERED, SCAN_DELS> &A, Params p) { A.t.min_count = p->min_del_count; A.t.min_per_10k = p->min_del_per_10k; }
-    static void classes(Result &out, const unsigned long long (&h)[8]) { out.n_low_depth = h[DEL_LOW_DEPTH]; out.n_kept = h[DEL_KEPT]; out.n_deleted = h[DEL_DELETED]; }
+    static void fill(ScanModeArgs<FILTERED, MODE> &A, Params p) { A.t.min_count = p->*N::kMinCount; A.t.min_per_10k = p->*N::kMinPer10k; }
+    static void classes(typename N::Result &out, const unsigned long long (&h)[8]) { out.n_low_depth = h[COUNT_LOW_DEPTH]; out.n_kept = h[COUNT_KEPT]; out.*N::kCalled = h[COUNT_CALLED]; }
     // the tile without its bases: records, ends, CIGAR words; under a filter the flags and the pass bits
     static uint64_t tile_bytes(const SiteResident &S) { return S.n * (sizeof(SiteRec) + 4) + S.ncig * 4 + (FILTERED ? (S.nbase + 7) / 8 + S.n * 2 : 0); }
 };
+template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_DELS> : ScanCountHost<FILTERED, SCAN_DELS> {};
 
-// the insertion mode: reads with a counting I operation anchored at a position, beside the scan's depth; behind the
-// candidates a second launch over them alone fetches what was inserted (site_scan.hip.h)
-template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_INS> : ScanModeHostBase {
+// behind the insertion mode's candidates a second launch over them alone fetches what was inserted (site_scan.hip.h)
+template <bool FILTERED> struct ScanModeHost<FILTERED, SCAN_INS> : ScanCountHost<FILTERED, SCAN_INS> {
     using Result = cl_ins_result;
     using Cand = cl_ins_candidate;
-    using Params = const cl_ins_params *;
-    static constexpr const char *kWho = "cl_site_scan_ins", *kLap = "insertion scan: reference in, kernel, candidates back";
-    static std::vector<Cand> &host_cand(SiteResident &S) { return S.ins_cand; }
-    static DevBuf<ScanInsCand> &dev_cand(SiteResident &S) { return S.si_cand; }
-    static const char *fault(Params p)
-    {
-        return !p ? "null params" : p->min_depth == 0 ? kNoDepth : p->min_ins_count == 0 ? "min_ins_count must be at least 1"
-             : (p->min_ins_per_10k < 1 || p->min_ins_per_10k > 10000) ? "min_ins_per_10k must lie in 1..10000" : nullptr;
-    }
-    static uint32_t min_depth(Params p) { return p->min_depth; }
-    static void fill(ScanModeArgs<FILTERED, SCAN_INS> &A, Params p) { A.t.min_count = p->min_ins_count; A.t.min_per_10k = p->min_ins_per_10k; }
-    static void classes(Result &out, const unsigned long long (&h)[8]) { out.n_low_depth = h[INS_LOW_DEPTH]; out.n_kept = h[INS_KEPT]; out.n_inserted = h[INS_INSERTED]; }
-    // the window scan reads what the deletion mode does
-    static uint64_t tile_bytes(const SiteResident &S) { return ScanModeHost<FILTERED, SCAN_DELS>::tile_bytes(S); }
     // The observations: the candidates' positions with the exclusive prefix sum of their ins go to the device, one
     // workgroup per candidate stores its insertions into its own slots of a buffer of exactly sum(ins) entries and says
     // how many it found.  t_scan and its bytes become those of both launches.
@@ -766,6 +792,19 @@ static cl_status site_scan_reference(SiteCtx *c, const uint8_t *ref_bases, uint6
     return CL_OK;
 }
 
+// one launch of k_site_scan over n_blocks windows between the events of t_scan, behind cleared class counters (if it has any)
+template <bool FILTERED, ScanMode MODE>
+static cl_status site_scan_launch(SiteCtx *c, const ScanModeArgs<FILTERED, MODE> &A, uint32_t n_blocks)
+{
+    KernelTimer &T = c->site.t_scan;
+    if (A.s.cls) HIP_TRY(c, hipMemsetAsync(A.s.cls, 0, 8 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, T.start(c->stream));
+    hipLaunchKernelGGL((k_site_scan<FILTERED, MODE>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, T.stop(c->stream));
+    return CL_OK;
+}
+
 // A scan that compacts candidates, of any mode and form: the checks, the index, the reference bytes of the range, the
 // kernel until the candidates fit, the candidates back and in ascending position, the mode's post step.
 template <bool FILTERED, ScanMode MODE>
@@ -801,16 +840,12 @@ static cl_status site_scan_run(SiteCtx *c, uint8_t min_quality, typename ScanHos
     ScanModeArgs<FILTERED, MODE> A;
     for (;;) {
         HIP_TRY(c, d_cand.reserve(cap));
-        HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
         // (the record is filled once the index and every buffer stand)
         site_scan_fill<FILTERED>(c, A, filter, min_quality, M::min_depth(prm), start, end);
         M::fill(A, prm);
         A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.s.n_cand = reinterpret_cast<uint32_t *>(S.sc_cls.p + SCAN_CLASSES);
         A.cand = d_cand.p; A.s.cand_cap = (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull);
-        HIP_TRY(c, S.t_scan.start(c->stream));
-        hipLaunchKernelGGL((k_site_scan<FILTERED, MODE>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, S.t_scan.stop(c->stream));
+        if ((s = site_scan_launch(c, A, n_blocks)) != CL_OK) return s;
         HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, S.t_scan.read(true));                         // (a scan that ran again: the launches' sum)
@@ -850,8 +885,8 @@ static cl_status site_scan_consensus_run(SiteCtx *c, uint8_t min_quality, typena
     if (!c) return CL_ERR_INVALID;
     if (!out) return fail(c, CL_ERR_INVALID, std::string(kWho) + ": null result");
     // (the deletion rule's parameters, refused as cl_site_scan_dels refuses them)
-    const cl_del_params dp = prm ? cl_del_params{prm->min_depth, prm->min_del_count, prm->min_del_per_10k} : cl_del_params{};
-    cl_status s = site_scan_enter<FILTERED>(c, kWho, filter, ScanModeHost<FILTERED, SCAN_DELS>::fault(prm ? &dp : nullptr), ref_bases, ref_len, start, end);
+    const char *fault = scan_count_fault<ScanCountNames<SCAN_DELS>>(prm, &cl_cons_params::min_del_count, &cl_cons_params::min_del_per_10k);
+    cl_status s = site_scan_enter<FILTERED>(c, kWho, filter, fault, ref_bases, ref_len, start, end);
     if (s != CL_OK) return s;
     SiteResident &S = c->site;
     memset(out, 0, sizeof(*out));
@@ -867,15 +902,11 @@ static cl_status site_scan_consensus_run(SiteCtx *c, uint8_t min_quality, typena
     if ((s = site_scan_reference(c, ref_bases, ref_len, start, end, n_ref)) != CL_OK) return s;
     const uint32_t win0 = start / kScanWin, n_blocks = (end - 1) / kScanWin - win0 + 1;
     HIP_TRY(c, S.sk_cons.reserve((size_t)n_blocks * kBlock));
-    HIP_TRY(c, hipMemsetAsync(S.sc_cls.p, 0, 8 * sizeof(unsigned long long), c->stream));
     ScanModeArgs<FILTERED, SCAN_CONS> A;
     site_scan_fill<FILTERED>(c, A, filter, min_quality, prm->min_depth, start, end);
     A.t.min_count = prm->min_del_count; A.t.min_per_10k = prm->min_del_per_10k;
     A.s.refb = S.sc_ref.p; A.s.cls = S.sc_cls.p; A.cand = S.sk_cons.p;
-    HIP_TRY(c, S.t_scan.start(c->stream));
-    hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_CONS>), dim3(n_blocks), dim3(kBlock), 0, c->stream, A);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, S.t_scan.stop(c->stream));
+    if ((s = site_scan_launch(c, A, n_blocks)) != CL_OK) return s;
     unsigned long long h_cls[8];
     HIP_TRY(c, hipMemcpyAsync(h_cls, S.sc_cls.p, sizeof(h_cls), hipMemcpyDeviceToHost, c->stream));
     // the range's bytes: the buffer's byte 0 is position win0 * kScanWin
@@ -911,10 +942,7 @@ static cl_status site_scan_counts_impl(SiteCtx *c, uint8_t min_quality, typename
     ScanModeArgs<FILTERED, SCAN_DENSE> A;
     site_scan_fill<FILTERED>(c, A, filter, min_quality, 1, start, end);
     A.s.dense = S.sc_dense.p;
-    HIP_TRY(c, S.t_scan.start(c->stream));
-    hipLaunchKernelGGL((k_site_scan<FILTERED, SCAN_DENSE>), dim3((end - 1) / kScanWin - start / kScanWin + 1), dim3(kBlock), 0, c->stream, A);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, S.t_scan.stop(c->stream));
+    if ((s = site_scan_launch(c, A, (end - 1) / kScanWin - start / kScanWin + 1)) != CL_OK) return s;
     HIP_TRY(c, hipMemcpyAsync(counts, S.sc_dense.p, n_dense * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, S.t_scan.read());

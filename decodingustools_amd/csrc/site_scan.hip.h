@@ -11,7 +11,7 @@
 // 1-based site p + 1): read start < contig_len, mapq >= min_quality, bases of M/=/X operations, query index < l_seq,
 // p < ref_len.  The unfiltered form has no flag or base-quality filter.
 //
-// Three kernels:
+// The kernels:
 //   k_site_scan_index   once per resident tile: the reference end of every read and, per window, the index range
 //                       [first, last) of the reads that overlap it (atomicMin / atomicMax of the read's index over
 //                       the windows of its span).  The range holds every overlapping read whatever the order of the
@@ -22,9 +22,11 @@
 //                       per base, consecutive positions in consecutive banks).  What happens to the finished planes is
 //                       the MODE: the counters themselves go out (SCAN_DENSE), or every thread judges positions and the
 //                       candidates are compacted with one ballot and one atomic per wave -- by the calling rule
-//                       (SCAN_CALLS), the second-allele rule (SCAN_MINOR), the deletion rule (SCAN_DELS) or the insertion
-//                       rule (SCAN_INS) -- or every position gets one byte of the called sequence and nothing is
-//                       compacted (SCAN_CONS).
+//                       (SCAN_CALLS), the second-allele rule (SCAN_MINOR) or the count rule of a deletion (SCAN_DELS) or
+//                       an insertion (SCAN_INS), one judge for both -- or every position gets one byte of the called
+//                       sequence and nothing is compacted (SCAN_CONS).  The planes that SCAN_DELS, SCAN_INS and SCAN_CONS
+//                       build from range ends (scan_run_ends; kScanEnds / kScanEnds0 say which) become counts in one
+//                       place, scan_window_counts, the head of those three modes' tails.
 //   k_site_scan_settle  filtered form only: the 16-code histogram of the few positions the planes cannot classify.
 //   k_site_scan_ins_alleles<FILTERED>
 //                       behind SCAN_INS: what was inserted at the called positions, one workgroup per position.
@@ -118,23 +120,15 @@ struct ScanMinorCand {
 };
 enum { MINOR_LOW_DEPTH = 0, MINOR_SINGLE = 1, MINOR_MINOR = 2 };             // its classes, in the first slots of cls
 
-// one compacted position of the deletion mode; the strand counts are 0 in the unfiltered form
-struct ScanDelCand {
+// one compacted position of the deletion or the insertion mode (there pos is the anchor), laid out as cl_del_candidate
+// and cl_ins_candidate: n is the del or the ins count; the strand counts are 0 in the unfiltered form
+struct ScanCountCand {
     uint32_t pos;                            // 1-based
     uint8_t  ref, pad[3];
-    uint32_t del, depth;                     // both strands
-    uint32_t del_fwd, del_rev, depth_fwd, depth_rev;
+    uint32_t n, depth;                       // both strands
+    uint32_t n_fwd, n_rev, depth_fwd, depth_rev;
 };
-enum { DEL_LOW_DEPTH = 0, DEL_KEPT = 1, DEL_DELETED = 2 };                   // its classes, in the first slots of cls
-
-// one compacted position of the insertion mode (pos: the anchor); the strand counts are 0 in the unfiltered form
-struct ScanInsCand {
-    uint32_t pos;                            // 1-based
-    uint8_t  ref, pad[3];
-    uint32_t ins, depth;                     // both strands
-    uint32_t ins_fwd, ins_rev, depth_fwd, depth_rev;
-};
-enum { INS_LOW_DEPTH = 0, INS_KEPT = 1, INS_INSERTED = 2 };                  // its classes, in the first slots of cls
+enum { COUNT_LOW_DEPTH = 0, COUNT_KEPT = 1, COUNT_CALLED = 2 };              // the two modes' classes (called: deleted, inserted), in the first slots of cls
 
 // k_site_scan_ins_alleles: a called position as the host sends it (the candidates in ascending position; off = the
 // exclusive prefix sum of their ins) and one counting insertion there as the device answers
@@ -215,16 +209,13 @@ template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_MINOR> {
     using Thresholds = ScanThresholds;
     static __device__ __forceinline__ bool emits(int cls) { return cls == MINOR_MINOR; }
 };
-template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_DELS> {
-    using Cand = ScanDelCand;
+struct ScanCountTraits {                                                      // the deletion and the insertion mode
+    using Cand = ScanCountCand;
     using Thresholds = ScanThresholds;
-    static __device__ __forceinline__ bool emits(int cls) { return cls == DEL_DELETED; }
+    static __device__ __forceinline__ bool emits(int cls) { return cls == COUNT_CALLED; }
 };
-template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_INS> {
-    using Cand = ScanInsCand;
-    using Thresholds = ScanThresholds;
-    static __device__ __forceinline__ bool emits(int cls) { return cls == INS_INSERTED; }
-};
+template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_DELS> : ScanCountTraits {};
+template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_INS> : ScanCountTraits {};
 // the consensus mode compacts nothing: its "candidates" are the packed bytes, one word per four positions
 template <bool FILTERED> struct ScanModeTraits<FILTERED, SCAN_CONS> {
     using Cand = uint32_t;
@@ -243,11 +234,13 @@ template <ScanMode MODE> inline constexpr bool kScanTwoCounts = MODE == SCAN_DEL
 constexpr uint32_t kConsPlanes = 6u, kConsRest = 4u, kConsDel = 5u;
 template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanPlanes = MODE == SCAN_CONS ? kConsPlanes
                                                                               : kScanTwoCounts<MODE> ? 2u * ScanForm<FILTERED>::kStrands : ScanForm<FILTERED>::kPlanes;
-// ... of which the last kScanEnds hold range ends that one workgroup-wide scan each turns into counts: both unfiltered
-// planes and the del planes under a filter in the deletion mode; the unfiltered depth plane, the first, in the insertion
-// mode; the del plane, the last, in the consensus mode
+// ... of which the kScanEnds planes from kScanEnds0 on hold range ends that scan_window_counts turns into counts: both
+// unfiltered planes and the del planes under a filter, always the last two, in the deletion mode; the unfiltered depth
+// plane, the first, in the insertion mode; the del plane, the last, in the consensus mode
 template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds = MODE == SCAN_DELS ? 2u : ((MODE == SCAN_INS && !FILTERED) || MODE == SCAN_CONS) ? 1u : 0u;
 template <bool FILTERED, ScanMode MODE> inline constexpr uint32_t kScanEnds0 = MODE == SCAN_DELS ? kScanPlanes<FILTERED, MODE> - 2u : MODE == SCAN_CONS ? kConsDel : 0u;
+// the modes whose tail is scan_window_counts: their planes are read four words at a time
+template <ScanMode MODE> inline constexpr bool kScanQuads = kScanTwoCounts<MODE> || MODE == SCAN_CONS;
 
 // number of CIGAR operations and bases of a read, with SiteRec's escape to the next record's offsets
 __device__ __forceinline__ void scan_read_extent(const SiteRec *rec, uint32_t r, const uint4 &rr, uint32_t &k1, unsigned long long &slen)
@@ -385,6 +378,32 @@ __device__ __forceinline__ bool scan_base_passes(const ScanFilter &f, unsigned l
     return (pw >> (bi & 63ull)) & 1ull;
 }
 
+// the pass bit of a single base b, loaded for it alone: a D operation's carrier, an I operation's anchor
+__device__ __forceinline__ bool scan_pass_bit(const ScanFilter &f, unsigned long long b)
+{
+    return !f.use_bq || ((f.pass[b >> 6] >> (b & 63ull)) & 1ull);
+}
+
+// the unfiltered form of the three: nothing is kept from base to base and every base passes
+__device__ __forceinline__ ScanNoFilter scan_pass_word(const ScanNoFilter &, unsigned long long, bool) { return {}; }
+__device__ __forceinline__ bool scan_base_passes(const ScanNoFilter &, unsigned long long, ScanNoFilter &) { return true; }
+__device__ __forceinline__ bool scan_pass_bit(const ScanNoFilter &, unsigned long long) { return true; }
+
+// the begin_run of scan_walk_read for a form's filter
+template <class Filter>
+__device__ __forceinline__ auto scan_begin_run(const Filter &f)
+{
+    return [&f](unsigned long long bi, bool any) { return scan_pass_word(f, bi, any); };
+}
+
+// A run of counted positions [o0, o1) of the window in a plane of range ends: +1 at its first position, -1 behind its last
+// (uint32 wrap-around; a -1 that would fall on index kScanWin is dropped).  scan_window_counts turns the ends into counts.
+__device__ __forceinline__ void scan_run_ends(uint32_t *plane, uint32_t o0, uint32_t o1)
+{
+    atomicAdd(&plane[o0], 1u);
+    if (o1 < kScanWin) atomicAdd(&plane[o1], 0xFFFFFFFFu);
+}
+
 // The calling rule.  Returns the class; rb becomes the upper-cased reference byte (anything but ACGT is "other"),
 // alt the most frequent of A C G T N (the first in that order among equals) and ai its index in that order.
 __device__ __forceinline__ int scan_classify(uint32_t A, uint32_t Cc, uint32_t G, uint32_t T, uint32_t N, uint32_t O, uint32_t &rb, uint32_t min_depth,
@@ -475,7 +494,7 @@ __device__ __forceinline__ int scan_classify_cons(uint32_t A, uint32_t Cc, uint3
     return CONS_NO_CALL;
 }
 
-// The tail of the two rule modes (the calling rule keeps its own, in the kernel).  A thread has kScanWin / kBlock
+// The tail of the second-allele rule and of the count rule (the calling rule keeps its own, in the kernel).  A thread has kScanWin / kBlock
 // positions: offset(j) is the window offset o of its j-th, judge(j, o, ref, cd) returns the class of position ws + o and
 // fills cd but for its pos, ref() being the reference byte as sent ('N' at and beyond hi).  The emitted class is compacted.
 template <bool FILTERED, ScanMode MODE, class Offset, class Judge>
@@ -498,13 +517,51 @@ __device__ __forceinline__ void scan_judge_positions(const ScanModeArgs<FILTERED
     scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), ax.s.cls, tid, lane);     // (s_cnt: every judge has read it)
 }
 
+// The finished planes of a window into registers, four consecutive positions per thread: q[k][j] = plane k at window offset
+// 4 tid + j.  The planes of range ends (kScanEnds of them from kScanEnds0 on, scan_run_ends) become counts on the way, by one
+// inclusive scan over the window each: within the thread, over the wave by DPP, over the workgroup through the waves'
+// totals, behind one barrier for all of them.  Sums are modulo 2^32, so a -1 may stand in front of its +1's total.
+template <bool FILTERED, ScanMode MODE>
+__device__ __forceinline__ void scan_window_counts(const uint32_t *s_cnt, uint32_t (&q)[kScanPlanes<FILTERED, MODE>][4])
+{
+    static_assert(kScanWin == 4u * (uint32_t)kBlock, "four positions per thread");
+    constexpr uint32_t kE0 = kScanEnds0<FILTERED, MODE>, kEnds = kScanEnds<FILTERED, MODE>;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+#pragma unroll
+    for (uint32_t k = 0; k < kScanPlanes<FILTERED, MODE>; ++k) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(&s_cnt[k * kScanWin + 4u * tid]);
+        q[k][0] = v.x; q[k][1] = v.y; q[k][2] = v.z; q[k][3] = v.w;
+    }
+    if constexpr (kEnds > 0u) {
+        __shared__ uint32_t s_wtot[kEnds][kBlock / 64];
+        uint32_t before[kEnds];                                                // the sum of the wave's earlier threads
+#pragma unroll
+        for (uint32_t e = 0; e < kEnds; ++e) {
+            uint32_t (&v)[4] = q[kE0 + e];
+            v[1] += v[0]; v[2] += v[1]; v[3] += v[2];
+            const uint32_t inc = dpp_incl_scan_u32(v[3]);
+            if (lane == 63u) s_wtot[e][wv] = inc;
+            before[e] = inc - v[3];
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t e = 0; e < kEnds; ++e) {
+            uint32_t add = before[e];
+#pragma unroll
+            for (uint32_t j = 0; j < (uint32_t)kBlock / 64u; ++j) add += j < wv ? s_wtot[e][j] : 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; ++j) q[kE0 + e][j] += add;
+        }
+    }
+}
+
 template <bool FILTERED, ScanMode MODE>
 __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MODE> ax)
 {
     using Form = ScanForm<FILTERED>;
     constexpr uint32_t S = Form::kStrands;
     constexpr uint32_t kPlanes = kScanPlanes<FILTERED, MODE>;
-    __shared__ alignas(kScanTwoCounts<MODE> || MODE == SCAN_CONS ? 16 : 8) uint32_t s_cnt[kPlanes * kScanWin];   // (the deletion, insertion and consensus modes read it four words at a time)
+    __shared__ alignas(kScanQuads<MODE> ? 16 : 8) uint32_t s_cnt[kPlanes * kScanWin];
     const ScanArgs &a = ax.s;
     const uint32_t tid = threadIdx.x;
     const uint32_t w = a.win0 + blockIdx.x;
@@ -523,71 +580,29 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
                 if (fl & ax.f.exclude_flags) continue;
                 rev = (fl >> 4) & 1u;
             }
-            if constexpr (MODE == SCAN_CONS) {
-                // planes: A C G T rest, one add per base; del from range ends, as in the deletion mode, under its carrier gate
-                scan_walk_read(a, r, rr, lo, hi,
-                    [&](unsigned long long bi, bool any) {
-                        if constexpr (FILTERED) return scan_pass_word(ax.f, bi, any); else return ScanNoFilter{};
-                    },
-                    [&](uint32_t p, unsigned long long bi, auto &pw) {
-                        if constexpr (FILTERED) { if (!scan_base_passes(ax.f, bi, pw)) return; }
-                        const uint32_t code = scan_base_code(a.seq4, bi);
-                        const uint32_t plane = code == 1u ? 0u : code == 2u ? 1u : code == 4u ? 2u : code == 8u ? 3u : kConsRest;
-                        atomicAdd(&s_cnt[plane * kScanWin + (p - ws)], 1u);
-                    },
-                    ScanNoHook{},
-                    [&](uint32_t p0, uint32_t p1, unsigned long long ci) {
-                        if constexpr (FILTERED) { if (ax.f.use_bq && !((ax.f.pass[ci >> 6] >> (ci & 63ull)) & 1ull)) return; }
-                        atomicAdd(&s_cnt[kConsDel * kScanWin + (p0 - ws)], 1u);
-                        if (p1 - ws < kScanWin) atomicAdd(&s_cnt[kConsDel * kScanWin + (p1 - ws)], 0xFFFFFFFFu);
-                    });
-            } else if constexpr (kScanTwoCounts<MODE>) {
-                // planes: depth by strand, then del (ins) by strand.  A run's ends: +1 at its first position, -1 behind its last
-                auto run_ends = [&](uint32_t plane, uint32_t p0, uint32_t p1) {
-                    atomicAdd(&s_cnt[plane * kScanWin + (p0 - ws)], 1u);
-                    if (p1 - ws < kScanWin) atomicAdd(&s_cnt[plane * kScanWin + (p1 - ws)], 0xFFFFFFFFu);
-                };
-                if constexpr (MODE == SCAN_INS && FILTERED) {
-                    scan_walk_read(a, r, rr, lo, hi,
-                        [&](unsigned long long bi, bool any) { return scan_pass_word(ax.f, bi, any); },
-                        [&](uint32_t p, unsigned long long bi, unsigned long long &pw) {
-                            if (scan_base_passes(ax.f, bi, pw)) atomicAdd(&s_cnt[rev * kScanWin + (p - ws)], 1u);
-                        },
-                        ScanNoHook{}, ScanNoHook{},
-                        [&](uint32_t p, unsigned long long ai, unsigned long long, uint32_t) {
-                            if (ax.f.use_bq && !((ax.f.pass[ai >> 6] >> (ai & 63ull)) & 1ull)) return;
-                            atomicAdd(&s_cnt[(S + rev) * kScanWin + (p - ws)], 1u);
-                        });
-                } else if constexpr (MODE == SCAN_INS) {
-                    scan_walk_read(a, r, rr, lo, hi, ScanNoHook{}, ScanNoHook{},
-                        [&](uint32_t p0, uint32_t p1) { run_ends(0u, p0, p1); }, ScanNoHook{},
-                        [&](uint32_t p, unsigned long long, unsigned long long, uint32_t) { atomicAdd(&s_cnt[kScanWin + (p - ws)], 1u); });
-                } else if constexpr (FILTERED) {
-                    scan_walk_read(a, r, rr, lo, hi,
-                        [&](unsigned long long bi, bool any) { return scan_pass_word(ax.f, bi, any); },
-                        [&](uint32_t p, unsigned long long bi, unsigned long long &pw) {
-                            if (scan_base_passes(ax.f, bi, pw)) atomicAdd(&s_cnt[rev * kScanWin + (p - ws)], 1u);
-                        },
-                        ScanNoHook{},
-                        [&](uint32_t p0, uint32_t p1, unsigned long long ci) {
-                            if (ax.f.use_bq && !((ax.f.pass[ci >> 6] >> (ci & 63ull)) & 1ull)) return;
-                            run_ends(S + rev, p0, p1);
-                        });
-                } else {
-                    scan_walk_read(a, r, rr, lo, hi, ScanNoHook{}, ScanNoHook{},
-                        [&](uint32_t p0, uint32_t p1) { run_ends(0u, p0, p1); },
-                        [&](uint32_t p0, uint32_t p1, unsigned long long) { run_ends(1u, p0, p1); });
-                }
-            } else {
-                scan_walk_read(a, r, rr, lo, hi,
-                    [&](unsigned long long bi, bool any) {
-                        if constexpr (FILTERED) return scan_pass_word(ax.f, bi, any); else return ScanNoFilter{};
-                    },
-                    [&](uint32_t p, unsigned long long bi, auto &pw) {
-                        if constexpr (FILTERED) { if (!scan_base_passes(ax.f, bi, pw)) return; }
-                        atomicAdd(&s_cnt[Form::plane(scan_base_code(a.seq4, bi), rev) * kScanWin + (p - ws)], 1u);
-                    });
-            }
+            // The hooks the modes hang on the walk.  Planes: the form's base planes (calling modes), A C G T rest del (consensus),
+            // depth by strand then del or ins by strand (deletion, insertion); second = the plane of this read's del or ins.
+            constexpr bool kDepthFromEnds = kScanTwoCounts<MODE> && !FILTERED;   // without a filter an M run is one run of the depth plane
+            const uint32_t second = MODE == SCAN_CONS ? kConsDel : S + rev;
+            auto add = [&](uint32_t plane, uint32_t p) { atomicAdd(&s_cnt[plane * kScanWin + (p - ws)], 1u); };
+            auto ends = [&](uint32_t plane, uint32_t p0, uint32_t p1) { scan_run_ends(&s_cnt[plane * kScanWin], p0 - ws, p1 - ws); };
+            const auto begin_run = scan_begin_run(ax.f);
+            auto base_by_code = [&](uint32_t p, unsigned long long bi, auto &pw) {
+                if (!scan_base_passes(ax.f, bi, pw)) return;
+                const uint32_t code = scan_base_code(a.seq4, bi);
+                if constexpr (MODE == SCAN_CONS) add(code == 1u ? 0u : code == 2u ? 1u : code == 4u ? 2u : code == 8u ? 3u : kConsRest, p);
+                else add(Form::plane(code, rev), p);
+            };
+            auto depth_by_base = [&](uint32_t p, unsigned long long bi, auto &pw) { if (scan_base_passes(ax.f, bi, pw)) add(rev, p); };
+            auto depth_by_run = [&](uint32_t p0, uint32_t p1) { ends(0u, p0, p1); };
+            auto del_run = [&](uint32_t p0, uint32_t p1, unsigned long long ci) { if (scan_pass_bit(ax.f, ci)) ends(second, p0, p1); };
+            auto ins_anchor = [&](uint32_t p, unsigned long long ai, unsigned long long, uint32_t) { if (scan_pass_bit(ax.f, ai)) add(second, p); };
+            if constexpr (MODE == SCAN_CONS) scan_walk_read(a, r, rr, lo, hi, begin_run, base_by_code, ScanNoHook{}, del_run);
+            else if constexpr (MODE == SCAN_DELS && kDepthFromEnds) scan_walk_read(a, r, rr, lo, hi, ScanNoHook{}, ScanNoHook{}, depth_by_run, del_run);
+            else if constexpr (MODE == SCAN_DELS) scan_walk_read(a, r, rr, lo, hi, begin_run, depth_by_base, ScanNoHook{}, del_run);
+            else if constexpr (MODE == SCAN_INS && kDepthFromEnds) scan_walk_read(a, r, rr, lo, hi, ScanNoHook{}, ScanNoHook{}, depth_by_run, ScanNoHook{}, ins_anchor);
+            else if constexpr (MODE == SCAN_INS) scan_walk_read(a, r, rr, lo, hi, begin_run, depth_by_base, ScanNoHook{}, ScanNoHook{}, ins_anchor);
+            else scan_walk_read(a, r, rr, lo, hi, begin_run, base_by_code);
         }
     }
     __syncthreads();
@@ -603,26 +618,12 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
             out[i] = v;
         }
     } else if constexpr (MODE == SCAN_CONS) {
-        // The deletion mode's tail: four consecutive positions per thread, all planes into registers, the del plane's range
-        // ends turned into counts by an inclusive scan (thread, wave by DPP, wave totals through LDS).  Then the rule per
-        // position and one aligned word of four bytes per thread: the buffer is indexed from the first window's start, so
-        // word blockIdx.x * kBlock + tid holds positions ws + 4 tid .. + 3 whatever the range's start is.
-        static_assert(kScanWin == 4u * (uint32_t)kBlock, "four positions per thread");
-        __shared__ uint32_t s_wtot[kBlock / 64];
-        const uint32_t lane = tid & 63u, wv = tid >> 6;
+        // The counts of the thread's four positions (scan_window_counts), the rule per position and one aligned word of four
+        // bytes per thread: the buffer is indexed from the first window's start, so word blockIdx.x * kBlock + tid holds
+        // positions ws + 4 tid .. + 3 whatever the range's start is.
         uint32_t q[kPlanes][4];
-#pragma unroll
-        for (uint32_t k = 0; k < kPlanes; ++k) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(&s_cnt[k * kScanWin + 4u * tid]);
-            q[k][0] = v.x; q[k][1] = v.y; q[k][2] = v.z; q[k][3] = v.w;
-        }
-        q[kConsDel][1] += q[kConsDel][0]; q[kConsDel][2] += q[kConsDel][1]; q[kConsDel][3] += q[kConsDel][2];
-        const uint32_t inc = dpp_incl_scan_u32(q[kConsDel][3]);
-        if (lane == 63u) s_wtot[wv] = inc;
-        __syncthreads();
-        uint32_t add = inc - q[kConsDel][3];
-#pragma unroll
-        for (uint32_t j = 0; j < (uint32_t)kBlock / 64u; ++j) add += j < wv ? s_wtot[j] : 0u;
+        scan_window_counts<FILTERED, MODE>(s_cnt, q);
+        const uint32_t lane = tid & 63u;
         uint32_t mine[SCAN_CLASSES] = {0, 0, 0, 0, 0, 0};
         uint32_t word = 0;
 #pragma unroll
@@ -631,7 +632,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
             uint32_t byte = kConsPad;
             if (p >= lo && p < we) {
                 const uint32_t rb = p < hi ? a.refb[p - a.start] : (uint32_t)'N';
-                const int cls = scan_classify_cons(q[0][j], q[1][j], q[2][j], q[3][j], q[kConsRest][j], q[kConsDel][j] + add, rb, a.min_depth,
+                const int cls = scan_classify_cons(q[0][j], q[1][j], q[2][j], q[3][j], q[kConsRest][j], q[kConsDel][j], rb, a.min_depth,
                                                    ax.t.min_count, ax.t.min_per_10k, byte);
                 mine[cls] += 1u;
             }
@@ -640,56 +641,20 @@ __global__ __launch_bounds__(kBlock) void k_site_scan(ScanModeArgs<FILTERED, MOD
         ax.cand[(size_t)blockIdx.x * kBlock + tid] = word;
         scan_reduce_classes(mine, reinterpret_cast<unsigned long long *>(s_cnt), a.cls, tid, lane);     // (s_cnt: every thread has read it)
     } else if constexpr (kScanTwoCounts<MODE>) {
-        // Four consecutive positions per thread, all planes into registers.  The planes of range ends (deletion mode: both
-        // unfiltered, the del planes under a filter: always the last two; insertion mode: the unfiltered depth plane)
-        // become counts by an inclusive scan over the window: within the thread, over the wave by DPP, over the workgroup
-        // through the waves' totals.
-        static_assert(kScanWin == 4u * (uint32_t)kBlock, "four positions per thread");
-        constexpr uint32_t kE0 = kScanEnds0<FILTERED, MODE>, kE1 = kE0 + kScanEnds<FILTERED, MODE>;
-        __shared__ uint32_t s_wtot[2][kBlock / 64];
-        const uint32_t lane = tid & 63u, wv = tid >> 6;
+        // The count rule of both modes over the thread's four positions (scan_window_counts): n, the del or ins count, against
+        // the rule's denominator -- span = depth + del for a deletion, which takes its reads out of the depth; the depth for
+        // an insertion, whose reads are in it.  low_depth below min_depth of it, called at min_count and min_per_10k of it.
         uint32_t q[kPlanes][4];
-#pragma unroll
-        for (uint32_t k = 0; k < kPlanes; ++k) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(&s_cnt[k * kScanWin + 4u * tid]);
-            q[k][0] = v.x; q[k][1] = v.y; q[k][2] = v.z; q[k][3] = v.w;
-        }
-        uint32_t before[2];                                                    // the sum of the wave's earlier threads
-#pragma unroll
-        for (uint32_t k = kE0; k < kE1; ++k) {
-            q[k][1] += q[k][0]; q[k][2] += q[k][1]; q[k][3] += q[k][2];
-            const uint32_t inc = dpp_incl_scan_u32(q[k][3]);
-            if (lane == 63u) s_wtot[k - kE0][wv] = inc;
-            before[k - kE0] = inc - q[k][3];
-        }
-        if constexpr (kE1 > kE0) __syncthreads();
-#pragma unroll
-        for (uint32_t k = kE0; k < kE1; ++k) {
-            uint32_t add = before[k - kE0];
-#pragma unroll
-            for (uint32_t j = 0; j < (uint32_t)kBlock / 64u; ++j) add += j < wv ? s_wtot[k - kE0][j] : 0u;
-#pragma unroll
-            for (uint32_t j = 0; j < 4u; ++j) q[k][j] += add;
-        }
-        if constexpr (MODE == SCAN_INS) scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return 4u * tid + j; }, [&](uint32_t j, uint32_t, auto &&ref, ScanInsCand &cd) {
-            const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, ins_f = q[S][j], ins_r = FILTERED ? q[2u * S - 1u][j] : 0u;
-            const unsigned long long depth = (unsigned long long)depth_f + depth_r, ins = (unsigned long long)ins_f + ins_r;
-            const int cls = depth < a.min_depth ? INS_LOW_DEPTH
-                          : (ins >= ax.t.min_count && 10000ull * ins >= (unsigned long long)ax.t.min_per_10k * depth) ? INS_INSERTED : INS_KEPT;
-            cd.ref = (uint8_t)(ref() & ~32u); cd.pad[0] = cd.pad[1] = cd.pad[2] = 0;
-            cd.ins = (uint32_t)ins; cd.depth = (uint32_t)depth;
-            cd.ins_fwd = FILTERED ? ins_f : 0u; cd.ins_rev = ins_r; cd.depth_fwd = FILTERED ? depth_f : 0u; cd.depth_rev = depth_r;
-            return cls;
-        });
-        else scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return 4u * tid + j; }, [&](uint32_t j, uint32_t, auto &&ref, ScanDelCand &cd) {
+        scan_window_counts<FILTERED, MODE>(s_cnt, q);
+        scan_judge_positions(ax, win, s_cnt, [&](uint32_t j) { return 4u * tid + j; }, [&](uint32_t j, uint32_t, auto &&ref, ScanCountCand &cd) {
             // (j is a constant of the unrolled loop: q stays in registers)
-            const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, del_f = q[S][j], del_r = FILTERED ? q[2u * S - 1u][j] : 0u;
-            const unsigned long long depth = (unsigned long long)depth_f + depth_r, del = (unsigned long long)del_f + del_r, span = depth + del;
-            const int cls = span < a.min_depth ? DEL_LOW_DEPTH
-                          : (del >= ax.t.min_count && 10000ull * del >= (unsigned long long)ax.t.min_per_10k * span) ? DEL_DELETED : DEL_KEPT;
+            const uint32_t depth_f = q[0][j], depth_r = FILTERED ? q[S - 1u][j] : 0u, n_f = q[S][j], n_r = FILTERED ? q[2u * S - 1u][j] : 0u;
+            const unsigned long long depth = (unsigned long long)depth_f + depth_r, n = (unsigned long long)n_f + n_r, of = MODE == SCAN_DELS ? depth + n : depth;
+            const int cls = of < a.min_depth ? COUNT_LOW_DEPTH
+                          : (n >= ax.t.min_count && 10000ull * n >= (unsigned long long)ax.t.min_per_10k * of) ? COUNT_CALLED : COUNT_KEPT;
             cd.ref = (uint8_t)(ref() & ~32u); cd.pad[0] = cd.pad[1] = cd.pad[2] = 0;
-            cd.del = (uint32_t)del; cd.depth = (uint32_t)depth;
-            cd.del_fwd = FILTERED ? del_f : 0u; cd.del_rev = del_r; cd.depth_fwd = FILTERED ? depth_f : 0u; cd.depth_rev = depth_r;
+            cd.n = (uint32_t)n; cd.depth = (uint32_t)depth;
+            cd.n_fwd = FILTERED ? n_f : 0u; cd.n_rev = n_r; cd.depth_fwd = FILTERED ? depth_f : 0u; cd.depth_rev = depth_r;
             return cls;
         });
     } else if constexpr (MODE == SCAN_MINOR) {
@@ -770,8 +735,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan_settle(ScanModeArgs<true, 
             const uint4 rr = *reinterpret_cast<const uint4 *>(a.rec + r);
             if (!scan_read_counts(a, rr, a.end[r], p, p + 1u)) continue;       // (p < contig_len <= 2^32 - 1)
             if ((uint32_t)ax.f.flag[r] & ax.f.exclude_flags) continue;
-            scan_walk_read(a, r, rr, p, p + 1u,
-                [&](unsigned long long bi, bool any) { return scan_pass_word(ax.f, bi, any); },
+            scan_walk_read(a, r, rr, p, p + 1u, scan_begin_run(ax.f),
                 [&](uint32_t, unsigned long long bi, unsigned long long &pw) {
                     if (scan_base_passes(ax.f, bi, pw)) atomicAdd(&s_h[scan_base_code(a.seq4, bi)], 1u);
                 });
@@ -809,7 +773,7 @@ __global__ __launch_bounds__(kBlock) void k_site_scan_ins_alleles(ScanModeArgs<F
             }
             scan_walk_read(a, r, rr, p, p + 1u, ScanNoHook{}, ScanNoHook{}, ScanNoHook{}, ScanNoHook{},
                 [&](uint32_t, unsigned long long ai, unsigned long long bi, uint32_t len) {
-                    if constexpr (FILTERED) { if (ax.f.use_bq && !((ax.f.pass[ai >> 6] >> (ai & 63ull)) & 1ull)) return; }
+                    if (!scan_pass_bit(ax.f, ai)) return;
                     const uint32_t k = atomicAdd(&s_n, 1u);
                     if (k >= st.ins) return;
                     ScanInsObs o;
