@@ -94,6 +94,16 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     PinBuf<uint32_t> h_dr_out;
     KernelTimer t_dr_count, t_dr_write;   // count launch + scan, write launch (recorded while profiling is on)
     double dr_ms = 0.0;
+    // The device buffers of the context, listed once: f(buffer) for each one that cl_layout_info.device_bytes counts, which
+    // is all of them but d_prof and the site engine's (they never were).  cl_destroy and cl_contig_layout walk this list.
+    template <class F> void each_buffer(F &&f)
+    {
+        f(d_pos); f(d_mapq); f(d_qual); f(d_ref); f(d_end); f(d_rec); f(d_heads); f(d_refn); f(d_rows); f(d_win_off); f(d_wide_idx);
+        f(d_win); f(d_state); f(d_runs); f(d_first_state); f(d_last_state); f(d_win_wide); f(d_winpart); f(d_fin); f(d_errflag);
+        f(d_runtab); f(d_lut); f(d_lut8); f(d_summary); f(d_iv); f(d_dbg); f(d_dr_win); f(d_dr_off); f(d_dr_out);
+    }
+    // the counter planes of k_pileup_rows and the depth kernels by the deepest window's rows (4 per group): 8 planes count to 255
+    uint32_t counter_planes() const { return max_groups <= 63u ? 8u : max_groups <= 16383u ? 16u : 32u; }
 
     uint32_t n_reads = 0;
     uint64_t n_cigar = 0, n_qual = 0;
@@ -105,7 +115,7 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     // profiling
     bool profiling = false;
     static constexpr int kEvSets = 64;       // runs that can be in flight before events are read back
-    hipEvent_t ev[kEvSets][CL_K_COUNT + 1] = {};
+    hipEvent_t ev[kEvSets][3] = {};          // per run: before the pileup, after it, after the tail
     bool ev_made = false;
     int ev_pending = 0;
     double ms[CL_K_COUNT] = {};
@@ -159,8 +169,8 @@ void build_lut8(const std::vector<uint32_t> &lut, uint32_t min_depth_for_low_map
 cl_status ensure_events(cl_ctx *c)
 {
     if (c->ev_made) return CL_OK;
-    for (int s = 0; s < cl_ctx::kEvSets; ++s)
-        for (int i = 0; i <= CL_K_COUNT; ++i) HIP_TRY(c, hipEventCreate(&c->ev[s][i]));
+    for (auto &set : c->ev)
+        for (hipEvent_t &e : set) HIP_TRY(c, hipEventCreate(&e));
     c->ev_made = true;
     return CL_OK;
 }
@@ -168,16 +178,12 @@ cl_status ensure_events(cl_ctx *c)
 cl_status harvest_events(cl_ctx *c)
 {
     for (int s = 0; s < c->ev_pending; ++s) {
-        HIP_TRY(c, hipEventSynchronize(c->ev[s][CL_K_COUNT]));
-        // events 0,3,4: the per-read and per-window indexes are built on the host at upload (CL_K_PREP and CL_K_BOUNDS
-        // stay 0; ev[1], ev[2] are unused)
-        static const int from[CL_K_COUNT] = {-1, -1, 0, 3}, to[CL_K_COUNT] = {-1, -1, 3, 4};
-        for (int i = 0; i < CL_K_COUNT; ++i) {
-            if (from[i] < 0) continue;
-            float t = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&t, c->ev[s][from[i]], c->ev[s][to[i]]));
-            c->ms[i] += t;
-        }
+        HIP_TRY(c, hipEventSynchronize(c->ev[s][2]));
+        // (the per-read and per-window indexes are built on the host at upload: CL_K_PREP and CL_K_BOUNDS stay 0)
+        float pileup = 0.f, tail = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&pileup, c->ev[s][0], c->ev[s][1]));
+        HIP_TRY(c, hipEventElapsedTime(&tail, c->ev[s][1], c->ev[s][2]));
+        c->ms[CL_K_PILEUP] += pileup; c->ms[CL_K_RLE] += tail;
         c->n_runs += 1;
     }
     c->ev_pending = 0;
@@ -920,9 +926,8 @@ template <bool DEBUG> void launch_rows(cl_ctx *c, const RowsArgs &a)
 #define CL_LAUNCH(DEEP_, NP_) do { \
         if (c->heads4) hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, true>), dim3(grid), dim3(kRowsBlock), 0, c->stream, a); \
         else hipLaunchKernelGGL((k_pileup_rows<(int)kT, DEBUG, DEEP_, NP_, false>), dim3(grid), dim3(kRowsBlock), 0, c->stream, a); } while (0)
-    // the counter planes by the deepest window's rows (4 per group): 8 planes count to 255
-    if (c->max_groups <= 63u) { if (c->deep) CL_LAUNCH(true, 8); else CL_LAUNCH(false, 8); }
-    else if (c->max_groups <= 16383u) { if (c->deep) CL_LAUNCH(true, 16); else CL_LAUNCH(false, 16); }
+    if (c->counter_planes() == 8u) { if (c->deep) CL_LAUNCH(true, 8); else CL_LAUNCH(false, 8); }
+    else if (c->counter_planes() == 16u) { if (c->deep) CL_LAUNCH(true, 16); else CL_LAUNCH(false, 16); }
     else { if (c->deep) CL_LAUNCH(true, 32); else CL_LAUNCH(false, 32); }
 #undef CL_LAUNCH
 }
@@ -949,10 +954,10 @@ cl_status enqueue(cl_ctx *c, bool debug, uint32_t *dbg_raw, uint32_t *dbg_qc, ui
         const BytesArgs a = bytes_args(c, dbg_raw, dbg_qc, dbg_low);
         if (debug) launch_bytes<true>(c, a); else launch_bytes<false>(c, a);
     }
-    if (prof) HIP_TRY(c, hipEventRecord(ev[3], c->stream));
+    if (prof) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
     launch_tail(c);
     if (prof) {
-        HIP_TRY(c, hipEventRecord(ev[4], c->stream));
+        HIP_TRY(c, hipEventRecord(ev[2], c->stream));
         c->ev_pending += 1;
     }
     HIP_TRY(c, hipGetLastError());
@@ -1068,19 +1073,12 @@ void cl_destroy(cl_ctx *c)
     join_prealloc(c);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     tmr.lap("destroy: sync");
-    c->d_pos.release(); c->d_mapq.release();
-    c->d_qual.release(); c->d_rows.release(); c->d_ref.release(); c->d_end.release(); c->d_rec.release(); c->d_heads.release(); c->d_refn.release();
-    c->d_win.release(); c->d_win_off.release(); c->d_state.release();
-    c->d_wide_idx.release();
-    c->d_runs.release(); c->d_first_state.release(); c->d_last_state.release(); c->d_win_wide.release();
-    c->d_winpart.release(); c->d_lut.release(); c->d_lut8.release(); c->d_summary.release();
-    c->d_iv.release(); c->d_dbg.release(); c->d_prof.release(); c->d_fin.release(); c->d_errflag.release(); c->d_runtab.release(); c->site.release();
-    c->t_prof.destroy();
-    c->d_dr_win.release(); c->d_dr_off.release(); c->d_dr_out.release(); c->h_dr_out.release();
-    c->t_dr_count.destroy(); c->t_dr_write.destroy();
+    c->each_buffer([](auto &buf) { buf.release(); });
+    c->d_prof.release(); c->site.release(); c->h_dr_out.release();
+    c->t_prof.destroy(); c->t_dr_count.destroy(); c->t_dr_write.destroy();
     if (c->ev_made)
-        for (int s = 0; s < cl_ctx::kEvSets; ++s)
-            for (int i = 0; i <= CL_K_COUNT; ++i) (void)hipEventDestroy(c->ev[s][i]);
+        for (auto &set : c->ev)
+            for (hipEvent_t e : set) (void)hipEventDestroy(e);
     tmr.lap("destroy: device buffers");
     c->ring.reset();
     tmr.lap("destroy: staging ring");
@@ -1444,21 +1442,18 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
         const int32_t *hp = c->hs.pos.data(); const uint8_t *hm = c->hs.mapq.data(); const uint32_t *he = c->hs.end.data();
         const uint32_t *ro = c->hs.rec_of.data();
         const uint32_t max_low = c->opt.max_low_mapq, hs = c->head_span;
-        if (c->heads4) {
-            rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_heads.p), ((uint64_t)n_rec + 1) * sizeof(uint32_t),
-                            rec_range_fill<uint32_t>(ro, n, n_rec, [hp, hm, he, ro, max_low](size_t i, auto &&put) {
-                const uint32_t low = (uint32_t)hm[i] <= max_low ? 0x80000000u : 0u, x = (uint32_t)hp[i];
-                if (ro[i + 1] != ro[i]) put(0u, (x & 0xFFFFu) | ((he[i] - x) << 16) | low);
-            }), rec_chunk_bytes());
-        } else {
-            rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_heads.p), ((uint64_t)n_rec + 1) * sizeof(uint2),
-                            rec_range_fill<uint2>(ro, n, n_rec, [hp, hm, he, ro, max_low, hs](size_t i, auto &&put) {
+        auto send_heads = [&](auto head) {                       // head: a value of the head's type, uint32_t or uint2
+            using Head = decltype(head);
+            return ring_start(c, reinterpret_cast<uint8_t *>(c->d_heads.p), ((uint64_t)n_rec + 1) * sizeof(Head),
+                              rec_range_fill<Head>(ro, n, n_rec, [=](size_t i, auto &&put) {
                 const uint32_t low = (uint32_t)hm[i] <= max_low ? 0x80000000u : 0u, cnt = ro[i + 1] - ro[i];
                 uint64_t x = (uint32_t)hp[i];
                 const uint64_t e = he[i];
-                for (uint32_t k = 0; k < cnt; ++k, x += hs) put(k, make_uint2((uint32_t)x, (uint32_t)std::min<uint64_t>(hs, e - x) | low));
+                if constexpr (sizeof(Head) == sizeof(uint32_t)) { if (cnt) put(0u, ((uint32_t)x & 0xFFFFu) | ((uint32_t)(e - x) << 16) | low); }
+                else for (uint32_t k = 0; k < cnt; ++k, x += hs) put(k, make_uint2((uint32_t)x, (uint32_t)std::min<uint64_t>(hs, e - x) | low));
             }), rec_chunk_bytes());
-        }
+        };
+        rs = c->heads4 ? send_heads(uint32_t()) : send_heads(uint2());
         if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
         if (rs != CL_OK) return rs;
         tmr.lap("upload: heads built + sent");
@@ -1824,15 +1819,10 @@ cl_status cl_contig_layout(cl_ctx *c, cl_layout_info *out)
     out->n_qual = c->n_qual; out->n_cigar = c->n_cigar;
     out->row_groups = c->n_row_groups; out->max_groups = c->max_groups;
     out->run_table_entries = c->n_runtab;
-    out->counter_planes = c->form == 3 ? (c->max_groups <= 63u ? 8u : c->max_groups <= 16383u ? 16u : 32u) : 0u;
-    // HBM this context holds (the capacity of every device buffer: what cl_destroy gives back)
+    out->counter_planes = c->form == 3 ? c->counter_planes() : 0u;
+    // HBM this context holds: the capacity of the device buffers of each_buffer, as cl_destroy walks them
     uint64_t b = 0;
-    b += c->d_pos.cap * 4 + c->d_mapq.cap + c->d_qual.cap + c->d_ref.cap + c->d_end.cap * 4 + c->d_rec.cap * sizeof(ReadRec) + c->d_heads.cap * sizeof(uint2) + c->d_refn.cap * 4;
-    b += c->d_rows.cap * sizeof(uint4) + c->d_win_off.cap * 4 + c->d_wide_idx.cap * 4 + c->d_win.cap * sizeof(WinMeta);
-    b += c->d_state.cap + c->d_runs.cap * 2 + c->d_first_state.cap + c->d_last_state.cap + c->d_win_wide.cap;
-    b += c->d_winpart.cap * sizeof(WinPartial) + c->d_fin.cap * sizeof(FinPartial) + c->d_errflag.cap * 4 + c->d_runtab.cap * 8;
-    b += c->d_lut.cap * 4 + c->d_lut8.cap * 4 + c->d_summary.cap * sizeof(DevSummary) + c->d_iv.cap * sizeof(Interval) + c->d_dbg.cap * 4;
-    b += c->d_dr_win.cap * 4 + c->d_dr_off.cap * 8 + c->d_dr_out.cap * 4;
+    c->each_buffer([&](auto &buf) { b += buf.cap * sizeof(*buf.p); });
     out->device_bytes = b;
     // what cl_contig_upload sent over the link for this contig (every transfer goes through the pinned staging ring)
     const uint64_t padded = (uint64_t)c->n_win * kT + 16;
@@ -1903,8 +1893,8 @@ cl_status cl_contig_depth_profile(cl_ctx *c, uint32_t n_bins, uint32_t window, c
 #define CL_LAUNCH(NP_) do { \
             if (c->heads4) hipLaunchKernelGGL((k_depth_profile<NP_, true>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a); \
             else hipLaunchKernelGGL((k_depth_profile<NP_, false>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a); } while (0)
-            if (c->max_groups <= 63u) CL_LAUNCH(8);
-            else if (c->max_groups <= 16383u) CL_LAUNCH(16);
+            if (c->counter_planes() == 8u) CL_LAUNCH(8);
+            else if (c->counter_planes() == 16u) CL_LAUNCH(16);
             else CL_LAUNCH(32);
 #undef CL_LAUNCH
             HIP_TRY(c, hipGetLastError());
@@ -1972,8 +1962,8 @@ cl_status cl_contig_depth_runs(cl_ctx *c, uint32_t kind, const uint32_t *edges, 
                 // (only the raw depths come from the heads: the qc depths are the rows' column sums)
                 if (kind == CL_DEPTH_RAW && c->heads4) hipLaunchKernelGGL((k_depth_runs<8, false, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
                 else if (kind == CL_DEPTH_RAW) hipLaunchKernelGGL((k_depth_runs<8, false, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else if (c->max_groups <= 63u) hipLaunchKernelGGL((k_depth_runs<8, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else if (c->max_groups <= 16383u) hipLaunchKernelGGL((k_depth_runs<16, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else if (c->counter_planes() == 8u) hipLaunchKernelGGL((k_depth_runs<8, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+                else if (c->counter_planes() == 16u) hipLaunchKernelGGL((k_depth_runs<16, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
                 else hipLaunchKernelGGL((k_depth_runs<32, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
             };
             // ---- count, scan: how many runs there are ----
