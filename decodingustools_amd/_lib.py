@@ -307,6 +307,24 @@ class dut_str_options(C.Structure):
                 ("min_allele_per_10k", C.c_uint32)]
 
 
+class cl_ep_result(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_cycles", C.c_uint32), ("pad", C.c_uint32),
+                ("n_reads", C.c_uint64), ("n_bases", C.c_uint64), ("n_uncomparable", C.c_uint64), ("n_ins", C.c_uint64), ("ins_bases", C.c_uint64),
+                ("n_del", C.c_uint64), ("del_bases", C.c_uint64), ("total", C.c_uint64 * 16),
+                ("from5", C.POINTER(C.c_uint64)), ("from3", C.POINTER(C.c_uint64)), ("ins5", C.POINTER(C.c_uint64)), ("ins3", C.POINTER(C.c_uint64)),
+                ("del5", C.POINTER(C.c_uint64)), ("del3", C.POINTER(C.c_uint64))]
+
+
+class dut_ep_reads(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("pos", C.c_void_p), ("flag", C.c_void_p), ("mapq", C.c_void_p), ("cigar_off", C.c_void_p), ("cigar", C.c_void_p),
+                ("seq_off", C.c_void_p), ("seq4", C.c_void_p), ("qual_off", C.c_void_p), ("qual", C.c_void_p)]
+
+
+class dut_ep_options(C.Structure):
+    _fields_ = [("min_quality", C.c_uint8), ("filtered", C.c_int), ("exclude_flags", C.c_uint16), ("has_min_base_quality", C.c_int),
+                ("min_base_quality", C.c_uint8), ("n_cycles", C.c_uint32)]
+
+
 class dut_variants_options(C.Structure):
     _fields_ = [("filtered", C.c_int), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
                 ("exclude_flags", C.c_uint16), ("min_alt_per_strand", C.c_uint32)]
@@ -323,6 +341,7 @@ class dut_tree_locus(C.Structure):
 CL_SCAN_MAX_DENSE = 1 << 20
 CL_STR_BINS, CL_STR_MAX_FLANK, CL_STR_MAX_LOCI, CL_STR_MAX_SPAN = 128, 64, 65536, 1024
 DUT_STR_UNITS_LEN = 24
+CL_EP_MAX_CYCLES = 256
 
 # every symbol the headers declare: (name, restype, argtypes)
 SYMBOLS = [
@@ -344,6 +363,9 @@ SYMBOLS = [
     ("cl_site_scan_consensus", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.POINTER(cl_cons_params), C.c_void_p, C.c_uint64,
                                          C.c_uint32, C.c_uint32, C.POINTER(cl_cons_result)]),
     ("cl_site_str_lengths", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(cl_str_result)]),
+    ("cl_site_error_profile", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                        C.POINTER(cl_ep_result)]),
+    ("cl_site_error_profile_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
     ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
@@ -394,6 +416,11 @@ SYMBOLS = [
                                 C.POINTER(dut_str_options), C.c_char_p, C.c_size_t]),
     ("dut_find_strs_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(dut_str_options), C.c_char_p, C.c_int, C.c_char_p,
                                       C.c_size_t]),
+    ("dut_error_profile_measure", C.c_int, [C.POINTER(dut_ep_reads), C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(dut_ep_options),
+                                            C.c_void_p, C.POINTER(cl_ep_result)]),
+    ("dut_error_profile_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_ep_result), C.POINTER(dut_ep_options), C.c_char_p, C.c_size_t]),
+    ("dut_error_profile_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_ep_options), C.c_char_p,
+                                          C.c_int, C.c_char_p, C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

@@ -383,6 +383,24 @@ class Engine:
             C.memmove(partial.ctypes.data, r.partial, partial.nbytes)
         return StrResult(hist=hist, partial=partial, kernel_ms=self.site_scan_stats()[0])
 
+    def site_error_profile(self, n_cycles, min_quality, ref, start=0, end=None, filter=None):
+        """cl_site_error_profile over [start, end) of the resident tile: substitutions by reference base and read base, the
+        same by distance from either end of the read, and insertion and deletion events by the same distances.  filter:
+        None for the unfiltered form (every read forward), else (exclude_flags, use_base_quality) of the attachment.  An
+        ErrorProfile of numpy uint64 arrays (copies), the scalars and the two launches' milliseconds."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        end = ref.shape[0] if end is None else end
+        r = _lib.cl_ep_result()
+        self._check(self._lib.cl_site_error_profile(self._h, int(min_quality), _filter_ref(filter), int(n_cycles), _ptr(ref), ref.shape[0], int(start), int(end),
+                                                    C.byref(r)))
+        return ErrorProfile.from_c(r, kernel_ms=self.site_scan_stats()[0])
+
+    def site_error_profile_stats(self):
+        """(table kernel milliseconds, slice sum milliseconds) of the last site_error_profile."""
+        a = C.c_double(); b = C.c_double()
+        self._check(self._lib.cl_site_error_profile_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def site_scan_ins_stats(self):
         """(window scan milliseconds, allele launch milliseconds) of the last site_scan_ins."""
         a = C.c_double(); b = C.c_double()
@@ -455,6 +473,64 @@ INS_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("pad", np.uint
 
 # cl_ins_obs: key = the first 32 inserted 4-bit codes, base j in key[j // 16] at bits 60 - 4 * (j % 16)
 INS_OBS = np.dtype([("pos", np.uint32), ("len", np.uint32), ("key", np.uint64, (2,)), ("strand", np.uint32), ("pad", np.uint32)])
+
+
+@dataclass
+class ErrorProfile:
+    """cl_ep_result (include/callable_loci.h): total[f, t], from5[d, f, t] and from3[d, f, t] count aligned bases with
+    reference base f and read base t (A C G T, in the orientation the molecule was sequenced in) at distance d from the
+    read's 5' and 3' end; ins5, ins3, del5, del3[d] count insertion and deletion events by the same distances."""
+    start: int
+    end: int
+    n_cycles: int
+    reads: int
+    bases: int
+    uncomparable: int
+    ins: int
+    ins_bases: int
+    dels: int
+    del_bases: int
+    total: np.ndarray
+    from5: np.ndarray
+    from3: np.ndarray
+    ins5: np.ndarray
+    ins3: np.ndarray
+    del5: np.ndarray
+    del3: np.ndarray
+    kernel_ms: float = 0.0
+
+    @staticmethod
+    def from_c(r, kernel_ms=0.0):
+        c = int(r.n_cycles)
+
+        def arr(ptr, n):
+            return np.ctypeslib.as_array(ptr, shape=(n,)).copy().astype(np.uint64)
+        return ErrorProfile(start=int(r.start), end=int(r.end), n_cycles=c, reads=int(r.n_reads), bases=int(r.n_bases), uncomparable=int(r.n_uncomparable),
+                            ins=int(r.n_ins), ins_bases=int(r.ins_bases), dels=int(r.n_del), del_bases=int(r.del_bases),
+                            total=np.array(list(r.total), np.uint64).reshape(4, 4), from5=arr(r.from5, 16 * c).reshape(c, 4, 4),
+                            from3=arr(r.from3, 16 * c).reshape(c, 4, 4), ins5=arr(r.ins5, c), ins3=arr(r.ins3, c), del5=arr(r.del5, c), del3=arr(r.del3, c),
+                            kernel_ms=kernel_ms)
+
+    def to_c(self):
+        """(cl_ep_result, the array its pointers are set into -- keep it alive as long as the record)."""
+        c = int(self.n_cycles)
+        tab = np.concatenate([np.ascontiguousarray(a, np.uint64).reshape(-1) for a in (self.from5, self.from3, self.ins5, self.ins3, self.del5, self.del3)])
+        if tab.shape[0] != 36 * c or np.asarray(self.total).size != 16:
+            raise ValueError("the tables do not have n_cycles cycles")
+        r = _lib.cl_ep_result()
+        r.start, r.end, r.n_cycles = int(self.start), int(self.end), c
+        r.n_reads, r.n_bases, r.n_uncomparable = int(self.reads), int(self.bases), int(self.uncomparable)
+        r.n_ins, r.ins_bases, r.n_del, r.del_bases = int(self.ins), int(self.ins_bases), int(self.dels), int(self.del_bases)
+        for k, v in enumerate(np.asarray(self.total, np.uint64).reshape(-1)):
+            r.total[k] = int(v)
+        p = tab.ctypes.data_as(C.POINTER(C.c_uint64))
+        at = lambda o: C.cast(C.addressof(p.contents) + 8 * o, C.POINTER(C.c_uint64))   # noqa: E731
+        r.from5, r.from3, r.ins5, r.ins3, r.del5, r.del3 = at(0), at(16 * c), at(32 * c), at(33 * c), at(34 * c), at(35 * c)
+        return r, tab
+
+    def tables_equal(self, other):
+        return (all(getattr(self, k) == getattr(other, k) for k in ("start", "end", "n_cycles", "reads", "bases", "uncomparable", "ins", "ins_bases", "dels", "del_bases"))
+                and all(np.array_equal(getattr(self, k), getattr(other, k)) for k in ("total", "from5", "from3", "ins5", "ins3", "del5", "del3")))
 
 
 @dataclass

@@ -1,5 +1,5 @@
 // dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
-// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions`, `find-insertions`, `consensus` and `find-strs`);
+// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions`, `find-insertions`, `consensus`, `find-strs` and `error-profile`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -52,7 +52,9 @@ static void usage()
             "       [--min-quality 20] [--min-del-fraction 0.7] [--min-del-count 3] [--min-ins-fraction 0.7] [--min-ins-count 3]\n"
             "       [--min-base-quality Q] [--exclude-flags MASK] [--fill N|ref] [--line-width 60] [--changes FILE] [--device 0]\n"
             "       dut-coverage find-strs <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> --loci FILE [--flank 5] [--min-depth 10]\n"
-            "       [--min-quality 20] [--min-allele-fraction 0.7] [--exclude-flags MASK] [--device 0]\n");
+            "       [--min-quality 20] [--min-allele-fraction 0.7] [--exclude-flags MASK] [--device 0]\n"
+            "       dut-coverage error-profile <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--cycles 50]\n"
+            "       [--min-quality 20] [--min-base-quality Q] [--exclude-flags MASK] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -241,7 +243,7 @@ static bool cli_count32(const char *flag, const std::string &v, uint32_t &dst)
     return true;
 }
 
-// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions, consensus, find-strs) share on the command line: the BAM, -r, -o,
+// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions, consensus, find-strs, error-profile) share on the command line: the BAM, -r, -o,
 // -L, --region (0-based, half open), --min-depth, --min-quality, the two filter flags, --device, -h.
 struct ScanCli {
     const char *name;
@@ -566,6 +568,37 @@ static int find_strs_main(int argc, char **argv)
     return scan_cli_leave(dut_find_strs_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), loci.c_str(), &o, c.out.c_str(), c.device, err, sizeof(err)), err);
 }
 
+static void usage_ep()
+{
+    fprintf(stderr, "Usage: dut-coverage error-profile <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--cycles 50]\n"
+                    "       [--min-quality 20] [--min-base-quality Q] [--exclude-flags MASK] [--device 0]\n"
+                    "  The sample's own error rates over the contig (or --region, 0-based half open): substitutions by reference\n"
+                    "  base and read base in the orientation the molecule was sequenced in, the same by distance from the read's 5'\n"
+                    "  and 3' end for the first --cycles positions (1..256), and insertion and deletion events by the same\n"
+                    "  distances.  Q and MASK as in find-variants.  One contig, one device.\n");
+}
+
+// error-profile: the read-centric table of mismatches, insertions and deletions by cycle (cl_site_error_profile).  Argument
+// errors leave with 2 before a device is opened.
+static int error_profile_main(int argc, char **argv)
+{
+    ScanCli c = {"error-profile", usage_ep};
+    dut_ep_options o = {20, 1, 0, 0, 0, 50};
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        if (a != "--cycles") return 0;
+        const std::string v = next();
+        if (!cli_count32("--cycles", v, o.n_cycles)) return -1;
+        if (o.n_cycles < 1 || o.n_cycles > CL_EP_MAX_CYCLES) { fprintf(stderr, "error: invalid value '%s' for '--cycles': 1..%u\n", v.c_str(), (unsigned)CL_EP_MAX_CYCLES); return -1; }
+        return 1;
+    });
+    if (st >= 0) return st;
+    o.min_quality = (uint8_t)c.min_quality;
+    c.filter_into(o);
+    char err[1024] = {0};
+    return scan_cli_leave(dut_error_profile_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), c.has_region ? 1 : 0, (uint32_t)c.start, (uint32_t)c.end, &o,
+                                                  c.out.c_str(), c.device, err, sizeof(err)), err);
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -589,6 +622,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "find-insertions")) return find_insertions_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "consensus")) return consensus_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-strs")) return find_strs_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "error-profile")) return error_profile_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

@@ -1,8 +1,8 @@
 // site_engine.hip.h -- the site engine (config 5; a textual part of callable_loci.hip's translation unit): the sparse
 // site pileup k_site_pileup with its host side (cl_site_upload / cl_site_run / cl_site_pileup), the host side of the
-// dense scans of site_scan.hip.h (cl_site_scan*, cl_site_attach_quals) and their entry points, and the repeat lengths
-// of site_str.hip.h (cl_site_str_lengths), which it includes.  Of a context it uses what EngineBase holds and its own
-// SiteResident.
+// dense scans of site_scan.hip.h (cl_site_scan*, cl_site_attach_quals) and their entry points, the repeat lengths of
+// site_str.hip.h (cl_site_str_lengths) and the error profile of site_errors.hip.h (cl_site_error_profile), which it
+// includes.  Of a context it uses what EngineBase holds and its own SiteResident.
 #pragma once
 
 #include "kernels.hip.h"
@@ -173,6 +173,12 @@ struct SiteResident {
     DevBuf<cl_str_locus> st_loci;
     DevBuf<uint32_t> st_hist, st_partial;
     std::vector<uint32_t> str_hist, str_partial;
+    // cl_site_error_profile (site_errors.hip.h): the workgroups' slices and their sum on the device, the sum as it came
+    // back, the tables in the result's layout; the sum launch's own events and duration
+    DevBuf<unsigned long long> ep_part, ep_sum;
+    std::vector<uint64_t> ep_host, ep_tab;
+    KernelTimer t_ep_sum;
+    double ep_sum_ms = 0.0;
     // the last cl_site_pileup / cl_site_run and the last cl_site_scan* of either form: the kernels' duration and their
     // algorithmic bytes; the candidates of the last cl_site_scan, cl_site_scan_ex, cl_site_scan_minor and cl_site_scan_dels
     KernelTimer t_pileup, t_scan;
@@ -185,10 +191,10 @@ struct SiteResident {
     double ins_scan_ms = 0.0, ins_alleles_ms = 0.0;      // the last cl_site_scan_ins: its two launches
     void release()
     {
-        t_pileup.destroy(); t_scan.destroy();
+        t_pileup.destroy(); t_scan.destroy(); t_ep_sum.destroy();
         q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release(); sd_cand.release();
         si_cand.release(); si_site.release(); si_obs.release(); si_found.release(); sk_cons.release();
-        st_loci.release(); st_hist.release(); st_partial.release();
+        st_loci.release(); st_hist.release(); st_partial.release(); ep_part.release(); ep_sum.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -970,6 +976,7 @@ template <class F> static cl_status site_entry(cl_ctx *h, F &&f)
 }
 
 #include "site_str.hip.h"
+#include "site_errors.hip.h"
 
 extern "C" {
 

@@ -8,7 +8,9 @@
 // the composed rule, the assembly of the bytes of cl_site_scan_consensus and the insertions into a sequence and a change
 // list, the FASTA and the change list's file, and dut_find_consensus_files over both scans on one resident tile.  And for
 // `find-strs`: the host route of cl_site_str_lengths over str_walk.h (dut_str_measure), the rule that turns a length
-// histogram into an allele, the unit notation, the loci file's parser, the TSV, and dut_find_strs_files.
+// histogram into an allele, the unit notation, the loci file's parser, the TSV, and dut_find_strs_files.  And for
+// `error-profile`: the host route of cl_site_error_profile over ep_walk.h (dut_error_profile_measure), the TSV, and
+// dut_error_profile_files.
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -23,6 +25,7 @@
 #include <vector>
 #include "host_parallel.h"
 #include "str_walk.h"
+#include "ep_walk.h"
 
 namespace {
 
@@ -1148,6 +1151,181 @@ int dut_find_strs_files(const char *bam_path, const char *fasta_path, const char
             memcpy(partial.data() + at, res.partial, m * 4);
         }
         return dut_str_write(output_path, contig, lp, n, skipped, hist.data(), partial.data(), 2, opt, err, err_len);
+    });
+}
+
+// ---- error-profile ----
+namespace {
+
+// the counts of one thread's reads, in the result's layout: from5 and from3 [cycle][16], ins5, ins3, del5, del3 [cycle],
+// then total[16], n_uncomparable, n_reads, n_ins, n_del, ins_bases, del_bases
+struct EpCounts {
+    uint32_t C;
+    std::vector<uint64_t> w;
+    explicit EpCounts(uint32_t c) : C(c), w((size_t)36 * c + 22, 0) {}
+    uint64_t *tail() { return w.data() + (size_t)36 * C; }
+};
+
+// the host's sink of ep_walk_read: one caller sees every base and event of read r
+struct EpHostSink {
+    const dut_ep_reads &R;
+    const uint8_t *ref;
+    EpCounts &n;
+    uint64_t r;
+    uint32_t L, rev;
+    bool use_bq;
+    uint8_t thr;
+    bool passes(uint32_t q) const
+    {
+        if (!use_bq) return true;
+        const uint64_t nq = R.qual_off[r + 1] - R.qual_off[r];
+        return q >= nq || R.qual[R.qual_off[r] + q] >= thr;
+    }
+    void cycles(uint64_t *t5, uint64_t *t3, uint32_t width, uint32_t col, uint32_t q) const
+    {
+        const uint32_t d5 = dut::ep_d5(q, L, rev), d3 = dut::ep_d3(q, L, rev);
+        if (d5 < n.C) t5[(size_t)d5 * width + col] += 1;
+        if (d3 < n.C) t3[(size_t)d3 * width + col] += 1;
+    }
+    void base(uint32_t p, uint32_t q) const
+    {
+        if (!passes(q)) return;
+        const uint64_t bi = R.seq_off[r] + q;
+        const uint32_t byte = R.seq4[bi >> 1], code = (bi & 1u) ? (byte & 15u) : (byte >> 4);
+        const uint32_t cell = dut::ep_cell(code, ref[p], rev);
+        n.tail()[cell] += 1;                                                    // (cell 16: n_uncomparable)
+        if (cell < 16u) cycles(n.w.data(), n.w.data() + (size_t)16 * n.C, 16, cell, q);
+    }
+    void event(uint32_t which, uint32_t q, uint32_t l) const
+    {
+        if (!passes(q)) return;
+        n.tail()[18 + which] += 1; n.tail()[20 + which] += l;
+        uint64_t *e = n.w.data() + (size_t)(32 + 2 * which) * n.C;
+        cycles(e, e + n.C, 1, 0, q);
+    }
+    void ins(uint32_t, uint32_t q, uint32_t l) const { event(0, q, l); }
+    void del(uint32_t, uint32_t q, uint32_t l) const { event(1, q, l); }
+};
+
+bool ep_options_ok(const dut_ep_options &o, char *err, size_t err_len)
+{
+    if (o.n_cycles >= 1 && o.n_cycles <= CL_EP_MAX_CYCLES) return true;
+    set_err(err, err_len, "n_cycles must lie in 1..256");
+    return false;
+}
+
+} // namespace
+
+int dut_error_profile_measure(const dut_ep_reads *reads, uint32_t contig_len, const uint8_t *ref_bases, uint64_t ref_len, uint32_t start, uint32_t end,
+                              const dut_ep_options *opt, uint64_t *tables, cl_ep_result *out)
+{
+    return no_throw(nullptr, 0, [&]() -> int {
+        if (!reads || !opt || !tables || !out || !ep_options_ok(*opt, nullptr, 0)) return CL_ERR_INVALID;
+        const dut_ep_reads &R = *reads;
+        const bool filtered = opt->filtered != 0, use_bq = filtered && opt->has_min_base_quality;
+        if (start > end || end > contig_len || (!ref_bases && ref_len)) return CL_ERR_INVALID;
+        if (R.n_reads && (!R.pos || !R.mapq || !R.cigar_off || !R.seq_off || (filtered && !R.flag) || (use_bq && !R.qual_off))) return CL_ERR_INVALID;
+        for (uint64_t r = 0; r < R.n_reads; ++r)
+            if (R.cigar_off[r + 1] < R.cigar_off[r] || R.seq_off[r + 1] < R.seq_off[r] || (use_bq && R.qual_off[r + 1] < R.qual_off[r])) return CL_ERR_INVALID;
+        if (R.n_reads && ((R.cigar_off[R.n_reads] > R.cigar_off[0] && !R.cigar) || (R.seq_off[R.n_reads] > R.seq_off[0] && !R.seq4) ||
+                          (use_bq && R.qual_off[R.n_reads] > R.qual_off[0] && !R.qual))) return CL_ERR_INVALID;
+        const uint32_t C = opt->n_cycles;
+        const uint32_t hi = (uint32_t)std::min<uint64_t>(end, ref_len);
+        EpCounts sum(C);
+        std::mutex mu;
+        const size_t grain = dut::grain_for((size_t)R.n_reads, 1u << 14), chunks = ((size_t)R.n_reads + grain - 1) / grain;
+        dut::parallel_for(start < hi ? chunks : 0, 1, [&](size_t ch) {
+            EpCounts mine(C);
+            for (uint64_t r = ch * grain, r1 = std::min<uint64_t>(R.n_reads, r + grain); r < r1; ++r) {
+                const uint32_t x = (uint32_t)R.pos[r];
+                if (x >= contig_len || x >= hi || R.mapq[r] < opt->min_quality) continue;
+                if (filtered && (R.flag[r] & opt->exclude_flags)) continue;
+                const uint32_t *cg = R.cigar + R.cigar_off[r];
+                const uint32_t n_ops = R.cigar_off[r + 1] - R.cigar_off[r];
+                uint64_t span = 0;
+                for (uint32_t k = 0; k < n_ops; ++k) span += ((0x18Du >> (cg[k] & 15u)) & 1u) ? (cg[k] >> 4) : 0u;
+                if (!span || (uint64_t)x + span <= start) continue;
+                mine.tail()[17] += 1;
+                const uint64_t L = R.seq_off[r + 1] - R.seq_off[r];
+                const EpHostSink sink{R, ref_bases, mine, r, (uint32_t)std::min<uint64_t>(L, 0xFFFFFFFFull), filtered ? (uint32_t)(R.flag[r] >> 4) & 1u : 0u,
+                                      use_bq, opt->min_base_quality};
+                dut::ep_walk_read(x, cg, n_ops, sink.L, start, hi, 0, 1, sink);
+            }
+            std::lock_guard<std::mutex> g(mu);
+            for (size_t i = 0; i < sum.w.size(); ++i) sum.w[i] += mine.w[i];
+        });
+        memset(out, 0, sizeof(*out));
+        out->start = start; out->end = end; out->n_cycles = C;
+        memcpy(tables, sum.w.data(), (size_t)36 * C * 8);
+        out->from5 = tables; out->from3 = tables + (size_t)16 * C;
+        out->ins5 = tables + (size_t)32 * C; out->ins3 = out->ins5 + C; out->del5 = out->ins3 + C; out->del3 = out->del5 + C;
+        const uint64_t *t = sum.tail();
+        for (int k = 0; k < 16; ++k) { out->total[k] = t[k]; out->n_bases += t[k]; }
+        out->n_uncomparable = t[16]; out->n_reads = t[17]; out->n_ins = t[18]; out->n_del = t[19]; out->ins_bases = t[20]; out->del_bases = t[21];
+        return CL_OK;
+    });
+}
+
+int dut_error_profile_write(const char *path, const char *contig, const cl_ep_result *res, const dut_ep_options *opt, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&]() -> int {
+        if (!path || !contig || !res || !opt) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (!ep_options_ok(*opt, err, err_len)) return CL_ERR_INVALID;
+        const uint32_t C = res->n_cycles;
+        if (C != opt->n_cycles) { set_err(err, err_len, "the result's n_cycles differs from the options'"); return CL_ERR_INVALID; }
+        if (!res->from5 || !res->from3 || !res->ins5 || !res->ins3 || !res->del5 || !res->del3) { set_err(err, err_len, "null table"); return CL_ERR_INVALID; }
+        auto rate = [](const uint64_t *cells) -> std::string {
+            uint64_t all = 0, diag = 0;
+            for (int k = 0; k < 16; ++k) { all += cells[k]; if (k % 5 == 0) diag += cells[k]; }
+            if (!all) return "NA";
+            char b[32];
+            snprintf(b, sizeof(b), "%.6f", (double)(all - diag) / (double)all);
+            return b;
+        };
+        uint64_t diag = 0;
+        for (int k = 0; k < 16; k += 5) diag += res->total[k];
+        char b[512], q[8] = ".";
+        if (opt->has_min_base_quality) snprintf(q, sizeof(q), "%u", (unsigned)opt->min_base_quality);
+        std::string s;
+        snprintf(b, sizeof(b), "##contig=%s\n##range=%u-%u\n##cycles=%u\n##min_quality=%u\n##min_base_quality=%s\n##exclude_flags=0x%04x\n", contig, res->start, res->end,
+                 C, (unsigned)opt->min_quality, q, (unsigned)opt->exclude_flags);
+        s += b;
+        snprintf(b, sizeof(b), "##reads=%llu\n##bases=%llu\n##uncomparable=%llu\n##mismatches=%llu\n##mismatch_rate=%s\n##insertions=%llu\n##inserted_bases=%llu\n"
+                               "##deletions=%llu\n##deleted_bases=%llu\n", (unsigned long long)res->n_reads, (unsigned long long)res->n_bases,
+                 (unsigned long long)res->n_uncomparable, (unsigned long long)(res->n_bases - diag), rate(res->total).c_str(), (unsigned long long)res->n_ins,
+                 (unsigned long long)res->ins_bases, (unsigned long long)res->n_del, (unsigned long long)res->del_bases);
+        s += b;
+        s += "#table\tcycle";
+        for (int f = 0; f < 4; ++f) for (int t = 0; t < 4; ++t) { s += '\t'; s += "ACGT"[f]; s += '>'; s += "ACGT"[t]; }
+        s += "\tins\tdel\tmismatch_rate\n";
+        auto line = [&](const char *table, const std::string &cycle, const uint64_t *cells, uint64_t n_ins, uint64_t n_del) {
+            s += table; s += '\t'; s += cycle;
+            for (int k = 0; k < 16; ++k) { s += '\t'; s += std::to_string(cells[k]); }
+            s += '\t' + std::to_string(n_ins) + '\t' + std::to_string(n_del) + '\t' + rate(cells) + '\n';
+        };
+        line("total", ".", res->total, res->n_ins, res->n_del);
+        for (uint32_t d = 0; d < C; ++d) line("5p", std::to_string(d + 1), res->from5 + (size_t)16 * d, res->ins5[d], res->del5[d]);
+        for (uint32_t d = 0; d < C; ++d) line("3p", std::to_string(d + 1), res->from3 + (size_t)16 * d, res->ins3[d], res->del3[d]);
+        return write_file(path, s, err, err_len);
+    });
+}
+
+int dut_error_profile_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start, uint32_t end,
+                            const dut_ep_options *opt, const char *output_path, int device_id, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&]() -> int {
+        if (!bam_path || !fasta_path || !contig || !output_path || !opt) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (!ep_options_ok(*opt, err, err_len)) return CL_ERR_INVALID;
+        ScanFiles F;
+        int rc = scan_files_open(F, bam_path, fasta_path, contig, has_region, start, end, err, err_len);
+        if (rc != CL_OK) return rc;
+        const FilterOptions flt = {opt->has_min_base_quality, opt->min_base_quality, opt->exclude_flags};
+        cl_scan_filter f;
+        if ((rc = scan_files_resident(F, contig, device_id, &flt, f, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
+        cl_ep_result res;
+        rc = cl_site_error_profile(F.ctx.get(), opt->min_quality, &f, opt->n_cycles, F.bases, F.blen, start, end, &res);
+        if (rc != CL_OK) { F.engine_err(err, err_len, "the error profile failed"); return rc; }
+        return dut_error_profile_write(output_path, contig, &res, opt, err, err_len);
     });
 }
 

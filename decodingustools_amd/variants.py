@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from .callable_loci import (DEL_CANDIDATE, INS_CANDIDATE, INS_OBS, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, ConsResult, DelResult,
-                            EngineError, InsResult, MinorResult, ScanResult, StrResult, _ptr)
+                            EngineError, ErrorProfile, InsResult, MinorResult, ScanResult, StrResult, _ptr)
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
@@ -544,3 +544,57 @@ def find_strs(bam_file: str, reference_file: str, contig: str, loci_file: str, o
     opt = _str_options(min_depth, min_quality, exclude_flags, flank, min_allele_fraction)
     _call(_lib.load().dut_find_strs_files, bam_file.encode(), reference_file.encode(), contig.encode(), loci_file.encode(), C.byref(opt),
           output_file.encode(), device_id, size=1024)
+
+
+def _ep_options(n_cycles, min_quality, exclude_flags, min_base_quality, filtered=True):
+    if not 0 <= int(min_quality) <= 255:
+        raise ValueError("min_quality: 0..255")
+    if not 0 <= int(exclude_flags) <= 0xFFFF:
+        raise ValueError("exclude_flags: 0..65535")
+    if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
+        raise ValueError("min_base_quality: 0..255")
+    if not 0 <= int(n_cycles) <= 0xFFFFFFFF:
+        raise ValueError("n_cycles: 0..2^32-1 (the library refuses what lies outside 1..256)")
+    return _lib.dut_ep_options(int(min_quality), 1 if filtered else 0, int(exclude_flags), 0 if min_base_quality is None else 1,
+                               int(min_base_quality or 0), int(n_cycles))
+
+
+def error_profile_measure(rec, contig_len: int, ref, n_cycles: int, min_quality: int, start: int = 0, end: Optional[int] = None,
+                          exclude_flags: Optional[int] = None, min_base_quality: Optional[int] = None) -> ErrorProfile:
+    """dut_error_profile_measure: what Engine.site_error_profile returns, from the records on the host (no device needed).
+    exclude_flags=None: the unfiltered form, every read forward; a mask (0 included): the filtered form, with
+    min_base_quality (None: every base passes) taken over the records' quality values."""
+    ref = np.ascontiguousarray(ref, np.uint8)
+    end = ref.shape[0] if end is None else end
+    keep = [np.ascontiguousarray(rec.pos, np.int32), np.ascontiguousarray(rec.flag, np.uint16), np.ascontiguousarray(rec.mapq, np.uint8),
+            np.ascontiguousarray(rec.cigar_off, np.uint32), np.ascontiguousarray(rec.cigar, np.uint32),
+            np.ascontiguousarray(rec.seq_off if rec.seq_off is not None else np.zeros(rec.n + 1, np.uint64), np.uint64),
+            np.ascontiguousarray(rec.seq4 if rec.seq4 is not None else np.zeros(0, np.uint8), np.uint8),
+            np.ascontiguousarray(rec.qual_off, np.uint64), np.ascontiguousarray(rec.qual, np.uint8)]
+    reads = _lib.dut_ep_reads(rec.n, *[a.ctypes.data if a.shape[0] else None for a in keep])
+    opt = _ep_options(n_cycles, min_quality, exclude_flags or 0, min_base_quality if exclude_flags is not None else None, exclude_flags is not None)
+    tables = np.zeros(36 * max(int(n_cycles), 1), np.uint64)
+    r = _lib.cl_ep_result()
+    st = _lib.load().dut_error_profile_measure(C.byref(reads), int(contig_len), _ptr(ref) if ref.shape[0] else None, ref.shape[0], int(start), int(end),
+                                               C.byref(opt), _ptr(tables), C.byref(r))
+    if st != 0:
+        raise EngineError(st, "dut_error_profile_measure refused its arguments")
+    return ErrorProfile.from_c(r)
+
+
+def write_error_profile(path: str, contig: str, result: ErrorProfile, min_quality: int = 20, min_base_quality: Optional[int] = None,
+                        exclude_flags: int = 0):
+    """The TSV of error-profile (dut_error_profile_write) for an ErrorProfile of Engine.site_error_profile or
+    error_profile_measure.  No device is needed."""
+    r, keep = result.to_c()
+    opt = _ep_options(result.n_cycles, min_quality, exclude_flags, min_base_quality)
+    _call(_lib.load().dut_error_profile_write, path.encode(), contig.encode(), C.byref(r), C.byref(opt))
+    del keep
+
+
+def error_profile(bam_file: str, reference_file: str, contig: str, output_file: str, region: Optional[Tuple[int, int]] = None, cycles: int = 50,
+                  min_quality: int = 20, min_base_quality: Optional[int] = None, exclude_flags: int = 0, device_id: int = 0):
+    """dut_error_profile_files: BAM (+ index) and FASTA in, the TSV of substitutions and indels by read cycle out.
+    region: (start, end), 0-based half open, or None for the whole contig."""
+    opt = _ep_options(cycles, min_quality, exclude_flags, min_base_quality)
+    _find_files(_lib.load().dut_error_profile_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(), device_id)

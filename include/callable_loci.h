@@ -649,6 +649,53 @@ typedef struct cl_str_result {
 cl_status cl_site_str_lengths(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: one strand */,
                               uint32_t flank, const cl_str_locus *loci, size_t n_loci, cl_str_result *out);
 
+/* ---- error profile: substitutions and indels by read cycle, over a range of the resident tile --------------------------- */
+/* One small table for the whole range [start, end) (0-based half open, end <= contig_len; hi = min(end, ref_len)), keyed
+ * by where in the read a base stood instead of where on the contig: what `samtools stats` (mismatches per cycle) and
+ * mapDamage (misincorporation by distance from either end) tabulate.  C = n_cycles.
+ * A read takes part iff its start is < contig_len, mapq >= min_quality, its reference span is not empty and overlaps
+ * [start, hi) and, under a filter, (flag & exclude_flags) == 0.  It is reverse iff a filter is given and flag & 0x10;
+ * without a filter no flag is read and every read is forward.  L is its stored base count.  Its CIGAR is walked from pos
+ * with x, the reference position reached (64 bits), and y, the stored bases consumed (M I S = X consume; D N H P do not).
+ * For a query index q < L: d5 = q (forward) or L - 1 - q (reverse), d3 = L - 1 - d5; soft-clipped bases count towards q.
+ *   aligned base   a base of an M/=/X operation at a position p of [start, hi) with query index q < L; under
+ *                  use_base_quality its pass bit must be set.  c = its 4-bit code, R = the upper-cased reference byte at p.
+ *                  c not one of 1 2 4 8 or R not one of ACGT: n_uncomparable += 1.  Otherwise f, t = the indices of R and c
+ *                  in A C G T, both complemented for a reverse read (3 - f, 3 - t: the table is in the orientation the
+ *                  molecule was sequenced in): total[4 f + t] += 1; d5 < C: from5[d5 * 16 + 4 f + t] += 1; d3 < C:
+ *                  from3[d3 * 16 + 4 f + t] += 1
+ *   insertion      an I operation of length l >= 1 directly behind an M/=/X operation of at least one base whose last
+ *                  position x - 1 (the anchor) lies in [start, hi), when the anchor base (query index y - 1) and all l
+ *                  inserted bases exist (y + l <= L) and, under use_base_quality, the anchor's pass bit is set:
+ *                  n_ins += 1, ins_bases += l, ins5[d5] += 1 if d5 < C, ins3[d3] += 1 if d3 < C, by the anchor base
+ *   deletion       a D operation (op 2, not N) of length l >= 1 whose first deleted position x lies in [start, hi) and
+ *                  whose carrier, query index y - 1, exists (1 <= y <= L) and, under use_base_quality, passes:
+ *                  n_del += 1, del_bases += l, del5 / del3 by the carrier's cycle under the same conditions
+ * n_reads counts the reads that take part, each once; n_bases = the sum of total.  Every count is exact for any depth.
+ * For a <= b <= c every count but n_reads over [a, c) is the sum of those over [a, b) and [b, c).
+ * The arrays are context-owned, in storage of their own, valid until the next cl_site_error_profile, cl_site_upload or
+ * cl_destroy; any order of this call, cl_site_run, the scans and cl_site_str_lengths on one tile is allowed, and the call
+ * builds the read index itself when it is the first on a fresh tile.  start == end returns zeros without a launch.  Two
+ * calls return identical bytes (no count crosses workgroups through an atomic).  cl_site_scan_stats speaks of both
+ * launches, the table kernel and the sum of its workgroups' slices, after the call.
+ * CL_ERR_INVALID (with a message, the context stays usable): everything cl_site_scan / cl_site_scan_ex refuse (no resident
+ * tile, a tile cl_site_pileup filtered, start > end, end > contig_len, another ref_len, a null reference, a filter with
+ * nothing attached), n_cycles outside [1, CL_EP_MAX_CYCLES], null out.  CL_ERR_DEVICE: a host-only debug context. */
+#define CL_EP_MAX_CYCLES 256
+typedef struct cl_ep_result {
+    uint32_t start, end, n_cycles, pad;
+    uint64_t n_reads, n_bases, n_uncomparable, n_ins, ins_bases, n_del, del_bases;
+    uint64_t total[16];                       /* [4 * from + to], A C G T */
+    const uint64_t *from5, *from3;            /* n_cycles * 16 */
+    const uint64_t *ins5, *ins3, *del5, *del3;/* n_cycles */
+} cl_ep_result;
+cl_status cl_site_error_profile(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: unfiltered, all forward */,
+                                uint32_t n_cycles, const uint8_t *ref_bases, uint64_t ref_len,
+                                uint32_t start, uint32_t end, cl_ep_result *out);
+/* Measurement: the two launches of the last cl_site_error_profile apart, in milliseconds (their sum is what
+ * cl_site_scan_stats reports): the table kernel, and the sum of the workgroups' slices. */
+cl_status cl_site_error_profile_stats(cl_ctx *ctx, double *table_ms, double *sum_ms);
+
 /* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
  * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
 cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);

@@ -423,6 +423,62 @@ int dut_str_write(const char *path, const char *contig, const dut_str_locus *loc
 int dut_find_strs_files(const char *bam_path, const char *fasta_path, const char *contig, const char *loci_path,
                         const dut_str_options *opt, const char *output_path, int device_id, char *err, size_t err_len);
 
+/* ---- error-profile: substitutions and indels by read cycle (cl_site_error_profile) ------------------------------------- */
+/* The reads of a contig as host arrays: pos / flag / mapq / cigar_off (n_reads + 1) / cigar as dut_str_measure takes them;
+ * the stored bases as 4-bit codes, base i of the array in byte i / 2, high nibble first, read r holding bases
+ * [seq_off[r], seq_off[r + 1]); the quality values numbered by qual_off, which need not agree with seq_off (a base without
+ * a value passes a base-quality filter, as in cl_site_attach_quals).  flag may be NULL for an unfiltered call, qual_off and
+ * qual when no base-quality threshold is given. */
+typedef struct dut_ep_reads {
+    uint64_t        n_reads;
+    const int32_t  *pos;
+    const uint16_t *flag;
+    const uint8_t  *mapq;
+    const uint32_t *cigar_off, *cigar;
+    const uint64_t *seq_off;
+    const uint8_t  *seq4;
+    const uint64_t *qual_off;
+    const uint8_t  *qual;
+} dut_ep_reads;
+
+/* What an error-profile run is asked.  filtered == 0: no flag is read, every read is forward, every base passes (the
+ * unfiltered form of cl_site_error_profile; exclude_flags and the threshold take no part).  dut_error_profile_files always
+ * runs the filtered form. */
+typedef struct dut_ep_options {
+    uint8_t  min_quality;
+    int      filtered;
+    uint16_t exclude_flags;
+    int      has_min_base_quality;    /* 0: every base passes */
+    uint8_t  min_base_quality;
+    uint32_t n_cycles;                /* 1..CL_EP_MAX_CYCLES */
+} dut_ep_options;
+
+/* cl_site_error_profile from host arrays, no device needed: the same tables and scalars (the walk is written once, in
+ * csrc/ep_walk.h, and both routes compile it) over [start, end) of a contig of contig_len positions with the reference
+ * bytes ref_bases[0, ref_len).  tables: 36 * n_cycles words of the caller's, filled as from5 and from3 [cycle][16], then
+ * ins5, ins3, del5, del3 [cycle]; out's pointers are set into it.  The reads are spread over DUT_THREADS threads.
+ * CL_ERR_INVALID: a null argument or array, n_cycles outside [1, CL_EP_MAX_CYCLES], start > end, end > contig_len, offsets
+ * that decrease.  What a caller without a device gets, and the yardstick of tools/error_profile_bench.py. */
+int dut_error_profile_measure(const dut_ep_reads *reads, uint32_t contig_len, const uint8_t *ref_bases, uint64_t ref_len,
+                              uint32_t start, uint32_t end, const dut_ep_options *opt, uint64_t *tables, cl_ep_result *out);
+
+/* The TSV (no device needed) of a result: comment lines ##contig= ##range=start-end ##cycles= ##min_quality=
+ * ##min_base_quality= ("." when not given) ##exclude_flags=0x%04x ##reads= ##bases= ##uncomparable= ##mismatches=
+ * ##mismatch_rate= ##insertions= ##inserted_bases= ##deletions= ##deleted_bases=, the header
+ *   #table cycle A>A A>C A>G A>T C>A ... T>T ins del mismatch_rate
+ * one `total` line with cycle ".", then `5p` lines for cycles 1..C and `3p` lines for cycles 1..C (1-based in the file).
+ * mismatch_rate = the off-diagonal sum over the 16-cell sum as %.6f, "NA" when that sum is 0.  CL_ERR_INVALID: a null
+ * argument, a result whose n_cycles is outside [1, CL_EP_MAX_CYCLES] or differs from the options'. */
+int dut_error_profile_write(const char *path, const char *contig, const cl_ep_result *res, const dut_ep_options *opt,
+                            char *err, size_t err_len);
+
+/* `error-profile` on files, one GPU: reads as dut_find_strs_files does, always attaches the records' flags and pass bits
+ * and runs the filtered form of cl_site_error_profile over the contig or the region, writes the TSV.  Errors with a
+ * message: those of dut_find_variants_files, n_cycles outside [1, CL_EP_MAX_CYCLES]. */
+int dut_error_profile_files(const char *bam_path, const char *fasta_path, const char *contig, int has_region, uint32_t start,
+                            uint32_t end, const dut_ep_options *opt, const char *output_path, int device_id, char *err,
+                            size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

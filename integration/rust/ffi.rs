@@ -109,6 +109,20 @@ extern "C" {
     pub fn dut_str_units(span: u32, delta: i32, period: u32, buf: *mut c_char) -> c_int;                   // buf: 24 bytes
     pub fn dut_find_strs_files(bam: *const c_char, fasta: *const c_char, contig: *const c_char, loci_path: *const c_char,
                                opt: *const DutStrOptions, output: *const c_char, device_id: c_int, err: *mut c_char, err_len: usize) -> c_int;
+    // error profile (README "Error profile"): substitutions by reference base and read base, the same by distance from either
+    // end of the read, and insertion and deletion events by the same distances, over [start, end) of the tile cl_site_upload
+    // left resident; filter null: unfiltered, every read forward.  n_cycles 1..256.  Context-owned arrays, valid until the
+    // next cl_site_error_profile / upload.  cl_site_error_profile_stats: the two launches of the last call apart
+    pub fn cl_site_error_profile(ctx: *mut ClCtx, min_quality: u8, filter: *const ClScanFilter, n_cycles: u32, ref_bases: *const u8,
+                                 ref_len: u64, start: u32, end: u32, out: *mut ClEpResult) -> c_int;
+    pub fn cl_site_error_profile_stats(ctx: *mut ClCtx, table_ms: *mut f64, sum_ms: *mut f64) -> c_int;
+    // include/dut_variants.h: the same from host arrays (tables: 36 * n_cycles words of the caller's), the TSV, `error-profile` on files
+    pub fn dut_error_profile_measure(reads: *const DutEpReads, contig_len: u32, ref_bases: *const u8, ref_len: u64, start: u32, end: u32,
+                                     opt: *const DutEpOptions, tables: *mut u64, out: *mut ClEpResult) -> c_int;
+    pub fn dut_error_profile_write(path: *const c_char, contig: *const c_char, res: *const ClEpResult, opt: *const DutEpOptions,
+                                   err: *mut c_char, err_len: usize) -> c_int;
+    pub fn dut_error_profile_files(bam: *const c_char, fasta: *const c_char, contig: *const c_char, has_region: c_int, start: u32, end: u32,
+                                   opt: *const DutEpOptions, output: *const c_char, device_id: c_int, err: *mut c_char, err_len: usize) -> c_int;
     // include/dut_fingerprint.h: the `fingerprint` sketch on the device (1 <= ksize <= 64)
     pub fn dut_fp_create(opt: *const DutFpOptions, device_id: c_int, stream: *mut c_void, out: *mut *mut DutFpCtx) -> c_int;
     pub fn dut_fp_push_seq4(ctx: *mut DutFpCtx, seq4: *const u8, base_off: *const u64, n_seq: u64) -> c_int;
@@ -151,6 +165,27 @@ pub struct ClStrLocus { pub start: u32, pub end: u32 }      // cl_str_locus: 0-b
 #[repr(C)]
 pub struct ClStrResult {          // cl_str_result: hist[(i * strands + strand) * 128 + delta + 63], bin 127 = every other delta
     pub n_loci: usize, pub hist: *const u32, pub partial: *const u32, pub strands: u32,
+}
+
+#[repr(C)]
+pub struct ClEpResult {           // cl_ep_result: total[4 * from + to] in A C G T; from5 / from3: n_cycles * 16; ins5 .. del3: n_cycles
+    pub start: u32, pub end: u32, pub n_cycles: u32, pub pad: u32,
+    pub n_reads: u64, pub n_bases: u64, pub n_uncomparable: u64, pub n_ins: u64, pub ins_bases: u64, pub n_del: u64, pub del_bases: u64,
+    pub total: [u64; 16],
+    pub from5: *const u64, pub from3: *const u64,
+    pub ins5: *const u64, pub ins3: *const u64, pub del5: *const u64, pub del3: *const u64,
+}
+
+#[repr(C)]
+pub struct DutEpReads {           // dut_ep_reads: flag may be null unfiltered, qual_off / qual without a base-quality threshold
+    pub n_reads: u64, pub pos: *const i32, pub flag: *const u16, pub mapq: *const u8, pub cigar_off: *const u32, pub cigar: *const u32,
+    pub seq_off: *const u64, pub seq4: *const u8, pub qual_off: *const u64, pub qual: *const u8,
+}
+
+#[repr(C)]
+pub struct DutEpOptions {         // dut_ep_options: filtered 0 = no flag read, every read forward, every base passes
+    pub min_quality: u8, pub filtered: c_int, pub exclude_flags: u16, pub has_min_base_quality: c_int, pub min_base_quality: u8,
+    pub n_cycles: u32,
 }
 
 #[repr(C)]
