@@ -81,6 +81,18 @@ __device__ __forceinline__ uint4 row_unit(const RowLane &rl, int k)
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void row_advance(RowLane &rl, int by) { rl.off += (uint32_t)by * 128u; rl.n -= by; }
+// a head at byte offset `off` of a buffer descriptor of heads, a zeroed one (no candidate) where the offset lies beyond it
+typedef unsigned int HeadWords __attribute__((ext_vector_type(2)));
+template <bool HEAD4> __device__ __forceinline__ typename HeadOf<HEAD4>::type head_fetch(__amdgpu_buffer_rsrc_t rs, uint32_t off);
+template <> __device__ __forceinline__ uint32_t head_fetch<true>(__amdgpu_buffer_rsrc_t rs, uint32_t off)
+{
+    return __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0);
+}
+template <> __device__ __forceinline__ uint2 head_fetch<false>(__amdgpu_buffer_rsrc_t rs, uint32_t off)
+{
+    const HeadWords v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
+    return make_uint2(v.x, v.y);
+}
 
 // ---------------------------------------------------------------------------------------------
 // k_pileup_rows: the pass-bit form of the pileup (the default; DUT_QUAL_FORM=bytes selects the byte forms, k_pileup).
@@ -89,12 +101,12 @@ __device__ __forceinline__ void row_advance(RowLane &rl, int by) { rl.off += (ui
 // (cl_push_reads: one bit per base, qual_pack.cpp), and the bits reach the device as ROWS (pass_rows.h): per window a
 // stack of T-bit rows, bit p of a row <-> reference position W + p, every read of the window (mapq >= min) alone in its
 // stretch of a row.  qc_depth[p] (mod.rs:30-37) is then the column sum of the window's rows -- taken BIT-SLICED: a lane
-// owns a block of 32 positions, a wave streams groups of 4 rows (one 16-byte load per lane: a unit of 128 bytes per
-// segment of 8 lanes, as many as the segment's own stack is high -- row_lane above --, no masks, no shifts), and adds
-// them into NP counter planes (plane k = bit k of
-// the 32 counts) with carry-save adders: three-input boolean operations (v_bitop3), about 4.5 instructions per row
-// for 32 positions.  No LDS atomics, no CIGAR, no offsets.  The other waves' planes are added by wave 0 and compared --
-// still bit-sliced -- with min_depth and max_depth (callable_profiler.rs:108-113): two 32-bit masks per block.
+// owns a block of 32 positions, the window's one wave streams groups of 4 rows (one 16-byte load per lane: a unit of
+// 128 bytes per segment of 8 lanes, as many as the segment's own stack is high -- row_lane above --, no masks, no
+// shifts), and adds them into NP counter planes (plane k = bit k of the 32 counts) with carry-save adders: three-input
+// boolean operations (v_bitop3), about 4.5 instructions per row for 32 positions.  No LDS atomics, no CIGAR, no
+// offsets.  The planes stay in the lane's registers and are compared there -- still bit-sliced -- with min_depth and
+// max_depth (callable_profiler.rs:108-113): two 32-bit masks, those of the 32 positions the lane goes on to classify.
 // quality_bases is the number of set bits (contig_profiler.rs:71: taken from the planes, sum of 2^p x popcount);
 // summed_baseq comes with the bits from the host's walk (contig_profiler.rs:70, per-read separable: SURVEY 8a-7).
 //
@@ -141,9 +153,9 @@ __device__ __forceinline__ uint32_t bs_less_than(const uint32_t (&c)[NP], unsign
     return lt;
 }
 
-// What k_pileup_rows takes (callable_loci.hip: rows_args fills it, every member, in this order).  The scalar registers
-// of a wave are one of the three things that limit the production instantiation's residency (see the LDS comment in the
-// kernel) and every argument that is read takes one or two of them.
+// What k_pileup_rows takes (callable_loci.hip: rows_args fills it, every member, in this order).  Every argument
+// that is read takes one or two scalar registers of the wave (they limited the two-wave form's residency; at 5 waves
+// per SIMD they no longer do: see the LDS comment in the kernel).
 struct RowsArgs {
     const uint4    *rows;         // per window and segment, units of 4 rows x 8 blocks (host, at upload)
     const void     *heads;        // per read with a reference span: 8 bytes, or 4 in an instantiation with HEAD4 (above)
@@ -166,51 +178,39 @@ struct RowsArgs {
     uint32_t       *dbg_raw, *dbg_qc, *dbg_low;
 };
 
-// threads per workgroup: 2 waves, 16 positions per thread in the final phase (against 256 threads, the measured winner,
-// what a wave does once per window -- scans, reductions, the planes' hand-over -- is done half as often)
-constexpr int kRowsBlock = 128;
-// the waves per SIMD the register allocation is to leave room for: what LDS admits -- 8 for the production form (16
-// workgroups of 2 waves per CU), 7 for 16 planes without DEEP (12 KB: 13 workgroups), 3 for the large forms; the
-// DEBUG forms (test dumps: s_dbg adds 2 to 8 KB of LDS) keep the bounds they always had
+// threads per workgroup: ONE wave per window, 32 positions per thread in the final phase -- the lane that counted a
+// block of 32 positions is the thread that classifies them.  (256 -> 128 threads was the measured winner of round 4,
+// 128 -> 64 that of round 21, DESIGN.md section 5: what a wave does once per window -- scans, reductions, set-up -- is
+// done once, and nothing travels between waves: no barrier waits, no planes or masks through LDS.)
+constexpr int kRowsBlock = 64;
+// The waves per SIMD the register allocation is to leave room for.  LDS admits 20 workgroups per CU for every form
+// without DEEP (8 192 bytes: 5 waves per SIMD, 96 vector registers) and 10 with it (16 384 bytes).  The production
+// form (8 planes) takes the 5.  The forms with more planes hold 16 or 32 of them beside the 48 row registers and are
+// given the registers instead: 4 waves (128) for 16 planes, 3 (168) for 32 planes and for DEEP, which keeps 10
+// workgroups on 4 SIMDs.  The DEBUG forms (test dumps) keep the planes alive through the final phase for the dump of
+// qc_depth and get one wave less than their form (at its registers the forms of 8 and of 32 planes spill).
 constexpr int rows_min_waves(bool DEBUG, bool DEEP, int NP)
 {
-    if (DEBUG) return (DEEP || NP > 8) ? 3 : 6;
-    return (DEEP || NP > 16) ? 3 : (NP > 8 ? 7 : 8);
+    return ((DEEP || NP > 16) ? 3 : (NP > 8 ? 4 : 5)) - (DEBUG ? 1 : 0);
 }
 template <int T, bool DEBUG, bool DEEP, int NP, bool HEAD4>
 __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k_pileup_rows(RowsArgs a)
 {
     constexpr int kBlock = kRowsBlock;                     // (shadows the namespace's 256 inside this kernel)
     constexpr int PER = T / kBlock;
-    static_assert(PER == 16 && T == 2048, "a lane owns a block of 32 positions: T = 64 x 32");
-    constexpr int kWaves = kBlock / 64;
+    static_assert(PER == 32 && T == 2048 && kBlock == 64, "a lane owns a block of 32 positions: T = 64 x 32, one wave");
     constexpr int kDiffWords = DEEP ? T : T / 2;
-    constexpr int G = 6;                                   // groups a wave has in flight: 12 per window before a second trip
+    constexpr int G = 12;                                  // groups the wave has in flight: 48 rows before a second trip
+    // LDS: the two difference arrays and nothing else -- 8 192 bytes (16 384 with DEEP), which admits 20 workgroups =
+    // 20 windows in flight per CU (the kernel's time follows the number of windows a CU has in flight:
+    // profiles/r04_occupancy.txt).  With one wave per workgroup that is 5 waves per SIMD: at most 96 vector registers;
+    // scalar registers do not bind (800 / 5).  One byte more of LDS would cost a workgroup per CU, so the byte
+    // thresholds stay in registers (wlut, below).
+    // The arrays are cleared, added to (atomics) and read by the same wave: what has to be ordered is that wave's own
+    // LDS operations.  __syncthreads() is used for it -- in a workgroup of one wave it is the wait for the LDS counter
+    // and a fence for the compiler, no s_barrier that anybody waits at.
     __shared__ __attribute__((aligned(16))) uint32_t s_raw[kDiffWords];
     __shared__ __attribute__((aligned(16))) uint32_t s_low[kDiffWords];
-    // LDS: the two difference arrays and ONE pool that is used twice -- 10 240 bytes in all, which admits 16 workgroups
-    // per CU (the kernel's time follows the number of workgroups a CU runs: profiles/r04_occupancy.txt).  LDS is one of
-    // three limits and with 2 waves per workgroup all three must allow 8 waves per SIMD: at most 64 vector registers,
-    // and at most 80 scalar registers (.sgpr_count; 81..96 leave 7 waves = 14 workgroups, 97.. leave 6 = 12, which is
-    // where this kernel stood while the compiler's own figure said 8: profiles/r11_rows_residency.json):
-    //   first   the counter planes of waves 1.. (wave 0 adds them to its own after the barrier; it is their only reader)
-    //   then    s_lt / s_gt and the low-MAPQ thresholds s_lut: a lane of wave 0 writes its words after it has read its
-    //           planes (they lie in the slots of that lane's own planes 0, 1 and kLutPlane of wave 1); s_last, s_wtot, s_wmax:
-    //           written behind the NEXT barrier, when wave 0 is long done with the planes
-    // (the waves' totals for the prefix sums across waves travel in the difference arrays: a lane's own, consumed slot)
-    constexpr int kPoolWords = (kWaves - 1) * NP * 64;
-    constexpr int kTenantsEnd = 128 + kBlock / 4 + kWaves * 24 + kWaves;        // words: s_lt, s_gt, s_last, s_wtot, s_wmax
-    constexpr int kLutPlane = (kTenantsEnd + 63) / 64;                          // the thresholds: the first whole plane behind them
-    static_assert(NP >= 8 && kLutPlane < NP && kPoolWords >= (kLutPlane + 1) * 64, "the pool holds its second tenants");
-    __shared__ __attribute__((aligned(16))) uint32_t s_pool[kPoolWords];
-    uint32_t (*s_pl)[NP][64] = reinterpret_cast<uint32_t (*)[NP][64]>(s_pool);
-    uint32_t *const s_lt = s_pool, *const s_gt = s_pool + 64;                  // per block: qc < min_depth, qc > max_depth
-    uint8_t *const s_last = reinterpret_cast<uint8_t *>(s_pool + 128);         // kBlock bytes
-    unsigned long long (*s_wtot)[12] = reinterpret_cast<unsigned long long (*)[12]>(s_pool + 128 + kBlock / 4);
-    uint32_t *const s_wmax = s_pool + 128 + kBlock / 4 + kWaves * 24;
-    // the low-MAPQ thresholds of depths below 255 as bytes: 255 = never (a count is at most the depth): a copy of a.lut8
-    uint8_t *const s_lut = reinterpret_cast<uint8_t *>(s_pool + kLutPlane * 64);
-    __shared__ uint32_t s_dbg[DEBUG ? NP : 1][64];         // DEBUG: the window's planes, for the dump of qc_depth
 #ifdef CL_ROWS_LDS_PAD
     __shared__ uint32_t s_pad[CL_ROWS_LDS_PAD / 4];        // (occupancy experiments only)
     s_pad[threadIdx.x] = threadIdx.x;
@@ -218,71 +218,87 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
 
     const uint32_t w = (blockIdx.x & 7u) * a.n_win8 + (blockIdx.x >> 3);   // XCD-contiguous window ranges
     if (w >= a.n_win) return;
-    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = threadIdx.x;
     const uint32_t W = w * (uint32_t)T;
-    // (the wave number from a scalar register: whatever is indexed or bounded by it below is scalar code)
-    const uint32_t lane = tid & 63u, wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    const uint32_t p0 = W + tid * PER;
+    const uint32_t p0 = W + lane * PER;
 
     const WinMeta wm = a.win[w];
     const uint32_t lo = wm.lo, hi = wm.hi, wlo = wm.wlo, wn = wm.wn;
     const uint32_t n_cand = wn + (hi - lo);
     const uint32_t ng = wm.rn;                             // groups of 4 rows: the highest of the window's segments
-    RowLane rl = row_lane(a.rows, wm, lane, wv);
+    RowLane rl = row_lane(a.rows, wm, lane, 0u);
 
-    // requested first, needed last: the window's rows (this wave's first G groups), the reference bytes
+    // requested first, needed last: the window's rows (the first G groups of every segment), the reference bits
     // (a lane gets the units its segment has, and zeros for the rest: row_lane)
     uint4 rv[G];
 #pragma unroll
-    for (int j = 0; j < G; ++j) rv[j] = row_unit(rl, kWaves * j);
-    // ... and the window's first candidates: heads (above), U per lane and trip
-    constexpr int U = 4;
+    for (int j = 0; j < G; ++j) rv[j] = row_unit(rl, j);
+    // ... and the window's first candidates: heads (above), U per lane and trip -- 512 in the first trip, which covers
+    // a window of a 30x short-read contig (about 430), so that no second, dependent load stands behind the first
+    constexpr int U = 8;
     typedef typename HeadOf<HEAD4>::type Head;
+    // The ordinary candidates [lo, hi) are read through a buffer descriptor of exactly their heads, as the rows are: a
+    // slot that is no ordinary candidate (a wide one, v < wn, or one past the last) asks for an offset beyond the
+    // descriptor and gets a zeroed head -- no candidate -- without touching memory.  So the U loads of a trip are
+    // straight code that is issued back to back behind the rows'.  (With a branch around each load, every head waited
+    // for all the loads before it, the rows included: 4 dependent round trips to memory per wave before round 21.)
+    // Wide candidates are rare and come first: only a trip that has some (a scalar test) fetches them, index then head.
+    const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char *>(static_cast<const char *>(a.heads) + (size_t)lo * sizeof(Head)), 0, (int)((hi - lo) * (uint32_t)sizeof(Head)), 0x00020000);
     auto load_heads = [&](uint32_t base, Head (&hh)[U]) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const uint32_t v = base + (uint32_t)u * kBlock + tid;
-            uint32_t r = lo + (v - wn);
-            if (v < wn) r = a.wide_idx[wlo + v];
-            __builtin_assume(r < (1u << 29));
-            hh[u] = Head();
-            if (v < n_cand) hh[u] = head_at<HEAD4>(a.heads, r);
+            const uint32_t o = base + (uint32_t)u * kBlock + lane - wn;      // (wraps for a wide slot: beyond hi - lo)
+            // (0xFFFFFFF0: beyond the heads of any window -- fewer than 2^29 of at most 8 bytes --, and + 7 does not wrap)
+            hh[u] = head_fetch<HEAD4>(hrs, o < hi - lo ? o * (uint32_t)sizeof(Head) : 0xFFFFFFF0u);
+        }
+        if (wn > base) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t v = base + (uint32_t)u * kBlock + lane;
+                if (v < wn) {
+                    const uint32_t r = a.wide_idx[wlo + v];
+                    __builtin_assume(r < (1u << 29));
+                    hh[u] = head_at<HEAD4>(a.heads, r);
+                }
+            }
         }
     };
     Head hh[U];
     load_heads(0u, hh);
-    // ... and wave 0's word of the byte thresholds, which it puts into LDS once it is done with the planes there
-    uint32_t wlut = 0u;
-    if (wv == 0) wlut = a.lut8[lane];
+    // ... and the lane's word of the byte thresholds: those of depths 4 lane .. 4 lane + 3.  The 256 bytes stay in the
+    // wave's registers; the fast path below fetches the word of depth d from lane d >> 2 (ds_bpermute: no LDS memory)
+    const uint32_t wlut = a.lut8[lane];
     // (bit p of refn: the reference base at p is 'N' / 'n' or lies beyond the reference, mod.rs:79-80, :100-101)
-    const uint32_t refn = (uint32_t)reinterpret_cast<const uint16_t *>(a.refn)[(size_t)w * (T / 16) + tid];
+    const uint32_t refn = a.refn[(size_t)w * (T / 32) + lane];
 
     // ---- clear ----
     {
         const uint4 z = make_uint4(0, 0, 0, 0);
         uint4 *r4 = reinterpret_cast<uint4 *>(s_raw), *l4 = reinterpret_cast<uint4 *>(s_low);
         const uint4 zb = DEEP ? z : make_uint4(0x8000u, 0x8000u, 0x8000u, 0x8000u);
-        for (int i = tid; i < kDiffWords / 4; i += kBlock) { r4[i] = zb; l4[i] = zb; }
+#pragma unroll
+        for (int i = 0; i < kDiffWords / 4 / kBlock; ++i) { r4[i * kBlock + lane] = zb; l4[i * kBlock + lane] = zb; }
     }
-    __syncthreads();
+    __syncthreads();                                       // (this wave's clear before its atomics: see the LDS comment)
 
-    // ---- the window's rows: this wave's groups wv, wv + 2, ... into its counter planes.  The wave number is taken
-    //      from a scalar register so that the tests on group numbers are scalar branches: a group slot past the window's
-    //      highest segment costs nothing (the kernel is bound by vector issue), and the loads of a next trip are only
-    //      issued when there is one (some segment with more than 12 groups: depth beyond 48) ----
+    // ---- the window's rows: every group into the lane's own counter planes.  The group count is in a scalar register,
+    //      so the tests on group numbers are scalar branches: a group slot past the window's highest segment costs
+    //      nothing, and the loads of a next trip are only issued when there is one (some segment with more than 12
+    //      groups: depth beyond 48).  The planes never leave the registers ----
     uint32_t c[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) c[p] = 0u;
     if (ng) {
-        for (uint32_t g0 = wv; g0 < ng; g0 += (uint32_t)kWaves * G) {
+        for (uint32_t g0 = 0; g0 < ng; g0 += (uint32_t)G) {
 #pragma unroll
             for (int j = 0; j < G; ++j) {
-                if (g0 + (uint32_t)kWaves * j < ng) bs_add4<NP>(c, rv[j]);
+                if (g0 + (uint32_t)j < ng) bs_add4<NP>(c, rv[j]);
             }
-            if (g0 + (uint32_t)kWaves * G < ng) {          // a deeper window: the next trip's groups (requested only now)
-                row_advance(rl, kWaves * G);
+            if (g0 + (uint32_t)G < ng) {                   // a deeper window: the next trip's groups (requested only now)
+                row_advance(rl, G);
 #pragma unroll
-                for (int j = 0; j < G; ++j) rv[j] = row_unit(rl, kWaves * j);
+                for (int j = 0; j < G; ++j) rv[j] = row_unit(rl, j);
             }
         }
     }
@@ -313,102 +329,115 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
         if (base >= n_cand) break;
         load_heads(base, hh);
     }
+    __syncthreads();                                       // (this wave's atomics before its reads: see the LDS comment)
 
-    if (wv != 0) {
+    // ---- final phase: depths, low-MAPQ rule, state, counts -- the lane's own 32 positions, bit i <-> position p0 + i ----
+    // qc_depth against the two depth thresholds (callable_profiler.rs:108-113), bit-sliced on the lane's own planes
+    const uint32_t ltb = bs_less_than<NP>(c, (unsigned long long)a.min_depth);
+    // qc > max_depth  <=>  !(qc < max_depth + 1); the rule is off for max_depth == 0
+    const uint32_t gtb = a.max_depth > 0u ? ~bs_less_than<NP>(c, (unsigned long long)a.max_depth + 1ull) : 0u;
+    // quality_bases (contig_profiler.rs:71): the sum of the block's 32 counts = sum over the planes of 2^p x set bits
+    unsigned long long nbits = 0;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) s_pl[wv - 1][p][lane] = c[p];
+    for (int p = 0; p < NP; ++p) nbits += (unsigned long long)__popc(c[p]) << p;
+
+    // The lane's differences: 16 packed words per array (DEEP: 32 words, re-read from LDS where they are needed), and
+    // first their sum, for the scan over the lanes.  Packed, a word is (0x8000 + d_even) | d_odd << 16 with no carry
+    // between the fields (at most 32 767 candidates without DEEP), so v_sad_u16 against 0 adds both fields of a word
+    // as unsigned 16-bit numbers: 16 of them give 2^19 + the lane's sum + 2^16 x (the negative odd fields) -- and the
+    // lane's sum lies within +-32 767: it is the low 16 bits, sign-extended.  One instruction per word, the fields are
+    // never split.  (A lane's sum may well be negative: ends without starts.)
+    constexpr int NH = DEEP ? 1 : PER / 2;                 // packed words per array that the lane holds
+    uint32_t xr[NH], xl[NH];
+    uint32_t tr = 0, tl = 0;
+    if constexpr (DEEP) {
+        xr[0] = xl[0] = 0u;
+#pragma unroll
+        for (int q = 0; q < PER / 4; ++q) {
+            const uint4 x = reinterpret_cast<const uint4 *>(s_raw)[lane * (PER / 4) + q];
+            const uint4 y = reinterpret_cast<const uint4 *>(s_low)[lane * (PER / 4) + q];
+            tr += x.x + x.y + x.z + x.w; tl += y.x + y.y + y.z + y.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < NH / 4; ++q) {
+            const uint4 x = reinterpret_cast<const uint4 *>(s_raw)[lane * (NH / 4) + q];
+            const uint4 y = reinterpret_cast<const uint4 *>(s_low)[lane * (NH / 4) + q];
+            xr[4 * q] = x.x; xr[4 * q + 1] = x.y; xr[4 * q + 2] = x.z; xr[4 * q + 3] = x.w;
+            xl[4 * q] = y.x; xl[4 * q + 1] = y.y; xl[4 * q + 2] = y.z; xl[4 * q + 3] = y.w;
+        }
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            tr = __builtin_amdgcn_sad_u16(xr[h], 0u, tr);
+            tl = __builtin_amdgcn_sad_u16(xl[h], 0u, tl);
+        }
+        tr = (uint32_t)(int32_t)(int16_t)(uint16_t)tr; tl = (uint32_t)(int32_t)(int16_t)(uint16_t)tl;
     }
-    __syncthreads();
+    // (two's complement in 32 bits, so the two scans stay separate)
+    const uint32_t offr = dpp_incl_scan_u32(tr) - tr, offl = dpp_incl_scan_u32(tl) - tl;
 
-    // ---- final phase: depths, low-MAPQ rule, state, counts (16 positions per thread) ----
-    {
-        // wave 0: the waves' planes added (a bit-sliced ripple adder per wave) and compared with the two depth
-        // thresholds (callable_profiler.rs:108-113); the other waves go on with their prefix sums meanwhile
-        unsigned long long nbits = 0;                      // set bits of the window's rows, by wave 0's lanes (-> quality_bases)
-        if (wv == 0) {
+    // raw_depth > 0, and the low-MAPQ rule (callable_profiler.rs:100-101): the two per-position tests, each a difference
+    // whose sign bit says "no", shifted into a mask by v_alignbit ({mask, d} >> 31) as the running sums walk the lane's
+    // positions upwards: position 0 ends in bit 31, one v_bfrev per mask puts it right.  No array of depths is held.
+    uint32_t covb = 0, lowb = 0, mx = 0;
+    if constexpr (!DEEP) {
+        // The fast path: the thresholds as bytes, trusted while the lane sees no depth of 255 or more (255 = never; a
+        // count is at most the depth).  raw - 1 wraps when raw == 0; low - threshold is negative when low < threshold.
+        // The byte of depth d: word d >> 2 of the table, held by that lane (a wrong lane's word beyond 255: not used).
+        // Eight positions at a time: their depths first and the eight fetches behind each other, then the tests, so
+        // that the wave waits for one round trip per eight positions and not for one per position.
+        uint32_t sr = offr, sl = offl, ncov = 0, nlow = 0;
+        constexpr int B = 8;
 #pragma unroll
-            for (int v = 1; v < kWaves; ++v) {
-                uint32_t carry = 0u;
+        for (int g = 0; g < PER; g += B) {
+            uint32_t r8[B], l8[B], t8[B];
 #pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    const uint32_t d = s_pl[v - 1][p][lane];
-                    const uint32_t s = c[p] ^ d ^ carry;
-                    carry = bs_maj(c[p], d, carry);
-                    c[p] = s;
+            for (int k = 0; k < B; ++k) {
+                const int i = g + k;
+                sr += (i & 1) ? (uint32_t)((int32_t)xr[i / 2] >> 16) : (xr[i / 2] & 0xFFFFu) - 0x8000u;
+                sl += (i & 1) ? (uint32_t)((int32_t)xl[i / 2] >> 16) : (xl[i / 2] & 0xFFFFu) - 0x8000u;
+                r8[k] = sr; l8[k] = sl;
+                t8[k] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(sr & ~3u), (int)wlut);
+            }
+#pragma unroll
+            for (int k = 0; k < B; ++k) {
+                mx = r8[k] > mx ? r8[k] : mx;
+                const uint32_t thr = __builtin_amdgcn_ubfe(t8[k], r8[k] << 3, 8u);
+                ncov = __builtin_amdgcn_alignbit(ncov, r8[k] - 1u, 31);
+                nlow = __builtin_amdgcn_alignbit(nlow, l8[k] - thr, 31);
+                if (DEBUG) {
+                    if (a.dbg_raw) a.dbg_raw[p0 + g + k] = r8[k];
+                    if (a.dbg_low) a.dbg_low[p0 + g + k] = l8[k];
                 }
             }
-            // quality_bases (contig_profiler.rs:71): the sum of the block's 32 counts = sum over the planes of 2^p x set bits
-#pragma unroll
-            for (int p = 0; p < NP; ++p) nbits += (unsigned long long)__popc(c[p]) << p;
-            s_lt[lane] = bs_less_than<NP>(c, (unsigned long long)a.min_depth);
-            // qc > max_depth  <=>  !(qc < max_depth + 1); the rule is off for max_depth == 0
-            s_gt[lane] = a.max_depth > 0u ? ~bs_less_than<NP>(c, (unsigned long long)a.max_depth + 1ull) : 0u;
-            if (DEBUG) {
-#pragma unroll
-                for (int p = 0; p < NP; ++p) s_dbg[p][lane] = c[p];
-            }
-            // the thresholds of depths 4 lane .. 4 lane + 3, four bytes in the lane's own word (requested at the top)
-            s_pool[kLutPlane * 64 + lane] = wlut;
         }
-        uint32_t vr[PER], vl[PER];
-        uint32_t sr = 0, sl = 0;
-        if (DEEP) {
-#pragma unroll
-            for (int i = 0; i < PER; ++i) {
-                sr += s_raw[tid * PER + i]; vr[i] = sr;
-                sl += s_low[tid * PER + i]; vl[i] = sl;
+        covb = ~__builtin_bitreverse32(ncov); lowb = ~__builtin_bitreverse32(nlow);
+    }
+    if (DEEP || mx >= 255u) {
+        // The general path, for the lanes that need it (the lane's positions again: its differences from LDS, two
+        // positions per step).  The same two sign bits as above, so that no test's outcome waits in a pair of scalar
+        // registers for the others: a threshold is clamped to 2^31 - 1 = never (a count is below 2^29), and so is that
+        // of a depth below min_depth_for_low_mapq; lut[0] is "never" already (build_lut fills with 0xFFFFFFFF and starts
+        // at depth 1).  A depth beyond the table takes the f64 divide (its load of the table's last entry is not used).
+        const uint32_t mdl = a.min_depth_for_low_mapq < 0x7FFFFFFFu ? a.min_depth_for_low_mapq : 0x7FFFFFFFu;
+        uint32_t sr = offr, sl = offl, ncov = 0, nlow = 0;
+        mx = 0;
+#pragma unroll 1
+        for (int h = 0; h < PER / 2; ++h) {
+            uint32_t dr[2], dl[2];
+            if (DEEP) {
+                dr[0] = s_raw[lane * PER + 2 * h]; dr[1] = s_raw[lane * PER + 2 * h + 1];
+                dl[0] = s_low[lane * PER + 2 * h]; dl[1] = s_low[lane * PER + 2 * h + 1];
+            } else {
+                const uint32_t xr = s_raw[lane * (PER / 2) + h], xl = s_low[lane * (PER / 2) + h];
+                dr[0] = (xr & 0xFFFFu) - 0x8000u; dr[1] = (uint32_t)((int32_t)xr >> 16);
+                dl[0] = (xl & 0xFFFFu) - 0x8000u; dl[1] = (uint32_t)((int32_t)xl >> 16);
             }
-        } else {
 #pragma unroll
-            for (int h = 0; h < PER / 2; ++h) {
-                const uint32_t wr = s_raw[tid * (PER / 2) + h], wl = s_low[tid * (PER / 2) + h];
-                sr += (wr & 0xFFFFu) - 0x8000u; vr[2 * h] = sr;
-                sr += (uint32_t)((int32_t)wr >> 16); vr[2 * h + 1] = sr;
-                sl += (wl & 0xFFFFu) - 0x8000u; vl[2 * h] = sl;
-                sl += (uint32_t)((int32_t)wl >> 16); vl[2 * h + 1] = sl;
-            }
-        }
-        // (a thread's sum of differences may be negative: two's complement in 32 bits, so the two scans stay separate)
-        const uint32_t ir = dpp_incl_scan_u32(sr), il = dpp_incl_scan_u32(sl);
-        // the wave's totals, for the waves behind it: in the first slot this lane has just consumed
-        constexpr int kSlot = DEEP ? PER : PER / 2;
-        if (lane == 63) { s_raw[tid * kSlot] = ir; s_low[tid * kSlot] = il; }
-        __syncthreads();
-        uint32_t offr = ir - sr, offl = il - sl;
-        for (uint32_t i = 0; i < wv; ++i) { offr += s_raw[(i * 64u + 63u) * kSlot]; offl += s_low[(i * 64u + 63u) * kSlot]; }
-        uint32_t mx = 0;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) { vr[i] += offr; vl[i] += offl; mx = vr[i] > mx ? vr[i] : mx; }
-        const uint32_t n_ok = p0 >= a.extent ? 0u : (a.extent - p0 < (uint32_t)PER ? a.extent - p0 : (uint32_t)PER);
-        // From here on the thread's PER positions are PER bits of a register: bit i <-> position p0 + i.
-        constexpr uint32_t FULL = 0xFFFFu;
-        const uint32_t okb = n_ok >= (uint32_t)PER ? FULL : ((1u << n_ok) - 1u);            // positions < extent
-        // qc_depth < min_depth, qc_depth > max_depth: PER consecutive bits of block (tid * PER) >> 5
-        const uint32_t ltb = (s_lt[(tid * PER) >> 5] >> ((tid * PER) & 31u)) & FULL;
-        const uint32_t gtb = (s_gt[(tid * PER) >> 5] >> ((tid * PER) & 31u)) & FULL;
-        // raw_depth > 0, and the low-MAPQ rule (callable_profiler.rs:100-101): the two per-position tests
-        uint32_t covb = 0, lowb = 0;
-        if (!DEEP && mx < 255u) {
-            // two instructions per test: a difference whose sign bit says "no" (raw - 1 wraps when raw == 0; low - lut
-            // is negative when low < lut: all are below 2^31), shifted into the mask by v_alignbit ({mask, d} >> 31)
-            uint32_t ncov = 0, nlow = 0;
-#pragma unroll
-            for (int i = PER - 1; i >= 0; --i) {
-                const uint32_t raw = vr[i];
-                ncov = __builtin_amdgcn_alignbit(ncov, raw - 1u, 31);
-                nlow = __builtin_amdgcn_alignbit(nlow, vl[i] - (uint32_t)s_lut[raw], 31);
-            }
-            covb = ~ncov & FULL; lowb = ~nlow & FULL;
-        } else {
-            // The same two sign bits as above, so that no test's outcome waits in a pair of scalar registers for the
-            // others: a threshold is clamped to 2^31 - 1 = never (a count is below 2^29), and so is that of a depth
-            // below min_depth_for_low_mapq; lut[0] is "never" already (build_lut fills with 0xFFFFFFFF and starts at depth
-            // 1).  A depth beyond the table takes the f64 divide (its load of the table's last entry is not used).
-            const uint32_t mdl = a.min_depth_for_low_mapq < 0x7FFFFFFFu ? a.min_depth_for_low_mapq : 0x7FFFFFFFu;
-            uint32_t ncov = 0, nlow = 0;
-#pragma unroll
-            for (int i = PER - 1; i >= 0; --i) {
-                const uint32_t raw = vr[i], low = vl[i];
+            for (int k = 0; k < 2; ++k) {
+                sr += dr[k]; sl += dl[k];
+                const uint32_t raw = sr, low = sl;
+                mx = raw > mx ? raw : mx;
                 uint32_t thr = a.lut[raw < kLutSize ? raw : kLutSize - 1u];
                 thr = thr < 0x7FFFFFFFu ? thr : 0x7FFFFFFFu;
                 thr |= (uint32_t)((int32_t)(raw - mdl) >> 31) >> 1;
@@ -419,113 +448,81 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
                 }
                 ncov = __builtin_amdgcn_alignbit(ncov, raw - 1u, 31);
                 nlow = __builtin_amdgcn_alignbit(nlow, d, 31);
-            }
-            covb = ~ncov & FULL; lowb = ~nlow & FULL;
-        }
-        // priorities of callable_profiler.rs:104-116, resolved into disjoint masks:
-        // REF_N > NO_COVERAGE > POOR_MAPPING_QUALITY > LOW_COVERAGE > EXCESSIVE_COVERAGE > CALLABLE
-        const uint32_t Nk = refn & okb, notN = ~refn & okb, covk = covb & okb;
-        const uint32_t t0 = notN & covk;
-        const uint32_t rLow = t0 & lowb, t1 = t0 & ~lowb;
-        const uint32_t rLT = t1 & ltb, t2 = t1 & ~ltb;
-        const uint32_t rGT = t2 & gtb, rC = t2 & ~gtb;
-        const uint32_t rNC = notN & ~covk;
-        uint32_t cnt[6];
-        cnt[0] = __popc(Nk); cnt[1] = __popc(rC); cnt[2] = __popc(rNC);
-        cnt[3] = __popc(rLT); cnt[4] = __popc(rGT); cnt[5] = __popc(rLow);
-        const uint32_t ncov = __popc(covk);
-        // the state (types.rs:36-43: REF_N 0, CALLABLE 1, NO_COVERAGE 2, LOW_COVERAGE 3, EXCESSIVE_COVERAGE 4,
-        // POOR_MAPPING_QUALITY 5) as three bit planes
-        const uint32_t s0 = rC | rLT | rLow, s1 = rNC | rLT, s2 = rGT | rLow;
-        auto state_at = [&](uint32_t j) -> uint32_t { return ((s0 >> j) & 1u) | (((s1 >> j) & 1u) << 1) | (((s2 >> j) & 1u) << 2); };
-        if (DEBUG) {
-#pragma unroll
-            for (int i = 0; i < PER; ++i) {
-                uint32_t qc = 0;
-                const uint32_t bit = ((tid * PER) & 31u) + (uint32_t)i;
-#pragma unroll
-                for (int p = 0; p < NP; ++p) qc |= ((s_dbg[p][(tid * PER) >> 5] >> bit) & 1u) << p;
-                if (a.dbg_raw) a.dbg_raw[p0 + i] = vr[i];
-                if (a.dbg_low) a.dbg_low[p0 + i] = vl[i];
-                if (a.dbg_qc) a.dbg_qc[p0 + i] = qc;
-                a.state[p0 + i] = (uint8_t)(((okb >> i) & 1u) ? state_at((uint32_t)i) : 0xFFu);
-            }
-        }
-        // run boundaries strictly inside the window: position p (> W) whose state differs from p-1
-        const uint32_t last_st = state_at((uint32_t)PER - 1u);
-        s_last[tid] = (uint8_t)last_st;
-        mx = dpp_wave_max_u32(mx);
-        if (lane == 0) s_wmax[wv] = mx;
-        __syncthreads();
-        const uint32_t pv = tid > 0 ? (uint32_t)s_last[tid - 1] : state_at(0u);
-        const uint32_t bnd = ((s0 ^ ((s0 << 1) | (pv & 1u))) | (s1 ^ ((s1 << 1) | ((pv >> 1) & 1u))) | (s2 ^ ((s2 << 1) | (pv >> 2)))) & okb;
-        const uint32_t nb = __popc(bnd);
-        if (!DEEP && NP == 8) {
-            // a thread's counts are <= PER = 16 and every wave total <= 1024: packed words of two 11-bit fields, one
-            // butterfly reduction each; the window's set bits (all with wave 0) are <= 255 x 2048 < 2^19
-            constexpr int NW = 5;
-            uint32_t pk[NW];
-            pk[0] = cnt[0] | (cnt[1] << 11);
-            pk[1] = cnt[2] | (cnt[3] << 11);
-            pk[2] = cnt[4] | (cnt[5] << 11);
-            pk[3] = ncov | (nb << 11);
-            pk[4] = (uint32_t)nbits;
-#pragma unroll
-            for (int q = 0; q < NW; ++q) pk[q] = dpp_wave_sum_u32(pk[q]);
-            if (lane == 0) {
-                unsigned long long *t = s_wtot[wv];
-                t[0] = pk[0] & 2047u; t[1] = pk[0] >> 11;
-                t[2] = pk[1] & 2047u; t[3] = pk[1] >> 11;
-                t[4] = pk[2] & 2047u; t[5] = pk[2] >> 11;
-                t[6] = pk[3] & 2047u; t[9] = pk[3] >> 11;
-                t[7] = pk[4];
-                t[8] = 0;
-                t[10] = 0; t[11] = 0;                    // (the reads' separable sums come from the host's walk)
-            }
-        } else {
-            unsigned long long v[10];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) v[q] = cnt[q];
-            v[6] = ncov; v[7] = nbits; v[8] = 0; v[9] = nb;
-#pragma unroll
-            for (int q = 0; q < 10; ++q) {
-                const unsigned long long r = wave_sum_u64(v[q]);
-                if (lane == 0) s_wtot[wv][q] = r;
-            }
-            if (lane == 0) { s_wtot[wv][10] = 0; s_wtot[wv][11] = 0; }
-        }
-        __syncthreads();
-        {
-            const uint32_t inc = dpp_incl_scan_u32(nb);
-            if (nb) {
-                uint32_t off = inc - nb;
-                for (uint32_t i = 0; i < wv; ++i) off += (uint32_t)s_wtot[i][9];
-                uint16_t *dst = a.runs + (size_t)w * T + off;
-                for (uint32_t m = bnd; m; m &= m - 1u) {     // (a lane has a boundary or two, rarely more)
-                    const uint32_t j = (uint32_t)__ffs((int)m) - 1u;
-                    *dst++ = (uint16_t)((tid * PER + j) | (state_at(j) << 12));
+                if (DEBUG) {
+                    if (a.dbg_raw) a.dbg_raw[p0 + 2 * h + k] = raw;
+                    if (a.dbg_low) a.dbg_low[p0 + 2 * h + k] = low;
                 }
             }
-            if (tid == 0) a.first_state[w] = (uint8_t)state_at(0u);
-            if (tid == kBlock - 1) a.last_state[w] = (uint8_t)last_st;
+        }
+        covb = ~__builtin_bitreverse32(ncov); lowb = ~__builtin_bitreverse32(nlow);
+    }
+    const uint32_t n_ok = p0 >= a.extent ? 0u : (a.extent - p0 < (uint32_t)PER ? a.extent - p0 : (uint32_t)PER);
+    const uint32_t okb = n_ok >= (uint32_t)PER ? 0xFFFFFFFFu : ((1u << n_ok) - 1u);          // positions < extent
+    // priorities of callable_profiler.rs:104-116, resolved into disjoint masks:
+    // REF_N > NO_COVERAGE > POOR_MAPPING_QUALITY > LOW_COVERAGE > EXCESSIVE_COVERAGE > CALLABLE
+    const uint32_t Nk = refn & okb, notN = ~refn & okb, covk = covb & okb;
+    const uint32_t t0 = notN & covk;
+    const uint32_t rLow = t0 & lowb, t1 = t0 & ~lowb;
+    const uint32_t rLT = t1 & ltb, t2 = t1 & ~ltb;
+    const uint32_t rGT = t2 & gtb, rC = t2 & ~gtb;
+    const uint32_t rNC = notN & ~covk;
+    // the state (types.rs:36-43: REF_N 0, CALLABLE 1, NO_COVERAGE 2, LOW_COVERAGE 3, EXCESSIVE_COVERAGE 4,
+    // POOR_MAPPING_QUALITY 5) as three bit planes
+    const uint32_t s0 = rC | rLT | rLow, s1 = rNC | rLT, s2 = rGT | rLow;
+    auto state_at = [&](uint32_t j) -> uint32_t { return ((s0 >> j) & 1u) | (((s1 >> j) & 1u) << 1) | (((s2 >> j) & 1u) << 2); };
+    if (DEBUG) {
+#pragma unroll 1
+        for (uint32_t i = 0; i < (uint32_t)PER; ++i) {
+            uint32_t qc = 0;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) qc |= ((c[p] >> i) & 1u) << p;
+            if (a.dbg_qc) a.dbg_qc[p0 + i] = qc;
+            a.state[p0 + i] = (uint8_t)(((okb >> i) & 1u) ? state_at(i) : 0xFFu);
         }
     }
-    // the window's partial: twelve 8-byte words, one per lane -- word k < 9 is the waves' total k (cnt[6], n_cov, sum_qc,
-    // sum_q), words 9 and 10 are totals 10 and 11 (sum_reflen, sum_mapq_reflen), word 11 is {n_inner = total 9, max_raw}
+    // run boundaries strictly inside the window: position p (> W) whose state differs from p-1.  The state before the
+    // lane's first position is the lane below's last; lane 0 takes its own first state (no boundary at the window's
+    // first position: the seam between windows is the tail's)
+    const uint32_t last_st = state_at((uint32_t)PER - 1u);
+    const uint32_t below = (uint32_t)__shfl_up((int)last_st, 1);
+    const uint32_t pv = lane > 0 ? below : state_at(0u);
+    const uint32_t bnd = ((s0 ^ ((s0 << 1) | (pv & 1u))) | (s1 ^ ((s1 << 1) | ((pv >> 1) & 1u))) | (s2 ^ ((s2 << 1) | (pv >> 2)))) & okb;
+    const uint32_t nb = __popc(bnd);
+    {
+        const uint32_t inc = dpp_incl_scan_u32(nb);
+        if (nb) {
+            uint16_t *dst = a.runs + (size_t)w * T + (inc - nb);
+            for (uint32_t m = bnd; m; m &= m - 1u) {         // (a lane has a boundary or two, rarely more)
+                const uint32_t j = (uint32_t)__ffs((int)m) - 1u;
+                *dst++ = (uint16_t)((lane * PER + j) | (state_at(j) << 12));
+            }
+        }
+        if (lane == 0) a.first_state[w] = (uint8_t)state_at(0u);
+        if (lane == kBlock - 1) a.last_state[w] = (uint8_t)last_st;
+    }
+    // ---- the window's partial: twelve 8-byte words, lane k writes word k -- word k < 9 is total k (cnt[6], n_cov,
+    //      sum_qc, sum_q), words 9 and 10 are sum_reflen and sum_mapq_reflen (zero, as sum_q: the reads' separable sums
+    //      come from the host's walk), word 11 is {n_inner, max_raw}.  A lane's counts are <= 32 and the window's
+    //      <= 2048: packed words of two 16-bit fields, one wave reduction each; the totals are in scalar registers ----
     static_assert(sizeof(WinPartial) == 96 && offsetof(WinPartial, sum_reflen) == 72 && offsetof(WinPartial, n_inner) == 88 &&
                   offsetof(WinPartial, max_raw) == 92, "WinPartial as twelve 8-byte words");
-    if (tid < 12u) {
-        const uint32_t q = tid < 9u ? tid : (tid == 11u ? 9u : tid + 1u);
-        unsigned long long v = 0;
+    {
+        const uint32_t pk0 = dpp_wave_sum_u32(__popc(Nk) | (__popc(rC) << 16));
+        const uint32_t pk1 = dpp_wave_sum_u32(__popc(rNC) | (__popc(rLT) << 16));
+        const uint32_t pk2 = dpp_wave_sum_u32(__popc(rGT) | (__popc(rLow) << 16));
+        const uint32_t pk3 = dpp_wave_sum_u32(__popc(covk) | (nb << 16));
+        // the window's set bits: below 2^32 up to 16 planes (65 535 x 2048 < 2^27)
+        const unsigned long long qc = NP <= 16 ? (unsigned long long)dpp_wave_sum_u32((uint32_t)nbits) : wave_sum_u64(nbits);
+        mx = dpp_wave_max_u32(mx);
+        const uint32_t f[12] = {pk0 & 0xFFFFu, pk0 >> 16, pk1 & 0xFFFFu, pk1 >> 16, pk2 & 0xFFFFu, pk2 >> 16,
+                                pk3 & 0xFFFFu, (uint32_t)qc, 0u, 0u, 0u, pk3 >> 16};
+        if (lane < 12u) {
+            uint32_t vlo = 0u;
 #pragma unroll
-        for (int i = 0; i < kWaves; ++i) v += s_wtot[i][q];
-        if (tid == 11u) {
-            uint32_t m = 0;
-#pragma unroll
-            for (int i = 0; i < kWaves; ++i) m = s_wmax[i] > m ? s_wmax[i] : m;
-            v = (unsigned long long)(uint32_t)v | ((unsigned long long)m << 32);
+            for (uint32_t k = 0; k < 12u; ++k) vlo = lane == k ? f[k] : vlo;
+            const uint32_t vhi = lane == 7u ? (uint32_t)(qc >> 32) : (lane == 11u ? mx : 0u);
+            reinterpret_cast<unsigned long long *>(a.winpart + w)[lane] = (unsigned long long)vlo | ((unsigned long long)vhi << 32);
         }
-        reinterpret_cast<unsigned long long *>(a.winpart + w)[tid] = v;
     }
 }
 
