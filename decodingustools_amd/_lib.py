@@ -325,6 +325,27 @@ class dut_ep_options(C.Structure):
                 ("min_base_quality", C.c_uint8), ("n_cycles", C.c_uint32)]
 
 
+class cl_link_result(C.Structure):
+    _fields_ = [("n_sites", C.c_size_t), ("n_pairs", C.c_size_t), ("first", C.POINTER(C.c_uint32)), ("tables", C.POINTER(C.c_uint32)),
+                ("site_counts", C.POINTER(C.c_uint32))]
+
+
+class dut_link_options(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_quality", C.c_uint8), ("filtered", C.c_int), ("exclude_flags", C.c_uint16),
+                ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8), ("max_dist", C.c_uint32), ("max_partners", C.c_uint32),
+                ("min_link_count", C.c_uint32), ("max_discord_per_10k", C.c_uint32)]
+
+
+class dut_link_params(C.Structure):
+    _fields_ = [("min_depth", C.c_uint32), ("min_link_count", C.c_uint32), ("max_discord_per_10k", C.c_uint32)]
+
+
+class dut_link_summary(C.Structure):
+    _fields_ = [("status", C.c_int), ("major_a", C.c_uint8), ("minor_a", C.c_uint8), ("major_b", C.c_uint8), ("minor_b", C.c_uint8),
+                ("depth_a", C.c_uint64), ("depth_b", C.c_uint64), ("both", C.c_uint64), ("MM", C.c_uint64), ("Mm", C.c_uint64), ("mM", C.c_uint64),
+                ("mm", C.c_uint64), ("other", C.c_uint64)]
+
+
 class dut_variants_options(C.Structure):
     _fields_ = [("filtered", C.c_int), ("has_min_base_quality", C.c_int), ("min_base_quality", C.c_uint8),
                 ("exclude_flags", C.c_uint16), ("min_alt_per_strand", C.c_uint32)]
@@ -342,6 +363,7 @@ CL_SCAN_MAX_DENSE = 1 << 20
 CL_STR_BINS, CL_STR_MAX_FLANK, CL_STR_MAX_LOCI, CL_STR_MAX_SPAN = 128, 64, 65536, 1024
 DUT_STR_UNITS_LEN = 24
 CL_EP_MAX_CYCLES = 256
+CL_LINK_CLASSES, CL_LINK_MAX_PARTNERS, CL_LINK_MAX_SITES, CL_LINK_MAX_PAIRS = 6, 15, 1 << 20, 1 << 20
 
 # every symbol the headers declare: (name, restype, argtypes)
 SYMBOLS = [
@@ -366,6 +388,8 @@ SYMBOLS = [
     ("cl_site_error_profile", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                         C.POINTER(cl_ep_result)]),
     ("cl_site_error_profile_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("cl_site_link_counts", C.c_int, [C.c_void_p, C.c_uint8, C.POINTER(cl_scan_filter), C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                      C.POINTER(cl_link_result)]),
     ("cl_debug_site_pass_bits", C.c_int, [C.POINTER(cl_site_quals), C.c_uint8, C.c_void_p, C.c_uint64]),
     # include/dut_variants.h
     ("dut_variants_annotate_ex", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,
@@ -421,6 +445,18 @@ SYMBOLS = [
     ("dut_error_profile_write", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(cl_ep_result), C.POINTER(dut_ep_options), C.c_char_p, C.c_size_t]),
     ("dut_error_profile_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(dut_ep_options), C.c_char_p,
                                           C.c_int, C.c_char_p, C.c_size_t]),
+    ("dut_link_pair_offsets", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("dut_link_measure", C.c_int, [C.POINTER(dut_ep_reads), C.c_uint32, C.POINTER(dut_link_options), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    ("dut_link_summarise", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(dut_link_params), C.POINTER(dut_link_summary)]),
+    ("dut_link_discordance_parse", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    ("dut_link_sites_parse", C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                       C.c_char_p, C.c_size_t]),
+    ("dut_link_sites_free", None, [C.POINTER(C.c_uint32)]),
+    ("dut_link_write", C.c_int, [C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(dut_link_options), C.c_char_p, C.c_size_t]),
+    ("dut_find_links_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(dut_link_options), C.c_char_p, C.c_int, C.c_char_p,
+                                       C.c_size_t]),
     ("dut_scan_classify", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_scan_classify_counts", C.c_int, [C.c_void_p, C.c_uint8, C.c_uint32, C.c_char_p]),
     ("dut_variants_annotate", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t,

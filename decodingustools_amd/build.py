@@ -22,6 +22,7 @@ HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "pileup_bytes
            os.path.join(CSRC, "depth_profile.hip.h"), os.path.join(CSRC, "depth_runs.hip.h"), os.path.join(CSRC, "site_scan.hip.h"),
            os.path.join(CSRC, "engine_base.hip.h"), os.path.join(CSRC, "site_engine.hip.h"),
            os.path.join(CSRC, "site_pass_bits.h"), os.path.join(CSRC, "site_str.hip.h"), os.path.join(CSRC, "str_walk.h"),
+           os.path.join(CSRC, "site_links.hip.h"), os.path.join(CSRC, "link_walk.h"),
            os.path.join(CSRC, "site_errors.hip.h"), os.path.join(CSRC, "ep_walk.h"),
            os.path.join(CSRC, "coverage_hook.h"),
            os.path.join(CSRC, "host_parallel.h"),

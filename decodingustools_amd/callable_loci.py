@@ -395,6 +395,27 @@ class Engine:
                                                     C.byref(r)))
         return ErrorProfile.from_c(r, kernel_ms=self.site_scan_stats()[0])
 
+    def site_link_counts(self, sites, max_dist, max_partners, min_quality, filter=None):
+        """cl_site_link_counts over the resident tile: for `sites` (0-based positions, strictly ascending) the pair set --
+        anchor i with the next sites, at most max_partners of them, no further than max_dist away -- and per pair the 6 x 6
+        table of the classes A C G T del other that one read observes at both sites; per site its six counts.  filter: None
+        for the unfiltered form, else (exclude_flags, use_base_quality) of the attachment.  A LinkResult of numpy uint32
+        arrays (copies) and the kernel's milliseconds."""
+        sites = np.ascontiguousarray(sites, np.uint32).reshape(-1)
+        r = _lib.cl_link_result()
+        self._check(self._lib.cl_site_link_counts(self._h, int(min_quality), _filter_ref(filter), _ptr(sites) if sites.shape[0] else None, sites.shape[0],
+                                                  int(max_dist), int(max_partners), C.byref(r)))
+        n, n_pairs = int(r.n_sites), int(r.n_pairs)
+        first = np.zeros(n + 1, np.uint32)
+        tables = np.zeros((n_pairs, _lib.CL_LINK_CLASSES, _lib.CL_LINK_CLASSES), np.uint32)
+        site_counts = np.zeros((n, _lib.CL_LINK_CLASSES), np.uint32)
+        C.memmove(first.ctypes.data, r.first, first.nbytes)
+        if n_pairs:
+            C.memmove(tables.ctypes.data, r.tables, tables.nbytes)
+        if n:
+            C.memmove(site_counts.ctypes.data, r.site_counts, site_counts.nbytes)
+        return LinkResult(first=first, tables=tables, site_counts=site_counts, kernel_ms=self.site_scan_stats()[0])
+
     def site_error_profile_stats(self):
         """(table kernel milliseconds, slice sum milliseconds) of the last site_error_profile."""
         a = C.c_double(); b = C.c_double()
@@ -531,6 +552,17 @@ class ErrorProfile:
     def tables_equal(self, other):
         return (all(getattr(self, k) == getattr(other, k) for k in ("start", "end", "n_cycles", "reads", "bases", "uncomparable", "ins", "ins_bases", "dels", "del_bases"))
                 and all(np.array_equal(getattr(self, k), getattr(other, k)) for k in ("total", "from5", "from3", "ins5", "ins3", "del5", "del3")))
+
+
+@dataclass
+class LinkResult:
+    """cl_link_result (include/callable_loci.h): first[i] = the CSR offset of anchor i's pairs (first[n] = n_pairs), pair
+    first[i] + (j - i - 1) being (i, j); tables[pair, ca, cb] = the reads that take part for the anchor and observe class ca
+    there and cb at the partner; site_counts[i, c] = the reads that observe class c at site i.  Classes: A C G T del other."""
+    first: np.ndarray
+    tables: np.ndarray
+    site_counts: np.ndarray
+    kernel_ms: float = 0.0
 
 
 @dataclass

@@ -1,5 +1,5 @@
 // dut-coverage -- the `coverage`, `find-y-branch` and `find-mt-branch` subcommands of the reference CLI (and this
-// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions`, `find-insertions`, `consensus`, `find-strs` and `error-profile`);
+// project's own `fingerprint` front end, `find-variants`, `find-minor-alleles`, `find-deletions`, `find-insertions`, `consensus`, `find-strs`, `error-profile` and `phase-sites`);
 // `coverage` is the default: (src/cli.rs:14-61, src/main.rs:36-70)
 // on the MI355X engine.  Same flags and defaults; BED to -o, the CoverageOutput JSON to ./summary.json.
 // -s/--summary: the HTML report (the reference's sections and numbers in this project's own markup); the
@@ -54,7 +54,10 @@ static void usage()
             "       dut-coverage find-strs <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> --loci FILE [--flank 5] [--min-depth 10]\n"
             "       [--min-quality 20] [--min-allele-fraction 0.7] [--exclude-flags MASK] [--device 0]\n"
             "       dut-coverage error-profile <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--cycles 50]\n"
-            "       [--min-quality 20] [--min-base-quality Q] [--exclude-flags MASK] [--device 0]\n");
+            "       [--min-quality 20] [--min-base-quality Q] [--exclude-flags MASK] [--device 0]\n"
+            "       dut-coverage phase-sites <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> --sites FILE [--max-dist 1000] [--max-partners 4]\n"
+            "       [--min-depth 10] [--min-quality 20] [--min-link-count 3] [--max-discordance 0.05] [--min-base-quality Q]\n"
+            "       [--exclude-flags MASK] [--device 0]\n");
 }
 
 // fingerprint (src/cli.rs:129-156, src/commands/fingerprint.rs:9-52): a k-mer MinHash sketch of every read of a
@@ -243,7 +246,7 @@ static bool cli_count32(const char *flag, const std::string &v, uint32_t &dst)
     return true;
 }
 
-// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions, consensus, find-strs, error-profile) share on the command line: the BAM, -r, -o,
+// What the scan subcommands (find-variants, find-minor-alleles, find-deletions, find-insertions, consensus, find-strs, error-profile, phase-sites) share on the command line: the BAM, -r, -o,
 // -L, --region (0-based, half open), --min-depth, --min-quality, the two filter flags, --device, -h.
 struct ScanCli {
     const char *name;
@@ -599,6 +602,55 @@ static int error_profile_main(int argc, char **argv)
                                                   c.out.c_str(), c.device, err, sizeof(err)), err);
 }
 
+static void usage_ps()
+{
+    fprintf(stderr, "Usage: dut-coverage phase-sites <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> --sites FILE [--max-dist 1000]\n"
+                    "       [--max-partners 4] [--min-depth 10] [--min-quality 20] [--min-link-count 3] [--max-discordance 0.05]\n"
+                    "       [--min-base-quality Q] [--exclude-flags MASK] [--device 0]\n"
+                    "  Whether the second alleles of two nearby sites ride on the same reads.  FILE is tab separated, column 1 the\n"
+                    "  contig, column 2 a 1-based position (the TSVs of find-variants, find-minor-alleles and find-deletions as they\n"
+                    "  are).  Every site is paired with the next --max-partners sites (1..15) within --max-dist positions; per pair\n"
+                    "  the reads that cover the first site are counted by what they show at both.  A pair is cis when at least\n"
+                    "  --min-link-count reads carry both minor alleles and at most --max-discordance (a decimal in [0, 0.4999], at\n"
+                    "  most four decimals) of the reads with a minor allele carry only one; trans when each minor allele has that\n"
+                    "  many reads without the other and as few carry both.  Q and MASK as in find-variants.  Reads only, no mates.\n");
+}
+
+// phase-sites: the joint allele counts of site pairs per read (cl_site_link_counts) and the integer rule over them.  Argument
+// errors leave with 2 before a device is opened.
+static int phase_sites_main(int argc, char **argv)
+{
+    ScanCli c = {"phase-sites", usage_ps};
+    dut_link_options o = {10, 20, 1, 0, 0, 0, 1000, 4, 3, 500};
+    std::string sites;
+    const int st = scan_cli_parse(argc, argv, c, [&](const std::string &a, auto &&next) {
+        if (a == "--sites") { sites = next(); return 1; }
+        if (a == "--max-dist" || a == "--max-partners" || a == "--min-link-count") {
+            const std::string v = next();
+            uint32_t &dst = a == "--max-dist" ? o.max_dist : a == "--max-partners" ? o.max_partners : o.min_link_count;
+            if (!cli_count32(a.c_str(), v, dst)) return -1;
+            const uint32_t most = a == "--max-partners" ? (uint32_t)CL_LINK_MAX_PARTNERS : 0xFFFFFFFFu;
+            if (dst < 1 || dst > most) { fprintf(stderr, "error: invalid value '%s' for '%s': 1..%u\n", v.c_str(), a.c_str(), most); return -1; }
+            return 1;
+        }
+        if (a == "--max-discordance") {
+            const std::string v = next();
+            char why[128] = {0};
+            if (dut_link_discordance_parse(v.c_str(), &o.max_discord_per_10k, why, sizeof(why)) == CL_OK) return 1;
+            fprintf(stderr, "error: invalid value '%s' for '--max-discordance': %s\n", v.c_str(), why);
+            return -1;
+        }
+        return 0;
+    });
+    if (st >= 0) return st;
+    if (sites.empty()) { fprintf(stderr, "error: phase-sites needs '--sites <FILE>'\n"); usage_ps(); return 2; }
+    if (c.has_region) { fprintf(stderr, "error: phase-sites takes no '--region'\n"); usage_ps(); return 2; }
+    o.min_depth = (uint32_t)c.min_depth; o.min_quality = (uint8_t)c.min_quality;
+    c.filter_into(o);
+    char err[1024] = {0};
+    return scan_cli_leave(dut_find_links_files(c.bam.c_str(), c.ref.c_str(), c.contig.c_str(), sites.c_str(), &o, c.out.c_str(), c.device, err, sizeof(err)), err);
+}
+
 // DUT_TIMING=1: the wall clock (CLOCK_REALTIME, seconds) at the start of main and right before the process leaves, so
 // that a harness that started the tool can tell what the loader took before main and what the exit took after it
 static void stamp(const char *what)
@@ -623,6 +675,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "consensus")) return consensus_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-strs")) return find_strs_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "error-profile")) return error_profile_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "phase-sites")) return phase_sites_main(argc, argv);
     cl_options opt = {4, 500, 10, 20, 10, 1, 0.1};      // src/cli.rs:34-60
     std::string bam, ref, out = "callable_regions.bed", summary = "summary.html";
     std::vector<const char *> contigs;

@@ -1,8 +1,8 @@
 // site_engine.hip.h -- the site engine (config 5; a textual part of callable_loci.hip's translation unit): the sparse
 // site pileup k_site_pileup with its host side (cl_site_upload / cl_site_run / cl_site_pileup), the host side of the
 // dense scans of site_scan.hip.h (cl_site_scan*, cl_site_attach_quals) and their entry points, the repeat lengths of
-// site_str.hip.h (cl_site_str_lengths) and the error profile of site_errors.hip.h (cl_site_error_profile), which it
-// includes.  Of a context it uses what EngineBase holds and its own SiteResident.
+// site_str.hip.h (cl_site_str_lengths), the error profile of site_errors.hip.h (cl_site_error_profile) and the linked
+// sites of site_links.hip.h (cl_site_link_counts), which it includes.  Of a context it uses what EngineBase holds and its own SiteResident.
 #pragma once
 
 #include "kernels.hip.h"
@@ -179,6 +179,10 @@ struct SiteResident {
     std::vector<uint64_t> ep_host, ep_tab;
     KernelTimer t_ep_sum;
     double ep_sum_ms = 0.0;
+    // cl_site_link_counts (site_links.hip.h): the sites and pair offsets as sent, the tables and site counts, on the device
+    // and back
+    DevBuf<uint32_t> lk_sites, lk_first, lk_tables, lk_counts;
+    std::vector<uint32_t> link_first, link_tables, link_counts;
     // the last cl_site_pileup / cl_site_run and the last cl_site_scan* of either form: the kernels' duration and their
     // algorithmic bytes; the candidates of the last cl_site_scan, cl_site_scan_ex, cl_site_scan_minor and cl_site_scan_dels
     KernelTimer t_pileup, t_scan;
@@ -195,6 +199,7 @@ struct SiteResident {
         q_pass.release(); q_flag.release(); sx_cand.release(); sx_amb.release(); sx_hist.release(); sm_cand.release(); sd_cand.release();
         si_cand.release(); si_site.release(); si_obs.release(); si_found.release(); sk_cons.release();
         st_loci.release(); st_hist.release(); st_partial.release(); ep_part.release(); ep_sum.release();
+        lk_sites.release(); lk_first.release(); lk_tables.release(); lk_counts.release();
         rec.release(); seq.release(); cig.release(); p0.release(); ix.release(); hist.release(); bk.release(); base.release();
         sc_end.release(); sc_wfirst.release(); sc_wlast.release(); sc_dense.release(); sc_ref.release(); sc_cls.release(); sc_cand.release();
         resident = false; scan_indexed = false;
@@ -977,6 +982,7 @@ template <class F> static cl_status site_entry(cl_ctx *h, F &&f)
 
 #include "site_str.hip.h"
 #include "site_errors.hip.h"
+#include "site_links.hip.h"
 
 extern "C" {
 

@@ -10,7 +10,9 @@
 // `find-strs`: the host route of cl_site_str_lengths over str_walk.h (dut_str_measure), the rule that turns a length
 // histogram into an allele, the unit notation, the loci file's parser, the TSV, and dut_find_strs_files.  And for
 // `error-profile`: the host route of cl_site_error_profile over ep_walk.h (dut_error_profile_measure), the TSV, and
-// dut_error_profile_files.
+// dut_error_profile_files.  And for `phase-sites`: the host route of cl_site_link_counts over link_walk.h
+// (dut_link_measure), the integer rule that names a pair cis or trans, the sites file's parser, the TSV, and
+// dut_find_links_files.
 #include "../../include/dut_variants.h"
 #include "../../include/dut_report.h"
 
@@ -26,6 +28,7 @@
 #include "host_parallel.h"
 #include "str_walk.h"
 #include "ep_walk.h"
+#include "link_walk.h"
 
 namespace {
 
@@ -397,7 +400,7 @@ int dut_scan_classify_counts(const uint32_t counts5[5], uint8_t ref_byte, uint32
 }
 
 // decimal text to parts per 10 000, exactly; the value in [1, max_per_10k], `range` naming that interval in the message
-static int fraction_parse(const char *text, uint32_t *per_10k, uint32_t max_per_10k, const char *range, char *err, size_t err_len)
+static int fraction_parse(const char *text, uint32_t *per_10k, uint32_t max_per_10k, const char *range, char *err, size_t err_len, uint32_t min_per_10k = 1)
 {
     if (per_10k) *per_10k = 0;
     if (!text || !per_10k) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
@@ -410,7 +413,7 @@ static int fraction_parse(const char *text, uint32_t *per_10k, uint32_t max_per_
     if (n_frac > 4) { set_err(err, err_len, "at most four decimals"); return CL_ERR_INVALID; }
     for (int k = n_frac; k < 4; ++k) frac *= 10;
     const uint64_t v = whole * 10000 + frac;
-    if (v < 1 || v > max_per_10k) { set_err(err, err_len, std::string("the fraction must lie in ") + range); return CL_ERR_INVALID; }
+    if (v < min_per_10k || v > max_per_10k) { set_err(err, err_len, std::string("the fraction must lie in ") + range); return CL_ERR_INVALID; }
     *per_10k = (uint32_t)v;
     return CL_OK;
 }
@@ -1326,6 +1329,297 @@ int dut_error_profile_files(const char *bam_path, const char *fasta_path, const 
         rc = cl_site_error_profile(F.ctx.get(), opt->min_quality, &f, opt->n_cycles, F.bases, F.blen, start, end, &res);
         if (rc != CL_OK) { F.engine_err(err, err_len, "the error profile failed"); return rc; }
         return dut_error_profile_write(output_path, contig, &res, opt, err, err_len);
+    });
+}
+
+// ---- phase-sites ----
+namespace {
+
+static_assert(CL_LINK_CLASSES == CL_LINK_WALK_CLASSES && CL_LINK_MAX_PARTNERS == CL_LINK_WALK_MAX_PARTNERS, "link_walk.h packs the observations of cl_link_result");
+
+// the host's source of link_observe_read: the stored bases and quality values of read r
+struct LinkHostSource {
+    const dut_ep_reads &R;
+    uint64_t r;
+    bool use_bq;
+    uint8_t thr;
+    uint32_t code(uint32_t q) const
+    {
+        const uint64_t bi = R.seq_off[r] + q;
+        const uint32_t byte = R.seq4[bi >> 1];
+        return (bi & 1u) ? (byte & 15u) : (byte >> 4);
+    }
+    bool passes(uint32_t q) const
+    {
+        if (!use_bq) return true;
+        const uint64_t nq = R.qual_off[r + 1] - R.qual_off[r];
+        return q >= nq || R.qual[R.qual_off[r] + q] >= thr;
+    }
+};
+
+bool link_options_ok(const dut_link_options &o, char *err, size_t err_len)
+{
+    char b[96] = {0};
+    if (o.min_depth == 0) snprintf(b, sizeof(b), "min_depth must be at least 1");
+    else if (o.max_dist == 0) snprintf(b, sizeof(b), "max_dist must be at least 1");
+    else if (o.max_partners < 1 || o.max_partners > CL_LINK_MAX_PARTNERS) snprintf(b, sizeof(b), "max_partners must lie in 1..%u", (unsigned)CL_LINK_MAX_PARTNERS);
+    else if (o.min_link_count == 0) snprintf(b, sizeof(b), "min_link_count must be at least 1");
+    else if (o.max_discord_per_10k > 4999) snprintf(b, sizeof(b), "max_discord_per_10k must lie in 0..4999");
+    else return true;
+    set_err(err, err_len, b);
+    return false;
+}
+
+// strictly ascending?  the index of the first site that is not, 0 when all are
+size_t link_unsorted_at(const uint32_t *sites, size_t n)
+{
+    for (size_t i = 1; i < n; ++i) if (sites[i] <= sites[i - 1]) return i;
+    return 0;
+}
+
+const char *const LINK_ALLELE[] = {"A", "C", "G", "T", "del"};
+const char *const LINK_STATUS[] = {"low_depth", "cis", "trans", "unresolved"};
+
+} // namespace
+
+int dut_link_discordance_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len)
+{
+    return fraction_parse(text, per_10k, 4999, "[0, 0.4999]", err, err_len, 0);
+}
+
+int dut_link_pair_offsets(const uint32_t *sites, size_t n_sites, uint32_t max_dist, uint32_t max_partners, uint32_t *first, uint64_t *n_pairs)
+{
+    if (n_pairs) *n_pairs = 0;
+    if ((n_sites && !sites) || !n_pairs || max_dist == 0 || max_partners < 1 || max_partners > CL_LINK_MAX_PARTNERS) return CL_ERR_INVALID;
+    if (link_unsorted_at(sites, n_sites)) return CL_ERR_INVALID;
+    uint64_t at = 0;
+    for (size_t i = 0; i < n_sites; ++i) {
+        if (first) first[i] = (uint32_t)std::min<uint64_t>(at, 0xFFFFFFFFull);
+        at += dut::link_partner_count(sites, n_sites, i, max_dist, max_partners);
+    }
+    if (first) first[n_sites] = (uint32_t)std::min<uint64_t>(at, 0xFFFFFFFFull);
+    *n_pairs = at;
+    return CL_OK;
+}
+
+int dut_link_measure(const dut_ep_reads *reads, uint32_t contig_len, const dut_link_options *opt, const uint32_t *sites, size_t n_sites,
+                     uint32_t *first, uint32_t *tables, uint32_t *site_counts)
+{
+    return no_throw(nullptr, 0, [&]() -> int {
+        if (!reads || !opt || !first || (n_sites && (!sites || !site_counts))) return CL_ERR_INVALID;
+        const dut_ep_reads &R = *reads;
+        const bool filtered = opt->filtered != 0, use_bq = filtered && opt->has_min_base_quality;
+        if (n_sites > CL_LINK_MAX_SITES) return CL_ERR_INVALID;
+        uint64_t n_pairs = 0;
+        if (dut_link_pair_offsets(sites, n_sites, opt->max_dist, opt->max_partners, first, &n_pairs) != CL_OK || n_pairs > CL_LINK_MAX_PAIRS) return CL_ERR_INVALID;
+        if (n_pairs && !tables) return CL_ERR_INVALID;
+        if (n_sites && sites[n_sites - 1] >= contig_len) return CL_ERR_INVALID;
+        if (R.n_reads > 0xFFFFFFF0ull) return CL_ERR_INVALID;
+        if (R.n_reads && (!R.pos || !R.mapq || !R.cigar_off || !R.seq_off || (filtered && !R.flag) || (use_bq && !R.qual_off))) return CL_ERR_INVALID;
+        for (uint64_t r = 0; r < R.n_reads; ++r)
+            if (R.cigar_off[r + 1] < R.cigar_off[r] || R.seq_off[r + 1] < R.seq_off[r] || (use_bq && R.qual_off[r + 1] < R.qual_off[r])) return CL_ERR_INVALID;
+        if (R.n_reads && ((R.cigar_off[R.n_reads] > R.cigar_off[0] && !R.cigar) || (R.seq_off[R.n_reads] > R.seq_off[0] && !R.seq4) ||
+                          (use_bq && R.qual_off[R.n_reads] > R.qual_off[0] && !R.qual))) return CL_ERR_INVALID;
+        // the reads of an anchor: per read its reference end (0: it never takes part), per window of kWin positions the range
+        // of the reads that overlap it -- wider for an unsorted tile, exact all the same
+        constexpr uint32_t kWin = 1024;
+        const size_t n_win = ((size_t)contig_len + kWin - 1) / kWin;
+        std::vector<uint32_t> rend(R.n_reads, 0), wfirst(n_win + 1, 0xFFFFFFFFu), wlast(n_win + 1, 0);
+        for (uint64_t r = 0; r < R.n_reads; ++r) {
+            const uint32_t x = (uint32_t)R.pos[r];
+            if (x >= contig_len) continue;
+            uint64_t span = 0;
+            for (uint32_t k = R.cigar_off[r]; k < R.cigar_off[r + 1]; ++k) { const uint32_t c = R.cigar[k]; span += ((0x18Du >> (c & 15u)) & 1u) ? (c >> 4) : 0u; }
+            if (!span) continue;
+            const uint64_t xe = (uint64_t)x + span;
+            rend[r] = xe > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)xe;
+            const uint32_t last_p = std::min(rend[r], contig_len) - 1u;
+            for (uint32_t w = x / kWin; w <= last_p / kWin; ++w) { wfirst[w] = std::min(wfirst[w], (uint32_t)r); wlast[w] = std::max(wlast[w], (uint32_t)r + 1u); }
+        }
+        dut::parallel_for(n_sites, 16, [&](size_t i) {
+            const uint32_t a = sites[i], n_part = first[i + 1] - first[i];
+            uint32_t *cnt = site_counts + i * CL_LINK_CLASSES;
+            uint32_t *tab = n_part ? tables + (size_t)first[i] * 36 : nullptr;
+            memset(cnt, 0, CL_LINK_CLASSES * 4);
+            if (n_part) memset(tab, 0, (size_t)n_part * 36 * 4);
+            for (uint32_t r = wfirst[a / kWin]; r < wlast[a / kWin]; ++r) {
+                if (R.mapq[r] < opt->min_quality || rend[r] <= a || (uint32_t)R.pos[r] > a) continue;
+                if (filtered && (R.flag[r] & opt->exclude_flags)) continue;
+                const uint64_t L = R.seq_off[r + 1] - R.seq_off[r];
+                const LinkHostSource src{R, r, use_bq, opt->min_base_quality};
+                const uint64_t obs = dut::link_observe_read((uint32_t)R.pos[r], R.cigar + R.cigar_off[r], R.cigar_off[r + 1] - R.cigar_off[r],
+                                                            (uint32_t)std::min<uint64_t>(L, 0xFFFFFFFFull), sites + i, n_part + 1u, src);
+                const uint32_t ca = dut::link_obs(obs, 0);
+                if (ca == LINK_NONE) continue;
+                cnt[ca] += 1u;
+                for (uint32_t j = 1; j <= n_part; ++j) {
+                    const uint32_t cb = dut::link_obs(obs, j);
+                    if (cb != LINK_NONE) tab[(size_t)(j - 1u) * 36 + 6u * ca + cb] += 1u;
+                }
+            }
+        });
+        return CL_OK;
+    });
+}
+
+// cis and trans exclude each other.  cis asks mm >= 1 and 10000 (Mm + mM) <= d m; trans asks Mm, mM >= 1 and 10000 mm <= d m,
+// with m = Mm + mM + mm >= 1 in both.  If both held, their sum would give 10000 m <= 2 d m, that is d >= 5000: with
+// d = max_discord_per_10k <= 4999 it cannot.
+int dut_link_summarise(const uint32_t *site_counts_a, const uint32_t *site_counts_b, const uint32_t *table, const dut_link_params *params, dut_link_summary *out)
+{
+    if (!site_counts_a || !site_counts_b || !table || !params || !out) return CL_ERR_INVALID;
+    if (params->min_depth == 0 || params->min_link_count == 0 || params->max_discord_per_10k > 4999) return CL_ERR_INVALID;
+    auto two = [](const uint32_t *c, uint8_t &major, uint8_t &minor) {
+        major = 0;
+        for (uint8_t k = 1; k < 5; ++k) if (c[k] > c[major]) major = k;          // the first among equals
+        minor = major == 0 ? 1 : 0;
+        for (uint8_t k = 0; k < 5; ++k) if (k != major && c[k] > c[minor]) minor = k;
+    };
+    memset(out, 0, sizeof(*out));
+    two(site_counts_a, out->major_a, out->minor_a);
+    two(site_counts_b, out->major_b, out->minor_b);
+    for (int k = 0; k < CL_LINK_CLASSES; ++k) { out->depth_a += site_counts_a[k]; out->depth_b += site_counts_b[k]; }
+    for (int k = 0; k < 36; ++k) out->both += table[k];
+    out->MM = table[6 * out->major_a + out->major_b]; out->Mm = table[6 * out->major_a + out->minor_b];
+    out->mM = table[6 * out->minor_a + out->major_b]; out->mm = table[6 * out->minor_a + out->minor_b];
+    const uint64_t n4 = out->MM + out->Mm + out->mM + out->mm, m = out->Mm + out->mM + out->mm;
+    const uint64_t d = params->max_discord_per_10k, k = params->min_link_count;     // (counts below 2^32: every product fits 64 bits)
+    out->other = out->both - n4;
+    out->status = n4 < params->min_depth ? DUT_LINK_LOW_DEPTH
+                : (out->mm >= k && 10000ull * (out->Mm + out->mM) <= d * m) ? DUT_LINK_CIS
+                : (out->Mm >= k && out->mM >= k && 10000ull * out->mm <= d * m) ? DUT_LINK_TRANS : DUT_LINK_UNRESOLVED;
+    return CL_OK;
+}
+
+int dut_link_sites_parse(const char *path, const char *contig, uint32_t **sites, size_t *n_sites, size_t *n_skipped, char *err, size_t err_len)
+{
+    if (sites) *sites = nullptr;
+    if (n_sites) *n_sites = 0;
+    if (n_skipped) *n_skipped = 0;
+    return no_throw(err, err_len, [&]() -> int {
+        if (!path || !contig || !sites || !n_sites || !n_skipped) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        FILE *f = fopen(path, "rb");
+        if (!f) { set_err(err, err_len, std::string("cannot read the sites file ") + path); return CL_ERR_INVALID; }
+        std::string text;
+        char buf[65536];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got);
+        const bool bad = ferror(f) != 0;
+        fclose(f);
+        if (bad) { set_err(err, err_len, std::string("cannot read the sites file ") + path); return CL_ERR_INVALID; }
+        std::vector<uint32_t> out;
+        size_t skipped = 0, line_no = 0;
+        for (size_t at = 0; at < text.size();) {
+            size_t nl = text.find('\n', at);
+            if (nl == std::string::npos) nl = text.size();
+            std::string line = text.substr(at, nl - at);
+            at = nl + 1;
+            ++line_no;
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty() || line[0] == '#') continue;
+            auto malformed = [&](const char *why) {
+                set_err(err, err_len, std::string(path) + ": line " + std::to_string(line_no) + ": " + why);
+                return CL_ERR_INVALID;
+            };
+            const size_t t1 = line.find('\t');
+            if (t1 == std::string::npos) return malformed("fewer than two tab-separated columns (contig position)");
+            const size_t t2 = line.find('\t', t1 + 1);
+            const std::string name = line.substr(0, t1), num = line.substr(t1 + 1, t2 == std::string::npos ? std::string::npos : t2 - t1 - 1);
+            uint32_t pos1 = 0;
+            if (name.empty()) return malformed("an empty contig");
+            if (!str_number(num, pos1) || pos1 == 0) return malformed("the position is not a 1-based decimal number below 2^32");
+            if (name != contig) { ++skipped; continue; }
+            out.push_back(pos1 - 1u);
+        }
+        std::sort(out.begin(), out.end());
+        out.erase(std::unique(out.begin(), out.end()), out.end());
+        if (!out.empty()) {
+            uint32_t *p = (uint32_t *)malloc(out.size() * sizeof(uint32_t));
+            if (!p) { set_err(err, err_len, "out of memory"); return CL_ERR_NOMEM; }
+            memcpy(p, out.data(), out.size() * sizeof(uint32_t));
+            *sites = p;
+        }
+        *n_sites = out.size(); *n_skipped = skipped;
+        return CL_OK;
+    });
+}
+
+void dut_link_sites_free(uint32_t *sites) { free(sites); }
+
+int dut_link_write(const char *path, const char *contig, const uint32_t *sites, size_t n_sites, size_t n_skipped, const uint32_t *first,
+                   const uint32_t *tables, const uint32_t *site_counts, const dut_link_options *opt, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&]() -> int {
+        if (!path || !contig || !opt || !first || (n_sites && (!sites || !site_counts))) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (!link_options_ok(*opt, err, err_len)) return CL_ERR_INVALID;
+        uint64_t n_pairs = 0;
+        std::vector<uint32_t> own(n_sites + 1);
+        if (dut_link_pair_offsets(sites, n_sites, opt->max_dist, opt->max_partners, own.data(), &n_pairs) != CL_OK) {
+            set_err(err, err_len, "the sites must be strictly ascending"); return CL_ERR_INVALID;
+        }
+        if (memcmp(own.data(), first, (n_sites + 1) * 4) != 0) { set_err(err, err_len, "first is not the pair set of these sites under max_dist and max_partners"); return CL_ERR_INVALID; }
+        if (n_pairs && !tables) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        const dut_link_params prm = {opt->min_depth, opt->min_link_count, opt->max_discord_per_10k};
+        uint64_t n_class[4] = {0, 0, 0, 0};
+        std::string body;
+        char b[768];
+        for (size_t i = 0; i < n_sites; ++i)
+            for (uint32_t p = first[i]; p < first[i + 1]; ++p) {
+                const size_t j = i + 1 + (p - first[i]);
+                dut_link_summary u;
+                if (dut_link_summarise(site_counts + i * 6, site_counts + j * 6, tables + (size_t)p * 36, &prm, &u) != CL_OK) { set_err(err, err_len, "summarising a pair failed"); return CL_ERR_INVALID; }
+                n_class[u.status] += 1;
+                snprintf(b, sizeof(b), "%s\t%llu\t%llu\t%u\t%s\t%s\t%s\t%s\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s\n", contig,
+                         (unsigned long long)sites[i] + 1ull, (unsigned long long)sites[j] + 1ull, sites[j] - sites[i], LINK_ALLELE[u.major_a], LINK_ALLELE[u.minor_a],
+                         LINK_ALLELE[u.major_b], LINK_ALLELE[u.minor_b], (unsigned long long)u.depth_a, (unsigned long long)u.depth_b, (unsigned long long)u.both,
+                         (unsigned long long)u.MM, (unsigned long long)u.Mm, (unsigned long long)u.mM, (unsigned long long)u.mm, (unsigned long long)u.other,
+                         LINK_STATUS[u.status]);
+                body += b;
+            }
+        char q[8] = ".";
+        if (opt->has_min_base_quality) snprintf(q, sizeof(q), "%u", (unsigned)opt->min_base_quality);
+        std::string s;
+        snprintf(b, sizeof(b), "##contig=%s\n##sites=%llu\n##sites_skipped=%llu\n##pairs=%llu\n##max_dist=%u\n##max_partners=%u\n##min_depth=%u\n##min_quality=%u\n"
+                               "##min_base_quality=%s\n##exclude_flags=0x%04x\n##min_link_count=%u\n##max_discordance=%.4f\n"
+                               "##low_depth=%llu\n##cis=%llu\n##trans=%llu\n##unresolved=%llu\n",
+                 contig, (unsigned long long)n_sites, (unsigned long long)n_skipped, (unsigned long long)n_pairs, opt->max_dist, opt->max_partners, opt->min_depth,
+                 (unsigned)opt->min_quality, q, (unsigned)opt->exclude_flags, opt->min_link_count, (double)opt->max_discord_per_10k / 10000.0,
+                 (unsigned long long)n_class[0], (unsigned long long)n_class[1], (unsigned long long)n_class[2], (unsigned long long)n_class[3]);
+        s += b;
+        s += "#contig\tpos_a\tpos_b\tdist\tmajor_a\tminor_a\tmajor_b\tminor_b\tdepth_a\tdepth_b\tboth\tMM\tMm\tmM\tmm\tother\tstatus\n";
+        s += body;
+        return write_file(path, s, err, err_len);
+    });
+}
+
+int dut_find_links_files(const char *bam_path, const char *fasta_path, const char *contig, const char *sites_path, const dut_link_options *opt,
+                         const char *output_path, int device_id, char *err, size_t err_len)
+{
+    return no_throw(err, err_len, [&]() -> int {
+        if (!bam_path || !fasta_path || !contig || !sites_path || !output_path || !opt) { set_err(err, err_len, "null argument"); return CL_ERR_INVALID; }
+        if (!link_options_ok(*opt, err, err_len)) return CL_ERR_INVALID;
+        uint32_t *sp = nullptr; size_t n = 0, skipped = 0;
+        int rc = dut_link_sites_parse(sites_path, contig, &sp, &n, &skipped, err, err_len);
+        if (rc != CL_OK) return rc;
+        std::unique_ptr<uint32_t, decltype(&dut_link_sites_free)> own(sp, dut_link_sites_free);
+        ScanFiles F;
+        uint32_t start = 0, end = 0;
+        if ((rc = scan_files_open(F, bam_path, fasta_path, contig, 0, start, end, err, err_len)) != CL_OK) return rc;
+        if (n > CL_LINK_MAX_SITES) { set_err(err, err_len, std::to_string(n) + " sites, more than " + std::to_string(CL_LINK_MAX_SITES)); return CL_ERR_INVALID; }
+        if (n && sp[n - 1] >= F.contig_len) {
+            set_err(err, err_len, "site " + std::to_string((unsigned long long)sp[n - 1] + 1ull) + " lies beyond contig " + contig + " (" + std::to_string(F.contig_len) + " bases)");
+            return CL_ERR_INVALID;
+        }
+        uint64_t n_pairs = 0;
+        if ((rc = dut_link_pair_offsets(sp, n, opt->max_dist, opt->max_partners, nullptr, &n_pairs)) != CL_OK) { set_err(err, err_len, "the pair set could not be formed"); return rc; }
+        if (n_pairs > CL_LINK_MAX_PAIRS) { set_err(err, err_len, std::to_string(n_pairs) + " pairs, more than " + std::to_string(CL_LINK_MAX_PAIRS) + ": lower --max-dist or --max-partners"); return CL_ERR_INVALID; }
+        const FilterOptions flt = {opt->has_min_base_quality, opt->min_base_quality, opt->exclude_flags};
+        cl_scan_filter f;
+        if ((rc = scan_files_resident(F, contig, device_id, &flt, f, []() {}, []() { return true; }, err, err_len)) != CL_OK) return rc;
+        cl_link_result res;
+        rc = cl_site_link_counts(F.ctx.get(), opt->min_quality, &f, sp, n, opt->max_dist, opt->max_partners, &res);
+        if (rc != CL_OK) { F.engine_err(err, err_len, "counting the linked sites failed"); return rc; }
+        return dut_link_write(output_path, contig, sp, n, skipped, res.first, res.tables, res.site_counts, opt, err, err_len);
     });
 }
 

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from .callable_loci import (DEL_CANDIDATE, INS_CANDIDATE, INS_OBS, MINOR_CANDIDATE, SCAN_CANDIDATE, SCAN_CANDIDATE_EX, ConsResult, DelResult,
-                            EngineError, ErrorProfile, InsResult, MinorResult, ScanResult, StrResult, _ptr)
+                            EngineError, ErrorProfile, InsResult, LinkResult, MinorResult, ScanResult, StrResult, _ptr)
 from .haplogroup import FTDNA, YDNA, HaplogroupTree
 
 LOW_DEPTH, MIXED, UNCOMPARABLE, MATCH, VARIANT, UNDETERMINED = range(6)
@@ -26,6 +26,8 @@ CONS_NOTES = ("", "anchor_deleted", "too_long", "no_allele")
 CLASS_NAMES = ("low_depth", "mixed", "uncomparable", "match", "variant", "undetermined")
 STR_LOW_DEPTH, STR_MIXED, STR_CALLED = range(3)
 STR_STATUS_NAMES = ("low_depth", "mixed", "called")
+LINK_LOW_DEPTH, LINK_CIS, LINK_TRANS, LINK_UNRESOLVED = range(4)
+LINK_STATUS_NAMES = ("low_depth", "cis", "trans", "unresolved")
 
 
 def _classify(fn, counts, width, ref_byte, min_depth) -> Tuple[int, str]:
@@ -598,3 +600,119 @@ def error_profile(bam_file: str, reference_file: str, contig: str, output_file: 
     region: (start, end), 0-based half open, or None for the whole contig."""
     opt = _ep_options(cycles, min_quality, exclude_flags, min_base_quality)
     _find_files(_lib.load().dut_error_profile_files, bam_file, reference_file, contig, region, C.byref(opt), output_file.encode(), device_id)
+
+
+def link_discordance_parse(text: str) -> int:
+    """dut_link_discordance_parse: decimal text in [0, 0.4999] with at most four decimals to parts per 10 000, exactly."""
+    return _fraction_parse(_lib.load().dut_link_discordance_parse, text)
+
+
+def _link_options(min_depth=10, min_quality=20, exclude_flags=0, min_base_quality=None, max_dist=1000, max_partners=4, min_link_count=3,
+                  max_discordance="0.05", filtered=True):
+    if not 0 <= int(min_quality) <= 255:
+        raise ValueError("min_quality: 0..255")
+    if not 0 <= int(exclude_flags) <= 0xFFFF:
+        raise ValueError("exclude_flags: 0..65535")
+    if min_base_quality is not None and not 0 <= int(min_base_quality) <= 255:
+        raise ValueError("min_base_quality: 0..255")
+    for name, v in (("min_depth", min_depth), ("max_dist", max_dist), ("max_partners", max_partners), ("min_link_count", min_link_count)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name}: 0..2^32-1")
+    return _lib.dut_link_options(int(min_depth), int(min_quality), 1 if filtered else 0, int(exclude_flags), 0 if min_base_quality is None else 1,
+                                 int(min_base_quality or 0), int(max_dist), int(max_partners), int(min_link_count), link_discordance_parse(str(max_discordance)))
+
+
+def link_pair_offsets(sites, max_dist: int, max_partners: int) -> np.ndarray:
+    """dut_link_pair_offsets: first (n + 1) of the pair set of strictly ascending sites; first[n] is the number of pairs."""
+    sites = np.ascontiguousarray(sites, np.uint32).reshape(-1)
+    first = np.zeros(sites.shape[0] + 1, np.uint32)
+    n_pairs = C.c_uint64()
+    st = _lib.load().dut_link_pair_offsets(_ptr(sites) if sites.shape[0] else None, sites.shape[0], int(max_dist), int(max_partners), _ptr(first), C.byref(n_pairs))
+    if st != 0:
+        raise EngineError(st, "dut_link_pair_offsets refused its arguments")
+    return first
+
+
+def link_measure(rec, contig_len: int, sites, max_dist: int, max_partners: int, min_quality: int, exclude_flags: Optional[int] = None,
+                 min_base_quality: Optional[int] = None) -> LinkResult:
+    """dut_link_measure: what Engine.site_link_counts returns, from the records on the host (no device needed).
+    exclude_flags=None: the unfiltered form; a mask (0 included): the filtered form, with min_base_quality (None: every
+    base passes) taken over the records' quality values."""
+    sites = np.ascontiguousarray(sites, np.uint32).reshape(-1)
+    n = sites.shape[0]
+    first = link_pair_offsets(sites, max_dist, max_partners)
+    tables = np.zeros((int(first[n]), _lib.CL_LINK_CLASSES, _lib.CL_LINK_CLASSES), np.uint32)
+    site_counts = np.zeros((n, _lib.CL_LINK_CLASSES), np.uint32)
+    keep = [np.ascontiguousarray(rec.pos, np.int32), np.ascontiguousarray(rec.flag, np.uint16), np.ascontiguousarray(rec.mapq, np.uint8),
+            np.ascontiguousarray(rec.cigar_off, np.uint32), np.ascontiguousarray(rec.cigar, np.uint32),
+            np.ascontiguousarray(rec.seq_off if rec.seq_off is not None else np.zeros(rec.n + 1, np.uint64), np.uint64),
+            np.ascontiguousarray(rec.seq4 if rec.seq4 is not None else np.zeros(0, np.uint8), np.uint8),
+            np.ascontiguousarray(rec.qual_off, np.uint64), np.ascontiguousarray(rec.qual, np.uint8)]
+    reads = _lib.dut_ep_reads(rec.n, *[a.ctypes.data if a.shape[0] else None for a in keep])
+    opt = _link_options(1, min_quality, exclude_flags or 0, min_base_quality if exclude_flags is not None else None, max_dist, max_partners,
+                        filtered=exclude_flags is not None)
+    st = _lib.load().dut_link_measure(C.byref(reads), int(contig_len), C.byref(opt), _ptr(sites) if n else None, n, _ptr(first),
+                                      _ptr(tables) if tables.shape[0] else None, _ptr(site_counts) if n else None)
+    if st != 0:
+        raise EngineError(st, "dut_link_measure refused its arguments")
+    return LinkResult(first=first, tables=tables, site_counts=site_counts)
+
+
+def link_summarise(site_counts_a, site_counts_b, table, min_depth: int = 10, min_link_count: int = 3, max_discord_per_10k: int = 500) -> dict:
+    """dut_link_summarise: one pair from its two sites' counts and its table -- status (LINK_LOW_DEPTH, LINK_CIS, LINK_TRANS,
+    LINK_UNRESOLVED), the major and minor class of each site (0..4: A C G T del), depth_a, depth_b, both, MM, Mm, mM, mm, other."""
+    a = np.ascontiguousarray(site_counts_a, np.uint32).reshape(-1)
+    b = np.ascontiguousarray(site_counts_b, np.uint32).reshape(-1)
+    t = np.ascontiguousarray(table, np.uint32).reshape(-1)
+    if a.shape[0] != 6 or b.shape[0] != 6 or t.shape[0] != 36:
+        raise ValueError("a site has 6 counts and a pair 36 cells")
+    for name, v in (("min_depth", min_depth), ("min_link_count", min_link_count), ("max_discord_per_10k", max_discord_per_10k)):
+        if not 0 <= int(v) <= 0xFFFFFFFF:
+            raise ValueError(f"{name}: 0..2^32-1")
+    prm = _lib.dut_link_params(int(min_depth), int(min_link_count), int(max_discord_per_10k))
+    u = _lib.dut_link_summary()
+    st = _lib.load().dut_link_summarise(_ptr(a), _ptr(b), _ptr(t), C.byref(prm), C.byref(u))
+    if st != 0:
+        raise EngineError(st, "invalid parameters")
+    return dict(status=int(u.status), major_a=int(u.major_a), minor_a=int(u.minor_a), major_b=int(u.major_b), minor_b=int(u.minor_b),
+                depth_a=int(u.depth_a), depth_b=int(u.depth_b), both=int(u.both), MM=int(u.MM), Mm=int(u.Mm), mM=int(u.mM), mm=int(u.mm), other=int(u.other))
+
+
+def link_sites_parse(path: str, contig: str) -> Tuple[np.ndarray, int]:
+    """dut_link_sites_parse: (the 0-based positions of `contig` in the file, sorted, duplicates merged; the lines of other
+    contigs).  An EngineError names a malformed line by its number."""
+    lib = _lib.load()
+    sp = C.POINTER(C.c_uint32)()
+    n, skipped = C.c_size_t(), C.c_size_t()
+    _call(lib.dut_link_sites_parse, path.encode(), contig.encode(), C.byref(sp), C.byref(n), C.byref(skipped))
+    try:
+        return np.array(sp[:n.value], np.uint32), int(skipped.value)
+    finally:
+        lib.dut_link_sites_free(sp)
+
+
+def write_links(path: str, contig: str, sites, result: LinkResult, sites_skipped: int = 0, max_dist: int = 1000, max_partners: int = 4, min_depth: int = 10,
+                min_quality: int = 20, min_link_count: int = 3, max_discordance="0.05", min_base_quality: Optional[int] = None, exclude_flags: int = 0):
+    """The TSV of phase-sites (dut_link_write) for 0-based sites and the LinkResult of Engine.site_link_counts or link_measure
+    over them under the same max_dist and max_partners.  No device is needed."""
+    sites = np.ascontiguousarray(sites, np.uint32).reshape(-1)
+    n = sites.shape[0]
+    first = np.ascontiguousarray(result.first, np.uint32).reshape(-1)
+    tables = np.ascontiguousarray(result.tables, np.uint32)
+    site_counts = np.ascontiguousarray(result.site_counts, np.uint32)
+    if first.shape[0] != n + 1 or site_counts.shape != (n, 6) or tables.shape != (int(first[n]), 6, 6):
+        raise ValueError("the result does not belong to these sites")
+    opt = _link_options(min_depth, min_quality, exclude_flags, min_base_quality, max_dist, max_partners, min_link_count, max_discordance)
+    _call(_lib.load().dut_link_write, path.encode(), contig.encode(), _ptr(sites) if n else None, n, int(sites_skipped), _ptr(first),
+          _ptr(tables) if tables.shape[0] else None, _ptr(site_counts) if n else None, C.byref(opt))
+
+
+def phase_sites(bam_file: str, reference_file: str, contig: str, sites_file: str, output_file: str, max_dist: int = 1000, max_partners: int = 4,
+                min_depth: int = 10, min_quality: int = 20, min_link_count: int = 3, max_discordance="0.05", min_base_quality: Optional[int] = None,
+                exclude_flags: int = 0, device_id: int = 0):
+    """dut_find_links_files: BAM (+ index), FASTA and a sites file (contig and 1-based position, tab separated; the TSVs of
+    find-variants, find-minor-alleles and find-deletions as they are) in, the TSV of linked site pairs out.
+    max_discordance: decimal text in [0, 0.4999], at most four decimals."""
+    opt = _link_options(min_depth, min_quality, exclude_flags, min_base_quality, max_dist, max_partners, min_link_count, max_discordance)
+    _call(_lib.load().dut_find_links_files, bam_file.encode(), reference_file.encode(), contig.encode(), sites_file.encode(), C.byref(opt),
+          output_file.encode(), device_id, size=1024)

@@ -696,6 +696,49 @@ cl_status cl_site_error_profile(cl_ctx *ctx, uint8_t min_quality, const cl_scan_
  * cl_site_scan_stats reports): the table kernel, and the sum of the workgroups' slices. */
 cl_status cl_site_error_profile_stats(cl_ctx *ctx, double *table_ms, double *sum_ms);
 
+/* ---- linked sites: what one read observes at two positions of the resident tile --------------------------------------- */
+/* Every scan above counts a column and forgets which read held which base; this call keeps, per pair of nearby sites, the
+ * 6 x 6 table of the classes A C G T del other one read observes at both.
+ * sites[0..n_sites): 0-based positions, strictly ascending, each < min(contig_len, ref_len) of the upload.  The pair set:
+ * for anchor i the partners are j = i+1, i+2, ... while j <= i + max_partners and sites[j] - sites[i] <= max_dist;
+ * first[i] is the CSR offset, pair first[i] + (j - i - 1) is (i, j), first[n_sites] = n_pairs.
+ * A read takes part for anchor a = sites[i] iff it passes the gates of cl_site_scan (read start < contig_len,
+ * mapq >= min_quality; under a filter (flag & exclude_flags) == 0) and its reference span covers a.  Its CIGAR is walked
+ * from pos with x, the reference position, and y, the stored bases consumed (M I S = X consume); L is the stored base count.
+ * Its observation at a site p:
+ *   p in an M = X operation, q = y + (p - x) < L and (no use_base_quality or the pass bit of q set): the class of the 4-bit
+ *     code at q -- 1 -> A (0), 2 -> C (1), 4 -> G (2), 8 -> T (3), every other code -> other (5); none when q >= L or the
+ *     pass bit is clear
+ *   p in a D operation (op 2) whose carrier y - 1 exists (1 <= y <= L) and, under use_base_quality, passes: del (4); none
+ *     when the carrier does not exist or does not pass
+ *   p in an N, or outside the read's span: none
+ * -- the conventions of cl_site_scan_counts[_ex] for bases and of cl_site_scan_dels for deletions.
+ * site_counts[i * 6 + c]: the reads that take part for site i and observe class c there.  tables[pair * 36 + 6 * ca + cb]:
+ * the reads that take part for anchor i and observe ca at sites[i] and cb at sites[j]; a read with no observation at
+ * either site adds nothing to the pair.  Mates are two reads.  Exact counts; two calls return identical bytes.
+ * The arrays are context-owned, in storage of their own, valid until the next cl_site_link_counts, cl_site_upload or
+ * cl_destroy; any order of this call, cl_site_run, the scans, cl_site_str_lengths and cl_site_error_profile on one tile is
+ * allowed, and the call builds the read index itself when it is the first on a fresh tile.  n_sites == 0 returns an empty
+ * result without a launch.  cl_site_scan_stats speaks of this launch after it.
+ * CL_ERR_INVALID (with a message, the context stays usable): no resident tile, a tile cl_site_pileup filtered, a filter
+ * with nothing attached, null sites with n_sites > 0, null out, n_sites > CL_LINK_MAX_SITES, sites not strictly ascending
+ * (the message names the index), a site >= min(contig_len, ref_len), max_dist == 0, max_partners outside
+ * [1, CL_LINK_MAX_PARTNERS], a pair set above CL_LINK_MAX_PAIRS (the message gives the count).  CL_ERR_DEVICE: a host-only
+ * debug context.  The checks come before any device work. */
+#define CL_LINK_CLASSES      6          /* A C G T del other */
+#define CL_LINK_MAX_PARTNERS 15
+#define CL_LINK_MAX_SITES    (1u << 20)
+#define CL_LINK_MAX_PAIRS    (1u << 20)
+typedef struct cl_link_result {
+    size_t          n_sites, n_pairs;
+    const uint32_t *first;         /* n_sites + 1 */
+    const uint32_t *tables;        /* n_pairs * 36 */
+    const uint32_t *site_counts;   /* n_sites * 6  */
+} cl_link_result;
+cl_status cl_site_link_counts(cl_ctx *ctx, uint8_t min_quality, const cl_scan_filter *filter /* NULL: unfiltered */,
+                              const uint32_t *sites, size_t n_sites, uint32_t max_dist, uint32_t max_partners,
+                              cl_link_result *out);
+
 /* Host only: the pass bits of an attachment as cl_site_attach_quals builds them, words [0, n_words): bit i of word w
  * <-> base 64 w + i in seq_off numbering; bits of no read are zero. */
 cl_status cl_debug_site_pass_bits(const cl_site_quals *quals, uint8_t min_base_quality, uint64_t *words_out, uint64_t n_words);

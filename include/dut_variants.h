@@ -479,6 +479,98 @@ int dut_error_profile_files(const char *bam_path, const char *fasta_path, const 
                             uint32_t end, const dut_ep_options *opt, const char *output_path, int device_id, char *err,
                             size_t err_len);
 
+/* ---- phase-sites: joint allele counts of site pairs per read (cl_site_link_counts) ------------------------------------- */
+/* What a phase-sites run is asked.  filtered == 0: no flag is read and every base passes (the unfiltered form of
+ * cl_site_link_counts; exclude_flags and the threshold take no part).  dut_find_links_files always runs the filtered form. */
+typedef struct dut_link_options {
+    uint32_t min_depth;               /* >= 1 */
+    uint8_t  min_quality;
+    int      filtered;
+    uint16_t exclude_flags;
+    int      has_min_base_quality;    /* 0: every base passes */
+    uint8_t  min_base_quality;
+    uint32_t max_dist;                /* >= 1 */
+    uint32_t max_partners;            /* 1..CL_LINK_MAX_PARTNERS */
+    uint32_t min_link_count;          /* >= 1 */
+    uint32_t max_discord_per_10k;     /* 0..4999 */
+} dut_link_options;
+
+/* The pair set of cl_site_link_counts for strictly ascending sites: first[i] (n_sites + 1 words, may be NULL) is the CSR
+ * offset of anchor i, *n_pairs the number of pairs -- not bounded by CL_LINK_MAX_PAIRS, so that a caller can see how far
+ * above it a set lies (offsets above 2^32 - 1 are clamped).  The engine, the host route and this function count the
+ * partners of an anchor by one function of csrc/link_walk.h.  CL_ERR_INVALID: null sites with n_sites > 0, null n_pairs,
+ * sites not strictly ascending, max_dist == 0, max_partners outside [1, CL_LINK_MAX_PARTNERS]. */
+int dut_link_pair_offsets(const uint32_t *sites, size_t n_sites, uint32_t max_dist, uint32_t max_partners, uint32_t *first,
+                          uint64_t *n_pairs);
+
+/* cl_site_link_counts from host arrays, no device needed: the same first, tables and site_counts (the walk is written
+ * once, in csrc/link_walk.h, and both routes compile it) for the reads of a contig of contig_len positions.  Of opt it
+ * reads min_quality, filtered, exclude_flags, has_min_base_quality, min_base_quality (taken over the reads' quality
+ * values; a base without one passes), max_dist and max_partners.  first: n_sites + 1, tables: 36 per pair (ask
+ * dut_link_pair_offsets for their number first), site_counts: 6 per site, the caller's arrays.  The anchors are spread
+ * over DUT_THREADS threads.  CL_ERR_INVALID: a null argument or array, what dut_link_pair_offsets refuses, more than
+ * CL_LINK_MAX_SITES sites or CL_LINK_MAX_PAIRS pairs, a site >= contig_len, offsets that decrease.  What a caller without
+ * a device gets, and the yardstick of tools/link_bench.py. */
+int dut_link_measure(const dut_ep_reads *reads, uint32_t contig_len, const dut_link_options *opt, const uint32_t *sites,
+                     size_t n_sites, uint32_t *first, uint32_t *tables, uint32_t *site_counts);
+
+/* One pair from its two sites' counts (6 each) and its table (36), in integers.
+ *   major       per site the fullest of A C G T del, the first in that order among equals
+ *   minor       the fullest of the other four under the same tie rule (its count may be 0)
+ *   both        the sum of the 36 cells;  MM Mm mM mm: the cells of {major_a, minor_a} x {major_b, minor_b};
+ *               other = both - n4 with n4 their sum;  m = Mm + mM + mm
+ *   low_depth   n4 < min_depth
+ *   cis         else mm >= min_link_count and 10000 * (Mm + mM) <= max_discord_per_10k * m
+ *   trans       else Mm >= min_link_count and mM >= min_link_count and 10000 * mm <= max_discord_per_10k * m
+ *   unresolved  everything else
+ * All products are taken in 64 bits.  max_discord_per_10k <= 4999 makes cis and trans exclude each other, in whichever
+ * order they are asked.  depth_a / depth_b: the sum of the site's six counts.  CL_ERR_INVALID: a null argument,
+ * min_depth == 0, min_link_count == 0, max_discord_per_10k > 4999. */
+enum { DUT_LINK_LOW_DEPTH = 0, DUT_LINK_CIS = 1, DUT_LINK_TRANS = 2, DUT_LINK_UNRESOLVED = 3 };
+typedef struct dut_link_params { uint32_t min_depth, min_link_count, max_discord_per_10k; } dut_link_params;
+typedef struct dut_link_summary {
+    int      status;
+    uint8_t  major_a, minor_a, major_b, minor_b;      /* 0..4: A C G T del */
+    uint64_t depth_a, depth_b, both, MM, Mm, mM, mm, other;
+} dut_link_summary;
+int dut_link_summarise(const uint32_t *site_counts_a, const uint32_t *site_counts_b, const uint32_t *table,
+                       const dut_link_params *params, dut_link_summary *out);
+
+/* "0.05" -> 500 parts per 10 000, exactly: a decimal in [0, 0.4999] with at most four decimals (the parser of the other
+ * fractions, with 0 allowed). */
+int dut_link_discordance_parse(const char *text, uint32_t *per_10k, char *err, size_t err_len);
+
+/* The sites file: tab separated, column 1 the contig, column 2 a 1-based position; further columns are ignored, lines that
+ * start with '#' and empty lines are skipped -- the TSVs of find-variants, find-minor-alleles and find-deletions (its
+ * start column) can be given as they are.  Lines of other contigs are skipped and counted in *n_skipped.  *sites: the
+ * 0-based positions of `contig`, sorted, duplicates merged, malloc'ed, release with dut_link_sites_free (NULL when there
+ * is none).  CL_ERR_INVALID with a message: an unreadable file; a malformed line, named by its number -- fewer than two
+ * columns, an empty contig, a position that is not a decimal number in [1, 2^32).  Whether a site fits the contig is not
+ * the parser's question. */
+int dut_link_sites_parse(const char *path, const char *contig, uint32_t **sites, size_t *n_sites, size_t *n_skipped,
+                         char *err, size_t err_len);
+void dut_link_sites_free(uint32_t *sites);
+
+/* The TSV (no device needed) of the pairs of n_sites strictly ascending 0-based sites with first, tables and site_counts as
+ * cl_site_link_counts or dut_link_measure return them under opt's max_dist and max_partners: comment lines ##contig=
+ * ##sites= ##sites_skipped= ##pairs= ##max_dist= ##max_partners= ##min_depth= ##min_quality= ##min_base_quality= ("." when
+ * not given) ##exclude_flags=0x%04x ##min_link_count= ##max_discordance=%.4f ##low_depth= ##cis= ##trans= ##unresolved=,
+ * the header
+ *   #contig pos_a pos_b dist major_a minor_a major_b minor_b depth_a depth_b both MM Mm mM mm other status
+ * and one line per pair in pair order, positions 1-based, alleles A C G T or del, the columns of dut_link_summarise.
+ * CL_ERR_INVALID: a null argument, refused options, a first that is not the pair set of the sites. */
+int dut_link_write(const char *path, const char *contig, const uint32_t *sites, size_t n_sites, size_t n_skipped,
+                   const uint32_t *first, const uint32_t *tables, const uint32_t *site_counts, const dut_link_options *opt,
+                   char *err, size_t err_len);
+
+/* `phase-sites` on files, one GPU: parses the sites file (before any device is opened), reads as dut_find_strs_files does,
+ * always attaches the records' flags and pass bits and runs the filtered form of cl_site_link_counts -- with no mask and
+ * no threshold it counts what the unfiltered form does -- and writes the TSV.  Errors with a message: those of
+ * dut_find_variants_files, refused options, an unreadable or malformed sites file, a site beyond the contig, a pair set
+ * above CL_LINK_MAX_PAIRS. */
+int dut_find_links_files(const char *bam_path, const char *fasta_path, const char *contig, const char *sites_path,
+                         const dut_link_options *opt, const char *output_path, int device_id, char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,27 @@ extern "C" {
                                    err: *mut c_char, err_len: usize) -> c_int;
     pub fn dut_error_profile_files(bam: *const c_char, fasta: *const c_char, contig: *const c_char, has_region: c_int, start: u32, end: u32,
                                    opt: *const DutEpOptions, output: *const c_char, device_id: c_int, err: *mut c_char, err_len: usize) -> c_int;
+    // linked sites (README "Linked sites"): for strictly ascending 0-based sites the pair set (every site with the next
+    // max_partners <= 15 sites within max_dist), per pair the 6 x 6 table of the classes A C G T del other one read observes at
+    // both sites, per site its six counts, over the tile cl_site_upload left resident; filter null: unfiltered.  Context-owned
+    // arrays, valid until the next cl_site_link_counts / upload.  At most 2^20 sites and 2^20 pairs
+    pub fn cl_site_link_counts(ctx: *mut ClCtx, min_quality: u8, filter: *const ClScanFilter, sites: *const u32, n_sites: usize, max_dist: u32,
+                               max_partners: u32, out: *mut ClLinkResult) -> c_int;
+    // include/dut_variants.h: the pair set alone (first may be null), the same counts from host arrays (first: n_sites + 1, tables:
+    // 36 per pair, site_counts: 6 per site, the caller's), one pair's summary, the sites file, the TSV, `phase-sites` on files
+    pub fn dut_link_pair_offsets(sites: *const u32, n_sites: usize, max_dist: u32, max_partners: u32, first: *mut u32, n_pairs: *mut u64) -> c_int;
+    pub fn dut_link_measure(reads: *const DutEpReads, contig_len: u32, opt: *const DutLinkOptions, sites: *const u32, n_sites: usize,
+                            first: *mut u32, tables: *mut u32, site_counts: *mut u32) -> c_int;
+    pub fn dut_link_summarise(site_counts_a: *const u32, site_counts_b: *const u32, table: *const u32, params: *const DutLinkParams,
+                              out: *mut DutLinkSummary) -> c_int;
+    pub fn dut_link_discordance_parse(text: *const c_char, per_10k: *mut u32, err: *mut c_char, err_len: usize) -> c_int;
+    pub fn dut_link_sites_parse(path: *const c_char, contig: *const c_char, sites: *mut *mut u32, n_sites: *mut usize, n_skipped: *mut usize,
+                                err: *mut c_char, err_len: usize) -> c_int;
+    pub fn dut_link_sites_free(sites: *mut u32);
+    pub fn dut_link_write(path: *const c_char, contig: *const c_char, sites: *const u32, n_sites: usize, n_skipped: usize, first: *const u32,
+                          tables: *const u32, site_counts: *const u32, opt: *const DutLinkOptions, err: *mut c_char, err_len: usize) -> c_int;
+    pub fn dut_find_links_files(bam: *const c_char, fasta: *const c_char, contig: *const c_char, sites_path: *const c_char,
+                                opt: *const DutLinkOptions, output: *const c_char, device_id: c_int, err: *mut c_char, err_len: usize) -> c_int;
     // include/dut_fingerprint.h: the `fingerprint` sketch on the device (1 <= ksize <= 64)
     pub fn dut_fp_create(opt: *const DutFpOptions, device_id: c_int, stream: *mut c_void, out: *mut *mut DutFpCtx) -> c_int;
     pub fn dut_fp_push_seq4(ctx: *mut DutFpCtx, seq4: *const u8, base_off: *const u64, n_seq: u64) -> c_int;
@@ -174,6 +195,27 @@ pub struct ClEpResult {           // cl_ep_result: total[4 * from + to] in A C G
     pub total: [u64; 16],
     pub from5: *const u64, pub from3: *const u64,
     pub ins5: *const u64, pub ins3: *const u64, pub del5: *const u64, pub del3: *const u64,
+}
+
+#[repr(C)]
+pub struct ClLinkResult {         // cl_link_result: first: n_sites + 1; tables: n_pairs * 36; site_counts: n_sites * 6 (A C G T del other)
+    pub n_sites: usize, pub n_pairs: usize,
+    pub first: *const u32, pub tables: *const u32, pub site_counts: *const u32,
+}
+
+#[repr(C)]
+pub struct DutLinkOptions {       // dut_link_options
+    pub min_depth: u32, pub min_quality: u8, pub filtered: c_int, pub exclude_flags: u16, pub has_min_base_quality: c_int,
+    pub min_base_quality: u8, pub max_dist: u32, pub max_partners: u32, pub min_link_count: u32, pub max_discord_per_10k: u32,
+}
+
+#[repr(C)]
+pub struct DutLinkParams { pub min_depth: u32, pub min_link_count: u32, pub max_discord_per_10k: u32 }
+
+#[repr(C)]
+pub struct DutLinkSummary {       // dut_link_summary: status 0 low_depth, 1 cis, 2 trans, 3 unresolved; alleles 0..4: A C G T del
+    pub status: c_int, pub major_a: u8, pub minor_a: u8, pub major_b: u8, pub minor_b: u8,
+    pub depth_a: u64, pub depth_b: u64, pub both: u64, pub major_major: u64, pub major_minor: u64, pub minor_major: u64, pub minor_minor: u64, pub other: u64,   // MM Mm mM mm
 }
 
 #[repr(C)]
