@@ -104,15 +104,21 @@ template <> __device__ __forceinline__ uint2 head_fetch<false>(__amdgpu_buffer_r
 // owns a block of 32 positions, the window's one wave streams groups of 4 rows (one 16-byte load per lane: a unit of
 // 128 bytes per segment of 8 lanes, as many as the segment's own stack is high -- row_lane above --, no masks, no
 // shifts), and adds them into NP counter planes (plane k = bit k of the 32 counts) with carry-save adders: three-input
-// boolean operations (v_bitop3), about 4.5 instructions per row for 32 positions.  No LDS atomics, no CIGAR, no
-// offsets.  The planes stay in the lane's registers and are compared there -- still bit-sliced -- with min_depth and
-// max_depth (callable_profiler.rs:108-113): two 32-bit masks, those of the 32 positions the lane goes on to classify.
+// boolean operations (v_bitop3), 16 or 8 rows through one tree (bs_add16, bs_add8 below), about 2.5 to 3 instructions
+// per row for 32 positions.  No LDS atomics, no CIGAR, no offsets.  The planes stay in the lane's registers and are
+// compared there -- still bit-sliced -- with min_depth and max_depth (callable_profiler.rs:108-113): two 32-bit masks,
+// those of the 32 positions the lane goes on to classify.
 // quality_bases is the number of set bits (contig_profiler.rs:71: taken from the planes, sum of 2^p x popcount);
 // summed_baseq comes with the bits from the host's walk (contig_profiler.rs:70, per-read separable: SURVEY 8a-7).
 //
 // The window's candidates are heads (8 or 4 bytes, one per read with a reference span; above): the +-1 scatter of raw_depth
-// and low_mapq_count (mod.rs:22-28) into difference arrays in LDS, nothing else -- the reads' other separable sums
-// (summed_coverage, summed_mapq) come from the host's walk too.
+// and low_mapq_count (mod.rs:22-28) into ONE difference array in LDS, nothing else -- the reads' other separable sums
+// (summed_coverage, summed_mapq) come from the host's walk too.  Word p of the array is the difference of the PACKED
+// count raw_depth + (low_mapq_count << 16) at position W + p: a head adds v = 1 + (low << 16) where it begins and -v
+// where it ends, two atomics whatever its mapq.  Sums of such words are linear mod 2^32, so every partial sum (a lane's,
+// the scan over the lanes) may wrap and borrow from field to field; the prefix sum AT a position is raw | low << 16
+// exactly, because without DEEP a window has at most 32 767 candidates (callable_loci.hip: kNeedDeep): low <= raw <=
+// 32 767, bits 15 and 31 clear.  The final phase tests that one word and never splits it (see there).
 //
 // The final phase works in the BIT DOMAIN: per position only the two tests that need the position's integers (raw_depth
 // > 0; the low-MAPQ rule, callable_profiler.rs:100-101) are taken, each leaving one bit; from there a thread's PER
@@ -122,7 +128,8 @@ template <> __device__ __forceinline__ uint2 head_fetch<false>(__amdgpu_buffer_r
 // set bits of the boundary mask.
 //
 // NP: counter planes -- 8 while no window has more than 255 rows (63 groups), 16 up to 65 535, else 32.
-// DEEP: 32-bit difference words (a window with more than 32 767 candidates), as in k_pileup.
+// DEEP: two arrays of 32-bit difference words, raw_depth's and low_mapq_count's (a window with more than 32 767
+//       candidates), as in k_pileup.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t bs_maj(uint32_t a, uint32_t b, uint32_t c) { return (a & b) | (c & (a | b)); }
 
@@ -137,6 +144,45 @@ __device__ __forceinline__ void bs_add4(uint32_t (&c)[NP], const uint4 x)
     c[1] = c[1] ^ k0 ^ k1;
 #pragma unroll
     for (int p = 2; p < NP; ++p) { const uint32_t t = c[p] & k; c[p] ^= k; k = t; }
+}
+
+// 8 and 16 rows (2 and 4 groups) at once, as a TREE of carry-save adders: the rows and plane 0 through three-input
+// adders (sum = a ^ b ^ c, carry = maj: one v_bitop3 each), their carries and plane 1 through the same, and so on until
+// one carry is left -- for plane 3 (8 rows) or 4 (16 rows) --, and only that one ripples through the planes above.  The
+// ripple is 12 of bs_add4's 18 operations; here it is paid once per 8 or 16 rows: 24 operations for 8 rows, 38 for 16,
+// against 36 and 72.  Exact as bs_add4 is: every adder keeps the weighted sum of what it takes (a + b + c = sum + 2 x
+// carry), so the planes hold the old counts + the rows' column sums mod 2^NP, and the one thing dropped is the carry out
+// of plane NP - 1.  That carry is zero while the true count is below 2^NP: 8 planes are used up to 63 groups = 252 rows
+// (<= 255), 16 up to 65 535 rows, and rows that are zeros (slots a segment does not have: row_unit) add nothing.
+__device__ __forceinline__ uint32_t bs_csa(uint32_t &s, uint32_t a, uint32_t b)
+{
+    const uint32_t k = bs_maj(s, a, b);
+    s ^= a ^ b;
+    return k;
+}
+template <int NP>
+__device__ __forceinline__ void bs_ripple(uint32_t (&c)[NP], int from, uint32_t k)
+{
+#pragma unroll
+    for (int p = from; p < NP; ++p) { const uint32_t t = c[p] & k; c[p] ^= k; k = t; }
+}
+template <int NP>
+__device__ __forceinline__ void bs_add8(uint32_t (&c)[NP], const uint4 x, const uint4 y)
+{
+    static_assert(NP >= 4, "the tree of 8 rows ends in plane 2");
+    const uint32_t a0 = bs_csa(c[0], x.x, x.y), a1 = bs_csa(c[0], x.z, x.w), a2 = bs_csa(c[0], y.x, y.y), a3 = bs_csa(c[0], y.z, y.w);
+    const uint32_t b0 = bs_csa(c[1], a0, a1), b1 = bs_csa(c[1], a2, a3);
+    bs_ripple<NP>(c, 3, bs_csa(c[2], b0, b1));
+}
+template <int NP>
+__device__ __forceinline__ void bs_add16(uint32_t (&c)[NP], const uint4 x, const uint4 y, const uint4 z, const uint4 v)
+{
+    static_assert(NP >= 5, "the tree of 16 rows ends in plane 3");
+    const uint32_t a0 = bs_csa(c[0], x.x, x.y), a1 = bs_csa(c[0], x.z, x.w), a2 = bs_csa(c[0], y.x, y.y), a3 = bs_csa(c[0], y.z, y.w);
+    const uint32_t a4 = bs_csa(c[0], z.x, z.y), a5 = bs_csa(c[0], z.z, z.w), a6 = bs_csa(c[0], v.x, v.y), a7 = bs_csa(c[0], v.z, v.w);
+    const uint32_t b0 = bs_csa(c[1], a0, a1), b1 = bs_csa(c[1], a2, a3), b2 = bs_csa(c[1], a4, a5), b3 = bs_csa(c[1], a6, a7);
+    const uint32_t d0 = bs_csa(c[2], b0, b1), d1 = bs_csa(c[2], b2, b3);
+    bs_ripple<NP>(c, 4, bs_csa(c[3], d0, d1));
 }
 
 // bit i = (the count of position i < K), for the NP planes of a block
@@ -163,7 +209,9 @@ struct RowsArgs {
     const WinMeta  *win;
     const uint32_t *refn;         // bit p = the reference base at p is 'N' / 'n' (or beyond the reference)
     const uint32_t *lut8;         // the low-MAPQ thresholds of depths 0..255 as bytes (255 = never): 64 words, built once per
-                                  // engine from its options (callable_loci.hip: build_lut8)
+                                  // engine from its options (callable_loci.hip: build_lut8).  Lane l keeps word l; the fast
+                                  // path fetches the word of a depth with ds_bpermute, which takes the lane from bits [7:2]
+                                  // of its address only, so it is handed the packed word raw | low << 16 as it is
     uint16_t       *runs;
     uint8_t        *first_state, *last_state;
     WinPartial     *winpart;
@@ -188,10 +236,11 @@ constexpr int kRowsBlock = 64;
 // form (8 planes) takes the 5.  The forms with more planes hold 16 or 32 of them beside the 48 row registers and are
 // given the registers instead: 4 waves (128) for 16 planes, 3 (168) for 32 planes and for DEEP, which keeps 10
 // workgroups on 4 SIMDs.  The DEBUG forms (test dumps) keep the planes alive through the final phase for the dump of
-// qc_depth and get one wave less than their form (at its registers the forms of 8 and of 32 planes spill).
+// qc_depth and get one wave less than their form (at its registers the forms of 8 and of 32 planes spill), the form of
+// 8 planes without DEEP two less: its walk holds the lane's 32 packed words beside the dumps' addresses and spills at 128.
 constexpr int rows_min_waves(bool DEBUG, bool DEEP, int NP)
 {
-    return ((DEEP || NP > 16) ? 3 : (NP > 8 ? 4 : 5)) - (DEBUG ? 1 : 0);
+    return ((DEEP || NP > 16) ? 3 : (NP > 8 ? 4 : 5)) - (DEBUG ? (!DEEP && NP <= 8 ? 2 : 1) : 0);
 }
 template <int T, bool DEBUG, bool DEEP, int NP, bool HEAD4>
 __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k_pileup_rows(RowsArgs a)
@@ -199,18 +248,17 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
     constexpr int kBlock = kRowsBlock;                     // (shadows the namespace's 256 inside this kernel)
     constexpr int PER = T / kBlock;
     static_assert(PER == 32 && T == 2048 && kBlock == 64, "a lane owns a block of 32 positions: T = 64 x 32, one wave");
-    constexpr int kDiffWords = DEEP ? T : T / 2;
     constexpr int G = 12;                                  // groups the wave has in flight: 48 rows before a second trip
-    // LDS: the two difference arrays and nothing else -- 8 192 bytes (16 384 with DEEP), which admits 20 workgroups =
-    // 20 windows in flight per CU (the kernel's time follows the number of windows a CU has in flight:
-    // profiles/r04_occupancy.txt).  With one wave per workgroup that is 5 waves per SIMD: at most 96 vector registers;
+    // LDS: the difference array and nothing else -- T packed words (raw + (low << 16): the kernel's comment), exactly
+    // 8 192 bytes; with DEEP two arrays of T words, 16 384.  8 192 bytes admit 20 workgroups = 20 windows in flight per
+    // CU (the kernel's time follows the number of windows a CU has in flight: profiles/r04_occupancy.txt).  With one wave per workgroup that is 5 waves per SIMD: at most 96 vector registers;
     // scalar registers do not bind (800 / 5).  One byte more of LDS would cost a workgroup per CU, so the byte
     // thresholds stay in registers (wlut, below).
-    // The arrays are cleared, added to (atomics) and read by the same wave: what has to be ordered is that wave's own
+    // The array is cleared, added to (atomics) and read by the same wave: what has to be ordered is that wave's own
     // LDS operations.  __syncthreads() is used for it -- in a workgroup of one wave it is the wait for the LDS counter
     // and a fence for the compiler, no s_barrier that anybody waits at.
-    __shared__ __attribute__((aligned(16))) uint32_t s_raw[kDiffWords];
-    __shared__ __attribute__((aligned(16))) uint32_t s_low[kDiffWords];
+    __shared__ __attribute__((aligned(16))) uint32_t s_diff[DEEP ? 2 * T : T];
+    uint32_t *const s_raw = s_diff, *const s_low = s_diff + T;             // (DEEP only: raw_depth's words, low_mapq_count's)
 #ifdef CL_ROWS_LDS_PAD
     __shared__ uint32_t s_pad[CL_ROWS_LDS_PAD / 4];        // (occupancy experiments only)
     s_pad[threadIdx.x] = threadIdx.x;
@@ -274,11 +322,9 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
 
     // ---- clear ----
     {
-        const uint4 z = make_uint4(0, 0, 0, 0);
-        uint4 *r4 = reinterpret_cast<uint4 *>(s_raw), *l4 = reinterpret_cast<uint4 *>(s_low);
-        const uint4 zb = DEEP ? z : make_uint4(0x8000u, 0x8000u, 0x8000u, 0x8000u);
+        uint4 *d4 = reinterpret_cast<uint4 *>(s_diff);
 #pragma unroll
-        for (int i = 0; i < kDiffWords / 4 / kBlock; ++i) { r4[i * kBlock + lane] = zb; l4[i * kBlock + lane] = zb; }
+        for (int i = 0; i < (DEEP ? 2 * T : T) / 4 / kBlock; ++i) d4[i * kBlock + lane] = make_uint4(0, 0, 0, 0);
     }
     __syncthreads();                                       // (this wave's clear before its atomics: see the LDS comment)
 
@@ -291,9 +337,13 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
     for (int p = 0; p < NP; ++p) c[p] = 0u;
     if (ng) {
         for (uint32_t g0 = 0; g0 < ng; g0 += (uint32_t)G) {
+            // (a chunk of four group slots: 16 rows through one tree when the window's highest segment has three or four
+            // groups there, 8 rows when it has one or two -- slots a segment does not have hold zeros --, nothing when
+            // it has none)
 #pragma unroll
-            for (int j = 0; j < G; ++j) {
-                if (g0 + (uint32_t)j < ng) bs_add4<NP>(c, rv[j]);
+            for (int j = 0; j < G; j += 4) {
+                if (g0 + (uint32_t)j + 2u < ng) bs_add16<NP>(c, rv[j], rv[j + 1], rv[j + 2], rv[j + 3]);
+                else if (g0 + (uint32_t)j < ng) bs_add8<NP>(c, rv[j], rv[j + 1]);
             }
             if (g0 + (uint32_t)G < ng) {                   // a deeper window: the next trip's groups (requested only now)
                 row_advance(rl, G);
@@ -311,17 +361,18 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
             // (a head of a cut span may lie past the window; a zeroed head: no candidate in this slot)
             if (hc.hit) {
                 const uint32_t cb = hc.cb, ce = hc.ce;
-                uint32_t ib, vb, ie, ve2;
-                if (DEEP) { ib = cb; vb = 1u; ie = ce; ve2 = 0xFFFFFFFFu; }
-                else {
-                    ib = cb >> 1; vb = (cb & 1u) ? 0x10000u : 1u;
-                    ie = ce >> 1; ve2 = (ce & 1u) ? 0xFFFF0000u : 0xFFFFFFFFu;
-                }
-                atomicAdd(&s_raw[ib], vb);
-                if (ce < (uint32_t)T) atomicAdd(&s_raw[ie], ve2);
-                if (hc.low) {
-                    atomicAdd(&s_low[ib], vb);
-                    if (ce < (uint32_t)T) atomicAdd(&s_low[ie], ve2);
+                if (DEEP) {
+                    atomicAdd(&s_raw[cb], 1u);
+                    if (ce < (uint32_t)T) atomicAdd(&s_raw[ce], 0xFFFFFFFFu);
+                    if (hc.low) {
+                        atomicAdd(&s_low[cb], 1u);
+                        if (ce < (uint32_t)T) atomicAdd(&s_low[ce], 0xFFFFFFFFu);
+                    }
+                } else {
+                    // both counts in one word: two atomics per head whatever its mapq
+                    const uint32_t v = 1u + (hc.low << 16);
+                    atomicAdd(&s_diff[cb], v);
+                    if (ce < (uint32_t)T) atomicAdd(&s_diff[ce], 0u - v);
                 }
             }
         }
@@ -341,40 +392,37 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
 #pragma unroll
     for (int p = 0; p < NP; ++p) nbits += (unsigned long long)__popc(c[p]) << p;
 
-    // The lane's differences: 16 packed words per array (DEEP: 32 words, re-read from LDS where they are needed), and
-    // first their sum, for the scan over the lanes.  Packed, a word is (0x8000 + d_even) | d_odd << 16 with no carry
-    // between the fields (at most 32 767 candidates without DEEP), so v_sad_u16 against 0 adds both fields of a word
-    // as unsigned 16-bit numbers: 16 of them give 2^19 + the lane's sum + 2^16 x (the negative odd fields) -- and the
-    // lane's sum lies within +-32 767: it is the low 16 bits, sign-extended.  One instruction per word, the fields are
-    // never split.  (A lane's sum may well be negative: ends without starts.)
-    constexpr int NH = DEEP ? 1 : PER / 2;                 // packed words per array that the lane holds
-    uint32_t xr[NH], xl[NH];
-    uint32_t tr = 0, tl = 0;
+    // The lane's differences: its 32 packed words (DEEP: 32 words of either array, re-read from LDS where they are
+    // needed), and first their sum, for the scan over the lanes.  A packed word is the difference of raw + (low << 16)
+    // at its position, and everything from here to the running sum is linear mod 2^32: the lane's sum, the scan over
+    // the lanes and the offsets may wrap and borrow between the fields as they like (a lane's sum may well be negative
+    // in either field: ends without starts) -- one chain of adds and ONE scan serve both counts.  What is exact is the
+    // running sum AT a position: raw | low << 16 with low <= raw <= 32 767, for without DEEP a window has at most
+    // 32 767 candidates (callable_loci.hip: kNeedDeep).  Bit 15 and bit 31 of it are clear; the tests below use that.
+    constexpr int NX = DEEP ? 1 : PER;                     // packed words that the lane holds
+    uint32_t x[NX];
+    uint32_t tr = 0, tl = 0;                               // (tr: the packed sum; tl: DEEP only)
     if constexpr (DEEP) {
-        xr[0] = xl[0] = 0u;
+        x[0] = 0u;
 #pragma unroll
         for (int q = 0; q < PER / 4; ++q) {
-            const uint4 x = reinterpret_cast<const uint4 *>(s_raw)[lane * (PER / 4) + q];
-            const uint4 y = reinterpret_cast<const uint4 *>(s_low)[lane * (PER / 4) + q];
-            tr += x.x + x.y + x.z + x.w; tl += y.x + y.y + y.z + y.w;
+            const uint4 xq = reinterpret_cast<const uint4 *>(s_raw)[lane * (PER / 4) + q];
+            const uint4 yq = reinterpret_cast<const uint4 *>(s_low)[lane * (PER / 4) + q];
+            tr += xq.x + xq.y + xq.z + xq.w; tl += yq.x + yq.y + yq.z + yq.w;
         }
     } else {
 #pragma unroll
-        for (int q = 0; q < NH / 4; ++q) {
-            const uint4 x = reinterpret_cast<const uint4 *>(s_raw)[lane * (NH / 4) + q];
-            const uint4 y = reinterpret_cast<const uint4 *>(s_low)[lane * (NH / 4) + q];
-            xr[4 * q] = x.x; xr[4 * q + 1] = x.y; xr[4 * q + 2] = x.z; xr[4 * q + 3] = x.w;
-            xl[4 * q] = y.x; xl[4 * q + 1] = y.y; xl[4 * q + 2] = y.z; xl[4 * q + 3] = y.w;
+        for (int q = 0; q < NX / 4; ++q) {
+            const uint4 xq = reinterpret_cast<const uint4 *>(s_diff)[lane * (NX / 4) + q];
+            x[4 * q] = xq.x; x[4 * q + 1] = xq.y; x[4 * q + 2] = xq.z; x[4 * q + 3] = xq.w;
         }
 #pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            tr = __builtin_amdgcn_sad_u16(xr[h], 0u, tr);
-            tl = __builtin_amdgcn_sad_u16(xl[h], 0u, tl);
-        }
-        tr = (uint32_t)(int32_t)(int16_t)(uint16_t)tr; tl = (uint32_t)(int32_t)(int16_t)(uint16_t)tl;
+        for (int i = 0; i < NX; ++i) tr += x[i];
     }
-    // (two's complement in 32 bits, so the two scans stay separate)
-    const uint32_t offr = dpp_incl_scan_u32(tr) - tr, offl = dpp_incl_scan_u32(tl) - tl;
+    // (two's complement in 32 bits; with DEEP the two scans stay separate)
+    const uint32_t offr = dpp_incl_scan_u32(tr) - tr;
+    uint32_t offl = 0u;
+    if constexpr (DEEP) offl = dpp_incl_scan_u32(tl) - tl;
 
     // raw_depth > 0, and the low-MAPQ rule (callable_profiler.rs:100-101): the two per-position tests, each a difference
     // whose sign bit says "no", shifted into a mask by v_alignbit ({mask, d} >> 31) as the running sums walk the lane's
@@ -386,31 +434,41 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
         // The byte of depth d: word d >> 2 of the table, held by that lane (a wrong lane's word beyond 255: not used).
         // Eight positions at a time: their depths first and the eight fetches behind each other, then the tests, so
         // that the wave waits for one round trip per eight positions and not for one per position.
-        uint32_t sr = offr, sl = offl, ncov = 0, nlow = 0;
+        //
+        // One running word s = raw | low << 16 serves all of it, its fields never split:
+        //   the fetch: ds_bpermute takes the lane from bits [7:2] of its address and nothing else, so it is given s
+        //     itself -- bits [7:2] of raw, raw >> 2 while raw < 256; v_alignbyte takes its byte count from bits [1:0]
+        //     of s, raw & 3, and turns the fetched word so that the byte of depth raw is its lowest;
+        //   raw > 0: (s << 16) - 0x10000 = (raw - 1) << 16, negative for raw == 0 only, because raw < 32 768 (bit 15
+        //     clear: raw << 16 is not negative itself).  The signed maximum of these words is that of raw - 1;
+        //   low >= threshold: (s >> 16) - (the turned word & 0xFF), written so that it is ONE subtraction with operand
+        //     selects (v_sub_u32_sdwa, word 1 of s and byte 0 of the turned word: read in the listing, no assembly).
+        uint32_t s = offr, ncov = 0, nlow = 0;
+        int32_t mc = -0x10000;                             // the largest (raw - 1) << 16 of the lane
         constexpr int B = 8;
 #pragma unroll
         for (int g = 0; g < PER; g += B) {
-            uint32_t r8[B], l8[B], t8[B];
+            uint32_t s8[B], t8[B];
 #pragma unroll
             for (int k = 0; k < B; ++k) {
-                const int i = g + k;
-                sr += (i & 1) ? (uint32_t)((int32_t)xr[i / 2] >> 16) : (xr[i / 2] & 0xFFFFu) - 0x8000u;
-                sl += (i & 1) ? (uint32_t)((int32_t)xl[i / 2] >> 16) : (xl[i / 2] & 0xFFFFu) - 0x8000u;
-                r8[k] = sr; l8[k] = sl;
-                t8[k] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(sr & ~3u), (int)wlut);
+                s += x[g + k];
+                s8[k] = s;
+                t8[k] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)s, (int)wlut);
             }
 #pragma unroll
             for (int k = 0; k < B; ++k) {
-                mx = r8[k] > mx ? r8[k] : mx;
-                const uint32_t thr = __builtin_amdgcn_ubfe(t8[k], r8[k] << 3, 8u);
-                ncov = __builtin_amdgcn_alignbit(ncov, r8[k] - 1u, 31);
-                nlow = __builtin_amdgcn_alignbit(nlow, l8[k] - thr, 31);
+                const uint32_t thr = __builtin_amdgcn_alignbyte(t8[k], t8[k], s8[k]) & 0xFFu;
+                const uint32_t dc = (s8[k] << 16) - 0x10000u;
+                mc = (int32_t)dc > mc ? (int32_t)dc : mc;
+                ncov = __builtin_amdgcn_alignbit(ncov, dc, 31);
+                nlow = __builtin_amdgcn_alignbit(nlow, (s8[k] >> 16) - thr, 31);
                 if (DEBUG) {
-                    if (a.dbg_raw) a.dbg_raw[p0 + g + k] = r8[k];
-                    if (a.dbg_low) a.dbg_low[p0 + g + k] = l8[k];
+                    if (a.dbg_raw) a.dbg_raw[p0 + g + k] = s8[k] & 0xFFFFu;
+                    if (a.dbg_low) a.dbg_low[p0 + g + k] = s8[k] >> 16;
                 }
             }
         }
+        mx = ((uint32_t)mc + 0x10000u) >> 16;
         covb = ~__builtin_bitreverse32(ncov); lowb = ~__builtin_bitreverse32(nlow);
     }
     if (DEEP || mx >= 255u) {
@@ -428,15 +486,14 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
             if (DEEP) {
                 dr[0] = s_raw[lane * PER + 2 * h]; dr[1] = s_raw[lane * PER + 2 * h + 1];
                 dl[0] = s_low[lane * PER + 2 * h]; dl[1] = s_low[lane * PER + 2 * h + 1];
-            } else {
-                const uint32_t xr = s_raw[lane * (PER / 2) + h], xl = s_low[lane * (PER / 2) + h];
-                dr[0] = (xr & 0xFFFFu) - 0x8000u; dr[1] = (uint32_t)((int32_t)xr >> 16);
-                dl[0] = (xl & 0xFFFFu) - 0x8000u; dl[1] = (uint32_t)((int32_t)xl >> 16);
+            } else {                                       // the packed words: sr is the running word, split per position
+                dr[0] = s_diff[lane * PER + 2 * h]; dr[1] = s_diff[lane * PER + 2 * h + 1];
+                dl[0] = dl[1] = 0u;
             }
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 sr += dr[k]; sl += dl[k];
-                const uint32_t raw = sr, low = sl;
+                const uint32_t raw = DEEP ? sr : sr & 0xFFFFu, low = DEEP ? sl : sr >> 16;
                 mx = raw > mx ? raw : mx;
                 uint32_t thr = a.lut[raw < kLutSize ? raw : kLutSize - 1u];
                 thr = thr < 0x7FFFFFFFu ? thr : 0x7FFFFFFFu;

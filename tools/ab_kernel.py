@@ -81,8 +81,8 @@ def main():
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", d, "--steps", str(a.steps), "--workload", a.workload],
                                env=env, capture_output=True, text=True, timeout=600)
             if p.returncode != 0:
-                print(l, "FAILED", p.stderr[-400:], flush=True)
-                continue
+                print(l, "FAILED", p.returncode, p.stderr[-400:], flush=True)
+                sys.exit(1)                                # (nothing more is started on a device after a child that failed)
             o = json.loads(p.stdout.strip().splitlines()[-1])
             if first is None:
                 first = (o["bed_md5"], o["sums"])
