@@ -3,7 +3,7 @@
 // Host side of the coverage engine: staging, uploads, kernel launches, event timing.  The work itself is in three headers:
 // pileup_rows.hip.h (k_pileup_rows, the pass-bit form: the product), pileup_bytes.hip.h (k_pileup, the byte forms of
 // DUT_QUAL_FORM=bytes) and kernels.hip.h (what both share: constants, the records between kernels and host, the wave
-// primitives, k_fin_windows and k_rle_write).  engine_base.hip.h holds the memory and transfer plumbing, site_engine.hip.h
+// primitives and k_tail, the one kernel behind the pileup).  engine_base.hip.h holds the memory and transfer plumbing, site_engine.hip.h
 // the site engine (all parts of this translation unit).  What needs no device of the way a tile of reads enters -- the
 // staged contig, the record of a push, the checks, the first pass over a tile and the whole walk of the pass-bit form -- is
 // tile_walk.h, plain C++ that the sanitizer driver runs; here are the entries, the byte forms' device side (prefetch,
@@ -49,7 +49,8 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     bool heads8_only = false;            // DUT_HEADS8=1 (a test hook): every contig gets 8-byte heads
     bool rows_uniform = false;           // DUT_ROWS_UNIFORM=1 (a test hook): every segment of a window as high as its highest
     bool heads4 = false;                 // the resident contig's heads are the 4-byte form (pileup_rows.hip.h: HEAD4)
-    uint64_t dev_sum_q = 0;          // of the resident contig: acc.host_sum_q at upload (handed to the summary workgroup of every run)
+    uint64_t dev_sum_q = 0;          // of the resident contig: acc.host_sum_q at upload (a start value of every run's summary: d_sum0)
+    uint32_t tail_max_chunks = kTailMaxChunks;   // most workgroups of k_tail (DUT_TAIL_CHUNKS: a test hook)
     uint32_t bounds_err = 0;             // kErrRange raised by the window bounds (reported by cl_contig_collect)
     uint32_t n_wide = 0;
 
@@ -66,20 +67,19 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     DevBuf<uint4> d_rows;            // pass-bit form: the windows' rows, units of 4 rows x 8 blocks (128 bytes each: pass_rows.h)
     uint64_t n_row_groups = 0;       // ... how many units
     uint32_t max_groups = 0;         // most units of any segment of any window: picks the number of counter planes of k_pileup_rows
-    DevBuf<uint32_t> d_win_off, d_wide_idx;
+    DevBuf<uint32_t> d_win_words, d_wide_idx;   // d_win_words: per window n_inner | first state << 16 | last state << 24 (kernels.hip.h)
     DevBuf<WinMeta> d_win;
     DevBuf<uint8_t> d_state;         // per-position states: allocated and written for debug dumps only
     DevBuf<uint16_t> d_runs;         // per window kT entries: run starts inside the window
-    DevBuf<uint8_t> d_first_state, d_last_state;
     DevBuf<uint8_t> d_win_wide;      // per window: sticky "needs 16-bit counter fields" mark (k_pileup)
     DevBuf<WinPartial> d_winpart;
-    DevBuf<FinPartial> d_fin;
     DevBuf<uint32_t> d_errflag;        // [0] error bits raised by the kernels of a run, [1] unused
     DevBuf<uint2> d_runtab;            // run-table form: the windows' match pieces (host_build_runs)
     uint64_t n_runtab = 0;
     DevBuf<uint32_t> d_lut;
     DevBuf<uint32_t> d_lut8;         // build_lut8's 64 words, what k_pileup_rows' fast path looks up
     DevBuf<DevSummary> d_summary;
+    DevBuf<DevSummary> d_sum0;       // the start values of a run's summary (filled at upload; the pileup's window 0 copies them)
     DevBuf<Interval> d_iv;
     DevBuf<uint32_t> d_dbg;          // 3 * n_win * T
     // cl_contig_depth_profile: {sum_raw, sum_qc}, hist_raw, hist_qc, win_raw, win_qc -- on the device and as copied back
@@ -98,9 +98,9 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     // is all of them but d_prof and the site engine's (they never were).  cl_destroy and cl_contig_layout walk this list.
     template <class F> void each_buffer(F &&f)
     {
-        f(d_pos); f(d_mapq); f(d_qual); f(d_ref); f(d_end); f(d_rec); f(d_heads); f(d_refn); f(d_rows); f(d_win_off); f(d_wide_idx);
-        f(d_win); f(d_state); f(d_runs); f(d_first_state); f(d_last_state); f(d_win_wide); f(d_winpart); f(d_fin); f(d_errflag);
-        f(d_runtab); f(d_lut); f(d_lut8); f(d_summary); f(d_iv); f(d_dbg); f(d_dr_win); f(d_dr_off); f(d_dr_out);
+        f(d_pos); f(d_mapq); f(d_qual); f(d_ref); f(d_end); f(d_rec); f(d_heads); f(d_refn); f(d_rows); f(d_win_words); f(d_wide_idx);
+        f(d_win); f(d_state); f(d_runs); f(d_win_wide); f(d_winpart); f(d_errflag);
+        f(d_runtab); f(d_lut); f(d_lut8); f(d_summary); f(d_sum0); f(d_iv); f(d_dbg); f(d_dr_win); f(d_dr_off); f(d_dr_out);
     }
     // the counter planes of k_pileup_rows and the depth kernels by the deepest window's rows (4 per group): 8 planes count to 255
     uint32_t counter_planes() const { return max_groups <= 63u ? 8u : max_groups <= 16383u ? 16u : 32u; }
@@ -752,9 +752,9 @@ cl_status stream_windows(cl_ctx *c, std::vector<WinMeta> &win)
 template <class F> void each_extent_buffer(cl_ctx *c, size_t n_win, bool pass_bits, F &&f)
 {
     const size_t padded = n_win * kT;
-    f(c->d_win, n_win + 1); f(c->d_win_off, n_win + 1); f(c->d_winpart, n_win + 1);
-    f(c->d_fin, n_win / kFinBlock + 2); f(c->d_runs, padded + 16);
-    f(c->d_first_state, n_win + 1); f(c->d_last_state, n_win + 1); f(c->d_win_wide, n_win + 1);
+    // (d_win_words: k_tail reads the words four at a time, so the array holds whole quads -- kernels.hip.h: quad_at)
+    f(c->d_win, n_win + 1); f(c->d_win_words, n_win + 4); f(c->d_winpart, n_win + 1);
+    f(c->d_runs, padded + 16); f(c->d_win_wide, n_win + 1);
     if (pass_bits) f(c->d_refn, padded / 32 + 4); else f(c->d_ref, padded + 16);
 }
 
@@ -768,6 +768,8 @@ cl_status size_for_extent(cl_ctx *c, uint32_t extent)
     each_extent_buffer(c, c->n_win, c->form == 3, [&](auto &buf, size_t n) { if (alloc == hipSuccess) alloc = buf.reserve(n); });
     HIP_TRY(c, alloc);
     HIP_TRY(c, hipMemsetAsync(c->d_win_wide.p, 0, c->n_win + 1, c->stream));
+    // (k_tail reads whole quads of packed words: the padding behind the last window's is never counted, and is zero)
+    HIP_TRY(c, hipMemsetAsync(c->d_win_words.p, 0, ((size_t)c->n_win + 4) * sizeof(uint32_t), c->stream));
     // reference bytes: [0,ref_len) from the caller, 'N' beyond (mod.rs:79-80).  The pass-bit form needs one bit of a
     // base -- is it 'N' / 'n' (mod.rs:100-101) --, taken here, where the bytes pass through the host's hands anyway:
     // 1/8 of the transfer, 1/8 of what every run reads
@@ -869,19 +871,48 @@ cl_status size_for_extent(cl_ctx *c, uint32_t extent)
     return CL_OK;
 }
 
-// what runs behind the pileup kernel: the windows' run lists -> intervals (scan + reduction over the windows, then one
-// wave per window and an extra workgroup for the contig summary)
-void launch_tail(cl_ctx *c)
+// The start values of a run's contig summary: zero counts, the host's separable sums (pass-bit form), the extent.
+DevSummary summary_start_values(const cl_ctx *c)
 {
-    const uint32_t n_fin = (c->n_win + kFinBlock - 1) / kFinBlock;
+    DevSummary s0{};
+    if (c->form == 3) { s0.summed_baseq = c->dev_sum_q; s0.summed_coverage = c->dev_sum_cov; s0.summed_mapq = c->dev_sum_mapq; }
+    s0.extent = c->extent;
+    return s0;
+}
+
+// windows per workgroup of k_tail: kTailMinWpc while that takes no more than `max_chunks` workgroups, else what fills
+// max_chunks, rounded up to a multiple of 16 (the kernel's waves) -- so that what every workgroup re-reads of the windows
+// before its own stays linear in the contig's length.  At most kTailMaxWpc, which a thread's four windows of the own
+// chunk cover: the cap yields to that (2^21 windows of 2 048 positions are the most a contig has: 4 096 at 512 chunks).
+uint32_t tail_wpc(uint32_t n_win, uint32_t max_chunks)
+{
+    if (max_chunks == 0u) max_chunks = 1u;
+    if ((n_win + kTailMinWpc - 1u) / kTailMinWpc <= max_chunks) return kTailMinWpc;
+    const uint64_t per = ((uint64_t)n_win + max_chunks - 1u) / max_chunks;
+    return (uint32_t)std::min<uint64_t>((per + 15u) & ~15ull, kTailMaxWpc);
+}
+
+// what runs behind the pileup kernel, one launch: the windows' run lists -> intervals, the windows' partials -> the
+// contig summary (k_tail).  `restart`: the summary's start values are copied by the stream (hipMemcpyAsync from d_sum0)
+// instead of by the pileup's window 0 -- the tail alone launched again (cl_contig_collect, a larger interval buffer: the
+// summary is accumulated, so it starts over); a contig without windows launches no pileup and gets them this way too.
+cl_status launch_tail(cl_ctx *c, bool restart)
+{
     const uint32_t cap = (uint32_t)std::min<size_t>(c->d_iv.cap, 0xFFFFFFFFu);
-    const unsigned long long sq = c->form == 3 ? c->dev_sum_q : 0ull, sc = c->form == 3 ? c->dev_sum_cov : 0ull, sm = c->form == 3 ? c->dev_sum_mapq : 0ull;
-    if (n_fin)
-        hipLaunchKernelGGL(k_fin_windows, dim3(n_fin), dim3(kFinBlock), 0, c->stream, c->d_winpart.p, c->d_first_state.p,
-                           c->d_last_state.p, kT, c->n_win, c->extent, c->d_win_off.p, c->d_fin.p);
-    hipLaunchKernelGGL((k_rle_write<(int)kT>), dim3((c->n_win + kBlock / 64 - 1) / (kBlock / 64) + 1), dim3(kBlock), 0, c->stream,
-                       c->d_runs.p, c->d_first_state.p, c->d_last_state.p, c->d_winpart.p, c->d_win_off.p, c->d_fin.p, n_fin,
-                       c->d_errflag.p, c->d_summary.p, c->n_win, c->extent, c->d_iv.p, cap, sq, sc, sm);
+    if (restart || c->n_win == 0)
+        HIP_TRY(c, hipMemcpyAsync(c->d_summary.p, c->d_sum0.p, sizeof(DevSummary), hipMemcpyDeviceToDevice, c->stream));
+    if (c->n_win == 0) {                                 // nothing to classify: the flags, as the tail leaves them
+        HIP_TRY(c, hipMemsetAsync(c->d_errflag.p, 0, 2 * sizeof(uint32_t), c->stream));
+        return CL_OK;
+    }
+    const uint32_t wpc = tail_wpc(c->n_win, c->tail_max_chunks);
+    // the summary's workgroups, in front of the grid: kTailSumWindows windows each, at most kTailMaxSum of them
+    const uint32_t n_sum = std::min((c->n_win + kTailSumWindows - 1u) / kTailSumWindows, kTailMaxSum);
+    const uint32_t wps = (c->n_win + n_sum - 1u) / n_sum;
+    hipLaunchKernelGGL((k_tail<(int)kT>), dim3(n_sum + (c->n_win + wpc - 1) / wpc), dim3(kTailBlock), 0, c->stream,
+                       c->d_runs.p, c->d_win_words.p, c->d_winpart.p, c->d_errflag.p, c->d_summary.p, c->n_win, c->extent, wpc,
+                       n_sum, wps, c->d_iv.p, cap);
+    return CL_OK;
 }
 
 // What a launch of either pileup kernel is given: one aggregate initialisation in the record's member order, so that a
@@ -893,7 +924,8 @@ BytesArgs bytes_args(const cl_ctx *c, uint32_t *dbg_raw, uint32_t *dbg_qc, uint3
     return BytesArgs{
         Reads{c->d_pos.p, c->d_mapq.p, c->d_qual.p + kQualPad, c->n_reads}, c->dopt,
         c->d_rec.p, c->d_end.p, c->d_win.p, c->d_wide_idx.p, c->d_ref.p, c->d_lut.p, c->d_runtab.p,
-        c->d_state.p, c->d_runs.p, c->d_first_state.p, c->d_last_state.p, c->d_winpart.p,
+        c->d_state.p, c->d_runs.p, c->d_win_words.p, c->d_winpart.p,
+        reinterpret_cast<unsigned long long *>(c->d_summary.p), reinterpret_cast<const unsigned long long *>(c->d_sum0.p),
         c->extent, c->n_win, (c->n_win + 7) / 8, dbg_raw, dbg_qc, dbg_low,
         (c->n_reads && c->n_qual <= 128ull * c->n_reads) ? 2u : 3u,   // upl: by the mean read length
         c->d_win_wide.p, c->d_errflag.p};
@@ -902,7 +934,8 @@ RowsArgs rows_args(const cl_ctx *c, uint32_t *dbg_raw, uint32_t *dbg_qc, uint32_
 {
     return RowsArgs{
         c->d_rows.p, c->d_heads.p, c->d_wide_idx.p, c->d_win.p, c->d_refn.p, c->d_lut8.p,
-        c->d_runs.p, c->d_first_state.p, c->d_last_state.p, c->d_winpart.p,
+        c->d_runs.p, c->d_win_words.p, c->d_winpart.p,
+        reinterpret_cast<unsigned long long *>(c->d_summary.p), reinterpret_cast<const unsigned long long *>(c->d_sum0.p),
         c->extent, c->n_win, (c->n_win + 7) / 8, c->opt.min_depth, c->opt.max_depth,
         c->opt.min_depth_for_low_mapq, c->d_lut.p, c->opt.max_low_mapq_fraction,
         c->d_state.p, dbg_raw, dbg_qc, dbg_low};
@@ -942,7 +975,7 @@ cl_status enqueue(cl_ctx *c, bool debug, uint32_t *dbg_raw, uint32_t *dbg_qc, ui
         if (s != CL_OK) return s;
     }
     hipEvent_t *ev = c->ev[c->ev_pending < cl_ctx::kEvSets ? c->ev_pending : 0];
-    // d_errflag is zero here: cleared at upload, and by the summary workgroup at the end of every run
+    // d_errflag is zero here: cleared at upload, and by k_tail at the end of every run
     // (a run has no per-read kernel: the read ends and CIGAR checkpoints the long-read forms need are an index the host
     // built at upload; CL_K_PREP stays in the timing table as an empty slot)
     if (prof) HIP_TRY(c, hipEventRecord(ev[0], c->stream));
@@ -955,7 +988,7 @@ cl_status enqueue(cl_ctx *c, bool debug, uint32_t *dbg_raw, uint32_t *dbg_qc, ui
         if (debug) launch_bytes<true>(c, a); else launch_bytes<false>(c, a);
     }
     if (prof) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-    launch_tail(c);
+    { const cl_status ts = launch_tail(c, false); if (ts != CL_OK) return ts; }
     if (prof) {
         HIP_TRY(c, hipEventRecord(ev[2], c->stream));
         c->ev_pending += 1;
@@ -1031,6 +1064,9 @@ cl_status cl_create(const cl_options *opt, int device_id, void *stream, cl_ctx *
     // DUT_HEAD_SPAN (a test hook): spans beyond this many positions are cut into several heads -- 2^31 - 1 in earnest, which
     // only a contig of more than 2 Gb can hold; the tests put the seams into ordinary reads
     { const char *h8 = getenv("DUT_HEADS8"); c->heads8_only = h8 && *h8 == '1'; }   // (a test hook: both head forms on one input)
+    // DUT_TAIL_CHUNKS=<n> (a test hook, and a column of A/B runs): the most workgroups k_tail gets, instead of kTailMaxChunks --
+    // with a small n a few hundred windows reach more than 64 windows per workgroup and a ragged last chunk
+    { const char *tc = getenv("DUT_TAIL_CHUNKS"); if (tc) { const unsigned long long v = strtoull(tc, nullptr, 0); if (v >= 1 && v <= 65535) c->tail_max_chunks = (uint32_t)v; } }
     c->rows_uniform = rows_uniform_env();
     { const char *hs = getenv("DUT_HEAD_SPAN"); if (hs) { const unsigned long long v = strtoull(hs, nullptr, 0); if (v >= 1 && v <= kHeadSpanMax) c->head_span = (uint32_t)v; } }
     if (hipSetDevice(device_id) != hipSuccess) { delete c; return CL_ERR_DEVICE; }
@@ -1055,7 +1091,7 @@ cl_status cl_create(const cl_options *opt, int device_id, void *stream, cl_ctx *
     uint32_t lut8[64];
     build_lut8(lut, opt->min_depth_for_low_mapq, lut8);
     bool ok = c->d_lut.reserve(kLutSize) == hipSuccess && c->d_lut8.reserve(64) == hipSuccess &&
-              c->d_summary.reserve(1) == hipSuccess && c->d_errflag.reserve(2) == hipSuccess &&
+              c->d_summary.reserve(1) == hipSuccess && c->d_sum0.reserve(1) == hipSuccess && c->d_errflag.reserve(2) == hipSuccess &&
               hipMemcpy(c->d_lut.p, lut.data(), kLutSize * sizeof(uint32_t), hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(c->d_lut8.p, lut8, sizeof(lut8), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok || ensure_pins(c) != CL_OK) { cl_destroy(c); return CL_ERR_DEVICE; }
@@ -1515,6 +1551,10 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     cl_status s = size_for_extent(c, (uint32_t)std::max<uint64_t>(c->contig_len, c->acc.host_max_end));
     if (s != CL_OK) return s;
     tmr.lap("upload: extent, ref, bounds");
+    {   // the start values of every run's summary (the stream is idle: size_for_extent ended with a sync)
+        const DevSummary s0 = summary_start_values(c);
+        HIP_TRY(c, hipMemcpy(c->d_sum0.p, &s0, sizeof(DevSummary), hipMemcpyHostToDevice));
+    }
     if (c->d_iv.cap == 0) HIP_TRY(c, c->d_iv.reserve(1u << 20));
     // The staged copy is no longer needed; its memory goes to the process's staging pool for the next contig, this
     // context's or another's (giving back and re-faulting a few hundred megabytes per contig was a fifth of a contig's
@@ -1703,7 +1743,8 @@ cl_status cl_contig_collect(cl_ctx *c, cl_contig_summary *out, const cl_interval
             // end, mod.rs:100-101: the extent was sized for that at upload from the ends computed at cl_push_reads)
             if (c->h_sum.n_intervals > c->d_iv.cap) {
                 HIP_TRY(c, c->d_iv.reserve(c->h_sum.n_intervals));
-                launch_tail(c);
+                s = launch_tail(c, true);
+                if (s != CL_OK) return s;
                 HIP_TRY(c, hipGetLastError());
             }
             converged = true;
@@ -1831,6 +1872,7 @@ cl_status cl_contig_layout(cl_ctx *c, cl_layout_info *out)
     else if (c->form == 0) h += c->n_qual + ((uint64_t)c->n_rec + 1) * sizeof(ReadRec);
     else h += c->n_qual + c->n_runtab * 8 + (uint64_t)c->n_reads * 9;
     out->upload_h2d_bytes = h;
+    if (c->n_win) { out->tail_wpc = tail_wpc(c->n_win, c->tail_max_chunks); out->tail_chunks = (c->n_win + out->tail_wpc - 1u) / out->tail_wpc; }
     return CL_OK;
 }
 

@@ -6,7 +6,9 @@
 // These are the forms of rounds 1-3.  The product runs k_pileup_rows (pileup_rows.hip.h); this kernel is kept as round 3
 // left it -- its experiment hooks are gone, their results are in DESIGN.md section 5 and profiles/r02_*, r03_* -- so that
 // bench.py's byte_form leg and the tests that run both forms stay reproducible.  It shares with k_pileup_rows what
-// kernels.hip.h holds and nothing else.
+// kernels.hip.h holds and nothing else.  (Since the tail is one launch it differs from round 3's by exactly what that
+// needs of either pileup: ONE store of the window's packed word where the two state bytes were stored, and the copy of
+// the summary's start values by the workgroup of window 0.)
 #pragma once
 #include "kernels.hip.h"
 #include <type_traits>
@@ -80,8 +82,10 @@ struct BytesArgs {
     const uint2    *runtab;       // run-table form (LONG = 2): per window, the M/=/X pieces of its reads (host, at upload)
     uint8_t        *state;        // n_win*T bytes; written by the DEBUG instantiation only (test dumps)
     uint16_t       *runs;         // per window T entries: the run starts strictly inside the window, rel. position | state << 12
-    uint8_t        *first_state, *last_state;   // per window: state of its first / last position (run seams)
+    uint32_t       *win_words;    // per window: n_inner | first state << 16 | last state << 24 (kernels.hip.h: win_word; run seams)
     WinPartial     *winpart;
+    unsigned long long *summary;  // the contig summary as 16 words, and the start values of a run (callable_loci.hip: d_sum0):
+    const unsigned long long *summary_start;   // the workgroup of window 0 copies them (kernels.hip.h: summary_start)
     uint32_t        extent;       // positions >= extent are not classified
     uint32_t        n_win;
     uint32_t        n_win8;       // ceil(n_win/8): XCD-contiguous window ranges
@@ -541,6 +545,7 @@ __global__ __launch_bounds__(kBlock, DEEP ? 4 : 8) void k_pileup(BytesArgs a)
     __syncthreads();
 
     // ---- final phase: depths, low-MAPQ rule, state, counts (8 positions per thread) ----
+    uint32_t first_st = 0;
     {
         uint32_t vr[PER], vl[PER];
         uint32_t sr = 0, sl = 0;
@@ -737,7 +742,7 @@ __global__ __launch_bounds__(kBlock, DEEP ? 4 : 8) void k_pileup(BytesArgs a)
         }
         __syncthreads();
         // the window's run list: every run start strictly inside the window, in position order
-        // (k_rle_write turns the lists into intervals; the per-position states never reach HBM)
+        // (k_tail turns the lists into intervals; the per-position states never reach HBM)
         {
             const uint32_t inc = dpp_incl_scan_u32(nb);
             if (nb) {
@@ -750,8 +755,7 @@ __global__ __launch_bounds__(kBlock, DEEP ? 4 : 8) void k_pileup(BytesArgs a)
                     for (int j = 0; j < 4; ++j)
                         if ((bmk[h] >> (8 * j)) & 1u) *dst++ = (uint16_t)((tid * PER + 4 * h + j) | (((S[h] >> (8 * j)) & 7u) << 12));
             }
-            if (tid == 0) a.first_state[w] = (uint8_t)(S[0] & 0xFFu);
-            if (tid == kBlock - 1) a.last_state[w] = (uint8_t)(S[PER / 4 - 1] >> 24);
+            first_st = S[0] & 0xFFu;                                             // (thread 0's is the window's)
         }
     }
     if (tid == 0) {
@@ -766,8 +770,11 @@ __global__ __launch_bounds__(kBlock, DEEP ? 4 : 8) void k_pileup(BytesArgs a)
         for (int i = 0; i < kWaves; ++i) m = s_wmax[i] > m ? s_wmax[i] : m;
         wp.max_raw = m;
         a.winpart[w] = wp;
+        // the window's packed word for the tail (s_last: every thread's last state, written before the barriers above)
+        a.win_words[w] = win_word(wp.n_inner, first_st, (uint32_t)s_last[kBlock - 1]);
         if (!DEEP && mode8 && (kByDepth || n_cand > 510u) && m > 255u) { a.win_wide[w] = 1; atomicOr(a.err_flag, kNeedWide8); }
     }
+    if (w == 0u) summary_start(a.summary, a.summary_start, tid);
 }
 
 } // namespace clk

@@ -213,8 +213,10 @@ struct RowsArgs {
                                   // path fetches the word of a depth with ds_bpermute, which takes the lane from bits [7:2]
                                   // of its address only, so it is handed the packed word raw | low << 16 as it is
     uint16_t       *runs;
-    uint8_t        *first_state, *last_state;
+    uint32_t       *win_words;    // per window: n_inner | first state << 16 | last state << 24 (kernels.hip.h: win_word)
     WinPartial     *winpart;
+    unsigned long long *summary;  // the contig summary as 16 words, and the start values of a run (callable_loci.hip: d_sum0):
+    const unsigned long long *summary_start;   // the workgroup of window 0 copies them (kernels.hip.h: summary_start)
     uint32_t        extent, n_win, n_win8;
     uint32_t        min_depth, max_depth;
     // the general path (a thread that sees a depth of 255 or more, or DEEP)
@@ -554,8 +556,6 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
                 *dst++ = (uint16_t)((lane * PER + j) | (state_at(j) << 12));
             }
         }
-        if (lane == 0) a.first_state[w] = (uint8_t)state_at(0u);
-        if (lane == kBlock - 1) a.last_state[w] = (uint8_t)last_st;
     }
     // ---- the window's partial: twelve 8-byte words, lane k writes word k -- word k < 9 is total k (cnt[6], n_cov,
     //      sum_qc, sum_q), words 9 and 10 are sum_reflen and sum_mapq_reflen (zero, as sum_q: the reads' separable sums
@@ -580,7 +580,11 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
             const uint32_t vhi = lane == 7u ? (uint32_t)(qc >> 32) : (lane == 11u ? mx : 0u);
             reinterpret_cast<unsigned long long *>(a.winpart + w)[lane] = (unsigned long long)vlo | ((unsigned long long)vhi << 32);
         }
+        // the window's packed word for the tail: n_inner is wave-uniform, the first state is lane 0's, the last lane 63's
+        const uint32_t last_w = (uint32_t)__builtin_amdgcn_readlane((int)last_st, kBlock - 1);
+        if (lane == 0) a.win_words[w] = win_word(pk3 >> 16, state_at(0u), last_w);
     }
+    if (w == 0u) summary_start(a.summary, a.summary_start, lane);   // (a scalar branch)
 }
 
 } // namespace clk

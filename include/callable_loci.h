@@ -274,6 +274,8 @@ typedef struct cl_layout_info {
     uint64_t run_table_entries;   /* byte form 2                                                                 */
     uint64_t device_bytes;        /* capacity of every device buffer of the context                              */
     uint64_t upload_h2d_bytes;    /* what cl_contig_upload (byte forms: and cl_push_reads) sent over the link    */
+    uint32_t tail_wpc;            /* windows per chunk of the tail kernel, and how many chunks it launches (0, 0  */
+    uint32_t tail_chunks;         /* for a contig without windows); DUT_TAIL_CHUNKS caps the chunks: a test hook   */
 } cl_layout_info;
 cl_status cl_contig_layout(cl_ctx *ctx, cl_layout_info *out);
 

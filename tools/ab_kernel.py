@@ -88,7 +88,7 @@ def main():
                 first = (o["bed_md5"], o["sums"])
             same = (o["bed_md5"], o["sums"]) == first
             res[l].append(o.get("pileup", 0.0))
-            print(os.path.basename(l), "pileup_ms", o.get("pileup"), "step_ms", o["ms_step"], "first_pass_s", o.get("first_pass_s"), "form", o.get("form"),
+            print(os.path.basename(l), "pileup_ms", o.get("pileup"), "tail_ms", o.get("rle"), "step_ms", o["ms_step"], "first_pass_s", o.get("first_pass_s"), "form", o.get("form"),
                   "groups", o.get("row_groups"), "max", o.get("max_groups"), "device_MB", o.get("device_mb"), "input_MB", o.get("input_mb"),
                   "same_as_first" if same else "DIFFERS", flush=True)
             if p.stderr.strip() and os.environ.get("DUT_TIMING") == "1":
