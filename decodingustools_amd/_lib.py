@@ -148,6 +148,20 @@ class dut_depth_bed_options(C.Structure):
     _fields_ = [("path", C.c_char_p), ("kind", C.c_uint32), ("edges", C.POINTER(C.c_uint32)), ("n_edges", C.c_uint32)]
 
 
+CL_TARGET_MAX_THRESHOLDS = 8
+CL_TARGETS_MAX = 1 << 24
+
+
+class cl_target_stats(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("len", C.c_uint32), ("reserved", C.c_uint32),
+                ("sum_raw", C.c_uint64), ("sum_qc", C.c_uint64), ("state", C.c_uint32 * 6),
+                ("ge_raw", C.c_uint32 * CL_TARGET_MAX_THRESHOLDS), ("ge_qc", C.c_uint32 * CL_TARGET_MAX_THRESHOLDS)]
+
+
+class dut_target_options(C.Structure):
+    _fields_ = [("bed_path", C.c_char_p), ("out_path", C.c_char_p), ("thresholds", C.POINTER(C.c_uint32)), ("n_thresholds", C.c_uint32)]
+
+
 class cl_scan_candidate(C.Structure):
     _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8), ("pad", C.c_uint8 * 2),
                 ("a", C.c_uint32), ("c", C.c_uint32), ("g", C.c_uint32), ("t", C.c_uint32), ("depth", C.c_uint32)]
@@ -488,6 +502,25 @@ SYMBOLS = [
                                          C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
                                          C.c_uint, C.POINTER(dut_depth_options), C.POINTER(dut_depth_bed_options), C.c_char_p,
                                          C.c_size_t]),
+    ("cl_contig_targets", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32),
+                                    C.c_uint32, C.POINTER(C.POINTER(cl_target_stats))]),
+    ("cl_contig_targets_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("dut_targets_parse", C.c_void_p, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
+    ("dut_targets_read", C.c_void_p, [C.c_char_p, C.c_char_p, C.c_size_t]),
+    ("dut_targets_free", None, [C.c_void_p]),
+    ("dut_targets_n_contigs", C.c_size_t, [C.c_void_p]),
+    ("dut_targets_contig", C.c_char_p, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("dut_targets_get", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
+                                  C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_uint32))]),
+    ("dut_thresholds_parse", C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]),
+    ("dut_targets_write_header", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
+    ("dut_targets_write", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(cl_target_stats), C.POINTER(C.c_char_p), C.c_size_t,
+                                    C.c_uint32, C.c_void_p]),
+    ("dut_targets_write_total", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("dut_coverage_files_ex3", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                         C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
+                                         C.c_uint, C.POINTER(dut_depth_options), C.POINTER(dut_depth_bed_options),
+                                         C.POINTER(dut_target_options), C.c_char_p, C.c_size_t]),
     ("cl_abi_version", C.c_int, []),
     ("cl_device_count", C.c_int, []),
     ("cl_create", C.c_int, [C.POINTER(cl_options), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -109,7 +109,8 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
                    summary_json: str = None, options: CallableOptions = None, contigs=None, device_id: int = 0,
                    output_summary: str = None, devices=None, depth_dist: str = None, depth_windows: str = None,
                    depth_summary: str = None, depth_cap: int = 1000, window: int = 0, depth_bed: str = None,
-                   depth_bed_kind: str = "raw", quantize: str = None):
+                   depth_bed_kind: str = "raw", quantize: str = None, targets: str = None, target_out: str = None,
+                   target_thresholds=None):
     """CoverageAnalyzer::analyze on files (CoverageInput of api/coverage.rs:124-132); summary_json
     receives the CoverageOutput JSON of main.rs:68-69; output_summary, when given, the HTML report
     (api/coverage.rs:104; None: not written, the JSON then names "summary.html").  The per-contig coverage
@@ -119,7 +120,9 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
     depth_dist / depth_windows (with window >= 16) / depth_summary: the depth profile files of dut_coverage_files_ex
     (formats: include/dut_coverage.h); depth_cap: depths above it share the last histogram bin.
     depth_bed: the per-base depth of every contig as a BED of runs of equal depth (dut_coverage_files_ex2);
-    depth_bed_kind "raw" or "qc"; quantize: band edges such as "1:4:100" (None or "": exact depth)."""
+    depth_bed_kind "raw" or "qc"; quantize: band edges such as "1:4:100" (None or "": exact depth).
+    targets: a BED of regions, target_out: the per-target table of dut_coverage_files_ex3 (include/dut_coverage.h has the
+    format); target_thresholds: up to 8 ascending depths (default 1, 10, 20, 30)."""
     lib = _lib.load()
     options = options or CallableOptions()
     oc = options.to_c()
@@ -131,6 +134,36 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
     err = C.create_string_buffer(1024)
     if depth_bed is None and (quantize is not None or depth_bed_kind != "raw"):
         raise EngineError(-1, "quantize and depth_bed_kind need depth_bed")
+    if targets is None and (target_out is not None or target_thresholds is not None):
+        raise EngineError(-1, "target_out and target_thresholds need targets")
+    if targets is not None and target_out is None:
+        raise EngineError(-1, "targets needs target_out")
+    if targets is not None:
+        thr = [int(t) for t in ((1, 10, 20, 30) if target_thresholds is None else target_thresholds)]
+        if any(t < 0 or t > 0xFFFFFFFF for t in thr):
+            raise EngineError(-1, "target_thresholds outside [0, 2^32 - 1]")
+        ta = (C.c_uint32 * max(len(thr), 1))(*thr)
+        to = _lib.dut_target_options(targets.encode(), target_out.encode(), ta, len(thr))
+        bo = None
+        if depth_bed is None and (quantize is not None or depth_bed_kind != "raw"):
+            raise EngineError(-1, "quantize and depth_bed_kind need depth_bed")
+        if depth_bed:
+            from .callable_loci import quantize_parse
+            if depth_bed_kind not in _lib.CL_DEPTH_KINDS:
+                raise EngineError(-1, f"depth_bed_kind {depth_bed_kind!r}: raw or qc")
+            edges = quantize_parse(quantize)
+            ea = (C.c_uint32 * max(len(edges), 1))(*edges)
+            bo = _lib.dut_depth_bed_options(depth_bed.encode(), _lib.CL_DEPTH_KINDS[depth_bed_kind], ea, len(edges))
+        dlist = [int(d) for d in devices] if devices is not None else [int(device_id)]
+        dv = (C.c_int * len(dlist))(*dlist)
+        enc = lambda p: p.encode() if p else None          # noqa: E731
+        do = _lib.dut_depth_options(int(depth_cap) + 1, int(window), enc(depth_dist), enc(depth_windows), enc(depth_summary))
+        st = lib.dut_coverage_files_ex3(bam_file.encode(), reference_file.encode(), output_bed.encode(), enc(summary_json),
+                                        enc(output_summary), C.byref(oc), arr, n, dv, len(dlist), 0, C.byref(do),
+                                        C.byref(bo) if bo is not None else None, C.byref(to), err, 1024)
+        if st != 0:
+            raise EngineError(st, err.value.decode())
+        return
     if depth_bed:
         from .callable_loci import quantize_parse
         if depth_bed_kind not in _lib.CL_DEPTH_KINDS:

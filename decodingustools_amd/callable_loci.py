@@ -468,6 +468,31 @@ class Engine:
         return DepthRuns(kind=int(r.kind), edges=e.copy(), extent=int(r.extent), n_runs=n, start=arr(r.start), value=arr(r.value),
                          kernel_ms=float(ms.value))
 
+    def target_stats(self, starts, ends, thresholds=(1, 10, 20, 30)):
+        """Depth and callable-base summaries of the resident contig over the targets [starts[i], ends[i]), 0-based half
+        open, in any order and overlapping at will (cl_contig_targets): a TargetStats of numpy arrays (copies), one entry
+        per target in the order given.  thresholds: up to 8 ascending depths, the first at least 1.  The contig must have
+        been collected (contig_collect or contig_finish) since its last run."""
+        def u32(v, what):
+            a = np.asarray(v)
+            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise EngineError(-1, f"target_stats: {what} outside [0, 2^32 - 1]")
+            return np.ascontiguousarray(a, np.uint32).reshape(-1)
+        s, e, t = u32(starts, "a start"), u32(ends, "an end"), u32(thresholds, "a threshold")
+        if s.size != e.size:
+            raise EngineError(-1, "target_stats: starts and ends differ in length")
+        u32p = C.POINTER(C.c_uint32)
+        out = C.POINTER(_lib.cl_target_stats)()
+        self._check(self._lib.cl_contig_targets(self._h, s.ctypes.data_as(u32p) if s.size else None, e.ctypes.data_as(u32p) if e.size else None,
+                                                int(s.size), t.ctypes.data_as(u32p) if t.size else None, int(t.size), C.byref(out)))
+        n = int(s.size)
+        rec = (np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), shape=(n * TARGET_STATS.itemsize,)).view(TARGET_STATS).copy()
+               if n else np.zeros(0, TARGET_STATS))
+        ms = C.c_double()
+        parts = (C.c_double * 3)()
+        self._check(self._lib.cl_contig_targets_ms(self._h, C.byref(ms), parts))
+        return TargetStats.from_records(rec, t.copy(), float(ms.value), tuple(float(x) for x in parts))
+
 
 # cl_scan_candidate as a numpy record: pos is 1-based, ref and alt are ASCII codes
 SCAN_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("alt", np.uint8), ("pad", np.uint8, (2,)), ("a", np.uint32),
@@ -686,6 +711,115 @@ class DepthRuns:
 
     def ends(self):
         return np.append(self.start[1:], np.uint32(self.extent)).astype(np.uint64) if self.n_runs else np.zeros(0, np.uint64)
+
+
+# cl_target_stats as a numpy record
+TARGET_STATS = np.dtype([("start", np.uint32), ("end", np.uint32), ("len", np.uint32), ("reserved", np.uint32),
+                         ("sum_raw", np.uint64), ("sum_qc", np.uint64), ("state", np.uint32, (6,)),
+                         ("ge_raw", np.uint32, (_lib.CL_TARGET_MAX_THRESHOLDS,)), ("ge_qc", np.uint32, (_lib.CL_TARGET_MAX_THRESHOLDS,))])
+assert TARGET_STATS.itemsize == C.sizeof(_lib.cl_target_stats)
+
+
+@dataclass
+class TargetStats:
+    """cl_target_stats per target (include/callable_loci.h), one array entry per target in the order given: start, end and
+    len clipped to the extent, the exact sums of raw and qc depth, state[i, s] = positions of CalledState s, and
+    ge_raw[i, k] / ge_qc[i, k] = positions with raw / qc depth >= thresholds[k]."""
+    thresholds: np.ndarray
+    start: np.ndarray
+    end: np.ndarray
+    len: np.ndarray
+    sum_raw: np.ndarray
+    sum_qc: np.ndarray
+    state: np.ndarray
+    ge_raw: np.ndarray
+    ge_qc: np.ndarray
+    kernel_ms: float = 0.0          # cl_contig_targets_ms: the three launches, while profiling is on
+    launch_ms: tuple = (0.0, 0.0, 0.0)   # ... k_target_depth, k_target_scan, k_target_finish apart
+
+    @classmethod
+    def from_records(cls, rec, thresholds, kernel_ms=0.0, launch_ms=(0.0, 0.0, 0.0)):
+        k = int(np.asarray(thresholds).size)
+        return cls(thresholds=np.asarray(thresholds, np.uint32), start=rec["start"].copy(), end=rec["end"].copy(), len=rec["len"].copy(),
+                   sum_raw=rec["sum_raw"].copy(), sum_qc=rec["sum_qc"].copy(), state=rec["state"].copy(),
+                   ge_raw=rec["ge_raw"][:, :k].copy(), ge_qc=rec["ge_qc"][:, :k].copy(), kernel_ms=kernel_ms, launch_ms=launch_ms)
+
+    def records(self):
+        """the cl_target_stats records (a TARGET_STATS array)"""
+        n, k = int(self.start.size), int(self.thresholds.size)
+        rec = np.zeros(n, TARGET_STATS)
+        for f in ("start", "end", "len", "sum_raw", "sum_qc", "state"):
+            rec[f] = getattr(self, f)
+        rec["ge_raw"][:, :k] = self.ge_raw
+        rec["ge_qc"][:, :k] = self.ge_qc
+        return rec
+
+
+def parse_targets(text):
+    """dut_targets_parse: BED text (str or bytes) -> a list of (contig, starts, ends, names) in the order the contigs
+    first appear, the targets of a contig in file order (starts and ends: numpy uint32; names: column 4, else ".").
+    Raises EngineError with the line number for a malformed line."""
+    lib = _lib.load()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    err = C.create_string_buffer(512)
+    h = lib.dut_targets_parse(raw, len(raw), err, 512)
+    if not h:
+        raise EngineError(-1, err.value.decode())
+    try:
+        out = []
+        for c in range(lib.dut_targets_n_contigs(h)):
+            n = C.c_size_t()
+            name = lib.dut_targets_contig(h, c, C.byref(n)).decode()
+            s, e, ln = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+            nm = C.POINTER(C.c_char_p)()
+            lib.dut_targets_get(h, c, C.byref(s), C.byref(e), C.byref(nm), C.byref(ln))
+            k = int(n.value)
+            out.append((name, np.ctypeslib.as_array(s, shape=(k,)).copy(), np.ctypeslib.as_array(e, shape=(k,)).copy(),
+                        [nm[i].decode() for i in range(k)]))
+        return out
+    finally:
+        lib.dut_targets_free(h)
+
+
+def thresholds_parse(spec):
+    """dut_thresholds_parse: the depth thresholds of a `--target-thresholds` argument ("1,10,20,30") as a list."""
+    t = (C.c_uint32 * _lib.CL_TARGET_MAX_THRESHOLDS)()
+    n = C.c_uint32()
+    err = C.create_string_buffer(256)
+    st = _lib.load().dut_thresholds_parse(spec.encode() if spec is not None else None, t, C.byref(n), err, 256)
+    if st != 0:
+        raise EngineError(st, err.value.decode())
+    return [int(t[i]) for i in range(n.value)]
+
+
+def write_target_stats(path, contigs, thresholds):
+    """dut_targets_write_header / dut_targets_write / dut_targets_write_total: the per-target table of include/dut_coverage.h.
+    contigs: (contig, TargetStats, names) in output order; the file ends with the `total` line over all of them."""
+    lib = _lib.load()
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    t = np.ascontiguousarray(thresholds, np.uint32).reshape(-1)
+    u32p = C.POINTER(C.c_uint32)
+    f = libc.fopen(path.encode(), b"wb")
+    if not f:
+        raise OSError("cannot open " + path)
+    total = (C.c_uint64 * 32)()                    # dut_target_total
+    st = lib.dut_targets_write_header(f, t.ctypes.data_as(u32p) if t.size else None, int(t.size))
+    for contig, stats, names in contigs:
+        rec = np.ascontiguousarray(stats.records())
+        n = int(rec.size)
+        nm = (C.c_char_p * max(n, 1))(*[(x or ".").encode() for x in names])
+        if st == 0:
+            st = lib.dut_targets_write(f, contig.encode(), rec.ctypes.data_as(C.POINTER(_lib.cl_target_stats)), nm, n, int(t.size),
+                                       C.cast(total, C.c_void_p))
+    if st == 0:
+        st = lib.dut_targets_write_total(f, C.cast(total, C.c_void_p), int(t.size))
+    if libc.fclose(f) != 0 and st == 0:
+        st = -1
+    if st != 0:
+        raise EngineError(st, "write_target_stats: cannot write " + path)
 
 
 def quantize_parse(spec):

@@ -14,6 +14,7 @@
 #include "pileup_rows.hip.h"
 #include "depth_profile.hip.h"
 #include "depth_runs.hip.h"
+#include "depth_targets.hip.h"
 #include "engine_base.hip.h"
 #include "site_engine.hip.h"
 #include "qual_pack.h"
@@ -36,6 +37,7 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
 
     // host staging of the current contig
     bool in_contig = false, uploaded = false, ran = false;
+    bool collected = false;          // cl_contig_collect has succeeded since the last cl_contig_run: d_iv holds all its intervals (cl_contig_targets)
     bool deep = false;               // this contig needs the 32-bit counter variant of k_pileup
     bool bits = true;                // the pass-bit form (default); DUT_QUAL_FORM=bytes at cl_create: the byte forms
     int form = 0;                    // the form of k_pileup the resident contig gets (pick_form, at upload)
@@ -94,6 +96,17 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     PinBuf<uint32_t> h_dr_out;
     KernelTimer t_dr_count, t_dr_write;   // count launch + scan, write launch (recorded while profiling is on)
     double dr_ms = 0.0;
+    // cl_contig_targets: what goes up (the points, the windows' ranges of them, the targets), the windows' totals (a record
+    // per window), their scanned offsets (a row per field), the prefixes at the points (a record per point), the records
+    // and the error word behind them -- and the records as copied back
+    DevBuf<uint32_t> d_tg_in, d_tg_out;
+    DevBuf<uint4> d_tg_pre;
+    DevBuf<ulonglong2> d_tg_win;
+    DevBuf<unsigned long long> d_tg_off;
+    std::vector<uint32_t> h_tg_in;
+    std::vector<cl_target_stats> h_tg_out;
+    KernelTimer t_tg[3];                  // k_target_depth, k_target_scan, k_target_finish (recorded while profiling is on)
+    double tg_ms[3] = {0.0, 0.0, 0.0};
     // The device buffers of the context, listed once: f(buffer) for each one that cl_layout_info.device_bytes counts, which
     // is all of them but d_prof and the site engine's (they never were).  cl_destroy and cl_contig_layout walk this list.
     template <class F> void each_buffer(F &&f)
@@ -1111,7 +1124,9 @@ void cl_destroy(cl_ctx *c)
     tmr.lap("destroy: sync");
     c->each_buffer([](auto &buf) { buf.release(); });
     c->d_prof.release(); c->site.release(); c->h_dr_out.release();
+    c->d_tg_in.release(); c->d_tg_pre.release(); c->d_tg_out.release(); c->d_tg_win.release(); c->d_tg_off.release();
     c->t_prof.destroy(); c->t_dr_count.destroy(); c->t_dr_write.destroy();
+    for (KernelTimer &t : c->t_tg) t.destroy();
     if (c->ev_made)
         for (auto &set : c->ev)
             for (hipEvent_t e : set) (void)hipEventDestroy(e);
@@ -1143,7 +1158,7 @@ cl_status cl_contig_begin(cl_ctx *c, int32_t tid, uint32_t contig_len, const uin
         c->hs.ref.append(ref_bases, nref); c->hs.cigar_off.push_back(0u); c->hs.qual_off.push_back(0ull);
         c->h_iv.clear();
         c->n_wide = 0; c->bounds_err = 0;
-        c->in_contig = true; c->uploaded = false; c->ran = false;
+        c->in_contig = true; c->uploaded = false; c->ran = false; c->collected = false;
         return CL_OK;
     });
 }
@@ -1561,7 +1576,7 @@ static cl_status cl_contig_upload_impl(cl_ctx *c)
     // host time).
     give_staging(c->hs);
     tmr.lap("upload: done");
-    c->uploaded = true; c->ran = false;
+    c->uploaded = true; c->ran = false; c->collected = false;
     return CL_OK;
 }
 
@@ -1685,6 +1700,7 @@ cl_status cl_contig_run(cl_ctx *c)
     Range rg("cl_contig_run");
     if (!c || !c->uploaded) return fail(c, CL_ERR_INVALID, "cl_contig_run before cl_contig_upload");
     HIP_TRY(c, hipSetDevice(c->device));
+    c->collected = false;
     cl_status s = enqueue(c, false, nullptr, nullptr, nullptr);
     if (s == CL_OK) c->ran = true;
     return s;
@@ -1765,6 +1781,7 @@ cl_status cl_contig_collect(cl_ctx *c, cl_contig_summary *out, const cl_interval
         }
         if (intervals) *intervals = c->h_iv.data();
         if (n_intervals) *n_intervals = niv;
+        c->collected = true;
         return CL_OK;
     });
 }
@@ -1793,7 +1810,7 @@ cl_status cl_contig_abort(cl_ctx *c)
         if (c->stream) (void)hipStreamSynchronize(c->stream);
     }
     drop_staged(c);
-    c->in_contig = false; c->uploaded = false; c->ran = false;
+    c->in_contig = false; c->uploaded = false; c->ran = false; c->collected = false;
     return CL_OK;
 }
 
@@ -2043,6 +2060,147 @@ cl_status cl_contig_depth_runs(cl_ctx *c, uint32_t kind, const uint32_t *edges, 
         out->kind = kind; out->n_edges = n_edges; out->extent = c->extent; out->n_runs = total;
         out->start = total ? c->h_dr_out.p : nullptr;
         out->value = total ? c->h_dr_out.p + total : nullptr;
+        return CL_OK;
+    });
+}
+
+// Depth and state summaries of the resident contig over a list of targets (include/callable_loci.h): the host sorts the
+// distinct query points that lie inside a window, k_target_depth takes the windows' totals and the prefixes at the points,
+// k_target_scan the offsets, k_target_finish the records (depth_targets.hip.h).  Nothing of a run is touched: summary,
+// intervals and window partials stay.
+cl_status cl_contig_targets_ms(cl_ctx *c, double *kernel_ms, double launch_ms[3])
+{
+    if (!c || !kernel_ms) return CL_ERR_INVALID;
+    *kernel_ms = c->tg_ms[0] + c->tg_ms[1] + c->tg_ms[2];
+    if (launch_ms) for (int i = 0; i < 3; ++i) launch_ms[i] = c->tg_ms[i];
+    return CL_OK;
+}
+
+cl_status cl_contig_targets(cl_ctx *c, const uint32_t *starts, const uint32_t *ends, size_t n_targets,
+                            const uint32_t *thresholds, uint32_t n_thresholds, const cl_target_stats **out)
+{
+    return guarded(c, [&]() -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null result");
+        *out = nullptr;
+        if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
+        if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_targets serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
+        if (n_targets > CL_TARGETS_MAX) return fail(c, CL_ERR_INVALID, "cl_contig_targets: more than 2^24 targets");
+        if (n_targets && (!starts || !ends)) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null starts or ends");
+        if (n_thresholds > CL_TARGET_MAX_THRESHOLDS) return fail(c, CL_ERR_INVALID, "cl_contig_targets: more than 8 thresholds");
+        if (n_thresholds && !thresholds) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null thresholds");
+        if (n_thresholds && thresholds[0] == 0u) return fail(c, CL_ERR_INVALID, "cl_contig_targets: the first threshold is 0 (every position has a depth of at least 0)");
+        for (uint32_t i = 1; i < n_thresholds; ++i)
+            if (thresholds[i] <= thresholds[i - 1]) return fail(c, CL_ERR_INVALID, "cl_contig_targets: the thresholds are not strictly ascending");
+        for (size_t i = 0; i < n_targets; ++i)
+            if (starts[i] > ends[i]) return fail(c, CL_ERR_INVALID, "cl_contig_targets: target " + std::to_string(i) + " has start > end");
+        if (!c->uploaded || !c->ran || !c->collected || c->form != 3)
+            return fail(c, CL_ERR_INVALID, "cl_contig_targets needs a contig that has been collected since its last run (cl_contig_collect or cl_contig_finish)");
+        if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
+        HIP_TRY(c, hipSetDevice(c->device));
+        for (double &m : c->tg_ms) m = 0.0;
+        if (n_targets == 0) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return CL_OK; }
+        const size_t n = n_targets, nw = c->n_win;
+        const uint32_t K = n_thresholds, V = 2u + 2u * K, extent = c->extent;
+        try { c->h_tg_out.assign(n, cl_target_stats{}); } catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "cl_contig_targets: the records"); }
+        static_assert(sizeof(cl_target_stats) == kTargetWords * sizeof(uint32_t), "record layout");
+        const size_t niv = c->h_sum.n_intervals;
+        // ---- the query points inside a window, ascending and distinct; per window its range of them; per target its two slots ----
+        std::vector<uint32_t> &h = c->h_tg_in;
+        std::vector<uint32_t> pts;
+        size_t n_live = 0;
+        try {
+            pts.reserve(2 * n);
+            for (size_t i = 0; i < n; ++i) {
+                const uint32_t e = std::min(ends[i], extent), s = std::min(starts[i], e);
+                if (s == e) continue;
+                ++n_live;
+                if (s % kT) pts.push_back(s);
+                if (e % kT) pts.push_back(e);
+            }
+            std::sort(pts.begin(), pts.end());
+            pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+            // layout of the upload: pt[n_pt], pt_first[nw + 1], tg[n][4]
+            h.assign(pts.size() + nw + 1 + 4 * n, 0u);
+        } catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "cl_contig_targets: the query points"); }
+        const size_t n_pt = pts.size();
+        if (n_pt) memcpy(h.data(), pts.data(), n_pt * sizeof(uint32_t));
+        uint32_t *pt_first = h.data() + n_pt, *tg = pt_first + nw + 1;
+        {
+            size_t j = 0;
+            for (size_t w = 0; w <= nw; ++w) {             // (every point is below extent <= nw * kT, or extent itself inside the last window)
+                while (j < n_pt && pts[j] < (uint64_t)w * kT) ++j;
+                pt_first[w] = (uint32_t)j;
+            }
+            pt_first[nw] = (uint32_t)n_pt;
+        }
+        auto slot_of = [&](uint32_t q) -> uint32_t {
+            if (q % kT == 0) return kTargetNoSlot;
+            return (uint32_t)(std::lower_bound(pts.begin(), pts.end(), q) - pts.begin());
+        };
+        for (size_t i = 0; i < n; ++i) {
+            const uint32_t e = std::min(ends[i], extent), s = std::min(starts[i], e);
+            tg[4 * i] = s; tg[4 * i + 1] = e;
+            tg[4 * i + 2] = s == e ? kTargetNoSlot : slot_of(s);   // (an empty target asks nothing)
+            tg[4 * i + 3] = s == e ? kTargetNoSlot : slot_of(e);
+        }
+        uint32_t err = 0u;
+        if (n_live == 0 || nw == 0) {
+            // (nothing to measure: every record is its clipped ends and zeros)
+            for (size_t i = 0; i < n; ++i) { c->h_tg_out[i].start = tg[4 * i]; c->h_tg_out[i].end = tg[4 * i + 1]; }
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            *out = c->h_tg_out.data();
+            return CL_OK;
+        }
+        // (none cannot cover the positions; the finish kernel indexes the intervals in 32 bits, 512 ahead)
+        if (niv == 0 || niv > 0x7FFFFFFFu || niv > c->d_iv.cap) return fail(c, CL_ERR_INTERNAL, "cl_contig_targets: the collected contig has no interval, or more than the device holds");
+        HIP_TRY(c, c->d_tg_in.reserve(h.size()));
+        HIP_TRY(c, c->d_tg_win.reserve((size_t)(kTargetTotSlots / 2) * nw));
+        HIP_TRY(c, c->d_tg_off.reserve((size_t)V * (nw + 1)));
+        HIP_TRY(c, c->d_tg_pre.reserve((size_t)(kTargetPreWords / 4) * std::max<size_t>(n_pt, 1)));
+        HIP_TRY(c, c->d_tg_out.reserve((size_t)kTargetWords * n + 1));
+        uint32_t *d_err = c->d_tg_out.p + (size_t)kTargetWords * n;
+        HIP_TRY(c, hipMemcpyAsync(c->d_tg_in.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_tg_out.p, 0, ((size_t)kTargetWords * n + 1) * sizeof(uint32_t), c->stream));
+        TargetArgs a;
+        memset(&a, 0, sizeof(a));
+        a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
+        a.extent = extent; a.n_win = c->n_win; a.n_pt = (uint32_t)n_pt;
+        a.pt = c->d_tg_in.p;                                 // (pt_first follows the points)
+        a.wtot = c->d_tg_win.p; a.pre = c->d_tg_pre.p; a.err = d_err;
+        for (uint32_t k = 0; k < CL_TARGET_MAX_THRESHOLDS; ++k) a.thr[k] = k < K ? thresholds[k] : 0xFFFFFFFFu;
+        // workgroups that stay, as k_depth_profile's: a window is a few microseconds of work
+        const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
+        if (c->profiling) HIP_TRY(c, c->t_tg[0].start(c->stream));
+#define CL_LAUNCH(NP_) do { \
+        if (c->heads4) hipLaunchKernelGGL((k_target_depth<NP_, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a); \
+        else hipLaunchKernelGGL((k_target_depth<NP_, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a); } while (0)
+        if (c->counter_planes() == 8u) CL_LAUNCH(8);
+        else if (c->counter_planes() == 16u) CL_LAUNCH(16);
+        else CL_LAUNCH(32);
+#undef CL_LAUNCH
+        HIP_TRY(c, hipGetLastError());
+        if (c->profiling) { HIP_TRY(c, c->t_tg[0].stop(c->stream)); HIP_TRY(c, c->t_tg[1].start(c->stream)); }
+        unsigned long long *d_off = c->d_tg_off.p;
+        hipLaunchKernelGGL(k_target_scan, dim3(V), dim3(kTargetScanBlock), 0, c->stream, reinterpret_cast<const unsigned long long *>(c->d_tg_win.p), c->n_win, K, d_off);
+        HIP_TRY(c, hipGetLastError());
+        if (c->profiling) { HIP_TRY(c, c->t_tg[1].stop(c->stream)); HIP_TRY(c, c->t_tg[2].start(c->stream)); }
+        TargetFinishArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.tg = c->d_tg_in.p + n_pt + nw + 1; fa.n = (uint32_t)n; fa.n_pt = (uint32_t)n_pt; fa.n_thr = K; fa.n_win = c->n_win;
+        fa.off = d_off; fa.pre = reinterpret_cast<const uint32_t *>(c->d_tg_pre.p); fa.iv = c->d_iv.p; fa.n_iv = (uint32_t)std::min<size_t>(niv, c->d_iv.cap); fa.extent = extent;
+        fa.out = c->d_tg_out.p; fa.err = d_err;
+        const uint32_t per = (uint32_t)(kTargetFinishBlock / 64);
+        hipLaunchKernelGGL(k_target_finish, dim3((uint32_t)((n + per - 1) / per)), dim3(kTargetFinishBlock), 0, c->stream, fa);
+        HIP_TRY(c, hipGetLastError());
+        if (c->profiling) HIP_TRY(c, c->t_tg[2].stop(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_tg_out.data(), c->d_tg_out.p, n * sizeof(cl_target_stats), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->profiling)
+            for (int i = 0; i < 3; ++i) { HIP_TRY(c, c->t_tg[i].read()); c->tg_ms[i] = c->t_tg[i].ms; }
+        if (err) return fail(c, CL_ERR_INTERNAL, "cl_contig_targets: a device-side check of the uploaded points, slots or intervals failed");
+        *out = c->h_tg_out.data();
         return CL_OK;
     });
 }

@@ -86,6 +86,12 @@ int coverage_files(const char *bam_path, const char *fasta_path, const char *bed
     FastaPtr fa(nullptr, dut_fasta_close);
     std::string msg;
     if (!open_pair(bam_path, fasta_path, bam, fa, msg)) { set_err(err, err_len, msg); return CL_ERR_INVALID; }
+    if (hook && hook->header) {
+        std::vector<const char *> refs;
+        for (int t = 0; t < dut_bam_n_ref(bam.get()); ++t) refs.push_back(dut_bam_ref_name(bam.get(), t));
+        const int hrc = hook->header(hook->user, refs.data(), refs.size());
+        if (hrc != CL_OK) { set_err(err, err_len, "the hook refused the BAM header"); return hrc; }
+    }
     // initialize_contig_stats / validate_contig_selection, api/coverage.rs:149-204
     std::vector<int> tids;
     std::vector<uint64_t> weight;
@@ -175,7 +181,7 @@ int coverage_files(const char *bam_path, const char *fasta_path, const char *bed
             Result r;
             int rc = dut_process_single_contig_runs(ctx[d].get(), &r.st, opt, t, dut_bam_ref_len(b.get(), t), cur.bases, cur.blen, &cur.rec, r.counts, &r.iv, &r.n_iv);
             // (the contig is still resident: what else a caller wants of it is taken here, on the device's thread)
-            if (rc == CL_OK && hook && hook->resident) rc = hook->resident(hook->user, ctx[d].get(), i);
+            if (rc == CL_OK && hook && hook->resident) rc = hook->resident(hook->user, ctx[d].get(), i, dut_bam_ref_name(b.get(), t));
             if (rc == CL_OK) rc = put(i, r);
             if (rc != CL_OK) {
                 const char *m = cl_last_error(ctx[d].get());

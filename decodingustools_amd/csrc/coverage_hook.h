@@ -1,5 +1,6 @@
 // coverage_hook.h -- the seam between the file-level coverage driver (coverage_files.cpp) and what a caller wants of a
-// contig beyond its runs, while it is resident on the device (depth_files.cpp: the depth profile).  The driver itself
+// contig beyond its runs, while it is resident on the device (depth_files.cpp: the depth profile, the depth BED, the
+// per-target table).  The driver itself
 // calls nothing of the engine that its existing entry points did not call; they pass no hook.
 #pragma once
 #include "../../include/dut_bam.h"
@@ -7,9 +8,12 @@
 namespace dut {
 
 struct ContigHook {
+    // once, on the calling thread, with the names of all contigs of the BAM header, before any device is opened (may be
+    // null).  A negative cl_status ends the analysis before it starts.
+    int (*header)(void *user, const char *const *ref_names, size_t n_refs);
     // on the device's host thread, right after selected contig i (index in tid order) has been run and collected on ctx
     // and before the next contig replaces it.  A negative cl_status ends the analysis (message: cl_last_error(ctx)).
-    int (*resident)(void *user, cl_ctx *ctx, size_t i);
+    int (*resident)(void *user, cl_ctx *ctx, size_t i, const char *contig_name);
     // on the calling thread, in tid order, after contig i's BED lines are written (one device or several)
     int (*deliver)(void *user, size_t i, const char *contig_name);
     // once, after the last contig of a run without error, before the summaries are written and the outputs are closed

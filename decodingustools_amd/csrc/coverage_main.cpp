@@ -36,6 +36,10 @@ static void usage()
             "         per-base depth as a BED of runs of equal depth (contig, start, end, depth; no header); kind raw (default)\n"
             "         or qc (quality-filtered); SPEC such as 1:4:100 merges runs within the bands 0, 1-3, 4-99, 100+ (at most\n"
             "         64 edges; a leading 0: and a trailing : are accepted)\n"
+            "       [--targets BED --target-out FILE [--target-thresholds 1,10,20,30]]\n"
+            "         per region of BED (0-based, half open; column 4 = name): length, mean raw / quality-filtered depth, callable\n"
+            "         bases and the other states, positions at >= each threshold (at most 8); a `total` line last, in which\n"
+            "         overlapping regions count twice\n"
             "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n"
             "       dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
@@ -685,6 +689,8 @@ int main(int argc, char **argv)
     bool has_window = false;
     std::string depth_bed, depth_bed_kind, quantize;
     bool has_kind = false, has_quantize = false;
+    std::string targets_bed, target_out, target_thr;
+    bool has_target_thr = false;
     // a whole non-negative number, or exit 2 with a message (before any device is opened)
     auto number = [](const char *flag, const char *v) -> unsigned long long {
         char *end = nullptr;
@@ -724,6 +730,9 @@ int main(int argc, char **argv)
         else if (a == "--depth-bed") depth_bed = next();
         else if (a == "--depth-bed-kind") { depth_bed_kind = next(); has_kind = true; }
         else if (a == "--quantize") { quantize = next(); has_quantize = true; }
+        else if (a == "--targets") targets_bed = next();
+        else if (a == "--target-out") target_out = next();
+        else if (a == "--target-thresholds") { target_thr = next(); has_target_thr = true; }
         else if (a == "--device") devices.assign(1, atoi(next()));
         else if (a == "--devices") {
             // the contigs are dealt to these devices (HIP ordinals, comma separated; an ordinal may repeat)
@@ -763,6 +772,23 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    if (!target_out.empty() && targets_bed.empty()) { fprintf(stderr, "error: '--target-out' needs '--targets <BED>'\n"); return 2; }
+    if (has_target_thr && targets_bed.empty()) { fprintf(stderr, "error: '--target-thresholds' needs '--targets <BED>'\n"); return 2; }
+    if (!targets_bed.empty() && target_out.empty()) { fprintf(stderr, "error: '--targets' needs '--target-out <FILE>'\n"); return 2; }
+    uint32_t thresholds[CL_TARGET_MAX_THRESHOLDS] = {0}, n_thresholds = 0;
+    if (!targets_bed.empty()) {
+        char why[512] = {0};
+        if (dut_thresholds_parse(has_target_thr ? target_thr.c_str() : nullptr, thresholds, &n_thresholds, why, sizeof(why)) != CL_OK) {
+            fprintf(stderr, "error: invalid value '%s' for '--target-thresholds': %s\n", target_thr.c_str(), why);
+            return 2;
+        }
+        // (read here once for its mistakes, before a device is opened; the library reads it again)
+        dut_targets *tg = dut_targets_read(targets_bed.c_str(), why, sizeof(why));
+        if (!tg) { fprintf(stderr, "error: invalid value for '--targets': %s\n", why); return 2; }
+        dut_targets_free(tg);
+    }
+    const dut_target_options target_opt = {targets_bed.empty() ? nullptr : targets_bed.c_str(), target_out.empty() ? nullptr : target_out.c_str(),
+                                           thresholds, n_thresholds};
     const dut_depth_bed_options depth_bed_opt = {depth_bed.empty() ? nullptr : depth_bed.c_str(),
                                                  depth_bed_kind == "qc" ? (uint32_t)CL_DEPTH_QC : (uint32_t)CL_DEPTH_RAW, edges, n_edges};
     if (devices.empty()) devices.push_back(0);
@@ -807,9 +833,9 @@ int main(int argc, char **argv)
     // the exit (DUT_CLI_TEARDOWN=1: given back piece by piece first, as a library caller's process would)
     const char *td = getenv("DUT_CLI_TEARDOWN");
     const unsigned flags = (td && *td == '1') ? 0u : DUT_FILES_LEAVE_TO_EXIT;
-    const int rc = dut_coverage_files_ex2(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
+    const int rc = dut_coverage_files_ex3(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
                                           contigs.empty() ? nullptr : contigs.data(), contigs.size(), devices.data(), devices.size(),
-                                          flags, &depth, &depth_bed_opt, err, sizeof(err));
+                                          flags, &depth, &depth_bed_opt, &target_opt, err, sizeof(err));
     if (rc != CL_OK) { fprintf(stderr, "Error: Analysis error: %s\n", err); leave(1); }
     // every output file is written and closed: leave without the HIP runtime's exit handlers
     stamp("exit");

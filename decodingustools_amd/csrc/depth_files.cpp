@@ -1,8 +1,9 @@
-// depth_files.cpp -- dut_coverage_files_ex / _ex2 (include/dut_bam.h): the file-level coverage run that also takes every
-// contig's depth profile (cl_contig_depth_profile) and / or its per-base depth runs (cl_contig_depth_runs) while the
-// contig is resident, and writes the distribution, window and summary files and the depth BED of include/dut_coverage.h
-// beside the BED.  The driver is coverage_files.cpp's; this file is its hook: two users (DepthRun, BedRun), composed in
-// Both when a run asks for both.
+// depth_files.cpp -- dut_coverage_files_ex / _ex2 / _ex3 (include/dut_bam.h): the file-level coverage run that also takes
+// every contig's depth profile (cl_contig_depth_profile), its per-base depth runs (cl_contig_depth_runs) and / or the
+// summaries of its targets (cl_contig_targets) while the contig is resident, and writes the distribution, window and
+// summary files, the depth BED and the per-target table of include/dut_coverage.h beside the BED.  The driver is
+// coverage_files.cpp's; this file is its hook: three users (DepthRun, BedRun, TargetRun), as many of them as a run asks
+// for behind one hook that calls them in that order (Many).
 #include "coverage_hook.h"
 #include "../../include/dut_coverage.h"
 
@@ -33,7 +34,7 @@ struct DepthRun {
     ~DepthRun() { dut_depth_acc_free(acc); }
 };
 
-int on_resident(void *user, cl_ctx *ctx, size_t i)
+int on_resident(void *user, cl_ctx *ctx, size_t i, const char *)
 {
     DepthRun *r = static_cast<DepthRun *>(user);
     cl_depth_profile p;
@@ -102,7 +103,7 @@ struct BedRun {
     ~BedRun() { if (f) fclose(f); }
 };
 
-int bed_resident(void *user, cl_ctx *ctx, size_t i)
+int bed_resident(void *user, cl_ctx *ctx, size_t i, const char *)
 {
     BedRun *r = static_cast<BedRun *>(user);
     cl_depth_runs d;
@@ -148,25 +149,109 @@ int bed_finish(void *user)
     return rc;
 }
 
-// both users behind one hook: the profile first, then the runs
-struct Both { DepthRun *depth; BedRun *bed; };
-int both_resident(void *user, cl_ctx *ctx, size_t i)
+// ---- the per-target table: one contig's records on their way from its device's thread to the file ----
+struct TargetRun {
+    std::string bed_path, out_path;
+    std::vector<uint32_t> thr;
+    std::unique_ptr<dut_targets, decltype(&dut_targets_free)> tg{nullptr, dut_targets_free};
+    std::map<std::string, size_t> by_name;               // contig name -> its index in tg
+    FILE *f = nullptr;
+    dut_target_total total{};
+    std::mutex mu;
+    std::map<size_t, std::vector<cl_target_stats>> taken;   // by selected-contig index (contigs with targets only)
+    std::string msg;
+    ~TargetRun() { if (f) fclose(f); }
+};
+
+// every contig of the regions must be one of the BAM's: a misspelt contig would otherwise silently report nothing
+int tg_header(void *user, const char *const *refs, size_t n_refs)
 {
-    Both *b = static_cast<Both *>(user);
-    const int rc = on_resident(b->depth, ctx, i);
-    return rc != CL_OK ? rc : bed_resident(b->bed, ctx, i);
+    TargetRun *r = static_cast<TargetRun *>(user);
+    for (size_t c = 0; c < dut_targets_n_contigs(r->tg.get()); ++c) {
+        const char *name = dut_targets_contig(r->tg.get(), c, nullptr);
+        bool found = false;
+        for (size_t t = 0; !found && t < n_refs; ++t) found = strcmp(refs[t], name) == 0;
+        if (!found) {
+            const uint32_t *lines = nullptr;
+            dut_targets_get(r->tg.get(), c, nullptr, nullptr, nullptr, &lines);
+            r->msg = r->bed_path + ": line " + std::to_string(lines[0]) + ": contig '" + name + "' is not in the BAM header";
+            return CL_ERR_INVALID;
+        }
+    }
+    return CL_OK;
 }
-int both_deliver(void *user, size_t i, const char *name)
+
+int tg_resident(void *user, cl_ctx *ctx, size_t i, const char *name)
 {
-    Both *b = static_cast<Both *>(user);
-    const int rc = on_deliver(b->depth, i, name);
-    return rc != CL_OK ? rc : bed_deliver(b->bed, i, name);
+    TargetRun *r = static_cast<TargetRun *>(user);
+    const auto it = r->by_name.find(name);
+    if (it == r->by_name.end()) return CL_OK;             // no target on this contig: no launch, no line
+    size_t n = 0;
+    const uint32_t *s = nullptr, *e = nullptr;
+    dut_targets_contig(r->tg.get(), it->second, &n);
+    dut_targets_get(r->tg.get(), it->second, &s, &e, nullptr, nullptr);
+    const cl_target_stats *st = nullptr;
+    const int rc = cl_contig_targets(ctx, s, e, n, r->thr.data(), (uint32_t)r->thr.size(), &st);
+    if (rc != CL_OK) return rc;
+    std::vector<cl_target_stats> copy(st, st + n);
+    std::lock_guard<std::mutex> g(r->mu);
+    r->taken[i] = std::move(copy);
+    return CL_OK;
 }
-int both_finish(void *user)
+
+int tg_deliver(void *user, size_t i, const char *name)
 {
-    Both *b = static_cast<Both *>(user);
-    const int rc = on_finish(b->depth), rc2 = bed_finish(b->bed);  // (both files are closed either way)
-    return rc != CL_OK ? rc : rc2;
+    TargetRun *r = static_cast<TargetRun *>(user);
+    const auto cit = r->by_name.find(name);
+    if (cit == r->by_name.end()) return CL_OK;
+    std::vector<cl_target_stats> st;
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        auto it = r->taken.find(i);
+        if (it == r->taken.end()) return CL_ERR_INVALID;
+        st = std::move(it->second);
+        r->taken.erase(it);
+    }
+    const char *const *names = nullptr;
+    dut_targets_get(r->tg.get(), cit->second, nullptr, nullptr, &names, nullptr);
+    const int rc = dut_targets_write(r->f, name, st.data(), names, st.size(), (uint32_t)r->thr.size(), &r->total);
+    if (rc != CL_OK) r->msg = "cannot write " + r->out_path + " (contig " + name + ")";
+    return rc;
+}
+
+int tg_finish(void *user)
+{
+    TargetRun *r = static_cast<TargetRun *>(user);
+    int rc = dut_targets_write_total(r->f, &r->total, (uint32_t)r->thr.size());
+    if (fclose(r->f) != 0) rc = CL_ERR_INVALID;
+    r->f = nullptr;
+    if (rc != CL_OK) r->msg = "cannot write " + r->out_path;
+    return rc;
+}
+
+// several users behind one hook, called in the order of the list
+struct Many { std::vector<dut::ContigHook> hooks; };
+int many_header(void *user, const char *const *refs, size_t n_refs)
+{
+    for (const dut::ContigHook &h : static_cast<Many *>(user)->hooks)
+        if (h.header) { const int rc = h.header(h.user, refs, n_refs); if (rc != CL_OK) return rc; }
+    return CL_OK;
+}
+int many_resident(void *user, cl_ctx *ctx, size_t i, const char *name)
+{
+    for (const dut::ContigHook &h : static_cast<Many *>(user)->hooks) { const int rc = h.resident(h.user, ctx, i, name); if (rc != CL_OK) return rc; }
+    return CL_OK;
+}
+int many_deliver(void *user, size_t i, const char *name)
+{
+    for (const dut::ContigHook &h : static_cast<Many *>(user)->hooks) { const int rc = h.deliver(h.user, i, name); if (rc != CL_OK) return rc; }
+    return CL_OK;
+}
+int many_finish(void *user)
+{
+    int rc = CL_OK;
+    for (const dut::ContigHook &h : static_cast<Many *>(user)->hooks) { const int r1 = h.finish(h.user); if (rc == CL_OK) rc = r1; }   // (every file is closed either way)
+    return rc;
 }
 
 void set_err(char *err, size_t n, const char *m) { if (err && n) snprintf(err, n, "%s", m); }
@@ -191,6 +276,18 @@ int check_bed_options(const dut_depth_bed_options *o, char *err, size_t err_len)
     return CL_OK;
 }
 
+int check_target_options(const dut_target_options *o, char *err, size_t err_len)
+{
+    const char *m = nullptr;
+    if (!o->out_path) m = "targets: no output file for the table";
+    else if (o->n_thresholds > CL_TARGET_MAX_THRESHOLDS) m = "targets: more than 8 thresholds";
+    else if (o->n_thresholds && !o->thresholds) m = "targets: null thresholds";
+    else if (o->n_thresholds && o->thresholds[0] == 0u) m = "targets: the first threshold is 0";
+    for (uint32_t i = 1; !m && i < o->n_thresholds; ++i) if (o->thresholds[i] <= o->thresholds[i - 1]) m = "targets: the thresholds are not strictly ascending";
+    if (m) { set_err(err, err_len, m); return CL_ERR_INVALID; }
+    return CL_OK;
+}
+
 } // namespace
 
 extern "C" int dut_coverage_files_ex(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
@@ -198,7 +295,7 @@ extern "C" int dut_coverage_files_ex(const char *bam_path, const char *fasta_pat
                                      const int *devices, size_t n_devices, unsigned flags, const dut_depth_options *depth,
                                      char *err, size_t err_len)
 {
-    return dut_coverage_files_ex2(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, depth, nullptr, err, err_len);
+    return dut_coverage_files_ex3(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, depth, nullptr, nullptr, err, err_len);
 }
 
 extern "C" int dut_coverage_files_ex2(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
@@ -206,17 +303,37 @@ extern "C" int dut_coverage_files_ex2(const char *bam_path, const char *fasta_pa
                                       const int *devices, size_t n_devices, unsigned flags, const dut_depth_options *depth,
                                       const dut_depth_bed_options *bed, char *err, size_t err_len)
 {
+    return dut_coverage_files_ex3(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, depth, bed, nullptr, err, err_len);
+}
+
+extern "C" int dut_coverage_files_ex3(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
+                                      const char *summary_html, const cl_options *opt, const char *const *contigs, size_t n_contigs,
+                                      const int *devices, size_t n_devices, unsigned flags, const dut_depth_options *depth,
+                                      const dut_depth_bed_options *bed, const dut_target_options *targets, char *err, size_t err_len)
+{
     const bool any = depth && (depth->dist_path || depth->windows_path || depth->summary_path);
     const bool any_bed = bed && bed->path;
-    if (!any && !any_bed)
+    const bool any_tg = targets && targets->bed_path;
+    if (!any && !any_bed && !any_tg)
         return dut_coverage_files_multi(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len);
     if (any && check_options(depth, err, err_len) != CL_OK) return CL_ERR_INVALID;
     if (any_bed && check_bed_options(bed, err, err_len) != CL_OK) return CL_ERR_INVALID;
     // the byte forms have neither (cl_contig_depth_profile, cl_contig_depth_runs): said before anything is read
-    { const char *qf = getenv("DUT_QUAL_FORM"); if (qf && strcmp(qf, "bytes") == 0) { set_err(err, err_len, any ? "depth profile: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : "depth BED: pass-bit form only (DUT_QUAL_FORM=bytes is set)"); return CL_ERR_INVALID; } }
+    if (any_tg && check_target_options(targets, err, err_len) != CL_OK) return CL_ERR_INVALID;
+    { const char *qf = getenv("DUT_QUAL_FORM"); if (qf && strcmp(qf, "bytes") == 0) { set_err(err, err_len, any ? "depth profile: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : any_bed ? "depth BED: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : "targets: pass-bit form only (DUT_QUAL_FORM=bytes is set)"); return CL_ERR_INVALID; } }
     try {
         DepthRun run;
         BedRun brun;
+        TargetRun trun;
+        if (any_tg) {
+            // (the regions are read before any output is created: a malformed BED leaves nothing behind)
+            trun.bed_path = targets->bed_path; trun.out_path = targets->out_path;
+            trun.thr.assign(targets->thresholds, targets->thresholds + targets->n_thresholds);
+            char e[512] = {0};
+            trun.tg.reset(dut_targets_read(targets->bed_path, e, sizeof(e)));
+            if (!trun.tg) { set_err(err, err_len, e); return CL_ERR_INVALID; }
+            for (size_t c = 0; c < dut_targets_n_contigs(trun.tg.get()); ++c) trun.by_name[dut_targets_contig(trun.tg.get(), c, nullptr)] = c;
+        }
         if (any) {
             run.o = *depth;
             if (!run.o.windows_path) run.o.window = 0;             // no window file: no window table is taken
@@ -229,14 +346,20 @@ extern "C" int dut_coverage_files_ex2(const char *bam_path, const char *fasta_pa
             brun.f = fopen(bed->path, "wb");
             if (!brun.f) { set_err(err, err_len, ("cannot create " + brun.path).c_str()); return CL_ERR_INVALID; }
         }
-        Both both = {&run, &brun};
-        const dut::ContigHook hook = any && any_bed ? dut::ContigHook{both_resident, both_deliver, both_finish, &both}
-                                     : any        ? dut::ContigHook{on_resident, on_deliver, on_finish, &run}
-                                                  : dut::ContigHook{bed_resident, bed_deliver, bed_finish, &brun};
+        if (any_tg) {
+            trun.f = fopen(targets->out_path, "wb");
+            if (!trun.f || dut_targets_write_header(trun.f, trun.thr.data(), (uint32_t)trun.thr.size()) != CL_OK) { set_err(err, err_len, ("cannot create " + trun.out_path).c_str()); return CL_ERR_INVALID; }
+        }
+        Many many;
+        if (any) many.hooks.push_back(dut::ContigHook{nullptr, on_resident, on_deliver, on_finish, &run});
+        if (any_bed) many.hooks.push_back(dut::ContigHook{nullptr, bed_resident, bed_deliver, bed_finish, &brun});
+        if (any_tg) many.hooks.push_back(dut::ContigHook{tg_header, tg_resident, tg_deliver, tg_finish, &trun});
+        const dut::ContigHook hook = {many_header, many_resident, many_deliver, many_finish, &many};
         const int rc = dut::coverage_files_hooked(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len, &hook);
         // the failure was this file's: its own words
         if (rc != CL_OK && !run.msg.empty()) set_err(err, err_len, run.msg.c_str());
         else if (rc != CL_OK && !brun.msg.empty()) set_err(err, err_len, brun.msg.c_str());
+        else if (rc != CL_OK && !trun.msg.empty()) set_err(err, err_len, trun.msg.c_str());
         return rc;
     } catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
 }

@@ -246,6 +246,47 @@ cl_status cl_contig_depth_runs(cl_ctx *ctx, uint32_t kind, const uint32_t *edges
  * cl_set_profiling was on for that call. */
 cl_status cl_contig_depth_runs_ms(cl_ctx *ctx, double *kernel_ms);
 
+/* ---- targets: depth and callable-base summaries of the resident contig over a list of regions ---------------- */
+/* What a coverage tool reports per region of a BED (exome or panel targets; mosdepth --by, Picard HsMetrics).  With raw[p]
+ * and qc[p] as above and state[p] the position's CalledState (what the intervals say), for n targets [start_i, end_i),
+ * 0-based half open, start_i <= end_i, in any order, overlapping, nested or repeated at will, and up to
+ * CL_TARGET_MAX_THRESHOLDS depth thresholds t_0 < t_1 < ..., t_0 >= 1: with e_i = min(end_i, extent) and
+ * s_i = min(start_i, e_i), record i holds
+ *   start, end, len      s_i, e_i and e_i - s_i: a target at or beyond the extent has length 0 and zeros everywhere else
+ *   sum_raw, sum_qc      the sums of raw[p] and qc[p] over [s_i, e_i), exact
+ *   state[6]             the positions of each CalledState; they add up to len
+ *   ge_raw[k], ge_qc[k]  the positions with raw[p] >= t_k and with qc[p] >= t_k, k < n_thresholds (0 beyond)
+ * Every target is independent of the others; the records come in the order the targets were given; every figure is an
+ * integer count and two calls return the same bytes (no count crosses workgroups through an atomic).  Three launches over
+ * the resident contig (depth_targets.hip.h): per engine window the totals of the depth fields and their prefix at the
+ * targets' ends inside it, a scan of the windows' totals, and one wave per target that also sums the states out of the
+ * device's interval array.  Only the records cross the link.  Taken only when asked: cl_contig_run enqueues what it always
+ * did.  Any number of calls per resident contig, interleaved with cl_contig_depth_profile, cl_contig_depth_runs and
+ * cl_contig_run -- but the call reads the intervals of the last run, so the contig must have been collected
+ * (cl_contig_collect or cl_contig_finish) since its last cl_contig_run: that is where counter-width re-runs and a too small
+ * interval buffer are settled.  n_targets == 0 is valid (*out = NULL).  *out points at context-owned host memory, valid until
+ * the next cl_contig_targets, cl_contig_begin or cl_destroy.
+ * CL_ERR_INVALID (with a message; the context stays usable): a null out; null starts / ends with n_targets > 0; a target
+ * with start > end; n_targets > CL_TARGETS_MAX; n_thresholds > CL_TARGET_MAX_THRESHOLDS; null thresholds with
+ * n_thresholds > 0; thresholds that are not strictly ascending, or a first threshold of 0; no contig collected since its
+ * last run; a context of the byte forms (DUT_QUAL_FORM=bytes).  CL_ERR_DEVICE: a host-only debug context.
+ * CL_ERR_INTERNAL: a device-side check of an uploaded index failed (nothing was read or stored out of range). */
+#define CL_TARGET_MAX_THRESHOLDS 8u
+#define CL_TARGETS_MAX (1u << 24)
+typedef struct cl_target_stats {
+    uint32_t start, end;          /* clipped to the extent */
+    uint32_t len, reserved;
+    uint64_t sum_raw, sum_qc;
+    uint32_t state[6];            /* types.rs:36-43 order */
+    uint32_t ge_raw[CL_TARGET_MAX_THRESHOLDS], ge_qc[CL_TARGET_MAX_THRESHOLDS];
+} cl_target_stats;
+cl_status cl_contig_targets(cl_ctx *ctx, const uint32_t *starts, const uint32_t *ends, size_t n_targets,
+                            const uint32_t *thresholds, uint32_t n_thresholds, const cl_target_stats **out);
+/* Measurement: the three launches of the last cl_contig_targets by device events, milliseconds: their sum in *kernel_ms
+ * and, when launch_ms is not NULL, k_target_depth, k_target_scan and k_target_finish apart; 0 unless cl_set_profiling was
+ * on for that call. */
+cl_status cl_contig_targets_ms(cl_ctx *ctx, double *kernel_ms, double launch_ms[3]);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 enum { CL_K_PREP = 0, CL_K_BOUNDS = 1, CL_K_PILEUP = 2, CL_K_RLE = 3, CL_K_COUNT = 4 };
 /* When on, every cl_contig_run brackets each kernel group with hipEvents on the stream. */

@@ -149,6 +149,31 @@ int dut_coverage_files_ex2(const char *bam_path, const char *fasta_path, const c
                            unsigned flags, const dut_depth_options *depth, const dut_depth_bed_options *bed,
                            char *err, size_t err_len);
 
+/* dut_coverage_files_ex2 that also writes the per-target table of a BED of regions (cl_contig_targets, callable_loci.h;
+ * the BED reader and the table: dut_targets_*, dut_coverage.h).  Every selected contig's targets are taken on the device
+ * while the contig is resident -- three more launches per contig that has targets --, copied on the device's thread, and
+ * written by the calling thread behind the contig's BED lines: contigs in the order of the BED output, a contig's targets
+ * in file order, a `total` line last; one device and several give the same bytes.  Combines with both other option sets
+ * in one run.  targets == NULL or no bed_path: exactly dut_coverage_files_ex2.  Pass-bit form only.
+ *   bed_path      the regions
+ *   out_path      the table
+ *   thresholds    n_thresholds depths (dut_thresholds_parse), strictly ascending, the first at least 1, at most
+ *                 CL_TARGET_MAX_THRESHOLDS
+ * A malformed BED, bad thresholds or a missing out_path are refused (CL_ERR_INVALID, message) before any device is
+ * touched; so is a target on a contig the BAM header does not have (the message names its line).  Targets on contigs
+ * the selection leaves out are skipped. */
+typedef struct dut_target_options {
+    const char *bed_path;
+    const char *out_path;
+    const uint32_t *thresholds;
+    uint32_t n_thresholds;
+} dut_target_options;
+int dut_coverage_files_ex3(const char *bam_path, const char *fasta_path, const char *bed_path,
+                           const char *summary_json, const char *summary_html, const cl_options *opt,
+                           const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
+                           unsigned flags, const dut_depth_options *depth, const dut_depth_bed_options *bed,
+                           const dut_target_options *targets, char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,42 @@ int dut_depth_acc_finish(dut_depth_acc *a, const char *dist_path, const char *su
 int dut_quantize_parse(const char *spec, uint32_t *edges, uint32_t *n_edges, char *err, size_t err_len);
 int dut_depth_bed_write(FILE *f, const char *contig, const cl_depth_runs *r, const uint32_t *edges);
 
+/* ---- targets: a BED of regions in, the table of cl_contig_targets' records out (host code only) ---------------
+ * dut_targets_parse: BED text.  A line wants at least 3 tab- or blank-separated columns, contig start end, 0-based half
+ * open, whole numbers up to 2^32 - 1, start <= end; column 4 is the target's name, else ".".  Blank lines and lines that
+ * start with `#`, `track` or `browser` are skipped; a line may end in CR LF.  The targets are grouped by contig, the
+ * contigs in the order they first appear, a contig's targets in file order.  NULL with the reason, line number first,
+ * in err for a malformed line (fewer than 3 columns, a malformed or too large number, start > end); an empty file is a
+ * valid list without contigs.  dut_targets_read: the same of a file (NULL also when it cannot be read).
+ * dut_targets_get: contig c's arrays, context-owned: starts, ends, names, and the 1-based line of every target.
+ * dut_thresholds_parse: `--target-thresholds LIST`, comma separated whole numbers that ascend strictly, the first at
+ * least 1, at most CL_TARGET_MAX_THRESHOLDS of them; NULL or empty text: 1,10,20,30.  CL_OK, or CL_ERR_INVALID with the
+ * reason in err.
+ * The table (tab separated):
+ *     #contig start end name length mean_raw mean_qc callable callable_frac ref_n no_coverage low_coverage
+ *     excessive_coverage poor_mapping_quality raw_ge_T... qc_ge_T...      (T: each threshold)
+ * one line per target, start, end and length clipped to the contig's extent; the means are sum / length in f64 as %.4f,
+ * callable_frac callable / length as %.6f, both `NA` for length 0; everything else is a count of positions.
+ * dut_targets_write adds every record to *total (may be NULL); dut_targets_write_total writes the last line, `total . . .`
+ * and the column sums -- targets that overlap count twice there -- with the means and the fraction taken over the sums. */
+typedef struct dut_targets dut_targets;
+dut_targets *dut_targets_parse(const char *text, size_t len, char *err, size_t err_len);
+dut_targets *dut_targets_read(const char *path, char *err, size_t err_len);
+void dut_targets_free(dut_targets *t);
+size_t dut_targets_n_contigs(const dut_targets *t);
+const char *dut_targets_contig(const dut_targets *t, size_t c, size_t *n_targets);
+int dut_targets_get(const dut_targets *t, size_t c, const uint32_t **starts, const uint32_t **ends, const char *const **names,
+                    const uint32_t **lines);
+int dut_thresholds_parse(const char *spec, uint32_t *thresholds, uint32_t *n_thresholds, char *err, size_t err_len);
+typedef struct dut_target_total {
+    uint64_t n_targets, len, sum_raw, sum_qc, state[6];
+    uint64_t ge_raw[CL_TARGET_MAX_THRESHOLDS], ge_qc[CL_TARGET_MAX_THRESHOLDS];
+} dut_target_total;
+int dut_targets_write_header(FILE *f, const uint32_t *thresholds, uint32_t n_thresholds);
+int dut_targets_write(FILE *f, const char *contig, const cl_target_stats *stats, const char *const *names, size_t n,
+                      uint32_t n_thresholds, dut_target_total *total);
+int dut_targets_write_total(FILE *f, const dut_target_total *total, uint32_t n_thresholds);
+
 /* Debug names of CalledState (types.rs:36-43) */
 const char *dut_state_name(uint32_t state);
 
