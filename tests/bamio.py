@@ -79,8 +79,9 @@ def write_bam(path, refs, per_tid, header_text="@HD\tVN:1.6\tSO:coordinate\n", w
             l_seq = len(qual)
             if rec.seq4 is not None:
                 s0 = int(rec.seq_off[i]); ls = int(rec.seq_off[i + 1]) - s0
-                codes = np.array([(rec.seq4[(s0 + j) >> 1] >> 4) if ((s0 + j) & 1) == 0 else (rec.seq4[(s0 + j) >> 1] & 15)
-                                  for j in range(ls)], dtype=np.uint8)
+                at = s0 + np.arange(ls, dtype=np.int64)      # (as arrays: a long read's record has a million bases)
+                byte = np.asarray(rec.seq4, dtype=np.uint8)[at >> 1]
+                codes = np.where((at & 1) == 0, byte >> 4, byte & 15).astype(np.uint8)
                 l_seq = ls
             else:
                 codes = np.full(l_seq, 1, dtype=np.uint8)

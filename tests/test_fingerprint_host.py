@@ -1,6 +1,7 @@
 """`fingerprint` without a device: the numpy restatement against the known answers, the library's shared hash code,
 max_hash and SHA-256 against it, the BAM and FASTQ readers, and the command line's argument and format errors."""
 import ctypes as C
+import gzip
 import hashlib
 import json
 import os
@@ -9,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fp_cases as F
 import fp_data
 import fp_ref
 from decodingustools_amd import _lib, build as _b
@@ -188,6 +190,122 @@ def test_fastq_stops_at_empty_id(lib, tmp_path, capfd):
     p.write_bytes(b"@a\nACGT\n+\nIIII\n@b x\nGGGA \n+\nIIII\n@ desc\nTTTT\n+\nIIII\n@c\nCCCC\n+\nIIII\n")
     assert _fastq_walk(lib, p) == [b"ACGT", b"GGGA"]
     assert "empty id" in capfd.readouterr().err
+
+
+def test_edge_lengths_and_seam_bytes_every_k(lib):
+    """The shared hash code, strip after strip as the kernel cuts them, on the inputs of the device's edge tests."""
+    for k in range(1, 65):
+        seqs = F.edge_lengths(k) + F.seam_bytes(k)
+        rh, rhn = fp_ref.window_hashes(*fp_ref.pack(seqs), k)
+        got = [fpm.kmer_hashes_host(s, k) for s in seqs]
+        h, hn = np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got])
+        assert np.array_equal(hn, rhn) and np.array_equal(h[~hn], rh[~rhn]), k
+        assert [len(g[0]) for g in got[:11]] == [0, 1, 2, 63, 64, 65, 66, 127, 128, 129, 130]
+        seqs = F.edge_lengths(k) + F.seam_bytes(k, seq4=True)
+        rh, rhn = fp_ref.window_hashes(*fp_ref.pack(seqs), k)
+        got = [fpm.kmer_hashes_host_seq4(fp_ref.encode_seq4(np.frombuffer(s, np.uint8)), len(s), k) for s in seqs]
+        h, hn = np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got])
+        assert np.array_equal(hn, rhn) and np.array_equal(h[~hn], rh[~rhn]), k
+    # what the seam cases are for: a special byte on each side of the first three seams, and a strip without a live window
+    for k in F.KS:
+        places = F.seam_places(k)
+        assert {63, 64, 127, 128, 64 + k - 1, 64 + k - 2, 5 * 64 - 1, 5 * 64 + k - 2} <= set(places)
+        assert len(F.seam_bytes(k)) == 4 * len(places) + 2 and len(F.seam_bytes(k, seq4=True)) == 3 * len(places) + 2
+        _, hn = fp_ref.kmer_hashes(F.seam_bytes(k)[-2], k)           # N over [64, 127 + k): windows 65 - k .. 126 + k
+        assert hn[64:128].all() and hn[max(65 - k, 0):127 + k].all() and not hn[127 + k] and not hn[64 - k]
+        _, hn = fp_ref.kmer_hashes(F.seam_bytes(k)[-1], k)           # N over [63, 128 + k): windows 64 - k .. 127 + k
+        assert hn[max(64 - k, 0):128 + k].all() and not hn[128 + k] and (k == 64 or not hn[63 - k])
+
+
+def _write_long_fastq(path, seqs, members=0, crlf=False, final_newline=True):
+    nl = b"\r\n" if crlf else b"\n"
+    recs = [b"@r%d long" % i + nl + s + nl + b"+" + nl + b"I" * len(s) + nl for i, s in enumerate(seqs)]
+    if not final_newline:
+        recs[-1] = recs[-1][:-len(nl)]
+    with open(path, "wb") as f:
+        if not members:
+            f.write(b"".join(recs))
+        else:
+            step = (len(recs) + members - 1) // members
+            for i in range(0, len(recs), step):
+                f.write(gzip.compress(b"".join(recs[i:i + step]), 1))
+
+
+@pytest.fixture(scope="module")
+def long_lines():
+    """Sequence lines around and beyond the reader's refill of 1 MiB, an empty one, and two short ones."""
+    rng = np.random.default_rng(31)
+    return [bytes(F.ACGT[rng.integers(0, 4, size=n)]) for n in ((3 << 20) + 17, 1 << 20, (1 << 20) - 1, 0, 100, 50)]
+
+
+FASTQ_FORMS = (("plain.fq", {}), ("two.fq.gz", {"members": 2}), ("crlf.fq", {"crlf": True}), ("open_end.fq", {"final_newline": False}))
+
+
+def test_fastq_reader_long_lines(lib, tmp_path, long_lines):
+    for name, kw in FASTQ_FORMS:
+        p = tmp_path / name
+        _write_long_fastq(p, long_lines, **kw)
+        for cap in (1, 1000, 1 << 30):
+            got = _fastq_walk(lib, p, cap)
+            assert [len(s) for s in got] == [len(s) for s in long_lines], (name, cap)
+            assert got == long_lines, (name, cap)
+
+
+@pytest.fixture(scope="module")
+def long_bam(tmp_path_factory):
+    p = tmp_path_factory.mktemp("fp_long") / "long.bam"
+    fp_data.write_reads_bam(p, [s.decode() for s in F.file_reads()])
+    return p
+
+
+def test_bam_walk_long_record(lib, long_bam):
+    want = list(F.file_reads())
+    assert len(want[0]) == 1 and len(want[2]) == 1 and len(want[1]) == F.BIG_LINE and len(want[1]) % 2 == 0
+    assert os.path.getsize(long_bam) > 4 * 65536                  # (the long record alone is many BGZF blocks)
+    for cap in (1, 20_000, 1 << 30):
+        got, batches = _bam_walk(lib, long_bam, cap)
+        assert [len(s) for s in got] == [len(s) for s in want], cap
+        assert got == want, cap
+        # one batch: the long record from base 1, its followers from an odd and an even base; small caps: from base 0
+        assert batches == {1: len(want), 20_000: batches, 1 << 30: 1}[cap] and (cap == 1 << 30 or batches >= 5), (cap, batches)
+
+
+def _checksum(seqs):
+    """tests/native/fp_readers_host.cpp's, in numpy's wrapping 64-bit arithmetic."""
+    b = np.frombuffer(b"".join(seqs), np.uint8).astype(np.uint64)
+    lens = np.array([len(s) for s in seqs], np.uint64)
+    with np.errstate(over="ignore"):
+        s = ((np.arange(len(b), dtype=np.uint64) + np.uint64(1)) * (b + np.uint64(1))).sum(dtype=np.uint64)
+        s += (((np.arange(len(lens), dtype=np.uint64) + np.uint64(1)) * lens) << np.uint64(32)).sum(dtype=np.uint64)
+    return int(s)
+
+
+def test_fp_readers_under_sanitizers(tmp_path, long_lines, long_bam):
+    """dut_fastq_next and dut_bam_next_seqs, in a program of their own under AddressSanitizer + UBSan, on the long-line
+    files: the numbers it prints are Python's, and the sanitizers have nothing to say."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "decodingustools_amd", "csrc")
+    exe = str(tmp_path / "fp_readers_host")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           os.path.join(root, "tests", "native", "fp_readers_host.cpp"), os.path.join(csrc, "fastq_io.cpp"), os.path.join(csrc, "bam_io.cpp"),
+           os.path.join(csrc, "qual_pack.cpp"), "-lz", "-ldl", "-lpthread", "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        if any(m in r.stderr for m in ("cannot find -lasan", "cannot find -lubsan", "unrecognized command-line option", "unrecognized argument")):
+            pytest.skip("sanitizer runtimes not installed here: " + r.stderr[-300:])
+        pytest.fail("the sanitizer build failed:\n" + r.stderr[-3000:])
+    runs = []
+    for name, kw in FASTQ_FORMS:
+        _write_long_fastq(tmp_path / name, long_lines, **kw)
+        runs += [(tmp_path / name, "fastq", cap, long_lines) for cap in (1, 1000, 1 << 30)]
+    runs += [(long_bam, "bam", cap, list(F.file_reads())) for cap in (1, 20_000, 1 << 30)]
+    for path, kind, cap, seqs in runs:
+        r = subprocess.run([exe, str(path), kind, str(cap)], capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, ASAN_OPTIONS="halt_on_error=1:detect_leaks=0", DUT_THREADS="3"))
+        assert r.returncode == 0 and r.stderr == "", (path, cap, r.stderr[-3000:])
+        rec, bases, chk, batches = (int(x) for x in r.stdout.split())
+        assert (rec, bases, chk) == (len(seqs), sum(len(s) for s in seqs), _checksum(seqs)), (path, cap)
+        assert batches == 1 if cap == 1 << 30 else batches > 1, (path, cap, batches)
 
 
 def _cli(*args, cwd=None):
