@@ -14,6 +14,7 @@ import pytest
 
 import ep_cases as S
 import ep_ref as R
+import long_cases as LS
 from decodingustools_amd import EngineError, ErrorProfile, build as _b, variants as V
 from decodingustools_amd.records import ContigRecords
 
@@ -78,6 +79,24 @@ def test_host_route_equals_the_reference(which):
     for order in (sorted(case.reads, key=lambda r: -r[0]), S.random.Random(3).sample(case.reads, len(case.reads))):
         other = S.Case(order, case.ref_len, sort=False)
         assert R.differences(measure(other, 7, 20, (0x704, True)), case.expected(7, 20, (0x704, True))) == []
+
+
+def test_host_route_equals_the_reference_on_long_reads():
+    """The tile of tests/long_cases.py: reads past 65 535 stored bases, past 255 and past 65 535 operations, over many windows."""
+    case = LS.whole()
+    LS.check_shape(case)
+    seen = 0
+    for (a, b), (C, mq, flt) in itertools.product(LS.EP_RANGES, LS.EP_COMBOS):
+        ex, bq = (None, None) if flt is None else (flt[0], LS.MBQ if flt[1] else None)
+        got = V.error_profile_measure(case.rec, LS.LC, LS.REF, C, mq, a, b, exclude_flags=ex, min_base_quality=bq)
+        want = case.ep_expected(C, mq, flt, a, b)
+        assert R.differences(got, want) == [], (a, b, C, mq, flt)
+        seen += want["bases"]
+    assert seen > 5_000_000
+    # from3 of a read past the escape needs its exact length: the last 256 positions of the forward read of 70 000 bases
+    tail = case.ep_expected(256, 20, (0, False), LS.M70 + 70_000 - 256, LS.M70 + 70_000)
+    assert int(tail["from3"][0].sum()) == 1 == int(tail["from3"][255].sum())
+    assert R.differences(V.error_profile_measure(case.rec, LS.LC, LS.REF, 256, 20, LS.M70 + 70_000 - 256, LS.M70 + 70_000, exclude_flags=0), tail) == []
 
 
 def test_host_route_with_one_thread_and_with_four():
@@ -199,17 +218,15 @@ def test_walk_and_host_route_under_address_and_ub_sanitizers(tmp_path):
             pytest.skip("sanitizer runtimes not installed here: " + r.stderr[-300:])
         pytest.fail("the sanitizer build failed:\n" + r.stderr[-3000:])
     # start end C min_quality filtered exclude_flags has_min_base_quality min_base_quality
-    configs = [(300, 4950, 7, 20, 1, 0x704, 1, S.MBQ), (0, S.L, 256, 0, 0, 0, 0, 0), (S.W, 2 * S.W, 1, 20, 1, 0, 0, 0), (1500, 1500, 7, 20, 0, 0, 0, 0),
-               (0, S.L, 201, 20, 1, 0xFFFF, 1, S.MBQ), (2 * S.W - 1, 2 * S.W + 1, 256, 0, 1, 0, 1, S.MBQ)]
-    for name, case in (("planted-short-reference", S.planted(4900)), ("random", S.randomised(1))):
+    short = [(300, 4950, 7, 20, 1, 0x704, 1, S.MBQ), (0, S.L, 256, 0, 0, 0, 0, 0), (S.W, 2 * S.W, 1, 20, 1, 0, 0, 0), (1500, 1500, 7, 20, 0, 0, 0, 0),
+             (0, S.L, 201, 20, 1, 0xFFFF, 1, S.MBQ), (2 * S.W - 1, 2 * S.W + 1, 256, 0, 1, 0, 1, S.MBQ)]
+    # the long reads: the walk's range starts and ends mid-window inside reads of 70 000 bases
+    long = [(33_333, 199_999, 256, 20, 1, 0x704, 1, LS.MBQ), (0, LS.LC, 256, 0, 0, 0, 0, 0), (66 * LS.W, 67 * LS.W, 1, 20, 1, 0, 0, 0),
+            (LS.LC - 1000, LS.LC, 256, 0, 1, 0, 1, LS.MBQ)]
+    for name, case, L, configs in (("planted-short-reference", S.planted(4900), S.L, short), ("random", S.randomised(1), S.L, short),
+                                   ("long", LS.whole().as_ep, LS.LC, long)):
         rec, ev = case.rec, case.events
-        lines = [f"{S.L} {case.ref_len} {rec.n} {len(configs)}", " ".join(str(int(b)) for b in case.ref)]
-        for i in range(rec.n):
-            a, b = int(rec.cigar_off[i]), int(rec.cigar_off[i + 1])
-            s0, s1 = int(rec.seq_off[i]), int(rec.seq_off[i + 1])
-            q0, q1 = int(rec.qual_off[i]), int(rec.qual_off[i + 1])
-            codes = [(int(rec.seq4[j >> 1]) & 15) if j & 1 else (int(rec.seq4[j >> 1]) >> 4) for j in range(s0, s1)]
-            lines.append(" ".join(str(int(x)) for x in [rec.pos[i], rec.flag[i], rec.mapq[i], b - a, *rec.cigar[a:b], s1 - s0, *codes, q1 - q0, *rec.qual[q0:q1]]))
+        lines = [f"{L} {case.ref_len} {rec.n} {len(configs)}", " ".join(map(str, case.ref.tolist()))] + LS.read_lines(rec)
         lines += [" ".join(str(x) for x in c) for c in configs]
         path = str(tmp_path / f"{name}.txt")
         open(path, "w").write("\n".join(lines) + "\n")
@@ -231,7 +248,7 @@ def test_walk_and_host_route_under_address_and_ub_sanitizers(tmp_path):
         h = f"{fnv((walk & 0xFFFFFFFF).reshape(-1)):016x}"
         want = [f"walk {h}", f"split {h}"]
         for k, (a, b, C, mq, filtered, ex, has_bq, bq) in enumerate(configs):
-            z = R.profile(ev, rec, S.L, case.ref, case.ref_len, a, b, C, mq, ex if filtered else None, bq if has_bq else None)
+            z = R.profile(ev, rec, L, case.ref, case.ref_len, a, b, C, mq, ex if filtered else None, bq if has_bq else None)
             words = [z[s] for s in ("reads", "bases", "uncomparable", "ins", "ins_bases", "dels", "del_bases")]
             for t in R.TABLES:
                 words += list(z[t].reshape(-1))

@@ -14,6 +14,7 @@ import pytest
 
 import link_cases as S
 import link_ref as R
+import long_cases as LS
 from decodingustools_amd import EngineError, LinkResult, build as _b, variants as V
 from decodingustools_amd.callable_loci import DEL_CANDIDATE, SCAN_CANDIDATE, DelResult, ScanResult
 from decodingustools_amd.records import ContigRecords
@@ -110,6 +111,29 @@ def test_host_route_equals_the_reference(which):
     assert none.first.tolist() == [0] and none.tables.shape == (0, 6, 6) and none.site_counts.shape == (0, 6)
     one = measure(case, D, K, 20, None, sites=case.sites[5:6])
     assert one.first.tolist() == [0, 0] and np.array_equal(one.site_counts[0], case.expected(D, K, 20, None)["site_counts"][5])
+
+
+def test_host_route_equals_the_reference_on_long_reads():
+    """The tile of tests/long_cases.py: pairs further apart than 65 535 positions inside one read, reads past 65 535 stored
+    bases and past 65 535 operations, a read over a 50 000N."""
+    case = LS.whole()
+    LS.check_shape(case)
+    far = 0
+    sites = np.array(LS.SITES, np.int64)
+    for (D, K), mq, flt in ((pairs, mq, flt) for pairs in LS.LINK_SETS for mq, flt in LS.LINK_COMBOS[pairs]):
+        ex, bq = (None, None) if flt is None else (flt[0], LS.MBQ if flt[1] else None)
+        want = case.link_expected(D, K, mq, flt)
+        assert R.differences(V.link_measure(case.rec, LS.LC, LS.SITES, D, K, mq, exclude_flags=ex, min_base_quality=bq), want) == [], (D, K, mq, flt)
+        first = want["first"].astype(np.int64)
+        anchor = np.repeat(np.arange(len(sites)), np.diff(first))
+        partner = anchor + 1 + np.arange(int(first[-1])) - first[anchor]
+        far = max(far, int(((sites[partner] - sites[anchor] > 65_535) & (want["tables"].sum((1, 2)) > 0)).sum()))
+    assert far >= 20
+    # a tile in descending coordinate order and a shuffled one: the same counts
+    for order in (sorted(case.reads, key=lambda r: -r[0]), S.random.Random(3).sample(case.reads, len(case.reads))):
+        other = LS.Case(order, sort=False)
+        assert R.differences(V.link_measure(other.rec, LS.LC, LS.SITES, 70_000, 15, 0, exclude_flags=0x704, min_base_quality=LS.MBQ),
+                             case.link_expected(70_000, 15, 0, (0x704, True))) == []
 
 
 def test_host_route_with_one_thread_and_with_four():
@@ -350,17 +374,13 @@ def test_walk_and_host_route_under_address_and_ub_sanitizers(tmp_path):
             pytest.skip("sanitizer runtimes not installed here: " + r.stderr[-300:])
         pytest.fail("the sanitizer build failed:\n" + r.stderr[-3000:])
     # max_dist max_partners min_quality filtered exclude_flags has_min_base_quality min_base_quality
-    configs = [(1000, 15, 20, 1, 0x704, 1, S.MBQ), (1000, 15, 0, 0, 0, 0, 0), (1, 1, 20, 1, 0, 0, 0), (40, 4, 0, 1, 0xFFFF, 1, S.MBQ), (2 ** 32 - 1, 15, 20, 1, 0, 1, S.MBQ)]
-    for name, case in (("planted", S.planted()), ("random", S.randomised(1))):
+    short = [(1000, 15, 20, 1, 0x704, 1, S.MBQ), (1000, 15, 0, 0, 0, 0, 0), (1, 1, 20, 1, 0, 0, 0), (40, 4, 0, 1, 0xFFFF, 1, S.MBQ), (2 ** 32 - 1, 15, 20, 1, 0, 1, S.MBQ)]
+    # the long reads: the walk's pair set reaches 70 000 positions, fifteen partners
+    long = [(70_000, 15, 20, 1, 0x704, 1, LS.MBQ), (2 ** 32 - 1, 15, 0, 0, 0, 0, 0), (1, 1, 20, 1, 0, 0, 0), (1000, 4, 0, 1, 0xFFFF, 1, LS.MBQ)]
+    for name, case, L, configs in (("planted", S.planted(), S.L, short), ("random", S.randomised(1), S.L, short), ("long", LS.whole().as_link, LS.LC, long)):
         rec, ev = case.rec, case.events
         sites = [int(s) for s in case.sites]
-        lines = [f"{S.L} {rec.n} {len(sites)} {len(configs)}"]
-        for i in range(rec.n):
-            a, b = int(rec.cigar_off[i]), int(rec.cigar_off[i + 1])
-            s0, s1 = int(rec.seq_off[i]), int(rec.seq_off[i + 1])
-            q0, q1 = int(rec.qual_off[i]), int(rec.qual_off[i + 1])
-            codes = [(int(rec.seq4[j >> 1]) & 15) if j & 1 else (int(rec.seq4[j >> 1]) >> 4) for j in range(s0, s1)]
-            lines.append(" ".join(str(int(x)) for x in [rec.pos[i], rec.flag[i], rec.mapq[i], b - a, *rec.cigar[a:b], s1 - s0, *codes, q1 - q0, *rec.qual[q0:q1]]))
+        lines = [f"{L} {rec.n} {len(sites)} {len(configs)}"] + LS.read_lines(rec)
         lines.append(" ".join(str(s) for s in sites))
         lines += [" ".join(str(x) for x in c) for c in configs]
         path = str(tmp_path / f"{name}.txt")
@@ -373,7 +393,7 @@ def test_walk_and_host_route_under_address_and_ub_sanitizers(tmp_path):
         words = []
         for rr in range(rec.n):
             lo, hi = int(ev["lo"][rr]), int(ev["hi"][rr])
-            if not (0 <= lo < S.L) or hi <= lo:
+            if not (0 <= lo < L) or hi <= lo:
                 continue
             for i in range(bisect.bisect_left(sites, lo), bisect.bisect_left(sites, hi)):
                 packed = 0
@@ -383,6 +403,6 @@ def test_walk_and_host_route_under_address_and_ub_sanitizers(tmp_path):
                 words += [packed & 0xFFFFFFFF, packed >> 32]
         want = [f"walk {fnv(words):016x}"]
         for k, (D, K, mq, filtered, ex, has_bq, bq) in enumerate(configs):
-            z = R.counts(ev, rec, S.L, sites, D, K, mq, ex if filtered else None, bq if has_bq else None)
+            z = R.counts(ev, rec, L, sites, D, K, mq, ex if filtered else None, bq if has_bq else None)
             want.append(f"measure {k} {fnv(list(z['first']) + list(z['tables'].reshape(-1)) + list(z['site_counts'].reshape(-1))):016x}")
         assert r.stdout.splitlines() == want, (name, r.stdout, want)

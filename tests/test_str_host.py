@@ -11,6 +11,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import long_cases as LS
 import str_cases as S
 import str_ref as R
 from decodingustools_amd import EngineError, build as _b, variants as V
@@ -64,6 +65,23 @@ def test_host_route_equals_the_reference(which):
         other = S.Case(order, case.loci, sort=False)
         got = V.str_measure(other.rec, S.L, case.loci, 5, 20, 0x704)
         assert np.array_equal(got.hist, case.expected(5, 20, 0x704)[0]) and np.array_equal(got.partial, case.expected(5, 20, 0x704)[1])
+
+
+def test_host_route_equals_the_reference_on_long_reads():
+    """The tile of tests/long_cases.py: loci at least 65 536 positions past a read's start, inside reads of some 6 000 and of
+    66 001 operations, over a 50 000N."""
+    case = LS.whole()
+    LS.check_shape(case)
+    some = 0
+    for flank, mq, ex in LS.STR_COMBOS:
+        hist, partial = case.str_expected(flank, mq, ex)
+        got = V.str_measure(case.rec, LS.LC, LS.LOCI, flank, mq, ex)
+        assert got.hist.shape == hist.shape and np.array_equal(got.hist, hist), (flank, mq, ex, np.argwhere(got.hist != hist)[:3])
+        assert np.array_equal(got.partial, partial), (flank, mq, ex)
+        some += int(hist.sum())
+    assert some > 10_000
+    hist, partial = case.str_expected(5, 20, None)
+    assert int(hist[:, 0, 127].sum()) >= 4 and int(hist[:, 0, 63 + 7].sum()) >= 2 and int(hist[:, 0, 63 - 12].sum()) >= 2 and int(partial.sum()) > 20
 
 
 def test_host_route_refusals_and_the_empty_call():
@@ -240,12 +258,9 @@ def test_walk_and_host_route_under_address_and_ub_sanitizers(tmp_path):
             pytest.skip("sanitizer runtimes not installed here: " + r.stderr[-300:])
         pytest.fail("the sanitizer build failed:\n" + r.stderr[-3000:])
     configs = [(5, 20, 2, 0x704), (1, 0, 1, 0), (64, 20, 2, 0), (5, 0, 2, 0xFFFF), (1, 20, 2, 0x704), (64, 0, 1, 0)]
-    for name, case in (("planted", S.planted()), ("random", S.randomised(1))):
+    for name, case, L in (("planted", S.planted(), S.L), ("random", S.randomised(1), S.L), ("long", LS.whole().as_str, LS.LC)):
         rec = case.rec
-        lines = [f"{S.L} {rec.n} {len(case.loci)} {len(configs)}"]
-        for i in range(rec.n):
-            a, b = int(rec.cigar_off[i]), int(rec.cigar_off[i + 1])
-            lines.append(" ".join(str(int(x)) for x in [rec.pos[i], rec.flag[i], rec.mapq[i], b - a, *rec.cigar[a:b]]))
+        lines = [f"{L} {rec.n} {len(case.loci)} {len(configs)}"] + LS.read_lines(rec, bases=False)
         lines += [f"{s} {e}" for s, e in case.loci] + [" ".join(str(x) for x in c) for c in configs]
         path = str(tmp_path / f"{name}.txt")
         open(path, "w").write("\n".join(lines) + "\n")
