@@ -19,6 +19,7 @@ SOURCES = [os.path.join(CSRC, "callable_loci.hip"), os.path.join(CSRC, "qual_pac
 CLI = os.path.join(LIBDIR, "dut-coverage")
 CLI_SRC = os.path.join(CSRC, "coverage_main.cpp")
 HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "pileup_bytes.hip.h"), os.path.join(CSRC, "pileup_rows.hip.h"),
+           os.path.join(CSRC, "window_depths.hip.h"),
            os.path.join(CSRC, "depth_profile.hip.h"), os.path.join(CSRC, "depth_runs.hip.h"), os.path.join(CSRC, "depth_targets.hip.h"),
            os.path.join(CSRC, "site_scan.hip.h"),
            os.path.join(CSRC, "engine_base.hip.h"), os.path.join(CSRC, "site_engine.hip.h"),

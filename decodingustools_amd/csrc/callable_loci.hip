@@ -12,6 +12,7 @@
 #include "kernels.hip.h"
 #include "pileup_bytes.hip.h"
 #include "pileup_rows.hip.h"
+#include "window_depths.hip.h"
 #include "depth_profile.hip.h"
 #include "depth_runs.hip.h"
 #include "depth_targets.hip.h"
@@ -953,7 +954,30 @@ RowsArgs rows_args(const cl_ctx *c, uint32_t *dbg_raw, uint32_t *dbg_qc, uint32_
         c->opt.min_depth_for_low_mapq, c->d_lut.p, c->opt.max_low_mapq_fraction,
         c->d_state.p, dbg_raw, dbg_qc, dbg_low};
 }
+// ... and what the three depth kernels read of a run (window_depths.hip.h): the first member of their records
+DepthResidents depth_residents(const cl_ctx *c)
+{
+    return DepthResidents{c->d_win.p, c->d_heads.p, c->d_wide_idx.p, c->d_rows.p, c->extent, c->n_win};
+}
 #pragma clang diagnostic pop
+
+// The instantiation of a depth kernel that fits the resident contig, out of the kernel's table over (counter planes 8, 16,
+// 32; heads of 8 bytes, of 4).  A kernel that does not look at one of the two has the same entry along it.
+template <class Args> using DepthKernel = void (*)(Args);
+template <class Args> DepthKernel<Args> depth_kernel(const cl_ctx *c, const DepthKernel<Args> (&table)[3][2])
+{
+    const uint32_t np = c->counter_planes();
+    return table[np == 8u ? 0 : np == 16u ? 1 : 2][c->heads4 ? 1 : 0];
+}
+const DepthKernel<DepthArgs> kDepthProfileKernels[3][2] = {{k_depth_profile<8, false>, k_depth_profile<8, true>},
+    {k_depth_profile<16, false>, k_depth_profile<16, true>}, {k_depth_profile<32, false>, k_depth_profile<32, true>}};
+const DepthKernel<TargetArgs> kTargetDepthKernels[3][2] = {{k_target_depth<8, false>, k_target_depth<8, true>},
+    {k_target_depth<16, false>, k_target_depth<16, true>}, {k_target_depth<32, false>, k_target_depth<32, true>}};
+// (only the raw depths come from the heads, and they need no plane; the qc depths are the rows' column sums)
+const DepthKernel<RunsArgs> kDepthRunsRawKernels[3][2] = {{k_depth_runs<8, false, false>, k_depth_runs<8, false, true>},
+    {k_depth_runs<8, false, false>, k_depth_runs<8, false, true>}, {k_depth_runs<8, false, false>, k_depth_runs<8, false, true>}};
+const DepthKernel<RunsArgs> kDepthRunsQcKernels[3][2] = {{k_depth_runs<8, true, false>, k_depth_runs<8, true, false>},
+    {k_depth_runs<16, true, false>, k_depth_runs<16, true, false>}, {k_depth_runs<32, true, false>, k_depth_runs<32, true, false>}};
 
 // (the 32-bit counter variant, DEEP, of either kernel is used only when the window bounds asked for it: kNeedDeep)
 template <bool DEBUG> void launch_bytes(cl_ctx *c, const BytesArgs &a)
@@ -1913,6 +1937,26 @@ cl_status cl_debug_depths(cl_ctx *c, uint32_t *raw, uint32_t *qc, uint32_t *low,
     });
 }
 
+// What cl_contig_depth_profile, cl_contig_depth_runs and cl_contig_targets (`who`) refuse alike, in the order they have
+// always refused it: the context's kind, the call's own arguments, the contig's state (`collected`: the call reads the
+// intervals too); behind it the device is current.  The arguments' checks look at nothing of the context, so the caller
+// makes them first and hands over what they gave (`args`): their place is decided here, a later fail() replaces their message.
+static cl_status depth_call_ready(cl_ctx *c, const char *who, bool collected, cl_status args)
+{
+    if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
+    if (!c->bits) return fail(c, CL_ERR_INVALID, std::string(who) + " serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
+    if (args != CL_OK) return args;
+    if (!c->uploaded || !c->ran || (collected && !c->collected) || c->form != 3)
+        return fail(c, CL_ERR_INVALID, std::string(who) + (collected ? " needs a contig that has been collected since its last run (cl_contig_collect or cl_contig_finish)"
+                                                                      : " needs a contig that has been run"));
+    if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return CL_OK;
+}
+
+#pragma clang diagnostic push                              // (argument records in member order, as rows_args)
+#pragma clang diagnostic error "-Wmissing-field-initializers"
+
 // The depth distribution of the resident contig (include/callable_loci.h): one extra launch of k_depth_profile over the
 // residents of the last run, a few KB back.  Nothing of a run is touched: summary, intervals and window partials stay.
 cl_status cl_contig_depth_profile_ms(cl_ctx *c, double *kernel_ms)
@@ -1928,34 +1972,24 @@ cl_status cl_contig_depth_profile(cl_ctx *c, uint32_t n_bins, uint32_t window, c
         if (!c) return CL_ERR_INVALID;
         if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: null result");
         memset(out, 0, sizeof(*out));
-        if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-        if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
-        if (n_bins < CL_DEPTH_MIN_BINS || n_bins > CL_DEPTH_MAX_BINS) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: n_bins outside [2, 4096]");
-        if (window != 0 && window < CL_DEPTH_MIN_WINDOW) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: a window of 1 to 15 positions (0 = no window table, else at least 16)");
-        if (!c->uploaded || !c->ran || c->form != 3) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile needs a contig that has been run");
-        if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
-        HIP_TRY(c, hipSetDevice(c->device));
+        const cl_status ready = depth_call_ready(c, "cl_contig_depth_profile", false, [&]() -> cl_status {
+            if (n_bins < CL_DEPTH_MIN_BINS || n_bins > CL_DEPTH_MAX_BINS) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: n_bins outside [2, 4096]");
+            if (window != 0 && window < CL_DEPTH_MIN_WINDOW) return fail(c, CL_ERR_INVALID, "cl_contig_depth_profile: a window of 1 to 15 positions (0 = no window table, else at least 16)");
+            return CL_OK;
+        }());
+        if (ready != CL_OK) return ready;
         const uint64_t n_windows = window ? ((uint64_t)c->extent + window - 1) / window : 0;
         const size_t n_words = 2 + 2 * (size_t)n_bins + 2 * (size_t)n_windows;
         HIP_TRY(c, c->d_prof.reserve(n_words));
         c->h_prof.assign(n_words, 0ull);
         HIP_TRY(c, hipMemsetAsync(c->d_prof.p, 0, n_words * sizeof(unsigned long long), c->stream));
         if (c->n_win) {
-            DepthArgs a;
-            a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
-            a.extent = c->extent; a.n_win = c->n_win; a.n_bins = n_bins; a.window = window;
-            a.sums = c->d_prof.p; a.hist = c->d_prof.p + 2; a.wins = c->d_prof.p + 2 + 2 * (size_t)n_bins; a.n_windows = n_windows;
+            const DepthArgs a{depth_residents(c), n_bins, window, c->d_prof.p + 2, c->d_prof.p + 2 + 2 * (size_t)n_bins, n_windows, c->d_prof.p};
             const size_t lds = 2u * (size_t)n_bins * sizeof(uint32_t);
             // workgroups that stay: a histogram is flushed once per workgroup
             const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
             if (c->profiling) HIP_TRY(c, c->t_prof.start(c->stream));
-#define CL_LAUNCH(NP_) do { \
-            if (c->heads4) hipLaunchKernelGGL((k_depth_profile<NP_, true>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a); \
-            else hipLaunchKernelGGL((k_depth_profile<NP_, false>), dim3(grid), dim3(kDepthBlock), lds, c->stream, a); } while (0)
-            if (c->counter_planes() == 8u) CL_LAUNCH(8);
-            else if (c->counter_planes() == 16u) CL_LAUNCH(16);
-            else CL_LAUNCH(32);
-#undef CL_LAUNCH
+            hipLaunchKernelGGL(depth_kernel(c, kDepthProfileKernels), dim3(grid), dim3(kDepthBlock), lds, c->stream, a);
             HIP_TRY(c, hipGetLastError());
             if (c->profiling) HIP_TRY(c, c->t_prof.stop(c->stream));
             HIP_TRY(c, hipMemcpyAsync(c->h_prof.data(), c->d_prof.p, n_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -1991,17 +2025,16 @@ cl_status cl_contig_depth_runs(cl_ctx *c, uint32_t kind, const uint32_t *edges, 
         if (!c) return CL_ERR_INVALID;
         if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: null result");
         memset(out, 0, sizeof(*out));
-        if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-        if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
-        if (kind != CL_DEPTH_RAW && kind != CL_DEPTH_QC) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: unknown depth kind (CL_DEPTH_RAW or CL_DEPTH_QC)");
-        if (n_edges > CL_RUNS_MAX_EDGES) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: more than 64 edges");
-        if (n_edges && !edges) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: null edges");
-        if (n_edges && edges[0] == 0u) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: the first edge is 0 (the first band starts at depth 0 by itself)");
-        for (uint32_t i = 1; i < n_edges; ++i)
-            if (edges[i] <= edges[i - 1]) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: the edges are not strictly ascending");
-        if (!c->uploaded || !c->ran || c->form != 3) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs needs a contig that has been run");
-        if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
-        HIP_TRY(c, hipSetDevice(c->device));
+        const cl_status ready = depth_call_ready(c, "cl_contig_depth_runs", false, [&]() -> cl_status {
+            if (kind != CL_DEPTH_RAW && kind != CL_DEPTH_QC) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: unknown depth kind (CL_DEPTH_RAW or CL_DEPTH_QC)");
+            if (n_edges > CL_RUNS_MAX_EDGES) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: more than 64 edges");
+            if (n_edges && !edges) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: null edges");
+            if (n_edges && edges[0] == 0u) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: the first edge is 0 (the first band starts at depth 0 by itself)");
+            for (uint32_t i = 1; i < n_edges; ++i)
+                if (edges[i] <= edges[i - 1]) return fail(c, CL_ERR_INVALID, "cl_contig_depth_runs: the edges are not strictly ascending");
+            return CL_OK;
+        }());
+        if (ready != CL_OK) return ready;
         c->dr_ms = 0.0;
         unsigned long long total = 0ull;
         uint32_t err = 0u;
@@ -2009,26 +2042,16 @@ cl_status cl_contig_depth_runs(cl_ctx *c, uint32_t kind, const uint32_t *edges, 
             const size_t nw = c->n_win;
             HIP_TRY(c, c->d_dr_win.reserve(3 * nw + 1));
             HIP_TRY(c, c->d_dr_off.reserve(nw + 1));
-            RunsArgs a;
-            memset(&a, 0, sizeof(a));
-            a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
-            a.extent = c->extent; a.n_win = c->n_win; a.n_edges = n_edges;
+            // (the count pass writes nothing through start and value; the edges follow)
+            RunsArgs a{depth_residents(c), n_edges, 0u, c->d_dr_win.p, c->d_dr_win.p + nw, c->d_dr_win.p + 2 * nw, c->d_dr_off.p,
+                       nullptr, nullptr, 0ull, c->d_dr_win.p + 3 * nw, {}};
             for (uint32_t i = 0; i < n_edges; ++i) a.edges[i] = edges[i];
-            a.cnt = c->d_dr_win.p; a.first = c->d_dr_win.p + nw; a.last = c->d_dr_win.p + 2 * nw; a.err = c->d_dr_win.p + 3 * nw;
-            a.off = c->d_dr_off.p;
             const uint32_t grid = std::min<uint32_t>(c->n_win, 65536u);
-            auto launch = [&]() {
-                // (only the raw depths come from the heads: the qc depths are the rows' column sums)
-                if (kind == CL_DEPTH_RAW && c->heads4) hipLaunchKernelGGL((k_depth_runs<8, false, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else if (kind == CL_DEPTH_RAW) hipLaunchKernelGGL((k_depth_runs<8, false, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else if (c->counter_planes() == 8u) hipLaunchKernelGGL((k_depth_runs<8, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else if (c->counter_planes() == 16u) hipLaunchKernelGGL((k_depth_runs<16, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-                else hipLaunchKernelGGL((k_depth_runs<32, true, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
-            };
+            const DepthKernel<RunsArgs> kernel = depth_kernel(c, kind == CL_DEPTH_RAW ? kDepthRunsRawKernels : kDepthRunsQcKernels);
+            auto launch = [&]() { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kDepthBlock), 0, c->stream, a); };
             // ---- count, scan: how many runs there are ----
             HIP_TRY(c, hipMemsetAsync(a.err, 0, sizeof(uint32_t), c->stream));
             if (c->profiling) HIP_TRY(c, c->t_dr_count.start(c->stream));
-            a.write = 0u;
             launch();
             HIP_TRY(c, hipGetLastError());
             hipLaunchKernelGGL(k_depth_runs_scan, dim3(1), dim3(kRunsScanBlock), 0, c->stream, a.cnt, a.first, a.last, c->n_win, c->d_dr_off.p, c->d_dr_off.p + nw);
@@ -2083,21 +2106,19 @@ cl_status cl_contig_targets(cl_ctx *c, const uint32_t *starts, const uint32_t *e
         if (!c) return CL_ERR_INVALID;
         if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null result");
         *out = nullptr;
-        if (c->host_only) return fail(c, CL_ERR_DEVICE, "a host-only context has no device");
-        if (!c->bits) return fail(c, CL_ERR_INVALID, "cl_contig_targets serves the pass-bit form only (the context runs DUT_QUAL_FORM=bytes)");
-        if (n_targets > CL_TARGETS_MAX) return fail(c, CL_ERR_INVALID, "cl_contig_targets: more than 2^24 targets");
-        if (n_targets && (!starts || !ends)) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null starts or ends");
-        if (n_thresholds > CL_TARGET_MAX_THRESHOLDS) return fail(c, CL_ERR_INVALID, "cl_contig_targets: more than 8 thresholds");
-        if (n_thresholds && !thresholds) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null thresholds");
-        if (n_thresholds && thresholds[0] == 0u) return fail(c, CL_ERR_INVALID, "cl_contig_targets: the first threshold is 0 (every position has a depth of at least 0)");
-        for (uint32_t i = 1; i < n_thresholds; ++i)
-            if (thresholds[i] <= thresholds[i - 1]) return fail(c, CL_ERR_INVALID, "cl_contig_targets: the thresholds are not strictly ascending");
-        for (size_t i = 0; i < n_targets; ++i)
-            if (starts[i] > ends[i]) return fail(c, CL_ERR_INVALID, "cl_contig_targets: target " + std::to_string(i) + " has start > end");
-        if (!c->uploaded || !c->ran || !c->collected || c->form != 3)
-            return fail(c, CL_ERR_INVALID, "cl_contig_targets needs a contig that has been collected since its last run (cl_contig_collect or cl_contig_finish)");
-        if (c->bounds_err & kErrRange) return fail(c, CL_ERR_RANGE, "a read ends beyond the engine's 32-bit coordinate range");
-        HIP_TRY(c, hipSetDevice(c->device));
+        const cl_status ready = depth_call_ready(c, "cl_contig_targets", true, [&]() -> cl_status {
+            if (n_targets > CL_TARGETS_MAX) return fail(c, CL_ERR_INVALID, "cl_contig_targets: more than 2^24 targets");
+            if (n_targets && (!starts || !ends)) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null starts or ends");
+            if (n_thresholds > CL_TARGET_MAX_THRESHOLDS) return fail(c, CL_ERR_INVALID, "cl_contig_targets: more than 8 thresholds");
+            if (n_thresholds && !thresholds) return fail(c, CL_ERR_INVALID, "cl_contig_targets: null thresholds");
+            if (n_thresholds && thresholds[0] == 0u) return fail(c, CL_ERR_INVALID, "cl_contig_targets: the first threshold is 0 (every position has a depth of at least 0)");
+            for (uint32_t i = 1; i < n_thresholds; ++i)
+                if (thresholds[i] <= thresholds[i - 1]) return fail(c, CL_ERR_INVALID, "cl_contig_targets: the thresholds are not strictly ascending");
+            for (size_t i = 0; i < n_targets; ++i)
+                if (starts[i] > ends[i]) return fail(c, CL_ERR_INVALID, "cl_contig_targets: target " + std::to_string(i) + " has start > end");
+            return CL_OK;
+        }());
+        if (ready != CL_OK) return ready;
         for (double &m : c->tg_ms) m = 0.0;
         if (n_targets == 0) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return CL_OK; }
         const size_t n = n_targets, nw = c->n_win;
@@ -2162,23 +2183,13 @@ cl_status cl_contig_targets(cl_ctx *c, const uint32_t *starts, const uint32_t *e
         uint32_t *d_err = c->d_tg_out.p + (size_t)kTargetWords * n;
         HIP_TRY(c, hipMemcpyAsync(c->d_tg_in.p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemsetAsync(c->d_tg_out.p, 0, ((size_t)kTargetWords * n + 1) * sizeof(uint32_t), c->stream));
-        TargetArgs a;
-        memset(&a, 0, sizeof(a));
-        a.win = c->d_win.p; a.heads = c->d_heads.p; a.wide_idx = c->d_wide_idx.p; a.rows = c->d_rows.p;
-        a.extent = extent; a.n_win = c->n_win; a.n_pt = (uint32_t)n_pt;
-        a.pt = c->d_tg_in.p;                                 // (pt_first follows the points)
-        a.wtot = c->d_tg_win.p; a.pre = c->d_tg_pre.p; a.err = d_err;
+        // (pt_first follows the points; the thresholds follow)
+        TargetArgs a{depth_residents(c), (uint32_t)n_pt, 0u, c->d_tg_in.p, c->d_tg_win.p, c->d_tg_pre.p, d_err, {}};
         for (uint32_t k = 0; k < CL_TARGET_MAX_THRESHOLDS; ++k) a.thr[k] = k < K ? thresholds[k] : 0xFFFFFFFFu;
         // workgroups that stay, as k_depth_profile's: a window is a few microseconds of work
         const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
         if (c->profiling) HIP_TRY(c, c->t_tg[0].start(c->stream));
-#define CL_LAUNCH(NP_) do { \
-        if (c->heads4) hipLaunchKernelGGL((k_target_depth<NP_, true>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a); \
-        else hipLaunchKernelGGL((k_target_depth<NP_, false>), dim3(grid), dim3(kDepthBlock), 0, c->stream, a); } while (0)
-        if (c->counter_planes() == 8u) CL_LAUNCH(8);
-        else if (c->counter_planes() == 16u) CL_LAUNCH(16);
-        else CL_LAUNCH(32);
-#undef CL_LAUNCH
+        hipLaunchKernelGGL(depth_kernel(c, kTargetDepthKernels), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());
         if (c->profiling) { HIP_TRY(c, c->t_tg[0].stop(c->stream)); HIP_TRY(c, c->t_tg[1].start(c->stream)); }
         unsigned long long *d_off = c->d_tg_off.p;
@@ -2204,5 +2215,6 @@ cl_status cl_contig_targets(cl_ctx *c, const uint32_t *starts, const uint32_t *e
         return CL_OK;
     });
 }
+#pragma clang diagnostic pop
 
 } // extern "C"

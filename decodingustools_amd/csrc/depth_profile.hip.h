@@ -1,5 +1,6 @@
 // depth_profile.hip.h -- k_depth_profile: the depth distribution of the resident contig, reduced on the device
-// (cl_contig_depth_profile, include/callable_loci.h).  Included by callable_loci.hip behind pileup_rows.hip.h (bs_add4, bs_maj, the heads).
+// (cl_contig_depth_profile, include/callable_loci.h).  Included by callable_loci.hip behind window_depths.hip.h (the
+// rebuild of both depths, shared with k_depth_runs and k_target_depth).
 //
 // A kernel of its own beside k_pileup_rows, not a further template flag of it: it reads the same residents (the
 // windows' pass-bit rows, heads and window records) and rebuilds raw_depth and qc_depth per position the same way
@@ -22,15 +23,10 @@
 
 namespace clk {
 
-constexpr int kDepthBlock = 128;
 constexpr int kDepthWinSlots = 2048 / 16 + 2;
 
 struct DepthArgs {
-    const WinMeta  *win;
-    const void     *heads;            // 8 bytes each, or 4 with HEAD4 (pileup_rows.hip.h)
-    const uint32_t *wide_idx;
-    const uint4    *rows;
-    uint32_t extent, n_win;
+    DepthResidents res;
     uint32_t n_bins, window;           // window = 0: no window table
     unsigned long long *hist;          // [2][n_bins]: raw, qc
     unsigned long long *wins;          // [2][n_windows]: raw, qc (window > 0)
@@ -41,8 +37,7 @@ struct DepthArgs {
 template <int NP, bool HEAD4>
 __global__ __launch_bounds__(kDepthBlock) void k_depth_profile(DepthArgs a)
 {
-    constexpr int T = 2048, BS = kDepthBlock, PER = T / BS;
-    static_assert(PER == 16 && BS == 128, "two waves, a lane of the final phase owns half a block of 32 positions");
+    constexpr int T = kDepthT, BS = kDepthBlock, PER = kDepthPer;
     __shared__ __attribute__((aligned(16))) uint32_t s_diff[T];
     __shared__ uint32_t s_pl[NP][64];                      // wave 1's planes, then the window's (written by wave 0)
     __shared__ unsigned long long s_win[2][kDepthWinSlots];
@@ -56,69 +51,27 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_profile(DepthArgs a)
     uint32_t *const h_raw = s_hist, *const h_qc = s_hist + nb;
     unsigned long long tot_raw = 0ull, tot_qc = 0ull;
 
-    for (uint32_t w = blockIdx.x; w < a.n_win; w += gridDim.x) {
+    for (uint32_t w = blockIdx.x; w < a.res.n_win; w += gridDim.x) {
         const uint32_t W = w * (uint32_t)T;
-        const WinMeta wm = a.win[w];
-        const uint32_t lo = wm.lo, wlo = wm.wlo, wn = wm.wn;
-        const uint32_t n_cand = wn + (wm.hi - lo);
-        const uint32_t ng = wm.rn;
-        const RowLane rl = row_lane(a.rows, wm, lane, wv);
+        const WinMeta wm = a.res.win[w];
+        const RowLane rl = row_lane(a.res.rows, wm, lane, wv);
 
-        // ---- clear (the previous window's readers are behind the barrier at the end of the loop) ----
-        {
-            uint4 *d4 = reinterpret_cast<uint4 *>(s_diff);
-            for (int i = tid; i < T / 4; i += BS) d4[i] = make_uint4(0, 0, 0, 0);
-            if (S) for (int i = tid; i < 2 * kDepthWinSlots; i += BS) (&s_win[0][0])[i] = 0ull;
-        }
+        wd_clear(s_diff, tid);
+        if (S) for (int i = tid; i < 2 * kDepthWinSlots; i += BS) (&s_win[0][0])[i] = 0ull;
         __syncthreads();
 
-        // ---- the window's rows: groups wv, wv + 2, ... into this wave's counter planes ----
         uint32_t c[NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) c[p] = 0u;
-        for (int k = 0; wv + (uint32_t)k < ng; k += 2) bs_add4<NP>(c, row_unit(rl, k));
-        // ---- the window's candidates: +-1 at the clipped span ends (as k_pileup_rows) ----
-        for (uint32_t v = tid; v < n_cand; v += BS) {
-            uint32_t r = lo + (v - wn);
-            if (v < wn) r = a.wide_idx[wlo + v];
-            const HeadCand hc = head_cand<T>(head_at<HEAD4>(a.heads, r), W);
-            if (hc.hit) {
-                atomicAdd(&s_diff[hc.cb], 1u);
-                if (hc.ce < (uint32_t)T) atomicAdd(&s_diff[hc.ce], 0xFFFFFFFFu);
-            }
-        }
-        if (wv != 0) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) s_pl[p][lane] = c[p];
-        }
+        wd_rows<NP>(c, rl, wm.rn, wv);
+        wd_scatter<HEAD4>(a.res, wm, W, s_diff, tid);
+        if (wv != 0) wd_planes_put<NP>(c, s_pl, lane);
         __syncthreads();
-        if (wv == 0) {
-            uint32_t carry = 0u;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const uint32_t d = s_pl[p][lane];
-                const uint32_t s = c[p] ^ d ^ carry;
-                carry = bs_maj(c[p], d, carry);
-                s_pl[p][lane] = s;                         // (a lane reads and writes its own slots only)
-            }
-        }
-        // ---- raw_depth: the differences scanned ----
-        uint32_t vr[PER];
-        uint32_t sr = 0;
-#pragma unroll
-        for (int q = 0; q < PER / 4; ++q) {
-            const uint4 d = reinterpret_cast<const uint4 *>(s_diff)[tid * (PER / 4) + q];
-            sr += d.x; vr[4 * q] = sr; sr += d.y; vr[4 * q + 1] = sr;
-            sr += d.z; vr[4 * q + 2] = sr; sr += d.w; vr[4 * q + 3] = sr;
-        }
-        const uint32_t ir = dpp_incl_scan_u32(sr);
-        if (tid == 63u) s_tot = ir;
+        if (wv == 0) wd_planes_add<NP>(c, s_pl, lane);
+        uint32_t vr[PER], vq[PER];
+        const uint32_t excl = wd_diff_scan(vr, s_diff, &s_tot, tid);
         __syncthreads();
-        const uint32_t off = ir - sr + (wv ? s_tot : 0u);
-        const uint32_t p0 = W + tid * PER;
-        const uint32_t n_ok = p0 >= a.extent ? 0u : (a.extent - p0 < (uint32_t)PER ? a.extent - p0 : (uint32_t)PER);
-        // ---- qc_depth: the 16 counts of this thread out of the planes of block tid / 2 ----
-        uint32_t vq[PER];
+        wd_diff_finish(vr, excl, &s_tot, wv);
+        // ---- qc_depth: wd_extract's loop in the kernel's own text.  Through the function this kernel takes 11 to 14
+        // registers more (a wave less per SIMD at 8 and 16 planes) or, with the function's asm, 8 more at 8 planes ----
 #pragma unroll
         for (int i = 0; i < PER; ++i) vq[i] = 0u;
 #pragma unroll
@@ -127,13 +80,14 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_profile(DepthArgs a)
 #pragma unroll
             for (int i = 0; i < PER; ++i) vq[i] |= ((word >> i) & 1u) << p;
         }
+        const DepthSpan sp = wd_span(W, tid, a.res.extent);
+        const uint32_t p0 = sp.p0, n_ok = sp.n_ok;
         // (positions at and beyond the extent: no read reaches them; they count nowhere)
         unsigned long long a_raw = 0ull, a_qc = 0ull, b_raw = 0ull, b_qc = 0ull;
         uint32_t brk = (uint32_t)PER, k0 = 0u;
         if (S) { k0 = p0 / S; const uint32_t left = S - (p0 - k0 * S); brk = left < (uint32_t)PER ? left : (uint32_t)PER; }
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            vr[i] += off;
             if ((uint32_t)i >= n_ok) { vr[i] = 0u; vq[i] = 0u; }
             if ((uint32_t)i < brk) { a_raw += vr[i]; a_qc += vq[i]; } else { b_raw += vr[i]; b_qc += vq[i]; }
             vr[i] = vr[i] < nb - 1u ? vr[i] : nb - 1u;

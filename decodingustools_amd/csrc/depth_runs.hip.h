@@ -2,7 +2,7 @@
 // device (cl_contig_depth_runs, include/callable_loci.h).  Included by callable_loci.hip behind depth_profile.hip.h.
 //
 // A sibling of k_depth_profile, a kernel of its own: it reads the same residents (window records, heads, wide list, rows)
-// and rebuilds a depth per position the same way -- bit-sliced counter planes for qc (bs_add4; wave 0 adds wave 1's), the
+// and rebuilds a depth per position with the same code (window_depths.hip.h) -- bit-sliced counter planes for qc, the
 // scanned +-1 difference array for raw; 128 threads, a window of 2048, 16 positions per thread --, but only the kind the
 // call asked for (QC: the raw kind reads no row, the qc kind no head), and instead of counting the depths it turns them
 // into runs.  No per-position array reaches HBM.
@@ -28,11 +28,7 @@ constexpr int kRunsMaxEdges = 64;                          // CL_RUNS_MAX_EDGES
 constexpr int kRunsScanBlock = 1024;
 
 struct RunsArgs {
-    const WinMeta  *win;
-    const void     *heads;            // 8 bytes each, or 4 with HEAD4 (pileup_rows.hip.h)
-    const uint32_t *wide_idx;
-    const uint4    *rows;
-    uint32_t extent, n_win;
+    DepthResidents res;
     uint32_t n_edges, write;
     uint32_t *cnt, *first, *last;      // [n_win] each: written by the count pass, read by the scan and the write pass
     const unsigned long long *off;     // [n_win]: the scan's offsets (write pass)
@@ -45,8 +41,7 @@ struct RunsArgs {
 template <int NP, bool QC, bool HEAD4>
 __global__ __launch_bounds__(kDepthBlock) void k_depth_runs(RunsArgs a)
 {
-    constexpr int T = 2048, BS = kDepthBlock, PER = T / BS;
-    static_assert(PER == 16 && BS == 128, "two waves, a thread's 16 positions are half a block of 32");
+    constexpr int T = kDepthT, BS = kDepthBlock, PER = kDepthPer;
     __shared__ __attribute__((aligned(16))) uint32_t s_diff[QC ? 4 : T];
     __shared__ uint32_t s_pl[QC ? NP : 1][64];             // wave 1's planes, then the window's (written by wave 0)
     __shared__ uint32_t s_edges[2 * kRunsMaxEdges];        // the edges, then 0xFFFFFFFF (the search probes below 128)
@@ -69,77 +64,32 @@ __global__ __launch_bounds__(kDepthBlock) void k_depth_runs(RunsArgs a)
         return pos;
     };
 
-    for (uint32_t w = blockIdx.x; w < a.n_win; w += gridDim.x) {
+    for (uint32_t w = blockIdx.x; w < a.res.n_win; w += gridDim.x) {
         const uint32_t W = w * (uint32_t)T;
-        const WinMeta wm = a.win[w];
+        const WinMeta wm = a.res.win[w];
         uint32_t d[PER];
         if constexpr (!QC) {
-            // ---- raw_depth: the +-1 of every candidate head at its clipped span ends, scanned (as k_depth_profile) ----
-            const uint32_t lo = wm.lo, wlo = wm.wlo, wn = wm.wn;
-            const uint32_t n_cand = wn + (wm.hi - lo);
-            {
-                uint4 *d4 = reinterpret_cast<uint4 *>(s_diff);
-                for (int i = tid; i < T / 4; i += BS) d4[i] = make_uint4(0, 0, 0, 0);
-            }
+            // ---- raw_depth (the raw kind reads no row) ----
+            wd_clear(s_diff, tid);
             __syncthreads();
-            for (uint32_t v = tid; v < n_cand; v += BS) {
-                uint32_t r = lo + (v - wn);
-                if (v < wn) r = a.wide_idx[wlo + v];
-                const HeadCand hc = head_cand<T>(head_at<HEAD4>(a.heads, r), W);
-                if (hc.hit) {
-                    atomicAdd(&s_diff[hc.cb], 1u);
-                    if (hc.ce < (uint32_t)T) atomicAdd(&s_diff[hc.ce], 0xFFFFFFFFu);
-                }
-            }
+            wd_scatter<HEAD4>(a.res, wm, W, s_diff, tid);
             __syncthreads();
-            uint32_t sr = 0;
-#pragma unroll
-            for (int q = 0; q < PER / 4; ++q) {
-                const uint4 x = reinterpret_cast<const uint4 *>(s_diff)[tid * (PER / 4) + q];
-                sr += x.x; d[4 * q] = sr; sr += x.y; d[4 * q + 1] = sr;
-                sr += x.z; d[4 * q + 2] = sr; sr += x.w; d[4 * q + 3] = sr;
-            }
-            const uint32_t ir = dpp_incl_scan_u32(sr);
-            if (tid == 63u) s_tot = ir;
+            const uint32_t excl = wd_diff_scan(d, s_diff, &s_tot, tid);
             __syncthreads();
-            const uint32_t off = ir - sr + (wv ? s_tot : 0u);
-#pragma unroll
-            for (int i = 0; i < PER; ++i) d[i] += off;
+            wd_diff_finish(d, excl, &s_tot, wv);
         } else {
-            // ---- qc_depth: the window's rows into the two waves' counter planes, summed by wave 0 (as k_depth_profile) ----
-            const uint32_t ng = wm.rn;
-            const RowLane rl = row_lane(a.rows, wm, lane, wv);
+            // ---- qc_depth (the qc kind reads no head) ----
+            const RowLane rl = row_lane(a.res.rows, wm, lane, wv);
             uint32_t c[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) c[p] = 0u;
-            for (int k = 0; wv + (uint32_t)k < ng; k += 2) bs_add4<NP>(c, row_unit(rl, k));
-            if (wv != 0) {
-#pragma unroll
-                for (int p = 0; p < NP; ++p) s_pl[p][lane] = c[p];
-            }
+            wd_rows<NP>(c, rl, wm.rn, wv);
+            if (wv != 0) wd_planes_put<NP>(c, s_pl, lane);
             __syncthreads();
-            if (wv == 0) {
-                uint32_t carry = 0u;
-#pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    const uint32_t x = s_pl[p][lane];
-                    const uint32_t s = c[p] ^ x ^ carry;
-                    carry = bs_maj(c[p], x, carry);
-                    s_pl[p][lane] = s;                     // (a lane reads and writes its own slots only)
-                }
-            }
+            if (wv == 0) wd_planes_add<NP>(c, s_pl, lane);
             __syncthreads();
-#pragma unroll
-            for (int i = 0; i < PER; ++i) d[i] = 0u;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const uint32_t word = s_pl[p][tid >> 1] >> ((tid & 1u) * 16u);
-#pragma unroll
-                for (int i = 0; i < PER; ++i) d[i] |= ((word >> i) & 1u) << p;
-            }
+            wd_extract<NP>(d, s_pl, tid);
         }
-        const uint32_t p0 = W + tid * PER;
-        const uint32_t n_ok = p0 >= a.extent ? 0u : (a.extent - p0 < (uint32_t)PER ? a.extent - p0 : (uint32_t)PER);
+        const DepthSpan sp = wd_span(W, tid, a.res.extent);
+        const uint32_t p0 = sp.p0, n_ok = sp.n_ok;
 
         // ---- depth -> value (in place): a search per change of depth ----
         if (ne) {

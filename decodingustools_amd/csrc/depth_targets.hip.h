@@ -9,8 +9,8 @@
 // this: C there is the scan's offset) and uploads them with, per window, the range of points inside it.
 //
 //   k_target_depth   a sibling of k_depth_profile and k_depth_runs, a kernel of its own: the same residents, the same
-//                    rebuild of both depths per position (bit-sliced counter planes for qc, the scanned +-1 difference
-//                    array for raw; 128 threads, a window of 2048, 16 positions per thread).  Per window the totals of f
+//                    rebuild of both depths per position (window_depths.hip.h: bit-sliced counter planes for qc, the scanned
+//                    +-1 difference array for raw; 128 threads, a window of 2048, 16 positions per thread).  Per window the totals of f
 //                    (64 bits each, one record per window, stored by one lane); in a window that holds query points (a workgroup-uniform branch) also the in-window
 //                    prefix of f at each of them: the points are marked in a 2048-bit mask in LDS, a point's slot is the
 //                    window's first slot plus the marks before it, and the thread that owns the position stores its
@@ -44,11 +44,7 @@ constexpr int kTargetTotSlots = 2 + 2 * kTargetMaxThr;
 static_assert(kTargetPreWords == 12, "three uint4 per point");
 
 struct TargetArgs {
-    const WinMeta  *win;
-    const void     *heads;            // 8 bytes each, or 4 with HEAD4 (pileup_rows.hip.h)
-    const uint32_t *wide_idx;
-    const uint4    *rows;
-    uint32_t extent, n_win;
+    DepthResidents res;
     uint32_t n_pt, pad;
     const uint32_t *pt;               // [n_pt]: the query points with q % 2048 != 0, ascending, distinct; behind them
                                       // pt_first[n_win + 1]: window w holds points [pt_first[w], pt_first[w + 1])
@@ -61,8 +57,7 @@ struct TargetArgs {
 template <int NP, bool HEAD4>
 __global__ __launch_bounds__(kDepthBlock) void k_target_depth(TargetArgs a)
 {
-    constexpr int T = 2048, BS = kDepthBlock, PER = T / BS, MT = kTargetMaxThr;
-    static_assert(PER == 16 && BS == 128, "two waves, a thread's 16 positions are half a block of 32");
+    constexpr int T = kDepthT, BS = kDepthBlock, PER = kDepthPer, MT = kTargetMaxThr;
     __shared__ __attribute__((aligned(16))) uint32_t s_diff[T];
     __shared__ uint32_t s_pl[NP][64];                      // wave 1's planes, then the window's (written by wave 0)
     __shared__ uint32_t s_mark[64];                        // bit p - W: p is a query point
@@ -78,92 +73,44 @@ __global__ __launch_bounds__(kDepthBlock) void k_target_depth(TargetArgs a)
 #pragma unroll
     for (int k = 0; k < MT; ++k) { uint32_t t = a.thr[k]; asm volatile("" : "+v"(t)); thr[k] = t; }
 
-    for (uint32_t w = blockIdx.x; w < a.n_win; w += gridDim.x) {
+    for (uint32_t w = blockIdx.x; w < a.res.n_win; w += gridDim.x) {
         const uint32_t W = w * (uint32_t)T;
-        const WinMeta wm = a.win[w];
-        const uint32_t lo = wm.lo, wlo = wm.wlo, wn = wm.wn;
-        const uint32_t n_cand = wn + (wm.hi - lo);
-        const uint32_t ng = wm.rn;
-        const RowLane rl = row_lane(a.rows, wm, lane, wv);
+        const WinMeta wm = a.res.win[w];
+        const RowLane rl = row_lane(a.res.rows, wm, lane, wv);
         // the window's points: a range of the uploaded list, held against the list before anything is read through it
         const uint32_t *pt_first = a.pt + a.n_pt;
         uint32_t pf = pt_first[w], pe = pt_first[w + 1u];
         if (pf > pe || pe > a.n_pt) { if (tid == 0u) atomicOr(a.err, 1u); pf = 0u; pe = 0u; }
         const uint32_t np = pe - pf;                       // (workgroup-uniform)
 
-        // ---- clear (the previous window's readers are behind the barrier at the end of the loop) ----
-        {
-            uint4 *d4 = reinterpret_cast<uint4 *>(s_diff);
-            for (int i = tid; i < T / 4; i += BS) d4[i] = make_uint4(0, 0, 0, 0);
-            if (wv == 0) s_mark[lane] = 0u;
-        }
+        wd_clear(s_diff, tid);
+        if (wv == 0) s_mark[lane] = 0u;
         __syncthreads();
 
-        // ---- the window's rows: groups wv, wv + 2, ... into this wave's counter planes (as k_depth_profile) ----
         uint32_t c[NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) c[p] = 0u;
-        for (int k = 0; wv + (uint32_t)k < ng; k += 2) bs_add4<NP>(c, row_unit(rl, k));
-        // ---- the window's candidates: +-1 at the clipped span ends ----
-        for (uint32_t v = tid; v < n_cand; v += BS) {
-            uint32_t r = lo + (v - wn);
-            if (v < wn) r = a.wide_idx[wlo + v];
-            const HeadCand hc = head_cand<T>(head_at<HEAD4>(a.heads, r), W);
-            if (hc.hit) {
-                atomicAdd(&s_diff[hc.cb], 1u);
-                if (hc.ce < (uint32_t)T) atomicAdd(&s_diff[hc.ce], 0xFFFFFFFFu);
-            }
-        }
+        wd_rows<NP>(c, rl, wm.rn, wv);
+        wd_scatter<HEAD4>(a.res, wm, W, s_diff, tid);
         // ---- the window's points: marks ----
         for (uint32_t j = tid; j < np; j += BS) {
             const uint32_t x = a.pt[pf + j] - W;           // (a point below W wraps beyond T)
             if (x < (uint32_t)T) atomicOr(&s_mark[x >> 5], 1u << (x & 31u));
             else atomicOr(a.err, 1u);
         }
-        if (wv != 0) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) s_pl[p][lane] = c[p];
-        }
+        if (wv != 0) wd_planes_put<NP>(c, s_pl, lane);
         __syncthreads();
         if (wv == 0) {
-            uint32_t carry = 0u;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                const uint32_t d = s_pl[p][lane];
-                const uint32_t s = c[p] ^ d ^ carry;
-                carry = bs_maj(c[p], d, carry);
-                s_pl[p][lane] = s;                         // (a lane reads and writes its own slots only)
-            }
+            wd_planes_add<NP>(c, s_pl, lane);
             if (np) {
                 const uint32_t m = (uint32_t)__popc(s_mark[lane]);
                 s_rank[lane] = dpp_incl_scan_u32(m) - m;
             }
         }
-        // ---- raw_depth: the differences scanned ----
-        uint32_t vr[PER];
-        uint32_t sr = 0;
-#pragma unroll
-        for (int q = 0; q < PER / 4; ++q) {
-            const uint4 d = reinterpret_cast<const uint4 *>(s_diff)[tid * (PER / 4) + q];
-            sr += d.x; vr[4 * q] = sr; sr += d.y; vr[4 * q + 1] = sr;
-            sr += d.z; vr[4 * q + 2] = sr; sr += d.w; vr[4 * q + 3] = sr;
-        }
-        const uint32_t ir = dpp_incl_scan_u32(sr);
-        if (wv == 0 && lane == 63u) s_tot = ir;
+        uint32_t vr[PER], vq[PER];
+        const uint32_t excl = wd_diff_scan(vr, s_diff, &s_tot, tid);
         __syncthreads();
-        const uint32_t off = ir - sr + (wv ? s_tot : 0u);
-        const uint32_t p0 = W + tid * PER;
-        const uint32_t n_ok = p0 >= a.extent ? 0u : (a.extent - p0 < (uint32_t)PER ? a.extent - p0 : (uint32_t)PER);
-        // ---- qc_depth: the 16 counts of this thread out of the planes of block tid / 2 ----
-        uint32_t vq[PER];
-#pragma unroll
-        for (int i = 0; i < PER; ++i) vq[i] = 0u;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const uint32_t word = s_pl[p][tid >> 1] >> ((tid & 1u) * 16u);
-#pragma unroll
-            for (int i = 0; i < PER; ++i) vq[i] |= ((word >> i) & 1u) << p;
-        }
+        wd_diff_finish(vr, excl, &s_tot, wv);
+        wd_extract<NP>(vq, s_pl, tid);
+        const uint32_t n_ok = wd_span(W, tid, a.res.extent).n_ok;
         // ---- the thread's totals of f (positions at and beyond the extent count nowhere) ----
         unsigned long long t_raw = 0ull, t_qc = 0ull;
         uint32_t t_ge[MT];
@@ -171,7 +118,6 @@ __global__ __launch_bounds__(kDepthBlock) void k_target_depth(TargetArgs a)
         for (int k = 0; k < MT; ++k) t_ge[k] = 0u;
 #pragma unroll
         for (int i = 0; i < PER; ++i) {
-            vr[i] += off;
             if ((uint32_t)i >= n_ok) { vr[i] = 0u; vq[i] = 0u; }
             t_raw += vr[i]; t_qc += vq[i];
 #pragma unroll

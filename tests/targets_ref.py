@@ -13,6 +13,20 @@ def clip(starts, ends, extent):
     return s, e
 
 
+def window_edge_targets(extent, w, T=2048):
+    """(starts, ends) of five targets at the edges of the per-window rebuild of the depths, around engine window w >= 1
+    (T positions) of a contig of `extent` positions: an empty one, one inside a single thread's 16 positions, one that
+    starts on the window's first position, one that crosses the seam from window w - 1, one clipped by the extent"""
+    W = w * T
+    assert w >= 1 and W + 700 < extent
+    return [W + 40, W + 18, W, W - 70, extent - 100], [W + 40, W + 30, W + 700, W + 80, extent + 5000]
+
+
+def oracle_state(so, eo, engine_state, extent):
+    """the oracle's states end at its last column eo: behind it the engine's own, up to the extent"""
+    return np.concatenate((np.asarray(so[:eo], np.uint8), np.asarray(engine_state[eo:extent], np.uint8)))
+
+
 def _cum(a):
     return np.concatenate(([0], np.cumsum(np.asarray(a, np.int64))))
 

@@ -15,6 +15,7 @@ import pytest
 import depth_contigs
 import depth_ref
 import runs_ref
+import targets_ref
 from helpers import make_options, oracle_run
 from decodingustools_amd import CallableOptions, CallableProfiler, ContigProfiler, Engine, process_single_contig, synth
 from decodingustools_amd.records import ContigRecords
@@ -137,6 +138,7 @@ def test_window_edges(tmp_path):
 H_L = 70 * T + 1234                                # 144 594 positions: past 65 536 and 131 072, the extent ends mid-window
 H_B = 40 * T                                       # a window boundary; H_B - 16 383 = 65 537, just past the first wrap
 H_EDGES = [1, 4, 10]
+H_TARGET_WINDOW, H_THR = 32, (1, 4, 10)            # targets around position 65 536, where the planted reads meet a seam
 
 
 def _h_records(which):
@@ -187,6 +189,8 @@ def _h_engine(which, heads8, head_span=None):
             out["dumps"] = eng.debug_depths(extent)
             out["profile"] = eng.depth_profile(1001, 500)
             out["runs"] = {(kind, bool(e)): eng.depth_runs(kind, e) for kind in ("raw", "qc") for e in (None, H_EDGES)}
+            eng.contig_collect()                                   # (the dump ran the contig again)
+            out["targets"] = eng.target_stats(*targets_ref.window_edge_targets(extent, H_TARGET_WINDOW), H_THR)
     finally:
         for k, v in saved.items():
             os.environ.pop(k, None)
@@ -238,7 +242,7 @@ def test_heads_stay_8_bytes_with_a_wide_read_or_a_cut_span():
 def test_depth_profile_and_depth_runs_in_both_head_forms(heads8):
     _, _, o, _ = _h_oracle("short")
     g = _h_engine("short", heads8)
-    ro, qo, _, _, eo = o["dumps"]
+    ro, qo, _, so, eo = o["dumps"]
     depth = {"raw": depth_ref.pad(ro, g["extent"]), "qc": depth_ref.pad(qo, g["extent"])}
     exp = depth_ref.profile(depth["raw"], depth["qc"], 1001, 500)
     got = g["profile"]
@@ -249,3 +253,9 @@ def test_depth_profile_and_depth_runs_in_both_head_forms(heads8):
         s, v = runs_ref.runs(depth[kind], H_EDGES if banded else None)
         assert r.n_runs == len(s), (kind, banded)
         assert np.array_equal(r.start, s) and np.array_equal(r.value, v), (kind, banded)
+    # k_target_depth rebuilds the depths with the same code: in this head form, and with the spans cut into heads of 37
+    for gt in (g, _h_engine("short", heads8, 37)):
+        state = targets_ref.oracle_state(so, eo, gt["dumps"][3], gt["extent"])
+        a, b = targets_ref.window_edge_targets(gt["extent"], H_TARGET_WINDOW)
+        assert gt["targets"].len.tolist() == [0, 12, 700, 150, 100]
+        targets_ref.same(gt["targets"], targets_ref.target_stats(depth["raw"], depth["qc"], state, a, b, H_THR), (heads8, gt is g))

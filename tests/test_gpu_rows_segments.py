@@ -5,7 +5,8 @@ that segment is high, from where the heights of the segments in front of it put 
 Every case is a contig of at most 4 windows (T = 2048), run as the upload lays it out and once more with
 DUT_ROWS_UNIFORM=1 (every segment as high as the window's highest, the heights' word 0: the equal-heights decode), and
 held against the oracle per position (raw, low, qc, state: the DEBUG instantiation of k_pileup_rows), as BED text, state
-counts and sums (the production instantiation), and through k_depth_profile and k_depth_runs, which read the same rows."""
+counts and sums (the production instantiation), and through k_depth_profile, k_depth_runs and k_target_depth, which read
+the same rows."""
 import functools
 import os
 import subprocess
@@ -17,6 +18,7 @@ import pytest
 
 import depth_ref
 import runs_ref
+import targets_ref
 from helpers import make_options, oracle_run
 from decodingustools_amd import CallableOptions, CallableProfiler, ContigProfiler, Engine, process_single_contig, synth
 from decodingustools_amd.records import ContigRecords
@@ -27,6 +29,7 @@ T, S = 2048, 256
 SUMS = ("n_covered_bases", "summed_coverage", "summed_baseq", "summed_mapq", "quality_bases", "n_reads")
 EDGES = [1, 4, 10]
 N_BINS, WINDOW = 1100, 500
+THR = (1, 4, 10)
 
 
 @pytest.fixture(autouse=True)
@@ -136,6 +139,9 @@ def run_case(name, uniform):
             dumps = eng.debug_depths(extent)
             prof = eng.depth_profile(N_BINS, WINDOW)
             runs = {(kind, bool(e)): eng.depth_runs(kind, e) for kind in ("raw", "qc") for e in (None, EDGES)}
+            eng.contig_collect()                                   # (the dump ran the contig again)
+            tg_a, tg_b = targets_ref.window_edge_targets(extent, 1)
+            tg = eng.target_stats(tg_a, tg_b, THR)
     finally:
         os.environ.pop("DUT_ROWS_UNIFORM", None)
         if saved is not None:
@@ -156,6 +162,8 @@ def run_case(name, uniform):
         s, v = runs_ref.runs(depth[kind], EDGES if banded else None)
         assert r.n_runs == len(s), (kind, banded)
         assert np.array_equal(r.start, s) and np.array_equal(r.value, v), (kind, banded)
+    assert tg.len.tolist() == [0, 12, 700, 150, 100]
+    targets_ref.same(tg, targets_ref.target_stats(depth["raw"], depth["qc"], targets_ref.oracle_state(so, eo, dumps[3], extent), tg_a, tg_b, THR))
     return lay
 
 
