@@ -7,7 +7,7 @@ from .records import ContigRecords  # noqa: F401
 from .callable_loci import (CallableOptions, CalledState, CallableProfiler, ContigProfiler,  # noqa: F401
                             ContigResult, ConsResult, DelResult, ErrorProfile, InsResult, LinkResult, StrResult, DepthAccumulator, DepthProfile, DepthRuns, Engine, EngineError, ScanResult,
                             admit_reads, compare_contig_names, depth_stats, genome_summary, process_single_contig,
-                            quantize_parse, write_depth_bed, TargetStats, parse_targets, thresholds_parse, write_target_stats)
+                            quantize_parse, write_depth_bed, TargetStats, TargetOrder, parse_targets, thresholds_parse, write_target_stats)
 from .fingerprint import Fingerprint, FingerprintError, FingerprintResult, fingerprint_file  # noqa: F401
 from .variants import (annotate_variants, error_profile, error_profile_measure, write_error_profile, cons_assemble, cons_classify_counts, consensus, del_classify_counts, del_events, del_fraction_parse, find_deletions,  # noqa: F401
                        find_insertions, find_strs, find_variants, ins_alleles, ins_classify_counts, scan_classify, scan_classify_counts, str_call, str_loci_parse, str_measure, str_units,
@@ -18,7 +18,7 @@ __all__ = ["ContigRecords", "CallableOptions", "CalledState", "CallableProfiler"
            "ContigResult", "DepthAccumulator", "DepthProfile", "DepthRuns", "Engine", "EngineError", "admit_reads",
            "compare_contig_names", "depth_stats", "genome_summary", "process_single_contig", "Fingerprint", "FingerprintError", "FingerprintResult",
            "fingerprint_file", "ScanResult", "annotate_variants", "find_variants", "scan_classify", "scan_classify_counts",
-           "write_variants", "quantize_parse", "write_depth_bed", "TargetStats", "parse_targets", "thresholds_parse", "write_target_stats", "DelResult", "find_deletions", "del_events", "write_deletions",
+           "write_variants", "quantize_parse", "write_depth_bed", "TargetStats", "TargetOrder", "parse_targets", "thresholds_parse", "write_target_stats", "DelResult", "find_deletions", "del_events", "write_deletions",
            "del_fraction_parse", "del_classify_counts", "InsResult", "find_insertions", "ins_alleles", "write_insertions",
            "ins_classify_counts", "ConsResult", "consensus", "cons_assemble", "cons_classify_counts", "write_consensus",
            "write_consensus_changes", "StrResult", "find_strs", "str_measure", "str_call", "str_units", "str_loci_parse", "write_strs",

@@ -158,6 +158,14 @@ class cl_target_stats(C.Structure):
                 ("ge_raw", C.c_uint32 * CL_TARGET_MAX_THRESHOLDS), ("ge_qc", C.c_uint32 * CL_TARGET_MAX_THRESHOLDS)]
 
 
+CL_TARGET_ORDER_MAX_PIECES = 1 << 26
+DUT_TARGETS_ORDER = 1
+
+
+class cl_target_order(C.Structure):
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("len", C.c_uint32), ("raw", C.c_uint32 * 5), ("qc", C.c_uint32 * 5)]
+
+
 class dut_target_options(C.Structure):
     _fields_ = [("bed_path", C.c_char_p), ("out_path", C.c_char_p), ("thresholds", C.POINTER(C.c_uint32)), ("n_thresholds", C.c_uint32)]
 
@@ -521,6 +529,17 @@ SYMBOLS = [
                                          C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
                                          C.c_uint, C.POINTER(dut_depth_options), C.POINTER(dut_depth_bed_options),
                                          C.POINTER(dut_target_options), C.c_char_p, C.c_size_t]),
+    ("cl_contig_target_order", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t,
+                                         C.POINTER(C.POINTER(cl_target_order))]),
+    ("cl_contig_target_order_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    ("dut_targets_write_header_ex", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_int]),
+    ("dut_targets_write_ex", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(cl_target_stats), C.POINTER(cl_target_order),
+                                       C.POINTER(C.c_char_p), C.c_size_t, C.c_uint32, C.c_void_p]),
+    ("dut_targets_write_total_ex", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]),
+    ("dut_coverage_files_ex4", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                         C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
+                                         C.c_uint, C.POINTER(dut_depth_options), C.POINTER(dut_depth_bed_options),
+                                         C.POINTER(dut_target_options), C.c_uint, C.c_char_p, C.c_size_t]),
     ("cl_abi_version", C.c_int, []),
     ("cl_device_count", C.c_int, []),
     ("cl_create", C.c_int, [C.POINTER(cl_options), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -110,7 +110,7 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
                    output_summary: str = None, devices=None, depth_dist: str = None, depth_windows: str = None,
                    depth_summary: str = None, depth_cap: int = 1000, window: int = 0, depth_bed: str = None,
                    depth_bed_kind: str = "raw", quantize: str = None, targets: str = None, target_out: str = None,
-                   target_thresholds=None):
+                   target_thresholds=None, target_quantiles: bool = False):
     """CoverageAnalyzer::analyze on files (CoverageInput of api/coverage.rs:124-132); summary_json
     receives the CoverageOutput JSON of main.rs:68-69; output_summary, when given, the HTML report
     (api/coverage.rs:104; None: not written, the JSON then names "summary.html").  The per-contig coverage
@@ -122,7 +122,8 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
     depth_bed: the per-base depth of every contig as a BED of runs of equal depth (dut_coverage_files_ex2);
     depth_bed_kind "raw" or "qc"; quantize: band edges such as "1:4:100" (None or "": exact depth).
     targets: a BED of regions, target_out: the per-target table of dut_coverage_files_ex3 (include/dut_coverage.h has the
-    format); target_thresholds: up to 8 ascending depths (default 1, 10, 20, 30)."""
+    format); target_thresholds: up to 8 ascending depths (default 1, 10, 20, 30); target_quantiles: the table also gets
+    minimum, quartiles and maximum of both depths per target (dut_coverage_files_ex4, DUT_TARGETS_ORDER)."""
     lib = _lib.load()
     options = options or CallableOptions()
     oc = options.to_c()
@@ -136,6 +137,8 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
         raise EngineError(-1, "quantize and depth_bed_kind need depth_bed")
     if targets is None and (target_out is not None or target_thresholds is not None):
         raise EngineError(-1, "target_out and target_thresholds need targets")
+    if targets is None and target_quantiles:
+        raise EngineError(-1, "target_quantiles needs targets")
     if targets is not None and target_out is None:
         raise EngineError(-1, "targets needs target_out")
     if targets is not None:
@@ -158,9 +161,10 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
         dv = (C.c_int * len(dlist))(*dlist)
         enc = lambda p: p.encode() if p else None          # noqa: E731
         do = _lib.dut_depth_options(int(depth_cap) + 1, int(window), enc(depth_dist), enc(depth_windows), enc(depth_summary))
-        st = lib.dut_coverage_files_ex3(bam_file.encode(), reference_file.encode(), output_bed.encode(), enc(summary_json),
+        st = lib.dut_coverage_files_ex4(bam_file.encode(), reference_file.encode(), output_bed.encode(), enc(summary_json),
                                         enc(output_summary), C.byref(oc), arr, n, dv, len(dlist), 0, C.byref(do),
-                                        C.byref(bo) if bo is not None else None, C.byref(to), err, 1024)
+                                        C.byref(bo) if bo is not None else None, C.byref(to),
+                                        _lib.DUT_TARGETS_ORDER if target_quantiles else 0, err, 1024)
         if st != 0:
             raise EngineError(st, err.value.decode())
         return

@@ -21,6 +21,7 @@ CLI_SRC = os.path.join(CSRC, "coverage_main.cpp")
 HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "pileup_bytes.hip.h"), os.path.join(CSRC, "pileup_rows.hip.h"),
            os.path.join(CSRC, "window_depths.hip.h"),
            os.path.join(CSRC, "depth_profile.hip.h"), os.path.join(CSRC, "depth_runs.hip.h"), os.path.join(CSRC, "depth_targets.hip.h"),
+           os.path.join(CSRC, "target_order.hip.h"), os.path.join(CSRC, "target_pieces.h"),
            os.path.join(CSRC, "site_scan.hip.h"),
            os.path.join(CSRC, "engine_base.hip.h"), os.path.join(CSRC, "site_engine.hip.h"),
            os.path.join(CSRC, "site_pass_bits.h"), os.path.join(CSRC, "site_str.hip.h"), os.path.join(CSRC, "str_walk.h"),

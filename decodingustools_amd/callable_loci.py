@@ -493,6 +493,32 @@ class Engine:
         self._check(self._lib.cl_contig_targets_ms(self._h, C.byref(ms), parts))
         return TargetStats.from_records(rec, t.copy(), float(ms.value), tuple(float(x) for x in parts))
 
+    def target_order(self, starts, ends):
+        """Minimum, quartiles and maximum of the raw and the quality-filtered depth of the resident contig over the targets
+        [starts[i], ends[i]), 0-based half open, in any order and overlapping at will (cl_contig_target_order): a
+        TargetOrder of numpy arrays (copies), one entry per target in the order given.  A quartile is an element of the
+        sorted depths ((j * len + 3) // 4 - 1, the lower middle value for the median of an even length), a whole number.
+        The contig must have been run; it need not have been collected."""
+        def u32(v, what):
+            a = np.asarray(v)
+            if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+                raise EngineError(-1, f"target_order: {what} outside [0, 2^32 - 1]")
+            return np.ascontiguousarray(a, np.uint32).reshape(-1)
+        s, e = u32(starts, "a start"), u32(ends, "an end")
+        if s.size != e.size:
+            raise EngineError(-1, "target_order: starts and ends differ in length")
+        u32p = C.POINTER(C.c_uint32)
+        out = C.POINTER(_lib.cl_target_order)()
+        self._check(self._lib.cl_contig_target_order(self._h, s.ctypes.data_as(u32p) if s.size else None,
+                                                     e.ctypes.data_as(u32p) if e.size else None, int(s.size), C.byref(out)))
+        n = int(s.size)
+        rec = (np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), shape=(n * TARGET_ORDER.itemsize,)).view(TARGET_ORDER).copy()
+               if n else np.zeros(0, TARGET_ORDER))
+        ms = C.c_double()
+        rounds = C.c_uint32()
+        self._check(self._lib.cl_contig_target_order_ms(self._h, C.byref(ms), C.byref(rounds)))
+        return TargetOrder.from_records(rec, float(ms.value), int(rounds.value))
+
 
 # cl_scan_candidate as a numpy record: pos is 1-based, ref and alt are ASCII codes
 SCAN_CANDIDATE = np.dtype([("pos", np.uint32), ("ref", np.uint8), ("alt", np.uint8), ("pad", np.uint8, (2,)), ("a", np.uint32),
@@ -755,6 +781,37 @@ class TargetStats:
         return rec
 
 
+# cl_target_order as a numpy record
+TARGET_ORDER = np.dtype([("start", np.uint32), ("end", np.uint32), ("len", np.uint32), ("raw", np.uint32, (5,)), ("qc", np.uint32, (5,))])
+assert TARGET_ORDER.itemsize == C.sizeof(_lib.cl_target_order)
+
+
+@dataclass
+class TargetOrder:
+    """cl_target_order per target (include/callable_loci.h), one array entry per target in the order given: start, end and
+    len clipped to the extent, raw[i] and qc[i] = (min, q1, median, q3, max) of the raw and the quality-filtered depth over
+    the target, all zeros for a target of length 0."""
+    start: np.ndarray
+    end: np.ndarray
+    len: np.ndarray
+    raw: np.ndarray
+    qc: np.ndarray
+    kernel_ms: float = 0.0          # cl_contig_target_order_ms: all launches, while profiling is on
+    n_rounds: int = 0               # ... the bit rounds: the bit length of the largest raw depth of any target
+
+    @classmethod
+    def from_records(cls, rec, kernel_ms=0.0, n_rounds=0):
+        return cls(start=rec["start"].copy(), end=rec["end"].copy(), len=rec["len"].copy(), raw=rec["raw"].copy().reshape(-1, 5),
+                   qc=rec["qc"].copy().reshape(-1, 5), kernel_ms=kernel_ms, n_rounds=n_rounds)
+
+    def records(self):
+        """the cl_target_order records (a TARGET_ORDER array)"""
+        rec = np.zeros(int(self.start.size), TARGET_ORDER)
+        for f in ("start", "end", "len", "raw", "qc"):
+            rec[f] = getattr(self, f)
+        return rec
+
+
 def parse_targets(text):
     """dut_targets_parse: BED text (str or bytes) -> a list of (contig, starts, ends, names) in the order the contigs
     first appear, the targets of a contig in file order (starts and ends: numpy uint32; names: column 4, else ".").
@@ -792,9 +849,11 @@ def thresholds_parse(spec):
     return [int(t[i]) for i in range(n.value)]
 
 
-def write_target_stats(path, contigs, thresholds):
-    """dut_targets_write_header / dut_targets_write / dut_targets_write_total: the per-target table of include/dut_coverage.h.
-    contigs: (contig, TargetStats, names) in output order; the file ends with the `total` line over all of them."""
+def write_target_stats(path, contigs, thresholds, order=None):
+    """dut_targets_write_header_ex / dut_targets_write_ex / dut_targets_write_total_ex: the per-target table of
+    include/dut_coverage.h.  contigs: (contig, TargetStats, names) in output order; the file ends with the `total` line over
+    all of them.  order: None, or one TargetOrder per entry of contigs (of the same targets): the table gets the ten
+    columns raw_min ... qc_max behind the others."""
     lib = _lib.load()
     libc = C.CDLL(None)
     libc.fopen.restype = C.c_void_p
@@ -806,16 +865,25 @@ def write_target_stats(path, contigs, thresholds):
     if not f:
         raise OSError("cannot open " + path)
     total = (C.c_uint64 * 32)()                    # dut_target_total
-    st = lib.dut_targets_write_header(f, t.ctypes.data_as(u32p) if t.size else None, int(t.size))
-    for contig, stats, names in contigs:
+    contigs = list(contigs)
+    if order is not None and len(order) != len(contigs):
+        libc.fclose(f)
+        raise EngineError(-1, "write_target_stats: one TargetOrder per contig")
+    cols = 0 if order is None else 1
+    st = lib.dut_targets_write_header_ex(f, t.ctypes.data_as(u32p) if t.size else None, int(t.size), cols)
+    for i, (contig, stats, names) in enumerate(contigs):
         rec = np.ascontiguousarray(stats.records())
         n = int(rec.size)
         nm = (C.c_char_p * max(n, 1))(*[(x or ".").encode() for x in names])
+        orec = np.ascontiguousarray(order[i].records()) if order is not None else None
+        if orec is not None and int(orec.size) != n:
+            st = st or -1
         if st == 0:
-            st = lib.dut_targets_write(f, contig.encode(), rec.ctypes.data_as(C.POINTER(_lib.cl_target_stats)), nm, n, int(t.size),
-                                       C.cast(total, C.c_void_p))
+            st = lib.dut_targets_write_ex(f, contig.encode(), rec.ctypes.data_as(C.POINTER(_lib.cl_target_stats)),
+                                          orec.ctypes.data_as(C.POINTER(_lib.cl_target_order)) if orec is not None else None,
+                                          nm, n, int(t.size), C.cast(total, C.c_void_p))
     if st == 0:
-        st = lib.dut_targets_write_total(f, C.cast(total, C.c_void_p), int(t.size))
+        st = lib.dut_targets_write_total_ex(f, C.cast(total, C.c_void_p), int(t.size), cols)
     if libc.fclose(f) != 0 and st == 0:
         st = -1
     if st != 0:

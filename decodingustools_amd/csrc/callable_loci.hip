@@ -16,11 +16,13 @@
 #include "depth_profile.hip.h"
 #include "depth_runs.hip.h"
 #include "depth_targets.hip.h"
+#include "target_order.hip.h"
 #include "engine_base.hip.h"
 #include "site_engine.hip.h"
 #include "qual_pack.h"
 #include "pass_rows.h"
 #include "tile_walk.h"
+#include "target_pieces.h"
 
 using namespace clk;
 
@@ -108,6 +110,16 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     std::vector<cl_target_stats> h_tg_out;
     KernelTimer t_tg[3];                  // k_target_depth, k_target_scan, k_target_finish (recorded while profiling is on)
     double tg_ms[3] = {0.0, 0.0, 0.0};
+    // cl_contig_target_order: what goes up (the pieces, the windows' ranges of them, the clipped targets), the targets'
+    // states with the two words behind them (the largest raw depth, the error word), the records -- and the records as
+    // copied back
+    DevBuf<uint32_t> d_to_in, d_to_st, d_to_out;
+    std::vector<TargetPiece> h_to_pc;
+    std::vector<uint32_t> h_to_first, h_to_tg;
+    std::vector<cl_target_order> h_to_out;
+    KernelTimer t_to[2];                  // the FIRST launch and its step; the rounds (recorded while profiling is on)
+    double to_ms = 0.0;
+    uint32_t to_rounds = 0;
     // The device buffers of the context, listed once: f(buffer) for each one that cl_layout_info.device_bytes counts, which
     // is all of them but d_prof and the site engine's (they never were).  cl_destroy and cl_contig_layout walk this list.
     template <class F> void each_buffer(F &&f)
@@ -973,6 +985,10 @@ const DepthKernel<DepthArgs> kDepthProfileKernels[3][2] = {{k_depth_profile<8, f
     {k_depth_profile<16, false>, k_depth_profile<16, true>}, {k_depth_profile<32, false>, k_depth_profile<32, true>}};
 const DepthKernel<TargetArgs> kTargetDepthKernels[3][2] = {{k_target_depth<8, false>, k_target_depth<8, true>},
     {k_target_depth<16, false>, k_target_depth<16, true>}, {k_target_depth<32, false>, k_target_depth<32, true>}};
+const DepthKernel<OrderArgs> kTargetOrderFirstKernels[3][2] = {{k_target_order<8, false, true>, k_target_order<8, true, true>},
+    {k_target_order<16, false, true>, k_target_order<16, true, true>}, {k_target_order<32, false, true>, k_target_order<32, true, true>}};
+const DepthKernel<OrderArgs> kTargetOrderRoundKernels[3][2] = {{k_target_order<8, false, false>, k_target_order<8, true, false>},
+    {k_target_order<16, false, false>, k_target_order<16, true, false>}, {k_target_order<32, false, false>, k_target_order<32, true, false>}};
 // (only the raw depths come from the heads, and they need no plane; the qc depths are the rows' column sums)
 const DepthKernel<RunsArgs> kDepthRunsRawKernels[3][2] = {{k_depth_runs<8, false, false>, k_depth_runs<8, false, true>},
     {k_depth_runs<8, false, false>, k_depth_runs<8, false, true>}, {k_depth_runs<8, false, false>, k_depth_runs<8, false, true>}};
@@ -1149,8 +1165,10 @@ void cl_destroy(cl_ctx *c)
     c->each_buffer([](auto &buf) { buf.release(); });
     c->d_prof.release(); c->site.release(); c->h_dr_out.release();
     c->d_tg_in.release(); c->d_tg_pre.release(); c->d_tg_out.release(); c->d_tg_win.release(); c->d_tg_off.release();
+    c->d_to_in.release(); c->d_to_st.release(); c->d_to_out.release();
     c->t_prof.destroy(); c->t_dr_count.destroy(); c->t_dr_write.destroy();
     for (KernelTimer &t : c->t_tg) t.destroy();
+    for (KernelTimer &t : c->t_to) t.destroy();
     if (c->ev_made)
         for (auto &set : c->ev)
             for (hipEvent_t e : set) (void)hipEventDestroy(e);
@@ -2212,6 +2230,115 @@ cl_status cl_contig_targets(cl_ctx *c, const uint32_t *starts, const uint32_t *e
             for (int i = 0; i < 3; ++i) { HIP_TRY(c, c->t_tg[i].read()); c->tg_ms[i] = c->t_tg[i].ms; }
         if (err) return fail(c, CL_ERR_INTERNAL, "cl_contig_targets: a device-side check of the uploaded points, slots or intervals failed");
         *out = c->h_tg_out.data();
+        return CL_OK;
+    });
+}
+
+// Minimum, quartiles and maximum of both depths of the resident contig over a list of targets (include/callable_loci.h):
+// the host cuts the targets at the windows into pieces (target_pieces.h); k_target_order takes the extremes, then, once
+// the host has read the largest raw depth of any target, one round per bit of it; k_target_order_step settles a round
+// (target_order.hip.h).  Nothing of a run is touched, and nothing but its residents is read: the contig need not be collected.
+cl_status cl_contig_target_order_ms(cl_ctx *c, double *kernel_ms, uint32_t *n_rounds)
+{
+    if (!c || !kernel_ms) return CL_ERR_INVALID;
+    *kernel_ms = c->to_ms;
+    if (n_rounds) *n_rounds = c->to_rounds;
+    return CL_OK;
+}
+
+cl_status cl_contig_target_order(cl_ctx *c, const uint32_t *starts, const uint32_t *ends, size_t n_targets, const cl_target_order **out)
+{
+    return guarded(c, [&]() -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_target_order: null result");
+        *out = nullptr;
+        const cl_status ready = depth_call_ready(c, "cl_contig_target_order", false, [&]() -> cl_status {
+            if (n_targets > CL_TARGETS_MAX) return fail(c, CL_ERR_INVALID, "cl_contig_target_order: more than 2^24 targets");
+            if (n_targets && (!starts || !ends)) return fail(c, CL_ERR_INVALID, "cl_contig_target_order: null starts or ends");
+            for (size_t i = 0; i < n_targets; ++i)
+                if (starts[i] > ends[i]) return fail(c, CL_ERR_INVALID, "cl_contig_target_order: target " + std::to_string(i) + " has start > end");
+            return CL_OK;
+        }());
+        if (ready != CL_OK) return ready;
+        c->to_ms = 0.0; c->to_rounds = 0u;
+        if (n_targets == 0) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return CL_OK; }
+        const size_t n = n_targets, nw = c->n_win;
+        const uint32_t extent = c->extent;
+        // (counted before a byte of the list is allocated)
+        const uint64_t n_pc64 = target_piece_count(starts, ends, n, extent);
+        if (n_pc64 > CL_TARGET_ORDER_MAX_PIECES)
+            return fail(c, CL_ERR_INVALID, "cl_contig_target_order: the targets cut at the windows are " + std::to_string(n_pc64) +
+                                           " pieces, more than the " + std::to_string(CL_TARGET_ORDER_MAX_PIECES) + " the call takes");
+        static_assert(sizeof(cl_target_order) == kOrderWords * sizeof(uint32_t), "record layout");
+        try {
+            c->h_to_out.assign(n, cl_target_order{});
+            c->h_to_tg.resize(2 * n);
+        } catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "cl_contig_target_order: the records"); }
+        for (size_t i = 0; i < n; ++i) {
+            const ClippedTarget t = clip_target(starts[i], ends[i], extent);
+            c->h_to_tg[2 * i] = t.s; c->h_to_tg[2 * i + 1] = t.e;
+            c->h_to_out[i].start = t.s; c->h_to_out[i].end = t.e; c->h_to_out[i].len = t.e - t.s;
+        }
+        if (n_pc64 == 0 || nw == 0) {
+            // (nothing to measure: every record is its clipped ends and zeros)
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            *out = c->h_to_out.data();
+            return CL_OK;
+        }
+        try {
+            if (!target_pieces_build(starts, ends, n, extent, c->n_win, c->h_to_pc, c->h_to_first))
+                return fail(c, CL_ERR_INTERNAL, "cl_contig_target_order: the windows do not cover the extent");
+        } catch (const std::bad_alloc &) { return fail(c, CL_ERR_NOMEM, "cl_contig_target_order: the pieces"); }
+        const size_t n_pc = c->h_to_pc.size();
+        // layout of the upload: pc[n_pc] (two words each), pc_first[nw + 1], tg[n][2]
+        HIP_TRY(c, c->d_to_in.reserve(2 * n_pc + nw + 1 + 2 * n));
+        HIP_TRY(c, c->d_to_st.reserve((size_t)kOrderStateWords * n + 2));
+        HIP_TRY(c, c->d_to_out.reserve((size_t)kOrderWords * n));
+        uint32_t *d_first = c->d_to_in.p + 2 * n_pc, *d_tg = d_first + nw + 1;
+        uint32_t *d_max = c->d_to_st.p + (size_t)kOrderStateWords * n, *d_err = d_max + 1;
+        HIP_TRY(c, hipMemcpyAsync(c->d_to_in.p, c->h_to_pc.data(), n_pc * sizeof(TargetPiece), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_first, c->h_to_first.data(), (nw + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_tg, c->h_to_tg.data(), 2 * n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(c->d_to_st.p, 0, ((size_t)kOrderStateWords * n + 2) * sizeof(uint32_t), c->stream));
+        OrderArgs a{depth_residents(c), (uint32_t)n_pc, (uint32_t)n, reinterpret_cast<const uint2 *>(c->d_to_in.p), d_first, c->d_to_st.p, d_err, 0u, 0u};
+        OrderStepArgs sa{d_tg, (uint32_t)n, extent, c->d_to_st.p, c->d_to_out.p, d_max, d_err, 1u, 0u, 0u, 0u};
+        // workgroups that stay, as k_target_depth's; eight threads per target in the step
+        const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
+        const uint32_t step_grid = (uint32_t)((8 * (uint64_t)n + kOrderStepBlock - 1) / kOrderStepBlock);
+        // ---- the extremes, the ranks, the largest raw depth of any target ----
+        if (c->profiling) HIP_TRY(c, c->t_to[0].start(c->stream));
+        hipLaunchKernelGGL(depth_kernel(c, kTargetOrderFirstKernels), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(k_target_order_step, dim3(step_grid), dim3(kOrderStepBlock), 0, c->stream, sa);
+        HIP_TRY(c, hipGetLastError());
+        if (c->profiling) HIP_TRY(c, c->t_to[0].stop(c->stream));
+        uint32_t max_raw = 0u, err = 0u;
+        HIP_TRY(c, hipMemcpyAsync(&max_raw, d_max, sizeof(max_raw), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        // ---- one round per bit of it, the most significant first ----
+        uint32_t B = 0u;
+        while (B < 32u && (max_raw >> B)) ++B;
+        sa.first = 0u;
+        if (B && c->profiling) HIP_TRY(c, c->t_to[1].start(c->stream));
+        for (uint32_t bit = B; bit-- > 0u;) {
+            a.bit = bit; sa.bit = bit; sa.last = bit == 0u ? 1u : 0u;
+            hipLaunchKernelGGL(depth_kernel(c, kTargetOrderRoundKernels), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(k_target_order_step, dim3(step_grid), dim3(kOrderStepBlock), 0, c->stream, sa);
+            HIP_TRY(c, hipGetLastError());
+        }
+        if (B && c->profiling) HIP_TRY(c, c->t_to[1].stop(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_to_out.data(), c->d_to_out.p, n * sizeof(cl_target_order), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->to_rounds = B;
+        if (c->profiling) {
+            HIP_TRY(c, c->t_to[0].read());
+            c->to_ms = c->t_to[0].ms;
+            if (B) { HIP_TRY(c, c->t_to[1].read()); c->to_ms += c->t_to[1].ms; }
+        }
+        if (err) return fail(c, CL_ERR_INTERNAL, "cl_contig_target_order: a device-side check of the uploaded pieces or targets failed");
+        *out = c->h_to_out.data();
         return CL_OK;
     });
 }

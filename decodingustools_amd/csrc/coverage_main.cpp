@@ -36,10 +36,10 @@ static void usage()
             "         per-base depth as a BED of runs of equal depth (contig, start, end, depth; no header); kind raw (default)\n"
             "         or qc (quality-filtered); SPEC such as 1:4:100 merges runs within the bands 0, 1-3, 4-99, 100+ (at most\n"
             "         64 edges; a leading 0: and a trailing : are accepted)\n"
-            "       [--targets BED --target-out FILE [--target-thresholds 1,10,20,30]]\n"
+            "       [--targets BED --target-out FILE [--target-thresholds 1,10,20,30] [--target-quantiles]]\n"
             "         per region of BED (0-based, half open; column 4 = name): length, mean raw / quality-filtered depth, callable\n"
             "         bases and the other states, positions at >= each threshold (at most 8); a `total` line last, in which\n"
-            "         overlapping regions count twice\n"
+            "         overlapping regions count twice; --target-quantiles adds minimum, quartiles and maximum of both depths\n"
             "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n"
             "       dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
@@ -690,7 +690,7 @@ int main(int argc, char **argv)
     std::string depth_bed, depth_bed_kind, quantize;
     bool has_kind = false, has_quantize = false;
     std::string targets_bed, target_out, target_thr;
-    bool has_target_thr = false;
+    bool has_target_thr = false, target_quantiles = false;
     // a whole non-negative number, or exit 2 with a message (before any device is opened)
     auto number = [](const char *flag, const char *v) -> unsigned long long {
         char *end = nullptr;
@@ -733,6 +733,7 @@ int main(int argc, char **argv)
         else if (a == "--targets") targets_bed = next();
         else if (a == "--target-out") target_out = next();
         else if (a == "--target-thresholds") { target_thr = next(); has_target_thr = true; }
+        else if (a == "--target-quantiles") target_quantiles = true;
         else if (a == "--device") devices.assign(1, atoi(next()));
         else if (a == "--devices") {
             // the contigs are dealt to these devices (HIP ordinals, comma separated; an ordinal may repeat)
@@ -773,6 +774,7 @@ int main(int argc, char **argv)
         }
     }
     if (!target_out.empty() && targets_bed.empty()) { fprintf(stderr, "error: '--target-out' needs '--targets <BED>'\n"); return 2; }
+    if (target_quantiles && targets_bed.empty()) { fprintf(stderr, "error: '--target-quantiles' needs '--targets <BED>'\n"); return 2; }
     if (has_target_thr && targets_bed.empty()) { fprintf(stderr, "error: '--target-thresholds' needs '--targets <BED>'\n"); return 2; }
     if (!targets_bed.empty() && target_out.empty()) { fprintf(stderr, "error: '--targets' needs '--target-out <FILE>'\n"); return 2; }
     uint32_t thresholds[CL_TARGET_MAX_THRESHOLDS] = {0}, n_thresholds = 0;
@@ -833,9 +835,9 @@ int main(int argc, char **argv)
     // the exit (DUT_CLI_TEARDOWN=1: given back piece by piece first, as a library caller's process would)
     const char *td = getenv("DUT_CLI_TEARDOWN");
     const unsigned flags = (td && *td == '1') ? 0u : DUT_FILES_LEAVE_TO_EXIT;
-    const int rc = dut_coverage_files_ex3(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
+    const int rc = dut_coverage_files_ex4(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
                                           contigs.empty() ? nullptr : contigs.data(), contigs.size(), devices.data(), devices.size(),
-                                          flags, &depth, &depth_bed_opt, &target_opt, err, sizeof(err));
+                                          flags, &depth, &depth_bed_opt, &target_opt, target_quantiles ? DUT_TARGETS_ORDER : 0u, err, sizeof(err));
     if (rc != CL_OK) { fprintf(stderr, "Error: Analysis error: %s\n", err); leave(1); }
     // every output file is written and closed: leave without the HIP runtime's exit handlers
     stamp("exit");

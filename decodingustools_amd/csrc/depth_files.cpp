@@ -1,4 +1,4 @@
-// depth_files.cpp -- dut_coverage_files_ex / _ex2 / _ex3 (include/dut_bam.h): the file-level coverage run that also takes
+// depth_files.cpp -- dut_coverage_files_ex / _ex2 / _ex3 / _ex4 (include/dut_bam.h): the file-level coverage run that also takes
 // every contig's depth profile (cl_contig_depth_profile), its per-base depth runs (cl_contig_depth_runs) and / or the
 // summaries of its targets (cl_contig_targets) while the contig is resident, and writes the distribution, window and
 // summary files, the depth BED and the per-target table of include/dut_coverage.h beside the BED.  The driver is
@@ -159,6 +159,8 @@ struct TargetRun {
     dut_target_total total{};
     std::mutex mu;
     std::map<size_t, std::vector<cl_target_stats>> taken;   // by selected-contig index (contigs with targets only)
+    bool order = false;                                  // DUT_TARGETS_ORDER: the ten columns of cl_contig_target_order too
+    std::map<size_t, std::vector<cl_target_order>> taken_order;
     std::string msg;
     ~TargetRun() { if (f) fclose(f); }
 };
@@ -194,8 +196,16 @@ int tg_resident(void *user, cl_ctx *ctx, size_t i, const char *name)
     const int rc = cl_contig_targets(ctx, s, e, n, r->thr.data(), (uint32_t)r->thr.size(), &st);
     if (rc != CL_OK) return rc;
     std::vector<cl_target_stats> copy(st, st + n);
+    std::vector<cl_target_order> ocopy;
+    if (r->order) {
+        const cl_target_order *ord = nullptr;
+        const int rc2 = cl_contig_target_order(ctx, s, e, n, &ord);
+        if (rc2 != CL_OK) return rc2;
+        ocopy.assign(ord, ord + n);
+    }
     std::lock_guard<std::mutex> g(r->mu);
     r->taken[i] = std::move(copy);
+    if (r->order) r->taken_order[i] = std::move(ocopy);
     return CL_OK;
 }
 
@@ -205,16 +215,23 @@ int tg_deliver(void *user, size_t i, const char *name)
     const auto cit = r->by_name.find(name);
     if (cit == r->by_name.end()) return CL_OK;
     std::vector<cl_target_stats> st;
+    std::vector<cl_target_order> ord;
     {
         std::lock_guard<std::mutex> g(r->mu);
         auto it = r->taken.find(i);
         if (it == r->taken.end()) return CL_ERR_INVALID;
         st = std::move(it->second);
         r->taken.erase(it);
+        if (r->order) {
+            auto ot = r->taken_order.find(i);
+            if (ot == r->taken_order.end() || ot->second.size() != st.size()) return CL_ERR_INVALID;
+            ord = std::move(ot->second);
+            r->taken_order.erase(ot);
+        }
     }
     const char *const *names = nullptr;
     dut_targets_get(r->tg.get(), cit->second, nullptr, nullptr, &names, nullptr);
-    const int rc = dut_targets_write(r->f, name, st.data(), names, st.size(), (uint32_t)r->thr.size(), &r->total);
+    const int rc = dut_targets_write_ex(r->f, name, st.data(), r->order ? ord.data() : nullptr, names, st.size(), (uint32_t)r->thr.size(), &r->total);
     if (rc != CL_OK) r->msg = "cannot write " + r->out_path + " (contig " + name + ")";
     return rc;
 }
@@ -222,7 +239,7 @@ int tg_deliver(void *user, size_t i, const char *name)
 int tg_finish(void *user)
 {
     TargetRun *r = static_cast<TargetRun *>(user);
-    int rc = dut_targets_write_total(r->f, &r->total, (uint32_t)r->thr.size());
+    int rc = dut_targets_write_total_ex(r->f, &r->total, (uint32_t)r->thr.size(), r->order ? 1 : 0);
     if (fclose(r->f) != 0) rc = CL_ERR_INVALID;
     r->f = nullptr;
     if (rc != CL_OK) r->msg = "cannot write " + r->out_path;
@@ -311,6 +328,17 @@ extern "C" int dut_coverage_files_ex3(const char *bam_path, const char *fasta_pa
                                       const int *devices, size_t n_devices, unsigned flags, const dut_depth_options *depth,
                                       const dut_depth_bed_options *bed, const dut_target_options *targets, char *err, size_t err_len)
 {
+    return dut_coverage_files_ex4(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, depth, bed, targets, 0u, err, err_len);
+}
+
+extern "C" int dut_coverage_files_ex4(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
+                                      const char *summary_html, const cl_options *opt, const char *const *contigs, size_t n_contigs,
+                                      const int *devices, size_t n_devices, unsigned flags, const dut_depth_options *depth,
+                                      const dut_depth_bed_options *bed, const dut_target_options *targets, unsigned target_flags,
+                                      char *err, size_t err_len)
+{
+    if (target_flags & ~DUT_TARGETS_ORDER) { set_err(err, err_len, "targets: unknown target flags"); return CL_ERR_INVALID; }
+    if ((target_flags & DUT_TARGETS_ORDER) && !(targets && targets->bed_path)) { set_err(err, err_len, "targets: the quantile columns (DUT_TARGETS_ORDER) need a BED of regions"); return CL_ERR_INVALID; }
     const bool any = depth && (depth->dist_path || depth->windows_path || depth->summary_path);
     const bool any_bed = bed && bed->path;
     const bool any_tg = targets && targets->bed_path;
@@ -328,6 +356,7 @@ extern "C" int dut_coverage_files_ex3(const char *bam_path, const char *fasta_pa
         if (any_tg) {
             // (the regions are read before any output is created: a malformed BED leaves nothing behind)
             trun.bed_path = targets->bed_path; trun.out_path = targets->out_path;
+            trun.order = (target_flags & DUT_TARGETS_ORDER) != 0u;
             trun.thr.assign(targets->thresholds, targets->thresholds + targets->n_thresholds);
             char e[512] = {0};
             trun.tg.reset(dut_targets_read(targets->bed_path, e, sizeof(e)));
@@ -348,7 +377,7 @@ extern "C" int dut_coverage_files_ex3(const char *bam_path, const char *fasta_pa
         }
         if (any_tg) {
             trun.f = fopen(targets->out_path, "wb");
-            if (!trun.f || dut_targets_write_header(trun.f, trun.thr.data(), (uint32_t)trun.thr.size()) != CL_OK) { set_err(err, err_len, ("cannot create " + trun.out_path).c_str()); return CL_ERR_INVALID; }
+            if (!trun.f || dut_targets_write_header_ex(trun.f, trun.thr.data(), (uint32_t)trun.thr.size(), trun.order ? 1 : 0) != CL_OK) { set_err(err, err_len, ("cannot create " + trun.out_path).c_str()); return CL_ERR_INVALID; }
         }
         Many many;
         if (any) many.hooks.push_back(dut::ContigHook{nullptr, on_resident, on_deliver, on_finish, &run});

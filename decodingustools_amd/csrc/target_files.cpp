@@ -1,5 +1,6 @@
 // target_files.cpp -- the host side of the per-target summaries (include/dut_coverage.h): the reader of a BED of regions,
-// the threshold list of `--target-thresholds`, and the table of cl_contig_targets' records.  Plain C++, no device.
+// the threshold list of `--target-thresholds`, and the table of cl_contig_targets' records, with the columns of
+// cl_contig_target_order's behind them when asked.  Plain C++, no device.
 #include "../../include/dut_coverage.h"
 
 #include <cerrno>
@@ -163,20 +164,27 @@ extern "C" int dut_thresholds_parse(const char *spec, uint32_t *thresholds, uint
 
 extern "C" int dut_targets_write_header(FILE *f, const uint32_t *thresholds, uint32_t n_thresholds)
 {
+    return dut_targets_write_header_ex(f, thresholds, n_thresholds, 0);
+}
+
+extern "C" int dut_targets_write_header_ex(FILE *f, const uint32_t *thresholds, uint32_t n_thresholds, int order_columns)
+{
     if (!f || n_thresholds > CL_TARGET_MAX_THRESHOLDS || (n_thresholds && !thresholds)) return CL_ERR_INVALID;
     bool ok = fputs("#contig\tstart\tend\tname\tlength\tmean_raw\tmean_qc\tcallable\tcallable_frac\tref_n\tno_coverage\tlow_coverage\t"
                     "excessive_coverage\tpoor_mapping_quality", f) >= 0;
     for (uint32_t k = 0; ok && k < n_thresholds; ++k) ok = fprintf(f, "\traw_ge_%" PRIu32, thresholds[k]) > 0;
     for (uint32_t k = 0; ok && k < n_thresholds; ++k) ok = fprintf(f, "\tqc_ge_%" PRIu32, thresholds[k]) > 0;
+    if (order_columns) ok = ok && fputs("\traw_min\traw_q1\traw_median\traw_q3\traw_max\tqc_min\tqc_q1\tqc_median\tqc_q3\tqc_max", f) >= 0;
     ok = ok && fputc('\n', f) != EOF;
     return ok ? CL_OK : CL_ERR_INVALID;
 }
 
 namespace {
 
-// the columns behind the name: the same for a target and for the total
+// the columns behind the name: the same for a target and for the total; with order_columns the ten order statistics
+// behind them (ord: a target of some length's raw[5], qc[5]; NULL: `NA`, quantiles do not add)
 bool write_figures(FILE *f, uint64_t len, uint64_t sum_raw, uint64_t sum_qc, const uint64_t state[6], const uint64_t *ge_raw,
-                   const uint64_t *ge_qc, uint32_t K)
+                   const uint64_t *ge_qc, uint32_t K, bool order_columns, const uint32_t *ord)
 {
     bool ok = fprintf(f, "\t%" PRIu64, len) > 0;
     if (len) ok = ok && fprintf(f, "\t%.4f\t%.4f", (double)sum_raw / (double)len, (double)sum_qc / (double)len) > 0;
@@ -188,6 +196,7 @@ bool write_figures(FILE *f, uint64_t len, uint64_t sum_raw, uint64_t sum_qc, con
                        state[CL_LOW_COVERAGE], state[CL_EXCESSIVE_COVERAGE], state[CL_POOR_MAPPING_QUALITY]) > 0;
     for (uint32_t k = 0; ok && k < K; ++k) ok = fprintf(f, "\t%" PRIu64, ge_raw[k]) > 0;
     for (uint32_t k = 0; ok && k < K; ++k) ok = fprintf(f, "\t%" PRIu64, ge_qc[k]) > 0;
+    for (int k = 0; ok && order_columns && k < 10; ++k) ok = ord ? fprintf(f, "\t%" PRIu32, ord[k]) > 0 : fputs("\tNA", f) >= 0;
     return ok && fputc('\n', f) != EOF;
 }
 
@@ -196,6 +205,12 @@ bool write_figures(FILE *f, uint64_t len, uint64_t sum_raw, uint64_t sum_qc, con
 extern "C" int dut_targets_write(FILE *f, const char *contig, const cl_target_stats *stats, const char *const *names, size_t n,
                                  uint32_t n_thresholds, dut_target_total *total)
 {
+    return dut_targets_write_ex(f, contig, stats, nullptr, names, n, n_thresholds, total);
+}
+
+extern "C" int dut_targets_write_ex(FILE *f, const char *contig, const cl_target_stats *stats, const cl_target_order *order,
+                                    const char *const *names, size_t n, uint32_t n_thresholds, dut_target_total *total)
+{
     if (!f || !contig || (n && !stats) || n_thresholds > CL_TARGET_MAX_THRESHOLDS) return CL_ERR_INVALID;
     for (size_t i = 0; i < n; ++i) {
         const cl_target_stats &s = stats[i];
@@ -203,7 +218,13 @@ extern "C" int dut_targets_write(FILE *f, const char *contig, const cl_target_st
         for (int j = 0; j < 6; ++j) st[j] = s.state[j];
         for (uint32_t k = 0; k < CL_TARGET_MAX_THRESHOLDS; ++k) { gr[k] = s.ge_raw[k]; gq[k] = s.ge_qc[k]; }
         if (fprintf(f, "%s\t%" PRIu32 "\t%" PRIu32 "\t%s", contig, s.start, s.end, names && names[i] ? names[i] : ".") <= 0) return CL_ERR_INVALID;
-        if (!write_figures(f, s.len, s.sum_raw, s.sum_qc, st, gr, gq, n_thresholds)) return CL_ERR_INVALID;
+        uint32_t ord[10];
+        if (order) {
+            // (both records are of the same target)
+            if (order[i].start != s.start || order[i].end != s.end) return CL_ERR_INVALID;
+            for (int k = 0; k < 5; ++k) { ord[k] = order[i].raw[k]; ord[5 + k] = order[i].qc[k]; }
+        }
+        if (!write_figures(f, s.len, s.sum_raw, s.sum_qc, st, gr, gq, n_thresholds, order != nullptr, order && s.len ? ord : nullptr)) return CL_ERR_INVALID;
         if (total) {
             total->n_targets += 1; total->len += s.len; total->sum_raw += s.sum_raw; total->sum_qc += s.sum_qc;
             for (int j = 0; j < 6; ++j) total->state[j] += st[j];
@@ -215,7 +236,12 @@ extern "C" int dut_targets_write(FILE *f, const char *contig, const cl_target_st
 
 extern "C" int dut_targets_write_total(FILE *f, const dut_target_total *t, uint32_t n_thresholds)
 {
+    return dut_targets_write_total_ex(f, t, n_thresholds, 0);
+}
+
+extern "C" int dut_targets_write_total_ex(FILE *f, const dut_target_total *t, uint32_t n_thresholds, int order_columns)
+{
     if (!f || !t || n_thresholds > CL_TARGET_MAX_THRESHOLDS) return CL_ERR_INVALID;
     if (fputs("total\t.\t.\t.", f) < 0) return CL_ERR_INVALID;
-    return write_figures(f, t->len, t->sum_raw, t->sum_qc, t->state, t->ge_raw, t->ge_qc, n_thresholds) ? CL_OK : CL_ERR_INVALID;
+    return write_figures(f, t->len, t->sum_raw, t->sum_qc, t->state, t->ge_raw, t->ge_qc, n_thresholds, order_columns != 0, nullptr) ? CL_OK : CL_ERR_INVALID;
 }

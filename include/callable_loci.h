@@ -287,6 +287,44 @@ cl_status cl_contig_targets(cl_ctx *ctx, const uint32_t *starts, const uint32_t 
  * on for that call. */
 cl_status cl_contig_targets_ms(cl_ctx *ctx, double *kernel_ms, double launch_ms[3]);
 
+/* ---- targets: minimum, quartiles and maximum of the depths per region ------------------------------------------- */
+/* What a per-target table shows beside the mean (Picard HsMetrics min_coverage / max_coverage, mosdepth --use-median,
+ * GATK DepthOfCoverage Q1 / median / Q3), and what the sums of cl_contig_targets cannot give.  Targets and clipping as
+ * there: e_i = min(end_i, extent), s_i = min(start_i, e_i), len = e_i - s_i.  For each kind (raw, qc), with d[p] the depth
+ * of that kind for p in [s_i, e_i), the five values are
+ *   [0], [4]   the smallest and the largest d[p]
+ *   [j]        j = 1, 2, 3 ([2] is the median): the smallest depth v with #{p : d[p] <= v} >= ceil(j * len / 4), i.e. the
+ *              element (j * len + 3) / 4 - 1 of the sorted depths -- the quartile rule of dut_depth_stats (dut_coverage.h):
+ *              for an even len the median is the lower middle value.  Whole numbers, exact.
+ * A target of length 0 has all ten values 0.  Targets come in any order, overlapping, nested or repeated; the records come
+ * in the order given; two calls return the same bytes (integer atomics only).  The host cuts the targets at the engine's
+ * windows of 2048 positions into pieces, at most CL_TARGET_ORDER_MAX_PIECES of them (8 bytes each on the host and the
+ * device); k_target_order (target_order.hip.h) rebuilds both depths per window and takes the extremes, the host reads one
+ * word -- the largest raw depth of any target, the only synchronisation before the result -- and one more pass over the
+ * windows follows per bit of it (about seven at 30x), each settling one bit of all six quartiles of every target.  No
+ * per-position array exists on the device or the host; only the records cross the link.  Taken only when asked:
+ * cl_contig_run enqueues what it always did.  Any number of calls per resident contig after cl_contig_run or
+ * cl_contig_finish, interleaved with cl_contig_targets, cl_contig_depth_profile, cl_contig_depth_runs and cl_contig_run;
+ * the call reads only the residents of the run, as cl_contig_depth_profile does, so the contig need not have been
+ * collected.  n_targets == 0 is valid (*out = NULL).  *out points at context-owned host memory, valid until the next
+ * cl_contig_target_order, cl_contig_begin or cl_destroy.
+ * CL_ERR_INVALID (with a message; the context stays usable): a null out; null starts / ends with n_targets > 0; a target
+ * with start > end (the message names it); n_targets > CL_TARGETS_MAX; no contig has been run; a context of the byte
+ * forms (DUT_QUAL_FORM=bytes); more than CL_TARGET_ORDER_MAX_PIECES pieces (the message gives the count and the limit;
+ * refused before anything is allocated or uploaded).  CL_ERR_DEVICE: a host-only debug context.  CL_ERR_INTERNAL: a
+ * device-side check of an uploaded index failed (nothing was read or stored out of range). */
+typedef struct cl_target_order {
+    uint32_t start, end, len;     /* clipped to the extent */
+    uint32_t raw[5], qc[5];       /* min, q1, median, q3, max */
+} cl_target_order;                /* 52 bytes */
+#define CL_TARGET_ORDER_MAX_PIECES (1u << 26)
+cl_status cl_contig_target_order(cl_ctx *ctx, const uint32_t *starts, const uint32_t *ends, size_t n_targets,
+                                 const cl_target_order **out);
+/* Measurement: all launches of the last cl_contig_target_order by device events, milliseconds (0 unless cl_set_profiling
+ * was on for that call), and, when n_rounds is not NULL, how many bit rounds it took: the bit length of the largest raw
+ * depth of any target. */
+cl_status cl_contig_target_order_ms(cl_ctx *ctx, double *kernel_ms, uint32_t *n_rounds);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 enum { CL_K_PREP = 0, CL_K_BOUNDS = 1, CL_K_PILEUP = 2, CL_K_RLE = 3, CL_K_COUNT = 4 };
 /* When on, every cl_contig_run brackets each kernel group with hipEvents on the stream. */

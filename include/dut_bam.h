@@ -174,6 +174,19 @@ int dut_coverage_files_ex3(const char *bam_path, const char *fasta_path, const c
                            unsigned flags, const dut_depth_options *depth, const dut_depth_bed_options *bed,
                            const dut_target_options *targets, char *err, size_t err_len);
 
+/* dut_coverage_files_ex3 with flags for the per-target table.  DUT_TARGETS_ORDER: every contig's targets also go through
+ * cl_contig_target_order while the contig is resident, and the table gets the ten columns raw_min ... qc_max behind the
+ * others (dut_targets_write_*_ex, dut_coverage.h).  BED, summaries and every other output are what they are without the
+ * flag; one device and several give the same bytes.  target_flags == 0: exactly dut_coverage_files_ex3.  The flag without
+ * targets (targets == NULL or no bed_path), or an unknown flag, is refused (CL_ERR_INVALID, message) before any file or
+ * device is touched. */
+#define DUT_TARGETS_ORDER 1u
+int dut_coverage_files_ex4(const char *bam_path, const char *fasta_path, const char *bed_path,
+                           const char *summary_json, const char *summary_html, const cl_options *opt,
+                           const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
+                           unsigned flags, const dut_depth_options *depth, const dut_depth_bed_options *bed,
+                           const dut_target_options *targets, unsigned target_flags, char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

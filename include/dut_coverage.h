@@ -228,6 +228,17 @@ int dut_targets_write_header(FILE *f, const uint32_t *thresholds, uint32_t n_thr
 int dut_targets_write(FILE *f, const char *contig, const cl_target_stats *stats, const char *const *names, size_t n,
                       uint32_t n_thresholds, dut_target_total *total);
 int dut_targets_write_total(FILE *f, const dut_target_total *total, uint32_t n_thresholds);
+/* The same table with the order statistics of cl_contig_target_order behind the existing columns, ten more:
+ *     raw_min raw_q1 raw_median raw_q3 raw_max qc_min qc_q1 qc_median qc_q3 qc_max
+ * whole numbers; `NA` for a target of length 0 and on the `total` line (quantiles do not add).  order_columns != 0 asks
+ * for the ten in the header and on the total line; dut_targets_write_ex writes them when `order` is not NULL: n records
+ * of the same targets as stats (CL_ERR_INVALID where a record's clipped start or end differs from its partner's).  With
+ * order_columns == 0 and order == NULL the three are the functions above, which forward here and write the bytes they
+ * always wrote. */
+int dut_targets_write_header_ex(FILE *f, const uint32_t *thresholds, uint32_t n_thresholds, int order_columns);
+int dut_targets_write_ex(FILE *f, const char *contig, const cl_target_stats *stats, const cl_target_order *order,
+                         const char *const *names, size_t n, uint32_t n_thresholds, dut_target_total *total);
+int dut_targets_write_total_ex(FILE *f, const dut_target_total *total, uint32_t n_thresholds, int order_columns);
 
 /* Debug names of CalledState (types.rs:36-43) */
 const char *dut_state_name(uint32_t state);
