@@ -77,7 +77,7 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     DevBuf<uint8_t> d_state;         // per-position states: allocated and written for debug dumps only
     DevBuf<uint16_t> d_runs;         // per window kT entries: run starts inside the window
     DevBuf<uint8_t> d_win_wide;      // per window: sticky "needs 16-bit counter fields" mark (k_pileup)
-    DevBuf<WinPartial> d_winpart;
+    DevBuf<uint4> d_winpart;           // the windows' totals: WinRecords (pass-bit form) or WinPartials (byte forms)
     DevBuf<uint32_t> d_errflag;        // [0] error bits raised by the kernels of a run, [1] unused
     DevBuf<uint2> d_runtab;            // run-table form: the windows' match pieces (host_build_runs)
     uint64_t n_runtab = 0;
@@ -779,7 +779,8 @@ template <class F> void each_extent_buffer(cl_ctx *c, size_t n_win, bool pass_bi
 {
     const size_t padded = n_win * kT;
     // (d_win_words: k_tail reads the words four at a time, so the array holds whole quads -- kernels.hip.h: quad_at)
-    f(c->d_win, n_win + 1); f(c->d_win_words, n_win + 4); f(c->d_winpart, n_win + 1);
+    // (d_winpart, in 16-byte words: a WinRecord per window in the pass-bit form, a WinPartial in the byte forms)
+    f(c->d_win, n_win + 1); f(c->d_win_words, n_win + 4); f(c->d_winpart, (n_win + 1) * ((pass_bits ? sizeof(WinRecord) : sizeof(WinPartial)) / sizeof(uint4)));
     f(c->d_runs, padded + 16); f(c->d_win_wide, n_win + 1);
     if (pass_bits) f(c->d_refn, padded / 32 + 4); else f(c->d_ref, padded + 16);
 }
@@ -935,8 +936,10 @@ cl_status launch_tail(cl_ctx *c, bool restart)
     // the summary's workgroups, in front of the grid: kTailSumWindows windows each, at most kTailMaxSum of them
     const uint32_t n_sum = std::min((c->n_win + kTailSumWindows - 1u) / kTailSumWindows, kTailMaxSum);
     const uint32_t wps = (c->n_win + n_sum - 1u) / n_sum;
-    hipLaunchKernelGGL((k_tail<(int)kT>), dim3(n_sum + (c->n_win + wpc - 1) / wpc), dim3(kTailBlock), 0, c->stream,
-                       c->d_runs.p, c->d_win_words.p, c->d_winpart.p, c->d_errflag.p, c->d_summary.p, c->n_win, c->extent, wpc,
+    // (the windows' totals: the records of k_pileup_rows in the pass-bit form, the WinPartials of k_pileup in the byte forms)
+    const auto kern = c->form == 3 ? k_tail<(int)kT, true> : k_tail<(int)kT, false>;
+    hipLaunchKernelGGL(kern, dim3(n_sum + (c->n_win + wpc - 1) / wpc), dim3(kTailBlock), 0, c->stream,
+                       c->d_runs.p, c->d_win_words.p, static_cast<const void *>(c->d_winpart.p), c->d_errflag.p, c->d_summary.p, c->n_win, c->extent, wpc,
                        n_sum, wps, c->d_iv.p, cap);
     return CL_OK;
 }
@@ -950,7 +953,7 @@ BytesArgs bytes_args(const cl_ctx *c, uint32_t *dbg_raw, uint32_t *dbg_qc, uint3
     return BytesArgs{
         Reads{c->d_pos.p, c->d_mapq.p, c->d_qual.p + kQualPad, c->n_reads}, c->dopt,
         c->d_rec.p, c->d_end.p, c->d_win.p, c->d_wide_idx.p, c->d_ref.p, c->d_lut.p, c->d_runtab.p,
-        c->d_state.p, c->d_runs.p, c->d_win_words.p, c->d_winpart.p,
+        c->d_state.p, c->d_runs.p, c->d_win_words.p, reinterpret_cast<WinPartial *>(c->d_winpart.p),
         reinterpret_cast<unsigned long long *>(c->d_summary.p), reinterpret_cast<const unsigned long long *>(c->d_sum0.p),
         c->extent, c->n_win, (c->n_win + 7) / 8, dbg_raw, dbg_qc, dbg_low,
         (c->n_reads && c->n_qual <= 128ull * c->n_reads) ? 2u : 3u,   // upl: by the mean read length
@@ -960,7 +963,7 @@ RowsArgs rows_args(const cl_ctx *c, uint32_t *dbg_raw, uint32_t *dbg_qc, uint32_
 {
     return RowsArgs{
         c->d_rows.p, c->d_heads.p, c->d_wide_idx.p, c->d_win.p, c->d_refn.p, c->d_lut8.p,
-        c->d_runs.p, c->d_win_words.p, c->d_winpart.p,
+        c->d_runs.p, c->d_win_words.p, reinterpret_cast<WinRecord *>(c->d_winpart.p),
         reinterpret_cast<unsigned long long *>(c->d_summary.p), reinterpret_cast<const unsigned long long *>(c->d_sum0.p),
         c->extent, c->n_win, (c->n_win + 7) / 8, c->opt.min_depth, c->opt.max_depth,
         c->opt.min_depth_for_low_mapq, c->d_lut.p, c->opt.max_low_mapq_fraction,

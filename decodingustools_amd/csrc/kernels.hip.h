@@ -38,7 +38,7 @@ constexpr int kQualPad = 32;         // bytes of padding in front of / behind th
 constexpr uint32_t kLutSize = 65536; // low-MAPQ threshold table entries (raw depth 0..65535)
 // (kLongOps, kWideSpan, kHeadSpanMax and the kErr* / kNeed* bits: engine_limits.h, shared with the host's tile walk)
 
-// per-window output of a pileup kernel (k_pileup_rows or k_pileup)
+// per-window output of k_pileup (the byte forms)
 struct WinPartial {
     unsigned long long cnt[6];       // state counts
     unsigned long long n_cov;        // positions with raw_depth > 0
@@ -49,6 +49,21 @@ struct WinPartial {
     uint32_t n_inner;                // run boundaries strictly inside the window
     uint32_t max_raw;
 };
+
+// per-window output of k_pileup_rows: the same totals as the wave's reductions leave them, 32 bytes that one lane stores
+// with two 16-byte stores.  A state count and n_cov are at most T = 2 048 (16-bit halves, no carry between them); the
+// pass-bit form has no sum_q / sum_reflen / sum_mapq_reflen of a window (the host's walk adds them up) and keeps n_inner
+// in the window's packed word alone (win_word below).  The tail unpacks (tail_summary_rows).
+struct __attribute__((aligned(16))) WinRecord {
+    uint32_t cnt01, cnt23, cnt45;    // state counts: cnt[2 k] | cnt[2 k + 1] << 16
+    uint32_t cov_qc;                 // n_cov | sum_qc << 12 with 8 counter planes (255 x 2 048 < 2^19), n_cov alone with more
+    uint32_t qc_lo, qc_hi;           // sum_qc with 16 or 32 planes (zero with 8): quality_bases = (cov_qc >> 12) + this
+    uint32_t max_raw;
+    uint32_t pad;
+};
+static_assert(sizeof(WinRecord) == 32 && alignof(WinRecord) == 16 && offsetof(WinRecord, cnt01) == 0 && offsetof(WinRecord, cnt23) == 4 &&
+              offsetof(WinRecord, cnt45) == 8 && offsetof(WinRecord, cov_qc) == 12 && offsetof(WinRecord, qc_lo) == 16 &&
+              offsetof(WinRecord, qc_hi) == 20 && offsetof(WinRecord, max_raw) == 24, "WinRecord as two 16-byte words");
 
 // mirrors cl_contig_summary (include/callable_loci.h) + engine-private tail
 struct DevSummary {
@@ -120,6 +135,18 @@ __device__ __forceinline__ uint32_t dpp_wave_max_u32(uint32_t v)
     t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); v = t > v ? t : v;
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
+// the same maximum as an inclusive scan: lane 63 holds the wave's, and may store it without a trip through an SGPR
+__device__ __forceinline__ uint32_t dpp_incl_max_u32(uint32_t v)
+{
+    uint32_t t;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false); v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false); v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false); v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false); v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false); v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false); v = t > v ? t : v;
+    return v;
+}
 // the sum over the wave, in every lane (lane 63 of the scan, read through an SGPR)
 __device__ __forceinline__ uint32_t dpp_wave_sum_u32(uint32_t v)
 {
@@ -161,7 +188,7 @@ struct __attribute__((aligned(32))) WinMeta {
 };
 
 // ---------------------------------------------------------------------------------------------
-// What the pileup leaves per window for the tail, beside the run list and the WinPartial: one packed word,
+// What the pileup leaves per window for the tail, beside the run list and the WinPartial or WinRecord: one packed word,
 //   n_inner | first_state << 16 | last_state << 24      (n_inner <= T - 1 = 2047; a state is 3 bits)
 // Everything the tail needs to place a window's intervals -- how many runs every window before it starts -- follows from
 // these words alone: c(v) = n_inner(v) + seam(v), seam(0) = 1, seam(v) = first(v) != last(v - 1).
@@ -219,6 +246,12 @@ constexpr uint32_t kTailMaxSum = 64;           // are no more than this many of 
 // word of the twelve is t mod 12 throughout: 768 = 64 x 12; coalesced), the 768 sums go through LDS to waves 0..11, a
 // word each, and 12 atomics per workgroup go to the summary -- a few hundred per contig.  Workgroup 0's thread 0 hands
 // err_flag[0] to the summary and clears the flags for the next run: it is their only reader behind the pileup.
+__device__ __forceinline__ void tail_flags(uint32_t *__restrict__ err_flag, DevSummary *__restrict__ summary)
+{
+    summary->err = err_flag[0];
+    // every kernel of the run is done with the flags: clear them for the next run (saves a memset launch)
+    err_flag[0] = 0; err_flag[1] = 0;
+}
 __device__ __forceinline__ void tail_summary(const WinPartial *__restrict__ winpart, uint32_t *__restrict__ err_flag,
                                              DevSummary *__restrict__ summary, uint32_t n_win, uint32_t wps)
 {
@@ -254,22 +287,70 @@ __device__ __forceinline__ void tail_summary(const WinPartial *__restrict__ winp
             if (lane == 0u && m) (void)__hip_atomic_fetch_max(sw + 12, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (blockIdx.x == 0u && tid == 0u) {
-        summary->err = err_flag[0];
-        // every kernel of the run is done with the flags: clear them for the next run (saves a memset launch)
-        err_flag[0] = 0; err_flag[1] = 0;
+    if (blockIdx.x == 0u && tid == 0u) tail_flags(err_flag, summary);
+}
+// The same for the records of k_pileup_rows (WinRecord above: 32 bytes a window, a third of the bytes).  Thread t takes the
+// windows t, t + 1024, ... of the workgroup's share, both 16-byte words of a record, and unpacks them into sums of its
+// own: a count is at most T a window and a thread has at most 32 windows (2^21 windows in kTailMaxSum workgroups of
+// 1 024 threads), so 32 bits hold a thread's, a wave's and the workgroup's count; sum_qc is kept in 64.  Then one DPP
+// reduction per total and wave, 16 values per total through LDS, and thread k adds total k to the summary: the same
+// words as tail_summary's (state_counts, n_covered_bases, quality_bases, max_raw_depth), again only where there is something to add.
+__device__ __forceinline__ void tail_summary_rows(const WinRecord *__restrict__ rec, uint32_t *__restrict__ err_flag,
+                                                  DevSummary *__restrict__ summary, uint32_t n_win, uint32_t wps)
+{
+    constexpr int kWaves = kTailBlock / 64, kTot = 9;      // cnt[6], n_cov, sum_qc, max_raw
+    __shared__ unsigned long long s_tot[kWaves][kTot];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t w0 = blockIdx.x * wps;
+    const uint32_t nw = w0 >= n_win ? 0u : (n_win - w0 < wps ? n_win - w0 : wps);
+    uint32_t f[7] = {0u, 0u, 0u, 0u, 0u, 0u, 0u}, mx = 0u;
+    unsigned long long qc = 0;
+    for (uint32_t i = tid; i < nw; i += (uint32_t)kTailBlock) {
+        const uint4 *r = reinterpret_cast<const uint4 *>(rec + w0 + i);
+        const uint4 x = r[0], y = r[1];
+        f[0] += x.x & 0xFFFFu; f[1] += x.x >> 16; f[2] += x.y & 0xFFFFu; f[3] += x.y >> 16; f[4] += x.z & 0xFFFFu; f[5] += x.z >> 16;
+        f[6] += x.w & 0xFFFu;
+        qc += (unsigned long long)(x.w >> 12) + ((unsigned long long)y.x | ((unsigned long long)y.y << 32));
+        mx = y.z > mx ? y.z : mx;
     }
+    unsigned long long t[kTot];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) t[k] = dpp_wave_sum_u32(f[k]);
+    t[7] = wave_sum_u64(qc);
+    t[8] = dpp_wave_max_u32(mx);
+    if (lane == 0u) {
+#pragma unroll
+        for (int k = 0; k < kTot; ++k) s_tot[wv][k] = t[k];
+    }
+    __syncthreads();
+    if (tid < (uint32_t)kTot) {
+        unsigned long long tot = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; ++k) { const unsigned long long v = s_tot[k][tid]; tot = tid == 8u ? (v > tot ? v : tot) : tot + v; }
+        unsigned long long *sw = reinterpret_cast<unsigned long long *>(summary);
+        // (state_counts[6] and n_covered_bases are words 0..6, quality_bases word 10, max_raw_depth word 12)
+        if (tot) {
+            if (tid == 8u) (void)__hip_atomic_fetch_max(sw + 12, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else (void)__hip_atomic_fetch_add(sw + (tid == 7u ? 10u : tid), tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (blockIdx.x == 0u && tid == 0u) tail_flags(err_flag, summary);
 }
 
 // (8 waves per SIMD, at most 64 vector registers: two workgroups per CU, so that the chunks of a chr21-sized contig --
 // 357 and the summary's 23 on 256 CUs -- are resident at once; at one workgroup per CU they ran in two rounds)
-template <int T>
+// RECORD: the windows' totals are the WinRecords of k_pileup_rows; else the WinPartials of k_pileup (launch_tail chooses).
+template <int T, bool RECORD>
 __global__ __launch_bounds__(kTailBlock, 8) void k_tail(const uint16_t *__restrict__ runs, const uint32_t *__restrict__ win_words,
-                                                      const WinPartial *__restrict__ winpart, uint32_t *__restrict__ err_flag,
+                                                      const void *__restrict__ winpart, uint32_t *__restrict__ err_flag,
                                                       DevSummary *__restrict__ summary, uint32_t n_win, uint32_t extent,
                                                       uint32_t wpc, uint32_t n_sum, uint32_t wps, Interval *__restrict__ iv, uint32_t iv_cap)
 {
-    if (blockIdx.x < n_sum) { tail_summary(winpart, err_flag, summary, n_win, wps); return; }
+    if (blockIdx.x < n_sum) {
+        if constexpr (RECORD) tail_summary_rows(static_cast<const WinRecord *>(winpart), err_flag, summary, n_win, wps);
+        else tail_summary(static_cast<const WinPartial *>(winpart), err_flag, summary, n_win, wps);
+        return;
+    }
     constexpr int kWaves = kTailBlock / 64;
     __shared__ uint32_t s_off[kTailMaxWpc];                // own chunk: runs before window i, relative to its owner thread's wave
     __shared__ uint32_t s_word[kTailMaxWpc + 1];           // own chunk: [i + 1] the word of window v0 + i, [0] that of v0 - 1

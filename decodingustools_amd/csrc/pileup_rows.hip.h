@@ -47,15 +47,21 @@ template <int T> __device__ __forceinline__ HeadCand head_cand(const uint32_t h,
 // equal-heights form, every segment wm.rn units (a window with a segment beyond 255 units, and DUT_ROWS_UNIFORM=1).
 // wm.rn is the largest height: the wave's loop bound.
 //
-// The units are read through a buffer descriptor of the WINDOW's own bytes, so that no lane can read outside them
-// whatever its offset, and a lane whose segment has no unit k asks for an offset beyond the descriptor: the load
-// returns zeros without touching memory.  That is straight code -- no branch around a load, every add waits for its
-// own load only -- and a segment lower than the window's highest simply adds zeros for the units beyond it.  A lane
-// gets the byte offset of its 16 bytes of unit g0 of its segment (g0: the first unit its wave takes) and how many
-// units the segment has from there on (n <= 0 for none).  Relative to g0, so that the k of an unrolled loop is a constant.
+// The units are read through a buffer descriptor of the WINDOW's own bytes, and a lane whose segment has no unit k asks
+// for an offset beyond the descriptor: the load returns zeros without touching memory.  That is straight code -- no
+// branch around a load, every add waits for its own load only -- and a segment lower than the window's highest simply
+// adds zeros for the units beyond it.  A lane gets the byte offset of its 16 bytes of unit g0 of its segment (g0: the
+// first unit its wave takes) and how many units the segment has from there on (n <= 0 for none).  Relative to g0, so
+// that the k of an unrolled loop is a constant: the load of unit g0 + k takes its k x 128 from the INSTRUCTION's
+// immediate offset (row_unit), and the lane's own part is one compare and one select, k < n ? off : kRowNoUnit, the
+// same constant for every k.  What keeps a lane inside its window's units:
+//   k < n    the select: off + 128 k is then unit g0 + k of the lane's own segment, which the window has (the heights
+//            are the window's own record, and the host has checked rlo + units against the resident rows);
+//   else     the descriptor: the immediate offset is part of the offset that the range check looks at (a SCALAR offset
+//            would not be), kRowNoUnit + 128 k is beyond every descriptor (num_records < 2^31) and does not wrap.
 // (The upload refuses a window whose units take 2^31 bytes or more, so offsets fit 32 bits: callable_loci.hip, size_for_extent.)
 typedef unsigned int RowWords __attribute__((ext_vector_type(4)));
-constexpr uint32_t kRowNoUnit = 0x80000000u;               // an offset no window's descriptor reaches (and + 16 k neither)
+constexpr uint32_t kRowNoUnit = 0x80000000u;               // an offset no window's descriptor reaches (and + 128 k neither: 128 k < 2^31)
 struct RowLane { __amdgpu_buffer_rsrc_t rs; uint32_t off; int32_t n; };
 __device__ __forceinline__ RowLane row_lane(const uint4 *rows, const WinMeta &wm, uint32_t lane, uint32_t g0)
 {
@@ -77,7 +83,11 @@ __device__ __forceinline__ RowLane row_lane(const uint4 *rows, const WinMeta &wm
 // the lane's 16 bytes of unit g0 + k of its segment, zeros where the segment has none; g0 on by `by` units
 __device__ __forceinline__ uint4 row_unit(const RowLane &rl, int k)
 {
-    const RowWords v = __builtin_amdgcn_raw_buffer_load_b128(rl.rs, (k < rl.n ? rl.off : kRowNoUnit) + (uint32_t)k * 128u, 0, 0);
+    uint32_t o = k < rl.n ? rl.off : kRowNoUnit;
+    // (opaque to the optimiser, so that the constant below stays one add behind the select -- which instruction selection
+    // folds into the load's immediate offset -- instead of being pushed into both of its arms: a v_add and a v_mov per load)
+    asm("" : "+v"(o));
+    const RowWords v = __builtin_amdgcn_raw_buffer_load_b128(rl.rs, o + (uint32_t)k * 128u, 0, 0);
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void row_advance(RowLane &rl, int by) { rl.off += (uint32_t)by * 128u; rl.n -= by; }
@@ -214,7 +224,7 @@ struct RowsArgs {
                                   // of its address only, so it is handed the packed word raw | low << 16 as it is
     uint16_t       *runs;
     uint32_t       *win_words;    // per window: n_inner | first state << 16 | last state << 24 (kernels.hip.h: win_word)
-    WinPartial     *winpart;
+    WinRecord      *winpart;      // per window: its totals, 32 bytes (kernels.hip.h)
     unsigned long long *summary;  // the contig summary as 16 words, and the start values of a run (callable_loci.hip: d_sum0):
     const unsigned long long *summary_start;   // the workgroup of window 0 copies them (kernels.hip.h: summary_start)
     uint32_t        extent, n_win, n_win8;
@@ -295,7 +305,19 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
     // Wide candidates are rare and come first: only a trip that has some (a scalar test) fetches them, index then head.
     const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<char *>(static_cast<const char *>(a.heads) + (size_t)lo * sizeof(Head)), 0, (int)((hi - lo) * (uint32_t)sizeof(Head)), 0x00020000);
+    // A trip of a window without wide candidates (a scalar test; every window of a short-read contig): slot v of the
+    // trip is head v of the descriptor, so the descriptor's own range check is the whole validity test.  The lane forms
+    // the byte offset of its first slot once, and slot u, 64 u heads on, takes its distance from the load's immediate
+    // offset (at most 7 x 64 x 8 bytes): no vector instruction per load.  Nothing wraps: base < n_cand < 2^28 here, so
+    // the offsets stay below 2^31 + 4 096, and every one at or beyond (hi - lo) x sizeof(Head) returns a zeroed head.
+    const bool plain_heads = wn == 0u && n_cand < (1u << 28);
     auto load_heads = [&](uint32_t base, Head (&hh)[U]) {
+        if (plain_heads) {
+            const uint32_t ob = (base + lane) * (uint32_t)sizeof(Head);
+#pragma unroll
+            for (int u = 0; u < U; ++u) hh[u] = head_fetch<HEAD4>(hrs, ob + (uint32_t)(u * kBlock) * (uint32_t)sizeof(Head));
+            return;
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const uint32_t o = base + (uint32_t)u * kBlock + lane - wn;      // (wraps for a wide slot: beyond hi - lo)
@@ -547,42 +569,37 @@ __global__ __launch_bounds__(kRowsBlock, rows_min_waves(DEBUG, DEEP, NP)) void k
     const uint32_t pv = lane > 0 ? below : state_at(0u);
     const uint32_t bnd = ((s0 ^ ((s0 << 1) | (pv & 1u))) | (s1 ^ ((s1 << 1) | ((pv >> 1) & 1u))) | (s2 ^ ((s2 << 1) | (pv >> 2)))) & okb;
     const uint32_t nb = __popc(bnd);
-    {
-        const uint32_t inc = dpp_incl_scan_u32(nb);
-        if (nb) {
-            uint16_t *dst = a.runs + (size_t)w * T + (inc - nb);
-            for (uint32_t m = bnd; m; m &= m - 1u) {         // (a lane has a boundary or two, rarely more)
-                const uint32_t j = (uint32_t)__ffs((int)m) - 1u;
-                *dst++ = (uint16_t)((lane * PER + j) | (state_at(j) << 12));
-            }
+    const uint32_t inc = dpp_incl_scan_u32(nb);            // (lane 63's: the window's n_inner)
+    if (nb) {
+        uint16_t *dst = a.runs + (size_t)w * T + (inc - nb);
+        for (uint32_t m = bnd; m; m &= m - 1u) {             // (a lane has a boundary or two, rarely more)
+            const uint32_t j = (uint32_t)__ffs((int)m) - 1u;
+            *dst++ = (uint16_t)((lane * PER + j) | (state_at(j) << 12));
         }
     }
-    // ---- the window's partial: twelve 8-byte words, lane k writes word k -- word k < 9 is total k (cnt[6], n_cov,
-    //      sum_qc, sum_q), words 9 and 10 are sum_reflen and sum_mapq_reflen (zero, as sum_q: the reads' separable sums
-    //      come from the host's walk), word 11 is {n_inner, max_raw}.  A lane's counts are <= 32 and the window's
-    //      <= 2048: packed words of two 16-bit fields, one wave reduction each; the totals are in scalar registers ----
-    static_assert(sizeof(WinPartial) == 96 && offsetof(WinPartial, sum_reflen) == 72 && offsetof(WinPartial, n_inner) == 88 &&
-                  offsetof(WinPartial, max_raw) == 92, "WinPartial as twelve 8-byte words");
+    // ---- the window's record (kernels.hip.h: WinRecord) and its packed word.  A lane's counts are <= 32 and the
+    //      window's <= 2048: packed words of two 16-bit fields, one inclusive scan each; with 8 planes the window's set
+    //      bits (<= 255 x 2048 < 2^19; a lane's <= 255 x 32) ride above the 12 bits of n_cov, so four scans and the
+    //      maximum are all.  The totals are LANE 63's scan values, so lane 63 stores them as they stand, and the packed
+    //      word with them -- n_inner is its `inc`, the last state its own, the first lane 0's: no total goes through a
+    //      scalar register and none is steered into a lane ----
     {
-        const uint32_t pk0 = dpp_wave_sum_u32(__popc(Nk) | (__popc(rC) << 16));
-        const uint32_t pk1 = dpp_wave_sum_u32(__popc(rNC) | (__popc(rLT) << 16));
-        const uint32_t pk2 = dpp_wave_sum_u32(__popc(rGT) | (__popc(rLow) << 16));
-        const uint32_t pk3 = dpp_wave_sum_u32(__popc(covk) | (nb << 16));
-        // the window's set bits: below 2^32 up to 16 planes (65 535 x 2048 < 2^27)
-        const unsigned long long qc = NP <= 16 ? (unsigned long long)dpp_wave_sum_u32((uint32_t)nbits) : wave_sum_u64(nbits);
-        mx = dpp_wave_max_u32(mx);
-        const uint32_t f[12] = {pk0 & 0xFFFFu, pk0 >> 16, pk1 & 0xFFFFu, pk1 >> 16, pk2 & 0xFFFFu, pk2 >> 16,
-                                pk3 & 0xFFFFu, (uint32_t)qc, 0u, 0u, 0u, pk3 >> 16};
-        if (lane < 12u) {
-            uint32_t vlo = 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < 12u; ++k) vlo = lane == k ? f[k] : vlo;
-            const uint32_t vhi = lane == 7u ? (uint32_t)(qc >> 32) : (lane == 11u ? mx : 0u);
-            reinterpret_cast<unsigned long long *>(a.winpart + w)[lane] = (unsigned long long)vlo | ((unsigned long long)vhi << 32);
+        const uint32_t t0 = dpp_incl_scan_u32(__popc(Nk) | (__popc(rC) << 16));
+        const uint32_t t1 = dpp_incl_scan_u32(__popc(rNC) | (__popc(rLT) << 16));
+        const uint32_t t2 = dpp_incl_scan_u32(__popc(rGT) | (__popc(rLow) << 16));
+        const uint32_t t3 = dpp_incl_scan_u32(__popc(covk) | (NP == 8 ? (uint32_t)nbits << 12 : 0u));
+        // (16 planes: the window's set bits are below 2^32, 65 535 x 2048 < 2^27; 32 planes: a 64-bit sum)
+        unsigned long long qc = 0;
+        if constexpr (NP == 16) qc = dpp_incl_scan_u32((uint32_t)nbits);
+        else if constexpr (NP > 16) qc = wave_sum_u64(nbits);
+        const uint32_t tm = dpp_incl_max_u32(mx);
+        const uint32_t first_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)state_at(0u));
+        if (lane == (uint32_t)kBlock - 1u) {
+            uint4 *rec = reinterpret_cast<uint4 *>(a.winpart + w);
+            rec[0] = make_uint4(t0, t1, t2, t3);
+            rec[1] = make_uint4((uint32_t)qc, (uint32_t)(qc >> 32), tm, 0u);
+            a.win_words[w] = win_word(inc, first_w, last_st);
         }
-        // the window's packed word for the tail: n_inner is wave-uniform, the first state is lane 0's, the last lane 63's
-        const uint32_t last_w = (uint32_t)__builtin_amdgcn_readlane((int)last_st, kBlock - 1);
-        if (lane == 0) a.win_words[w] = win_word(pk3 >> 16, state_at(0u), last_w);
     }
     if (w == 0u) summary_start(a.summary, a.summary_start, lane);   // (a scalar branch)
 }
