@@ -8,7 +8,8 @@ from .callable_loci import (CallableOptions, CalledState, CallableProfiler, Cont
                             ContigResult, ConsResult, DelResult, ErrorProfile, InsResult, LinkResult, StrResult, DepthAccumulator, DepthProfile, DepthRuns, Engine, EngineError, ScanResult,
                             admit_reads, compare_contig_names, depth_stats, genome_summary, process_single_contig,
                             quantize_parse, write_depth_bed, TargetStats, TargetOrder, parse_targets, thresholds_parse, write_target_stats)
-from .fingerprint import Fingerprint, FingerprintError, FingerprintResult, fingerprint_file  # noqa: F401
+from .fingerprint import (Fingerprint, FingerprintError, FingerprintResult, fingerprint_file,  # noqa: F401
+                          CompareResult, SketchFile, SketchSet, compare_files, compare_host, read_fingerprint_file)
 from .variants import (annotate_variants, error_profile, error_profile_measure, write_error_profile, cons_assemble, cons_classify_counts, consensus, del_classify_counts, del_events, del_fraction_parse, find_deletions,  # noqa: F401
                        find_insertions, find_strs, find_variants, ins_alleles, ins_classify_counts, scan_classify, scan_classify_counts, str_call, str_loci_parse, str_measure, str_units,
                        write_consensus, write_consensus_changes, write_deletions, write_insertions, write_strs, write_variants,
@@ -23,4 +24,5 @@ __all__ = ["ContigRecords", "CallableOptions", "CalledState", "CallableProfiler"
            "ins_classify_counts", "ConsResult", "consensus", "cons_assemble", "cons_classify_counts", "write_consensus",
            "write_consensus_changes", "StrResult", "find_strs", "str_measure", "str_call", "str_units", "str_loci_parse", "write_strs",
            "ErrorProfile", "error_profile", "error_profile_measure", "write_error_profile",
+           "CompareResult", "SketchFile", "SketchSet", "compare_files", "compare_host", "read_fingerprint_file",
            "LinkResult", "phase_sites", "link_measure", "link_pair_offsets", "link_summarise", "link_sites_parse", "write_links"]

@@ -106,6 +106,21 @@ class dut_fp_options(C.Structure):
                 ("has_max_frequency", C.c_int32)]
 
 
+class dut_fpc_record(C.Structure):
+    _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("n_common", C.c_uint64), ("sum_a", C.c_uint64),
+                ("sum_b", C.c_uint64), ("sum_min", C.c_uint64)]
+
+
+class dut_fpc_sketch(C.Structure):
+    _fields_ = [("ksize", C.c_uint32), ("scaled", C.c_uint64), ("n", C.c_uint64), ("hashes", C.c_void_p),
+                ("counts", C.c_void_p), ("region", C.c_char * 32), ("max_frequency", C.c_uint32),
+                ("has_max_frequency", C.c_int32), ("owner", C.c_void_p)]
+
+
+class dut_fpc_file_options(C.Structure):
+    _fields_ = [("query", C.c_char_p), ("min_jaccard", C.c_double), ("has_min_jaccard", C.c_int32)]
+
+
 class dut_fp_result(C.Structure):
     _fields_ = [("processed", C.c_uint64), ("n_distinct", C.c_uint64), ("n_entries", C.c_uint64),
                 ("hashes", C.c_void_p), ("counts", C.c_void_p), ("hexdigest", C.c_char * 65)]
@@ -643,6 +658,23 @@ SYMBOLS = [
     ("dut_fp_kmer_hashes_host_seq4", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("dut_fp_max_hash", C.c_uint64, [C.c_uint64]),
     ("dut_fp_sha256", None, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("dut_fpc_create", C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("dut_fpc_destroy", None, [C.c_void_p]),
+    ("dut_fpc_last_error", C.c_char_p, [C.c_void_p]),
+    ("dut_fpc_add", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]),
+    ("dut_fpc_compare", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    ("dut_fpc_compare_all", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    ("dut_fpc_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("dut_fpc_tile", C.c_uint32, []),
+    ("dut_fpc_compare_host", C.c_int, [C.POINTER(dut_fpc_sketch), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                       C.c_char_p, C.c_size_t]),
+    ("dut_fp_file_read", C.c_int, [C.c_char_p, C.POINTER(dut_fpc_sketch), C.c_char_p, C.c_size_t]),
+    ("dut_fp_file_free", None, [C.POINTER(dut_fpc_sketch)]),
+    ("dut_fpc_write", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_uint64, C.c_double, C.c_int]),
+    ("dut_fpc_write_matrix", C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("dut_fingerprint_compare_files", C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(dut_fpc_file_options), C.c_char_p,
+                                                C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]),
     ("dut_fastq_open", C.c_void_p, [C.c_char_p, C.c_char_p, C.c_size_t]),
     ("dut_fastq_next", C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_void_p)]),

@@ -14,7 +14,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libcallable_hip.so")
 SOURCES = [os.path.join(CSRC, "callable_loci.hip"), os.path.join(CSRC, "qual_pack.cpp"), os.path.join(CSRC, "host_coverage.cpp"),
            os.path.join(CSRC, "bam_io.cpp"), os.path.join(CSRC, "coverage_files.cpp"), os.path.join(CSRC, "report.cpp"),
-           os.path.join(CSRC, "haplogroup.cpp"), os.path.join(CSRC, "fingerprint.hip"), os.path.join(CSRC, "fastq_io.cpp"),
+           os.path.join(CSRC, "haplogroup.cpp"), os.path.join(CSRC, "fingerprint.hip"), os.path.join(CSRC, "fingerprint_compare.hip"), os.path.join(CSRC, "fastq_io.cpp"),
            os.path.join(CSRC, "depth_files.cpp"), os.path.join(CSRC, "target_files.cpp"), os.path.join(CSRC, "variants.cpp")]
 CLI = os.path.join(LIBDIR, "dut-coverage")
 CLI_SRC = os.path.join(CSRC, "coverage_main.cpp")
@@ -26,7 +26,7 @@ HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "pileup_bytes
            os.path.join(CSRC, "engine_base.hip.h"), os.path.join(CSRC, "site_engine.hip.h"),
            os.path.join(CSRC, "site_pass_bits.h"), os.path.join(CSRC, "site_str.hip.h"), os.path.join(CSRC, "str_walk.h"),
            os.path.join(CSRC, "site_links.hip.h"), os.path.join(CSRC, "link_walk.h"),
-           os.path.join(CSRC, "site_errors.hip.h"), os.path.join(CSRC, "ep_walk.h"),
+           os.path.join(CSRC, "site_errors.hip.h"), os.path.join(CSRC, "ep_walk.h"), os.path.join(CSRC, "fp_compare.h"),
            os.path.join(CSRC, "coverage_hook.h"),
            os.path.join(CSRC, "host_parallel.h"),
            os.path.join(CSRC, "qual_pack.h"), os.path.join(CSRC, "pass_rows.h"),

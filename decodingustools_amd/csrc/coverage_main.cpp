@@ -41,6 +41,7 @@ static void usage()
             "         bases and the other states, positions at >= each threshold (at most 8); a `total` line last, in which\n"
             "         overlapping regions count twice; --target-quantiles adds minimum, quartiles and maximum of both depths\n"
             "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n"
+            "       dut-coverage fingerprint-compare A.fp B.fp [C.fp ...] [--list FILE] -o out.tsv [--matrix FILE] [--query Q.fp] [--min-jaccard X] [--device 0]\n"
             "       dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
             "       [--min-quality 20] [--tree FILE [--provider ftdna|decodingus] [--tree-type y|mt]] [--device 0]\n"
             "       dut-coverage find-minor-alleles <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
@@ -130,6 +131,76 @@ static int fingerprint_main(int argc, char **argv)
     const int rc = dut_fp_files(input.c_str(), ref.empty() ? nullptr : ref.c_str(), out.empty() ? nullptr : out.c_str(), &opt,
                                 region.c_str(), device, digest, &processed, err, sizeof(err));
     if (digest[0]) printf("Processed %llu sequences\n%s\n", (unsigned long long)processed, digest);
+    if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
+    fflush(nullptr);
+    _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
+}
+
+// fingerprint-compare: the hash files `fingerprint -o` wrote, against each other (or --query against each of them) on the
+// device.  Argument errors are reported before any file is read or a device is opened.
+static int fingerprint_compare_main(int argc, char **argv)
+{
+    std::vector<std::string> files;
+    std::string out, matrix, query, list;
+    dut_fpc_file_options opt = {nullptr, 0.0, 0};
+    int device = 0;
+    auto usage_fc = []() {
+        fprintf(stderr,
+                "Usage: dut-coverage fingerprint-compare A.fp B.fp [C.fp ...] [--list FILE] -o out.tsv [--matrix FILE]\n"
+                "       [--query Q.fp] [--min-jaccard X] [--device 0]\n"
+                "  The files are what `fingerprint -o` writes.  Without --query: all pairs i < j; with it: Q against each other file.\n"
+                "  --list adds one path per line.  --matrix: the square Jaccard matrix (without --query only).\n"
+                "  --min-jaccard leaves out the lines below X (0..1).\n");
+    };
+    for (int i = 2; i < argc; ++i) {
+        std::string a = argv[i], val;
+        const size_t eq = a.find('=');
+        const bool has_eq = a.rfind("--", 0) == 0 && eq != std::string::npos;
+        if (has_eq) { val = a.substr(eq + 1); a = a.substr(0, eq); }
+        auto next = [&]() -> const char * {
+            if (has_eq) return val.c_str();
+            if (i + 1 >= argc) { usage_fc(); exit(2); }
+            return argv[++i];
+        };
+        if (a == "-o" || a == "--output") out = next();
+        else if (a == "--matrix") matrix = next();
+        else if (a == "--query") query = next();
+        else if (a == "--list") list = next();
+        else if (a == "--min-jaccard") {
+            const char *v = next();
+            char *end = nullptr;
+            errno = 0;
+            const double x = strtod(v, &end);
+            if (!*v || errno || *end || !(x >= 0.0 && x <= 1.0)) { fprintf(stderr, "error: invalid value '%s' for '--min-jaccard' (0..1)\n", v); return 2; }
+            opt.min_jaccard = x; opt.has_min_jaccard = 1;
+        }
+        else if (a == "--device") device = atoi(next());
+        else if (a == "-h" || a == "--help") { usage_fc(); return 0; }
+        else if (!a.empty() && a[0] != '-') files.push_back(a);
+        else { fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage_fc(); return 2; }
+    }
+    if (out.empty()) { fprintf(stderr, "error: fingerprint-compare needs '-o <FILE>'\n"); usage_fc(); return 2; }
+    if (!query.empty() && !matrix.empty()) { fprintf(stderr, "error: '--matrix' is written without '--query' only\n"); return 2; }
+    if (!list.empty()) {
+        FILE *f = fopen(list.c_str(), "rb");
+        if (!f) { fprintf(stderr, "Error: cannot open %s: %s\n", list.c_str(), strerror(errno)); return 1; }
+        std::string line;
+        for (int ch; (ch = fgetc(f)) != EOF || !line.empty();) {
+            if (ch != '\n' && ch != EOF) { line += (char)ch; continue; }
+            while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+            if (!line.empty()) files.push_back(line);
+            line.clear();
+            if (ch == EOF) break;
+        }
+        fclose(f);
+    }
+    if (files.size() + (query.empty() ? 0 : 1) < 2) { fprintf(stderr, "error: fingerprint-compare needs at least two sketches\n"); usage_fc(); return 2; }
+    std::vector<const char *> paths;
+    for (const std::string &p : files) paths.push_back(p.c_str());
+    if (!query.empty()) opt.query = query.c_str();
+    char err[1024] = {0};
+    const int rc = dut_fingerprint_compare_files(paths.data(), paths.size(), &opt, out.c_str(), matrix.empty() ? nullptr : matrix.c_str(),
+                                                 device, err, sizeof(err));
     if (rc != CL_OK) { fprintf(stderr, "Error: %s\n", err); fflush(nullptr); _exit(1); }
     fflush(nullptr);
     _exit(0);                              // outputs are closed; skip the HIP runtime's exit handlers (see main)
@@ -672,6 +743,7 @@ int main(int argc, char **argv)
     if (argc > 1 && !strcmp(argv[1], "find-y-branch")) return find_branch_main(argc, argv, DUT_TREE_YDNA);
     if (argc > 1 && !strcmp(argv[1], "find-mt-branch")) return find_branch_main(argc, argv, DUT_TREE_MTDNA);
     if (argc > 1 && !strcmp(argv[1], "fingerprint")) return fingerprint_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "fingerprint-compare")) return fingerprint_compare_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-variants")) return find_variants_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-minor-alleles")) return find_minor_main(argc, argv);
     if (argc > 1 && !strcmp(argv[1], "find-deletions")) return find_deletions_main(argc, argv);

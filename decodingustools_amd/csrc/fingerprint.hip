@@ -21,6 +21,7 @@
 
 #include "../../include/dut_bam.h"
 #include "../../include/dut_fingerprint.h"
+#include "fp_compare.h"
 #include "host_parallel.h"
 
 #include <algorithm>
@@ -181,14 +182,7 @@ FP_HD void strip_walk(const Src &src, uint64_t w0, uint32_t nwin, uint32_t k, ui
     }
 }
 
-inline uint64_t max_hash(uint64_t scaled)
-{
-    // ((u64::MAX as f64) / scaled as f64) as u64, with Rust's saturating cast (scaled 0 and 1: u64::MAX)
-    const double two64 = 18446744073709551616.0;
-    const double d = two64 / (double)scaled;
-    if (!(d < two64)) return ~0ull;
-    return (uint64_t)d;
-}
+inline uint64_t max_hash(uint64_t scaled) { return fpc::max_hash(scaled); }   // (fp_compare.h: the file reader checks against it too)
 
 // ---- SHA-256 (FIPS 180-4) ----
 struct Sha256 {
