@@ -125,6 +125,67 @@ def assert_wide_only_windows(rec, depths):
     return found
 
 
+# ---- more wide candidates in a window than a workgroup of the depth kernels has threads ----
+PILE_L = 60_000
+PILE_OPTIONS = dict(max_depth=1_000_000)           # admission drops nothing
+DEPTH_BLOCK = 128                                  # kDepthBlock: the stride of wd_scatter's loop over a window's candidates
+
+
+@functools.lru_cache(maxsize=None)
+def wide_pile(n_wide, n_deep=0):
+    """short reads at 12x; n_wide reads with a gap of 17,000 or 20,000 positions that start 5 positions apart from 0 on, of
+    every mapq (0 / 30 / 60) and base quality (10 / 30), so that raw, low-mapq and qc depth all differ; 20 reads with a gap
+    of 30,000 from window 3 on.  The first windows have more than 128 candidates from the wide list and the short reads
+    behind them: the candidate loop takes a second trip inside the wide part, and one trip straddles the two parts.
+    n_deep passing reads of 120 positions on 60 positions of window 1: beyond 252 of them a segment's stack of rows is
+    higher than 63 units, and the contig takes 16 counter planes."""
+    L = PILE_L
+    base = synth.short_read_contig(L, 12, 71)
+    extra = [(5 * i, "60M17000D40M" if i % 2 else "100M20000N100M", (0, 30, 60)[i % 3], (10, 30)[(i // 2) % 2], 0, f"w{i}")
+             for i in range(n_wide)]
+    extra += [(3 * T + 7 * i, "50M30000N50M", (60, 0, 30)[i % 3], 30, 0, f"x{i}") for i in range(20)]
+    extra += [(T + 1000 + i % 60, "120M", 60, 10 if i % 5 == 4 else 30, 0, f"d{i}") for i in range(n_deep)]
+    rec = merge(base, ContigRecords.from_reads(sorted(extra, key=lambda r: r[0])))
+    return _with_oracle(("chrP", 6, L, synth.make_reference(L, 72), rec), PILE_OPTIONS)
+
+
+def assert_wide_pile_windows(rec, depths):
+    """from the reads and the oracle alone: at least one window is overlapped by more spans above WIDE_SPAN than
+    DEPTH_BLOCK, short reads start inside that same window, and the three depths differ there"""
+    span = ref_spans(rec)
+    pos = rec.pos.astype(np.int64)
+    wide = span > WIDE_SPAN
+    w_pos, w_end = pos[wide], (pos + span)[wide]
+    s_pos = np.sort(pos[~wide & (span > 0)])
+    found = []
+    for w in range(-(-len(depths["raw"]) // T)):
+        lo, hi = w * T, (w + 1) * T
+        n_wide = int(((w_pos < hi) & (w_end > lo)).sum())
+        n_short = int(np.searchsorted(s_pos, hi) - np.searchsorted(s_pos, lo))
+        if n_wide > DEPTH_BLOCK and n_short > 0:
+            found.append(w)
+            raw, qc = depths["raw"][lo:hi], depths["qc"][lo:hi]
+            assert 0 < int(qc.max()) < int(raw.max()), w
+    assert found, "no window with more than %d wide candidates and short reads behind them" % DEPTH_BLOCK
+    return found
+
+
+# ---- one position deeper than the counter planes of 8 and of 16 bits hold ----
+DEEP_L = 7000
+DEEP_OPTIONS = dict(max_depth=1_000_000)
+
+
+@functools.lru_cache(maxsize=None)
+def deep_pile(depth):
+    """`depth` reads on 60 positions (of 120 bases; 300 of them: 16 counter planes) or on 4 (of 20 bases; 66,000: 32)"""
+    L = DEEP_L
+    rng = np.random.default_rng(depth)
+    reads = [[int(p), "120M" if depth < 1000 else "20M", int(rng.choice([10, 20, 60, 60])), int(rng.choice([10, 20, 40])), 0, f"d{i}"]
+             for i, p in enumerate(np.sort(rng.integers(2000, 2060 if depth < 1000 else 2004, depth)))]
+    rec = ContigRecords.from_reads([tuple(r) for r in reads])
+    return _with_oracle(("chrD", 3, L, synth.make_reference(L, 8), rec), DEEP_OPTIONS)
+
+
 # ---- past one window per workgroup of k_depth_runs: 65536 is its launch constant ----
 RUNS_GRID = 65536
 BIG_L = RUNS_GRID * T + 3 * T + 5                  # 65540 windows: workgroups 0..3 of k_depth_runs take a second one

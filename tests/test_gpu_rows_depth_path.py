@@ -14,6 +14,7 @@ import pytest
 
 import depth_contigs
 import depth_ref
+import order_ref
 import runs_ref
 import targets_ref
 from helpers import make_options, oracle_run
@@ -191,6 +192,7 @@ def _h_engine(which, heads8, head_span=None):
             out["runs"] = {(kind, bool(e)): eng.depth_runs(kind, e) for kind in ("raw", "qc") for e in (None, H_EDGES)}
             eng.contig_collect()                                   # (the dump ran the contig again)
             out["targets"] = eng.target_stats(*targets_ref.window_edge_targets(extent, H_TARGET_WINDOW), H_THR)
+            out["target_order"] = eng.target_order(*targets_ref.window_edge_targets(extent, H_TARGET_WINDOW))
     finally:
         for k, v in saved.items():
             os.environ.pop(k, None)
@@ -209,6 +211,18 @@ def _h_same_as_oracle(g, which):
     assert g["sums"] == {k: o["stats"][k] for k in SUMS}
     assert g["counts"] == o["state_counts"]
     assert g["bed"] == bed
+
+
+def _h_targets_same_as_oracle(g, which, what):
+    """k_target_depth and k_target_order rebuild the depths with the code of the profile and the runs: the five targets
+    around window H_TARGET_WINDOW against the references over the oracle's depths"""
+    ro, qo, _, so, eo = _h_oracle(which)[2]["dumps"]
+    raw, qc = depth_ref.pad(ro, g["extent"]), depth_ref.pad(qo, g["extent"])
+    state = targets_ref.oracle_state(so, eo, g["dumps"][3], g["extent"])
+    a, b = targets_ref.window_edge_targets(g["extent"], H_TARGET_WINDOW)
+    assert g["targets"].len.tolist() == g["target_order"].len.tolist() == [0, 12, 700, 150, 100]
+    targets_ref.same(g["targets"], targets_ref.target_stats(raw, qc, state, a, b, H_THR), what)
+    order_ref.same(g["target_order"], order_ref.target_order(raw, qc, a, b), what)
 
 
 def test_heads4_position_wrap_and_the_most_negative_offset():
@@ -230,6 +244,8 @@ def test_heads_stay_8_bytes_with_a_wide_read_or_a_cut_span():
     wide, wide8 = _h_engine("wide", False), _h_engine("wide", True)
     _h_same_as_oracle(wide, "wide")
     assert wide["bytes"] == wide8["bytes"] and wide["layout"]["upload_h2d_bytes"] == wide8["layout"]["upload_h2d_bytes"]
+    _h_targets_same_as_oracle(wide, "wide", "wide")
+    _h_targets_same_as_oracle(wide8, "wide", "wide, DUT_HEADS8")
     cut, cut8 = _h_engine("short", False, 37), _h_engine("short", True, 37)
     _h_same_as_oracle(cut, "short")
     assert cut["layout"]["n_records"] > 2 * _h_engine("short", True)["layout"]["n_records"]   # spans cut into heads of 37 positions
@@ -259,3 +275,4 @@ def test_depth_profile_and_depth_runs_in_both_head_forms(heads8):
         a, b = targets_ref.window_edge_targets(gt["extent"], H_TARGET_WINDOW)
         assert gt["targets"].len.tolist() == [0, 12, 700, 150, 100]
         targets_ref.same(gt["targets"], targets_ref.target_stats(depth["raw"], depth["qc"], state, a, b, H_THR), (heads8, gt is g))
+        _h_targets_same_as_oracle(gt, "short", (heads8, gt is g))

@@ -5,8 +5,8 @@ that segment is high, from where the heights of the segments in front of it put 
 Every case is a contig of at most 4 windows (T = 2048), run as the upload lays it out and once more with
 DUT_ROWS_UNIFORM=1 (every segment as high as the window's highest, the heights' word 0: the equal-heights decode), and
 held against the oracle per position (raw, low, qc, state: the DEBUG instantiation of k_pileup_rows), as BED text, state
-counts and sums (the production instantiation), and through k_depth_profile, k_depth_runs and k_target_depth, which read
-the same rows."""
+counts and sums (the production instantiation), and through k_depth_profile, k_depth_runs, k_target_depth and
+k_target_order, which read the same rows."""
 import functools
 import os
 import subprocess
@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import depth_ref
+import order_ref
 import runs_ref
 import targets_ref
 from helpers import make_options, oracle_run
@@ -142,6 +143,7 @@ def run_case(name, uniform):
             eng.contig_collect()                                   # (the dump ran the contig again)
             tg_a, tg_b = targets_ref.window_edge_targets(extent, 1)
             tg = eng.target_stats(tg_a, tg_b, THR)
+            tg_order = eng.target_order(tg_a, tg_b)
     finally:
         os.environ.pop("DUT_ROWS_UNIFORM", None)
         if saved is not None:
@@ -164,6 +166,8 @@ def run_case(name, uniform):
         assert np.array_equal(r.start, s) and np.array_equal(r.value, v), (kind, banded)
     assert tg.len.tolist() == [0, 12, 700, 150, 100]
     targets_ref.same(tg, targets_ref.target_stats(depth["raw"], depth["qc"], targets_ref.oracle_state(so, eo, dumps[3], extent), tg_a, tg_b, THR))
+    assert tg_order.len.tolist() == [0, 12, 700, 150, 100]
+    order_ref.same(tg_order, order_ref.target_order(depth["raw"], depth["qc"], tg_a, tg_b))
     return lay
 
 

@@ -136,15 +136,11 @@ def test_adversarial_contigs(L, deep, overhang, tmp_path):
 
 @pytest.mark.parametrize("depth,planes,rounds", [(300, 16, 9), (66_000, 32, 17)])
 def test_deep_piles_select_the_16_and_32_plane_kernels(depth, planes, rounds, tmp_path):
-    L = 7000
-    rng = np.random.default_rng(depth)
-    reads = [[int(p), "120M" if depth < 1000 else "20M", int(rng.choice([10, 20, 60, 60])), int(rng.choice([10, 20, 40])), 0, f"d{i}"]
-             for i, p in enumerate(np.sort(rng.integers(2000, 2060 if depth < 1000 else 2004, depth)))]
-    rec = ContigRecords.from_reads([tuple(r) for r in reads])
-    ref = synth.make_reference(L, 8)
-    check([("chrD", 3, L, ref, rec)], dict(max_depth=1_000_000), tmp_path)
-    with Engine(_opts(dict(max_depth=1_000_000)), 0) as eng:
-        eng.contig_begin(3, L, ref)
+    contig, o_res, _, _ = depth_contigs.deep_pile(depth)
+    _, tid, L, ref, rec = contig
+    check([contig], depth_contigs.DEEP_OPTIONS, tmp_path, o_res=o_res)
+    with Engine(_opts(depth_contigs.DEEP_OPTIONS), 0) as eng:
+        eng.contig_begin(tid, L, ref)
         eng.push_reads(rec.pos, rec.mapq, rec.cigar_off, rec.cigar, rec.qual_off, rec.qual)
         eng.contig_finish()
         assert eng.contig_layout()["counter_planes"] == planes

@@ -146,15 +146,11 @@ def test_adversarial_contigs(L, deep, overhang, tmp_path):
 
 @pytest.mark.parametrize("depth,planes", [(300, 16), (66_000, 32)])
 def test_deep_piles_select_the_16_and_32_plane_kernels(depth, planes, tmp_path):
-    L = 7000
-    rng = np.random.default_rng(depth)
-    reads = [[int(p), "120M" if depth < 1000 else "20M", int(rng.choice([10, 20, 60, 60])), int(rng.choice([10, 20, 40])), 0, f"d{i}"]
-             for i, p in enumerate(np.sort(rng.integers(2000, 2060 if depth < 1000 else 2004, depth)))]
-    rec = ContigRecords.from_reads([tuple(r) for r in reads])
-    ref = synth.make_reference(L, 8)
-    check([("chrD", 3, L, ref, rec)], dict(max_depth=1_000_000), tmp_path, thresholds=(DEFAULT_THR, (255, 256), (32767, 32768), (65_999, 66_000, 66_001)))
-    with Engine(_opts(dict(max_depth=1_000_000)), 0) as eng:
-        eng.contig_begin(3, L, ref)
+    contig, o_res, _, _ = depth_contigs.deep_pile(depth)
+    _, tid, L, ref, rec = contig
+    check([contig], depth_contigs.DEEP_OPTIONS, tmp_path, o_res=o_res, thresholds=(DEFAULT_THR, (255, 256), (32767, 32768), (65_999, 66_000, 66_001)))
+    with Engine(_opts(depth_contigs.DEEP_OPTIONS), 0) as eng:
+        eng.contig_begin(tid, L, ref)
         eng.push_reads(rec.pos, rec.mapq, rec.cigar_off, rec.cigar, rec.qual_off, rec.qual)
         eng.contig_finish()
         assert eng.contig_layout()["counter_planes"] == planes
