@@ -7,7 +7,8 @@ from .records import ContigRecords  # noqa: F401
 from .callable_loci import (CallableOptions, CalledState, CallableProfiler, ContigProfiler,  # noqa: F401
                             ContigResult, ConsResult, DelResult, ErrorProfile, InsResult, LinkResult, StrResult, DepthAccumulator, DepthProfile, DepthRuns, Engine, EngineError, ScanResult,
                             admit_reads, compare_contig_names, depth_stats, genome_summary, process_single_contig,
-                            quantize_parse, write_depth_bed, TargetStats, TargetOrder, parse_targets, thresholds_parse, write_target_stats)
+                            quantize_parse, write_depth_bed, TargetStats, TargetOrder, parse_targets, thresholds_parse, write_target_stats,
+                            GcBias, gc_bias_stats, write_gc_bias, write_gc_summary)
 from .fingerprint import (Fingerprint, FingerprintError, FingerprintResult, fingerprint_file,  # noqa: F401
                           CompareResult, SketchFile, SketchSet, compare_files, compare_host, read_fingerprint_file)
 from .variants import (annotate_variants, error_profile, error_profile_measure, write_error_profile, cons_assemble, cons_classify_counts, consensus, del_classify_counts, del_events, del_fraction_parse, find_deletions,  # noqa: F401
@@ -25,4 +26,5 @@ __all__ = ["ContigRecords", "CallableOptions", "CalledState", "CallableProfiler"
            "write_consensus_changes", "StrResult", "find_strs", "str_measure", "str_call", "str_units", "str_loci_parse", "write_strs",
            "ErrorProfile", "error_profile", "error_profile_measure", "write_error_profile",
            "CompareResult", "SketchFile", "SketchSet", "compare_files", "compare_host", "read_fingerprint_file",
-           "LinkResult", "phase_sites", "link_measure", "link_pair_offsets", "link_summarise", "link_sites_parse", "write_links"]
+           "LinkResult", "phase_sites", "link_measure", "link_pair_offsets", "link_summarise", "link_sites_parse", "write_links",
+           "GcBias", "gc_bias_stats", "write_gc_bias", "write_gc_summary"]

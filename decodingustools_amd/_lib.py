@@ -185,6 +185,28 @@ class dut_target_options(C.Structure):
     _fields_ = [("bed_path", C.c_char_p), ("out_path", C.c_char_p), ("thresholds", C.POINTER(C.c_uint32)), ("n_thresholds", C.c_uint32)]
 
 
+CL_GC_BINS = 101
+CL_GC_MAX_WINDOW = 1024
+
+
+class cl_gc_bias(C.Structure):
+    _fields_ = [("window", C.c_uint32), ("max_invalid", C.c_uint32), ("extent", C.c_uint32), ("pad_", C.c_uint32),
+                ("n_skipped", C.c_uint64), ("positions", C.c_uint64 * CL_GC_BINS), ("sum_raw", C.c_uint64 * CL_GC_BINS),
+                ("sum_qc", C.c_uint64 * CL_GC_BINS), ("zero_raw", C.c_uint64 * CL_GC_BINS)]
+
+
+class dut_gc_stats(C.Structure):
+    _fields_ = [("positions", C.c_uint64), ("sum_raw", C.c_uint64), ("sum_qc", C.c_uint64),
+                ("total_mean_raw", C.c_double), ("total_mean_qc", C.c_double),
+                ("at_dropout_raw", C.c_double), ("gc_dropout_raw", C.c_double), ("at_dropout_qc", C.c_double), ("gc_dropout_qc", C.c_double),
+                ("mean_raw", C.c_double * CL_GC_BINS), ("mean_qc", C.c_double * CL_GC_BINS), ("norm_raw", C.c_double * CL_GC_BINS),
+                ("norm_qc", C.c_double * CL_GC_BINS), ("zero_frac", C.c_double * CL_GC_BINS)]
+
+
+class dut_gc_options(C.Structure):
+    _fields_ = [("bias_path", C.c_char_p), ("summary_path", C.c_char_p), ("window", C.c_uint32), ("max_invalid", C.c_uint32)]
+
+
 class cl_scan_candidate(C.Structure):
     _fields_ = [("pos", C.c_uint32), ("ref", C.c_uint8), ("alt", C.c_uint8), ("pad", C.c_uint8 * 2),
                 ("a", C.c_uint32), ("c", C.c_uint32), ("g", C.c_uint32), ("t", C.c_uint32), ("depth", C.c_uint32)]
@@ -555,6 +577,19 @@ SYMBOLS = [
                                          C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
                                          C.c_uint, C.POINTER(dut_depth_options), C.POINTER(dut_depth_bed_options),
                                          C.POINTER(dut_target_options), C.c_uint, C.c_char_p, C.c_size_t]),
+    ("dut_coverage_files_ex5", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                         C.POINTER(cl_options), C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_int), C.c_size_t,
+                                         C.c_uint, C.POINTER(dut_depth_options), C.POINTER(dut_depth_bed_options),
+                                         C.POINTER(dut_target_options), C.c_uint, C.POINTER(dut_gc_options), C.c_char_p, C.c_size_t]),
+    ("cl_contig_gc_bias", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(cl_gc_bias)]),
+    ("cl_contig_gc_bias_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("cl_debug_gc_bits", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    ("dut_gc_bias_add", C.c_int, [C.POINTER(cl_gc_bias), C.POINTER(cl_gc_bias)]),
+    ("dut_gc_bias_stats", C.c_int, [C.POINTER(cl_gc_bias), C.POINTER(dut_gc_stats)]),
+    ("dut_gc_bias_write_header", C.c_int, [C.c_void_p]),
+    ("dut_gc_bias_write", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(cl_gc_bias)]),
+    ("dut_gc_summary_write_header", C.c_int, [C.c_void_p]),
+    ("dut_gc_summary_write", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(cl_gc_bias)]),
     ("cl_abi_version", C.c_int, []),
     ("cl_device_count", C.c_int, []),
     ("cl_create", C.c_int, [C.POINTER(cl_options), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -110,7 +110,8 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
                    output_summary: str = None, devices=None, depth_dist: str = None, depth_windows: str = None,
                    depth_summary: str = None, depth_cap: int = 1000, window: int = 0, depth_bed: str = None,
                    depth_bed_kind: str = "raw", quantize: str = None, targets: str = None, target_out: str = None,
-                   target_thresholds=None, target_quantiles: bool = False):
+                   target_thresholds=None, target_quantiles: bool = False, gc_bias: str = None, gc_summary: str = None,
+                   gc_window: int = None, gc_max_invalid: int = None):
     """CoverageAnalyzer::analyze on files (CoverageInput of api/coverage.rs:124-132); summary_json
     receives the CoverageOutput JSON of main.rs:68-69; output_summary, when given, the HTML report
     (api/coverage.rs:104; None: not written, the JSON then names "summary.html").  The per-contig coverage
@@ -123,7 +124,10 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
     depth_bed_kind "raw" or "qc"; quantize: band edges such as "1:4:100" (None or "": exact depth).
     targets: a BED of regions, target_out: the per-target table of dut_coverage_files_ex3 (include/dut_coverage.h has the
     format); target_thresholds: up to 8 ascending depths (default 1, 10, 20, 30); target_quantiles: the table also gets
-    minimum, quartiles and maximum of both depths per target (dut_coverage_files_ex4, DUT_TARGETS_ORDER)."""
+    minimum, quartiles and maximum of both depths per target (dut_coverage_files_ex4, DUT_TARGETS_ORDER).
+    gc_bias / gc_summary: the GC-bias table and summary of dut_coverage_files_ex5 (include/dut_coverage.h has the
+    formats), with a window of gc_window positions (default 100) around each position and at most gc_max_invalid
+    (default 4) invalid bases in it."""
     lib = _lib.load()
     options = options or CallableOptions()
     oc = options.to_c()
@@ -141,6 +145,40 @@ def coverage_files(bam_file: str, reference_file: str, output_bed: str = "callab
         raise EngineError(-1, "target_quantiles needs targets")
     if targets is not None and target_out is None:
         raise EngineError(-1, "targets needs target_out")
+    if gc_bias is None and gc_summary is None and (gc_window is not None or gc_max_invalid is not None):
+        raise EngineError(-1, "gc_window and gc_max_invalid need gc_bias or gc_summary")
+    if gc_bias is not None or gc_summary is not None:
+        gw, gk = int(100 if gc_window is None else gc_window), int(4 if gc_max_invalid is None else gc_max_invalid)
+        if not 1 <= gw <= _lib.CL_GC_MAX_WINDOW:
+            raise EngineError(-1, "gc_window outside [1, 1024]")
+        if not 0 <= gk < gw:
+            raise EngineError(-1, "gc_max_invalid is not below gc_window")
+        enc = lambda p: p.encode() if p else None          # noqa: E731
+        go = _lib.dut_gc_options(enc(gc_bias), enc(gc_summary), gw, gk)
+        to = bo = None
+        if targets is not None:
+            thr = [int(t) for t in ((1, 10, 20, 30) if target_thresholds is None else target_thresholds)]
+            if any(t < 0 or t > 0xFFFFFFFF for t in thr):
+                raise EngineError(-1, "target_thresholds outside [0, 2^32 - 1]")
+            ta = (C.c_uint32 * max(len(thr), 1))(*thr)
+            to = _lib.dut_target_options(targets.encode(), target_out.encode(), ta, len(thr))
+        if depth_bed:
+            from .callable_loci import quantize_parse
+            if depth_bed_kind not in _lib.CL_DEPTH_KINDS:
+                raise EngineError(-1, f"depth_bed_kind {depth_bed_kind!r}: raw or qc")
+            edges = quantize_parse(quantize)
+            ea = (C.c_uint32 * max(len(edges), 1))(*edges)
+            bo = _lib.dut_depth_bed_options(depth_bed.encode(), _lib.CL_DEPTH_KINDS[depth_bed_kind], ea, len(edges))
+        dlist = [int(d) for d in devices] if devices is not None else [int(device_id)]
+        dv = (C.c_int * len(dlist))(*dlist)
+        do = _lib.dut_depth_options(int(depth_cap) + 1, int(window), enc(depth_dist), enc(depth_windows), enc(depth_summary))
+        st = lib.dut_coverage_files_ex5(bam_file.encode(), reference_file.encode(), output_bed.encode(), enc(summary_json),
+                                        enc(output_summary), C.byref(oc), arr, n, dv, len(dlist), 0, C.byref(do),
+                                        C.byref(bo) if bo is not None else None, C.byref(to) if to is not None else None,
+                                        _lib.DUT_TARGETS_ORDER if target_quantiles else 0, C.byref(go), err, 1024)
+        if st != 0:
+            raise EngineError(st, err.value.decode())
+        return
     if targets is not None:
         thr = [int(t) for t in ((1, 10, 20, 30) if target_thresholds is None else target_thresholds)]
         if any(t < 0 or t > 0xFFFFFFFF for t in thr):

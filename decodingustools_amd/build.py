@@ -15,13 +15,13 @@ LIB = os.path.join(LIBDIR, "libcallable_hip.so")
 SOURCES = [os.path.join(CSRC, "callable_loci.hip"), os.path.join(CSRC, "qual_pack.cpp"), os.path.join(CSRC, "host_coverage.cpp"),
            os.path.join(CSRC, "bam_io.cpp"), os.path.join(CSRC, "coverage_files.cpp"), os.path.join(CSRC, "report.cpp"),
            os.path.join(CSRC, "haplogroup.cpp"), os.path.join(CSRC, "fingerprint.hip"), os.path.join(CSRC, "fingerprint_compare.hip"), os.path.join(CSRC, "fastq_io.cpp"),
-           os.path.join(CSRC, "depth_files.cpp"), os.path.join(CSRC, "target_files.cpp"), os.path.join(CSRC, "variants.cpp")]
+           os.path.join(CSRC, "depth_files.cpp"), os.path.join(CSRC, "target_files.cpp"), os.path.join(CSRC, "variants.cpp"), os.path.join(CSRC, "gc_files.cpp")]
 CLI = os.path.join(LIBDIR, "dut-coverage")
 CLI_SRC = os.path.join(CSRC, "coverage_main.cpp")
 HEADERS = [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "pileup_bytes.hip.h"), os.path.join(CSRC, "pileup_rows.hip.h"),
            os.path.join(CSRC, "window_depths.hip.h"),
            os.path.join(CSRC, "depth_profile.hip.h"), os.path.join(CSRC, "depth_runs.hip.h"), os.path.join(CSRC, "depth_targets.hip.h"),
-           os.path.join(CSRC, "target_order.hip.h"), os.path.join(CSRC, "target_pieces.h"),
+           os.path.join(CSRC, "target_order.hip.h"), os.path.join(CSRC, "gc_bias.hip.h"), os.path.join(CSRC, "gc_bits.h"), os.path.join(CSRC, "target_pieces.h"),
            os.path.join(CSRC, "site_scan.hip.h"),
            os.path.join(CSRC, "engine_base.hip.h"), os.path.join(CSRC, "site_engine.hip.h"),
            os.path.join(CSRC, "site_pass_bits.h"), os.path.join(CSRC, "site_str.hip.h"), os.path.join(CSRC, "str_walk.h"),

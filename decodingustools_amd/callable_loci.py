@@ -450,6 +450,25 @@ class Engine:
                             hist_qc=arr(p.hist_qc, int(p.n_bins)), win_raw=arr(p.win_raw, nw) if window else None,
                             win_qc=arr(p.win_qc, nw) if window else None, kernel_ms=float(ms.value))
 
+    def gc_bias(self, ref, window=100, max_invalid=4):
+        """Both depths of the resident contig by the GC content of `ref` (bytes, or a numpy uint8 array; None or empty:
+        every position is skipped) in a window of `window` positions centred on each position (cl_contig_gc_bias): a
+        GcBias of numpy uint64 arrays.  Positions with more than max_invalid invalid bases in their window are skipped.
+        Every call packs and uploads the reference's two bit planes again."""
+        if ref is None:
+            r = np.zeros(0, np.uint8)
+        elif isinstance(ref, (bytes, bytearray, memoryview)):
+            r = np.frombuffer(bytes(ref), np.uint8)
+        else:
+            r = np.ascontiguousarray(ref, dtype=np.uint8).reshape(-1)
+        if not (0 <= int(window) <= 0xFFFFFFFF and 0 <= int(max_invalid) <= 0xFFFFFFFF):
+            raise EngineError(-1, "gc_bias: window or max_invalid outside [0, 2^32 - 1]")
+        g = _lib.cl_gc_bias()
+        self._check(self._lib.cl_contig_gc_bias(self._h, _ptr(r) if r.size else None, int(r.size), int(window), int(max_invalid), C.byref(g)))
+        ms, up = C.c_double(), C.c_double()
+        self._check(self._lib.cl_contig_gc_bias_ms(self._h, C.byref(ms), C.byref(up)))
+        return GcBias._from_c(g, float(ms.value), float(up.value))
+
     def depth_runs(self, kind="raw", edges=None):
         """The per-position depth of the resident contig as runs of equal value, built on the device
         (cl_contig_depth_runs): a DepthRuns of numpy uint32 arrays (copies).  kind: "raw" or "qc" (or the ABI's 0 / 1);
@@ -721,6 +740,120 @@ class DepthProfile:
         p.hist_raw, p.hist_qc, p.win_raw, p.win_qc = [k.ctypes.data_as(u64p) if k is not None and k.size else u64p() for k in keep]
         # (an empty histogram still needs a pointer: n_bins >= 2 always; only the window tables may be empty)
         return p, keep
+
+
+@dataclass
+class GcBias:
+    """cl_gc_bias (include/callable_loci.h): per GC percentage b of the window around a position, positions[b] counted
+    positions, the sums of their raw and qc depth and zero_raw[b] of them without a read; n_skipped positions had more
+    than max_invalid invalid bases in their window.  Records add up (`+`, dut_gc_bias_add)."""
+    window: int
+    max_invalid: int
+    extent: int
+    n_skipped: int
+    positions: np.ndarray
+    sum_raw: np.ndarray
+    sum_qc: np.ndarray
+    zero_raw: np.ndarray
+    kernel_ms: float = 0.0          # cl_contig_gc_bias_ms: the kernel by device events while profiling is on
+    upload_ms: float = 0.0          # ... pack + upload of the reference's bit planes, by the host's clock
+
+    @classmethod
+    def _from_c(cls, g, kernel_ms=0.0, upload_ms=0.0):
+        def arr(a):
+            return np.ctypeslib.as_array(a).astype(np.uint64)
+        return cls(window=int(g.window), max_invalid=int(g.max_invalid), extent=int(g.extent), n_skipped=int(g.n_skipped),
+                   positions=arr(g.positions), sum_raw=arr(g.sum_raw), sum_qc=arr(g.sum_qc), zero_raw=arr(g.zero_raw),
+                   kernel_ms=kernel_ms, upload_ms=upload_ms)
+
+    @classmethod
+    def empty(cls):
+        """a zeroed record: the start of a sum (it takes the window and max_invalid of the first record added)"""
+        return cls._from_c(_lib.cl_gc_bias())
+
+    def _c(self):
+        g = _lib.cl_gc_bias()
+        g.window, g.max_invalid, g.extent, g.n_skipped = self.window, self.max_invalid, self.extent, self.n_skipped
+        for f in ("positions", "sum_raw", "sum_qc", "zero_raw"):
+            a = np.ascontiguousarray(getattr(self, f), np.uint64).reshape(-1)
+            if a.size != _lib.CL_GC_BINS:
+                raise EngineError(-1, f"GcBias.{f}: {_lib.CL_GC_BINS} bins")
+            getattr(g, f)[:] = [int(x) for x in a]
+        return g
+
+    def add(self, other):
+        """dut_gc_bias_add: the sum of both records (EngineError where window or max_invalid differ)"""
+        t, p = self._c(), other._c()
+        st = _lib.load().dut_gc_bias_add(C.byref(t), C.byref(p))
+        if st != 0:
+            raise EngineError(st, "dut_gc_bias_add: the records differ in window or max_invalid")
+        return GcBias._from_c(t)
+
+    __add__ = add
+
+    def tobytes(self):
+        return bytes(self._c())
+
+
+def gc_bias_stats(g: GcBias):
+    """dut_gc_bias_stats: the totals, the per-bin means, normalised means and zero fractions (numpy f64, NaN where not
+    available) and the four dropouts (None where not available) of a GcBias, as a dict."""
+    c = g._c()
+    out = _lib.dut_gc_stats()
+    st = _lib.load().dut_gc_bias_stats(C.byref(c), C.byref(out))
+    if st != 0:
+        raise EngineError(st, "dut_gc_bias_stats failed")
+
+    def arr(a):
+        v = np.ctypeslib.as_array(a).astype(np.float64)
+        v[v < 0] = np.nan
+        return v
+
+    def num(x):
+        return None if x < 0 else float(x)
+    return {"positions": int(out.positions), "sum_raw": int(out.sum_raw), "sum_qc": int(out.sum_qc),
+            "total_mean_raw": num(out.total_mean_raw), "total_mean_qc": num(out.total_mean_qc),
+            "at_dropout_raw": num(out.at_dropout_raw), "gc_dropout_raw": num(out.gc_dropout_raw),
+            "at_dropout_qc": num(out.at_dropout_qc), "gc_dropout_qc": num(out.gc_dropout_qc),
+            "mean_raw": arr(out.mean_raw), "mean_qc": arr(out.mean_qc), "norm_raw": arr(out.norm_raw), "norm_qc": arr(out.norm_qc),
+            "zero_frac": arr(out.zero_frac)}
+
+
+def _write_gc(path, contigs, header, line, total):
+    lib = _lib.load()
+    libc = C.CDLL(None)
+    libc.fopen.restype = C.c_void_p
+    libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    contigs = list(contigs)
+    f = libc.fopen(path.encode(), b"wb")
+    if not f:
+        raise OSError("cannot open " + path)
+    st = getattr(lib, header)(f)
+    acc = None
+    for name, g in contigs:
+        c = g._c()
+        if st == 0:
+            st = getattr(lib, line)(f, name.encode(), C.byref(c))
+        acc = g if acc is None else acc.add(g)
+    if st == 0 and total and acc is not None:
+        c = acc._c()
+        st = getattr(lib, line)(f, b"total", C.byref(c))
+    if libc.fclose(f) != 0 and st == 0:
+        st = -1
+    if st != 0:
+        raise EngineError(st, "cannot write " + path)
+
+
+def write_gc_bias(path, contigs, total=True):
+    """dut_gc_bias_write_header / dut_gc_bias_write: the bias table of include/dut_coverage.h.  contigs: (name, GcBias) in
+    output order; total: the sum of the records follows as `total`."""
+    _write_gc(path, contigs, "dut_gc_bias_write_header", "dut_gc_bias_write", total)
+
+
+def write_gc_summary(path, contigs, total=True):
+    """dut_gc_summary_write_header / dut_gc_summary_write: one summary line per (name, GcBias), then `total`."""
+    _write_gc(path, contigs, "dut_gc_summary_write_header", "dut_gc_summary_write", total)
 
 
 @dataclass

@@ -17,9 +17,11 @@
 #include "depth_runs.hip.h"
 #include "depth_targets.hip.h"
 #include "target_order.hip.h"
+#include "gc_bias.hip.h"
 #include "engine_base.hip.h"
 #include "site_engine.hip.h"
 #include "qual_pack.h"
+#include "gc_bits.h"
 #include "pass_rows.h"
 #include "tile_walk.h"
 #include "target_pieces.h"
@@ -120,6 +122,13 @@ struct cl_ctx : SiteCtx {              // (EngineBase, and the site engine's sta
     KernelTimer t_to[2];                  // the FIRST launch and its step; the rounds (recorded while profiling is on)
     double to_ms = 0.0;
     uint32_t to_rounds = 0;
+    // cl_contig_gc_bias: the reference's {gc, valid} pairs of a call (gc_bias.hip.h), what the kernel adds to, and that as
+    // copied back
+    DevBuf<uint4> d_gc_bits;
+    DevBuf<unsigned long long> d_gc_out;
+    unsigned long long h_gc_out[kGcOutWords] = {};
+    KernelTimer t_gc;                     // the last call's kernel (recorded while profiling is on)
+    double gc_upload_ms = 0.0;            // ... and its pack + upload, by the host's clock
     // The device buffers of the context, listed once: f(buffer) for each one that cl_layout_info.device_bytes counts, which
     // is all of them but d_prof and the site engine's (they never were).  cl_destroy and cl_contig_layout walk this list.
     template <class F> void each_buffer(F &&f)
@@ -992,6 +1001,8 @@ const DepthKernel<OrderArgs> kTargetOrderFirstKernels[3][2] = {{k_target_order<8
     {k_target_order<16, false, true>, k_target_order<16, true, true>}, {k_target_order<32, false, true>, k_target_order<32, true, true>}};
 const DepthKernel<OrderArgs> kTargetOrderRoundKernels[3][2] = {{k_target_order<8, false, false>, k_target_order<8, true, false>},
     {k_target_order<16, false, false>, k_target_order<16, true, false>}, {k_target_order<32, false, false>, k_target_order<32, true, false>}};
+const DepthKernel<GcArgs> kGcBiasKernels[3][2] = {{k_gc_bias<8, false>, k_gc_bias<8, true>},
+    {k_gc_bias<16, false>, k_gc_bias<16, true>}, {k_gc_bias<32, false>, k_gc_bias<32, true>}};
 // (only the raw depths come from the heads, and they need no plane; the qc depths are the rows' column sums)
 const DepthKernel<RunsArgs> kDepthRunsRawKernels[3][2] = {{k_depth_runs<8, false, false>, k_depth_runs<8, false, true>},
     {k_depth_runs<8, false, false>, k_depth_runs<8, false, true>}, {k_depth_runs<8, false, false>, k_depth_runs<8, false, true>}};
@@ -1167,6 +1178,7 @@ void cl_destroy(cl_ctx *c)
     tmr.lap("destroy: sync");
     c->each_buffer([](auto &buf) { buf.release(); });
     c->d_prof.release(); c->site.release(); c->h_dr_out.release();
+    c->d_gc_bits.release(); c->d_gc_out.release(); c->t_gc.destroy();
     c->d_tg_in.release(); c->d_tg_pre.release(); c->d_tg_out.release(); c->d_tg_win.release(); c->d_tg_off.release();
     c->d_to_in.release(); c->d_to_st.release(); c->d_to_out.release();
     c->t_prof.destroy(); c->t_dr_count.destroy(); c->t_dr_write.destroy();
@@ -1674,6 +1686,13 @@ cl_status cl_debug_ref_n_bits(const uint8_t *ref, uint64_t n_bases, uint64_t n_w
     return CL_OK;
 }
 
+cl_status cl_debug_gc_bits(const uint8_t *ref, uint64_t n_bases, uint64_t n_words, int level, uint64_t *gc_out, uint64_t *valid_out)
+{
+    if ((n_bases && !ref) || (n_words && (!gc_out || !valid_out)) || level < 0 || level > 2) return CL_ERR_INVALID;
+    dut::gc_bit_words(ref, n_bases, n_words, gc_out, valid_out, 1, level);
+    return CL_OK;
+}
+
 cl_status cl_debug_host_create(const cl_options *opt, cl_ctx **out)
 {
     if (!opt || !out) return CL_ERR_INVALID;
@@ -2025,6 +2044,77 @@ cl_status cl_contig_depth_profile(cl_ctx *c, uint32_t n_bins, uint32_t window, c
         out->hist_raw = h + 2; out->hist_qc = h + 2 + n_bins;
         out->win_raw = window ? h + 2 + 2 * (size_t)n_bins : nullptr;
         out->win_qc = window ? h + 2 + 2 * (size_t)n_bins + n_windows : nullptr;
+        return CL_OK;
+    });
+}
+
+// Both depths of the resident contig by the GC content around each position (include/callable_loci.h): the caller's
+// reference bytes become the two bit planes of gc_bits.h on their way through the staging ring, one launch of k_gc_bias
+// over them and the residents of the last run, 3.2 KB back.  Nothing of a run is touched: summary, intervals and
+// window partials stay.  The planes are packed and sent by every call; nothing is kept across calls.
+cl_status cl_contig_gc_bias_ms(cl_ctx *c, double *kernel_ms, double *upload_ms)
+{
+    if (!c || !kernel_ms) return CL_ERR_INVALID;
+    *kernel_ms = c->t_gc.ms;
+    if (upload_ms) *upload_ms = c->gc_upload_ms;
+    return CL_OK;
+}
+
+cl_status cl_contig_gc_bias(cl_ctx *c, const uint8_t *ref, uint64_t ref_len, uint32_t window, uint32_t max_invalid, cl_gc_bias *out)
+{
+    static_assert(CL_GC_BINS == kGcBins && CL_GC_MAX_WINDOW == 2 * kGcPad, "the kernel's bins and halo");
+    return guarded(c, [&]() -> cl_status {
+        if (!c) return CL_ERR_INVALID;
+        if (!out) return fail(c, CL_ERR_INVALID, "cl_contig_gc_bias: null result");
+        memset(out, 0, sizeof(*out));
+        const cl_status ready = depth_call_ready(c, "cl_contig_gc_bias", false, [&]() -> cl_status {
+            if (!ref && ref_len) return fail(c, CL_ERR_INVALID, "cl_contig_gc_bias: null reference with a length");
+            if (window < 1 || window > CL_GC_MAX_WINDOW) return fail(c, CL_ERR_INVALID, "cl_contig_gc_bias: window outside [1, 1024]");
+            if (max_invalid >= window) return fail(c, CL_ERR_INVALID, "cl_contig_gc_bias: max_invalid is not below the window");
+            return CL_OK;
+        }());
+        if (ready != CL_OK) return ready;
+        c->t_gc.ms = 0.0; c->gc_upload_ms = 0.0;
+        out->window = window; out->max_invalid = max_invalid; out->extent = c->extent;
+        if (c->n_win == 0) { HIP_TRY(c, hipStreamSynchronize(c->stream)); return CL_OK; }   // (no position: nothing is counted or skipped)
+        // ---- the planes: pair k is {gc, valid} of the positions [64 k - kGcPad, 64 k - kGcPad + 64); the pairs in front
+        // of position 0 and every base at or beyond ref_len are invalid; no base at or beyond the padded extent is read ----
+        const uint64_t padded = (uint64_t)c->n_win * kT;
+        const uint64_t n_pairs = (padded + 2 * kGcPad) / 64, front = kGcPad / 64;
+        const uint64_t nref = std::min<uint64_t>(ref_len, padded);
+        HIP_TRY(c, c->d_gc_bits.reserve(n_pairs));
+        HIP_TRY(c, c->d_gc_out.reserve(kGcOutWords));
+        drop_prefetch(c);                                  // (an unclaimed prefetch of this context holds the ring)
+        const double t0 = StageTimer::now();
+        cl_status rs = ring_start(c, reinterpret_cast<uint8_t *>(c->d_gc_bits.p), n_pairs * 16, [ref, nref, front](uint64_t off, uint64_t len, uint8_t *dst) {
+            // (a buffer of the ring is a whole number of pairs: 4 MB, and the transfer is n_pairs * 16 bytes)
+            uint64_t k = off / 16, n = len / 16;
+            uint64_t *w = reinterpret_cast<uint64_t *>(dst);
+            for (; n && k < front; ++k, --n, w += 2) w[0] = w[1] = 0ull;
+            if (!n) return;
+            const uint64_t p = (k - front) * 64;
+            dut::gc_bit_words(p < nref ? ref + p : nullptr, p < nref ? nref - p : 0, n, w, w + 1, 2, dut::gc_bits_level());
+        });
+        if (rs == CL_OK) rs = ring_finish(c); else (void)ring_finish(c);
+        if (rs != CL_OK) return rs;
+        c->gc_upload_ms = (StageTimer::now() - t0) * 1e3;
+        HIP_TRY(c, hipMemsetAsync(c->d_gc_out.p, 0, kGcOutWords * sizeof(unsigned long long), c->stream));
+        const GcArgs a{depth_residents(c), c->d_gc_bits.p, window, max_invalid, c->d_gc_out.p};
+        // workgroups that stay: the bins are flushed once per workgroup (gc_bias.hip.h has what their widths rest on)
+        const uint32_t grid = std::min<uint32_t>(c->n_win, 2048u);
+        if (c->profiling) HIP_TRY(c, c->t_gc.start(c->stream));
+        hipLaunchKernelGGL(depth_kernel(c, kGcBiasKernels), dim3(grid), dim3(kDepthBlock), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+        if (c->profiling) HIP_TRY(c, c->t_gc.stop(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_gc_out, c->d_gc_out.p, kGcOutWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->profiling) HIP_TRY(c, c->t_gc.read());
+        const unsigned long long *h = c->h_gc_out;
+        out->n_skipped = h[kGcBins];
+        for (int b = 0; b < kGcBins; ++b) {
+            out->positions[b] = h[b]; out->zero_raw[b] = h[kGcBins + 1 + b];
+            out->sum_raw[b] = h[2 * kGcBins + 1 + b]; out->sum_qc[b] = h[3 * kGcBins + 1 + b];
+        }
         return CL_OK;
     });
 }

@@ -182,6 +182,7 @@ int coverage_files(const char *bam_path, const char *fasta_path, const char *bed
             int rc = dut_process_single_contig_runs(ctx[d].get(), &r.st, opt, t, dut_bam_ref_len(b.get(), t), cur.bases, cur.blen, &cur.rec, r.counts, &r.iv, &r.n_iv);
             // (the contig is still resident: what else a caller wants of it is taken here, on the device's thread)
             if (rc == CL_OK && hook && hook->resident) rc = hook->resident(hook->user, ctx[d].get(), i, dut_bam_ref_name(b.get(), t));
+            if (rc == CL_OK && hook && hook->resident_ref) rc = hook->resident_ref(hook->user, ctx[d].get(), i, dut_bam_ref_name(b.get(), t), cur.bases, cur.blen);
             if (rc == CL_OK) rc = put(i, r);
             if (rc != CL_OK) {
                 const char *m = cl_last_error(ctx[d].get());

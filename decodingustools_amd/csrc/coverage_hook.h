@@ -19,6 +19,10 @@ struct ContigHook {
     // once, after the last contig of a run without error, before the summaries are written and the outputs are closed
     int (*finish)(void *user);
     void *user;
+    // as `resident` and right behind it, with the contig's reference bases as the driver holds them (ref_len may differ
+    // from the contig's length; null and 0 for a contig without bases).  May be null; the last member, so that a hook
+    // that lists the five above leaves it so.
+    int (*resident_ref)(void *user, cl_ctx *ctx, size_t i, const char *contig_name, const uint8_t *ref, uint64_t ref_len);
 };
 
 // dut_coverage_files_multi with a hook (null: exactly that call)

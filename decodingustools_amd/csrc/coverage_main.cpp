@@ -40,6 +40,11 @@ static void usage()
             "         per region of BED (0-based, half open; column 4 = name): length, mean raw / quality-filtered depth, callable\n"
             "         bases and the other states, positions at >= each threshold (at most 8); a `total` line last, in which\n"
             "         overlapping regions count twice; --target-quantiles adds minimum, quartiles and maximum of both depths\n"
+            "       [--gc-bias FILE] [--gc-summary FILE] [--gc-window 100] [--gc-max-n 4]\n"
+            "         depth by the GC content of the reference in a window of W positions (1..1024) centred on each position: per\n"
+            "         contig and in total a line per GC percentage (positions, mean and normalised depth, share without reads) and\n"
+            "         a summary line with the AT and GC dropout; positions with more than K invalid bases (N, IUPAC) in the\n"
+            "         window are skipped (K < W)\n"
             "       dut-coverage fingerprint <INPUT> [-r REF] [--ksize 31] [--scaled 1000] [--max-frequency N] [-o FILE] [-R full|chrY|chrM] [--device 0]\n"
             "       dut-coverage fingerprint-compare A.fp B.fp [C.fp ...] [--list FILE] -o out.tsv [--matrix FILE] [--query Q.fp] [--min-jaccard X] [--device 0]\n"
             "       dut-coverage find-variants <BAM_FILE> -r <REFERENCE_FILE> -o <TSV> -L <CONTIG> [--region START-END] [--min-depth 10]\n"
@@ -763,6 +768,9 @@ int main(int argc, char **argv)
     bool has_kind = false, has_quantize = false;
     std::string targets_bed, target_out, target_thr;
     bool has_target_thr = false, target_quantiles = false;
+    std::string gc_bias, gc_summary;
+    unsigned long long gc_window = 100, gc_max_n = 4;
+    bool has_gc_window = false, has_gc_max_n = false;
     // a whole non-negative number, or exit 2 with a message (before any device is opened)
     auto number = [](const char *flag, const char *v) -> unsigned long long {
         char *end = nullptr;
@@ -806,6 +814,10 @@ int main(int argc, char **argv)
         else if (a == "--target-out") target_out = next();
         else if (a == "--target-thresholds") { target_thr = next(); has_target_thr = true; }
         else if (a == "--target-quantiles") target_quantiles = true;
+        else if (a == "--gc-bias") gc_bias = next();
+        else if (a == "--gc-summary") gc_summary = next();
+        else if (a == "--gc-window") { gc_window = number("--gc-window", next()); has_gc_window = true; }
+        else if (a == "--gc-max-n") { gc_max_n = number("--gc-max-n", next()); has_gc_max_n = true; }
         else if (a == "--device") devices.assign(1, atoi(next()));
         else if (a == "--devices") {
             // the contigs are dealt to these devices (HIP ordinals, comma separated; an ordinal may repeat)
@@ -863,6 +875,11 @@ int main(int argc, char **argv)
     }
     const dut_target_options target_opt = {targets_bed.empty() ? nullptr : targets_bed.c_str(), target_out.empty() ? nullptr : target_out.c_str(),
                                            thresholds, n_thresholds};
+    // ... and the GC bias's
+    if ((has_gc_window || has_gc_max_n) && gc_bias.empty() && gc_summary.empty()) { fprintf(stderr, "error: '%s' needs '--gc-bias <FILE>' or '--gc-summary <FILE>'\n", has_gc_window ? "--gc-window" : "--gc-max-n"); return 2; }
+    if (gc_window < 1 || gc_window > CL_GC_MAX_WINDOW) { fprintf(stderr, "error: invalid value '%llu' for '--gc-window': 1..%d\n", gc_window, CL_GC_MAX_WINDOW); return 2; }
+    if (gc_max_n >= gc_window) { fprintf(stderr, "error: invalid value '%llu' for '--gc-max-n': below the window of %llu\n", gc_max_n, gc_window); return 2; }
+    const dut_gc_options gc_opt = {gc_bias.empty() ? nullptr : gc_bias.c_str(), gc_summary.empty() ? nullptr : gc_summary.c_str(), (uint32_t)gc_window, (uint32_t)gc_max_n};
     const dut_depth_bed_options depth_bed_opt = {depth_bed.empty() ? nullptr : depth_bed.c_str(),
                                                  depth_bed_kind == "qc" ? (uint32_t)CL_DEPTH_QC : (uint32_t)CL_DEPTH_RAW, edges, n_edges};
     if (devices.empty()) devices.push_back(0);
@@ -907,9 +924,9 @@ int main(int argc, char **argv)
     // the exit (DUT_CLI_TEARDOWN=1: given back piece by piece first, as a library caller's process would)
     const char *td = getenv("DUT_CLI_TEARDOWN");
     const unsigned flags = (td && *td == '1') ? 0u : DUT_FILES_LEAVE_TO_EXIT;
-    const int rc = dut_coverage_files_ex4(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
+    const int rc = dut_coverage_files_ex5(bam.c_str(), ref.c_str(), out.c_str(), "summary.json", summary.c_str(), &opt,
                                           contigs.empty() ? nullptr : contigs.data(), contigs.size(), devices.data(), devices.size(),
-                                          flags, &depth, &depth_bed_opt, &target_opt, target_quantiles ? DUT_TARGETS_ORDER : 0u, err, sizeof(err));
+                                          flags, &depth, &depth_bed_opt, &target_opt, target_quantiles ? DUT_TARGETS_ORDER : 0u, &gc_opt, err, sizeof(err));
     if (rc != CL_OK) { fprintf(stderr, "Error: Analysis error: %s\n", err); leave(1); }
     // every output file is written and closed: leave without the HIP runtime's exit handlers
     stamp("exit");

@@ -1,9 +1,10 @@
-// depth_files.cpp -- dut_coverage_files_ex / _ex2 / _ex3 / _ex4 (include/dut_bam.h): the file-level coverage run that also takes
+// depth_files.cpp -- dut_coverage_files_ex / _ex2 / _ex3 / _ex4 / _ex5 (include/dut_bam.h): the file-level coverage run that also takes
 // every contig's depth profile (cl_contig_depth_profile), its per-base depth runs (cl_contig_depth_runs) and / or the
 // summaries of its targets (cl_contig_targets) while the contig is resident, and writes the distribution, window and
 // summary files, the depth BED and the per-target table of include/dut_coverage.h beside the BED.  The driver is
 // coverage_files.cpp's; this file is its hook: three users (DepthRun, BedRun, TargetRun), as many of them as a run asks
-// for behind one hook that calls them in that order (Many).
+// for behind one hook that calls them in that order (Many).  A fourth user, GcRun, takes the contig's GC-bias record
+// (cl_contig_gc_bias) from the bases the driver holds and writes the bias table and summary.
 #include "coverage_hook.h"
 #include "../../include/dut_coverage.h"
 
@@ -246,6 +247,60 @@ int tg_finish(void *user)
     return rc;
 }
 
+// ---- GC bias: one contig's record on its way from its device's thread to the two files ----
+struct GcRun {
+    dut_gc_options o{};
+    FILE *fb = nullptr, *fs = nullptr;
+    cl_gc_bias total{};
+    std::mutex mu;
+    std::map<size_t, cl_gc_bias> taken;  // by selected-contig index
+    std::string msg;
+    ~GcRun() { if (fb) fclose(fb); if (fs) fclose(fs); }
+};
+
+int gc_resident(void *, cl_ctx *, size_t, const char *) { return CL_OK; }   // (the record wants the bases: gc_resident_ref)
+
+int gc_resident_ref(void *user, cl_ctx *ctx, size_t i, const char *, const uint8_t *ref, uint64_t ref_len)
+{
+    GcRun *r = static_cast<GcRun *>(user);
+    cl_gc_bias g;
+    const int rc = cl_contig_gc_bias(ctx, ref_len ? ref : nullptr, ref_len, r->o.window, r->o.max_invalid, &g);
+    if (rc != CL_OK) return rc;
+    std::lock_guard<std::mutex> lk(r->mu);
+    r->taken[i] = g;
+    return CL_OK;
+}
+
+int gc_deliver(void *user, size_t i, const char *name)
+{
+    GcRun *r = static_cast<GcRun *>(user);
+    cl_gc_bias g;
+    {
+        std::lock_guard<std::mutex> lk(r->mu);
+        auto it = r->taken.find(i);
+        if (it == r->taken.end()) return CL_ERR_INVALID;
+        g = it->second;
+        r->taken.erase(it);
+    }
+    int rc = dut_gc_bias_add(&r->total, &g);
+    if (rc == CL_OK && r->fb) rc = dut_gc_bias_write(r->fb, name, &g);
+    if (rc == CL_OK && r->fs) rc = dut_gc_summary_write(r->fs, name, &g);
+    if (rc != CL_OK) r->msg = std::string("cannot write the GC bias files (contig ") + name + ")";
+    return rc;
+}
+
+int gc_finish(void *user)
+{
+    GcRun *r = static_cast<GcRun *>(user);
+    // (no contig: the total still says which window it would have had)
+    if (r->total.window == 0) { r->total.window = r->o.window; r->total.max_invalid = r->o.max_invalid; }
+    int rc = CL_OK;
+    if (r->fb) { rc = dut_gc_bias_write(r->fb, "total", &r->total); if (fclose(r->fb) != 0) rc = CL_ERR_INVALID; r->fb = nullptr; }
+    if (r->fs) { const int r2 = dut_gc_summary_write(r->fs, "total", &r->total); if (rc == CL_OK) rc = r2; if (fclose(r->fs) != 0) rc = CL_ERR_INVALID; r->fs = nullptr; }
+    if (rc != CL_OK) r->msg = "cannot write the GC bias files";
+    return rc;
+}
+
 // several users behind one hook, called in the order of the list
 struct Many { std::vector<dut::ContigHook> hooks; };
 int many_header(void *user, const char *const *refs, size_t n_refs)
@@ -257,6 +312,12 @@ int many_header(void *user, const char *const *refs, size_t n_refs)
 int many_resident(void *user, cl_ctx *ctx, size_t i, const char *name)
 {
     for (const dut::ContigHook &h : static_cast<Many *>(user)->hooks) { const int rc = h.resident(h.user, ctx, i, name); if (rc != CL_OK) return rc; }
+    return CL_OK;
+}
+int many_resident_ref(void *user, cl_ctx *ctx, size_t i, const char *name, const uint8_t *ref, uint64_t ref_len)
+{
+    for (const dut::ContigHook &h : static_cast<Many *>(user)->hooks)
+        if (h.resident_ref) { const int rc = h.resident_ref(h.user, ctx, i, name, ref, ref_len); if (rc != CL_OK) return rc; }
     return CL_OK;
 }
 int many_deliver(void *user, size_t i, const char *name)
@@ -305,6 +366,15 @@ int check_target_options(const dut_target_options *o, char *err, size_t err_len)
     return CL_OK;
 }
 
+int check_gc_options(const dut_gc_options *o, char *err, size_t err_len)
+{
+    const char *m = nullptr;
+    if (o->window < 1 || o->window > CL_GC_MAX_WINDOW) m = "GC bias: the window must be 1 to 1024 positions";
+    else if (o->max_invalid >= o->window) m = "GC bias: the number of invalid bases allowed must be below the window";
+    if (m) { set_err(err, err_len, m); return CL_ERR_INVALID; }
+    return CL_OK;
+}
+
 } // namespace
 
 extern "C" int dut_coverage_files_ex(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
@@ -337,22 +407,34 @@ extern "C" int dut_coverage_files_ex4(const char *bam_path, const char *fasta_pa
                                       const dut_depth_bed_options *bed, const dut_target_options *targets, unsigned target_flags,
                                       char *err, size_t err_len)
 {
+    return dut_coverage_files_ex5(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, depth, bed, targets, target_flags, nullptr, err, err_len);
+}
+
+extern "C" int dut_coverage_files_ex5(const char *bam_path, const char *fasta_path, const char *bed_path, const char *summary_json,
+                                      const char *summary_html, const cl_options *opt, const char *const *contigs, size_t n_contigs,
+                                      const int *devices, size_t n_devices, unsigned flags, const dut_depth_options *depth,
+                                      const dut_depth_bed_options *bed, const dut_target_options *targets, unsigned target_flags,
+                                      const dut_gc_options *gc, char *err, size_t err_len)
+{
     if (target_flags & ~DUT_TARGETS_ORDER) { set_err(err, err_len, "targets: unknown target flags"); return CL_ERR_INVALID; }
     if ((target_flags & DUT_TARGETS_ORDER) && !(targets && targets->bed_path)) { set_err(err, err_len, "targets: the quantile columns (DUT_TARGETS_ORDER) need a BED of regions"); return CL_ERR_INVALID; }
     const bool any = depth && (depth->dist_path || depth->windows_path || depth->summary_path);
     const bool any_bed = bed && bed->path;
     const bool any_tg = targets && targets->bed_path;
-    if (!any && !any_bed && !any_tg)
+    const bool any_gc = gc && (gc->bias_path || gc->summary_path);
+    if (!any && !any_bed && !any_tg && !any_gc)
         return dut_coverage_files_multi(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len);
     if (any && check_options(depth, err, err_len) != CL_OK) return CL_ERR_INVALID;
     if (any_bed && check_bed_options(bed, err, err_len) != CL_OK) return CL_ERR_INVALID;
     // the byte forms have neither (cl_contig_depth_profile, cl_contig_depth_runs): said before anything is read
     if (any_tg && check_target_options(targets, err, err_len) != CL_OK) return CL_ERR_INVALID;
-    { const char *qf = getenv("DUT_QUAL_FORM"); if (qf && strcmp(qf, "bytes") == 0) { set_err(err, err_len, any ? "depth profile: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : any_bed ? "depth BED: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : "targets: pass-bit form only (DUT_QUAL_FORM=bytes is set)"); return CL_ERR_INVALID; } }
+    if (any_gc && check_gc_options(gc, err, err_len) != CL_OK) return CL_ERR_INVALID;
+    { const char *qf = getenv("DUT_QUAL_FORM"); if (qf && strcmp(qf, "bytes") == 0) { set_err(err, err_len, any ? "depth profile: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : any_bed ? "depth BED: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : any_tg ? "targets: pass-bit form only (DUT_QUAL_FORM=bytes is set)" : "GC bias: pass-bit form only (DUT_QUAL_FORM=bytes is set)"); return CL_ERR_INVALID; } }
     try {
         DepthRun run;
         BedRun brun;
         TargetRun trun;
+        GcRun grun;
         if (any_tg) {
             // (the regions are read before any output is created: a malformed BED leaves nothing behind)
             trun.bed_path = targets->bed_path; trun.out_path = targets->out_path;
@@ -379,16 +461,23 @@ extern "C" int dut_coverage_files_ex4(const char *bam_path, const char *fasta_pa
             trun.f = fopen(targets->out_path, "wb");
             if (!trun.f || dut_targets_write_header_ex(trun.f, trun.thr.data(), (uint32_t)trun.thr.size(), trun.order ? 1 : 0) != CL_OK) { set_err(err, err_len, ("cannot create " + trun.out_path).c_str()); return CL_ERR_INVALID; }
         }
+        if (any_gc) {
+            grun.o = *gc;
+            if (gc->bias_path && (!(grun.fb = fopen(gc->bias_path, "wb")) || dut_gc_bias_write_header(grun.fb) != CL_OK)) { set_err(err, err_len, (std::string("cannot create ") + gc->bias_path).c_str()); return CL_ERR_INVALID; }
+            if (gc->summary_path && (!(grun.fs = fopen(gc->summary_path, "wb")) || dut_gc_summary_write_header(grun.fs) != CL_OK)) { set_err(err, err_len, (std::string("cannot create ") + gc->summary_path).c_str()); return CL_ERR_INVALID; }
+        }
         Many many;
         if (any) many.hooks.push_back(dut::ContigHook{nullptr, on_resident, on_deliver, on_finish, &run});
         if (any_bed) many.hooks.push_back(dut::ContigHook{nullptr, bed_resident, bed_deliver, bed_finish, &brun});
         if (any_tg) many.hooks.push_back(dut::ContigHook{tg_header, tg_resident, tg_deliver, tg_finish, &trun});
-        const dut::ContigHook hook = {many_header, many_resident, many_deliver, many_finish, &many};
+        if (any_gc) many.hooks.push_back(dut::ContigHook{nullptr, gc_resident, gc_deliver, gc_finish, &grun, gc_resident_ref});
+        const dut::ContigHook hook = {many_header, many_resident, many_deliver, many_finish, &many, any_gc ? many_resident_ref : nullptr};
         const int rc = dut::coverage_files_hooked(bam_path, fasta_path, bed_path, summary_json, summary_html, opt, contigs, n_contigs, devices, n_devices, flags, err, err_len, &hook);
         // the failure was this file's: its own words
         if (rc != CL_OK && !run.msg.empty()) set_err(err, err_len, run.msg.c_str());
         else if (rc != CL_OK && !brun.msg.empty()) set_err(err, err_len, brun.msg.c_str());
         else if (rc != CL_OK && !trun.msg.empty()) set_err(err, err_len, trun.msg.c_str());
+        else if (rc != CL_OK && !grun.msg.empty()) set_err(err, err_len, grun.msg.c_str());
         return rc;
     } catch (...) { set_err(err, err_len, "out of memory or internal error"); return CL_ERR_NOMEM; }
 }

@@ -215,6 +215,39 @@ cl_status cl_contig_depth_profile(cl_ctx *ctx, uint32_t n_bins, uint32_t window,
  * was on for that call. */
 cl_status cl_contig_depth_profile_ms(cl_ctx *ctx, double *kernel_ms);
 
+/* ---- GC bias: depth of the resident contig by the GC content around each position -------------------------------- */
+/* What a WGS report shows right after the mean depth (Picard CollectGcBiasMetrics, the AT and GC dropout figures,
+ * deepTools computeGCBias), per position and with a centred window.  ref[0, ref_len) are reference bytes; a base is GC
+ * (one of G C g c), AT (one of A T a t) or invalid (every other byte: N, n, the IUPAC codes, S among them; and every
+ * position < 0 or >= ref_len).  For every position p of [0, extent), with the window [p - window / 2, p - window / 2 +
+ * window), g(p) its GC bases and v(p) its invalid bases:
+ *   v(p) > max_invalid   p is skipped (n_skipped)
+ *   otherwise            p is counted in bin b = 100 g(p) / (window - v(p)) (integer division, 0 <= b <= 100):
+ *                        positions[b] += 1, sum_raw[b] += raw[p], sum_qc[b] += qc[p], zero_raw[b] += (raw[p] == 0)
+ * with raw and qc the two depths of the depth profile above, so that sum positions + n_skipped == extent.  Every figure
+ * is a plain count: records of contigs, devices or ranks add up (dut_gc_bias_add, dut_coverage.h), and two calls return
+ * the same bytes.  ref_len may be smaller or larger than the extent; no base at or beyond the extent rounded up to 2048
+ * is read; ref == NULL with ref_len == 0 is valid (everything is skipped).  The reference crosses the link as two bits
+ * per position, packed on the host (gc_bits.h) and sent through the staging ring by EVERY call: nothing is cached across
+ * calls (a caller that wants several windows pays the upload for each).  Reduced on the device by one kernel
+ * (gc_bias.hip.h) -- no per-position array exists anywhere --, taken only when asked: cl_contig_run enqueues what it always
+ * did.  Any number of calls per resident contig, after cl_contig_run (or cl_contig_finish), collected or not, in any
+ * order with the other depth calls and cl_contig_run; the call waits for the stream and drops an unclaimed
+ * cl_contig_prefetch_qual of the context (it holds the ring).  `out` is the caller's.
+ * CL_ERR_INVALID: null out; null ref with ref_len > 0; window outside [1, CL_GC_MAX_WINDOW]; max_invalid >= window; no
+ * contig has been run; a context of the byte forms.  CL_ERR_DEVICE: a host-only debug context. */
+#define CL_GC_BINS 101
+#define CL_GC_MAX_WINDOW 1024
+typedef struct cl_gc_bias {
+    uint32_t window, max_invalid, extent, pad_;
+    uint64_t n_skipped;
+    uint64_t positions[CL_GC_BINS], sum_raw[CL_GC_BINS], sum_qc[CL_GC_BINS], zero_raw[CL_GC_BINS];
+} cl_gc_bias;
+cl_status cl_contig_gc_bias(cl_ctx *ctx, const uint8_t *ref, uint64_t ref_len, uint32_t window, uint32_t max_invalid, cl_gc_bias *out);
+/* Measurement: the kernel of the last cl_contig_gc_bias by device events (0 unless cl_set_profiling was on for that
+ * call) and its pack + upload by the host's clock, milliseconds.  upload_ms may be NULL. */
+cl_status cl_contig_gc_bias_ms(cl_ctx *ctx, double *kernel_ms, double *upload_ms);
+
 /* ---- per-base depth of the resident contig, run-length encoded ---------------------------- */
 /* What a coverage tool writes as its per-base and quantized depth BED: one run per stretch of equal value.  For the depth
  * kind of the call (CL_DEPTH_RAW: raw_depth, CL_DEPTH_QC: qc_depth of mod.rs:17-42, as above) every position p of
@@ -385,6 +418,10 @@ cl_status cl_debug_qual_pack(const uint8_t *qual, uint64_t n, uint8_t min_base_q
  * that is 'N' or 'n'; mod.rs:79-80: positions beyond the reference read as 'N'): bit i of word w <-> position 64 w + i,
  * n_words words for n_bases bases (levels as above). */
 cl_status cl_debug_ref_n_bits(const uint8_t *ref, uint64_t n_bases, uint64_t n_words, int level, uint64_t *words_out);
+/* Host only: the reference's two bit planes as cl_contig_gc_bias sends them (gc: the byte is one of G C g c; valid: one
+ * of A C G T a c g t; both 0 for every other byte and beyond the bases): bit i of word w <-> position 64 w + i, n_words
+ * words a plane for n_bases bases (levels as above). */
+cl_status cl_debug_gc_bits(const uint8_t *ref, uint64_t n_bases, uint64_t n_words, int level, uint64_t *gc_out, uint64_t *valid_out);
 /* A context WITHOUT a device, for the CPU test suite only: cl_contig_begin / cl_push_reads (pass-bit form) stage a
  * contig on the host exactly as a device context does, and cl_debug_pass_rows runs the upload's row builder over it.
  * Every call that needs a device fails with CL_ERR_DEVICE: there is no CPU pileup. */

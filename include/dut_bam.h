@@ -187,6 +187,28 @@ int dut_coverage_files_ex4(const char *bam_path, const char *fasta_path, const c
                            unsigned flags, const dut_depth_options *depth, const dut_depth_bed_options *bed,
                            const dut_target_options *targets, unsigned target_flags, char *err, size_t err_len);
 
+/* dut_coverage_files_ex4 that also takes every selected contig's GC-bias record (cl_contig_gc_bias, callable_loci.h)
+ * while the contig is resident, from the FASTA bases the run holds for it anyway -- one more upload of 2 bits a position
+ * and one more launch per contig --, and writes the bias table and / or the summary of dut_coverage.h: the contigs in the
+ * order of the BED output, then the sum of their records (dut_gc_bias_add) as `total`; one device and several give the
+ * same bytes.  Combines with every other option set in one run; BED, summaries and every other output are what they are
+ * without it.  gc == NULL or neither path: exactly dut_coverage_files_ex4.  Pass-bit form only.
+ *   bias_path, summary_path   either may be NULL
+ *   window                    1 to CL_GC_MAX_WINDOW positions (the command line's default: 100)
+ *   max_invalid               below window (the command line's default: 4)
+ * A window or max_invalid outside these is refused (CL_ERR_INVALID, message) before any file or device is touched. */
+typedef struct dut_gc_options {
+    const char *bias_path;
+    const char *summary_path;
+    uint32_t window, max_invalid;
+} dut_gc_options;
+int dut_coverage_files_ex5(const char *bam_path, const char *fasta_path, const char *bed_path,
+                           const char *summary_json, const char *summary_html, const cl_options *opt,
+                           const char *const *contigs, size_t n_contigs, const int *devices, size_t n_devices,
+                           unsigned flags, const dut_depth_options *depth, const dut_depth_bed_options *bed,
+                           const dut_target_options *targets, unsigned target_flags, const dut_gc_options *gc,
+                           char *err, size_t err_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,39 @@ int dut_targets_write_ex(FILE *f, const char *contig, const cl_target_stats *sta
                          const char *const *names, size_t n, uint32_t n_thresholds, dut_target_total *total);
 int dut_targets_write_total_ex(FILE *f, const dut_target_total *total, uint32_t n_thresholds, int order_columns);
 
+/* ---- GC bias: sums, statistics and text files of cl_contig_gc_bias' records (host code only) -----------------
+ * dut_gc_bias_add: total += part, bin by bin and n_skipped (plain counts: contigs, devices and ranks add up); extent
+ * is added too and saturates at 2^32 - 1.  A total whose window is 0 (a zeroed record) takes the part's window and
+ * max_invalid; otherwise CL_ERR_INVALID where they differ, the total unchanged.
+ * dut_gc_bias_stats, all in f64, each operand converted from its exact 64-bit integer first, sums taken in ascending
+ * bin order from 0.0:
+ *   P = sum positions, S_raw = sum sum_raw, S_qc = sum sum_qc                 (64-bit integers, exact)
+ *   mean_raw[b] = sum_raw[b] / positions[b], mean_qc[b] likewise, zero_frac[b] = zero_raw[b] / positions[b]
+ *   total_mean_raw = S_raw / P, total_mean_qc = S_qc / P
+ *   norm_raw[b] = mean_raw[b] / total_mean_raw, norm_qc[b] likewise
+ *   at_dropout_raw = 100 * (sum over b = 0..50 of max(0, positions[b] / P - sum_raw[b] / S_raw))
+ *   gc_dropout_raw the same over b = 51..100; both likewise for qc with sum_qc and S_qc      (Picard's AT_DROPOUT, GC_DROPOUT)
+ * A quotient whose denominator is 0, and whatever is computed from one, is "not available": DUT_GC_NA (every
+ * available figure is >= 0).
+ * The bias table (tab separated), one line per non-empty bin (positions[b] > 0) in ascending gc:
+ *     #contig gc positions mean_raw mean_qc norm_raw norm_qc zero_frac
+ * the means as %.4f, norm_* and zero_frac as %.6f, `NA` where not available.  The summary, one line per record:
+ *     #contig window max_invalid positions skipped mean_raw mean_qc at_dropout_raw gc_dropout_raw at_dropout_qc gc_dropout_qc
+ * positions = P, skipped = n_skipped, the means (total_mean_*) as %.4f, the dropouts as %.6f, `NA` where not available. */
+#define DUT_GC_NA (-1.0)
+typedef struct dut_gc_stats {
+    uint64_t positions, sum_raw, sum_qc;           /* P, S_raw, S_qc */
+    double total_mean_raw, total_mean_qc;
+    double at_dropout_raw, gc_dropout_raw, at_dropout_qc, gc_dropout_qc;
+    double mean_raw[CL_GC_BINS], mean_qc[CL_GC_BINS], norm_raw[CL_GC_BINS], norm_qc[CL_GC_BINS], zero_frac[CL_GC_BINS];
+} dut_gc_stats;
+int dut_gc_bias_add(cl_gc_bias *total, const cl_gc_bias *part);
+int dut_gc_bias_stats(const cl_gc_bias *g, dut_gc_stats *out);
+int dut_gc_bias_write_header(FILE *f);
+int dut_gc_bias_write(FILE *f, const char *contig, const cl_gc_bias *g);
+int dut_gc_summary_write_header(FILE *f);
+int dut_gc_summary_write(FILE *f, const char *contig, const cl_gc_bias *g);
+
 /* Debug names of CalledState (types.rs:36-43) */
 const char *dut_state_name(uint32_t state);
 
